@@ -9,7 +9,11 @@ of 22 050 Hz audio), fp32, synthetic weights (seed 1234), durations pinned to 3 
 N > 1: one process per GPU (torchrun), weights broadcast ONCE over RCCL/xGMI from rank 0, then each rank synthesises its
 own utterances with no data-path collective (weak scaling).
 
-Prints ONE JSON line (driver contract) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line (driver contract). A plain run sets up, warms up, times --steps steps and prints the headline (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`); `--dump-outputs DIR` then also writes the waveform of the last timed
+step as DIR/audio.npy (float32). Everything else the bench measures — prepare / end-to-end latencies, the request stream, the
+32-utterance batch, the `roofline` objects, the scale bench, batching and streaming side metrics, `cpu_baseline`, and on N > 1 the
+C-ABI communicator rehearsal — runs only with `--full` (`--no-cpu-baseline` / `--no-scale-bench` / `--no-profile` trim that).
 """
 import argparse
 import json
@@ -189,10 +193,19 @@ def main():
     ap.add_argument("--no-scale-bench", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--slots", type=int, default=8, help="utterances in flight for the batch-throughput side metric")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (latencies, request stream, batch32, roofline, scale bench, "
+                         "batching, streaming, CPU baseline); a plain run measures only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveform of the last timed step to DIR/audio.npy (float32; rank 0 only)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if not args.full:  # the side measurements below are --full only
+        args.no_cpu_baseline = args.no_scale_bench = args.no_profile = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torchrun: be the launcher (before anything in this process touches the GPU)
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -248,17 +261,20 @@ def main():
         # Every rank must take the SAME path through the collectives below: a rank that skipped one (librccl not loadable by the
         # library, id creation failed on rank 0) while the others entered it would hang the job, not report an error. So the ranks
         # first agree — MIN over ranks of "RCCL is usable through the C-ABI here" (rank 0's flag includes creating the id) — and
-        # the rehearsal runs on all ranks or on none.
+        # the rehearsal runs on all ranks or on none. It is a --full check (every rank parses the same argv, so all skip it together).
         uid, why = None, ""
-        try:
-            usable = 1 if ph.comm_available() else 0
-            if usable and rank == 0:
-                uid = ph.comm_unique_id()
-        except Exception as e:
-            usable, why = 0, repr(e)
-        flag = torch.tensor([usable], dtype=torch.int32, device="cuda")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        if int(flag.item()) == 1:
+        if args.full:
+            try:
+                usable = 1 if ph.comm_available() else 0
+                if usable and rank == 0:
+                    uid = ph.comm_unique_id()
+            except Exception as e:
+                usable, why = 0, repr(e)
+            flag = torch.tensor([usable], dtype=torch.int32, device="cuda")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        if not args.full:
+            comm_info = None
+        elif int(flag.item()) == 1:
             idt = torch.zeros(ph.COMM_ID_BYTES, dtype=torch.uint8, device="cuda")
             if rank == 0:
                 idt.copy_(torch.frombuffer(bytearray(uid), dtype=torch.uint8))
@@ -309,14 +325,16 @@ def main():
     first_request_ms = (time.perf_counter() - a) * 1e3
     cold_breakdown.update({k: v for k, v in rt.last_build_breakdown().items() if k in ("capture", "instantiate")})
     warm = []
-    for k in range(5):
-        i2 = ids[:len(ids) - k] if k else ids  # k ≠ 0: another true length inside the same (T, F) bucket
-        d2 = dur[:len(i2)]
-        a = time.perf_counter()
-        rt.prepare(0, i2, d2, noise[:, :sum(d2)], 0.667)
-        warm.append((time.perf_counter() - a) * 1e3)
+    if args.full:
+        for k in range(5):
+            i2 = ids[:len(ids) - k] if k else ids  # k ≠ 0: another true length inside the same (T, F) bucket
+            d2 = dur[:len(i2)]
+            a = time.perf_counter()
+            rt.prepare(0, i2, d2, noise[:, :sum(d2)], 0.667)
+            warm.append((time.perf_counter() - a) * 1e3)
     plan0 = rt.plan_info(0)
-    rt.prepare(0, ids, dur, noise, 0.667)
+    if args.full:
+        rt.prepare(0, ids, dur, noise, 0.667)
 
     out_buf = rt.pinned_empty(n_samples)  # page-locked destination (piper_hip_host_alloc): the D2H of the waveform is one DMA
 
@@ -330,7 +348,7 @@ def main():
     t0 = time.perf_counter()
     gpu_ms = []
     for _ in range(args.steps):
-        step()
+        audio = step()
         gpu_ms.append(rt.last_gpu_ms(0))
     barrier()
     elapsed = time.perf_counter() - t0
@@ -339,6 +357,9 @@ def main():
         elapsed = phd.max_over_ranks(elapsed, device="cuda")
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * args.steps * audio_sec / elapsed  # whole-job audio-seconds per wall-second
+    if args.dump_outputs and rank == 0:  # what a caller of the timed path receives: the waveform of the last timed step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "audio.npy"), np.array(audio, dtype=np.float32, copy=True))
 
     out = {
         "metric": "audio-sec/wall-sec (RTF^-1) with ms/utterance, Piper VITS en_GB-medium geometry, scale-bench factor",
@@ -364,45 +385,46 @@ def main():
         "prepare_ms_cold_breakdown": dict(cold_breakdown, note="first plan build of the process (it also creates the process's first HIP stream); capture + instantiate run "
                                           "AFTER the eager first launch has been enqueued, overlapping it"),
         "first_request_ms": round(first_request_ms, 3),
-        "prepare_ms_warm": round(float(np.median(warm)), 4),
         "plan": {"bucket_ids": plan0["bucket_t"], "bucket_frames": plan0["bucket_f"]},
     }
-    # end to end for one request on a cached plan: ids / durations / noise on the HOST → audio on the HOST
-    e2e = []
-    for _ in range(min(20, args.steps)):
-        a = time.perf_counter()
-        rt.prepare(0, ids, dur, noise, 0.667)
-        rt.launch(0)
-        rt.collect(0)
-        e2e.append((time.perf_counter() - a) * 1e3)
-    out["end_to_end_ms"] = round(float(np.median(e2e)), 4)
-    if cfg.dp_present:  # the same with the frames per id PREDICTED on the device (duration predictor + one D2H of T int32)
-        dpn = np.zeros((2, len(ids)), np.float32)
-        rt.prepare(1, ids, None, None, 0.667, noise_mode="device", dp_noise=dpn)
-        rt.launch(1); rt.collect(1)
-        e2p = []
+    if args.full:
+        out["prepare_ms_warm"] = round(float(np.median(warm)), 4)
+        # end to end for one request on a cached plan: ids / durations / noise on the HOST → audio on the HOST
+        e2e = []
         for _ in range(min(20, args.steps)):
             a = time.perf_counter()
+            rt.prepare(0, ids, dur, noise, 0.667)
+            rt.launch(0)
+            rt.collect(0)
+            e2e.append((time.perf_counter() - a) * 1e3)
+        out["end_to_end_ms"] = round(float(np.median(e2e)), 4)
+        if cfg.dp_present:  # the same with the frames per id PREDICTED on the device (duration predictor + one D2H of T int32)
+            dpn = np.zeros((2, len(ids)), np.float32)
             rt.prepare(1, ids, None, None, 0.667, noise_mode="device", dp_noise=dpn)
-            rt.launch(1)
-            au = rt.collect(1)
-            e2p.append((time.perf_counter() - a) * 1e3)
-        out["end_to_end_predicted_durations"] = {"ms": round(float(np.median(e2p)), 4), "samples": int(au.size),
-                                                 "note": "duration predictor + device RandomNormalLike; no host-supplied tensors but the ids"}
-        # the same without the host round trip between the predictor and the flow: the caller bounds the frames (here 3 per id, the
-        # plan the headline runs), generate_path runs on the device, the lengths come back with the waveform
-        bound = 3 * len(ids)
-        rt.prepare(1, ids, None, None, 0.667, noise_mode="device", dp_noise=dpn, max_frames=bound)
-        rt.launch(1); rt.collect(1)
-        e2b = []
-        for _ in range(min(20, args.steps)):
-            a = time.perf_counter()
+            rt.launch(1); rt.collect(1)
+            e2p = []
+            for _ in range(min(20, args.steps)):
+                a = time.perf_counter()
+                rt.prepare(1, ids, None, None, 0.667, noise_mode="device", dp_noise=dpn)
+                rt.launch(1)
+                au = rt.collect(1)
+                e2p.append((time.perf_counter() - a) * 1e3)
+            out["end_to_end_predicted_durations"] = {"ms": round(float(np.median(e2p)), 4), "samples": int(au.size),
+                                                     "note": "duration predictor + device RandomNormalLike; no host-supplied tensors but the ids"}
+            # the same without the host round trip between the predictor and the flow: the caller bounds the frames (here 3 per id, the
+            # plan the headline runs), generate_path runs on the device, the lengths come back with the waveform
+            bound = 3 * len(ids)
             rt.prepare(1, ids, None, None, 0.667, noise_mode="device", dp_noise=dpn, max_frames=bound)
-            rt.launch(1)
-            ab = rt.collect(1)
-            e2b.append((time.perf_counter() - a) * 1e3)
-        out["end_to_end_predicted_durations"]["bounded"] = {"ms": round(float(np.median(e2b)), 4), "samples": int(ab.size), "max_frames": bound,
-            "note": "piper_hip_voice_prepare_batch_bounded: one stream, no synchronisation before collect; plan = bucket(max_frames)"}
+            rt.launch(1); rt.collect(1)
+            e2b = []
+            for _ in range(min(20, args.steps)):
+                a = time.perf_counter()
+                rt.prepare(1, ids, None, None, 0.667, noise_mode="device", dp_noise=dpn, max_frames=bound)
+                rt.launch(1)
+                ab = rt.collect(1)
+                e2b.append((time.perf_counter() - a) * 1e3)
+            out["end_to_end_predicted_durations"]["bounded"] = {"ms": round(float(np.median(e2b)), 4), "samples": int(ab.size), "max_frames": bound,
+                "note": "piper_hip_voice_prepare_batch_bounded: one stream, no synchronisation before collect; plan = bucket(max_frames)"}
     # ---- a server's view: 200 requests of mixed length, one after the other on one slot id — ids, durations and noise
     # on the HOST → audio on the HOST. Lengths are seeded draws (14 … 400 ids, 1 … 5 frames per id), so requests land in many (T, F)
     # buckets: a bucket's first request builds its plan (schedule + arena, ≈ 0.5 ms) and runs eagerly, later ones replay the graph.

@@ -596,6 +596,35 @@ def test_cli_scale_bench_and_one_shot(rt_medium, tmp_path):
         assert np.array_equal(np.frombuffer(w.readframes(ref.size), "<i2"), ref)
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_waveform(rt_medium, tmp_path):
+    """A plain `bench.py` run (no --full) prints only the headline, times exactly --steps steps, and --dump-outputs writes the
+    waveform of the last timed step: the same samples this library returns for the bench's seeded utterance."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["higher_is_better"] is True
+    assert j["unit"] == "audio-sec/wall-sec" and j["dtype"] == "f32" and j["metric"].startswith("audio-sec/wall-sec")
+    assert abs(j["value"] - j["config"]["samples"] / 22050 / (j["ms_per_step"] * 1e-3)) <= 1e-2 * j["value"]
+    for side in ("roofline", "cpu_baseline", "scale_bench", "request_stream", "batch32", "end_to_end_ms", "streaming"):
+        assert side not in j, side  # --full only
+    audio = np.load(dump / "audio.npy")
+    assert audio.dtype == np.float32 and audio.size == j["config"]["samples"] == 86016
+    ids, dur, noise = bench.utterance(8, 1234, rt_medium.cfg.inter)
+    rt_medium.prepare(4, ids, dur, noise, 0.667)
+    rt_medium.launch(4)
+    assert_close(audio, rt_medium.collect(4), WAVE_TOL, "bench --dump-outputs vs the library")
+
+
 def test_bf16_fused_pairs_equal_the_two_launch_path(tmp_path):
     """rb_pair_bf16_kernel against conv_bf16_kernel × 2 (PIPER_HIP_NO_RB_PAIR is read once per process, so: two child processes):
     the rounding points are the same, what differs is fp32 summation order and the bf16 roundings it flips — mutual SNR ≥ 45 dB and

@@ -11,7 +11,7 @@ for cfg in "$@"; do
   i=$((i+1))
   d="$OUT/c$i"; rm -rf "$d"
   echo "== [$i] $cfg"
-  ( export $cfg; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-scale-bench --steps 40 --warmup 5 ${BENCH_ARGS} > "$d.log" 2>&1 )
+  ( export $cfg; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-scale-bench --steps 40 --warmup 5 ${BENCH_ARGS} > "$d.log" 2>&1 )
   python3 - "$d" "$d.log" <<'PY'
 import sys,glob,csv,json,re
 d,log=sys.argv[1],sys.argv[2]

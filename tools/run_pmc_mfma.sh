@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-scale-bench --no-profile --steps 40 --warmup 5"
+COMMON="--full --no-cpu-baseline --no-scale-bench --no-profile --steps 40 --warmup 5"
 pass() {  # name, counters, bench args...
   local name=$1 ctr=$2; shift 2
   timeout -k 10 240 rocprofv3 --pmc $ctr --output-format csv -d "$OUT/${name}" -- python3 "$ROOT/bench.py" "$@" > "$OUT/${name}.log" 2>&1

@@ -14,19 +14,19 @@ prof() {  # name, bench args...
   timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/${name}_write" -- python3 "$ROOT/bench.py" "$@" > "$OUT/${name}_write.log" 2>&1
   echo "profiled $name"
 }
-COMMON="--no-cpu-baseline --no-scale-bench --steps 40 --warmup 5"
+COMMON="--full --no-cpu-baseline --no-scale-bench --steps 40 --warmup 5"
 prof f32 $COMMON
 prof high_bf16 --quality high --precision bf16 $COMMON
 # kernel-trace only for the two configurations VERDICT r1 #4 names (conv_win / rb_pair where they dominate)
-timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/f64_stats" -- python3 "$ROOT/bench.py" --factor 64 --steps 20 --no-cpu-baseline --no-scale-bench > "$OUT/f64_stats.log" 2>&1
-timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/high_f32_stats" -- python3 "$ROOT/bench.py" --quality high --steps 20 --no-cpu-baseline --no-scale-bench > "$OUT/high_f32_stats.log" 2>&1
+timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/f64_stats" -- python3 "$ROOT/bench.py" --full --factor 64 --steps 20 --no-cpu-baseline --no-scale-bench > "$OUT/f64_stats.log" 2>&1
+timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/high_f32_stats" -- python3 "$ROOT/bench.py" --full --quality high --steps 20 --no-cpu-baseline --no-scale-bench > "$OUT/high_f32_stats.log" 2>&1
 cd "$ROOT"
-timeout -k 10 300 python3 bench.py > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
 echo "bench full done"
-timeout -k 10 200 python3 bench.py --quality high --precision bf16 --no-cpu-baseline > "$OUT/bench_high_bf16.json" 2> "$OUT/bench_high_bf16.err"
-timeout -k 10 200 python3 bench.py --quality medium --precision bf16 --no-cpu-baseline > "$OUT/bench_medium_bf16.json" 2>> "$OUT/bench_high_bf16.err"
-timeout -k 10 200 python3 bench.py --quality high --no-cpu-baseline --no-scale-bench > "$OUT/bench_high_f32.json" 2>> "$OUT/bench_high_bf16.err"
-timeout -k 10 200 python3 bench.py --factor 64 --no-cpu-baseline --no-scale-bench --steps 20 > "$OUT/bench_factor64.json" 2>> "$OUT/bench_high_bf16.err"
+timeout -k 10 200 python3 bench.py --full --quality high --precision bf16 --no-cpu-baseline > "$OUT/bench_high_bf16.json" 2> "$OUT/bench_high_bf16.err"
+timeout -k 10 200 python3 bench.py --full --quality medium --precision bf16 --no-cpu-baseline > "$OUT/bench_medium_bf16.json" 2>> "$OUT/bench_high_bf16.err"
+timeout -k 10 200 python3 bench.py --full --quality high --no-cpu-baseline --no-scale-bench > "$OUT/bench_high_f32.json" 2>> "$OUT/bench_high_bf16.err"
+timeout -k 10 200 python3 bench.py --full --factor 64 --no-cpu-baseline --no-scale-bench --steps 20 > "$OUT/bench_factor64.json" 2>> "$OUT/bench_high_bf16.err"
 echo "bench variants done"
 timeout -k 10 100 python3 tools/profile_steps.py > "$OUT/steps_factor8.txt"
 timeout -k 10 100 python3 tools/profile_steps.py --factor 64 > "$OUT/steps_factor64.txt"
