@@ -443,15 +443,17 @@ int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_utterance*
 int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int max_frames);
 /* Plans (schedule + arena + HIP graph) are cached per voice by bucket — phonemes rounded up to 16, frames to 16 (64 beyond
  * 1024) — and batch size, least recently used first out, so a (T, F) never seen before usually finds its graph ready and
- * `prepare` is only the input upload ("warm"); a new bucket pays schedule construction + one validation pass + capture +
- * instantiate once ("cold"). Reports the bucket of a prepared slot and the cache's size. */
+ * `prepare` is only the input upload ("warm"); a new bucket pays schedule construction + arena inside `prepare` once ("cold"), and
+ * the plan's first launch runs eagerly and captures + instantiates its graph behind itself. Reports the bucket of a prepared slot and
+ * the cache's size. */
 int piper_hip_voice_plan_info(const piper_hip_voice* v, int slot, int32_t* bucket_t, int32_t* bucket_f, int32_t* cached_plans,
                               size_t* cached_bytes);
 /* Bounds of the voice's plan cache: at most `max_plans` plans and `max_bytes` of arenas (0 = the default 24 GiB) are kept; idle plans are
  * evicted least recently used first, plans attached to a slot never. Defaults: 128 plans. */
 int piper_hip_voice_set_plan_cache(piper_hip_voice* v, int max_plans, size_t max_bytes);
 /* Wall milliseconds of the phases of the LATEST plan build (a "cold" prepare): [0] stream / events, [1] schedule construction + arena
- * allocation, [2] arena initialisation, [3] eager validation pass, [4] graph capture, [5] graph instantiate. */
+ * allocation, [2] arena initialisation, [3] always 0 (there is no validation pass any more; the entry is kept for the ABI), [4] graph
+ * capture, [5] graph instantiate. [4] and [5] are 0 after the prepare and are filled by the plan's first launch. */
 int piper_hip_voice_last_build_breakdown(const piper_hip_voice* v, double out_ms[6]);
 /* Batch size of a prepared slot (0 if the slot is not prepared). */
 int piper_hip_voice_batch_size(const piper_hip_voice* v, int slot);

@@ -197,12 +197,15 @@ struct ConvW {  // one resident conv: packed (MFMA) or raw (direct) weights + bi
   bool mfma = false;
 };
 
+// A plan's streams and events: the main stream with the timing events ev0 / ev1 (create_set), and the two side streams of schedules with
+// parallel branches with their fork / join events (ensure_side_streams, created on first use). A plan holds one while it is attached.
+struct StreamSet {
+  hipStream_t stream = nullptr, side[2] = {nullptr, nullptr};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
+};
+
 struct Slot {
-  bool inited = false;
-  hipStream_t stream = nullptr;
-  hipStream_t side[2] = {nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  StreamSet set;  // empty (set.stream == nullptr) while the plan is idle: slot_init takes one, give_back_set returns it
   // A Slot is a PLAN: schedule + arena + graph for one bucket (kind, T, F, NB). T and F are the bucket's row lengths; the
   // true lengths of the NB batch items live in device memory (lensT / lensF) where every length-aware kernel reads them, so
   // one captured graph serves every utterance that fits the bucket — exactly (positions past a true length read as zero
@@ -222,16 +225,12 @@ struct Slot {
   void* dp_scalars = nullptr;  // [NB] DpScalars (device)
   int32_t* dp_dur = nullptr;   // [NB][T] predicted frames per id
   std::vector<int32_t> h_dur;  // predicted durations of the attached request, per item back to back (host)
-  int* h_lens = nullptr;       // pinned staging [2·NB]
   // kind 3 prepared by piper_hip_voice_prepare_batch_bounded: the frame counts are decided on the device and reach the host with the
   // waveform (collect). Until then h_F holds the bucket's capacity.
   bool bounded_pending = false;
   int bounded_cap = 0;         // max_frames the caller allowed
   hipEvent_t ev_in = nullptr;  // kind 3: "the copy of the predictor plan's projection has been read" (that plan's stream waits for it)
   float* stats = nullptr;      // [NB][2·inter][T] encoder projection (m_p ; logs_p): output of kinds 0 / 2, INPUT of kind 3
-  float* h_audio = nullptr;    // pinned landing buffer of the waveform (collect: device → pinned DMA, then a host memcpy)
-  size_t h_audio_cap = 0;
-  size_t h_cap_lens = 0;
   // device buffers
   std::vector<void*> owned;
   int64_t* ids = nullptr;
@@ -239,8 +238,6 @@ struct Slot {
   float* noise = nullptr;
   float* noise_scale = nullptr;  // [NB] device
   unsigned* rng = nullptr;       // [NB][2] device: {generate noise on the device?, seed}
-  std::vector<float> h_noise_scale;
-  std::vector<unsigned> h_rng;
   float* audio = nullptr;
   int64_t n_samples = 0;
   std::vector<Step> steps;
@@ -261,10 +258,6 @@ struct Slot {
   hipGraphExec_t front_exec = nullptr;  // encoder + flow only
   int st_chunk = 0, st_next = -1, st_halo = 0;
   int cur_lane = 0;  // lane given to steps added by add_conv
-  // host staging (pinned so the H2D copies are truly async)
-  int64_t* h_ids = nullptr;
-  int32_t* h_f2i = nullptr;
-  size_t h_cap_t = 0, h_cap_f = 0;
 };
 
 }  // namespace
@@ -321,15 +314,14 @@ struct piper_hip_voice {
   // Plans are cached voice-wide, least-recently-used first out; a user slot id is a handle on one of them. A TTS server sees
   // a new (T, F) almost every call: with buckets the plan for it usually exists already (prepare = input upload only).
   std::vector<std::unique_ptr<Slot>> plans;
-  struct StreamSet { hipStream_t stream, side[2]; hipEvent_t ev0, ev1, ev_fork, ev_join[2]; };
-  std::vector<StreamSet> free_sets;  // streams / events of evicted plans, reused by the next build (a HIP stream costs ≈ 3 ms to create)
-  double last_build_ms[6] = {0, 0, 0, 0, 0, 0};  // the latest plan build: stream/events, schedule + arena, arena init, eager pass, capture, instantiate
+  std::vector<StreamSet> free_sets;  // sets of idle plans and those voice_create made, for the next plan attached (a HIP stream costs ≈ 3 ms to create)
+  double last_build_ms[6] = {0, 0, 0, 0, 0, 0};  // the latest plan build: stream/events, schedule + arena, arena init, 0 (ABI), capture, instantiate
   size_t plan_cache_max = 128, plan_cache_bytes = (size_t)24 << 30;
   // Page-locked staging of a slot id's inputs and of its (short) waveform: it belongs to the SLOT ID, not to the plan attached to it —
   // a new bucket then costs no hipHostMalloc (≈ 0.3–1 ms each, four per plan until round 3). Grown in powers of two, freed with the voice.
   struct Staging {
     int64_t* h_ids = nullptr; int32_t* h_f2i = nullptr; int* h_lens = nullptr; float* h_audio = nullptr;
-    size_t cap_t = 0, cap_f = 0, cap_lens = 0, audio_cap = 0;
+    size_t cap_t = 0, cap_f = 0, cap_lens = 0, audio_cap = 0;  // (every cap_* / *_cap counts elements: grow_pinned)
     // bounded prepare (durations predicted, no host round trip): scalars of the request, the predictor's noise, and what the device reports
     // back (frames per item, durations) — the last two written by a kernel through the host mapping
     char* h_misc = nullptr; float* h_dpn = nullptr; int32_t* h_res = nullptr;
@@ -547,6 +539,86 @@ int compile_weights(piper_hip_voice* v, Packer& pk, bool dry, const std::vector<
   return PIPER_HIP_OK;
 }
 
+// ---- stream sets: created by create_set, taken by slot_init, given back by give_back_set, destroyed with the voice -------------
+
+// The first device → host copy a STREAM hands to the copy engine costs 7 … 17 ms (r3, tools/probe/first_run.py with PIPER_HIP_COLLECT_DMA=1:
+// 8.1 ms in collect for 1.0 ms of GPU work; warming another stream of the process did not help). Every stream a plan will use gets that copy
+// out of the way when it is created — while the voice loads for the four it pre-creates.
+void warm_stream_copies(piper_hip_voice* v, hipStream_t q) {
+  void* hp = nullptr;
+  const size_t nb = std::min<size_t>((size_t)2 << 20, v->blob_floats * sizeof(float));  // large enough for the copy ENGINE (small ones are blitted)
+  if (!v->blob || hipHostMalloc(&hp, nb) != hipSuccess) { (void)hipGetLastError(); return; }
+  hipLaunchKernelGGL(empty_kernel, dim3(1), dim3(64), 0, q);  // as in a request: the copy waits for a kernel of the same stream
+  (void)hipMemcpyAsync(hp, v->blob, nb, hipMemcpyDeviceToHost, q);
+  (void)hipStreamSynchronize(q);
+  (void)hipHostFree(hp);
+  (void)hipGetLastError();
+}
+
+void destroy_set(StreamSet& st) {
+  for (hipEvent_t e : {st.ev0, st.ev1, st.ev_fork, st.ev_join[0], st.ev_join[1]})
+    if (e) (void)hipEventDestroy(e);
+  for (hipStream_t q : {st.side[0], st.side[1], st.stream})
+    if (q) (void)hipStreamDestroy(q);
+  st = {};
+}
+
+// A new set: the main stream and its timing events, with the stream's first copy made. On failure nothing is left behind.
+// r3 (tools/probe/cold_prepare.py): creating the three streams of a plan was 8.6–10 ms of an 11 ms plan build. The two side streams are only
+// for schedules with parallel branches (ensure_side_streams), so a set starts with one.
+int create_set(piper_hip_voice* v, StreamSet& st) {
+  st = {};
+  hipError_t e = hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreate(&st.ev0);
+  if (e == hipSuccess) e = hipEventCreate(&st.ev1);
+  if (e != hipSuccess) {
+    destroy_set(st);
+    PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream set: creation failed: %s", hipGetErrorString(e));
+  }
+  warm_stream_copies(v, st.stream);
+  return PIPER_HIP_OK;
+}
+
+// An idle plan needs no stream: its set goes to the next plan that is attached (usually the one replacing it on the same slot id), so that
+// after a slot id's first request no prepare creates a stream again (≈ 3 ms each, r3). The caller has synchronised the stream.
+void give_back_set(piper_hip_voice* v, Slot& s) {
+  if (s.set.stream) v->free_sets.push_back(s.set);
+  s.set = {};
+}
+
+// `count` sets on the free list while the voice loads (voice_create). Not fatal: slot_init creates what is missing. Returns the first
+// set's stream, or null if none could be created.
+hipStream_t precreate_sets(piper_hip_voice* v, int count) {
+  for (int i = 0; i < count; i++) {
+    StreamSet st;
+    if (create_set(v, st)) {
+      (void)hipGetLastError();
+      break;
+    }
+    v->free_sets.push_back(st);
+  }
+  return v->free_sets.empty() ? nullptr : v->free_sets[0].stream;
+}
+
+// A set for the plan: one given back earlier if there is one, a new one otherwise.
+int slot_init(piper_hip_voice* v, Slot& s) {
+  if (s.set.stream) return PIPER_HIP_OK;
+  if (v->free_sets.empty()) return create_set(v, s.set);
+  s.set = v->free_sets.back();
+  v->free_sets.pop_back();
+  return PIPER_HIP_OK;
+}
+
+int ensure_side_streams(Slot& s) {
+  StreamSet& st = s.set;
+  for (int i = 0; i < 2; i++) {
+    if (!st.side[i]) PH_HIP(hipStreamCreateWithFlags(&st.side[i], hipStreamNonBlocking), PIPER_HIP_ERR_LAUNCH);
+    if (!st.ev_join[i]) PH_HIP(hipEventCreateWithFlags(&st.ev_join[i], hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+  }
+  if (!st.ev_fork) PH_HIP(hipEventCreateWithFlags(&st.ev_fork, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
 void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   if (s.exec) { (void)hipGraphExecDestroy(s.exec); s.exec = nullptr; }
   if (s.graph) { (void)hipGraphDestroy(s.graph); s.graph = nullptr; }
@@ -560,15 +632,10 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.taps.clear();
   s.T = s.F = -1;
   s.built = false;
-  if (all) {  // (host buffers belong to the plan whether or not it currently holds a stream set)
-    // (the pinned staging buffers are the slot id's: piper_hip_voice::staging)
+  if (all) {  // (the pinned staging buffers are the slot id's: piper_hip_voice::staging)
     if (s.ev_in) (void)hipEventDestroy(s.ev_in);
     s.ev_in = nullptr;
-    s.h_ids = nullptr; s.h_f2i = nullptr; s.h_lens = nullptr; s.h_audio = nullptr; s.h_cap_t = s.h_cap_f = s.h_cap_lens = 0; s.h_audio_cap = 0;
-    // streams and events go back to the voice (the caller has synchronised them); piper_hip_voice_destroy destroys them
-    if (s.stream) v->free_sets.push_back({s.stream, {s.side[0], s.side[1]}, s.ev0, s.ev1, s.ev_fork, {s.ev_join[0], s.ev_join[1]}});
-    s.stream = nullptr; s.side[0] = s.side[1] = nullptr; s.ev0 = s.ev1 = s.ev_fork = nullptr; s.ev_join[0] = s.ev_join[1] = nullptr;
-    s.inited = false;
+    give_back_set(v, s);  // piper_hip_voice_destroy destroys the sets
   }
 }
 
@@ -663,7 +730,7 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
   const piper_hip_voice_config& c = v->cfg;
   const int I = c.inter;
   const size_t B = (size_t)NB;
-  hipStream_t zs = s.stream;
+  hipStream_t zs = s.set.stream;
   static const bool no_par = getenv("PIPER_HIP_BF16_SERIAL_RB") != nullptr;
   static const bool no_merge = getenv("PIPER_HIP_NO_MERGED_RB") != nullptr;
   // short utterances / small batches: the three ResBlocks advance in one launch; otherwise one launch per conv, as parallel
@@ -1669,8 +1736,6 @@ int build_duration_predictor(piper_hip_voice* v, Slot& s, Arena& ar, const float
   return PIPER_HIP_OK;
 }
 
-int ensure_side_streams(Slot& s);
-
 int run_schedule(Slot& s, hipStream_t q, bool parallel) {
   if (parallel) {
     const int rc0 = ensure_side_streams(s);
@@ -1679,20 +1744,20 @@ int run_schedule(Slot& s, hipStream_t q, bool parallel) {
   for (auto& st : s.steps) {
     if (st.kind == Step::FORK) {
       if (parallel) {
-        PH_HIP(hipEventRecord(s.ev_fork, q), PIPER_HIP_ERR_LAUNCH);
-        for (int i = 0; i < 2; i++) PH_HIP(hipStreamWaitEvent(s.side[i], s.ev_fork, 0), PIPER_HIP_ERR_LAUNCH);
+        PH_HIP(hipEventRecord(s.set.ev_fork, q), PIPER_HIP_ERR_LAUNCH);
+        for (int i = 0; i < 2; i++) PH_HIP(hipStreamWaitEvent(s.set.side[i], s.set.ev_fork, 0), PIPER_HIP_ERR_LAUNCH);
       }
       continue;
     }
     if (st.kind == Step::JOIN) {
       if (parallel)
         for (int i = 0; i < 2; i++) {
-          PH_HIP(hipEventRecord(s.ev_join[i], s.side[i]), PIPER_HIP_ERR_LAUNCH);
-          PH_HIP(hipStreamWaitEvent(q, s.ev_join[i], 0), PIPER_HIP_ERR_LAUNCH);
+          PH_HIP(hipEventRecord(s.set.ev_join[i], s.set.side[i]), PIPER_HIP_ERR_LAUNCH);
+          PH_HIP(hipStreamWaitEvent(q, s.set.ev_join[i], 0), PIPER_HIP_ERR_LAUNCH);
         }
       continue;
     }
-    hipStream_t target = (parallel && st.lane > 0) ? s.side[st.lane - 1] : q;
+    hipStream_t target = (parallel && st.lane > 0) ? s.set.side[st.lane - 1] : q;
     int rc = st.run(target);
     if (rc) return rc;
   }
@@ -1701,73 +1766,95 @@ int run_schedule(Slot& s, hipStream_t q, bool parallel) {
   return PIPER_HIP_OK;
 }
 
-// The first device → host copy a STREAM hands to the copy engine costs 7 … 17 ms (r3, tools/probe/first_run.py with PIPER_HIP_COLLECT_DMA=1:
-// 8.1 ms in collect for 1.0 ms of GPU work; warming another stream of the process did not help). Every stream a plan will use gets that copy
-// out of the way when it is created — while the voice loads for the four it pre-creates.
-void warm_stream_copies(piper_hip_voice* v, hipStream_t q) {
-  void* hp = nullptr;
-  const size_t nb = std::min<size_t>((size_t)2 << 20, v->blob_floats * sizeof(float));  // large enough for the copy ENGINE (small ones are blitted)
-  if (!v->blob || hipHostMalloc(&hp, nb) != hipSuccess) { (void)hipGetLastError(); return; }
-  hipLaunchKernelGGL(empty_kernel, dim3(1), dim3(64), 0, q);  // as in a request: the copy waits for a kernel of the same stream
-  (void)hipMemcpyAsync(hp, v->blob, nb, hipMemcpyDeviceToHost, q);
-  (void)hipStreamSynchronize(q);
-  (void)hipHostFree(hp);
-  (void)hipGetLastError();
-}
-
-int slot_init(piper_hip_voice* v, Slot& s) {
-  if (s.inited) return PIPER_HIP_OK;
-  if (!v->free_sets.empty()) {  // a set an evicted plan left behind
-    const auto st = v->free_sets.back();
-    v->free_sets.pop_back();
-    s.stream = st.stream; s.side[0] = st.side[0]; s.side[1] = st.side[1];
-    s.ev0 = st.ev0; s.ev1 = st.ev1; s.ev_fork = st.ev_fork; s.ev_join[0] = st.ev_join[0]; s.ev_join[1] = st.ev_join[1];
-    s.inited = true;
-    return PIPER_HIP_OK;
+// What `enqueue(q)` issues on q, captured into *g and instantiated into *ge. On failure neither is left behind (both stay null) and the
+// error message starts with `what`. `ms` (optional): wall time of the capture [0] and of the instantiate [1].
+template <typename Enqueue>
+int capture_graph(hipStream_t q, Enqueue&& enqueue, hipGraph_t* g, hipGraphExec_t* ge, const char* what, double* ms = nullptr) {
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  *g = nullptr;
+  *ge = nullptr;
+  hipError_t e = hipStreamBeginCapture(q, hipStreamCaptureModeThreadLocal);
+  if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "%s: begin capture failed: %s", what, hipGetErrorString(e));
+  const int rc = enqueue(q);
+  e = hipStreamEndCapture(q, g);
+  const auto t1 = clk::now();
+  const char* failed = "graph capture";
+  if (!rc && e == hipSuccess) {
+    e = hipGraphInstantiate(ge, *g, nullptr, nullptr, 0);
+    failed = "graph instantiate";
   }
-  // r3 (tools/probe/cold_prepare.py): creating the three streams of a plan was 8.6–10 ms of an 11 ms plan build. The two side
-  // streams are only for schedules with parallel branches (ensure_side_streams), so a plan now creates one.
-  PH_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipEventCreate(&s.ev0), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipEventCreate(&s.ev1), PIPER_HIP_ERR_LAUNCH);
-  warm_stream_copies(v, s.stream);
-  s.inited = true;
+  if (rc || e != hipSuccess) {
+    if (*g) (void)hipGraphDestroy(*g);
+    *g = nullptr;
+    *ge = nullptr;
+    if (rc) return rc;
+    PH_FAIL(PIPER_HIP_ERR_LAUNCH, "%s: %s failed: %s", what, failed, hipGetErrorString(e));
+  }
+  if (ms) {
+    ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    ms[1] = std::chrono::duration<double, std::milli>(clk::now() - t1).count();
+  }
   return PIPER_HIP_OK;
 }
 
-int ensure_side_streams(Slot& s) {
-  for (int i = 0; i < 2; i++) {
-    if (!s.side[i]) PH_HIP(hipStreamCreateWithFlags(&s.side[i], hipStreamNonBlocking), PIPER_HIP_ERR_LAUNCH);
-    if (!s.ev_join[i]) PH_HIP(hipEventCreateWithFlags(&s.ev_join[i], hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
-  }
-  if (!s.ev_fork) PH_HIP(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+// What every prepare / predict checks on item b of a batch: ids given, 1 ≤ t ≤ 4096 (the --max-phonemes cap, PiperCLI.swift:394), a known
+// noise_mode
+int check_item(const piper_hip_utterance& u, int b) {
+  if (!u.phoneme_ids) PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: null ids", b);
+  if (u.t < 1 || u.t > 4096) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: %d ids outside [1,4096] (PiperCLI.swift:394)", b, u.t);
+  if (u.noise_mode != PIPER_HIP_NOISE_INJECTED && u.noise_mode != PIPER_HIP_NOISE_DEVICE)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: unknown noise_mode %d", b, u.noise_mode);
   return PIPER_HIP_OK;
 }
 
-int check_utt(const piper_hip_voice* v, const piper_hip_utterance* u, int64_t* F_out) {
-  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  if (!u || !u->phoneme_ids) PH_FAIL(PIPER_HIP_ERR_ARG, "utterance: null ids");
-  if (u->t < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance: need at least one phoneme id");
-  if (u->t > 4096) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance: %d ids exceeds the 4096 cap (PiperCLI.swift:394)", u->t);
-  if (!u->durations) {  // to be predicted: the frame count is not known yet
-    if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_ARG, "utterance: durations are NULL and the voice has no duration predictor");
+// Frames of item b (its ids already checked): the sum of its durations, or −1 when they are to be predicted
+int utt_frames(const piper_hip_voice* v, const piper_hip_utterance& u, int b, int64_t* F_out) {
+  if (!u.durations) {  // to be predicted: the frame count is not known yet
+    if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: durations are NULL and the voice has no duration predictor", b);
     // `noise` is [inter, F] and F is what the predictor is about to decide: the caller cannot have sized it, and the ABI carries no
     // size to check it against (in the reference an override tensor brings its shape, TensorValue.swift:4-43)
-    if (u->noise)
-      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance: noise given but durations are NULL — its [inter, F] shape depends on the predicted durations: call "
-                                 "piper_hip_voice_predict_durations first and pass durations + noise, or use noise_mode = DEVICE");
+    if (u.noise)
+      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: noise given but durations are NULL — its [inter, F] shape depends on the predicted durations: call "
+                                 "piper_hip_voice_predict_durations first and pass durations + noise, or use noise_mode = DEVICE", b);
     *F_out = -1;
     return PIPER_HIP_OK;
   }
   int64_t F = 0;
-  for (int i = 0; i < u->t; i++) {
-    if (u->durations[i] < 0) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance: negative duration");
-    F += u->durations[i];
+  for (int i = 0; i < u.t; i++) {
+    if (u.durations[i] < 0) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: negative duration", b);
+    F += u.durations[i];
   }
-  if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance: zero frames");
-  if (F * v->hop > 0x3fffffff / 64) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance: %lld frames too long", (long long)F);
+  if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: zero frames", b);
+  if (F * v->hop > 0x3fffffff / 64) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: %lld frames too long", b, (long long)F);
   *F_out = F;
   return PIPER_HIP_OK;
+}
+
+// ids of n utterances → rows of T, zero past each one's end (any legal id)
+void pack_ids(const piper_hip_utterance* utts, int n, int T, int64_t* ids) {
+  for (int b = 0; b < n; b++) {
+    int64_t* row = ids + (size_t)b * T;
+    memcpy(row, utts[b].phoneme_ids, (size_t)utts[b].t * sizeof(int64_t));
+    std::fill(row + utts[b].t, row + T, (int64_t)0);
+  }
+}
+
+// The duration predictor's inputs of n utterances: each one's `dp` noise [2, t] in two rows of T (zero past t; all zero without one), and
+// its DpScalars. (Device mode draws element (row, t) of the item's OWN [1, 2, T_b] tensor: the kernel indexes the bucket row, so the draw
+// index must be remapped when T_b < T — done by generating on the host side of the index: see dp_init_kernel (uses T).)
+void pack_dp_inputs(const piper_hip_utterance* utts, int n, int T, float* noise, void* scalars) {
+  for (int b = 0; b < n; b++) {
+    const piper_hip_utterance& u = utts[b];
+    for (int r = 0; r < 2; r++) {
+      float* row = noise + ((size_t)b * 2 + r) * T;
+      const int given = u.dp_noise ? u.t : 0;
+      if (given) memcpy(row, u.dp_noise + (size_t)r * u.t, (size_t)given * sizeof(float));
+      std::fill(row + given, row + T, 0.0f);
+    }
+    dp_scalars_fill(scalars, b, u.noise_w, u.length_scale == 0.0f ? 1.0f : u.length_scale,
+                    (!u.dp_noise && u.noise_mode == PIPER_HIP_NOISE_DEVICE) ? 1u : 0u, u.seed);
+  }
 }
 
 }  // namespace
@@ -1830,34 +1917,20 @@ PH_EXPORT int piper_hip_voice_create(piper_hip_ctx* ctx, const piper_hip_voice_c
   // Four stream sets up front: creating a HIP stream costs ≈ 3 ms (8 ms for the first of a process, tools/probe/cold_prepare.py) — paid here,
   // while the voice loads, it is off the first request (first_request_ms 21 → 13 in bench.py). Plans take sets from this list (slot_init)
   // and give them back when they go idle (detach); a voice serving more than four slot ids at once creates the rest on demand.
-  for (int i = 0; i < 4; i++) {
-    piper_hip_voice::StreamSet st = {};
-    if (hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&st.ev0) != hipSuccess || hipEventCreate(&st.ev1) != hipSuccess) {
-      (void)hipGetLastError();
-      if (st.ev0) (void)hipEventDestroy(st.ev0);
-      if (st.stream) (void)hipStreamDestroy(st.stream);
-      break;  // not fatal: slot_init creates what is missing
-    }
-    v->free_sets.push_back(st);
-  }
   // … and the process's first graph capture + instantiate (≈ 8 ms against ≈ 1 ms for later ones: the runtime sets its graph machinery up
   // on first use) on a one-kernel graph, for the same reason. Failure is not fatal.
-  if (!v->free_sets.empty()) {
-    const hipStream_t q = v->free_sets[0].stream;
+  if (const hipStream_t q = precreate_sets(v.get(), 4)) {
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
-    if (hipStreamBeginCapture(q, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-      hipLaunchKernelGGL(empty_kernel, dim3(1), dim3(64), 0, q);
-      if (hipStreamEndCapture(q, &g) == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess && ge) {
-        (void)hipGraphLaunch(ge, q);
-        (void)hipStreamSynchronize(q);
-      }
+    auto one_kernel = [](hipStream_t q) { hipLaunchKernelGGL(empty_kernel, dim3(1), dim3(64), 0, q); return PIPER_HIP_OK; };
+    if (capture_graph(q, one_kernel, &g, &ge, "voice_create") == PIPER_HIP_OK) {
+      (void)hipGraphLaunch(ge, q);
+      (void)hipStreamSynchronize(q);
+      (void)hipGraphExecDestroy(ge);
+      (void)hipGraphDestroy(g);
     }
-    if (ge) (void)hipGraphExecDestroy(ge);
-    if (g) (void)hipGraphDestroy(g);
     (void)hipGetLastError();
   }
-  for (auto& st : v->free_sets) warm_stream_copies(v.get(), st.stream);
   *out = v.release();
   return PIPER_HIP_OK;
 }
@@ -1964,19 +2037,14 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_noise) (void)hipHostFree(sg.h_noise);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
-  for (auto& st : v->free_sets) {
-    for (hipEvent_t e : {st.ev0, st.ev1, st.ev_fork, st.ev_join[0], st.ev_join[1]})
-      if (e) (void)hipEventDestroy(e);
-    for (hipStream_t q : {st.side[0], st.side[1], st.stream})
-      if (q) (void)hipStreamDestroy(q);
-  }
+  for (auto& st : v->free_sets) destroy_set(st);
   for (void* p : v->owned) (void)v->ctx->pool.release(p);
   delete v;
 }
 
 PH_EXPORT int64_t piper_hip_voice_num_samples(const piper_hip_voice* v, const piper_hip_utterance* u) {
   int64_t F = 0;
-  if (check_utt(v, u, &F)) return -1;
+  if (!v || !u || !u->phoneme_ids || u->t < 1 || u->t > 4096 || utt_frames(v, *u, 0, &F)) return -1;  // (noise_mode is not looked at)
   if (F < 0) return -2;
   return F * v->hop;
 }
@@ -2006,7 +2074,7 @@ void evict_idle_plans(piper_hip_voice* v) {
       if (!v->plans[i]->in_use && (victim < 0 || v->plans[i]->last_use < v->plans[victim]->last_use)) victim = i;
     if (victim < 0) return;  // everything is attached: nothing to evict
     Slot& d = *v->plans[victim];
-    if (d.stream) (void)hipStreamSynchronize(d.stream);
+    if (d.set.stream) (void)hipStreamSynchronize(d.set.stream);
     slot_release(v, d, true);
     v->plans.erase(v->plans.begin() + victim);
   }
@@ -2018,30 +2086,18 @@ void evict_idle_plans(piper_hip_voice* v) {
 // `on`: the stream the plan runs on (default: its own). A plan without parallel lanes may run on any stream — the bounded prepare puts
 // the predictor plan on the stream of the plan that continues from it, so the two need no event between them.
 int launch_plan(piper_hip_voice* v, Slot& s, hipStream_t on = nullptr) {
-  const hipStream_t q = on ? on : s.stream;
+  const hipStream_t q = on ? on : s.set.stream;
   if (s.exec) {
     PH_HIP(hipGraphLaunch(s.exec, q), PIPER_HIP_ERR_LAUNCH);
     return PIPER_HIP_OK;
   }
-  int rc = run_schedule(s, q, false);
+  const int rc = run_schedule(s, q, false);
   if (rc) return rc;
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  hipError_t e = hipStreamBeginCapture(q, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "plan: begin capture failed: %s", hipGetErrorString(e));
   // fp32 generator: parallel ResBlock branches measured SLOWER on hipGraph (fork/join edges cost more than the three
   // short kernels gain), so that graph stays a single chain unless asked otherwise. The bf16 generator's builder decides
   // for itself (s.parallel).
-  rc = run_schedule(s, q, s.parallel && !on);
-  hipError_t ce = hipStreamEndCapture(q, &s.graph);
-  if (rc) return rc;
-  if (ce != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "plan: graph capture failed: %s", hipGetErrorString(ce));
-  const auto t1 = clk::now();
-  ce = hipGraphInstantiate(&s.exec, s.graph, nullptr, nullptr, 0);
-  if (ce != hipSuccess) { s.exec = nullptr; PH_FAIL(PIPER_HIP_ERR_LAUNCH, "plan: graph instantiate failed: %s", hipGetErrorString(ce)); }
-  v->last_build_ms[4] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  v->last_build_ms[5] = std::chrono::duration<double, std::milli>(clk::now() - t1).count();
-  return PIPER_HIP_OK;
+  const bool parallel = s.parallel && !on;
+  return capture_graph(q, [&](hipStream_t q) { return run_schedule(s, q, parallel); }, &s.graph, &s.exec, "plan", v->last_build_ms + 4);
 }
 
 // An idle plan for (kind, Tb, Fb, NB) at the voice's precision, built (schedule + arena; its graph follows its first run) if
@@ -2072,14 +2128,14 @@ int acquire_plan(piper_hip_voice* v, int kind, int Tb, int Fb, int NB, Slot** ou
   Slot& s = *np;
   // a plan may be captured / profiled before every input has been uploaded: give the length arrays and index inputs legal values
   {
-    hipLaunchKernelGGL(fill_lens_kernel, dim3((unsigned)ceil_div(NB, 64)), dim3(64), 0, s.stream, s.lensT, s.lensF, Tb, Fb, NB);
+    hipLaunchKernelGGL(fill_lens_kernel, dim3((unsigned)ceil_div(NB, 64)), dim3(64), 0, s.set.stream, s.lensT, s.lensF, Tb, Fb, NB);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && s.ids) e = hipMemsetAsync(s.ids, 0, (size_t)NB * Tb * sizeof(int64_t), s.stream);
-    if (e == hipSuccess && s.frame2id) e = hipMemsetAsync(s.frame2id, 0, (size_t)NB * Fb * sizeof(int32_t), s.stream);
-    if (e == hipSuccess && s.rng) e = hipMemsetAsync(s.rng, 0, (size_t)NB * 2 * sizeof(unsigned), s.stream);
-    if (e == hipSuccess && s.dp_scalars) e = hipMemsetAsync(s.dp_scalars, 0, dp_scalars_bytes(NB), s.stream);
-    if (e == hipSuccess && s.dp_noise) e = hipMemsetAsync(s.dp_noise, 0, (size_t)NB * 2 * Tb * sizeof(float), s.stream);
-    if (e == hipSuccess) e = stream_wait(s.stream);
+    if (e == hipSuccess && s.ids) e = hipMemsetAsync(s.ids, 0, (size_t)NB * Tb * sizeof(int64_t), s.set.stream);
+    if (e == hipSuccess && s.frame2id) e = hipMemsetAsync(s.frame2id, 0, (size_t)NB * Fb * sizeof(int32_t), s.set.stream);
+    if (e == hipSuccess && s.rng) e = hipMemsetAsync(s.rng, 0, (size_t)NB * 2 * sizeof(unsigned), s.set.stream);
+    if (e == hipSuccess && s.dp_scalars) e = hipMemsetAsync(s.dp_scalars, 0, dp_scalars_bytes(NB), s.set.stream);
+    if (e == hipSuccess && s.dp_noise) e = hipMemsetAsync(s.dp_noise, 0, (size_t)NB * 2 * Tb * sizeof(float), s.set.stream);
+    if (e == hipSuccess) e = stream_wait(s.set.stream);
     if (e != hipSuccess) { slot_release(v, s, true); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "voice_prepare: arena initialisation failed: %s", hipGetErrorString(e)); }
   }
   lap();
@@ -2088,44 +2144,60 @@ int acquire_plan(piper_hip_voice* v, int kind, int Tb, int Fb, int NB, Slot** ou
   // first request of a bucket). The plan's FIRST launch goes out eagerly — that run IS the request's answer — and the graph is
   // captured and instantiated right behind it, host work that overlaps the GPU's (launch_plan).
   s.built = true;
-  lap(); lap(); lap();
+  v->last_build_ms[3] = v->last_build_ms[4] = v->last_build_ms[5] = 0;  // [3] kept for the ABI; [4] / [5]: the plan's first launch
   *out = np.get();
   v->plans.push_back(std::move(np));
   *built = true;
   return PIPER_HIP_OK;
 }
 
+// The bounded prepare's encoder + predictor plan of slot id `slot` goes idle (it keeps its stream set, see detach).
+void release_dp(piper_hip_voice* v, int slot) {
+  if (v->attached_dp[slot]) v->attached_dp[slot]->in_use = false;
+  v->attached_dp[slot] = nullptr;
+}
+
 void detach(piper_hip_voice* v, int slot) {
   Slot* p = v->attached[slot];
   if (!p) return;
-  if (p->stream) (void)hipStreamSynchronize(p->stream);  // its last launch may still be running / reading the inputs
+  if (p->set.stream) (void)hipStreamSynchronize(p->set.stream);  // its last launch may still be running / reading the inputs
   p->in_use = false;
   p->st_next = -1;
   p->bounded_pending = false;
   v->attached[slot] = nullptr;
-  if (v->attached_dp[slot]) {  // ran on p's stream (bounded prepare): idle now
-    v->attached_dp[slot]->in_use = false;
-    v->attached_dp[slot] = nullptr;
+  release_dp(v, slot);  // ran on p's stream: idle now
+  give_back_set(v, *p);
+}
+
+// The plan of bucket (kind, T, F, NB) on slot id `slot`: the one attached already if it matches, otherwise the attached one is detached and
+// the bucket's plan is taken from the cache (or built) and attached. Then, if `evict`, idle plans beyond the cache's bounds go.
+int attach_plan(piper_hip_voice* v, int slot, int kind, int T, int F, int NB, Slot** out, bool evict = true) {
+  Slot* cur = v->attached[slot];
+  if (!(cur && cur->built && cur->kind == kind && cur->T == T && cur->F == F && cur->NB == NB && cur->prec == v->precision)) {
+    if (cur) detach(v, slot);
+    bool built = false;
+    const int rc = acquire_plan(v, kind, T, F, NB, &cur, &built);
+    if (rc) return rc;
+    cur->in_use = true;
+    v->attached[slot] = cur;
+    if (evict) evict_idle_plans(v);
   }
-  // An idle plan needs no stream: hand the set to the next plan that is attached (usually the one replacing this plan on the same
-  // slot id), so that after a slot id's first request no prepare ever creates a stream again (≈ 3 ms each, r3).
-  if (p->inited && p->stream) {
-    v->free_sets.push_back({p->stream, {p->side[0], p->side[1]}, p->ev0, p->ev1, p->ev_fork, {p->ev_join[0], p->ev_join[1]}});
-    p->stream = nullptr; p->side[0] = p->side[1] = nullptr; p->ev0 = p->ev1 = p->ev_fork = nullptr; p->ev_join[0] = p->ev_join[1] = nullptr;
-    p->inited = false;
-  }
+  *out = cur;
+  return PIPER_HIP_OK;
 }
 
 }  // namespace
 
 namespace {
 int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out);
+// Page-locked staging `p` of `cap` elements, grown (contents dropped) to hold `need`: `min_cap` elements or a power of two times that.
+// On failure p is null and cap 0.
 template <typename Tp>
-int grow_pinned(Tp*& p, size_t& cap, size_t need) {
+int grow_pinned(Tp*& p, size_t& cap, size_t need, size_t min_cap = 1024) {
   if (cap >= need) return PIPER_HIP_OK;
   if (p) (void)hipHostFree(p);
   p = nullptr; cap = 0;
-  size_t c = 1024;
+  size_t c = min_cap;
   while (c < need) c <<= 1;
   PH_HIP(hipHostMalloc((void**)&p, c * sizeof(Tp)), PIPER_HIP_ERR_ALLOC);
   cap = c;
@@ -2156,8 +2228,8 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     if (any_null) {
       int64_t total = 0;
       for (int b = 0; b < n; b++) {
-        if (utts[b].t < 1 || utts[b].t > 4096) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: bad phoneme count", b);
-        if (!utts[b].durations && utts[b].noise)  // the refusal check_utt makes: here the durations are still NULL, below they are the predicted ones
+        if ((rc = check_item(utts[b], b))) return rc;
+        if (!utts[b].durations && utts[b].noise)  // the refusal utt_frames makes: here the durations are still NULL, below they are the predicted ones
           PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: noise given but durations are NULL — its [inter, F] shape depends on the predicted durations: call "
                                      "piper_hip_voice_predict_durations first and pass durations + noise, or use noise_mode = DEVICE", b);
         total += utts[b].t;
@@ -2180,9 +2252,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   }
   for (int b = 0; b < n; b++) {
     int64_t Fb = 0;
-    if ((rc = check_utt(v, &utts[b], &Fb))) return rc;
-    if (utts[b].noise_mode != PIPER_HIP_NOISE_INJECTED && utts[b].noise_mode != PIPER_HIP_NOISE_DEVICE)
-      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: unknown noise_mode %d", b, utts[b].noise_mode);
+    if ((rc = check_item(utts[b], b)) || (rc = utt_frames(v, utts[b], b, &Fb))) return rc;
     hT[b] = utts[b].t;
     hF[b] = (int)Fb;
     Tmax = std::max(Tmax, utts[b].t);
@@ -2191,110 +2261,73 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   const int T = bucket_t(Tmax), F = bucket_f((int)Fmax), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  Slot* cur = v->attached[slot];
   const int kind = (dp_plan && dp_plan->stats && dp_plan->T == T && dp_plan->NB == n) ? 3 : 0;
-  const bool same = cur && cur->built && cur->kind == kind && cur->T == T && cur->F == F && cur->NB == n && cur->prec == v->precision;
-  if (cur && !same) detach(v, slot);
-  if (!same) {
-    bool built = false;
-    if ((rc = acquire_plan(v, kind, T, F, n, &cur, &built))) return rc;
-    cur->in_use = true;
-    v->attached[slot] = cur;
-    evict_idle_plans(v);
-  }
+  Slot* cur = nullptr;
+  if ((rc = attach_plan(v, slot, kind, T, F, n, &cur))) return rc;
   Slot& s = *cur;
+  const hipStream_t q = s.set.stream;
   s.last_use = ++v->use_clock;
   // the previous launch on this plan may still be reading the inputs
-  PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);
   s.bounded_pending = false;
-  if (v->attached_dp[slot]) { v->attached_dp[slot]->in_use = false; v->attached_dp[slot] = nullptr; }
+  release_dp(v, slot);
   if (kind == 3)  // the predictor's plan has finished (predict synchronises): its projection becomes this plan's input
   {
-    PH_HIP(hipMemcpyAsync(s.stats, dp_plan->stats, (size_t)n * 2 * I * T * sizeof(float), hipMemcpyDeviceToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipMemcpyAsync(s.stats, dp_plan->stats, (size_t)n * 2 * I * T * sizeof(float), hipMemcpyDeviceToDevice, q), PIPER_HIP_ERR_LAUNCH);
     // the predictor plan goes back to the cache when this function returns: whatever runs on it next must not overwrite the
     // projection before this copy has read it
     if (!s.ev_in) PH_HIP(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipEventRecord(s.ev_in, s.stream), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipStreamWaitEvent(dp_plan->stream, s.ev_in, 0), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipEventRecord(s.ev_in, q), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipStreamWaitEvent(dp_plan->set.stream, s.ev_in, 0), PIPER_HIP_ERR_LAUNCH);
   }
   s.st_next = -1;
   s.h_T = hT;
   s.h_F = hF;
-  {
-    auto& sg = v->staging[slot];
-    auto grow = [](size_t need) { size_t c = 1024; while (c < need) c <<= 1; return c; };
-    if (sg.cap_t < (size_t)T * n) {
-      if (sg.h_ids) (void)hipHostFree(sg.h_ids);
-      sg.h_ids = nullptr; sg.cap_t = 0;
-      const size_t c = grow((size_t)T * n);
-      PH_HIP(hipHostMalloc((void**)&sg.h_ids, c * sizeof(int64_t)), PIPER_HIP_ERR_ALLOC);
-      sg.cap_t = c;
-    }
-    if (sg.cap_f < (size_t)F * n) {
-      if (sg.h_f2i) (void)hipHostFree(sg.h_f2i);
-      sg.h_f2i = nullptr; sg.cap_f = 0;
-      const size_t c = grow((size_t)F * n);
-      PH_HIP(hipHostMalloc((void**)&sg.h_f2i, c * sizeof(int32_t)), PIPER_HIP_ERR_ALLOC);
-      sg.cap_f = c;
-    }
-    if (sg.cap_lens < (size_t)2 * n) {
-      if (sg.h_lens) (void)hipHostFree(sg.h_lens);
-      sg.h_lens = nullptr; sg.cap_lens = 0;
-      const size_t c = grow((size_t)2 * n);
-      PH_HIP(hipHostMalloc((void**)&sg.h_lens, c * sizeof(int)), PIPER_HIP_ERR_ALLOC);
-      sg.cap_lens = c;
-    }
-    s.h_ids = sg.h_ids; s.h_f2i = sg.h_f2i; s.h_lens = sg.h_lens;  // borrowed for this request (the plan's stream was synchronised above)
-  }
-  s.h_noise_scale.resize(n);
-  s.h_rng.resize(2 * (size_t)n);
   s.h_dur.clear();
-  // Everything that goes to the device leaves from page-locked memory of the slot id: an asynchronous copy from PAGEABLE memory makes the
-  // runtime pin (or stage) the caller's pages on the spot. The noise tensor is copied into bucket rows here, on the host.
-  auto& sgp = v->staging[slot];
-  {
-    size_t noise_floats = 0;
-    for (int b = 0; b < n; b++) if (utts[b].noise) noise_floats = (size_t)n * I * F;
-    if (noise_floats && (rc = grow_pinned(sgp.h_noise, sgp.cap_noise, noise_floats))) return rc;
-    if ((rc = grow_pinned(sgp.h_misc, sgp.cap_misc, (size_t)n * (2 * sizeof(unsigned) + sizeof(float)) + 64))) return rc;
-  }
-  unsigned* p_rng = (unsigned*)sgp.h_misc;
+  // Everything that goes to the device leaves from page-locked memory of the slot id (the plan's stream was synchronised above): an
+  // asynchronous copy from PAGEABLE memory makes the runtime pin (or stage) the caller's pages on the spot. The noise tensor is copied into
+  // bucket rows here, on the host.
+  auto& sg = v->staging[slot];
+  bool any_noise = false;
+  for (int b = 0; b < n; b++) any_noise = any_noise || utts[b].noise;
+  if ((rc = grow_pinned(sg.h_ids, sg.cap_t, (size_t)T * n)) || (rc = grow_pinned(sg.h_f2i, sg.cap_f, (size_t)F * n)) ||
+      (rc = grow_pinned(sg.h_lens, sg.cap_lens, (size_t)2 * n)) || (any_noise && (rc = grow_pinned(sg.h_noise, sg.cap_noise, (size_t)n * I * F))) ||
+      (rc = grow_pinned(sg.h_misc, sg.cap_misc, (size_t)n * (2 * sizeof(unsigned) + sizeof(float)) + 64)))
+    return rc;
+  unsigned* p_rng = (unsigned*)sg.h_misc;
   float* p_ns = (float*)(p_rng + 2 * (size_t)n);
+  pack_ids(utts, n, T, sg.h_ids);
   for (int b = 0; b < n; b++) {
     const piper_hip_utterance* u = &utts[b];
     const int Tb = hT[b], Fb = hF[b];
     s.h_dur.insert(s.h_dur.end(), u->durations, u->durations + Tb);
-    s.h_lens[b] = Tb;
-    s.h_lens[n + b] = Fb;
-    s.h_rng[2 * b] = (!u->noise && u->noise_mode == PIPER_HIP_NOISE_DEVICE) ? 1u : 0u;
-    s.h_rng[2 * b + 1] = u->seed;
-    memcpy(s.h_ids + (size_t)b * T, u->phoneme_ids, (size_t)Tb * sizeof(int64_t));
-    for (int t = Tb; t < T; t++) s.h_ids[(size_t)b * T + t] = 0;  // rows of the bucket beyond the utterance: any legal id
+    sg.h_lens[b] = Tb;
+    sg.h_lens[n + b] = Fb;
     int f = 0;  // generate_path: frame f belongs to the phoneme whose cumulative duration covers it
     for (int t = 0; t < Tb; t++)
-      for (int j = 0; j < u->durations[t]; j++) s.h_f2i[(size_t)b * F + f++] = t;
-    for (; f < F; f++) s.h_f2i[(size_t)b * F + f] = 0;
-    s.h_noise_scale[b] = u->noise_scale;
-    // noise [I, Fb] → rows of the bucket [I, F]
-    p_rng[2 * b] = s.h_rng[2 * b]; p_rng[2 * b + 1] = s.h_rng[2 * b + 1];
+      for (int j = 0; j < u->durations[t]; j++) sg.h_f2i[(size_t)b * F + f++] = t;
+    for (; f < F; f++) sg.h_f2i[(size_t)b * F + f] = 0;
+    p_rng[2 * b] = (!u->noise && u->noise_mode == PIPER_HIP_NOISE_DEVICE) ? 1u : 0u;
+    p_rng[2 * b + 1] = u->seed;
     p_ns[b] = u->noise_scale;
+    // noise [I, Fb] → rows of the bucket [I, F]
     if (u->noise) {
-      float* hb = sgp.h_noise + (size_t)b * I * F;
+      float* hb = sg.h_noise + (size_t)b * I * F;
       for (int c = 0; c < I; c++) {
         memcpy(hb + (size_t)c * F, u->noise + (size_t)c * Fb, (size_t)Fb * sizeof(float));
         if (Fb < F) memset(hb + (size_t)c * F + Fb, 0, (size_t)(F - Fb) * sizeof(float));
       }
-      PH_HIP(hipMemcpyAsync(s.noise + (size_t)b * I * F, hb, (size_t)I * F * sizeof(float), hipMemcpyHostToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
-    } else if (!s.h_rng[2 * b])
-      PH_HIP(hipMemsetAsync(s.noise + (size_t)b * I * F, 0, (size_t)I * F * sizeof(float), s.stream), PIPER_HIP_ERR_LAUNCH);
+      PH_HIP(hipMemcpyAsync(s.noise + (size_t)b * I * F, hb, (size_t)I * F * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+    } else if (!p_rng[2 * b])
+      PH_HIP(hipMemsetAsync(s.noise + (size_t)b * I * F, 0, (size_t)I * F * sizeof(float), q), PIPER_HIP_ERR_LAUNCH);
   }
-  PH_HIP(hipMemcpyAsync(s.rng, p_rng, 2 * (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.noise_scale, p_ns, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.ids, s.h_ids, (size_t)T * n * sizeof(int64_t), hipMemcpyHostToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.frame2id, s.h_f2i, (size_t)F * n * sizeof(int32_t), hipMemcpyHostToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.lensT, s.h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.lensF, s.h_lens + n, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);  // noise / scalars come from caller memory
+  PH_HIP(hipMemcpyAsync(s.rng, p_rng, 2 * (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.noise_scale, p_ns, (size_t)n * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.ids, sg.h_ids, (size_t)T * n * sizeof(int64_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.frame2id, sg.h_f2i, (size_t)F * n * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.lensT, sg.h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.lensF, sg.h_lens + n, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);  // noise / scalars come from caller memory
   s.timed = false;
   return slot;
 }
@@ -2364,36 +2397,28 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
   if (max_frames < 1 || (int64_t)max_frames * std::max(v->hop, 1) > 0x3fffffff / 64) PH_FAIL(PIPER_HIP_ERR_SHAPE, "prepare_batch_bounded: max_frames %d out of range", max_frames);
   if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0): supply durations");
-  int Tmax = 0;
+  int Tmax = 0, rc;
   for (int b = 0; b < n; b++) {
     const piper_hip_utterance& u = utts[b];
-    if (!u.phoneme_ids) PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: null ids", b);
-    if (u.t < 1 || u.t > 4096) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: %d ids outside [1,4096]", b, u.t);
+    if ((rc = check_item(u, b))) return rc;
     if (u.durations || u.noise)
       PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: prepare_batch_bounded predicts the durations and cannot take a host noise tensor (its shape depends "
                                  "on them): pass durations = noise = NULL (noise_mode DEVICE draws it on the device)", b);
-    if (u.noise_mode != PIPER_HIP_NOISE_INJECTED && u.noise_mode != PIPER_HIP_NOISE_DEVICE)
-      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: unknown noise_mode %d", b, u.noise_mode);
     Tmax = std::max(Tmax, u.t);
   }
   const int T = bucket_t(Tmax), F = bucket_f(max_frames), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  int rc;
-  Slot* cur = v->attached[slot];
-  const bool same = cur && cur->built && cur->kind == 3 && cur->T == T && cur->F == F && cur->NB == n && cur->prec == v->precision;
-  if (cur && !same) detach(v, slot);
-  if (!same) {
-    bool built = false;
-    if ((rc = acquire_plan(v, 3, T, F, n, &cur, &built))) return rc;
-    cur->in_use = true;
-    v->attached[slot] = cur;
-  }
+  Slot* cur = nullptr;
+  if ((rc = attach_plan(v, slot, 3, T, F, n, &cur, false))) return rc;
   Slot& s = *cur;
   s.last_use = ++v->use_clock;
-  PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);  // the previous request of this slot id: its staging and its predictor plan are idle now
+  PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);  // the previous request of this slot id: its staging and its predictor plan are idle now
   Slot* dp = v->attached_dp[slot];
-  if (dp && !(dp->built && dp->T == T && dp->NB == n && dp->prec == v->precision)) { dp->in_use = false; dp = v->attached_dp[slot] = nullptr; }
+  if (dp && !(dp->built && dp->T == T && dp->NB == n && dp->prec == v->precision)) {
+    release_dp(v, slot);
+    dp = nullptr;
+  }
   if (!dp) {
     bool built = false;
     if ((rc = acquire_plan(v, 2, T, 16, n, &dp, &built))) return rc;
@@ -2401,7 +2426,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
     v->attached_dp[slot] = dp;
   }
   dp->last_use = s.last_use;
-  evict_idle_plans(v);
+  evict_idle_plans(v);  // only now: neither plan can be evicted between the two acquires
   auto& sg = v->staging[slot];
   const size_t misc_bytes = (size_t)n * (sizeof(int) + 2 * sizeof(unsigned) + sizeof(float)) + dp_scalars_bytes(n);
   if ((rc = grow_pinned(sg.h_ids, sg.cap_t, (size_t)T * n)) || (rc = grow_pinned(sg.h_misc, sg.cap_misc, misc_bytes)) ||
@@ -2411,26 +2436,17 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   unsigned* h_rng = (unsigned*)(h_lens + n);
   float* h_ns = (float*)(h_rng + 2 * n);
   char* h_sc = (char*)(h_ns + n);
-  bool any_noise = false;
+  pack_ids(utts, n, T, sg.h_ids);
+  pack_dp_inputs(utts, n, T, sg.h_dpn, h_sc);
   for (int b = 0; b < n; b++) {
     const piper_hip_utterance& u = utts[b];
-    memcpy(sg.h_ids + (size_t)b * T, u.phoneme_ids, (size_t)u.t * sizeof(int64_t));
-    for (int t = u.t; t < T; t++) sg.h_ids[(size_t)b * T + t] = 0;
     h_lens[b] = u.t;
-    const bool dev = u.noise_mode == PIPER_HIP_NOISE_DEVICE;
-    h_rng[2 * b] = dev ? 1u : 0u;
+    h_rng[2 * b] = u.noise_mode == PIPER_HIP_NOISE_DEVICE ? 1u : 0u;
     h_rng[2 * b + 1] = u.seed;
     h_ns[b] = u.noise_scale;
-    for (int r = 0; r < 2; r++) {
-      float* row = sg.h_dpn + ((size_t)b * 2 + r) * T;
-      if (u.dp_noise) { memcpy(row, u.dp_noise + (size_t)r * u.t, (size_t)u.t * sizeof(float)); any_noise = true; }
-      for (int t = u.dp_noise ? u.t : 0; t < T; t++) row[t] = 0.0f;
-    }
-    dp_scalars_fill(h_sc, b, u.noise_w, u.length_scale == 0.0f ? 1.0f : u.length_scale, (!u.dp_noise && dev) ? 1u : 0u, u.seed);
     sg.h_res[b] = -1;
   }
-  (void)any_noise;
-  const hipStream_t q = s.stream;
+  const hipStream_t q = s.set.stream;
   PH_HIP(hipMemcpyAsync(dp->ids, sg.h_ids, (size_t)n * T * sizeof(int64_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(dp->lensT, h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(dp->dp_noise, sg.h_dpn, (size_t)n * 2 * T * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
@@ -2489,9 +2505,6 @@ __global__ __launch_bounds__(256) void copy_out_len_kernel(const float* __restri
 }
 }  // namespace
 
-namespace {
-int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out);
-}
 PH_EXPORT int piper_hip_voice_predict_durations(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out,
                                                 int max_entries) {
   return predict_impl(v, utts, n, durations_out, logw_out, max_entries, nullptr);
@@ -2503,13 +2516,10 @@ int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int
   if (!v || !utts || !durations_out) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0)");
-  int Tmax = 0;
+  int Tmax = 0, rc;
   int64_t total = 0;
   for (int b = 0; b < n; b++) {
-    if (!utts[b].phoneme_ids) PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: null ids", b);
-    if (utts[b].t < 1 || utts[b].t > 4096) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: %d ids outside [1,4096]", b, utts[b].t);
-    if (utts[b].noise_mode != PIPER_HIP_NOISE_INJECTED && utts[b].noise_mode != PIPER_HIP_NOISE_DEVICE)
-      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: unknown noise_mode %d", b, utts[b].noise_mode);
+    if ((rc = check_item(utts[b], b))) return rc;
     Tmax = std::max(Tmax, utts[b].t);
     total += utts[b].t;
   }
@@ -2518,36 +2528,27 @@ int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int
   const int T = bucket_t(Tmax);
   Slot* pl = nullptr;
   bool built = false;
-  int rc = acquire_plan(v, 2, T, 16, n, &pl, &built);
-  if (rc) return rc;
+  if ((rc = acquire_plan(v, 2, T, 16, n, &pl, &built))) return rc;
   Slot& s = *pl;
   s.in_use = true;
   s.last_use = ++v->use_clock;
-  std::vector<int64_t> ids((size_t)n * T, 0);
+  std::vector<int64_t> ids((size_t)n * T);
   std::vector<int> lens(n);
-  std::vector<float> nz((size_t)n * 2 * T, 0.0f);
+  std::vector<float> nz((size_t)n * 2 * T);
   std::vector<char> sc(dp_scalars_bytes(n));
-  for (int b = 0; b < n; b++) {
-    const piper_hip_utterance& u = utts[b];
-    memcpy(ids.data() + (size_t)b * T, u.phoneme_ids, (size_t)u.t * sizeof(int64_t));
-    lens[b] = u.t;
-    if (u.dp_noise)
-      for (int r = 0; r < 2; r++) memcpy(nz.data() + ((size_t)b * 2 + r) * T, u.dp_noise + (size_t)r * u.t, (size_t)u.t * sizeof(float));
-    // device mode draws element (row, t) of the item's OWN [1, 2, T_b] tensor: the kernel indexes the bucket row, so the draw
-    // index must be remapped when T_b < T — done by generating on the host side of the index: see dp_init_kernel (uses T).
-    dp_scalars_fill(sc.data(), b, u.noise_w, u.length_scale == 0.0f ? 1.0f : u.length_scale,
-                    (!u.dp_noise && u.noise_mode == PIPER_HIP_NOISE_DEVICE) ? 1u : 0u, u.seed);
-  }
-  hipError_t e = hipMemcpyAsync(s.ids, ids.data(), ids.size() * sizeof(int64_t), hipMemcpyHostToDevice, s.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s.lensT, lens.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s.dp_noise, nz.data(), nz.size() * sizeof(float), hipMemcpyHostToDevice, s.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s.dp_scalars, sc.data(), sc.size(), hipMemcpyHostToDevice, s.stream);
+  pack_ids(utts, n, T, ids.data());
+  pack_dp_inputs(utts, n, T, nz.data(), sc.data());
+  for (int b = 0; b < n; b++) lens[b] = utts[b].t;
+  hipError_t e = hipMemcpyAsync(s.ids, ids.data(), ids.size() * sizeof(int64_t), hipMemcpyHostToDevice, s.set.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.lensT, lens.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s.set.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.dp_noise, nz.data(), nz.size() * sizeof(float), hipMemcpyHostToDevice, s.set.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.dp_scalars, sc.data(), sc.size(), hipMemcpyHostToDevice, s.set.stream);
   if (e == hipSuccess && launch_plan(v, s)) e = hipErrorUnknown;
   std::vector<int32_t> dur((size_t)n * T);
   std::vector<float> lw(logw_out ? (size_t)n * T : 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(dur.data(), s.dp_dur, dur.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream);
-  if (e == hipSuccess && logw_out) e = hipMemcpyAsync(lw.data(), s.taps["logw"].p, lw.size() * sizeof(float), hipMemcpyDeviceToHost, s.stream);
-  if (e == hipSuccess) e = stream_wait(s.stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dur.data(), s.dp_dur, dur.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s.set.stream);
+  if (e == hipSuccess && logw_out) e = hipMemcpyAsync(lw.data(), s.taps["logw"].p, lw.size() * sizeof(float), hipMemcpyDeviceToHost, s.set.stream);
+  if (e == hipSuccess) e = stream_wait(s.set.stream);
   if (plan_out && e == hipSuccess) *plan_out = pl;  // stays in_use: see above
   else s.in_use = false;
   evict_idle_plans(v);
@@ -2644,12 +2645,12 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *p;
-  PH_HIP(hipEventRecord(s.ev0, s.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipEventRecord(s.set.ev0, s.set.stream), PIPER_HIP_ERR_LAUNCH);
   {
     const int lrc = launch_plan(v, s);
     if (lrc) return lrc;
   }
-  PH_HIP(hipEventRecord(s.ev1, s.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);
   s.timed = true;
   return PIPER_HIP_OK;
 }
@@ -2660,6 +2661,10 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *p;
+  auto& sg = v->staging[slot];
+  // The slot id's page-locked landing buffer of the waveform (16 Ki floats = 64 KiB at least). Failing to grow it is not fatal: the waveform
+  // then goes to the caller's buffer directly, and the sticky error of the failed hipHostMalloc is cleared (the next launch would report it).
+  constexpr size_t kAudioMinCap = (size_t)16 << 10;
   if (s.bounded_pending) {
     // lengths still on the device. Short buckets: the waveform rows go to the slot id's page-locked buffer at bucket stride by a kernel that
     // reads each length from device memory — ONE synchronisation for lengths and samples; long ones: synchronise, then the usual copy.
@@ -2668,27 +2673,19 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     if (host_audio && max_samples < row * s.NB)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_prepared_samples before collect), got %lld",
               (long long)(row * s.NB), (long long)max_samples);
-    auto& sg = v->staging[slot];
     float* dst_dev = nullptr;
     if (host_audio && ub <= ((size_t)1 << 20) && (v->hop & 3) == 0) {
-      if (sg.audio_cap < ub) {
-        if (sg.h_audio) (void)hipHostFree(sg.h_audio);
-        sg.h_audio = nullptr; sg.audio_cap = 0;
-        size_t c = 65536;
-        while (c < ub) c <<= 1;
-        if (hipHostMalloc((void**)&sg.h_audio, c) == hipSuccess) sg.audio_cap = c;
-        else { sg.h_audio = nullptr; (void)hipGetLastError(); }
-      }
+      if (grow_pinned(sg.h_audio, sg.audio_cap, (size_t)row * s.NB, kAudioMinCap)) (void)hipGetLastError();
       if (sg.h_audio && hipHostGetDevicePointer((void**)&dst_dev, sg.h_audio, 0) != hipSuccess) { dst_dev = nullptr; (void)hipGetLastError(); }
     }
     if (dst_dev) {
       for (int b = 0; b < s.NB; b++) {
         const int blocks = (int)std::min<int64_t>((row + 4 * 256 - 1) / (4 * 256), 1024);
-        hipLaunchKernelGGL(copy_out_len_kernel, dim3(blocks), dim3(256), 0, s.stream, s.audio + (int64_t)b * s.n_samples, dst_dev + (int64_t)b * row, s.lensF, b, v->hop);
+        hipLaunchKernelGGL(copy_out_len_kernel, dim3(blocks), dim3(256), 0, s.set.stream, s.audio + (int64_t)b * s.n_samples, dst_dev + (int64_t)b * row, s.lensF, b, v->hop);
         PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
       }
     }
-    PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
     const int frc = bounded_finish(v, slot, s);
     if (frc) return frc;
     if (dst_dev) {
@@ -2724,20 +2721,9 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
       if (hipPointerGetAttributes(&at, host_audio) == hipSuccess) caller_pinned = at.type == hipMemoryTypeHost;
       else (void)hipGetLastError();
     }
-    {
-      auto& sg = v->staging[slot];
-      if (!caller_pinned && bytes <= kChunkedMax && sg.audio_cap < bytes) {
-        if (sg.h_audio) (void)hipHostFree(sg.h_audio);
-        sg.h_audio = nullptr; sg.audio_cap = 0;
-        size_t c = 65536;
-        while (c < bytes) c <<= 1;
-        if (hipHostMalloc((void**)&sg.h_audio, c) == hipSuccess) sg.audio_cap = c;
-        else { sg.h_audio = nullptr; (void)hipGetLastError(); }
-      }
-      s.h_audio = sg.audio_cap >= bytes ? sg.h_audio : nullptr;
-    }
-    if (!caller_pinned && bytes > kPinnedMax && bytes <= kChunkedMax && s.h_audio) {
-      auto& sg = v->staging[slot];
+    if (!caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap)) (void)hipGetLastError();
+    float* h_audio = sg.audio_cap >= (size_t)total ? sg.h_audio : nullptr;
+    if (!caller_pinned && bytes > kPinnedMax && bytes <= kChunkedMax && h_audio) {
       // the items back to back in the staging buffer, cut into chunks; `cuts` = end offset (floats) of each chunk
       std::vector<int64_t> cuts;
       int64_t off = 0;
@@ -2746,14 +2732,14 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
         const float* src = s.audio + (int64_t)b * s.n_samples;
         for (int64_t c0 = 0; c0 < nb; c0 += (int64_t)(kChunk / sizeof(float))) {
           const int64_t cn = std::min<int64_t>((int64_t)(kChunk / sizeof(float)), nb - c0);
-          PH_HIP(hipMemcpyAsync(s.h_audio + off + c0, src + c0, (size_t)cn * sizeof(float), hipMemcpyDeviceToHost, s.stream), PIPER_HIP_ERR_LAUNCH);
+          PH_HIP(hipMemcpyAsync(h_audio + off + c0, src + c0, (size_t)cn * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
           const size_t k = cuts.size();
           if (sg.chunk_ev.size() <= k) {
             hipEvent_t e = nullptr;
             PH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
             sg.chunk_ev.push_back(e);
           }
-          PH_HIP(hipEventRecord(sg.chunk_ev[k], s.stream), PIPER_HIP_ERR_LAUNCH);
+          PH_HIP(hipEventRecord(sg.chunk_ev[k], s.set.stream), PIPER_HIP_ERR_LAUNCH);
           cuts.push_back(off + c0 + cn);
         }
         off += nb;
@@ -2767,12 +2753,12 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
           (void)hipGetLastError();
           for (int i = 0; i < 16; i++) __builtin_ia32_pause();
         }
-        memcpy(host_audio + done, s.h_audio + done, (size_t)(cuts[k] - done) * sizeof(float));
+        memcpy(host_audio + done, h_audio + done, (size_t)(cuts[k] - done) * sizeof(float));
         done = cuts[k];
       }
       return PIPER_HIP_OK;
     }
-    float* dst = (!caller_pinned && bytes <= kPinnedMax && s.h_audio) ? s.h_audio : host_audio;
+    float* dst = (!caller_pinned && bytes <= kPinnedMax && h_audio) ? h_audio : host_audio;
     // Short waveforms into page-locked memory are written by a KERNEL through the host mapping instead of the copy engine: the
     // hand-over from the last kernel of the graph to another kernel costs ≈ 2 µs, to the DMA engine ≈ 10 µs (PIPER_HIP_COLLECT_DMA=1:
     // always the copy engine).
@@ -2780,7 +2766,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     float* dst_dev = nullptr;
     // (a destination the caller page-locked takes the copy kernel up to 16 MB: the engine's hand-over and completion varied 0.07 … 0.3 ms
     // from process to process on a 2.75 MB waveform, r3)
-    if (!dma_only && (caller_pinned ? bytes <= kChunkedMax : bytes <= kPinnedMax) && (caller_pinned || dst == s.h_audio)) {
+    if (!dma_only && (caller_pinned ? bytes <= kChunkedMax : bytes <= kPinnedMax) && (caller_pinned || dst == h_audio)) {
       if (hipHostGetDevicePointer((void**)&dst_dev, dst, 0) != hipSuccess) { dst_dev = nullptr; (void)hipGetLastError(); }
     }
     int64_t off = 0;
@@ -2789,21 +2775,21 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
       const float* src = s.audio + (int64_t)b * s.n_samples;
       if (dst_dev && nb > 0) {
         const int blocks = (int)std::min<int64_t>((nb + 4 * 256 - 1) / (4 * 256), 1024);
-        hipLaunchKernelGGL(copy_out_kernel, dim3(blocks), dim3(256), 0, s.stream, src, dst_dev + off, nb);
+        hipLaunchKernelGGL(copy_out_kernel, dim3(blocks), dim3(256), 0, s.set.stream, src, dst_dev + off, nb);
         PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
       } else {
-        PH_HIP(hipMemcpyAsync(dst + off, src, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, s.stream), PIPER_HIP_ERR_LAUNCH);
+        PH_HIP(hipMemcpyAsync(dst + off, src, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
       }
       off += nb;
     }
     // a copy-ENGINE transfer completes through the runtime's own signal handling: polling the stream next to it delayed the completion of a
     // 2.75 MB waveform by ≈ 0.2 ms (factor 64, r3) — park for those, poll only behind the copy kernel
-    if (dst_dev) PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
-    else PH_HIP(hipStreamSynchronize(s.stream), PIPER_HIP_ERR_LAUNCH);
+    if (dst_dev) PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
+    else PH_HIP(hipStreamSynchronize(s.set.stream), PIPER_HIP_ERR_LAUNCH);
     if (dst != host_audio) memcpy(host_audio, dst, bytes);
     return PIPER_HIP_OK;
   }
-  PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
   return PIPER_HIP_OK;
 }
 
@@ -2830,29 +2816,20 @@ int generator_halo_frames(const piper_hip_voice_config& c) {
   return (int)(r + 3);
 }
 
-// graph of the steps selected by `pick` (eager pass first: validates launches and sets kernel attributes)
-int capture_steps(Slot& s, const std::vector<int>& pick, hipGraph_t* g, hipGraphExec_t* ge) {
+int run_steps(Slot& s, const std::vector<int>& pick, hipStream_t q) {
   for (int i : pick) {
-    int rc = s.steps[i].run(s.stream);
+    const int rc = s.steps[i].run(q);
     if (rc) return rc;
-  }
-  PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipStreamBeginCapture(s.stream, hipStreamCaptureModeThreadLocal), PIPER_HIP_ERR_LAUNCH);
-  int rc = PIPER_HIP_OK;
-  for (int i : pick)
-    if ((rc = s.steps[i].run(s.stream))) break;
-  hipError_t ce = hipStreamEndCapture(s.stream, g);
-  if (rc || ce != hipSuccess) {
-    if (*g) { (void)hipGraphDestroy(*g); *g = nullptr; }
-    if (rc) return rc;
-    PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream: graph capture failed: %s", hipGetErrorString(ce));
-  }
-  ce = hipGraphInstantiate(ge, *g, nullptr, nullptr, 0);
-  if (ce != hipSuccess) {
-    (void)hipGraphDestroy(*g); *g = nullptr;
-    PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream: graph instantiate failed: %s", hipGetErrorString(ce));
   }
   return PIPER_HIP_OK;
+}
+
+// graph of the steps selected by `pick` (eager pass first: validates launches and sets kernel attributes)
+int capture_steps(Slot& s, const std::vector<int>& pick, hipGraph_t* g, hipGraphExec_t* ge) {
+  const int rc = run_steps(s, pick, s.set.stream);
+  if (rc) return rc;
+  PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
+  return capture_graph(s.set.stream, [&](hipStream_t q) { return run_steps(s, pick, q); }, g, ge, "stream");
 }
 
 }  // namespace
@@ -2872,8 +2849,8 @@ PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_u
     }
     if ((rc = capture_steps(s, front, &s.front_graph, &s.front_exec))) return rc;
   }
-  PH_HIP(hipGraphLaunch(s.front_exec, s.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipEventRecord(s.ev1, s.stream), PIPER_HIP_ERR_LAUNCH);  // z is ready when ev1 fires
+  PH_HIP(hipGraphLaunch(s.front_exec, s.set.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);  // z is ready when ev1 fires
   s.st_chunk = chunk_frames;
   s.st_halo = generator_halo_frames(v->cfg);
   s.st_next = 0;
@@ -2904,16 +2881,16 @@ PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* h
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
   const int I = v->cfg.inter;
-  hipError_t e = hipStreamWaitEvent(gs->stream, s.ev1, 0);
+  hipError_t e = hipStreamWaitEvent(gs->set.stream, s.set.ev1, 0);
   int lens[2] = {0, Fc};
-  if (e == hipSuccess) e = hipMemcpyAsync(gs->lensF, &lens[1], sizeof(int), hipMemcpyHostToDevice, gs->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(gs->lensF, &lens[1], sizeof(int), hipMemcpyHostToDevice, gs->set.stream);
   if (e == hipSuccess)
     e = hipMemcpy2DAsync(gs->zin, (size_t)gs->F * sizeof(float), s.z_out + a, (size_t)s.F * sizeof(float), (size_t)Fc * sizeof(float), (size_t)I,
-                         hipMemcpyDeviceToDevice, gs->stream);
+                         hipMemcpyDeviceToDevice, gs->set.stream);
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (e == hipSuccess && host_audio)
-    e = hipMemcpyAsync(host_audio, gs->audio + (int64_t)(f0 - a) * v->hop, (size_t)want * sizeof(float), hipMemcpyDeviceToHost, gs->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(gs->stream);
+    e = hipMemcpyAsync(host_audio, gs->audio + (int64_t)(f0 - a) * v->hop, (size_t)want * sizeof(float), hipMemcpyDeviceToHost, gs->set.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(gs->set.stream);
   gs->in_use = false;
   evict_idle_plans(v);
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next: %s", hipGetErrorString(e));
@@ -2948,7 +2925,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
   if (host) {
     if (max_floats < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
     PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-    PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
     size_t off = 0;
     for (int b = 0; b < s.NB; b++) {
       const size_t len = (size_t)(t.unit == 0 ? s.h_T[b] : s.h_F[b]);
@@ -2965,16 +2942,16 @@ PH_EXPORT int piper_hip_voice_last_gpu_ms(piper_hip_voice* v, int slot, double* 
   Slot* sp = slot_plan(v, slot);
   if (!sp || !sp->timed) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no timed launch", slot);
   Slot& s = *sp;
-  PH_HIP(hipEventSynchronize(s.ev1), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipEventSynchronize(s.set.ev1), PIPER_HIP_ERR_LAUNCH);
   float f = 0;
-  PH_HIP(hipEventElapsedTime(&f, s.ev0, s.ev1), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipEventElapsedTime(&f, s.set.ev0, s.set.ev1), PIPER_HIP_ERR_LAUNCH);
   *ms = f;
   return PIPER_HIP_OK;
 }
 
 PH_EXPORT piper_hip_stream piper_hip_voice_slot_stream(piper_hip_voice* v, int slot) {
   Slot* sp = slot_plan(v, slot);
-  return sp ? (piper_hip_stream)sp->stream : nullptr;
+  return sp ? (piper_hip_stream)sp->set.stream : nullptr;
 }
 
 PH_EXPORT int piper_hip_voice_profile(piper_hip_voice* v, int slot, int iters, piper_hip_kernel_stat* out, int max_entries,
@@ -2993,14 +2970,14 @@ PH_EXPORT int piper_hip_voice_profile(piper_hip_voice* v, int slot, int iters, p
                                                         // pass on a fresh box must not poison a row: BENCH_r01 showed a 324 µs enc2.qkv)
   int rc = PIPER_HIP_OK;
   for (int it = 0; it < iters + 1 && !rc; it++) {  // first pass is warm-up
-    hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, s.stream, (unsigned long long)(100 * (1500 + 12 * n)));  // µs → ticks
-    PH_HIP(hipEventRecord(ev[0], s.stream), PIPER_HIP_ERR_LAUNCH);
+    hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, s.set.stream, (unsigned long long)(100 * (1500 + 12 * n)));  // µs → ticks
+    PH_HIP(hipEventRecord(ev[0], s.set.stream), PIPER_HIP_ERR_LAUNCH);
     for (int i = 0; i < n && !rc; i++) {
-      if (s.steps[i].kind == Step::LAUNCH) rc = s.steps[i].run(s.stream);
-      if (!rc && hipEventRecord(ev[i + 1], s.stream) != hipSuccess) rc = PIPER_HIP_ERR_LAUNCH;
+      if (s.steps[i].kind == Step::LAUNCH) rc = s.steps[i].run(s.set.stream);
+      if (!rc && hipEventRecord(ev[i + 1], s.set.stream) != hipSuccess) rc = PIPER_HIP_ERR_LAUNCH;
     }
     if (rc) break;
-    PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
     if (it == 0) continue;
     for (int i = 0; i < n; i++) {
       float ms = 0;
@@ -3013,13 +2990,13 @@ PH_EXPORT int piper_hip_voice_profile(piper_hip_voice* v, int slot, int iters, p
   double floor_us = 0.0;
   if (!rc) {
     const int nf = std::min(32, n);
-    hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, s.stream, (unsigned long long)(100 * 800));
-    if (hipEventRecord(ev[0], s.stream) != hipSuccess) rc = PIPER_HIP_ERR_LAUNCH;
+    hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, s.set.stream, (unsigned long long)(100 * 800));
+    if (hipEventRecord(ev[0], s.set.stream) != hipSuccess) rc = PIPER_HIP_ERR_LAUNCH;
     for (int i = 1; i <= nf && !rc; i++) {
-      hipLaunchKernelGGL(empty_kernel, dim3(1), dim3(64), 0, s.stream);
-      if (hipEventRecord(ev[i], s.stream) != hipSuccess) rc = PIPER_HIP_ERR_LAUNCH;
+      hipLaunchKernelGGL(empty_kernel, dim3(1), dim3(64), 0, s.set.stream);
+      if (hipEventRecord(ev[i], s.set.stream) != hipSuccess) rc = PIPER_HIP_ERR_LAUNCH;
     }
-    if (!rc && nf > 0 && stream_wait(s.stream) == hipSuccess) {
+    if (!rc && nf > 0 && stream_wait(s.set.stream) == hipSuccess) {
       float ms = 0;
       if (hipEventElapsedTime(&ms, ev[0], ev[nf]) == hipSuccess) floor_us = ms * 1000.0 / nf;
     }
@@ -3083,31 +3060,18 @@ PH_EXPORT int piper_hip_voice_time_subset(piper_hip_voice* v, int slot, const ch
     if (avg_launch_us) *avg_launch_us = 0;
     return PIPER_HIP_OK;
   }
-  PH_HIP(stream_wait(s.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
   hipGraph_t g = nullptr;
   hipGraphExec_t ge = nullptr;
-  PH_HIP(hipStreamBeginCapture(s.stream, hipStreamCaptureModeThreadLocal), PIPER_HIP_ERR_LAUNCH);
-  int rc = PIPER_HIP_OK;
-  for (int i : pick)
-    if ((rc = s.steps[i].run(s.stream))) break;
-  hipError_t ce = hipStreamEndCapture(s.stream, &g);
-  if (rc || ce != hipSuccess) {
-    if (g) (void)hipGraphDestroy(g);
-    if (rc) return rc;
-    PH_FAIL(PIPER_HIP_ERR_LAUNCH, "time_subset: capture failed: %s", hipGetErrorString(ce));
-  }
-  ce = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-  if (ce != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    PH_FAIL(PIPER_HIP_ERR_LAUNCH, "time_subset: instantiate failed: %s", hipGetErrorString(ce));
-  }
-  hipError_t e = hipGraphLaunch(ge, s.stream);  // warm-up
-  if (e == hipSuccess) e = hipEventRecord(s.ev0, s.stream);
-  for (int it = 0; it < iters && e == hipSuccess; it++) e = hipGraphLaunch(ge, s.stream);
-  if (e == hipSuccess) e = hipEventRecord(s.ev1, s.stream);
-  if (e == hipSuccess) e = hipEventSynchronize(s.ev1);
+  const int rc = capture_graph(s.set.stream, [&](hipStream_t q) { return run_steps(s, pick, q); }, &g, &ge, "time_subset");
+  if (rc) return rc;
+  hipError_t e = hipGraphLaunch(ge, s.set.stream);  // warm-up
+  if (e == hipSuccess) e = hipEventRecord(s.set.ev0, s.set.stream);
+  for (int it = 0; it < iters && e == hipSuccess; it++) e = hipGraphLaunch(ge, s.set.stream);
+  if (e == hipSuccess) e = hipEventRecord(s.set.ev1, s.set.stream);
+  if (e == hipSuccess) e = hipEventSynchronize(s.set.ev1);
   float ms = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.ev0, s.ev1);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.set.ev0, s.set.ev1);
   (void)hipGraphExecDestroy(ge);
   (void)hipGraphDestroy(g);
   s.timed = false;

@@ -947,7 +947,8 @@ class HipRuntime:
         _check(self.lib.piper_hip_voice_set_plan_cache(self.voice, int(max_plans), int(max_bytes)))
 
     def last_build_breakdown(self):
-        """ms of the phases of the latest plan build (cold prepare): streams, schedule + arena, arena init, eager pass, capture, instantiate."""
+        """ms of the phases of the latest plan build (cold prepare): streams, schedule + arena, arena init, eager_pass (always 0, kept
+        for the ABI), capture and instantiate (0 after the prepare, filled by the plan's first launch)."""
         a = (C.c_double * 6)()
         _check(self.lib.piper_hip_voice_last_build_breakdown(self.voice, a))
         return dict(zip(("streams_events", "schedule_and_arena", "arena_init", "eager_pass", "capture", "instantiate"), (round(x, 3) for x in a)))
