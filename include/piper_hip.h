@@ -476,6 +476,18 @@ int piper_hip_voice_predict_durations(piper_hip_voice* v, const piper_hip_uttera
 int piper_hip_voice_receptive_field(const piper_hip_voice* v);
 int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_utterance* u, int slot, int chunk_frames);
 int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples);
+/* Batched streaming: one slot holds a group of `n` utterances (1 ≤ n ≤ 256, ragged; durations may be NULL = predicted, as in
+ * prepare_batch). The encoder and the flow run once for the whole group; each stream_next_batch then decodes the next `chunk_frames`
+ * of every item still active in ONE generator launch (batch = n rounded up to a power of two; finished, dropped and pad rows have
+ * length 0). Each item's chunks equal what stream_begin / stream_next give for that utterance alone.
+ * stream_begin_batch returns the number of steps (max over items of ceil(F_i / chunk_frames)) or a negative status.
+ * stream_next_batch writes the chunks of the active items back to back in item order into host_audio (at most n · chunk_frames · hop
+ * samples); n_samples[i] (n entries) = samples of item i in this step, 0 once item i is finished or dropped. All zero = end of the
+ * group. stream_next on a slot holding a group of n > 1 returns PIPER_HIP_ERR_ARG.
+ * stream_drop: the client of item `item` went away; later steps skip it. */
+int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames);
+int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples);
+int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item);
 /* prepare + launch + collect: PiperMetalRuntime.synthesize (PiperMetalRuntime.swift:62-80). */
 int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u, float* host_audio,
                                int64_t max_samples, int64_t* n_samples);

@@ -74,6 +74,7 @@ __global__ __launch_bounds__(kBT) void pack_act_c8_kernel(const float* __restric
   const int CB = (C + 7) >> 3;
   const int n = blockIdx.z, cb = blockIdx.y;
   const int Lv = len_ptr ? min(len_ptr[n], L) : L;
+  if (len_ptr && Lv == 0) return;  // a row of length 0 is read by nobody (block-uniform)
   const float* xb = x + ((int64_t)n * C + cb * 8) * L;
   uint4* ab = (uint4*)act + ((int64_t)n * CB + cb) * row + kC8Halo;
   for (int pos = blockIdx.x * kBT + threadIdx.x; pos < L; pos += gridDim.x * kBT) {
@@ -93,6 +94,7 @@ __global__ __launch_bounds__(kBT) void pack_mean3_c8_kernel(const float* __restr
   const int CB = (C + 7) >> 3;
   const int n = blockIdx.z, cb = blockIdx.y;
   const int Lv = len_ptr ? min(len_ptr[n] * len_mul, L) : L;
+  if (len_ptr && Lv == 0) return;  // a row of length 0 is read by nobody (block-uniform)
   const int64_t off = ((int64_t)n * C + cb * 8) * L;
   uint4* ab = (uint4*)act + ((int64_t)n * CB + cb) * row + kC8Halo;
   for (int pos = blockIdx.x * kBT + threadIdx.x; pos < L; pos += gridDim.x * kBT) {
@@ -130,6 +132,8 @@ __global__ __launch_bounds__(kBT) void conv_bf16_kernel(const ConvBf16Multi mult
   const int taps = ct ? p.K / p.ct_stride : p.K;
   const int C16 = p.Cin >> 4, CB = p.Cin >> 3;
   const int n = blockIdx.z % batch;
+  // a row of length 0 (batched streaming: a finished, dropped or pad item) is read by nobody: no work, no stores (block-uniform)
+  if (p.len_ptr && p.len_ptr[n] == 0) return;
   const int nb0 = blockIdx.x * NBC;                              // first column of the block
   const int mt0 = (blockIdx.y * WM + wm) * MTW;                  // first row tile of this wave
   // window: input positions [nb0 + off_min, nb0 + NBC + off_max)

@@ -60,6 +60,7 @@ __global__ __launch_bounds__((MT / MTW) * kWN * 64, 2) void rb_pair_bf16_kernel(
   const int pa = (p.Ka - 1) * p.dila / 2, pb = (p.Kb - 1) * p.dilb / 2;
   const int c0 = blockIdx.x * kColsB;
   const int Lv = p.len_ptr ? min(p.len_ptr[n] * p.len_mul, p.L) : p.L;
+  if (p.len_ptr && Lv == 0) return;  // a row of length 0 (batched streaming) is read by nobody, its image included
   if (c0 >= Lv) {  // nothing anyone reads — except the activation image, whose "zero past the true length" invariant must hold
     if (p.act && c0 < p.L) {
       for (int i = threadIdx.x; i < CB * kColsB; i += BT) {

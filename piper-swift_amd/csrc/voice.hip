@@ -257,6 +257,14 @@ struct Slot {
   hipGraph_t front_graph = nullptr;
   hipGraphExec_t front_exec = nullptr;  // encoder + flow only
   int st_chunk = 0, st_next = -1, st_halo = 0;
+  // batched stream of a full-schedule slot (piper_hip_voice_stream_*_batch): bs_n items (0 = none), the next frame of each, dropped
+  // flags; the per-step descriptor table and the packed chunks live in device buffers of this plan (released with it)
+  int bs_n = 0;
+  std::vector<int> bs_next;
+  std::vector<uint8_t> bs_dropped;
+  int* bs_desc = nullptr;     // [kMaxGroup][kDescInts] device
+  float* bs_pack = nullptr;   // the packed chunks of one step, device
+  size_t bs_pack_cap = 0;     // floats
   int cur_lane = 0;  // lane given to steps added by add_conv
 };
 
@@ -328,6 +336,8 @@ struct piper_hip_voice {
     size_t cap_misc = 0, cap_dpn = 0, cap_res = 0;
     float* h_noise = nullptr;  // the caller's noise tensors, laid out in bucket rows (prepare_batch)
     size_t cap_noise = 0;
+    int* h_desc = nullptr;     // batched stream: the step's descriptor table (one H2D per step)
+    size_t cap_desc = 0;
     std::vector<hipEvent_t> chunk_ev;  // collect, 1 … 16 MB waveforms: one event per 1 MB chunk landed in h_audio
   } staging[kMaxSlots];
   Slot* attached[kMaxSlots] = {};
@@ -625,6 +635,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   if (s.front_exec) { (void)hipGraphExecDestroy(s.front_exec); s.front_exec = nullptr; }
   if (s.front_graph) { (void)hipGraphDestroy(s.front_graph); s.front_graph = nullptr; }
   s.st_next = -1; s.zin = nullptr; s.z_out = nullptr;
+  s.bs_n = 0; s.bs_desc = nullptr; s.bs_pack = nullptr; s.bs_pack_cap = 0;  // (both buffers are in `owned`)
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   for (void* p : s.owned) (void)v->ctx->pool.release(p);
   s.owned.clear();
@@ -2035,6 +2046,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_dpn) (void)hipHostFree(sg.h_dpn);
     if (sg.h_res) (void)hipHostFree(sg.h_res);
     if (sg.h_noise) (void)hipHostFree(sg.h_noise);
+    if (sg.h_desc) (void)hipHostFree(sg.h_desc);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
   for (auto& st : v->free_sets) destroy_set(st);
@@ -2163,6 +2175,7 @@ void detach(piper_hip_voice* v, int slot) {
   if (p->set.stream) (void)hipStreamSynchronize(p->set.stream);  // its last launch may still be running / reading the inputs
   p->in_use = false;
   p->st_next = -1;
+  p->bs_n = 0;
   p->bounded_pending = false;
   v->attached[slot] = nullptr;
   release_dp(v, slot);  // ran on p's stream: idle now
@@ -2281,6 +2294,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     PH_HIP(hipStreamWaitEvent(dp_plan->set.stream, s.ev_in, 0), PIPER_HIP_ERR_LAUNCH);
   }
   s.st_next = -1;
+  s.bs_n = 0;
   s.h_T = hT;
   s.h_F = hF;
   s.h_dur.clear();
@@ -2464,6 +2478,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   hipLaunchKernelGGL(dp_paths_kernel, dim3(n), dim3(256), 0, q, dp->dp_dur, dp->lensT, T, F, std::min(max_frames, F), s.frame2id, s.lensF, rep, n);
   PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
   s.st_next = -1;
+  s.bs_n = 0;
   s.h_T.assign(n, 0);
   for (int b = 0; b < n; b++) s.h_T[b] = utts[b].t;
   s.h_F.assign(n, F);  // capacity until collect has the device's answer
@@ -2836,21 +2851,31 @@ int capture_steps(Slot& s, const std::vector<int>& pick, hipGraph_t* g, hipGraph
 
 PH_EXPORT int piper_hip_voice_receptive_field(const piper_hip_voice* v) { return v ? generator_halo_frames(v->cfg) : -1; }
 
-PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_utterance* u, int slot, int chunk_frames) {
-  if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin: chunk_frames must be >= 1");
-  int rc = piper_hip_voice_prepare(v, u, slot);
-  if (rc < 0) return rc;
-  Slot& s = *v->attached[slot];
-  if (!s.front_exec) {  // encoder + flow as their own graph (everything before the generator's first launch)
+namespace {
+// The prepared slot's encoder + flow as their own graph (everything before the generator's first launch), captured on first use, then
+// launched; z is ready when the plan's ev1 fires. Shared by the single and the batched stream.
+int launch_front(Slot& s) {
+  if (!s.front_exec) {
     std::vector<int> front;
     for (int i = 0; i < (int)s.steps.size(); i++) {
       if (s.steps[i].name.compare(0, 4, "dec.") == 0) break;
       if (s.steps[i].kind == Step::LAUNCH) front.push_back(i);
     }
-    if ((rc = capture_steps(s, front, &s.front_graph, &s.front_exec))) return rc;
+    const int rc = capture_steps(s, front, &s.front_graph, &s.front_exec);
+    if (rc) return rc;
   }
   PH_HIP(hipGraphLaunch(s.front_exec, s.set.stream), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);  // z is ready when ev1 fires
+  PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_utterance* u, int slot, int chunk_frames) {
+  if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin: chunk_frames must be >= 1");
+  int rc = piper_hip_voice_prepare(v, u, slot);
+  if (rc < 0) return rc;
+  Slot& s = *v->attached[slot];
+  if ((rc = launch_front(s))) return rc;
   s.st_chunk = chunk_frames;
   s.st_halo = generator_halo_frames(v->cfg);
   s.st_next = 0;
@@ -2860,6 +2885,7 @@ PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_u
 PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   Slot* sp = slot_plan(v, slot);
+  if (sp && sp->bs_n > 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a group of %d streams: use stream_next_batch", slot, sp->bs_n);
   if (!sp || sp->st_next < 0) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no stream in progress", slot);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *sp;
@@ -2896,6 +2922,200 @@ PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* h
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next: %s", hipGetErrorString(e));
   *n_samples = want;
   s.st_next = f1;
+  return PIPER_HIP_OK;
+}
+
+// ---- batched streaming: a group of n utterances on one slot, the next chunk of every active item in one generator launch ------------
+namespace {
+
+constexpr int kMaxGroup = 256;
+// The per-step descriptor: one row of kDescInts per generator row — source item, window start a, window length Fc (0: finished, dropped
+// or pad row), halo skip (f0 − a)·hop, samples of the chunk, offset of the chunk in the packed output.
+enum { kDescSrc = 0, kDescA, kDescFc, kDescSkip, kDescN, kDescOff, kDescInts };
+
+// z windows of one step → the generator plan's input: row r of zin [NBg][I][Fg] = z[src][:, a .. a + Fc), zero past Fc; lensF[r] = Fc.
+// One thread per 4 frames of one channel, so the loads run along frames (coalesced); float4 loads where the window start is 16-byte
+// aligned (z rows are bucket rows, F % 16 == 0). A row of length 0 writes only its length.
+__global__ __launch_bounds__(256) void stream_window_gather_kernel(const float* __restrict__ z, int F, const int* __restrict__ desc,
+                                                                  float* __restrict__ zin, int* __restrict__ lensF, int I, int Fg) {
+  const int r = blockIdx.y;
+  const int* d = desc + r * kDescInts;
+  const int src = d[kDescSrc], a = d[kDescA], Fc = d[kDescFc];
+  if (blockIdx.x == 0 && threadIdx.x == 0) lensF[r] = Fc;
+  if (Fc == 0) return;
+  const int q4 = Fg >> 2;  // Fg % 16 == 0
+  const int total = I * q4;
+  const float* zr = z + (int64_t)src * I * F + a;
+  float* out = zin + (int64_t)r * I * Fg;
+  const bool vec = (a & 3) == 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int c = i / q4, j = (i - c * q4) * 4;
+    const float* zp = zr + (int64_t)c * F + j;
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (j < Fc) {
+      if (vec) {  // a + j is a multiple of 4 below F (a multiple of 16): all four lie in the row
+        const float4 t = *(const float4*)zp;
+        v.x = t.x; v.y = j + 1 < Fc ? t.y : 0.0f; v.z = j + 2 < Fc ? t.z : 0.0f; v.w = j + 3 < Fc ? t.w : 0.0f;
+      } else {
+        v.x = zp[0];
+        if (j + 1 < Fc) v.y = zp[1];
+        if (j + 2 < Fc) v.z = zp[2];
+        if (j + 3 < Fc) v.w = zp[3];
+      }
+    }
+    *(float4*)(out + (int64_t)c * Fg + j) = v;
+  }
+}
+
+// Each active row's chunk out of the generator plan's audio [NBg][row] (the halo samples dropped), packed back to back.
+__global__ __launch_bounds__(256) void stream_chunk_pack_kernel(const float* __restrict__ audio, int64_t row, const int* __restrict__ desc,
+                                                                float* __restrict__ out) {
+  const int* d = desc + blockIdx.y * kDescInts;
+  const int n = d[kDescN];
+  if (n == 0) return;
+  const float* src = audio + (int64_t)blockIdx.y * row + d[kDescSkip];
+  float* dst = out + d[kDescOff];
+  const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+  if (((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) && (n & 3) == 0) {
+    for (int i = tid; i < (n >> 2); i += nth) ((float4*)dst)[i] = ((const float4*)src)[i];
+  } else {
+    for (int i = tid; i < n; i += nth) dst[i] = src[i];
+  }
+}
+
+// A device buffer of the plan (released with it, see slot_release)
+int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out) {
+  const int rc = v->ctx->pool.alloc(bytes, out);
+  if (rc) return rc;
+  s.owned.push_back(*out);
+  s.arena_bytes += bytes;
+  return PIPER_HIP_OK;
+}
+
+void plan_free(piper_hip_voice* v, Slot& s, void* p, size_t bytes) {
+  auto it = std::find(s.owned.begin(), s.owned.end(), p);
+  if (it == s.owned.end()) return;
+  s.owned.erase(it);
+  s.arena_bytes -= bytes;
+  (void)v->ctx->pool.release(p);
+}
+
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames) {
+  if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  if (n < 1 || n > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: group of %d outside [1,%d]", n, kMaxGroup);
+  if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin_batch: chunk_frames must be >= 1");
+  if ((int64_t)chunk_frames * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: %d × %d frames per step too many", n, chunk_frames);
+  int rc = piper_hip_voice_prepare_batch(v, utts, n, slot);  // encoder (+ predictor) inputs of the whole group on one plan
+  if (rc < 0) return rc;
+  Slot& s = *v->attached[slot];
+  void* p = nullptr;
+  if (!s.bs_desc) {
+    if ((rc = plan_alloc(v, s, (size_t)kMaxGroup * kDescInts * sizeof(int), &p))) return rc;
+    s.bs_desc = (int*)p;
+  }
+  const size_t pack = (size_t)n * chunk_frames * v->hop;
+  if (s.bs_pack_cap < pack) {
+    if (s.bs_pack) plan_free(v, s, s.bs_pack, s.bs_pack_cap * sizeof(float));
+    s.bs_pack = nullptr;
+    s.bs_pack_cap = 0;
+    if ((rc = plan_alloc(v, s, pack * sizeof(float), &p))) return rc;
+    s.bs_pack = (float*)p;
+    s.bs_pack_cap = pack;
+  }
+  if ((rc = launch_front(s))) return rc;
+  s.st_chunk = chunk_frames;
+  s.st_halo = generator_halo_frames(v->cfg);
+  s.bs_n = n;
+  s.bs_next.assign(n, 0);
+  s.bs_dropped.assign(n, 0);
+  int steps = 0;
+  for (int b = 0; b < n; b++) steps = std::max(steps, (int)ceil_div(s.h_F[b], chunk_frames));
+  return steps;
+}
+
+PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
+  if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  Slot* sp = slot_plan(v, slot);
+  if (!sp || sp->bs_n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  Slot& s = *sp;
+  const int n = s.bs_n, hop = v->hop;
+  int NBg = 1;  // the generator's batch: n rounded up to a power of two, fixed for the life of the group
+  while (NBg < n) NBg <<= 1;
+  auto& sg = v->staging[slot];
+  int rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * kDescInts);
+  if (rc) return rc;
+  // the descriptor of this step (the previous step's upload has completed: every step ends with a wait)
+  int* d = sg.h_desc;
+  std::vector<int64_t> got(n, 0);
+  int64_t total = 0;
+  int Fmax = 0;
+  for (int r = 0; r < NBg; r++) {
+    int* e = d + (size_t)r * kDescInts;
+    for (int k = 0; k < kDescInts; k++) e[k] = 0;
+    e[kDescSrc] = r < n ? r : 0;
+    if (r >= n || s.bs_dropped[r] || s.bs_next[r] >= s.h_F[r]) continue;
+    // the window of stream_next: chunk + receptive field, clamped to the utterance
+    const int Ft = s.h_F[r], f0 = s.bs_next[r], f1 = std::min(Ft, f0 + s.st_chunk);
+    const int a = std::max(0, f0 - s.st_halo), b = std::min(Ft, f1 + s.st_halo);
+    e[kDescA] = a;
+    e[kDescFc] = b - a;
+    e[kDescSkip] = (f0 - a) * hop;
+    e[kDescN] = (f1 - f0) * hop;
+    e[kDescOff] = (int)total;
+    got[r] = e[kDescN];
+    total += e[kDescN];
+    Fmax = std::max(Fmax, b - a);
+  }
+  for (int i = 0; i < n; i++) n_samples[i] = 0;
+  if (total == 0) return PIPER_HIP_OK;  // end of the group
+  if (host_audio && max_samples < total)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
+  if ((size_t)total > s.bs_pack_cap) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.bs_pack_cap);
+  constexpr size_t kAudioMinCap = (size_t)16 << 10;
+  if (host_audio && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
+  // generator-only plan of the step's longest window at the group's batch size (rows past their end have length 0)
+  Slot* gs = nullptr;
+  bool built = false;
+  if ((rc = acquire_plan(v, 1, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
+  gs->in_use = true;
+  gs->last_use = ++v->use_clock;
+  const hipStream_t q = gs->set.stream;
+  const int I = v->cfg.inter, Fg = gs->F;
+  hipError_t e = hipStreamWaitEvent(q, s.set.ev1, 0);  // z of the group
+  if (e == hipSuccess) e = hipMemcpyAsync(s.bs_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) {
+    const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (Fg / 4), 256), 64);
+    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, s.z_out, s.F, s.bs_desc, gs->zin, gs->lensF, I, Fg);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
+  if (e == hipSuccess) {
+    const int px = (int)std::min<int64_t>(ceil_div((int64_t)s.st_chunk * hop, 1024), 64);
+    hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.bs_desc, s.bs_pack);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && host_audio) e = hipMemcpyAsync(sg.h_audio, s.bs_pack, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, q);
+  if (e == hipSuccess) e = stream_wait(q);
+  gs->in_use = false;
+  evict_idle_plans(v);
+  if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
+  if (host_audio) memcpy(host_audio, sg.h_audio, (size_t)total * sizeof(float));
+  for (int i = 0; i < n; i++) {
+    n_samples[i] = got[i];
+    if (got[i]) s.bs_next[i] = std::min(s.h_F[i], s.bs_next[i] + s.st_chunk);
+  }
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  Slot* sp = slot_plan(v, slot);
+  if (!sp || sp->bs_n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
+  if (item < 0 || item >= sp->bs_n) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, sp->bs_n);
+  sp->bs_dropped[item] = 1;
   return PIPER_HIP_OK;
 }
 

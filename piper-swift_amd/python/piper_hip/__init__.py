@@ -195,6 +195,9 @@ _PROTOS = {
     "piper_hip_voice_receptive_field": (C.c_int, [c_vp]),
     "piper_hip_voice_stream_begin": (C.c_int, [c_vp, C.POINTER(Utterance), C.c_int, C.c_int]),
     "piper_hip_voice_stream_next": (C.c_int, [c_vp, C.c_int, c_f32p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_begin_batch": (C.c_int, [c_vp, C.POINTER(Utterance), C.c_int, C.c_int, C.c_int]),
+    "piper_hip_voice_stream_next_batch": (C.c_int, [c_vp, C.c_int, c_f32p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_drop": (C.c_int, [c_vp, C.c_int, C.c_int]),
     "piper_hip_memory_stats": (C.c_int, [c_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "piper_hip_memory_trim": (C.c_int, [c_vp]),
     "piper_hip_memory_reserve": (C.c_int, [c_vp, C.c_size_t]),
@@ -919,6 +922,38 @@ class HipRuntime:
             if got.value == 0:
                 return
             yield buf[:got.value].copy()
+
+    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0):
+        """Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
+        noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
+        arrays — the next chunk of every item, empty once the item is finished or dropped (stream_drop)."""
+        n = len(utterances)
+        arr = (Utterance * max(n, 1))()
+        keep = []
+        for i, item in enumerate(utterances):
+            ids, dur, noise = item[:3]
+            u, k = self._utt(ids, dur, noise, noiseScale, **(item[3] if len(item) > 3 else {}))
+            arr[i] = u
+            keep.append(k)
+        steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
+        if steps < 0:
+            _check(steps)
+        buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), np.float32)
+        got = (C.c_int64 * n)()
+        while True:
+            _check(self.lib.piper_hip_voice_stream_next_batch(self.voice, slot, buf.ctypes.data_as(c_f32p), buf.size, got))
+            counts = [int(x) for x in got]
+            if not any(counts):
+                return
+            out, off = [], 0
+            for c in counts:
+                out.append(buf[off:off + c].copy())
+                off += c
+            yield out
+
+    def stream_drop(self, slot, item):
+        """The client of item `item` of the batched stream on `slot` went away: later steps skip it."""
+        _check(self.lib.piper_hip_voice_stream_drop(self.voice, slot, int(item)))
 
     def prepare_batch(self, slot, utterances, noiseScale=0.667):
         """utterances: list of (phonemeIDs, durations, noise-or-None); lengths may differ (ragged batch, one bucket)."""

@@ -111,6 +111,46 @@ public final class PiperHIPRuntime {
         } }
     }
 
+    /// Batched streaming (piper_hip_voice_stream_begin_batch): a group of utterances on one slot, encoder + flow once for the group, then
+    /// every active item's next chunk in one generator launch per step. `onStep` receives one array per item (empty once it has finished);
+    /// `durations[i] == nil` = predicted by the voice's duration predictor.
+    public func synthesizeStreamBatch(phonemeIDs: [[Int64]], durations: [[Int32]?], noiseScale: Float, chunkFrames: Int32 = 64,
+                                      slot: Int32 = 0, onStep: ([[Float]]) -> Void) throws {
+        let n = phonemeIDs.count
+        let ids = phonemeIDs.map { ContiguousArray($0) }
+        let durs = durations.map { $0.map { ContiguousArray($0) } }
+        var utts = [piper_hip_utterance]()
+        var steps: Int32 = 0
+        try withExtendedLifetime((ids, durs)) {
+            for i in 0..<n {
+                let ip = ids[i].withUnsafeBufferPointer { $0.baseAddress }       // storage kept alive by withExtendedLifetime
+                let dp = durs[i]?.withUnsafeBufferPointer { $0.baseAddress }
+                utts.append(piper_hip_utterance(phoneme_ids: ip, t: Int32(ids[i].count), durations: dp, noise: nil, noise_scale: noiseScale,
+                                                noise_mode: Int32(PIPER_HIP_NOISE_INJECTED), seed: 1234, length_scale: 1.0, noise_w: 0.8,
+                                                dp_noise: nil))
+            }
+            steps = piper_hip_voice_stream_begin_batch(voice, &utts, Int32(n), slot, chunkFrames)   // encoder + flow of the group
+            if steps < 0 { try HIPBackend.check(steps) }
+        }
+        var buf = [Float](repeating: 0, count: n * Int(chunkFrames) * hop)
+        var counts = [Int64](repeating: 0, count: n)
+        while true {
+            try HIPBackend.check(piper_hip_voice_stream_next_batch(voice, slot, &buf, Int64(buf.count), &counts))
+            if counts.allSatisfy({ $0 == 0 }) { return }
+            var out = [[Float]](), off = 0
+            for c in counts {
+                out.append(Array(buf[off..<off + Int(c)]))
+                off += Int(c)
+            }
+            onStep(out)
+        }
+    }
+
+    /// The client of item `item` of the batched stream on `slot` went away: later steps skip it.
+    public func streamDrop(slot: Int32, item: Int32) throws {
+        try HIPBackend.check(piper_hip_voice_stream_drop(voice, slot, item))
+    }
+
     /// WavFileWriter (Sources/PiperCLI/WavFileWriter.swift:20-60): float → int16 with the CLI's x·32767 clamp, RIFF header.
     public func writeWav(_ samples: [Float], to path: String) throws {
         try HIPBackend.check(piper_hip_wav_write(path, samples, samples.count, sampleRate))
