@@ -243,7 +243,7 @@ struct Slot {
   std::vector<Step> steps;
   struct Tap {  // a named intermediate: [NB] items of [C][row] floats, of which the first len_b (T or F of item b) are real
     const float* p;
-    int C, row, unit;  // unit: 0 = phonemes (T), 1 = frames (F)
+    int C, row, unit;  // unit: 0 = phonemes (T), k ≥ 1 = k positions per frame (1: frames; a generator stage: its upsampling so far)
     size_t batch_stride;
   };
   std::map<std::string, Tap> taps;
@@ -797,6 +797,20 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
     }
     if (ar.rc) return ar.rc;
     const std::string p = "dec.s" + std::to_string(u) + ".";
+    // Read-only taps on the stage's fp32 tensors (tests/test_gpu_bf16_exact.py): names only — no launch, no copy, no buffer. A dilation
+    // step that is not the ResBlock's last lands in tmp[j][d & 1] and is registered when no later step overwrites it: the last two
+    // of them (every step of the presets' three). The closing step of the last ResBlock has no fp32 tensor of its own on the schedules
+    // that fold the MRF mean into its epilogue: there only the mean exists (fp32 in the last stage: "dec.mean"; else the next image).
+    auto tap_f32 = [&](const std::string& name, const float* ptr) {
+      if (ptr) s.taps[name] = {ptr, S.Cout, Lo, Lo / F, (size_t)S.Cout * Lo};
+    };
+    auto tap_step = [&](int j, int di, const float* ptr) {
+      if (di + 3 >= c.rb_n_dil) tap_f32(p + "rb" + std::to_string(j) + ".c" + std::to_string(di), ptr);
+    };
+    tap_f32(p + "up", up);
+    if (last_stage) tap_f32("dec.mean", m);
+    // the bf16 image of lrelu(MRF mean) that the next stage reads, as raw bits: row cb holds positions × 8 channels × bf16 = 4 floats per position
+    if (a_next) s.taps[p + "mean_act"] = {(const float*)a_next + kC8Halo * 4, S.Cout / 8, row * 4, Lo / F * 4, (size_t)(S.Cout / 8) * row * 4};
     {
       ConvBf16Args a;
       a.x = a_in; a.y = up; a.act = a_up; a.act_alpha = 0.1f;
@@ -840,6 +854,7 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
           }
           src[j] = dst;
           src_act[j] = dst_act;
+          if (!(lastd && j == 2)) tap_step(j, di, dst);
         }
         // ResBlock1 pairs that are not the stage's last: both convs in one launch, intermediate in LDS (rb_pair_bf16.hip)
         static const bool no_pair = getenv("PIPER_HIP_NO_RB_PAIR") != nullptr;
@@ -879,6 +894,7 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
               // all three last pairs in one launch (rb2 writes its own fp32 output), then the MRF mean as a small elementwise
               // launch: a single pair of a 128-channel stage is 96 blocks for 256 CUs (52 µs; r3h), the mean 8 µs
               pk.a[2].y = r[2]; pk.a[2].act = nullptr; pk.a[2].mrf_a = nullptr; pk.a[2].mrf_b = nullptr;
+              tap_step(2, di, r[2]);
               add_pairs(nm + "ab_lrelu_conv_lrelu_conv_res_x3", 0, 3, fl[0] + fl[1] + fl[2]);
               Step st;
               st.name = p + "mrf_mean" + (last_stage ? "" : "_lrelu_to_bf16");
@@ -967,6 +983,7 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
           add_conv_bf16(v, s, nm + (fuse_mean ? "_lrelu_conv_res_mrfmean" : "_lrelu_conv_res"), v->rb_b[u][j][di],
                         finish(rbconv(src_act, dil)), fl);
         }
+        if (!fuse_mean) tap_step(j, di, dst);
         src = dst;
         src_act = dst_act;
       }
@@ -3140,7 +3157,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
   const Slot::Tap& t = it->second;
   // items back to back, each compacted to its true length: [C][len_b]
   size_t total = 0;
-  for (int b = 0; b < s.NB; b++) total += (size_t)t.C * (size_t)(t.unit == 0 ? s.h_T[b] : s.h_F[b]);
+  for (int b = 0; b < s.NB; b++) total += (size_t)t.C * (size_t)(t.unit == 0 ? s.h_T[b] : s.h_F[b] * t.unit);
   if (n_floats) *n_floats = total;
   if (host) {
     if (max_floats < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
@@ -3148,7 +3165,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
     PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
     size_t off = 0;
     for (int b = 0; b < s.NB; b++) {
-      const size_t len = (size_t)(t.unit == 0 ? s.h_T[b] : s.h_F[b]);
+      const size_t len = (size_t)(t.unit == 0 ? s.h_T[b] : s.h_F[b] * t.unit);
       PH_HIP(hipMemcpy2D(host + off, len * sizeof(float), t.p + (size_t)b * t.batch_stride, (size_t)t.row * sizeof(float), len * sizeof(float),
                          (size_t)t.C, hipMemcpyDeviceToHost), PIPER_HIP_ERR_LAUNCH);
       off += (size_t)t.C * len;

@@ -149,6 +149,9 @@ def test_config4_high_bf16_factor8_vs_oracle(backend, voices):
         s = snr_db(bf, ref)
         print(f"high bf16 factor 8: SNR vs fp32 oracle = {s:.1f} dB, max|Δ| = {np.abs(bf - ref).max():.3e}")
         assert bf.size == 86016 and s >= 35.0, s
+        # and every unit of the generator against the rounding-exact reference, fed the GPU's own taps (tests/bf16_ref.py)
+        import bf16_ref
+        bf16_ref.verify_slot(rt, blob, 0, [336], bf, "config 4")
     finally:
         rt.close()
 

@@ -472,12 +472,16 @@ def test_bf16_generator_snr(quality, voices, backend):
         print(f"{quality}: bf16 generator SNR vs fp32 oracle = {s:.1f} dB; max|Δ| = {np.abs(bf - ref).max():.3e}")
         assert s >= BF16_MIN_SNR_DB, s
         assert not np.array_equal(bf, fp32)  # it really is a different arithmetic
+        # the SNR sees nothing below the rounding error itself: every unit against the rounding-exact reference, fed the GPU's own taps
+        import bf16_ref
+        bf16_ref.verify_slot(rt, blob, 0, [F], bf, f"{quality} snr case")
         # batch of 2 through the bf16 schedule
         rt.prepare_batch(1, [(ids, dur, noise), (ids[::-1], dur, None)], 0.667)
         rt.launch(1)
         both = rt.collect(1).reshape(2, -1)
         assert snr_db(both[0], ref) >= BF16_MIN_SNR_DB
         assert snr_db(both[1], orc.synthesize(cfg, blob, ids[::-1], dur, None, 0.667)) >= BF16_MIN_SNR_DB
+        bf16_ref.verify_slot(rt, blob, 1, [F, F], both.reshape(-1), f"{quality} snr case, batch of 2")
         # and back: the fp32 path is bit-identical to what it produced before the switch
         rt.set_precision("f32")
         assert np.array_equal(rt.synthesize(ids, dur, noise, 0.667), fp32)
