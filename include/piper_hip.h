@@ -495,7 +495,18 @@ int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u,
  * copy a named intermediate of the slot's last run to host. Names: "enc_out" [H,T], "m_p" [inter,T],
  * "logs_p" [inter,T], "z_p" [inter,F], "z" [inter,F], "dec_pre" [up_initial,F] — per batch item, compacted to the item's
  * true T / F (the bucket's padding is not copied), items back to back. With predicted durations, "logw" [1,T] of the
- * predictor is available through piper_hip_voice_predict_durations. */
+ * predictor is available through piper_hip_voice_predict_durations.
+ * Generator taps (fp32 tensors [C_u, F · up_rates[0..u]] of stage u; a name exists only where the slot's schedule keeps that tensor
+ * until the plan has run, any other name is PIPER_HIP_ERR_ARG):
+ *   "dec.s{u}.up"            the stage's ConvTranspose output (every schedule, fp32 and bf16);
+ *   "dec.s{u}.rb{j}.c{d}"    ResBlock j after dilation step d. bf16 and the fp32 per-conv schedule: the last three steps, except the
+ *                            closing step of the last ResBlock where the MRF mean is folded into its epilogue. fp32 merged schedule:
+ *                            the last two steps (ping-pong buffers); a step fused inside a pair launch has no tensor, so a ResBlock2
+ *                            stage that runs as one pair launch keeps "c1" only;
+ *   "dec.s{u}.mean_lrelu"    fp32 per-conv schedule: lrelu(MRF mean) as the next stage reads it (slope 0.1; last stage 0.01);
+ *   "dec.s{u}.mean_act"      bf16, u < n_ups − 1: the bf16 image of lrelu(MRF mean, 0.1) as raw bits, [C_u / 8][len][8] bf16 words
+ *                            (4 floats per position and channel group);
+ *   "dec.mean"               bf16: the last stage's fp32 MRF mean. */
 int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name, float* host, size_t max_floats,
                         size_t* n_floats);
 /* GPU milliseconds of the slot's last completed launch (hipEvent pair on the slot's stream) ⇔

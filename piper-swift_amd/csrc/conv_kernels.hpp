@@ -238,8 +238,12 @@ __global__ __launch_bounds__(BT) void conv_stream_kernel(const ConvArgs p, const
   const int chunk = in_grid ? tile / mt_eff : 0;
   const int t0 = chunk * TM * NT;
   // Bucketed / ragged batches: a tile whose every column lies at or past the item's TRUE length computes nothing anyone reads
-  // (consumers mask by the same length) — 'same'-length convs and ConvTranspose (GEMM columns = input positions) only
-  const bool past_len = p.len_ptr && (p.Lout == p.Lin || p.epilogue == EPI_CONVT) && t0 >= true_len(p, n);
+  // (consumers mask by the same length) — 'same'-length convs and ConvTranspose (GEMM columns = input positions) only.
+  // ConvTranspose column q writes the outputs from q·s − pad on: the columns len … len + pad/s still reach below len·s (from x[len − 1]),
+  // so a tile is past the length only when its first output is (a tile starting exactly at len used to be skipped: the last `pad`
+  // outputs of an item whose length is a multiple of the tile width kept what the buffer held).
+  const bool past_len = p.len_ptr && (p.epilogue == EPI_CONVT ? t0 * p.ct_stride - p.ct_padL >= true_len(p, n) * p.ct_stride
+                                                             : p.Lout == p.Lin && t0 >= true_len(p, n));
   const bool active = in_grid && !past_len;
   const int j = lane & (TM - 1), kk = lane / TM;
   const int ncp = (p.Cin + CPS - 1) / CPS;  // channel units (pairs / quads)

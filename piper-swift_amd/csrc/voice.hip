@@ -1063,6 +1063,15 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
     }
     if (ar.rc) return ar.rc;
     const std::string p = "dec.s" + std::to_string(u) + ".";
+    // Read-only taps (tests/test_gpu_f32_exact.py), under the names of build_generator_bf16: names only — no launch, no copy, no buffer.
+    // The ping-pong buffers keep the last two ResBlock steps; held[j][i] is the step whose output buf[j][i] holds when the stage has run.
+    // A step fused inside a pair launch (ResBlock2: the first of the two) has no tensor and therefore no name.
+    auto tap_f32 = [&](const std::string& name, const float* ptr) { s.taps[name] = {ptr, S.Cout, Lo, Lo / F, (size_t)S.Cout * Lo}; };
+    int held[kWinMulti][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
+    auto holds = [&](float* const y[kWinMulti], int di) {
+      for (int j = 0; j < kWinMulti; j++) held[j][y[j] == buf[j][1]] = di;
+    };
+    tap_f32(p + "up", up);
     {  // ConvTranspose on lrelu(input) — input = conv_pre output, or the mean of the previous stage's ResBlocks
       Step st;
       st.name = p + (cur[1] ? "mrfmean_lrelu_convT" : "lrelu_convT");
@@ -1161,6 +1170,7 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
       const std::string nm = p + "rb012.c" + std::to_string(di);
       if (c.resblock_type == 1 && add_pair(nm + "ab_lrelu_conv_lrelu_conv_res_x3", 2 * di, 2 * di + 1, dil, one, false, true, src, dst)) {
         for (int j = 0; j < kWinMulti; j++) src[j] = dst[j];
+        holds(dst, di);
         continue;
       }
       if (c.resblock_type == 2 && di + 1 < c.rb_n_dil) {
@@ -1169,6 +1179,7 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
         if (add_pair(p + "rb012.c" + std::to_string(di) + std::to_string(di + 1) + "_lrelu_conv_res_pair_x3", di, di + 1, dil, dil2, true, false, src, dst)) {
           for (int j = 0; j < kWinMulti; j++) src[j] = dst[j];
           di++;
+          holds(dst, di);
           continue;
         }
       }
@@ -1183,7 +1194,11 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
         add_multi(nm + "_lrelu_conv_res_x3", w, src, src, dst, dil);
       }
       for (int j = 0; j < kWinMulti; j++) src[j] = dst[j];
+      holds(dst, di);
     }
+    for (int j = 0; j < kWinMulti; j++)
+      for (int i = 0; i < 2; i++)
+        if (held[j][i] >= 0) tap_f32(p + "rb" + std::to_string(j) + ".c" + std::to_string(held[j][i]), buf[j][i]);
     for (int j = 0; j < kWinMulti; j++) cur[j] = src[j];
     L = Lo;
   }
@@ -1583,6 +1598,12 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, int mode =
     float* m = ar.f32(B * S.Cout * Lo);  // lrelu(mean of the three ResBlock outputs): input of the next stage
     if (ar.rc) return ar.rc;
     const float mean_alpha = (u + 1 == c.n_ups) ? 0.01f : 0.1f;  // F.leaky_relu default slope before conv_post
+    // Read-only taps (tests/test_gpu_f32_exact.py): names only. Every step has a buffer of its own here, except the closing step of the
+    // last ResBlock where the mean is folded into its epilogue; "mean_lrelu" is what the next stage (or conv_post) reads:
+    // lrelu(MRF mean, 0.1), in the last stage lrelu(MRF mean, 0.01).
+    auto tap_f32 = [&](const std::string& name, const float* ptr) { s.taps[name] = {ptr, S.Cout, Lo, Lo / F, (size_t)S.Cout * Lo}; };
+    tap_f32(p + "up", up);
+    tap_f32(p + "mean_lrelu", m);
     for (int j = 0; j < c.n_rb; j++) {
       s.cur_lane = j < 3 ? j : 0;
       const int K = c.rb_kernels[j];
@@ -1594,6 +1615,7 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, int mode =
         const bool fuse_mean = lastd && j + 1 == c.n_rb && !parallel_rb;
         float* dst = lastd ? (fuse_mean ? m : r[j]) : ((di & 1) ? tmp2[j] : tmp[j]);
         const std::string nm = p + "rb" + std::to_string(j) + ".c" + std::to_string(di);
+        if (!fuse_mean && di + 3 >= c.rb_n_dil) tap_f32(nm, dst);  // (tmp / tmp2 keep the last two steps before the closing one)
         auto rbconv = [&](const float* in, const float* res, float* out, int dl) {
           ConvArgs a = plain(in, out, S.Cout, S.Cout, Lo, lensF, Lo / F);
           a.dil = dl; a.padL = (K * dl - dl) / 2; a.prologue = PRO_LRELU; a.alpha = 0.1f; a.res = res;

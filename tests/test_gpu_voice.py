@@ -508,8 +508,9 @@ def test_voice_loaded_from_onnx_file(backend, voices, tmp_path):
 
 @pytest.mark.parametrize("quality", ["medium", "high"])
 def test_large_batch_takes_the_per_conv_schedules(quality, voices, backend):
-    """NB·F above the merge threshold (1536): fp32 runs one launch per ResBlock conv with the MRF mean fused into its
-    producer, bf16 additionally uses parallel graph branches for ResBlock1. Both must still match the oracle."""
+    """NB·F above bf16's merge threshold (1536): bf16 runs one launch per ResBlock conv with the MRF mean fused into its producer, and
+    parallel graph branches for ResBlock1. fp32 has no such limit since the pair kernel (merged_max = 1 << 40): it stays on the merged
+    schedule here too (asserted in test_gpu_f32_exact.py::test_batch_of_twenty). Both must still match the oracle."""
     cfg, blob = voices[quality]
     rt = ph.HipRuntime(backend, cfg, blob)
     try:
