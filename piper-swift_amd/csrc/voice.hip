@@ -3,7 +3,7 @@
 // Stands where PiperMetalRuntime.synthesize → GraphExecutor.executeOutput stands in the reference
 // (PiperMetalRuntime.swift:62-80, GraphExecutor.swift:156-327), but instead of interpreting 2 755 ONNX nodes with a
 // fresh buffer, a string-keyed table lookup and (in the unbatched mode) a blocking commit per node, the voice is
-// compiled once into ≈110 launches over a preplanned arena:
+// compiled once into 80 launches (medium voice) over a preplanned arena:
 //   encoder layer = qkv conv · rel-attention · o conv · add+LayerNorm · ffn1(+ReLU) · ffn2 · add+LayerNorm
 //   flow coupling = pre conv (Flip/Split folded into channel maps) · 4×[in conv + tanh·sigmoid gate, res/skip conv
 //                   writing x and skip in place] · post conv with x1 ← x1 − m in place (Concat folded)
@@ -204,13 +204,21 @@ struct StreamSet {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
 };
 
+// What a plan computes. PLAN_PREDICT then PLAN_FROM_STATS is a whole utterance with predicted durations that runs the encoder once.
+enum PlanKind : int {
+  PLAN_WHOLE = 0,       // whole utterance: text encoder, flow, generator
+  PLAN_GENERATOR = 1,   // generator only, over a window of the latent (streaming)
+  PLAN_PREDICT = 2,     // text encoder + projection + duration predictor
+  PLAN_FROM_STATS = 3,  // everything AFTER the text encoder (expansion, flow, generator), from an m_p / logs_p tensor copied in from a PLAN_PREDICT plan
+};
+
 struct Slot {
   StreamSet set;  // empty (set.stream == nullptr) while the plan is idle: slot_init takes one, give_back_set returns it
   // A Slot is a PLAN: schedule + arena + graph for one bucket (kind, T, F, NB). T and F are the bucket's row lengths; the
   // true lengths of the NB batch items live in device memory (lensT / lensF) where every length-aware kernel reads them, so
   // one captured graph serves every utterance that fits the bucket — exactly (positions past a true length read as zero
   // padding, attention excludes keys past it), not approximately.
-  int kind = 0;  // 0 = whole utterance, 1 = generator only (streaming window)
+  PlanKind kind = PLAN_WHOLE;
   int T = -1, F = -1, NB = 1;
   int prec = 0;            // generator precision the schedule was built for
   bool in_use = false;     // attached to a user slot id
@@ -220,17 +228,17 @@ struct Slot {
   int* lensT = nullptr;    // [NB] device: true phoneme count per item
   int* lensF = nullptr;    // [NB] device: true frame count per item
   std::vector<int> h_T, h_F;   // the same on the host (collect / tap / streaming)
-  // duration-predictor plan (kind 2): encoder + predictor → frames per id
+  // duration-predictor plan (PLAN_PREDICT): encoder + predictor → frames per id
   float* dp_noise = nullptr;   // [NB][2][T] injected `dp` RandomNormalLike tensor
   void* dp_scalars = nullptr;  // [NB] DpScalars (device)
   int32_t* dp_dur = nullptr;   // [NB][T] predicted frames per id
   std::vector<int32_t> h_dur;  // predicted durations of the attached request, per item back to back (host)
-  // kind 3 prepared by piper_hip_voice_prepare_batch_bounded: the frame counts are decided on the device and reach the host with the
+  // PLAN_FROM_STATS prepared by piper_hip_voice_prepare_batch_bounded: the frame counts are decided on the device and reach the host with the
   // waveform (collect). Until then h_F holds the bucket's capacity.
   bool bounded_pending = false;
   int bounded_cap = 0;         // max_frames the caller allowed
-  hipEvent_t ev_in = nullptr;  // kind 3: "the copy of the predictor plan's projection has been read" (that plan's stream waits for it)
-  float* stats = nullptr;      // [NB][2·inter][T] encoder projection (m_p ; logs_p): output of kinds 0 / 2, INPUT of kind 3
+  hipEvent_t ev_in = nullptr;  // PLAN_FROM_STATS: "the copy of the predictor plan's projection has been read" (that plan's stream waits for it)
+  float* stats = nullptr;      // [NB][2·inter][T] encoder projection (m_p ; logs_p): output of PLAN_WHOLE / PLAN_PREDICT, INPUT of PLAN_FROM_STATS
   // device buffers
   std::vector<void*> owned;
   int64_t* ids = nullptr;
@@ -265,7 +273,6 @@ struct Slot {
   int* bs_desc = nullptr;     // [kMaxGroup][kDescInts] device
   float* bs_pack = nullptr;   // the packed chunks of one step, device
   size_t bs_pack_cap = 0;     // floats
-  int cur_lane = 0;  // lane given to steps added by add_conv
 };
 
 }  // namespace
@@ -672,78 +679,232 @@ struct Arena {
 
 double conv_bytes(int Cin, int Cout, int K, int64_t L) { return 4.0 * ((double)Cin * L + (double)Cout * L + (double)Cout * Cin * K + Cout); }
 
-// conv step over a resident ConvW
-void add_conv(piper_hip_voice* v, Slot& s, const std::string& name, const ConvW& w, ConvArgs a, int64_t Lout_for_work) {
-  a.w = w.w;
-  a.w16 = w.w16;
-  a.w16g = w.w16g;
-  a.w8 = w.w8;
-  a.bias = w.bias;
-  a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
-  piper_hip_ctx* ctx = v->ctx;
-  Step st;
-  st.name = name;
-  const bool mfma = w.mfma;
-  st.run = [ctx, a, mfma](hipStream_t q) { return mfma ? launch_conv_mfma(ctx, q, a) : launch_conv_direct(ctx, q, a); };
-  st.flops = a.N * conv_flops(w.Cout, w.Cin, w.K, Lout_for_work);
-  st.bytes = a.N * conv_bytes(w.Cin, a.gate ? w.Cout / 2 : w.Cout, w.K, Lout_for_work);
-  st.lane = s.cur_lane;
-  st.tag = mfma ? "conv_mfma" : "conv_small";
-  s.steps.push_back(std::move(st));
-}
-
-// conv step over a bf16 fragment image
-void add_conv_bf16(piper_hip_voice* v, Slot& s, const std::string& name, const piper_hip_voice::ConvWB& w, ConvBf16Args a,
-                   double flops) {
-  a.w = w.w; a.bias = w.bias; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
-  piper_hip_ctx* ctx = v->ctx;
-  Step st;
-  st.name = name;
-  st.run = [ctx, a](hipStream_t q) { return launch_conv_bf16(ctx, q, a); };
-  st.flops = flops;
+// what a bf16 conv moves: the bf16 input image and weights, the bf16 output image, the fp32 result / residual / MRF operands
+double conv_bf16_bytes(const ConvBf16Args& a) {
   const double cols = (double)a.N * a.Lout, out_cols = a.ct_stride > 0 ? cols * a.ct_stride : cols;
-  st.bytes = 2.0 * (w.Cin * cols + (double)w.Cout * w.Cin * w.K) + (a.act ? 2.0 : 0.0) * w.Cout * out_cols +
-             ((a.y ? 4.0 : 0.0) + (a.res ? 4.0 : 0.0) + (a.mrf_a ? 8.0 : 0.0)) * w.Cout * out_cols;
-  st.lane = s.cur_lane;
-  st.tag = "conv_bf16";
-  s.steps.push_back(std::move(st));
+  return 2.0 * (a.Cin * cols + (double)a.Cout * a.Cin * a.K) + (a.act ? 2.0 : 0.0) * a.Cout * out_cols +
+         ((a.y ? 4.0 : 0.0) + (a.res ? 4.0 : 0.0) + (a.mrf_a ? 8.0 : 0.0)) * a.Cout * out_cols;
 }
 
-// several same-shape bf16 convs (the stage's ResBlocks) as one launch
-void add_conv_bf16_multi(piper_hip_voice* v, Slot& s, const std::string& name, const piper_hip_voice::ConvWB* const* ws,
-                         const ConvBf16Args* args, int count, double flops) {
-  struct Pack { ConvBf16Args a[kBf16Multi]; } pk;
-  double bytes = 0;
-  for (int i = 0; i < count; i++) {
-    ConvBf16Args a = args[i];
-    const auto& w = *ws[i];
-    a.w = w.w; a.bias = w.bias; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
-    pk.a[i] = a;
-    const double cols = (double)a.N * a.Lout;
-    bytes += 2.0 * (w.Cin * cols + (double)w.Cout * w.Cin * w.K) + (a.act ? 2.0 : 0.0) * w.Cout * cols +
-             ((a.y ? 4.0 : 0.0) + (a.res ? 4.0 : 0.0) + (a.mrf_a ? 8.0 : 0.0)) * w.Cout * cols;
+// What the schedule builders work on: the voice, the plan being built and its arena, the bucket (T, F, NB), the device arrays of the
+// items' true lengths, and the lane of the steps added next. Every step, fork, join and tap of a plan is appended here.
+struct Builder {
+  piper_hip_voice* v;
+  Slot& s;
+  Arena ar;
+  const int T, F, NB;
+  const int *lensT = nullptr, *lensF = nullptr;
+  int lane = 0;  // given to the steps added next (Step::lane): the ResBlock loops of the per-conv generators move it
+  Builder(piper_hip_voice* v_, Slot& s_, int T_, int F_, int NB_) : v(v_), s(s_), ar{v_, &s_}, T(T_), F(F_), NB(NB_) {}
+  Builder(const Builder&) = delete;  // a step's closure copies the few values its launch needs, never the builder
+
+  void step(const std::string& name, const char* tag, double flops, double bytes, std::function<int(hipStream_t)> run) {
+    Step st;
+    st.name = name;
+    st.tag = tag;
+    st.flops = flops; st.bytes = bytes;
+    st.lane = lane;
+    st.run = std::move(run);
+    s.steps.push_back(std::move(st));
   }
-  piper_hip_ctx* ctx = v->ctx;
-  Step st;
-  st.name = name;
-  st.run = [ctx, pk, count](hipStream_t q) { return launch_conv_bf16_multi(ctx, q, pk.a, count); };
-  st.flops = flops; st.bytes = bytes;
-  st.lane = 0;
-  st.tag = "conv_bf16";
-  s.steps.push_back(std::move(st));
+  void mark(const std::string& name, Step::Kind kind) {
+    Step st;
+    st.name = name;
+    st.kind = kind;
+    s.steps.push_back(std::move(st));
+  }
+  void fork(const std::string& name) { mark(name, Step::FORK); }
+  void join(const std::string& name) { mark(name, Step::JOIN); }
+  // a named intermediate: [NB] items of [C][row] floats, batch_stride apart (0 ⇒ dense: C · row)
+  void tap(const std::string& name, const float* p, int C, int row, int unit, size_t batch_stride = 0) {
+    s.taps[name] = {p, C, row, unit, batch_stride ? batch_stride : (size_t)C * row};
+  }
+
+  // lens = the per-item true lengths the rows of this conv are measured in (phonemes or frames), mul = positions per unit
+  ConvArgs plain(const float* in, float* out, int Cin_, int Cout_, int L, const int* lens, int mul = 1) const {
+    ConvArgs a;
+    a.x = in; a.y = out; a.N = NB; a.Lin = L; a.Lout = L; a.x_batch_stride = (int64_t)Cin_ * L; a.y_batch_stride = (int64_t)Cout_ * L;
+    a.y_len = L;
+    a.len_ptr = lens; a.len_mul = mul;
+    return a;
+  }
+
+  // conv step over a resident ConvW
+  void conv(const std::string& name, const ConvW& w, ConvArgs a, int64_t Lout_for_work) {
+    a.w = w.w;
+    a.w16 = w.w16;
+    a.w16g = w.w16g;
+    a.w8 = w.w8;
+    a.bias = w.bias;
+    a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
+    piper_hip_ctx* ctx = v->ctx;
+    const bool mfma = w.mfma;
+    step(name, mfma ? "conv_mfma" : "conv_small", a.N * conv_flops(w.Cout, w.Cin, w.K, Lout_for_work),
+         a.N * conv_bytes(w.Cin, a.gate ? w.Cout / 2 : w.Cout, w.K, Lout_for_work),
+         [ctx, a, mfma](hipStream_t q) { return mfma ? launch_conv_mfma(ctx, q, a) : launch_conv_direct(ctx, q, a); });
+  }
+
+  // conv step over a bf16 fragment image
+  void conv_bf16(const std::string& name, const piper_hip_voice::ConvWB& w, ConvBf16Args a, double flops) {
+    a.w = w.w; a.bias = w.bias; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
+    piper_hip_ctx* ctx = v->ctx;
+    step(name, "conv_bf16", flops, conv_bf16_bytes(a), [ctx, a](hipStream_t q) { return launch_conv_bf16(ctx, q, a); });
+  }
+
+  // several same-shape bf16 convs (the stage's ResBlocks) as one launch
+  void conv_bf16_multi(const std::string& name, const piper_hip_voice::ConvWB* const* ws, const ConvBf16Args* args, int count, double flops) {
+    struct Pack { ConvBf16Args a[kBf16Multi]; } pk;
+    double bytes = 0;
+    for (int i = 0; i < count; i++) {
+      ConvBf16Args& a = pk.a[i] = args[i];
+      const auto& w = *ws[i];
+      a.w = w.w; a.bias = w.bias; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
+      bytes += conv_bf16_bytes(a);
+    }
+    piper_hip_ctx* ctx = v->ctx;
+    step(name, "conv_bf16", flops, bytes, [ctx, pk, count](hipStream_t q) { return launch_conv_bf16_multi(ctx, q, pk.a, count); });
+  }
+};
+
+// ---- A/B switches of the generator builders. Each is parsed in one place, and looked up (ph::tuning_getenv records the ones that are
+// set, piper_hip_config_string() reports them) the first time a builder that honours it asks.
+bool no_merged_rb() { static const bool on = getenv("PIPER_HIP_NO_MERGED_RB") != nullptr; return on; }  // both precisions: one launch per conv
+bool no_rb_pair() { static const bool on = getenv("PIPER_HIP_NO_RB_PAIR") != nullptr; return on; }      // both precisions: no two-conv launches
+
+struct GenF32Switches {
+  const bool parallel_rb = getenv("PIPER_HIP_PARALLEL_RB") != nullptr;
+  const bool use_win = getenv("PIPER_HIP_NO_WIN") == nullptr;  // window kernel for the generator's long rows
+  // PIPER_HIP_NO_PIPE=1 keeps round 1's one-tile-per-block window kernel.
+  // conv_pipe (persistent, chunk-pipelined) wins once a launch holds enough work to amortise its prologue and tail — the
+  // high voice's 128/256-channel stages: 89 vs 73 TFLOP/s — and loses to the one-tile-per-block window kernel on the medium
+  // voice at factor 8 (48 vs 46 µs per merged launch). Threshold on the launch's FLOPs; PIPER_HIP_PIPE_MIN_GFLOP overrides.
+  const bool no_pipe = getenv("PIPER_HIP_NO_PIPE") != nullptr;
+  const double pipe_min_flops = [] { const char* e = getenv("PIPER_HIP_PIPE_MIN_GFLOP"); return (e ? atof(e) : 5.0) * 1e9; }();
+  // r2f (factor 64): as a single-conv launch it also loses at 32 / 64 channels (135 vs 114 µs, 105 vs 100 µs: one chunk per
+  // tile leaves nothing to pipeline, and 2 blocks per CU hide less than the window kernel's 4) and wins from 128 channels up.
+  // ConvTranspose: it won (112 vs 145 µs) until the window kernel staged narrow windows with a flat index and kept the phases
+  // of a column range in one block; since then the window kernel wins at every size measured (factor 64: 126 / 121 vs
+  // 187 / 204 µs, 8 × factor 8: 111 / 119 vs 181 / 201 µs, high voice factor 32: 215 vs 312 µs) — never by default,
+  // PIPER_HIP_PIPE_CT_MIN_GFLOP=g brings it back for launches of ≥ g GFLOP.
+  const double pipe_ct_min_flops = [] { const char* e = getenv("PIPER_HIP_PIPE_CT_MIN_GFLOP"); return e ? atof(e) * 1e9 : 1e30; }();
+  bool pipe_pays(double launch_flops, int Cin, bool ct) const {
+    return !no_pipe && launch_flops >= (ct ? pipe_ct_min_flops : pipe_min_flops) && (ct || Cin >= 128);
+  }
+};
+const GenF32Switches& gen_f32_switches() {
+  static const GenF32Switches sw;
+  return sw;
 }
 
-// HiFi-GAN generator with bf16 contraction operands. Same graph as the fp32 generator below;
+// ---- generator pieces that more than one builder schedules
+
+// window-kernel arguments of a 'same'-padded stride-1 conv on lrelu(x, 0.1) over rows of L positions; mrf_a / mrf_b: the MRF mean
+// ((mrf_a + mrf_b) + result) / 3 and the LeakyReLU(out_alpha) after it, folded into the epilogue
+ConvWinArgs win_args(const Builder& b, const ConvW& w, const float* x, const float* res, float* y, int dil, int L, const float* mrf_a = nullptr,
+                     const float* mrf_b = nullptr, float out_alpha = 1.0f) {
+  ConvWinArgs wa;
+  wa.x = x; wa.w4 = w.w4; wa.bias = w.bias; wa.res = res; wa.y = y;
+  wa.pro_alpha = 0.1f;
+  if (mrf_a) { wa.mrf_a = mrf_a; wa.mrf_b = mrf_b; wa.out_alpha = out_alpha; }
+  wa.N = b.NB; wa.Cin = w.Cin; wa.Cout = w.Cout; wa.K = w.K; wa.dil = dil; wa.padL = (w.K * dil - dil) / 2;
+  wa.Lin = L; wa.Lout = L; wa.y_len = L;
+  wa.len_ptr = b.lensF; wa.len_mul = L / b.F;
+  return wa;
+}
+
+// fp32 ConvTranspose of stage S, rows of L → L · stride positions, on lrelu(input, pro_alpha) — input = cur[0] (pro_alpha 1: its producer
+// applied the LeakyReLU already) or, with cur[1] and cur[2] set, the MRF mean of the three. Pipe, window or streaming kernel.
+void add_convt_f32(Builder& b, const std::string& name, const piper_hip_voice::Stage& S, const float* const cur[3], float pro_alpha, float* up,
+                   int L) {
+  const GenF32Switches& sw = gen_f32_switches();
+  piper_hip_ctx* ctx = b.v->ctx;
+  const int NB = b.NB, Lo = L * S.stride;
+  const double flops = NB * 2.0 * S.Cin * S.Cout * (double)S.K * L;  // convT(Cin,Cout,K,s,Lin)
+  const double bytes = NB * 4.0 * ((double)S.Cin * L * (cur[1] ? 3 : 1) + (double)S.Cout * Lo + (double)S.Cin * S.Cout * S.K + S.Cout);
+  const bool pipe = sw.use_win && sw.pipe_pays(flops, S.Cin, true) && S.up.w5 && convt_pipe_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, L);
+  if (pipe || (sw.use_win && S.up.w4 && convt_win_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, L))) {
+    ConvWinArgs wa;
+    wa.x = cur[0]; wa.x2 = cur[1]; wa.x3 = cur[2]; wa.w4 = pipe ? S.up.w5 : S.up.w4; wa.bias = S.up.bias; wa.y = up;
+    wa.pro_alpha = pro_alpha;
+    wa.N = NB; wa.Cin = S.Cin; wa.Cout = S.Cout; wa.K = S.K; wa.Lin = L; wa.Lout = L; wa.y_len = Lo;
+    wa.ct_stride = S.stride; wa.ct_pad = S.pad;
+    wa.len_ptr = b.lensF; wa.len_mul = L / b.F;
+    if (pipe) b.step(name, "conv_mfma", flops, bytes, [ctx, wa](hipStream_t q) { return launch_conv_pipe_multi(ctx, q, &wa, 1); });
+    else b.step(name, "conv_mfma", flops, bytes, [ctx, wa](hipStream_t q) { return launch_conv_win(ctx, q, wa); });
+    return;
+  }
+  ConvArgs a;
+  a.x = cur[0]; a.x2 = cur[1]; a.x3 = cur[2];
+  a.prologue = cur[1] ? PRO_AVG3_LRELU : pro_alpha == 1.0f ? PRO_NONE : PRO_LRELU;
+  a.alpha = 0.1f;
+  a.y = up; a.N = NB; a.dil = -1; a.padL = 0; a.Lin = L; a.Lout = (Lo - 1 + S.pad) / S.stride + 1;
+  a.len_ptr = b.lensF; a.len_mul = L / b.F;
+  a.x_batch_stride = (int64_t)S.Cin * L; a.y_batch_stride = (int64_t)S.Cout * Lo; a.y_len = Lo;
+  a.epilogue = EPI_CONVT; a.ct_stride = S.stride; a.ct_padL = S.pad; a.ct_Lout = Lo;
+  a.w = S.up.w; a.w16 = S.up.w16; a.bias = S.up.bias; a.Cin = S.up.Cin; a.Cout = S.up.Cout; a.K = S.up.K;
+  b.step(name, "conv_mfma", flops, bytes, [ctx, a](hipStream_t q) { return launch_conv_mfma(ctx, q, a); });
+}
+
+// y = lrelu(((r0 + r1) + r2) / 3, alpha) over cnt floats, as a launch of its own
+void add_mrf_mean(Builder& b, const std::string& name, const float* r0, const float* r1, const float* r2, float* y, int64_t cnt, float alpha) {
+  b.step(name, "", 0, 0, [=](hipStream_t q) {
+    const int grid = (int)std::min<int64_t>(ceil_div(cnt, (int64_t)kBlock * 4), 2048);
+    hipLaunchKernelGGL(mrf_mean_lrelu_kernel, dim3(grid), dim3(kBlock), 0, q, r0, r1, r2, y, cnt, alpha);
+    return PIPER_HIP_OK;
+  });
+}
+
+// The waveform: conv_post (→ 1 channel, k7: thread-per-output fp32 kernel) + tanh over rows of L samples. `prologue` says what its input still
+// needs: PRO_NONE — x is lrelu(MRF mean, 0.01) already; PRO_LRELU — x is the MRF mean; PRO_AVG3_LRELU — x, x2, x3 are the ResBlock outputs
+// to average (0.01 = F.leaky_relu's default slope before conv_post).
+int add_conv_post(Builder& b, const std::string& name, const float* x, const float* x2, const float* x3, int prologue, int L) {
+  Slot& s = b.s;
+  s.n_samples = L;
+  s.audio = b.ar.f32((size_t)b.NB * L);
+  if (b.ar.rc) return b.ar.rc;
+  ConvArgs a;
+  a.x = x; a.x2 = x2; a.x3 = x3;
+  a.prologue = prologue;
+  if (prologue != PRO_NONE) a.alpha = 0.01f;
+  a.y = s.audio; a.N = b.NB; a.padL = 3; a.Lin = L; a.Lout = L;
+  a.len_ptr = b.lensF; a.len_mul = L / b.F;
+  a.x_batch_stride = (int64_t)b.v->conv_post.Cin * L; a.y_batch_stride = L; a.y_len = L;
+  a.epilogue = EPI_TANH;
+  b.conv(name, b.v->conv_post, a, L);
+  return PIPER_HIP_OK;
+}
+
+// arguments of a 'same'-padded ResBlock conv (kernel K, dilation dil) over rows of Lo positions: fp32 on lrelu(in, 0.1) …
+ConvArgs rb_args_f32(const Builder& b, const float* in, const float* res, float* out, int C, int K, int dil, int Lo) {
+  ConvArgs a = b.plain(in, out, C, C, Lo, b.lensF, Lo / b.F);
+  a.dil = dil; a.padL = (K * dil - dil) / 2; a.prologue = PRO_LRELU; a.alpha = 0.1f; a.res = res;
+  return a;
+}
+// … and bf16 on the C8 image `in` (row positions per channel block) that its producer wrote as lrelu(·, 0.1)
+ConvBf16Args rb_args_bf16(const Builder& b, const uint16_t* in, int K, int dil, int Lo, int row) {
+  ConvBf16Args a;
+  a.x = in; a.N = b.NB; a.dil = dil; a.padL = (K * dil - dil) / 2; a.Lout = Lo; a.x_row = row; a.act_row = row; a.y_len = Lo;
+  a.act_alpha = 0.1f;
+  a.len_ptr = b.lensF; a.len_mul = Lo / b.F;
+  return a;
+}
+
+// HiFi-GAN generator with bf16 contraction operands. Same graph as the fp32 generators below;
 // what changes is the data each conv READS: the C8 bf16 image of LeakyReLU(x) written by its producer's epilogue
 // (conv_bf16.h). The residual stream, the bias adds and the MRF mean stay fp32, so rounding enters only through the
 // operands of each contraction and does not accumulate along the residual chain.
-int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z, float* dec0, int F, int NB) {
+int build_generator_bf16(Builder& b, const float* z, float* dec0) {
+  piper_hip_voice* v = b.v;
+  Slot& s = b.s;
+  Arena& ar = b.ar;
+  const int F = b.F, NB = b.NB;
   const piper_hip_voice_config& c = v->cfg;
+  piper_hip_ctx* ctx = v->ctx;
   const int I = c.inter;
   const size_t B = (size_t)NB;
   hipStream_t zs = s.set.stream;
   static const bool no_par = getenv("PIPER_HIP_BF16_SERIAL_RB") != nullptr;
-  static const bool no_merge = getenv("PIPER_HIP_NO_MERGED_RB") != nullptr;
+  const bool no_merge = no_merged_rb();
   // short utterances / small batches: the three ResBlocks advance in one launch; otherwise one launch per conv, as parallel
   // graph branches for the 18-conv ResBlock1 stages (+10 %; the 6-conv ResBlock2 stages do not gain)
   const bool merged = !no_merge && c.n_rb == 3 && (int64_t)NB * F <= 1536;
@@ -758,20 +919,17 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
   uint16_t* a_in = image(c.up_initial, F);
   if (ar.rc) return ar.rc;
   {
-    Step st;
-    st.name = "dec.z_to_bf16";
-    const int* lf = s.lensF;
-    st.run = [=](hipStream_t q) { return pack_act_c8(q, z, NB, I, F, 1.0f, zc8, 0, lf); };
-    s.steps.push_back(st);
+    const int* lf = b.lensF;
+    b.step("dec.z_to_bf16", "", 0, 0, [=](hipStream_t q) { return pack_act_c8(q, z, NB, I, F, 1.0f, zc8, 0, lf); });
   }
   {
     ConvBf16Args a;
     a.x = zc8; a.y = dec0; a.act = a_in; a.act_alpha = 0.1f;  // the first stage's ConvTranspose reads lrelu(conv_pre)
     a.N = NB; a.dil = 1; a.padL = 3; a.Lout = F; a.x_row = (int)c8_row_len(F); a.act_row = (int)c8_row_len(F); a.y_len = F;
-    a.len_ptr = s.lensF; a.len_mul = 1;
-    add_conv_bf16(v, s, "dec.conv_pre", v->conv_pre_b, a, NB * conv_flops(c.up_initial, I, 7, F));
+    a.len_ptr = b.lensF; a.len_mul = 1;
+    b.conv_bf16("dec.conv_pre", v->conv_pre_b, a, NB * conv_flops(c.up_initial, I, 7, F));
   }
-  s.taps["dec_pre"] = {dec0, c.up_initial, F, 1, (size_t)c.up_initial * F};
+  b.tap("dec_pre", dec0, c.up_initial, F, 1);
   int L = F;
   const float* mean = nullptr;
   for (int u = 0; u < c.n_ups; u++) {
@@ -802,7 +960,7 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
     // of them (every step of the presets' three). The closing step of the last ResBlock has no fp32 tensor of its own on the schedules
     // that fold the MRF mean into its epilogue: there only the mean exists (fp32 in the last stage: "dec.mean"; else the next image).
     auto tap_f32 = [&](const std::string& name, const float* ptr) {
-      if (ptr) s.taps[name] = {ptr, S.Cout, Lo, Lo / F, (size_t)S.Cout * Lo};
+      if (ptr) b.tap(name, ptr, S.Cout, Lo, Lo / F);
     };
     auto tap_step = [&](int j, int di, const float* ptr) {
       if (di + 3 >= c.rb_n_dil) tap_f32(p + "rb" + std::to_string(j) + ".c" + std::to_string(di), ptr);
@@ -810,14 +968,14 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
     tap_f32(p + "up", up);
     if (last_stage) tap_f32("dec.mean", m);
     // the bf16 image of lrelu(MRF mean) that the next stage reads, as raw bits: row cb holds positions × 8 channels × bf16 = 4 floats per position
-    if (a_next) s.taps[p + "mean_act"] = {(const float*)a_next + kC8Halo * 4, S.Cout / 8, row * 4, Lo / F * 4, (size_t)(S.Cout / 8) * row * 4};
+    if (a_next) b.tap(p + "mean_act", (const float*)a_next + kC8Halo * 4, S.Cout / 8, row * 4, Lo / F * 4);
     {
       ConvBf16Args a;
       a.x = a_in; a.y = up; a.act = a_up; a.act_alpha = 0.1f;
       a.N = NB; a.Lout = L; a.x_row = (int)c8_row_len(L); a.act_row = row; a.y_len = Lo;
       a.ct_stride = S.stride; a.ct_pad = S.pad;
-      a.len_ptr = s.lensF; a.len_mul = Lo / F;
-      add_conv_bf16(v, s, p + "lrelu_convT", v->up_b[u], a, NB * 2.0 * S.Cin * S.Cout * (double)S.K * L);
+      a.len_ptr = b.lensF; a.len_mul = Lo / F;
+      b.conv_bf16(p + "lrelu_convT", v->up_b[u], a, NB * 2.0 * S.Cin * S.Cout * (double)S.K * L);
     }
     if (merged) {
       // conv i of rb0, rb1, rb2 have the same shape and no dependence on each other: one launch advances all three. Only the
@@ -833,22 +991,15 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
         for (int j = 0; j < 3; j++) {
           const int K = c.rb_kernels[j], dl = c.rb_dilations[j][di];
           fl[j] = NB * conv_flops(S.Cout, S.Cout, K, Lo);
-          auto base = [&](const uint16_t* in, int d2) {
-            ConvBf16Args a;
-            a.x = in; a.N = NB; a.dil = d2; a.padL = (K * d2 - d2) / 2; a.Lout = Lo; a.x_row = row; a.act_row = row; a.y_len = Lo;
-            a.act_alpha = 0.1f;
-            a.len_ptr = s.lensF; a.len_mul = Lo / F;
-            return a;
-          };
           float* dst = lastd ? (j == 2 ? m : r[j]) : tmp[j][di & 1];
           uint16_t* dst_act = lastd ? (j == 2 ? a_next : nullptr) : act[j][di & 1];
-          ConvBf16Args fin = base(c.resblock_type == 1 ? mid[j] : src_act[j], c.resblock_type == 1 ? 1 : dl);
+          ConvBf16Args fin = rb_args_bf16(b, c.resblock_type == 1 ? mid[j] : src_act[j], K, c.resblock_type == 1 ? 1 : dl, Lo, row);
           fin.res = src[j]; fin.y = dst; fin.act = dst_act;
           if (lastd && j == 2) { fin.mrf_a = r[0]; fin.mrf_b = r[1]; }
           bb[j] = fin;
           wb[j] = c.resblock_type == 1 ? &v->rb_b[u][j][2 * di + 1] : &v->rb_b[u][j][di];
           if (c.resblock_type == 1) {
-            aa[j] = base(src_act[j], dl);
+            aa[j] = rb_args_bf16(b, src_act[j], K, dl, Lo, row);
             aa[j].act = mid[j];
             wa[j] = &v->rb_b[u][j][2 * di];
           }
@@ -857,7 +1008,7 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
           if (!(lastd && j == 2)) tap_step(j, di, dst);
         }
         // ResBlock1 pairs that are not the stage's last: both convs in one launch, intermediate in LDS (rb_pair_bf16.hip)
-        static const bool no_pair = getenv("PIPER_HIP_NO_RB_PAIR") != nullptr;
+        const bool no_pair = no_rb_pair();
         if (c.resblock_type == 1 && !no_pair) {
           struct Pack { RbPairBf16Args a[3]; } pk;
           bool ok = true;
@@ -872,57 +1023,39 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
             q.act_row = row;
             q.wa = wa[j]->w; q.ba = wa[j]->bias; q.wb = wb[j]->w; q.bb = wb[j]->bias;
             q.Ka = wa[j]->K; q.dila = aa[j].dil; q.Kb = wb[j]->K; q.dilb = 1; q.alpha = 0.1f;
-            q.N = NB; q.C = S.Cout; q.L = Lo; q.len_ptr = s.lensF; q.len_mul = Lo / F;
+            q.N = NB; q.C = S.Cout; q.L = Lo; q.len_ptr = b.lensF; q.len_mul = Lo / F;
             ok = q.x && (q.y || q.act) && q.wa && q.wb && q.ba && q.bb && wa[j]->Cin == S.Cout && wa[j]->Cout == S.Cout && wb[j]->Cin == S.Cout && wb[j]->Cout == S.Cout &&
                  rb_pair_bf16_eligible(S.Cout, q.Ka, q.dila, q.Kb, q.dilb, Lo);
           }
           if (ok) {
-            piper_hip_ctx* ctx = v->ctx;
-            auto add_pairs = [&](const std::string& name, int first, int count, double flops) {
-              struct P2 { RbPairBf16Args a[3]; } p2;
-              for (int i = 0; i < 3; i++) p2.a[i] = pk.a[first + (i < count ? i : 0)];
-              Step st;
-              st.name = name;
-              st.tag = "conv_bf16";
-              st.flops = 2.0 * flops;
-              st.bytes = NB * count * (2.0 * 4.0 * S.Cout * (double)Lo);
-              st.run = [ctx, p2, count](hipStream_t q) { return launch_rb_pair_bf16_multi(ctx, q, p2.a, count); };
-              s.steps.push_back(std::move(st));
-            };
-            if (!lastd) add_pairs(nm + "ab_lrelu_conv_lrelu_conv_res_x3", 0, 3, fl[0] + fl[1] + fl[2]);
-            else {
+            if (lastd) {
               // all three last pairs in one launch (rb2 writes its own fp32 output), then the MRF mean as a small elementwise
               // launch: a single pair of a 128-channel stage is 96 blocks for 256 CUs (52 µs; r3h), the mean 8 µs
               pk.a[2].y = r[2]; pk.a[2].act = nullptr; pk.a[2].mrf_a = nullptr; pk.a[2].mrf_b = nullptr;
               tap_step(2, di, r[2]);
-              add_pairs(nm + "ab_lrelu_conv_lrelu_conv_res_x3", 0, 3, fl[0] + fl[1] + fl[2]);
-              Step st;
-              st.name = p + "mrf_mean" + (last_stage ? "" : "_lrelu_to_bf16");
+            }
+            b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16", 2.0 * (fl[0] + fl[1] + fl[2]), NB * 3 * (2.0 * 4.0 * S.Cout * (double)Lo),
+                   [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16_multi(ctx, q, pk.a, 3); });
+            if (lastd) {
+              const std::string mn = p + "mrf_mean" + (last_stage ? "" : "_lrelu_to_bf16");
               const float *r0 = r[0], *r1 = r[1], *r2 = r[2];
-              const int* lf = s.lensF;
+              const int* lf = b.lensF;
               const int Cc = S.Cout, lm = Lo / F;
-              if (last_stage) {  // conv_post applies its LeakyReLU(0.01) itself: slope 1 here
-                const int64_t cnt = (int64_t)NB * S.Cout * Lo;
-                st.run = [=](hipStream_t q) {
-                  const int grid = (int)std::min<int64_t>(ceil_div(cnt, (int64_t)kBlock * 4), 2048);
-                  hipLaunchKernelGGL(mrf_mean_lrelu_kernel, dim3(grid), dim3(kBlock), 0, q, r0, r1, r2, m, cnt, 1.0f);
-                  return PIPER_HIP_OK;
-                };
-              } else {
-                st.run = [=](hipStream_t q) { return pack_mean3_c8(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm); };
-              }
-              s.steps.push_back(st);
+              if (last_stage)  // conv_post applies its LeakyReLU(0.01) itself: slope 1 here
+                add_mrf_mean(b, mn, r0, r1, r2, m, (int64_t)NB * S.Cout * Lo, 1.0f);
+              else
+                b.step(mn, "", 0, 0, [=](hipStream_t q) { return pack_mean3_c8(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm); });
             }
             continue;
           }
         }
-        if (c.resblock_type == 1) add_conv_bf16_multi(v, s, nm + "a_lrelu_conv_x3", wa, aa, 3, fl[0] + fl[1] + fl[2]);
+        if (c.resblock_type == 1) b.conv_bf16_multi(nm + "a_lrelu_conv_x3", wa, aa, 3, fl[0] + fl[1] + fl[2]);
         const std::string bn = c.resblock_type == 1 ? "b" : "";
         if (!lastd) {
-          add_conv_bf16_multi(v, s, nm + bn + "_lrelu_conv_res_x3", wb, bb, 3, fl[0] + fl[1] + fl[2]);
+          b.conv_bf16_multi(nm + bn + "_lrelu_conv_res_x3", wb, bb, 3, fl[0] + fl[1] + fl[2]);
         } else {
-          add_conv_bf16_multi(v, s, nm + bn + "_lrelu_conv_res_x2", wb, bb, 2, fl[0] + fl[1]);
-          add_conv_bf16_multi(v, s, nm + bn + "_lrelu_conv_res_mrfmean", wb + 2, bb + 2, 1, fl[2]);
+          b.conv_bf16_multi(nm + bn + "_lrelu_conv_res_x2", wb, bb, 2, fl[0] + fl[1]);
+          b.conv_bf16_multi(nm + bn + "_lrelu_conv_res_mrfmean", wb + 2, bb + 2, 1, fl[2]);
         }
       }
       a_in = a_next;
@@ -933,17 +1066,12 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
     // The stage's three ResBlocks are independent chains of short, latency-bound launches that leave most CUs idle:
     // rb0 / rb1 run as side branches of the graph, rb2 on the main lane, joined before rb2's last conv (which folds the
     // MRF mean over all three).
-    if (s.parallel) {
-      Step f;
-      f.name = p + "fork";
-      f.kind = Step::FORK;
-      s.steps.push_back(f);
-    }
+    if (s.parallel) b.fork(p + "fork");
     for (int j = 0; j < c.n_rb; j++) {
       const int K = c.rb_kernels[j];
       const float* src = up;
       const uint16_t* src_act = a_up;
-      s.cur_lane = (j + 1 == c.n_rb) ? 0 : j + 1;
+      b.lane = (j + 1 == c.n_rb) ? 0 : j + 1;
       for (int di = 0; di < c.rb_n_dil; di++) {
         const int dil = c.rb_dilations[j][di];
         const bool lastd = di + 1 == c.rb_n_dil;
@@ -951,13 +1079,6 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
         float* dst = lastd ? (fuse_mean ? m : r[j]) : tmp[j][di & 1];
         uint16_t* dst_act = lastd ? (fuse_mean ? a_next : nullptr) : act[j][di & 1];
         const std::string nm = p + "rb" + std::to_string(j) + ".c" + std::to_string(di);
-        auto rbconv = [&](const uint16_t* in, int dl) {
-          ConvBf16Args a;
-          a.x = in; a.N = NB; a.dil = dl; a.padL = (K * dl - dl) / 2; a.Lout = Lo; a.x_row = row; a.act_row = row; a.y_len = Lo;
-          a.act_alpha = 0.1f;
-          a.len_ptr = s.lensF; a.len_mul = Lo / F;
-          return a;
-        };
         auto finish = [&](ConvBf16Args a) {  // the conv that closes the residual: x ← x + conv(…)
           a.res = src; a.y = dst; a.act = dst_act;
           if (fuse_mean) { a.mrf_a = r[0]; a.mrf_b = r[1]; }
@@ -965,48 +1086,32 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
         };
         const double fl = NB * conv_flops(S.Cout, S.Cout, K, Lo);
         auto join = [&]() {
-          if (!(fuse_mean && s.parallel)) return;
-          Step jn;
-          jn.name = p + "join";
-          jn.kind = Step::JOIN;
-          s.steps.push_back(jn);
+          if (fuse_mean && s.parallel) b.join(p + "join");
         };
         if (c.resblock_type == 1) {
-          ConvBf16Args a1 = rbconv(src_act, dil);
+          ConvBf16Args a1 = rb_args_bf16(b, src_act, K, dil, Lo, row);
           a1.act = mid[j];
-          add_conv_bf16(v, s, nm + "a_lrelu_conv", v->rb_b[u][j][2 * di], a1, fl);
+          b.conv_bf16(nm + "a_lrelu_conv", v->rb_b[u][j][2 * di], a1, fl);
           join();
-          add_conv_bf16(v, s, nm + (fuse_mean ? "b_lrelu_conv_res_mrfmean" : "b_lrelu_conv_res"), v->rb_b[u][j][2 * di + 1],
-                        finish(rbconv(mid[j], 1)), fl);
+          b.conv_bf16(nm + (fuse_mean ? "b_lrelu_conv_res_mrfmean" : "b_lrelu_conv_res"), v->rb_b[u][j][2 * di + 1],
+                      finish(rb_args_bf16(b, mid[j], K, 1, Lo, row)), fl);
         } else {
           join();
-          add_conv_bf16(v, s, nm + (fuse_mean ? "_lrelu_conv_res_mrfmean" : "_lrelu_conv_res"), v->rb_b[u][j][di],
-                        finish(rbconv(src_act, dil)), fl);
+          b.conv_bf16(nm + (fuse_mean ? "_lrelu_conv_res_mrfmean" : "_lrelu_conv_res"), v->rb_b[u][j][di],
+                      finish(rb_args_bf16(b, src_act, K, dil, Lo, row)), fl);
         }
         if (!fuse_mean) tap_step(j, di, dst);
         src = dst;
         src_act = dst_act;
       }
     }
-    s.cur_lane = 0;
+    b.lane = 0;
     a_in = a_next;
     mean = m;
     L = Lo;
   }
-  s.n_samples = L;
-  s.audio = ar.f32(B * L);
-  if (ar.rc) return ar.rc;
-  {
-    ConvArgs a;  // 32→1 k7: thread-per-output fp32 kernel on the fp32 mean, LeakyReLU(0.01) as its prologue
-    a.x = mean;
-    a.prologue = PRO_LRELU; a.alpha = 0.01f;
-    a.y = s.audio; a.N = NB; a.padL = 3; a.Lin = L; a.Lout = L;
-    a.len_ptr = s.lensF; a.len_mul = L / F;
-    a.x_batch_stride = (int64_t)v->conv_post.Cin * L; a.y_batch_stride = L; a.y_len = L;
-    a.epilogue = EPI_TANH;
-    add_conv(v, s, "dec.conv_post_tanh", v->conv_post, a, L);
-  }
-  return PIPER_HIP_OK;
+  // LeakyReLU(0.01) on the fp32 mean as conv_post's prologue
+  return add_conv_post(b, "dec.conv_post_tanh", mean, nullptr, nullptr, PRO_LRELU, L);
 }
 
 // fp32 HiFi-GAN generator with the stage's three ResBlocks advanced together: conv i of rb0, rb1, rb2 are independent and
@@ -1014,26 +1119,15 @@ int build_generator_bf16(piper_hip_voice* v, Slot& s, Arena& ar, const float* z,
 // (launch_conv_win_multi). The MRF mean (r0+r1+r2)/3 is folded into the consumer's staging (ConvTranspose of the next
 // stage / conv_post). Medium voice: 23 → 11 generator launches; high: 77 → 29. Returns UNSUPPORTED (nothing scheduled)
 // when a conv falls outside the window kernel's geometry, and the caller schedules the per-conv path instead.
-int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, int F, int NB) {
+int build_generator_merged(Builder& b, float* dec0) {
+  piper_hip_voice* v = b.v;
+  Arena& ar = b.ar;
+  const int F = b.F, NB = b.NB;
   const piper_hip_voice_config& c = v->cfg;
   piper_hip_ctx* ctx = v->ctx;
   const size_t B = (size_t)NB;
   if (c.n_rb != kWinMulti) return PIPER_HIP_ERR_UNSUPPORTED;
-  // A/B switches: PIPER_HIP_NO_PIPE=1 keeps round 1's one-tile-per-block window kernel; PIPER_HIP_PIPE_MIN_F (frames × batch)
-  // is the size below which the window kernel's in-block K-split still wins (very short utterances: fewer tiles than CUs)
-  // conv_pipe (persistent, chunk-pipelined) wins once a launch holds enough work to amortise its prologue and tail — the
-  // high voice's 128/256-channel stages: 89 vs 73 TFLOP/s — and loses to the one-tile-per-block window kernel on the medium
-  // voice at factor 8 (48 vs 46 µs per merged launch). Threshold on the launch's FLOPs; PIPER_HIP_PIPE_MIN_GFLOP overrides.
-  static const bool no_pipe = getenv("PIPER_HIP_NO_PIPE") != nullptr;
-  static const double pipe_min_flops = [] { const char* e = getenv("PIPER_HIP_PIPE_MIN_GFLOP"); return (e ? atof(e) : 5.0) * 1e9; }();
-  // r2f (factor 64): as a single-conv launch it also loses at 32 / 64 channels (135 vs 114 µs, 105 vs 100 µs: one chunk per
-  // tile leaves nothing to pipeline, and 2 blocks per CU hide less than the window kernel's 4) and wins from 128 channels up.
-  // ConvTranspose: it won (112 vs 145 µs) until the window kernel staged narrow windows with a flat index and kept the phases
-  // of a column range in one block; since then the window kernel wins at every size measured (factor 64: 126 / 121 vs
-  // 187 / 204 µs, 8 × factor 8: 111 / 119 vs 181 / 201 µs, high voice factor 32: 215 vs 312 µs) — never by default,
-  // PIPER_HIP_PIPE_CT_MIN_GFLOP=g brings it back for launches of ≥ g GFLOP.
-  static const double pipe_ct_min_flops = [] { const char* e = getenv("PIPER_HIP_PIPE_CT_MIN_GFLOP"); return e ? atof(e) * 1e9 : 1e30; }();
-  auto pipe_pays = [&](double launch_flops, int Cin, bool ct) { return !no_pipe && launch_flops >= (ct ? pipe_ct_min_flops : pipe_min_flops) && (ct || Cin >= 128); };
+  const GenF32Switches& sw = gen_f32_switches();
   {
     int L = F;
     for (int u = 0; u < c.n_ups; u++) {
@@ -1066,42 +1160,14 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
     // Read-only taps (tests/test_gpu_f32_exact.py), under the names of build_generator_bf16: names only — no launch, no copy, no buffer.
     // The ping-pong buffers keep the last two ResBlock steps; held[j][i] is the step whose output buf[j][i] holds when the stage has run.
     // A step fused inside a pair launch (ResBlock2: the first of the two) has no tensor and therefore no name.
-    auto tap_f32 = [&](const std::string& name, const float* ptr) { s.taps[name] = {ptr, S.Cout, Lo, Lo / F, (size_t)S.Cout * Lo}; };
+    auto tap_f32 = [&](const std::string& name, const float* ptr) { b.tap(name, ptr, S.Cout, Lo, Lo / F); };
     int held[kWinMulti][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
     auto holds = [&](float* const y[kWinMulti], int di) {
       for (int j = 0; j < kWinMulti; j++) held[j][y[j] == buf[j][1]] = di;
     };
     tap_f32(p + "up", up);
-    {  // ConvTranspose on lrelu(input) — input = conv_pre output, or the mean of the previous stage's ResBlocks
-      Step st;
-      st.name = p + (cur[1] ? "mrfmean_lrelu_convT" : "lrelu_convT");
-      st.tag = "conv_mfma";
-      st.flops = NB * 2.0 * S.Cin * S.Cout * (double)S.K * L;
-      st.bytes = NB * 4.0 * ((double)S.Cin * L * (cur[1] ? 3 : 1) + (double)S.Cout * Lo + (double)S.Cin * S.Cout * S.K + S.Cout);
-      const bool ct_pipe = pipe_pays(st.flops, S.Cin, true) && S.up.w5 && convt_pipe_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, L);
-      if (ct_pipe || (S.up.w4 && convt_win_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, L))) {
-        ConvWinArgs wa;
-        wa.x = cur[0]; wa.x2 = cur[1]; wa.x3 = cur[2]; wa.w4 = ct_pipe ? S.up.w5 : S.up.w4; wa.bias = S.up.bias; wa.y = up;
-        wa.pro_alpha = 0.1f;
-        wa.N = NB; wa.Cin = S.Cin; wa.Cout = S.Cout; wa.K = S.K; wa.Lin = L; wa.Lout = L; wa.y_len = Lo;
-        wa.ct_stride = S.stride; wa.ct_pad = S.pad;
-        wa.len_ptr = s.lensF; wa.len_mul = L / F;
-        if (ct_pipe) st.run = [ctx, wa](hipStream_t q) { return launch_conv_pipe_multi(ctx, q, &wa, 1); };
-        else st.run = [ctx, wa](hipStream_t q) { return launch_conv_win(ctx, q, wa); };
-      } else {
-        ConvArgs a;
-        a.x = cur[0]; a.x2 = cur[1]; a.x3 = cur[2];
-        a.prologue = cur[1] ? PRO_AVG3_LRELU : PRO_LRELU;
-        a.alpha = 0.1f;
-        a.y = up; a.N = NB; a.dil = -1; a.padL = 0; a.Lin = L; a.Lout = (Lo - 1 + S.pad) / S.stride + 1;
-        a.len_ptr = s.lensF; a.len_mul = L / F;
-        a.x_batch_stride = (int64_t)S.Cin * L; a.y_batch_stride = (int64_t)S.Cout * Lo; a.y_len = Lo;
-        a.epilogue = EPI_CONVT; a.ct_stride = S.stride; a.ct_padL = S.pad; a.ct_Lout = Lo;
-        a.w = S.up.w; a.w16 = S.up.w16; a.bias = S.up.bias; a.Cin = S.up.Cin; a.Cout = S.up.Cout; a.K = S.up.K;
-        st.run = [ctx, a](hipStream_t q) { return launch_conv_mfma(ctx, q, a); };
-      }
-      s.steps.push_back(st);
-    }
+    // ConvTranspose on lrelu(input) — input = conv_pre output, or the mean of the previous stage's ResBlocks
+    add_convt_f32(b, p + (cur[1] ? "mrfmean_lrelu_convT" : "lrelu_convT"), S, cur, 0.1f, up, L);
     const float* src[kWinMulti] = {up, up, up};
     auto add_multi = [&](const std::string& name, const ConvW* ws[kWinMulti], const float* const x[kWinMulti],
                          const float* const res[kWinMulti], float* const y[kWinMulti], const int dil[kWinMulti]) {
@@ -1109,33 +1175,24 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
       double fl = 0, by = 0;
       double launch_fl = 0;
       for (int j = 0; j < kWinMulti; j++) launch_fl += NB * conv_flops(ws[j]->Cout, ws[j]->Cin, ws[j]->K, Lo);
-      bool pipe = pipe_pays(launch_fl, ws[0]->Cin, false);
+      bool pipe = sw.pipe_pays(launch_fl, ws[0]->Cin, false);
       for (int j = 0; j < kWinMulti; j++)
         pipe = pipe && ws[j]->w5 && conv_pipe_eligible(ws[j]->Cout, ws[j]->Cin, ws[j]->K, dil[j], (ws[j]->K * dil[j] - dil[j]) / 2, Lo, Lo);
       for (int j = 0; j < kWinMulti; j++) {
-        ConvWinArgs& wa = pk.a[j];
         const ConvW& w = *ws[j];
-        wa.x = x[j]; wa.w4 = pipe ? w.w5 : w.w4; wa.bias = w.bias; wa.res = res[j]; wa.y = y[j];
-        wa.pro_alpha = 0.1f;
-        wa.N = NB; wa.Cin = w.Cin; wa.Cout = w.Cout; wa.K = w.K; wa.dil = dil[j]; wa.padL = (w.K * dil[j] - dil[j]) / 2;
-        wa.Lin = Lo; wa.Lout = Lo; wa.y_len = Lo;
-        wa.len_ptr = s.lensF; wa.len_mul = Lo / F;
+        pk.a[j] = win_args(b, w, x[j], res[j], y[j], dil[j], Lo);
+        if (pipe) pk.a[j].w4 = w.w5;
         fl += NB * conv_flops(w.Cout, w.Cin, w.K, Lo);
         by += NB * conv_bytes(w.Cin, w.Cout, w.K, Lo);
       }
-      Step st;
-      st.name = name;
-      if (pipe) st.run = [ctx, pk](hipStream_t q) { return launch_conv_pipe_multi(ctx, q, pk.a, kWinMulti); };
-      else st.run = [ctx, pk](hipStream_t q) { return launch_conv_win_multi(ctx, q, pk.a, kWinMulti); };
-      st.flops = fl; st.bytes = by;
-      st.tag = "conv_mfma";
-      s.steps.push_back(std::move(st));
+      if (pipe) b.step(name, "conv_mfma", fl, by, [ctx, pk](hipStream_t q) { return launch_conv_pipe_multi(ctx, q, pk.a, kWinMulti); });
+      else b.step(name, "conv_mfma", fl, by, [ctx, pk](hipStream_t q) { return launch_conv_win_multi(ctx, q, pk.a, kWinMulti); });
     };
     // two chained convs per launch, intermediate in LDS (rb_pair.hip): ResBlock1 — (convs1[di], convs2[di]); ResBlock2 —
     // steps (di, di+1). PIPER_HIP_NO_RB_PAIR=1 keeps the conv-by-conv schedule (A/B). Very short utterances (under 128 frames in the
     // launch: factors 1 and 2) leave the pair kernel's 256-column tiles too few blocks — 41 at factor 1 — and run conv by conv
     // (r2: factor 1 0.649 → 0.620 ms, factor 2 0.670 → 0.659; from factor 4 on the pair kernel wins). PIPER_HIP_RB_PAIR_MIN_F moves it.
-    static const bool no_pair_env = getenv("PIPER_HIP_NO_RB_PAIR") != nullptr;
+    const bool no_pair_env = no_rb_pair();
     static const int64_t pair_min_f = [] { const char* e = getenv("PIPER_HIP_RB_PAIR_MIN_F"); return e ? atoll(e) : 128ll; }();
     const bool no_pair = no_pair_env || (int64_t)F * NB < pair_min_f;
     auto add_pair = [&](const std::string& name, int ia, int ib, const int da[kWinMulti], const int db[kWinMulti], bool res_a, bool res_b_x,
@@ -1150,16 +1207,11 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
         RbPairArgs& a = pk.a[j];
         a.x = x[j]; a.y = y[j]; a.wa4 = wa.w4; a.ba = wa.bias; a.wb4 = wb.w4; a.bb = wb.bias;
         a.Ka = wa.K; a.dila = da[j]; a.Kb = wb.K; a.dilb = db[j]; a.res_a = res_a; a.res_b_x = res_b_x; a.alpha = 0.1f;
-        a.N = NB; a.C = wa.Cin; a.L = Lo; a.len_ptr = s.lensF; a.len_mul = Lo / F;
+        a.N = NB; a.C = wa.Cin; a.L = Lo; a.len_ptr = b.lensF; a.len_mul = Lo / F;
         fl += NB * (conv_flops(wa.Cout, wa.Cin, wa.K, Lo) + conv_flops(wb.Cout, wb.Cin, wb.K, Lo));
         by += NB * 4.0 * (2.0 * wa.Cin * (double)Lo + (double)wa.Cin * wa.Cin * (wa.K + wb.K) + 2.0 * wa.Cin);  // x in, y out, weights
       }
-      Step st;
-      st.name = name;
-      st.run = [ctx, pk](hipStream_t q) { return launch_rb_pair_multi(ctx, q, pk.a, kWinMulti); };
-      st.flops = fl; st.bytes = by;
-      st.tag = "conv_mfma";
-      s.steps.push_back(std::move(st));
+      b.step(name, "conv_mfma", fl, by, [ctx, pk](hipStream_t q) { return launch_rb_pair_multi(ctx, q, pk.a, kWinMulti); });
       return true;
     };
     for (int di = 0; di < c.rb_n_dil; di++) {
@@ -1202,344 +1254,19 @@ int build_generator_merged(piper_hip_voice* v, Slot& s, Arena& ar, float* dec0, 
     for (int j = 0; j < kWinMulti; j++) cur[j] = src[j];
     L = Lo;
   }
-  s.n_samples = L;
-  s.audio = ar.f32(B * L);
-  if (ar.rc) return ar.rc;
-  {
-    ConvArgs a;
-    a.x = cur[0]; a.x2 = cur[1]; a.x3 = cur[2];
-    a.prologue = PRO_AVG3_LRELU; a.alpha = 0.01f;  // F.leaky_relu default slope before conv_post, on the MRF mean
-    a.y = s.audio; a.N = NB; a.padL = 3; a.Lin = L; a.Lout = L;
-    a.len_ptr = s.lensF; a.len_mul = L / F;
-    a.x_batch_stride = (int64_t)v->conv_post.Cin * L; a.y_batch_stride = L; a.y_len = L;
-    a.epilogue = EPI_TANH;
-    add_conv(v, s, "dec.mrfmean_conv_post_tanh", v->conv_post, a, L);
-  }
-  return PIPER_HIP_OK;
+  return add_conv_post(b, "dec.mrfmean_conv_post_tanh", cur[0], cur[1], cur[2], PRO_AVG3_LRELU, L);
 }
 
-// the duration predictor on the encoder output x [NB][H][T]: → s.dp_dur / "logw" tap
-int build_duration_predictor(piper_hip_voice* v, Slot& s, Arena& ar, const float* x, int T, int NB);
-
-// mode 0: whole utterance; 1: generator only (streaming window); 2: text encoder + projection + duration predictor;
-// 3: everything AFTER the text encoder (expansion, flow, generator) from an m_p / logs_p tensor copied in from a mode-2 plan —
-// the pair (2, 3) is a whole utterance with predicted durations that runs the encoder once
-int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, int mode = 0) {
-  const bool gen_only = mode == 1;
-  const bool from_stats = mode == 3;
+// fp32 HiFi-GAN generator conv by conv: the stage's ResBlocks as three lanes between a fork and a join, the MRF mean + LeakyReLU folded
+// into the stage's very last conv (PIPER_HIP_PARALLEL_RB: a launch of its own after the join).
+int build_generator_f32_per_conv(Builder& b, float* dec0) {
+  piper_hip_voice* v = b.v;
+  Arena& ar = b.ar;
+  const int F = b.F, NB = b.NB;
   const piper_hip_voice_config& c = v->cfg;
   piper_hip_ctx* ctx = v->ctx;
-  const int H = c.hidden, I = c.inter, d = H / c.n_heads;
-  slot_release(v, s, false);
-  static const bool parallel_rb = getenv("PIPER_HIP_PARALLEL_RB") != nullptr;
-  static const bool use_win = getenv("PIPER_HIP_NO_WIN") == nullptr;  // window kernel for the generator's long rows
-  static const bool no_pipe1 = getenv("PIPER_HIP_NO_PIPE") != nullptr;
-  static const double pipe_min_flops1 = [] { const char* e = getenv("PIPER_HIP_PIPE_MIN_GFLOP"); return (e ? atof(e) : 5.0) * 1e9; }();
-  static const double pipe_ct_min_flops1 = [] { const char* e = getenv("PIPER_HIP_PIPE_CT_MIN_GFLOP"); return e ? atof(e) * 1e9 : 1e30; }();
-  auto pipe_pays1 = [&](double launch_flops, int Cin, bool ct) { return !no_pipe1 && launch_flops >= (ct ? pipe_ct_min_flops1 : pipe_min_flops1) && (ct || Cin >= 128); };
-  Arena ar{v, &s};
-  if (c.n_rb != 3) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice: n_rb=%d (only the 3-kernel MRF of Piper voices is scheduled)", c.n_rb);
-  s.T = T; s.F = F; s.NB = NB;
-  s.kind = mode;
-  s.prec = v->precision;
-  s.arena_bytes = 0;
-  s.parallel = parallel_rb;
   const size_t B = (size_t)NB;
-  s.lensT = (int*)ar.raw(B * sizeof(int));
-  s.lensF = (int*)ar.raw(B * sizeof(int));
-  if (ar.rc) return ar.rc;
-  const int* lensT = s.lensT;
-  const int* lensF = s.lensF;
-  // lens = the per-item true lengths the rows of this conv are measured in (phonemes or frames), mul = positions per unit
-  auto plain = [&](const float* in, float* out, int Cin_, int Cout_, int L, const int* lens, int mul = 1) {
-    ConvArgs a;
-    a.x = in; a.y = out; a.N = NB; a.Lin = L; a.Lout = L; a.x_batch_stride = (int64_t)Cin_ * L; a.y_batch_stride = (int64_t)Cout_ * L;
-    a.y_len = L;
-    a.len_ptr = lens; a.len_mul = mul;
-    return a;
-  };
-  const float* z = nullptr;
-  float* dec0 = nullptr;
-  if (gen_only) {  // streaming: only the generator, over a window of the latent that the caller copies into zin
-    s.zin = ar.f32(B * (size_t)I * F);
-    dec0 = ar.f32(B * (size_t)c.up_initial * F);
-    if (ar.rc) return ar.rc;
-    z = s.zin;
-  } else {
-  s.ids = (int64_t*)ar.raw(B * T * sizeof(int64_t));
-  s.frame2id = (int32_t*)ar.raw(B * F * sizeof(int32_t));
-  s.noise = ar.f32(B * I * F);
-  s.noise_scale = ar.f32(B);
-  s.rng = (unsigned*)ar.raw(B * 2 * sizeof(unsigned));
-  // ---------------- text encoder
-  float* x = ar.f32(B * (size_t)H * T);
-  float* x1 = ar.f32(B * (size_t)H * T);
-  float* qkv = ar.f32(B * (size_t)3 * H * T);
-  float* att = ar.f32(B * (size_t)H * T);
-  // long rows: the attention core runs key-split in two parts plus a merge (attention.hip); scratch for the parts, shared by the layers
-  const int att_parts = rel_attention_split_parts(ctx, NB, c.n_heads, H / std::max(1, c.n_heads), T, c.window);
-  float* att_po = att_parts > 1 ? ar.f32(B * (size_t)att_parts * H * T) : nullptr;
-  float* att_pml = att_parts > 1 ? ar.f32(B * (size_t)c.n_heads * att_parts * 2 * T) : nullptr;
-  float* y = ar.f32(B * (size_t)H * T);
-  float* ff = ar.f32(B * (size_t)c.ffn * T);
-  float* stats = ar.f32(B * (size_t)2 * I * T);
-  float* zp = ar.f32(B * (size_t)I * F);
-  float* zflip = ar.f32(B * (size_t)I * F);
-  float* zp_tap = ar.f32(B * (size_t)I * F);
-  float* h = ar.f32(B * (size_t)H * F);
-  float* acts = ar.f32(B * (size_t)H * F);
-  float* skip = ar.f32(B * (size_t)H * F);
-  dec0 = ar.f32(B * (size_t)c.up_initial * F);
-  if (ar.rc) return ar.rc;
-  s.stats = stats;
-  if (!from_stats) {
-  {
-    Step st;
-    st.name = "embed";
-    const int64_t* ids = s.ids;
-    const float* emb = tensor(v, "enc_p.emb.weight");
-    const int nv = c.n_vocab;
-    const float scale = sqrtf((float)H);
-    st.run = [=](hipStream_t q) {
-      const int grid = (int)std::min<int64_t>(ceil_div((int64_t)H * T, kBlock), 2048);
-      hipLaunchKernelGGL(embed_kernel, dim3(grid, NB), dim3(kBlock), 0, q, ids, emb, x, H, T, nv, scale);
-      return PIPER_HIP_OK;
-    };
-    s.steps.push_back(st);
-  }
-  const int kf = c.ffn_kernel;
-  // LayerNorms without launches of their own: the conv BEFORE a LayerNorm adds the residual and leaves per-column partial
-  // sums (stats_out), the conv AFTER it normalises its input on load (PRO_LN) and writes the normalised tensor once.
-  // PIPER_HIP_NO_LN_FUSE=1 keeps the add+LayerNorm kernels (A/B).
-  // Above ≈ 640 columns (r2: factor 64 and 8 × factor 8, T·NB = 896: 3.07–3.09 vs 3.10 ms, 2.87 vs 2.90 ms) the normalisation
-  // inside the consumers' K loops costs more than the twelve launches it saves; up to T·NB = 448 the fused form wins (factor 8:
-  // 0.853 vs 0.879 ms). PIPER_HIP_LN_FUSE_MAX_T moves the crossover.
-  static const bool ln_fuse = getenv("PIPER_HIP_NO_LN_FUSE") == nullptr;
-  static const int64_t ln_fuse_max_t = [] { const char* e = getenv("PIPER_HIP_LN_FUSE_MAX_T"); return e ? atoll(e) : 640ll; }();
-  const bool ln_ok = ln_fuse && (kf == 1 || kf == 3) && v->proj.mfma && H <= 256 && (int64_t)T * NB <= ln_fuse_max_t;
-  float* st1 = ln_ok ? ar.f32(B * (size_t)ceil_div(H, 16) * T * 2) : nullptr;
-  float* st2 = ln_ok ? ar.f32(B * (size_t)ceil_div(H, 16) * T * 2) : nullptr;
-  if (ar.rc) return ar.rc;
-  // Round 3: where conv_lean.hip takes all three consumers (qkv, ffn1, proj of one utterance: a block holds every channel of its
-  // columns), the CONSUMER computes the LayerNorm statistics of its own operand (ConvArgs::ln_self) and the producers are plain
-  // residual adds — no statistics tensor crosses the kernel boundary.
-  const bool ln_self = ln_ok && mode != 2 && conv_lean_ln_self_ok(ctx, H, 3 * H, 1, 0, T, NB) && conv_lean_ln_self_ok(ctx, H, c.ffn, kf, (kf - 1) / 2, T, NB) &&
-                       conv_lean_ln_self_ok(ctx, H, 2 * I, 1, 0, T, NB);
-  auto with_ln = [&](ConvArgs a, const float* stats, const float* g, const float* be, float* normalised) {
-    a.prologue = PRO_LN;
-    a.ln_stats = ln_self ? nullptr : stats; a.ln_self = ln_self ? 1 : 0;
-    a.ln_gamma = g; a.ln_beta = be; a.ln_out = normalised; a.ln_eps = 1e-5f;
-    return a;
-  };
-  for (int l = 0; l < c.n_layers; l++) {
-    const auto& L = v->enc[l];
-    const std::string p = "enc" + std::to_string(l) + ".";
-    if (ln_ok && l > 0)  // x = LN2 of the previous layer, applied to y = x1 + ffn2(…) on load; materialised into x
-      add_conv(v, s, p + "ln2_qkv", L.qkv, with_ln(plain(y, qkv, H, 3 * H, T, lensT), st2, v->enc[l - 1].g2, v->enc[l - 1].b2, x), T);
-    else
-    add_conv(v, s, p + "qkv", L.qkv, plain(x, qkv, H, 3 * H, T, lensT), T);
-    auto add_ln = [&](const std::string& nm, const float* a, const float* b, const float* g, const float* be, float* out) {
-      Step st;
-      st.name = nm;
-      st.tag = "add_layernorm";
-      st.run = [=](hipStream_t q) {
-        float* o = out;
-        return piper_hip_add_layernorm_f32(ctx, a, b, g, be, NB, H, T, 1e-5f, &o, (piper_hip_stream)q);
-      };
-      s.steps.push_back(st);
-    };
-    bool ln1_pending = false;  // LN1 still to be applied by ffn1's prologue (y holds x + conv_o(att), st1 its statistics)
-    // mm(2,T,T,96) ×2 + mm(2,T,2T−1,96) ×2 (SURVEY.md Appendix A)
-    const double att_flops = NB * 2.0 * c.n_heads * ((double)T * T * d * 2 + (double)T * (2 * T - 1) * d * 2);
-    const double att_bytes = NB * 4.0 * c.n_heads * (2.0 * ((double)T * d + (double)d * T + (double)T * T) + 2.0 * ((double)T * d + (double)d * (2 * T - 1) + (double)T * (2 * T - 1)));
-    if (L.o.w16 && attention_block_wanted() && attention_block_eligible(c.n_heads, d, c.window, T)) {
-      // attention + conv_o + Add + LayerNorm in one launch: the block owns every channel of its 16 columns
-      Step st;
-      st.name = p + "attention_o_add_ln1";
-      st.tag = "attention_block";
-      const float *ek = L.ek, *ev = L.ev, *wo = L.o.w16, *bo = L.o.bias, *g1 = L.g1, *b1 = L.b1;
-      const int nh = c.n_heads, w = c.window;
-      const int o_nsteps = (int)(packed_conv_floats(H, H, 1, 16) / ((size_t)ceil_div(H, 16) * 64));
-      st.run = [=](hipStream_t q) {
-        return launch_attention_block(ctx, q, qkv, qkv + (size_t)H * T, qkv + (size_t)2 * H * T, ek, ev, wo, bo, x, g1, b1, x1, NB, nh, d, T, w,
-                                      (int64_t)3 * H * T, (int64_t)H * T, lensT, o_nsteps, 1e-5f);
-      };
-      st.flops = att_flops + NB * conv_flops(H, H, 1, T);
-      st.bytes = att_bytes + NB * conv_bytes(H, H, 1, T);
-      s.steps.push_back(st);
-    } else {
-    {
-      Step st;
-      st.name = p + "rel_attention";
-      st.tag = "rel_attention";
-      const float *ek = L.ek, *ev = L.ev;
-      const int nh = c.n_heads, w = c.window;
-      st.run = [=](hipStream_t q) {
-        if (att_parts > 1)
-          return launch_rel_attention_split(ctx, q, qkv, qkv + (size_t)H * T, qkv + (size_t)2 * H * T, ek, ev, att, NB, nh, d, T, w,
-                                            (int64_t)3 * H * T, (int64_t)H * T, lensT, att_parts, att_po, att_pml);
-        return launch_rel_attention(ctx, q, qkv, qkv + (size_t)H * T, qkv + (size_t)2 * H * T, ek, ev, att, NB, nh, d, T, w,
-                                    (int64_t)3 * H * T, (int64_t)H * T, lensT);
-      };
-      st.flops = att_flops;
-      st.bytes = att_bytes;
-      s.steps.push_back(st);
-    }
-    if (ln_ok) {  // y = x + conv_o(att) with its LayerNorm statistics; the normalisation itself happens in ffn1's prologue
-      ConvArgs a = plain(att, y, H, H, T, lensT);
-      a.res = x; a.stats_out = ln_self ? nullptr : st1;
-      add_conv(v, s, p + (ln_self ? "o_add" : "o_add_stats"), L.o, a, T);
-      ln1_pending = true;
-    } else {
-    add_conv(v, s, p + "o", L.o, plain(att, y, H, H, T, lensT), T);
-    add_ln(p + "add_ln1", x, y, L.g1, L.b1, x1);
-    }
-    }
-    {
-      ConvArgs a = plain(ln1_pending ? y : x1, ff, H, c.ffn, T, lensT);
-      a.padL = (kf - 1) / 2;
-      if (ln1_pending) a = with_ln(a, st1, L.g1, L.b1, x1);
-      a.epilogue = EPI_RELU;
-      add_conv(v, s, p + (ln1_pending ? "ln1_ffn1_relu" : "ffn1_relu"), L.f1, a, T);
-      ConvArgs b = plain(ff, y, c.ffn, H, T, lensT);
-      b.padL = (kf - 1) / 2;
-      if (ln_ok) { b.res = x1; b.stats_out = ln_self ? nullptr : st2; }
-      add_conv(v, s, p + (ln_self ? "ffn2_add" : ln_ok ? "ffn2_add_stats" : "ffn2"), L.f2, b, T);
-    }
-    if (!ln_ok) add_ln(p + "add_ln2", x1, y, L.g2, L.b2, x);
-  }
-  s.taps["enc_out"] = {x, H, T, 0, (size_t)H * T};
-  if (mode == 2) {  // x must exist in memory for the predictor: with the LayerNorm folded into its consumer, materialise it
-    if (ln_ok && c.n_layers > 0) {
-      Step st;
-      st.name = "enc.ln2_final";
-      st.tag = "add_layernorm";
-      const float *g2 = v->enc[c.n_layers - 1].g2, *b2 = v->enc[c.n_layers - 1].b2;
-      st.run = [=](hipStream_t q) {
-        float* o = x;
-        return piper_hip_add_layernorm_f32(ctx, y, nullptr, g2, b2, NB, H, T, 1e-5f, &o, (piper_hip_stream)q);
-      };
-      s.steps.push_back(st);
-    }
-    add_conv(v, s, "enc.proj", v->proj, plain(x, stats, H, 2 * I, T, lensT), T);  // kept for the mode-3 plan that continues from here
-    return build_duration_predictor(v, s, ar, x, T, NB);
-  }
-  if (ln_ok && c.n_layers > 0)
-    add_conv(v, s, "enc.ln2_proj", v->proj, with_ln(plain(y, stats, H, 2 * I, T, lensT), st2, v->enc[c.n_layers - 1].g2, v->enc[c.n_layers - 1].b2, x), T);
-  else
-  add_conv(v, s, "enc.proj", v->proj, plain(x, stats, H, 2 * I, T, lensT), T);
-  }  // !from_stats
-  s.taps["m_p"] = {stats, I, T, 0, (size_t)2 * I * T};  // halves of the [2I, T] projection
-  s.taps["logs_p"] = {stats + (size_t)I * T, I, T, 0, (size_t)2 * I * T};
-  {
-    Step st;
-    st.name = "expand_noise";
-    const int32_t* f2i = s.frame2id;
-    const float* nz = s.noise;
-    const float* nsd = s.noise_scale;
-    const unsigned* rngd = s.rng;
-    st.run = [=](hipStream_t q) {
-      const int grid = (int)std::min<int64_t>(ceil_div((int64_t)I * F, kBlock), 4096);
-      hipLaunchKernelGGL(expand_noise_kernel, dim3(grid, NB), dim3(kBlock), 0, q, stats, f2i, nz, zp, zp_tap, I, T, F, nsd, rngd, lensF);
-      return PIPER_HIP_OK;
-    };
-    // path expansion counted as the reference's two MatMuls mm(1,F,192,T)
-    st.flops = NB * 2.0 * 2.0 * F * (double)I * T;
-    st.bytes = NB * 2.0 * 4.0 * ((double)F * T + (double)T * I + (double)F * I);
-    s.steps.push_back(st);
-  }
-  s.taps["z_p"] = {zp_tap, I, F, 1, (size_t)I * F};
-  // ---------------- flow (reverse)
-  bool flipped = false;
-  const int half = I / 2;
-  for (int f = c.n_flows - 1; f >= 0; f--) {
-    flipped = !flipped;
-    const auto& C = v->flows[f];
-    const std::string p = "flow" + std::to_string(f) + ".";
-    // post of this coupling + x1 − m + Flip + pre of the next one in ONE launch (flow_seam.hip); PIPER_HIP_NO_FLOW_SEAM=1 keeps them apart
-    static const bool no_seam = getenv("PIPER_HIP_NO_FLOW_SEAM") != nullptr;
-    auto seam_ok = [&](const piper_hip_voice::Coupling& A, const piper_hip_voice::Coupling& B) {
-      return !no_seam && I == 2 * half && flow_seam_eligible(H, half) && A.post.w16 && B.pre.w16 && A.post.bias && B.pre.bias && A.post.K == 1 && B.pre.K == 1 &&
-             A.post.Cin == H && A.post.Cout == half && B.pre.Cin == half && B.pre.Cout == H;
-    };
-    const bool pre_done = f + 1 < c.n_flows && seam_ok(v->flows[f + 1], C);  // the previous (f + 1) coupling's seam already wrote h
-    if (!pre_done) {
-      ConvArgs a = plain(zp, h, I, H, F, lensF);
-      a.in_ch_base = flipped ? I - 1 : 0;
-      a.in_ch_sign = flipped ? -1 : 1;
-      add_conv(v, s, p + "pre", C.pre, a, F);
-    }
-    for (int i = 0; i < c.wn_layers; i++) {
-      const bool last = i + 1 == c.wn_layers;
-      ConvArgs a = plain(h, acts, H, H, F, lensF);
-      a.padL = (c.wn_kernel - 1) / 2;
-      a.gate = 1;
-      add_conv(v, s, p + "wn" + std::to_string(i) + ".in_gate", C.in[i], a, F);
-      ConvArgs b = plain(acts, h, H, H, F, lensF);
-      b.y2 = skip; b.y2_batch_stride = (int64_t)H * F;
-      b.skip = i == 0 ? nullptr : skip;
-      if (last) b.epilogue = EPI_WN_SKIP_LAST;
-      else { b.epilogue = EPI_WN_RES_SKIP; b.wn_c = H; b.res = h; }
-      add_conv(v, s, p + "wn" + std::to_string(i) + ".res_skip", C.rs[i], b, F);
-    }
-    if (f > 0 && seam_ok(C, v->flows[f - 1])) {
-      const auto& Nx = v->flows[f - 1];
-      Step st;
-      st.name = p + "post_sub_flip_pre" + std::to_string(f - 1);
-      st.tag = "conv_mfma";
-      const float *p16 = C.post.w16, *pb = C.post.bias, *q16 = Nx.pre.w16, *qb = Nx.pre.bias;
-      const int ps = (int)(packed_conv_floats(half, H, 1, 16) / ((size_t)ceil_div(half, 16) * 64));
-      const int qs = (int)(packed_conv_floats(H, half, 1, 16) / ((size_t)ceil_div(H, 16) * 64));
-      const int ob = flipped ? I - 1 - half : half, os = flipped ? -1 : 1;
-      st.run = [=](hipStream_t q) { return launch_flow_seam(q, skip, zp, h, p16, pb, q16, qb, NB, H, half, F, ps, qs, ob, os, lensF); };
-      st.flops = NB * (conv_flops(half, H, 1, F) + conv_flops(H, half, 1, F));
-      st.bytes = NB * 4.0 * ((double)H * F + 2.0 * half * F + (double)H * F + 2.0 * half * H);
-      s.steps.push_back(st);
-    } else {
-      ConvArgs a = plain(skip, zp, H, I, F, lensF);
-      a.epilogue = EPI_RSUB;
-      a.res = zp;
-      a.out_ch_base = flipped ? I - 1 - half : half;
-      a.out_ch_sign = flipped ? -1 : 1;
-      add_conv(v, s, p + "post_sub", C.post, a, F);
-    }
-  }
-  z = zp;
-  if (flipped) {  // odd number of couplings: materialise the last Flip once
-    Step st;
-    st.name = "flow.final_flip";
-    st.run = [=](hipStream_t q) {
-      const int grid = (int)std::min<int64_t>(ceil_div((int64_t)I * F, kBlock), 4096);
-      hipLaunchKernelGGL(flip_channels_kernel, dim3(grid, NB), dim3(kBlock), 0, q, zp, zflip, I, F);
-      return PIPER_HIP_OK;
-    };
-    s.steps.push_back(st);
-    z = zflip;
-  }
-  s.z_out = z;
-  }  // !gen_only
-  s.taps["z"] = {z, I, F, 1, (size_t)I * F};
-  if (v->precision == PIPER_HIP_PRECISION_BF16) return build_generator_bf16(v, s, ar, z, dec0, F, NB);
-  // ---------------- HiFi-GAN generator
-  {
-    ConvArgs a = plain(z, dec0, I, c.up_initial, F, lensF);
-    a.padL = 3;
-    add_conv(v, s, "dec.conv_pre", v->conv_pre, a, F);
-  }
-  s.taps["dec_pre"] = {dec0, c.up_initial, F, 1, (size_t)c.up_initial * F};
-  static const bool no_merge = getenv("PIPER_HIP_NO_MERGED_RB") != nullptr;
-  // Advancing the three ResBlocks in one launch pays while a single conv cannot fill the chip (short utterances, small
-  // batches); with many tiles per conv (NB·F large) the per-conv schedule with the mean fused into its producer is faster
-  // (measured at 8 × factor 8: 2 650 vs 2 840 utterances/s).
-  // r2t: with two chained convs per launch (rb_pair.hip) the merged schedule is also the faster one for long rows;
-  // PIPER_HIP_MERGED_MAX_F restores a frames × batch limit for A/B runs.
-  static const int64_t merged_max = [] { const char* e = getenv("PIPER_HIP_MERGED_MAX_F"); return e ? (int64_t)atoll(e) : (int64_t)1 << 40; }();
-  if (use_win && !no_merge && !parallel_rb && (int64_t)NB * F <= merged_max) {
-    const size_t mark = s.steps.size();
-    const int rcm = build_generator_merged(v, s, ar, dec0, F, NB);
-    if (rcm != PIPER_HIP_ERR_UNSUPPORTED) return rcm;
-    s.steps.resize(mark);  // geometry outside the window kernel: schedule conv by conv below
-  }
+  const GenF32Switches& sw = gen_f32_switches();
   const float* cur[3] = {dec0, nullptr, nullptr};
   bool cur_is_mrf = false;
   int L = F;
@@ -1559,68 +1286,30 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, int mode =
     }
     if (ar.rc) return ar.rc;
     const std::string p = "dec.s" + std::to_string(u) + ".";
-    {
-      ConvArgs a;
-      a.x = cur[0];
-      a.prologue = cur_is_mrf ? PRO_NONE : PRO_LRELU;  // the MRF mean kernel already applied LeakyReLU(0.1)
-      a.alpha = 0.1f;
-      a.y = up; a.N = NB; a.dil = -1; a.padL = 0; a.Lin = L; a.Lout = (Lo - 1 + S.pad) / S.stride + 1;
-      a.len_ptr = s.lensF; a.len_mul = L / F;
-      a.x_batch_stride = (int64_t)S.Cin * L; a.y_batch_stride = (int64_t)S.Cout * Lo; a.y_len = Lo;
-      a.epilogue = EPI_CONVT; a.ct_stride = S.stride; a.ct_padL = S.pad; a.ct_Lout = Lo;
-      a.w = S.up.w; a.w16 = S.up.w16; a.bias = S.up.bias; a.Cin = S.up.Cin; a.Cout = S.up.Cout; a.K = S.up.K;
-      Step st;
-      st.name = p + "lrelu_convT";
-      st.tag = "conv_mfma";
-      const double ct_flops = NB * 2.0 * S.Cin * S.Cout * (double)S.K * L;
-      const bool ct_pipe1 = use_win && pipe_pays1(ct_flops, S.Cin, true) && S.up.w5 && convt_pipe_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, L);
-      if (ct_pipe1 || (use_win && S.up.w4 && convt_win_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, L))) {
-        ConvWinArgs wa;
-        wa.x = cur[0]; wa.w4 = ct_pipe1 ? S.up.w5 : S.up.w4; wa.bias = S.up.bias; wa.y = up;
-        wa.pro_alpha = cur_is_mrf ? 1.0f : 0.1f;
-        wa.N = NB; wa.Cin = S.Cin; wa.Cout = S.Cout; wa.K = S.K; wa.Lin = L; wa.Lout = L; wa.y_len = Lo;
-        wa.ct_stride = S.stride; wa.ct_pad = S.pad;
-        wa.len_ptr = s.lensF; wa.len_mul = L / F;
-        if (ct_pipe1) st.run = [ctx, wa](hipStream_t q) { return launch_conv_pipe_multi(ctx, q, &wa, 1); };
-        else st.run = [ctx, wa](hipStream_t q) { return launch_conv_win(ctx, q, wa); };
-      } else
-      st.run = [ctx, a](hipStream_t q) { return launch_conv_mfma(ctx, q, a); };
-      st.flops = NB * 2.0 * S.Cin * S.Cout * (double)S.K * L;  // convT(Cin,Cout,K,s,Lin)
-      st.bytes = NB * 4.0 * ((double)S.Cin * L + (double)S.Cout * Lo + (double)S.Cin * S.Cout * S.K + S.Cout);
-      s.steps.push_back(st);
-    }
-    {  // the stage's ResBlocks read the same `up` and write disjoint buffers: run them as parallel graph branches
-      Step f;
-      f.name = p + "fork";
-      f.kind = Step::FORK;
-      s.steps.push_back(f);
-    }
+    // the MRF mean kernel already applied LeakyReLU(0.1): slope 1 here
+    add_convt_f32(b, p + "lrelu_convT", S, cur, cur_is_mrf ? 1.0f : 0.1f, up, L);
+    b.fork(p + "fork");  // the stage's ResBlocks read the same `up` and write disjoint buffers: run them as parallel graph branches
     float* m = ar.f32(B * S.Cout * Lo);  // lrelu(mean of the three ResBlock outputs): input of the next stage
     if (ar.rc) return ar.rc;
     const float mean_alpha = (u + 1 == c.n_ups) ? 0.01f : 0.1f;  // F.leaky_relu default slope before conv_post
     // Read-only taps (tests/test_gpu_f32_exact.py): names only. Every step has a buffer of its own here, except the closing step of the
     // last ResBlock where the mean is folded into its epilogue; "mean_lrelu" is what the next stage (or conv_post) reads:
     // lrelu(MRF mean, 0.1), in the last stage lrelu(MRF mean, 0.01).
-    auto tap_f32 = [&](const std::string& name, const float* ptr) { s.taps[name] = {ptr, S.Cout, Lo, Lo / F, (size_t)S.Cout * Lo}; };
+    auto tap_f32 = [&](const std::string& name, const float* ptr) { b.tap(name, ptr, S.Cout, Lo, Lo / F); };
     tap_f32(p + "up", up);
     tap_f32(p + "mean_lrelu", m);
     for (int j = 0; j < c.n_rb; j++) {
-      s.cur_lane = j < 3 ? j : 0;
+      b.lane = j < 3 ? j : 0;
       const int K = c.rb_kernels[j];
       const float* src = up;
       for (int di = 0; di < c.rb_n_dil; di++) {
         const int dil = c.rb_dilations[j][di];
         const bool lastd = di + 1 == c.rb_n_dil;
         // the very last conv of the stage folds the MRF mean + LeakyReLU into its epilogue (r0, r1 are complete by then)
-        const bool fuse_mean = lastd && j + 1 == c.n_rb && !parallel_rb;
+        const bool fuse_mean = lastd && j + 1 == c.n_rb && !sw.parallel_rb;
         float* dst = lastd ? (fuse_mean ? m : r[j]) : ((di & 1) ? tmp2[j] : tmp[j]);
         const std::string nm = p + "rb" + std::to_string(j) + ".c" + std::to_string(di);
         if (!fuse_mean && di + 3 >= c.rb_n_dil) tap_f32(nm, dst);  // (tmp / tmp2 keep the last two steps before the closing one)
-        auto rbconv = [&](const float* in, const float* res, float* out, int dl) {
-          ConvArgs a = plain(in, out, S.Cout, S.Cout, Lo, lensF, Lo / F);
-          a.dil = dl; a.padL = (K * dl - dl) / 2; a.prologue = PRO_LRELU; a.alpha = 0.1f; a.res = res;
-          return a;
-        };
         auto with_mean = [&](ConvArgs a) {
           if (fuse_mean) {
             a.epilogue = EPI_MRF_MEAN;
@@ -1628,83 +1317,255 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, int mode =
           }
           return a;
         };
-        // long rows: the window kernel (conv_win.hip); otherwise the streaming kernel
+        // long rows: the window kernel (conv_win.hip), or the pipe kernel where it pays; otherwise the streaming kernel
         auto add_rb = [&](const std::string& name, const ConvW& w, const ConvArgs& a) {
-          if (!(use_win && w.w4 && conv_win_eligible(w.Cout, w.Cin, w.K, a.dil, a.padL, Lo, Lo))) {
-            add_conv(v, s, name, w, a, Lo);
+          if (!(sw.use_win && w.w4 && conv_win_eligible(w.Cout, w.Cin, w.K, a.dil, a.padL, Lo, Lo))) {
+            b.conv(name, w, a, Lo);
             return;
           }
-          ConvWinArgs wa;
-          wa.x = a.x; wa.w4 = w.w4; wa.bias = w.bias; wa.res = a.res; wa.y = a.y;
-          wa.pro_alpha = a.alpha;
-          if (a.epilogue == EPI_MRF_MEAN) { wa.mrf_a = a.mrf_a; wa.mrf_b = a.mrf_b; wa.out_alpha = a.alpha2; }
-          wa.N = NB; wa.Cin = w.Cin; wa.Cout = w.Cout; wa.K = w.K; wa.dil = a.dil; wa.padL = a.padL;
-          wa.Lin = Lo; wa.Lout = Lo; wa.y_len = Lo;
-          wa.len_ptr = s.lensF; wa.len_mul = Lo / F;
-          Step st;
-          st.name = name;
-          st.flops = NB * conv_flops(w.Cout, w.Cin, w.K, Lo);
-          if (pipe_pays1(st.flops, w.Cin, false) && w.w5 && conv_pipe_eligible(w.Cout, w.Cin, w.K, a.dil, a.padL, Lo, Lo)) {
+          ConvWinArgs wa = win_args(b, w, a.x, a.res, a.y, a.dil, Lo, a.epilogue == EPI_MRF_MEAN ? a.mrf_a : nullptr, a.mrf_b, a.alpha2);
+          const double flops = NB * conv_flops(w.Cout, w.Cin, w.K, Lo), bytes = NB * conv_bytes(w.Cin, w.Cout, w.K, Lo);
+          if (sw.pipe_pays(flops, w.Cin, false) && w.w5 && conv_pipe_eligible(w.Cout, w.Cin, w.K, a.dil, a.padL, Lo, Lo)) {
             wa.w4 = w.w5;
-            st.run = [ctx, wa](hipStream_t q) { return launch_conv_pipe_multi(ctx, q, &wa, 1); };
-          } else
-          st.run = [ctx, wa](hipStream_t q) { return launch_conv_win(ctx, q, wa); };
-          st.bytes = NB * conv_bytes(w.Cin, w.Cout, w.K, Lo);
-          st.lane = s.cur_lane;
-          st.tag = "conv_mfma";
-          s.steps.push_back(std::move(st));
+            b.step(name, "conv_mfma", flops, bytes, [ctx, wa](hipStream_t q) { return launch_conv_pipe_multi(ctx, q, &wa, 1); });
+          } else {
+            b.step(name, "conv_mfma", flops, bytes, [ctx, wa](hipStream_t q) { return launch_conv_win(ctx, q, wa); });
+          }
         };
         if (c.resblock_type == 1) {
-          add_rb(nm + "a_lrelu_conv", S.rb[j][2 * di], rbconv(src, nullptr, mid[j], dil));
+          add_rb(nm + "a_lrelu_conv", S.rb[j][2 * di], rb_args_f32(b, src, nullptr, mid[j], S.Cout, K, dil, Lo));
           add_rb(nm + (fuse_mean ? "b_lrelu_conv_res_mrfmean" : "b_lrelu_conv_res"), S.rb[j][2 * di + 1],
-                 with_mean(rbconv(mid[j], src, dst, 1)));
+                 with_mean(rb_args_f32(b, mid[j], src, dst, S.Cout, K, 1, Lo)));
         } else {
           add_rb(nm + (fuse_mean ? "_lrelu_conv_res_mrfmean" : "_lrelu_conv_res"), S.rb[j][di],
-                 with_mean(rbconv(src, src, dst, dil)));
+                 with_mean(rb_args_f32(b, src, src, dst, S.Cout, K, dil, Lo)));
         }
         src = dst;
       }
     }
-    s.cur_lane = 0;
-    {
-      Step jn;
-      jn.name = p + "join";
-      jn.kind = Step::JOIN;
-      s.steps.push_back(jn);
-    }
-    if (parallel_rb) {  // branches finish independently: the mean needs its own launch after the join
-      Step st;
-      st.name = p + "mrf_mean_lrelu";
-      const float *r0 = r[0], *r1 = r[1], *r2 = r[2];
-      const int64_t cnt = (int64_t)NB * S.Cout * Lo;
-      st.run = [=](hipStream_t q) {
-        const int grid = (int)std::min<int64_t>(ceil_div(cnt, (int64_t)kBlock * 4), 2048);
-        hipLaunchKernelGGL(mrf_mean_lrelu_kernel, dim3(grid), dim3(kBlock), 0, q, r0, r1, r2, m, cnt, mean_alpha);
-        return PIPER_HIP_OK;
-      };
-      s.steps.push_back(st);
-    }
+    b.lane = 0;
+    b.join(p + "join");
+    if (sw.parallel_rb)  // branches finish independently: the mean needs its own launch after the join
+      add_mrf_mean(b, p + "mrf_mean_lrelu", r[0], r[1], r[2], m, (int64_t)NB * S.Cout * Lo, mean_alpha);
     cur[0] = m; cur[1] = nullptr; cur[2] = nullptr;
     cur_is_mrf = true;
     L = Lo;
   }
-  s.n_samples = L;
-  s.audio = ar.f32(B * L);
-  if (ar.rc) return ar.rc;
+  // LeakyReLU(0.01) of the MRF mean was applied by the mean kernel
+  return add_conv_post(b, "dec.conv_post_tanh", cur[0], nullptr, nullptr, PRO_NONE, L);
+}
+
+// arena buffers of everything in front of the generator (planned by build_schedule)
+struct FrontBuffers {
+  float *x, *x1, *qkv, *att, *att_po, *att_pml, *y, *ff, *stats, *zp, *zflip, *zp_tap, *h, *acts, *skip;
+  int att_parts;
+};
+
+// ---------------- text encoder: embed, the layers, and the projection to m_p / logs_p. for_predictor: the encoder output x must exist in
+// memory (the duration predictor reads it), so a LayerNorm folded into its consumer is materialised.
+int build_encoder(Builder& b, const FrontBuffers& fb, bool for_predictor) {
+  piper_hip_voice* v = b.v;
+  Arena& ar = b.ar;
+  const int T = b.T, NB = b.NB;
+  const int* lensT = b.lensT;
+  const piper_hip_voice_config& c = v->cfg;
+  piper_hip_ctx* ctx = v->ctx;
+  const int H = c.hidden, I = c.inter, d = H / c.n_heads;
+  const size_t B = (size_t)NB;
+  float *x = fb.x, *x1 = fb.x1, *qkv = fb.qkv, *att = fb.att, *att_po = fb.att_po, *att_pml = fb.att_pml, *y = fb.y, *ff = fb.ff, *stats = fb.stats;
+  const int att_parts = fb.att_parts;
   {
-    ConvArgs a;
-    a.x = cur[0];
-    a.prologue = PRO_NONE;  // LeakyReLU(0.01) of the MRF mean was applied by the mean kernel
-    a.y = s.audio; a.N = NB; a.padL = 3; a.Lin = L; a.Lout = L;
-    a.len_ptr = s.lensF; a.len_mul = L / F;
-    a.x_batch_stride = (int64_t)v->conv_post.Cin * L; a.y_batch_stride = L; a.y_len = L;
-    a.epilogue = EPI_TANH;
-    add_conv(v, s, "dec.conv_post_tanh", v->conv_post, a, L);
+    const int64_t* ids = b.s.ids;
+    const float* emb = tensor(v, "enc_p.emb.weight");
+    const int nv = c.n_vocab;
+    const float scale = sqrtf((float)H);
+    b.step("embed", "", 0, 0, [=](hipStream_t q) {
+      const int grid = (int)std::min<int64_t>(ceil_div((int64_t)H * T, kBlock), 2048);
+      hipLaunchKernelGGL(embed_kernel, dim3(grid, NB), dim3(kBlock), 0, q, ids, emb, x, H, T, nv, scale);
+      return PIPER_HIP_OK;
+    });
   }
+  const int kf = c.ffn_kernel;
+  // LayerNorms without launches of their own: the conv BEFORE a LayerNorm adds the residual and leaves per-column partial
+  // sums (stats_out), the conv AFTER it normalises its input on load (PRO_LN) and writes the normalised tensor once.
+  // PIPER_HIP_NO_LN_FUSE=1 keeps the add+LayerNorm kernels (A/B).
+  // Above ≈ 640 columns (r2: factor 64 and 8 × factor 8, T·NB = 896: 3.07–3.09 vs 3.10 ms, 2.87 vs 2.90 ms) the normalisation
+  // inside the consumers' K loops costs more than the twelve launches it saves; up to T·NB = 448 the fused form wins (factor 8:
+  // 0.853 vs 0.879 ms). PIPER_HIP_LN_FUSE_MAX_T moves the crossover.
+  static const bool ln_fuse = getenv("PIPER_HIP_NO_LN_FUSE") == nullptr;
+  static const int64_t ln_fuse_max_t = [] { const char* e = getenv("PIPER_HIP_LN_FUSE_MAX_T"); return e ? atoll(e) : 640ll; }();
+  const bool ln_ok = ln_fuse && (kf == 1 || kf == 3) && v->proj.mfma && H <= 256 && (int64_t)T * NB <= ln_fuse_max_t;
+  float* st1 = ln_ok ? ar.f32(B * (size_t)ceil_div(H, 16) * T * 2) : nullptr;
+  float* st2 = ln_ok ? ar.f32(B * (size_t)ceil_div(H, 16) * T * 2) : nullptr;
+  if (ar.rc) return ar.rc;
+  // Round 3: where conv_lean.hip takes all three consumers (qkv, ffn1, proj of one utterance: a block holds every channel of its
+  // columns), the CONSUMER computes the LayerNorm statistics of its own operand (ConvArgs::ln_self) and the producers are plain
+  // residual adds — no statistics tensor crosses the kernel boundary.
+  const bool ln_self = ln_ok && !for_predictor && conv_lean_ln_self_ok(ctx, H, 3 * H, 1, 0, T, NB) && conv_lean_ln_self_ok(ctx, H, c.ffn, kf, (kf - 1) / 2, T, NB) &&
+                       conv_lean_ln_self_ok(ctx, H, 2 * I, 1, 0, T, NB);
+  auto with_ln = [&](ConvArgs a, const float* stats, const float* g, const float* be, float* normalised) {
+    a.prologue = PRO_LN;
+    a.ln_stats = ln_self ? nullptr : stats; a.ln_self = ln_self ? 1 : 0;
+    a.ln_gamma = g; a.ln_beta = be; a.ln_out = normalised; a.ln_eps = 1e-5f;
+    return a;
+  };
+  auto add_ln = [&](const std::string& nm, const float* a, const float* a2, const float* g, const float* be, float* out) {
+    b.step(nm, "add_layernorm", 0, 0, [=](hipStream_t q) {
+      float* o = out;
+      return piper_hip_add_layernorm_f32(ctx, a, a2, g, be, NB, H, T, 1e-5f, &o, (piper_hip_stream)q);
+    });
+  };
+  for (int l = 0; l < c.n_layers; l++) {
+    const auto& L = v->enc[l];
+    const std::string p = "enc" + std::to_string(l) + ".";
+    if (ln_ok && l > 0)  // x = LN2 of the previous layer, applied to y = x1 + ffn2(…) on load; materialised into x
+      b.conv(p + "ln2_qkv", L.qkv, with_ln(b.plain(y, qkv, H, 3 * H, T, lensT), st2, v->enc[l - 1].g2, v->enc[l - 1].b2, x), T);
+    else
+      b.conv(p + "qkv", L.qkv, b.plain(x, qkv, H, 3 * H, T, lensT), T);
+    bool ln1_pending = false;  // LN1 still to be applied by ffn1's prologue (y holds x + conv_o(att), st1 its statistics)
+    // mm(2,T,T,96) ×2 + mm(2,T,2T−1,96) ×2 (SURVEY.md Appendix A)
+    const double att_flops = NB * 2.0 * c.n_heads * ((double)T * T * d * 2 + (double)T * (2 * T - 1) * d * 2);
+    const double att_bytes = NB * 4.0 * c.n_heads * (2.0 * ((double)T * d + (double)d * T + (double)T * T) + 2.0 * ((double)T * d + (double)d * (2 * T - 1) + (double)T * (2 * T - 1)));
+    const float *ek = L.ek, *ev = L.ev;
+    const int nh = c.n_heads, w = c.window;
+    if (L.o.w16 && attention_block_wanted() && attention_block_eligible(c.n_heads, d, c.window, T)) {
+      // attention + conv_o + Add + LayerNorm in one launch: the block owns every channel of its 16 columns
+      const float *wo = L.o.w16, *bo = L.o.bias, *g1 = L.g1, *b1 = L.b1;
+      const int o_nsteps = (int)(packed_conv_floats(H, H, 1, 16) / ((size_t)ceil_div(H, 16) * 64));
+      b.step(p + "attention_o_add_ln1", "attention_block", att_flops + NB * conv_flops(H, H, 1, T), att_bytes + NB * conv_bytes(H, H, 1, T),
+             [=](hipStream_t q) {
+               return launch_attention_block(ctx, q, qkv, qkv + (size_t)H * T, qkv + (size_t)2 * H * T, ek, ev, wo, bo, x, g1, b1, x1, NB, nh, d, T, w,
+                                             (int64_t)3 * H * T, (int64_t)H * T, lensT, o_nsteps, 1e-5f);
+             });
+    } else {
+      b.step(p + "rel_attention", "rel_attention", att_flops, att_bytes, [=](hipStream_t q) {
+        if (att_parts > 1)
+          return launch_rel_attention_split(ctx, q, qkv, qkv + (size_t)H * T, qkv + (size_t)2 * H * T, ek, ev, att, NB, nh, d, T, w,
+                                            (int64_t)3 * H * T, (int64_t)H * T, lensT, att_parts, att_po, att_pml);
+        return launch_rel_attention(ctx, q, qkv, qkv + (size_t)H * T, qkv + (size_t)2 * H * T, ek, ev, att, NB, nh, d, T, w,
+                                    (int64_t)3 * H * T, (int64_t)H * T, lensT);
+      });
+      if (ln_ok) {  // y = x + conv_o(att) with its LayerNorm statistics; the normalisation itself happens in ffn1's prologue
+        ConvArgs a = b.plain(att, y, H, H, T, lensT);
+        a.res = x; a.stats_out = ln_self ? nullptr : st1;
+        b.conv(p + (ln_self ? "o_add" : "o_add_stats"), L.o, a, T);
+        ln1_pending = true;
+      } else {
+        b.conv(p + "o", L.o, b.plain(att, y, H, H, T, lensT), T);
+        add_ln(p + "add_ln1", x, y, L.g1, L.b1, x1);
+      }
+    }
+    {
+      ConvArgs a = b.plain(ln1_pending ? y : x1, ff, H, c.ffn, T, lensT);
+      a.padL = (kf - 1) / 2;
+      if (ln1_pending) a = with_ln(a, st1, L.g1, L.b1, x1);
+      a.epilogue = EPI_RELU;
+      b.conv(p + (ln1_pending ? "ln1_ffn1_relu" : "ffn1_relu"), L.f1, a, T);
+      ConvArgs a2 = b.plain(ff, y, c.ffn, H, T, lensT);
+      a2.padL = (kf - 1) / 2;
+      if (ln_ok) { a2.res = x1; a2.stats_out = ln_self ? nullptr : st2; }
+      b.conv(p + (ln_self ? "ffn2_add" : ln_ok ? "ffn2_add_stats" : "ffn2"), L.f2, a2, T);
+    }
+    if (!ln_ok) add_ln(p + "add_ln2", x1, y, L.g2, L.b2, x);
+  }
+  b.tap("enc_out", x, H, T, 0);
+  const bool ln2_pending = ln_ok && c.n_layers > 0;  // the last layer's LN2 is still to be applied to y
+  if (ln2_pending && for_predictor) add_ln("enc.ln2_final", y, nullptr, v->enc[c.n_layers - 1].g2, v->enc[c.n_layers - 1].b2, x);
+  if (ln2_pending && !for_predictor)
+    b.conv("enc.ln2_proj", v->proj, with_ln(b.plain(y, stats, H, 2 * I, T, lensT), st2, v->enc[c.n_layers - 1].g2, v->enc[c.n_layers - 1].b2, x), T);
+  else
+    b.conv("enc.proj", v->proj, b.plain(x, stats, H, 2 * I, T, lensT), T);  // (for the predictor: kept for the plan that continues from here)
   return PIPER_HIP_OK;
 }
 
-int build_duration_predictor(piper_hip_voice* v, Slot& s, Arena& ar, const float* x, int T, int NB) {
+// ---------------- expansion of m_p / logs_p to frames with the noise, and the flow (reverse). Returns where it leaves z.
+const float* build_flow(Builder& b, const FrontBuffers& fb) {
+  piper_hip_voice* v = b.v;
+  Slot& s = b.s;
+  const int T = b.T, F = b.F, NB = b.NB;
+  const int* lensF = b.lensF;
+  const piper_hip_voice_config& c = v->cfg;
+  const int H = c.hidden, I = c.inter;
+  float *stats = fb.stats, *zp = fb.zp, *zflip = fb.zflip, *zp_tap = fb.zp_tap, *h = fb.h, *acts = fb.acts, *skip = fb.skip;
+  {
+    const int32_t* f2i = s.frame2id;
+    const float* nz = s.noise;
+    const float* nsd = s.noise_scale;
+    const unsigned* rngd = s.rng;
+    // path expansion counted as the reference's two MatMuls mm(1,F,192,T)
+    b.step("expand_noise", "", NB * 2.0 * 2.0 * F * (double)I * T, NB * 2.0 * 4.0 * ((double)F * T + (double)T * I + (double)F * I), [=](hipStream_t q) {
+      const int grid = (int)std::min<int64_t>(ceil_div((int64_t)I * F, kBlock), 4096);
+      hipLaunchKernelGGL(expand_noise_kernel, dim3(grid, NB), dim3(kBlock), 0, q, stats, f2i, nz, zp, zp_tap, I, T, F, nsd, rngd, lensF);
+      return PIPER_HIP_OK;
+    });
+  }
+  b.tap("z_p", zp_tap, I, F, 1);
+  bool flipped = false;
+  const int half = I / 2;
+  for (int f = c.n_flows - 1; f >= 0; f--) {
+    flipped = !flipped;
+    const auto& C = v->flows[f];
+    const std::string p = "flow" + std::to_string(f) + ".";
+    // post of this coupling + x1 − m + Flip + pre of the next one in ONE launch (flow_seam.hip); PIPER_HIP_NO_FLOW_SEAM=1 keeps them apart
+    static const bool no_seam = getenv("PIPER_HIP_NO_FLOW_SEAM") != nullptr;
+    auto seam_ok = [&](const piper_hip_voice::Coupling& A, const piper_hip_voice::Coupling& B) {
+      return !no_seam && I == 2 * half && flow_seam_eligible(H, half) && A.post.w16 && B.pre.w16 && A.post.bias && B.pre.bias && A.post.K == 1 && B.pre.K == 1 &&
+             A.post.Cin == H && A.post.Cout == half && B.pre.Cin == half && B.pre.Cout == H;
+    };
+    const bool pre_done = f + 1 < c.n_flows && seam_ok(v->flows[f + 1], C);  // the previous (f + 1) coupling's seam already wrote h
+    if (!pre_done) {
+      ConvArgs a = b.plain(zp, h, I, H, F, lensF);
+      a.in_ch_base = flipped ? I - 1 : 0;
+      a.in_ch_sign = flipped ? -1 : 1;
+      b.conv(p + "pre", C.pre, a, F);
+    }
+    for (int i = 0; i < c.wn_layers; i++) {
+      const bool last = i + 1 == c.wn_layers;
+      ConvArgs a = b.plain(h, acts, H, H, F, lensF);
+      a.padL = (c.wn_kernel - 1) / 2;
+      a.gate = 1;
+      b.conv(p + "wn" + std::to_string(i) + ".in_gate", C.in[i], a, F);
+      ConvArgs a2 = b.plain(acts, h, H, H, F, lensF);
+      a2.y2 = skip; a2.y2_batch_stride = (int64_t)H * F;
+      a2.skip = i == 0 ? nullptr : skip;
+      if (last) a2.epilogue = EPI_WN_SKIP_LAST;
+      else { a2.epilogue = EPI_WN_RES_SKIP; a2.wn_c = H; a2.res = h; }
+      b.conv(p + "wn" + std::to_string(i) + ".res_skip", C.rs[i], a2, F);
+    }
+    if (f > 0 && seam_ok(C, v->flows[f - 1])) {
+      const auto& Nx = v->flows[f - 1];
+      const float *p16 = C.post.w16, *pb = C.post.bias, *q16 = Nx.pre.w16, *qb = Nx.pre.bias;
+      const int ps = (int)(packed_conv_floats(half, H, 1, 16) / ((size_t)ceil_div(half, 16) * 64));
+      const int qs = (int)(packed_conv_floats(H, half, 1, 16) / ((size_t)ceil_div(H, 16) * 64));
+      const int ob = flipped ? I - 1 - half : half, os = flipped ? -1 : 1;
+      b.step(p + "post_sub_flip_pre" + std::to_string(f - 1), "conv_mfma", NB * (conv_flops(half, H, 1, F) + conv_flops(H, half, 1, F)),
+             NB * 4.0 * ((double)H * F + 2.0 * half * F + (double)H * F + 2.0 * half * H),
+             [=](hipStream_t q) { return launch_flow_seam(q, skip, zp, h, p16, pb, q16, qb, NB, H, half, F, ps, qs, ob, os, lensF); });
+    } else {
+      ConvArgs a = b.plain(skip, zp, H, I, F, lensF);
+      a.epilogue = EPI_RSUB;
+      a.res = zp;
+      a.out_ch_base = flipped ? I - 1 - half : half;
+      a.out_ch_sign = flipped ? -1 : 1;
+      b.conv(p + "post_sub", C.post, a, F);
+    }
+  }
+  if (!flipped) return zp;
+  // odd number of couplings: materialise the last Flip once
+  b.step("flow.final_flip", "", 0, 0, [=](hipStream_t q) {
+    const int grid = (int)std::min<int64_t>(ceil_div((int64_t)I * F, kBlock), 4096);
+    hipLaunchKernelGGL(flip_channels_kernel, dim3(grid, NB), dim3(kBlock), 0, q, zp, zflip, I, F);
+    return PIPER_HIP_OK;
+  });
+  return zflip;
+}
+
+// the duration predictor on the encoder output x [NB][H][T]: → s.dp_dur / "logw" tap
+int build_duration_predictor(Builder& b, const float* x) {
+  piper_hip_voice* v = b.v;
+  Slot& s = b.s;
+  Arena& ar = b.ar;
+  const int T = b.T, NB = b.NB;
   const piper_hip_voice_config& c = v->cfg;
   piper_hip_ctx* ctx = v->ctx;
   const int H = c.hidden, nbins = c.dp_bins, K = c.dp_kernel;
@@ -1721,29 +1582,24 @@ int build_duration_predictor(piper_hip_voice* v, Slot& s, Arena& ar, const float
   s.dp_scalars = ar.raw(dp_scalars_bytes(NB));
   s.dp_dur = (int32_t*)ar.raw(B * T * sizeof(int32_t));
   if (ar.rc) return ar.rc;
-  const int* lensT = s.lensT;
+  const int* lensT = b.lensT;
   auto conv_k1 = [&](const std::string& name, const ConvW& w, const float* in, int64_t in_bs, float* out, const float* res) {
     ConvArgs a;
     a.x = in; a.y = out; a.N = NB; a.Lin = T; a.Lout = T; a.x_batch_stride = in_bs; a.y_batch_stride = (int64_t)w.Cout * T; a.y_len = T;
     a.len_ptr = lensT; a.res = res;
-    add_conv(v, s, name, w, a, T);
+    b.conv(name, w, a, T);
   };
   auto dds_stack = [&](const std::string& name, const std::vector<piper_hip_voice::DdsLayer>& layers, float* cur, float* other) {
     // layer i: cur → other, then swap; returns where the result lives
     int dil = 1;
     for (size_t i = 0; i < layers.size(); i++) {
       const auto& L = layers[i];
-      Step st;
-      st.name = name + ".dds" + std::to_string(i);
-      st.tag = "dds_layer";
       const float *src = cur, *dw_w = L.dw_w, *dw_b = L.dw_b, *g1 = L.g1, *b1 = L.b1, *pw = L.pw.w16, *pwb = L.pw.bias, *g2 = L.g2, *b2 = L.b2;
       float* dst = other;
       const int steps = (int)(packed_conv_floats(H, H, 1, 16) / ((size_t)ceil_div(H, 16) * 64));
       const int d2 = dil;
-      st.run = [=](hipStream_t q) { return launch_dds_layer(ctx, q, src, dw_w, dw_b, g1, b1, pw, pwb, g2, b2, dst, NB, H, T, K, d2, steps, lensT, 1e-5f); };
-      st.flops = NB * (conv_flops(H, H, 1, T) + conv_flops(H, 1, K, T));
-      st.bytes = NB * 4.0 * (2.0 * H * T + (double)H * H);
-      s.steps.push_back(st);
+      b.step(name + ".dds" + std::to_string(i), "dds_layer", NB * (conv_flops(H, H, 1, T) + conv_flops(H, 1, K, T)), NB * 4.0 * (2.0 * H * T + (double)H * H),
+             [=](hipStream_t q) { return launch_dds_layer(ctx, q, src, dw_w, dw_b, g1, b1, pw, pwb, g2, b2, dst, NB, H, T, K, d2, steps, lensT, 1e-5f); });
       std::swap(cur, other);
       dil *= K;
     }
@@ -1753,37 +1609,113 @@ int build_duration_predictor(piper_hip_voice* v, Slot& s, Arena& ar, const float
   conv_k1("dp.pre", v->dp[0].pre, x, (int64_t)H * T, a0, nullptr);
   float* r = dds_stack("dp", v->dp[0].dds, a0, a1);
   conv_k1("dp.proj", v->dp[0].proj, r, (int64_t)H * T, cond, nullptr);
-  {
-    Step st;
-    st.name = "dp.init_latent";
-    const float* nz = s.dp_noise;
-    const void* sc = s.dp_scalars;
-    st.run = [=](hipStream_t q) { return launch_dp_init(q, nz, sc, z, NB, T, lensT); };
-    s.steps.push_back(st);
-  }
-  for (size_t b = 1; b < v->dp.size(); b++) {
-    const auto& Bk = v->dp[b];
+  const float* nz = s.dp_noise;
+  const void* sc = s.dp_scalars;
+  b.step("dp.init_latent", "", 0, 0, [=](hipStream_t q) { return launch_dp_init(q, nz, sc, z, NB, T, lensT); });
+  for (size_t bi = 1; bi < v->dp.size(); bi++) {
+    const auto& Bk = v->dp[bi];
     const std::string p = "dp.flow" + std::to_string(Bk.flow);
     conv_k1(p + ".pre_add_cond", Bk.pre, z, (int64_t)2 * T, a0, cond);  // h = pre(z0) + g: the DDSConv's `x + g`
     float* hr = dds_stack(p, Bk.dds, a0, a1);
     conv_k1(p + ".proj", Bk.proj, hr, (int64_t)H * T, hsp, nullptr);
-    Step st;
-    st.name = p + ".spline_flip";
     const float tb = c.dp_tail_bound, fc = (float)H;
-    st.run = [=](hipStream_t q) { return launch_dp_spline(q, hsp, z, NB, T, nbins, tb, fc, lensT); };
-    s.steps.push_back(st);
+    b.step(p + ".spline_flip", "", 0, 0, [=](hipStream_t q) { return launch_dp_spline(q, hsp, z, NB, T, nbins, tb, fc, lensT); });
   }
   {
-    Step st;
-    st.name = "dp.affine_exp_ceil";
     const float *m = v->dp_m, *lg = v->dp_logs;
-    const void* sc = s.dp_scalars;
     int32_t* dur = s.dp_dur;
-    st.run = [=](hipStream_t q) { return launch_dp_final(q, z, m, lg, sc, logw, dur, NB, T, lensT); };
-    s.steps.push_back(st);
+    b.step("dp.affine_exp_ceil", "", 0, 0, [=](hipStream_t q) { return launch_dp_final(q, z, m, lg, sc, logw, dur, NB, T, lensT); });
   }
-  s.taps["logw"] = {logw, 1, T, 0, (size_t)T};
+  b.tap("logw", logw, 1, T, 0);
   return PIPER_HIP_OK;
+}
+
+// Buffer planning, then the builders of what the plan's kind asks for at the voice's precision.
+int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind kind = PLAN_WHOLE) {
+  const piper_hip_voice_config& c = v->cfg;
+  const int H = c.hidden, I = c.inter;
+  slot_release(v, s, false);
+  const GenF32Switches& sw = gen_f32_switches();
+  Builder b(v, s, T, F, NB);
+  Arena& ar = b.ar;
+  if (c.n_rb != 3) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice: n_rb=%d (only the 3-kernel MRF of Piper voices is scheduled)", c.n_rb);
+  s.T = T; s.F = F; s.NB = NB;
+  s.kind = kind;
+  s.prec = v->precision;
+  s.arena_bytes = 0;
+  s.parallel = sw.parallel_rb;
+  const size_t B = (size_t)NB;
+  s.lensT = (int*)ar.raw(B * sizeof(int));
+  s.lensF = (int*)ar.raw(B * sizeof(int));
+  if (ar.rc) return ar.rc;
+  b.lensT = s.lensT;
+  b.lensF = s.lensF;
+  const float* z = nullptr;
+  float* dec0 = nullptr;
+  if (kind == PLAN_GENERATOR) {  // streaming: only the generator, over a window of the latent that the caller copies into zin
+    s.zin = ar.f32(B * (size_t)I * F);
+    dec0 = ar.f32(B * (size_t)c.up_initial * F);
+    if (ar.rc) return ar.rc;
+    z = s.zin;
+  } else {
+    s.ids = (int64_t*)ar.raw(B * T * sizeof(int64_t));
+    s.frame2id = (int32_t*)ar.raw(B * F * sizeof(int32_t));
+    s.noise = ar.f32(B * I * F);
+    s.noise_scale = ar.f32(B);
+    s.rng = (unsigned*)ar.raw(B * 2 * sizeof(unsigned));
+    FrontBuffers fb{};
+    fb.x = ar.f32(B * (size_t)H * T);
+    fb.x1 = ar.f32(B * (size_t)H * T);
+    fb.qkv = ar.f32(B * (size_t)3 * H * T);
+    fb.att = ar.f32(B * (size_t)H * T);
+    // long rows: the attention core runs key-split in two parts plus a merge (attention.hip); scratch for the parts, shared by the layers
+    fb.att_parts = rel_attention_split_parts(v->ctx, NB, c.n_heads, H / std::max(1, c.n_heads), T, c.window);
+    fb.att_po = fb.att_parts > 1 ? ar.f32(B * (size_t)fb.att_parts * H * T) : nullptr;
+    fb.att_pml = fb.att_parts > 1 ? ar.f32(B * (size_t)c.n_heads * fb.att_parts * 2 * T) : nullptr;
+    fb.y = ar.f32(B * (size_t)H * T);
+    fb.ff = ar.f32(B * (size_t)c.ffn * T);
+    fb.stats = ar.f32(B * (size_t)2 * I * T);
+    fb.zp = ar.f32(B * (size_t)I * F);
+    fb.zflip = ar.f32(B * (size_t)I * F);
+    fb.zp_tap = ar.f32(B * (size_t)I * F);
+    fb.h = ar.f32(B * (size_t)H * F);
+    fb.acts = ar.f32(B * (size_t)H * F);
+    fb.skip = ar.f32(B * (size_t)H * F);
+    dec0 = ar.f32(B * (size_t)c.up_initial * F);
+    if (ar.rc) return ar.rc;
+    s.stats = fb.stats;
+    if (kind != PLAN_FROM_STATS) {
+      const int rc = build_encoder(b, fb, kind == PLAN_PREDICT);
+      if (rc) return rc;
+    }
+    if (kind == PLAN_PREDICT) return build_duration_predictor(b, fb.x);
+    b.tap("m_p", fb.stats, I, T, 0, (size_t)2 * I * T);  // halves of the [2I, T] projection
+    b.tap("logs_p", fb.stats + (size_t)I * T, I, T, 0, (size_t)2 * I * T);
+    z = s.z_out = build_flow(b, fb);
+  }
+  b.tap("z", z, I, F, 1);
+  if (v->precision == PIPER_HIP_PRECISION_BF16) return build_generator_bf16(b, z, dec0);
+  // ---------------- HiFi-GAN generator, fp32
+  {
+    ConvArgs a = b.plain(z, dec0, I, c.up_initial, F, b.lensF);
+    a.padL = 3;
+    b.conv("dec.conv_pre", v->conv_pre, a, F);
+  }
+  b.tap("dec_pre", dec0, c.up_initial, F, 1);
+  const bool no_merge = no_merged_rb();
+  // Advancing the three ResBlocks in one launch pays while a single conv cannot fill the chip (short utterances, small
+  // batches); with many tiles per conv (NB·F large) the per-conv schedule with the mean fused into its producer is faster
+  // (measured at 8 × factor 8: 2 650 vs 2 840 utterances/s).
+  // r2t: with two chained convs per launch (rb_pair.hip) the merged schedule is also the faster one for long rows;
+  // PIPER_HIP_MERGED_MAX_F restores a frames × batch limit for A/B runs.
+  static const int64_t merged_max = [] { const char* e = getenv("PIPER_HIP_MERGED_MAX_F"); return e ? (int64_t)atoll(e) : (int64_t)1 << 40; }();
+  if (sw.use_win && !no_merge && !sw.parallel_rb && (int64_t)NB * F <= merged_max) {
+    const size_t mark = s.steps.size();
+    const int rcm = build_generator_merged(b, dec0);
+    if (rcm != PIPER_HIP_ERR_UNSUPPORTED) return rcm;
+    s.steps.resize(mark);  // geometry outside the window kernel: schedule conv by conv below
+  }
+  return build_generator_f32_per_conv(b, dec0);
 }
 
 int run_schedule(Slot& s, hipStream_t q, bool parallel) {
@@ -2153,7 +2085,7 @@ int launch_plan(piper_hip_voice* v, Slot& s, hipStream_t on = nullptr) {
 
 // An idle plan for (kind, Tb, Fb, NB) at the voice's precision, built (schedule + arena; its graph follows its first run) if
 // the cache has none. *built reports whether this call paid for a build ("cold" prepare).
-int acquire_plan(piper_hip_voice* v, int kind, int Tb, int Fb, int NB, Slot** out, bool* built) {
+int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot** out, bool* built) {
   *built = false;
   for (auto& p : v->plans)
     if (!p->in_use && p->built && p->kind == kind && p->T == Tb && p->F == Fb && p->NB == NB && p->prec == v->precision) {
@@ -2223,7 +2155,7 @@ void detach(piper_hip_voice* v, int slot) {
 
 // The plan of bucket (kind, T, F, NB) on slot id `slot`: the one attached already if it matches, otherwise the attached one is detached and
 // the bucket's plan is taken from the cache (or built) and attached. Then, if `evict`, idle plans beyond the cache's bounds go.
-int attach_plan(piper_hip_voice* v, int slot, int kind, int T, int F, int NB, Slot** out, bool evict = true) {
+int attach_plan(piper_hip_voice* v, int slot, PlanKind kind, int T, int F, int NB, Slot** out, bool evict = true) {
   Slot* cur = v->attached[slot];
   if (!(cur && cur->built && cur->kind == kind && cur->T == T && cur->F == F && cur->NB == NB && cur->prec == v->precision)) {
     if (cur) detach(v, slot);
@@ -2269,7 +2201,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   // the predicted frames per id exactly as if the caller had supplied them
   std::vector<piper_hip_utterance> resolved;
   std::vector<int32_t> predicted;
-  Slot* dp_plan = nullptr;  // the encoder + predictor plan whose m_p / logs_p the main plan continues from (kind 3: no second encoder pass)
+  Slot* dp_plan = nullptr;  // the encoder + predictor plan whose m_p / logs_p the main plan continues from (PLAN_FROM_STATS: no second encoder pass)
   struct DpRelease {
     Slot*& p;
     ~DpRelease() { if (p) p->in_use = false; }
@@ -2313,7 +2245,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   const int T = bucket_t(Tmax), F = bucket_f((int)Fmax), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  const int kind = (dp_plan && dp_plan->stats && dp_plan->T == T && dp_plan->NB == n) ? 3 : 0;
+  const PlanKind kind = (dp_plan && dp_plan->stats && dp_plan->T == T && dp_plan->NB == n) ? PLAN_FROM_STATS : PLAN_WHOLE;
   Slot* cur = nullptr;
   if ((rc = attach_plan(v, slot, kind, T, F, n, &cur))) return rc;
   Slot& s = *cur;
@@ -2323,7 +2255,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);
   s.bounded_pending = false;
   release_dp(v, slot);
-  if (kind == 3)  // the predictor's plan has finished (predict synchronises): its projection becomes this plan's input
+  if (kind == PLAN_FROM_STATS)  // the predictor's plan has finished (predict synchronises): its projection becomes this plan's input
   {
     PH_HIP(hipMemcpyAsync(s.stats, dp_plan->stats, (size_t)n * 2 * I * T * sizeof(float), hipMemcpyDeviceToDevice, q), PIPER_HIP_ERR_LAUNCH);
     // the predictor plan goes back to the cache when this function returns: whatever runs on it next must not overwrite the
@@ -2463,7 +2395,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot* cur = nullptr;
-  if ((rc = attach_plan(v, slot, 3, T, F, n, &cur, false))) return rc;
+  if ((rc = attach_plan(v, slot, PLAN_FROM_STATS, T, F, n, &cur, false))) return rc;
   Slot& s = *cur;
   s.last_use = ++v->use_clock;
   PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);  // the previous request of this slot id: its staging and its predictor plan are idle now
@@ -2474,7 +2406,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   }
   if (!dp) {
     bool built = false;
-    if ((rc = acquire_plan(v, 2, T, 16, n, &dp, &built))) return rc;
+    if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &dp, &built))) return rc;
     dp->in_use = true;
     v->attached_dp[slot] = dp;
   }
@@ -2582,7 +2514,7 @@ int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int
   const int T = bucket_t(Tmax);
   Slot* pl = nullptr;
   bool built = false;
-  if ((rc = acquire_plan(v, 2, T, 16, n, &pl, &built))) return rc;
+  if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &pl, &built))) return rc;
   Slot& s = *pl;
   s.in_use = true;
   s.last_use = ++v->use_clock;
@@ -2941,7 +2873,7 @@ PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* h
   // generator-only plan of the window's bucket (first / interior / last windows of a stream usually share one)
   Slot* gs = nullptr;
   bool built = false;
-  int rc = acquire_plan(v, 1, 0, bucket_f(Fc), 1, &gs, &built);
+  int rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fc), 1, &gs, &built);
   if (rc) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
@@ -3118,7 +3050,7 @@ PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, fl
   // generator-only plan of the step's longest window at the group's batch size (rows past their end have length 0)
   Slot* gs = nullptr;
   bool built = false;
-  if ((rc = acquire_plan(v, 1, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
+  if ((rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
   const hipStream_t q = gs->set.stream;
