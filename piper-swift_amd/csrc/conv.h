@@ -103,6 +103,30 @@ int launch_conv_mfma(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a);
 // The k = 1 convs of one utterance with a minimal instruction count: conv_lean.hip. Same return convention as try_launch_conv_short.
 int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a);
 bool conv_lean_ln_self_ok(piper_hip_ctx* ctx, int Cin, int Cout, int K, int padL, int L, int N);
+// The linear tail of a reverse flow coupling as ONE k = 1 conv (conv_lean.hip: conv_k1_tail_kernel). The last WaveNet
+// layer's res_skip conv (H → H, skip only), post (H → half), x1 − m, the Flip and the next coupling's pre (half → H) have no
+// nonlinearity between them: fold_flow_tail multiplies them out once per voice (float64, rounded once) into the 16-row fragment image
+// the launch reads. seam = 0: the last coupling, whose tail ends at x1new.
+struct FlowTailArgs {
+  const float *acts = nullptr, *skip = nullptr;  // [N][H][F]: the last gated conv's output, the skip sum of the layers before it
+  const float* zin = nullptr;                    // [N][2·half][F]: the buffer that holds x1
+  float* zout = nullptr;                         // x1new goes here (seam: a different buffer, other row tiles read x1 as an operand)
+  float* h = nullptr;                            // [N][H][F]: the next coupling's pre (seam)
+  const float *w = nullptr, *bias = nullptr;     // fold_flow_tail's image and bias
+  const int* len_ptr = nullptr;
+  int N = 1, H = 0, half = 0, F = 0, seam = 0;
+  int out_ch_base = 0, out_ch_sign = 1;          // x1 row r ↔ physical channel out_ch_base + out_ch_sign·r of z
+};
+bool flow_tail_shape_ok(int H, int half);
+bool flow_tail_plan_ok(piper_hip_ctx* ctx, int H, int half, int F, int N);
+inline int flow_tail_steps(int H, int half, int seam) { return (2 * H + (seam ? half : 0)) / 4; }
+inline size_t flow_tail_image_floats(int H, int half, int seam) { return (size_t)((half + (seam ? H : 0)) / 16) * flow_tail_steps(H, half, seam) * 64; }
+inline size_t flow_tail_scratch_doubles(int H, int half) { return (size_t)half * (H + 1) + (size_t)H * H; }
+// w_rs / b_rs [H × H], w_post / b_post [half × H], w_pre / b_pre [H × half] (null: seam = 0): raw conv weights on the device.
+// x1_sign: the coupling's channel map (+1 / −1). scratch: flow_tail_scratch_doubles doubles, free for reuse behind this call on `s`.
+int fold_flow_tail(hipStream_t s, const float* w_rs, const float* b_rs, const float* w_post, const float* b_post, const float* w_pre, const float* b_pre,
+                   int H, int half, int x1_sign, double* scratch, float* image, float* bias);
+int launch_flow_tail(piper_hip_ctx* ctx, hipStream_t s, const FlowTailArgs& t);
 // Short rows (one utterance's encoder / flow convs): conv_short.hip. 1 = enqueued, 0 = not this kernel's case (use launch_conv_mfma's
 // streaming kernel), < 0 = error. Called by launch_conv_mfma.
 int try_launch_conv_short(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a);

@@ -123,6 +123,93 @@ __global__ __launch_bounds__(512) void conv_k1_kernel(const LeanArgs a, const in
   }
 }
 
+// ---- the linear tail of one flow coupling, folded into ONE k = 1 conv (fold_flow_tail packs its matrix when the voice is created) ----
+// Graph: the last WaveNet layer's res_skip conv (skip only), post, x1 − m, Flip and the next coupling's pre are 1×1 convs with no
+// nonlinearity between them, so both results are one matrix over tensors that exist once the last gated conv has finished:
+//   rows < half : x1new = x1 − (A1·acts + W_post·skip_acc + c1)             → z_out through the coupling's channel map (res − v)
+//   rows ≥ half : h'    = P·x1 − (P·A1)·acts − (P·W_post)·skip_acc + bias'  → h   (absent in the last coupling: NX = 0)
+// conv_k1_kernel with a contraction of three segments, each behind its own base pointer: a wave takes NX quads of x1 (ascending
+// physical rows of z_in: the fold ordered the matrix columns by them), NS of skip_acc and NA of acts — every load still base + lane +
+// immediate. Other row tiles read the old x1 as an operand, so z_out is never the buffer z_in lives in while there are h' rows.
+struct TailArgs {
+  const float *acts, *skip, *zin, *w, *bias;
+  float *zout, *h;
+  const int* len_ptr;
+  int L, half, rows, nsteps;
+  int x1_base_bytes;        // byte offset of the first (lowest) physical x1 row in a batch item of z
+  int out_ch_base, out_ch_sign;
+  int hs_batch_bytes, z_batch_bytes;
+  long long hs_bs, z_bs;    // floats between batch items of acts / skip / h, and of z
+};
+
+template <int NX, int NS, int NA>
+__global__ __launch_bounds__(512) void conv_k1_tail_kernel(const TailArgs a, const int nch) {
+  constexpr int NT = NX + NS + NA;
+  __shared__ float red_all[2 * 8 * 4 * 64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int mt = blockIdx.x, n = blockIdx.z;
+  const int lim = a.len_ptr ? min(a.len_ptr[n], a.L) : a.L;
+  int ch = blockIdx.y;
+  if (ch * 16 >= lim) return;
+  const int j = lane & 15, kk = lane >> 4;
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(a.acts + (long long)n * a.hs_bs), 0, a.hs_batch_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.skip + (long long)n * a.hs_bs), 0, a.hs_batch_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)(a.zin + (long long)n * a.z_bs), 0, a.z_batch_bytes, 0x00020000);
+  const float* wa = a.w + (((long long)mt * a.nsteps + wave * NT) << 6) + lane;
+  const int q_stride = 16 * a.L;  // bytes from one channel quad to the next
+  const int vrow = kk * a.L * 4;
+  const int sx = a.x1_base_bytes + wave * NX * q_stride, ss = wave * NS * q_stride, sa = wave * NA * q_stride;
+  float av[NT], bv[NT];
+#pragma unroll
+  for (int i = 0; i < NT; i++) av[i] = wa[i * 64];
+  auto request = [&](int c16) {
+    const int voff = vrow + min(c16 + j, a.L - 1) * 4;  // (columns past the row end are not stored)
+#pragma unroll
+    for (int i = 0; i < NX; i++) bv[i] = bload(rz, voff, sx + i * q_stride);
+#pragma unroll
+    for (int i = 0; i < NS; i++) bv[NX + i] = bload(rs, voff, ss + i * q_stride);
+#pragma unroll
+    for (int i = 0; i < NA; i++) bv[NX + NS + i] = bload(ra, voff, sa + i * q_stride);
+  };
+  request(ch * 16);
+  const int row = 16 * mt + 4 * kk + wave;
+  const float bias = wave < 4 ? a.bias[min(row, a.rows - 1)] : 0.0f;  // bias first, as in every conv here
+  const bool to_z = 16 * mt < a.half;                                  // block-uniform: half is a multiple of 16
+  for (int it = 0;; it++) {
+    const int t0 = ch * 16;
+    const int nxt = ch + (int)gridDim.y;
+    const bool more = nxt < nch && nxt * 16 < lim;  // block-uniform
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < NT; i++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[i], acc, 0, 0, 0);
+    if (more) request(nxt * 16);  // the next chunk's operands: on their way during the exchange and the epilogue
+    float* red = red_all + (it & 1) * (8 * 4 * 64);
+#pragma unroll
+    for (int r = 0; r < 4; r++) red[(wave * 4 + r) * 64 + lane] = acc[r];
+    __syncthreads();
+    if (wave < 4) {
+      const int col = t0 + j;
+      float v = bias;
+      float part[8];
+#pragma unroll
+      for (int s = 0; s < 8; s++) part[s] = red[(s * 4 + wave) * 64 + lane];
+#pragma unroll
+      for (int s = 0; s < 8; s++) v += part[s];
+      if (row < a.rows && col < a.L) {
+        if (to_z) {
+          const long long idx = (long long)n * a.z_bs + (long long)(a.out_ch_base + a.out_ch_sign * row) * a.L + col;
+          a.zout[idx] = a.zin[idx] - v;
+        } else {
+          a.h[(long long)n * a.hs_bs + (long long)(row - a.half) * a.L + col] = v;
+        }
+      }
+    }
+    if (!more) break;
+    ch = nxt;
+  }
+}
+
 // ---- the WaveNet gated conv (k taps, tanh·sigmoid) of one utterance, same diet ----
 // Weights: the gate-packed 16-row image (8 tanh rows + their 8 sigmoid rows per tile, pack_conv_weights_gate16). 8 waves split the
 // contraction (NQ channel quads each); a wave stages the [4·NQ] × [16 + K − 1] window of ITS channels in its own piece of LDS — the
@@ -651,6 +738,40 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_lean launch failed: %s", hipGetErrorString(e));
   return 1;
+}
+
+// ---- the folded tail of a flow coupling (conv_k1_tail_kernel) ----
+// The voice's widths the kernel is instantiated for: 8 waves × (3 + 6 + 6) channel quads (Piper's medium and high voices).
+bool flow_tail_shape_ok(int H, int half) { return H == 192 && half == 96; }
+
+// The launch's limits for one plan: those of the lean k = 1 convs (beyond them the general kernels that tile the columns through LDS
+// are the faster schedule, and the builder keeps it).
+bool flow_tail_plan_ok(piper_hip_ctx* ctx, int H, int half, int F, int N) {
+  static const bool off = getenv("PIPER_HIP_NO_LEAN") != nullptr;
+  if (off || !flow_tail_shape_ok(H, half) || F < 1 || N < 1 || N > 65535) return false;
+  const int64_t tiles = ceil_div(half + H, 16) * ceil_div(F, 16) * (int64_t)N;
+  return tiles <= 64 * (int64_t)ctx->num_cus && (int64_t)std::max(H, 2 * half) * F * 4 < 0x7fffffffLL;
+}
+
+int launch_flow_tail(piper_hip_ctx* ctx, hipStream_t s, const FlowTailArgs& t) {
+  if (!flow_tail_plan_ok(ctx, t.H, t.half, t.F, t.N) || !t.w || !t.bias || !t.acts || !t.skip || !t.zin || !t.zout || (t.seam && (!t.h || t.zin == t.zout)))
+    PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "flow_tail: H=%d half=%d F=%d N=%d not covered", t.H, t.half, t.F, t.N);
+  TailArgs a;
+  a.acts = t.acts; a.skip = t.skip; a.zin = t.zin; a.w = t.w; a.bias = t.bias; a.zout = t.zout; a.h = t.h; a.len_ptr = t.len_ptr;
+  a.L = t.F; a.half = t.half; a.rows = t.seam ? t.half + t.H : t.half;
+  a.nsteps = flow_tail_steps(t.H, t.half, t.seam);
+  // x1 row r lives in physical channel out_ch_base + out_ch_sign·r; the matrix columns follow the ascending physical rows
+  a.x1_base_bytes = (t.out_ch_sign > 0 ? t.out_ch_base : t.out_ch_base - (t.half - 1)) * t.F * 4;
+  a.out_ch_base = t.out_ch_base; a.out_ch_sign = t.out_ch_sign;
+  a.hs_bs = (long long)t.H * t.F; a.z_bs = (long long)2 * t.half * t.F;
+  a.hs_batch_bytes = (int)(a.hs_bs * 4); a.z_batch_bytes = (int)(a.z_bs * 4);
+  const int mtiles = a.rows / 16, nchunks = (int)ceil_div(t.F, 16);
+  const dim3 grid((unsigned)mtiles, (unsigned)chunk_groups(ctx, mtiles, nchunks, t.N), (unsigned)t.N);
+  if (t.seam) hipLaunchKernelGGL((conv_k1_tail_kernel<3, 6, 6>), grid, dim3(512), 0, s, a, nchunks);
+  else hipLaunchKernelGGL((conv_k1_tail_kernel<0, 6, 6>), grid, dim3(512), 0, s, a, nchunks);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "flow_tail launch failed: %s", hipGetErrorString(e));
+  return PIPER_HIP_OK;
 }
 
 }  // namespace ph

@@ -295,6 +295,8 @@ struct piper_hip_voice {
   struct Coupling {
     ConvW pre, post;
     std::vector<ConvW> in, rs;
+    // the linear tail (last res_skip, post, x1 − m, Flip, the next coupling's pre) as one matrix: fold_flow_tail, null when not folded
+    const float *tail_w = nullptr, *tail_b = nullptr;
   };
   std::vector<Coupling> flows;
   ConvW conv_pre, conv_post;
@@ -472,6 +474,30 @@ int compile_weights(piper_hip_voice* v, Packer& pk, bool dry, const std::vector<
     snprintf(nm, sizeof nm, "flow.flows.%d.post", 2 * f);
     C.post = make_conv(pk, dry, nm, I / 2, H, 1);
     v->flows.push_back(C);
+  }
+  // The folded tails (conv.h: FlowTailArgs). Coupling f's tail ends in the pre of coupling f − 1, the next one the reverse flow runs;
+  // coupling 0's ends at x1new. The reverse pass flips before every coupling, so coupling f sees its x1 through a reversed channel
+  // map exactly when n_flows − f is odd.
+  if (flow_tail_shape_ok(H, I / 2) && I % 2 == 0 && c.wn_layers >= 2 && c.n_flows >= 1) {
+    const int half = I / 2;
+    double* scratch = (double*)pk.take(2 * flow_tail_scratch_doubles(H, half));
+    for (int f = 0; f < c.n_flows; f++) {
+      auto& C = v->flows[f];
+      const int seam = f > 0;
+      float* img = pk.take(flow_tail_image_floats(H, half, seam));
+      float* tb = pk.take((size_t)half + (seam ? H : 0));
+      if (dry) continue;
+      auto raw = [&](const char* what, int g) {
+        snprintf(nm, sizeof nm, "flow.flows.%d.%s", 2 * g, what);
+        return std::string(nm);
+      };
+      const std::string rs = raw("enc.res_skip_layers.", f) + std::to_string(c.wn_layers - 1), post = raw("post", f), pre = raw("pre", std::max(f - 1, 0));
+      const int rc = fold_flow_tail(pk.s, tensor(v, rs + ".weight"), tensor(v, rs + ".bias"), tensor(v, post + ".weight"), tensor(v, post + ".bias"),
+                                    seam ? tensor(v, pre + ".weight") : nullptr, seam ? tensor(v, pre + ".bias") : nullptr, H, half,
+                                    (c.n_flows - f) % 2 ? -1 : 1, scratch, img, tb);
+      if (rc) return rc;
+      C.tail_w = img; C.tail_b = tb;
+    }
   }
   v->conv_pre = make_conv(pk, dry, "dec.conv_pre", c.up_initial, I, 7);
   int ch = c.up_initial;
@@ -1502,17 +1528,26 @@ const float* build_flow(Builder& b, const FrontBuffers& fb) {
   b.tap("z_p", zp_tap, I, F, 1);
   bool flipped = false;
   const int half = I / 2;
+  // post of a coupling + x1 − m + Flip + pre of the next one in ONE launch (flow_seam.hip); PIPER_HIP_NO_FLOW_SEAM=1 keeps them apart
+  static const bool no_seam = getenv("PIPER_HIP_NO_FLOW_SEAM") != nullptr;
+  auto seam_ok = [&](const piper_hip_voice::Coupling& A, const piper_hip_voice::Coupling& B) {
+    return !no_seam && I == 2 * half && flow_seam_eligible(H, half) && A.post.w16 && B.pre.w16 && A.post.bias && B.pre.bias && A.post.K == 1 && B.pre.K == 1 &&
+           A.post.Cin == H && A.post.Cout == half && B.pre.Cin == half && B.pre.Cout == H;
+  };
+  // … and with the last WaveNet layer's res_skip conv in front of them multiplied into the same matrix when the voice was created: one
+  // lean k = 1 launch per coupling (conv.h: FlowTailArgs). PIPER_HIP_NO_FLOW_FOLD=1 keeps the schedule above.
+  static const bool no_fold = getenv("PIPER_HIP_NO_FLOW_FOLD") != nullptr;
+  bool fold = !no_fold && c.wn_layers >= 2 && flow_tail_plan_ok(v->ctx, H, half, F, NB);
+  for (int f = 0; f < c.n_flows && fold; f++)
+    fold = v->flows[f].tail_w && v->flows[f].tail_b && (f == 0 || seam_ok(v->flows[f], v->flows[f - 1]));
+  // A folded seam's other row tiles read the old x1 as an operand, so it writes x1new to the OTHER of zp / zflip: the two halves of z
+  // (physical channels [0, half) and [half, I)) travel separately. zloc[k] is the buffer half k was last written to.
+  float* zloc[2] = {zp, zp};
   for (int f = c.n_flows - 1; f >= 0; f--) {
     flipped = !flipped;
     const auto& C = v->flows[f];
     const std::string p = "flow" + std::to_string(f) + ".";
-    // post of this coupling + x1 − m + Flip + pre of the next one in ONE launch (flow_seam.hip); PIPER_HIP_NO_FLOW_SEAM=1 keeps them apart
-    static const bool no_seam = getenv("PIPER_HIP_NO_FLOW_SEAM") != nullptr;
-    auto seam_ok = [&](const piper_hip_voice::Coupling& A, const piper_hip_voice::Coupling& B) {
-      return !no_seam && I == 2 * half && flow_seam_eligible(H, half) && A.post.w16 && B.pre.w16 && A.post.bias && B.pre.bias && A.post.K == 1 && B.pre.K == 1 &&
-             A.post.Cin == H && A.post.Cout == half && B.pre.Cin == half && B.pre.Cout == H;
-    };
-    const bool pre_done = f + 1 < c.n_flows && seam_ok(v->flows[f + 1], C);  // the previous (f + 1) coupling's seam already wrote h
+    const bool pre_done = f + 1 < c.n_flows && (fold || seam_ok(v->flows[f + 1], C));  // the previous (f + 1) coupling's seam already wrote h
     if (!pre_done) {
       ConvArgs a = b.plain(zp, h, I, H, F, lensF);
       a.in_ch_base = flipped ? I - 1 : 0;
@@ -1525,6 +1560,7 @@ const float* build_flow(Builder& b, const FrontBuffers& fb) {
       a.padL = (c.wn_kernel - 1) / 2;
       a.gate = 1;
       b.conv(p + "wn" + std::to_string(i) + ".in_gate", C.in[i], a, F);
+      if (last && fold) break;
       ConvArgs a2 = b.plain(acts, h, H, H, F, lensF);
       a2.y2 = skip; a2.y2_batch_stride = (int64_t)H * F;
       a2.skip = i == 0 ? nullptr : skip;
@@ -1532,32 +1568,48 @@ const float* build_flow(Builder& b, const FrontBuffers& fb) {
       else { a2.epilogue = EPI_WN_RES_SKIP; a2.wn_c = H; a2.res = h; }
       b.conv(p + "wn" + std::to_string(i) + ".res_skip", C.rs[i], a2, F);
     }
-    if (f > 0 && seam_ok(C, v->flows[f - 1])) {
+    const int ob = flipped ? I - 1 - half : half, os = flipped ? -1 : 1;
+    // what the graph ops behind a seam / a post_sub cost (the folded launch reports the ops it replaces, not its own matrix)
+    const double seam_flops = NB * (conv_flops(half, H, 1, F) + conv_flops(H, half, 1, F));
+    const double seam_bytes = NB * 4.0 * ((double)H * F + 2.0 * half * F + (double)H * F + 2.0 * half * H);
+    if (fold) {
+      const int xh = flipped ? 0 : 1;  // the half of z this coupling's x1 is
+      FlowTailArgs t;
+      t.acts = acts; t.skip = skip; t.zin = zloc[xh]; t.h = h; t.w = C.tail_w; t.bias = C.tail_b; t.len_ptr = lensF;
+      t.N = NB; t.H = H; t.half = half; t.F = F; t.seam = f > 0; t.out_ch_base = ob; t.out_ch_sign = os;
+      // a seam: the other buffer. The last coupling reads x1 in its epilogue only: it finishes where the other half already is.
+      t.zout = f > 0 ? (zloc[xh] == zp ? zflip : zp) : zloc[1 - xh];
+      zloc[xh] = t.zout;
+      piper_hip_ctx* ctx = v->ctx;
+      const std::string rs = p + "wn" + std::to_string(c.wn_layers - 1) + ".res_skip_";
+      const double rs_flops = NB * conv_flops(H, H, 1, F), rs_bytes = NB * conv_bytes(H, H, 1, F);
+      if (f > 0) b.step(rs + "post_sub_flip_pre" + std::to_string(f - 1), "conv_mfma", rs_flops + seam_flops, rs_bytes + seam_bytes, [=](hipStream_t q) { return launch_flow_tail(ctx, q, t); });
+      else b.step(rs + "post_sub", "conv_mfma", rs_flops + NB * conv_flops(half, H, 1, F), rs_bytes + NB * conv_bytes(H, half, 1, F), [=](hipStream_t q) { return launch_flow_tail(ctx, q, t); });
+    } else if (f > 0 && seam_ok(C, v->flows[f - 1])) {
       const auto& Nx = v->flows[f - 1];
       const float *p16 = C.post.w16, *pb = C.post.bias, *q16 = Nx.pre.w16, *qb = Nx.pre.bias;
       const int ps = (int)(packed_conv_floats(half, H, 1, 16) / ((size_t)ceil_div(half, 16) * 64));
       const int qs = (int)(packed_conv_floats(H, half, 1, 16) / ((size_t)ceil_div(H, 16) * 64));
-      const int ob = flipped ? I - 1 - half : half, os = flipped ? -1 : 1;
-      b.step(p + "post_sub_flip_pre" + std::to_string(f - 1), "conv_mfma", NB * (conv_flops(half, H, 1, F) + conv_flops(H, half, 1, F)),
-             NB * 4.0 * ((double)H * F + 2.0 * half * F + (double)H * F + 2.0 * half * H),
+      b.step(p + "post_sub_flip_pre" + std::to_string(f - 1), "conv_mfma", seam_flops, seam_bytes,
              [=](hipStream_t q) { return launch_flow_seam(q, skip, zp, h, p16, pb, q16, qb, NB, H, half, F, ps, qs, ob, os, lensF); });
     } else {
       ConvArgs a = b.plain(skip, zp, H, I, F, lensF);
       a.epilogue = EPI_RSUB;
       a.res = zp;
-      a.out_ch_base = flipped ? I - 1 - half : half;
-      a.out_ch_sign = flipped ? -1 : 1;
+      a.out_ch_base = ob;
+      a.out_ch_sign = os;
       b.conv(p + "post_sub", C.post, a, F);
     }
   }
-  if (!flipped) return zp;
+  float *z = zloc[0], *zother = z == zp ? zflip : zp;  // (both halves end in one buffer: the last coupling saw to that)
+  if (!flipped) return z;
   // odd number of couplings: materialise the last Flip once
   b.step("flow.final_flip", "", 0, 0, [=](hipStream_t q) {
     const int grid = (int)std::min<int64_t>(ceil_div((int64_t)I * F, kBlock), 4096);
-    hipLaunchKernelGGL(flip_channels_kernel, dim3(grid, NB), dim3(kBlock), 0, q, zp, zflip, I, F);
+    hipLaunchKernelGGL(flip_channels_kernel, dim3(grid, NB), dim3(kBlock), 0, q, z, zother, I, F);
     return PIPER_HIP_OK;
   });
-  return zflip;
+  return zother;
 }
 
 // the duration predictor on the encoder output x [NB][H][T]: → s.dp_dur / "logw" tap
