@@ -506,7 +506,22 @@ int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u,
  *   "dec.s{u}.mean_lrelu"    fp32 per-conv schedule: lrelu(MRF mean) as the next stage reads it (slope 0.1; last stage 0.01);
  *   "dec.s{u}.mean_act"      bf16, u < n_ups − 1: the bf16 image of lrelu(MRF mean, 0.1) as raw bits, [C_u / 8][len][8] bf16 words
  *                            (4 floats per position and channel group);
- *   "dec.mean"               bf16: the last stage's fp32 MRF mean. */
+ *   "dec.mean"               bf16: the last stage's fp32 MRF mean.
+ * Step selector. Name grammar:   ["predict:"] <tensor> ["@" <step name>]   |   ["predict:"] "@steps"
+ *   "<tensor>@<step name>"   the tensor as it stands right after the named step of the slot's schedule (step names: what
+ *                            piper_hip_voice_profile reports). The call waits for the slot's stream, runs the schedule's launches eagerly
+ *                            from the first step through the named one (the inputs staged by prepare are still in place), copies out as
+ *                            above, then runs the remaining steps, so every buffer ends in the state a full run leaves. An unknown step
+ *                            name is PIPER_HIP_ERR_ARG; a plan whose inputs do not persist (a generator-only stream window) and a bounded
+ *                            slot that has not been collected yet are PIPER_HIP_ERR_UNSUPPORTED.
+ *   Work buffers of the front half, reused layer after layer and therefore only meaningful with "@": "front.x", "front.x1", "front.att",
+ *   "front.y" [hidden,T], "front.qkv" [3·hidden,T], "front.ff" [ffn,T], "front.stats" [2·inter,T] (m_p ; logs_p), "front.zp",
+ *   "front.zflip" [inter,F] (the two buffers the halves of the flow's latent travel through), "front.h", "front.acts", "front.skip"
+ *   [hidden,F]; of the duration predictor: "dp.a0", "dp.a1", "dp.cond" [hidden,T], "dp.hsp" [3·bins − 1,T], "dp.z" [2,T], "dp.logw" [1,T],
+ *   "dp.dur" [1,T] (the int32 frames per id as raw bits).
+ *   "predict:<tensor>[@<step>]"  addresses the cached encoder + duration-predictor plan of the slot's bucket T and batch size (the plan a
+ *                            prepare without durations ran) with the slot's true lengths; PIPER_HIP_ERR_ARG when none is cached.
+ *   "@steps"                 the schedule's launch names in order, one per line, one character code per float. */
 int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name, float* host, size_t max_floats,
                         size_t* n_floats);
 /* GPU milliseconds of the slot's last completed launch (hipEvent pair on the slot's stream) ⇔

@@ -1679,6 +1679,14 @@ int build_duration_predictor(Builder& b, const float* x) {
     b.step("dp.affine_exp_ceil", "", 0, 0, [=](hipStream_t q) { return launch_dp_final(q, z, m, lg, sc, logw, dur, NB, T, lensT); });
   }
   b.tap("logw", logw, 1, T, 0);
+  // the predictor's work buffers ("@<step>" selector); dp.dur holds the int32 frames per id as raw bits
+  b.tap("dp.a0", a0, H, T, 0);
+  b.tap("dp.a1", a1, H, T, 0);
+  b.tap("dp.cond", cond, H, T, 0);
+  b.tap("dp.hsp", hsp, 3 * nbins - 1, T, 0);
+  b.tap("dp.z", z, 2, T, 0);
+  b.tap("dp.logw", logw, 1, T, 0);
+  b.tap("dp.dur", (const float*)s.dp_dur, 1, T, 0);
   return PIPER_HIP_OK;
 }
 
@@ -1736,6 +1744,19 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind k
     dec0 = ar.f32(B * (size_t)c.up_initial * F);
     if (ar.rc) return ar.rc;
     s.stats = fb.stats;
+    // The front half's work buffers as taps: reused layer after layer, so only meaningful with the "@<step>" selector of piper_hip_voice_tap.
+    b.tap("front.x", fb.x, H, T, 0);
+    b.tap("front.x1", fb.x1, H, T, 0);
+    b.tap("front.qkv", fb.qkv, 3 * H, T, 0);
+    b.tap("front.att", fb.att, H, T, 0);
+    b.tap("front.y", fb.y, H, T, 0);
+    b.tap("front.ff", fb.ff, c.ffn, T, 0);
+    b.tap("front.stats", fb.stats, 2 * I, T, 0);
+    b.tap("front.zp", fb.zp, I, F, 1);
+    b.tap("front.zflip", fb.zflip, I, F, 1);
+    b.tap("front.h", fb.h, H, F, 1);
+    b.tap("front.acts", fb.acts, H, F, 1);
+    b.tap("front.skip", fb.skip, H, F, 1);
     if (kind != PLAN_FROM_STATS) {
       const int rc = build_encoder(b, fb, kind == PLAN_PREDICT);
       if (rc) return rc;
@@ -3157,24 +3178,84 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
   if (!v || !name) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   Slot* sp = slot_plan(v, slot);
   if (!sp) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
-  Slot& s = *sp;
-  auto it = s.taps.find(name);
+  const Slot& owner = *sp;  // the true lengths of the items are the slot's
+  // grammar: ["predict:"] <tensor> ["@" <step name>]   |   ["predict:"] "@steps"
+  std::string full(name);
+  Slot* tp = sp;
+  if (full.compare(0, 8, "predict:") == 0) {  // the cached encoder + predictor plan of the slot's bucket T and batch size
+    full.erase(0, 8);
+    tp = nullptr;
+    for (auto& p : v->plans)
+      if (p->built && p->kind == PLAN_PREDICT && p->T == owner.T && p->NB == owner.NB && p->prec == v->precision) { tp = p.get(); break; }
+    if (!tp) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': no predictor plan of %d ids x %d items is cached", name, owner.T, owner.NB);
+  }
+  Slot& s = *tp;
+  const size_t at = full.find('@');
+  const std::string tensor_name = full.substr(0, at), step_name = at == std::string::npos ? std::string() : full.substr(at + 1);
+  if (at != std::string::npos && tensor_name.empty() && step_name == "steps") {
+    // the names of the schedule's launches in order, one per line, one character per float: what piper_hip_voice_profile reports, for a plan
+    // that no slot id reaches
+    std::string all;
+    for (const Step& st : s.steps)
+      if (st.kind == Step::LAUNCH) all += st.name + "\n";
+    if (n_floats) *n_floats = all.size();
+    if (host) {
+      if (max_floats < all.size()) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
+      for (size_t i = 0; i < all.size(); i++) host[i] = (float)(unsigned char)all[i];
+    }
+    return PIPER_HIP_OK;
+  }
+  auto it = s.taps.find(tensor_name);
   if (it == s.taps.end()) PH_FAIL(PIPER_HIP_ERR_ARG, "unknown tap '%s'", name);
   const Slot::Tap& t = it->second;
+  int upto = -1;  // index of the named step
+  if (at != std::string::npos) {
+    // the schedule replays from the inputs that prepare staged: they must still be in place
+    if (s.kind == PLAN_GENERATOR) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "tap '%s': a generator-only window plan keeps no inputs to replay from", name);
+    if (owner.bounded_pending) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "tap '%s': the slot's frame counts are still on the device (collect first)", name);
+    for (int i = 0; i < (int)s.steps.size() && upto < 0; i++)
+      if (s.steps[i].kind == Step::LAUNCH && s.steps[i].name == step_name) upto = i;
+    if (upto < 0) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': the schedule has no step '%s'", name, step_name.c_str());
+  }
   // items back to back, each compacted to its true length: [C][len_b]
   size_t total = 0;
-  for (int b = 0; b < s.NB; b++) total += (size_t)t.C * (size_t)(t.unit == 0 ? s.h_T[b] : s.h_F[b] * t.unit);
+  for (int b = 0; b < s.NB; b++) total += (size_t)t.C * (size_t)(t.unit == 0 ? owner.h_T[b] : owner.h_F[b] * t.unit);
   if (n_floats) *n_floats = total;
   if (host) {
     if (max_floats < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
     PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-    PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
+    if (tp != sp) {  // an idle plan has given its stream set back
+      PH_HIP(stream_wait(owner.set.stream), PIPER_HIP_ERR_LAUNCH);
+      const int rc = slot_init(v, s);
+      if (rc) return rc;
+    }
+    const hipStream_t q = s.set.stream;
+    PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);
+    auto run_range = [&](int from, int to) -> int {  // eagerly, in schedule order on the plan's stream (as piper_hip_voice_profile does)
+      for (int i = from; i < to; i++)
+        if (s.steps[i].kind == Step::LAUNCH) {
+          const int rc = s.steps[i].run(q);
+          if (rc) return rc;
+        }
+      PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
+      PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);
+      return PIPER_HIP_OK;
+    };
+    if (upto >= 0) {
+      const int rc = run_range(0, upto + 1);
+      if (rc) return rc;
+    }
     size_t off = 0;
     for (int b = 0; b < s.NB; b++) {
-      const size_t len = (size_t)(t.unit == 0 ? s.h_T[b] : s.h_F[b] * t.unit);
-      PH_HIP(hipMemcpy2D(host + off, len * sizeof(float), t.p + (size_t)b * t.batch_stride, (size_t)t.row * sizeof(float), len * sizeof(float),
-                         (size_t)t.C, hipMemcpyDeviceToHost), PIPER_HIP_ERR_LAUNCH);
+      const size_t len = (size_t)(t.unit == 0 ? owner.h_T[b] : owner.h_F[b] * t.unit);
+      if (len)
+        PH_HIP(hipMemcpy2D(host + off, len * sizeof(float), t.p + (size_t)b * t.batch_stride, (size_t)t.row * sizeof(float), len * sizeof(float),
+                           (size_t)t.C, hipMemcpyDeviceToHost), PIPER_HIP_ERR_LAUNCH);
       off += (size_t)t.C * len;
+    }
+    if (upto >= 0) {  // the rest of the schedule: every buffer ends as a full run leaves it
+      const int rc = run_range(upto + 1, (int)s.steps.size());
+      if (rc) return rc;
     }
   }
   return PIPER_HIP_OK;

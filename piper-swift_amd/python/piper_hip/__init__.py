@@ -1012,12 +1012,24 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
-    def tap(self, slot, name, max_floats):
-        out = np.empty(max_floats, np.float32)
+    def tap(self, slot, name, max_floats=None):
+        """A named intermediate of the slot, items back to back at their true lengths (max_floats None: sized by the library).
+        Name grammar (include/piper_hip.h): ["predict:"] <tensor> ["@" <step name>] — "front.x@enc2.ln2_qkv" is the work buffer x right
+        after that step (the schedule is replayed up to it, then finished); "predict:" addresses the cached encoder + predictor plan of the
+        slot's bucket; the front.* / dp.* work buffers are only meaningful with "@". See also steps()."""
         n = C.c_size_t()
+        if max_floats is None:
+            _check(self.lib.piper_hip_voice_tap(self.voice, slot, name.encode(), None, 0, C.byref(n)))
+            max_floats = max(int(n.value), 1)
+        out = np.empty(max_floats, np.float32)
         _check(self.lib.piper_hip_voice_tap(self.voice, slot, name.encode(), out.ctypes.data_as(c_f32p), max_floats,
                                             C.byref(n)))
         return out[:n.value]
+
+    def steps(self, slot, predict=False):
+        """Launch names of the slot's schedule in order (predict=True: of the cached encoder + predictor plan of its bucket)."""
+        raw = self.tap(slot, ("predict:" if predict else "") + "@steps")
+        return bytes(raw.astype(np.uint8)).decode().split("\n")[:-1]
 
     def last_gpu_ms(self, slot):
         ms = C.c_double()
