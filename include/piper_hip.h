@@ -488,6 +488,28 @@ int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio,
 int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames);
 int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples);
 int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item);
+/* Streaming pool: a batched stream whose rows are taken and freed while it runs (continuous batching for the generator). The closest
+ * reference role is still PiperMetalRuntime.synthesizeStream (PiperMetalRuntime.swift:82-115); the pool itself has no counterpart there.
+ * A session joins at any time, is active from the next stream_next_batch on, and frees its row with its last chunk or a stream_drop; the
+ * next join may take that row (free rows are handed out lowest index first). Each item's chunks are what stream_begin / stream_next give
+ * for that utterance alone (same windows; fp32 summation order). The generator batch is `capacity` rounded up to a power of two for the
+ * pool's whole life, as for a group, so groups and pools of one size share generator plans and no plan is built mid-stream.
+ * On a pool slot: stream_next_batch takes n_samples[capacity] and packs the chunks back to back in row order; all zero = the pool is idle
+ * (not closed). stream_drop(v, slot, item) drops the session in that row. stream_next returns PIPER_HIP_ERR_ARG. prepare*, stream_begin,
+ * stream_begin_batch and stream_pool_open on the slot close the pool first, as a prepare replaces a prepare; voice_destroy closes open pools.
+ * A refused join leaves nothing joined and the pool intact: more items than free rows = PIPER_HIP_ERR_SHAPE; work_slot == slot, or a
+ * work_slot that itself holds a pool = PIPER_HIP_ERR_ARG. After a join, piper_hip_voice_durations / piper_hip_voice_prepared_samples on
+ * work_slot report that join's items (it is a prepared slot). A join with supplied durations does not wait for its encoder + flow; with
+ * durations == NULL it keeps prepare_batch's host round trip for the predicted frame counts. */
+/* An empty pool of `capacity` rows (1 ≤ capacity ≤ 256) on `slot`; every step decodes chunk_frames frames per active row. */
+int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int capacity, int chunk_frames);
+/* Encoder + flow (and the predictor where durations == NULL) for n new utterances on `work_slot` (any other slot id; what it held is
+ * replaced, and it may be reused for another join or prepare as soon as this returns). Their latents move into free rows of the pool.
+ * items_out[n] = the rows taken (the item ids for n_samples / stream_drop). samples_out[n] = total samples each item will deliver. */
+int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
+                                     int* items_out, int64_t* samples_out);
+int piper_hip_voice_stream_pool_free_rows(const piper_hip_voice* v, int slot);   /* ≥ 0, or a negative status */
+int piper_hip_voice_stream_pool_close(piper_hip_voice* v, int slot);
 /* prepare + launch + collect: PiperMetalRuntime.synthesize (PiperMetalRuntime.swift:62-80). */
 int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u, float* host_audio,
                                int64_t max_samples, int64_t* n_samples);

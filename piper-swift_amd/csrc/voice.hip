@@ -275,6 +275,32 @@ struct Slot {
   size_t bs_pack_cap = 0;     // floats
 };
 
+// Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
+// or stream_drop) while the stream runs. It belongs to the voice per slot id, not to a plan — a pool has no single front plan: every join
+// runs encoder + flow on a work slot's plan and moves the latents into the rows' own stores.
+struct PoolRowRef {  // device table entry: where row r's latent [inter][stride] lives
+  const float* z;
+  int64_t stride;
+};
+struct PoolJoinEnt {  // per-join table entry of stream_adopt_kernel
+  int src, row, F, pad;
+};
+struct StreamPool {
+  int capacity = 0, NBg = 1, chunk = 0, halo = 0;
+  struct Row {
+    float* z = nullptr;   // [inter][stride] row store (context pool), kept while the pool lives, regrown for a longer utterance
+    size_t cap = 0;       // floats
+    int stride = 0;       // bucket_f(F) of the item in the row
+    int F = 0, next = 0;  // the item's frames, its next frame
+    bool active = false;  // false: free (never taken, finished or dropped)
+  };
+  std::vector<Row> rows;
+  PoolRowRef* d_rows = nullptr;   // device: [NBg] row table, then the [capacity] PoolJoinEnt table of the latest join (one upload per join)
+  int* d_desc = nullptr;          // device: [NBg][kDescInts] descriptor of the step (one upload per step)
+  float* pack = nullptr;         // device: the packed chunks of one step, capacity · chunk · hop floats
+  std::vector<hipEvent_t> ev_free, ev_pending;  // ev_pending: "the adopt of a join since the last step has run", one per join
+};
+
 }  // namespace
 
 struct piper_hip_voice {
@@ -350,6 +376,7 @@ struct piper_hip_voice {
     std::vector<hipEvent_t> chunk_ev;  // collect, 1 … 16 MB waveforms: one event per 1 MB chunk landed in h_audio
   } staging[kMaxSlots];
   Slot* attached[kMaxSlots] = {};
+  std::unique_ptr<StreamPool> pools[kMaxSlots];  // the streaming pool a slot id holds (then attached[slot] is null)
   Slot* attached_dp[kMaxSlots] = {};  // bounded prepare: the encoder + predictor plan this slot id holds until its next prepare / detach
   uint64_t use_clock = 0;
   int hop = 1;
@@ -681,6 +708,21 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
     s.ev_in = nullptr;
     give_back_set(v, s);  // piper_hip_voice_destroy destroys the sets
   }
+}
+
+// Closes the streaming pool of slot id `slot`, if it holds one: waits for the adopts still queued (they write the row stores), then gives
+// the row stores and tables back to the context pool.
+void pool_close(piper_hip_voice* v, int slot) {
+  StreamPool* P = v->pools[slot].get();
+  if (!P) return;
+  for (hipEvent_t e : P->ev_pending) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+  for (hipEvent_t e : P->ev_free) (void)hipEventDestroy(e);
+  for (auto& r : P->rows)
+    if (r.z) (void)v->ctx->pool.release(r.z);
+  if (P->d_rows) (void)v->ctx->pool.release(P->d_rows);
+  if (P->d_desc) (void)v->ctx->pool.release(P->d_desc);
+  if (P->pack) (void)v->ctx->pool.release(P->pack);
+  v->pools[slot].reset();
 }
 
 struct Arena {
@@ -2080,6 +2122,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
   if (!v) return;
   (void)hipSetDevice(v->ctx->device);
   (void)hipDeviceSynchronize();
+  for (int i = 0; i < kMaxSlots; i++) pool_close(v, i);
   for (auto& pl : v->plans) slot_release(v, *pl, true);
   for (auto& sg : v->staging) {
     if (sg.h_ids) (void)hipHostFree(sg.h_ids);
@@ -2229,6 +2272,7 @@ void detach(piper_hip_voice* v, int slot) {
 // The plan of bucket (kind, T, F, NB) on slot id `slot`: the one attached already if it matches, otherwise the attached one is detached and
 // the bucket's plan is taken from the cache (or built) and attached. Then, if `evict`, idle plans beyond the cache's bounds go.
 int attach_plan(piper_hip_voice* v, int slot, PlanKind kind, int T, int F, int NB, Slot** out, bool evict = true) {
+  pool_close(v, slot);  // a prepare replaces what the slot id holds, a streaming pool included
   Slot* cur = v->attached[slot];
   if (!(cur && cur->built && cur->kind == kind && cur->T == T && cur->F == F && cur->NB == NB && cur->prec == v->precision)) {
     if (cur) detach(v, slot);
@@ -3046,6 +3090,166 @@ void plan_free(piper_hip_voice* v, Slot& s, void* p, size_t bytes) {
 
 }  // namespace
 
+// ---- streaming pool: the rows of a batched stream are taken and freed while it runs ------------------------------------------------------
+namespace {
+
+StreamPool* slot_pool(const piper_hip_voice* v, int slot) { return (v && slot >= 0 && slot < kMaxSlots) ? v->pools[slot].get() : nullptr; }
+
+// A join's latents → the pool's row stores: entry j of `tab` copies the first F columns of item src of the work plan's z [n][I][Fw] into
+// the store of pool row `row`, rows[row] = [I][stride], and zeroes the columns from F to stride, so a row never shows what an earlier, longer item left there.
+// One thread per 4 frames of one channel, along frames (coalesced); both sides are bucket rows on 16-byte-aligned bases (Fw % 16 ==
+// stride % 16 == 0, stride = bucket_f(F) ≤ Fw), so every access is an aligned float4 inside its row. blockIdx.y = the join's entry.
+__global__ __launch_bounds__(256) void stream_adopt_kernel(const float* __restrict__ z, int Fw, const PoolJoinEnt* __restrict__ tab,
+                                                          const PoolRowRef* __restrict__ rows, int I) {
+  const PoolJoinEnt e = tab[blockIdx.y];
+  const PoolRowRef rr = rows[e.row];
+  const int stride = (int)rr.stride, q4 = stride >> 2;
+  const int total = I * q4;
+  const float* zi = z + (int64_t)e.src * I * Fw;
+  float* out = (float*)rr.z;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int c = i / q4, j = (i - c * q4) * 4;
+    float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (j < e.F) {
+      t = *(const float4*)(zi + (int64_t)c * Fw + j);
+      if (j + 1 >= e.F) t.y = 0.0f;
+      if (j + 2 >= e.F) t.z = 0.0f;
+      if (j + 3 >= e.F) t.w = 0.0f;
+    }
+    *(float4*)(out + (int64_t)c * stride + j) = t;
+  }
+}
+
+// stream_window_gather_kernel for a pool: the latent of descriptor row r's source is the row store rows[src] (base pointer and row
+// stride from the table) instead of z + src·I·F. Everything else — zero past Fc, lensF from the descriptor — is the group kernel's.
+__global__ __launch_bounds__(256) void stream_pool_gather_kernel(const PoolRowRef* __restrict__ rows, const int* __restrict__ desc,
+                                                                float* __restrict__ zin, int* __restrict__ lensF, int I, int Fg) {
+  const int r = blockIdx.y;
+  const int* d = desc + r * kDescInts;
+  const int src = d[kDescSrc], a = d[kDescA], Fc = d[kDescFc];
+  if (blockIdx.x == 0 && threadIdx.x == 0) lensF[r] = Fc;
+  if (Fc == 0) return;
+  const int q4 = Fg >> 2;  // Fg % 16 == 0
+  const int total = I * q4;
+  const int64_t F = rows[src].stride;
+  const float* zr = rows[src].z + a;
+  float* out = zin + (int64_t)r * I * Fg;
+  const bool vec = (a & 3) == 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int c = i / q4, j = (i - c * q4) * 4;
+    const float* zp = zr + (int64_t)c * F + j;
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (j < Fc) {
+      if (vec) {  // a + j is a multiple of 4 below the row stride (a multiple of 16): all four lie in the row
+        const float4 t = *(const float4*)zp;
+        v.x = t.x; v.y = j + 1 < Fc ? t.y : 0.0f; v.z = j + 2 < Fc ? t.z : 0.0f; v.w = j + 3 < Fc ? t.w : 0.0f;
+      } else {
+        v.x = zp[0];
+        if (j + 1 < Fc) v.y = zp[1];
+        if (j + 2 < Fc) v.z = zp[2];
+        if (j + 3 < Fc) v.w = zp[3];
+      }
+    }
+    *(float4*)(out + (int64_t)c * Fg + j) = v;
+  }
+}
+
+int pool_free_rows(const StreamPool& P) {
+  int k = 0;
+  for (const auto& r : P.rows) k += r.active ? 0 : 1;
+  return k;
+}
+
+// An event for a join's adopt: one that an earlier step has consumed, or a new one.
+int pool_event(StreamPool& P, hipEvent_t* out) {
+  if (!P.ev_free.empty()) {
+    *out = P.ev_free.back();
+    P.ev_free.pop_back();
+    return PIPER_HIP_OK;
+  }
+  PH_HIP(hipEventCreateWithFlags(out, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
+// stream_next_batch on a pool slot: the next chunk of every active row in one generator launch at the pool's fixed batch.
+int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples) {
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  const int n = P.capacity, NBg = P.NBg, hop = v->hop;
+  auto& sg = v->staging[slot];
+  int rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * kDescInts);
+  if (rc) return rc;
+  // the descriptor of this step (the previous step's upload has completed: every step ends with a wait)
+  int* d = sg.h_desc;
+  std::vector<int64_t> got(n, 0);
+  int64_t total = 0;
+  int Fmax = 0;
+  for (int r = 0; r < NBg; r++) {
+    int* e = d + (size_t)r * kDescInts;
+    for (int k = 0; k < kDescInts; k++) e[k] = 0;
+    e[kDescSrc] = r < n ? r : 0;
+    if (r >= n || !P.rows[r].active) continue;
+    // the window of stream_next: chunk + receptive field, clamped to the utterance
+    const int Ft = P.rows[r].F, f0 = P.rows[r].next, f1 = std::min(Ft, f0 + P.chunk);
+    const int a = std::max(0, f0 - P.halo), b = std::min(Ft, f1 + P.halo);
+    e[kDescA] = a;
+    e[kDescFc] = b - a;
+    e[kDescSkip] = (f0 - a) * hop;
+    e[kDescN] = (f1 - f0) * hop;
+    e[kDescOff] = (int)total;
+    got[r] = e[kDescN];
+    total += e[kDescN];
+    Fmax = std::max(Fmax, b - a);
+  }
+  for (int i = 0; i < n; i++) n_samples[i] = 0;
+  if (total == 0) return PIPER_HIP_OK;  // idle: no active row (joins since the last step stay pending)
+  if (host_audio && max_samples < total)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
+  constexpr size_t kAudioMinCap = (size_t)16 << 10;
+  if (host_audio && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
+  // generator-only plan of the step's longest window at the pool's batch size: the plans a group of the same size uses
+  Slot* gs = nullptr;
+  bool built = false;
+  if ((rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
+  gs->in_use = true;
+  gs->last_use = ++v->use_clock;
+  const hipStream_t q = gs->set.stream;
+  const int I = v->cfg.inter, Fg = gs->F;
+  hipError_t e = hipSuccess;
+  for (hipEvent_t ev : P.ev_pending)  // the latents of every join since the last step: the GPU waits, the host does not
+    if (e == hipSuccess) e = hipStreamWaitEvent(q, ev, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(P.d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) {
+    const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (Fg / 4), 256), 64);
+    hipLaunchKernelGGL(stream_pool_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, P.d_rows, P.d_desc, gs->zin, gs->lensF, I, Fg);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
+  if (e == hipSuccess) {
+    const int px = (int)std::min<int64_t>(ceil_div((int64_t)P.chunk * hop, 1024), 64);
+    hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, P.d_desc, P.pack);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && host_audio) e = hipMemcpyAsync(sg.h_audio, P.pack, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, q);
+  if (e == hipSuccess) e = stream_wait(q);
+  gs->in_use = false;
+  evict_idle_plans(v);
+  if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
+  // the wait above covers the adopts q waited for: their events can be recorded again
+  P.ev_free.insert(P.ev_free.end(), P.ev_pending.begin(), P.ev_pending.end());
+  P.ev_pending.clear();
+  if (host_audio) memcpy(host_audio, sg.h_audio, (size_t)total * sizeof(float));
+  for (int i = 0; i < n; i++) {
+    n_samples[i] = got[i];
+    if (!got[i]) continue;
+    auto& r = P.rows[i];
+    r.next = std::min(r.F, r.next + P.chunk);
+    if (r.next >= r.F) r.active = false;  // last chunk delivered: the row is free for the next join
+  }
+  return PIPER_HIP_OK;
+}
+
+}  // namespace
+
 PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames) {
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: group of %d outside [1,%d]", n, kMaxGroup);
@@ -3081,6 +3285,7 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
 
 PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples);
   Slot* sp = slot_plan(v, slot);
   if (!sp || sp->bs_n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
@@ -3156,10 +3361,136 @@ PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, fl
 
 PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (StreamPool* P = slot_pool(v, slot)) {  // the session in that row leaves: the row is free for the next join
+    if (item < 0 || item >= P->capacity) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, P->capacity);
+    P->rows[item].active = false;
+    return PIPER_HIP_OK;
+  }
   Slot* sp = slot_plan(v, slot);
   if (!sp || sp->bs_n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   if (item < 0 || item >= sp->bs_n) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, sp->bs_n);
   sp->bs_dropped[item] = 1;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int capacity, int chunk_frames) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (capacity < 1 || capacity > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_open: capacity %d outside [1,%d]", capacity, kMaxGroup);
+  if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_open: chunk_frames must be >= 1");
+  if ((int64_t)chunk_frames * v->hop * capacity > 0x3fffffff)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_open: %d × %d frames per step too many", capacity, chunk_frames);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  pool_close(v, slot);
+  detach(v, slot);  // what the slot id held is replaced, as by a prepare
+  std::unique_ptr<StreamPool> P(new StreamPool());
+  P->capacity = capacity;
+  while (P->NBg < capacity) P->NBg <<= 1;  // the generator's batch, fixed for the life of the pool (the rule of a group)
+  P->chunk = chunk_frames;
+  P->halo = generator_halo_frames(v->cfg);
+  P->rows.resize(capacity);
+  void* p = nullptr;
+  int rc = v->ctx->pool.alloc((size_t)P->NBg * sizeof(PoolRowRef) + (size_t)capacity * sizeof(PoolJoinEnt), &p);
+  if (!rc) P->d_rows = (PoolRowRef*)p;
+  if (!rc) { rc = v->ctx->pool.alloc((size_t)P->NBg * kDescInts * sizeof(int), &p); if (!rc) P->d_desc = (int*)p; }
+  if (!rc) { rc = v->ctx->pool.alloc((size_t)capacity * chunk_frames * v->hop * sizeof(float), &p); if (!rc) P->pack = (float*)p; }
+  v->pools[slot] = std::move(P);
+  if (rc) { pool_close(v, slot); return rc; }
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
+                                               int* items_out, int64_t* samples_out) {
+  if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  StreamPool* P = slot_pool(v, slot);
+  if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
+  if (work_slot < 0 || work_slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "work slot %d out of range [0,%d)", work_slot, kMaxSlots);
+  if (work_slot == slot) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join: the work slot is the pool's slot %d", slot);
+  if (slot_pool(v, work_slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join: work slot %d holds a streaming pool", work_slot);
+  if (n < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join: %d items", n);
+  const int free_rows = pool_free_rows(*P);
+  if (n > free_rows) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join: %d items, %d free rows of %d", n, free_rows, P->capacity);
+  // encoder (+ predictor) inputs of the join on the work slot's plan, then encoder + flow on that plan's stream
+  int rc = piper_hip_voice_prepare_batch(v, utts, n, work_slot);
+  if (rc < 0) return rc;
+  Slot& w = *v->attached[work_slot];
+  const int I = v->cfg.inter;
+  // rows, lowest free index first, and their stores. Nothing of the pool changes before everything that can fail has succeeded.
+  std::vector<int> take;
+  for (int r = 0; r < P->capacity && (int)take.size() < n; r++)
+    if (!P->rows[r].active) take.push_back(r);
+  auto& sg = v->staging[work_slot];  // free: prepare_batch waited for whatever used this slot id's staging before
+  const size_t tab_ints = (size_t)P->NBg * sizeof(PoolRowRef) / sizeof(int), join_ints = (size_t)n * sizeof(PoolJoinEnt) / sizeof(int);
+  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * (sizeof(PoolRowRef) + sizeof(PoolJoinEnt)) / sizeof(int)))) return rc;
+  int stride_max = 0;
+  for (int i = 0; i < n; i++) {
+    auto& r = P->rows[take[i]];
+    const int stride = bucket_f(w.h_F[i]);
+    stride_max = std::max(stride_max, stride);
+    const size_t need = (size_t)I * stride;
+    if (r.cap >= need) continue;
+    // a longer utterance takes the row: a larger store. No step is in flight (every step ends with a host wait); an adopt of a join
+    // since the last step may still be writing the old store (joined, dropped, row taken again) — wait for those.
+    for (hipEvent_t ev : P->ev_pending) PH_HIP(hipEventSynchronize(ev), PIPER_HIP_ERR_LAUNCH);
+    void* p = nullptr;
+    if ((rc = v->ctx->pool.alloc(need * sizeof(float), &p))) return rc;
+    if (r.z) (void)v->ctx->pool.release(r.z);
+    r.z = (float*)p;
+    r.cap = need;
+  }
+  hipEvent_t ev = nullptr;
+  if ((rc = pool_event(*P, &ev))) return rc;
+  if ((rc = launch_front(w))) { P->ev_free.push_back(ev); return rc; }
+  // The adopt runs on the work plan's own stream: behind its front graph, and ahead of everything that waits for that stream before the
+  // plan's arena is reused (prepare on the same plan, detach, evict_idle_plans). It first waits for the adopts of earlier joins since the
+  // last step: they read the tables this join uploads anew, and one of them may write a row this join takes again.
+  const hipStream_t q = w.set.stream;
+  PoolRowRef* tab = (PoolRowRef*)sg.h_desc;  // the whole row table as it stands after this join, then the join's own table
+  PoolJoinEnt* jt = (PoolJoinEnt*)(sg.h_desc + tab_ints);
+  for (int r = 0; r < P->NBg; r++) {
+    tab[r].z = r < P->capacity ? P->rows[r].z : nullptr;
+    tab[r].stride = r < P->capacity ? P->rows[r].stride : 0;
+  }
+  for (int i = 0; i < n; i++) {
+    tab[take[i]].stride = bucket_f(w.h_F[i]);
+    jt[i] = PoolJoinEnt{i, take[i], w.h_F[i], 0};
+  }
+  hipError_t e = hipSuccess;
+  for (hipEvent_t pe : P->ev_pending)
+    if (e == hipSuccess) e = hipStreamWaitEvent(q, pe, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(P->d_rows, sg.h_desc, (tab_ints + join_ints) * sizeof(int), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) {
+    const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (stride_max / 4), 256), 64);
+    hipLaunchKernelGGL(stream_adopt_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev, q);
+  if (e != hipSuccess) { P->ev_free.push_back(ev); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_pool_join: %s", hipGetErrorString(e)); }
+  P->ev_pending.push_back(ev);
+  for (int i = 0; i < n; i++) {  // active from the next step on
+    auto& r = P->rows[take[i]];
+    r.stride = bucket_f(w.h_F[i]);
+    r.F = w.h_F[i];
+    r.next = 0;
+    r.active = true;
+    if (items_out) items_out[i] = take[i];
+    if (samples_out) samples_out[i] = (int64_t)w.h_F[i] * v->hop;
+  }
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_free_rows(const piper_hip_voice* v, int slot) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  const StreamPool* P = slot_pool(v, slot);
+  if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
+  return pool_free_rows(*P);
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_close(piper_hip_voice* v, int slot) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (!slot_pool(v, slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  pool_close(v, slot);
   return PIPER_HIP_OK;
 }
 

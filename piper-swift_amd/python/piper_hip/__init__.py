@@ -198,6 +198,11 @@ _PROTOS = {
     "piper_hip_voice_stream_begin_batch": (C.c_int, [c_vp, C.POINTER(Utterance), C.c_int, C.c_int, C.c_int]),
     "piper_hip_voice_stream_next_batch": (C.c_int, [c_vp, C.c_int, c_f32p, C.c_int64, C.POINTER(C.c_int64)]),
     "piper_hip_voice_stream_drop": (C.c_int, [c_vp, C.c_int, C.c_int]),
+    "piper_hip_voice_stream_pool_open": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int]),
+    "piper_hip_voice_stream_pool_join": (C.c_int, [c_vp, C.c_int, C.POINTER(Utterance), C.c_int, C.c_int, C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_pool_free_rows": (C.c_int, [c_vp, C.c_int]),
+    "piper_hip_voice_stream_pool_close": (C.c_int, [c_vp, C.c_int]),
     "piper_hip_memory_stats": (C.c_int, [c_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "piper_hip_memory_trim": (C.c_int, [c_vp]),
     "piper_hip_memory_reserve": (C.c_int, [c_vp, C.c_size_t]),
@@ -780,6 +785,57 @@ def piper_json(text):
     return info
 
 
+class StreamPool:
+    """What HipRuntime.stream_pool returns: join() new sessions, step() for the next chunk of every active one, drop() a session."""
+
+    def __init__(self, rt, slot, capacity, chunk_frames, work_slot):
+        self.rt, self.slot, self.capacity, self.chunk_frames, self.work_slot = rt, slot, capacity, chunk_frames, work_slot
+        self._buf = np.empty(max(capacity * chunk_frames * rt.cfg.hop, 1), np.float32)
+        self._got = (C.c_int64 * capacity)()
+
+    def join(self, utterances, noiseScale=0.667):
+        """utterances as for synthesize_stream_batch: (phonemeIDs, durations-or-None, noise-or-None[, dict]). Returns [(item, samples)]:
+        the row each session took and the samples it will deliver in all. Active from the next step()."""
+        rt, n = self.rt, len(utterances)
+        arr = (Utterance * max(n, 1))()
+        keep = []
+        for i, item in enumerate(utterances):
+            ids, dur, noise = item[:3]
+            u, k = rt._utt(ids, dur, noise, noiseScale, **(item[3] if len(item) > 3 else {}))
+            arr[i] = u
+            keep.append(k)
+        items = (C.c_int * max(n, 1))()
+        samples = (C.c_int64 * max(n, 1))()
+        _check(rt.lib.piper_hip_voice_stream_pool_join(rt.voice, self.slot, arr, n, self.work_slot, items, samples))
+        rt._keep.pop(self.work_slot, None)  # the inputs were copied before the call returned
+        return [(int(items[i]), int(samples[i])) for i in range(n)]
+
+    def step(self):
+        """{item: chunk} of every active session; an empty dict when the pool is idle."""
+        rt = self.rt
+        _check(rt.lib.piper_hip_voice_stream_next_batch(rt.voice, self.slot, self._buf.ctypes.data_as(c_f32p), self._buf.size, self._got))
+        out, off = {}, 0
+        for item in range(self.capacity):
+            c = int(self._got[item])
+            if c:
+                out[item] = self._buf[off:off + c].copy()
+                off += c
+        return out
+
+    def drop(self, item):
+        _check(self.rt.lib.piper_hip_voice_stream_drop(self.rt.voice, self.slot, int(item)))
+
+    @property
+    def free_rows(self):
+        rc = self.rt.lib.piper_hip_voice_stream_pool_free_rows(self.rt.voice, self.slot)
+        if rc < 0:
+            _check(rc)
+        return rc
+
+    def close(self):
+        _check(self.rt.lib.piper_hip_voice_stream_pool_close(self.rt.voice, self.slot))
+
+
 class HipRuntime:
     """PiperMetalRuntime.synthesize (PiperMetalRuntime.swift:62-80) over the C-ABI, durations/noise injected."""
 
@@ -954,6 +1010,15 @@ class HipRuntime:
     def stream_drop(self, slot, item):
         """The client of item `item` of the batched stream on `slot` went away: later steps skip it."""
         _check(self.lib.piper_hip_voice_stream_drop(self.voice, slot, int(item)))
+
+    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None):
+        """A streaming pool (piper_hip_voice_stream_pool_open) of `capacity` rows on `slot`: sessions join and leave while it runs.
+        work_slot: the slot id whose plan runs the joins' encoder + flow (default: the next slot id)."""
+        if work_slot is None:
+            work_slot = slot + 1 if slot + 1 < 16 else slot - 1
+        _check(self.lib.piper_hip_voice_stream_pool_open(self.voice, slot, int(capacity), int(chunkFrames)))
+        self._keep.pop(slot, None)
+        return StreamPool(self, slot, int(capacity), int(chunkFrames), int(work_slot))
 
     def prepare_batch(self, slot, utterances, noiseScale=0.667):
         """utterances: list of (phonemeIDs, durations, noise-or-None); lengths may differ (ragged batch, one bucket)."""

@@ -151,6 +151,58 @@ public final class PiperHIPRuntime {
         try HIPBackend.check(piper_hip_voice_stream_drop(voice, slot, item))
     }
 
+    /// A streaming pool (piper_hip_voice_stream_pool_open): `capacity` rows on `slot` that sessions join and leave while the stream runs.
+    /// The pool itself has no counterpart in PiperMetalRuntime; the closest role is synthesizeStream.
+    public func streamPoolOpen(slot: Int32, capacity: Int32, chunkFrames: Int32 = 64) throws {
+        try HIPBackend.check(piper_hip_voice_stream_pool_open(voice, slot, capacity, chunkFrames))
+    }
+
+    /// New sessions for the pool on `slot`: encoder + flow run on `workSlot`, the latents move into free rows. Returns, per utterance, the
+    /// row it took (its item id for streamPoolStep / streamDrop) and the samples it will deliver in all. `durations[i] == nil` = predicted.
+    public func streamPoolJoin(slot: Int32, workSlot: Int32, phonemeIDs: [[Int64]], durations: [[Int32]?], noiseScale: Float,
+                               seeds: [UInt32]? = nil) throws -> [(item: Int32, samples: Int64)] {
+        let n = phonemeIDs.count
+        let ids = phonemeIDs.map { ContiguousArray($0) }
+        let durs = durations.map { $0.map { ContiguousArray($0) } }
+        var utts = [piper_hip_utterance]()
+        var items = [Int32](repeating: 0, count: n)
+        var samples = [Int64](repeating: 0, count: n)
+        try withExtendedLifetime((ids, durs)) {
+            for i in 0..<n {
+                let ip = ids[i].withUnsafeBufferPointer { $0.baseAddress }       // storage kept alive by withExtendedLifetime
+                let dp = durs[i]?.withUnsafeBufferPointer { $0.baseAddress }
+                utts.append(piper_hip_utterance(phoneme_ids: ip, t: Int32(ids[i].count), durations: dp, noise: nil, noise_scale: noiseScale,
+                                                noise_mode: Int32(PIPER_HIP_NOISE_DEVICE), seed: seeds?[i] ?? 1234, length_scale: 1.0,
+                                                noise_w: 0.8, dp_noise: nil))
+            }
+            try HIPBackend.check(piper_hip_voice_stream_pool_join(voice, slot, &utts, Int32(n), workSlot, &items, &samples))
+        }
+        return (0..<n).map { (items[$0], samples[$0]) }
+    }
+
+    /// The next chunk of every active session of the pool on `slot` (piper_hip_voice_stream_next_batch), keyed by item; empty = idle.
+    public func streamPoolStep(slot: Int32, capacity: Int32, chunkFrames: Int32 = 64) throws -> [Int32: [Float]] {
+        var buf = [Float](repeating: 0, count: Int(capacity) * Int(chunkFrames) * hop)
+        var counts = [Int64](repeating: 0, count: Int(capacity))
+        try HIPBackend.check(piper_hip_voice_stream_next_batch(voice, slot, &buf, Int64(buf.count), &counts))
+        var out = [Int32: [Float]](), off = 0
+        for (item, c) in counts.enumerated() where c > 0 {
+            out[Int32(item)] = Array(buf[off..<off + Int(c)])
+            off += Int(c)
+        }
+        return out
+    }
+
+    public func streamPoolFreeRows(slot: Int32) throws -> Int32 {
+        let rc = piper_hip_voice_stream_pool_free_rows(voice, slot)
+        if rc < 0 { try HIPBackend.check(rc) }
+        return rc
+    }
+
+    public func streamPoolClose(slot: Int32) throws {
+        try HIPBackend.check(piper_hip_voice_stream_pool_close(voice, slot))
+    }
+
     /// WavFileWriter (Sources/PiperCLI/WavFileWriter.swift:20-60): float → int16 with the CLI's x·32767 clamp, RIFF header.
     public func writeWav(_ samples: [Float], to path: String) throws {
         try HIPBackend.check(piper_hip_wav_write(path, samples, samples.count, sampleRate))
