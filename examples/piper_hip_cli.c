@@ -8,7 +8,10 @@
  *                            (PiperCLI.swift:288, 395, 524-537). Same flags: --warmup (1) --iters (3) --scale-factors (1,2,4,8,16) --max-phonemes (4096)
  *                            --model voice.onnx [--config voice.onnx.json].
  *   --phoneme-ids a,b,c …    one utterance → --output file.wav (16-bit, WavFileWriter.swift:20-60); the espeak-ng front end of the reference CLI is
- *                            out of scope, so the ids are the input.
+ *                            out of scope, so the ids are the input. --output-raw file.raw writes the s16le stream instead (or as
+ *                            well), converted on the device (piper_hip_voice_synthesize_pcm16; after --output, collect_pcm16 on the
+ *                            slot that ran): --volume V scales it (linear, default 1),
+ *                            --normalize applies Piper's peak normalisation (audio_float_to_int16). Both flags act on --output-raw only.
  * Without --model the synthetic voice of the tests is used (--quality medium|high); its duration predictor has random weights, so frames per id are
  * pinned to --pin-frames (3, the bench's convention) unless --predict asks for the predictor (the only mode a real voice has).
  *
@@ -107,6 +110,38 @@ static int run_one(runner* r, const int64_t* ids, int t, int64_t* samples) {
   return 0;
 }
 
+/* The utterance as 16-bit samples converted on the device. *pcm is malloc'ed; the caller frees it, after a failure too.
+ * ran != 0: run_one has just run this utterance on slot 0 and its waveform is still in the plan, so piper_hip_voice_collect_pcm16 converts
+ * that. Otherwise pinned durations go through piper_hip_voice_synthesize_pcm16 in one call; with --predict the length is the predictor's,
+ * so the slot is prepared (once), asked for it, launched and collected as PCM. */
+static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_pcm_params* prm, int ran, int16_t** pcm, int64_t* samples) {
+  piper_hip_utterance u;
+  memset(&u, 0, sizeof u);
+  u.phoneme_ids = ids; u.t = t; u.noise_scale = r->noise_scale; u.seed = 1234;
+  u.length_scale = r->length_scale; u.noise_w = r->noise_w; u.noise_mode = PIPER_HIP_NOISE_DEVICE;
+  int rc;
+  int64_t cap = 0;
+  *pcm = NULL;
+  if (!ran && !r->predict) {
+    int32_t* dur = (int32_t*)malloc(sizeof(int32_t) * (size_t)t);
+    for (int i = 0; i < t; i++) dur[i] = r->pin_frames;
+    u.durations = dur;
+    cap = piper_hip_voice_num_samples(r->voice, &u);
+    rc = cap < 0 ? (int)cap : 0;
+    if (!rc) *pcm = (int16_t*)malloc(sizeof(int16_t) * (size_t)(cap > 0 ? cap : 1));
+    if (!rc) rc = piper_hip_voice_synthesize_pcm16(r->voice, &u, prm, *pcm, cap, samples);
+    free(dur);
+    return rc;
+  }
+  if (!ran && (rc = piper_hip_voice_prepare(r->voice, &u, 0)) < 0) return rc;
+  if ((rc = piper_hip_voice_prepared_samples(r->voice, 0, NULL, 0, &cap)) < 0) return rc;
+  *pcm = (int16_t*)malloc(sizeof(int16_t) * (size_t)(cap > 0 ? cap : 1));
+  if (!ran && (rc = piper_hip_voice_launch(r->voice, 0)) < 0) return rc;
+  if ((rc = piper_hip_voice_collect_pcm16(r->voice, 0, prm, *pcm, cap)) < 0) return rc;
+  *samples = cap;
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const char* model = arg_value(argc, argv, "--model");
   const char* config = arg_value(argc, argv, "--config");
@@ -115,7 +150,7 @@ int main(int argc, char** argv) {
   const char* ids_arg = arg_value(argc, argv, "--phoneme-ids");
   if (!scale_bench && !ids_arg) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
-                    "       %s --phoneme-ids 1,20,0,… --output out.wav\n"
+                    "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high] [--predict] [--pin-frames N]\n", argv[0], argv[0]);
     return 2;
   }
@@ -169,13 +204,43 @@ int main(int argc, char** argv) {
     int64_t ids[4096];
     const int t = parse_csv_i64(ids_arg, ids, 4096);
     const char* out = arg_value(argc, argv, "--output");
-    if (t < 1 || !out) { fprintf(stderr, "--phoneme-ids needs a comma-separated list and --output a path\n"); return 2; }
+    const char* out_raw = arg_value(argc, argv, "--output-raw");
+    if (t < 1 || (!out && !out_raw)) { fprintf(stderr, "--phoneme-ids needs a comma-separated list and --output or --output-raw a path\n"); return 2; }
     int64_t n = 0;
-    CHECK(run_one(&r, ids, t, &n));
     double gpu = 0.0;
-    CHECK(piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu));
-    CHECK(piper_hip_wav_write(out, r.audio, (size_t)n, cfg.sample_rate));
-    fprintf(stderr, "%lld samples (%.3f s at %d Hz), %.3f ms on the GPU -> %s\n", (long long)n, (double)n / cfg.sample_rate, cfg.sample_rate, gpu, out);
+    if (out) {
+      CHECK(run_one(&r, ids, t, &n));
+      CHECK(piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu));
+      CHECK(piper_hip_wav_write(out, r.audio, (size_t)n, cfg.sample_rate));
+      fprintf(stderr, "%lld samples (%.3f s at %d Hz), %.3f ms on the GPU -> %s\n", (long long)n, (double)n / cfg.sample_rate, cfg.sample_rate, gpu, out);
+    }
+    if (out_raw) { /* s16le, the samples converted on the device */
+      piper_hip_pcm_params prm;
+      prm.gain = arg_value(argc, argv, "--volume") ? (float)atof(arg_value(argc, argv, "--volume")) : 1.0f;
+      prm.normalize = has_flag(argc, argv, "--normalize");
+      int16_t* pcm = NULL;
+      int failed = 0;
+      const int prc = run_one_pcm16(&r, ids, t, &prm, out != NULL, &pcm, &n);
+      if (prc < 0) {
+        fprintf(stderr, "--output-raw failed (%d): %s\n", prc, piper_hip_last_error());
+        failed = 1;
+      } else {
+        (void)piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu);
+        FILE* fr = fopen(out_raw, "wb");
+        failed = !fr || fwrite(pcm, sizeof(int16_t), (size_t)n, fr) != (size_t)n;
+        if (fr && fclose(fr) != 0) failed = 1;
+        if (failed) fprintf(stderr, "cannot write %s\n", out_raw);
+        else fprintf(stderr, "%lld samples (%.3f s at %d Hz) as s16le, %.3f ms on the GPU -> %s\n", (long long)n, (double)n / cfg.sample_rate, cfg.sample_rate, gpu, out_raw);
+      }
+      free(pcm);
+      if (failed) { /* leave as the success path does */
+        free(r.audio);
+        piper_hip_voice_destroy(r.voice);
+        piper_hip_destroy(ctx);
+        return 1;
+      }
+    }
+    free(r.audio);
     piper_hip_voice_destroy(r.voice);
     piper_hip_destroy(ctx);
     return 0;

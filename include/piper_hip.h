@@ -513,6 +513,42 @@ int piper_hip_voice_stream_pool_close(piper_hip_voice* v, int slot);
 /* prepare + launch + collect: PiperMetalRuntime.synthesize (PiperMetalRuntime.swift:62-80). */
 int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u, float* host_audio,
                                int64_t max_samples, int64_t* n_samples);
+
+/* ---- 16-bit PCM straight from the device (DESIGN.md §4 "PCM output") ----
+ * Every host of this library ends in 16-bit PCM (WavFileWriter.swift:20-30 in the reference's CLI; Piper's own tools emit int16). These
+ * entry points convert on the device, right behind the plan's graph on the slot's stream, and transfer int16: half the bytes of the fp32
+ * waveform and no conversion pass on the host. The arithmetic is a contract, bit for bit:
+ *   normalize == 0   y = x · gain (one fp32 multiply; gain 1 leaves x as it is), then exactly piper_hip_pcm16_from_f32(y): NaN → 0, clamp to
+ *                    [−1, 1], × 32767.0 in DOUBLE precision, truncate toward zero.
+ *   normalize == 1   Piper's audio_float_to_int16 carried out in float32, per utterance (batch item): peak = max |x| over the item's true
+ *                    samples (NaN ignored; an empty item has peak 0), scale = the correctly rounded fp32 quotient 32767 / max(0.01, peak),
+ *                    v = x · scale, then v · gain (both fp32), NaN → 0, clamp to [−32767, 32767], truncate toward zero.
+ * gain: linear volume, 0 is taken as 1.0; negative or non-finite is PIPER_HIP_ERR_ARG. A NULL params pointer means {1.0, 0}. */
+typedef struct {
+  float gain;        /* linear volume; 0 is taken as 1.0 */
+  int32_t normalize; /* 0: the reference conversion; 1: peak normalisation per utterance */
+} piper_hip_pcm_params;
+/* Per-op: `count` device floats → `count` device int16 (normalize == 0 arithmetic). `*out` convention of the other ops; a caller-supplied
+ * `*out` needs 2-byte alignment only. count may be 0. */
+int piper_hip_pcm16_f32(piper_hip_ctx* ctx, const float* x, size_t count, float gain, int16_t** out, piper_hip_stream stream);
+/* piper_hip_voice_collect with int16 samples: waits like collect, leaves the slot as collect leaves it (the fp32 audio stays in the plan, so
+ * collect and collect_pcm16 may each be called afterwards, in any order, with different params) and writes the items back to back at their
+ * true lengths. On a bounded slot it is the collecting call: host_pcm needs room for the capacity (as collect), the first `total`
+ * samples are the answer (piper_hip_voice_prepared_samples afterwards), an item over max_frames is PIPER_HIP_ERR_SHAPE. */
+int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm, int64_t max_samples);
+/* prepare + launch + collect_pcm16 on slot 0. */
+int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int16_t* host_pcm,
+                                     int64_t max_samples, int64_t* n_samples);
+/* stream_next / stream_next_batch (groups and pools) with int16 samples. A PCM step consumes the step exactly as the float call does, and
+ * float and PCM steps may alternate on one stream. normalize = 1 is PIPER_HIP_ERR_UNSUPPORTED and consumes nothing (an utterance's peak is
+ * not known before its last window); gain is allowed. */
+int piper_hip_voice_stream_next_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
+                                      int64_t max_samples, int64_t* n_samples);
+int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
+                                            int64_t max_samples, int64_t* n_samples);
+/* After a collect_pcm16 with normalize = 1: max |x| of each item of the slot (PIPER_HIP_ERR_ARG before one). */
+int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* peaks, int max_items);
+
 /* Debug taps ⇔ GraphExecutor.execute(maxNodeIndex:) returning intermediates (GraphExecutor.swift:75-152):
  * copy a named intermediate of the slot's last run to host. Names: "enc_out" [H,T], "m_p" [inter,T],
  * "logs_p" [inter,T], "z_p" [inter,F], "z" [inter,F], "dec_pre" [up_initial,F] — per batch item, compacted to the item's

@@ -1,0 +1,200 @@
+// pcm16.hip — fp32 waveform → 16-bit PCM on the device: the last hop before the bus (include/piper_hip.h "16-bit PCM straight from the device").
+//
+// The arithmetic is a contract, tested bit for bit against the host's piper_hip_pcm16_from_f32 (audio_io.cpp) and a numpy restatement:
+//   reference mode   y = x·gain (fp32; ·1.0f is the identity on every non-NaN float), NaN → 0, clamp to [−1, 1], ×32767.0 in DOUBLE, truncate
+//                    toward zero. The multiply is f64 because x·32767 in fp32 can round UP across an integer boundary and the sample would
+//                    then be one more than the host's; one v_mul_f64 per sample is free in a kernel that waits for memory.
+//   peak mode        Piper's audio_float_to_int16 in float32: v = x·scale_b, v·gain, NaN → 0, clamp to [−32767, 32767], truncate; scale_b =
+//                    fp32(32767 / max(0.01, peak_b)), the quotient taken in double and rounded once (= the correctly rounded fp32 quotient).
+// The library is built with -ffp-contract=off; none of the products below is followed by an add anyway.
+//
+// Memory: every kernel here moves each sample once — 16-byte loads, one 16-byte (8 samples) or 8-byte (4 samples) store where source and
+// destination are aligned (with hop = 256 every item of a voice path is), scalar otherwise and for the tail. The destination may be a
+// page-locked host buffer seen through its device mapping: the stores then ARE the transfer.
+#include "pcm16.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace ph {
+namespace {
+
+struct PcmCvt {
+  float gain, scale;
+  int norm;
+};
+
+__device__ __forceinline__ int pcm_cvt(float x, const PcmCvt c) {
+  if (c.norm) {
+    float v = x * c.scale;
+    v = v * c.gain;
+    v = v != v ? 0.0f : fminf(fmaxf(v, -32767.0f), 32767.0f);
+    return (int)v;  // v_cvt_i32_f32 truncates toward zero
+  }
+  double d = (double)(x * c.gain);
+  d = d != d ? 0.0 : fmin(fmax(d, -1.0), 1.0);
+  return (int)(d * 32767.0);  // v_cvt_i32_f64 truncates toward zero
+}
+
+__device__ __forceinline__ unsigned pcm_pair(float lo, float hi, const PcmCvt c) {
+  return ((unsigned)pcm_cvt(lo, c) & 0xffffu) | ((unsigned)pcm_cvt(hi, c) << 16);  // little-endian: the first sample in the low half
+}
+
+// n samples src → dst, shared among `nth` threads of which this is `tid`
+__device__ __forceinline__ void pcm_span(const float* __restrict__ src, int16_t* __restrict__ dst, int64_t n, int64_t tid, int64_t nth,
+                                         const PcmCvt c) {
+  const bool src16 = ((uintptr_t)src & 15) == 0;
+  int64_t done = 0;
+  if (src16 && ((uintptr_t)dst & 15) == 0) {
+    const int64_t n8 = n >> 3;
+    for (int64_t i = tid; i < n8; i += nth) {
+      const float4 a = ((const float4*)src)[2 * i], b = ((const float4*)src)[2 * i + 1];
+      uint4 o;
+      o.x = pcm_pair(a.x, a.y, c); o.y = pcm_pair(a.z, a.w, c); o.z = pcm_pair(b.x, b.y, c); o.w = pcm_pair(b.z, b.w, c);
+      ((uint4*)dst)[i] = o;
+    }
+    done = n8 << 3;
+  } else if (src16 && ((uintptr_t)dst & 7) == 0) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = tid; i < n4; i += nth) {
+      const float4 a = ((const float4*)src)[i];
+      uint2 o;
+      o.x = pcm_pair(a.x, a.y, c); o.y = pcm_pair(a.z, a.w, c);
+      ((uint2*)dst)[i] = o;
+    }
+    done = n4 << 2;
+  }
+  for (int64_t i = done + tid; i < n; i += nth) dst[i] = (int16_t)pcm_cvt(src[i], c);
+}
+
+__device__ __forceinline__ int clamp_len(int len, int F) { return min(max(len, 0), F); }
+
+// Plan audio [NB][row] → the items back to back at their true lengths. blockIdx.y = item; the item's offset is the sum of the lengths
+// before it (NB ≤ 256 = one per thread), so plain, ragged and bounded slots — whose lengths only the device knows — take the same launch.
+__global__ __launch_bounds__(256) void pcm16_pack_kernel(const float* __restrict__ audio, int64_t row, const int* __restrict__ lensF, int F, int hop,
+                                                         float gain, const float* __restrict__ peaks, float* __restrict__ peaks_host,
+                                                         int16_t* __restrict__ out) {
+  __shared__ int part[4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  int before = tid < b ? clamp_len(lensF[tid], F) : 0;
+  for (int off = 32; off > 0; off >>= 1) before += __shfl_down(before, off);
+  if ((tid & 63) == 0) part[tid >> 6] = before;
+  __syncthreads();
+  const int64_t at = (int64_t)(part[0] + part[1] + part[2] + part[3]) * hop;
+  const int64_t n = (int64_t)clamp_len(lensF[b], F) * hop;
+  PcmCvt c;
+  c.gain = gain; c.scale = 1.0f; c.norm = 0;
+  if (peaks) {
+    const float peak = peaks[b];
+    c.scale = (float)(32767.0 / (double)fmaxf(0.01f, peak));
+    c.norm = 1;
+    if (peaks_host && blockIdx.x == 0 && tid == 0) peaks_host[b] = peak;
+  }
+  pcm_span(audio + (int64_t)b * row, out + at, n, (int64_t)blockIdx.x * 256 + tid, (int64_t)gridDim.x * 256, c);
+}
+
+// peaks[b] = max |x| of item b (zeroed before the launch). Max is exact in any order, and the bit patterns of non-negative floats order
+// like unsigned integers, so one vector atomic max per block is deterministic. fmaxf drops a NaN operand.
+__global__ __launch_bounds__(256) void pcm16_peak_kernel(const float* __restrict__ audio, int64_t row, const int* __restrict__ lensF, int F, int hop,
+                                                         float* __restrict__ peaks) {
+  __shared__ float part[4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int64_t n = (int64_t)clamp_len(lensF[b], F) * hop;
+  const float* src = audio + (int64_t)b * row;
+  const int64_t gt = (int64_t)blockIdx.x * 256 + tid, nth = (int64_t)gridDim.x * 256;
+  float m = 0.0f;
+  int64_t done = 0;
+  if (((uintptr_t)src & 15) == 0) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = gt; i < n4; i += nth) {
+      const float4 a = ((const float4*)src)[i];
+      m = fmaxf(fmaxf(m, fabsf(a.x)), fmaxf(fabsf(a.y), fmaxf(fabsf(a.z), fabsf(a.w))));
+    }
+    done = n4 << 2;
+  }
+  for (int64_t i = done + gt; i < n; i += nth) m = fmaxf(m, fabsf(src[i]));
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off));
+  if ((tid & 63) == 0) part[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    m = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+    if (m > 0.0f) atomicMax((unsigned*)peaks + b, __float_as_uint(m));  // (a block past the item's end has nothing to add)
+  }
+}
+
+__global__ __launch_bounds__(256) void pcm16_flat_kernel(const float* __restrict__ x, int64_t n, float gain, int16_t* __restrict__ out) {
+  PcmCvt c;
+  c.gain = gain; c.scale = 1.0f; c.norm = 0;
+  pcm_span(x, out, n, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256, c);
+}
+
+// stream_chunk_pack_kernel (voice.hip) with int16 output: each active row's chunk out of the generator plan's audio [NBg][row], the halo
+// samples dropped, packed back to back at the descriptor's offsets.
+__global__ __launch_bounds__(256) void stream_chunk_pack_pcm16_kernel(const float* __restrict__ audio, int64_t row, const int* __restrict__ desc,
+                                                                      float gain, int16_t* __restrict__ out) {
+  const int* d = desc + blockIdx.y * kDescInts;
+  const int n = d[kDescN];
+  if (n == 0) return;
+  PcmCvt c;
+  c.gain = gain; c.scale = 1.0f; c.norm = 0;
+  pcm_span(audio + (int64_t)blockIdx.y * row + d[kDescSkip], out + d[kDescOff], n, (int64_t)blockIdx.x * 256 + threadIdx.x,
+           (int64_t)gridDim.x * 256, c);
+}
+
+// blocks along an item: 8 samples per thread and pass, at most 1024 blocks (copy_out_kernel's bound in voice.hip)
+int span_blocks(int64_t samples, int per_thread) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div(samples, (int64_t)256 * per_thread), 1), 1024); }
+
+}  // namespace
+
+hipError_t launch_pcm16_pack(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, float gain,
+                             const float* peaks, float* peaks_host, int16_t* out) {
+  if (NB < 1 || NB > 256) return hipErrorInvalidValue;  // the offset of an item is summed by one block of 256 threads
+  hipLaunchKernelGGL(pcm16_pack_kernel, dim3(span_blocks((int64_t)F * hop, 8), NB), dim3(256), 0, q, audio, row, lensF, F, hop, gain, peaks,
+                     peaks_host, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pcm16_peak(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, float* peaks) {
+  if (NB < 1 || NB > 256) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(peaks, 0, (size_t)NB * sizeof(float), q);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pcm16_peak_kernel, dim3(span_blocks((int64_t)F * hop, 16), NB), dim3(256), 0, q, audio, row, lensF, F, hop, peaks);
+  return hipGetLastError();
+}
+
+hipError_t launch_pcm16_flat(hipStream_t q, const float* x, int64_t n, float gain, int16_t* out, int num_cus) {
+  const int64_t cap = (int64_t)num_cus * 8;
+  const int grid = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256 * 8), 1), cap);
+  hipLaunchKernelGGL(pcm16_flat_kernel, dim3(grid), dim3(256), 0, q, x, n, gain, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_stream_chunk_pack_pcm16(hipStream_t q, int px, int NBg, const float* audio, int64_t row, const int* desc, float gain,
+                                          int16_t* out) {
+  hipLaunchKernelGGL(stream_chunk_pack_pcm16_kernel, dim3(px, NBg), dim3(256), 0, q, audio, row, desc, gain, out);
+  return hipGetLastError();
+}
+
+namespace { PH_WARM(pcm16, pcm16_pack_kernel); }
+
+}  // namespace ph
+
+using namespace ph;
+
+PH_EXPORT int piper_hip_pcm16_f32(piper_hip_ctx* ctx, const float* x, size_t count, float gain, int16_t** out, piper_hip_stream stream) {
+  PH_CHECK_CTX(ctx);  // stays first: without a device this returns UNAVAILABLE before any other field of ctx is touched (tests/test_pcm16_ref.py)
+  if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16_f32: null output pointer");
+  if (!x && count) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16_f32: null input");
+  if (!(gain >= 0.0f) || !std::isfinite(gain)) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16_f32: gain %g is negative or not finite", (double)gain);
+  if (((uintptr_t)*out & 1) != 0) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16_f32: the output buffer is not 2-byte aligned");
+  if (!*out) {
+    void* p = nullptr;
+    const int rc = ctx->pool.alloc(count * sizeof(int16_t), &p);
+    if (rc) return rc;
+    *out = (int16_t*)p;
+  }
+  if (count == 0) return PIPER_HIP_OK;
+  StreamScope ss(ctx, stream);
+  (void)launch_pcm16_flat(ss.s, x, (int64_t)count, gain == 0.0f ? 1.0f : gain, *out, ctx->num_cus);
+  return ss.finish("pcm16_f32");
+}

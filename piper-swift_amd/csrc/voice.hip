@@ -23,6 +23,7 @@
 #include "conv.h"
 #include "conv_bf16.h"
 #include "conv_win.h"
+#include "pcm16.h"
 #include "rng.h"
 
 namespace ph {
@@ -273,6 +274,11 @@ struct Slot {
   int* bs_desc = nullptr;     // [kMaxGroup][kDescInts] device
   float* bs_pack = nullptr;   // the packed chunks of one step, device
   size_t bs_pack_cap = 0;     // floats
+  // 16-bit PCM output (piper_hip_voice_collect_pcm16 / stream_next_pcm16): device buffers of this plan (in `owned`), allocated on first use
+  int16_t* pcm = nullptr;     // the items back to back, as they travel to the host
+  size_t pcm_cap = 0;         // samples
+  float* peaks = nullptr;     // [NB] max |x| per item (normalize = 1)
+  std::vector<float> h_peaks; // the same on the host after a normalising collect_pcm16 (empty: none since the last launch)
 };
 
 // Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
@@ -373,6 +379,8 @@ struct piper_hip_voice {
     size_t cap_noise = 0;
     int* h_desc = nullptr;     // batched stream: the step's descriptor table (one H2D per step)
     size_t cap_desc = 0;
+    float* h_peaks = nullptr;  // collect_pcm16 with normalize = 1: the items' peaks, written by the pack kernel through the host mapping
+    size_t cap_peaks = 0;
     std::vector<hipEvent_t> chunk_ev;  // collect, 1 … 16 MB waveforms: one event per 1 MB chunk landed in h_audio
   } staging[kMaxSlots];
   Slot* attached[kMaxSlots] = {};
@@ -696,6 +704,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   if (s.front_graph) { (void)hipGraphDestroy(s.front_graph); s.front_graph = nullptr; }
   s.st_next = -1; s.zin = nullptr; s.z_out = nullptr;
   s.bs_n = 0; s.bs_desc = nullptr; s.bs_pack = nullptr; s.bs_pack_cap = 0;  // (both buffers are in `owned`)
+  s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();      // (these too)
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   for (void* p : s.owned) (void)v->ctx->pool.release(p);
   s.owned.clear();
@@ -2134,6 +2143,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_res) (void)hipHostFree(sg.h_res);
     if (sg.h_noise) (void)hipHostFree(sg.h_noise);
     if (sg.h_desc) (void)hipHostFree(sg.h_desc);
+    if (sg.h_peaks) (void)hipHostFree(sg.h_peaks);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
   for (auto& st : v->free_sets) destroy_set(st);
@@ -2431,6 +2441,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   PH_HIP(hipMemcpyAsync(s.lensF, sg.h_lens + n, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);  // noise / scalars come from caller memory
   s.timed = false;
+  s.h_peaks.clear();
   return slot;
 }
 
@@ -2574,10 +2585,16 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   s.bounded_pending = true;
   s.bounded_cap = std::min(max_frames, F);
   s.timed = false;
+  s.h_peaks.clear();
   return slot;
 }
 
 namespace {
+// The copy-out thresholds of piper_hip_voice_collect (the measurements behind them are told there), in bytes on the wire; the 16-bit PCM
+// paths (pcm_route / pcm_land) use the same ones: kernel stores or one DMA into page-locked staging up to kPinnedMax, kChunk pieces with
+// the host copying behind them up to kChunkedMax, the runtime's own pipelined copy beyond.
+constexpr size_t kPinnedMax = (size_t)1 << 20, kChunkedMax = (size_t)16 << 20, kChunk = (size_t)1 << 20;
+
 // after the slot's stream has been synchronised: the device's frame counts and durations → h_F / h_dur; an item over the bound is an error
 int bounded_finish(piper_hip_voice* v, int slot, Slot& s) {
   const auto& sg = v->staging[slot];
@@ -2755,6 +2772,7 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   }
   PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);
   s.timed = true;
+  s.h_peaks.clear();  // the peaks a normalising collect_pcm16 reported belong to the previous run
   return PIPER_HIP_OK;
 }
 
@@ -2810,12 +2828,10 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     // box to box (r2z: 45 … 130 µs for 344 KB). Up to 1 MB (a factor-8 … 16 utterance) the waveform lands in a pinned buffer of
     // the plan by one DMA and is copied out by the host; beyond that the runtime's pipelined chunks beat DMA + memcpy
     // (factor 64, 2.75 MB: +0.12 ms with the pinned hop).
-    constexpr size_t kPinnedMax = (size_t)1 << 20;
     // 1 … 16 MB into PAGEABLE memory: handing the caller's buffer to the runtime makes it page-lock that buffer on the spot, and for a buffer
     // it has not seen before that took 7 ms (r3, tools/probe/first_run.py: the first 1.2 MB waveform of a process, 9.4 ms in collect for
     // 1.9 ms of GPU work). Such waveforms land in the slot id's page-locked buffer in 1 MB chunks, each followed by an event, and the host
     // copies chunk k out while chunk k + 1 is on the wire. Larger ones still go to the runtime (its pipelined staging wins there).
-    constexpr size_t kChunkedMax = (size_t)16 << 20, kChunk = (size_t)1 << 20;
     const size_t bytes = (size_t)total * sizeof(float);
     // a destination the caller page-locked itself (piper_hip_host_alloc) takes the DMA directly
     bool caller_pinned = false;
@@ -2970,8 +2986,108 @@ PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_u
   return (int)ceil_div(s.h_F[0], chunk_frames);
 }
 
-PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
+namespace {
+int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
+
+// ---- 16-bit PCM out of a plan: where the convert kernel stores and how the samples reach the caller. The policy and the thresholds are
+// collect's (see there for the measurements behind them): a destination the caller page-locked takes kernel stores through its host
+// mapping up to 16 MB; a pageable one is served through the slot id's page-locked staging — kernel stores up to 1 MB, 1 MB chunks by the
+// copy engine with the host copying behind them up to 16 MB — and handed to the runtime beyond that. PIPER_HIP_COLLECT_DMA: always the
+// copy engine. The staging is sg.h_audio, the waveform's own landing buffer, holding two samples per float.
+
+struct PcmRoute {
+  int16_t* kdst = nullptr;     // where the convert kernel stores
+  int16_t* stage = nullptr;    // the slot id's page-locked staging when it holds the samples, else null
+  bool mapped = false;         // kdst is host memory seen from the device: the stores are the transfer
+  bool caller_pinned = false;  // (then kdst is the caller's buffer itself)
+};
+
+// `samples` will travel to `host`; a device buffer, if one is needed, belongs to `plan` and holds `dev_samples`
+int pcm_route(piper_hip_voice* v, Slot& plan, piper_hip_voice::Staging& sg, int16_t* host, size_t samples, size_t dev_samples, PcmRoute* r) {
+  constexpr size_t kAudioMinCap = (size_t)16 << 10;
+  const size_t bytes = samples * sizeof(int16_t);
+  {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, host) == hipSuccess) r->caller_pinned = at.type == hipMemoryTypeHost;
+    else (void)hipGetLastError();
+  }
+  if (!r->caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (samples + 1) / 2, kAudioMinCap)) (void)hipGetLastError();
+  r->stage = (!r->caller_pinned && sg.h_audio && sg.audio_cap * 2 >= samples) ? (int16_t*)sg.h_audio : nullptr;
+  static const bool dma_only = getenv("PIPER_HIP_COLLECT_DMA") != nullptr;
+  void* target = r->caller_pinned ? (bytes <= kChunkedMax ? (void*)host : nullptr) : (bytes <= kPinnedMax ? (void*)r->stage : nullptr);
+  if (!dma_only && target) {
+    void* dev = nullptr;
+    if (hipHostGetDevicePointer(&dev, target, 0) == hipSuccess && dev) { r->kdst = (int16_t*)dev; r->mapped = true; }
+    else (void)hipGetLastError();
+  }
+  if (!r->mapped) {
+    if (plan.pcm_cap < dev_samples) {
+      void* p = nullptr;
+      const int rc = plan_alloc(v, plan, dev_samples * sizeof(int16_t), &p);  // (a smaller one stays with the plan until it is released)
+      if (rc) return rc;
+      plan.pcm = (int16_t*)p;
+      plan.pcm_cap = dev_samples;
+    }
+    r->kdst = plan.pcm;
+  }
+  return PIPER_HIP_OK;
+}
+
+// Behind the convert kernel on q: wait for it, and bring `samples` samples to `host` unless the kernel stored them through a mapping
+// (then they are in the caller's buffer already, or in r.stage, from where the caller copies what it needs).
+int pcm_land(piper_hip_voice::Staging& sg, const PcmRoute& r, hipStream_t q, int16_t* host, size_t samples) {
+  if (r.mapped) {
+    PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);
+    return PIPER_HIP_OK;
+  }
+  const size_t bytes = samples * sizeof(int16_t);
+  if (!r.caller_pinned && r.stage && bytes > kPinnedMax && bytes <= kChunkedMax) {
+    const size_t nchunks = (bytes + kChunk - 1) / kChunk;
+    for (size_t k = 0; k < nchunks; k++) {
+      const size_t at = k * kChunk, cb = std::min(kChunk, bytes - at);
+      PH_HIP(hipMemcpyAsync((char*)r.stage + at, (const char*)r.kdst + at, cb, hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
+      if (sg.chunk_ev.size() <= k) {
+        hipEvent_t e = nullptr;
+        PH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+        sg.chunk_ev.push_back(e);
+      }
+      PH_HIP(hipEventRecord(sg.chunk_ev[k], q), PIPER_HIP_ERR_LAUNCH);
+    }
+    for (size_t k = 0; k < nchunks; k++) {
+      for (;;) {  // poll, as collect does: the chunks arrive every ≈ 20 µs
+        const hipError_t e = hipEventQuery(sg.chunk_ev[k]);
+        if (e == hipSuccess) break;
+        if (e != hipErrorNotReady) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "pcm16: %s", hipGetErrorString(e));
+        (void)hipGetLastError();
+        for (int i = 0; i < 16; i++) __builtin_ia32_pause();
+      }
+      const size_t at = k * kChunk;
+      memcpy((char*)host + at, (const char*)r.stage + at, std::min(kChunk, bytes - at));
+    }
+    return PIPER_HIP_OK;
+  }
+  int16_t* dst = (!r.caller_pinned && r.stage && bytes <= kPinnedMax) ? r.stage : host;
+  PH_HIP(hipMemcpyAsync(dst, r.kdst, bytes, hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipStreamSynchronize(q), PIPER_HIP_ERR_LAUNCH);
+  if (dst != host) memcpy(host, dst, bytes);
+  return PIPER_HIP_OK;
+}
+
+// params of a PCM entry point → gain (0 = 1.0) and the normalize flag; a negative or non-finite gain is an argument error
+int pcm_params(const piper_hip_pcm_params* p, float* gain, bool* normalize) {
+  *gain = 1.0f;
+  *normalize = false;
+  if (!p) return PIPER_HIP_OK;
+  if (!(p->gain >= 0.0f) || !std::isfinite(p->gain)) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16: gain %g is negative or not finite", (double)p->gain);
+  if (p->gain != 0.0f) *gain = p->gain;
+  *normalize = p->normalize != 0;
+  return PIPER_HIP_OK;
+}
+
+// stream_next; pcm: the chunk leaves as int16 (host_pcm, gain) — converted by a kernel behind the window's graph — instead of fp32
+int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm, float gain) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
   Slot* sp = slot_plan(v, slot);
   if (sp && sp->bs_n > 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a group of %d streams: use stream_next_batch", slot, sp->bs_n);
   if (!sp || sp->st_next < 0) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no stream in progress", slot);
@@ -2986,7 +3102,7 @@ PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* h
   const int a = std::max(0, f0 - s.st_halo), b = std::min(Ftrue, f1 + s.st_halo);
   const int Fc = b - a;
   const int64_t want = (int64_t)(f1 - f0) * v->hop;
-  if (host_audio && max_samples < want) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next: buffer holds %lld < %lld samples", (long long)max_samples, (long long)want);
+  if (want_out && max_samples < want) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next: buffer holds %lld < %lld samples", (long long)max_samples, (long long)want);
   // generator-only plan of the window's bucket (first / interior / last windows of a stream usually share one)
   Slot* gs = nullptr;
   bool built = false;
@@ -3002,24 +3118,39 @@ PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* h
     e = hipMemcpy2DAsync(gs->zin, (size_t)gs->F * sizeof(float), s.z_out + a, (size_t)s.F * sizeof(float), (size_t)Fc * sizeof(float), (size_t)I,
                          hipMemcpyDeviceToDevice, gs->set.stream);
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
-  if (e == hipSuccess && host_audio)
-    e = hipMemcpyAsync(host_audio, gs->audio + (int64_t)(f0 - a) * v->hop, (size_t)want * sizeof(float), hipMemcpyDeviceToHost, gs->set.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(gs->set.stream);
+  if (pcm && want_out) {
+    PcmRoute r;
+    if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], host_pcm, (size_t)want, (size_t)gs->F * v->hop, &r);
+    if (e == hipSuccess && !rc) e = launch_pcm16_flat(gs->set.stream, gs->audio + (int64_t)(f0 - a) * v->hop, want, gain, r.kdst, v->ctx->num_cus);
+    if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, host_pcm, (size_t)want);
+    if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)want * sizeof(int16_t));
+    if (e != hipSuccess || rc) (void)hipStreamSynchronize(gs->set.stream);  // nothing of the window may still run when its plan goes idle
+  } else {
+    if (e == hipSuccess && host_audio)
+      e = hipMemcpyAsync(host_audio, gs->audio + (int64_t)(f0 - a) * v->hop, (size_t)want * sizeof(float), hipMemcpyDeviceToHost, gs->set.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(gs->set.stream);
+  }
   gs->in_use = false;
   evict_idle_plans(v);
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next: %s", hipGetErrorString(e));
+  if (rc) return rc;
   *n_samples = want;
   s.st_next = f1;
   return PIPER_HIP_OK;
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
+  return stream_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f);
 }
 
 // ---- batched streaming: a group of n utterances on one slot, the next chunk of every active item in one generator launch ------------
 namespace {
 
 constexpr int kMaxGroup = 256;
-// The per-step descriptor: one row of kDescInts per generator row — source item, window start a, window length Fc (0: finished, dropped
-// or pad row), halo skip (f0 − a)·hop, samples of the chunk, offset of the chunk in the packed output.
-enum { kDescSrc = 0, kDescA, kDescFc, kDescSkip, kDescN, kDescOff, kDescInts };
+// The per-step descriptor (kDescSrc … kDescInts: pcm16.h, shared with the int16 pack kernel): one row of kDescInts per generator row — source
+// item, window start a, window length Fc (0: finished, dropped or pad row), halo skip (f0 − a)·hop, samples of the chunk, offset of the
+// chunk in the packed output.
 
 // z windows of one step → the generator plan's input: row r of zin [NBg][I][Fg] = z[src][:, a .. a + Fc), zero past Fc; lensF[r] = Fc.
 // One thread per 4 frames of one channel, so the loads run along frames (coalesced); float4 loads where the window start is 16-byte
@@ -3172,7 +3303,12 @@ int pool_event(StreamPool& P, hipEvent_t* out) {
 }
 
 // stream_next_batch on a pool slot: the next chunk of every active row in one generator launch at the pool's fixed batch.
-int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples) {
+// pcm: the chunks leave as int16 (host_pcm, gain) instead of fp32 (host_audio) — the int16 sibling of the pack kernel writes them into the
+// same device and staging buffers, half filled, and half the bytes cross the bus.
+int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm = false,
+              int16_t* host_pcm = nullptr, float gain = 1.0f) {
+  const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
+  const size_t sample_bytes = pcm ? sizeof(int16_t) : sizeof(float);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   const int n = P.capacity, NBg = P.NBg, hop = v->hop;
   auto& sg = v->staging[slot];
@@ -3202,10 +3338,10 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, in
   }
   for (int i = 0; i < n; i++) n_samples[i] = 0;
   if (total == 0) return PIPER_HIP_OK;  // idle: no active row (joins since the last step stay pending)
-  if (host_audio && max_samples < total)
+  if (want_out && max_samples < total)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
   constexpr size_t kAudioMinCap = (size_t)16 << 10;
-  if (host_audio && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
+  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
   // generator-only plan of the step's longest window at the pool's batch size: the plans a group of the same size uses
   Slot* gs = nullptr;
   bool built = false;
@@ -3226,10 +3362,14 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, in
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (e == hipSuccess) {
     const int px = (int)std::min<int64_t>(ceil_div((int64_t)P.chunk * hop, 1024), 64);
-    hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, P.d_desc, P.pack);
-    e = hipGetLastError();
+    if (pcm) {
+      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, P.d_desc, gain, (int16_t*)P.pack);
+    } else {
+      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, P.d_desc, P.pack);
+      e = hipGetLastError();
+    }
   }
-  if (e == hipSuccess && host_audio) e = hipMemcpyAsync(sg.h_audio, P.pack, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, q);
+  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, P.pack, (size_t)total * sample_bytes, hipMemcpyDeviceToHost, q);
   if (e == hipSuccess) e = stream_wait(q);
   gs->in_use = false;
   evict_idle_plans(v);
@@ -3237,7 +3377,7 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, in
   // the wait above covers the adopts q waited for: their events can be recorded again
   P.ev_free.insert(P.ev_free.end(), P.ev_pending.begin(), P.ev_pending.end());
   P.ev_pending.clear();
-  if (host_audio) memcpy(host_audio, sg.h_audio, (size_t)total * sizeof(float));
+  if (want_out) memcpy(pcm ? (void*)host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
   for (int i = 0; i < n; i++) {
     n_samples[i] = got[i];
     if (!got[i]) continue;
@@ -3283,9 +3423,13 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
   return steps;
 }
 
-PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
+namespace {
+// stream_next_batch; pcm / host_pcm / gain as for pool_step
+int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm, float gain) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples);
+  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples, pcm, host_pcm, gain);
+  const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
+  const size_t sample_bytes = pcm ? sizeof(int16_t) : sizeof(float);
   Slot* sp = slot_plan(v, slot);
   if (!sp || sp->bs_n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
@@ -3320,11 +3464,11 @@ PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, fl
   }
   for (int i = 0; i < n; i++) n_samples[i] = 0;
   if (total == 0) return PIPER_HIP_OK;  // end of the group
-  if (host_audio && max_samples < total)
+  if (want_out && max_samples < total)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
   if ((size_t)total > s.bs_pack_cap) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.bs_pack_cap);
   constexpr size_t kAudioMinCap = (size_t)16 << 10;
-  if (host_audio && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
+  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
   // generator-only plan of the step's longest window at the group's batch size (rows past their end have length 0)
   Slot* gs = nullptr;
   bool built = false;
@@ -3343,20 +3487,29 @@ PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, fl
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (e == hipSuccess) {
     const int px = (int)std::min<int64_t>(ceil_div((int64_t)s.st_chunk * hop, 1024), 64);
-    hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.bs_desc, s.bs_pack);
-    e = hipGetLastError();
+    if (pcm) {
+      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, s.bs_desc, gain, (int16_t*)s.bs_pack);
+    } else {
+      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.bs_desc, s.bs_pack);
+      e = hipGetLastError();
+    }
   }
-  if (e == hipSuccess && host_audio) e = hipMemcpyAsync(sg.h_audio, s.bs_pack, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, q);
+  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, s.bs_pack, (size_t)total * sample_bytes, hipMemcpyDeviceToHost, q);
   if (e == hipSuccess) e = stream_wait(q);
   gs->in_use = false;
   evict_idle_plans(v);
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
-  if (host_audio) memcpy(host_audio, sg.h_audio, (size_t)total * sizeof(float));
+  if (want_out) memcpy(pcm ? (void*)host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
   for (int i = 0; i < n; i++) {
     n_samples[i] = got[i];
     if (got[i]) s.bs_next[i] = std::min(s.h_F[i], s.bs_next[i] + s.st_chunk);
   }
   return PIPER_HIP_OK;
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
+  return batch_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f);
 }
 
 PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item) {
@@ -3492,6 +3645,113 @@ PH_EXPORT int piper_hip_voice_stream_pool_close(piper_hip_voice* v, int slot) {
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   pool_close(v, slot);
   return PIPER_HIP_OK;
+}
+
+// ---- 16-bit PCM straight from the device (pcm16.hip): the launches go on the slot's stream behind the plan's graph, outside it -----------
+PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm, int64_t max_samples) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  Slot* p = slot_plan(v, slot);
+  if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
+  float gain;
+  bool normalize;
+  int rc = pcm_params(params, &gain, &normalize);
+  if (rc) return rc;
+  if (!host_pcm) return piper_hip_voice_collect(v, slot, nullptr, 0);  // just wait (a bounded slot: and learn the lengths)
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  Slot& s = *p;
+  auto& sg = v->staging[slot];
+  const int NB = s.NB, hop = v->hop;
+  if (NB > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: %d items (at most %d)", NB, kMaxGroup);
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / hop);  // frames of a row of s.audio
+  const bool bounded = s.bounded_pending;
+  // a bounded slot's lengths are still on the device: the caller makes room for the capacity, as for collect
+  int64_t need = 0;
+  if (bounded) need = (int64_t)F * hop * NB;
+  else for (int b = 0; b < NB; b++) need += (int64_t)s.h_F[b] * hop;
+  if (max_samples < need) {
+    if (bounded)
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_prepared_samples before collect), got %lld",
+              (long long)need, (long long)max_samples);
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: buffer holds %lld < %lld samples", (long long)max_samples, (long long)need);
+  }
+  float* peaks_host = nullptr;
+  if (normalize) {
+    if (!s.peaks) {
+      void* q = nullptr;
+      if ((rc = plan_alloc(v, s, (size_t)NB * sizeof(float), &q))) return rc;
+      s.peaks = (float*)q;
+    }
+    if ((rc = grow_pinned(sg.h_peaks, sg.cap_peaks, (size_t)kMaxGroup, (size_t)kMaxGroup))) return rc;
+    if (hipHostGetDevicePointer((void**)&peaks_host, sg.h_peaks, 0) != hipSuccess) { peaks_host = nullptr; (void)hipGetLastError(); }
+  }
+  PcmRoute r;
+  if ((rc = pcm_route(v, s, sg, host_pcm, (size_t)need, (size_t)F * hop * NB, &r))) return rc;
+  const hipStream_t q = s.set.stream;
+  if (normalize) PH_HIP(launch_pcm16_peak(q, s.audio, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(launch_pcm16_pack(q, s.audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst), PIPER_HIP_ERR_LAUNCH);
+  if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, (size_t)NB * sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
+  if ((rc = pcm_land(sg, r, q, host_pcm, (size_t)need))) return rc;
+  if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
+  if (r.mapped && !r.caller_pinned) {  // the kernel stored into the staging: the true total is known by now
+    int64_t total = 0;
+    for (int b = 0; b < NB; b++) total += (int64_t)s.h_F[b] * hop;
+    memcpy(host_pcm, r.stage, (size_t)total * sizeof(int16_t));
+  }
+  if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + NB);
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* peaks, int max_items) {
+  if (!v || !peaks) PH_FAIL(PIPER_HIP_ERR_ARG, "peaks: null argument");
+  const Slot* p = slot_plan(v, slot);
+  if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
+  if (p->h_peaks.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "peaks: slot %d has not been collected with normalize = 1 since its last launch", slot);
+  if (max_items < (int)p->h_peaks.size()) PH_FAIL(PIPER_HIP_ERR_SHAPE, "peaks: buffer holds %d < %d items", max_items, (int)p->h_peaks.size());
+  memcpy(peaks, p->h_peaks.data(), p->h_peaks.size() * sizeof(float));
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int16_t* host_pcm,
+                                               int64_t max_samples, int64_t* n_samples) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  float gain;
+  bool normalize;
+  int rc = pcm_params(params, &gain, &normalize);
+  if (rc) return rc;
+  if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
+  if ((rc = piper_hip_voice_launch(v, 0))) return rc;
+  if ((rc = piper_hip_voice_collect_pcm16(v, 0, params, host_pcm, max_samples))) return rc;
+  if (n_samples) *n_samples = (int64_t)v->attached[0]->h_F[0] * v->hop;
+  return PIPER_HIP_OK;
+}
+
+namespace {
+// a stream step's params: normalisation needs the utterance's peak, which no step before the last knows
+int pcm_step_params(const piper_hip_voice* v, const piper_hip_pcm_params* params, float* gain) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  bool normalize;
+  const int rc = pcm_params(params, gain, &normalize);
+  if (rc) return rc;
+  if (normalize) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "pcm16: normalize = 1 on a stream step (the utterance's peak is not known before its last window)");
+  return PIPER_HIP_OK;
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_next_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
+                                                int64_t max_samples, int64_t* n_samples) {
+  float gain;
+  const int rc = pcm_step_params(v, params, &gain);
+  if (rc) return rc;
+  if (slot_pool(v, slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a streaming pool: use stream_next_batch_pcm16", slot);
+  return stream_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain);
+}
+
+PH_EXPORT int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
+                                                      int64_t max_samples, int64_t* n_samples) {
+  float gain;
+  const int rc = pcm_step_params(v, params, &gain);
+  if (rc) return rc;
+  return batch_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain);
 }
 
 PH_EXPORT int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u, float* host_audio,

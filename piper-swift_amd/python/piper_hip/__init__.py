@@ -112,6 +112,14 @@ class Utterance(C.Structure):
 NOISE_MODES = {"injected": 0, "device": 1}
 
 
+class PcmParams(C.Structure):
+    """piper_hip_pcm_params: linear gain (0 = 1.0) and the peak-normalisation flag of the 16-bit PCM entry points."""
+    _fields_ = [("gain", C.c_float), ("normalize", C.c_int32)]
+
+
+c_i16p = C.POINTER(C.c_int16)
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("avg_us", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -232,6 +240,12 @@ _PROTOS = {
     "piper_hip_voice_launch": (C.c_int, [c_vp, C.c_int]),
     "piper_hip_voice_collect": (C.c_int, [c_vp, C.c_int, c_f32p, C.c_int64]),
     "piper_hip_voice_synthesize": (C.c_int, [c_vp, C.POINTER(Utterance), c_f32p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_pcm16_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_float, C.POINTER(c_vp), c_vp]),
+    "piper_hip_voice_collect_pcm16": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), c_i16p, C.c_int64]),
+    "piper_hip_voice_synthesize_pcm16": (C.c_int, [c_vp, C.POINTER(Utterance), C.POINTER(PcmParams), c_i16p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_next_pcm16": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), c_i16p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_next_batch_pcm16": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), c_i16p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_peaks": (C.c_int, [c_vp, C.c_int, c_f32p, C.c_int]),
     "piper_hip_voice_tap": (C.c_int, [c_vp, C.c_int, C.c_char_p, c_f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "piper_hip_voice_last_gpu_ms": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_double)]),
     "piper_hip_voice_slot_stream": (c_vp, [c_vp, C.c_int]),
@@ -308,10 +322,11 @@ def device_count():
 
 
 class DeviceBuffer:
-    """An MTLBuffer stand-in: device pointer + element count, owned by a backend's pool."""
+    """An MTLBuffer stand-in: device pointer + element count, owned by a backend's pool. `count` is in elements of `dtype`: float32
+    everywhere but for the result of pcm16F32, whose buffer holds `count` int16 samples (read it with downloadInt16, not downloadFloat32)."""
 
-    def __init__(self, backend, ptr, count, owned=True):
-        self.backend, self.ptr, self.count, self.owned = backend, ptr, int(count), owned
+    def __init__(self, backend, ptr, count, owned=True, dtype=np.float32):
+        self.backend, self.ptr, self.count, self.owned, self.dtype = backend, ptr, int(count), owned, np.dtype(dtype)
 
     def free(self):
         if self.owned and self.ptr:
@@ -370,6 +385,8 @@ class HipBackend:
         return DeviceBuffer(self, p.value, a.size)
 
     def downloadFloat32(self, buf, count=None):
+        if count is None and isinstance(buf, DeviceBuffer) and buf.dtype != np.float32:
+            raise TypeError(f"downloadFloat32: the buffer holds {buf.count} {buf.dtype} elements, not floats")
         n = buf.count if count is None else int(count)
         out = np.empty(n, np.float32)
         _check(self.lib.piper_hip_download_f32(self.ctx, _ptr(buf), out.ctypes.data_as(c_f32p), n))
@@ -557,6 +574,23 @@ class HipBackend:
         _check(self.lib.piper_hip_download_f32(self.ctx, p, out.ctypes.data_as(c_f32p), 2 * int(count)))
         _check(self.lib.piper_hip_free(self.ctx, p))
         return out.view(np.uint32).reshape(-1, 2)
+
+    def pcm16F32(self, buf, gain=1.0, count=None, out=None, commandBuffer=None):
+        """`count` device floats → 16-bit PCM on the device (piper_hip_pcm16_f32): x · gain, clamp to [−1, 1], × 32767 in double, truncate —
+        the samples pcm16() gives on the host. Returns a DeviceBuffer of `count` int16 (downloadInt16); `out`: a device address to write to
+        (2-byte alignment suffices), returned as it is."""
+        n = buf.count if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        _check(self.lib.piper_hip_pcm16_f32(self.ctx, _ptr(buf), n, float(gain), C.byref(p), commandBuffer))
+        return DeviceBuffer(self, p.value, n, owned=out is None, dtype=np.int16)
+
+    def downloadInt16(self, buf, count=None):
+        """The first `count` int16 of a device buffer of this backend's pool → host array. (Copied as whole floats: an odd count reads one
+        sample more, which a pool block — a power of two of at least 256 bytes — always holds.)"""
+        n = buf.count if count is None else int(count)
+        out = np.empty(n + 1, np.int16)
+        _check(self.lib.piper_hip_download_f32(self.ctx, _ptr(buf), out.ctypes.data_as(c_f32p), (n + 1) // 2))
+        return out[:n].copy()
 
     # -- fused
     def relAttentionF32(self, q, k, v, embRelK, embRelV, n, heads, headDim, t, window, commandBuffer=None):
@@ -810,15 +844,22 @@ class StreamPool:
         rt._keep.pop(self.work_slot, None)  # the inputs were copied before the call returned
         return [(int(items[i]), int(samples[i])) for i in range(n)]
 
-    def step(self):
-        """{item: chunk} of every active session; an empty dict when the pool is idle."""
+    def step(self, pcm=False, gain=1.0, normalize=False):
+        """{item: chunk} of every active session; an empty dict when the pool is idle. pcm=True: int16 chunks converted on the device
+        (piper_hip_voice_stream_next_batch_pcm16; normalize is refused there — UnsupportedOp — and consumes nothing)."""
         rt = self.rt
-        _check(rt.lib.piper_hip_voice_stream_next_batch(rt.voice, self.slot, self._buf.ctypes.data_as(c_f32p), self._buf.size, self._got))
+        if pcm:
+            buf = self._buf.view(np.int16)[:self._buf.size]
+            prm = PcmParams(float(gain), int(bool(normalize)))
+            _check(rt.lib.piper_hip_voice_stream_next_batch_pcm16(rt.voice, self.slot, C.byref(prm), buf.ctypes.data_as(c_i16p), buf.size, self._got))
+        else:
+            buf = self._buf
+            _check(rt.lib.piper_hip_voice_stream_next_batch(rt.voice, self.slot, buf.ctypes.data_as(c_f32p), buf.size, self._got))
         out, off = {}, 0
         for item in range(self.capacity):
             c = int(self._got[item])
             if c:
-                out[item] = self._buf[off:off + c].copy()
+                out[item] = buf[off:off + c].copy()
                 off += c
         return out
 
@@ -965,24 +1006,30 @@ class HipRuntime:
             off += len(ids)
         return outs
 
-    def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0):
-        """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window."""
+    def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0):
+        """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
+        pcm=True: int16 chunks converted on the device (piper_hip_voice_stream_next_pcm16), scaled by `gain`."""
         u, keep = self._utt(phonemeIDs, durations, noise, noiseScale)
         n_chunks = self.lib.piper_hip_voice_stream_begin(self.voice, C.byref(u), slot, int(chunkFrames))
         if n_chunks < 0:
             _check(n_chunks)
-        buf = np.empty(int(chunkFrames) * self.cfg.hop, np.float32)
+        buf = np.empty(int(chunkFrames) * self.cfg.hop, np.int16 if pcm else np.float32)
         got = C.c_int64()
+        prm = PcmParams(float(gain), 0)
         while True:
-            _check(self.lib.piper_hip_voice_stream_next(self.voice, slot, buf.ctypes.data_as(c_f32p), buf.size, C.byref(got)))
+            if pcm:
+                _check(self.lib.piper_hip_voice_stream_next_pcm16(self.voice, slot, C.byref(prm), buf.ctypes.data_as(c_i16p), buf.size, C.byref(got)))
+            else:
+                _check(self.lib.piper_hip_voice_stream_next(self.voice, slot, buf.ctypes.data_as(c_f32p), buf.size, C.byref(got)))
             if got.value == 0:
                 return
             yield buf[:got.value].copy()
 
-    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0):
+    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0):
         """Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
-        arrays — the next chunk of every item, empty once the item is finished or dropped (stream_drop)."""
+        arrays — the next chunk of every item, empty once the item is finished or dropped (stream_drop). pcm=True: int16 chunks converted on
+        the device (piper_hip_voice_stream_next_batch_pcm16), scaled by `gain`."""
         n = len(utterances)
         arr = (Utterance * max(n, 1))()
         keep = []
@@ -994,10 +1041,14 @@ class HipRuntime:
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
-        buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), np.float32)
+        buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), np.int16 if pcm else np.float32)
         got = (C.c_int64 * n)()
+        prm = PcmParams(float(gain), 0)
         while True:
-            _check(self.lib.piper_hip_voice_stream_next_batch(self.voice, slot, buf.ctypes.data_as(c_f32p), buf.size, got))
+            if pcm:
+                _check(self.lib.piper_hip_voice_stream_next_batch_pcm16(self.voice, slot, C.byref(prm), buf.ctypes.data_as(c_i16p), buf.size, got))
+            else:
+                _check(self.lib.piper_hip_voice_stream_next_batch(self.voice, slot, buf.ctypes.data_as(c_f32p), buf.size, got))
             counts = [int(x) for x in got]
             if not any(counts):
                 return
@@ -1076,6 +1127,44 @@ class HipRuntime:
             n = self.prepared_samples(slot)[1]
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
+
+    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None):
+        """collect() with 16-bit PCM converted on the device (piper_hip_voice_collect_pcm16): the items back to back at their true lengths.
+        normalize=False: the samples pcm16(collect(slot)) gives; normalize=True: Piper's peak normalisation per item (peaks(slot) afterwards).
+        The fp32 waveform stays in the plan: collect / collect_pcm16 may follow in any order."""
+        n = self._keep[slot][1]
+        if out is None:
+            out = np.empty(max(n, 1), np.int16)
+        assert out.dtype == np.int16 and out.size >= n and out.flags.c_contiguous
+        prm = PcmParams(float(gain), int(bool(normalize)))
+        _check(self.lib.piper_hip_voice_collect_pcm16(self.voice, slot, C.byref(prm), out.ctypes.data_as(c_i16p), n))
+        if len(self._keep[slot]) > 2 and self._keep[slot][2]:  # bounded: n was the capacity; the true lengths are known now
+            n = self.prepared_samples(slot)[1]
+            self._keep[slot] = (self._keep[slot][0], n, False)
+        return out[:n]
+
+    def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
+                         normalize=False, **kw):
+        """synthesize() ending in 16-bit PCM converted on the device (slot 0)."""
+        if durations is not None and not kw:  # the one-call C entry point
+            u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
+            n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
+            out = np.empty(max(n, 1), np.int16)
+            got = C.c_int64()
+            prm = PcmParams(float(gain), int(bool(normalize)))
+            _check(self.lib.piper_hip_voice_synthesize_pcm16(self.voice, C.byref(u), C.byref(prm), out.ctypes.data_as(c_i16p), n, C.byref(got)))
+            self._keep.pop(0, None)
+            return out[:got.value]
+        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, **kw)
+        self.launch(0)
+        return self.collect_pcm16(0, gain, normalize)
+
+    def peaks(self, slot):
+        """max |x| of each item of the slot, after a collect_pcm16(normalize=True) of its latest run."""
+        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
+        out = np.empty(max(nb, 1), np.float32)
+        _check(self.lib.piper_hip_voice_peaks(self.voice, slot, out.ctypes.data_as(c_f32p), nb))
+        return out[:nb]
 
     def tap(self, slot, name, max_floats=None):
         """A named intermediate of the slot, items back to back at their true lengths (max_floats None: sized by the library).

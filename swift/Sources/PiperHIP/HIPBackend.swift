@@ -155,6 +155,14 @@ public final class HIPBackend {
         try unaryF32(PIPER_HIP_LEAKYRELU, input: input, count: count, alpha: alpha, commandBuffer: commandBuffer)
     }
 
+    /// `count` device floats → `count` int16 on the device (piper_hip_pcm16_f32): x · gain, clamp to [−1, 1], × 32767 in double, truncate —
+    /// the samples WavFileWriter.swift:20-30 writes. The buffer holds int16 (`count` · 2 bytes).
+    public func pcm16F32(input: HIPBuffer, count: Int, gain: Float = 1.0, commandBuffer: Stream? = nil) throws -> HIPBuffer {
+        var out: UnsafeMutablePointer<Int16>? = nil
+        try Self.check(piper_hip_pcm16_f32(ctx, input.f32, count, gain, &out, commandBuffer))
+        return HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx)
+    }
+
     // ---- binary with NumPy broadcasting, output rank ≤ 4 (MetalBackend.swift:2099-2134, 2592-2610) ----
     private func binaryBroadcastF32(_ op: piper_hip_binary_op, a: HIPBuffer, aShape: [Int], b: HIPBuffer, bShape: [Int],
                                     commandBuffer: Stream?) throws -> (out: HIPBuffer, outShape: [Int]) {

@@ -203,6 +203,70 @@ public final class PiperHIPRuntime {
         try HIPBackend.check(piper_hip_voice_stream_pool_close(voice, slot))
     }
 
+    // ---- 16-bit PCM converted on the device (include/piper_hip.h "16-bit PCM straight from the device") ----
+
+    /// piper_hip_voice_collect_pcm16 on a launched slot: the items back to back as int16. normalize = false: the samples
+    /// piper_hip_pcm16_from_f32 gives for what collect returns; true: Piper's peak normalisation per item (peaks(slot:) afterwards).
+    public func collectPCM16(slot: Int32, gain: Float = 1.0, normalize: Bool = false) throws -> [Int16] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: normalize ? 1 : 0)
+        var cap: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_prepared_samples(voice, slot, nil, 0, &cap))      // a bounded slot: its capacity
+        var pcm = [Int16](repeating: 0, count: Int(cap))
+        try HIPBackend.check(piper_hip_voice_collect_pcm16(voice, slot, &prm, &pcm, cap))
+        var total: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_prepared_samples(voice, slot, nil, 0, &total))    // the true length now
+        pcm.removeLast(pcm.count - Int(total))
+        return pcm
+    }
+
+    /// synthesize(phonemeIDs:durations:noise:noiseScale:) ending in int16 (piper_hip_voice_synthesize_pcm16).
+    public func synthesizePCM16(phonemeIDs: [Int64], durations: [Int32], noise: [Float]?, noiseScale: Float, gain: Float = 1.0,
+                                normalize: Bool = false) throws -> [Int16] {
+        var n: Int64 = 0
+        var prm = piper_hip_pcm_params(gain: gain, normalize: normalize ? 1 : 0)
+        return try phonemeIDs.withUnsafeBufferPointer { ids in try durations.withUnsafeBufferPointer { dur in
+            try (noise ?? []).withUnsafeBufferPointer { nz in
+                var u = piper_hip_utterance(phoneme_ids: ids.baseAddress, t: Int32(ids.count), durations: dur.baseAddress,
+                                            noise: noise == nil ? nil : nz.baseAddress, noise_scale: noiseScale,
+                                            noise_mode: Int32(PIPER_HIP_NOISE_INJECTED), seed: 1234, length_scale: 1.0, noise_w: 0.8, dp_noise: nil)
+                var pcm = [Int16](repeating: 0, count: Int(piper_hip_voice_num_samples(voice, &u)))
+                try HIPBackend.check(piper_hip_voice_synthesize_pcm16(voice, &u, &prm, &pcm, Int64(pcm.count), &n))
+                return pcm
+            }
+        } }
+    }
+
+    /// max |x| of each item of the slot after a collectPCM16(normalize: true) of its latest run.
+    public func peaks(slot: Int32) throws -> [Float] {
+        var out = [Float](repeating: 0, count: Int(piper_hip_voice_batch_size(voice, slot)))
+        try HIPBackend.check(piper_hip_voice_peaks(voice, slot, &out, Int32(out.count)))
+        return out
+    }
+
+    /// The next chunk of the single stream on `slot` as int16 (piper_hip_voice_stream_next_pcm16); empty at the end of the stream.
+    public func streamNextPCM16(slot: Int32, chunkFrames: Int32 = 64, gain: Float = 1.0) throws -> [Int16] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: 0)
+        var buf = [Int16](repeating: 0, count: Int(chunkFrames) * hop)
+        var n: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_stream_next_pcm16(voice, slot, &prm, &buf, Int64(buf.count), &n))
+        return Array(buf[0..<Int(n)])
+    }
+
+    /// The next chunk of every active item of the group (`rows` = its size) or pool (`rows` = its capacity) on `slot` as int16
+    /// (piper_hip_voice_stream_next_batch_pcm16), keyed by item; empty = the group has ended / the pool is idle. Float and PCM steps may alternate.
+    public func streamNextBatchPCM16(slot: Int32, rows: Int32, chunkFrames: Int32 = 64, gain: Float = 1.0) throws -> [Int32: [Int16]] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: 0)
+        var buf = [Int16](repeating: 0, count: Int(rows) * Int(chunkFrames) * hop)
+        var counts = [Int64](repeating: 0, count: Int(rows))
+        try HIPBackend.check(piper_hip_voice_stream_next_batch_pcm16(voice, slot, &prm, &buf, Int64(buf.count), &counts))
+        var out = [Int32: [Int16]](), off = 0
+        for (item, c) in counts.enumerated() where c > 0 {
+            out[Int32(item)] = Array(buf[off..<off + Int(c)])
+            off += Int(c)
+        }
+        return out
+    }
+
     /// WavFileWriter (Sources/PiperCLI/WavFileWriter.swift:20-60): float → int16 with the CLI's x·32767 clamp, RIFF header.
     public func writeWav(_ samples: [Float], to path: String) throws {
         try HIPBackend.check(piper_hip_wav_write(path, samples, samples.count, sampleRate))
