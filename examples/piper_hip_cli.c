@@ -12,7 +12,7 @@
  *                            well), converted on the device (piper_hip_voice_synthesize_pcm16; after --output, collect_pcm16 on the
  *                            slot that ran): --volume V scales it (linear, default 1),
  *                            --normalize applies Piper's peak normalisation (audio_float_to_int16). Both flags act on --output-raw only.
- * Without --model the synthetic voice of the tests is used (--quality medium|high); its duration predictor has random weights, so frames per id are
+ * Without --model the synthetic voice of the tests is used (--quality medium|high|low|x_low; low and x_low are the 16 kHz tier); its duration predictor has random weights, so frames per id are
  * pinned to --pin-frames (3, the bench's convention) unless --predict asks for the predictor (the only mode a real voice has).
  *
  * build: gcc -std=c99 -O2 -Iinclude examples/piper_hip_cli.c -Lpiper-swift_amd/lib -lpiper_hip -Wl,-rpath,$PWD/piper-swift_amd/lib -o piper_hip_cli
@@ -146,12 +146,19 @@ int main(int argc, char** argv) {
   const char* model = arg_value(argc, argv, "--model");
   const char* config = arg_value(argc, argv, "--config");
   const char* quality = arg_value(argc, argv, "--quality");
+  static const char* const quality_names[4] = {"medium", "high", "low", "x_low"}; /* piper_hip_voice_config_preset's numbering */
+  static const char* const synthetic_names[4] = {"synthetic:medium", "synthetic:high", "synthetic:low", "synthetic:x_low"};
+  int preset = 0;
+  if (quality) {
+    for (preset = 0; preset < 4 && strcmp(quality, quality_names[preset]) != 0; preset++) {}
+    if (preset == 4) { fprintf(stderr, "--quality %s: expected medium, high, low or x_low\n", quality); return 2; }
+  }
   const int scale_bench = has_flag(argc, argv, "--scale-bench");
   const char* ids_arg = arg_value(argc, argv, "--phoneme-ids");
   if (!scale_bench && !ids_arg) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize]\n"
-                    "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high] [--predict] [--pin-frames N]\n", argv[0], argv[0]);
+                    "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n", argv[0], argv[0]);
     return 2;
   }
 
@@ -190,7 +197,7 @@ int main(int argc, char** argv) {
       r.noise_scale = info.noise_scale; r.length_scale = info.length_scale; r.noise_w = info.noise_w;
     }
   } else {
-    CHECK(piper_hip_voice_config_preset(quality && strcmp(quality, "high") == 0 ? 1 : 0, &cfg));
+    CHECK(piper_hip_voice_config_preset(preset, &cfg));
     CHECK(piper_hip_voice_blob_floats(&cfg, &n_floats));
     blob = (float*)malloc(n_floats * sizeof(float));
     CHECK(piper_hip_voice_synthetic_blob(&cfg, 1234, blob, n_floats));
@@ -256,7 +263,7 @@ int main(int argc, char** argv) {
   const int want_timings = tenv && strcmp(tenv, "1") == 0;
 
   printf("{\n  \"backend\": \"piper-hip\",\n  \"base_test_phonemes\": 14,\n  \"iters\": %d,\n  \"max_phonemes\": %d,\n  \"mode\": \"scale-bench\",\n  \"model_path\": \"%s\",\n  \"results\": [\n",
-         iters, max_phonemes, model ? model : (quality && strcmp(quality, "high") == 0 ? "synthetic:high" : "synthetic:medium"));
+         iters, max_phonemes, model ? model : synthetic_names[preset]);
   int64_t* ids = (int64_t*)malloc(sizeof(int64_t) * 4096);
   double* wall = (double*)malloc(sizeof(double) * (size_t)iters);
   for (int fi = 0; fi < nf; fi++) {

@@ -299,7 +299,9 @@ typedef struct {
   float dp_tail_bound;   /* 5.0 */
 } piper_hip_voice_config;
 
-/* Piper medium / high geometry (SURVEY.md §8a †). quality: 0 = medium, 1 = high. */
+/* Piper's four published geometries (SURVEY.md §8a †). quality: 0 = medium, 1 = high, 2 = low (the medium geometry at
+ * sample_rate 16000), 3 = x_low (hidden 96, inter 96, ffn 384, two heads of head_dim 48, the medium generator and
+ * predictor fields, sample_rate 16000). Any other value: PIPER_HIP_ERR_ARG. */
 int piper_hip_voice_config_preset(int quality, piper_hip_voice_config* out);
 /* Number of floats in the packed weight blob for `cfg` (layout: include/piper_hip_voice_layout.h). */
 int piper_hip_voice_blob_floats(const piper_hip_voice_config* cfg, size_t* n_floats);

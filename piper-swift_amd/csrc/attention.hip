@@ -911,6 +911,24 @@ int launch_att_block(hipStream_t s, const float* q, const float* k, const float*
   return 0;
 }
 
+// Head dims the MFMA kernels are instantiated for: 96 (medium, high, low) and 48 (x_low). The templates carry D throughout (NS = D/4
+// contraction steps, NCT = D/16 channel tiles — 3 of the 8 waves run P·V at D = 48 — and D·32 float4 slots per staged tile, a whole
+// multiple of the 512 threads for both); the LDS row strides kLdK / kLdV / Tp depend on the key axis only.
+bool att_head_dim_ok(int d) { return d == 96 || d == 48; }
+
+int dispatch_att_lds(int d, hipStream_t s, const float* q, const float* k, const float* v, const float* ek, const float* ev, float* out, int N, int H,
+                     int T, int w, int64_t in_bs, int64_t out_bs, const int* len_ptr, int nsplit, float* part_o, float* part_ml) {
+  return d == 96 ? launch_att_lds<96>(s, q, k, v, ek, ev, out, N, H, T, w, in_bs, out_bs, len_ptr, nsplit, part_o, part_ml)
+                 : launch_att_lds<48>(s, q, k, v, ek, ev, out, N, H, T, w, in_bs, out_bs, len_ptr, nsplit, part_o, part_ml);
+}
+
+template <int RV>
+int dispatch_att_mfma(int d, hipStream_t s, const float* q, const float* k, const float* v, const float* ek, const float* ev, float* out, int N,
+                      int H, int T, int w, int64_t in_bs, int64_t out_bs, const int* len_ptr) {
+  return d == 96 ? launch_att_mfma<96, RV>(s, q, k, v, ek, ev, out, N, H, T, w, in_bs, out_bs, len_ptr)
+                 : launch_att_mfma<48, RV>(s, q, k, v, ek, ev, out, N, H, T, w, in_bs, out_bs, len_ptr);
+}
+
 }  // namespace
 
 namespace ph {
@@ -924,7 +942,7 @@ int rel_attention_split_parts(piper_hip_ctx* ctx, int N, int H, int d, int T, in
   static const bool no_split = getenv("PIPER_HIP_ATT_NO_SPLIT") != nullptr;
   static const int forced = [] { const char* e = getenv("PIPER_HIP_ATT_SPLIT"); return e ? std::min(std::max(atoi(e), 2), 8) : 0; }();  // tuning
   static const int min_t = [] { const char* e = getenv("PIPER_HIP_ATT_SPLIT_MIN_T"); return e ? atoi(e) : 129; }();  // two key tiles or more
-  if (no_split || d != 96 || T < min_t || T > 1024 || (T & 3) != 0 || w < 0 || 2 * w + 1 > 16 || N < 1 || H < 1) return 1;
+  if (no_split || !att_head_dim_ok(d) || T < min_t || T > 1024 || (T & 3) != 0 || w < 0 || 2 * w + 1 > 16 || N < 1 || H < 1) return 1;
   const int ntile = (T + kTK - 1) / kTK;
   const int64_t blocks = (int64_t)ceil_div(T, 16) * H * N;
   const int parts = forced ? forced : (int)std::min<int64_t>(ntile, ctx->num_cus / std::max<int64_t>(1, blocks));
@@ -935,10 +953,10 @@ int launch_rel_attention_split(piper_hip_ctx* ctx, hipStream_t s, const float* q
                                const float* ev, float* out, int N, int H, int d, int T, int w, int64_t in_batch_stride,
                                int64_t out_batch_stride, const int* len_ptr, int nsplit, float* part_o, float* part_ml) {
   if (N <= 0 || T <= 0) return PIPER_HIP_OK;
-  if (nsplit < 2 || !part_o || !part_ml || d != 96 || H > 65535 || N > 65535 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) != 0 ||
+  if (nsplit < 2 || !part_o || !part_ml || !att_head_dim_ok(d) || H > 65535 || N > 65535 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) != 0 ||
       (in_batch_stride & 3) != 0 || nsplit > (T + kTK - 1) / kTK || nsplit > 8 || T > 1024 || (T & 3) != 0 || w < 0 || 2 * w + 1 > 16)
     return launch_rel_attention(ctx, s, q, k, v, ek, ev, out, N, H, d, T, w, in_batch_stride, out_batch_stride, len_ptr);
-  if (launch_att_lds<96>(s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr, nsplit, part_o, part_ml) != 0)
+  if (dispatch_att_lds(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr, nsplit, part_o, part_ml) != 0)
     return launch_rel_attention(ctx, s, q, k, v, ek, ev, out, N, H, d, T, w, in_batch_stride, out_batch_stride, len_ptr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rel_attention (split) launch failed: %s", hipGetErrorString(e));
@@ -951,24 +969,24 @@ int launch_rel_attention(piper_hip_ctx* ctx, hipStream_t s, const float* q, cons
   if (N <= 0 || T <= 0) return PIPER_HIP_OK;
   static const bool no_mfma = getenv("PIPER_HIP_ATT_SCALAR") != nullptr;  // A/B switch: the round-1 scalar kernel
   static const bool no_lds = getenv("PIPER_HIP_ATT_NO_LDS") != nullptr;  // A/B switch: register-fragment MFMA kernel
-  if (!no_mfma && !no_lds && d == 96 && w >= 0 && 2 * w + 1 <= 16 && H <= 65535 && N <= 65535 && T <= 1024 && T >= 4 && (T & 3) == 0 &&
+  if (!no_mfma && !no_lds && att_head_dim_ok(d) && w >= 0 && 2 * w + 1 <= 16 && H <= 65535 && N <= 65535 && T <= 1024 && T >= 4 && (T & 3) == 0 &&
       (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0 && (in_batch_stride & 3) == 0) {
-    if (launch_att_lds<96>(s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr, 1, nullptr, nullptr) == 0) {
+    if (dispatch_att_lds(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr, 1, nullptr, nullptr) == 0) {
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rel_attention (lds) launch failed: %s", hipGetErrorString(e));
       return PIPER_HIP_OK;
     }
   }
-  if (!no_mfma && d == 96 && w >= 0 && 2 * w + 1 <= 16 && H <= 65535 && N <= 65535 && T <= 4096) {
-    int rc = T <= 2048 ? launch_att_mfma<96, 16>(s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr)
-                       : launch_att_mfma<96, 8>(s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr);
+  if (!no_mfma && att_head_dim_ok(d) && w >= 0 && 2 * w + 1 <= 16 && H <= 65535 && N <= 65535 && T <= 4096) {
+    int rc = T <= 2048 ? dispatch_att_mfma<16>(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr)
+                       : dispatch_att_mfma<8>(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr);
     if (rc == 0) {
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rel_attention (mfma) launch failed: %s", hipGetErrorString(e));
       return PIPER_HIP_OK;
     }
   }
-  if (len_ptr) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "rel_attention: per-item lengths need the MFMA kernel (head_dim 96, window ≤ 7)");
+  if (len_ptr) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "rel_attention: per-item lengths need the MFMA kernel (head_dim 96 or 48, window ≤ 7)");
   if (d > kBlock) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "rel_attention: head_dim %d > %d", d, kBlock);
   if (T > 4096) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "rel_attention: T=%d exceeds 4096 (reference max-phonemes cap)", T);
   if (H > 65535 || N > 65535) PH_FAIL(PIPER_HIP_ERR_SHAPE, "rel_attention: heads/batch too large");

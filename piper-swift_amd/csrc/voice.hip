@@ -1972,7 +1972,9 @@ PH_EXPORT int piper_hip_voice_create(piper_hip_ctx* ctx, const piper_hip_voice_c
   *out = nullptr;
   int rc = validate_config(cfg);
   if (rc) return rc;
-  if (cfg->hidden % 32 || cfg->inter % 64) PH_FAIL(PIPER_HIP_ERR_SHAPE, "voice: hidden must be a multiple of 32 and inter of 64");
+  // hidden % 32: the gated convs pair tanh / sigmoid rows in 64-row units of 2·hidden; inter % 32: the couplings work on 16-row tiles of
+  // inter / 2 channels (x_low: 48 = 3 tiles)
+  if (cfg->hidden % 32 || cfg->inter % 32) PH_FAIL(PIPER_HIP_ERR_SHAPE, "voice: hidden and inter must be multiples of 32");
   PH_HIP(hipSetDevice(ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   std::unique_ptr<piper_hip_voice> v(new piper_hip_voice());
   v->ctx = ctx;

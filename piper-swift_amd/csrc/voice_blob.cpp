@@ -22,6 +22,11 @@ PH_EXPORT int piper_hip_voice_config_preset(int quality, piper_hip_voice_config*
   c->n_rb = 3;
   c->sample_rate = 22050;
   c->dp_present = 1; c->dp_kernel = 3; c->dp_dds_layers = 3; c->dp_n_flows = 4; c->dp_bins = 10; c->dp_tail_bound = 5.0f;
+  if (quality == 2 || quality == 3) {  // the 16 kHz tier: low = medium at 16 000 Hz; x_low = 96 channels (head_dim 48) on the medium generator
+    c->sample_rate = 16000;
+    if (quality == 3) { c->hidden = 96; c->inter = 96; c->ffn = 384; }
+    quality = 0;
+  }
   if (quality == 0) {  // medium: ResBlock2, 256 ch, rates 8,8,4
     c->up_initial = 256;
     c->n_ups = 3;
@@ -48,7 +53,7 @@ PH_EXPORT int piper_hip_voice_config_preset(int quality, piper_hip_voice_config*
       c->rb_dilations[j][0] = 1; c->rb_dilations[j][1] = 3; c->rb_dilations[j][2] = 5;
     }
   } else {
-    PH_FAIL(PIPER_HIP_ERR_ARG, "unknown quality preset %d (0 = medium, 1 = high)", quality);
+    PH_FAIL(PIPER_HIP_ERR_ARG, "unknown quality preset %d (0 = medium, 1 = high, 2 = low, 3 = x_low)", quality);
   }
   return PIPER_HIP_OK;
 }

@@ -635,9 +635,13 @@ class HipBackend:
 
 # ---------------------------------------------------------------- voice level (PiperMetalRuntime)
 
+QUALITIES = {"medium": 0, "high": 1, "low": 2, "x_low": 3}
+
+
 def voice_config(quality="medium"):
+    """Piper's four published qualities; low and x_low are the 16 kHz tier (x_low: 96 channels, head_dim 48)."""
     cfg = VoiceConfig()
-    _check(load_library().piper_hip_voice_config_preset({"medium": 0, "high": 1}[quality], C.byref(cfg)))
+    _check(load_library().piper_hip_voice_config_preset(QUALITIES[quality], C.byref(cfg)))
     return cfg
 
 

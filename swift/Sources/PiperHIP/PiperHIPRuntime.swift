@@ -3,6 +3,26 @@
 import CPiperHIP
 import Foundation
 
+/// Piper's four published qualities, numbered as piper_hip_voice_config_preset numbers them. low and xLow are the 16 kHz tier: low is the
+/// medium geometry at 16 000 Hz, xLow has 96 channels (two heads of head_dim 48) in front of the medium generator.
+public enum PiperHIPQuality: Int32, CaseIterable {
+    case medium = 0, high = 1, low = 2, xLow = 3
+
+    /// The name Piper's voice list and `voice.onnx.json` ("audio.quality") use: "medium", "high", "low", "x_low".
+    public var name: String { ["medium", "high", "low", "x_low"][Int(rawValue)] }
+    public init?(name: String) {
+        guard let q = PiperHIPQuality.allCases.first(where: { $0.name == name }) else { return nil }
+        self = q
+    }
+
+    /// The geometry of the quality (piper_hip_voice_config_preset): what piper_hip_onnx_infer_config returns for a voice of that quality.
+    public func config() throws -> piper_hip_voice_config {
+        var cfg = piper_hip_voice_config()
+        try HIPBackend.check(piper_hip_voice_config_preset(rawValue, &cfg))
+        return cfg
+    }
+}
+
 public final class PiperHIPRuntime {
     private let backend: HIPBackend
     private var voice: OpaquePointer?
