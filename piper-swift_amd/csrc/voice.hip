@@ -213,6 +213,13 @@ enum PlanKind : int {
   PLAN_FROM_STATS = 3,  // everything AFTER the text encoder (expansion, flow, generator), from an m_p / logs_p tensor copied in from a PLAN_PREDICT plan
 };
 
+// One row of a batched stream on the host, the same record for an item of a group (Slot::bs_rows) and a row of a pool (StreamPool::Row):
+// the item's frames, its next frame, and whether the next step decodes a chunk of it (false: finished, dropped, or a pool row never taken).
+struct StreamRow {
+  int F = 0, next = 0;
+  bool active = false;
+};
+
 struct Slot {
   StreamSet set;  // empty (set.stream == nullptr) while the plan is idle: slot_init takes one, give_back_set returns it
   // A Slot is a PLAN: schedule + arena + graph for one bucket (kind, T, F, NB). T and F are the bucket's row lengths; the
@@ -266,11 +273,9 @@ struct Slot {
   hipGraph_t front_graph = nullptr;
   hipGraphExec_t front_exec = nullptr;  // encoder + flow only
   int st_chunk = 0, st_next = -1, st_halo = 0;
-  // batched stream of a full-schedule slot (piper_hip_voice_stream_*_batch): bs_n items (0 = none), the next frame of each, dropped
-  // flags; the per-step descriptor table and the packed chunks live in device buffers of this plan (released with it)
-  int bs_n = 0;
-  std::vector<int> bs_next;
-  std::vector<uint8_t> bs_dropped;
+  // batched stream of a full-schedule slot (piper_hip_voice_stream_*_batch): one StreamRow per item of the group (empty = none), F copied
+  // from h_F at stream_begin_batch; the per-step descriptor table and the packed chunks live in device buffers of this plan (released with it)
+  std::vector<StreamRow> bs_rows;
   int* bs_desc = nullptr;     // [kMaxGroup][kDescInts] device
   float* bs_pack = nullptr;   // the packed chunks of one step, device
   size_t bs_pack_cap = 0;     // floats
@@ -281,9 +286,15 @@ struct Slot {
   std::vector<float> h_peaks; // the same on the host after a normalising collect_pcm16 (empty: none since the last launch)
 };
 
+// No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
+void reset_stream_state(Slot& s) {
+  s.st_next = -1;
+  s.bs_rows.clear();
+}
+
 // Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
 // or stream_drop) while the stream runs. It belongs to the voice per slot id, not to a plan — a pool has no single front plan: every join
-// runs encoder + flow on a work slot's plan and moves the latents into the rows' own stores.
+// runs encoder + flow on a work slot's plan and moves the latents into the rows' own stores. A row is a group's StreamRow plus its store.
 struct PoolRowRef {  // device table entry: where row r's latent [inter][stride] lives
   const float* z;
   int64_t stride;
@@ -293,12 +304,10 @@ struct PoolJoinEnt {  // per-join table entry of stream_adopt_kernel
 };
 struct StreamPool {
   int capacity = 0, NBg = 1, chunk = 0, halo = 0;
-  struct Row {
-    float* z = nullptr;   // [inter][stride] row store (context pool), kept while the pool lives, regrown for a longer utterance
-    size_t cap = 0;       // floats
-    int stride = 0;       // bucket_f(F) of the item in the row
-    int F = 0, next = 0;  // the item's frames, its next frame
-    bool active = false;  // false: free (never taken, finished or dropped)
+  struct Row : StreamRow {  // active = false: the row is free (never taken, finished or dropped)
+    float* z = nullptr;     // [inter][stride] row store (context pool), kept while the pool lives, regrown for a longer utterance
+    size_t cap = 0;         // floats
+    int stride = 0;         // bucket_f(F) of the item in the row
   };
   std::vector<Row> rows;
   PoolRowRef* d_rows = nullptr;   // device: [NBg] row table, then the [capacity] PoolJoinEnt table of the latest join (one upload per join)
@@ -702,8 +711,9 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   if (s.graph) { (void)hipGraphDestroy(s.graph); s.graph = nullptr; }
   if (s.front_exec) { (void)hipGraphExecDestroy(s.front_exec); s.front_exec = nullptr; }
   if (s.front_graph) { (void)hipGraphDestroy(s.front_graph); s.front_graph = nullptr; }
-  s.st_next = -1; s.zin = nullptr; s.z_out = nullptr;
-  s.bs_n = 0; s.bs_desc = nullptr; s.bs_pack = nullptr; s.bs_pack_cap = 0;  // (both buffers are in `owned`)
+  reset_stream_state(s);
+  s.zin = nullptr; s.z_out = nullptr;
+  s.bs_desc = nullptr; s.bs_pack = nullptr; s.bs_pack_cap = 0;  // (both buffers are in `owned`)
   s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();      // (these too)
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   for (void* p : s.owned) (void)v->ctx->pool.release(p);
@@ -2273,8 +2283,7 @@ void detach(piper_hip_voice* v, int slot) {
   if (!p) return;
   if (p->set.stream) (void)hipStreamSynchronize(p->set.stream);  // its last launch may still be running / reading the inputs
   p->in_use = false;
-  p->st_next = -1;
-  p->bs_n = 0;
+  reset_stream_state(*p);
   p->bounded_pending = false;
   v->attached[slot] = nullptr;
   release_dp(v, slot);  // ran on p's stream: idle now
@@ -2393,8 +2402,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     PH_HIP(hipEventRecord(s.ev_in, q), PIPER_HIP_ERR_LAUNCH);
     PH_HIP(hipStreamWaitEvent(dp_plan->set.stream, s.ev_in, 0), PIPER_HIP_ERR_LAUNCH);
   }
-  s.st_next = -1;
-  s.bs_n = 0;
+  reset_stream_state(s);
   s.h_T = hT;
   s.h_F = hF;
   s.h_dur.clear();
@@ -2578,8 +2586,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   if (!rep) PH_FAIL(PIPER_HIP_ERR_UNAVAILABLE, "prepare_batch_bounded: page-locked memory has no device mapping on this system");
   hipLaunchKernelGGL(dp_paths_kernel, dim3(n), dim3(256), 0, q, dp->dp_dur, dp->lensT, T, F, std::min(max_frames, F), s.frame2id, s.lensF, rep, n);
   PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
-  s.st_next = -1;
-  s.bs_n = 0;
+  reset_stream_state(s);
   s.h_T.assign(n, 0);
   for (int b = 0; b < n; b++) s.h_T[b] = utts[b].t;
   s.h_F.assign(n, F);  // capacity until collect has the device's answer
@@ -2596,6 +2603,16 @@ namespace {
 // paths (pcm_route / pcm_land) use the same ones: kernel stores or one DMA into page-locked staging up to kPinnedMax, kChunk pieces with
 // the host copying behind them up to kChunkedMax, the runtime's own pipelined copy beyond.
 constexpr size_t kPinnedMax = (size_t)1 << 20, kChunkedMax = (size_t)16 << 20, kChunk = (size_t)1 << 20;
+// The least size, in floats, of a slot id's page-locked landing buffer of the waveform (sg.h_audio): 16 Ki floats = 64 KiB.
+constexpr size_t kAudioMinCap = (size_t)16 << 10;
+
+// Did the caller page-lock this destination itself (piper_hip_host_alloc)? Then it takes a DMA or kernel stores directly.
+bool is_caller_pinned(const void* host) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, host) == hipSuccess) return at.type == hipMemoryTypeHost;
+  (void)hipGetLastError();
+  return false;
+}
 
 // after the slot's stream has been synchronised: the device's frame counts and durations → h_F / h_dur; an item over the bound is an error
 int bounded_finish(piper_hip_voice* v, int slot, Slot& s) {
@@ -2785,9 +2802,8 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *p;
   auto& sg = v->staging[slot];
-  // The slot id's page-locked landing buffer of the waveform (16 Ki floats = 64 KiB at least). Failing to grow it is not fatal: the waveform
+  // The slot id's page-locked landing buffer of the waveform (kAudioMinCap at least). Failing to grow it is not fatal: the waveform
   // then goes to the caller's buffer directly, and the sticky error of the failed hipHostMalloc is cleared (the next launch would report it).
-  constexpr size_t kAudioMinCap = (size_t)16 << 10;
   if (s.bounded_pending) {
     // lengths still on the device. Short buckets: the waveform rows go to the slot id's page-locked buffer at bucket stride by a kernel that
     // reads each length from device memory — ONE synchronisation for lengths and samples; long ones: synchronise, then the usual copy.
@@ -2836,12 +2852,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     // copies chunk k out while chunk k + 1 is on the wire. Larger ones still go to the runtime (its pipelined staging wins there).
     const size_t bytes = (size_t)total * sizeof(float);
     // a destination the caller page-locked itself (piper_hip_host_alloc) takes the DMA directly
-    bool caller_pinned = false;
-    {
-      hipPointerAttribute_t at;
-      if (hipPointerGetAttributes(&at, host_audio) == hipSuccess) caller_pinned = at.type == hipMemoryTypeHost;
-      else (void)hipGetLastError();
-    }
+    const bool caller_pinned = is_caller_pinned(host_audio);
     if (!caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap)) (void)hipGetLastError();
     float* h_audio = sg.audio_cap >= (size_t)total ? sg.h_audio : nullptr;
     if (!caller_pinned && bytes > kPinnedMax && bytes <= kChunkedMax && h_audio) {
@@ -3006,13 +3017,8 @@ struct PcmRoute {
 
 // `samples` will travel to `host`; a device buffer, if one is needed, belongs to `plan` and holds `dev_samples`
 int pcm_route(piper_hip_voice* v, Slot& plan, piper_hip_voice::Staging& sg, int16_t* host, size_t samples, size_t dev_samples, PcmRoute* r) {
-  constexpr size_t kAudioMinCap = (size_t)16 << 10;
   const size_t bytes = samples * sizeof(int16_t);
-  {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, host) == hipSuccess) r->caller_pinned = at.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();
-  }
+  r->caller_pinned = is_caller_pinned(host);
   if (!r->caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (samples + 1) / 2, kAudioMinCap)) (void)hipGetLastError();
   r->stage = (!r->caller_pinned && sg.h_audio && sg.audio_cap * 2 >= samples) ? (int16_t*)sg.h_audio : nullptr;
   static const bool dma_only = getenv("PIPER_HIP_COLLECT_DMA") != nullptr;
@@ -3086,24 +3092,36 @@ int pcm_params(const piper_hip_pcm_params* p, float* gain, bool* normalize) {
   return PIPER_HIP_OK;
 }
 
+// What one stream step decodes of an utterance of F frames whose next frame is `next`: latent frames [a, a + Fc), of whose audio the first
+// `skip` samples are dropped and the following `n` are the chunk; `end` is the stream's next frame afterwards.
+struct Window {
+  int a = 0, Fc = 0, skip = 0, n = 0, end = 0;
+};
+
+// window = chunk + receptive field, clamped to the utterance: at the utterance's own ends the convs' zero padding is
+// then the same zero padding the whole-utterance run sees, inside it the halo frames are recomputed and dropped
+Window window_of(int F, int next, int chunk, int halo, int hop) {
+  const int f0 = next, f1 = std::min(F, f0 + chunk);
+  const int a = std::max(0, f0 - halo), b = std::min(F, f1 + halo);
+  return Window{a, b - a, (f0 - a) * hop, (f1 - f0) * hop, f1};
+}
+
 // stream_next; pcm: the chunk leaves as int16 (host_pcm, gain) — converted by a kernel behind the window's graph — instead of fp32
 int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm, float gain) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
   Slot* sp = slot_plan(v, slot);
-  if (sp && sp->bs_n > 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a group of %d streams: use stream_next_batch", slot, sp->bs_n);
+  if (sp && sp->bs_rows.size() > 1)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a group of %d streams: use stream_next_batch", slot, (int)sp->bs_rows.size());
   if (!sp || sp->st_next < 0) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no stream in progress", slot);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *sp;
   const int Ftrue = s.h_F[0];
   *n_samples = 0;
   if (s.st_next >= Ftrue) return PIPER_HIP_OK;  // end of stream
-  const int f0 = s.st_next, f1 = std::min(Ftrue, f0 + s.st_chunk);
-  // window = chunk + receptive field, clamped to the utterance: at the utterance's own ends the convs' zero padding is
-  // then the same zero padding the whole-utterance run sees, inside it the halo frames are recomputed and dropped
-  const int a = std::max(0, f0 - s.st_halo), b = std::min(Ftrue, f1 + s.st_halo);
-  const int Fc = b - a;
-  const int64_t want = (int64_t)(f1 - f0) * v->hop;
+  const Window w = window_of(Ftrue, s.st_next, s.st_chunk, s.st_halo, v->hop);
+  const int a = w.a, Fc = w.Fc;
+  const int64_t want = w.n;
   if (want_out && max_samples < want) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next: buffer holds %lld < %lld samples", (long long)max_samples, (long long)want);
   // generator-only plan of the window's bucket (first / interior / last windows of a stream usually share one)
   Slot* gs = nullptr;
@@ -3123,13 +3141,13 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (pcm && want_out) {
     PcmRoute r;
     if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], host_pcm, (size_t)want, (size_t)gs->F * v->hop, &r);
-    if (e == hipSuccess && !rc) e = launch_pcm16_flat(gs->set.stream, gs->audio + (int64_t)(f0 - a) * v->hop, want, gain, r.kdst, v->ctx->num_cus);
+    if (e == hipSuccess && !rc) e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, gain, r.kdst, v->ctx->num_cus);
     if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, host_pcm, (size_t)want);
     if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)want * sizeof(int16_t));
     if (e != hipSuccess || rc) (void)hipStreamSynchronize(gs->set.stream);  // nothing of the window may still run when its plan goes idle
   } else {
     if (e == hipSuccess && host_audio)
-      e = hipMemcpyAsync(host_audio, gs->audio + (int64_t)(f0 - a) * v->hop, (size_t)want * sizeof(float), hipMemcpyDeviceToHost, gs->set.stream);
+      e = hipMemcpyAsync(host_audio, gs->audio + w.skip, (size_t)want * sizeof(float), hipMemcpyDeviceToHost, gs->set.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(gs->set.stream);
   }
   gs->in_use = false;
@@ -3137,7 +3155,7 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next: %s", hipGetErrorString(e));
   if (rc) return rc;
   *n_samples = want;
-  s.st_next = f1;
+  s.st_next = w.end;
   return PIPER_HIP_OK;
 }
 }  // namespace
@@ -3150,6 +3168,20 @@ PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* h
 namespace {
 
 constexpr int kMaxGroup = 256;
+
+// The generator's batch of a batched stream of n rows: n rounded up to a power of two, fixed for the life of the group or pool.
+int group_batch(int n) {
+  int NBg = 1;
+  while (NBg < n) NBg <<= 1;
+  return NBg;
+}
+
+// The limits of a step of n rows of chunk_frames each, reported in the name of the entry point `who`.
+int check_step_size(const piper_hip_voice* v, const char* who, int n, int chunk_frames) {
+  if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: chunk_frames must be >= 1", who);
+  if ((int64_t)chunk_frames * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "%s: %d × %d frames per step too many", who, n, chunk_frames);
+  return PIPER_HIP_OK;
+}
 // The per-step descriptor (kDescSrc … kDescInts: pcm16.h, shared with the int16 pack kernel): one row of kDescInts per generator row — source
 // item, window start a, window length Fc (0: finished, dropped or pad row), halo skip (f0 − a)·hop, samples of the chunk, offset of the
 // chunk in the packed output.
@@ -3157,8 +3189,11 @@ constexpr int kMaxGroup = 256;
 // z windows of one step → the generator plan's input: row r of zin [NBg][I][Fg] = z[src][:, a .. a + Fc), zero past Fc; lensF[r] = Fc.
 // One thread per 4 frames of one channel, so the loads run along frames (coalesced); float4 loads where the window start is 16-byte
 // aligned (z rows are bucket rows, F % 16 == 0). A row of length 0 writes only its length.
-__global__ __launch_bounds__(256) void stream_window_gather_kernel(const float* __restrict__ z, int F, const int* __restrict__ desc,
-                                                                  float* __restrict__ zin, int* __restrict__ lensF, int I, int Fg) {
+// The latent of source item src is z + src·I·Fz, rows of Fz floats (a group: the front plan's z), or, where `rows` is given, the row store
+// rows[src] (a pool: base pointer and row stride from the table). The choice is the same for every thread of the launch.
+__global__ __launch_bounds__(256) void stream_window_gather_kernel(const float* __restrict__ z, int Fz, const PoolRowRef* __restrict__ rows,
+                                                                  const int* __restrict__ desc, float* __restrict__ zin,
+                                                                  int* __restrict__ lensF, int I, int Fg) {
   const int r = blockIdx.y;
   const int* d = desc + r * kDescInts;
   const int src = d[kDescSrc], a = d[kDescA], Fc = d[kDescFc];
@@ -3166,7 +3201,15 @@ __global__ __launch_bounds__(256) void stream_window_gather_kernel(const float* 
   if (Fc == 0) return;
   const int q4 = Fg >> 2;  // Fg % 16 == 0
   const int total = I * q4;
-  const float* zr = z + (int64_t)src * I * F + a;
+  int64_t F;
+  const float* zr;
+  if (rows) {
+    F = rows[src].stride;
+    zr = rows[src].z + a;
+  } else {
+    F = Fz;
+    zr = z + (int64_t)src * I * Fz + a;
+  }
   float* out = zin + (int64_t)r * I * Fg;
   const bool vec = (a & 3) == 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
@@ -3253,40 +3296,6 @@ __global__ __launch_bounds__(256) void stream_adopt_kernel(const float* __restri
   }
 }
 
-// stream_window_gather_kernel for a pool: the latent of descriptor row r's source is the row store rows[src] (base pointer and row
-// stride from the table) instead of z + src·I·F. Everything else — zero past Fc, lensF from the descriptor — is the group kernel's.
-__global__ __launch_bounds__(256) void stream_pool_gather_kernel(const PoolRowRef* __restrict__ rows, const int* __restrict__ desc,
-                                                                float* __restrict__ zin, int* __restrict__ lensF, int I, int Fg) {
-  const int r = blockIdx.y;
-  const int* d = desc + r * kDescInts;
-  const int src = d[kDescSrc], a = d[kDescA], Fc = d[kDescFc];
-  if (blockIdx.x == 0 && threadIdx.x == 0) lensF[r] = Fc;
-  if (Fc == 0) return;
-  const int q4 = Fg >> 2;  // Fg % 16 == 0
-  const int total = I * q4;
-  const int64_t F = rows[src].stride;
-  const float* zr = rows[src].z + a;
-  float* out = zin + (int64_t)r * I * Fg;
-  const bool vec = (a & 3) == 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int c = i / q4, j = (i - c * q4) * 4;
-    const float* zp = zr + (int64_t)c * F + j;
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (j < Fc) {
-      if (vec) {  // a + j is a multiple of 4 below the row stride (a multiple of 16): all four lie in the row
-        const float4 t = *(const float4*)zp;
-        v.x = t.x; v.y = j + 1 < Fc ? t.y : 0.0f; v.z = j + 2 < Fc ? t.z : 0.0f; v.w = j + 3 < Fc ? t.w : 0.0f;
-      } else {
-        v.x = zp[0];
-        if (j + 1 < Fc) v.y = zp[1];
-        if (j + 2 < Fc) v.z = zp[2];
-        if (j + 3 < Fc) v.w = zp[3];
-      }
-    }
-    *(float4*)(out + (int64_t)c * Fg + j) = v;
-  }
-}
-
 int pool_free_rows(const StreamPool& P) {
   int k = 0;
   for (const auto& r : P.rows) k += r.active ? 0 : 1;
@@ -3304,47 +3313,64 @@ int pool_event(StreamPool& P, hipEvent_t* out) {
   return PIPER_HIP_OK;
 }
 
-// stream_next_batch on a pool slot: the next chunk of every active row in one generator launch at the pool's fixed batch.
+// A batched stream as one step sees it: a group's (batch_step) or a pool's (pool_step).
+template <class Row>  // StreamRow, or a record that extends it
+struct StepView {
+  Row* rows;                 // [n] host records
+  int n, NBg;                // items, and the generator's batch (group_batch(n), fixed for the life of the stream)
+  int chunk, halo;           // frames
+  int* d_desc;               // device: [NBg][kDescInts] descriptor of the step (one upload per step)
+  float* pack;               // device: the packed chunks of one step
+  size_t pack_cap;           // floats
+  const float* z;            // the latents as stream_window_gather_kernel takes them: z [n][I][Fz] …
+  int Fz;
+  const PoolRowRef* d_rows;  // … or the device row table
+  const hipEvent_t* wait;    // "the latents are there": what the step's stream waits for (the GPU waits, the host does not)
+  size_t n_wait;
+};
+
+// stream_next_batch: the next chunk of every active row in one generator launch at the stream's fixed batch; *ran = a step ran and has
+// been waited for (false: no active row, nothing was launched).
 // pcm: the chunks leave as int16 (host_pcm, gain) instead of fp32 (host_audio) — the int16 sibling of the pack kernel writes them into the
 // same device and staging buffers, half filled, and half the bytes cross the bus.
-int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm = false,
-              int16_t* host_pcm = nullptr, float gain = 1.0f) {
+template <class Row>
+int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm,
+                 int16_t* host_pcm, float gain, bool* ran) {
+  *ran = false;
   const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
   const size_t sample_bytes = pcm ? sizeof(int16_t) : sizeof(float);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  const int n = P.capacity, NBg = P.NBg, hop = v->hop;
+  const int n = s.n, NBg = s.NBg, hop = v->hop;
   auto& sg = v->staging[slot];
   int rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * kDescInts);
   if (rc) return rc;
   // the descriptor of this step (the previous step's upload has completed: every step ends with a wait)
   int* d = sg.h_desc;
-  std::vector<int64_t> got(n, 0);
+  std::vector<Window> win(n);
   int64_t total = 0;
   int Fmax = 0;
   for (int r = 0; r < NBg; r++) {
     int* e = d + (size_t)r * kDescInts;
     for (int k = 0; k < kDescInts; k++) e[k] = 0;
     e[kDescSrc] = r < n ? r : 0;
-    if (r >= n || !P.rows[r].active) continue;
-    // the window of stream_next: chunk + receptive field, clamped to the utterance
-    const int Ft = P.rows[r].F, f0 = P.rows[r].next, f1 = std::min(Ft, f0 + P.chunk);
-    const int a = std::max(0, f0 - P.halo), b = std::min(Ft, f1 + P.halo);
-    e[kDescA] = a;
-    e[kDescFc] = b - a;
-    e[kDescSkip] = (f0 - a) * hop;
-    e[kDescN] = (f1 - f0) * hop;
+    if (r >= n || !s.rows[r].active) continue;
+    const Window w = win[r] = window_of(s.rows[r].F, s.rows[r].next, s.chunk, s.halo, hop);
+    e[kDescA] = w.a;
+    e[kDescFc] = w.Fc;
+    e[kDescSkip] = w.skip;
+    e[kDescN] = w.n;
     e[kDescOff] = (int)total;
-    got[r] = e[kDescN];
-    total += e[kDescN];
-    Fmax = std::max(Fmax, b - a);
+    total += w.n;
+    Fmax = std::max(Fmax, w.Fc);
   }
   for (int i = 0; i < n; i++) n_samples[i] = 0;
-  if (total == 0) return PIPER_HIP_OK;  // idle: no active row (joins since the last step stay pending)
+  if (total == 0) return PIPER_HIP_OK;  // end of the group / an idle pool
   if (want_out && max_samples < total)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
-  constexpr size_t kAudioMinCap = (size_t)16 << 10;
+  if ((size_t)total > s.pack_cap) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.pack_cap);
   if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
-  // generator-only plan of the step's longest window at the pool's batch size: the plans a group of the same size uses
+  // generator-only plan of the step's longest window at the stream's batch size (rows past their end have length 0): a pool and a group
+  // of the same size use the same plans
   Slot* gs = nullptr;
   bool built = false;
   if ((rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
@@ -3353,40 +3379,51 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, in
   const hipStream_t q = gs->set.stream;
   const int I = v->cfg.inter, Fg = gs->F;
   hipError_t e = hipSuccess;
-  for (hipEvent_t ev : P.ev_pending)  // the latents of every join since the last step: the GPU waits, the host does not
-    if (e == hipSuccess) e = hipStreamWaitEvent(q, ev, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(P.d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
+  for (size_t k = 0; k < s.n_wait; k++)
+    if (e == hipSuccess) e = hipStreamWaitEvent(q, s.wait[k], 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(s.d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
   if (e == hipSuccess) {
     const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (Fg / 4), 256), 64);
-    hipLaunchKernelGGL(stream_pool_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, P.d_rows, P.d_desc, gs->zin, gs->lensF, I, Fg);
+    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, s.z, s.Fz, s.d_rows, s.d_desc, gs->zin, gs->lensF, I, Fg);
     e = hipGetLastError();
   }
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (e == hipSuccess) {
-    const int px = (int)std::min<int64_t>(ceil_div((int64_t)P.chunk * hop, 1024), 64);
+    const int px = (int)std::min<int64_t>(ceil_div((int64_t)s.chunk * hop, 1024), 64);
     if (pcm) {
-      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, P.d_desc, gain, (int16_t*)P.pack);
+      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, s.d_desc, gain, (int16_t*)s.pack);
     } else {
-      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, P.d_desc, P.pack);
+      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.d_desc, s.pack);
       e = hipGetLastError();
     }
   }
-  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, P.pack, (size_t)total * sample_bytes, hipMemcpyDeviceToHost, q);
+  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, s.pack, (size_t)total * sample_bytes, hipMemcpyDeviceToHost, q);
   if (e == hipSuccess) e = stream_wait(q);
   gs->in_use = false;
   evict_idle_plans(v);
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
-  // the wait above covers the adopts q waited for: their events can be recorded again
-  P.ev_free.insert(P.ev_free.end(), P.ev_pending.begin(), P.ev_pending.end());
-  P.ev_pending.clear();
+  *ran = true;
   if (want_out) memcpy(pcm ? (void*)host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
   for (int i = 0; i < n; i++) {
-    n_samples[i] = got[i];
-    if (!got[i]) continue;
-    auto& r = P.rows[i];
-    r.next = std::min(r.F, r.next + P.chunk);
-    if (r.next >= r.F) r.active = false;  // last chunk delivered: the row is free for the next join
+    n_samples[i] = win[i].n;
+    if (!win[i].n) continue;
+    s.rows[i].next = win[i].end;
+    if (win[i].end >= s.rows[i].F) s.rows[i].active = false;  // last chunk delivered (a pool: the row is free for the next join)
   }
+  return PIPER_HIP_OK;
+}
+
+// stream_next_batch on a pool slot: the latents are the row stores, ready when the adopts of the joins since the last step have run
+int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm,
+              float gain) {
+  const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, (size_t)P.capacity * P.chunk * v->hop,
+                                       nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size()};
+  bool ran = false;
+  const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, &ran);
+  if (rc || !ran) return rc;  // (an idle pool: joins since the last step stay pending)
+  // the step's wait covers the adopts its stream waited for: their events can be recorded again
+  P.ev_free.insert(P.ev_free.end(), P.ev_pending.begin(), P.ev_pending.end());
+  P.ev_pending.clear();
   return PIPER_HIP_OK;
 }
 
@@ -3395,8 +3432,7 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, in
 PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames) {
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: group of %d outside [1,%d]", n, kMaxGroup);
-  if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin_batch: chunk_frames must be >= 1");
-  if ((int64_t)chunk_frames * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: %d × %d frames per step too many", n, chunk_frames);
+  if (int rc = check_step_size(v, "stream_begin_batch", n, chunk_frames)) return rc;
   int rc = piper_hip_voice_prepare_batch(v, utts, n, slot);  // encoder (+ predictor) inputs of the whole group on one plan
   if (rc < 0) return rc;
   Slot& s = *v->attached[slot];
@@ -3417,96 +3453,26 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
   if ((rc = launch_front(s))) return rc;
   s.st_chunk = chunk_frames;
   s.st_halo = generator_halo_frames(v->cfg);
-  s.bs_n = n;
-  s.bs_next.assign(n, 0);
-  s.bs_dropped.assign(n, 0);
+  s.bs_rows.resize(n);
+  for (int b = 0; b < n; b++) s.bs_rows[b] = StreamRow{s.h_F[b], 0, s.h_F[b] > 0};
   int steps = 0;
   for (int b = 0; b < n; b++) steps = std::max(steps, (int)ceil_div(s.h_F[b], chunk_frames));
   return steps;
 }
 
 namespace {
-// stream_next_batch; pcm / host_pcm / gain as for pool_step
+// stream_next_batch; pcm / host_pcm / gain as for batched_step. A group's latents are the front plan's z, ready when its ev1 fires.
 int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm, float gain) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples, pcm, host_pcm, gain);
-  const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
-  const size_t sample_bytes = pcm ? sizeof(int16_t) : sizeof(float);
   Slot* sp = slot_plan(v, slot);
-  if (!sp || sp->bs_n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
-  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  if (!sp || sp->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   Slot& s = *sp;
-  const int n = s.bs_n, hop = v->hop;
-  int NBg = 1;  // the generator's batch: n rounded up to a power of two, fixed for the life of the group
-  while (NBg < n) NBg <<= 1;
-  auto& sg = v->staging[slot];
-  int rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * kDescInts);
-  if (rc) return rc;
-  // the descriptor of this step (the previous step's upload has completed: every step ends with a wait)
-  int* d = sg.h_desc;
-  std::vector<int64_t> got(n, 0);
-  int64_t total = 0;
-  int Fmax = 0;
-  for (int r = 0; r < NBg; r++) {
-    int* e = d + (size_t)r * kDescInts;
-    for (int k = 0; k < kDescInts; k++) e[k] = 0;
-    e[kDescSrc] = r < n ? r : 0;
-    if (r >= n || s.bs_dropped[r] || s.bs_next[r] >= s.h_F[r]) continue;
-    // the window of stream_next: chunk + receptive field, clamped to the utterance
-    const int Ft = s.h_F[r], f0 = s.bs_next[r], f1 = std::min(Ft, f0 + s.st_chunk);
-    const int a = std::max(0, f0 - s.st_halo), b = std::min(Ft, f1 + s.st_halo);
-    e[kDescA] = a;
-    e[kDescFc] = b - a;
-    e[kDescSkip] = (f0 - a) * hop;
-    e[kDescN] = (f1 - f0) * hop;
-    e[kDescOff] = (int)total;
-    got[r] = e[kDescN];
-    total += e[kDescN];
-    Fmax = std::max(Fmax, b - a);
-  }
-  for (int i = 0; i < n; i++) n_samples[i] = 0;
-  if (total == 0) return PIPER_HIP_OK;  // end of the group
-  if (want_out && max_samples < total)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
-  if ((size_t)total > s.bs_pack_cap) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.bs_pack_cap);
-  constexpr size_t kAudioMinCap = (size_t)16 << 10;
-  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
-  // generator-only plan of the step's longest window at the group's batch size (rows past their end have length 0)
-  Slot* gs = nullptr;
-  bool built = false;
-  if ((rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
-  gs->in_use = true;
-  gs->last_use = ++v->use_clock;
-  const hipStream_t q = gs->set.stream;
-  const int I = v->cfg.inter, Fg = gs->F;
-  hipError_t e = hipStreamWaitEvent(q, s.set.ev1, 0);  // z of the group
-  if (e == hipSuccess) e = hipMemcpyAsync(s.bs_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
-  if (e == hipSuccess) {
-    const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (Fg / 4), 256), 64);
-    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, s.z_out, s.F, s.bs_desc, gs->zin, gs->lensF, I, Fg);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
-  if (e == hipSuccess) {
-    const int px = (int)std::min<int64_t>(ceil_div((int64_t)s.st_chunk * hop, 1024), 64);
-    if (pcm) {
-      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, s.bs_desc, gain, (int16_t*)s.bs_pack);
-    } else {
-      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.bs_desc, s.bs_pack);
-      e = hipGetLastError();
-    }
-  }
-  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, s.bs_pack, (size_t)total * sample_bytes, hipMemcpyDeviceToHost, q);
-  if (e == hipSuccess) e = stream_wait(q);
-  gs->in_use = false;
-  evict_idle_plans(v);
-  if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
-  if (want_out) memcpy(pcm ? (void*)host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
-  for (int i = 0; i < n; i++) {
-    n_samples[i] = got[i];
-    if (got[i]) s.bs_next[i] = std::min(s.h_F[i], s.bs_next[i] + s.st_chunk);
-  }
-  return PIPER_HIP_OK;
+  const int n = (int)s.bs_rows.size();
+  const StepView<StreamRow> view{s.bs_rows.data(), n, group_batch(n), s.st_chunk, s.st_halo, s.bs_desc, s.bs_pack, s.bs_pack_cap,
+                                 s.z_out, s.F, nullptr, &s.set.ev1, 1};
+  bool ran = false;
+  return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, &ran);
 }
 }  // namespace
 
@@ -3522,9 +3488,10 @@ PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item
     return PIPER_HIP_OK;
   }
   Slot* sp = slot_plan(v, slot);
-  if (!sp || sp->bs_n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
-  if (item < 0 || item >= sp->bs_n) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, sp->bs_n);
-  sp->bs_dropped[item] = 1;
+  if (!sp || sp->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
+  const int n = (int)sp->bs_rows.size();
+  if (item < 0 || item >= n) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, n);
+  sp->bs_rows[item].active = false;
   return PIPER_HIP_OK;
 }
 
@@ -3532,15 +3499,13 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
   if (capacity < 1 || capacity > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_open: capacity %d outside [1,%d]", capacity, kMaxGroup);
-  if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_open: chunk_frames must be >= 1");
-  if ((int64_t)chunk_frames * v->hop * capacity > 0x3fffffff)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_open: %d × %d frames per step too many", capacity, chunk_frames);
+  if (int rc = check_step_size(v, "stream_pool_open", capacity, chunk_frames)) return rc;
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   pool_close(v, slot);
   detach(v, slot);  // what the slot id held is replaced, as by a prepare
   std::unique_ptr<StreamPool> P(new StreamPool());
   P->capacity = capacity;
-  while (P->NBg < capacity) P->NBg <<= 1;  // the generator's batch, fixed for the life of the pool (the rule of a group)
+  P->NBg = group_batch(capacity);
   P->chunk = chunk_frames;
   P->halo = generator_halo_frames(v->cfg);
   P->rows.resize(capacity);

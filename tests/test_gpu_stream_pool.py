@@ -233,6 +233,36 @@ def test_plans_and_determinism(rt_medium, utts):
     assert rt.plan_info(13)["cached_plans"] <= plans + 1
 
 
+@pytest.mark.parametrize("pcm", [False, True], ids=["fp32", "pcm16_gain_0.5"])
+def test_group_and_pool_steps_are_bit_equal(rt_medium, utts, pcm):
+    """C, A, E (F = 30, 84, 336: ragged, none a multiple of 32, C shorter than one chunk, E longer than three) at chunk 32 as a group of 3
+    and joined at once into an empty pool of capacity 3 — generator batch 4, one pad row. A group and a pool run the same step on the same
+    generator plans with equal inputs: the same number of steps, and every step's n_samples and packed chunks equal bit for bit."""
+    rt = rt_medium
+    items = [utts[name] for name in "CAE"]
+    Fs = [frames(utts, name) for name in "CAE"]
+    halo = rt.lib.piper_hip_voice_receptive_field(rt.voice)
+    assert len(set(Fs)) == 3 and any(F % 32 for F in Fs) and min(Fs) < 32 + halo and max(Fs) > 3 * 32
+    kw = {"pcm": True, "gain": 0.5} if pcm else {}
+    group = [(tuple(c.size for c in chunks), np.concatenate(chunks))
+             for chunks in rt.synthesize_stream_batch(items, 0.667, chunkFrames=32, slot=8, **kw)]
+    pool = rt.stream_pool(10, 3, chunkFrames=32, work_slot=11)
+    assert [item for item, _ in pool.join(items, 0.667)] == [0, 1, 2]
+    pooled = []
+    while True:
+        out = pool.step(**kw)
+        if not out:
+            break
+        pooled.append((tuple(out[i].size if i in out else 0 for i in range(3)), np.concatenate([out[i] for i in sorted(out)])))
+    pool.close()
+    assert len(group) == len(pooled) == -(-max(Fs) // 32)
+    for k, ((n_g, x_g), (n_p, x_p)) in enumerate(zip(group, pooled)):
+        assert n_g == n_p, (k, n_g, n_p)
+        assert x_g.dtype == x_p.dtype == (np.int16 if pcm else np.float32)
+        assert np.array_equal(x_g, x_p), f"step {k}: group and pool differ in {int(np.count_nonzero(x_g != x_p))} of {x_g.size} samples"
+    assert sum(sum(n) for n, _ in group) == sum(Fs) * rt.cfg.hop
+
+
 def test_high_voice_fp32_and_bf16(backend, voices):
     cfg, blob = voices["high"]
     rt = ph.HipRuntime(backend, cfg, blob)
