@@ -12,6 +12,8 @@
  *                            well), converted on the device (piper_hip_voice_synthesize_pcm16; after --output, collect_pcm16 on the
  *                            slot that ran): --volume V scales it (linear, default 1),
  *                            --normalize applies Piper's peak normalisation (audio_float_to_int16). Both flags act on --output-raw only.
+ *                            --output-rate N (8000 … 48000) resamples on the device (piper_hip_voice_collect_pcm16_rate): --output-raw is
+ *                            then s16le at N Hz, and --output a WAV whose header carries N (piper_hip_wav_write_pcm16).
  * Without --model the synthetic voice of the tests is used (--quality medium|high|low|x_low; low and x_low are the 16 kHz tier); its duration predictor has random weights, so frames per id are
  * pinned to --pin-frames (3, the bench's convention) unless --predict asks for the predictor (the only mode a real voice has).
  *
@@ -114,7 +116,8 @@ static int run_one(runner* r, const int64_t* ids, int t, int64_t* samples) {
  * ran != 0: run_one has just run this utterance on slot 0 and its waveform is still in the plan, so piper_hip_voice_collect_pcm16 converts
  * that. Otherwise pinned durations go through piper_hip_voice_synthesize_pcm16 in one call; with --predict the length is the predictor's,
  * so the slot is prepared (once), asked for it, launched and collected as PCM. */
-static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_pcm_params* prm, int ran, int16_t** pcm, int64_t* samples) {
+static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_pcm_params* prm, int ran, int in_rate, int rate, int16_t** pcm,
+                         int64_t* samples) {
   piper_hip_utterance u;
   memset(&u, 0, sizeof u);
   u.phoneme_ids = ids; u.t = t; u.noise_scale = r->noise_scale; u.seed = 1234;
@@ -127,17 +130,19 @@ static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_p
     for (int i = 0; i < t; i++) dur[i] = r->pin_frames;
     u.durations = dur;
     cap = piper_hip_voice_num_samples(r->voice, &u);
+    if (cap >= 0 && rate != in_rate) cap = piper_hip_resample_count(in_rate, rate, cap);
     rc = cap < 0 ? (int)cap : 0;
     if (!rc) *pcm = (int16_t*)malloc(sizeof(int16_t) * (size_t)(cap > 0 ? cap : 1));
-    if (!rc) rc = piper_hip_voice_synthesize_pcm16(r->voice, &u, prm, *pcm, cap, samples);
+    if (!rc) rc = piper_hip_voice_synthesize_pcm16_rate(r->voice, &u, prm, rate, *pcm, cap, samples);
     free(dur);
     return rc;
   }
   if (!ran && (rc = piper_hip_voice_prepare(r->voice, &u, 0)) < 0) return rc;
   if ((rc = piper_hip_voice_prepared_samples(r->voice, 0, NULL, 0, &cap)) < 0) return rc;
+  if (rate != in_rate && (cap = piper_hip_resample_count(in_rate, rate, cap)) < 0) return (int)cap;
   *pcm = (int16_t*)malloc(sizeof(int16_t) * (size_t)(cap > 0 ? cap : 1));
   if (!ran && (rc = piper_hip_voice_launch(r->voice, 0)) < 0) return rc;
-  if ((rc = piper_hip_voice_collect_pcm16(r->voice, 0, prm, *pcm, cap)) < 0) return rc;
+  if ((rc = piper_hip_voice_collect_pcm16_rate(r->voice, 0, prm, rate, *pcm, cap)) < 0) return rc;
   *samples = cap;
   return 0;
 }
@@ -157,7 +162,7 @@ int main(int argc, char** argv) {
   const char* ids_arg = arg_value(argc, argv, "--phoneme-ids");
   if (!scale_bench && !ids_arg) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
-                    "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize]\n"
+                    "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n", argv[0], argv[0]);
     return 2;
   }
@@ -215,11 +220,19 @@ int main(int argc, char** argv) {
     if (t < 1 || (!out && !out_raw)) { fprintf(stderr, "--phoneme-ids needs a comma-separated list and --output or --output-raw a path\n"); return 2; }
     int64_t n = 0;
     double gpu = 0.0;
+    const int rate = arg_value(argc, argv, "--output-rate") ? atoi(arg_value(argc, argv, "--output-rate")) : cfg.sample_rate;
     if (out) {
       CHECK(run_one(&r, ids, t, &n));
       CHECK(piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu));
-      CHECK(piper_hip_wav_write(out, r.audio, (size_t)n, cfg.sample_rate));
-      fprintf(stderr, "%lld samples (%.3f s at %d Hz), %.3f ms on the GPU -> %s\n", (long long)n, (double)n / cfg.sample_rate, cfg.sample_rate, gpu, out);
+      if (rate == cfg.sample_rate) {
+        CHECK(piper_hip_wav_write(out, r.audio, (size_t)n, cfg.sample_rate));
+      } else { /* the slot that ran, resampled and converted on the device */
+        int16_t* wpcm = NULL;
+        CHECK(run_one_pcm16(&r, ids, t, NULL, 1, cfg.sample_rate, rate, &wpcm, &n));
+        CHECK(piper_hip_wav_write_pcm16(out, wpcm, (size_t)n, rate));
+        free(wpcm);
+      }
+      fprintf(stderr, "%lld samples (%.3f s at %d Hz), %.3f ms on the GPU -> %s\n", (long long)n, (double)n / rate, rate, gpu, out);
     }
     if (out_raw) { /* s16le, the samples converted on the device */
       piper_hip_pcm_params prm;
@@ -227,7 +240,7 @@ int main(int argc, char** argv) {
       prm.normalize = has_flag(argc, argv, "--normalize");
       int16_t* pcm = NULL;
       int failed = 0;
-      const int prc = run_one_pcm16(&r, ids, t, &prm, out != NULL, &pcm, &n);
+      const int prc = run_one_pcm16(&r, ids, t, &prm, out != NULL, cfg.sample_rate, rate, &pcm, &n);
       if (prc < 0) {
         fprintf(stderr, "--output-raw failed (%d): %s\n", prc, piper_hip_last_error());
         failed = 1;
@@ -237,7 +250,7 @@ int main(int argc, char** argv) {
         failed = !fr || fwrite(pcm, sizeof(int16_t), (size_t)n, fr) != (size_t)n;
         if (fr && fclose(fr) != 0) failed = 1;
         if (failed) fprintf(stderr, "cannot write %s\n", out_raw);
-        else fprintf(stderr, "%lld samples (%.3f s at %d Hz) as s16le, %.3f ms on the GPU -> %s\n", (long long)n, (double)n / cfg.sample_rate, cfg.sample_rate, gpu, out_raw);
+        else fprintf(stderr, "%lld samples (%.3f s at %d Hz) as s16le, %.3f ms on the GPU -> %s\n", (long long)n, (double)n / rate, rate, gpu, out_raw);
       }
       free(pcm);
       if (failed) { /* leave as the success path does */

@@ -551,6 +551,61 @@ int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int slot, const 
 /* After a collect_pcm16 with normalize = 1: max |x| of each item of the slot (PIPER_HIP_ERR_ARG before one). */
 int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* peaks, int max_items);
 
+/* ---- Output rate: 8–48 kHz PCM from the device (DESIGN.md §4 "Output rate") ----
+ * A voice synthesises at its own rate (22 050 Hz; low and x_low 16 000 Hz). These entry points convert to the consumer's rate on the device,
+ * fused into the 16-bit PCM conversion, behind the plan's graph on the slot's stream. The conversion is a contract, bit for bit:
+ *   ratio     g = gcd(in, out), L = out / g, M = in / g. Output sample j sits at input position j·M / L.
+ *   filter    Kaiser-windowed sinc designed in double, once per (in, out): P = 2·ceil(24·max(L, M) / L) taps per phase (integer arithmetic),
+ *             cutoff fc = 0.93·min(1, L / M); tap time tau(p, t) = t − (P/2 − 1) − p / L for phase p in [0, L), tap t in [0, P);
+ *             h = fc·sinc(fc·tau), sinc(x) = sin(pi x) / (pi x); w = I0(9·sqrt(1 − (tau / (P/2))^2)) / I0(9) for |tau| < P/2, else 0;
+ *             c[p][t] = h·w, every phase divided by its own sum in double (unit DC gain), rounded once to fp32. The table is [L][P] floats.
+ *   sample    u = j·M in 64-bit integers, n = u div L, p = u mod L:  y[j] = sum over t = 0 … P−1 of c[p][t] · x[n − (P/2 − 1) + t],
+ *             x reading as 0 outside [0, N); accumulated in fp32 in ascending t from 0.0f, each product rounded, then each sum (no FMA).
+ *             An item of N samples yields J(N) = ceil(N·L / M) samples.
+ *   to int16  y goes through exactly the contract of piper_hip_pcm_params above. With normalize = 1 the peak is that of the fp32 waveform
+ *             at the voice's rate, so piper_hip_voice_peaks means the same at every rate; an overshoot of the resampled signal is clamped.
+ *   rates     output 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000, and L ≤ 640, P ≤ 256 (every pair from 16 000 and 22 050:
+ *             P ≤ 134, table ≤ 121 KB); anything else is PIPER_HIP_ERR_UNSUPPORTED. out == in is not a filter: the call behaves bit for
+ *             bit as the un-resampled one.
+ * Streams are exact across chunk boundaries: a step whose chunk covers input samples [s, e) of N emits outputs [j0, j1), j0 where the
+ * previous step ended (0 at the start), j1 = J(N) on the item's last step (e == N), else max(j0, ceil((e − P/2)·L / M)) — every output
+ * whose taps end before e; the up to P − 1 samples before s come from a per-row history on the device. The concatenation of a row's
+ * steps equals the whole-item conversion of the same fp32 samples bit for bit. A step delivers at most
+ * ceil((e − s)·L / M) + ceil((P/2)·L / M) + 1 samples per row (piper_hip_resample_step_bound). */
+/* Host-only (no device needed): L, M and taps per phase of a pair (each pointer may be NULL); the [L][P] table the kernels use;
+ * J(n_in); the per-row step bound. The two counts return a negative status on a bad pair or a negative n_in. */
+int piper_hip_resample_info(int32_t in_rate, int32_t out_rate, int32_t* L, int32_t* M, int32_t* taps);
+int piper_hip_resample_taps(int32_t in_rate, int32_t out_rate, float* table, size_t max_floats);
+int64_t piper_hip_resample_count(int32_t in_rate, int32_t out_rate, int64_t n_in);
+int64_t piper_hip_resample_step_bound(int32_t in_rate, int32_t out_rate, int64_t n_in);
+/* piper_hip_wav_write for samples that are 16-bit PCM already, at whatever rate they were delivered. */
+int piper_hip_wav_write_pcm16(const char* path, const int16_t* pcm, size_t n, int32_t sample_rate);
+/* Per-op: `count` device floats → J(count) device samples, the fp32 y (resample_f32) or int16 of y·gain (normalize == 0 arithmetic).
+ * `*out` convention of the other ops; *out_count (may be NULL) receives J(count). */
+int piper_hip_resample_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t in_rate, int32_t out_rate, float** out,
+                           size_t* out_count, piper_hip_stream stream);
+int piper_hip_resample_pcm16_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t in_rate, int32_t out_rate, float gain,
+                                 int16_t** out, size_t* out_count, piper_hip_stream stream);
+/* collect_pcm16 at out_rate: the same rules on plain, ragged and bounded slots, the items back to back at J(true length). The fp32 audio
+ * stays in the plan, so it may follow or precede collect / collect_pcm16 in any order. On a bounded slot max_samples must cover J of the
+ * capacity per item. */
+int piper_hip_voice_collect_pcm16_rate(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int32_t out_rate, int16_t* host_pcm,
+                                       int64_t max_samples);
+/* prepare + launch + collect_pcm16_rate on slot 0; *n_samples = J(samples of the utterance). */
+int piper_hip_voice_synthesize_pcm16_rate(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params,
+                                          int32_t out_rate, int16_t* host_pcm, int64_t max_samples, int64_t* n_samples);
+/* The output rate of the stream on `slot`: allowed after stream_begin, stream_begin_batch or stream_pool_open and before the slot's first
+ * step (a pool: also before its first join); later it is PIPER_HIP_ERR_ARG. From then on stream_next_pcm16 / stream_next_batch_pcm16 on
+ * that slot deliver at out_rate: n_samples[i] are output samples (all zero still means end / idle), stream_pool_join's samples_out reports
+ * J(N_i), and the float steps stream_next / stream_next_batch return PIPER_HIP_ERR_ARG and consume nothing. A max_samples too small is
+ * PIPER_HIP_ERR_SHAPE and consumes nothing; normalize = 1 stays PIPER_HIP_ERR_UNSUPPORTED on steps; a step at a rate needs a buffer
+ * (host_pcm == NULL is PIPER_HIP_ERR_ARG on single streams, groups and pools alike, and consumes nothing). A new begin / open resets the
+ * slot to the voice's own rate. stream_rate reports the current rate (or a negative status). */
+int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int32_t out_rate);
+int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot);
+/* The int16 samples one step of that slot can deliver at its current rate (rows × the per-row bound), or a negative status. */
+int64_t piper_hip_voice_stream_step_capacity(piper_hip_voice* v, int slot);
+
 /* Debug taps ⇔ GraphExecutor.execute(maxNodeIndex:) returning intermediates (GraphExecutor.swift:75-152):
  * copy a named intermediate of the slot's last run to host. Names: "enc_out" [H,T], "m_p" [inter,T],
  * "logs_p" [inter,T], "z_p" [inter,F], "z" [inter,F], "dec_pre" [up_initial,F] — per batch item, compacted to the item's

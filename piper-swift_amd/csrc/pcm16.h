@@ -9,6 +9,32 @@ namespace ph {
 // samples of the chunk, offset of the chunk in the packed output (in samples, whatever the sample type).
 enum { kDescSrc = 0, kDescA, kDescFc, kDescSkip, kDescN, kDescOff, kDescInts };
 
+// The conversion of one sample (pcm16.hip tells the contract), shared with the resampling kernels (resample.hip): norm == 0 is the reference
+// mode on x·gain, norm == 1 the peak mode with `scale` = fp32(32767 / max(0.01, peak)).
+struct PcmCvt {
+  float gain, scale;
+  int norm;
+};
+
+__device__ __forceinline__ int pcm_cvt(float x, const PcmCvt c) {
+  if (c.norm) {
+    float v = x * c.scale;
+    v = v * c.gain;
+    v = v != v ? 0.0f : fminf(fmaxf(v, -32767.0f), 32767.0f);
+    return (int)v;  // v_cvt_i32_f32 truncates toward zero
+  }
+  double d = (double)(x * c.gain);
+  d = d != d ? 0.0 : fmin(fmax(d, -1.0), 1.0);
+  return (int)(d * 32767.0);  // v_cvt_i32_f64 truncates toward zero
+}
+
+__device__ __forceinline__ unsigned pcm_pair(float lo, float hi, const PcmCvt c) {
+  return ((unsigned)pcm_cvt(lo, c) & 0xffffu) | ((unsigned)pcm_cvt(hi, c) << 16);  // little-endian: the first sample in the low half
+}
+
+// frames of an item as the device reports them, clamped to the plan's row
+__device__ __forceinline__ int clamp_len(int len, int F) { return min(max(len, 0), F); }
+
 // Items of plan audio [NB][row] → back to back at their true lengths lensF[b]·hop in `out` (device memory or a page-locked host mapping),
 // item b at hop·Σ_{i<b} lensF[i]; lengths are read from device memory and clamped to F, so at most NB·F·hop samples are written.
 // peaks == nullptr: the reference conversion of x·gain. peaks != nullptr ([NB], from launch_pcm16_peak): peak normalisation per item;

@@ -19,27 +19,6 @@
 namespace ph {
 namespace {
 
-struct PcmCvt {
-  float gain, scale;
-  int norm;
-};
-
-__device__ __forceinline__ int pcm_cvt(float x, const PcmCvt c) {
-  if (c.norm) {
-    float v = x * c.scale;
-    v = v * c.gain;
-    v = v != v ? 0.0f : fminf(fmaxf(v, -32767.0f), 32767.0f);
-    return (int)v;  // v_cvt_i32_f32 truncates toward zero
-  }
-  double d = (double)(x * c.gain);
-  d = d != d ? 0.0 : fmin(fmax(d, -1.0), 1.0);
-  return (int)(d * 32767.0);  // v_cvt_i32_f64 truncates toward zero
-}
-
-__device__ __forceinline__ unsigned pcm_pair(float lo, float hi, const PcmCvt c) {
-  return ((unsigned)pcm_cvt(lo, c) & 0xffffu) | ((unsigned)pcm_cvt(hi, c) << 16);  // little-endian: the first sample in the low half
-}
-
 // n samples src → dst, shared among `nth` threads of which this is `tid`
 __device__ __forceinline__ void pcm_span(const float* __restrict__ src, int16_t* __restrict__ dst, int64_t n, int64_t tid, int64_t nth,
                                          const PcmCvt c) {
@@ -66,8 +45,6 @@ __device__ __forceinline__ void pcm_span(const float* __restrict__ src, int16_t*
   }
   for (int64_t i = done + tid; i < n; i += nth) dst[i] = (int16_t)pcm_cvt(src[i], c);
 }
-
-__device__ __forceinline__ int clamp_len(int len, int F) { return min(max(len, 0), F); }
 
 // Plan audio [NB][row] → the items back to back at their true lengths. blockIdx.y = item; the item's offset is the sum of the lengths
 // before it (NB ≤ 256 = one per thread), so plain, ragged and bounded slots — whose lengths only the device knows — take the same launch.

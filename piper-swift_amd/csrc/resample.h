@@ -1,0 +1,47 @@
+// resample.h — rational sample-rate conversion fused into the 16-bit PCM conversion (resample.hip); launched from voice.hip behind a
+// plan's graph, never captured into it. The arithmetic is the contract of include/piper_hip.h "Output rate".
+#pragma once
+#include "common.h"
+
+namespace ph {
+
+// The filter of one (in, out) pair, designed in double on the host once per process (rs_design) and kept for its life.
+struct RsDesign {
+  int in = 0, out = 0, L = 0, M = 0, P = 0;  // out / gcd, in / gcd, taps per phase
+  std::vector<float> taps;                   // [L][P]
+};
+// PIPER_HIP_ERR_UNSUPPORTED for a pair outside the contract (output rate not in the list, L > 640 or P > 256), PIPER_HIP_ERR_ARG for a rate ≤ 0.
+int rs_design(int in_rate, int out_rate, const RsDesign** out);
+inline int64_t rs_count(const RsDesign& d, int64_t n_in) { return ceil_div(n_in * d.L, d.M); }  // J(n_in)
+// the first output a stream step may NOT emit yet when the item's samples [0, e) are known and more follow: ⌈(e − P/2)·L / M⌉, at least 0
+inline int64_t rs_ready(const RsDesign& d, int64_t e) { return e <= d.P / 2 ? 0 : ceil_div((e - d.P / 2) * d.L, d.M); }
+// outputs one row can deliver in a step over n_in input samples
+inline int64_t rs_step_bound(const RsDesign& d, int64_t n_in) { return ceil_div(n_in * d.L, d.M) + ceil_div((int64_t)(d.P / 2) * d.L, d.M) + 1; }
+
+// The filter as the kernels take it: the [L][P] table in device memory.
+struct RsFilter {
+  const float* taps;
+  int L, M, P;
+};
+
+// Samples of a stream row the next step reads before its chunk: the last kRsHist true samples of the previous chunk (P − 1 ≤ 255 are needed).
+constexpr int kRsHist = 256;
+
+// One generator row of a resampling stream step (voice.hip fills it, resample_step_kernel reads it): the chunk is the n_in samples behind
+// the halo skip of the row's plan audio, input samples [s, s + n_in) of the item; the step emits outputs [j0, j0 + count) at `off` samples
+// into the packed output. n_in == 0: the row has nothing in this step.
+struct RsStepRow {
+  int64_t s, j0;
+  int skip, n_in, count, off;
+};
+
+// Items of plan audio [NB][row] → back to back at J(lensF[b]·hop) samples each (lengths read from device memory and clamped to F), item b
+// at Σ_{i<b} J(·). out_f32 != nullptr: the fp32 y; otherwise int16 into out_pcm through the PCM contract — gain, and peak normalisation
+// per item when peaks != nullptr, as launch_pcm16_pack. lensF == nullptr: one item of n_flat contiguous samples (NB = 1). NB ≤ 256.
+hipError_t launch_resample_items(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, int64_t n_flat,
+                                 const RsFilter& f, float gain, const float* peaks, float* peaks_host, int16_t* out_pcm, float* out_f32);
+// One stream step: every row's outputs packed at the descriptor's offsets as int16; hist_old / hist_new are [NBg][kRsHist] (read / written).
+hipError_t launch_resample_step(hipStream_t q, int NBg, int max_count, const float* audio, int64_t row, const RsStepRow* desc,
+                                const float* hist_old, float* hist_new, const RsFilter& f, float gain, int16_t* out);
+
+}  // namespace ph

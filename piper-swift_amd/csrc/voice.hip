@@ -24,6 +24,7 @@
 #include "conv_bf16.h"
 #include "conv_win.h"
 #include "pcm16.h"
+#include "resample.h"
 #include "rng.h"
 
 namespace ph {
@@ -220,6 +221,18 @@ struct StreamRow {
   bool active = false;
 };
 
+// The output rate of a stream — single, group or pool (piper_hip_voice_stream_set_rate): 0 is the voice's own rate. A resampling stream
+// keeps, per generator row, the last kRsHist samples of the previous chunk in device memory, in two buffers that change roles every step
+// (one launch reads the old history and writes the new one), and uploads a descriptor of its own per step.
+struct StreamRate {
+  int rate = 0;
+  bool started = false;       // a step has run (a pool: or a session has joined): the rate can no longer change
+  int parity = 0;             // which history buffer the next step reads
+  int rows = 0;               // generator rows the buffers below hold
+  float* hist = nullptr;      // device [2][rows][kRsHist]
+  RsStepRow* desc = nullptr;  // device [rows]
+};
+
 struct Slot {
   StreamSet set;  // empty (set.stream == nullptr) while the plan is idle: slot_init takes one, give_back_set returns it
   // A Slot is a PLAN: schedule + arena + graph for one bucket (kind, T, F, NB). T and F are the bucket's row lengths; the
@@ -284,12 +297,14 @@ struct Slot {
   size_t pcm_cap = 0;         // samples
   float* peaks = nullptr;     // [NB] max |x| per item (normalize = 1)
   std::vector<float> h_peaks; // the same on the host after a normalising collect_pcm16 (empty: none since the last launch)
+  StreamRate rs;              // output rate of the stream in progress; its buffers are in `owned`
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
 void reset_stream_state(Slot& s) {
   s.st_next = -1;
   s.bs_rows.clear();
+  s.rs.rate = 0; s.rs.started = false; s.rs.parity = 0;  // (a new stream starts at the voice's own rate; the buffers stay with the plan)
 }
 
 // Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
@@ -314,6 +329,8 @@ struct StreamPool {
   int* d_desc = nullptr;          // device: [NBg][kDescInts] descriptor of the step (one upload per step)
   float* pack = nullptr;         // device: the packed chunks of one step, capacity · chunk · hop floats
   std::vector<hipEvent_t> ev_free, ev_pending;  // ev_pending: "the adopt of a join since the last step has run", one per join
+  StreamRate rs;                 // output rate of the pool; its buffers come from the context pool and go back in pool_close
+  size_t pack_bytes = 0;         // of `pack`
 };
 
 }  // namespace
@@ -397,6 +414,9 @@ struct piper_hip_voice {
   Slot* attached_dp[kMaxSlots] = {};  // bounded prepare: the encoder + predictor plan this slot id holds until its next prepare / detach
   uint64_t use_clock = 0;
   int hop = 1;
+  // Output rates used so far: the filter of (cfg.sample_rate → rate) and its table in device memory (context pool), freed with the voice.
+  struct RateTable { const RsDesign* d = nullptr; float* taps = nullptr; };
+  std::map<int, RateTable> rate_tables;
 };
 
 namespace {
@@ -715,6 +735,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.zin = nullptr; s.z_out = nullptr;
   s.bs_desc = nullptr; s.bs_pack = nullptr; s.bs_pack_cap = 0;  // (both buffers are in `owned`)
   s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();      // (these too)
+  s.rs = StreamRate();                                                         // (and the resampling history and descriptor)
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   for (void* p : s.owned) (void)v->ctx->pool.release(p);
   s.owned.clear();
@@ -741,6 +762,8 @@ void pool_close(piper_hip_voice* v, int slot) {
   if (P->d_rows) (void)v->ctx->pool.release(P->d_rows);
   if (P->d_desc) (void)v->ctx->pool.release(P->d_desc);
   if (P->pack) (void)v->ctx->pool.release(P->pack);
+  if (P->rs.hist) (void)v->ctx->pool.release(P->rs.hist);
+  if (P->rs.desc) (void)v->ctx->pool.release(P->rs.desc);
   v->pools[slot].reset();
 }
 
@@ -2160,6 +2183,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
   }
   for (auto& st : v->free_sets) destroy_set(st);
   for (void* p : v->owned) (void)v->ctx->pool.release(p);
+  for (auto& rt : v->rate_tables) (void)v->ctx->pool.release(rt.second.taps);
   delete v;
 }
 
@@ -3092,6 +3116,41 @@ int pcm_params(const piper_hip_pcm_params* p, float* gain, bool* normalize) {
   return PIPER_HIP_OK;
 }
 
+// The filter from the voice's rate to out_rate, its table in device memory (uploaded on first use, kept by the voice).
+int voice_filter(piper_hip_voice* v, int out_rate, const RsDesign** d, RsFilter* f) {
+  const RsDesign* des = nullptr;
+  int rc = rs_design(v->cfg.sample_rate, out_rate, &des);
+  if (rc) return rc;
+  auto it = v->rate_tables.find(out_rate);
+  if (it == v->rate_tables.end()) {
+    void* p = nullptr;
+    if ((rc = v->ctx->pool.alloc(des->taps.size() * sizeof(float), &p))) return rc;
+    if (hipMemcpy(p, des->taps.data(), des->taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)v->ctx->pool.release(p);
+      PH_FAIL(PIPER_HIP_ERR_LAUNCH, "resample: the filter table could not be uploaded");
+    }
+    piper_hip_voice::RateTable t;
+    t.d = des; t.taps = (float*)p;
+    it = v->rate_tables.emplace(out_rate, t).first;
+  }
+  if (d) *d = des;
+  *f = RsFilter{it->second.taps, des->L, des->M, des->P};
+  return PIPER_HIP_OK;
+}
+
+// The outputs [j0, j1) a resampling step emits for a row whose chunk is the input samples [s, e) of N: everything whose taps end before e
+// (the halo behind e is an approximation, the next chunk does not exist yet), the rest of the item on its last step.
+void rate_range(const RsDesign& d, int64_t s, int64_t e, int64_t N, int64_t* j0, int64_t* j1) {
+  *j0 = s == 0 ? 0 : rs_ready(d, s);
+  *j1 = e >= N ? rs_count(d, N) : std::max(*j0, rs_ready(d, e));
+}
+
+// ints of a slot id's page-locked descriptor staging: the kDesc* table of a step, then the RsStepRow table of a resampling one
+constexpr size_t kDescStageInts = (size_t)256 * kDescInts;
+constexpr size_t kRateStageInts = kDescStageInts + (size_t)256 * sizeof(RsStepRow) / sizeof(int);
+static_assert(kDescStageInts * sizeof(int) % alignof(RsStepRow) == 0, "the RsStepRow table starts aligned");
+
 // What one stream step decodes of an utterance of F frames whose next frame is `next`: latent frames [a, a + Fc), of whose audio the first
 // `skip` samples are dropped and the following `n` are the chunk; `end` is the stream's next frame afterwards.
 struct Window {
@@ -3121,7 +3180,23 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (s.st_next >= Ftrue) return PIPER_HIP_OK;  // end of stream
   const Window w = window_of(Ftrue, s.st_next, s.st_chunk, s.st_halo, v->hop);
   const int a = w.a, Fc = w.Fc;
-  const int64_t want = w.n;
+  int64_t want = w.n;
+  // a slot with an output rate of its own delivers int16 only: the chunk goes through the resampling step kernel instead of the flat one
+  StreamRate& rs = s.rs;
+  const RsDesign* rd = nullptr;
+  RsFilter rf{};
+  RsStepRow rrow{};
+  if (rs.rate) {
+    if (!pcm) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next: slot %d delivers at %d Hz: use stream_next_pcm16", slot, rs.rate);
+    if (!want_out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_pcm16: a stream with an output rate needs a buffer");
+    int rc0 = voice_filter(v, rs.rate, &rd, &rf);
+    if (!rc0) rc0 = grow_pinned(v->staging[slot].h_desc, v->staging[slot].cap_desc, kRateStageInts);
+    if (rc0) return rc0;
+    int64_t j0, j1;
+    rate_range(*rd, (int64_t)s.st_next * v->hop, (int64_t)w.end * v->hop, (int64_t)Ftrue * v->hop, &j0, &j1);
+    rrow = RsStepRow{(int64_t)s.st_next * v->hop, j0, w.skip, w.n, (int)(j1 - j0), 0};
+    want = j1 - j0;
+  }
   if (want_out && max_samples < want) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next: buffer holds %lld < %lld samples", (long long)max_samples, (long long)want);
   // generator-only plan of the window's bucket (first / interior / last windows of a stream usually share one)
   Slot* gs = nullptr;
@@ -3140,8 +3215,17 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (pcm && want_out) {
     PcmRoute r;
-    if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], host_pcm, (size_t)want, (size_t)gs->F * v->hop, &r);
-    if (e == hipSuccess && !rc) e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, gain, r.kdst, v->ctx->num_cus);
+    const size_t dev_samples = (size_t)std::max<int64_t>((int64_t)gs->F * v->hop, rd ? rs_step_bound(*rd, (int64_t)gs->F * v->hop) : 0);
+    if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], host_pcm, (size_t)want, dev_samples, &r);
+    if (rd) {  // (every step ends with a wait: the staged descriptor of the previous one has been read)
+      RsStepRow* h = (RsStepRow*)(v->staging[slot].h_desc + kDescStageInts);
+      if (e == hipSuccess && !rc) { *h = rrow; e = hipMemcpyAsync(rs.desc, h, sizeof(RsStepRow), hipMemcpyHostToDevice, gs->set.stream); }
+      if (e == hipSuccess && !rc)
+        e = launch_resample_step(gs->set.stream, 1, rrow.count, gs->audio, 0, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
+                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, r.kdst);
+    } else if (e == hipSuccess && !rc) {
+      e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, gain, r.kdst, v->ctx->num_cus);
+    }
     if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, host_pcm, (size_t)want);
     if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)want * sizeof(int16_t));
     if (e != hipSuccess || rc) (void)hipStreamSynchronize(gs->set.stream);  // nothing of the window may still run when its plan goes idle
@@ -3156,6 +3240,8 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (rc) return rc;
   *n_samples = want;
   s.st_next = w.end;
+  rs.started = true;
+  if (rd) rs.parity ^= 1;
   return PIPER_HIP_OK;
 }
 }  // namespace
@@ -3327,6 +3413,7 @@ struct StepView {
   const PoolRowRef* d_rows;  // … or the device row table
   const hipEvent_t* wait;    // "the latents are there": what the step's stream waits for (the GPU waits, the host does not)
   size_t n_wait;
+  StreamRate* rs;            // the stream's output rate; a resampling step packs int16 through resample_step_kernel and its own descriptor
 };
 
 // stream_next_batch: the next chunk of every active row in one generator launch at the stream's fixed batch; *ran = a step ran and has
@@ -3342,8 +3429,19 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   const int n = s.n, NBg = s.NBg, hop = v->hop;
   auto& sg = v->staging[slot];
-  int rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * kDescInts);
-  if (rc) return rc;
+  StreamRate& rs = *s.rs;
+  const RsDesign* rd = nullptr;
+  RsFilter rf{};
+  int rc;
+  if (rs.rate) {
+    if (!pcm) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch: slot %d delivers at %d Hz: use stream_next_batch_pcm16", slot, rs.rate);
+    if (!want_out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch_pcm16: a stream with an output rate needs a buffer");
+    if ((rc = voice_filter(v, rs.rate, &rd, &rf))) return rc;
+  }
+  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, rd ? kRateStageInts : kDescStageInts))) return rc;
+  RsStepRow* rrow = (RsStepRow*)(sg.h_desc + kDescStageInts);  // (only touched when rd)
+  std::vector<int64_t> cnt(n, 0);  // samples each item delivers in this step
+  int max_cnt = 0;
   // the descriptor of this step (the previous step's upload has completed: every step ends with a wait)
   int* d = sg.h_desc;
   std::vector<Window> win(n);
@@ -3353,6 +3451,7 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     int* e = d + (size_t)r * kDescInts;
     for (int k = 0; k < kDescInts; k++) e[k] = 0;
     e[kDescSrc] = r < n ? r : 0;
+    if (rd) rrow[r] = RsStepRow{0, 0, 0, 0, 0, 0};
     if (r >= n || !s.rows[r].active) continue;
     const Window w = win[r] = window_of(s.rows[r].F, s.rows[r].next, s.chunk, s.halo, hop);
     e[kDescA] = w.a;
@@ -3360,15 +3459,24 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     e[kDescSkip] = w.skip;
     e[kDescN] = w.n;
     e[kDescOff] = (int)total;
-    total += w.n;
+    cnt[r] = w.n;
+    if (rd) {
+      int64_t j0, j1;
+      rate_range(*rd, (int64_t)s.rows[r].next * hop, (int64_t)w.end * hop, (int64_t)s.rows[r].F * hop, &j0, &j1);
+      rrow[r] = RsStepRow{(int64_t)s.rows[r].next * hop, j0, w.skip, w.n, (int)(j1 - j0), (int)total};
+      cnt[r] = j1 - j0;
+      max_cnt = std::max(max_cnt, (int)(j1 - j0));
+    }
+    total += cnt[r];
     Fmax = std::max(Fmax, w.Fc);
   }
   for (int i = 0; i < n; i++) n_samples[i] = 0;
-  if (total == 0) return PIPER_HIP_OK;  // end of the group / an idle pool
+  if (Fmax == 0) return PIPER_HIP_OK;  // end of the group / an idle pool
   if (want_out && max_samples < total)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
-  if ((size_t)total > s.pack_cap) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.pack_cap);
-  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap))) return rc;
+  if (rd ? (size_t)total * sizeof(int16_t) > s.pack_cap * sizeof(float) : (size_t)total > s.pack_cap)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.pack_cap);
+  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, rd ? ((size_t)total + 1) / 2 : (size_t)total, kAudioMinCap))) return rc;
   // generator-only plan of the step's longest window at the stream's batch size (rows past their end have length 0): a pool and a group
   // of the same size use the same plans
   Slot* gs = nullptr;
@@ -3390,7 +3498,12 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (e == hipSuccess) {
     const int px = (int)std::min<int64_t>(ceil_div((int64_t)s.chunk * hop, 1024), 64);
-    if (pcm) {
+    if (rd) {
+      e = hipMemcpyAsync(rs.desc, rrow, (size_t)NBg * sizeof(RsStepRow), hipMemcpyHostToDevice, q);
+      if (e == hipSuccess)
+        e = launch_resample_step(q, NBg, max_cnt, gs->audio, gs->n_samples, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
+                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, (int16_t*)s.pack);
+    } else if (pcm) {
       e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, s.d_desc, gain, (int16_t*)s.pack);
     } else {
       hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.d_desc, s.pack);
@@ -3404,8 +3517,10 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
   *ran = true;
   if (want_out) memcpy(pcm ? (void*)host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
+  rs.started = true;
+  if (rd) rs.parity ^= 1;
   for (int i = 0; i < n; i++) {
-    n_samples[i] = win[i].n;
+    n_samples[i] = cnt[i];
     if (!win[i].n) continue;
     s.rows[i].next = win[i].end;
     if (win[i].end >= s.rows[i].F) s.rows[i].active = false;  // last chunk delivered (a pool: the row is free for the next join)
@@ -3416,8 +3531,8 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
 // stream_next_batch on a pool slot: the latents are the row stores, ready when the adopts of the joins since the last step have run
 int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm,
               float gain) {
-  const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, (size_t)P.capacity * P.chunk * v->hop,
-                                       nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size()};
+  const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, P.pack_bytes / sizeof(float),
+                                       nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), &P.rs};
   bool ran = false;
   const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, &ran);
   if (rc || !ran) return rc;  // (an idle pool: joins since the last step stay pending)
@@ -3470,7 +3585,7 @@ int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samp
   Slot& s = *sp;
   const int n = (int)s.bs_rows.size();
   const StepView<StreamRow> view{s.bs_rows.data(), n, group_batch(n), s.st_chunk, s.st_halo, s.bs_desc, s.bs_pack, s.bs_pack_cap,
-                                 s.z_out, s.F, nullptr, &s.set.ev1, 1};
+                                 s.z_out, s.F, nullptr, &s.set.ev1, 1, &s.rs};
   bool ran = false;
   return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, &ran);
 }
@@ -3513,7 +3628,8 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
   int rc = v->ctx->pool.alloc((size_t)P->NBg * sizeof(PoolRowRef) + (size_t)capacity * sizeof(PoolJoinEnt), &p);
   if (!rc) P->d_rows = (PoolRowRef*)p;
   if (!rc) { rc = v->ctx->pool.alloc((size_t)P->NBg * kDescInts * sizeof(int), &p); if (!rc) P->d_desc = (int*)p; }
-  if (!rc) { rc = v->ctx->pool.alloc((size_t)capacity * chunk_frames * v->hop * sizeof(float), &p); if (!rc) P->pack = (float*)p; }
+  P->pack_bytes = (size_t)capacity * chunk_frames * v->hop * sizeof(float);
+  if (!rc) { rc = v->ctx->pool.alloc(P->pack_bytes, &p); if (!rc) P->pack = (float*)p; }
   v->pools[slot] = std::move(P);
   if (rc) { pool_close(v, slot); return rc; }
   return PIPER_HIP_OK;
@@ -3530,6 +3646,9 @@ PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, con
   if (n < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join: %d items", n);
   const int free_rows = pool_free_rows(*P);
   if (n > free_rows) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join: %d items, %d free rows of %d", n, free_rows, P->capacity);
+  const RsDesign* rate_d = nullptr;  // samples_out counts what the pool delivers
+  if (P->rs.rate)
+    if (int rc0 = rs_design(v->cfg.sample_rate, P->rs.rate, &rate_d)) return rc0;
   // encoder (+ predictor) inputs of the join on the work slot's plan, then encoder + flow on that plan's stream
   int rc = piper_hip_voice_prepare_batch(v, utts, n, work_slot);
   if (rc < 0) return rc;
@@ -3594,8 +3713,9 @@ PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, con
     r.next = 0;
     r.active = true;
     if (items_out) items_out[i] = take[i];
-    if (samples_out) samples_out[i] = (int64_t)w.h_F[i] * v->hop;
+    if (samples_out) samples_out[i] = rate_d ? rs_count(*rate_d, (int64_t)w.h_F[i] * v->hop) : (int64_t)w.h_F[i] * v->hop;
   }
+  P->rs.started = true;  // the pool's output rate is fixed from its first join on
   return PIPER_HIP_OK;
 }
 
@@ -3615,7 +3735,10 @@ PH_EXPORT int piper_hip_voice_stream_pool_close(piper_hip_voice* v, int slot) {
 }
 
 // ---- 16-bit PCM straight from the device (pcm16.hip): the launches go on the slot's stream behind the plan's graph, outside it -----------
-PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm, int64_t max_samples) {
+namespace {
+// collect_pcm16, and collect_pcm16_rate where out_rate differs from the voice's own: then item b is J(its true samples) long and the pack
+// kernel's place is taken by the resampling one (rd / rf: its filter); everything else — the peaks, the route, the landing — is shared.
+int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int out_rate, int16_t* host_pcm, int64_t max_samples) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   Slot* p = slot_plan(v, slot);
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
@@ -3623,6 +3746,16 @@ PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const 
   bool normalize;
   int rc = pcm_params(params, &gain, &normalize);
   if (rc) return rc;
+  const RsDesign* rd = nullptr;
+  RsFilter rf{};
+  if (out_rate != v->cfg.sample_rate) {
+    if ((rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;  // (a rate outside the contract is refused before anything waits)
+    if (host_pcm) {
+      PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+      if ((rc = voice_filter(v, out_rate, &rd, &rf))) return rc;
+    }
+  }
+  const auto out_len = [&](int64_t samples) { return rd ? rs_count(*rd, samples) : samples; };
   if (!host_pcm) return piper_hip_voice_collect(v, slot, nullptr, 0);  // just wait (a bounded slot: and learn the lengths)
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *p;
@@ -3633,8 +3766,8 @@ PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const 
   const bool bounded = s.bounded_pending;
   // a bounded slot's lengths are still on the device: the caller makes room for the capacity, as for collect
   int64_t need = 0;
-  if (bounded) need = (int64_t)F * hop * NB;
-  else for (int b = 0; b < NB; b++) need += (int64_t)s.h_F[b] * hop;
+  if (bounded) need = out_len((int64_t)F * hop) * NB;
+  else for (int b = 0; b < NB; b++) need += out_len((int64_t)s.h_F[b] * hop);
   if (max_samples < need) {
     if (bounded)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_prepared_samples before collect), got %lld",
@@ -3652,20 +3785,35 @@ PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const 
     if (hipHostGetDevicePointer((void**)&peaks_host, sg.h_peaks, 0) != hipSuccess) { peaks_host = nullptr; (void)hipGetLastError(); }
   }
   PcmRoute r;
-  if ((rc = pcm_route(v, s, sg, host_pcm, (size_t)need, (size_t)F * hop * NB, &r))) return rc;
+  if ((rc = pcm_route(v, s, sg, host_pcm, (size_t)need, (size_t)std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB, &r))) return rc;
   const hipStream_t q = s.set.stream;
   if (normalize) PH_HIP(launch_pcm16_peak(q, s.audio, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(launch_pcm16_pack(q, s.audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst), PIPER_HIP_ERR_LAUNCH);
+  if (rd)
+    PH_HIP(launch_resample_items(q, s.audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, nullptr),
+           PIPER_HIP_ERR_LAUNCH);
+  else
+    PH_HIP(launch_pcm16_pack(q, s.audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst), PIPER_HIP_ERR_LAUNCH);
   if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, (size_t)NB * sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
   if ((rc = pcm_land(sg, r, q, host_pcm, (size_t)need))) return rc;
   if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
   if (r.mapped && !r.caller_pinned) {  // the kernel stored into the staging: the true total is known by now
     int64_t total = 0;
-    for (int b = 0; b < NB; b++) total += (int64_t)s.h_F[b] * hop;
+    for (int b = 0; b < NB; b++) total += out_len((int64_t)s.h_F[b] * hop);
     memcpy(host_pcm, r.stage, (size_t)total * sizeof(int16_t));
   }
   if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + NB);
   return PIPER_HIP_OK;
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm, int64_t max_samples) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  return collect_pcm(v, slot, params, v->cfg.sample_rate, host_pcm, max_samples);
+}
+
+PH_EXPORT int piper_hip_voice_collect_pcm16_rate(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int32_t out_rate, int16_t* host_pcm,
+                                                 int64_t max_samples) {
+  return collect_pcm(v, slot, params, out_rate, host_pcm, max_samples);
 }
 
 PH_EXPORT int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* peaks, int max_items) {
@@ -3690,6 +3838,126 @@ PH_EXPORT int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_h
   if ((rc = piper_hip_voice_collect_pcm16(v, 0, params, host_pcm, max_samples))) return rc;
   if (n_samples) *n_samples = (int64_t)v->attached[0]->h_F[0] * v->hop;
   return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_synthesize_pcm16_rate(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params,
+                                                    int32_t out_rate, int16_t* host_pcm, int64_t max_samples, int64_t* n_samples) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  float gain;
+  bool normalize;
+  int rc = pcm_params(params, &gain, &normalize);
+  if (rc) return rc;
+  const RsDesign* rd = nullptr;
+  if (out_rate != v->cfg.sample_rate && (rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
+  if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
+  if ((rc = piper_hip_voice_launch(v, 0))) return rc;
+  if ((rc = collect_pcm(v, 0, params, out_rate, host_pcm, max_samples))) return rc;
+  const int64_t n = (int64_t)v->attached[0]->h_F[0] * v->hop;
+  if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
+  return PIPER_HIP_OK;
+}
+
+namespace {
+// The stream slot id `slot` holds, as the rate entry points see it: its rate record, generator rows, items and samples per row and step.
+struct StreamRef {
+  StreamRate* rs = nullptr;
+  int rows = 0, items = 0;
+  int64_t chunk_samples = 0;
+  StreamPool* pool = nullptr;
+  Slot* plan = nullptr;
+};
+int stream_ref(piper_hip_voice* v, int slot, const char* who, StreamRef* r) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (StreamPool* P = slot_pool(v, slot)) {
+    *r = StreamRef{&P->rs, P->NBg, P->capacity, (int64_t)P->chunk * v->hop, P, nullptr};
+    return PIPER_HIP_OK;
+  }
+  Slot* sp = slot_plan(v, slot);
+  if (sp && !sp->bs_rows.empty()) {
+    const int n = (int)sp->bs_rows.size();
+    *r = StreamRef{&sp->rs, group_batch(n), n, (int64_t)sp->st_chunk * v->hop, nullptr, sp};
+    return PIPER_HIP_OK;
+  }
+  if (sp && sp->st_next >= 0) {
+    *r = StreamRef{&sp->rs, 1, 1, (int64_t)sp->st_chunk * v->hop, nullptr, sp};
+    return PIPER_HIP_OK;
+  }
+  PH_FAIL(PIPER_HIP_ERR_ARG, "%s: slot %d has no stream in progress", who, slot);
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int32_t out_rate) {
+  StreamRef r;
+  int rc = stream_ref(v, slot, "stream_set_rate", &r);
+  if (rc) return rc;
+  if (r.rs->started)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d has %s: the rate is set before", slot, r.pool ? "stepped or been joined" : "stepped");
+  if (out_rate == v->cfg.sample_rate) {  // not a filter: the steps are the un-resampled ones
+    r.rs->rate = 0;
+    return PIPER_HIP_OK;
+  }
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  const RsDesign* rd = nullptr;
+  RsFilter rf{};
+  if ((rc = voice_filter(v, out_rate, &rd, &rf))) return rc;
+  // the history and the descriptor of the stream's rows, and a packed-output buffer that holds a step at this rate
+  const size_t hist_bytes = (size_t)2 * r.rows * kRsHist * sizeof(float), desc_bytes = (size_t)r.rows * sizeof(RsStepRow);
+  const size_t pack_bytes = (size_t)r.items * (size_t)rs_step_bound(*rd, r.chunk_samples) * sizeof(int16_t);
+  void* p = nullptr;
+  if (r.rs->rows < r.rows) {
+    if (r.pool) {
+      if (r.rs->hist) (void)v->ctx->pool.release(r.rs->hist);
+      if (r.rs->desc) (void)v->ctx->pool.release(r.rs->desc);
+      r.rs->hist = nullptr; r.rs->desc = nullptr; r.rs->rows = 0;
+      if ((rc = v->ctx->pool.alloc(hist_bytes, &p))) return rc;
+      r.rs->hist = (float*)p;
+      if ((rc = v->ctx->pool.alloc(desc_bytes, &p))) return rc;
+      r.rs->desc = (RsStepRow*)p;
+    } else {  // (a plan keeps what an earlier, smaller stream allocated until it is released)
+      r.rs->rows = 0;
+      if ((rc = plan_alloc(v, *r.plan, hist_bytes, &p))) return rc;
+      r.rs->hist = (float*)p;
+      if ((rc = plan_alloc(v, *r.plan, desc_bytes, &p))) return rc;
+      r.rs->desc = (RsStepRow*)p;
+    }
+    r.rs->rows = r.rows;
+  }
+  if (r.pool && r.pool->pack_bytes < pack_bytes) {
+    if ((rc = v->ctx->pool.alloc(pack_bytes, &p))) return rc;
+    if (r.pool->pack) (void)v->ctx->pool.release(r.pool->pack);  // (no step has run on this pool)
+    r.pool->pack = (float*)p;
+    r.pool->pack_bytes = pack_bytes;
+  }
+  if (r.plan && !r.plan->bs_rows.empty() && r.plan->bs_pack_cap * sizeof(float) < pack_bytes) {
+    Slot& s = *r.plan;  // (every step ends with a wait: nothing of an earlier stream on this plan still reads the buffer)
+    if (s.bs_pack) plan_free(v, s, s.bs_pack, s.bs_pack_cap * sizeof(float));
+    s.bs_pack = nullptr;
+    s.bs_pack_cap = 0;
+    const size_t floats = (pack_bytes + sizeof(float) - 1) / sizeof(float);
+    if ((rc = plan_alloc(v, s, floats * sizeof(float), &p))) return rc;
+    s.bs_pack = (float*)p;
+    s.bs_pack_cap = floats;
+  }
+  r.rs->parity = 0;
+  r.rs->rate = out_rate;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot) {
+  StreamRef r;
+  const int rc = stream_ref(v, slot, "stream_rate", &r);
+  if (rc) return rc;
+  return r.rs->rate ? r.rs->rate : v->cfg.sample_rate;
+}
+
+PH_EXPORT int64_t piper_hip_voice_stream_step_capacity(piper_hip_voice* v, int slot) {
+  StreamRef r;
+  int rc = stream_ref(v, slot, "stream_step_capacity", &r);
+  if (rc) return rc;
+  if (!r.rs->rate) return (int64_t)r.items * r.chunk_samples;
+  const RsDesign* rd = nullptr;
+  if ((rc = rs_design(v->cfg.sample_rate, r.rs->rate, &rd))) return rc;
+  return (int64_t)r.items * rs_step_bound(*rd, r.chunk_samples);
 }
 
 namespace {

@@ -246,6 +246,20 @@ _PROTOS = {
     "piper_hip_voice_stream_next_pcm16": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), c_i16p, C.c_int64, C.POINTER(C.c_int64)]),
     "piper_hip_voice_stream_next_batch_pcm16": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), c_i16p, C.c_int64, C.POINTER(C.c_int64)]),
     "piper_hip_voice_peaks": (C.c_int, [c_vp, C.c_int, c_f32p, C.c_int]),
+    "piper_hip_resample_info": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "piper_hip_resample_taps": (C.c_int, [C.c_int32, C.c_int32, c_f32p, C.c_size_t]),
+    "piper_hip_resample_count": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "piper_hip_resample_step_bound": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "piper_hip_wav_write_pcm16": (C.c_int, [C.c_char_p, c_i16p, C.c_size_t, C.c_int32]),
+    "piper_hip_resample_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(c_vp), C.POINTER(C.c_size_t), c_vp]),
+    "piper_hip_resample_pcm16_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_int32, C.c_int32, C.c_float, C.POINTER(c_vp), C.POINTER(C.c_size_t),
+                                               c_vp]),
+    "piper_hip_voice_collect_pcm16_rate": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int32, c_i16p, C.c_int64]),
+    "piper_hip_voice_synthesize_pcm16_rate": (C.c_int, [c_vp, C.POINTER(Utterance), C.POINTER(PcmParams), C.c_int32, c_i16p, C.c_int64,
+                                                        C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_set_rate": (C.c_int, [c_vp, C.c_int, C.c_int32]),
+    "piper_hip_voice_stream_rate": (C.c_int, [c_vp, C.c_int]),
+    "piper_hip_voice_stream_step_capacity": (C.c_int64, [c_vp, C.c_int]),
     "piper_hip_voice_tap": (C.c_int, [c_vp, C.c_int, C.c_char_p, c_f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "piper_hip_voice_last_gpu_ms": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_double)]),
     "piper_hip_voice_slot_stream": (c_vp, [c_vp, C.c_int]),
@@ -584,6 +598,25 @@ class HipBackend:
         _check(self.lib.piper_hip_pcm16_f32(self.ctx, _ptr(buf), n, float(gain), C.byref(p), commandBuffer))
         return DeviceBuffer(self, p.value, n, owned=out is None, dtype=np.int16)
 
+    def resampleF32(self, buf, inRate, outRate, count=None, out=None, commandBuffer=None):
+        """`count` device floats at inRate → J(count) device floats at outRate (piper_hip_resample_f32): the fp32 y of the output-rate
+        contract (include/piper_hip.h "Output rate"). Returns a DeviceBuffer of J(count) float32."""
+        n = buf.count if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        got = C.c_size_t()
+        _check(self.lib.piper_hip_resample_f32(self.ctx, _ptr(buf), n, int(inRate), int(outRate), C.byref(p), C.byref(got), commandBuffer))
+        return DeviceBuffer(self, p.value, got.value, owned=out is None)
+
+    def resamplePcm16F32(self, buf, inRate, outRate, gain=1.0, count=None, out=None, commandBuffer=None):
+        """The same ending in 16-bit PCM (piper_hip_resample_pcm16_f32): y · gain through pcm16F32's arithmetic. Returns a DeviceBuffer of
+        J(count) int16 (downloadInt16); `out`: a device address to write to (2-byte alignment suffices), returned as it is."""
+        n = buf.count if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        got = C.c_size_t()
+        _check(self.lib.piper_hip_resample_pcm16_f32(self.ctx, _ptr(buf), n, int(inRate), int(outRate), float(gain), C.byref(p), C.byref(got),
+                                                     commandBuffer))
+        return DeviceBuffer(self, p.value, got.value, owned=out is None, dtype=np.int16)
+
     def downloadInt16(self, buf, count=None):
         """The first `count` int16 of a device buffer of this backend's pool → host array. (Copied as whole floats: an odd count reads one
         sample more, which a pool block — a power of two of at least 256 bytes — always holds.)"""
@@ -817,6 +850,43 @@ def wav_write(path, samples, sample_rate=22050):
     _check(load_library().piper_hip_wav_write(str(path).encode(), a.ctypes.data_as(c_f32p), a.size, int(sample_rate)))
 
 
+def wav_write_pcm16(path, pcm, sample_rate=22050):
+    """A mono WAV file from samples that are 16-bit PCM already, at the rate they were delivered."""
+    a = np.ascontiguousarray(pcm, np.int16)
+    _check(load_library().piper_hip_wav_write_pcm16(str(path).encode(), a.ctypes.data_as(c_i16p), a.size, int(sample_rate)))
+
+
+def resample_info(in_rate, out_rate):
+    """(L, M, taps per phase) of the output-rate contract for a rate pair; UnsupportedOp for a pair outside it. Host-only."""
+    L, M, P = C.c_int32(), C.c_int32(), C.c_int32()
+    _check(load_library().piper_hip_resample_info(int(in_rate), int(out_rate), C.byref(L), C.byref(M), C.byref(P)))
+    return L.value, M.value, P.value
+
+
+def resample_taps(in_rate, out_rate):
+    """The [L][P] float32 coefficient table the kernels use for a rate pair. Host-only."""
+    L, _, P = resample_info(in_rate, out_rate)
+    out = np.empty((L, P), np.float32)
+    _check(load_library().piper_hip_resample_taps(int(in_rate), int(out_rate), out.ctypes.data_as(c_f32p), out.size))
+    return out
+
+
+def _count(rc):
+    if rc < 0:
+        _check(int(rc))
+    return int(rc)
+
+
+def resample_count(in_rate, out_rate, n_in):
+    """J(n_in): the samples an item of n_in samples yields at out_rate. Host-only."""
+    return _count(load_library().piper_hip_resample_count(int(in_rate), int(out_rate), int(n_in)))
+
+
+def resample_step_bound(in_rate, out_rate, n_in):
+    """The most samples one stream row delivers in a step over n_in input samples. Host-only."""
+    return _count(load_library().piper_hip_resample_step_bound(int(in_rate), int(out_rate), int(n_in)))
+
+
 def piper_json(text):
     info = PiperJsonInfo()
     _check(load_library().piper_hip_piper_json(text.encode("utf-8"), C.byref(info)))
@@ -830,6 +900,16 @@ class StreamPool:
         self.rt, self.slot, self.capacity, self.chunk_frames, self.work_slot = rt, slot, capacity, chunk_frames, work_slot
         self._buf = np.empty(max(capacity * chunk_frames * rt.cfg.hop, 1), np.float32)
         self._got = (C.c_int64 * capacity)()
+        self.rate = None
+
+    def set_rate(self, rate):
+        """Deliver at `rate` Hz (piper_hip_voice_stream_set_rate): before the first join. step() then returns int16 chunks only."""
+        self.rt.stream_set_rate(self.slot, rate)
+        if int(rate) == self.rt.cfg.sample_rate:  # not a filter: the pool stays as it was opened, float steps included
+            self.rate = None
+            return
+        self.rate = int(rate)
+        self._buf = np.empty((self.rt.stream_step_capacity(self.slot) + 1) // 2, np.float32)
 
     def join(self, utterances, noiseScale=0.667):
         """utterances as for synthesize_stream_batch: (phonemeIDs, durations-or-None, noise-or-None[, dict]). Returns [(item, samples)]:
@@ -853,7 +933,7 @@ class StreamPool:
         (piper_hip_voice_stream_next_batch_pcm16; normalize is refused there — UnsupportedOp — and consumes nothing)."""
         rt = self.rt
         if pcm:
-            buf = self._buf.view(np.int16)[:self._buf.size]
+            buf = self._buf.view(np.int16)[:self._buf.size * (2 if self.rate else 1)]
             prm = PcmParams(float(gain), int(bool(normalize)))
             _check(rt.lib.piper_hip_voice_stream_next_batch_pcm16(rt.voice, self.slot, C.byref(prm), buf.ctypes.data_as(c_i16p), buf.size, self._got))
         else:
@@ -1010,14 +1090,30 @@ class HipRuntime:
             off += len(ids)
         return outs
 
-    def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0):
+    def stream_set_rate(self, slot, rate):
+        """The output rate of the stream on `slot` (piper_hip_voice_stream_set_rate): after its begin / open, before its first step."""
+        _check(self.lib.piper_hip_voice_stream_set_rate(self.voice, slot, int(rate)))
+
+    def stream_rate(self, slot):
+        return _count(self.lib.piper_hip_voice_stream_rate(self.voice, slot))
+
+    def stream_step_capacity(self, slot):
+        """The int16 samples one step of the stream on `slot` can deliver at its current rate."""
+        return _count(self.lib.piper_hip_voice_stream_step_capacity(self.voice, slot))
+
+    def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None):
         """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
-        pcm=True: int16 chunks converted on the device (piper_hip_voice_stream_next_pcm16), scaled by `gain`."""
+        pcm=True: int16 chunks converted on the device (piper_hip_voice_stream_next_pcm16), scaled by `gain`. rate: int16 chunks at that
+        output rate (stream_set_rate; implies pcm)."""
         u, keep = self._utt(phonemeIDs, durations, noise, noiseScale)
         n_chunks = self.lib.piper_hip_voice_stream_begin(self.voice, C.byref(u), slot, int(chunkFrames))
         if n_chunks < 0:
             _check(n_chunks)
-        buf = np.empty(int(chunkFrames) * self.cfg.hop, np.int16 if pcm else np.float32)
+        buf = np.empty(int(chunkFrames) * self.cfg.hop, np.int16 if pcm or rate else np.float32)
+        if rate:
+            pcm = True
+            self.stream_set_rate(slot, rate)
+            buf = np.empty(self.stream_step_capacity(slot), np.int16)
         got = C.c_int64()
         prm = PcmParams(float(gain), 0)
         while True:
@@ -1029,11 +1125,11 @@ class HipRuntime:
                 return
             yield buf[:got.value].copy()
 
-    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0):
+    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None):
         """Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
         arrays — the next chunk of every item, empty once the item is finished or dropped (stream_drop). pcm=True: int16 chunks converted on
-        the device (piper_hip_voice_stream_next_batch_pcm16), scaled by `gain`."""
+        the device (piper_hip_voice_stream_next_batch_pcm16), scaled by `gain`. rate: int16 chunks at that output rate (implies pcm)."""
         n = len(utterances)
         arr = (Utterance * max(n, 1))()
         keep = []
@@ -1045,7 +1141,11 @@ class HipRuntime:
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
-        buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), np.int16 if pcm else np.float32)
+        buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), np.int16 if pcm or rate else np.float32)
+        if rate:
+            pcm = True
+            self.stream_set_rate(slot, rate)
+            buf = np.empty(self.stream_step_capacity(slot), np.int16)
         got = (C.c_int64 * n)()
         prm = PcmParams(float(gain), 0)
         while True:
@@ -1066,14 +1166,17 @@ class HipRuntime:
         """The client of item `item` of the batched stream on `slot` went away: later steps skip it."""
         _check(self.lib.piper_hip_voice_stream_drop(self.voice, slot, int(item)))
 
-    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None):
+    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None, rate=None):
         """A streaming pool (piper_hip_voice_stream_pool_open) of `capacity` rows on `slot`: sessions join and leave while it runs.
         work_slot: the slot id whose plan runs the joins' encoder + flow (default: the next slot id)."""
         if work_slot is None:
             work_slot = slot + 1 if slot + 1 < 16 else slot - 1
         _check(self.lib.piper_hip_voice_stream_pool_open(self.voice, slot, int(capacity), int(chunkFrames)))
         self._keep.pop(slot, None)
-        return StreamPool(self, slot, int(capacity), int(chunkFrames), int(work_slot))
+        pool = StreamPool(self, slot, int(capacity), int(chunkFrames), int(work_slot))
+        if rate:
+            pool.set_rate(rate)
+        return pool
 
     def prepare_batch(self, slot, utterances, noiseScale=0.667):
         """utterances: list of (phonemeIDs, durations, noise-or-None); lengths may differ (ragged batch, one bucket)."""
@@ -1132,11 +1235,14 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
-    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None):
+    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None):
         """collect() with 16-bit PCM converted on the device (piper_hip_voice_collect_pcm16): the items back to back at their true lengths.
         normalize=False: the samples pcm16(collect(slot)) gives; normalize=True: Piper's peak normalisation per item (peaks(slot) afterwards).
-        The fp32 waveform stays in the plan: collect / collect_pcm16 may follow in any order."""
+        The fp32 waveform stays in the plan: collect / collect_pcm16 may follow in any order. rate: resampled on the device to that output
+        rate (piper_hip_voice_collect_pcm16_rate), item b at J(its true samples)."""
         n = self._keep[slot][1]
+        if rate is not None and int(rate) != self.cfg.sample_rate:  # (the voice's own rate is not a filter: the plain call)
+            return self._collect_pcm16_rate(slot, gain, normalize, out, int(rate))
         if out is None:
             out = np.empty(max(n, 1), np.int16)
         assert out.dtype == np.int16 and out.size >= n and out.flags.c_contiguous
@@ -1147,9 +1253,37 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
+    def _collect_pcm16_rate(self, slot, gain, normalize, out, rate):
+        src = self.cfg.sample_rate
+        bounded = len(self._keep[slot]) > 2 and self._keep[slot][2]
+        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
+        per, total = self.prepared_samples(slot)  # (a bounded slot: the capacity, spread evenly over the items)
+        room = nb * resample_count(src, rate, total // max(nb, 1)) if bounded else sum(resample_count(src, rate, p) for p in per)
+        if out is None:
+            out = np.empty(max(room, 1), np.int16)
+        assert out.dtype == np.int16 and out.size >= room and out.flags.c_contiguous
+        prm = PcmParams(float(gain), int(bool(normalize)))
+        _check(self.lib.piper_hip_voice_collect_pcm16_rate(self.voice, slot, C.byref(prm), rate, out.ctypes.data_as(c_i16p), room))
+        if bounded:  # the true lengths are known now
+            per, total = self.prepared_samples(slot)
+            self._keep[slot] = (self._keep[slot][0], total, False)
+        return out[:sum(resample_count(src, rate, p) for p in per)]
+
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, **kw):
-        """synthesize() ending in 16-bit PCM converted on the device (slot 0)."""
+                         normalize=False, rate=None, **kw):
+        """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate."""
+        if rate is not None and int(rate) == self.cfg.sample_rate:
+            rate = None
+        if durations is not None and not kw and rate is not None:  # piper_hip_voice_synthesize_pcm16_rate
+            u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
+            n = resample_count(self.cfg.sample_rate, rate, int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
+            out = np.empty(max(n, 1), np.int16)
+            got = C.c_int64()
+            prm = PcmParams(float(gain), int(bool(normalize)))
+            _check(self.lib.piper_hip_voice_synthesize_pcm16_rate(self.voice, C.byref(u), C.byref(prm), int(rate), out.ctypes.data_as(c_i16p), n,
+                                                                  C.byref(got)))
+            self._keep.pop(0, None)
+            return out[:got.value]
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
@@ -1161,7 +1295,7 @@ class HipRuntime:
             return out[:got.value]
         self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, **kw)
         self.launch(0)
-        return self.collect_pcm16(0, gain, normalize)
+        return self.collect_pcm16(0, gain, normalize, rate=rate)
 
     def peaks(self, slot):
         """max |x| of each item of the slot, after a collect_pcm16(normalize=True) of its latest run."""

@@ -163,6 +163,44 @@ public final class HIPBackend {
         return HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx)
     }
 
+    /// `count` device floats at inRate → J(count) device floats at outRate (piper_hip_resample_f32): the fp32 y of the output-rate contract.
+    public func resampleF32(input: HIPBuffer, count: Int, inRate: Int32, outRate: Int32, commandBuffer: Stream? = nil) throws -> (HIPBuffer, Int) {
+        var out: UnsafeMutablePointer<Float>? = nil
+        var n = 0
+        try Self.check(piper_hip_resample_f32(ctx, input.f32, count, inRate, outRate, &out, &n, commandBuffer))
+        return (HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx), n)
+    }
+
+    /// The same ending in int16 (piper_hip_resample_pcm16_f32): y · gain through pcm16F32's arithmetic. The buffer holds J(count) int16.
+    public func resamplePcm16F32(input: HIPBuffer, count: Int, inRate: Int32, outRate: Int32, gain: Float = 1.0,
+                                 commandBuffer: Stream? = nil) throws -> (HIPBuffer, Int) {
+        var out: UnsafeMutablePointer<Int16>? = nil
+        var n = 0
+        try Self.check(piper_hip_resample_pcm16_f32(ctx, input.f32, count, inRate, outRate, gain, &out, &n, commandBuffer))
+        return (HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx), n)
+    }
+
+    /// (L, M, taps per phase) of a rate pair and its [L][P] coefficient table (piper_hip_resample_info / _taps; host-only).
+    public static func resampleInfo(inRate: Int32, outRate: Int32) throws -> (l: Int32, m: Int32, taps: Int32) {
+        var l: Int32 = 0, m: Int32 = 0, p: Int32 = 0
+        try check(piper_hip_resample_info(inRate, outRate, &l, &m, &p))
+        return (l, m, p)
+    }
+
+    public static func resampleTaps(inRate: Int32, outRate: Int32) throws -> [Float] {
+        let i = try resampleInfo(inRate: inRate, outRate: outRate)
+        var t = [Float](repeating: 0, count: Int(i.l) * Int(i.taps))
+        try check(piper_hip_resample_taps(inRate, outRate, &t, t.count))
+        return t
+    }
+
+    /// The most samples one stream row delivers in a step over `n` input samples (piper_hip_resample_step_bound; host-only).
+    public static func resampleStepBound(inRate: Int32, outRate: Int32, n: Int64) throws -> Int64 {
+        let b = piper_hip_resample_step_bound(inRate, outRate, n)
+        if b < 0 { try check(Int32(b)) }
+        return b
+    }
+
     // ---- binary with NumPy broadcasting, output rank ≤ 4 (MetalBackend.swift:2099-2134, 2592-2610) ----
     private func binaryBroadcastF32(_ op: piper_hip_binary_op, a: HIPBuffer, aShape: [Int], b: HIPBuffer, bShape: [Int],
                                     commandBuffer: Stream?) throws -> (out: HIPBuffer, outShape: [Int]) {

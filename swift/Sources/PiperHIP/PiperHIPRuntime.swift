@@ -287,6 +287,95 @@ public final class PiperHIPRuntime {
         return out
     }
 
+    // ---- Output rate: resampled to 8–48 kHz PCM on the device (include/piper_hip.h "Output rate") ----
+
+    /// J(n): the samples `n` samples at the voice's rate yield at `rate` (piper_hip_resample_count).
+    public func resampleCount(_ n: Int64, rate: Int32) throws -> Int64 {
+        let j = piper_hip_resample_count(sampleRate, rate, n)
+        if j < 0 { try HIPBackend.check(Int32(j)) }
+        return j
+    }
+
+    /// collectPCM16 at `rate` (piper_hip_voice_collect_pcm16_rate): item b at J(its true samples), in any order with collect / collectPCM16.
+    public func collectPCM16(slot: Int32, rate: Int32, gain: Float = 1.0, normalize: Bool = false) throws -> [Int16] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: normalize ? 1 : 0)
+        let nb = Int(piper_hip_voice_batch_size(voice, slot))
+        var per = [Int64](repeating: 0, count: max(nb, 1))
+        try HIPBackend.check(piper_hip_voice_prepared_samples(voice, slot, &per, Int32(nb), nil))   // a bounded slot: the capacity per item
+        var cap: Int64 = 0
+        for b in 0..<nb { cap += try resampleCount(per[b], rate: rate) }
+        var pcm = [Int16](repeating: 0, count: Int(cap))
+        try HIPBackend.check(piper_hip_voice_collect_pcm16_rate(voice, slot, &prm, rate, &pcm, cap))
+        try HIPBackend.check(piper_hip_voice_prepared_samples(voice, slot, &per, Int32(nb), nil))   // the true lengths now
+        var total: Int64 = 0
+        for b in 0..<nb { total += try resampleCount(per[b], rate: rate) }
+        pcm.removeLast(pcm.count - Int(total))
+        return pcm
+    }
+
+    /// synthesizePCM16 at `rate` (piper_hip_voice_synthesize_pcm16_rate).
+    public func synthesizePCM16(phonemeIDs: [Int64], durations: [Int32], noise: [Float]?, noiseScale: Float, rate: Int32, gain: Float = 1.0,
+                                normalize: Bool = false) throws -> [Int16] {
+        var n: Int64 = 0
+        var prm = piper_hip_pcm_params(gain: gain, normalize: normalize ? 1 : 0)
+        return try phonemeIDs.withUnsafeBufferPointer { ids in try durations.withUnsafeBufferPointer { dur in
+            try (noise ?? []).withUnsafeBufferPointer { nz in
+                var u = piper_hip_utterance(phoneme_ids: ids.baseAddress, t: Int32(ids.count), durations: dur.baseAddress,
+                                            noise: noise == nil ? nil : nz.baseAddress, noise_scale: noiseScale,
+                                            noise_mode: Int32(PIPER_HIP_NOISE_INJECTED), seed: 1234, length_scale: 1.0, noise_w: 0.8, dp_noise: nil)
+                var pcm = [Int16](repeating: 0, count: Int(try resampleCount(piper_hip_voice_num_samples(voice, &u), rate: rate)))
+                try HIPBackend.check(piper_hip_voice_synthesize_pcm16_rate(voice, &u, &prm, rate, &pcm, Int64(pcm.count), &n))
+                return pcm
+            }
+        } }
+    }
+
+    /// The output rate of the stream on `slot` (piper_hip_voice_stream_set_rate): after its begin / open, before its first step (a pool:
+    /// and its first join). The PCM steps then deliver at `rate`; the float steps are refused.
+    public func streamSetRate(slot: Int32, rate: Int32) throws {
+        try HIPBackend.check(piper_hip_voice_stream_set_rate(voice, slot, rate))
+    }
+
+    public func streamRate(slot: Int32) throws -> Int32 {
+        let r = piper_hip_voice_stream_rate(voice, slot)
+        if r < 0 { try HIPBackend.check(r) }
+        return r
+    }
+
+    /// The int16 samples one step of the stream on `slot` can deliver at its current rate (piper_hip_voice_stream_step_capacity).
+    public func streamStepCapacity(slot: Int32) throws -> Int {
+        let c = piper_hip_voice_stream_step_capacity(voice, slot)
+        if c < 0 { try HIPBackend.check(Int32(c)) }
+        return Int(c)
+    }
+
+    /// streamNextPCM16 / streamNextBatchPCM16 on a slot with an output rate: the buffer is sized by streamStepCapacity.
+    public func streamNextPCM16AtRate(slot: Int32, gain: Float = 1.0) throws -> [Int16] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: 0)
+        var buf = [Int16](repeating: 0, count: try streamStepCapacity(slot: slot))
+        var n: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_stream_next_pcm16(voice, slot, &prm, &buf, Int64(buf.count), &n))
+        return Array(buf[0..<Int(n)])
+    }
+
+    public func streamNextBatchPCM16AtRate(slot: Int32, rows: Int32, gain: Float = 1.0) throws -> [Int32: [Int16]] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: 0)
+        var buf = [Int16](repeating: 0, count: try streamStepCapacity(slot: slot))
+        var counts = [Int64](repeating: 0, count: Int(rows))
+        try HIPBackend.check(piper_hip_voice_stream_next_batch_pcm16(voice, slot, &prm, &buf, Int64(buf.count), &counts))
+        var out = [Int32: [Int16]](), off = 0
+        for (item, c) in counts.enumerated() where c > 0 {
+            out[Int32(item)] = Array(buf[off..<off + Int(c)])
+            off += Int(c)
+        }
+        return out
+    }
+
+    /// A mono WAV from samples that are 16-bit PCM already, at the rate they were delivered (piper_hip_wav_write_pcm16).
+    public func writeWav(pcm: [Int16], rate: Int32, to path: String) throws {
+        try HIPBackend.check(piper_hip_wav_write_pcm16(path, pcm, pcm.count, rate))
+    }
+
     /// WavFileWriter (Sources/PiperCLI/WavFileWriter.swift:20-60): float → int16 with the CLI's x·32767 clamp, RIFF header.
     public func writeWav(_ samples: [Float], to path: String) throws {
         try HIPBackend.check(piper_hip_wav_write(path, samples, samples.count, sampleRate))
