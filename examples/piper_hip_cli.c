@@ -14,6 +14,10 @@
  *                            --normalize applies Piper's peak normalisation (audio_float_to_int16). Both flags act on --output-raw only.
  *                            --output-rate N (8000 … 48000) resamples on the device (piper_hip_voice_collect_pcm16_rate): --output-raw is
  *                            then s16le at N Hz, and --output a WAV whose header carries N (piper_hip_wav_write_pcm16).
+ *                            --output-encoding s16le|mulaw|alaw (default s16le): G.711 bytes companded on the device
+ *                            (piper_hip_voice_collect_g711 / synthesize_g711) — --output-raw is then one byte per sample, --output a
+ *                            G.711 WAV at the output rate (piper_hip_wav_write_g711); combinable with --output-rate, --volume and
+ *                            --normalize (with a law the last two act on --output as well: the file holds the same bytes).
  * Without --model the synthetic voice of the tests is used (--quality medium|high|low|x_low; low and x_low are the 16 kHz tier); its duration predictor has random weights, so frames per id are
  * pinned to --pin-frames (3, the bench's convention) unless --predict asks for the predictor (the only mode a real voice has).
  *
@@ -112,12 +116,14 @@ static int run_one(runner* r, const int64_t* ids, int t, int64_t* samples) {
   return 0;
 }
 
-/* The utterance as 16-bit samples converted on the device. *pcm is malloc'ed; the caller frees it, after a failure too.
+/* The utterance as 16-bit samples converted on the device — law != 0: as G.711 bytes, through the _g711 twins of the calls named here.
+ * *pcm is malloc'ed; the caller frees it, after a failure too.
  * ran != 0: run_one has just run this utterance on slot 0 and its waveform is still in the plan, so piper_hip_voice_collect_pcm16 converts
  * that. Otherwise pinned durations go through piper_hip_voice_synthesize_pcm16 in one call; with --predict the length is the predictor's,
  * so the slot is prepared (once), asked for it, launched and collected as PCM. */
-static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_pcm_params* prm, int ran, int in_rate, int rate, int16_t** pcm,
+static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_pcm_params* prm, int ran, int in_rate, int rate, int law, void** pcm,
                          int64_t* samples) {
+  const size_t elem = law ? 1 : sizeof(int16_t);
   piper_hip_utterance u;
   memset(&u, 0, sizeof u);
   u.phoneme_ids = ids; u.t = t; u.noise_scale = r->noise_scale; u.seed = 1234;
@@ -132,17 +138,20 @@ static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_p
     cap = piper_hip_voice_num_samples(r->voice, &u);
     if (cap >= 0 && rate != in_rate) cap = piper_hip_resample_count(in_rate, rate, cap);
     rc = cap < 0 ? (int)cap : 0;
-    if (!rc) *pcm = (int16_t*)malloc(sizeof(int16_t) * (size_t)(cap > 0 ? cap : 1));
-    if (!rc) rc = piper_hip_voice_synthesize_pcm16_rate(r->voice, &u, prm, rate, *pcm, cap, samples);
+    if (!rc) *pcm = malloc(elem * (size_t)(cap > 0 ? cap : 1));
+    if (!rc) rc = law ? piper_hip_voice_synthesize_g711(r->voice, &u, prm, law, rate, (uint8_t*)*pcm, cap, samples)
+                      : piper_hip_voice_synthesize_pcm16_rate(r->voice, &u, prm, rate, (int16_t*)*pcm, cap, samples);
     free(dur);
     return rc;
   }
   if (!ran && (rc = piper_hip_voice_prepare(r->voice, &u, 0)) < 0) return rc;
   if ((rc = piper_hip_voice_prepared_samples(r->voice, 0, NULL, 0, &cap)) < 0) return rc;
   if (rate != in_rate && (cap = piper_hip_resample_count(in_rate, rate, cap)) < 0) return (int)cap;
-  *pcm = (int16_t*)malloc(sizeof(int16_t) * (size_t)(cap > 0 ? cap : 1));
+  *pcm = malloc(elem * (size_t)(cap > 0 ? cap : 1));
   if (!ran && (rc = piper_hip_voice_launch(r->voice, 0)) < 0) return rc;
-  if ((rc = piper_hip_voice_collect_pcm16_rate(r->voice, 0, prm, rate, *pcm, cap)) < 0) return rc;
+  rc = law ? piper_hip_voice_collect_g711(r->voice, 0, prm, law, rate, (uint8_t*)*pcm, cap)
+           : piper_hip_voice_collect_pcm16_rate(r->voice, 0, prm, rate, (int16_t*)*pcm, cap);
+  if (rc < 0) return rc;
   *samples = cap;
   return 0;
 }
@@ -160,9 +169,13 @@ int main(int argc, char** argv) {
   }
   const int scale_bench = has_flag(argc, argv, "--scale-bench");
   const char* ids_arg = arg_value(argc, argv, "--phoneme-ids");
+  const char* enc = arg_value(argc, argv, "--output-encoding");
+  const int law = !enc || strcmp(enc, "s16le") == 0 ? 0 : strcmp(enc, "mulaw") == 0 ? PIPER_HIP_G711_MULAW : strcmp(enc, "alaw") == 0 ? PIPER_HIP_G711_ALAW : -1;
+  if (law < 0) { fprintf(stderr, "--output-encoding %s: expected s16le, mulaw or alaw\n", enc); return 2; }
   if (!scale_bench && !ids_arg) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
+                    "                [--output-encoding s16le|mulaw|alaw]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n", argv[0], argv[0]);
     return 2;
   }
@@ -221,36 +234,43 @@ int main(int argc, char** argv) {
     int64_t n = 0;
     double gpu = 0.0;
     const int rate = arg_value(argc, argv, "--output-rate") ? atoi(arg_value(argc, argv, "--output-rate")) : cfg.sample_rate;
+    piper_hip_pcm_params prm;
+    prm.gain = arg_value(argc, argv, "--volume") ? (float)atof(arg_value(argc, argv, "--volume")) : 1.0f;
+    prm.normalize = has_flag(argc, argv, "--normalize");
     if (out) {
       CHECK(run_one(&r, ids, t, &n));
       CHECK(piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu));
-      if (rate == cfg.sample_rate) {
+      if (law) { /* the slot that ran, companded (and resampled) on the device */
+        void* wg = NULL;
+        int wrc = run_one_pcm16(&r, ids, t, &prm, 1, cfg.sample_rate, rate, law, &wg, &n);
+        if (wrc >= 0) wrc = piper_hip_wav_write_g711(out, law, (const uint8_t*)wg, (size_t)n, rate);
+        free(wg); /* after a failure too */
+        CHECK(wrc);
+      } else if (rate == cfg.sample_rate) {
         CHECK(piper_hip_wav_write(out, r.audio, (size_t)n, cfg.sample_rate));
       } else { /* the slot that ran, resampled and converted on the device */
-        int16_t* wpcm = NULL;
-        CHECK(run_one_pcm16(&r, ids, t, NULL, 1, cfg.sample_rate, rate, &wpcm, &n));
-        CHECK(piper_hip_wav_write_pcm16(out, wpcm, (size_t)n, rate));
-        free(wpcm);
+        void* wpcm = NULL;
+        int wrc = run_one_pcm16(&r, ids, t, NULL, 1, cfg.sample_rate, rate, 0, &wpcm, &n);
+        if (wrc >= 0) wrc = piper_hip_wav_write_pcm16(out, (const int16_t*)wpcm, (size_t)n, rate);
+        free(wpcm); /* after a failure too */
+        CHECK(wrc);
       }
       fprintf(stderr, "%lld samples (%.3f s at %d Hz), %.3f ms on the GPU -> %s\n", (long long)n, (double)n / rate, rate, gpu, out);
     }
-    if (out_raw) { /* s16le, the samples converted on the device */
-      piper_hip_pcm_params prm;
-      prm.gain = arg_value(argc, argv, "--volume") ? (float)atof(arg_value(argc, argv, "--volume")) : 1.0f;
-      prm.normalize = has_flag(argc, argv, "--normalize");
-      int16_t* pcm = NULL;
+    if (out_raw) { /* s16le or G.711 bytes, the samples converted on the device */
+      void* pcm = NULL;
       int failed = 0;
-      const int prc = run_one_pcm16(&r, ids, t, &prm, out != NULL, cfg.sample_rate, rate, &pcm, &n);
+      const int prc = run_one_pcm16(&r, ids, t, &prm, out != NULL, cfg.sample_rate, rate, law, &pcm, &n);
       if (prc < 0) {
         fprintf(stderr, "--output-raw failed (%d): %s\n", prc, piper_hip_last_error());
         failed = 1;
       } else {
         (void)piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu);
         FILE* fr = fopen(out_raw, "wb");
-        failed = !fr || fwrite(pcm, sizeof(int16_t), (size_t)n, fr) != (size_t)n;
+        failed = !fr || fwrite(pcm, law ? 1 : sizeof(int16_t), (size_t)n, fr) != (size_t)n;
         if (fr && fclose(fr) != 0) failed = 1;
         if (failed) fprintf(stderr, "cannot write %s\n", out_raw);
-        else fprintf(stderr, "%lld samples (%.3f s at %d Hz) as s16le, %.3f ms on the GPU -> %s\n", (long long)n, (double)n / rate, rate, gpu, out_raw);
+        else fprintf(stderr, "%lld samples (%.3f s at %d Hz) as %s, %.3f ms on the GPU -> %s\n", (long long)n, (double)n / rate, rate, enc ? enc : "s16le", gpu, out_raw);
       }
       free(pcm);
       if (failed) { /* leave as the success path does */

@@ -606,6 +606,62 @@ int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot);
 /* The int16 samples one step of that slot can deliver at its current rate (rows × the per-row bound), or a negative status. */
 int64_t piper_hip_voice_stream_step_capacity(piper_hip_voice* v, int slot);
 
+/* ---- G.711 output: μ-law and A-law bytes from the device (DESIGN.md §4 "G.711 output") ----
+ * A telephony consumer (RTP PCMU / PCMA, a SIP trunk) takes one G.711 byte per sample, not s16le. These entry points compand on the
+ * device, in the kernels that write int16 otherwise, and transfer the bytes: half of what the PCM path carries and no companding pass on
+ * the host. A byte is a pure function of the int16 sample the contracts above define: byte = law(s), s exactly what the 16-bit PCM
+ * contract gives for that sample — normalize 0 or 1, with gain, at the voice's rate or resampled. Nothing about s changes. `>>` is an
+ * arithmetic shift on a 32-bit int:
+ *   μ-law   v = s >> 2;  neg = v < 0;  m = min(neg ? −v : v, 8159) + 33                      (33 … 8192)
+ *           seg  = how many of {0x3F,0x7F,0xFF,0x1FF,0x3FF,0x7FF,0xFFF,0x1FFF} are < m        (0 … 8)
+ *           code = seg == 8 ? 0x7F : (seg << 4) | ((m >> (seg + 1)) & 15)
+ *           byte = code ^ (neg ? 0x7F : 0xFF)
+ *   A-law   v = s >> 3;  neg = v < 0;  m = neg ? −v − 1 : v                                  (0 … 4095)
+ *           seg  = how many of {0x1F,0x3F,0x7F,0xFF,0x1FF,0x3FF,0x7FF,0xFFF} are < m          (0 … 7)
+ *           code = (seg << 4) | ((m >> (seg < 2 ? 1 : seg)) & 15)
+ *           byte = code ^ (neg ? 0x55 : 0xD5)
+ * This is the definition of Sun's g711.c, which CPython's audioop.lin2ulaw / lin2alaw (width 2) implement; the tests compare against
+ * tables made with audioop on all 65 536 inputs. It is NOT the one's-complement variant of ITU-T G.191, which differs on some negative
+ * inputs: here μ(−1) = μ(−4) = 0x7E. Known answers (μ, A): 0 → 0xFF, 0xD5; −1 → 0x7E, 0x55; 32767 → 0x80, 0xAA; −32768 → 0x00, 0x2A.
+ * μ-law produces 255 distinct codes (never 0x7F), A-law all 256.
+ * Decoding is host only, for consumers and tests:
+ *   μ-law   u = ~b & 0xFF;  t = (((u & 15) << 3) + 0x84) << ((u & 0x70) >> 4);  s = (u & 0x80) ? 0x84 − t : t − 0x84
+ *   A-law   a = b ^ 0x55;  t = (a & 15) << 4;  seg = (a & 0x70) >> 4;
+ *           t = seg == 0 ? t + 8 : seg == 1 ? t + 0x108 : (t + 0x108) << (seg − 1);  s = (a & 0x80) ? t : −t
+ * A law that is neither constant is PIPER_HIP_ERR_ARG everywhere. */
+#define PIPER_HIP_G711_MULAW 1
+#define PIPER_HIP_G711_ALAW  2
+/* Host-only (no device needed): n int16 samples → n bytes, and back. n may be 0. */
+int piper_hip_g711_from_pcm16(int law, const int16_t* pcm, size_t n, uint8_t* out);
+int piper_hip_g711_to_pcm16(int law, const uint8_t* in, size_t n, int16_t* pcm);
+/* A mono G.711 WAV file: an 18-byte fmt chunk (format tag 7 for μ-law, 6 for A-law, 1 channel, byte rate = sample rate, block align 1,
+ * 8 bits, cbSize 0), a fact chunk holding n, the data chunk with a pad byte behind it when n is odd; the RIFF size counts all of it. */
+int piper_hip_wav_write_g711(const char* path, int law, const uint8_t* bytes, size_t n, int32_t sample_rate);
+/* Per-op: `count` device floats at in_rate → J(count) device bytes at out_rate, law(int16 of y·gain) with the normalize == 0 arithmetic.
+ * `*out` convention of the other ops; a caller-supplied `*out` may sit at any byte address. *out_count (may be NULL) receives J(count).
+ * in_rate == out_rate (> 0) is not a filter: the rates are not looked up in the list and the bytes are law(·) of what
+ * piper_hip_pcm16_f32 gives. Otherwise the rate rules and status codes are those of piper_hip_resample_pcm16_f32. count may be 0. */
+int piper_hip_g711_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t in_rate, int32_t out_rate, float gain, int law, uint8_t** out,
+                       size_t* out_count, piper_hip_stream stream);
+/* collect_pcm16_rate / synthesize_pcm16_rate with G.711 bytes, every rule carried over: plain, ragged and bounded slots, the items back to
+ * back at J(true length) (an item may start at any byte), the bounded slot's collecting call, any order with collect, collect_pcm16 and
+ * collect_pcm16_rate (the fp32 audio stays in the plan), normalize = 1 with piper_hip_voice_peaks afterwards. out_rate equal to the
+ * voice's rate is not a filter. max_samples and *n_samples count samples, which are bytes here. */
+int piper_hip_voice_collect_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, int32_t out_rate, uint8_t* host,
+                                 int64_t max_samples);
+int piper_hip_voice_synthesize_g711(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int law,
+                                    int32_t out_rate, uint8_t* host, int64_t max_samples, int64_t* n_samples);
+/* stream_next_pcm16 / stream_next_batch_pcm16 (single streams, groups and pools) with G.711 bytes. The law is an argument of the step, not
+ * state of the slot; the rate is what stream_set_rate set, or the voice's own. A G.711 step consumes the step exactly as a PCM step does —
+ * the same output range [j0, j1), the same history update — so PCM and G.711 steps may alternate on one stream, and on a slot at the
+ * voice's own rate float steps as well. n_samples[i] counts samples (= bytes); piper_hip_voice_stream_step_capacity answers for these
+ * steps too. Refused calls follow the PCM steps and consume nothing: normalize = 1 is PIPER_HIP_ERR_UNSUPPORTED, a short buffer
+ * PIPER_HIP_ERR_SHAPE, host == NULL on a slot with an output rate PIPER_HIP_ERR_ARG, a bad law PIPER_HIP_ERR_ARG. */
+int piper_hip_voice_stream_next_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
+                                     int64_t max_samples, int64_t* n_samples);
+int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
+                                           int64_t max_samples, int64_t* n_samples);
+
 /* Debug taps ⇔ GraphExecutor.execute(maxNodeIndex:) returning intermediates (GraphExecutor.swift:75-152):
  * copy a named intermediate of the slot's last run to host. Names: "enc_out" [H,T], "m_p" [inter,T],
  * "logs_p" [inter,T], "z_p" [inter,F], "z" [inter,F], "dec_pre" [up_initial,F] — per batch item, compacted to the item's

@@ -10,10 +10,12 @@ namespace ph {
 enum { kDescSrc = 0, kDescA, kDescFc, kDescSkip, kDescN, kDescOff, kDescInts };
 
 // The conversion of one sample (pcm16.hip tells the contract), shared with the resampling kernels (resample.hip): norm == 0 is the reference
-// mode on x·gain, norm == 1 the peak mode with `scale` = fp32(32767 / max(0.01, peak)).
+// mode on x·gain, norm == 1 the peak mode with `scale` = fp32(32767 / max(0.01, peak)). law: the G.711 law of a kernel whose sink is one
+// byte per sample (PIPER_HIP_G711_MULAW / _ALAW, uniform per launch); the int16 and fp32 sinks do not read it.
 struct PcmCvt {
   float gain, scale;
   int norm;
+  int law;
 };
 
 __device__ __forceinline__ int pcm_cvt(float x, const PcmCvt c) {
@@ -32,6 +34,28 @@ __device__ __forceinline__ unsigned pcm_pair(float lo, float hi, const PcmCvt c)
   return ((unsigned)pcm_cvt(lo, c) & 0xffffu) | ((unsigned)pcm_cvt(hi, c) << 16);  // little-endian: the first sample in the low half
 }
 
+// int16 sample → G.711 byte (include/piper_hip.h "G.711 output": the Sun g711.c definition), branch-free. The segment is the bit length of
+// the biased magnitude instead of a table search: μ-law m = min(|s >> 2|, 8159) + 33 lies in [33, 8192], seg = ⌊log2 m⌋ − 5, and seg 8
+// (m = 8192 only) yields 0x80, which the min turns into the clip code 0x7F; A-law m = s >> 3 with the sign's bits flipped (−v − 1) lies in
+// [0, 4095], seg = max(0, bitlen(m) − 5), the mantissa shift is max(seg, 1). The sign is bit 7 of the mask.
+__device__ __forceinline__ unsigned g711_cvt(int s, int law) {
+  const bool alaw = law == PIPER_HIP_G711_ALAW;
+  const int v = s >> (alaw ? 3 : 2);
+  const int sgn = v >> 31;  // 0 or −1
+  const int m = alaw ? (v ^ sgn) : min((v ^ sgn) - sgn, 8159) + 33;
+  const int bl = 32 - __clz(m | 1);  // bit length (m | 1: 0 counts as one bit, every other m is unchanged in length)
+  const int seg = alaw ? max(bl - 5, 0) : bl - 6;
+  const int sh = alaw ? max(seg, 1) : seg + 1;
+  const int code = min((seg << 4) | ((m >> sh) & 15), 0x7F);
+  return (unsigned)(code ^ (alaw ? 0xD5 : 0xFF) ^ (sgn & 0x80));
+}
+
+// four samples → four bytes, the first in the low byte (little-endian)
+__device__ __forceinline__ unsigned g711_quad(float a, float b, float c2, float d, const PcmCvt c) {
+  return g711_cvt(pcm_cvt(a, c), c.law) | (g711_cvt(pcm_cvt(b, c), c.law) << 8) | (g711_cvt(pcm_cvt(c2, c), c.law) << 16) |
+         (g711_cvt(pcm_cvt(d, c), c.law) << 24);
+}
+
 // frames of an item as the device reports them, clamped to the plan's row
 __device__ __forceinline__ int clamp_len(int len, int F) { return min(max(len, 0), F); }
 
@@ -39,14 +63,15 @@ __device__ __forceinline__ int clamp_len(int len, int F) { return min(max(len, 0
 // item b at hop·Σ_{i<b} lensF[i]; lengths are read from device memory and clamped to F, so at most NB·F·hop samples are written.
 // peaks == nullptr: the reference conversion of x·gain. peaks != nullptr ([NB], from launch_pcm16_peak): peak normalisation per item;
 // peaks_host (optional, host mapping) then receives a copy of the peaks. NB ≤ 256.
+// law (here and below): 0 = `out` is int16_t*; PIPER_HIP_G711_MULAW / _ALAW = `out` is uint8_t*, one byte per sample, at any byte address.
 hipError_t launch_pcm16_pack(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, float gain,
-                             const float* peaks, float* peaks_host, int16_t* out);
+                             const float* peaks, float* peaks_host, void* out, int law);
 // peaks[b] = max |x| over item b's true samples (NaN ignored, 0 for an empty item). Zeroes `peaks` first (stream-ordered).
 hipError_t launch_pcm16_peak(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, float* peaks);
 // n contiguous samples, the reference conversion of x·gain
-hipError_t launch_pcm16_flat(hipStream_t q, const float* x, int64_t n, float gain, int16_t* out, int num_cus);
-// stream_chunk_pack_kernel with int16 output: same descriptor, same grid
+hipError_t launch_pcm16_flat(hipStream_t q, const float* x, int64_t n, float gain, void* out, int law, int num_cus);
+// stream_chunk_pack_kernel with int16 or G.711 output: same descriptor, same grid
 hipError_t launch_stream_chunk_pack_pcm16(hipStream_t q, int px, int NBg, const float* audio, int64_t row, const int* desc, float gain,
-                                          int16_t* out);
+                                          void* out, int law);
 
 }  // namespace ph

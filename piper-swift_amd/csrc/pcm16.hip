@@ -11,6 +11,11 @@
 // Memory: every kernel here moves each sample once — 16-byte loads, one 16-byte (8 samples) or 8-byte (4 samples) store where source and
 // destination are aligned (with hop = 256 every item of a voice path is), scalar otherwise and for the tail. The destination may be a
 // page-locked host buffer seen through its device mapping: the stores then ARE the transfer.
+//
+// G.711 (include/piper_hip.h "G.711 output"): the same kernels with a one-byte sink — the sample type is their template parameter, the law
+// travels in PcmCvt. 16 samples leave as one 16-byte store where source and destination are aligned, four as one dword behind a head of
+// up to three byte stores otherwise; no store covers a byte outside the span, because the neighbouring bytes of a packed output belong to
+// another item whose block writes them at the same time.
 #include "pcm16.h"
 
 #include <algorithm>
@@ -46,11 +51,46 @@ __device__ __forceinline__ void pcm_span(const float* __restrict__ src, int16_t*
   for (int64_t i = done + tid; i < n; i += nth) dst[i] = (int16_t)pcm_cvt(src[i], c);
 }
 
+// the same with one G.711 byte per sample (c.law), dst at any byte address
+__device__ __forceinline__ void pcm_span(const float* __restrict__ src, uint8_t* __restrict__ dst, int64_t n, int64_t tid, int64_t nth,
+                                         const PcmCvt c) {
+  const int64_t head = min(n, (int64_t)((4 - ((uintptr_t)dst & 3)) & 3));  // byte stores up to the first 4-byte-aligned address
+  for (int64_t i = tid; i < head; i += nth) dst[i] = (uint8_t)g711_cvt(pcm_cvt(src[i], c), c.law);
+  const float* s = src + head;
+  uint8_t* d = dst + head;
+  const int64_t m = n - head;
+  const bool src16 = ((uintptr_t)s & 15) == 0;
+  int64_t done = 0;
+  if (src16 && ((uintptr_t)d & 15) == 0) {
+    const int64_t n16 = m >> 4;
+    for (int64_t i = tid; i < n16; i += nth) {
+      const float4 a = ((const float4*)s)[4 * i], b = ((const float4*)s)[4 * i + 1], e = ((const float4*)s)[4 * i + 2], f = ((const float4*)s)[4 * i + 3];
+      uint4 o;
+      o.x = g711_quad(a.x, a.y, a.z, a.w, c); o.y = g711_quad(b.x, b.y, b.z, b.w, c);
+      o.z = g711_quad(e.x, e.y, e.z, e.w, c); o.w = g711_quad(f.x, f.y, f.z, f.w, c);
+      ((uint4*)d)[i] = o;
+    }
+    done = n16 << 4;
+  } else {
+    const int64_t n4 = m >> 2;
+    for (int64_t i = tid; i < n4; i += nth) {
+      float4 a;
+      if (src16) a = ((const float4*)s)[i];
+      else { a.x = s[4 * i]; a.y = s[4 * i + 1]; a.z = s[4 * i + 2]; a.w = s[4 * i + 3]; }
+      ((unsigned*)d)[i] = g711_quad(a.x, a.y, a.z, a.w, c);
+    }
+    done = n4 << 2;
+  }
+  for (int64_t i = done + tid; i < m; i += nth) d[i] = (uint8_t)g711_cvt(pcm_cvt(s[i], c), c.law);
+}
+
 // Plan audio [NB][row] → the items back to back at their true lengths. blockIdx.y = item; the item's offset is the sum of the lengths
 // before it (NB ≤ 256 = one per thread), so plain, ragged and bounded slots — whose lengths only the device knows — take the same launch.
+// T: int16_t, or uint8_t for G.711 by `law`.
+template <class T>
 __global__ __launch_bounds__(256) void pcm16_pack_kernel(const float* __restrict__ audio, int64_t row, const int* __restrict__ lensF, int F, int hop,
                                                          float gain, const float* __restrict__ peaks, float* __restrict__ peaks_host,
-                                                         int16_t* __restrict__ out) {
+                                                         T* __restrict__ out, int law) {
   __shared__ int part[4];
   const int b = blockIdx.y, tid = threadIdx.x;
   int before = tid < b ? clamp_len(lensF[tid], F) : 0;
@@ -60,7 +100,7 @@ __global__ __launch_bounds__(256) void pcm16_pack_kernel(const float* __restrict
   const int64_t at = (int64_t)(part[0] + part[1] + part[2] + part[3]) * hop;
   const int64_t n = (int64_t)clamp_len(lensF[b], F) * hop;
   PcmCvt c;
-  c.gain = gain; c.scale = 1.0f; c.norm = 0;
+  c.gain = gain; c.scale = 1.0f; c.norm = 0; c.law = law;
   if (peaks) {
     const float peak = peaks[b];
     c.scale = (float)(32767.0 / (double)fmaxf(0.01f, peak));
@@ -99,21 +139,23 @@ __global__ __launch_bounds__(256) void pcm16_peak_kernel(const float* __restrict
   }
 }
 
-__global__ __launch_bounds__(256) void pcm16_flat_kernel(const float* __restrict__ x, int64_t n, float gain, int16_t* __restrict__ out) {
+template <class T>
+__global__ __launch_bounds__(256) void pcm16_flat_kernel(const float* __restrict__ x, int64_t n, float gain, T* __restrict__ out, int law) {
   PcmCvt c;
-  c.gain = gain; c.scale = 1.0f; c.norm = 0;
+  c.gain = gain; c.scale = 1.0f; c.norm = 0; c.law = law;
   pcm_span(x, out, n, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256, c);
 }
 
-// stream_chunk_pack_kernel (voice.hip) with int16 output: each active row's chunk out of the generator plan's audio [NBg][row], the halo
-// samples dropped, packed back to back at the descriptor's offsets.
+// stream_chunk_pack_kernel (voice.hip) with int16 or G.711 output: each active row's chunk out of the generator plan's audio [NBg][row], the
+// halo samples dropped, packed back to back at the descriptor's offsets.
+template <class T>
 __global__ __launch_bounds__(256) void stream_chunk_pack_pcm16_kernel(const float* __restrict__ audio, int64_t row, const int* __restrict__ desc,
-                                                                      float gain, int16_t* __restrict__ out) {
+                                                                      float gain, T* __restrict__ out, int law) {
   const int* d = desc + blockIdx.y * kDescInts;
   const int n = d[kDescN];
   if (n == 0) return;
   PcmCvt c;
-  c.gain = gain; c.scale = 1.0f; c.norm = 0;
+  c.gain = gain; c.scale = 1.0f; c.norm = 0; c.law = law;
   pcm_span(audio + (int64_t)blockIdx.y * row + d[kDescSkip], out + d[kDescOff], n, (int64_t)blockIdx.x * 256 + threadIdx.x,
            (int64_t)gridDim.x * 256, c);
 }
@@ -124,10 +166,14 @@ int span_blocks(int64_t samples, int per_thread) { return (int)std::min<int64_t>
 }  // namespace
 
 hipError_t launch_pcm16_pack(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, float gain,
-                             const float* peaks, float* peaks_host, int16_t* out) {
+                             const float* peaks, float* peaks_host, void* out, int law) {
   if (NB < 1 || NB > 256) return hipErrorInvalidValue;  // the offset of an item is summed by one block of 256 threads
-  hipLaunchKernelGGL(pcm16_pack_kernel, dim3(span_blocks((int64_t)F * hop, 8), NB), dim3(256), 0, q, audio, row, lensF, F, hop, gain, peaks,
-                     peaks_host, out);
+  if (law)
+    hipLaunchKernelGGL(pcm16_pack_kernel<uint8_t>, dim3(span_blocks((int64_t)F * hop, 16), NB), dim3(256), 0, q, audio, row, lensF, F, hop, gain,
+                       peaks, peaks_host, (uint8_t*)out, law);
+  else
+    hipLaunchKernelGGL(pcm16_pack_kernel<int16_t>, dim3(span_blocks((int64_t)F * hop, 8), NB), dim3(256), 0, q, audio, row, lensF, F, hop, gain,
+                       peaks, peaks_host, (int16_t*)out, 0);
   return hipGetLastError();
 }
 
@@ -139,20 +185,22 @@ hipError_t launch_pcm16_peak(hipStream_t q, const float* audio, int64_t row, con
   return hipGetLastError();
 }
 
-hipError_t launch_pcm16_flat(hipStream_t q, const float* x, int64_t n, float gain, int16_t* out, int num_cus) {
+hipError_t launch_pcm16_flat(hipStream_t q, const float* x, int64_t n, float gain, void* out, int law, int num_cus) {
   const int64_t cap = (int64_t)num_cus * 8;
-  const int grid = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256 * 8), 1), cap);
-  hipLaunchKernelGGL(pcm16_flat_kernel, dim3(grid), dim3(256), 0, q, x, n, gain, out);
+  const int grid = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256 * (law ? 16 : 8)), 1), cap);
+  if (law) hipLaunchKernelGGL(pcm16_flat_kernel<uint8_t>, dim3(grid), dim3(256), 0, q, x, n, gain, (uint8_t*)out, law);
+  else hipLaunchKernelGGL(pcm16_flat_kernel<int16_t>, dim3(grid), dim3(256), 0, q, x, n, gain, (int16_t*)out, 0);
   return hipGetLastError();
 }
 
 hipError_t launch_stream_chunk_pack_pcm16(hipStream_t q, int px, int NBg, const float* audio, int64_t row, const int* desc, float gain,
-                                          int16_t* out) {
-  hipLaunchKernelGGL(stream_chunk_pack_pcm16_kernel, dim3(px, NBg), dim3(256), 0, q, audio, row, desc, gain, out);
+                                          void* out, int law) {
+  if (law) hipLaunchKernelGGL(stream_chunk_pack_pcm16_kernel<uint8_t>, dim3(px, NBg), dim3(256), 0, q, audio, row, desc, gain, (uint8_t*)out, law);
+  else hipLaunchKernelGGL(stream_chunk_pack_pcm16_kernel<int16_t>, dim3(px, NBg), dim3(256), 0, q, audio, row, desc, gain, (int16_t*)out, 0);
   return hipGetLastError();
 }
 
-namespace { PH_WARM(pcm16, pcm16_pack_kernel); }
+namespace { PH_WARM(pcm16, pcm16_pack_kernel<int16_t>); }
 
 }  // namespace ph
 
@@ -172,6 +220,6 @@ PH_EXPORT int piper_hip_pcm16_f32(piper_hip_ctx* ctx, const float* x, size_t cou
   }
   if (count == 0) return PIPER_HIP_OK;
   StreamScope ss(ctx, stream);
-  (void)launch_pcm16_flat(ss.s, x, (int64_t)count, gain == 0.0f ? 1.0f : gain, *out, ctx->num_cus);
+  (void)launch_pcm16_flat(ss.s, x, (int64_t)count, gain == 0.0f ? 1.0f : gain, *out, 0, ctx->num_cus);
   return ss.finish("pcm16_f32");
 }

@@ -36,12 +36,14 @@ struct RsStepRow {
 };
 
 // Items of plan audio [NB][row] → back to back at J(lensF[b]·hop) samples each (lengths read from device memory and clamped to F), item b
-// at Σ_{i<b} J(·). out_f32 != nullptr: the fp32 y; otherwise int16 into out_pcm through the PCM contract — gain, and peak normalisation
-// per item when peaks != nullptr, as launch_pcm16_pack. lensF == nullptr: one item of n_flat contiguous samples (NB = 1). NB ≤ 256.
+// at Σ_{i<b} J(·). elem = bytes of a sample of `out`: 4 the fp32 y; 2 int16 through the PCM contract — gain, and peak normalisation per
+// item when peaks != nullptr, as launch_pcm16_pack; 1 the G.711 byte of that int16 by `law` (PIPER_HIP_G711_*), `out` at any byte address.
+// lensF == nullptr: one item of n_flat contiguous samples (NB = 1). NB ≤ 256.
 hipError_t launch_resample_items(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, int64_t n_flat,
-                                 const RsFilter& f, float gain, const float* peaks, float* peaks_host, int16_t* out_pcm, float* out_f32);
-// One stream step: every row's outputs packed at the descriptor's offsets as int16; hist_old / hist_new are [NBg][kRsHist] (read / written).
+                                 const RsFilter& f, float gain, const float* peaks, float* peaks_host, void* out, int elem, int law);
+// One stream step: every row's outputs packed at the descriptor's offsets as int16 (law 0) or G.711 bytes; hist_old / hist_new are
+// [NBg][kRsHist] (read / written).
 hipError_t launch_resample_step(hipStream_t q, int NBg, int max_count, const float* audio, int64_t row, const RsStepRow* desc,
-                                const float* hist_old, float* hist_new, const RsFilter& f, float gain, int16_t* out);
+                                const float* hist_old, float* hist_new, const RsFilter& f, float gain, void* out, int law);
 
 }  // namespace ph

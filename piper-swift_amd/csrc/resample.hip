@@ -10,7 +10,8 @@
 //
 // A block is one row by a tile of consecutive outputs: the tile's input span (tile · M / L + P samples) is staged into LDS once, by 16-byte
 // loads where the source is aligned, zeros (outside the item) and the stream's history (before the chunk) resolved while staging; every
-// thread then runs the P-term sums of its outputs out of LDS, two adjacent outputs per thread so that int16 leaves in 4-byte stores.
+// thread then runs the P-term sums of its outputs out of LDS, two adjacent outputs per thread so that int16 leaves in 4-byte stores — four
+// where the sink is one G.711 byte per sample (include/piper_hip.h "G.711 output"), which then leave as one dword as well.
 // Coefficients come from the table in global memory (at most 121 KB, cache-resident), through LDS when L ≤ 3. Nothing is atomic or
 // order-dependent. The destination may be a page-locked host buffer seen through its device mapping.
 #include "resample.h"
@@ -24,7 +25,10 @@
 namespace ph {
 namespace {
 
-constexpr int kRsTile = 1024;       // outputs per tile: two pairs per thread
+constexpr int kRsTile = 1024;       // outputs per tile: two pairs per thread (int16, fp32), one quad per thread (G.711 bytes)
+constexpr int kRsTileMin = 64;      // rs_geometry halves the tile down to this at most; a thread's pair or quad never straddles a tile
+static_assert(kRsTile % 4 == 0 && kRsTileMin % 4 == 0 && kRsTile % kRsTileMin == 0 && ((kRsTile / kRsTileMin) & (kRsTile / kRsTileMin - 1)) == 0,
+              "every tile rs_geometry can choose is a multiple of 4: a byte quad is one aligned dword inside one tile");
 constexpr int kRsLdsPhases = 3;     // the table goes through LDS up to this many phases
 constexpr size_t kRsLdsMax = 64 << 10;  // LDS of a block: the tile is halved before this is exceeded (two blocks per CU hold 80 KB each)
 
@@ -47,17 +51,22 @@ __device__ __forceinline__ float rs_at(const RsSrc& r, int64_t g) {
 // LDS floats of a block: the table when it is staged, then the tile's input span
 __host__ __device__ inline int rs_coef_floats(int L, int P) { return L <= kRsLdsPhases ? (L * P + 3) & ~3 : 0; }
 
-// The row's outputs → dst[0 … count): F32 = fp32 y, else int16 through `c`. CL: the table has been staged into LDS.
-// Outputs are numbered v = (j − j0) + lead with lead = 1 when dst is 2- but not 4-byte aligned, so that an even v is a 4-byte-aligned
-// int16 address: a thread owns the pair (v, v + 1) and stores it as one word where both are outputs.
-template <bool F32, bool CL>
+// The row's outputs → dst[0 … count). E = bytes of an output: 4 = fp32 y, 2 = int16 through `c`, 1 = the G.711 byte (c.law) of that int16.
+// CL: the table has been staged into LDS.
+// Outputs are numbered v = (j − j0) + lead, lead = the elements between dst and the 4-byte-aligned address at or below it (int16: 0 or 1,
+// bytes: dst & 3), so that a v which is a multiple of W = 4 / E (fp32: 2) is a 4-byte-aligned address: a thread owns the W outputs
+// (v … v + W − 1) and stores them as one word where all are outputs of this row, one by one at the row's head and tail — the bytes beside
+// them belong to another row of a packed output, which another block writes at the same time.
+template <int E, bool CL>
 __device__ __forceinline__ void rs_row(const RsSrc r, const RsFilter f, const PcmCvt c, void* dst, int tile, float* lds) {
+  constexpr bool F32 = E == 4;
+  constexpr int W = E == 1 ? 4 : 2;
   if (r.count <= 0) return;  // (the whole block: an empty item)
   const int tid = threadIdx.x, half = f.P >> 1;
   float* xs = lds + rs_coef_floats(f.L, f.P);
   if (CL)
     for (int i = tid; i < f.L * f.P; i += 256) lds[i] = f.taps[i];  // (the first tile's barrier covers it)
-  const int lead = F32 ? 0 : (int)(((uintptr_t)dst >> 1) & 1);
+  const int lead = F32 ? 0 : E == 2 ? (int)(((uintptr_t)dst >> 1) & 1) : (int)((uintptr_t)dst & 3);
   const int64_t vend = r.count + lead;
   for (int64_t v0 = (int64_t)blockIdx.x * tile; v0 < vend; v0 += (int64_t)gridDim.x * tile) {
     const int64_t ja = r.j0 + (v0 > lead ? v0 - lead : 0), jb = r.j0 + (v0 + tile < vend ? v0 + tile : vend) - lead;  // the tile's outputs [ja, jb)
@@ -80,12 +89,12 @@ __device__ __forceinline__ void rs_row(const RsSrc r, const RsFilter f, const Pc
       *(float4*)(xs + 4 * q) = v;
     }
     __syncthreads();
-    for (int q = tid; q < (tile >> 1); q += 256) {
-      const int64_t v = v0 + 2 * q;
-      float y[2] = {0.0f, 0.0f};
-      bool ok[2];
+    for (int q = tid; q < tile / W; q += 256) {
+      const int64_t v = v0 + W * q;
+      float y[W] = {};
+      bool ok[W];
 #pragma unroll
-      for (int k = 0; k < 2; k++) {
+      for (int k = 0; k < W; k++) {
         ok[k] = v + k >= lead && v + k < vend;
         if (!ok[k]) continue;
         const int64_t j = r.j0 + v + k - lead;
@@ -101,15 +110,23 @@ __device__ __forceinline__ void rs_row(const RsSrc r, const RsFilter f, const Pc
         }
         y[k] = acc;
       }
-      const int64_t o = v - lead;  // index of the pair's first sample in dst
+      const int64_t o = v - lead;  // index of the thread's first sample in dst
       if (F32) {
         if (ok[0]) ((float*)dst)[o] = y[0];
         if (ok[1]) ((float*)dst)[o + 1] = y[1];
-      } else if (ok[0] && ok[1]) {
-        *(unsigned*)((int16_t*)dst + o) = pcm_pair(y[0], y[1], c);
+      } else if (E == 2) {
+        if (ok[0] && ok[1]) {
+          *(unsigned*)((int16_t*)dst + o) = pcm_pair(y[0], y[1], c);
+        } else {
+          if (ok[0]) ((int16_t*)dst)[o] = (int16_t)pcm_cvt(y[0], c);
+          if (ok[1]) ((int16_t*)dst)[o + 1] = (int16_t)pcm_cvt(y[1], c);
+        }
+      } else if (ok[0] && ok[W - 1]) {  // (the outputs are a range: first and last inside means all inside)
+        *(unsigned*)((uint8_t*)dst + o) = g711_quad(y[0], y[1], y[W / 2], y[W - 1], c);
       } else {
-        if (ok[0]) ((int16_t*)dst)[o] = (int16_t)pcm_cvt(y[0], c);
-        if (ok[1]) ((int16_t*)dst)[o + 1] = (int16_t)pcm_cvt(y[1], c);
+#pragma unroll
+        for (int k = 0; k < W; k++)
+          if (ok[k]) ((uint8_t*)dst)[o + k] = (uint8_t)g711_cvt(pcm_cvt(y[k], c), c.law);
       }
     }
   }
@@ -120,11 +137,11 @@ __device__ __forceinline__ int64_t rs_count_dev(int64_t n, const RsFilter f) { r
 // Plan audio [NB][row] → the items back to back at J(len·hop). blockIdx.y = item; its offset is the sum of the J before it (NB ≤ 256 = one
 // per thread), so plain, ragged and bounded slots — whose lengths only the device knows — take the same launch. lensF == nullptr: one
 // item of n_flat samples (the per-op entry points).
-template <bool F32, bool CL>
+template <int E, bool CL>
 __global__ __launch_bounds__(256) void resample_items_kernel(const float* __restrict__ audio, int64_t row, const int* __restrict__ lensF, int F,
                                                              int hop, int64_t n_flat, const RsFilter f, float gain,
                                                              const float* __restrict__ peaks, float* __restrict__ peaks_host, void* out,
-                                                             int tile) {
+                                                             int tile, int law) {
   extern __shared__ float4 rs_lds[];
   __shared__ long long part[4];
   const int b = blockIdx.y, tid = threadIdx.x;
@@ -135,7 +152,7 @@ __global__ __launch_bounds__(256) void resample_items_kernel(const float* __rest
   const int64_t at = part[0] + part[1] + part[2] + part[3];
   const int64_t n = lensF ? (int64_t)clamp_len(lensF[b], F) * hop : n_flat;
   PcmCvt c;
-  c.gain = gain; c.scale = 1.0f; c.norm = 0;
+  c.gain = gain; c.scale = 1.0f; c.norm = 0; c.law = law;
   if (peaks) {
     const float peak = peaks[b];
     c.scale = (float)(32767.0 / (double)fmaxf(0.01f, peak));
@@ -144,16 +161,15 @@ __global__ __launch_bounds__(256) void resample_items_kernel(const float* __rest
   }
   RsSrc r;
   r.x = audio + (int64_t)b * row; r.hist = nullptr; r.s = 0; r.e = n; r.j0 = 0; r.count = rs_count_dev(n, f);
-  void* dst = F32 ? (void*)((float*)out + at) : (void*)((int16_t*)out + at);
-  rs_row<F32, CL>(r, f, c, dst, tile, (float*)rs_lds);
+  rs_row<E, CL>(r, f, c, (char*)out + at * E, tile, (float*)rs_lds);
 }
 
 // One stream step: row blockIdx.y's chunk sits behind the halo skip of its plan audio, what came before it in the row's history. The
 // row's first block also leaves the last kRsHist samples of (history ++ chunk) as the next step's history, in the other buffer.
-template <bool CL>
+template <int E, bool CL>
 __global__ __launch_bounds__(256) void resample_step_kernel(const float* __restrict__ audio, int64_t row, const RsStepRow* __restrict__ desc,
                                                             const float* __restrict__ hist_old, float* __restrict__ hist_new, const RsFilter f,
-                                                            float gain, int16_t* __restrict__ out, int tile) {
+                                                            float gain, void* __restrict__ out, int tile, int law) {
   extern __shared__ float4 rs_lds[];
   const RsStepRow d = desc[blockIdx.y];
   // A row without a chunk leaves no history behind although the buffers change roles for the whole stream. That is sound because no row
@@ -169,8 +185,8 @@ __global__ __launch_bounds__(256) void resample_step_kernel(const float* __restr
     hist_new[(int64_t)blockIdx.y * kRsHist + i] = at >= 0 ? r.x[at] : (r.hist ? r.hist[i + d.n_in] : 0.0f);
   }
   PcmCvt c;
-  c.gain = gain; c.scale = 1.0f; c.norm = 0;
-  rs_row<false, CL>(r, f, c, out + d.off, tile, (float*)rs_lds);
+  c.gain = gain; c.scale = 1.0f; c.norm = 0; c.law = law;
+  rs_row<E, CL>(r, f, c, (char*)out + (int64_t)d.off * E, tile, (float*)rs_lds);
 }
 
 // The tile and the dynamic LDS of a launch with filter f
@@ -179,7 +195,7 @@ void rs_geometry(const RsFilter& f, int* tile, size_t* lds_bytes) {
   for (;;) {
     const size_t floats = (size_t)rs_coef_floats(f.L, f.P) + (size_t)ceil_div((int64_t)t * f.M, f.L) + f.P + 8;
     *lds_bytes = ((floats + 3) & ~(size_t)3) * sizeof(float);
-    if (*lds_bytes <= kRsLdsMax || t <= 64) break;
+    if (*lds_bytes <= kRsLdsMax || t <= kRsTileMin) break;
     t >>= 1;
   }
   *tile = t;
@@ -244,38 +260,41 @@ int rs_design(int in_rate, int out_rate, const RsDesign** out) {
 }
 
 hipError_t launch_resample_items(hipStream_t q, const float* audio, int64_t row, const int* lensF, int F, int hop, int NB, int64_t n_flat,
-                                 const RsFilter& f, float gain, const float* peaks, float* peaks_host, int16_t* out_pcm, float* out_f32) {
+                                 const RsFilter& f, float gain, const float* peaks, float* peaks_host, void* out, int elem, int law) {
   if (NB < 1 || NB > 256 || (!lensF && NB != 1)) return hipErrorInvalidValue;  // the offset of an item is summed by one block of 256 threads
   int tile;
   size_t lds;
   rs_geometry(f, &tile, &lds);
   const int64_t n_max = lensF ? (int64_t)F * hop : n_flat;
-  const int64_t outs = ceil_div(n_max * f.L, f.M) + 1;  // (+1: a destination that is not 4-byte aligned shifts the tiles by one)
+  const int64_t outs = ceil_div(n_max * f.L, f.M) + (elem == 1 ? 3 : 1);  // (a destination that is not 4-byte aligned shifts the tiles: by one int16, by up to three bytes)
   const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(outs, tile), 1), 1024), NB);
   const bool cl = f.L <= kRsLdsPhases;
-  void* out = out_f32 ? (void*)out_f32 : (void*)out_pcm;
-#define RS_ITEMS(F32, CL) \
-  hipLaunchKernelGGL((resample_items_kernel<F32, CL>), grid, dim3(256), lds, q, audio, row, lensF, F, hop, n_flat, f, gain, peaks, peaks_host, out, tile)
-  if (out_f32) { if (cl) RS_ITEMS(true, true); else RS_ITEMS(true, false); }
-  else { if (cl) RS_ITEMS(false, true); else RS_ITEMS(false, false); }
+  if (elem != 4 && elem != 2 && elem != 1) return hipErrorInvalidValue;
+#define RS_ITEMS(E, CL) \
+  hipLaunchKernelGGL((resample_items_kernel<E, CL>), grid, dim3(256), lds, q, audio, row, lensF, F, hop, n_flat, f, gain, peaks, peaks_host, out, tile, law)
+  if (elem == 4) { if (cl) RS_ITEMS(4, true); else RS_ITEMS(4, false); }
+  else if (elem == 2) { if (cl) RS_ITEMS(2, true); else RS_ITEMS(2, false); }
+  else { if (cl) RS_ITEMS(1, true); else RS_ITEMS(1, false); }
 #undef RS_ITEMS
   return hipGetLastError();
 }
 
 hipError_t launch_resample_step(hipStream_t q, int NBg, int max_count, const float* audio, int64_t row, const RsStepRow* desc,
-                                const float* hist_old, float* hist_new, const RsFilter& f, float gain, int16_t* out) {
+                                const float* hist_old, float* hist_new, const RsFilter& f, float gain, void* out, int law) {
   int tile;
   size_t lds;
   rs_geometry(f, &tile, &lds);
-  const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div((int64_t)max_count + 1, tile), 1), 1024), NBg);
-  if (f.L <= kRsLdsPhases)
-    hipLaunchKernelGGL((resample_step_kernel<true>), grid, dim3(256), lds, q, audio, row, desc, hist_old, hist_new, f, gain, out, tile);
-  else
-    hipLaunchKernelGGL((resample_step_kernel<false>), grid, dim3(256), lds, q, audio, row, desc, hist_old, hist_new, f, gain, out, tile);
+  const dim3 grid((unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div((int64_t)max_count + (law ? 3 : 1), tile), 1), 1024), NBg);
+  const bool cl = f.L <= kRsLdsPhases;
+#define RS_STEP(E, CL) \
+  hipLaunchKernelGGL((resample_step_kernel<E, CL>), grid, dim3(256), lds, q, audio, row, desc, hist_old, hist_new, f, gain, out, tile, law)
+  if (law) { if (cl) RS_STEP(1, true); else RS_STEP(1, false); }
+  else { if (cl) RS_STEP(2, true); else RS_STEP(2, false); }
+#undef RS_STEP
   return hipGetLastError();
 }
 
-namespace { PH_WARM(resample, (resample_items_kernel<false, false>)); }
+namespace { PH_WARM(resample, (resample_items_kernel<2, false>)); }
 
 }  // namespace ph
 
@@ -322,9 +341,10 @@ PH_EXPORT int64_t piper_hip_resample_step_bound(int32_t in_rate, int32_t out_rat
 // ---- per-op
 
 namespace {
-// x[count] → *out (fp32 y or int16), the table uploaded behind a pool block that is returned at the context's next sync point
+// x[count] → *out — the fp32 y (elem 4), int16 (elem 2) or G.711 bytes by `law` (elem 1) —, the table uploaded behind a pool block that
+// is returned at the context's next sync point
 int resample_op(piper_hip_ctx* ctx, const char* who, const float* x, size_t count, int in_rate, int out_rate, float gain, void** out, size_t elem,
-                size_t* out_count, piper_hip_stream stream) {
+                int law, size_t* out_count, piper_hip_stream stream) {
   if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: null output pointer", who);
   if (!x && count) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: null input", who);
   if (!(gain >= 0.0f) || !std::isfinite(gain)) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: gain %g is negative or not finite", who, (double)gain);
@@ -345,8 +365,7 @@ int resample_op(piper_hip_ctx* ctx, const char* who, const float* x, size_t coun
   StreamScope ss(ctx, stream);
   PH_HIP(hipMemcpyAsync(tab, d->taps.data(), d->taps.size() * sizeof(float), hipMemcpyHostToDevice, ss.s), PIPER_HIP_ERR_LAUNCH);
   const RsFilter f{(const float*)tab, d->L, d->M, d->P};
-  (void)launch_resample_items(ss.s, x, 0, nullptr, 0, 1, 1, (int64_t)count, f, gain == 0.0f ? 1.0f : gain, nullptr, nullptr,
-                              elem == 2 ? (int16_t*)*out : nullptr, elem == 4 ? (float*)*out : nullptr);
+  (void)launch_resample_items(ss.s, x, 0, nullptr, 0, 1, 1, (int64_t)count, f, gain == 0.0f ? 1.0f : gain, nullptr, nullptr, *out, (int)elem, law);
   return ss.finish(who);
 }
 }  // namespace
@@ -370,7 +389,7 @@ PH_EXPORT int piper_hip_resample_f32(piper_hip_ctx* ctx, const float* x, size_t 
     PH_HIP(hipMemcpyAsync(*out, x, count * sizeof(float), hipMemcpyDeviceToDevice, ss.s), PIPER_HIP_ERR_LAUNCH);
     return ss.finish("resample_f32");
   }
-  return resample_op(ctx, "resample_f32", x, count, in_rate, out_rate, 1.0f, (void**)out, sizeof(float), out_count, stream);
+  return resample_op(ctx, "resample_f32", x, count, in_rate, out_rate, 1.0f, (void**)out, sizeof(float), 0, out_count, stream);
 }
 
 PH_EXPORT int piper_hip_resample_pcm16_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t in_rate, int32_t out_rate, float gain,
@@ -381,5 +400,30 @@ PH_EXPORT int piper_hip_resample_pcm16_f32(piper_hip_ctx* ctx, const float* x, s
     if (!rc && out_count) *out_count = count;
     return rc;
   }
-  return resample_op(ctx, "resample_pcm16_f32", x, count, in_rate, out_rate, gain, (void**)out, sizeof(int16_t), out_count, stream);
+  return resample_op(ctx, "resample_pcm16_f32", x, count, in_rate, out_rate, gain, (void**)out, sizeof(int16_t), 0, out_count, stream);
+}
+
+// ---- G.711 (include/piper_hip.h "G.711 output")
+
+PH_EXPORT int piper_hip_g711_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t in_rate, int32_t out_rate, float gain, int law,
+                                 uint8_t** out, size_t* out_count, piper_hip_stream stream) {
+  PH_CHECK_CTX(ctx);  // stays first: without a device this returns UNAVAILABLE before any other field of ctx is touched
+  if (law != PIPER_HIP_G711_MULAW && law != PIPER_HIP_G711_ALAW) PH_FAIL(PIPER_HIP_ERR_ARG, "g711_f32: law %d (1 = mu-law, 2 = A-law)", law);
+  if (in_rate != out_rate || in_rate <= 0)
+    return resample_op(ctx, "g711_f32", x, count, in_rate, out_rate, gain, (void**)out, 1, law, out_count, stream);
+  // not a filter: the byte of every sample of piper_hip_pcm16_f32
+  if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "g711_f32: null output pointer");
+  if (!x && count) PH_FAIL(PIPER_HIP_ERR_ARG, "g711_f32: null input");
+  if (!(gain >= 0.0f) || !std::isfinite(gain)) PH_FAIL(PIPER_HIP_ERR_ARG, "g711_f32: gain %g is negative or not finite", (double)gain);
+  if (!*out) {
+    void* p = nullptr;
+    const int rc = ctx->pool.alloc(count, &p);
+    if (rc) return rc;
+    *out = (uint8_t*)p;
+  }
+  if (out_count) *out_count = count;
+  if (count == 0) return PIPER_HIP_OK;
+  StreamScope ss(ctx, stream);
+  (void)launch_pcm16_flat(ss.s, x, (int64_t)count, gain == 0.0f ? 1.0f : gain, *out, law, ctx->num_cus);
+  return ss.finish("g711_f32");
 }

@@ -293,8 +293,8 @@ struct Slot {
   float* bs_pack = nullptr;   // the packed chunks of one step, device
   size_t bs_pack_cap = 0;     // floats
   // 16-bit PCM output (piper_hip_voice_collect_pcm16 / stream_next_pcm16): device buffers of this plan (in `owned`), allocated on first use
-  int16_t* pcm = nullptr;     // the items back to back, as they travel to the host
-  size_t pcm_cap = 0;         // samples
+  void* pcm = nullptr;        // the items back to back, as they travel to the host (int16, or one G.711 byte per sample)
+  size_t pcm_cap = 0;         // bytes
   float* peaks = nullptr;     // [NB] max |x| per item (normalize = 1)
   std::vector<float> h_peaks; // the same on the host after a normalising collect_pcm16 (empty: none since the last launch)
   StreamRate rs;              // output rate of the stream in progress; its buffers are in `owned`
@@ -3030,35 +3030,37 @@ int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
 // collect's (see there for the measurements behind them): a destination the caller page-locked takes kernel stores through its host
 // mapping up to 16 MB; a pageable one is served through the slot id's page-locked staging — kernel stores up to 1 MB, 1 MB chunks by the
 // copy engine with the host copying behind them up to 16 MB — and handed to the runtime beyond that. PIPER_HIP_COLLECT_DMA: always the
-// copy engine. The staging is sg.h_audio, the waveform's own landing buffer, holding two samples per float.
+// copy engine. The staging is sg.h_audio, the waveform's own landing buffer, holding two int16 samples per float or four G.711 bytes.
+// elem = bytes of a sample (2, or 1 for G.711); the thresholds apply to the byte count.
 
 struct PcmRoute {
-  int16_t* kdst = nullptr;     // where the convert kernel stores
-  int16_t* stage = nullptr;    // the slot id's page-locked staging when it holds the samples, else null
+  void* kdst = nullptr;        // where the convert kernel stores
+  void* stage = nullptr;       // the slot id's page-locked staging when it holds the samples, else null
   bool mapped = false;         // kdst is host memory seen from the device: the stores are the transfer
   bool caller_pinned = false;  // (then kdst is the caller's buffer itself)
 };
 
 // `samples` will travel to `host`; a device buffer, if one is needed, belongs to `plan` and holds `dev_samples`
-int pcm_route(piper_hip_voice* v, Slot& plan, piper_hip_voice::Staging& sg, int16_t* host, size_t samples, size_t dev_samples, PcmRoute* r) {
-  const size_t bytes = samples * sizeof(int16_t);
+int pcm_route(piper_hip_voice* v, Slot& plan, piper_hip_voice::Staging& sg, void* host, size_t elem, size_t samples, size_t dev_samples,
+              PcmRoute* r) {
+  const size_t bytes = samples * elem;
   r->caller_pinned = is_caller_pinned(host);
-  if (!r->caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (samples + 1) / 2, kAudioMinCap)) (void)hipGetLastError();
-  r->stage = (!r->caller_pinned && sg.h_audio && sg.audio_cap * 2 >= samples) ? (int16_t*)sg.h_audio : nullptr;
+  if (!r->caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (bytes + 3) / 4, kAudioMinCap)) (void)hipGetLastError();
+  r->stage = (!r->caller_pinned && sg.h_audio && sg.audio_cap * sizeof(float) >= bytes) ? (void*)sg.h_audio : nullptr;
   static const bool dma_only = getenv("PIPER_HIP_COLLECT_DMA") != nullptr;
   void* target = r->caller_pinned ? (bytes <= kChunkedMax ? (void*)host : nullptr) : (bytes <= kPinnedMax ? (void*)r->stage : nullptr);
   if (!dma_only && target) {
     void* dev = nullptr;
-    if (hipHostGetDevicePointer(&dev, target, 0) == hipSuccess && dev) { r->kdst = (int16_t*)dev; r->mapped = true; }
+    if (hipHostGetDevicePointer(&dev, target, 0) == hipSuccess && dev) { r->kdst = dev; r->mapped = true; }
     else (void)hipGetLastError();
   }
   if (!r->mapped) {
-    if (plan.pcm_cap < dev_samples) {
+    if (plan.pcm_cap < dev_samples * elem) {
       void* p = nullptr;
-      const int rc = plan_alloc(v, plan, dev_samples * sizeof(int16_t), &p);  // (a smaller one stays with the plan until it is released)
+      const int rc = plan_alloc(v, plan, dev_samples * elem, &p);  // (a smaller one stays with the plan until it is released)
       if (rc) return rc;
-      plan.pcm = (int16_t*)p;
-      plan.pcm_cap = dev_samples;
+      plan.pcm = p;
+      plan.pcm_cap = dev_samples * elem;
     }
     r->kdst = plan.pcm;
   }
@@ -3067,12 +3069,12 @@ int pcm_route(piper_hip_voice* v, Slot& plan, piper_hip_voice::Staging& sg, int1
 
 // Behind the convert kernel on q: wait for it, and bring `samples` samples to `host` unless the kernel stored them through a mapping
 // (then they are in the caller's buffer already, or in r.stage, from where the caller copies what it needs).
-int pcm_land(piper_hip_voice::Staging& sg, const PcmRoute& r, hipStream_t q, int16_t* host, size_t samples) {
+int pcm_land(piper_hip_voice::Staging& sg, const PcmRoute& r, hipStream_t q, void* host, size_t elem, size_t samples) {
   if (r.mapped) {
     PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);
     return PIPER_HIP_OK;
   }
-  const size_t bytes = samples * sizeof(int16_t);
+  const size_t bytes = samples * elem;
   if (!r.caller_pinned && r.stage && bytes > kPinnedMax && bytes <= kChunkedMax) {
     const size_t nchunks = (bytes + kChunk - 1) / kChunk;
     for (size_t k = 0; k < nchunks; k++) {
@@ -3098,7 +3100,7 @@ int pcm_land(piper_hip_voice::Staging& sg, const PcmRoute& r, hipStream_t q, int
     }
     return PIPER_HIP_OK;
   }
-  int16_t* dst = (!r.caller_pinned && r.stage && bytes <= kPinnedMax) ? r.stage : host;
+  void* dst = (!r.caller_pinned && r.stage && bytes <= kPinnedMax) ? r.stage : host;
   PH_HIP(hipMemcpyAsync(dst, r.kdst, bytes, hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipStreamSynchronize(q), PIPER_HIP_ERR_LAUNCH);
   if (dst != host) memcpy(host, dst, bytes);
@@ -3165,9 +3167,12 @@ Window window_of(int F, int next, int chunk, int halo, int hop) {
   return Window{a, b - a, (f0 - a) * hop, (f1 - f0) * hop, f1};
 }
 
-// stream_next; pcm: the chunk leaves as int16 (host_pcm, gain) — converted by a kernel behind the window's graph — instead of fp32
-int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm, float gain) {
+// stream_next; pcm: the chunk leaves as int16 (host_pcm, gain) — converted by a kernel behind the window's graph — instead of fp32, or,
+// with law = PIPER_HIP_G711_*, as one G.711 byte per sample (host_pcm is then a byte buffer); the step is the same in every other respect
+int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm, float gain,
+                int law) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  const size_t elem = law ? 1 : sizeof(int16_t);
   const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
   Slot* sp = slot_plan(v, slot);
   if (sp && sp->bs_rows.size() > 1)
@@ -3216,18 +3221,18 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (pcm && want_out) {
     PcmRoute r;
     const size_t dev_samples = (size_t)std::max<int64_t>((int64_t)gs->F * v->hop, rd ? rs_step_bound(*rd, (int64_t)gs->F * v->hop) : 0);
-    if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], host_pcm, (size_t)want, dev_samples, &r);
+    if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], host_pcm, elem, (size_t)want, dev_samples, &r);
     if (rd) {  // (every step ends with a wait: the staged descriptor of the previous one has been read)
       RsStepRow* h = (RsStepRow*)(v->staging[slot].h_desc + kDescStageInts);
       if (e == hipSuccess && !rc) { *h = rrow; e = hipMemcpyAsync(rs.desc, h, sizeof(RsStepRow), hipMemcpyHostToDevice, gs->set.stream); }
       if (e == hipSuccess && !rc)
         e = launch_resample_step(gs->set.stream, 1, rrow.count, gs->audio, 0, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, r.kdst);
+                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, r.kdst, law);
     } else if (e == hipSuccess && !rc) {
-      e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, gain, r.kdst, v->ctx->num_cus);
+      e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, gain, r.kdst, law, v->ctx->num_cus);
     }
-    if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, host_pcm, (size_t)want);
-    if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)want * sizeof(int16_t));
+    if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, host_pcm, elem, (size_t)want);
+    if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)want * elem);
     if (e != hipSuccess || rc) (void)hipStreamSynchronize(gs->set.stream);  // nothing of the window may still run when its plan goes idle
   } else {
     if (e == hipSuccess && host_audio)
@@ -3247,7 +3252,7 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
-  return stream_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f);
+  return stream_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f, 0);
 }
 
 // ---- batched streaming: a group of n utterances on one slot, the next chunk of every active item in one generator launch ------------
@@ -3419,13 +3424,14 @@ struct StepView {
 // stream_next_batch: the next chunk of every active row in one generator launch at the stream's fixed batch; *ran = a step ran and has
 // been waited for (false: no active row, nothing was launched).
 // pcm: the chunks leave as int16 (host_pcm, gain) instead of fp32 (host_audio) — the int16 sibling of the pack kernel writes them into the
-// same device and staging buffers, half filled, and half the bytes cross the bus.
+// same device and staging buffers, half filled, and half the bytes cross the bus. law = PIPER_HIP_G711_* (with pcm): one G.711 byte per
+// sample instead, host_pcm a byte buffer — a quarter filled, a quarter of the bytes.
 template <class Row>
 int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm,
-                 int16_t* host_pcm, float gain, bool* ran) {
+                 void* host_pcm, float gain, int law, bool* ran) {
   *ran = false;
   const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
-  const size_t sample_bytes = pcm ? sizeof(int16_t) : sizeof(float);
+  const size_t sample_bytes = pcm ? (law ? 1 : sizeof(int16_t)) : sizeof(float);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   const int n = s.n, NBg = s.NBg, hop = v->hop;
   auto& sg = v->staging[slot];
@@ -3502,9 +3508,9 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
       e = hipMemcpyAsync(rs.desc, rrow, (size_t)NBg * sizeof(RsStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
         e = launch_resample_step(q, NBg, max_cnt, gs->audio, gs->n_samples, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, (int16_t*)s.pack);
+                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, s.pack, law);
     } else if (pcm) {
-      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, s.d_desc, gain, (int16_t*)s.pack);
+      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, s.d_desc, gain, s.pack, law);
     } else {
       hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.d_desc, s.pack);
       e = hipGetLastError();
@@ -3516,7 +3522,7 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   evict_idle_plans(v);
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
   *ran = true;
-  if (want_out) memcpy(pcm ? (void*)host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
+  if (want_out) memcpy(pcm ? host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
   rs.started = true;
   if (rd) rs.parity ^= 1;
   for (int i = 0; i < n; i++) {
@@ -3529,12 +3535,12 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
 }
 
 // stream_next_batch on a pool slot: the latents are the row stores, ready when the adopts of the joins since the last step have run
-int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm,
-              float gain) {
+int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm,
+              float gain, int law) {
   const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, P.pack_bytes / sizeof(float),
                                        nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), &P.rs};
   bool ran = false;
-  const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, &ran);
+  const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran);
   if (rc || !ran) return rc;  // (an idle pool: joins since the last step stay pending)
   // the step's wait covers the adopts its stream waited for: their events can be recorded again
   P.ev_free.insert(P.ev_free.end(), P.ev_pending.begin(), P.ev_pending.end());
@@ -3576,10 +3582,11 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
 }
 
 namespace {
-// stream_next_batch; pcm / host_pcm / gain as for batched_step. A group's latents are the front plan's z, ready when its ev1 fires.
-int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, int16_t* host_pcm, float gain) {
+// stream_next_batch; pcm / host_pcm / gain / law as for batched_step. A group's latents are the front plan's z, ready when its ev1 fires.
+int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm, float gain,
+               int law) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples, pcm, host_pcm, gain);
+  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law);
   Slot* sp = slot_plan(v, slot);
   if (!sp || sp->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   Slot& s = *sp;
@@ -3587,12 +3594,12 @@ int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samp
   const StepView<StreamRow> view{s.bs_rows.data(), n, group_batch(n), s.st_chunk, s.st_halo, s.bs_desc, s.bs_pack, s.bs_pack_cap,
                                  s.z_out, s.F, nullptr, &s.set.ev1, 1, &s.rs};
   bool ran = false;
-  return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, &ran);
+  return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran);
 }
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
-  return batch_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f);
+  return batch_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f, 0);
 }
 
 PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item) {
@@ -3738,8 +3745,10 @@ PH_EXPORT int piper_hip_voice_stream_pool_close(piper_hip_voice* v, int slot) {
 namespace {
 // collect_pcm16, and collect_pcm16_rate where out_rate differs from the voice's own: then item b is J(its true samples) long and the pack
 // kernel's place is taken by the resampling one (rd / rf: its filter); everything else — the peaks, the route, the landing — is shared.
-int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int out_rate, int16_t* host_pcm, int64_t max_samples) {
+// law = PIPER_HIP_G711_*: collect_g711 — the same kernels with their one-byte sink, host_pcm a byte buffer.
+int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int out_rate, void* host_pcm, int64_t max_samples, int law) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  const size_t elem = law ? 1 : sizeof(int16_t);
   Slot* p = slot_plan(v, slot);
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
   float gain;
@@ -3785,21 +3794,21 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
     if (hipHostGetDevicePointer((void**)&peaks_host, sg.h_peaks, 0) != hipSuccess) { peaks_host = nullptr; (void)hipGetLastError(); }
   }
   PcmRoute r;
-  if ((rc = pcm_route(v, s, sg, host_pcm, (size_t)need, (size_t)std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB, &r))) return rc;
+  if ((rc = pcm_route(v, s, sg, host_pcm, elem, (size_t)need, (size_t)std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB, &r))) return rc;
   const hipStream_t q = s.set.stream;
   if (normalize) PH_HIP(launch_pcm16_peak(q, s.audio, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
   if (rd)
-    PH_HIP(launch_resample_items(q, s.audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, nullptr),
+    PH_HIP(launch_resample_items(q, s.audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
            PIPER_HIP_ERR_LAUNCH);
   else
-    PH_HIP(launch_pcm16_pack(q, s.audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(launch_pcm16_pack(q, s.audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
   if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, (size_t)NB * sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
-  if ((rc = pcm_land(sg, r, q, host_pcm, (size_t)need))) return rc;
+  if ((rc = pcm_land(sg, r, q, host_pcm, elem, (size_t)need))) return rc;
   if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
   if (r.mapped && !r.caller_pinned) {  // the kernel stored into the staging: the true total is known by now
     int64_t total = 0;
     for (int b = 0; b < NB; b++) total += out_len((int64_t)s.h_F[b] * hop);
-    memcpy(host_pcm, r.stage, (size_t)total * sizeof(int16_t));
+    memcpy(host_pcm, r.stage, (size_t)total * elem);
   }
   if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + NB);
   return PIPER_HIP_OK;
@@ -3808,12 +3817,12 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
 
 PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm, int64_t max_samples) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  return collect_pcm(v, slot, params, v->cfg.sample_rate, host_pcm, max_samples);
+  return collect_pcm(v, slot, params, v->cfg.sample_rate, host_pcm, max_samples, 0);
 }
 
 PH_EXPORT int piper_hip_voice_collect_pcm16_rate(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int32_t out_rate, int16_t* host_pcm,
                                                  int64_t max_samples) {
-  return collect_pcm(v, slot, params, out_rate, host_pcm, max_samples);
+  return collect_pcm(v, slot, params, out_rate, host_pcm, max_samples, 0);
 }
 
 PH_EXPORT int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* peaks, int max_items) {
@@ -3851,7 +3860,7 @@ PH_EXPORT int piper_hip_voice_synthesize_pcm16_rate(piper_hip_voice* v, const pi
   if (out_rate != v->cfg.sample_rate && (rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
   if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
-  if ((rc = collect_pcm(v, 0, params, out_rate, host_pcm, max_samples))) return rc;
+  if ((rc = collect_pcm(v, 0, params, out_rate, host_pcm, max_samples, 0))) return rc;
   const int64_t n = (int64_t)v->attached[0]->h_F[0] * v->hop;
   if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
   return PIPER_HIP_OK;
@@ -3978,7 +3987,7 @@ PH_EXPORT int piper_hip_voice_stream_next_pcm16(piper_hip_voice* v, int slot, co
   const int rc = pcm_step_params(v, params, &gain);
   if (rc) return rc;
   if (slot_pool(v, slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a streaming pool: use stream_next_batch_pcm16", slot);
-  return stream_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain);
+  return stream_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain, 0);
 }
 
 PH_EXPORT int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
@@ -3986,7 +3995,59 @@ PH_EXPORT int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int sl
   float gain;
   const int rc = pcm_step_params(v, params, &gain);
   if (rc) return rc;
-  return batch_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain);
+  return batch_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain, 0);
+}
+
+// ---- G.711 (include/piper_hip.h "G.711 output"): the PCM entry points with a one-byte sink; the law is an argument of each call ---------
+namespace {
+int g711_law(const char* who, int law) {
+  if (law != PIPER_HIP_G711_MULAW && law != PIPER_HIP_G711_ALAW) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: law %d (1 = mu-law, 2 = A-law)", who, law);
+  return PIPER_HIP_OK;
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_collect_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, int32_t out_rate,
+                                           uint8_t* host, int64_t max_samples) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (int rc = g711_law("collect_g711", law)) return rc;
+  return collect_pcm(v, slot, params, out_rate, host, max_samples, law);
+}
+
+PH_EXPORT int piper_hip_voice_synthesize_g711(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int law,
+                                              int32_t out_rate, uint8_t* host, int64_t max_samples, int64_t* n_samples) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  float gain;
+  bool normalize;
+  int rc = g711_law("synthesize_g711", law);
+  if (!rc) rc = pcm_params(params, &gain, &normalize);
+  if (rc) return rc;
+  const RsDesign* rd = nullptr;
+  if (out_rate != v->cfg.sample_rate && (rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
+  if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
+  if ((rc = piper_hip_voice_launch(v, 0))) return rc;
+  if ((rc = collect_pcm(v, 0, params, out_rate, host, max_samples, law))) return rc;
+  const int64_t n = (int64_t)v->attached[0]->h_F[0] * v->hop;
+  if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_next_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
+                                               int64_t max_samples, int64_t* n_samples) {
+  float gain;
+  int rc = pcm_step_params(v, params, &gain);
+  if (!rc) rc = g711_law("stream_next_g711", law);
+  if (rc) return rc;
+  if (slot_pool(v, slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a streaming pool: use stream_next_batch_g711", slot);
+  return stream_step(v, slot, nullptr, max_samples, n_samples, true, host, gain, law);
+}
+
+PH_EXPORT int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
+                                                     int64_t max_samples, int64_t* n_samples) {
+  float gain;
+  int rc = pcm_step_params(v, params, &gain);
+  if (!rc) rc = g711_law("stream_next_batch_g711", law);
+  if (rc) return rc;
+  return batch_step(v, slot, nullptr, max_samples, n_samples, true, host, gain, law);
 }
 
 PH_EXPORT int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u, float* host_audio,

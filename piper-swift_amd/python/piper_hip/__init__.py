@@ -118,6 +118,16 @@ class PcmParams(C.Structure):
 
 
 c_i16p = C.POINTER(C.c_int16)
+c_u8p = C.POINTER(C.c_uint8)
+
+# G.711 laws (include/piper_hip.h "G.711 output")
+G711_MULAW, G711_ALAW = 1, 2
+
+
+def _law(law):
+    """"mulaw" / "alaw" (or PIPER_HIP_G711_*) → the constant; anything else is passed on for the library to refuse."""
+    return {"mulaw": G711_MULAW, "ulaw": G711_MULAW, "pcmu": G711_MULAW, "alaw": G711_ALAW, "pcma": G711_ALAW}.get(
+        law.lower() if isinstance(law, str) else law, law if isinstance(law, int) else -1)
 
 
 class KernelStat(C.Structure):
@@ -260,6 +270,16 @@ _PROTOS = {
     "piper_hip_voice_stream_set_rate": (C.c_int, [c_vp, C.c_int, C.c_int32]),
     "piper_hip_voice_stream_rate": (C.c_int, [c_vp, C.c_int]),
     "piper_hip_voice_stream_step_capacity": (C.c_int64, [c_vp, C.c_int]),
+    "piper_hip_g711_from_pcm16": (C.c_int, [C.c_int, c_i16p, C.c_size_t, c_u8p]),
+    "piper_hip_g711_to_pcm16": (C.c_int, [C.c_int, c_u8p, C.c_size_t, c_i16p]),
+    "piper_hip_wav_write_g711": (C.c_int, [C.c_char_p, C.c_int, c_u8p, C.c_size_t, C.c_int32]),
+    "piper_hip_g711_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_int32, C.c_int32, C.c_float, C.c_int, C.POINTER(c_vp), C.POINTER(C.c_size_t),
+                                     c_vp]),
+    "piper_hip_voice_collect_g711": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int, C.c_int32, c_u8p, C.c_int64]),
+    "piper_hip_voice_synthesize_g711": (C.c_int, [c_vp, C.POINTER(Utterance), C.POINTER(PcmParams), C.c_int, C.c_int32, c_u8p, C.c_int64,
+                                                  C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_next_g711": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_next_batch_g711": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
     "piper_hip_voice_tap": (C.c_int, [c_vp, C.c_int, C.c_char_p, c_f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "piper_hip_voice_last_gpu_ms": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_double)]),
     "piper_hip_voice_slot_stream": (c_vp, [c_vp, C.c_int]),
@@ -617,6 +637,26 @@ class HipBackend:
                                                      commandBuffer))
         return DeviceBuffer(self, p.value, got.value, owned=out is None, dtype=np.int16)
 
+    def g711F32(self, buf, law, inRate=None, outRate=None, gain=1.0, count=None, out=None, commandBuffer=None):
+        """`count` device floats → G.711 bytes on the device (piper_hip_g711_f32): law ("mulaw" / "alaw") of the int16 that pcm16F32 —
+        or, with inRate != outRate, resamplePcm16F32 — gives. Returns a DeviceBuffer of J(count) uint8 (downloadUint8); `out`: a device
+        address to write to (any byte address), returned as it is."""
+        n = buf.count if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        got = C.c_size_t()
+        r_in = 1 if inRate is None else int(inRate)
+        r_out = r_in if outRate is None else int(outRate)
+        _check(self.lib.piper_hip_g711_f32(self.ctx, _ptr(buf), n, r_in, r_out, float(gain), _law(law), C.byref(p), C.byref(got), commandBuffer))
+        return DeviceBuffer(self, p.value, got.value, owned=out is None, dtype=np.uint8)
+
+    def downloadUint8(self, buf, count=None):
+        """The first `count` bytes of a device buffer of this backend's pool → host array. (Copied as whole floats, as downloadInt16: up to
+        three bytes more are read, which a pool block always holds.)"""
+        n = buf.count if count is None else int(count)
+        out = np.empty((n + 3) // 4 * 4, np.uint8)
+        _check(self.lib.piper_hip_download_f32(self.ctx, _ptr(buf), out.ctypes.data_as(c_f32p), (n + 3) // 4))
+        return out[:n].copy()
+
     def downloadInt16(self, buf, count=None):
         """The first `count` int16 of a device buffer of this backend's pool → host array. (Copied as whole floats: an odd count reads one
         sample more, which a pool block — a power of two of at least 256 bytes — always holds.)"""
@@ -856,6 +896,28 @@ def wav_write_pcm16(path, pcm, sample_rate=22050):
     _check(load_library().piper_hip_wav_write_pcm16(str(path).encode(), a.ctypes.data_as(c_i16p), a.size, int(sample_rate)))
 
 
+def g711_encode(pcm, law):
+    """int16 samples → G.711 bytes ("mulaw" / "alaw") on the host (piper_hip_g711_from_pcm16): the function the device applies."""
+    a = np.ascontiguousarray(pcm, np.int16)
+    out = np.empty(a.size, np.uint8)
+    _check(load_library().piper_hip_g711_from_pcm16(_law(law), a.ctypes.data_as(c_i16p), a.size, out.ctypes.data_as(c_u8p)))
+    return out
+
+
+def g711_decode(data, law):
+    """G.711 bytes → int16 samples on the host (piper_hip_g711_to_pcm16)."""
+    a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8)
+    out = np.empty(a.size, np.int16)
+    _check(load_library().piper_hip_g711_to_pcm16(_law(law), a.ctypes.data_as(c_u8p), a.size, out.ctypes.data_as(c_i16p)))
+    return out
+
+
+def wav_write_g711(path, data, law, sample_rate=8000):
+    """A mono G.711 WAV file (format tag 7 / 6, fact chunk) from bytes that are companded already."""
+    a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8)
+    _check(load_library().piper_hip_wav_write_g711(str(path).encode(), _law(law), a.ctypes.data_as(c_u8p), a.size, int(sample_rate)))
+
+
 def resample_info(in_rate, out_rate):
     """(L, M, taps per phase) of the output-rate contract for a rate pair; UnsupportedOp for a pair outside it. Host-only."""
     L, M, P = C.c_int32(), C.c_int32(), C.c_int32()
@@ -928,11 +990,17 @@ class StreamPool:
         rt._keep.pop(self.work_slot, None)  # the inputs were copied before the call returned
         return [(int(items[i]), int(samples[i])) for i in range(n)]
 
-    def step(self, pcm=False, gain=1.0, normalize=False):
+    def step(self, pcm=False, gain=1.0, normalize=False, encoding=None):
         """{item: chunk} of every active session; an empty dict when the pool is idle. pcm=True: int16 chunks converted on the device
-        (piper_hip_voice_stream_next_batch_pcm16; normalize is refused there — UnsupportedOp — and consumes nothing)."""
+        (piper_hip_voice_stream_next_batch_pcm16; normalize is refused there — UnsupportedOp — and consumes nothing). encoding "mulaw" /
+        "alaw": uint8 chunks of G.711 bytes instead (piper_hip_voice_stream_next_batch_g711), at the pool's rate."""
         rt = self.rt
-        if pcm:
+        if encoding is not None:
+            buf = self._buf.view(np.uint8)[:self._buf.size * (4 if self.rate else 1)]
+            prm = PcmParams(float(gain), int(bool(normalize)))
+            _check(rt.lib.piper_hip_voice_stream_next_batch_g711(rt.voice, self.slot, C.byref(prm), _law(encoding), buf.ctypes.data_as(c_u8p),
+                                                                 buf.size, self._got))
+        elif pcm:
             buf = self._buf.view(np.int16)[:self._buf.size * (2 if self.rate else 1)]
             prm = PcmParams(float(gain), int(bool(normalize)))
             _check(rt.lib.piper_hip_voice_stream_next_batch_pcm16(rt.voice, self.slot, C.byref(prm), buf.ctypes.data_as(c_i16p), buf.size, self._got))
@@ -1101,23 +1169,30 @@ class HipRuntime:
         """The int16 samples one step of the stream on `slot` can deliver at its current rate."""
         return _count(self.lib.piper_hip_voice_stream_step_capacity(self.voice, slot))
 
-    def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None):
+    def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None,
+                          encoding=None):
         """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
         pcm=True: int16 chunks converted on the device (piper_hip_voice_stream_next_pcm16), scaled by `gain`. rate: int16 chunks at that
-        output rate (stream_set_rate; implies pcm)."""
+        output rate (stream_set_rate; implies pcm). encoding "mulaw" / "alaw": uint8 chunks of G.711 bytes instead of int16
+        (piper_hip_voice_stream_next_g711), at `rate` or the voice's own."""
         u, keep = self._utt(phonemeIDs, durations, noise, noiseScale)
         n_chunks = self.lib.piper_hip_voice_stream_begin(self.voice, C.byref(u), slot, int(chunkFrames))
         if n_chunks < 0:
             _check(n_chunks)
-        buf = np.empty(int(chunkFrames) * self.cfg.hop, np.int16 if pcm or rate else np.float32)
+        law = None if encoding is None else _law(encoding)
+        sample = np.uint8 if law is not None else np.int16
+        buf = np.empty(int(chunkFrames) * self.cfg.hop, sample if pcm or rate or law is not None else np.float32)
         if rate:
             pcm = True
             self.stream_set_rate(slot, rate)
-            buf = np.empty(self.stream_step_capacity(slot), np.int16)
+            buf = np.empty(self.stream_step_capacity(slot), sample)
         got = C.c_int64()
         prm = PcmParams(float(gain), 0)
         while True:
-            if pcm:
+            if law is not None:
+                _check(self.lib.piper_hip_voice_stream_next_g711(self.voice, slot, C.byref(prm), law, buf.ctypes.data_as(c_u8p), buf.size,
+                                                                 C.byref(got)))
+            elif pcm:
                 _check(self.lib.piper_hip_voice_stream_next_pcm16(self.voice, slot, C.byref(prm), buf.ctypes.data_as(c_i16p), buf.size, C.byref(got)))
             else:
                 _check(self.lib.piper_hip_voice_stream_next(self.voice, slot, buf.ctypes.data_as(c_f32p), buf.size, C.byref(got)))
@@ -1125,11 +1200,12 @@ class HipRuntime:
                 return
             yield buf[:got.value].copy()
 
-    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None):
+    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None, encoding=None):
         """Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
         arrays — the next chunk of every item, empty once the item is finished or dropped (stream_drop). pcm=True: int16 chunks converted on
-        the device (piper_hip_voice_stream_next_batch_pcm16), scaled by `gain`. rate: int16 chunks at that output rate (implies pcm)."""
+        the device (piper_hip_voice_stream_next_batch_pcm16), scaled by `gain`. rate: int16 chunks at that output rate (implies pcm).
+        encoding "mulaw" / "alaw": uint8 chunks of G.711 bytes instead of int16 (piper_hip_voice_stream_next_batch_g711)."""
         n = len(utterances)
         arr = (Utterance * max(n, 1))()
         keep = []
@@ -1141,15 +1217,19 @@ class HipRuntime:
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
-        buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), np.int16 if pcm or rate else np.float32)
+        law = None if encoding is None else _law(encoding)
+        sample = np.uint8 if law is not None else np.int16
+        buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), sample if pcm or rate or law is not None else np.float32)
         if rate:
             pcm = True
             self.stream_set_rate(slot, rate)
-            buf = np.empty(self.stream_step_capacity(slot), np.int16)
+            buf = np.empty(self.stream_step_capacity(slot), sample)
         got = (C.c_int64 * n)()
         prm = PcmParams(float(gain), 0)
         while True:
-            if pcm:
+            if law is not None:
+                _check(self.lib.piper_hip_voice_stream_next_batch_g711(self.voice, slot, C.byref(prm), law, buf.ctypes.data_as(c_u8p), buf.size, got))
+            elif pcm:
                 _check(self.lib.piper_hip_voice_stream_next_batch_pcm16(self.voice, slot, C.byref(prm), buf.ctypes.data_as(c_i16p), buf.size, got))
             else:
                 _check(self.lib.piper_hip_voice_stream_next_batch(self.voice, slot, buf.ctypes.data_as(c_f32p), buf.size, got))
@@ -1296,6 +1376,42 @@ class HipRuntime:
         self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, **kw)
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
+
+    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None):
+        """collect_pcm16 ending in G.711 bytes ("mulaw" / "alaw") companded on the device (piper_hip_voice_collect_g711): one uint8 per
+        sample, the items back to back at J(their true samples) at `rate` (default: the voice's own). Every rule of collect_pcm16 holds."""
+        src = self.cfg.sample_rate
+        rate = src if rate is None else int(rate)
+        count = (lambda p: p) if rate == src else (lambda p: resample_count(src, rate, p))
+        bounded = len(self._keep[slot]) > 2 and self._keep[slot][2]
+        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
+        per, total = self.prepared_samples(slot)  # (a bounded slot: the capacity, spread evenly over the items)
+        room = nb * count(total // max(nb, 1)) if bounded else sum(count(p) for p in per)
+        if out is None:
+            out = np.empty(max(room, 1), np.uint8)
+        assert out.dtype == np.uint8 and out.size >= room and out.flags.c_contiguous
+        prm = PcmParams(float(gain), int(bool(normalize)))
+        _check(self.lib.piper_hip_voice_collect_g711(self.voice, slot, C.byref(prm), _law(law), rate, out.ctypes.data_as(c_u8p), room))
+        if bounded:  # the true lengths are known now
+            per, total = self.prepared_samples(slot)
+            self._keep[slot] = (self._keep[slot][0], total, False)
+        return out[:sum(count(p) for p in per)]
+
+    def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None):
+        """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's."""
+        src = self.cfg.sample_rate
+        rate = src if rate is None else int(rate)
+        u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
+        n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
+        if rate != src:
+            n = resample_count(src, rate, n)
+        out = np.empty(max(n, 1), np.uint8)
+        got = C.c_int64()
+        prm = PcmParams(float(gain), int(bool(normalize)))
+        _check(self.lib.piper_hip_voice_synthesize_g711(self.voice, C.byref(u), C.byref(prm), _law(law), rate, out.ctypes.data_as(c_u8p), n,
+                                                        C.byref(got)))
+        self._keep.pop(0, None)
+        return out[:got.value]
 
     def peaks(self, slot):
         """max |x| of each item of the slot, after a collect_pcm16(normalize=True) of its latest run."""

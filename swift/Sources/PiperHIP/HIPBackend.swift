@@ -180,6 +180,29 @@ public final class HIPBackend {
         return (HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx), n)
     }
 
+    /// `count` device floats at inRate → J(count) G.711 bytes at outRate on the device (piper_hip_g711_f32; law = PIPER_HIP_G711_MULAW or
+    /// _ALAW): law(int16 of y · gain). inRate == outRate is not a filter. The buffer holds J(count) bytes.
+    public func g711F32(input: HIPBuffer, count: Int, law: Int32, inRate: Int32, outRate: Int32, gain: Float = 1.0,
+                        commandBuffer: Stream? = nil) throws -> (HIPBuffer, Int) {
+        var out: UnsafeMutablePointer<UInt8>? = nil
+        var n = 0
+        try Self.check(piper_hip_g711_f32(ctx, input.f32, count, inRate, outRate, gain, law, &out, &n, commandBuffer))
+        return (HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx), n)
+    }
+
+    /// int16 samples → G.711 bytes and back on the host (piper_hip_g711_from_pcm16 / _to_pcm16): the function the device applies.
+    public static func g711Encode(_ pcm: [Int16], law: Int32) throws -> [UInt8] {
+        var out = [UInt8](repeating: 0, count: pcm.count)
+        try check(piper_hip_g711_from_pcm16(law, pcm, pcm.count, &out))
+        return out
+    }
+
+    public static func g711Decode(_ bytes: [UInt8], law: Int32) throws -> [Int16] {
+        var out = [Int16](repeating: 0, count: bytes.count)
+        try check(piper_hip_g711_to_pcm16(law, bytes, bytes.count, &out))
+        return out
+    }
+
     /// (L, M, taps per phase) of a rate pair and its [L][P] coefficient table (piper_hip_resample_info / _taps; host-only).
     public static func resampleInfo(inRate: Int32, outRate: Int32) throws -> (l: Int32, m: Int32, taps: Int32) {
         var l: Int32 = 0, m: Int32 = 0, p: Int32 = 0

@@ -371,6 +371,75 @@ public final class PiperHIPRuntime {
         return out
     }
 
+    // ---- G.711 output: μ-law / A-law bytes companded on the device (include/piper_hip.h "G.711 output") ----
+
+    /// collectPCM16 ending in G.711 bytes (piper_hip_voice_collect_g711; law = PIPER_HIP_G711_MULAW or _ALAW) at `rate` (nil: the voice's
+    /// own): item b at J(its true samples), in any order with collect / collectPCM16.
+    public func collectG711(slot: Int32, law: Int32, rate: Int32? = nil, gain: Float = 1.0, normalize: Bool = false) throws -> [UInt8] {
+        let r = rate ?? sampleRate
+        var prm = piper_hip_pcm_params(gain: gain, normalize: normalize ? 1 : 0)
+        let nb = Int(piper_hip_voice_batch_size(voice, slot))
+        var per = [Int64](repeating: 0, count: max(nb, 1))
+        try HIPBackend.check(piper_hip_voice_prepared_samples(voice, slot, &per, Int32(nb), nil))   // a bounded slot: the capacity per item
+        var cap: Int64 = 0
+        for b in 0..<nb { cap += r == sampleRate ? per[b] : try resampleCount(per[b], rate: r) }
+        var bytes = [UInt8](repeating: 0, count: Int(cap))
+        try HIPBackend.check(piper_hip_voice_collect_g711(voice, slot, &prm, law, r, &bytes, cap))
+        try HIPBackend.check(piper_hip_voice_prepared_samples(voice, slot, &per, Int32(nb), nil))   // the true lengths now
+        var total: Int64 = 0
+        for b in 0..<nb { total += r == sampleRate ? per[b] : try resampleCount(per[b], rate: r) }
+        bytes.removeLast(bytes.count - Int(total))
+        return bytes
+    }
+
+    /// synthesizePCM16 ending in G.711 bytes (piper_hip_voice_synthesize_g711).
+    public func synthesizeG711(phonemeIDs: [Int64], durations: [Int32], noise: [Float]?, noiseScale: Float, law: Int32, rate: Int32? = nil,
+                               gain: Float = 1.0, normalize: Bool = false) throws -> [UInt8] {
+        let r = rate ?? sampleRate
+        var n: Int64 = 0
+        var prm = piper_hip_pcm_params(gain: gain, normalize: normalize ? 1 : 0)
+        return try phonemeIDs.withUnsafeBufferPointer { ids in try durations.withUnsafeBufferPointer { dur in
+            try (noise ?? []).withUnsafeBufferPointer { nz in
+                var u = piper_hip_utterance(phoneme_ids: ids.baseAddress, t: Int32(ids.count), durations: dur.baseAddress,
+                                            noise: noise == nil ? nil : nz.baseAddress, noise_scale: noiseScale,
+                                            noise_mode: Int32(PIPER_HIP_NOISE_INJECTED), seed: 1234, length_scale: 1.0, noise_w: 0.8, dp_noise: nil)
+                let samples = piper_hip_voice_num_samples(voice, &u)
+                var bytes = [UInt8](repeating: 0, count: Int(r == sampleRate ? samples : try resampleCount(samples, rate: r)))
+                try HIPBackend.check(piper_hip_voice_synthesize_g711(voice, &u, &prm, law, r, &bytes, Int64(bytes.count), &n))
+                return bytes
+            }
+        } }
+    }
+
+    /// The next chunk of the single stream on `slot` as G.711 bytes (piper_hip_voice_stream_next_g711), at the slot's rate; empty at the
+    /// end of the stream. The law is an argument of the step: PCM and G.711 steps may alternate.
+    public func streamNextG711(slot: Int32, law: Int32, gain: Float = 1.0) throws -> [UInt8] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: 0)
+        var buf = [UInt8](repeating: 0, count: try streamStepCapacity(slot: slot))
+        var n: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_stream_next_g711(voice, slot, &prm, law, &buf, Int64(buf.count), &n))
+        return Array(buf[0..<Int(n)])
+    }
+
+    /// The next chunk of every active item of a group or pool as G.711 bytes (piper_hip_voice_stream_next_batch_g711), keyed by item.
+    public func streamNextBatchG711(slot: Int32, rows: Int32, law: Int32, gain: Float = 1.0) throws -> [Int32: [UInt8]] {
+        var prm = piper_hip_pcm_params(gain: gain, normalize: 0)
+        var buf = [UInt8](repeating: 0, count: try streamStepCapacity(slot: slot))
+        var counts = [Int64](repeating: 0, count: Int(rows))
+        try HIPBackend.check(piper_hip_voice_stream_next_batch_g711(voice, slot, &prm, law, &buf, Int64(buf.count), &counts))
+        var out = [Int32: [UInt8]](), off = 0
+        for (item, c) in counts.enumerated() where c > 0 {
+            out[Int32(item)] = Array(buf[off..<off + Int(c)])
+            off += Int(c)
+        }
+        return out
+    }
+
+    /// A mono G.711 WAV (format tag 7 / 6, fact chunk) from bytes that are companded already (piper_hip_wav_write_g711).
+    public func writeWav(g711 bytes: [UInt8], law: Int32, rate: Int32, to path: String) throws {
+        try HIPBackend.check(piper_hip_wav_write_g711(path, law, bytes, bytes.count, rate))
+    }
+
     /// A mono WAV from samples that are 16-bit PCM already, at the rate they were delivered (piper_hip_wav_write_pcm16).
     public func writeWav(pcm: [Int16], rate: Int32, to path: String) throws {
         try HIPBackend.check(piper_hip_wav_write_pcm16(path, pcm, pcm.count, rate))
