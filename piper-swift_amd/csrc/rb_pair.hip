@@ -10,12 +10,13 @@
 //
 // Here a block computes BOTH convs of a pair for a column tile:
 //   stage   lrelu(x) window  [C × (256 + 2·pa)]  → LDS (aligned float4, zero outside [0, len))
-//   conv a  x1 = [x +] conv_a(lrelu(x)) + bias on 8 column tiles of 32 (= the output tiles + a halo each side: 16 columns
-//           when conv b reaches ≤ 16 positions ⇒ 7 output tiles, else 48 ⇒ 5); lrelu(x1) → LDS (zero outside [0, len): it is
+//   conv a  x1 = [x +] conv_a(lrelu(x)) + bias on 8 column tiles of 32 (= the output columns + a halo each side: conv b's
+//           reach pb = (Kb−1)·dilb/2, so 256 − 2·pb output columns); lrelu(x1) → LDS (zero outside [0, len): it is
 //           the NEXT conv's zero-padded input), raw x1 → the dead x window (ResBlock2's residual)
-//   conv b  y = (x1 | x) + conv_b(lrelu(x1)) + bias on the output tiles → global (buffer stores)
+//   conv b  y = (x1 | x) + conv_b(lrelu(x1)) + bias on the ceil(output columns / 32) output tiles, the last one partial
+//           → global (buffer stores)
 // One read of x and one write of y per pair instead of three reads and two writes, one launch instead of two, and a wave
-// runs 2 × (2 tiles × 16·K·C/32) MFMAs between its prologue and epilogue. The halo recompute costs 8/7 (8/5) on conv a.
+// runs 2 × (2 tiles × 16·K·C/32) MFMAs between its prologue and epilogue. The halo recompute costs 256 / (256 − 2·pb) on conv a.
 // The K-loops hold no vector ALU work beyond one address add per LDS read pair (see lrelu_max below for why).
 // Exact fp32 (v_mfma_f32_32x32x2_f32), the same contraction order as conv_win_kernel (tap-major, channel pairs ascending).
 #include <algorithm>
@@ -32,10 +33,27 @@ constexpr int kRA = 8;        // float4 weight groups in flight (32 steps)
 constexpr int kStepPad = 16;  // conv_win's fragment image pads steps to a multiple of 16
 constexpr int kWN = 4, kNTW = 2, kT1 = kWN * kNTW;
 constexpr int kColsA = 32 * kT1;        // 256 columns of x1 per block
-// x1 columns each side of the block's output columns: 16 when conv b reaches ≤ 16 positions (7 output tiles per block),
-// otherwise 48 (5 output tiles; Piper medium's third ResBlock: kernel 7, dilation 12 ⇒ reach 36)
-__host__ __device__ constexpr int halo_of(int pb) { return pb <= 16 ? 16 : 48; }
-constexpr int kMaxReachB = 48;
+// Column tiling of a pair whose conv b reaches pb positions each side. EXACT (the default): the halo IS the reach, so the 256
+// x1 columns yield 256 − 2·pb output columns (Piper medium: 252 / 232 / 184 for reach 2 / 12 / 36) in ceil(·/32) conv-b
+// tiles, the last one partial; a last tile with fewer than kMinLiveCols live columns is not worth its K-loop and is dropped
+// (232 → 224). Rounded (PIPER_HIP_PAIR_HALO_ROUNDED=1, the A/B): halo 16 for pb ≤ 16, else 48 ⇒ 224 or 160 columns, whole tiles.
+#ifndef PH_PAIR_MIN_LIVE
+#define PH_PAIR_MIN_LIVE 16
+#endif
+constexpr int kMinLiveCols = PH_PAIR_MIN_LIVE;
+template <bool EXACT>
+__host__ __device__ constexpr int halo_of(int pb) { return EXACT ? pb : (pb <= 16 ? 16 : 48); }
+template <bool EXACT>
+__host__ __device__ constexpr int out_cols_of(int pb) {
+  const int n = kColsA - 2 * halo_of<EXACT>(pb);
+  return (n & 31) < kMinLiveCols ? n & ~31 : n;
+}
+constexpr int kMaxReachB = 48;  // ⇒ at least 160 output columns per tile
+// A partial last conv-b tile reads lrelu(x1) columns up to 255 + 2·pb of its row: the row padding, then the next row, and
+// past the last row the bias table that follows the image — always inside the block's LDS (W1 ≥ 256, the table holds
+// kWinMulti·2·C floats). Those columns are never initialised and need not be: a B-operand column feeds only the output column
+// of the same index, and epilogue b stores no column at or past the tile's output width.
+static_assert(2 * kMaxReachB + 31 < kWinMulti * 2 * 32, "conv b's over-read past x1 column 255 must end inside the bias table");
 constexpr int kStageU = 10;            // float4 window loads per thread, all in flight: C·Wx/4 ≤ kStageU·threads
 
 struct RbPairMulti {
@@ -76,7 +94,10 @@ struct PairSched {
 // PERSISTENT: a block loops over its tiles; while it multiplies tile i, the window of tile i+1 is already on its way from
 // memory into registers (issued at the start of conv a, committed to LDS after conv b), and the weight ring of the next conv
 // is always started before the epilogue in front of it.
-template <int MT>
+// EXACT: the column tiling above, and conv-b tile j on wave column j % 4 (6 tiles ⇒ 2,2,1,1 per wave column, 8 ⇒ 2,2,2,2) —
+// the blocked mapping (tiles 2·wn, 2·wn + 1) would give 6 tiles as 2,2,2,0 and load the SIMDs of wave columns 0 and 2 with
+// four tile loops where 5 tiles loaded them with three.
+template <int MT, bool EXACT>
 __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairMulti multi, const PairSched sch, const int Wx, const int W1,
                                                                const unsigned inv_w4) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -98,6 +119,9 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
     biasS[i] = rem < C ? p.ba[rem] : p.bb[rem - C];
   }
   const int rowlane = wm * 32 + 4 * h;
+  // first column of this wave's j-th tile: conv a (and the rounded conv b) — tiles 2·wn, 2·wn + 1; EXACT conv b — wn, wn + 4
+  constexpr int kStrideB = EXACT ? 32 * kWN : 32;
+  const int tcol_a = wn * kNTW * 32, tcol_b = EXACT ? wn * 32 : tcol_a;
   const unsigned lane16 = (unsigned)lane * 16u;
   const int G = (int)gridDim.x, bid = (int)blockIdx.x;
 
@@ -105,7 +129,7 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
     const float *x, *wa4, *wb4;
     float* y;
     int bias_off;  // of conv a in biasS; conv b: + C
-    int Ka, dila, Kb, dilb, res_a, res_b_x, L, Lv, pa, pb, halo, c0, ga, shift, Sa, Spa, Sb, Spb, ntb;
+    int Ka, dila, Kb, dilb, res_a, res_b_x, L, Lv, pa, pb, halo, ncb, c0, ga, shift, Sa, Spa, Sb, Spb, ntb;
     float alpha;
   };
   auto tile_index = [&](int round) {
@@ -127,15 +151,16 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
     t.Ka = p.Ka; t.dila = p.dila; t.Kb = p.Kb; t.dilb = p.dilb; t.res_a = p.res_a; t.res_b_x = p.res_b_x; t.L = p.L; t.alpha = p.alpha;
     t.Lv = p.len_ptr ? min(p.len_ptr[n] * p.len_mul, p.L) : p.L;
     t.pa = (p.Ka - 1) * p.dila / 2; t.pb = (p.Kb - 1) * p.dilb / 2;
-    t.halo = halo_of(t.pb);
-    const int ncb = kColsA - 2 * t.halo;            // output columns per tile: 224 or 160
-    t.c0 = bx * ncb;                                 // first output column
+    t.halo = halo_of<EXACT>(t.pb);
+    t.ncb = out_cols_of<EXACT>(t.pb);                // output columns per tile
+    t.c0 = bx * t.ncb;                               // first output column
     const int g0 = t.c0 - t.halo - t.pa;             // input position of window column `shift`
     t.ga = g0 & ~3;
     t.shift = g0 - t.ga;
     t.Sa = p.Ka * C2; t.Spa = (t.Sa + kStepPad - 1) / kStepPad * kStepPad;
     t.Sb = p.Kb * C2; t.Spb = (t.Sb + kStepPad - 1) / kStepPad * kStepPad;
-    t.ntb = min(max((ncb >> 5) - wn * kNTW, 0), kNTW);  // this wave's conv-b tiles
+    const int ntb_all = (t.ncb + 31) >> 5;          // conv-b tiles of the block; this wave's share of them:
+    t.ntb = EXACT ? min(max((ntb_all - wn + kWN - 1) / kWN, 0), kNTW) : min(max(ntb_all - wn * kNTW, 0), kNTW);
     return t;
   };
 
@@ -180,8 +205,8 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
 
   // ---- one conv over this wave's column tiles: B straight from an LDS image [C][Wrow], A through the ring
   f32x16 acc[kNTW];
-  auto run_conv = [&](auto nt_tag, const float* img, const int Wrow, const int S, const int Sp, const int dil, const int col0, const int bias_off) {
-    constexpr int NT = decltype(nt_tag)::value;
+  auto run_conv = [&](auto nt_tag, auto stride_tag, const float* img, const int Wrow, const int S, const int Sp, const int dil, const int col0, const int bias_off) {
+    constexpr int NT = decltype(nt_tag)::value, STRIDE = decltype(stride_tag)::value;  // tiles, and columns from one to the next
 #pragma unroll
     for (int g4 = 0; g4 < 4; g4++) {  // register q of lane (r,h): row (q&3) + 8·(q>>2) + 4·h
       const float4 bv = *(const float4*)(biasS + bias_off + rowlane + 8 * g4);
@@ -196,7 +221,7 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
 #pragma unroll
       for (int e = 0; e < 4; e++) {
 #pragma unroll
-        for (int j = 0; j < NT; j++) b[slot][j][e] = img[lbase + sidx + 32 * j];
+        for (int j = 0; j < NT; j++) b[slot][j][e] = img[lbase + sidx + STRIDE * j];
         c_n++;
         const bool wrap = c_n == C2;
         c_n = wrap ? 0 : c_n;
@@ -258,11 +283,11 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
     // requested right after the conv in front of the epilogue that uses it. Buffer loads: lane part of the address in one
     // register, row part a scalar offset; out of range ⇒ 0.
     float resx[kNTW][16];
-    auto load_res = [&](int gres0) {
+    auto load_res = [&](int gres0, int tcol, int stride) {
       const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)cur.x, 0, C * cur.L * 4, 0x00020000);
 #pragma unroll
       for (int j = 0; j < kNTW; j++) {
-        const int g = gres0 + (wn * kNTW + j) * 32 + rr;
+        const int g = gres0 + tcol + stride * j + rr;
         const int voff = (g >= 0 && g < cur.L) ? (rl * cur.L + g) * 4 : -4;
 #pragma unroll
         for (int q = 0; q < 16; q++) resx[j][q] = bload(rx, voff, ((q & 3) + 8 * (q >> 2)) * cur.L * 4);
@@ -278,10 +303,10 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
     // prefetch / commit stay (block-uniform)
     const bool live = cur.c0 < cur.Lv;
     // ======== conv a: x1 columns [c0 − halo, c0 − halo + 256) = tiles wn·2, wn·2 + 1 of the tile's 8
-    if (live) run_conv(std::integral_constant<int, kNTW>{}, xs, Wx, cur.Sa, cur.Spa, cur.dila, cur.shift + wn * kNTW * 32, cur.bias_off);
+    if (live) run_conv(std::integral_constant<int, kNTW>{}, std::integral_constant<int, 32>{}, xs, Wx, cur.Sa, cur.Spa, cur.dila, cur.shift + tcol_a, cur.bias_off);
     PH_STAMP(2);
     if (live) ring_start(cur.wb4, cur.Spb);  // conv b's ring: its round trip hides behind the x1 epilogue and the barriers
-    if (live && cur.res_a) load_res(cur.c0 - cur.halo);
+    if (live && cur.res_a) load_res(cur.c0 - cur.halo, tcol_a, 32);
     __syncthreads();               // every wave is done reading the x window: its memory now takes the raw x1
     PH_STAMP(3);
 
@@ -289,7 +314,7 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
        // residual). register q of lane (r,h): row (q&3) + 8·(q>>2) + 4·h, column r
 #pragma unroll
       for (int j = 0; j < kNTW; j++) {
-        const int colw = (wn * kNTW + j) * 32 + rr;       // x1 column
+        const int colw = tcol_a + j * 32 + rr;            // x1 column
         const int g = cur.c0 - cur.halo + colw;           // its position in the row
         const bool in = g >= 0 && g < cur.Lv;
 #pragma unroll
@@ -307,24 +332,26 @@ __global__ __launch_bounds__(MT * kWN * 64, 2) void rb_pair_kernel(const RbPairM
     __syncthreads();
 
     PH_STAMP(4);
-    // ======== conv b: the tile's output tiles, two per wave column (the last ones get one or none)
+    // ======== conv b: the tile's output tiles, up to two per wave column (the last ones get one or none)
     if (live && cur.ntb > 0) {
-      const int col0b = cur.halo - cur.pb + wn * kNTW * 32;
+      const int col0b = cur.halo - cur.pb + tcol_b;  // EXACT: halo = pb
       __builtin_amdgcn_s_waitcnt(0x0F70);
-      if (cur.ntb == 2) run_conv(std::integral_constant<int, 2>{}, x1s, W1, cur.Sb, cur.Spb, cur.dilb, col0b, cur.bias_off + C);
-      else run_conv(std::integral_constant<int, 1>{}, x1s, W1, cur.Sb, cur.Spb, cur.dilb, col0b, cur.bias_off + C);
+      if (cur.ntb == 2) run_conv(std::integral_constant<int, 2>{}, std::integral_constant<int, kStrideB>{}, x1s, W1, cur.Sb, cur.Spb, cur.dilb, col0b, cur.bias_off + C);
+      else run_conv(std::integral_constant<int, 1>{}, std::integral_constant<int, kStrideB>{}, x1s, W1, cur.Sb, cur.Spb, cur.dilb, col0b, cur.bias_off + C);
     }
     PH_STAMP(5);
     if (has_next) ring_start(nxt.wa4, nxt.Spa);  // next tile's conv a ring: lands during the epilogue and the barriers
-    if (live && cur.res_b_x && cur.ntb > 0) load_res(cur.c0);
+    if (live && cur.res_b_x && cur.ntb > 0) load_res(cur.c0, tcol_b, kStrideB);
     if (live && cur.ntb > 0) {  // y = acc (bias inside) + (x | x1) → global; 2 rows × 32 consecutive columns per store instruction
       const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)cur.y, 0, C * cur.L * 4, 0x00020000);
 #pragma unroll
       for (int j = 0; j < kNTW; j++) {
         if (j >= cur.ntb) break;
-        const int colo = (wn * kNTW + j) * 32 + rr;        // output column within the tile
+        const int colo = tcol_b + j * kStrideB + rr;       // output column within the tile
         const int g = cur.c0 + colo;
-        const int voff = g < cur.L ? (rl * cur.L + g) * 4 : -4;  // −4: out of range ⇒ the store is dropped
+        // −4: out of range ⇒ the store is dropped. colo ≥ ncb (partial last tile): the neighbouring block's columns, and
+        // computed here from x1 columns this block does not have
+        const int voff = (colo < cur.ncb && g < cur.L) ? (rl * cur.L + g) * 4 : -4;
 #pragma unroll
         for (int q = 0; q < 16; q++) {
           const int rq = (q & 3) + 8 * (q >> 2);
@@ -362,22 +389,31 @@ PairGeom pair_geom(int C, int pa_max, int pb_max) {
   for (int pass = 0; pass < 2; pass++) {
     g.Wx = pad(kColsA + 2 * pa_max + 3, pass == 0);
     g.W1 = pad(kColsA, pass == 0);
-    (void)pb_max;
+    (void)pb_max;  // conv b's reach costs no LDS: see the static_assert at kMaxReachB
     g.lds = ((size_t)C * g.Wx + 4 + (size_t)C * g.W1 + (size_t)kWinMulti * 2 * C) * sizeof(float);
     if (g.lds <= 160 * 1024 && (C * g.Wx) / 4 <= kStageU * (C / 32) * kWN * 64) break;
   }
   return g;
 }
 
-template <int MT>
+template <int MT, bool EXACT>
 void launch_pair_inst(piper_hip_ctx* ctx, hipStream_t s, const RbPairMulti& m, const PairSched& sch, const PairGeom& g) {
   static bool raised[kMaxDevices] = {};
   if (g.lds > 64 * 1024 && lds_optin_needed(raised))
-    (void)hipFuncSetAttribute((const void*)rb_pair_kernel<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)rb_pair_kernel<MT, EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const unsigned inv = (unsigned)(0x100000000ull / (unsigned)(g.Wx >> 2)) + 1u;
   const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / g.lds)));  // resident blocks per CU (LDS; ≤ 256 VGPRs ⇒ ≤ 2 waves/SIMD)
   const int grid = std::min(sch.total, per_cu * ctx->num_cus);
-  hipLaunchKernelGGL((rb_pair_kernel<MT>), dim3(grid), dim3(MT * kWN * 64), g.lds, s, m, sch, g.Wx, g.W1, inv);
+  hipLaunchKernelGGL((rb_pair_kernel<MT, EXACT>), dim3(grid), dim3(MT * kWN * 64), g.lds, s, m, sch, g.Wx, g.W1, inv);
+}
+
+// Which tiling a launch of C channels takes (one rule per launch: its pairs share the kernel instantiation).
+// PIPER_HIP_PAIR_HALO_ROUNDED=1 restores the 16 / 48 halos and the blocked conv-b tile mapping (A/B, and the bit-identity test:
+// either tiling gives every output element the same contraction order).
+bool pair_exact_tiles(int C) {
+  static const bool rounded = getenv("PIPER_HIP_PAIR_HALO_ROUNDED") != nullptr;
+  (void)C;
+  return !rounded;
 }
 
 }  // namespace
@@ -416,24 +452,26 @@ int launch_rb_pair_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairArgs* pa
   if (g.lds > 160 * 1024 || (a.C * g.Wx) / 4 > kStageU * (a.C / 32) * kWN * 64)
     PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "rb_pair: window of %zu bytes (row %d) exceeds LDS / the staging registers", g.lds, g.Wx);
   std::sort(idx, idx + count, [&](int l, int r2) { return pairs[l].Ka + pairs[l].Kb > pairs[r2].Ka + pairs[r2].Kb; });
+  const bool exact = pair_exact_tiles(a.C);
   PairSched sch = {};
   sch.batch = a.N;
   for (int i = 0; i < count; i++) {
     const RbPairArgs& b = pairs[idx[i]];
     sch.order |= idx[i] << (4 * i);
-    sch.ntx[i] = (int)ceil_div(a.L, kColsA - 2 * halo_of((b.Kb - 1) * b.dilb / 2));
+    const int pb = (b.Kb - 1) * b.dilb / 2;
+    sch.ntx[i] = (int)ceil_div(a.L, exact ? out_cols_of<true>(pb) : out_cols_of<false>(pb));
     sch.cnt[i] = sch.ntx[i] * a.N;
     sch.total += sch.cnt[i];
   }
   for (int i = count; i < kWinMulti; i++) { sch.ntx[i] = 1; sch.cnt[i] = 0; }
   RbPairMulti m;
   for (int i = 0; i < kWinMulti; i++) m.c[i] = pairs[i < count ? i : 0];
-  if (a.C == 32) launch_pair_inst<1>(ctx, s, m, sch, g);
-  else launch_pair_inst<2>(ctx, s, m, sch, g);
+  if (a.C == 32) exact ? launch_pair_inst<1, true>(ctx, s, m, sch, g) : launch_pair_inst<1, false>(ctx, s, m, sch, g);
+  else exact ? launch_pair_inst<2, true>(ctx, s, m, sch, g) : launch_pair_inst<2, false>(ctx, s, m, sch, g);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rb_pair launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;
 }
 
 }  // namespace ph
-namespace ph { namespace { PH_WARM(rb_pair, (rb_pair_kernel<1>)); } }
+namespace ph { namespace { PH_WARM(rb_pair, (rb_pair_kernel<1, true>)); } }

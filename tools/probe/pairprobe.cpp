@@ -103,7 +103,7 @@ int main(int argc, char** argv) {
     const char* names[8] = {"top", "ring-a wait", "conv a", "ring b + res + barrier", "epilogue a + barrier", "conv b", "ring a' + epilogue b", "barrier + commit + barrier"};
     const int waves = C / 8;  // per block
     for (int round = 0; round < 4; round++) {
-      double sum[8] = {0}, tile = 0;
+      double sum[8] = {0}, tile = 0, convb[4] = {0};  // convb: by wave column (wave w of a block: column w / (C / 32))
       int cnt = 0;
       unsigned long long kmin = ~0ull, kmax = 0;
       for (int b = 0; b < 512; b++)
@@ -113,12 +113,14 @@ int main(int argc, char** argv) {
           for (int k = 1; k < 7; k++) sum[k] += (double)(t[k] - t[k - 1]);
           if (t[7]) sum[7] += (double)(t[7] - t[6]);
           tile += (double)(t[6] - t[0]);
+          convb[w / (C / 32)] += (double)(t[5] - t[4]);
           kmin = std::min(kmin, t[0]); kmax = std::max(kmax, t[6]);
           cnt++;
         }
       if (!cnt) continue;
       printf("  round %d (%d waves): tile %.0f ticks; span of the round %.0f ticks (s_memtime: shader cycles)\n", round, cnt, tile / cnt, (double)(kmax - kmin));
       for (int k = 1; k < 8; k++) printf("    %-28s %8.1f ticks\n", names[k], sum[k] / cnt);
+      printf("    conv b by wave column        %8.1f %8.1f %8.1f %8.1f ticks\n", convb[0] * 4 / cnt, convb[1] * 4 / cnt, convb[2] * 4 / cnt, convb[3] * 4 / cnt);
     }
   }
 #endif
