@@ -58,8 +58,10 @@ def report_line(label, rows, ref_s, **extra):
     print("FRONTEXACT " + json.dumps(dict(case=label, worst={k: round(v, 5) for k, v in fr.worst_by_kind(rows).items()}, ref_s=round(ref_s, 2), **extra)))
 
 
-def run_and_verify(rt, blob, slot, utts, label, check_z=True):
-    """prepare + launch + collect, z of every item against the oracle, then every front step of every item. → (audio, rows, step names)."""
+def run_and_verify(rt, blob, slot, utts, label, check_z=True, z_max_ids=None, att_floorless=False):
+    """prepare + launch + collect, z of every item against the oracle (z_max_ids: only of the items with at most that many ids — the CPU
+    oracle's flow is the slow part of a long item, which the steps cover one by one), then every front step of every item (att_floorless:
+    front_ref.verify's keyword). → (audio, rows, step names)."""
     cfg = rt.cfg
     if len(utts) == 1:
         rt.prepare(slot, *utts[0], fr.NOISE_SCALE)
@@ -72,10 +74,12 @@ def run_and_verify(rt, blob, slot, utts, label, check_z=True):
         z = rt.tap(slot, "z")
         offs = np.concatenate([[0], np.cumsum(lensF)]) * cfg.inter
         for b, u in enumerate(utts):
+            if z_max_ids is not None and len(u[0]) > z_max_ids:
+                continue
             _, taps = orc.synthesize(cfg, blob, u[0], u[1], u[2], fr.NOISE_SCALE, taps=True)
             assert_close(z[offs[b]:offs[b + 1]], taps["z"].reshape(-1), OP_TOL, f"{label}[{b}]: z vs oracle")
     dev = fr.GpuDevice(rt, slot, lensT, lensF)
-    rows, ref_s = fr.verify(dev, cfg, blob, [fr.Inputs(*u) for u in utts], label)
+    rows, ref_s = fr.verify(dev, cfg, blob, [fr.Inputs(*u) for u in utts], label, att_floorless=att_floorless)
     # the tensor "z" the generator reads is the buffer the last flow step left the latent in
     report_line(label, rows, ref_s, T=lensT, F=lensF)
     return audio, rows, [n for n in dev.steps() if fr.is_front_step(n)]

@@ -16,6 +16,7 @@ import wave
 import numpy as np
 import pytest
 
+import att_ref
 import front_ref as fr
 import katdata as kd
 import oracle as orc
@@ -98,8 +99,10 @@ def test_single_utterance_vs_oracle(T, bucket, rt_xl, xl, refs):
 @pytest.mark.parametrize("T,bucket", [(1030, 1040), (2050, 2064)])
 def test_long_rows_encoder_vs_oracle(T, bucket, rt_xl, xl):
     """Above 1024 the register-fragment kernels: att_mfma<48, 16> up to 2048, att_mfma<48, 8> above (id rows are bucketed in steps of 16 at
-    every length: 1040 and 2064). Only the encoder is compared (enc_out, m_p, logs_p against oracle.text_encoder) so the CPU generator is
-    not paid for; one frame per id."""
+    every length: 1040 and 2064). The true lengths lie 10 and 14 columns below the bucket, so what this reaches of the length masking is
+    the last key tile only, and enc_out under the rule with the floor; lengths far below the bucket and at the tile and chunk edges, and
+    the attention step itself without the floor, are in tests/test_gpu_attention_lengths.py. Only the encoder is compared (enc_out, m_p,
+    logs_p against oracle.text_encoder) so the CPU generator is not paid for; one frame per id."""
     cfg, blob = xl
     ids = np.random.RandomState(T).randint(0, 130, size=T).tolist()
     dur = [1] * T
@@ -341,3 +344,5 @@ def test_rel_attention_op(d, T, backend):
     out, shp = b.relAttentionF32(*(b.uploadFloat32(a) for a in (q, k, v, ek, ev)), 1, H, d, T, w)
     got = b.downloadFloat32(out, int(np.prod(shp))).reshape(shp)
     assert_close(got, orc.rel_attention(q, k, v, ek, ev, H, d, T, w), OP_TOL, f"rel_attention d={d} T={T}")
+    r = att_ref.floorless(got, att_ref.rel_attention(q, k, v, ek, ev, H, d, T, w))  # and without the floor, against float64
+    assert r["ok"], f"d={d} T={T}: max|Δ| {r['err']:.3e} is {r['ratio']:.2f} × OP_TOL · ‖ref‖∞"

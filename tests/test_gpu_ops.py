@@ -4,6 +4,7 @@ Mirrors how the reference would test MetalBackend per op (it has no such tests: 
 import numpy as np
 import pytest
 
+import att_ref
 import katdata as kd
 import oracle as orc
 import piper_hip as ph
@@ -168,6 +169,8 @@ def test_rel_attention(T, backend, golden_mods):
     assert_close(y, orc.rel_attention(q, k, v, ek, ev, 2, 96, T, 4), OP_TOL, "vs oracle")
     if f"rel_attention.T{T}" in golden_mods:
         assert_close(y, golden_mods[f"rel_attention.T{T}"], OP_TOL, "vs golden")
+    r = att_ref.floorless(y, att_ref.rel_attention(q, k, v, ek, ev, 2, 96, T, 4))  # and without the floor, against float64
+    assert r["ok"], f"T={T}: max|Δ| {r['err']:.3e} is {r['ratio']:.2f} × OP_TOL · ‖ref‖∞"
 
 
 def test_rel_attention_equals_unfused_ops(backend):

@@ -392,9 +392,11 @@ def test_ragged_batch_and_bucketed_plans(rt_medium, voices):
 
 
 def test_key_split_attention_with_true_lengths(rt_medium, voices):
-    """Rows of more than one key tile run the attention core key-split (parts + merge kernel); the number of parts a block sees
-    depends on the item's TRUE length, not on the bucket: a 2-item batch in the T = 304 bucket whose items end inside the third and
-    inside the second key tile, each against the oracle run alone (enc_out tap and waveform)."""
+    """Rows of more than one key tile run the attention core key-split (parts + merge kernel); the number of parts that hold a key
+    depends on the item's TRUE length, not on the bucket: a 2-item batch in the T = 304 bucket (76 blocks: three parts on 228 CUs or
+    more, two from 152) whose items end inside the third and inside the second key tile, so the merge skips one whole part of the
+    second item; each against the oracle run alone (enc_out tap and waveform, the rule with the floor). An item with two parts
+    without a key, and the attention step itself without the floor, are in tests/test_gpu_attention_lengths.py."""
     cfg, blob = voices["medium"]
     rng = np.random.RandomState(33)
     utts = []
