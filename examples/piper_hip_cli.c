@@ -18,6 +18,10 @@
  *                            (piper_hip_voice_collect_g711 / synthesize_g711) — --output-raw is then one byte per sample, --output a
  *                            G.711 WAV at the output rate (piper_hip_wav_write_g711); combinable with --output-rate, --volume and
  *                            --normalize (with a law the last two act on --output as well: the file holds the same bytes).
+ *   --speaker N              both modes: speaker N of a multi-speaker voice (the graph's `sid`; piper_hip_voice_attach_speakers +
+ *                            piper_hip_voice_slot_speakers). With --model the file's speaker table is loaded (opt-in: without the flag such a
+ *                            file is refused; its node graph is NOT verified — no verifier for the conditioned graph exists yet); without
+ *                            --model the synthetic voice gets a synthetic table of --speakers rows (8).
  * Without --model the synthetic voice of the tests is used (--quality medium|high|low|x_low; low and x_low are the 16 kHz tier); its duration predictor has random weights, so frames per id are
  * pinned to --pin-frames (3, the bench's convention) unless --predict asks for the predictor (the only mode a real voice has).
  *
@@ -176,7 +180,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
                     "                [--output-encoding s16le|mulaw|alaw]\n"
-                    "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n", argv[0], argv[0]);
+                    "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n"
+                    "               [--speaker N [--speakers S]]\n", argv[0], argv[0]);
     return 2;
   }
 
@@ -188,13 +193,35 @@ int main(int argc, char** argv) {
   r.noise_scale = 0.667f; r.length_scale = 1.0f; r.noise_w = 0.8f; /* PiperConfig defaults; the voice's .onnx.json overrides them */
   r.predict = has_flag(argc, argv, "--predict");
   r.pin_frames = arg_value(argc, argv, "--pin-frames") ? atoi(arg_value(argc, argv, "--pin-frames")) : 3;
+  /* --speaker N: the `sid` of a multi-speaker voice (PiperMetalRuntime.synthesize reads it next to the scales, PiperMetalRuntime.swift:62-80).
+   * Opt-in: without the flag a multi-speaker file is refused as before. */
+  const char* speaker_arg = arg_value(argc, argv, "--speaker");
+  const int speaker = speaker_arg ? atoi(speaker_arg) : -1;
+  if (speaker_arg && speaker < 0) { fprintf(stderr, "--speaker %s: expected a speaker id >= 0\n", speaker_arg); return 2; }
+  piper_hip_speaker_config scfg;
+  float* sblob = NULL;
+  memset(&scfg, 0, sizeof scfg);
   if (model) {
     piper_hip_onnx* m = NULL;
     CHECK(piper_hip_onnx_open(model, &m));
-    CHECK(piper_hip_onnx_infer_config(m, &cfg));
+    if (speaker_arg) {
+      CHECK(piper_hip_onnx_infer_config_speakers(m, &cfg));
+      CHECK(piper_hip_onnx_speaker_config(m, &cfg, &scfg));
+      if (scfg.n_speakers < 1) { fprintf(stderr, "--speaker: %s is a single-speaker voice\n", model); return 2; }
+    } else {
+      CHECK(piper_hip_onnx_infer_config(m, &cfg));
+    }
     CHECK(piper_hip_voice_blob_floats(&cfg, &n_floats));
     blob = (float*)malloc(n_floats * sizeof(float));
-    CHECK(piper_hip_onnx_build_blob(m, &cfg, blob, n_floats)); /* verifies the graph first */
+    if (scfg.n_speakers) { /* no verifier for the conditioned graph exists yet: the caller vouches that this is a standard multi-speaker Piper VITS */
+      size_t sn = 0;
+      CHECK(piper_hip_onnx_build_blob_unchecked(m, &cfg, blob, n_floats));
+      CHECK(piper_hip_speaker_blob_floats(&cfg, &scfg, &sn));
+      sblob = (float*)malloc(sn * sizeof(float));
+      CHECK(piper_hip_onnx_build_speaker_blob(m, &cfg, &scfg, sblob, sn));
+    } else {
+      CHECK(piper_hip_onnx_build_blob(m, &cfg, blob, n_floats)); /* verifies the graph first */
+    }
     piper_hip_onnx_close(m);
     r.predict = 1; /* a real voice decides its own durations */
     if (config) { /* PiperConfig (PiperConfig.swift:3-47): sample rate and the three inference scales */
@@ -211,6 +238,7 @@ int main(int argc, char** argv) {
       const int jrc = piper_hip_piper_json(text, &info);
       free(text);
       CHECK(jrc);
+      if (scfg.n_speakers) CHECK(piper_hip_voice_check_json_speakers(&cfg, &scfg, &info));
       if (info.sample_rate > 0) cfg.sample_rate = info.sample_rate;
       r.noise_scale = info.noise_scale; r.length_scale = info.length_scale; r.noise_w = info.noise_w;
     }
@@ -219,11 +247,27 @@ int main(int argc, char** argv) {
     CHECK(piper_hip_voice_blob_floats(&cfg, &n_floats));
     blob = (float*)malloc(n_floats * sizeof(float));
     CHECK(piper_hip_voice_synthetic_blob(&cfg, 1234, blob, n_floats));
+    if (speaker_arg) { /* the synthetic voice with a synthetic table of --speakers rows (8), gin 512 */
+      size_t sn = 0;
+      scfg.n_speakers = arg_value(argc, argv, "--speakers") ? atoi(arg_value(argc, argv, "--speakers")) : 8;
+      scfg.gin = 512;
+      CHECK(piper_hip_speaker_blob_floats(&cfg, &scfg, &sn));
+      sblob = (float*)malloc(sn * sizeof(float));
+      CHECK(piper_hip_speaker_synthetic_blob(&cfg, &scfg, 4321, sblob, sn));
+    }
   }
   piper_hip_ctx* ctx = NULL;
   CHECK(piper_hip_create(0, &ctx));
   CHECK(piper_hip_voice_create(ctx, &cfg, blob, 0, &r.voice));
   free(blob);
+  if (sblob) { /* the table before the first prepare, then slot 0's speaker for every utterance of this run */
+    piper_hip_speaker spk;
+    memset(&spk, 0, sizeof spk);
+    spk.n = 1; spk.ids[0] = speaker; spk.weights[0] = 1.0f;
+    CHECK(piper_hip_voice_attach_speakers(r.voice, &scfg, sblob, 0));
+    free(sblob);
+    CHECK(piper_hip_voice_slot_speakers(r.voice, 0, &spk, 1)); /* an id past the table: PIPER_HIP_ERR_ARG */
+  }
 
   if (!scale_bench) { /* one shot: ids → WAV */
     int64_t ids[4096];

@@ -382,9 +382,9 @@ typedef struct {
   float noise_scale, length_scale, noise_w;
 } piper_hip_piper_json_info;
 int piper_hip_piper_json(const char* json_text, piper_hip_piper_json_info* out);
-/* Is the voice the `.onnx.json` describes one this library renders correctly with geometry `cfg`? ERR_UNSUPPORTED for
- * num_speakers > 1 (speaker conditioning is not implemented: the audio would be wrong without any error), ERR_SHAPE when
- * num_symbols differs from the embedding rows of the graph. */
+/* Is the voice the `.onnx.json` describes one this library renders correctly with geometry `cfg` ALONE? ERR_UNSUPPORTED for
+ * num_speakers > 1 (without its speaker table the audio would be wrong without any error; the opt-in route is
+ * piper_hip_voice_check_json_speakers below), ERR_SHAPE when num_symbols differs from the embedding rows of the graph. */
 int piper_hip_voice_check_json(const piper_hip_voice_config* cfg, const piper_hip_piper_json_info* info);
 
 /* Waveform → 16-bit PCM / mono WAV (WavFileWriter.swift:20-30, 44-60): clamp to [−1,1], ×32767, truncate toward zero. */
@@ -662,6 +662,77 @@ int piper_hip_voice_stream_next_g711(piper_hip_voice* v, int slot, const piper_h
 int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
                                            int64_t max_samples, int64_t* n_samples);
 
+/* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
+ * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]
+ * (the graph's `sid` input, read by PiperMetalRuntime.synthesize next to `scales`, PiperMetalRuntime.swift:62-80; in the graph a Gather
+ * and Conv / Add nodes, GraphExecutor.swift:653-666, 1739-1810, 741-779):
+ *   duration predictor   x = dp.pre(x) + dp.cond(g)                                                     hidden channels
+ *   flow coupling f, WaveNet layer l
+ *                        acts = tanh(a + g_l[:H]) · sigmoid(b + g_l[H:]), [a;b] = in_layers[l](x),
+ *                        g_l = cond_layer(g)[2H·l : 2H·(l+1)]                                           2·hidden per layer
+ *   generator            x = dec.conv_pre(z) + dec.cond(g)                                              up_initial
+ * g has length 1 in time, so each of these is a per-item, per-channel constant added where the conv's own bias is added. The EFFECTIVE
+ * BIAS of a conditioned conv is e[c] = fl(b[c] + fl(bc[c] + d[c])): d[c] the fp32 dot product of cond row c with g (any summation order), bc
+ * the cond bias, b the conv's own bias; the consumer adds e exactly where it adds b in a voice without speakers, as one float. The rows
+ * of one item in the order dp.pre (hidden; no such rows with dp_present = 0); for f in 0 … n_flows − 1, for l in 0 … wn_layers − 1: 2·hidden each; dec.conv_pre (up_initial)
+ * form its SPEAKER ROW of Ctot = hidden + n_flows·wn_layers·2·hidden + up_initial floats (medium 6 592, high 6 848, x_low 3 424).
+ * A speaker is a short mix g = Σ_k w_k · emb_g[id_k], 1 ≤ n ≤ 4, accumulated in fp32 from 0.0f in ascending k (product rounded, then the
+ * sum): n = 1, w = 1.0 is the table row itself, the plain `sid`.
+ * Everything here is opt-in: a voice nobody attached a table to builds the schedules, step names and buffers it built before these
+ * symbols existed, and every refusal of a multi-speaker file stays at its entry point (piper_hip_onnx_infer_config,
+ * piper_hip_voice_check_json, piper_hip_onnx_verify_graph). */
+typedef struct {
+  int32_t n_speakers; /* 1 … 65 536 */
+  int32_t gin;        /* 4 … 1024, a multiple of 4 (Piper: 512) */
+} piper_hip_speaker_config;
+/* The speaker blob: packed fp32 like the voice blob, host-only entry points with the conventions of their voice twins. Tensor order:
+ * emb_g.weight [S, gin]; dp.cond.weight [hidden, gin, 1], dp.cond.bias (only with cfg->dp_present); for each coupling f:
+ * flow.flows.{2f}.enc.cond_layer.weight [2·hidden·wn_layers, gin, 1], .bias; dec.cond.weight [up_initial, gin, 1], dec.cond.bias.
+ * The synthetic rule is piper_hip_voice_synthetic_blob's (tensor i of THIS blob takes index i), cond weights with fan_in = gin, emb_g
+ * with fan_in = 1 (unit variance, like nn.Embedding). The voice blob, its layout and piper_hip_voice_config do not change. */
+int piper_hip_speaker_blob_floats(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg, size_t* n_floats);
+int piper_hip_speaker_blob_layout(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg, piper_hip_tensor_info* out,
+                                  int max_entries, int* n_entries);
+int piper_hip_speaker_synthetic_blob(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg, uint64_t seed, float* host_blob,
+                                     size_t n_floats);
+/* Give the voice its speaker table: once, before the voice's first prepare / predict / stream (later or twice: PIPER_HIP_ERR_ARG). Packs
+ * the table, the cond weights [Ctot, gin], the cond biases and the conditioned convs' own biases for the request-path kernel
+ * (csrc/speaker.hip); the blob is not retained. `on_device` as for piper_hip_voice_create. */
+int piper_hip_voice_attach_speakers(piper_hip_voice* v, const piper_hip_speaker_config* scfg, const float* blob, int on_device);
+int piper_hip_voice_num_speakers(const piper_hip_voice* v); /* 0 without a table (and for a NULL voice) */
+typedef struct {
+  int32_t n;        /* 1 … 4 mix entries */
+  int32_t ids[4];   /* rows of emb_g */
+  float weights[4];
+} piper_hip_speaker;
+/* The speakers of a slot id: entry i is for item i of every later prepare*, stream_begin* and synthesize* (slot 0) on that slot; for
+ * stream_pool_join it is the assignment of `work_slot`. Items past `n` take the last entry; n = 0 (spk may be NULL) resets to the default,
+ * speaker 0 alone. The assignment persists until replaced. A bad id, an entry's n outside 1 … 4, or a non-finite weight is
+ * PIPER_HIP_ERR_ARG, checked here on the host (the device never indexes past the table); n outside 0 … 256 is PIPER_HIP_ERR_ARG; a voice
+ * without a table is PIPER_HIP_ERR_UNSUPPORTED. The speakers reach the device with the ids and lengths of a prepare (plan inputs): one
+ * launch per plan ("spk.rows", the first step) computes the speaker rows of all its items — the predictor plan the dp.pre rows, the main
+ * plan the flow and generator rows — and a graph replay needs no host work. A stream carries each item's conv_pre row with its latent:
+ * a pool row keeps its speaker until it is freed. */
+int piper_hip_voice_slot_speakers(piper_hip_voice* v, int slot, const piper_hip_speaker* spk, int n);
+/* piper_hip_voice_predict_durations (which has no slot) with speakers[n], one per utterance (NULL: speaker 0 alone; on a voice without a
+ * table a non-NULL array is PIPER_HIP_ERR_UNSUPPORTED). */
+int piper_hip_voice_predict_durations_speakers(piper_hip_voice* v, const piper_hip_utterance* utts, int n, const piper_hip_speaker* speakers,
+                                               int32_t* durations_out, float* logw_out, int max_entries);
+/* Multi-speaker `.onnx` files, opt-in. piper_hip_onnx_infer_config, piper_hip_onnx_build_blob, piper_hip_voice_check_json and
+ * piper_hip_onnx_verify_graph refuse such a file exactly as before; a verifier for the conditioned graph does not exist yet, so the main
+ * blob of such a file comes from piper_hip_onnx_build_blob_unchecked and the caller vouches for the graph.
+ *   speaker_config          n_speakers = 0 (and gin = 0) when the file has no `emb_g.weight`; otherwise every cond tensor's presence and
+ *                           shape is checked against `cfg`: PIPER_HIP_ERR_SHAPE naming the tensor.
+ *   infer_config_speakers   infer_config without the refusal of `emb_g` / `cond` initializers.
+ *   build_speaker_blob      the cond tensors in the order above, folding weight_g / weight_v pairs as the main loader does.
+ *   check_json_speakers     check_json with num_speakers == n_speakers required instead of ≤ 1 (a missing or 0 count reads as 1). */
+int piper_hip_onnx_speaker_config(const piper_hip_onnx* m, const piper_hip_voice_config* cfg, piper_hip_speaker_config* scfg);
+int piper_hip_onnx_infer_config_speakers(const piper_hip_onnx* m, piper_hip_voice_config* cfg);
+int piper_hip_onnx_build_speaker_blob(const piper_hip_onnx* m, const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg,
+                                      float* host_blob, size_t n_floats);
+int piper_hip_voice_check_json_speakers(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg,
+                                        const piper_hip_piper_json_info* info);
+
 /* Debug taps ⇔ GraphExecutor.execute(maxNodeIndex:) returning intermediates (GraphExecutor.swift:75-152):
  * copy a named intermediate of the slot's last run to host. Names: "enc_out" [H,T], "m_p" [inter,T],
  * "logs_p" [inter,T], "z_p" [inter,F], "z" [inter,F], "dec_pre" [up_initial,F] — per batch item, compacted to the item's
@@ -692,7 +763,10 @@ int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const p
  *   "dp.dur" [1,T] (the int32 frames per id as raw bits).
  *   "predict:<tensor>[@<step>]"  addresses the cached encoder + duration-predictor plan of the slot's bucket T and batch size (the plan a
  *                            prepare without durations ran) with the slot's true lengths; PIPER_HIP_ERR_ARG when none is cached.
- *   "@steps"                 the schedule's launch names in order, one per line, one character code per float. */
+ *   "@steps"                 the schedule's launch names in order, one per line, one character code per float.
+ * A voice with a speaker table (piper_hip_voice_attach_speakers) adds, per batch item at a fixed length: "spk.g" [gin], the mixed speaker
+ * vector, and "spk.bias" [Ctot], the item's speaker row — a plan writes the rows it computes and leaves the others 0.0: the slot's plan the
+ * flow and generator rows, "predict:spk.bias" the dp.pre rows. */
 int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name, float* host, size_t max_floats,
                         size_t* n_floats);
 /* GPU milliseconds of the slot's last completed launch (hipEvent pair on the slot's stream) ⇔

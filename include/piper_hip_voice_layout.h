@@ -184,4 +184,26 @@ static inline size_t piper_hip_layout_walk(const piper_hip_voice_config* c, pipe
   return off;
 }
 
+/* The speaker blob of a multi-speaker voice (piper_hip.h "Multi-speaker voices"): the speaker table, then the k = 1 `cond` convs over
+ * g = emb_g[sid] in the order their rows take in an item's speaker row. Walks every tensor in order; returns the total float count. */
+static inline size_t piper_hip_speaker_layout_walk(const piper_hip_voice_config* c, const piper_hip_speaker_config* sc,
+                                                   piper_layout_visitor fn, void* user) {
+  size_t off = 0;
+  char p[96];
+  const long long H = c->hidden, G = sc->gin;
+  piper__emit(fn, user, &off, "emb_g.weight", PIPER_T_EMB, 2, sc->n_speakers, G, 1, 1); /* unit variance, like nn.Embedding */
+  if (c->dp_present) piper__conv(fn, user, &off, "dp.cond", H, G, 1, 1);
+  for (int f = 0; f < c->n_flows; f++) {
+    snprintf(p, sizeof p, "flow.flows.%d.enc.cond_layer", 2 * f);
+    piper__conv(fn, user, &off, p, 2 * H * c->wn_layers, G, 1, 1);
+  }
+  piper__conv(fn, user, &off, "dec.cond", c->up_initial, G, 1, 1);
+  return off;
+}
+/* Floats of one item's speaker row, and where the rows of dp.pre end (= where the flow's begin). */
+static inline long long piper_hip_speaker_dp_rows(const piper_hip_voice_config* c) { return c->dp_present ? c->hidden : 0; }
+static inline long long piper_hip_speaker_row_floats(const piper_hip_voice_config* c) {
+  return piper_hip_speaker_dp_rows(c) + (long long)c->n_flows * c->wn_layers * 2 * c->hidden + c->up_initial;
+}
+
 #endif /* PIPER_HIP_VOICE_LAYOUT_H */

@@ -44,6 +44,7 @@ struct ConvArgs {
   int64_t x_batch_stride = 0;  // floats between batch items of x (x2/x3 share it)
   int64_t y_batch_stride = 0;  // floats between batch items of y / res
   int64_t y2_batch_stride = 0;
+  int64_t bias_batch_stride = 0;  // floats between the bias rows of batch items; 0 = one row shared by all (speaker-conditioned convs: an item's effective bias)
   int in_ch_base = 0, in_ch_sign = 1;    // physical input channel = in_ch_base + in_ch_sign·ci  (folds Flip/Split)
   int out_ch_base = 0, out_ch_sign = 1;  // physical output channel of y/res = out_ch_base + out_ch_sign·co
   int y_len = 0;                         // row length of y/res/y2/skip (floats)

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void conv_direct_kernel(const ConvArgs p) {
     const int xo = (int)(gid % p.Lout);
     const int64_t t2 = gid / p.Lout;
     const int co = (int)(t2 % p.Cout), n = (int)(t2 / p.Cout);
-    float acc = p.bias ? p.bias[co] : 0.0f;
+    float acc = p.bias ? p.bias[(int64_t)n * p.bias_batch_stride + co] : 0.0f;
     const int ciBase = (co / cog) * cig;
     const float* xb = p.x + (int64_t)n * p.x_batch_stride;
     const float* x2b = PRO == PRO_AVG3_LRELU ? p.x2 + (int64_t)n * p.x_batch_stride : nullptr;
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kSmallBT) void conv_small_cout_kernel(const ConvArg
   if (p.len_ptr && t0 >= Lv) return;  // every output of this block lies past the true length ('same' convs: Lout = Lin); block-uniform
   float acc[COUT];
 #pragma unroll
-  for (int co = 0; co < COUT; co++) acc[co] = p.bias ? p.bias[co] : 0.0f;
+  for (int co = 0; co < COUT; co++) acc[co] = p.bias ? p.bias[(int64_t)n * p.bias_batch_stride + co] : 0.0f;
   for (int c0 = 0; c0 < p.Cin; c0 += kSmallCK) {
     const int ck = min(kSmallCK, p.Cin - c0);
     __syncthreads();
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(BT) void conv_cout1_wide_kernel(const ConvArgs p) {
   };
   float acc[4];
 #pragma unroll
-  for (int o = 0; o < 4; o++) acc[o] = p.bias ? p.bias[0] : 0.0f;  // bias first (CPUBackend.conv1d)
+  for (int o = 0; o < 4; o++) acc[o] = p.bias ? p.bias[(int64_t)n * p.bias_batch_stride] : 0.0f;  // bias first (CPUBackend.conv1d)
   issue(0);
   for (int c0 = 0; c0 < p.Cin; c0 += kWideCK) {
     __syncthreads();                     // the previous chunk's readers are done (first pass: ws is complete)
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void conv_cout1_split_kernel(const ConvArgs p)
   *(float4*)(red + wave * kOut + 4 * lane) = make_float4(acc[0], acc[1], acc[2], acc[3]);
   __syncthreads();
   // thread tid finishes output tid: bias first, then the four channel groups in order (deterministic)
-  float v = p.bias ? p.bias[0] : 0.0f;
+  float v = p.bias ? p.bias[(int64_t)n * p.bias_batch_stride] : 0.0f;
 #pragma unroll
   for (int w2 = 0; w2 < 4; w2++) v += red[w2 * kOut + tid];
   const int xo = t0 + tid;

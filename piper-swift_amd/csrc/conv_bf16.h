@@ -25,6 +25,7 @@ struct ConvBf16Args {
   const uint16_t* x = nullptr;  // C8 image of the input [N][Cin/8][x_row][8]
   const uint16_t* w = nullptr;  // packed fragments (pack_conv_weights_bf16 / pack_convt_weights_bf16)
   const float* bias = nullptr;  // [Cout] or null
+  int64_t bias_batch_stride = 0;  // floats between the bias rows of batch items; 0 = one row shared by all (conv_pre of a voice with speakers)
   const float* res = nullptr;   // fp32 [N][Cout][y_len] added to the result (residual stream), may be null
   const float* mrf_a = nullptr; // both set: result = ((mrf_a + mrf_b) + result) / 3  (HiFi-GAN MRF mean)
   const float* mrf_b = nullptr;

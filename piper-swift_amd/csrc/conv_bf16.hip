@@ -264,7 +264,7 @@ __global__ __launch_bounds__(kBT) void conv_bf16_kernel(const ConvBf16Multi mult
 #pragma unroll
     for (int q = 0; q < 16; q++) {
       const int coc = min(co0 + (q & 3) + 8 * (q >> 2) + 4 * h, p.Cout - 1);
-      bias_v[q] = p.bias ? p.bias[coc] : 0.0f;
+      bias_v[q] = p.bias ? p.bias[(int64_t)n * p.bias_batch_stride + coc] : 0.0f;
     }
 #pragma unroll
     for (int j = 0; j < NTW; j++) {

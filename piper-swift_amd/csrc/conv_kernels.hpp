@@ -250,13 +250,14 @@ __global__ __launch_bounds__(BT) void conv_stream_kernel(const ConvArgs p, const
   const int nsteps = ngroups * S;  // packed steps per row tile (zero-padded to whole groups)
 
   AccT acc[NA][NT];
+  const float* const bias_n = p.bias + (int64_t)n * p.bias_batch_stride;  // the item's bias row (stride 0: the shared one); only read when p.bias
 #pragma unroll
   for (int a = 0; a < NA; a++) {
     const int mbase = (a == 0 ? mt : mt + mt_eff) * TM;
 #pragma unroll
     for (int r = 0; r < NR; r++) {
       const int row = mbase + acc_row_t<TM>(r, lane);
-      const float b = (ks == 0 && p.bias && row < p.Cout) ? p.bias[bias_index(p, row)] : 0.0f;
+      const float b = (ks == 0 && p.bias && row < p.Cout) ? bias_n[bias_index(p, row)] : 0.0f;
 #pragma unroll
       for (int nt = 0; nt < NT; nt++) acc[a][nt][r] = b;
     }
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(256) void conv_tile_kernel(const ConvArgs p, const 
 #pragma unroll
     for (int r = 0; r < 16; r++) {
       const int row = (mt0 + m) * 32 + acc_row(r, lane);
-      const float b = (p.bias && row < p.Cout) ? p.bias[bias_index(p, row)] : 0.0f;
+      const float b = (p.bias && row < p.Cout) ? (p.bias + (int64_t)n * p.bias_batch_stride)[bias_index(p, row)] : 0.0f;
 #pragma unroll
       for (int nt = 0; nt < NTW; nt++) acc[m][nt][r] = b;
     }

@@ -36,6 +36,7 @@ struct LeanArgs {
   int out_ch_base, out_ch_sign;
   int x_batch_bytes;
   long long x_bs, y_bs, y2_bs;  // floats between batch items
+  long long bias_bs;            // floats between the items' bias rows (0: one shared row); honoured by conv_k1_kernel
 };
 
 __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(512) void conv_k1_kernel(const LeanArgs a, const in
   }
   // wave w (< 4) finishes accumulator register w: rows 16·mt + 4·kk + w; slices added in fixed order on top of the bias
   const int row = 16 * mt + 4 * kk + wave;
-  const float bias = (wave < 4 && a.bias) ? a.bias[min(row, a.Cout - 1)] : 0.0f;  // bias first (CPUBackend.swift:46-63)
+  const float bias = (wave < 4 && a.bias) ? a.bias[(long long)n * a.bias_bs + min(row, a.Cout - 1)] : 0.0f;  // bias first (CPUBackend.swift:46-63)
   for (int it = 0;; it++) {
     const int t0 = ch * 16;
     const int nxt = ch + (int)gridDim.y;
@@ -220,7 +221,7 @@ struct GateArgs {
   float* y;
   const int* len_ptr;
   int len_mul, Lin, Lout, rows_out, y_len, nsteps, pad, x_batch_bytes;
-  long long x_bs, y_bs;
+  long long x_bs, y_bs, bias_bs;  // floats between batch items (bias_bs 0: one shared bias row)
 };
 
 template <int K, int NQ>
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(512) void conv_gate_kernel(const GateArgs a, const 
   // wave w (< 4) finishes register w: tile rows i = 4·kk + w — lanes 0–31 hold tanh rows (i < 8), lanes 32–63 their sigmoid partners
   const int i8 = 4 * kk + wave;
   const int h = 8 * mt + (i8 & 7);
-  const float bias = (wave < 4 && a.bias) ? a.bias[(i8 < 8 ? 0 : a.rows_out) + min(h, a.rows_out - 1)] : 0.0f;  // bias first (CPUBackend.swift:46-63)
+  const float bias = (wave < 4 && a.bias) ? a.bias[(long long)n * a.bias_bs + (i8 < 8 ? 0 : a.rows_out) + min(h, a.rows_out - 1)] : 0.0f;  // bias first (CPUBackend.swift:46-63)
   for (int it = 0;; it++) {  // chunks ch, ch + gridDim.y, … with the same weight fragments (see conv_k1_kernel)
     const int t0 = ch * 16;
     const int nxt = ch + (int)gridDim.y;
@@ -654,7 +655,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
     GateArgs g;
     g.x = c.x; g.w = c.w16g; g.bias = c.bias; g.y = c.y; g.len_ptr = c.len_ptr; g.len_mul = c.len_mul;
     g.Lin = c.Lin; g.Lout = c.Lout; g.rows_out = c.Cout / 2; g.y_len = c.y_len; g.nsteps = (c.Cin / 4) * c.K; g.pad = c.padL;
-    g.x_batch_bytes = (int)(c.x_batch_stride * 4); g.x_bs = c.x_batch_stride; g.y_bs = c.y_batch_stride;
+    g.x_batch_bytes = (int)(c.x_batch_stride * 4); g.x_bs = c.x_batch_stride; g.y_bs = c.y_batch_stride; g.bias_bs = c.bias_batch_stride;
     const dim3 grid((unsigned)mt_g, (unsigned)chunk_groups(ctx, mt_g, nch, c.N), (unsigned)c.N);
     if (c.K == 5) hipLaunchKernelGGL((conv_gate_kernel<5, 6>), grid, dim3(512), 0, s, g, nch);
     else hipLaunchKernelGGL((conv_gate_kernel<3, 6>), grid, dim3(512), 0, s, g, nch);
@@ -663,6 +664,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
     return 1;
   }
   if (c.prologue == PRO_LN && c.ln_self) {  // LayerNorm computed by the consumer itself: qkv / proj (k 1) and the FFN's first conv (k 3)
+    if (c.bias_batch_stride) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "conv: ln_self takes one bias row for all items");
     if (!conv_lean_ln_self_ok(ctx, c.Cin, c.Cout, c.K, c.padL, c.Lout, c.N)) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "conv: ln_self on a shape conv_lean does not cover");
     if (!c.w16 || c.stats_out || c.res || c.dil != 1 || c.Lin != c.Lout || c.in_ch_sign != 1 || c.in_ch_base != 0 || c.out_ch_sign != 1 || c.out_ch_base != 0 ||
         !c.ln_gamma || !c.ln_beta || (c.epilogue != EPI_STORE && c.epilogue != EPI_RELU) || (c.K == 1 && c.epilogue != EPI_STORE))
@@ -675,7 +677,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
     a.x_row_bytes = c.Lin * 4; a.kk_sign = 1; a.x_base_bytes = 0; a.q_stride = 16 * c.Lin;
     a.out_ch_base = 0; a.out_ch_sign = 1;
     a.x_batch_bytes = (int)(c.x_batch_stride * 4);
-    a.x_bs = c.x_batch_stride; a.y_bs = c.y_batch_stride; a.y2_bs = 0;
+    a.x_bs = c.x_batch_stride; a.y_bs = c.y_batch_stride; a.y2_bs = 0; a.bias_bs = 0;
     LnArgs ln{c.ln_gamma, c.ln_beta, c.ln_out, c.ln_eps};
     const dim3 grid((unsigned)ceil_div(c.Cout, 16), (unsigned)ceil_div(c.Lout, 16), (unsigned)c.N);
     if (c.K == 1) hipLaunchKernelGGL((conv_k1_ln_kernel<6>), grid, dim3(512), 0, s, a, ln);
@@ -686,7 +688,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
     return 1;
   }
   if (c.K == 3 && c.w8 && c.Cin == 768 && c.prologue == PRO_NONE && c.epilogue == EPI_STORE && !c.stats_out && !c.gate && c.dil == 1 && c.padL == 1 &&
-      c.Lin == c.Lout && c.in_ch_sign == 1 && c.in_ch_base == 0 && c.out_ch_sign == 1 && c.out_ch_base == 0 && c.N <= 65535) {
+      c.Lin == c.Lout && c.in_ch_sign == 1 && c.in_ch_base == 0 && c.out_ch_sign == 1 && c.out_ch_base == 0 && c.N <= 65535 && !c.bias_batch_stride) {
     const int mt8 = (int)ceil_div(c.Cout, 8), nch = (int)ceil_div(c.Lout, 16);
     // up to two blocks per CU: beyond that the 73 KB slab per block costs more than the idle CUs did (factor 64, 1 344 blocks: 36.7 µs against
     // 17.8 on the streaming kernel; factor 8, 168 blocks: 10.0 against 10.8)
@@ -696,7 +698,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
       a.len_ptr = c.len_ptr; a.len_mul = c.len_mul;
       a.Lin = c.Lin; a.Lout = c.Lout; a.Cout = c.Cout; a.y_len = c.y_len; a.wn_c = 0; a.nsteps = (c.Cin / 4) * c.K;
       a.x_row_bytes = c.Lin * 4; a.kk_sign = 1; a.x_base_bytes = 0; a.q_stride = 16 * c.Lin; a.out_ch_base = 0; a.out_ch_sign = 1;
-      a.x_batch_bytes = (int)(c.x_batch_stride * 4); a.x_bs = c.x_batch_stride; a.y_bs = c.y_batch_stride; a.y2_bs = 0;
+      a.x_batch_bytes = (int)(c.x_batch_stride * 4); a.x_bs = c.x_batch_stride; a.y_bs = c.y_batch_stride; a.y2_bs = 0; a.bias_bs = 0;
       const int w_bytes = mt8 * a.nsteps * 128;
       constexpr int NQ = 24;
       const size_t lds = (size_t)(8 * 4 * 64 + 8 * (4 * NQ) * 20) * sizeof(float);
@@ -731,7 +733,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
   a.q_stride = c.in_ch_sign * 16 * c.Lin;
   a.out_ch_base = c.out_ch_base; a.out_ch_sign = c.out_ch_sign;
   a.x_batch_bytes = (int)(c.x_batch_stride * 4);
-  a.x_bs = c.x_batch_stride; a.y_bs = c.y_batch_stride; a.y2_bs = c.y2_batch_stride;
+  a.x_bs = c.x_batch_stride; a.y_bs = c.y_batch_stride; a.y2_bs = c.y2_batch_stride; a.bias_bs = c.bias_batch_stride;
   const dim3 grid((unsigned)mtiles, (unsigned)chunk_groups(ctx, mtiles, nchunks, c.N), (unsigned)c.N);
   const bool ok = NQ == 3 ? launch_lean_nq<3>(s, grid, a, c.epilogue, nchunks) : launch_lean_nq<6>(s, grid, a, c.epilogue, nchunks);
   if (!ok) return 0;

@@ -60,8 +60,8 @@ __global__ __launch_bounds__(BT) void conv_short_kernel(const ConvArgs p, const 
   const int Cin = p.Cin, Cout = p.Cout, padL = p.padL, Lin = p.Lin, Lout = p.Lout, in_base = p.in_ch_base, in_sign = p.in_ch_sign;
   const int* len_ptr = p.len_ptr;
   const int len_mul = p.len_mul;
-  const int64_t xbs = p.x_batch_stride;
-  asm volatile("" ::"s"(px), "s"(pw), "s"(pbias), "s"(pres), "s"(pskip), "s"(py), "s"(py2));
+  const int64_t xbs = p.x_batch_stride, bbs = p.bias_batch_stride;
+  asm volatile("" ::"s"(px), "s"(pw), "s"(pbias), "s"(pres), "s"(pskip), "s"(py), "s"(py2), "s"(bbs));
   asm volatile("" ::"s"(Cin), "s"(Cout), "s"(padL), "s"(Lin), "s"(Lout), "s"(in_base), "s"(in_sign), "s"(len_ptr), "s"(len_mul), "s"(xbs));
   const int KS = 1 << ks_log2;
   const int WT = (BT / 64) >> ks_log2;
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(BT) void conv_short_kernel(const ConvArgs p, const 
         co = 16 * mt + i;
         row_ok = co < Cout;
       }
-      float v = pbias ? pbias[row_ok ? co : 0] : 0.0f;
+      float v = pbias ? pbias[(int64_t)n * bbs + (row_ok ? co : 0)] : 0.0f;
       if (!row_ok) v = 0.0f;
       const float* src = red + (nt * 4 + r) * 64 + lane;
       float part[16];

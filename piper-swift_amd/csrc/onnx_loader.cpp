@@ -418,14 +418,16 @@ PH_EXPORT int piper_hip_onnx_read_f32(const piper_hip_onnx* m, int index, float*
   return read_floats(m->tensors[index], dst, n);
 }
 
-PH_EXPORT int piper_hip_onnx_infer_config(const piper_hip_onnx* m, piper_hip_voice_config* cfg) {
+namespace {
+// piper_hip_onnx_infer_config (speakers = false) and piper_hip_onnx_infer_config_speakers (true: the same without the refusal below)
+int infer_config_impl(const piper_hip_onnx* m, piper_hip_voice_config* cfg, bool speakers) {
   if (!m || !cfg) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   memset(cfg, 0, sizeof *cfg);
   // Multi-speaker voices condition the flow, the duration predictor and the generator on a speaker embedding `g`
-  // (emb_g + cond / cond_layer convs). None of that is implemented here, and ignoring it would synthesise the wrong voice
-  // without any error — refuse instead.
+  // (emb_g + cond / cond_layer convs). This entry point hands out a geometry WITHOUT them, and running it that way would synthesise
+  // the wrong voice without any error — refuse instead (the opt-in route: piper_hip_onnx_infer_config_speakers + speaker_config).
   for (const Tensor& it : m->tensors)
-    if (it.name.compare(0, 5, "emb_g") == 0 || it.name.find(".cond.") != std::string::npos || it.name.find(".cond_layer.") != std::string::npos)
+    if (!speakers && (it.name.compare(0, 5, "emb_g") == 0 || it.name.find(".cond.") != std::string::npos || it.name.find(".cond_layer.") != std::string::npos))
       PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "onnx: multi-speaker voice (initializer '%s'): speaker conditioning is not implemented", it.name.c_str());
   for (const Tensor& it : m->tensors)  // geometry fields are int32: refuse dims that would be truncated
     for (int64_t dm : it.dims)
@@ -512,6 +514,59 @@ PH_EXPORT int piper_hip_onnx_infer_config(const piper_hip_onnx* m, piper_hip_voi
   return piper_hip_voice_blob_floats(cfg, &n);  // validates the geometry
 }
 
+// name, or its weight-norm pair's _v: the tensor that carries the shape
+const Tensor* shape_of(const piper_hip_onnx* m, const std::string& name) {
+  const Tensor* t = resolve(m, name);
+  return t ? t : find(m, name + "_v");
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_onnx_infer_config(const piper_hip_onnx* m, piper_hip_voice_config* cfg) { return infer_config_impl(m, cfg, false); }
+PH_EXPORT int piper_hip_onnx_infer_config_speakers(const piper_hip_onnx* m, piper_hip_voice_config* cfg) { return infer_config_impl(m, cfg, true); }
+
+PH_EXPORT int piper_hip_onnx_speaker_config(const piper_hip_onnx* m, const piper_hip_voice_config* cfg, piper_hip_speaker_config* scfg) {
+  if (!m || !cfg || !scfg) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  scfg->n_speakers = 0;
+  scfg->gin = 0;
+  const Tensor* e = find(m, "emb_g.weight");
+  if (!e) return PIPER_HIP_OK;  // a single-speaker voice
+  if (e->dims.size() != 2 || e->dims[0] < 1 || e->dims[0] > 65536 || e->dims[1] < 4 || e->dims[1] > 1024 || e->dims[1] % 4)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "onnx: 'emb_g.weight' must be [1 … 65536 speakers, gin] with gin a multiple of 4 in [4, 1024]");
+  const int64_t S = e->dims[0], gin = e->dims[1];
+  const piper_hip_speaker_config sc{(int32_t)S, (int32_t)gin};
+  struct Check {
+    const piper_hip_onnx* m;
+    int rc;
+  } ck{m, PIPER_HIP_OK};
+  // every tensor of the speaker blob behind the table: present (or as a weight-norm pair) and of the layout's shape
+  piper_hip_speaker_layout_walk(cfg, &sc, [](const piper_tensor_desc* d, void* user) {
+    Check* c = (Check*)user;
+    if (c->rc || !strcmp(d->name, "emb_g.weight")) return;
+    const Tensor* t = shape_of(c->m, d->name);
+    bool ok = t && (int)t->dims.size() == d->rank;
+    for (int i = 0; ok && i < d->rank; i++) ok = t->dims[i] == d->shape[i];
+    if (!ok) {
+      set_error("onnx: multi-speaker voice: initializer '%s' is missing or not [%lld, %lld, %lld]", d->name, d->shape[0], d->shape[1], d->shape[2]);
+      c->rc = PIPER_HIP_ERR_SHAPE;
+    }
+  }, &ck);
+  if (ck.rc) return ck.rc;
+  *scfg = sc;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_onnx_build_speaker_blob(const piper_hip_onnx* m, const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg,
+                                                float* host_blob, size_t n_floats) {
+  if (!m || !cfg || !scfg || !host_blob) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  size_t need = 0;
+  int rc = piper_hip_speaker_blob_floats(cfg, scfg, &need);
+  if (rc) return rc;
+  if (n_floats != need) PH_FAIL(PIPER_HIP_ERR_SHAPE, "onnx_build_speaker_blob: blob has %zu floats, the geometry needs %zu", n_floats, need);
+  BlobFill b{m, host_blob, PIPER_HIP_OK, {}, {}};
+  piper_hip_speaker_layout_walk(cfg, scfg, fill_visit, &b);  // (folds weight_g / weight_v pairs exactly as the main blob's walk does)
+  return b.rc;
+}
+
 PH_EXPORT int piper_hip_onnx_build_blob(const piper_hip_onnx* m, const piper_hip_voice_config* cfg, float* host_blob, size_t n_floats) {
   if (!m || !cfg || !host_blob) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   // the weights are only handed out for a graph that IS the computation the schedule performs (onnx_verify.cpp)
@@ -566,6 +621,17 @@ PH_EXPORT int piper_hip_piper_json(const char* json_text, piper_hip_piper_json_i
     if (json_number(s, "length_scale", &v, inf)) out->length_scale = (float)v;
     if (json_number(s, "noise_w", &v, inf)) out->noise_w = (float)v;
   }
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_check_json_speakers(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg,
+                                                  const piper_hip_piper_json_info* info) {
+  if (!cfg || !scfg || !info) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  const int said = info->num_speakers < 1 ? 1 : info->num_speakers;
+  if (said != scfg->n_speakers)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "voice json says %d speakers, the graph's speaker table has %d rows", said, scfg->n_speakers);
+  if (info->num_symbols != cfg->n_vocab)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "voice json says %d symbols, the graph's embedding has %d rows", info->num_symbols, cfg->n_vocab);
   return PIPER_HIP_OK;
 }
 

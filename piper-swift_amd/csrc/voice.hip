@@ -26,9 +26,11 @@
 #include "pcm16.h"
 #include "resample.h"
 #include "rng.h"
+#include "speaker.h"
 
 namespace ph {
 int validate_config(const piper_hip_voice_config* c);
+int validate_speaker_config(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* sc);
 int launch_rel_attention(piper_hip_ctx* ctx, hipStream_t s, const float* q, const float* k, const float* v, const float* ek,
                          const float* ev, float* out, int N, int H, int d, int T, int w, int64_t in_batch_stride,
                          int64_t out_batch_stride, const int* len_ptr);
@@ -267,6 +269,12 @@ struct Slot {
   float* noise = nullptr;
   float* noise_scale = nullptr;  // [NB] device
   unsigned* rng = nullptr;       // [NB][2] device: {generate noise on the device?, seed}
+  // a voice with a speaker table (null otherwise): the items' speakers, a plan input staged like ids and lengths; what the plan's
+  // "spk.rows" step makes of them — g [NB][gin] and the speaker rows [NB][Ctot], of which this plan computes its own part. A generator
+  // window plan has no step: spk_bias is [NB][up_initial], the conv_pre rows that travel with the rows' latents.
+  piper_hip_speaker* spk_in = nullptr;
+  float* spk_g = nullptr;
+  float* spk_bias = nullptr;
   float* audio = nullptr;
   int64_t n_samples = 0;
   std::vector<Step> steps;
@@ -331,6 +339,7 @@ struct StreamPool {
   std::vector<hipEvent_t> ev_free, ev_pending;  // ev_pending: "the adopt of a join since the last step has run", one per join
   StreamRate rs;                 // output rate of the pool; its buffers come from the context pool and go back in pool_close
   size_t pack_bytes = 0;         // of `pack`
+  float* spk_rows = nullptr;     // device: [capacity][up_initial] conv_pre rows of the sessions in the rows (a voice with speakers; else null)
 };
 
 }  // namespace
@@ -408,7 +417,16 @@ struct piper_hip_voice {
     float* h_peaks = nullptr;  // collect_pcm16 with normalize = 1: the items' peaks, written by the pack kernel through the host mapping
     size_t cap_peaks = 0;
     std::vector<hipEvent_t> chunk_ev;  // collect, 1 … 16 MB waveforms: one event per 1 MB chunk landed in h_audio
+    piper_hip_speaker* h_spk = nullptr;  // the items' speakers of a prepare (a voice with a speaker table)
+    size_t cap_spk = 0;
   } staging[kMaxSlots];
+  // Speaker table of a multi-speaker voice (piper_hip_voice_attach_speakers; spk.S == 0: none): the device tables of speaker.hip, where an
+  // item's speaker row keeps the dp.pre rows [0, spk_dp_rows), the flow's from there and the conv_pre rows from spk_pre_off, and each
+  // slot id's assignment (empty: speaker 0 alone; items past the end take the last entry).
+  SpeakerTables spk;
+  int spk_dp_rows = 0, spk_pre_off = 0;
+  std::vector<piper_hip_speaker> slot_spk[kMaxSlots];
+  bool planned = false;  // a plan has been asked for: the voice's schedules are fixed (no attach_speakers any more)
   Slot* attached[kMaxSlots] = {};
   std::unique_ptr<StreamPool> pools[kMaxSlots];  // the streaming pool a slot id holds (then attached[slot] is null)
   Slot* attached_dp[kMaxSlots] = {};  // bounded prepare: the encoder + predictor plan this slot id holds until its next prepare / detach
@@ -737,6 +755,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();      // (these too)
   s.rs = StreamRate();                                                         // (and the resampling history and descriptor)
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
+  s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   for (void* p : s.owned) (void)v->ctx->pool.release(p);
   s.owned.clear();
   s.steps.clear();
@@ -764,6 +783,7 @@ void pool_close(piper_hip_voice* v, int slot) {
   if (P->pack) (void)v->ctx->pool.release(P->pack);
   if (P->rs.hist) (void)v->ctx->pool.release(P->rs.hist);
   if (P->rs.desc) (void)v->ctx->pool.release(P->rs.desc);
+  if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
   v->pools[slot].reset();
 }
 
@@ -839,13 +859,22 @@ struct Builder {
     return a;
   }
 
+  // A voice with a speaker table: the conv whose rows start at `row` of the speaker row (a main or predictor plan), or conv_pre of a
+  // generator window plan (row < 0), reads each item's effective bias. A voice without: nothing changes (the conv's own bias, stride 0).
+  template <class Args>
+  void speaker_bias(Args& a, int row) const {
+    if (!v->spk.S || !s.spk_bias) return;
+    a.bias = row < 0 ? s.spk_bias : s.spk_bias + row;
+    a.bias_batch_stride = row < 0 ? v->cfg.up_initial : v->spk.Ctot;
+  }
+
   // conv step over a resident ConvW
   void conv(const std::string& name, const ConvW& w, ConvArgs a, int64_t Lout_for_work) {
     a.w = w.w;
     a.w16 = w.w16;
     a.w16g = w.w16g;
     a.w8 = w.w8;
-    a.bias = w.bias;
+    if (!a.bias) a.bias = w.bias;  // (a speaker-conditioned conv comes with its items' effective biases: speaker_bias)
     a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
     piper_hip_ctx* ctx = v->ctx;
     const bool mfma = w.mfma;
@@ -856,7 +885,8 @@ struct Builder {
 
   // conv step over a bf16 fragment image
   void conv_bf16(const std::string& name, const piper_hip_voice::ConvWB& w, ConvBf16Args a, double flops) {
-    a.w = w.w; a.bias = w.bias; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
+    a.w = w.w; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
+    if (!a.bias) a.bias = w.bias;  // (conv_pre of a voice with speakers comes with its items' effective biases)
     piper_hip_ctx* ctx = v->ctx;
     step(name, "conv_bf16", flops, conv_bf16_bytes(a), [ctx, a](hipStream_t q) { return launch_conv_bf16(ctx, q, a); });
   }
@@ -1037,6 +1067,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
     a.x = zc8; a.y = dec0; a.act = a_in; a.act_alpha = 0.1f;  // the first stage's ConvTranspose reads lrelu(conv_pre)
     a.N = NB; a.dil = 1; a.padL = 3; a.Lout = F; a.x_row = (int)c8_row_len(F); a.act_row = (int)c8_row_len(F); a.y_len = F;
     a.len_ptr = b.lensF; a.len_mul = 1;
+    b.speaker_bias(a, s.kind == PLAN_GENERATOR ? -1 : v->spk_pre_off);  // x = dec.conv_pre(z) + dec.cond(g), the bias stays fp32
     b.conv_bf16("dec.conv_pre", v->conv_pre_b, a, NB * conv_flops(c.up_initial, I, 7, F));
   }
   b.tap("dec_pre", dec0, c.up_initial, F, 1);
@@ -1643,6 +1674,7 @@ const float* build_flow(Builder& b, const FrontBuffers& fb) {
       ConvArgs a = b.plain(h, acts, H, H, F, lensF);
       a.padL = (c.wn_kernel - 1) / 2;
       a.gate = 1;
+      b.speaker_bias(a, v->spk_dp_rows + (f * c.wn_layers + i) * 2 * H);  // acts = tanh(a + g_l[:H]) · sigmoid(b + g_l[H:])
       b.conv(p + "wn" + std::to_string(i) + ".in_gate", C.in[i], a, F);
       if (last && fold) break;
       ConvArgs a2 = b.plain(acts, h, H, H, F, lensF);
@@ -1719,10 +1751,11 @@ int build_duration_predictor(Builder& b, const float* x) {
   s.dp_dur = (int32_t*)ar.raw(B * T * sizeof(int32_t));
   if (ar.rc) return ar.rc;
   const int* lensT = b.lensT;
-  auto conv_k1 = [&](const std::string& name, const ConvW& w, const float* in, int64_t in_bs, float* out, const float* res) {
+  auto conv_k1 = [&](const std::string& name, const ConvW& w, const float* in, int64_t in_bs, float* out, const float* res, bool spk = false) {
     ConvArgs a;
     a.x = in; a.y = out; a.N = NB; a.Lin = T; a.Lout = T; a.x_batch_stride = in_bs; a.y_batch_stride = (int64_t)w.Cout * T; a.y_len = T;
     a.len_ptr = lensT; a.res = res;
+    if (spk) b.speaker_bias(a, 0);  // x = dp.pre(x) + dp.cond(g): the first rows of the speaker row
     b.conv(name, w, a, T);
   };
   auto dds_stack = [&](const std::string& name, const std::vector<piper_hip_voice::DdsLayer>& layers, float* cur, float* other) {
@@ -1742,7 +1775,7 @@ int build_duration_predictor(Builder& b, const float* x) {
     return cur;
   };
   // x → pre → DDSConv → proj = the conditioning of every flow
-  conv_k1("dp.pre", v->dp[0].pre, x, (int64_t)H * T, a0, nullptr);
+  conv_k1("dp.pre", v->dp[0].pre, x, (int64_t)H * T, a0, nullptr, true);
   float* r = dds_stack("dp", v->dp[0].dds, a0, a1);
   conv_k1("dp.proj", v->dp[0].proj, r, (int64_t)H * T, cond, nullptr);
   const float* nz = s.dp_noise;
@@ -1794,6 +1827,26 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind k
   if (ar.rc) return ar.rc;
   b.lensT = s.lensT;
   b.lensF = s.lensF;
+  if (v->spk.S) {  // a voice with a speaker table (one without allocates and schedules exactly what it did before there were any)
+    const SpeakerTables tab = v->spk;
+    if (kind == PLAN_GENERATOR) {
+      s.spk_bias = ar.f32(B * (size_t)c.up_initial);  // the rows' conv_pre biases, copied in with their latent windows
+      if (ar.rc) return ar.rc;
+    } else {
+      s.spk_in = (piper_hip_speaker*)ar.raw(B * sizeof(piper_hip_speaker));
+      s.spk_g = ar.f32(B * (size_t)tab.gin);
+      s.spk_bias = ar.f32(B * (size_t)tab.Ctot);
+      if (ar.rc) return ar.rc;
+      // the predictor plan computes the dp.pre rows, the others the flow and generator rows: nothing is computed twice
+      const int row0 = kind == PLAN_PREDICT ? 0 : v->spk_dp_rows, rows = kind == PLAN_PREDICT ? v->spk_dp_rows : tab.Ctot - v->spk_dp_rows;
+      const piper_hip_speaker* in = s.spk_in;
+      float *g = s.spk_g, *e = s.spk_bias;
+      b.step("spk.rows", "speaker", NB * 2.0 * rows * tab.gin, 4.0 * ((double)rows * tab.gin + 2.0 * rows + NB * ((double)rows + 5.0 * tab.gin)),
+             [=](hipStream_t q) { return launch_speaker_rows(q, tab, in, NB, row0, rows, g, e); });
+      b.tap("spk.g", s.spk_g, 1, tab.gin, -1);
+      b.tap("spk.bias", s.spk_bias, 1, tab.Ctot, -1);
+    }
+  }
   const float* z = nullptr;
   float* dec0 = nullptr;
   if (kind == PLAN_GENERATOR) {  // streaming: only the generator, over a window of the latent that the caller copies into zin
@@ -1856,6 +1909,7 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind k
   {
     ConvArgs a = b.plain(z, dec0, I, c.up_initial, F, b.lensF);
     a.padL = 3;
+    b.speaker_bias(a, kind == PLAN_GENERATOR ? -1 : v->spk_pre_off);  // x = dec.conv_pre(z) + dec.cond(g)
     b.conv("dec.conv_pre", v->conv_pre, a, F);
   }
   b.tap("dec_pre", dec0, c.up_initial, F, 1);
@@ -1970,6 +2024,43 @@ int utt_frames(const piper_hip_voice* v, const piper_hip_utterance& u, int b, in
   return PIPER_HIP_OK;
 }
 
+// The speaker of item i of a prepare on slot id `slot`: entry i of the slot's assignment, its last entry past the end, speaker 0 alone
+// without one (piper_hip_voice_slot_speakers)
+piper_hip_speaker speaker_of(const piper_hip_voice* v, int slot, int i) {
+  const auto& a = v->slot_spk[slot];
+  if (a.empty()) {
+    piper_hip_speaker d{};
+    d.n = 1;
+    d.weights[0] = 1.0f;
+    return d;
+  }
+  return a[std::min((size_t)i, a.size() - 1)];
+}
+
+// What the host checks of entry i, so that the device never indexes past the table
+int check_speaker(const piper_hip_voice* v, const piper_hip_speaker& sp, int i) {
+  if (sp.n < 1 || sp.n > 4) PH_FAIL(PIPER_HIP_ERR_ARG, "speaker %d: a mix of %d entries (1 … 4)", i, sp.n);
+  for (int k = 0; k < sp.n; k++) {
+    if (sp.ids[k] < 0 || sp.ids[k] >= v->spk.S) PH_FAIL(PIPER_HIP_ERR_ARG, "speaker %d: id %d outside the table's %d rows", i, sp.ids[k], v->spk.S);
+    if (!std::isfinite(sp.weights[k])) PH_FAIL(PIPER_HIP_ERR_ARG, "speaker %d: weight %d is not finite", i, k);
+  }
+  return PIPER_HIP_OK;
+}
+
+// The speakers of a prepare of n items on slot id `slot` → the plan's input (nothing for a voice without a table), from the slot id's
+// page-locked staging on q. The caller has waited for whatever used that staging before.
+int stage_speakers(piper_hip_voice* v, int slot, Slot& plan, int n, hipStream_t q) {
+  if (!v->spk.S || !plan.spk_in) return PIPER_HIP_OK;
+  auto& sg = v->staging[slot];
+  if (!sg.h_spk) {  // kMaxGroup records, once per slot id
+    PH_HIP(hipHostMalloc((void**)&sg.h_spk, 256 * sizeof(piper_hip_speaker)), PIPER_HIP_ERR_ALLOC);
+    sg.cap_spk = 256;
+  }
+  for (int b = 0; b < n; b++) sg.h_spk[b] = speaker_of(v, slot, b);
+  PH_HIP(hipMemcpyAsync(plan.spk_in, sg.h_spk, (size_t)n * sizeof(piper_hip_speaker), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
 // ids of n utterances → rows of T, zero past each one's end (any legal id)
 void pack_ids(const piper_hip_utterance* utts, int n, int T, int64_t* ids) {
   for (int b = 0; b < n; b++) {
@@ -2076,6 +2167,75 @@ PH_EXPORT int piper_hip_voice_create(piper_hip_ctx* ctx, const piper_hip_voice_c
   return PIPER_HIP_OK;
 }
 
+// ---- speakers (piper_hip.h "Multi-speaker voices") --------------------------------------------------------------------------------
+PH_EXPORT int piper_hip_voice_attach_speakers(piper_hip_voice* v, const piper_hip_speaker_config* scfg, const float* blob, int on_device) {
+  if (!v || !blob) PH_FAIL(PIPER_HIP_ERR_ARG, "voice_attach_speakers: null argument");
+  int rc = validate_speaker_config(&v->cfg, scfg);
+  if (rc) return rc;
+  if (v->spk.S) PH_FAIL(PIPER_HIP_ERR_ARG, "voice_attach_speakers: the voice has a speaker table already");
+  if (v->planned) PH_FAIL(PIPER_HIP_ERR_ARG, "voice_attach_speakers: the voice has prepared already (attach the table before the first prepare)");
+  piper_hip_ctx* ctx = v->ctx;
+  const piper_hip_voice_config& c = v->cfg;
+  PH_HIP(hipSetDevice(ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  std::map<std::string, piper_tensor_desc> idx;
+  IndexOut io{&idx};
+  piper_hip_speaker_layout_walk(&c, scfg, index_visit, &io);
+  const int gin = scfg->gin, S = scfg->n_speakers, H = c.hidden;
+  const int Ctot = (int)piper_hip_speaker_row_floats(&c), dp_rows = (int)piper_hip_speaker_dp_rows(&c);
+  void* p = nullptr;
+  if ((rc = ctx->pool.alloc(((size_t)S * gin + (size_t)Ctot * gin + 2 * (size_t)Ctot) * sizeof(float), &p))) return rc;
+  float* emb = (float*)p;
+  float* w = emb + (size_t)S * gin;
+  float* bc = w + (size_t)Ctot * gin;
+  float* b_own = bc + Ctot;
+  const hipStream_t q = ctx->default_stream;
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  hipError_t e = hipMemcpyAsync(emb, blob + idx["emb_g.weight"].offset, (size_t)S * gin * sizeof(float), kind, q);
+  int row = 0;
+  bool missing = false;
+  // `rows` rows of the speaker row from here on: the cond conv `cond` (or a slice of it, from cond row `from`) over the conv `own`
+  auto put = [&](const std::string& cond, int from, int rows, const std::string& own) {
+    const float* ob = tensor(v, own + ".bias");
+    if (!ob) { missing = true; return; }
+    if (e == hipSuccess) e = hipMemcpyAsync(w + (size_t)row * gin, blob + idx[cond + ".weight"].offset + (size_t)from * gin, (size_t)rows * gin * sizeof(float), kind, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(bc + row, blob + idx[cond + ".bias"].offset + from, (size_t)rows * sizeof(float), kind, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(b_own + row, ob, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, q);
+    row += rows;
+  };
+  if (dp_rows) put("dp.cond", 0, H, "dp.pre");
+  for (int f = 0; f < c.n_flows; f++)
+    for (int l = 0; l < c.wn_layers; l++)
+      put("flow.flows." + std::to_string(2 * f) + ".enc.cond_layer", 2 * H * l, 2 * H, "flow.flows." + std::to_string(2 * f) + ".enc.in_layers." + std::to_string(l));
+  const int pre_off = row;
+  put("dec.cond", 0, c.up_initial, "dec.conv_pre");
+  if (e == hipSuccess) e = hipStreamSynchronize(q);  // (a host blob may go away when this returns)
+  if (e != hipSuccess || missing || row != Ctot) {
+    (void)hipStreamSynchronize(q);
+    (void)ctx->pool.release(p);
+    if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "voice_attach_speakers: %s", hipGetErrorString(e));
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "voice_attach_speakers: the voice lacks a bias the speakers condition");
+  }
+  v->owned.push_back(p);
+  v->spk.emb = emb; v->spk.w = w; v->spk.bc = bc; v->spk.b_own = b_own;
+  v->spk.S = S; v->spk.gin = gin; v->spk.Ctot = Ctot;
+  v->spk_dp_rows = dp_rows;
+  v->spk_pre_off = pre_off;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_num_speakers(const piper_hip_voice* v) { return v ? v->spk.S : 0; }
+
+PH_EXPORT int piper_hip_voice_slot_speakers(piper_hip_voice* v, int slot, const piper_hip_speaker* spk, int n) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (!v->spk.S) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice_slot_speakers: the voice has no speaker table (piper_hip_voice_attach_speakers)");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (n < 0 || n > 256 || (n > 0 && !spk)) PH_FAIL(PIPER_HIP_ERR_ARG, "voice_slot_speakers: %d entries (0 … 256)", n);
+  for (int i = 0; i < n; i++)
+    if (int rc = check_speaker(v, spk[i], i)) return rc;  // (the assignment in place stays on a refusal)
+  v->slot_spk[slot].assign(spk, spk + n);
+  return PIPER_HIP_OK;
+}
+
 PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16)
@@ -2179,6 +2339,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_noise) (void)hipHostFree(sg.h_noise);
     if (sg.h_desc) (void)hipHostFree(sg.h_desc);
     if (sg.h_peaks) (void)hipHostFree(sg.h_peaks);
+    if (sg.h_spk) (void)hipHostFree(sg.h_spk);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
   for (auto& st : v->free_sets) destroy_set(st);
@@ -2249,6 +2410,7 @@ int launch_plan(piper_hip_voice* v, Slot& s, hipStream_t on = nullptr) {
 // the cache has none. *built reports whether this call paid for a build ("cold" prepare).
 int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot** out, bool* built) {
   *built = false;
+  v->planned = true;
   for (auto& p : v->plans)
     if (!p->in_use && p->built && p->kind == kind && p->T == Tb && p->F == Fb && p->NB == NB && p->prec == v->precision) {
       const int rc0 = slot_init(v, *p);  // a plan that went idle gave its stream set back (detach)
@@ -2280,6 +2442,11 @@ int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot
     if (e == hipSuccess && s.rng) e = hipMemsetAsync(s.rng, 0, (size_t)NB * 2 * sizeof(unsigned), s.set.stream);
     if (e == hipSuccess && s.dp_scalars) e = hipMemsetAsync(s.dp_scalars, 0, dp_scalars_bytes(NB), s.set.stream);
     if (e == hipSuccess && s.dp_noise) e = hipMemsetAsync(s.dp_noise, 0, (size_t)NB * 2 * Tb * sizeof(float), s.set.stream);
+    // speakers: a zeroed record is an empty mix (g = 0); the rows this plan does not compute, and a window plan's rows, read as 0.0
+    if (e == hipSuccess && s.spk_in) e = hipMemsetAsync(s.spk_in, 0, (size_t)NB * sizeof(piper_hip_speaker), s.set.stream);
+    if (e == hipSuccess && s.spk_g) e = hipMemsetAsync(s.spk_g, 0, (size_t)NB * v->spk.gin * sizeof(float), s.set.stream);
+    if (e == hipSuccess && s.spk_bias)
+      e = hipMemsetAsync(s.spk_bias, 0, (size_t)NB * (kind == PLAN_GENERATOR ? v->cfg.up_initial : v->spk.Ctot) * sizeof(float), s.set.stream);
     if (e == hipSuccess) e = stream_wait(s.set.stream);
     if (e != hipSuccess) { slot_release(v, s, true); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "voice_prepare: arena initialisation failed: %s", hipGetErrorString(e)); }
   }
@@ -2335,7 +2502,8 @@ int attach_plan(piper_hip_voice* v, int slot, PlanKind kind, int T, int F, int N
 }  // namespace
 
 namespace {
-int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out);
+int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
+                 const piper_hip_speaker* speakers = nullptr);
 // Page-locked staging `p` of `cap` elements, grown (contents dropped) to hold `need`: `min_cap` elements or a power of two times that.
 // On failure p is null and cap 0.
 template <typename Tp>
@@ -2381,7 +2549,9 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
         total += utts[b].t;
       }
       predicted.resize((size_t)total);
-      if ((rc = predict_impl(v, utts, n, predicted.data(), nullptr, (int)total, &dp_plan))) return rc;
+      std::vector<piper_hip_speaker> spk;  // the predictor is conditioned too: x = dp.pre(x) + dp.cond(g)
+      for (int b = 0; b < n && v->spk.S; b++) spk.push_back(speaker_of(v, slot, b));
+      if ((rc = predict_impl(v, utts, n, predicted.data(), nullptr, (int)total, &dp_plan, spk.empty() ? nullptr : spk.data()))) return rc;
       resolved.assign(utts, utts + n);
       int64_t off = 0;
       for (int b = 0; b < n; b++) {
@@ -2442,6 +2612,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     return rc;
   unsigned* p_rng = (unsigned*)sg.h_misc;
   float* p_ns = (float*)(p_rng + 2 * (size_t)n);
+  if ((rc = stage_speakers(v, slot, s, n, q))) return rc;
   pack_ids(utts, n, T, sg.h_ids);
   for (int b = 0; b < n; b++) {
     const piper_hip_utterance* u = &utts[b];
@@ -2594,6 +2765,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
     sg.h_res[b] = -1;
   }
   const hipStream_t q = s.set.stream;
+  if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q))) return rc;
   PH_HIP(hipMemcpyAsync(dp->ids, sg.h_ids, (size_t)n * T * sizeof(int64_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(dp->lensT, h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(dp->dp_noise, sg.h_dpn, (size_t)n * 2 * T * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
@@ -2672,13 +2844,34 @@ PH_EXPORT int piper_hip_voice_predict_durations(piper_hip_voice* v, const piper_
                                                 int max_entries) {
   return predict_impl(v, utts, n, durations_out, logw_out, max_entries, nullptr);
 }
+PH_EXPORT int piper_hip_voice_predict_durations_speakers(piper_hip_voice* v, const piper_hip_utterance* utts, int n, const piper_hip_speaker* speakers,
+                                                         int32_t* durations_out, float* logw_out, int max_entries) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  if (speakers) {
+    if (!v->spk.S) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "predict_durations_speakers: the voice has no speaker table (piper_hip_voice_attach_speakers)");
+    if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
+    for (int i = 0; i < n; i++)
+      if (int rc = check_speaker(v, speakers[i], i)) return rc;
+  }
+  return predict_impl(v, utts, n, durations_out, logw_out, max_entries, nullptr, speakers);
+}
 namespace {
 // plan_out (optional): the encoder + predictor plan that ran, left marked in_use so that its m_p / logs_p stay put until the caller
 // has enqueued the copy into the plan that continues from them (the caller clears in_use)
-int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out) {
+// speakers (optional): [n], one per utterance, checked by the caller; null on a voice with a table = speaker 0 alone
+int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
+                 const piper_hip_speaker* speakers) {
   if (!v || !utts || !durations_out) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0)");
+  std::vector<piper_hip_speaker> spk;
+  if (v->spk.S) {
+    piper_hip_speaker d{};
+    d.n = 1;
+    d.weights[0] = 1.0f;
+    spk.assign((size_t)n, d);
+    if (speakers) spk.assign(speakers, speakers + n);
+  }
   int Tmax = 0, rc;
   int64_t total = 0;
   for (int b = 0; b < n; b++) {
@@ -2706,6 +2899,7 @@ int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int
   if (e == hipSuccess) e = hipMemcpyAsync(s.lensT, lens.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s.set.stream);
   if (e == hipSuccess) e = hipMemcpyAsync(s.dp_noise, nz.data(), nz.size() * sizeof(float), hipMemcpyHostToDevice, s.set.stream);
   if (e == hipSuccess) e = hipMemcpyAsync(s.dp_scalars, sc.data(), sc.size(), hipMemcpyHostToDevice, s.set.stream);
+  if (e == hipSuccess && s.spk_in) e = hipMemcpyAsync(s.spk_in, spk.data(), spk.size() * sizeof(piper_hip_speaker), hipMemcpyHostToDevice, s.set.stream);
   if (e == hipSuccess && launch_plan(v, s)) e = hipErrorUnknown;
   std::vector<int32_t> dur((size_t)n * T);
   std::vector<float> lw(logw_out ? (size_t)n * T : 0);
@@ -3217,6 +3411,8 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (e == hipSuccess)
     e = hipMemcpy2DAsync(gs->zin, (size_t)gs->F * sizeof(float), s.z_out + a, (size_t)s.F * sizeof(float), (size_t)Fc * sizeof(float), (size_t)I,
                          hipMemcpyDeviceToDevice, gs->set.stream);
+  if (e == hipSuccess && gs->spk_bias)  // the item's conv_pre row travels with its latent window
+    e = hipMemcpyAsync(gs->spk_bias, s.spk_bias + v->spk_pre_off, (size_t)v->cfg.up_initial * sizeof(float), hipMemcpyDeviceToDevice, gs->set.stream);
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (pcm && want_out) {
     PcmRoute r;
@@ -3284,11 +3480,15 @@ int check_step_size(const piper_hip_voice* v, const char* who, int n, int chunk_
 // rows[src] (a pool: base pointer and row stride from the table). The choice is the same for every thread of the launch.
 __global__ __launch_bounds__(256) void stream_window_gather_kernel(const float* __restrict__ z, int Fz, const PoolRowRef* __restrict__ rows,
                                                                   const int* __restrict__ desc, float* __restrict__ zin,
-                                                                  int* __restrict__ lensF, int I, int Fg) {
+                                                                  int* __restrict__ lensF, int I, int Fg, const float* __restrict__ spk_src,
+                                                                  int64_t spk_stride, float* __restrict__ spk_dst, int U) {
   const int r = blockIdx.y;
   const int* d = desc + r * kDescInts;
   const int src = d[kDescSrc], a = d[kDescA], Fc = d[kDescFc];
   if (blockIdx.x == 0 && threadIdx.x == 0) lensF[r] = Fc;
+  // a voice with speakers (spk_dst): the source item's conv_pre row [U] moves with its latent — spk_src + src·spk_stride → row r
+  if (spk_dst && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < U; i += 256) spk_dst[(int64_t)r * U + i] = spk_src[(int64_t)src * spk_stride + i];
   if (Fc == 0) return;
   const int q4 = Fg >> 2;  // Fg % 16 == 0
   const int total = I * q4;
@@ -3367,9 +3567,13 @@ StreamPool* slot_pool(const piper_hip_voice* v, int slot) { return (v && slot >=
 // One thread per 4 frames of one channel, along frames (coalesced); both sides are bucket rows on 16-byte-aligned bases (Fw % 16 ==
 // stride % 16 == 0, stride = bucket_f(F) ≤ Fw), so every access is an aligned float4 inside its row. blockIdx.y = the join's entry.
 __global__ __launch_bounds__(256) void stream_adopt_kernel(const float* __restrict__ z, int Fw, const PoolJoinEnt* __restrict__ tab,
-                                                          const PoolRowRef* __restrict__ rows, int I) {
+                                                          const PoolRowRef* __restrict__ rows, int I, const float* __restrict__ spk_src,
+                                                          int64_t spk_stride, float* __restrict__ spk_rows, int U) {
   const PoolJoinEnt e = tab[blockIdx.y];
   const PoolRowRef rr = rows[e.row];
+  // a voice with speakers (spk_rows): the item's conv_pre row [U] enters the pool with its latent and stays until the row is taken again
+  if (spk_rows && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < U; i += 256) spk_rows[(int64_t)e.row * U + i] = spk_src[(int64_t)e.src * spk_stride + i];
   const int stride = (int)rr.stride, q4 = stride >> 2;
   const int total = I * q4;
   const float* zi = z + (int64_t)e.src * I * Fw;
@@ -3419,6 +3623,8 @@ struct StepView {
   const hipEvent_t* wait;    // "the latents are there": what the step's stream waits for (the GPU waits, the host does not)
   size_t n_wait;
   StreamRate* rs;            // the stream's output rate; a resampling step packs int16 through resample_step_kernel and its own descriptor
+  const float* spk = nullptr;  // a voice with speakers: the items' conv_pre rows, item src at spk + src·spk_stride (null otherwise)
+  int64_t spk_stride = 0;
 };
 
 // stream_next_batch: the next chunk of every active row in one generator launch at the stream's fixed batch; *ran = a step ran and has
@@ -3498,7 +3704,8 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   if (e == hipSuccess) e = hipMemcpyAsync(s.d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
   if (e == hipSuccess) {
     const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (Fg / 4), 256), 64);
-    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, s.z, s.Fz, s.d_rows, s.d_desc, gs->zin, gs->lensF, I, Fg);
+    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, s.z, s.Fz, s.d_rows, s.d_desc, gs->zin, gs->lensF, I, Fg, s.spk,
+                       s.spk_stride, s.spk ? gs->spk_bias : nullptr, v->cfg.up_initial);
     e = hipGetLastError();
   }
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
@@ -3538,7 +3745,7 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
 int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm,
               float gain, int law) {
   const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, P.pack_bytes / sizeof(float),
-                                       nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), &P.rs};
+                                       nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), &P.rs, P.spk_rows, v->cfg.up_initial};
   bool ran = false;
   const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran);
   if (rc || !ran) return rc;  // (an idle pool: joins since the last step stay pending)
@@ -3592,7 +3799,7 @@ int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samp
   Slot& s = *sp;
   const int n = (int)s.bs_rows.size();
   const StepView<StreamRow> view{s.bs_rows.data(), n, group_batch(n), s.st_chunk, s.st_halo, s.bs_desc, s.bs_pack, s.bs_pack_cap,
-                                 s.z_out, s.F, nullptr, &s.set.ev1, 1, &s.rs};
+                                 s.z_out, s.F, nullptr, &s.set.ev1, 1, &s.rs, s.spk_bias ? s.spk_bias + v->spk_pre_off : nullptr, v->spk.Ctot};
   bool ran = false;
   return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran);
 }
@@ -3625,6 +3832,7 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   pool_close(v, slot);
   detach(v, slot);  // what the slot id held is replaced, as by a prepare
+  v->planned = true;
   std::unique_ptr<StreamPool> P(new StreamPool());
   P->capacity = capacity;
   P->NBg = group_batch(capacity);
@@ -3637,6 +3845,14 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
   if (!rc) { rc = v->ctx->pool.alloc((size_t)P->NBg * kDescInts * sizeof(int), &p); if (!rc) P->d_desc = (int*)p; }
   P->pack_bytes = (size_t)capacity * chunk_frames * v->hop * sizeof(float);
   if (!rc) { rc = v->ctx->pool.alloc(P->pack_bytes, &p); if (!rc) P->pack = (float*)p; }
+  if (!rc && v->spk.S) {  // the rows' conv_pre biases; a row never taken reads as 0.0
+    const size_t bytes = (size_t)capacity * v->cfg.up_initial * sizeof(float);
+    rc = v->ctx->pool.alloc(bytes, &p);
+    if (!rc) {
+      P->spk_rows = (float*)p;
+      if (hipMemset(p, 0, bytes) != hipSuccess) { (void)hipGetLastError(); rc = PIPER_HIP_ERR_LAUNCH; ph::set_error("stream_pool_open: clearing the speaker rows failed"); }
+    }
+  }
   v->pools[slot] = std::move(P);
   if (rc) { pool_close(v, slot); return rc; }
   return PIPER_HIP_OK;
@@ -3707,7 +3923,8 @@ PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, con
   if (e == hipSuccess) e = hipMemcpyAsync(P->d_rows, sg.h_desc, (tab_ints + join_ints) * sizeof(int), hipMemcpyHostToDevice, q);
   if (e == hipSuccess) {
     const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (stride_max / 4), 256), 64);
-    hipLaunchKernelGGL(stream_adopt_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I);
+    hipLaunchKernelGGL(stream_adopt_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I,
+                       w.spk_bias ? w.spk_bias + v->spk_pre_off : nullptr, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr, v->cfg.up_initial);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipEventRecord(ev, q);
@@ -4105,8 +4322,10 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
     if (upto < 0) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': the schedule has no step '%s'", name, step_name.c_str());
   }
   // items back to back, each compacted to its true length: [C][len_b]
+  // (unit < 0: a tensor of fixed length, the whole row for every item — the speaker taps)
+  auto item_len = [&](int b) { return (size_t)(t.unit < 0 ? t.row : t.unit == 0 ? owner.h_T[b] : owner.h_F[b] * t.unit); };
   size_t total = 0;
-  for (int b = 0; b < s.NB; b++) total += (size_t)t.C * (size_t)(t.unit == 0 ? owner.h_T[b] : owner.h_F[b] * t.unit);
+  for (int b = 0; b < s.NB; b++) total += (size_t)t.C * item_len(b);
   if (n_floats) *n_floats = total;
   if (host) {
     if (max_floats < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
@@ -4134,7 +4353,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
     }
     size_t off = 0;
     for (int b = 0; b < s.NB; b++) {
-      const size_t len = (size_t)(t.unit == 0 ? owner.h_T[b] : owner.h_F[b] * t.unit);
+      const size_t len = item_len(b);
       if (len)
         PH_HIP(hipMemcpy2D(host + off, len * sizeof(float), t.p + (size_t)b * t.batch_stride, (size_t)t.row * sizeof(float), len * sizeof(float),
                            (size_t)t.C, hipMemcpyDeviceToHost), PIPER_HIP_ERR_LAUNCH);

@@ -186,3 +186,45 @@ PH_EXPORT int piper_hip_voice_synthetic_blob(const piper_hip_voice_config* cfg, 
   piper_hip_layout_walk(cfg, synth_visit, &so);
   return PIPER_HIP_OK;
 }
+
+// ---- the speaker blob of a multi-speaker voice (piper_hip.h "Multi-speaker voices"): the voice blob's conventions, one more walk ----
+namespace ph {
+int validate_speaker_config(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* sc) {
+  int rc = validate_config(cfg);
+  if (rc) return rc;
+  if (!sc) PH_FAIL(PIPER_HIP_ERR_ARG, "null speaker config");
+  if (sc->n_speakers < 1 || sc->n_speakers > 65536) PH_FAIL(PIPER_HIP_ERR_SHAPE, "n_speakers %d outside [1, 65536]", sc->n_speakers);
+  if (sc->gin < 4 || sc->gin > 1024 || sc->gin % 4) PH_FAIL(PIPER_HIP_ERR_SHAPE, "gin %d must be a multiple of 4 in [4, 1024]", sc->gin);
+  return PIPER_HIP_OK;
+}
+}  // namespace ph
+
+PH_EXPORT int piper_hip_speaker_blob_floats(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg, size_t* n_floats) {
+  int rc = ph::validate_speaker_config(cfg, scfg);
+  if (rc) return rc;
+  if (!n_floats) PH_FAIL(PIPER_HIP_ERR_ARG, "null n_floats");
+  *n_floats = piper_hip_speaker_layout_walk(cfg, scfg, nullptr, nullptr);
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_speaker_blob_layout(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg, piper_hip_tensor_info* out,
+                                            int max_entries, int* n_entries) {
+  int rc = ph::validate_speaker_config(cfg, scfg);
+  if (rc) return rc;
+  LayoutOut lo{out, max_entries, 0};
+  piper_hip_speaker_layout_walk(cfg, scfg, layout_visit, &lo);
+  if (n_entries) *n_entries = lo.n;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_speaker_synthetic_blob(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg, uint64_t seed,
+                                               float* host_blob, size_t n_floats) {
+  int rc = ph::validate_speaker_config(cfg, scfg);
+  if (rc) return rc;
+  if (!host_blob) PH_FAIL(PIPER_HIP_ERR_ARG, "null blob");
+  const size_t need = piper_hip_speaker_layout_walk(cfg, scfg, nullptr, nullptr);
+  if (n_floats < need) PH_FAIL(PIPER_HIP_ERR_SHAPE, "speaker blob too small: %zu < %zu floats", n_floats, need);
+  SynthOut so{host_blob, seed, 0};
+  piper_hip_speaker_layout_walk(cfg, scfg, synth_visit, &so);
+  return PIPER_HIP_OK;
+}

@@ -112,6 +112,33 @@ class Utterance(C.Structure):
 NOISE_MODES = {"injected": 0, "device": 1}
 
 
+class SpeakerConfig(C.Structure):
+    """piper_hip_speaker_config: the speaker table's rows and the width gin of a speaker vector (multiple of 4, 4 … 1024)."""
+    _fields_ = [("n_speakers", C.c_int32), ("gin", C.c_int32)]
+
+
+class Speaker(C.Structure):
+    """piper_hip_speaker: a mix g = Σ_k weights[k] · emb_g[ids[k]] of 1 … 4 table rows."""
+    _fields_ = [("n", C.c_int32), ("ids", C.c_int32 * 4), ("weights", C.c_float * 4)]
+
+
+def _speaker(s):
+    """int → that speaker alone; {id: weight} or [(id, weight), …] → a mix; a Speaker is passed through. What does not fit the record is
+    handed on out of range, for the library to refuse."""
+    if isinstance(s, Speaker):
+        return s
+    pairs = [(int(s), 1.0)] if isinstance(s, (int, np.integer)) else list(s.items() if isinstance(s, dict) else s)
+    out = Speaker()
+    out.n = len(pairs)
+    for k, (i, w) in enumerate(pairs[:4]):
+        out.ids[k], out.weights[k] = int(i), float(w)
+    return out
+
+
+def _speakers(speakers):
+    return (Speaker * len(speakers))(*[_speaker(s) for s in speakers])
+
+
 class PcmParams(C.Structure):
     """piper_hip_pcm_params: linear gain (0 = 1.0) and the peak-normalisation flag of the 16-bit PCM entry points."""
     _fields_ = [("gain", C.c_float), ("normalize", C.c_int32)]
@@ -286,6 +313,18 @@ _PROTOS = {
     "piper_hip_voice_profile": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),
     "piper_hip_voice_time_subset": (C.c_int, [c_vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                               C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "piper_hip_speaker_blob_floats": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig), C.POINTER(C.c_size_t)]),
+    "piper_hip_speaker_blob_layout": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig), C.POINTER(TensorInfo), C.c_int,
+                                                C.POINTER(C.c_int)]),
+    "piper_hip_speaker_synthetic_blob": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig), C.c_uint64, c_f32p, C.c_size_t]),
+    "piper_hip_voice_attach_speakers": (C.c_int, [c_vp, C.POINTER(SpeakerConfig), c_vp, C.c_int]),
+    "piper_hip_voice_num_speakers": (C.c_int, [c_vp]),
+    "piper_hip_voice_slot_speakers": (C.c_int, [c_vp, C.c_int, C.POINTER(Speaker), C.c_int]),
+    "piper_hip_voice_predict_durations_speakers": (C.c_int, [c_vp, C.POINTER(Utterance), C.c_int, C.POINTER(Speaker), c_i32p, c_f32p, C.c_int]),
+    "piper_hip_onnx_speaker_config": (C.c_int, [c_vp, C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig)]),
+    "piper_hip_onnx_infer_config_speakers": (C.c_int, [c_vp, C.POINTER(VoiceConfig)]),
+    "piper_hip_onnx_build_speaker_blob": (C.c_int, [c_vp, C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig), c_f32p, C.c_size_t]),
+    "piper_hip_voice_check_json_speakers": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig), C.POINTER(PiperJsonInfo)]),
 }
 
 _lib = None
@@ -742,6 +781,40 @@ def synthetic_blob(cfg, seed=1234):
     return blob
 
 
+def speaker_config(n_speakers, gin=512):
+    """The speaker table of a multi-speaker voice: rows and the width of a speaker vector (Piper: 512)."""
+    return SpeakerConfig(int(n_speakers), int(gin))
+
+
+def speaker_blob_floats(cfg, scfg):
+    n = C.c_size_t()
+    _check(load_library().piper_hip_speaker_blob_floats(C.byref(cfg), C.byref(scfg), C.byref(n)))
+    return n.value
+
+
+def speaker_blob_layout(cfg, scfg):
+    lib = load_library()
+    n = C.c_int()
+    _check(lib.piper_hip_speaker_blob_layout(C.byref(cfg), C.byref(scfg), None, 0, C.byref(n)))
+    arr = (TensorInfo * n.value)()
+    _check(lib.piper_hip_speaker_blob_layout(C.byref(cfg), C.byref(scfg), arr, n.value, C.byref(n)))
+    return [dict(name=t.name.decode(), kind=t.kind, shape=[int(t.shape[i]) for i in range(t.rank)], fan_in=int(t.fan_in),
+                 offset=int(t.offset), count=int(t.count)) for t in arr]
+
+
+def synthetic_speaker_blob(cfg, scfg, seed=4321):
+    """Host-only (no GPU): synthetic speaker table and cond convs, by the rule of synthetic_blob with a seed of its own."""
+    n = speaker_blob_floats(cfg, scfg)
+    blob = np.empty(n, np.float32)
+    _check(load_library().piper_hip_speaker_synthetic_blob(C.byref(cfg), C.byref(scfg), seed, blob.ctypes.data_as(c_f32p), n))
+    return blob
+
+
+def speaker_row_floats(cfg):
+    """Ctot: floats of one item's speaker row (dp.pre; the flow's gated convs; dec.conv_pre)."""
+    return (cfg.hidden if cfg.dp_present else 0) + cfg.n_flows * cfg.wn_layers * 2 * cfg.hidden + cfg.up_initial
+
+
 COMM_ID_BYTES = 128
 
 
@@ -860,12 +933,47 @@ class OnnxModel:
         _check(fn(self.h, C.byref(cfg), blob.ctypes.data_as(c_f32p), blob.size))
         return blob
 
+    def infer_config_speakers(self):
+        """infer_config that does not refuse a multi-speaker file (`emb_g` / `cond` initializers)."""
+        cfg = VoiceConfig()
+        _check(self.lib.piper_hip_onnx_infer_config_speakers(self.h, C.byref(cfg)))
+        return cfg
 
-def load_voice(onnx_path, json_path=None, verify=True):
+    def speaker_config(self, cfg):
+        """The file's speaker table (n_speakers = 0: none); raises ShapeMismatch naming a missing or misshapen cond tensor."""
+        scfg = SpeakerConfig()
+        _check(self.lib.piper_hip_onnx_speaker_config(self.h, C.byref(cfg), C.byref(scfg)))
+        return scfg
+
+    def build_speaker_blob(self, cfg, scfg):
+        blob = np.empty(speaker_blob_floats(cfg, scfg), np.float32)
+        _check(self.lib.piper_hip_onnx_build_speaker_blob(self.h, C.byref(cfg), C.byref(scfg), blob.ctypes.data_as(c_f32p), blob.size))
+        return blob
+
+
+def load_voice(onnx_path, json_path=None, verify=True, speakers=False):
     """(cfg, blob, json info) of a Piper voice: `<voice>.onnx` + `<voice>.onnx.json` (PiperVoices layout). The node graph is verified
-    against the launch schedule (refused otherwise) unless verify=False."""
+    against the launch schedule (refused otherwise) unless verify=False.
+    speakers=True: a multi-speaker voice is taken instead of refused and the result is (cfg, blob, json info, scfg, speaker blob) — for
+    HipRuntime(...).attach_speakers(scfg, speaker_blob); scfg.n_speakers == 0 and a None blob for a file without a table. No verifier
+    for the conditioned graph exists yet: the main blob of a file WITH a table is built unchecked, whatever `verify` says."""
     m = OnnxModel(onnx_path)
     try:
+        if speakers:
+            cfg = m.infer_config_speakers()
+            scfg = m.speaker_config(cfg)
+            info = None
+            jp = json_path or (str(onnx_path) + ".json")
+            if os.path.exists(jp):
+                info = piper_json(open(jp, "r", encoding="utf-8").read())
+                if scfg.n_speakers:
+                    _check(load_library().piper_hip_voice_check_json_speakers(C.byref(cfg), C.byref(scfg), C.byref(info)))
+                else:
+                    _check(load_library().piper_hip_voice_check_json(C.byref(cfg), C.byref(info)))
+                cfg.sample_rate = info.sample_rate
+            if not scfg.n_speakers:
+                return cfg, m.build_blob(cfg, verify), info, scfg, None
+            return cfg, m.build_blob(cfg, False), info, scfg, m.build_speaker_blob(cfg, scfg)
         cfg = m.infer_config()
         info = None
         jp = json_path or (str(onnx_path) + ".json")
@@ -1053,6 +1161,26 @@ class HipRuntime:
             self.lib.piper_hip_host_free(self.backend.ctx, p)
         self._pinned = []
 
+    def attach_speakers(self, scfg, blob, on_device=False):
+        """The speaker table of a multi-speaker voice (piper_hip_voice_attach_speakers): once, before the first prepare."""
+        if on_device:
+            ptr = _ptr(blob)
+        else:
+            self._spk_blob = np.ascontiguousarray(blob, np.float32)
+            ptr = self._spk_blob.ctypes.data_as(c_vp)
+        _check(self.lib.piper_hip_voice_attach_speakers(self.voice, C.byref(scfg), ptr, int(on_device)))
+
+    def num_speakers(self):
+        return int(self.lib.piper_hip_voice_num_speakers(self.voice))
+
+    def slot_speakers(self, slot, speakers):
+        """The speakers of the slot's items from now on: entry i for item i of every later prepare / stream begin (a pool join: of its work
+        slot), the last entry for items past the list, None or [] = speaker 0 alone again. An entry is an id, a {id: weight} mix of up
+        to four, or a Speaker."""
+        speakers = list(speakers or [])
+        arr = _speakers(speakers) if speakers else None
+        _check(self.lib.piper_hip_voice_slot_speakers(self.voice, int(slot), arr, len(speakers)))
+
     def set_precision(self, precision):
         """"f32" (default, the parity configuration) or "bf16" (generator convs on bf16 operands, fp32 accumulate)."""
         code = {"f32": 0, "fp32": 0, "bf16": 1}.get(precision, precision)
@@ -1075,9 +1203,12 @@ class HipRuntime:
         u, _k = self._utt(ids, durations, None, 0.0)
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
-    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, **kw):
+    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
-        reference's `overrides`. Without durations the frames per id come from the voice's duration predictor."""
+        reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
+        speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays."""
+        if speaker is not None:
+            self.slot_speakers(0, [speaker])
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
@@ -1139,8 +1270,9 @@ class HipRuntime:
         _check(self.lib.piper_hip_voice_durations(self.voice, slot, out.ctypes.data_as(c_i32p), n.value, C.byref(n)))
         return out
 
-    def predict_durations(self, utterances, noise_w=0.8, length_scale=1.0, noise_mode="injected", seed=1234):
-        """utterances: list of (phonemeIDs, dp_noise-or-None). Returns (durations, logw) lists per utterance."""
+    def predict_durations(self, utterances, noise_w=0.8, length_scale=1.0, noise_mode="injected", seed=1234, speakers=None):
+        """utterances: list of (phonemeIDs, dp_noise-or-None). Returns (durations, logw) lists per utterance. speakers (a voice with a
+        speaker table): one entry per utterance, as for slot_speakers (piper_hip_voice_predict_durations_speakers)."""
         n = len(utterances)
         arr = (Utterance * n)()
         keep = []
@@ -1151,7 +1283,11 @@ class HipRuntime:
         total = sum(len(u[0]) for u in utterances)
         dur = np.empty(total, np.int32)
         lw = np.empty(total, np.float32)
-        _check(self.lib.piper_hip_voice_predict_durations(self.voice, arr, n, dur.ctypes.data_as(c_i32p), lw.ctypes.data_as(c_f32p), total))
+        if speakers is not None:
+            _check(self.lib.piper_hip_voice_predict_durations_speakers(self.voice, arr, n, _speakers(list(speakers)), dur.ctypes.data_as(c_i32p),
+                                                                       lw.ctypes.data_as(c_f32p), total))
+        else:
+            _check(self.lib.piper_hip_voice_predict_durations(self.voice, arr, n, dur.ctypes.data_as(c_i32p), lw.ctypes.data_as(c_f32p), total))
         outs, off = [], 0
         for ids, _ in utterances:
             outs.append((dur[off:off + len(ids)].copy(), lw[off:off + len(ids)].copy()))

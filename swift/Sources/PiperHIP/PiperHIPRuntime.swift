@@ -31,30 +31,73 @@ public final class PiperHIPRuntime {
 
     /// A Piper voice file: the ONNX loader (host-only C++) infers the geometry, folds weight norm and lays the weights out in the order
     /// of include/piper_hip_voice_layout.h; `voice.onnx.json` supplies the sample rate (PiperConfig.swift:3-47).
-    public init(modelPath: String, device: Int32 = 0) throws {
+    /// `speakers: true` takes a multi-speaker voice (`emb_g` + cond convs) instead of refusing it: the speaker table is loaded and attached
+    /// (piper_hip_voice_attach_speakers) and `slotSpeakers` chooses who speaks. No verifier for the conditioned graph exists yet, so the
+    /// weights of such a file are taken unchecked (piper_hip_onnx_build_blob_unchecked): the caller vouches that it is a standard Piper VITS.
+    public init(modelPath: String, device: Int32 = 0, speakers: Bool = false) throws {
         backend = try HIPBackend(device: device)
         var model: OpaquePointer?
         try HIPBackend.check(piper_hip_onnx_open(modelPath, &model))
         defer { piper_hip_onnx_close(model) }
         var cfg = piper_hip_voice_config()
-        try HIPBackend.check(piper_hip_onnx_infer_config(model, &cfg))
+        var scfg = piper_hip_speaker_config()
+        if speakers {
+            try HIPBackend.check(piper_hip_onnx_infer_config_speakers(model, &cfg))
+            try HIPBackend.check(piper_hip_onnx_speaker_config(model, &cfg, &scfg))   // n_speakers = 0: a single-speaker file
+        } else {
+            try HIPBackend.check(piper_hip_onnx_infer_config(model, &cfg))
+        }
         if let json = try? String(contentsOfFile: modelPath + ".json", encoding: .utf8) {
             var info = piper_hip_piper_json_info()
             try HIPBackend.check(piper_hip_piper_json(json, &info))
-            try HIPBackend.check(piper_hip_voice_check_json(&cfg, &info))       // num_symbols vs n_vocab, single speaker
+            if scfg.n_speakers > 0 {
+                try HIPBackend.check(piper_hip_voice_check_json_speakers(&cfg, &scfg, &info))   // num_speakers == table rows
+            } else {
+                try HIPBackend.check(piper_hip_voice_check_json(&cfg, &info))   // num_symbols vs n_vocab, single speaker
+            }
             cfg.sample_rate = info.sample_rate
         }
         var n = 0
         try HIPBackend.check(piper_hip_voice_blob_floats(&cfg, &n))
         var blob = [Float](repeating: 0, count: n)
-        try HIPBackend.check(piper_hip_onnx_build_blob(model, &cfg, &blob, n))
+        if scfg.n_speakers > 0 {
+            try HIPBackend.check(piper_hip_onnx_build_blob_unchecked(model, &cfg, &blob, n))
+        } else {
+            try HIPBackend.check(piper_hip_onnx_build_blob(model, &cfg, &blob, n))
+        }
         try HIPBackend.check(piper_hip_voice_create(backend.ctx, &cfg, blob, 0, &voice))
+        if scfg.n_speakers > 0 {                                               // before the voice's first prepare
+            var sn = 0
+            try HIPBackend.check(piper_hip_speaker_blob_floats(&cfg, &scfg, &sn))
+            var sblob = [Float](repeating: 0, count: sn)
+            try HIPBackend.check(piper_hip_onnx_build_speaker_blob(model, &cfg, &scfg, &sblob, sn))
+            try HIPBackend.check(piper_hip_voice_attach_speakers(voice, &scfg, sblob, 0))
+        }
         sampleRate = cfg.sample_rate
         var h = 1                                                              // hop = Π upsample rates (256 for Piper)
         withUnsafeBytes(of: &cfg.up_rates) { r in for i in 0..<Int(cfg.n_ups) { h *= Int(r.load(fromByteOffset: 4 * i, as: Int32.self)) } }
         hop = h
     }
     deinit { piper_hip_voice_destroy(voice) }
+
+    /// Rows of the voice's speaker table; 0 for a single-speaker voice (piper_hip_voice_num_speakers).
+    public var numSpeakers: Int32 { piper_hip_voice_num_speakers(voice) }
+
+    /// The speakers of a slot's items from now on (piper_hip_voice_slot_speakers) — the graph's `sid`, read by PiperMetalRuntime.synthesize
+    /// next to the scales (PiperMetalRuntime.swift:62-80). Entry i is for item i of every later prepare / stream begin on the slot (a pool
+    /// join: of its work slot), the last entry for items past the list, an empty list = speaker 0 alone again. An entry is a mix of one to
+    /// four (id, weight) pairs: g = Σ weight · emb_g[id]; [(id, 1)] is the plain speaker id.
+    public func slotSpeakers(slot: Int32, speakers: [[(id: Int32, weight: Float)]]) throws {
+        var recs = speakers.map { mix -> piper_hip_speaker in
+            var s = piper_hip_speaker()
+            s.n = Int32(mix.count)                                             // outside 1 … 4: refused by the library
+            withUnsafeMutableBytes(of: &s.ids) { p in for (k, e) in mix.prefix(4).enumerated() { p.storeBytes(of: e.id, toByteOffset: 4 * k, as: Int32.self) } }
+            withUnsafeMutableBytes(of: &s.weights) { p in for (k, e) in mix.prefix(4).enumerated() { p.storeBytes(of: e.weight, toByteOffset: 4 * k, as: Float.self) } }
+            return s
+        }
+        try HIPBackend.check(piper_hip_voice_slot_speakers(voice, slot, &recs, Int32(recs.count)))
+    }
+    public func slotSpeaker(slot: Int32, id: Int32) throws { try slotSpeakers(slot: slot, speakers: [[(id: id, weight: 1.0)]]) }
 
     /// PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:) — the whole graph on the device: `durations == nil` ⇒ the
     /// voice's stochastic duration predictor runs (part of the plan's HIP graph); `noise_mode = DEVICE` ⇒ both RandomNormalLike tensors are
