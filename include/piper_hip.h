@@ -662,6 +662,67 @@ int piper_hip_voice_stream_next_g711(piper_hip_voice* v, int slot, const piper_h
 int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
                                            int64_t max_samples, int64_t* n_samples);
 
+/* ---- Mixed formats: every row of a batched stream picks its rate, encoding and gain (DESIGN.md §4 "Mixed formats") ----
+ * One process that serves a SIP trunk (8 kHz μ-law), browsers (48 kHz s16) and an ASR tap (16 kHz s16) from one voice wants ONE pool: one
+ * generator launch per step for all of them, and one output launch behind it whatever the formats present. On a mixed slot the output
+ * format is a property of the item (group) or of the row's occupant (pool), fixed from the call that supplies it until the row is freed.
+ * Per row the arithmetic is the contracts above and nothing else: S16 rows follow "16-bit PCM" (normalize = 0) and "Output rate", μ-law and
+ * A-law rows "G.711 output", each with the stream emit rule [j0, j1) of the row's own (L, M, P). F32 rows at a rate deliver the fp32 y of
+ * piper_hip_resample_f32, F32 rows at the voice's own rate the float chunk itself. The concatenation of a row's chunks equals the
+ * whole-item conversion of the item's fp32 samples at the row's format, bit for bit; a mixed slot whose rows all carry one format
+ * delivers, row by row, the bytes and counts of a slot with stream_set_rate and the matching step call.
+ * Normalisation is not offered: a format has no field for it, because steps never could normalise. Single streams (stream_begin) are out
+ * of scope: one row has stream_set_rate plus a law per step already.
+ *
+ * Layout of one step's output. Rows are written in row order. Row r's chunk starts at byte_off[r] and holds n_samples[r] · elem(r) bytes,
+ * elem = 2 for S16, 1 for G.711, 4 for F32. byte_off of the first delivering row is 0; every later one is the previous delivering row's
+ * end rounded up to a multiple of 4. A row that delivers nothing reports the offset the next delivering row takes (n_samples[r] = 0; it
+ * owns no byte). The content of the pad bytes is unspecified. The step's total is the last delivering row's end.
+ *
+ * Sizing the buffer. A row's share of a step is B · elem rounded up to a multiple of 4, with B = chunk_frames · hop at the voice's own
+ * rate and B = piper_hip_resample_step_bound(voice rate, out_rate, chunk_frames · hop) otherwise — host-only arithmetic, so a host can
+ * size its buffer ahead of joins (capacity × the largest share it will ever admit). piper_hip_voice_stream_step_capacity_bytes sums the
+ * shares of the rows as they stand.
+ *
+ * Format checks happen on the host, at the call that supplies the format: encoding outside 0 … 3, a negative or non-finite gain, or a
+ * gain other than 0 or 1 on an F32 row is PIPER_HIP_ERR_ARG; a rate outside the "Output rate" list (or L > 640, or P > 256) is
+ * PIPER_HIP_ERR_UNSUPPORTED. out_rate 0 or the voice's own rate is not a filter. */
+#define PIPER_HIP_ENC_S16   0
+#define PIPER_HIP_ENC_MULAW 1   /* == PIPER_HIP_G711_MULAW */
+#define PIPER_HIP_ENC_ALAW  2   /* == PIPER_HIP_G711_ALAW  */
+#define PIPER_HIP_ENC_F32   3
+typedef struct {
+  int32_t out_rate;  /* 0 = the voice's own rate (not a filter) */
+  int32_t encoding;  /* PIPER_HIP_ENC_* */
+  float   gain;      /* 0 is taken as 1.0; F32 rows: must be 0 or 1 */
+} piper_hip_stream_format;   /* all zero = s16 at the voice's rate, gain 1 */
+/* Marks the batched stream on `slot` mixed. Allowed exactly where stream_set_rate is: after stream_begin_batch or stream_pool_open, before
+ * the slot's first step, and for a pool also before its first join. It allocates the per-row history as stream_set_rate does; every row
+ * starts in the default format (all zero). PIPER_HIP_ERR_ARG, and nothing changes: on a single stream (stream_begin), on a slot that has
+ * a rate set, on a second call, after the slot has started. A new begin / open resets the slot to not mixed. On a mixed slot
+ * stream_set_rate, stream_rate and stream_step_capacity return PIPER_HIP_ERR_ARG. */
+int piper_hip_voice_stream_set_mixed(piper_hip_voice* v, int slot);
+/* A mixed GROUP, before its first step: the formats of items 0 … n−1 (n ≥ 1); items past n take the last entry. A refused call changes
+ * nothing. On a pool it is PIPER_HIP_ERR_ARG: there the join brings the formats. */
+int piper_hip_voice_stream_item_formats(piper_hip_voice* v, int slot, const piper_hip_stream_format* fmts, int n);
+/* stream_pool_join on a mixed pool with one format per joining item. samples_out[i] = J(N_i) at item i's rate (N_i at the voice's own).
+ * A row keeps its format until it is freed; the next occupant brings its own and never sees the previous occupant's history. A plain
+ * stream_pool_join on a mixed pool joins its items in the default format. A refused join leaves nothing joined. On a pool that is not
+ * mixed it is PIPER_HIP_ERR_ARG. */
+int piper_hip_voice_stream_pool_join_formats(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
+                                             const piper_hip_stream_format* fmts, int* items_out, int64_t* samples_out);
+/* The step of a mixed slot, and the only one it accepts: every other stream_next call on a mixed slot, and this call on a slot that is not
+ * mixed, is PIPER_HIP_ERR_ARG and consumes nothing. n_samples and byte_off have one entry per item (group) or row (pool); n_samples
+ * counts samples, as the other steps do; the bytes follow the layout above. All n_samples zero means end / idle. max_bytes smaller than
+ * the step's total is PIPER_HIP_ERR_SHAPE, host == NULL PIPER_HIP_ERR_ARG; both consume nothing. stream_drop works as before. */
+int piper_hip_voice_stream_next_batch_mixed(piper_hip_voice* v, int slot, void* host, int64_t max_bytes, int64_t* n_samples, int64_t* byte_off);
+/* The bytes one step of that mixed slot can deliver with the rows' current formats: the sum of the shares (above) of the rows that hold
+ * an unfinished item. Free pool rows count 0, so ask again after a join. A negative status on a slot that is not mixed. */
+int64_t piper_hip_voice_stream_step_capacity_bytes(piper_hip_voice* v, int slot);
+/* The format of item / row `item` as the slot holds it: out_rate 0 when it is the voice's own rate, gain never 0. PIPER_HIP_ERR_ARG for
+ * a free pool row, an item out of range, or a slot that is not mixed. */
+int piper_hip_voice_stream_item_format(piper_hip_voice* v, int slot, int item, piper_hip_stream_format* out);
+
 /* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
  * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]
  * (the graph's `sid` input, read by PiperMetalRuntime.synthesize next to `scales`, PiperMetalRuntime.swift:62-80; in the graph a Gather

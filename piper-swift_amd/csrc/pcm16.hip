@@ -24,66 +24,6 @@
 namespace ph {
 namespace {
 
-// n samples src → dst, shared among `nth` threads of which this is `tid`
-__device__ __forceinline__ void pcm_span(const float* __restrict__ src, int16_t* __restrict__ dst, int64_t n, int64_t tid, int64_t nth,
-                                         const PcmCvt c) {
-  const bool src16 = ((uintptr_t)src & 15) == 0;
-  int64_t done = 0;
-  if (src16 && ((uintptr_t)dst & 15) == 0) {
-    const int64_t n8 = n >> 3;
-    for (int64_t i = tid; i < n8; i += nth) {
-      const float4 a = ((const float4*)src)[2 * i], b = ((const float4*)src)[2 * i + 1];
-      uint4 o;
-      o.x = pcm_pair(a.x, a.y, c); o.y = pcm_pair(a.z, a.w, c); o.z = pcm_pair(b.x, b.y, c); o.w = pcm_pair(b.z, b.w, c);
-      ((uint4*)dst)[i] = o;
-    }
-    done = n8 << 3;
-  } else if (src16 && ((uintptr_t)dst & 7) == 0) {
-    const int64_t n4 = n >> 2;
-    for (int64_t i = tid; i < n4; i += nth) {
-      const float4 a = ((const float4*)src)[i];
-      uint2 o;
-      o.x = pcm_pair(a.x, a.y, c); o.y = pcm_pair(a.z, a.w, c);
-      ((uint2*)dst)[i] = o;
-    }
-    done = n4 << 2;
-  }
-  for (int64_t i = done + tid; i < n; i += nth) dst[i] = (int16_t)pcm_cvt(src[i], c);
-}
-
-// the same with one G.711 byte per sample (c.law), dst at any byte address
-__device__ __forceinline__ void pcm_span(const float* __restrict__ src, uint8_t* __restrict__ dst, int64_t n, int64_t tid, int64_t nth,
-                                         const PcmCvt c) {
-  const int64_t head = min(n, (int64_t)((4 - ((uintptr_t)dst & 3)) & 3));  // byte stores up to the first 4-byte-aligned address
-  for (int64_t i = tid; i < head; i += nth) dst[i] = (uint8_t)g711_cvt(pcm_cvt(src[i], c), c.law);
-  const float* s = src + head;
-  uint8_t* d = dst + head;
-  const int64_t m = n - head;
-  const bool src16 = ((uintptr_t)s & 15) == 0;
-  int64_t done = 0;
-  if (src16 && ((uintptr_t)d & 15) == 0) {
-    const int64_t n16 = m >> 4;
-    for (int64_t i = tid; i < n16; i += nth) {
-      const float4 a = ((const float4*)s)[4 * i], b = ((const float4*)s)[4 * i + 1], e = ((const float4*)s)[4 * i + 2], f = ((const float4*)s)[4 * i + 3];
-      uint4 o;
-      o.x = g711_quad(a.x, a.y, a.z, a.w, c); o.y = g711_quad(b.x, b.y, b.z, b.w, c);
-      o.z = g711_quad(e.x, e.y, e.z, e.w, c); o.w = g711_quad(f.x, f.y, f.z, f.w, c);
-      ((uint4*)d)[i] = o;
-    }
-    done = n16 << 4;
-  } else {
-    const int64_t n4 = m >> 2;
-    for (int64_t i = tid; i < n4; i += nth) {
-      float4 a;
-      if (src16) a = ((const float4*)s)[i];
-      else { a.x = s[4 * i]; a.y = s[4 * i + 1]; a.z = s[4 * i + 2]; a.w = s[4 * i + 3]; }
-      ((unsigned*)d)[i] = g711_quad(a.x, a.y, a.z, a.w, c);
-    }
-    done = n4 << 2;
-  }
-  for (int64_t i = done + tid; i < m; i += nth) d[i] = (uint8_t)g711_cvt(pcm_cvt(s[i], c), c.law);
-}
-
 // Plan audio [NB][row] → the items back to back at their true lengths. blockIdx.y = item; the item's offset is the sum of the lengths
 // before it (NB ≤ 256 = one per thread), so plain, ragged and bounded slots — whose lengths only the device knows — take the same launch.
 // T: int16_t, or uint8_t for G.711 by `law`.

@@ -35,6 +35,20 @@ struct RsStepRow {
   int skip, n_in, count, off;
 };
 
+// One generator row of a mixed-format stream step (include/piper_hip.h "Mixed formats"; voice.hip fills it, mixed_step_kernel reads it):
+// RsStepRow with a BYTE offset into the packed output (a multiple of 4), plus the row's own format — its filter (L == 0: the voice's own
+// rate, not a filter: the chunk goes through the chunk-pack body and no history is read or written), the bytes of an output (4 fp32,
+// 2 int16, 1 G.711 by `law`), the gain, and the tile of rs_geometry for that filter (mix_step_plan fills it). n_in == 0: nothing in this step.
+struct MixStepRow {
+  int64_t s, j0, off;
+  const float* taps;
+  int skip, n_in, count;
+  int L, M, P;
+  int elem, law;
+  float gain;
+  int tile;
+};
+
 // Items of plan audio [NB][row] → back to back at J(lensF[b]·hop) samples each (lengths read from device memory and clamped to F), item b
 // at Σ_{i<b} J(·). elem = bytes of a sample of `out`: 4 the fp32 y; 2 int16 through the PCM contract — gain, and peak normalisation per
 // item when peaks != nullptr, as launch_pcm16_pack; 1 the G.711 byte of that int16 by `law` (PIPER_HIP_G711_*), `out` at any byte address.
@@ -45,5 +59,11 @@ hipError_t launch_resample_items(hipStream_t q, const float* audio, int64_t row,
 // [NBg][kRsHist] (read / written).
 hipError_t launch_resample_step(hipStream_t q, int NBg, int max_count, const float* audio, int64_t row, const RsStepRow* desc,
                                 const float* hist_old, float* hist_new, const RsFilter& f, float gain, void* out, int law);
+// One mixed-format stream step. mix_step_plan sets `tile` of every row of the host table that delivers through a filter and returns the
+// launch's geometry: grid.x covers the row that needs the most tiles (pack_blocks: what the rows at the voice's rate want), the dynamic
+// LDS is the largest any delivering row's filter needs. launch_mixed_step then takes the uploaded table; one launch whatever the formats.
+void mix_step_plan(MixStepRow* rows, int NBg, int pack_blocks, int* grid_x, size_t* lds_bytes);
+hipError_t launch_mixed_step(hipStream_t q, int NBg, int grid_x, size_t lds_bytes, const float* audio, int64_t row, const MixStepRow* desc,
+                             const float* hist_old, float* hist_new, void* out);
 
 }  // namespace ph

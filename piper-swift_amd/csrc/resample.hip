@@ -189,6 +189,43 @@ __global__ __launch_bounds__(256) void resample_step_kernel(const float* __restr
   rs_row<E, CL>(r, f, c, (char*)out + (int64_t)d.off * E, tile, (float*)rs_lds);
 }
 
+// One step of a mixed-format stream (include/piper_hip.h "Mixed formats"): row blockIdx.y brings its own filter, sink and gain in its
+// descriptor, and the block runs the body the uniform launch of that format runs — rs_row<E, false> behind a filter (the table read from
+// global memory at every L), pcm_span at the voice's own rate. Every branch below is formed from the descriptor, which the whole block
+// reads at one address: no wave diverges on the sink. Rows are packed at 4-byte-aligned BYTE offsets, so rs_row's lead is 0 and pcm_span's
+// head is empty; neither is special-cased. History as in resample_step_kernel, for the rows that have a filter; its soundness argument
+// holds unchanged, because a row keeps its format from its first step to its last.
+__global__ __launch_bounds__(256) void mixed_step_kernel(const float* __restrict__ audio, int64_t row, const MixStepRow* __restrict__ desc,
+                                                         const float* __restrict__ hist_old, float* __restrict__ hist_new,
+                                                         void* __restrict__ out) {
+  extern __shared__ float4 rs_lds[];
+  const MixStepRow d = desc[blockIdx.y];
+  if (d.n_in == 0) return;
+  const float* x = audio + (int64_t)blockIdx.y * row + d.skip;
+  void* dst = (char*)out + d.off;
+  PcmCvt c;
+  c.gain = d.gain; c.scale = 1.0f; c.norm = 0; c.law = d.law;
+  if (d.L == 0) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+    if (d.elem == 4) pcm_span(x, (float*)dst, (int64_t)d.n_in, tid, nth, c);
+    else if (d.elem == 2) pcm_span(x, (int16_t*)dst, (int64_t)d.n_in, tid, nth, c);
+    else pcm_span(x, (uint8_t*)dst, (int64_t)d.n_in, tid, nth, c);
+    return;
+  }
+  RsSrc r;
+  r.x = x;
+  r.hist = d.s > 0 ? hist_old + (int64_t)blockIdx.y * kRsHist : nullptr;  // a row's first step sees nothing of the row's previous occupant
+  r.s = d.s; r.e = d.s + d.n_in; r.j0 = d.j0; r.count = d.count;
+  if (blockIdx.x == 0 && threadIdx.x < kRsHist) {
+    const int i = threadIdx.x, at = d.n_in - kRsHist + i;
+    hist_new[(int64_t)blockIdx.y * kRsHist + i] = at >= 0 ? r.x[at] : (r.hist ? r.hist[i + d.n_in] : 0.0f);
+  }
+  const RsFilter f{d.taps, d.L, d.M, d.P};
+  if (d.elem == 4) rs_row<4, false>(r, f, c, dst, d.tile, (float*)rs_lds);
+  else if (d.elem == 2) rs_row<2, false>(r, f, c, dst, d.tile, (float*)rs_lds);
+  else rs_row<1, false>(r, f, c, dst, d.tile, (float*)rs_lds);
+}
+
 // The tile and the dynamic LDS of a launch with filter f
 void rs_geometry(const RsFilter& f, int* tile, size_t* lds_bytes) {
   int t = kRsTile;
@@ -291,6 +328,32 @@ hipError_t launch_resample_step(hipStream_t q, int NBg, int max_count, const flo
   if (law) { if (cl) RS_STEP(1, true); else RS_STEP(1, false); }
   else { if (cl) RS_STEP(2, true); else RS_STEP(2, false); }
 #undef RS_STEP
+  return hipGetLastError();
+}
+
+void mix_step_plan(MixStepRow* rows, int NBg, int pack_blocks, int* grid_x, size_t* lds_bytes) {
+  int64_t gx = 1;
+  size_t lds = 0;
+  for (int r = 0; r < NBg; r++) {
+    MixStepRow& d = rows[r];
+    if (d.n_in == 0) continue;
+    if (d.L == 0) {
+      gx = std::max<int64_t>(gx, pack_blocks);
+      continue;
+    }
+    size_t bytes;
+    rs_geometry(RsFilter{d.taps, d.L, d.M, d.P}, &d.tile, &bytes);
+    lds = std::max(lds, bytes);  // (a multiple of 16: the base of every row's span is 16-byte aligned)
+    gx = std::max(gx, ceil_div((int64_t)d.count + 3, d.tile));
+  }
+  *grid_x = (int)std::min<int64_t>(gx, 1024);
+  *lds_bytes = lds;
+}
+
+hipError_t launch_mixed_step(hipStream_t q, int NBg, int grid_x, size_t lds_bytes, const float* audio, int64_t row, const MixStepRow* desc,
+                             const float* hist_old, float* hist_new, void* out) {
+  if (NBg < 1 || grid_x < 1 || lds_bytes > kRsLdsMax) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mixed_step_kernel, dim3(grid_x, NBg), dim3(256), lds_bytes, q, audio, row, desc, hist_old, hist_new, out);
   return hipGetLastError();
 }
 

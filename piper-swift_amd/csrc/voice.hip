@@ -216,11 +216,18 @@ enum PlanKind : int {
   PLAN_FROM_STATS = 3,  // everything AFTER the text encoder (expansion, flow, generator), from an m_p / logs_p tensor copied in from a PLAN_PREDICT plan
 };
 
+// A row's output format on a mixed slot (include/piper_hip.h "Mixed formats"), as checked: rate 0 = the voice's own, gain never 0.
+struct RowFormat {
+  int rate = 0, enc = PIPER_HIP_ENC_S16;
+  float gain = 1.0f;
+};
+
 // One row of a batched stream on the host, the same record for an item of a group (Slot::bs_rows) and a row of a pool (StreamPool::Row):
 // the item's frames, its next frame, and whether the next step decodes a chunk of it (false: finished, dropped, or a pool row never taken).
 struct StreamRow {
   int F = 0, next = 0;
   bool active = false;
+  RowFormat fmt;  // read on a mixed slot only; set by stream_item_formats (group) or the join that took the row (pool)
 };
 
 // The output rate of a stream — single, group or pool (piper_hip_voice_stream_set_rate): 0 is the voice's own rate. A resampling stream
@@ -233,6 +240,11 @@ struct StreamRate {
   int rows = 0;               // generator rows the buffers below hold
   float* hist = nullptr;      // device [2][rows][kRsHist]
   RsStepRow* desc = nullptr;  // device [rows]
+  // Mixed formats (piper_hip_voice_stream_set_mixed): every row brings its own rate, encoding and gain (StreamRow::fmt); `rate` stays 0.
+  // The history is the one above, used by the rows that have a filter; the step's descriptor is a MixStepRow table of its own.
+  bool mixed = false;
+  int mix_rows = 0;             // generator rows `mdesc` holds
+  MixStepRow* mdesc = nullptr;  // device [mix_rows]
 };
 
 struct Slot {
@@ -312,7 +324,7 @@ struct Slot {
 void reset_stream_state(Slot& s) {
   s.st_next = -1;
   s.bs_rows.clear();
-  s.rs.rate = 0; s.rs.started = false; s.rs.parity = 0;  // (a new stream starts at the voice's own rate; the buffers stay with the plan)
+  s.rs.rate = 0; s.rs.started = false; s.rs.parity = 0; s.rs.mixed = false;  // (a new stream starts at the voice's own rate; the buffers stay with the plan)
 }
 
 // Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
@@ -783,6 +795,7 @@ void pool_close(piper_hip_voice* v, int slot) {
   if (P->pack) (void)v->ctx->pool.release(P->pack);
   if (P->rs.hist) (void)v->ctx->pool.release(P->rs.hist);
   if (P->rs.desc) (void)v->ctx->pool.release(P->rs.desc);
+  if (P->rs.mdesc) (void)v->ctx->pool.release(P->rs.mdesc);
   if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
   v->pools[slot].reset();
 }
@@ -3345,7 +3358,42 @@ void rate_range(const RsDesign& d, int64_t s, int64_t e, int64_t N, int64_t* j0,
 // ints of a slot id's page-locked descriptor staging: the kDesc* table of a step, then the RsStepRow table of a resampling one
 constexpr size_t kDescStageInts = (size_t)256 * kDescInts;
 constexpr size_t kRateStageInts = kDescStageInts + (size_t)256 * sizeof(RsStepRow) / sizeof(int);
+constexpr size_t kMixStageInts = kDescStageInts + (size_t)256 * sizeof(MixStepRow) / sizeof(int);  // (a mixed step: the MixStepRow table instead)
 static_assert(kDescStageInts * sizeof(int) % alignof(RsStepRow) == 0, "the RsStepRow table starts aligned");
+static_assert(kDescStageInts * sizeof(int) % alignof(MixStepRow) == 0 && sizeof(MixStepRow) % sizeof(int) == 0, "the MixStepRow table starts aligned");
+
+// ---- mixed formats (include/piper_hip.h "Mixed formats"): what a row's format means on the host
+int fmt_elem(const RowFormat& f) { return f.enc == PIPER_HIP_ENC_F32 ? 4 : f.enc == PIPER_HIP_ENC_S16 ? 2 : 1; }
+int64_t round_up4(int64_t bytes) { return (bytes + 3) & ~(int64_t)3; }
+
+// A caller's format → the row's record, every check of the header's table on the host; nothing is uploaded here.
+int check_format(const piper_hip_voice* v, const char* who, const piper_hip_stream_format& in, RowFormat* out) {
+  if (in.encoding < PIPER_HIP_ENC_S16 || in.encoding > PIPER_HIP_ENC_F32) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: encoding %d outside [0,3]", who, in.encoding);
+  if (!(in.gain >= 0.0f) || !std::isfinite(in.gain)) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: gain %g is negative or not finite", who, (double)in.gain);
+  if (in.encoding == PIPER_HIP_ENC_F32 && in.gain != 0.0f && in.gain != 1.0f)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "%s: an F32 row has no gain (got %g)", who, (double)in.gain);
+  RowFormat f;
+  f.enc = in.encoding;
+  f.gain = in.gain == 0.0f ? 1.0f : in.gain;
+  f.rate = (in.out_rate == 0 || in.out_rate == v->cfg.sample_rate) ? 0 : in.out_rate;
+  if (f.rate) {
+    const RsDesign* d = nullptr;
+    if (int rc = rs_design(v->cfg.sample_rate, f.rate, &d)) return rc;
+  }
+  *out = f;
+  return PIPER_HIP_OK;
+}
+
+// bytes a row of that format can deliver in one step over chunk_samples input samples, rounded up to the next row's start
+int64_t fmt_step_bytes(const piper_hip_voice* v, const RowFormat& f, int64_t chunk_samples) {
+  int64_t n = chunk_samples;
+  if (f.rate) {
+    const RsDesign* d = nullptr;
+    if (rs_design(v->cfg.sample_rate, f.rate, &d)) return 0;  // (checked when the format was supplied)
+    n = rs_step_bound(*d, chunk_samples);
+  }
+  return round_up4(n * fmt_elem(f));
+}
 
 // What one stream step decodes of an utterance of F frames whose next frame is `next`: latent frames [a, a + Fc), of whose audio the first
 // `skip` samples are dropped and the following `n` are the chunk; `end` is the stream's next frame afterwards.
@@ -3632,16 +3680,21 @@ struct StepView {
 // pcm: the chunks leave as int16 (host_pcm, gain) instead of fp32 (host_audio) — the int16 sibling of the pack kernel writes them into the
 // same device and staging buffers, half filled, and half the bytes cross the bus. law = PIPER_HIP_G711_* (with pcm): one G.711 byte per
 // sample instead, host_pcm a byte buffer — a quarter filled, a quarter of the bytes.
+// mix != nullptr: the step of a mixed slot (stream_next_batch_mixed) — every row in its own format (StreamRow::fmt) at 4-byte-aligned byte
+// offsets of host_pcm, max_samples counting BYTES; pcm, gain and law are not read. The generator part is the same.
 template <class Row>
 int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm,
-                 void* host_pcm, float gain, int law, bool* ran) {
+                 void* host_pcm, float gain, int law, bool* ran, int64_t* mix = nullptr) {
   *ran = false;
+  StreamRate& rs = *s.rs;
+  if (rs.mixed && !mix) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a mixed-format stream: use stream_next_batch_mixed", slot);
+  if (!rs.mixed && mix) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch_mixed: slot %d is not mixed (stream_set_mixed)", slot);
+  if (mix) pcm = true;  // (the output is host_pcm)
   const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
-  const size_t sample_bytes = pcm ? (law ? 1 : sizeof(int16_t)) : sizeof(float);
+  const size_t sample_bytes = mix ? 1 : pcm ? (law ? 1 : sizeof(int16_t)) : sizeof(float);  // (a mixed step's totals count bytes)
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   const int n = s.n, NBg = s.NBg, hop = v->hop;
   auto& sg = v->staging[slot];
-  StreamRate& rs = *s.rs;
   const RsDesign* rd = nullptr;
   RsFilter rf{};
   int rc;
@@ -3650,8 +3703,9 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     if (!want_out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch_pcm16: a stream with an output rate needs a buffer");
     if ((rc = voice_filter(v, rs.rate, &rd, &rf))) return rc;
   }
-  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, rd ? kRateStageInts : kDescStageInts))) return rc;
+  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, mix ? kMixStageInts : rd ? kRateStageInts : kDescStageInts))) return rc;
   RsStepRow* rrow = (RsStepRow*)(sg.h_desc + kDescStageInts);  // (only touched when rd)
+  MixStepRow* mrow = (MixStepRow*)(sg.h_desc + kDescStageInts);  // (only touched when mix: the same place)
   std::vector<int64_t> cnt(n, 0);  // samples each item delivers in this step
   int max_cnt = 0;
   // the descriptor of this step (the previous step's upload has completed: every step ends with a wait)
@@ -3664,6 +3718,8 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     for (int k = 0; k < kDescInts; k++) e[k] = 0;
     e[kDescSrc] = r < n ? r : 0;
     if (rd) rrow[r] = RsStepRow{0, 0, 0, 0, 0, 0};
+    if (mix) mrow[r] = MixStepRow{};
+    if (mix && r < n) mix[r] = round_up4(total);  // (a row that delivers nothing: where the next delivering row starts)
     if (r >= n || !s.rows[r].active) continue;
     const Window w = win[r] = window_of(s.rows[r].F, s.rows[r].next, s.chunk, s.halo, hop);
     e[kDescA] = w.a;
@@ -3679,16 +3735,38 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
       cnt[r] = j1 - j0;
       max_cnt = std::max(max_cnt, (int)(j1 - j0));
     }
-    total += cnt[r];
+    if (mix) {  // the row's own design, count, byte offset and descriptor (the filter table was uploaded when the format was supplied)
+      const RowFormat& fm = s.rows[r].fmt;
+      MixStepRow m{};
+      m.s = (int64_t)s.rows[r].next * hop;
+      m.skip = w.skip; m.n_in = w.n; m.count = w.n;
+      m.elem = fmt_elem(fm);
+      m.law = m.elem == 1 ? fm.enc : 0;
+      m.gain = fm.gain;
+      if (fm.rate) {
+        const RsDesign* fd = nullptr;
+        RsFilter ff{};
+        if ((rc = voice_filter(v, fm.rate, &fd, &ff))) return rc;
+        int64_t j0, j1;
+        rate_range(*fd, m.s, (int64_t)w.end * hop, (int64_t)s.rows[r].F * hop, &j0, &j1);
+        m.j0 = j0; m.count = (int)(j1 - j0);
+        m.taps = ff.taps; m.L = ff.L; m.M = ff.M; m.P = ff.P;
+      }
+      cnt[r] = m.count;
+      if (m.count > 0) total = round_up4(total);  // (a row that delivers nothing owns no byte, pad included)
+      m.off = mix[r];
+      mrow[r] = m;
+    }
+    total += mix ? cnt[r] * mrow[r].elem : cnt[r];  // (a mixed step's total counts bytes)
     Fmax = std::max(Fmax, w.Fc);
   }
   for (int i = 0; i < n; i++) n_samples[i] = 0;
   if (Fmax == 0) return PIPER_HIP_OK;  // end of the group / an idle pool
   if (want_out && max_samples < total)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
-  if (rd ? (size_t)total * sizeof(int16_t) > s.pack_cap * sizeof(float) : (size_t)total > s.pack_cap)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld %s", (long long)max_samples, (long long)total, mix ? "bytes" : "samples");
+  if (mix ? (size_t)total > s.pack_cap * sizeof(float) : rd ? (size_t)total * sizeof(int16_t) > s.pack_cap * sizeof(float) : (size_t)total > s.pack_cap)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.pack_cap);
-  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, rd ? ((size_t)total + 1) / 2 : (size_t)total, kAudioMinCap))) return rc;
+  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, mix ? ((size_t)total + 3) / 4 : rd ? ((size_t)total + 1) / 2 : (size_t)total, kAudioMinCap))) return rc;
   // generator-only plan of the step's longest window at the stream's batch size (rows past their end have length 0): a pool and a group
   // of the same size use the same plans
   Slot* gs = nullptr;
@@ -3711,7 +3789,15 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (e == hipSuccess) {
     const int px = (int)std::min<int64_t>(ceil_div((int64_t)s.chunk * hop, 1024), 64);
-    if (rd) {
+    if (mix) {
+      int gx;
+      size_t lds;
+      mix_step_plan(mrow, NBg, px, &gx, &lds);
+      e = hipMemcpyAsync(rs.mdesc, mrow, (size_t)NBg * sizeof(MixStepRow), hipMemcpyHostToDevice, q);
+      if (e == hipSuccess)
+        e = launch_mixed_step(q, NBg, gx, lds, gs->audio, gs->n_samples, rs.mdesc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
+                              rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, s.pack);
+    } else if (rd) {
       e = hipMemcpyAsync(rs.desc, rrow, (size_t)NBg * sizeof(RsStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
         e = launch_resample_step(q, NBg, max_cnt, gs->audio, gs->n_samples, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
@@ -3731,7 +3817,7 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   *ran = true;
   if (want_out) memcpy(pcm ? host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
   rs.started = true;
-  if (rd) rs.parity ^= 1;
+  if (rd || mix) rs.parity ^= 1;  // (a mixed step: whichever rows had a filter)
   for (int i = 0; i < n; i++) {
     n_samples[i] = cnt[i];
     if (!win[i].n) continue;
@@ -3743,11 +3829,11 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
 
 // stream_next_batch on a pool slot: the latents are the row stores, ready when the adopts of the joins since the last step have run
 int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm,
-              float gain, int law) {
+              float gain, int law, int64_t* mix) {
   const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, P.pack_bytes / sizeof(float),
                                        nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), &P.rs, P.spk_rows, v->cfg.up_initial};
   bool ran = false;
-  const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran);
+  const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran, mix);
   if (rc || !ran) return rc;  // (an idle pool: joins since the last step stay pending)
   // the step's wait covers the adopts its stream waited for: their events can be recorded again
   P.ev_free.insert(P.ev_free.end(), P.ev_pending.begin(), P.ev_pending.end());
@@ -3791,9 +3877,9 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
 namespace {
 // stream_next_batch; pcm / host_pcm / gain / law as for batched_step. A group's latents are the front plan's z, ready when its ev1 fires.
 int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm, float gain,
-               int law) {
+               int law, int64_t* mix = nullptr) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law);
+  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, mix);
   Slot* sp = slot_plan(v, slot);
   if (!sp || sp->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   Slot& s = *sp;
@@ -3801,7 +3887,7 @@ int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samp
   const StepView<StreamRow> view{s.bs_rows.data(), n, group_batch(n), s.st_chunk, s.st_halo, s.bs_desc, s.bs_pack, s.bs_pack_cap,
                                  s.z_out, s.F, nullptr, &s.set.ev1, 1, &s.rs, s.spk_bias ? s.spk_bias + v->spk_pre_off : nullptr, v->spk.Ctot};
   bool ran = false;
-  return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran);
+  return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran, mix);
 }
 }  // namespace
 
@@ -3858,11 +3944,15 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
   return PIPER_HIP_OK;
 }
 
-PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
-                                               int* items_out, int64_t* samples_out) {
+namespace {
+// stream_pool_join; fmts != nullptr: stream_pool_join_formats — one format per joining item of a mixed pool (nullptr there: the default)
+int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot, const piper_hip_stream_format* fmts,
+              bool with_formats, int* items_out, int64_t* samples_out) {
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
   if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
+  if (with_formats && !P->rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join_formats: the pool on slot %d is not mixed (stream_set_mixed)", slot);
+  if (with_formats && !fmts) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join_formats: null formats");
   if (work_slot < 0 || work_slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "work slot %d out of range [0,%d)", work_slot, kMaxSlots);
   if (work_slot == slot) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join: the work slot is the pool's slot %d", slot);
   if (slot_pool(v, work_slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join: work slot %d holds a streaming pool", work_slot);
@@ -3872,6 +3962,30 @@ PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, con
   const RsDesign* rate_d = nullptr;  // samples_out counts what the pool delivers
   if (P->rs.rate)
     if (int rc0 = rs_design(v->cfg.sample_rate, P->rs.rate, &rate_d)) return rc0;
+  // a mixed pool: the joining items' formats, checked on the host, their filter tables uploaded here (never inside a step), and a packed
+  // buffer that holds a step of the rows as they will stand (no step is in flight: every step ends with a wait)
+  std::vector<RowFormat> jf(P->rs.mixed ? n : 0);
+  if (with_formats)
+    for (int i = 0; i < n; i++)
+      if (int rc0 = check_format(v, "stream_pool_join_formats", fmts[i], &jf[i])) return rc0;
+  if (P->rs.mixed) {
+    PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+    int64_t bytes = 0;
+    for (const auto& r : P->rows) bytes += r.active ? fmt_step_bytes(v, r.fmt, (int64_t)P->chunk * v->hop) : 0;
+    for (int i = 0; i < n; i++) {
+      RsFilter ff{};
+      if (jf[i].rate)
+        if (int rc0 = voice_filter(v, jf[i].rate, nullptr, &ff)) return rc0;
+      bytes += fmt_step_bytes(v, jf[i], (int64_t)P->chunk * v->hop);
+    }
+    if ((size_t)bytes > P->pack_bytes) {
+      void* p = nullptr;
+      if (int rc0 = v->ctx->pool.alloc((size_t)bytes, &p)) return rc0;
+      if (P->pack) (void)v->ctx->pool.release(P->pack);
+      P->pack = (float*)p;
+      P->pack_bytes = (size_t)bytes;
+    }
+  }
   // encoder (+ predictor) inputs of the join on the work slot's plan, then encoder + flow on that plan's stream
   int rc = piper_hip_voice_prepare_batch(v, utts, n, work_slot);
   if (rc < 0) return rc;
@@ -3936,11 +4050,25 @@ PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, con
     r.F = w.h_F[i];
     r.next = 0;
     r.active = true;
+    r.fmt = P->rs.mixed ? jf[i] : RowFormat();
     if (items_out) items_out[i] = take[i];
-    if (samples_out) samples_out[i] = rate_d ? rs_count(*rate_d, (int64_t)w.h_F[i] * v->hop) : (int64_t)w.h_F[i] * v->hop;
+    const RsDesign* item_d = rate_d;
+    if (r.fmt.rate) (void)rs_design(v->cfg.sample_rate, r.fmt.rate, &item_d);  // (checked above)
+    if (samples_out) samples_out[i] = item_d ? rs_count(*item_d, (int64_t)w.h_F[i] * v->hop) : (int64_t)w.h_F[i] * v->hop;
   }
   P->rs.started = true;  // the pool's output rate is fixed from its first join on
   return PIPER_HIP_OK;
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
+                                               int* items_out, int64_t* samples_out) {
+  return pool_join(v, slot, utts, n, work_slot, nullptr, false, items_out, samples_out);
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_join_formats(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
+                                                       const piper_hip_stream_format* fmts, int* items_out, int64_t* samples_out) {
+  return pool_join(v, slot, utts, n, work_slot, fmts, true, items_out, samples_out);
 }
 
 PH_EXPORT int piper_hip_voice_stream_pool_free_rows(const piper_hip_voice* v, int slot) {
@@ -4110,12 +4238,15 @@ int stream_ref(piper_hip_voice* v, int slot, const char* who, StreamRef* r) {
   }
   PH_FAIL(PIPER_HIP_ERR_ARG, "%s: slot %d has no stream in progress", who, slot);
 }
+int rate_buffers(piper_hip_voice* v, const StreamRef& r);
+int pack_buffer(piper_hip_voice* v, const StreamRef& r, size_t pack_bytes);
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int32_t out_rate) {
   StreamRef r;
   int rc = stream_ref(v, slot, "stream_set_rate", &r);
   if (rc) return rc;
+  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d is mixed: every row has its own rate", slot);
   if (r.rs->started)
     PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d has %s: the rate is set before", slot, r.pool ? "stepped or been joined" : "stepped");
   if (out_rate == v->cfg.sample_rate) {  // not a filter: the steps are the un-resampled ones
@@ -4127,9 +4258,20 @@ PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int3
   RsFilter rf{};
   if ((rc = voice_filter(v, out_rate, &rd, &rf))) return rc;
   // the history and the descriptor of the stream's rows, and a packed-output buffer that holds a step at this rate
-  const size_t hist_bytes = (size_t)2 * r.rows * kRsHist * sizeof(float), desc_bytes = (size_t)r.rows * sizeof(RsStepRow);
   const size_t pack_bytes = (size_t)r.items * (size_t)rs_step_bound(*rd, r.chunk_samples) * sizeof(int16_t);
+  if ((rc = rate_buffers(v, r))) return rc;
+  if ((rc = pack_buffer(v, r, pack_bytes))) return rc;
+  r.rs->parity = 0;
+  r.rs->rate = out_rate;
+  return PIPER_HIP_OK;
+}
+
+namespace {
+// The per-row history [2][rows][kRsHist] and the RsStepRow table of the stream's generator rows (kept when they are large enough already).
+int rate_buffers(piper_hip_voice* v, const StreamRef& r) {
+  const size_t hist_bytes = (size_t)2 * r.rows * kRsHist * sizeof(float), desc_bytes = (size_t)r.rows * sizeof(RsStepRow);
   void* p = nullptr;
+  int rc;
   if (r.rs->rows < r.rows) {
     if (r.pool) {
       if (r.rs->hist) (void)v->ctx->pool.release(r.rs->hist);
@@ -4148,6 +4290,13 @@ PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int3
     }
     r.rs->rows = r.rows;
   }
+  return PIPER_HIP_OK;
+}
+
+// A packed-output buffer of at least pack_bytes for the stream (no step is in flight: every step ends with a wait).
+int pack_buffer(piper_hip_voice* v, const StreamRef& r, size_t pack_bytes) {
+  void* p = nullptr;
+  int rc;
   if (r.pool && r.pool->pack_bytes < pack_bytes) {
     if ((rc = v->ctx->pool.alloc(pack_bytes, &p))) return rc;
     if (r.pool->pack) (void)v->ctx->pool.release(r.pool->pack);  // (no step has run on this pool)
@@ -4164,22 +4313,124 @@ PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int3
     s.bs_pack = (float*)p;
     s.bs_pack_cap = floats;
   }
-  r.rs->parity = 0;
-  r.rs->rate = out_rate;
   return PIPER_HIP_OK;
 }
+
+// the StreamRow of item / row i of the batched stream r refers to
+StreamRow& ref_row(const StreamRef& r, int i) { return r.pool ? (StreamRow&)r.pool->rows[i] : r.plan->bs_rows[i]; }
+
+// stream_ref for the mixed entry points: a batched stream (group or pool) that stream_set_mixed has marked
+int mixed_ref(piper_hip_voice* v, int slot, const char* who, StreamRef* r) {
+  if (int rc = stream_ref(v, slot, who, r)) return rc;
+  if (!r->rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: slot %d is not mixed (stream_set_mixed)", who, slot);
+  return PIPER_HIP_OK;
+}
+}  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot) {
   StreamRef r;
   const int rc = stream_ref(v, slot, "stream_rate", &r);
   if (rc) return rc;
+  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_rate: slot %d is mixed: every row has its own rate (stream_item_format)", slot);
   return r.rs->rate ? r.rs->rate : v->cfg.sample_rate;
+}
+
+// ---- mixed formats (include/piper_hip.h "Mixed formats")
+
+PH_EXPORT int piper_hip_voice_stream_set_mixed(piper_hip_voice* v, int slot) {
+  StreamRef r;
+  int rc = stream_ref(v, slot, "stream_set_mixed", &r);
+  if (rc) return rc;
+  if (!r.pool && r.plan->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d holds a single stream (stream_set_rate and a law per step serve it)", slot);
+  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d is mixed already", slot);
+  if (r.rs->rate) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has the output rate %d set", slot, r.rs->rate);
+  if (r.rs->started)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has %s", slot, r.pool ? "stepped or been joined" : "stepped");
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  if ((rc = rate_buffers(v, r))) return rc;
+  if (r.rs->mix_rows < r.rows) {
+    void* p = nullptr;
+    const size_t bytes = (size_t)r.rows * sizeof(MixStepRow);
+    if (r.pool) {
+      if (r.rs->mdesc) (void)v->ctx->pool.release(r.rs->mdesc);
+      r.rs->mdesc = nullptr; r.rs->mix_rows = 0;
+      if ((rc = v->ctx->pool.alloc(bytes, &p))) return rc;
+    } else {  // (a plan keeps what an earlier, smaller stream allocated until it is released)
+      r.rs->mix_rows = 0;
+      if ((rc = plan_alloc(v, *r.plan, bytes, &p))) return rc;
+    }
+    r.rs->mdesc = (MixStepRow*)p;
+    r.rs->mix_rows = r.rows;
+  }
+  for (int i = 0; i < r.items; i++) ref_row(r, i).fmt = RowFormat();  // (s16 at the voice's rate: the buffer of the begin / open holds it)
+  r.rs->parity = 0;
+  r.rs->mixed = true;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_item_formats(piper_hip_voice* v, int slot, const piper_hip_stream_format* fmts, int n) {
+  StreamRef r;
+  int rc = mixed_ref(v, slot, "stream_item_formats", &r);
+  if (rc) return rc;
+  if (r.pool) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: slot %d holds a pool: the join brings the formats (stream_pool_join_formats)", slot);
+  if (!fmts || n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: %d formats", fmts ? n : 0);
+  if (r.rs->started) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: slot %d has stepped: a row keeps its format", slot);
+  std::vector<RowFormat> f(r.items);
+  for (int i = 0; i < r.items; i++)
+    if ((rc = check_format(v, "stream_item_formats", fmts[std::min(i, n - 1)], &f[i]))) return rc;
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  int64_t bytes = 0;
+  for (int i = 0; i < r.items; i++) {
+    RsFilter ff{};
+    if (f[i].rate && (rc = voice_filter(v, f[i].rate, nullptr, &ff))) return rc;
+    bytes += fmt_step_bytes(v, f[i], r.chunk_samples);
+  }
+  if ((rc = pack_buffer(v, r, (size_t)bytes))) return rc;
+  for (int i = 0; i < r.items; i++) ref_row(r, i).fmt = f[i];
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_next_batch_mixed(piper_hip_voice* v, int slot, void* host, int64_t max_bytes, int64_t* n_samples,
+                                                      int64_t* byte_off) {
+  if (!v || !n_samples || !byte_off) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  StreamRef r;
+  const int rc = mixed_ref(v, slot, "stream_next_batch_mixed", &r);
+  if (rc) return rc;
+  if (!host) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch_mixed: a mixed step needs a buffer");
+  return batch_step(v, slot, nullptr, max_bytes, n_samples, true, host, 1.0f, 0, byte_off);
+}
+
+PH_EXPORT int64_t piper_hip_voice_stream_step_capacity_bytes(piper_hip_voice* v, int slot) {
+  StreamRef r;
+  const int rc = mixed_ref(v, slot, "stream_step_capacity_bytes", &r);
+  if (rc) return rc;
+  int64_t bytes = 0;
+  for (int i = 0; i < r.items; i++) {
+    const StreamRow& row = ref_row(r, i);
+    if (row.active) bytes += fmt_step_bytes(v, row.fmt, r.chunk_samples);
+  }
+  return bytes;
+}
+
+PH_EXPORT int piper_hip_voice_stream_item_format(piper_hip_voice* v, int slot, int item, piper_hip_stream_format* out) {
+  StreamRef r;
+  const int rc = mixed_ref(v, slot, "stream_item_format", &r);
+  if (rc) return rc;
+  if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: null output");
+  if (item < 0 || item >= r.items) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: item %d outside [0,%d)", item, r.items);
+  const StreamRow& row = ref_row(r, item);
+  if (r.pool && !row.active) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: row %d of the pool on slot %d is free", item, slot);
+  out->out_rate = row.fmt.rate;
+  out->encoding = row.fmt.enc;
+  out->gain = row.fmt.gain;
+  return PIPER_HIP_OK;
 }
 
 PH_EXPORT int64_t piper_hip_voice_stream_step_capacity(piper_hip_voice* v, int slot) {
   StreamRef r;
   int rc = stream_ref(v, slot, "stream_step_capacity", &r);
   if (rc) return rc;
+  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_step_capacity: slot %d is mixed: stream_step_capacity_bytes", slot);
   if (!r.rs->rate) return (int64_t)r.items * r.chunk_samples;
   const RsDesign* rd = nullptr;
   if ((rc = rs_design(v->cfg.sample_rate, r.rs->rate, &rd))) return rc;

@@ -157,6 +157,49 @@ def _law(law):
         law.lower() if isinstance(law, str) else law, law if isinstance(law, int) else -1)
 
 
+# encodings of a mixed stream's rows (include/piper_hip.h "Mixed formats")
+ENC_S16, ENC_MULAW, ENC_ALAW, ENC_F32 = 0, 1, 2, 3
+_ENCODINGS = {"s16": ENC_S16, "pcm16": ENC_S16, "mulaw": ENC_MULAW, "ulaw": ENC_MULAW, "pcmu": ENC_MULAW, "alaw": ENC_ALAW, "pcma": ENC_ALAW,
+              "f32": ENC_F32, "float32": ENC_F32}
+ENC_DTYPES = {ENC_S16: np.int16, ENC_MULAW: np.uint8, ENC_ALAW: np.uint8, ENC_F32: np.float32}
+
+
+class StreamFormat(C.Structure):
+    """piper_hip_stream_format: the output format of one row of a mixed stream. out_rate 0 = the voice's own rate; gain 0 = 1.0."""
+    _fields_ = [("out_rate", C.c_int32), ("encoding", C.c_int32), ("gain", C.c_float)]
+
+    @property
+    def dtype(self):
+        return ENC_DTYPES[int(self.encoding)]
+
+    def __repr__(self):
+        return "StreamFormat(rate=%d, encoding=%d, gain=%g)" % (self.out_rate, self.encoding, self.gain)
+
+
+def stream_format(rate=None, encoding="s16", gain=1.0):
+    """A StreamFormat from rate= (None or 0: the voice's own), encoding= "s16" | "mulaw" | "alaw" | "f32" (or ENC_*), gain=. What can be
+    told here without a voice is: an unknown encoding, a negative or non-finite gain and a gain other than 1 on an f32 row raise
+    InvalidArgument, a rate outside the output-rate list UnsupportedOp — the statuses the library gives for the same formats."""
+    enc = _ENCODINGS.get(encoding.lower()) if isinstance(encoding, str) else (int(encoding) if int(encoding) in ENC_DTYPES else None)
+    if enc is None:
+        raise InvalidArgument("stream_format: encoding %r (s16, mulaw, alaw or f32)" % (encoding,))
+    gain = float(gain)
+    if not (gain >= 0.0) or gain == float("inf"):
+        raise InvalidArgument("stream_format: gain %r is negative or not finite" % gain)
+    if enc == ENC_F32 and gain not in (0.0, 1.0):
+        raise InvalidArgument("stream_format: an f32 row has no gain (got %r)" % gain)
+    rate = int(rate or 0)
+    if rate and rate not in (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000):
+        raise UnsupportedOp("stream_format: output rate %d (supported: 8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000)" % rate)
+    return StreamFormat(rate, enc, gain)
+
+
+def _formats(formats):
+    """[StreamFormat | dict | None] → a ctypes array (None: the default format)"""
+    fs = [f if isinstance(f, StreamFormat) else stream_format(**(f or {})) for f in formats]
+    return (StreamFormat * max(len(fs), 1))(*fs)
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("avg_us", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -307,6 +350,13 @@ _PROTOS = {
                                                   C.POINTER(C.c_int64)]),
     "piper_hip_voice_stream_next_g711": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
     "piper_hip_voice_stream_next_batch_g711": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_set_mixed": (C.c_int, [c_vp, C.c_int]),
+    "piper_hip_voice_stream_item_formats": (C.c_int, [c_vp, C.c_int, C.POINTER(StreamFormat), C.c_int]),
+    "piper_hip_voice_stream_pool_join_formats": (C.c_int, [c_vp, C.c_int, C.POINTER(Utterance), C.c_int, C.c_int, C.POINTER(StreamFormat),
+                                                           C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_next_batch_mixed": (C.c_int, [c_vp, C.c_int, c_vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_step_capacity_bytes": (C.c_int64, [c_vp, C.c_int]),
+    "piper_hip_voice_stream_item_format": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(StreamFormat)]),
     "piper_hip_voice_tap": (C.c_int, [c_vp, C.c_int, C.c_char_p, c_f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "piper_hip_voice_last_gpu_ms": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_double)]),
     "piper_hip_voice_slot_stream": (c_vp, [c_vp, C.c_int]),
@@ -1070,7 +1120,16 @@ class StreamPool:
         self.rt, self.slot, self.capacity, self.chunk_frames, self.work_slot = rt, slot, capacity, chunk_frames, work_slot
         self._buf = np.empty(max(capacity * chunk_frames * rt.cfg.hop, 1), np.float32)
         self._got = (C.c_int64 * capacity)()
+        self._off = (C.c_int64 * capacity)()
         self.rate = None
+        self.mixed = False
+        self._fmt = {}  # (mixed) row → the StreamFormat of the session in it
+
+    def set_mixed(self):
+        """Every row picks its rate, encoding and gain (piper_hip_voice_stream_set_mixed): before the first join. join(formats=[...]) then
+        brings the formats and step_mixed() is the pool's step."""
+        self.rt.stream_set_mixed(self.slot)
+        self.mixed = True
 
     def set_rate(self, rate):
         """Deliver at `rate` Hz (piper_hip_voice_stream_set_rate): before the first join. step() then returns int16 chunks only."""
@@ -1081,9 +1140,11 @@ class StreamPool:
         self.rate = int(rate)
         self._buf = np.empty((self.rt.stream_step_capacity(self.slot) + 1) // 2, np.float32)
 
-    def join(self, utterances, noiseScale=0.667):
+    def join(self, utterances, noiseScale=0.667, formats=None):
         """utterances as for synthesize_stream_batch: (phonemeIDs, durations-or-None, noise-or-None[, dict]). Returns [(item, samples)]:
-        the row each session took and the samples it will deliver in all. Active from the next step()."""
+        the row each session took and the samples it will deliver in all. Active from the next step().
+        formats (a mixed pool): one StreamFormat (or dict of stream_format's arguments, or None) per utterance
+        (piper_hip_voice_stream_pool_join_formats); without it the sessions join in the default format."""
         rt, n = self.rt, len(utterances)
         arr = (Utterance * max(n, 1))()
         keep = []
@@ -1094,9 +1155,37 @@ class StreamPool:
             keep.append(k)
         items = (C.c_int * max(n, 1))()
         samples = (C.c_int64 * max(n, 1))()
-        _check(rt.lib.piper_hip_voice_stream_pool_join(rt.voice, self.slot, arr, n, self.work_slot, items, samples))
+        if formats is not None:
+            if len(formats) != n:
+                raise InvalidArgument("join: %d formats for %d utterances" % (len(formats), n))
+            fa = _formats(formats)
+            _check(rt.lib.piper_hip_voice_stream_pool_join_formats(rt.voice, self.slot, arr, n, self.work_slot, fa, items, samples))
+        else:
+            _check(rt.lib.piper_hip_voice_stream_pool_join(rt.voice, self.slot, arr, n, self.work_slot, items, samples))
         rt._keep.pop(self.work_slot, None)  # the inputs were copied before the call returned
+        if self.mixed:
+            for i in range(n):
+                self._fmt[int(items[i])] = rt.stream_item_format(self.slot, int(items[i]))
+            need = rt.stream_step_capacity_bytes(self.slot)
+            if need > self._buf.nbytes:
+                self._buf = np.empty((need + 3) // 4, np.float32)
         return [(int(items[i]), int(samples[i])) for i in range(n)]
+
+    def step_mixed(self, raw=False):
+        """The step of a mixed pool (piper_hip_voice_stream_next_batch_mixed): a list with one numpy array per row, of the row's dtype
+        (int16, uint8 or float32) and empty where the row delivered nothing; all empty when the pool is idle.
+        raw=True: (n_samples, byte_off, bytes) as the library returned them instead."""
+        rt = self.rt
+        buf = self._buf.view(np.uint8)
+        _check(rt.lib.piper_hip_voice_stream_next_batch_mixed(rt.voice, self.slot, buf.ctypes.data_as(c_vp), buf.size, self._got, self._off))
+        counts, offs = [int(x) for x in self._got], [int(x) for x in self._off]
+        out, total = [], 0
+        for r in range(self.capacity):
+            dt = np.dtype(self._fmt[r].dtype if r in self._fmt else np.int16)
+            out.append(buf[offs[r]:offs[r] + counts[r] * dt.itemsize].view(dt).copy() if counts[r] else np.empty(0, dt))
+            if counts[r]:
+                total = offs[r] + counts[r] * dt.itemsize
+        return (counts, offs, buf[:total].copy()) if raw else out
 
     def step(self, pcm=False, gain=1.0, normalize=False, encoding=None):
         """{item: chunk} of every active session; an empty dict when the pool is idle. pcm=True: int16 chunks converted on the device
@@ -1305,6 +1394,23 @@ class HipRuntime:
         """The int16 samples one step of the stream on `slot` can deliver at its current rate."""
         return _count(self.lib.piper_hip_voice_stream_step_capacity(self.voice, slot))
 
+    def stream_set_mixed(self, slot):
+        """Marks the batched stream on `slot` mixed (piper_hip_voice_stream_set_mixed): every row picks its rate, encoding and gain."""
+        _check(self.lib.piper_hip_voice_stream_set_mixed(self.voice, slot))
+
+    def stream_item_formats(self, slot, formats):
+        """The formats of a mixed group's items (piper_hip_voice_stream_item_formats): items past the list take the last entry."""
+        _check(self.lib.piper_hip_voice_stream_item_formats(self.voice, slot, _formats(formats), len(formats)))
+
+    def stream_item_format(self, slot, item):
+        out = StreamFormat()
+        _check(self.lib.piper_hip_voice_stream_item_format(self.voice, slot, int(item), C.byref(out)))
+        return out
+
+    def stream_step_capacity_bytes(self, slot):
+        """The bytes one step of the mixed stream on `slot` can deliver with the rows' current formats."""
+        return _count(self.lib.piper_hip_voice_stream_step_capacity_bytes(self.voice, slot))
+
     def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None,
                           encoding=None):
         """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
@@ -1336,12 +1442,15 @@ class HipRuntime:
                 return
             yield buf[:got.value].copy()
 
-    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None, encoding=None):
+    def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None, encoding=None,
+                                formats=None):
         """Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
         arrays — the next chunk of every item, empty once the item is finished or dropped (stream_drop). pcm=True: int16 chunks converted on
         the device (piper_hip_voice_stream_next_batch_pcm16), scaled by `gain`. rate: int16 chunks at that output rate (implies pcm).
-        encoding "mulaw" / "alaw": uint8 chunks of G.711 bytes instead of int16 (piper_hip_voice_stream_next_batch_g711)."""
+        encoding "mulaw" / "alaw": uint8 chunks of G.711 bytes instead of int16 (piper_hip_voice_stream_next_batch_g711).
+        formats: a mixed group — one StreamFormat (or dict, or None) per item, items past the list take the last; every step's arrays then
+        have their item's dtype (piper_hip_voice_stream_next_batch_mixed). pcm, gain, rate and encoding must be left alone with it."""
         n = len(utterances)
         arr = (Utterance * max(n, 1))()
         keep = []
@@ -1353,6 +1462,19 @@ class HipRuntime:
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
+        if formats is not None:
+            if pcm or rate or encoding is not None or gain != 1.0:
+                raise InvalidArgument("synthesize_stream_batch: formats= carries the rate, encoding and gain of every item")
+            self.stream_set_mixed(slot)
+            self.stream_item_formats(slot, formats)
+            dts = [np.dtype(self.stream_item_format(slot, i).dtype) for i in range(n)]
+            raw = np.empty(max(self.stream_step_capacity_bytes(slot), 4), np.uint8)
+            got, off = (C.c_int64 * n)(), (C.c_int64 * n)()
+            while True:
+                _check(self.lib.piper_hip_voice_stream_next_batch_mixed(self.voice, slot, raw.ctypes.data_as(c_vp), raw.size, got, off))
+                if not any(int(x) for x in got):
+                    return
+                yield [raw[int(off[i]):int(off[i]) + int(got[i]) * dts[i].itemsize].view(dts[i]).copy() for i in range(n)]
         law = None if encoding is None else _law(encoding)
         sample = np.uint8 if law is not None else np.int16
         buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), sample if pcm or rate or law is not None else np.float32)
@@ -1382,9 +1504,10 @@ class HipRuntime:
         """The client of item `item` of the batched stream on `slot` went away: later steps skip it."""
         _check(self.lib.piper_hip_voice_stream_drop(self.voice, slot, int(item)))
 
-    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None, rate=None):
+    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None, rate=None, mixed=False):
         """A streaming pool (piper_hip_voice_stream_pool_open) of `capacity` rows on `slot`: sessions join and leave while it runs.
-        work_slot: the slot id whose plan runs the joins' encoder + flow (default: the next slot id)."""
+        work_slot: the slot id whose plan runs the joins' encoder + flow (default: the next slot id). mixed=True: every joining session
+        brings its own format (join(formats=[...]), step_mixed())."""
         if work_slot is None:
             work_slot = slot + 1 if slot + 1 < 16 else slot - 1
         _check(self.lib.piper_hip_voice_stream_pool_open(self.voice, slot, int(capacity), int(chunkFrames)))
@@ -1392,6 +1515,8 @@ class HipRuntime:
         pool = StreamPool(self, slot, int(capacity), int(chunkFrames), int(work_slot))
         if rate:
             pool.set_rate(rate)
+        if mixed:
+            pool.set_mixed()
         return pool
 
     def prepare_batch(self, slot, utterances, noiseScale=0.667):

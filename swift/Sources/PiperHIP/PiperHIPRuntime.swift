@@ -478,6 +478,74 @@ public final class PiperHIPRuntime {
         return out
     }
 
+    // ---- mixed formats (include/piper_hip.h "Mixed formats"): every row of a group or pool in its own rate, encoding and gain
+
+    /// Marks the batched stream on `slot` mixed (piper_hip_voice_stream_set_mixed): right after streamBeginBatch / streamPoolOpen.
+    public func streamSetMixed(slot: Int32) throws {
+        try HIPBackend.check(piper_hip_voice_stream_set_mixed(voice, slot))
+    }
+
+    /// The formats of a mixed group's items, before its first step (piper_hip_voice_stream_item_formats); items past the list take the last.
+    public func streamItemFormats(slot: Int32, formats: [piper_hip_stream_format]) throws {
+        try HIPBackend.check(piper_hip_voice_stream_item_formats(voice, slot, formats, Int32(formats.count)))
+    }
+
+    /// The format of item / row `item` of a mixed slot as the library holds it (piper_hip_voice_stream_item_format).
+    public func streamItemFormat(slot: Int32, item: Int32) throws -> piper_hip_stream_format {
+        var f = piper_hip_stream_format(out_rate: 0, encoding: 0, gain: 0)
+        try HIPBackend.check(piper_hip_voice_stream_item_format(voice, slot, item, &f))
+        return f
+    }
+
+    /// The bytes one step of the mixed slot can deliver with the rows' current formats (piper_hip_voice_stream_step_capacity_bytes).
+    public func streamStepCapacityBytes(slot: Int32) throws -> Int {
+        let n = piper_hip_voice_stream_step_capacity_bytes(voice, slot)
+        if n < 0 { try HIPBackend.check(Int32(n)) }
+        return Int(n)
+    }
+
+    /// streamPoolJoin on a mixed pool with one format per utterance (piper_hip_voice_stream_pool_join_formats).
+    public func streamPoolJoin(slot: Int32, workSlot: Int32, phonemeIDs: [[Int64]], durations: [[Int32]?], noiseScale: Float,
+                               formats: [piper_hip_stream_format], seeds: [UInt32]? = nil) throws -> [(item: Int32, samples: Int64)] {
+        let n = phonemeIDs.count
+        precondition(formats.count == n, "one format per utterance")
+        let ids = phonemeIDs.map { ContiguousArray($0) }
+        let durs = durations.map { $0.map { ContiguousArray($0) } }
+        var utts = [piper_hip_utterance]()
+        var items = [Int32](repeating: 0, count: n)
+        var samples = [Int64](repeating: 0, count: n)
+        try withExtendedLifetime((ids, durs)) {
+            for i in 0..<n {
+                let ip = ids[i].withUnsafeBufferPointer { $0.baseAddress }       // storage kept alive by withExtendedLifetime
+                let dp = durs[i]?.withUnsafeBufferPointer { $0.baseAddress }
+                utts.append(piper_hip_utterance(phoneme_ids: ip, t: Int32(ids[i].count), durations: dp, noise: nil, noise_scale: noiseScale,
+                                                noise_mode: Int32(PIPER_HIP_NOISE_DEVICE), seed: seeds?[i] ?? 1234, length_scale: 1.0,
+                                                noise_w: 0.8, dp_noise: nil))
+            }
+            try HIPBackend.check(piper_hip_voice_stream_pool_join_formats(voice, slot, &utts, Int32(n), workSlot, formats, &items, &samples))
+        }
+        return (0..<n).map { (items[$0], samples[$0]) }
+    }
+
+    /// The step of a mixed group or pool (piper_hip_voice_stream_next_batch_mixed): per delivering item / row its chunk as raw bytes —
+    /// int16 or float32 in host order, or G.711 bytes, by the row's format (streamItemFormat). Empty = end / idle.
+    public func streamNextBatchMixed(slot: Int32, rows: Int32) throws -> [Int32: [UInt8]] {
+        var buf = [UInt8](repeating: 0, count: max(try streamStepCapacityBytes(slot: slot), 4))
+        var counts = [Int64](repeating: 0, count: Int(rows))
+        var offs = [Int64](repeating: 0, count: Int(rows))
+        // the element sizes are read before the step: a pool row whose session delivers its last chunk is free afterwards
+        let elems: [Int] = (0..<rows).map { r in
+            guard let f = try? streamItemFormat(slot: slot, item: r) else { return 0 }  // a free pool row
+            return f.encoding == PIPER_HIP_ENC_F32 ? 4 : f.encoding == PIPER_HIP_ENC_S16 ? 2 : 1
+        }
+        try HIPBackend.check(piper_hip_voice_stream_next_batch_mixed(voice, slot, &buf, Int64(buf.count), &counts, &offs))
+        var out = [Int32: [UInt8]]()
+        for (item, c) in counts.enumerated() where c > 0 {
+            out[Int32(item)] = Array(buf[Int(offs[item])..<Int(offs[item]) + Int(c) * elems[item]])
+        }
+        return out
+    }
+
     /// A mono G.711 WAV (format tag 7 / 6, fact chunk) from bytes that are companded already (piper_hip_wav_write_g711).
     public func writeWav(g711 bytes: [UInt8], law: Int32, rate: Int32, to path: String) throws {
         try HIPBackend.check(piper_hip_wav_write_g711(path, law, bytes, bytes.count, rate))
