@@ -502,7 +502,7 @@ int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item);
  * A refused join leaves nothing joined and the pool intact: more items than free rows = PIPER_HIP_ERR_SHAPE; work_slot == slot, or a
  * work_slot that itself holds a pool = PIPER_HIP_ERR_ARG. After a join, piper_hip_voice_durations / piper_hip_voice_prepared_samples on
  * work_slot report that join's items (it is a prepared slot). A join with supplied durations does not wait for its encoder + flow; with
- * durations == NULL it keeps prepare_batch's host round trip for the predicted frame counts. */
+ * durations == NULL it keeps prepare_batch's host round trip for the predicted frame counts (stream_pool_join_bounded, below, does not). */
 /* An empty pool of `capacity` rows (1 ≤ capacity ≤ 256) on `slot`; every step decodes chunk_frames frames per active row. */
 int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int capacity, int chunk_frames);
 /* Encoder + flow (and the predictor where durations == NULL) for n new utterances on `work_slot` (any other slot id; what it held is
@@ -793,6 +793,50 @@ int piper_hip_onnx_build_speaker_blob(const piper_hip_onnx* m, const piper_hip_v
                                       float* host_blob, size_t n_floats);
 int piper_hip_voice_check_json_speakers(const piper_hip_voice_config* cfg, const piper_hip_speaker_config* scfg,
                                         const piper_hip_piper_json_info* info);
+
+/* ---- Streaming pool: joins with predicted durations that never wait (DESIGN.md §4 "Bounded pool joins") ----
+ * stream_pool_join with durations == NULL stalls the host until the predicted frame counts are back. The bounded join takes the route of
+ * prepare_batch_bounded instead: the caller bounds the frames per item, the counts stay on the device, and the join enqueues its work and
+ * returns.
+ *   Accepted utterances  exactly what prepare_batch_bounded accepts: durations == NULL, noise == NULL (noise_mode DEVICE draws it on the
+ *                        device), the same max_frames range; every refusal of that call carries over with its status.
+ *   Refused joins        as stream_pool_join(_formats): more items than free rows = PIPER_HIP_ERR_SHAPE; work_slot == slot, a work slot
+ *                        holding a pool, fmts on a pool that is not mixed, a format the pool refuses = PIPER_HIP_ERR_ARG (or the format's
+ *                        own status). A refused join leaves nothing joined and the pool intact.
+ *   Host waits           none: no stream or event synchronisation, no blocking copy. Two waits of the existing code remain: the one a join
+ *                        makes for the adopts still queued before it REGROWS a row store, and whatever prepare_batch_bounded does to
+ *                        recycle the work slot (its stream is waited for before its staging is rewritten; a bucket seen for the first
+ *                        time builds its plans).
+ *   Work slot            runs the bounded encoder, predictor, generate_path and flow. Every row store of the join is sized for the work
+ *                        plan's frame bucket (the bucket of max_frames), which is the row's stride. Afterwards the work slot is a bounded
+ *                        slot whose lengths are still on the device; it may be reused at once. piper_hip_voice_durations(work_slot) and
+ *                        prepared_samples answer with the true values once the join has resolved, unless the slot was prepared again.
+ *   Row state            a row taken by a bounded join is taken from the join on (it counts against stream_pool_free_rows) but has no
+ *                        known length until it is resolved.
+ *   Resolution           at the start of the next stream_next_batch* call of any flavour, or in stream_pool_item_samples: the host waits
+ *                        for the join's event — which the step's stream would have waited for anyway — and reads the frame count the
+ *                        device reported. F ≤ max_frames: the row is an ordinary active row with that F; windows, emit rule per format
+ *                        and history are those of any other row. F > max_frames: the row is free again and marked failed until it is
+ *                        taken again; it never delivers, the other items of the join are unaffected and the step returns OK.
+ *   Order                a bounded join is active from the next step on, like any join: the step waits for the joins made before it,
+ *                        so the pool stays deterministic.
+ *   stream_drop          on a row that is still pending frees it; the next join may take it (its adopt runs behind the pending one).
+ *   Closing              stream_pool_close, voice_destroy and a prepare* / stream_pool_open on the slot wait for joins in flight first.
+ *   Rates and formats    on a pool with an output rate the counts are J(N) at that rate. On a mixed pool the joining items' filter
+ *                        tables are uploaded in the join, never inside a step, the packed buffer is regrown from the rows' shares of a
+ *                        step as in stream_pool_join_formats, and stream_step_capacity_bytes counts a pending row's share. */
+/* stream_pool_join for utterances whose durations are PREDICTED, without the host round trip: the caller bounds the frames per item as in
+ * prepare_batch_bounded. Nothing in this call waits for the GPU. fmts: NULL, or n formats on a mixed pool (as stream_pool_join_formats;
+ * non-NULL on a pool that is not mixed is PIPER_HIP_ERR_ARG). items_out[n] = the rows taken. There is no samples_out: the counts are
+ * not known yet (piper_hip_voice_stream_pool_item_samples). */
+int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
+                                             int max_frames, const piper_hip_stream_format* fmts, int* items_out);
+/* Total samples row `item`'s occupant will deliver, at the row's rate (J(N) on a rated or mixed row). Waits for the join that filled the
+ * row if its front is still running. PIPER_HIP_ERR_SHAPE (message naming wanted and allowed frames) when the predictor exceeded the
+ * join's max_frames: that item delivers nothing and its row is free. PIPER_HIP_ERR_ARG for a row that never held an item or is out of range. */
+int piper_hip_voice_stream_pool_item_samples(piper_hip_voice* v, int slot, int item, int64_t* samples);
+/* Joins of this pool whose front has not finished yet (hipEventQuery; never waits). ≥ 0, or a negative status. */
+int piper_hip_voice_stream_pool_joins_pending(piper_hip_voice* v, int slot);
 
 /* Debug taps ⇔ GraphExecutor.execute(maxNodeIndex:) returning intermediates (GraphExecutor.swift:75-152):
  * copy a named intermediate of the slot's last run to host. Names: "enc_out" [H,T], "m_p" [inter,T],

@@ -343,8 +343,21 @@ struct StreamPool {
     float* z = nullptr;     // [inter][stride] row store (context pool), kept while the pool lives, regrown for a longer utterance
     size_t cap = 0;         // floats
     int stride = 0;         // bucket_f(F) of the item in the row
+    // stream_pool_join_bounded: the row is taken (active) but its F is still on the device until pool_resolve has read the adopt's report
+    bool pending = false;
+    bool held = false;      // F is the length of the row's latest occupant (stream_pool_item_samples)
+    int over_want = 0, over_cap = 0;  // over_want > 0: the latest bounded occupant wanted more frames than its join allowed and never ran
   };
   std::vector<Row> rows;
+  struct BoundedJoin {  // a bounded join that pool_resolve has not seen yet: its event (one of ev_pending) and the work slot's prepare
+    hipEvent_t ev;
+    int work_slot;
+    const Slot* plan;
+    uint64_t prepared;  // the plan's last_use at the join: the same value later = the work slot has not been prepared again
+  };
+  std::vector<BoundedJoin> bounded;
+  int32_t* h_rep = nullptr;       // page-locked [capacity][2]: {wanted frames, allowed frames} per row, written by stream_adopt_bounded_kernel
+  int32_t* d_rep = nullptr;       // its device mapping
   PoolRowRef* d_rows = nullptr;   // device: [NBg] row table, then the [capacity] PoolJoinEnt table of the latest join (one upload per join)
   int* d_desc = nullptr;          // device: [NBg][kDescInts] descriptor of the step (one upload per step)
   float* pack = nullptr;         // device: the packed chunks of one step, capacity · chunk · hop floats
@@ -797,6 +810,7 @@ void pool_close(piper_hip_voice* v, int slot) {
   if (P->rs.desc) (void)v->ctx->pool.release(P->rs.desc);
   if (P->rs.mdesc) (void)v->ctx->pool.release(P->rs.mdesc);
   if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
+  if (P->h_rep) (void)hipHostFree(P->h_rep);  // (the adopts that write it have run: waited for above)
   v->pools[slot].reset();
 }
 
@@ -3639,6 +3653,40 @@ __global__ __launch_bounds__(256) void stream_adopt_kernel(const float* __restri
   }
 }
 
+// stream_adopt_kernel for a bounded join (stream_pool_join_bounded): the item's frame count is not a table entry but the work plan's
+// device lensF[src], which dp_paths_kernel decided on the same stream just before the flow. Entry j's F is the join's bound (cap); the
+// kernel copies min(lensF, cap, stride, Fw) columns — every index below comes from that clamped length — and zeroes the rest of the row up
+// to its stride. The same layout rules hold (Fw % 16 == stride % 16 == 0, 16-byte-aligned bases), so every access is an aligned float4
+// inside its row. One thread per entry reports {wanted frames, cap} of the row to rep [capacity][2] (page-locked host memory, its device
+// mapping): want[src] is dp_paths_kernel's count BEFORE clamping, the number the host decides "fits / over the bound" by.
+__global__ __launch_bounds__(256) void stream_adopt_bounded_kernel(const float* __restrict__ z, int Fw, const int* __restrict__ lensF,
+                                                                  const int32_t* __restrict__ want, const PoolJoinEnt* __restrict__ tab,
+                                                                  const PoolRowRef* __restrict__ rows, int I, const float* __restrict__ spk_src,
+                                                                  int64_t spk_stride, float* __restrict__ spk_rows, int U, int32_t* __restrict__ rep) {
+  const PoolJoinEnt e = tab[blockIdx.y];
+  const PoolRowRef rr = rows[e.row];
+  if (spk_rows && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < U; i += 256) spk_rows[(int64_t)e.row * U + i] = spk_src[(int64_t)e.src * spk_stride + i];
+  const int stride = (int)rr.stride, q4 = stride >> 2;
+  const int cap = max(min(min(e.F, stride), Fw), 0);
+  const int F = min(max(lensF[e.src], 0), cap);
+  if (blockIdx.x == 0 && threadIdx.x == 0) *(int2*)(rep + 2 * (int64_t)e.row) = make_int2(want[e.src], e.F);
+  const int total = I * q4;
+  const float* zi = z + (int64_t)e.src * I * Fw;
+  float* out = (float*)rr.z;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int c = i / q4, j = (i - c * q4) * 4;
+    float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (j < F) {  // (j + 3 < Fw: j is a multiple of 4 below F ≤ Fw, and Fw % 4 == 0)
+      t = *(const float4*)(zi + (int64_t)c * Fw + j);
+      if (j + 1 >= F) t.y = 0.0f;
+      if (j + 2 >= F) t.z = 0.0f;
+      if (j + 3 >= F) t.w = 0.0f;
+    }
+    *(float4*)(out + (int64_t)c * stride + j) = t;
+  }
+}
+
 int pool_free_rows(const StreamPool& P) {
   int k = 0;
   for (const auto& r : P.rows) k += r.active ? 0 : 1;
@@ -3827,9 +3875,44 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   return PIPER_HIP_OK;
 }
 
+// The bounded joins since the last resolve (stream_pool_join_bounded) become ordinary rows: the host waits for each join's event — its
+// adopt has run, and dp_paths_kernel before it — and reads what the adopt reported per row. F ≤ cap: the row is active with that F from
+// here on. F > cap: the row is free again and remembers both numbers for stream_pool_item_samples; the join's other rows are not
+// touched. A work slot that still holds the join's prepare learns its lengths and durations here (piper_hip_voice_durations).
+int pool_resolve(piper_hip_voice* v, StreamPool& P) {
+  if (P.bounded.empty()) return PIPER_HIP_OK;
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  for (const auto& j : P.bounded) PH_HIP(hipEventSynchronize(j.ev), PIPER_HIP_ERR_LAUNCH);
+  for (const auto& j : P.bounded) {
+    Slot* w = v->attached[j.work_slot];
+    if (w && w == j.plan && w->last_use == j.prepared && w->bounded_pending) (void)bounded_finish(v, j.work_slot, *w);  // (an item over its bound is the row's error)
+  }
+  P.bounded.clear();
+  int bad = -1;
+  for (int r = 0; r < P.capacity; r++) {
+    auto& row = P.rows[r];
+    if (!row.pending) continue;
+    row.pending = false;
+    const int want = P.h_rep[2 * r], cap = P.h_rep[2 * r + 1];
+    if (want >= 1 && want <= cap && cap <= row.stride) {
+      row.F = want;
+      row.next = 0;
+      row.held = true;
+    } else {
+      row.active = false;
+      row.over_want = want > cap ? want : 0;
+      row.over_cap = cap;
+      if (want <= cap) bad = r;
+    }
+  }
+  if (bad >= 0) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream pool: the device reported no frame count for row %d (the row is free)", bad);
+  return PIPER_HIP_OK;
+}
+
 // stream_next_batch on a pool slot: the latents are the row stores, ready when the adopts of the joins since the last step have run
 int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm,
               float gain, int law, int64_t* mix) {
+  if (int rc0 = pool_resolve(v, P)) return rc0;
   const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, P.pack_bytes / sizeof(float),
                                        nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), &P.rs, P.spk_rows, v->cfg.up_initial};
   bool ran = false;
@@ -3900,6 +3983,7 @@ PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item
   if (StreamPool* P = slot_pool(v, slot)) {  // the session in that row leaves: the row is free for the next join
     if (item < 0 || item >= P->capacity) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, P->capacity);
     P->rows[item].active = false;
+    P->rows[item].pending = false;  // (a bounded join still in flight: ev_pending keeps its adopt away from the row's next occupant)
     return PIPER_HIP_OK;
   }
   Slot* sp = slot_plan(v, slot);
@@ -3945,9 +4029,26 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
 }
 
 namespace {
-// stream_pool_join; fmts != nullptr: stream_pool_join_formats — one format per joining item of a mixed pool (nullptr there: the default)
+// launch_front for a join that must not wait: a plan whose front has no graph yet runs the front steps eagerly — that run is the join's
+// answer — and captures the graph behind it, as launch_plan does for a plan's first run (the capture enqueues nothing).
+int launch_front_async(Slot& s) {
+  if (s.front_exec) return launch_front(s);
+  std::vector<int> front;
+  for (int i = 0; i < (int)s.steps.size(); i++) {
+    if (s.steps[i].name.compare(0, 4, "dec.") == 0) break;
+    if (s.steps[i].kind == Step::LAUNCH) front.push_back(i);
+  }
+  int rc = run_steps(s, front, s.set.stream);
+  if (rc) return rc;
+  PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);
+  return capture_graph(s.set.stream, [&](hipStream_t q) { return run_steps(s, front, q); }, &s.front_graph, &s.front_exec, "stream");
+}
+
+// stream_pool_join; fmts != nullptr: stream_pool_join_formats — one format per joining item of a mixed pool (nullptr there: the default).
+// bound > 0: stream_pool_join_bounded — the work slot is prepared by prepare_batch_bounded, the frame counts stay on the device and the
+// rows are pending until pool_resolve; nothing below waits for the GPU then, but for the two waits the header names.
 int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot, const piper_hip_stream_format* fmts,
-              bool with_formats, int* items_out, int64_t* samples_out) {
+              bool with_formats, int* items_out, int64_t* samples_out, int bound = 0) {
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
   if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
@@ -3987,10 +4088,28 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
     }
   }
   // encoder (+ predictor) inputs of the join on the work slot's plan, then encoder + flow on that plan's stream
-  int rc = piper_hip_voice_prepare_batch(v, utts, n, work_slot);
+  int rc = bound ? piper_hip_voice_prepare_batch_bounded(v, utts, n, work_slot, bound) : piper_hip_voice_prepare_batch(v, utts, n, work_slot);
   if (rc < 0) return rc;
   Slot& w = *v->attached[work_slot];
   const int I = v->cfg.inter;
+  // a bounded join: every row has the work plan's frame bucket for its stride (w.h_F holds that bucket until the lengths are known)
+  auto item_stride = [&](int i) { return bound ? w.F : bucket_f(w.h_F[i]); };
+  int32_t* want_rep = nullptr;  // bounded: the device mapping of the work slot's report (dp_paths_kernel's counts before clamping)
+  if (bound) {
+    if (!P->h_rep) {
+      PH_HIP(hipHostMalloc((void**)&P->h_rep, (size_t)P->capacity * 2 * sizeof(int32_t)), PIPER_HIP_ERR_ALLOC);
+      if (hipHostGetDevicePointer((void**)&P->d_rep, P->h_rep, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipHostFree(P->h_rep);
+        P->h_rep = nullptr;
+        PH_FAIL(PIPER_HIP_ERR_UNAVAILABLE, "stream_pool_join_bounded: page-locked memory has no device mapping on this system");
+      }
+    }
+    if (hipHostGetDevicePointer((void**)&want_rep, v->staging[work_slot].h_res, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      PH_FAIL(PIPER_HIP_ERR_UNAVAILABLE, "stream_pool_join_bounded: page-locked memory has no device mapping on this system");
+    }
+  }
   // rows, lowest free index first, and their stores. Nothing of the pool changes before everything that can fail has succeeded.
   std::vector<int> take;
   for (int r = 0; r < P->capacity && (int)take.size() < n; r++)
@@ -4001,7 +4120,7 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   int stride_max = 0;
   for (int i = 0; i < n; i++) {
     auto& r = P->rows[take[i]];
-    const int stride = bucket_f(w.h_F[i]);
+    const int stride = item_stride(i);
     stride_max = std::max(stride_max, stride);
     const size_t need = (size_t)I * stride;
     if (r.cap >= need) continue;
@@ -4016,7 +4135,7 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   }
   hipEvent_t ev = nullptr;
   if ((rc = pool_event(*P, &ev))) return rc;
-  if ((rc = launch_front(w))) { P->ev_free.push_back(ev); return rc; }
+  if ((rc = bound ? launch_front_async(w) : launch_front(w))) { P->ev_free.push_back(ev); return rc; }
   // The adopt runs on the work plan's own stream: behind its front graph, and ahead of everything that waits for that stream before the
   // plan's arena is reused (prepare on the same plan, detach, evict_idle_plans). It first waits for the adopts of earlier joins since the
   // last step: they read the tables this join uploads anew, and one of them may write a row this join takes again.
@@ -4028,8 +4147,8 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
     tab[r].stride = r < P->capacity ? P->rows[r].stride : 0;
   }
   for (int i = 0; i < n; i++) {
-    tab[take[i]].stride = bucket_f(w.h_F[i]);
-    jt[i] = PoolJoinEnt{i, take[i], w.h_F[i], 0};
+    tab[take[i]].stride = item_stride(i);
+    jt[i] = PoolJoinEnt{i, take[i], bound ? w.bounded_cap : w.h_F[i], 0};
   }
   hipError_t e = hipSuccess;
   for (hipEvent_t pe : P->ev_pending)
@@ -4037,19 +4156,29 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   if (e == hipSuccess) e = hipMemcpyAsync(P->d_rows, sg.h_desc, (tab_ints + join_ints) * sizeof(int), hipMemcpyHostToDevice, q);
   if (e == hipSuccess) {
     const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (stride_max / 4), 256), 64);
-    hipLaunchKernelGGL(stream_adopt_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I,
-                       w.spk_bias ? w.spk_bias + v->spk_pre_off : nullptr, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr, v->cfg.up_initial);
+    const float* spk_src = w.spk_bias ? w.spk_bias + v->spk_pre_off : nullptr;
+    if (bound)
+      hipLaunchKernelGGL(stream_adopt_bounded_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, w.lensF, want_rep,
+                         (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I, spk_src, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr,
+                         v->cfg.up_initial, P->d_rep);
+    else
+      hipLaunchKernelGGL(stream_adopt_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I,
+                         spk_src, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr, v->cfg.up_initial);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipEventRecord(ev, q);
   if (e != hipSuccess) { P->ev_free.push_back(ev); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_pool_join: %s", hipGetErrorString(e)); }
   P->ev_pending.push_back(ev);
+  if (bound) P->bounded.push_back(StreamPool::BoundedJoin{ev, work_slot, &w, w.last_use});
   for (int i = 0; i < n; i++) {  // active from the next step on
     auto& r = P->rows[take[i]];
-    r.stride = bucket_f(w.h_F[i]);
-    r.F = w.h_F[i];
+    r.stride = item_stride(i);
+    r.F = bound ? 0 : w.h_F[i];  // (bounded: pool_resolve brings it before any step reads it)
     r.next = 0;
     r.active = true;
+    r.pending = bound != 0;
+    r.held = !bound;
+    r.over_want = r.over_cap = 0;
     r.fmt = P->rs.mixed ? jf[i] : RowFormat();
     if (items_out) items_out[i] = take[i];
     const RsDesign* item_d = rate_d;
@@ -4069,6 +4198,58 @@ PH_EXPORT int piper_hip_voice_stream_pool_join(piper_hip_voice* v, int slot, con
 PH_EXPORT int piper_hip_voice_stream_pool_join_formats(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
                                                        const piper_hip_stream_format* fmts, int* items_out, int64_t* samples_out) {
   return pool_join(v, slot, utts, n, work_slot, fmts, true, items_out, samples_out);
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
+                                                       int max_frames, const piper_hip_stream_format* fmts, int* items_out) {
+  if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  // prepare_batch_bounded's own refusals, before anything of the pool is looked at or regrown (it repeats them)
+  if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join_bounded: %d items outside [1,256]", n);
+  if (max_frames < 1 || (int64_t)max_frames * std::max(v->hop, 1) > 0x3fffffff / 64)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join_bounded: max_frames %d out of range", max_frames);
+  if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0): supply durations (stream_pool_join)");
+  for (int b = 0; b < n; b++) {
+    if (int rc = check_item(utts[b], b)) return rc;
+    if (utts[b].durations || utts[b].noise)
+      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: stream_pool_join_bounded predicts the durations and cannot take a host noise tensor (its shape "
+                                 "depends on them): pass durations = noise = NULL (noise_mode DEVICE draws it on the device)", b);
+  }
+  return pool_join(v, slot, utts, n, work_slot, fmts, fmts != nullptr, items_out, nullptr, max_frames);
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_item_samples(piper_hip_voice* v, int slot, int item, int64_t* samples) {
+  if (!v || !samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  StreamPool* P = slot_pool(v, slot);
+  if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
+  if (item < 0 || item >= P->capacity) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_item_samples: item %d outside [0,%d)", item, P->capacity);
+  if (P->rows[item].pending)
+    if (int rc = pool_resolve(v, *P)) return rc;
+  const auto& r = P->rows[item];
+  if (r.over_want > 0)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream pool row %d: the predictor wants %d frames, the join allowed %d — the item delivers nothing and its row is "
+                                 "free: join it again with a larger bound", item, r.over_want, r.over_cap);
+  if (!r.held) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_item_samples: row %d of the pool on slot %d holds no item whose length is known", item, slot);
+  const int64_t N = (int64_t)r.F * v->hop;
+  const int rate = P->rs.mixed ? r.fmt.rate : P->rs.rate;
+  const RsDesign* d = nullptr;
+  if (rate)
+    if (int rc = rs_design(v->cfg.sample_rate, rate, &d)) return rc;
+  *samples = d ? rs_count(*d, N) : N;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_pool_joins_pending(piper_hip_voice* v, int slot) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  const StreamPool* P = slot_pool(v, slot);
+  if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  int k = 0;
+  for (hipEvent_t ev : P->ev_pending) {  // one per join since the last step that ran
+    const hipError_t e = hipEventQuery(ev);
+    if (e == hipErrorNotReady) { k++; (void)hipGetLastError(); continue; }  // (not an error: nothing for the next launch check to find)
+    if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_pool_joins_pending: %s", hipGetErrorString(e));
+  }
+  return k;
 }
 
 PH_EXPORT int piper_hip_voice_stream_pool_free_rows(const piper_hip_voice* v, int slot) {

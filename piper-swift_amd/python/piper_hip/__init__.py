@@ -375,6 +375,10 @@ _PROTOS = {
     "piper_hip_onnx_infer_config_speakers": (C.c_int, [c_vp, C.POINTER(VoiceConfig)]),
     "piper_hip_onnx_build_speaker_blob": (C.c_int, [c_vp, C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig), c_f32p, C.c_size_t]),
     "piper_hip_voice_check_json_speakers": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(SpeakerConfig), C.POINTER(PiperJsonInfo)]),
+    "piper_hip_voice_stream_pool_join_bounded": (C.c_int, [c_vp, C.c_int, C.POINTER(Utterance), C.c_int, C.c_int, C.c_int, C.POINTER(StreamFormat),
+                                                           C.POINTER(C.c_int)]),
+    "piper_hip_voice_stream_pool_item_samples": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_stream_pool_joins_pending": (C.c_int, [c_vp, C.c_int]),
 }
 
 _lib = None
@@ -1170,6 +1174,46 @@ class StreamPool:
             if need > self._buf.nbytes:
                 self._buf = np.empty((need + 3) // 4, np.float32)
         return [(int(items[i]), int(samples[i])) for i in range(n)]
+
+    def join_bounded(self, utterances, max_frames, noiseScale=0.667, formats=None):
+        """join() for utterances whose durations are predicted, without the host round trip (piper_hip_voice_stream_pool_join_bounded):
+        at most max_frames frames per item, durations and noise None (the dict's noise_mode="device" draws the noise on the device).
+        Nothing waits for the GPU. Returns [item, ...], the rows taken; item_samples(item) tells what each will deliver once its length
+        is known and raises ShapeMismatch for an item the predictor made longer than max_frames (that row is free again)."""
+        rt, n = self.rt, len(utterances)
+        arr = (Utterance * max(n, 1))()
+        keep = []
+        for i, item in enumerate(utterances):
+            ids, dur, noise = item[:3]
+            u, k = rt._utt(ids, dur, noise, noiseScale, **(item[3] if len(item) > 3 else {}))
+            arr[i] = u
+            keep.append(k)
+        items = (C.c_int * max(n, 1))()
+        fa = None
+        if formats is not None:
+            if len(formats) != n:
+                raise InvalidArgument("join_bounded: %d formats for %d utterances" % (len(formats), n))
+            fa = _formats(formats)
+        _check(rt.lib.piper_hip_voice_stream_pool_join_bounded(rt.voice, self.slot, arr, n, self.work_slot, int(max_frames), fa, items))
+        rt._keep.pop(self.work_slot, None)  # the inputs were copied before the call returned
+        if self.mixed:
+            for i in range(n):
+                self._fmt[int(items[i])] = rt.stream_item_format(self.slot, int(items[i]))
+            need = rt.stream_step_capacity_bytes(self.slot)
+            if need > self._buf.nbytes:
+                self._buf = np.empty((need + 3) // 4, np.float32)
+        return [int(items[i]) for i in range(n)]
+
+    def item_samples(self, item):
+        """Total samples the occupant of row `item` will deliver, at the row's rate (piper_hip_voice_stream_pool_item_samples); waits for
+        the join that filled the row if it is still running. ShapeMismatch: a bounded join's item over its max_frames."""
+        got = C.c_int64()
+        _check(self.rt.lib.piper_hip_voice_stream_pool_item_samples(self.rt.voice, self.slot, int(item), C.byref(got)))
+        return int(got.value)
+
+    def joins_pending(self):
+        """Joins whose encoder + flow have not finished yet (piper_hip_voice_stream_pool_joins_pending); never waits."""
+        return _count(self.rt.lib.piper_hip_voice_stream_pool_joins_pending(self.rt.voice, self.slot))
 
     def step_mixed(self, raw=False):
         """The step of a mixed pool (piper_hip_voice_stream_next_batch_mixed): a list with one numpy array per row, of the row's dtype

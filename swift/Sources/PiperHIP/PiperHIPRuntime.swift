@@ -527,6 +527,49 @@ public final class PiperHIPRuntime {
         return (0..<n).map { (items[$0], samples[$0]) }
     }
 
+    // ---- bounded pool joins (include/piper_hip.h "Streaming pool: joins with predicted durations that never wait")
+
+    /// streamPoolJoin for utterances whose durations are predicted, without the host round trip
+    /// (piper_hip_voice_stream_pool_join_bounded): at most `maxFrames` frames per item, nothing waits for the GPU. `formats`: one per
+    /// utterance on a mixed pool, nil otherwise. Returns the rows taken; streamPoolItemSamples tells what each will deliver.
+    public func streamPoolJoinBounded(slot: Int32, workSlot: Int32, phonemeIDs: [[Int64]], maxFrames: Int32, noiseScale: Float,
+                                      formats: [piper_hip_stream_format]? = nil, seeds: [UInt32]? = nil) throws -> [Int32] {
+        let n = phonemeIDs.count
+        precondition(formats == nil || formats!.count == n, "one format per utterance")
+        let ids = phonemeIDs.map { ContiguousArray($0) }
+        var utts = [piper_hip_utterance]()
+        var items = [Int32](repeating: 0, count: n)
+        try withExtendedLifetime(ids) {
+            for i in 0..<n {
+                let ip = ids[i].withUnsafeBufferPointer { $0.baseAddress }       // storage kept alive by withExtendedLifetime
+                utts.append(piper_hip_utterance(phoneme_ids: ip, t: Int32(ids[i].count), durations: nil, noise: nil, noise_scale: noiseScale,
+                                                noise_mode: Int32(PIPER_HIP_NOISE_DEVICE), seed: seeds?[i] ?? 1234, length_scale: 1.0,
+                                                noise_w: 0.8, dp_noise: nil))
+            }
+            if let f = formats {
+                try HIPBackend.check(piper_hip_voice_stream_pool_join_bounded(voice, slot, &utts, Int32(n), workSlot, maxFrames, f, &items))
+            } else {
+                try HIPBackend.check(piper_hip_voice_stream_pool_join_bounded(voice, slot, &utts, Int32(n), workSlot, maxFrames, nil, &items))
+            }
+        }
+        return items
+    }
+
+    /// Total samples the occupant of row `item` will deliver, at the row's rate (piper_hip_voice_stream_pool_item_samples); waits for the
+    /// join that filled the row if it is still running. Throws the shape error for a bounded item the predictor made longer than its bound.
+    public func streamPoolItemSamples(slot: Int32, item: Int32) throws -> Int64 {
+        var n: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_stream_pool_item_samples(voice, slot, item, &n))
+        return n
+    }
+
+    /// Joins of the pool whose encoder + flow have not finished yet (piper_hip_voice_stream_pool_joins_pending); never waits.
+    public func streamPoolJoinsPending(slot: Int32) throws -> Int32 {
+        let rc = piper_hip_voice_stream_pool_joins_pending(voice, slot)
+        if rc < 0 { try HIPBackend.check(rc) }
+        return rc
+    }
+
     /// The step of a mixed group or pool (piper_hip_voice_stream_next_batch_mixed): per delivering item / row its chunk as raw bytes —
     /// int16 or float32 in host order, or G.711 bytes, by the row's format (streamItemFormat). Empty = end / idle.
     public func streamNextBatchMixed(slot: Int32, rows: Int32) throws -> [Int32: [UInt8]] {
