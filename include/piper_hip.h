@@ -486,7 +486,9 @@ int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio,
  * stream_next_batch writes the chunks of the active items back to back in item order into host_audio (at most n · chunk_frames · hop
  * samples); n_samples[i] (n entries) = samples of item i in this step, 0 once item i is finished or dropped. All zero = end of the
  * group. stream_next on a slot holding a group of n > 1 returns PIPER_HIP_ERR_ARG.
- * stream_drop: the client of item `item` went away; later steps skip it. */
+ * stream_drop: the client of item `item` went away; later steps skip it (its row has length 0). Until the frame where its stream would have
+ * ended, the item's window still counts when a step picks its plan, so the other items receive, bit for bit, the samples they would have
+ * received without the drop; once only dropped items are left the group has ended. */
 int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames);
 int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples);
 int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item);
@@ -853,8 +855,10 @@ int piper_hip_voice_stream_pool_joins_pending(piper_hip_voice* v, int slot);
  *   "dec.s{u}.mean_lrelu"    fp32 per-conv schedule: lrelu(MRF mean) as the next stage reads it (slope 0.1; last stage 0.01);
  *   "dec.s{u}.mean_act"      bf16, u < n_ups − 1: the bf16 image of lrelu(MRF mean, 0.1) as raw bits, [C_u / 8][len][8] bf16 words
  *                            (4 floats per position and channel group);
- *   "dec.mean"               bf16: the last stage's fp32 MRF mean.
+ *   "dec.mean"               bf16: the last stage's fp32 MRF mean;
+ *   "audio"                  the waveform rows [1][F·hop] of the plan (every plan kind), items at F_b·hop samples.
  * Step selector. Name grammar:   ["predict:"] <tensor> ["@" <step name>]   |   ["predict:"] "@steps"
+ *                                ["window:"] <tensor>                       |   "window:@steps"
  *   "<tensor>@<step name>"   the tensor as it stands right after the named step of the slot's schedule (step names: what
  *                            piper_hip_voice_profile reports). The call waits for the slot's stream, runs the schedule's launches eagerly
  *                            from the first step through the named one (the inputs staged by prepare are still in place), copies out as
@@ -869,6 +873,14 @@ int piper_hip_voice_stream_pool_joins_pending(piper_hip_voice* v, int slot);
  *   "predict:<tensor>[@<step>]"  addresses the cached encoder + duration-predictor plan of the slot's bucket T and batch size (the plan a
  *                            prepare without durations ran) with the slot's true lengths; PIPER_HIP_ERR_ARG when none is cached.
  *   "@steps"                 the schedule's launch names in order, one per line, one character code per float.
+ *   "window:<tensor>"        on a slot that holds a single stream, a group or a streaming pool: the tensor in the generator window plan of
+ *                            the slot's LATEST stream step. Items are that step's generator rows 0 … NBg − 1 (one for a single stream),
+ *                            each compacted to its window length Fc of that step; a row with Fc = 0 (finished, dropped, free, pad)
+ *                            contributes nothing, so n_floats = Σ C · Fc_r · positions per frame. "window:audio" is the window's
+ *                            waveform before the chunk is cut out of it. PIPER_HIP_ERR_ARG when no step has run on the slot since it was
+ *                            prepared or opened, when the plan has been evicted from the cache, or when another stream has run the plan
+ *                            since (its tensors are no longer this step's). "window:<tensor>@<step>" is PIPER_HIP_ERR_UNSUPPORTED, as
+ *                            above; "window:@steps" lists the window plan's launches.
  * A voice with a speaker table (piper_hip_voice_attach_speakers) adds, per batch item at a fixed length: "spk.g" [gin], the mixed speaker
  * vector, and "spk.bias" [Ctot], the item's speaker row — a plan writes the rows it computes and leaves the others 0.0: the slot's plan the
  * flow and generator rows, "predict:spk.bias" the dp.pre rows. */

@@ -227,6 +227,10 @@ struct RowFormat {
 struct StreamRow {
   int F = 0, next = 0;
   bool active = false;
+  // A group's item after stream_drop: it delivers nothing (active = false), but until the frame where its stream would have ended its window
+  // still counts when a step chooses its plan, so the other items run the plans — and receive the samples, bit for bit — that they would
+  // have without the drop. A pool's rows are never ghosts: a dropped row is free for the next join at once.
+  bool ghost = false;
   RowFormat fmt;  // read on a mixed slot only; set by stream_item_formats (group) or the join that took the row (pool)
 };
 
@@ -367,6 +371,15 @@ struct StreamPool {
   float* spk_rows = nullptr;     // device: [capacity][up_initial] conv_pre rows of the sessions in the rows (a voice with speakers; else null)
 };
 
+// What the latest stream step of a slot id ran (the "window:" selector of piper_hip_voice_tap): the generator window plan, its last_use
+// stamp of that step — another value later = someone else has run the plan since — and the window length Fc of every generator row
+// (one for a single stream; 0: a finished, dropped, free or pad row). Host bookkeeping only; plan == nullptr: no step has run.
+struct WindowRecord {
+  const Slot* plan = nullptr;
+  uint64_t stamp = 0;
+  std::vector<int> Fc;
+};
+
 }  // namespace
 
 struct piper_hip_voice {
@@ -455,6 +468,7 @@ struct piper_hip_voice {
   Slot* attached[kMaxSlots] = {};
   std::unique_ptr<StreamPool> pools[kMaxSlots];  // the streaming pool a slot id holds (then attached[slot] is null)
   Slot* attached_dp[kMaxSlots] = {};  // bounded prepare: the encoder + predictor plan this slot id holds until its next prepare / detach
+  WindowRecord windows[kMaxSlots];    // the latest stream step of each slot id (single stream, group or pool)
   uint64_t use_clock = 0;
   int hop = 1;
   // Output rates used so far: the filter of (cfg.sample_rate → rate) and its table in device memory (context pool), freed with the voice.
@@ -1029,6 +1043,7 @@ int add_conv_post(Builder& b, const std::string& name, const float* x, const flo
   s.n_samples = L;
   s.audio = b.ar.f32((size_t)b.NB * L);
   if (b.ar.rc) return b.ar.rc;
+  b.tap("audio", s.audio, 1, L, L / b.F);  // the waveform rows (a window plan: before the chunk is cut out of them)
   ConvArgs a;
   a.x = x; a.x2 = x2; a.x3 = x3;
   a.prologue = prologue;
@@ -2497,6 +2512,7 @@ void release_dp(piper_hip_voice* v, int slot) {
 }
 
 void detach(piper_hip_voice* v, int slot) {
+  v->windows[slot] = WindowRecord();  // what the slot id streamed is gone with what it held
   Slot* p = v->attached[slot];
   if (!p) return;
   if (p->set.stream) (void)hipStreamSynchronize(p->set.stream);  // its last launch may still be running / reading the inputs
@@ -2512,6 +2528,7 @@ void detach(piper_hip_voice* v, int slot) {
 // the bucket's plan is taken from the cache (or built) and attached. Then, if `evict`, idle plans beyond the cache's bounds go.
 int attach_plan(piper_hip_voice* v, int slot, PlanKind kind, int T, int F, int NB, Slot** out, bool evict = true) {
   pool_close(v, slot);  // a prepare replaces what the slot id holds, a streaming pool included
+  v->windows[slot] = WindowRecord();  // (and the record of its latest stream step)
   Slot* cur = v->attached[slot];
   if (!(cur && cur->built && cur->kind == kind && cur->T == T && cur->F == F && cur->NB == NB && cur->prec == v->precision)) {
     if (cur) detach(v, slot);
@@ -3466,6 +3483,7 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (rc) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
+  v->windows[slot] = WindowRecord{gs, gs->last_use, {Fc}};
   const int I = v->cfg.inter;
   hipError_t e = hipStreamWaitEvent(gs->set.stream, s.set.ev1, 0);
   int lens[2] = {0, Fc};
@@ -3761,6 +3779,8 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   std::vector<Window> win(n);
   int64_t total = 0;
   int Fmax = 0;
+  bool live = false;  // a row delivers in this step
+  std::vector<int> ghost_end(n, -1);
   for (int r = 0; r < NBg; r++) {
     int* e = d + (size_t)r * kDescInts;
     for (int k = 0; k < kDescInts; k++) e[k] = 0;
@@ -3768,7 +3788,13 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     if (rd) rrow[r] = RsStepRow{0, 0, 0, 0, 0, 0};
     if (mix) mrow[r] = MixStepRow{};
     if (mix && r < n) mix[r] = round_up4(total);  // (a row that delivers nothing: where the next delivering row starts)
+    if (r < n && !s.rows[r].active && s.rows[r].ghost) {  // a dropped item: length 0 in the step, its window only sizes the plan
+      const Window g = window_of(s.rows[r].F, s.rows[r].next, s.chunk, s.halo, hop);
+      Fmax = std::max(Fmax, g.Fc);
+      ghost_end[r] = g.end;
+    }
     if (r >= n || !s.rows[r].active) continue;
+    live = true;
     const Window w = win[r] = window_of(s.rows[r].F, s.rows[r].next, s.chunk, s.halo, hop);
     e[kDescA] = w.a;
     e[kDescFc] = w.Fc;
@@ -3809,7 +3835,7 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     Fmax = std::max(Fmax, w.Fc);
   }
   for (int i = 0; i < n; i++) n_samples[i] = 0;
-  if (Fmax == 0) return PIPER_HIP_OK;  // end of the group / an idle pool
+  if (!live) return PIPER_HIP_OK;  // end of the group / an idle pool (dropped items alone run no step)
   if (want_out && max_samples < total)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld %s", (long long)max_samples, (long long)total, mix ? "bytes" : "samples");
   if (mix ? (size_t)total > s.pack_cap * sizeof(float) : rd ? (size_t)total * sizeof(int16_t) > s.pack_cap * sizeof(float) : (size_t)total > s.pack_cap)
@@ -3822,6 +3848,13 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   if ((rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
+  {
+    WindowRecord& wr = v->windows[slot];
+    wr.plan = gs;
+    wr.stamp = gs->last_use;
+    wr.Fc.assign((size_t)NBg, 0);
+    for (int r = 0; r < n; r++) wr.Fc[r] = win[r].Fc;  // (a row that is not active kept the default window: Fc = 0)
+  }
   const hipStream_t q = gs->set.stream;
   const int I = v->cfg.inter, Fg = gs->F;
   hipError_t e = hipSuccess;
@@ -3868,6 +3901,10 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   if (rd || mix) rs.parity ^= 1;  // (a mixed step: whichever rows had a filter)
   for (int i = 0; i < n; i++) {
     n_samples[i] = cnt[i];
+    if (ghost_end[i] >= 0) {
+      s.rows[i].next = ghost_end[i];
+      if (ghost_end[i] >= s.rows[i].F) s.rows[i].ghost = false;
+    }
     if (!win[i].n) continue;
     s.rows[i].next = win[i].end;
     if (win[i].end >= s.rows[i].F) s.rows[i].active = false;  // last chunk delivered (a pool: the row is free for the next join)
@@ -3990,6 +4027,7 @@ PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item
   if (!sp || sp->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   const int n = (int)sp->bs_rows.size();
   if (item < 0 || item >= n) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, n);
+  if (sp->bs_rows[item].active) sp->bs_rows[item].ghost = sp->bs_rows[item].next < sp->bs_rows[item].F;
   sp->bs_rows[item].active = false;
   return PIPER_HIP_OK;
 }
@@ -4712,13 +4750,27 @@ PH_EXPORT int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utt
 PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name, float* host, size_t max_floats,
                                   size_t* n_floats) {
   if (!v || !name) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  // grammar: ["predict:"] <tensor> ["@" <step name>]   |   ["predict:"] "@steps"   |   ["window:"] <tensor>   |   "window:@steps"
+  std::string full(name);
   Slot* sp = slot_plan(v, slot);
+  const WindowRecord* win = nullptr;  // "window:": the generator plan of the slot's latest stream step, rows at that step's window lengths
+  if (full.compare(0, 7, "window:") == 0) {
+    full.erase(0, 7);
+    if (slot < 0 || slot >= kMaxSlots || (!sp && !slot_pool(v, slot))) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': slot %d holds no stream", name, slot);
+    win = &v->windows[slot];
+    if (!win->plan) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': no stream step has run on slot %d", name, slot);
+    Slot* gp = nullptr;
+    for (auto& p : v->plans)
+      if (p.get() == win->plan && p->built && p->kind == PLAN_GENERATOR) gp = p.get();
+    if (!gp) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': the window plan of slot %d's latest step has been evicted", name, slot);
+    if (gp->last_use != win->stamp || gp->NB != (int)win->Fc.size())
+      PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': the window plan of slot %d's latest step has run another step since", name, slot);
+    sp = gp;
+  }
   if (!sp) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
   const Slot& owner = *sp;  // the true lengths of the items are the slot's
-  // grammar: ["predict:"] <tensor> ["@" <step name>]   |   ["predict:"] "@steps"
-  std::string full(name);
   Slot* tp = sp;
-  if (full.compare(0, 8, "predict:") == 0) {  // the cached encoder + predictor plan of the slot's bucket T and batch size
+  if (!win && full.compare(0, 8, "predict:") == 0) {  // the cached encoder + predictor plan of the slot's bucket T and batch size
     full.erase(0, 8);
     tp = nullptr;
     for (auto& p : v->plans)
@@ -4755,7 +4807,10 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
   }
   // items back to back, each compacted to its true length: [C][len_b]
   // (unit < 0: a tensor of fixed length, the whole row for every item — the speaker taps)
-  auto item_len = [&](int b) { return (size_t)(t.unit < 0 ? t.row : t.unit == 0 ? owner.h_T[b] : owner.h_F[b] * t.unit); };
+  // (a window plan: the window lengths of the recorded step, in place of a slot's frame counts)
+  auto item_len = [&](int b) {
+    return (size_t)(t.unit < 0 ? t.row : t.unit == 0 ? (win ? 0 : owner.h_T[b]) : (win ? win->Fc[b] : owner.h_F[b]) * t.unit);
+  };
   size_t total = 0;
   for (int b = 0; b < s.NB; b++) total += (size_t)t.C * item_len(b);
   if (n_floats) *n_floats = total;
@@ -4768,7 +4823,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
       if (rc) return rc;
     }
     const hipStream_t q = s.set.stream;
-    PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);
+    if (q) PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);  // (a window plan's step ended with a wait; the plan may have given its set back)
     auto run_range = [&](int from, int to) -> int {  // eagerly, in schedule order on the plan's stream (as piper_hip_voice_profile does)
       for (int i = from; i < to; i++)
         if (s.steps[i].kind == Step::LAUNCH) {

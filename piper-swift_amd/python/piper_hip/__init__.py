@@ -1729,7 +1729,8 @@ class HipRuntime:
         """A named intermediate of the slot, items back to back at their true lengths (max_floats None: sized by the library).
         Name grammar (include/piper_hip.h): ["predict:"] <tensor> ["@" <step name>] — "front.x@enc2.ln2_qkv" is the work buffer x right
         after that step (the schedule is replayed up to it, then finished); "predict:" addresses the cached encoder + predictor plan of the
-        slot's bucket; the front.* / dp.* work buffers are only meaningful with "@". See also steps()."""
+        slot's bucket; the front.* / dp.* work buffers are only meaningful with "@". "window:<tensor>" reads the generator window plan of
+        the slot's latest stream step (single stream, group or pool), rows at that step's window lengths. See also steps()."""
         n = C.c_size_t()
         if max_floats is None:
             _check(self.lib.piper_hip_voice_tap(self.voice, slot, name.encode(), None, 0, C.byref(n)))
@@ -1739,9 +1740,10 @@ class HipRuntime:
                                             C.byref(n)))
         return out[:n.value]
 
-    def steps(self, slot, predict=False):
-        """Launch names of the slot's schedule in order (predict=True: of the cached encoder + predictor plan of its bucket)."""
-        raw = self.tap(slot, ("predict:" if predict else "") + "@steps")
+    def steps(self, slot, predict=False, window=False):
+        """Launch names of the slot's schedule in order (predict=True: of the cached encoder + predictor plan of its bucket; window=True:
+        of the generator window plan of the slot's latest stream step)."""
+        raw = self.tap(slot, ("window:" if window else "predict:" if predict else "") + "@steps")
         return bytes(raw.astype(np.uint8)).decode().split("\n")[:-1]
 
     def last_gpu_ms(self, slot):

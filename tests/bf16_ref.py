@@ -325,24 +325,45 @@ def decode_c8(raw, C):
     return (u.transpose(0, 2, 1).reshape(C, -1).astype(np.uint32) << 16).view(np.float32)
 
 
-def read_taps(rt, slot, frames):
-    """Every registered tap of a prepared and launched bf16 slot → one {name: [C, len]} per batch item (frames: true frame count per item).
-    A name the plan did not register (a tensor its schedule never materialises) is simply absent; verify_item decides whether that is allowed."""
-    cfg = rt.cfg
-    items = [{} for _ in frames]
-    for name, C, mul in tap_names(cfg):
+class TapSizeMismatch(AssertionError):
+    """A tap whose total size is not Σ C · len_b · positions per unit of the lengths the caller expects: .name, .got, .sizes."""
+
+    def __init__(self, name, got, sizes):
+        super().__init__(f"tap {name}: {got} floats, expected {sum(sizes)} = Σ {list(sizes)}")
+        self.name, self.got, self.sizes = name, got, list(sizes)
+
+
+def read_named_taps(rt, slot, names, lengths, items=None, prefix=""):
+    """The taps `names` = [(name, channels, positions per unit of length)] of a slot → one {name: [C, len]} per item (lengths: the length
+    each item is compacted to — the true frame counts of a launched slot, or, with prefix "window:", the window lengths of the slot's latest
+    stream step, 0 for a row that contributes nothing; items not asked for stay empty). The library sizes the buffer, so a tap that holds
+    more or less than Σ C · len · positions raises TapSizeMismatch instead of being cut. A name the plan did not register (a tensor its
+    schedule never materialises) is absent; every other refusal of the selector is raised. "mean_act" images are decoded (decode_c8)."""
+    want = range(len(lengths)) if items is None else items
+    out = [{} for _ in lengths]
+    for name, C, mul in names:
         packed = name.endswith("mean_act")
-        sizes = [C * f * mul // (2 if packed else 1) for f in frames]
+        sizes = [C * f * mul // (2 if packed else 1) for f in lengths]
         try:
-            raw = rt.tap(slot, name, max(sum(sizes), 1))
-        except ph.ExecutionError:
-            continue
-        assert raw.size == sum(sizes), (name, raw.size, sizes)
-        off = 0
-        for it, n in zip(items, sizes):
-            it[name] = decode_c8(raw[off:off + n], C) if packed else raw[off:off + n].reshape(C, -1).copy()
-            off += n
-    return items
+            raw = rt.tap(slot, prefix + name)
+        except ph.InvalidArgument as e:
+            if "unknown tap" in str(e):
+                continue
+            raise
+        if raw.size != sum(sizes):
+            raise TapSizeMismatch(prefix + name, raw.size, sizes)
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        for b in want:
+            part = raw[offs[b]:offs[b + 1]]
+            out[b][name] = decode_c8(part, C) if packed else part.reshape(C, -1).copy()
+    return out
+
+
+def read_taps(rt, slot, frames, items=None, prefix=""):
+    """Every registered tap of a prepared and launched bf16 slot → one {name: [C, len]} per batch item (frames: true frame count per item);
+    prefix "window:": of the generator window plan of the slot's latest stream step (frames: the rows' window lengths).
+    A name the plan did not register is simply absent; verify_item decides whether that is allowed."""
+    return read_named_taps(rt, slot, tap_names(rt.cfg), frames, items, prefix)
 
 
 def verify_slot(rt, blob, slot, frames, audio, label="", items=None, report=print):

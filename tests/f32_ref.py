@@ -23,7 +23,6 @@ import numpy as np
 
 import bf16_ref as br
 import katdata as kd
-import piper_hip as ph
 from conftest import OP_TOL
 
 SLOPE = 0.1
@@ -274,22 +273,11 @@ def tap_names(cfg):
     return names
 
 
-def read_taps(rt, slot, frames, items=None):
+def read_taps(rt, slot, frames, items=None, prefix=""):
     """Every registered tap of a prepared and launched fp32 slot → one {name: [C, len]} per batch item (frames: true frame count per item;
-    items not asked for stay empty). A name the plan did not register is absent; verify_item decides whether that is allowed."""
-    want = range(len(frames)) if items is None else items
-    out = [{} for _ in frames]
-    for name, C, mul in tap_names(rt.cfg):
-        sizes = [C * f * mul for f in frames]
-        try:
-            raw = rt.tap(slot, name, max(sum(sizes), 1))
-        except ph.ExecutionError:
-            continue
-        assert raw.size == sum(sizes), (name, raw.size, sizes)
-        offs = np.concatenate([[0], np.cumsum(sizes)])
-        for b in want:
-            out[b][name] = raw[offs[b]:offs[b + 1]].reshape(C, -1).copy()
-    return out
+    items not asked for stay empty); prefix "window:": of the generator window plan of the slot's latest stream step (frames: the rows'
+    window lengths). A name the plan did not register is absent; verify_item decides whether that is allowed."""
+    return br.read_named_taps(rt, slot, tap_names(rt.cfg), frames, items, prefix)
 
 
 def verify_slot(rt, blob, slot, frames, audio, label="", items=None, report=print):

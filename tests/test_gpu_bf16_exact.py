@@ -7,8 +7,9 @@ mean_from_rb). Per unit the run prints max|Δ|, the bound, and the share of elem
 
 A tap is compacted to each item's true length, so "zero past the true length" is checked where it matters: the reference feeds zeros there, and
 a stale image tail would show in the last `reach` columns of the consumer. The fp32 streams themselves are not zero past the true length by
-design (nobody reads them there). Window plans of the streaming path are not attached to a slot id, so `piper_hip_voice_tap` cannot reach
-them without a new selector: streams keep their SNR checks (test_gpu_voice.py, test_gpu_stream_batch.py)."""
+design (nobody reads them there). Window plans of the streaming path are not attached to a slot id: tests/test_gpu_stream_windows.py
+reaches them through the tap's "window:" selector and runs this chained check on every step of a stream; the streams keep their SNR checks
+next to it (test_gpu_voice.py, test_gpu_stream_batch.py)."""
 import os
 import subprocess
 import sys

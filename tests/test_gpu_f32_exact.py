@@ -8,8 +8,9 @@ of tanh's saturation (f32_ref.Waveform). Per unit the run prints max|Δ|, the bo
 
 A tap is compacted to each item's true length; the reference feeds zeros past it. The fp32 streams are NOT zeroed there on the device, so
 a kernel that forgets len_ptr shows in the last `reach` columns of its output — most of all on a reused plan after a longer utterance.
-Window plans of the streaming path are not attached to a slot id (piper_hip_voice_tap cannot reach them without a new selector): streams stay
-pinned to the whole utterance at 2e-5 (test_gpu_voice.py, test_gpu_stream_batch.py).
+Window plans of the streaming path are not attached to a slot id: tests/test_gpu_stream_windows.py reaches them through the tap's "window:"
+selector and runs this chained check on every step of a stream; the streams themselves stay pinned to the whole utterance at 2e-5
+(test_gpu_voice.py, test_gpu_stream_batch.py).
 
 Which kernel a launch takes follows from the builder (csrc/voice.hip) and launch_conv_win_multi (csrc/conv_win.hip). Where the step name or the
 `flops` field of the profile tells, the cases assert it. A plan is built for the BUCKET of its longest item, Fb = ⌈F / 16⌉ · 16 (⌈F / 64⌉ · 64
