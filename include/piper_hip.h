@@ -63,6 +63,14 @@ int piper_hip_device_count(void);
 /* MetalContext.init (Metal/MetalContext.swift:9-33) + MetalBackend.init (MetalBackend.swift:12-15). */
 int piper_hip_create(int device, piper_hip_ctx** out);
 void piper_hip_destroy(piper_hip_ctx* ctx);
+/* Route records, a debugging aid (DESIGN.md "Route records"): while armed (on != 0; off by default) every conv, ResBlock-pair, flow-seam and
+ * attention launcher of this context appends one line "<variant> | Cout=… Cin=… Lout=… N=… CUs=…" when it has chosen its kernel: the variant is
+ * the kernel family with its template and launch parameters, gate, prologue, epilogue and conv / convT; the shape stands apart. An op entry
+ * point keeps the records of the last call: piper_hip_last_routes copies them out, '\n' between records ('\0'-terminated; *needed = bytes
+ * with the terminator, buf may be NULL to ask). A voice plan keeps them per step: the "@routes" selectors of piper_hip_voice_tap. Arming or
+ * disarming forgets the context's records; plans enqueued while disarmed report empty routes. One thread drives an armed context. */
+int piper_hip_routes_arm(piper_hip_ctx* ctx, int on);
+int piper_hip_last_routes(piper_hip_ctx* ctx, char* buf, size_t n, size_t* needed);
 /* Device memory held by the context's pool (buffers + cached free blocks) and the part currently handed out. The pool
  * recycles power-of-two blocks, so a host that sees many utterance shapes plateaus instead of growing; `memory_trim`
  * returns the cached free blocks to the driver (the role ARC plays for MTLBuffer in the reference). */
@@ -881,6 +889,11 @@ int piper_hip_voice_stream_pool_joins_pending(piper_hip_voice* v, int slot);
  *                            prepared or opened, when the plan has been evicted from the cache, or when another stream has run the plan
  *                            since (its tensors are no longer this step's). "window:<tensor>@<step>" is PIPER_HIP_ERR_UNSUPPORTED, as
  *                            above; "window:@steps" lists the window plan's launches.
+ *   "@routes"                one line per launch of the schedule: step name, tab, the route records of the step's most recent enqueue
+ *                            (piper_hip_routes_arm; "; " between the records of one launch), one character code per float. Also
+ *                            "predict:@routes" and "window:@routes". A captured graph replays the kernels it was captured with, so the
+ *                            records hold for replays; a plan enqueued while the context was not armed reports nothing behind the tabs.
+ *                            Reading them runs nothing and changes no tensor.
  * A voice with a speaker table (piper_hip_voice_attach_speakers) adds, per batch item at a fixed length: "spk.g" [gin], the mixed speaker
  * vector, and "spk.bias" [Ctot], the item's speaker row — a plan writes the rows it computes and leaves the others 0.0: the slot's plan the
  * flow and generator rows, "predict:spk.bias" the dp.pre rows. */

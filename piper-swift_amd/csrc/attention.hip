@@ -958,6 +958,7 @@ int launch_rel_attention_split(piper_hip_ctx* ctx, hipStream_t s, const float* q
     return launch_rel_attention(ctx, s, q, k, v, ek, ev, out, N, H, d, T, w, in_batch_stride, out_batch_stride, len_ptr);
   if (dispatch_att_lds(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr, nsplit, part_o, part_ml) != 0)
     return launch_rel_attention(ctx, s, q, k, v, ek, ev, out, N, H, d, T, w, in_batch_stride, out_batch_stride, len_ptr);
+  PH_ROUTE(ctx, H * d, d, T, N, "att_lds D=%d split=%d", d, nsplit);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rel_attention (split) launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;
@@ -972,6 +973,7 @@ int launch_rel_attention(piper_hip_ctx* ctx, hipStream_t s, const float* q, cons
   if (!no_mfma && !no_lds && att_head_dim_ok(d) && w >= 0 && 2 * w + 1 <= 16 && H <= 65535 && N <= 65535 && T <= 1024 && T >= 4 && (T & 3) == 0 &&
       (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0 && (in_batch_stride & 3) == 0) {
     if (dispatch_att_lds(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr, 1, nullptr, nullptr) == 0) {
+      PH_ROUTE(ctx, H * d, d, T, N, "att_lds D=%d split=1", d);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rel_attention (lds) launch failed: %s", hipGetErrorString(e));
       return PIPER_HIP_OK;
@@ -981,6 +983,7 @@ int launch_rel_attention(piper_hip_ctx* ctx, hipStream_t s, const float* q, cons
     int rc = T <= 2048 ? dispatch_att_mfma<16>(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr)
                        : dispatch_att_mfma<8>(d, s, q, k, v, ek, ev, out, N, H, T, w, in_batch_stride, out_batch_stride, len_ptr);
     if (rc == 0) {
+      PH_ROUTE(ctx, H * d, d, T, N, "att_mfma D=%d RV=%d", d, T <= 2048 ? 16 : 8);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rel_attention (mfma) launch failed: %s", hipGetErrorString(e));
       return PIPER_HIP_OK;
@@ -1022,6 +1025,7 @@ int launch_rel_attention(piper_hip_ctx* ctx, hipStream_t s, const float* q, cons
 #else
                        out_batch_stride, G, TK);
 #endif
+  PH_ROUTE(ctx, H * d, d, T, N, "att_scalar R=%d", R);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rel_attention launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;
@@ -1052,6 +1056,7 @@ int launch_attention_block(piper_hip_ctx* ctx, hipStream_t s, const float* q, co
   if (launch_att_block<96>(s, q, k, v, ek, ev, wo16, bo, xres, gamma, beta, out, N, H, T, w, in_batch_stride, x_batch_stride, len_ptr, o_nsteps,
                            eps) != 0)
     PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "attention_block: needs more than 160 KiB of LDS");
+  PH_ROUTE(ctx, H * d, d, T, N, "att_block D=%d", d);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "attention_block launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;
@@ -1070,6 +1075,7 @@ PH_EXPORT int piper_hip_rel_attention_f32(piper_hip_ctx* ctx, const float* q, co
   if (cnt == 0) return PIPER_HIP_OK;
   if (!q || !k || !v || !emb_rel_k || !emb_rel_v) PH_FAIL(PIPER_HIP_ERR_ARG, "rel_attention: null input");
   ph::StreamScope ss(ctx, stream);
+  ph::RouteScope routes(ctx);
   const int64_t bs = heads * head_dim * t;
   const int nsplit = ph::rel_attention_split_parts(ctx, (int)n, (int)heads, (int)head_dim, (int)t, (int)window);
   if (nsplit > 1) {
@@ -1106,6 +1112,7 @@ PH_EXPORT int piper_hip_attention_block_f32(piper_hip_ctx* ctx, const float* q, 
     PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "attention_block: covered geometry is head_dim 96, heads·head_dim ≤ 256, window ≤ 7, T ≤ 2048 — compose "
                                        "rel_attention + conv1d + add_layernorm instead");
   ph::StreamScope ss(ctx, stream);
+  ph::RouteScope routes(ctx);
   void* pw = nullptr;
   rc = ctx->pool.alloc(ph::packed_conv_floats(C, C, 1, 16) * sizeof(float), &pw);
   if (rc) return rc;

@@ -120,9 +120,35 @@ struct piper_hip_ctx {
   // op-internal temporaries (packed weights, fused-op intermediates) of non-blocking calls: returned to the pool at
   // the next host-visible sync point of this context
   std::vector<void*> deferred;
+  // Route records (piper_hip_routes_arm): while armed, every launcher appends one line of text — which kernel variant it chose, then
+  // the shape — to *route_sink at the moment it has made its choice. An op entry point points the sink at last_routes for the length
+  // of the call (RouteScope); a voice plan's step points it at the step's own string while it enqueues. Host bookkeeping of a
+  // debugging aid: one thread drives an armed context.
+  bool routes_on = false;
+  std::string* route_sink = nullptr;
+  std::string last_routes;
 };
 
 namespace ph {
+
+// "<variant> | Cout=… Cin=… Lout=… N=… CUs=…" appended to the context's sink, records separated by '\n'. The variant part names the family,
+// its template and launch parameters, gate, prologue, epilogue and conv / convT; the shape stands apart so that variants compare
+// without it.
+void route_note(piper_hip_ctx* ctx, int64_t Cout, int64_t Cin, int64_t Lout, int64_t N, const char* fmt, ...) __attribute__((format(printf, 6, 7)));
+// disarmed (the default): one predictable branch per launch
+#define PH_ROUTE(ctx, Cout, Cin, Lout, N, ...)                                                          \
+  do {                                                                                                  \
+    if (__builtin_expect((ctx)->routes_on, 0)) ::ph::route_note(ctx, Cout, Cin, Lout, N, __VA_ARGS__); \
+  } while (0)
+// an op entry point: the records of this call replace those of the last one
+struct RouteScope {
+  piper_hip_ctx* ctx;
+  explicit RouteScope(piper_hip_ctx* c) : ctx(c) {
+    if (__builtin_expect(c->routes_on, 0)) { c->last_routes.clear(); c->route_sink = &c->last_routes; }
+  }
+  ~RouteScope() { ctx->route_sink = nullptr; }
+  RouteScope(const RouteScope&) = delete;
+};
 
 void release_deferred(piper_hip_ctx* ctx);
 inline void defer_free(piper_hip_ctx* ctx, void* p) {

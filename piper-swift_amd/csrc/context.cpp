@@ -1,5 +1,6 @@
 // context.cpp — device context, pooled buffers, transfers, streams, timers.
 // Replaces Metal/MetalContext.swift:4-62 and the buffer/blit helpers of MetalBackend.swift:34-66, 841-874, 963-993.
+#include <algorithm>
 #include <mutex>
 #include "common.h"
 
@@ -200,7 +201,40 @@ int ensure_out(piper_hip_ctx* ctx, float** out, size_t count, int) {
   return PIPER_HIP_OK;
 }
 
+void route_note(piper_hip_ctx* ctx, int64_t Cout, int64_t Cin, int64_t Lout, int64_t N, const char* fmt, ...) {
+  std::string* sink = ctx->route_sink;
+  if (!sink) return;  // a launch outside an op call or a plan step: nobody reads it
+  char buf[256];
+  va_list ap;
+  va_start(ap, fmt);
+  int n = vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  n = std::max(0, std::min(n, (int)sizeof buf - 1));
+  // (the CU count stands with the shape: the heuristics weigh the shape against it)
+  snprintf(buf + n, sizeof buf - n, " | Cout=%lld Cin=%lld Lout=%lld N=%lld CUs=%d", (long long)Cout, (long long)Cin, (long long)Lout, (long long)N, ctx->num_cus);
+  if (!sink->empty()) *sink += '\n';
+  *sink += buf;
+}
+
 }  // namespace ph
+
+PH_EXPORT int piper_hip_routes_arm(piper_hip_ctx* ctx, int on) {
+  if (!ctx) PH_FAIL(PIPER_HIP_ERR_ARG, "null context");
+  ctx->routes_on = on != 0;
+  ctx->route_sink = nullptr;
+  ctx->last_routes.clear();
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_last_routes(piper_hip_ctx* ctx, char* buf, size_t n, size_t* needed) {
+  if (!ctx) PH_FAIL(PIPER_HIP_ERR_ARG, "null context");
+  if (needed) *needed = ctx->last_routes.size() + 1;
+  if (buf) {
+    if (n < ctx->last_routes.size() + 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "last_routes: buffer of %zu bytes, %zu needed", n, ctx->last_routes.size() + 1);
+    memcpy(buf, ctx->last_routes.c_str(), ctx->last_routes.size() + 1);
+  }
+  return PIPER_HIP_OK;
+}
 
 PH_EXPORT const char* piper_hip_last_error(void) { return ph::get_error(); }
 PH_EXPORT int piper_hip_abi_version(void) { return PIPER_HIP_ABI_VERSION; }

@@ -24,6 +24,21 @@ enum Epilogue : int {
   EPI_MRF_MEAN = 7,     // r2 = v + res;  y = lrelu(((mrf_a + mrf_b) + r2) / 3, alpha2)   (last ResBlock conv of a stage)
 };
 
+// the names route records use (common.h: PH_ROUTE)
+inline const char* prologue_name(int p) {
+  static const char* const n[] = {"none", "lrelu", "avg3_lrelu", "ln"};
+  return p >= 0 && p < 4 ? n[p] : "?";
+}
+inline const char* epilogue_name(int e) {
+  static const char* const n[] = {"store", "relu", "tanh", "rsub", "wn_res_skip", "wn_skip_last", "convt", "mrf_mean"};
+  return e >= 0 && e < 8 ? n[e] : "?";
+}
+
+// one record of a launcher that works on ConvArgs `a`: "<family and its parameters> gate=… pro=… epi=… res=… conv|convT"
+#define PH_ROUTE_CONV(ctx, a, fmt, ...)                                                                                         \
+  PH_ROUTE(ctx, (a).Cout, (a).Cin, (a).Lout, (a).N, fmt " gate=%d pro=%s epi=%s res=%d %s", ##__VA_ARGS__, (a).gate,           \
+           ::ph::prologue_name((a).prologue), ::ph::epilogue_name((a).epilogue), (a).res ? 1 : 0, (a).epilogue == ::ph::EPI_CONVT ? "convT" : "conv")
+
 struct ConvArgs {
   // tensors
   const float* x = nullptr;   // [N, x_channels, Lin]

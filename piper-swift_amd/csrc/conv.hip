@@ -457,15 +457,17 @@ bool try_launch_tile(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a) {
   // everywhere else (ConvTranspose phases, 128-channel stages, anything that gives < 4 blocks per CU)
   if (mode != 1 && (blocks < 4 * ctx->num_cus || MT > 2 || a.epilogue == EPI_CONVT)) return false;
   const int nsteps = padded_steps(a.Cin, a.K);
+  bool ok = false;
   switch (a.K) {
-    case 1: return launch_tile_k<1>(s, a, MT, NTW, nsteps);
-    case 2: return launch_tile_k<2>(s, a, MT, NTW, nsteps);
-    case 3: return launch_tile_k<3>(s, a, MT, NTW, nsteps);
-    case 5: return launch_tile_k<5>(s, a, MT, NTW, nsteps);
-    case 7: return launch_tile_k<7>(s, a, MT, NTW, nsteps);
-    case 11: return launch_tile_k<11>(s, a, MT, NTW, nsteps);
+    case 1: ok = launch_tile_k<1>(s, a, MT, NTW, nsteps); break;
+    case 2: ok = launch_tile_k<2>(s, a, MT, NTW, nsteps); break;
+    case 3: ok = launch_tile_k<3>(s, a, MT, NTW, nsteps); break;
+    case 5: ok = launch_tile_k<5>(s, a, MT, NTW, nsteps); break;
+    case 7: ok = launch_tile_k<7>(s, a, MT, NTW, nsteps); break;
+    case 11: ok = launch_tile_k<11>(s, a, MT, NTW, nsteps); break;
   }
-  return false;
+  if (ok) PH_ROUTE_CONV(ctx, a, "tile K=%d MT=%d NTW=%d", a.K, MT, NTW);
+  return ok;
 }
 
 }  // namespace
@@ -624,6 +626,7 @@ int launch_conv_mfma(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a_in) {
     }
   }
   if (!ok) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "conv_mfma: variant K=%d NT=%d TM=%d gate=%d prologue=%d not compiled", a.K, NT, TM, a.gate, a.prologue);
+  PH_ROUTE_CONV(ctx, a, "stream K=%d TM=%d NT=%d KS=%d BT=%d", a.K, TM, NT, KS, BT);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_mfma launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;
@@ -656,8 +659,15 @@ int launch_conv_direct(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a) {
           case PRO_LRELU: hipLaunchKernelGGL((conv_cout1_split_kernel<PRO_LRELU>), g, dim3(256), 0, s, a); break;
           default: hipLaunchKernelGGL((conv_cout1_split_kernel<PRO_AVG3_LRELU>), g, dim3(256), 0, s, a); break;
         }
-      } else launch_wide<64>(s, a);
-    } else launch_wide<256>(s, a);
+        PH_ROUTE_CONV(ctx, a, "cout1_split K=%d", a.K);
+      } else {
+        launch_wide<64>(s, a);
+        PH_ROUTE_CONV(ctx, a, "cout1_wide K=%d BT=64", a.K);
+      }
+    } else {
+      launch_wide<256>(s, a);
+      PH_ROUTE_CONV(ctx, a, "cout1_wide K=%d BT=256", a.K);
+    }
     hipError_t e3 = hipGetLastError();
     if (e3 != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_cout1_wide launch failed: %s", hipGetErrorString(e3));
     return PIPER_HIP_OK;
@@ -682,6 +692,7 @@ int launch_conv_direct(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a) {
       default: PH_SMALL(PRO_AVG3_LRELU) break;
     }
 #undef PH_SMALL
+    PH_ROUTE_CONV(ctx, a, "small_cout CO=%d vec4=%d", a.Cout < 4 ? a.Cout : 4, vec4);
     hipError_t e2 = hipGetLastError();
     if (e2 != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_small_cout launch failed: %s", hipGetErrorString(e2));
     return PIPER_HIP_OK;
@@ -692,6 +703,7 @@ int launch_conv_direct(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a) {
     case PRO_LRELU: hipLaunchKernelGGL(conv_direct_kernel<PRO_LRELU>, dim3(grid), dim3(kBlock), 0, s, a); break;
     default: hipLaunchKernelGGL(conv_direct_kernel<PRO_AVG3_LRELU>, dim3(grid), dim3(kBlock), 0, s, a); break;
   }
+  PH_ROUTE_CONV(ctx, a, "direct stride=%d groups=%d", a.stride, a.groups);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_direct launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;
@@ -704,6 +716,7 @@ int launch_convt_direct(piper_hip_ctx* ctx, hipStream_t s, const float* x, const
   const int grid = (int)std::min<int64_t>(ceil_div(total, kBlock), (int64_t)ctx->num_cus * 16);
   hipLaunchKernelGGL(convt_direct_kernel, dim3(grid), dim3(kBlock), 0, s, x, w, bias, y, N, Cin, Lin, Cout, K, stride, dil, padL,
                      Lout, groups);
+  PH_ROUTE(ctx, Cout, Cin, Lout, N, "convt_direct stride=%d groups=%d convT", stride, groups);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "convt_direct launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;

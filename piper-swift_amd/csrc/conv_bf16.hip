@@ -437,7 +437,12 @@ int launch_conv_bf16_multi(piper_hip_ctx* ctx, hipStream_t s, const ConvBf16Args
   const dim3 grid((unsigned)ceil_div(a.Lout, WN * NTW * 32), (unsigned)ceil_div(MT, WM * MTW), (unsigned)(a.N * count));
   ConvBf16Multi multi;
   for (int i = 0; i < kBf16Multi; i++) multi.c[i] = convs[i < count ? i : 0];
-  return launch_cfg(s, multi, a.N, MTW, NTW, WM, grid, lds);
+  const int rc = launch_cfg(s, multi, a.N, MTW, NTW, WM, grid, lds);
+  if (!rc)
+    for (int i = 0; i < count; i++)
+      PH_ROUTE(ctx, convs[i].Cout, convs[i].Cin, convs[i].Lout, convs[i].N, "bf16 K=%d MTW=%d NTW=%d WM=%d multi=%d %s", convs[i].K, MTW, NTW, WM, count,
+               ct ? "convT" : "conv");
+  return rc;
 }
 
 }  // namespace ph

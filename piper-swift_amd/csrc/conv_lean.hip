@@ -659,6 +659,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
     const dim3 grid((unsigned)mt_g, (unsigned)chunk_groups(ctx, mt_g, nch, c.N), (unsigned)c.N);
     if (c.K == 5) hipLaunchKernelGGL((conv_gate_kernel<5, 6>), grid, dim3(512), 0, s, g, nch);
     else hipLaunchKernelGGL((conv_gate_kernel<3, 6>), grid, dim3(512), 0, s, g, nch);
+    PH_ROUTE_CONV(ctx, c, "lean_gate K=%d NQ=6", c.K);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_gate launch failed: %s", hipGetErrorString(e));
     return 1;
@@ -683,6 +684,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
     if (c.K == 1) hipLaunchKernelGGL((conv_k1_ln_kernel<6>), grid, dim3(512), 0, s, a, ln);
     else if (c.epilogue == EPI_RELU) hipLaunchKernelGGL((conv_k3_ln_kernel<6, EPI_RELU>), grid, dim3(512), 0, s, a, ln);
     else hipLaunchKernelGGL((conv_k3_ln_kernel<6, EPI_STORE>), grid, dim3(512), 0, s, a, ln);
+    PH_ROUTE_CONV(ctx, c, "lean_ln K=%d NQ=6", c.K);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_lean (LayerNorm) launch failed: %s", hipGetErrorString(e));
     return 1;
@@ -706,6 +708,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
       if (lds_optin_needed(configured))
         (void)hipFuncSetAttribute((const void*)conv_k3_r8_kernel<NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       hipLaunchKernelGGL((conv_k3_r8_kernel<NQ>), dim3((unsigned)mt8, (unsigned)nch, (unsigned)c.N), dim3(512), lds, s, a, w_bytes);
+      PH_ROUTE_CONV(ctx, c, "lean_k3_r8 K=3 NQ=%d", NQ);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_lean (8-row tiles) launch failed: %s", hipGetErrorString(e));
       return 1;
@@ -737,6 +740,7 @@ int try_launch_conv_lean(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& c) {
   const dim3 grid((unsigned)mtiles, (unsigned)chunk_groups(ctx, mtiles, nchunks, c.N), (unsigned)c.N);
   const bool ok = NQ == 3 ? launch_lean_nq<3>(s, grid, a, c.epilogue, nchunks) : launch_lean_nq<6>(s, grid, a, c.epilogue, nchunks);
   if (!ok) return 0;
+  PH_ROUTE_CONV(ctx, c, "lean_k1 K=1 NQ=%d", NQ);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_lean launch failed: %s", hipGetErrorString(e));
   return 1;
@@ -771,6 +775,7 @@ int launch_flow_tail(piper_hip_ctx* ctx, hipStream_t s, const FlowTailArgs& t) {
   const dim3 grid((unsigned)mtiles, (unsigned)chunk_groups(ctx, mtiles, nchunks, t.N), (unsigned)t.N);
   if (t.seam) hipLaunchKernelGGL((conv_k1_tail_kernel<3, 6, 6>), grid, dim3(512), 0, s, a, nchunks);
   else hipLaunchKernelGGL((conv_k1_tail_kernel<0, 6, 6>), grid, dim3(512), 0, s, a, nchunks);
+  PH_ROUTE(ctx, a.rows, 2 * t.H + (t.seam ? t.half : 0), t.F, t.N, "flow_tail seam=%d conv", t.seam);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "flow_tail launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;

@@ -535,6 +535,9 @@ int launch_conv_pipe_multi(piper_hip_ctx* ctx, hipStream_t s, const ConvWinArgs*
   PH_PIPE_CASE(4, 1, 1) PH_PIPE_CASE(4, 1, 2) PH_PIPE_CASE(2, 2, 1) PH_PIPE_CASE(2, 2, 2) PH_PIPE_CASE(1, 4, 1) PH_PIPE_CASE(1, 4, 2)
   PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "conv_pipe: no instance for WM=%d WN=%d NTW=%d", g.WM, g.WN, g.NTW);
 #undef PH_PIPE_CASE
+  for (int i = 0; i < count; i++)
+    PH_ROUTE(ctx, convs[i].Cout, convs[i].Cin, convs[i].Lout, convs[i].N, "pipe K=%d WM=%d WN=%d NTW=%d multi=%d avg3=%d %s", convs[i].K, g.WM, g.WN, g.NTW, count,
+             avg ? 1 : 0, ct ? "convT" : "conv");
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_pipe launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;

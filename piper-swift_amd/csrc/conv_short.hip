@@ -437,6 +437,7 @@ int try_launch_conv_short(piper_hip_ctx* ctx, hipStream_t s, const ConvArgs& a_i
     case 7: ok = launch_short_k<7>(s, a, NT, BT, nspans, mtiles, ks_log2, nsteps, rows_alloc, grid, lds); break;
   }
   if (!ok) return 0;
+  PH_ROUTE_CONV(ctx, a, "short K=%d NT=%d KS=%d BT=%d QC=%d", a.K, NT, KS, BT, QC);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_short launch failed: %s", hipGetErrorString(e));
   return 1;

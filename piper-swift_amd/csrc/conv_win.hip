@@ -433,6 +433,9 @@ int launch_conv_win_multi(piper_hip_ctx* ctx, hipStream_t s, const ConvWinArgs* 
   PH_WIN_CASE(4, 1, 2)
   PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "conv_win: no instance for WM=%d WN=%d KS=%d", WM, WN, KS);
 #undef PH_WIN_CASE
+  for (int i = 0; i < count; i++)
+    PH_ROUTE(ctx, convs[i].Cout, convs[i].Cin, convs[i].Lout, convs[i].N, "win K=%d WM=%d WN=%d KS=%d multi=%d xcd=%d avg3=%d %s", convs[i].K, WM, WN, KS, count,
+             xcd_rows, convs[i].x2 ? 1 : 0, a.ct_stride > 0 ? "convT" : "conv");
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "conv_win launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;

@@ -99,13 +99,14 @@ bool flow_seam_eligible(int H, int half) { return H >= 16 && H <= kSeamMaxH && (
 
 // post16 / pre16: 16-wide fragment images (pack_conv_weights tm = 16) of post [half × H × 1] and of the NEXT coupling's pre [H × half × 1];
 // ob / os: post's output channel map into zp (row r ↦ channel ob + os·r). skip [N][H][F], zp [N][2·half][F] (updated in place), h [N][H][F].
-int launch_flow_seam(hipStream_t s, const float* skip, float* zp, float* h, const float* post16, const float* post_b, const float* pre16,
+int launch_flow_seam(piper_hip_ctx* ctx, hipStream_t s, const float* skip, float* zp, float* h, const float* post16, const float* post_b, const float* pre16,
                      const float* pre_b, int N, int H, int half, int F, int post_steps, int pre_steps, int ob, int os, const int* len_ptr) {
   if (N <= 0 || F <= 0) return PIPER_HIP_OK;
   if (!flow_seam_eligible(H, half) || N > 65535 || !post_b || !pre_b) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "flow_seam: H=%d half=%d not covered", H, half);
   const dim3 grid((unsigned)ceil_div(F, 16), (unsigned)N);
   hipLaunchKernelGGL(flow_seam_kernel, grid, dim3(64 * (H / 16)), (size_t)half * 16 * sizeof(float), s, skip, zp, h, post16, post_b, pre16, pre_b, H,
                      half, F, post_steps, pre_steps, ob, os, len_ptr);
+  PH_ROUTE(ctx, half + H, H + half, F, N, "flow_seam waves=%d conv", H / 16);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "flow_seam launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;

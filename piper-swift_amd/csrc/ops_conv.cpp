@@ -47,6 +47,7 @@ PH_EXPORT int piper_hip_conv1d_f32(piper_hip_ctx* ctx, const float* x, const int
   if (count == 0) return PIPER_HIP_OK;
   if (!x || !w) PH_FAIL(PIPER_HIP_ERR_ARG, "conv1dF32: null input");
   StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
   ConvArgs a;
   a.x = x; a.bias = bias; a.y = *out;
   a.N = (int)N; a.Cin = (int)Cin; a.Cout = (int)Cout; a.K = (int)K; a.dil = p->dilation; a.padL = p->pad_l;
@@ -112,6 +113,7 @@ PH_EXPORT int piper_hip_convtranspose1d_f32(piper_hip_ctx* ctx, const float* x, 
   if (count == 0) return PIPER_HIP_OK;
   if (!x || !w) PH_FAIL(PIPER_HIP_ERR_ARG, "convTranspose1dF32: null input");
   StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
   const int s = p->stride;
   static const bool no_win = getenv("PIPER_HIP_NO_WIN") != nullptr;
   if (!no_win && g == 1 && p->dilation == 1 && p->output_padding == 0 && p->pad_l == p->pad_r && Lin >= 256 &&
@@ -185,6 +187,7 @@ PH_EXPORT int piper_hip_conv1d_bf16(piper_hip_ctx* ctx, const float* x, const in
   if (count == 0) return PIPER_HIP_OK;
   if (!x || !w) PH_FAIL(PIPER_HIP_ERR_ARG, "conv1dBF16: null input");
   StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
   const int64_t Lmax = Lin > Lout ? Lin : Lout;
   const int64_t row = c8_row_len(Lmax);
   const size_t img_bytes = (size_t)N * (Cin / 8) * row * 16;
@@ -231,6 +234,7 @@ PH_EXPORT int piper_hip_convtranspose1d_bf16(piper_hip_ctx* ctx, const float* x,
   if (count == 0) return PIPER_HIP_OK;
   if (!x || !w) PH_FAIL(PIPER_HIP_ERR_ARG, "convTranspose1dBF16: null input");
   StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
   const int64_t row = c8_row_len(Lin);
   const size_t img_bytes = (size_t)N * (Cin / 8) * row * 16;
   void *img = nullptr, *pw = nullptr;
@@ -272,6 +276,7 @@ PH_EXPORT int piper_hip_wavenet_layer_f32(piper_hip_ctx* ctx, const float* x, co
   if (cnt == 0) return PIPER_HIP_OK;
   if (!x || !w_in || !w_rs) PH_FAIL(PIPER_HIP_ERR_ARG, "wavenet_layer: null input");
   StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
   const int C = (int)c, T = (int)t, K = (int)k;
   const int Crs = last ? C : 2 * C;
   float *p_in = nullptr, *p_rs = nullptr, *acts = nullptr;
@@ -325,6 +330,7 @@ PH_EXPORT int piper_hip_hifigan_resblock_f32(piper_hip_ctx* ctx, int type, const
   if (cnt == 0) return PIPER_HIP_OK;
   if (!x) PH_FAIL(PIPER_HIP_ERR_ARG, "hifigan_resblock: null input");
   StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
   const int C = (int)c, T = (int)t, K = (int)k;
   const bool mfma = conv_mfma_eligible(C, C, K, 1, 1);
   // ping-pong so the residual source is never the buffer being written

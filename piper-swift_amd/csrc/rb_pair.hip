@@ -468,6 +468,9 @@ int launch_rb_pair_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairArgs* pa
   for (int i = 0; i < kWinMulti; i++) m.c[i] = pairs[i < count ? i : 0];
   if (a.C == 32) exact ? launch_pair_inst<1, true>(ctx, s, m, sch, g) : launch_pair_inst<1, false>(ctx, s, m, sch, g);
   else exact ? launch_pair_inst<2, true>(ctx, s, m, sch, g) : launch_pair_inst<2, false>(ctx, s, m, sch, g);
+  for (int i = 0; i < count; i++)
+    PH_ROUTE(ctx, pairs[i].C, pairs[i].C, pairs[i].L, pairs[i].N, "rb_pair MT=%d exact=%d Ka=%d da=%d Kb=%d db=%d multi=%d res_a=%d res_b_x=%d conv", a.C / 32, exact ? 1 : 0,
+             pairs[i].Ka, pairs[i].dila, pairs[i].Kb, pairs[i].dilb, count, pairs[i].res_a ? 1 : 0, pairs[i].res_b_x ? 1 : 0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rb_pair launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;

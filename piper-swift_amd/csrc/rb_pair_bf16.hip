@@ -294,7 +294,6 @@ bool rb_pair_bf16_eligible(int C, int Ka, int dila, int Kb, int dilb, int L) {
 }
 
 int launch_rb_pair_bf16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairBf16Args* pairs, int count) {
-  (void)ctx;
   if (count < 1 || count > kWinMulti) PH_FAIL(PIPER_HIP_ERR_ARG, "rb_pair_bf16: %d pairs in one launch (1..%d)", count, kWinMulti);
   const RbPairBf16Args& a = pairs[0];
   if (a.N <= 0 || a.L <= 0) return PIPER_HIP_OK;
@@ -318,6 +317,9 @@ int launch_rb_pair_bf16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairBf1
   if (a.C == 32) launch_inst<1, 1>(s, m, a.N, order, g, grid);
   else if (a.C == 64) launch_inst<2, 1>(s, m, a.N, order, g, grid);
   else launch_inst<4, 2>(s, m, a.N, order, g, grid);
+  for (int i = 0; i < count; i++)
+    PH_ROUTE(ctx, pairs[i].C, pairs[i].C, pairs[i].L, pairs[i].N, "rb_pair_bf16 MT=%d MTW=%d Ka=%d da=%d Kb=%d db=%d multi=%d conv", a.C / 32, a.C == 128 ? 2 : 1, pairs[i].Ka,
+             pairs[i].dila, pairs[i].Kb, pairs[i].dilb, count);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rb_pair_bf16 launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;

@@ -41,7 +41,7 @@ int launch_rel_attention_split(piper_hip_ctx* ctx, hipStream_t s, const float* q
 size_t dp_scalars_bytes(int n);
 void dp_scalars_fill(void* host, int i, float noise_w, float length_scale, unsigned gen, unsigned seed);
 bool flow_seam_eligible(int H, int half);
-int launch_flow_seam(hipStream_t s, const float* skip, float* zp, float* h, const float* post16, const float* post_b, const float* pre16,
+int launch_flow_seam(piper_hip_ctx* ctx, hipStream_t s, const float* skip, float* zp, float* h, const float* post16, const float* post_b, const float* pre16,
                      const float* pre_b, int N, int H, int half, int F, int post_steps, int pre_steps, int ob, int os, const int* len_ptr);
 bool dds_layer_eligible(int H, int K);
 int launch_dds_layer(piper_hip_ctx* ctx, hipStream_t s, const float* x, const float* dw_w, const float* dw_b, const float* g1, const float* b1,
@@ -187,6 +187,18 @@ struct Step {
   std::string tag;  // kernel family ("conv_mfma", "conv_small", "rel_attention", …) for piper_hip_voice_time_subset
   int lane = 0;  // 0 = the slot's stream; 1, 2 = side streams between a FORK and a JOIN (independent ResBlocks of one stage)
   enum Kind { LAUNCH, FORK, JOIN } kind = LAUNCH;
+  // route records of the most recent enqueue, eager or under capture (a captured graph replays the same kernels): empty unless the
+  // context was armed then (piper_hip_routes_arm)
+  piper_hip_ctx* ctx = nullptr;
+  std::string routes;
+  int enqueue(hipStream_t q) {
+    if (__builtin_expect(!ctx->routes_on, 1)) return run(q);
+    routes.clear();
+    ctx->route_sink = &routes;
+    const int rc = run(q);
+    ctx->route_sink = nullptr;
+    return rc;
+  }
 };
 
 struct ConvW {  // one resident conv: packed (MFMA) or raw (direct) weights + bias pointer into the resident blob
@@ -876,6 +888,7 @@ struct Builder {
     st.flops = flops; st.bytes = bytes;
     st.lane = lane;
     st.run = std::move(run);
+    st.ctx = v->ctx;
     s.steps.push_back(std::move(st));
   }
   void mark(const std::string& name, Step::Kind kind) {
@@ -1748,8 +1761,9 @@ const float* build_flow(Builder& b, const FrontBuffers& fb) {
       const float *p16 = C.post.w16, *pb = C.post.bias, *q16 = Nx.pre.w16, *qb = Nx.pre.bias;
       const int ps = (int)(packed_conv_floats(half, H, 1, 16) / ((size_t)ceil_div(half, 16) * 64));
       const int qs = (int)(packed_conv_floats(H, half, 1, 16) / ((size_t)ceil_div(H, 16) * 64));
+      piper_hip_ctx* ctx = v->ctx;
       b.step(p + "post_sub_flip_pre" + std::to_string(f - 1), "conv_mfma", seam_flops, seam_bytes,
-             [=](hipStream_t q) { return launch_flow_seam(q, skip, zp, h, p16, pb, q16, qb, NB, H, half, F, ps, qs, ob, os, lensF); });
+             [=](hipStream_t q) { return launch_flow_seam(ctx, q, skip, zp, h, p16, pb, q16, qb, NB, H, half, F, ps, qs, ob, os, lensF); });
     } else {
       ConvArgs a = b.plain(skip, zp, H, I, F, lensF);
       a.epilogue = EPI_RSUB;
@@ -1993,7 +2007,7 @@ int run_schedule(Slot& s, hipStream_t q, bool parallel) {
       continue;
     }
     hipStream_t target = (parallel && st.lane > 0) ? s.set.side[st.lane - 1] : q;
-    int rc = st.run(target);
+    int rc = st.enqueue(target);
     if (rc) return rc;
   }
   hipError_t e = hipGetLastError();
@@ -3212,7 +3226,7 @@ int generator_halo_frames(const piper_hip_voice_config& c) {
 
 int run_steps(Slot& s, const std::vector<int>& pick, hipStream_t q) {
   for (int i : pick) {
-    const int rc = s.steps[i].run(q);
+    const int rc = s.steps[i].enqueue(q);
     if (rc) return rc;
   }
   return PIPER_HIP_OK;
@@ -4751,6 +4765,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
                                   size_t* n_floats) {
   if (!v || !name) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   // grammar: ["predict:"] <tensor> ["@" <step name>]   |   ["predict:"] "@steps"   |   ["window:"] <tensor>   |   "window:@steps"
+  //          ["predict:" | "window:"] "@routes"
   std::string full(name);
   Slot* sp = slot_plan(v, slot);
   const WindowRecord* win = nullptr;  // "window:": the generator plan of the slot's latest stream step, rows at that step's window lengths
@@ -4780,6 +4795,26 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
   Slot& s = *tp;
   const size_t at = full.find('@');
   const std::string tensor_name = full.substr(0, at), step_name = at == std::string::npos ? std::string() : full.substr(at + 1);
+  if (at != std::string::npos && tensor_name.empty() && step_name == "routes") {
+    // one line per launch: step name, tab, the route records of its most recent enqueue ("; " between the records of one launch; nothing
+    // behind the tab when the context was not armed then). Runs nothing and changes no tensor.
+    std::string all;
+    for (const Step& st : s.steps) {
+      if (st.kind != Step::LAUNCH) continue;
+      all += st.name + "\t";
+      for (const char c : st.routes) {
+        if (c == '\n') all += "; ";
+        else all += c;
+      }
+      all += "\n";
+    }
+    if (n_floats) *n_floats = all.size();
+    if (host) {
+      if (max_floats < all.size()) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
+      for (size_t i = 0; i < all.size(); i++) host[i] = (float)(unsigned char)all[i];
+    }
+    return PIPER_HIP_OK;
+  }
   if (at != std::string::npos && tensor_name.empty() && step_name == "steps") {
     // the names of the schedule's launches in order, one per line, one character per float: what piper_hip_voice_profile reports, for a plan
     // that no slot id reaches
@@ -4827,7 +4862,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
     auto run_range = [&](int from, int to) -> int {  // eagerly, in schedule order on the plan's stream (as piper_hip_voice_profile does)
       for (int i = from; i < to; i++)
         if (s.steps[i].kind == Step::LAUNCH) {
-          const int rc = s.steps[i].run(q);
+          const int rc = s.steps[i].enqueue(q);
           if (rc) return rc;
         }
       PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
@@ -4890,7 +4925,7 @@ PH_EXPORT int piper_hip_voice_profile(piper_hip_voice* v, int slot, int iters, p
     hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, s.set.stream, (unsigned long long)(100 * (1500 + 12 * n)));  // µs → ticks
     PH_HIP(hipEventRecord(ev[0], s.set.stream), PIPER_HIP_ERR_LAUNCH);
     for (int i = 0; i < n && !rc; i++) {
-      if (s.steps[i].kind == Step::LAUNCH) rc = s.steps[i].run(s.set.stream);
+      if (s.steps[i].kind == Step::LAUNCH) rc = s.steps[i].enqueue(s.set.stream);
       if (!rc && hipEventRecord(ev[i + 1], s.set.stream) != hipSuccess) rc = PIPER_HIP_ERR_LAUNCH;
     }
     if (rc) break;

@@ -209,6 +209,8 @@ _PROTOS = {
     "piper_hip_last_error": (C.c_char_p, []),
     "piper_hip_abi_version": (C.c_int, []),
     "piper_hip_config_string": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "piper_hip_routes_arm": (C.c_int, [c_vp, C.c_int]),
+    "piper_hip_last_routes": (C.c_int, [c_vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "piper_hip_device_count": (C.c_int, []),
     "piper_hip_create": (C.c_int, [C.c_int, C.POINTER(c_vp)]),
     "piper_hip_destroy": (None, [c_vp]),
@@ -480,6 +482,20 @@ class HipBackend:
         if self.ctx:
             self.lib.piper_hip_destroy(self.ctx)
             self.ctx = None
+
+    def arm_routes(self, on=True):
+        """Route records (include/piper_hip.h, piper_hip_routes_arm): while armed, every conv / ResBlock-pair / flow-seam / attention launcher
+        of this context notes which kernel variant it chose. Off by default. See last_routes() and HipRuntime.routes()."""
+        _check(self.lib.piper_hip_routes_arm(self.ctx, 1 if on else 0))
+
+    def last_routes(self):
+        """The route records of the last op call on this context, one "<variant> | <shape>" string per launch ([] when disarmed)."""
+        n = C.c_size_t()
+        _check(self.lib.piper_hip_last_routes(self.ctx, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(int(n.value), 1))
+        _check(self.lib.piper_hip_last_routes(self.ctx, buf, len(buf), None))
+        txt = buf.value.decode()
+        return txt.split("\n") if txt else []
 
     def __enter__(self):
         return self
@@ -1745,6 +1761,17 @@ class HipRuntime:
         of the generator window plan of the slot's latest stream step)."""
         raw = self.tap(slot, ("window:" if window else "predict:" if predict else "") + "@steps")
         return bytes(raw.astype(np.uint8)).decode().split("\n")[:-1]
+
+    def routes(self, slot, predict=False, window=False):
+        """[(step name, [route records])] of the slot's schedule, one entry per launch: what each step's launchers chose at its most recent
+        enqueue (HipBackend.arm_routes before the plan is prepared; a plan enqueued while disarmed has empty lists). predict / window as
+        for steps(). Runs nothing."""
+        raw = self.tap(slot, ("window:" if window else "predict:" if predict else "") + "@routes")
+        out = []
+        for line in bytes(raw.astype(np.uint8)).decode().split("\n")[:-1]:
+            name, _, recs = line.partition("\t")
+            out.append((name, recs.split("; ") if recs else []))
+        return out
 
     def last_gpu_ms(self, slot):
         ms = C.c_double()

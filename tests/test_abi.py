@@ -22,7 +22,8 @@ def header_symbols():
 def test_library_exports_every_declared_symbol():
     lib = ph.load_library()
     syms = header_symbols()
-    assert len(syms) >= 45
+    assert len(syms) >= 47
+    assert {"piper_hip_routes_arm", "piper_hip_last_routes"} <= set(syms)  # the route records: one entry point arms, one reads
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/piper_hip.h but not exported"
     # and the python shim binds exactly the declared set
@@ -104,6 +105,13 @@ def test_fails_loudly_without_gpu():
     p = C.c_void_p()
     assert lib.piper_hip_alloc(None, 16, C.byref(p)) == -7
     assert lib.piper_hip_unary_f32(None, 0, None, 4, 0.0, C.byref(p), None) == -7
+
+
+def test_route_record_entry_points_reject_a_null_context():
+    lib = ph.load_library()
+    n = C.c_size_t(7)
+    assert lib.piper_hip_routes_arm(None, 1) == -7 and b"null context" in lib.piper_hip_last_error()
+    assert lib.piper_hip_last_routes(None, None, 0, C.byref(n)) == -7 and n.value == 7
 
 
 def test_header_is_plain_c_and_links_from_c(tmp_path):

@@ -112,3 +112,21 @@ def test_planted_defects_fail_the_exact_check_and_pass_the_snr_bar(voices, chain
             return br.Bf16Ref.mean32(r0, r1, r1 if MeanDefect.stage == cfg.n_ups - 1 else r2)
     b = MeanDefect(cfg, blob).generator(z)["audio"]
     print(f"defect B (mean's third operand = r1, last stage): waveform SNR vs clean {snr_db(b, clean):.1f} dB")
+
+
+def test_a_mean_that_cancels_to_zero_keeps_its_error_bound(voices):
+    """Regression (profiles/conv_routes.md, Finding): three ResBlock outputs that cancel to exactly 0.0 in the reference's fp32 order — the
+    device, summing the last conv in another order, lands a few 1e-9 beside it. A zero has no binade, so round_amb gave it no allowance and
+    the image had to be 0 bit for bit. Its true value is known to ±err like every other element's: a value within err passes, nothing else."""
+    cfg, blob = voices["high"]
+    R = br.Bf16Ref(cfg, blob)
+    h32 = np.array([[0.0, 0.0, 0.5, 0.0]], np.float32)
+    err = np.array([[1e-5, 0.0, 1e-5, 1e-5]])
+    hb, cost = R.round_amb(h32, err)
+    assert np.array_equal(hb, h32)
+    assert 1e-5 <= cost[0, 0] <= 1.01e-5 + 2.0 ** -24 and cost[0, 1] == 0 and cost[0, 2] == 0 and cost[0, 3] == cost[0, 0]
+    unit = br.Unit(hb, cost, base=0.0)
+    assert unit.compare(np.array([[-3.987e-9, 0.0, 0.5, 9e-6]], np.float32))["ok"]       # what the device gave at the element found
+    assert not unit.compare(np.array([[0.0, 1e-9, 0.5, 0.0]], np.float32))["ok"]          # an exact zero (no error) stays exact
+    assert not unit.compare(np.array([[3.2e-5, 0.0, 0.5, 0.0]], np.float32))["ok"]        # and the allowance is err, not a bf16 ulp of the tensor
+    assert not unit.compare(np.array([[0.0, 0.0, 0.50390625, 0.0]], np.float32))["ok"]    # an unambiguous element one bf16 ulp off

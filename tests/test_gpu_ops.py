@@ -1,10 +1,13 @@
 """GPU parity tests proper: the HIP path through the C-ABI vs the oracle and the committed golden vectors.
 
 Mirrors how the reference would test MetalBackend per op (it has no such tests: SURVEY.md §4)."""
+import contextlib
+
 import numpy as np
 import pytest
 
 import att_ref
+import conv_ref as cr
 import katdata as kd
 import oracle as orc
 import piper_hip as ph
@@ -18,6 +21,27 @@ pytestmark = pytest.mark.gpu
 
 def up(b, a):
     return b.uploadFloat32(np.ascontiguousarray(a, np.float32))
+
+
+@contextlib.contextmanager
+def routes_armed(b):
+    """The shared backend reports which kernel variants its launchers choose (HipBackend.arm_routes) for the length of the block."""
+    b.arm_routes(True)
+    try:
+        yield
+    finally:
+        b.arm_routes(False)
+
+
+def assert_routes(b, family, what, **params):
+    """Every launch of the last op call took a kernel of `family` with these parameters — on 256 CUs; another CU count may choose otherwise."""
+    recs = b.last_routes()
+    assert recs, f"{what}: no route reported"
+    if cr.cus_of(recs) != 256:
+        return
+    for v in cr.variants(recs):
+        p = cr.params_of(v)
+        assert cr.family_of(v) == family and all(p.get(k) == str(x) for k, x in params.items()), f"{what}: wanted {family} {params}, ran {recs}"
 
 
 def dl(b, buf, shape):
@@ -341,11 +365,15 @@ def test_free_is_stream_ordered(backend):
         d.free()
 
 
-# Long rows take the LDS-tiled bulk kernel (conv_tile_kernel); the KAT table above only reaches the streaming kernel.
+# Long rows. These cases were written for the LDS-tiled bulk kernel (conv_tile_kernel); since it is kept for launches of at least four blocks per
+# CU with at most 64 output channels per block, none of them reaches it on 256 CUs (tests/test_gpu_conv_routes.py has cases that do). What
+# they take is asserted below: the ResBlock entry point's single convs and a row that is no multiple of 4 the streaming kernel, 16-byte rows
+# through conv1dF32 the window kernel, or the chunk-pipelined one where Cin % 32 == 0 and the contraction has two chunks.
 BULK_CONV = [  # (Cin, Cout, K, dil, L, lrelu)
     (32, 32, 7, 12, 20000, True), (32, 32, 3, 1, 16384 + 5, True), (64, 64, 5, 6, 9000, True), (64, 64, 11, 5, 9000, True),
     (128, 128, 7, 3, 6000, False), (256, 256, 3, 1, 4500, True), (32, 64, 1, 1, 20000, False), (48, 40, 5, 2, 20001, True),
 ]
+BULK_FAMILY = ["stream", "stream", "stream", "stream", "pipe", "stream", "win", "stream"]
 
 
 @pytest.mark.parametrize("case", BULK_CONV, ids=[f"c{c[0]}x{c[1]}_k{c[2]}_d{c[3]}_L{c[4]}" for c in BULK_CONV])
@@ -357,9 +385,12 @@ def test_conv1d_bulk(case, backend):
     b = kd.sym(sd + 2, (cout,), 0.1)
     pad = (k * d - d) // 2
     bk = backend
+    family = BULK_FAMILY[BULK_CONV.index(case)]
     if act:  # through the fused ResBlock entry point (LeakyReLU prologue + residual epilogue) when square
         if cin == cout:
-            out = bk.hifiganResblockF32(2, up(bk, x), 1, cin, L, k, [d], [up(bk, w)], [up(bk, b)], 0.1)
+            with routes_armed(bk):
+                out = bk.hifiganResblockF32(2, up(bk, x), 1, cin, L, k, [d], [up(bk, w)], [up(bk, b)], 0.1)
+                assert_routes(bk, family, str(case), K=k, pro="lrelu", res=1)
             ref = orc.hifigan_resblock(2, x, k, [d], [w], [b], 0.1)
             assert_close(bk.downloadFloat32(out), ref, OP_TOL)
             return
@@ -367,7 +398,9 @@ def test_conv1d_bulk(case, backend):
         x = orc.unary(ph.LEAKYRELU, x, 0.1)
     else:
         xa = up(bk, x)
-    out, shp = bk.conv1dF32(xa, list(x.shape), up(bk, w), list(w.shape), up(bk, b), dilation=d, padL=pad, padR=pad)
+    with routes_armed(bk):
+        out, shp = bk.conv1dF32(xa, list(x.shape), up(bk, w), list(w.shape), up(bk, b), dilation=d, padL=pad, padR=pad)
+        assert_routes(bk, family, str(case), K=k)
     assert_close(dl(bk, out, shp), orc.conv1d(x, w, b, 1, d, pad, pad, 1), OP_TOL)
 
 
@@ -437,8 +470,14 @@ def test_conv1d_long_rows_window_kernel(idx, backend):
     x = kd.sym(SD + 1200 + idx, (N, Cin, L))
     w = kd.weight(SD + 1250 + idx, (Cout, Cin, K), Cin * K)
     b = kd.sym(SD + 1290 + idx, (Cout,), 0.1) if has_b else None
-    out, shp = backend.conv1dF32(up(backend, x), list(x.shape), up(backend, w), list(w.shape),
-                                 None if b is None else up(backend, b), dilation=d, padL=pl, padR=pr)
+    with routes_armed(backend):
+        out, shp = backend.conv1dF32(up(backend, x), list(x.shape), up(backend, w), list(w.shape),
+                                     None if b is None else up(backend, b), dilation=d, padL=pl, padR=pr)
+        # What runs today, against the comments of katdata.CONV_WIN_CASES: conv_pipe has since taken every case whose Cin is a multiple of
+        # 32 (0 … 5 were written for the window kernel, whose only case left is 6; its K-split has cases in tests/test_gpu_conv_routes.py
+        # and the generator plans). Case 8's window (4 waves × 2 tiles × 32 + reach 8 + 6 columns) exceeds conv_pipe's 256: one tile per wave.
+        assert_routes(backend, "win" if idx == 6 else "pipe", f"conv1d window case {idx}", K=K,
+                      **{0: dict(WM=1, WN=4), 1: dict(WM=2, WN=2), 6: dict(KS=4), 8: dict(NTW=1), 9: dict(WM=2, WN=2, NTW=2), 10: dict(WM=2, WN=2)}.get(idx, {}))
     ref = orc.conv1d(x, w, b, 1, d, pl, pr)
     assert shp == list(ref.shape)
     assert_close(dl(backend, out, shp), ref, OP_TOL, f"conv1d window case {idx}")
@@ -451,8 +490,15 @@ def test_convtranspose1d_long_rows_window_kernel(idx, backend):
     x = kd.sym(SD + 1300 + idx, (N, Cin, L))
     w = kd.weight(SD + 1350 + idx, (Cin, Cout, K), Cin * K // s)
     b = kd.sym(SD + 1390 + idx, (Cout,), 0.1)
-    out, shp = backend.convTranspose1dF32(up(backend, x), list(x.shape), up(backend, w), list(w.shape), up(backend, b),
-                                          stride=s, padL=pad, padR=pad)
+    with routes_armed(backend):
+        out, shp = backend.convTranspose1dF32(up(backend, x), list(x.shape), up(backend, w), list(w.shape), up(backend, b),
+                                              stride=s, padL=pad, padR=pad)
+        # conv_pipe's ConvTranspose path runs on request only (test_convtranspose1d_chunk_pipelined_kernel_on_request). Case 7 (K 6, stride 3:
+        # K − stride is odd) is outside the window kernel's geometry: the streaming kernel's phase decomposition, two taps per phase.
+        if idx == 7:
+            assert_routes(backend, "stream", f"convT window case {idx}", K=2, kind="convT", epi="convt")
+        else:
+            assert_routes(backend, "win", f"convT window case {idx}", K=K, kind="convT")
     ref = orc.convtranspose1d(x, w, b, s, 1, pad, pad)
     assert shp == list(ref.shape)
     assert_close(dl(backend, out, shp), ref, OP_TOL, f"convT window case {idx}")
@@ -519,7 +565,12 @@ def test_hifigan_resblock_fused_pairs(case, backend):
     ws = [kd.weight(sd + 1 + i, (Cc, Cc, K), Cc * K) for i in range(nconv)]
     bs = [kd.sym(sd + 40 + i, (Cc,), 0.1) for i in range(nconv)]
     b = backend
-    out = b.hifiganResblockF32(type_, up(b, x), N, Cc, T, K, dils, [up(b, w) for w in ws], [up(b, v) for v in bs], 0.1)
+    with routes_armed(b):
+        out = b.hifiganResblockF32(type_, up(b, x), N, Cc, T, K, dils, [up(b, w) for w in ws], [up(b, v) for v in bs], 0.1)
+        recs = b.last_routes()
+        npairs = len(dils) if type_ == 1 else len(dils) // 2  # ResBlock2 with an odd count: the pairs, then a single conv
+        assert [cr.family_of(cr.variant_of(r)) for r in recs] == ["rb_pair"] * npairs + ["stream"] * (type_ == 2 and len(dils) % 2) or \
+            cr.cus_of(recs) != 256, recs
     got = b.downloadFloat32(out).reshape(N, Cc, T)
     for n in range(N):
         assert_close(got[n], orc.hifigan_resblock(type_, x[n:n + 1], K, dils, ws, bs)[0], OP_TOL, f"item {n} vs oracle")
