@@ -449,7 +449,8 @@ int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_utterance*
  * the waveform is what prepare_batch would have produced. Nothing waits for the GPU here. Until `collect`,
  * piper_hip_voice_prepared_samples reports the CAPACITY (n · bucket(max_frames) · hop) — the room `collect` needs — and afterwards the
  * true lengths; piper_hip_voice_durations answers after `collect`. An item whose prediction exceeds `max_frames` makes `collect` fail
- * with PIPER_HIP_ERR_SHAPE (prepare it again with a larger bound or through prepare_batch). */
+ * with PIPER_HIP_ERR_SHAPE (prepare it again with a larger bound or through prepare_batch) — unless the item carries a prosody with
+ * `fit` (piper_hip_voice_slot_prosody): then its durations are compressed to the bound on the device and it succeeds. */
 int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int max_frames);
 /* Plans (schedule + arena + HIP graph) are cached per voice by bucket — phonemes rounded up to 16, frames to 16 (64 beyond
  * 1024) — and batch size, least recently used first out, so a (T, F) never seen before usually finds its graph ready and
@@ -827,7 +828,9 @@ int piper_hip_voice_check_json_speakers(const piper_hip_voice_config* cfg, const
  *                        for the join's event — which the step's stream would have waited for anyway — and reads the frame count the
  *                        device reported. F ≤ max_frames: the row is an ordinary active row with that F; windows, emit rule per format
  *                        and history are those of any other row. F > max_frames: the row is free again and marked failed until it is
- *                        taken again; it never delivers, the other items of the join are unaffected and the step returns OK.
+ *                        taken again; it never delivers, the other items of the join are unaffected and the step returns OK. An item
+ *                        whose prosody asks for `fit` (piper_hip_voice_slot_prosody on the work slot) never gets there: its durations
+ *                        are compressed to max_frames on the device and the row resolves to an ordinary active row.
  *   Order                a bounded join is active from the next step on, like any join: the step waits for the joins made before it,
  *                        so the pool stays deterministic.
  *   stream_drop          on a row that is still pending frees it; the next join may take it (its adopt runs behind the pending one).
@@ -847,6 +850,60 @@ int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int slot, const
 int piper_hip_voice_stream_pool_item_samples(piper_hip_voice* v, int slot, int item, int64_t* samples);
 /* Joins of this pool whose front has not finished yet (hipEventQuery; never waits). ≥ 0, or a negative status. */
 int piper_hip_voice_stream_pool_joins_pending(piper_hip_voice* v, int slot);
+
+/* ---- Per-phoneme prosody: length, pause and noise control on every route (DESIGN.md §4 "Prosody") ----
+ * The three `scales` of PiperMetalRuntime.synthesize (PiperMetalRuntime.swift:62-80) shape a whole utterance. A TTS host also wants a pause
+ * after a clause (SSML <break>), a slower or faster word (<prosody rate>), a ceiling on one runaway duration of the stochastic predictor
+ * and a flatter or livelier word. All of these are per-phoneme-id controls on two things the library computes itself: the frames per id
+ * and the prior noise per frame; on the bounded routes neither ever reaches the host. The arithmetic is a contract; its integer part
+ * holds bit for bit:
+ *   w0 = fl(expf(logw) · length_scale)                        what the predictor's last step computes without prosody
+ *   w1 = fl(w0 · length[t])
+ *   c  = ceilf(w1);  d0 = c > 0 ? (c < 1e6 ? (int32)c : 1000000) : 0      NaN → 0
+ *   d1 = max_frames[t] > 0 ? min(d0, max_frames[t]) : d0
+ *   d  = max(d1, min_frames[t])                               ids past the item's length: 0
+ *   fit (bounded routes, fit ≠ 0):  S = Σ d in int64;  if S > cap:  d[t] = (int32)((int64)d[t] · cap / S)   (floor)
+ *         cap = the call's max_frames. Σ d ≤ cap follows. The bound is hard, so fitting may go below min_frames.
+ *         wanted = S, fitted = 1. Otherwise d is unchanged, wanted = S, fitted = 0.
+ *   then the rule of every route: the frame count is max(Σ d, 1), frame f belongs to the smallest t with cum[t] > f
+ *   ns[t] = fl(noise_scale · noise[t])
+ *   z_p[c][f] = m_p[c][t(f)] + fl(fl(nz[c][f] · expf(logs_p[c][t(f)])) · ns[t(f)])
+ * Multiplying by 1.0f is exact, so an all-neutral prosody (1.0 for length and noise, 0 for the frame fields, or NULL arrays) gives the
+ * result of the same request without prosody bit for bit. Without `fit` a bounded request over its bound fails as it does without prosody.
+ * A request that carries prosody runs plans of its own (step names "dp.affine_exp_ceil_prosody" and "expand_noise_prosody" in the places
+ * of "dp.affine_exp_ceil" and "expand_noise", the per-id arrays as plan inputs [NB][T] staged with the ids); a request without finds the
+ * plans, step lists, buffers and kernel arguments it found before these symbols existed. The predictor plan of a request with prosody
+ * keeps w0 as tap "dp.w" [1,T]; "dp.w.row" and "dp.dur.row" are the same buffer and "dp.dur" as whole bucket rows [T] per item, not
+ * compacted to the item's length: both are 0 past it. "predict:" selectors of piper_hip_voice_tap and piper_hip_voice_time_subset address
+ * the predictor plan the slot's last prepare ran. piper_hip_voice_predict_durations has no slot and ignores prosody. */
+typedef struct {
+  const float*   length;      /* [t] multiplier on the id's duration w; NULL = all 1.0 */
+  const int32_t* min_frames;  /* [t] floor on the id's frames (a pause: raise the blank after a word); NULL = all 0 */
+  const int32_t* max_frames;  /* [t] ceiling on the id's frames, 0 = none; NULL = none */
+  const float*   noise;       /* [t] multiplier on noise_scale for the frames of this id; NULL = all 1.0 */
+  int32_t t;                  /* entries of every non-NULL array; must equal the utterance's t */
+  int32_t fit;                /* bounded routes only: compress instead of failing when the frames exceed the call's max_frames */
+} piper_hip_prosody;          /* 40 bytes */
+/* Host-only. length and noise finite and in [0, 1000]; frame values in [0, 1 000 000]; max_frames[i] ≠ 0 requires min_frames[i] ≤
+ * max_frames[i]; t ≥ 1. Any violation is PIPER_HIP_ERR_ARG with a message naming the field and the index. */
+int piper_hip_prosody_check(const piper_hip_prosody* p);
+/* Host-only: the rule above from w0 [t] on. p may be NULL (neutral); p->t ≠ t is PIPER_HIP_ERR_SHAPE. Fitting happens when p->fit ≠ 0,
+ * cap > 0 and the total exceeds cap. frames_out [t]; *wanted (optional) = S. */
+int piper_hip_prosody_frames(const piper_hip_prosody* p, const float* w0, int32_t t, int64_t cap, int32_t* frames_out, int64_t* wanted);
+/* The prosody of the NEXT staging call on slot id `slot`: entry i is for item i; items past `n` have none. Staging calls are prepare,
+ * prepare_batch, prepare_batch_bounded, stream_begin, stream_begin_batch, synthesize* (slot 0) and stream_pool_join* (the slot is the
+ * work_slot). The staging call takes the assignment and clears it, whether or not it succeeds; the arrays are copied here, so the caller's
+ * memory may go away at once. n = 0 clears the assignment; n outside 0 … 256 is PIPER_HIP_ERR_ARG; every entry passes the checks of
+ * piper_hip_prosody_check here, on the host, with a message naming the entry, the field and the index.
+ * Checked by the staging call (a refused call stages nothing): t different from the item's t = PIPER_HIP_ERR_SHAPE; on an item with
+ * supplied durations any non-NULL length, min_frames or max_frames, or fit ≠ 0 = PIPER_HIP_ERR_ARG (the caller owns those durations; noise
+ * alone applies — which is also all a voice with dp_present = 0 can take); fit ≠ 0 on a route without a frame bound (prepare,
+ * prepare_batch, stream_begin*, the plain pool joins) = PIPER_HIP_ERR_ARG. */
+int piper_hip_voice_slot_prosody(piper_hip_voice* v, int slot, const piper_hip_prosody* items, int n);
+/* Where piper_hip_voice_durations answers (after prepare on the unbounded routes, after collect or the resolution of a bounded join on the
+ * others): per item the frames the rule wanted before fitting (S) and whether fitting happened. piper_hip_voice_durations reports the
+ * frames actually used, so the fitted ones. Either array may be NULL; at most max_items entries are written. */
+int piper_hip_voice_prosody_report(const piper_hip_voice* v, int slot, int64_t* wanted_frames, int32_t* fitted, int max_items);
 
 /* Debug taps ⇔ GraphExecutor.execute(maxNodeIndex:) returning intermediates (GraphExecutor.swift:75-152):
  * copy a named intermediate of the slot's last run to host. Names: "enc_out" [H,T], "m_p" [inter,T],
@@ -878,8 +935,10 @@ int piper_hip_voice_stream_pool_joins_pending(piper_hip_voice* v, int slot);
  *   "front.zflip" [inter,F] (the two buffers the halves of the flow's latent travel through), "front.h", "front.acts", "front.skip"
  *   [hidden,F]; of the duration predictor: "dp.a0", "dp.a1", "dp.cond" [hidden,T], "dp.hsp" [3·bins − 1,T], "dp.z" [2,T], "dp.logw" [1,T],
  *   "dp.dur" [1,T] (the int32 frames per id as raw bits).
- *   "predict:<tensor>[@<step>]"  addresses the cached encoder + duration-predictor plan of the slot's bucket T and batch size (the plan a
- *                            prepare without durations ran) with the slot's true lengths; PIPER_HIP_ERR_ARG when none is cached.
+ *   "predict:<tensor>[@<step>]"  addresses the encoder + duration-predictor plan the slot's last prepare ran, with the slot's true lengths:
+ *                            the plan a bounded prepare left attached to the slot id, else the one prepare_batch ran if the cache still
+ *                            holds it, else the first cached plan of the slot's form (with or without prosody), bucket T and batch size;
+ *                            PIPER_HIP_ERR_ARG when none is cached. Another request that has run the plan since has left its own values.
  *   "@steps"                 the schedule's launch names in order, one per line, one character code per float.
  *   "window:<tensor>"        on a slot that holds a single stream, a group or a streaming pool: the tensor in the generator window plan of
  *                            the slot's LATEST stream step. Items are that step's generator rows 0 … NBg − 1 (one for a single stream),
@@ -918,7 +977,9 @@ int piper_hip_voice_profile(piper_hip_voice* v, int slot, int iters, piper_hip_k
 /* Time a subset of the slot's schedule the way it runs in production: the launches whose name contains `name_filter`
  * ("" = all; "a|b|c" = the launches named exactly a, b or c) are captured into their own HIP graph and replayed `iters` times between two hipEvents on the slot's
  * stream. avg_launch_us = elapsed / (iters · n_launches) — kernel time plus the dispatch boundary, no per-kernel event
- * overhead; flops/bytes are the algorithmic totals of the subset (SURVEY.md Appendix A recipe). */
+ * overhead; flops/bytes are the algorithmic totals of the subset (SURVEY.md Appendix A recipe). A filter that starts with "predict:"
+ * times launches of the predictor plan the slot's last prepare ran instead (the plan piper_hip_voice_tap's "predict:" addresses;
+ * PIPER_HIP_ERR_ARG when none is cached). */
 int piper_hip_voice_time_subset(piper_hip_voice* v, int slot, const char* name_filter, int iters, double* avg_launch_us,
                                 int* n_launches, double* flops, double* bytes);
 

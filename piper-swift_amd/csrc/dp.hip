@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "dp_scalars.h"
 #include "rng.h"
 
 namespace ph {
@@ -288,12 +289,7 @@ __global__ __launch_bounds__(64 * kW) void dds_layer_kernel(const float* __restr
   PH_DSTAMP(6);
 }
 
-// per-item scalars of the predictor, in device memory so that a replayed graph sees new values
-struct DpScalars {
-  float noise_w, length_scale;
-  unsigned gen, seed;  // gen ≠ 0: draw the `dp` RandomNormalLike tensor on the device
-};
-
+// (DpScalars, dp_scalars.h: per-item scalars of the predictor, in device memory so that a replayed graph sees new values)
 // z [N][2][T] = noise·noise_w, rows already FLIPPED for the first ConvFlow (reverse pass: flip, then flow): row 0 ← noise row 1.
 __global__ __launch_bounds__(256) void dp_init_kernel(const float* __restrict__ noise, const DpScalars* __restrict__ sc, float* __restrict__ z, int T,
                                                      const int* __restrict__ len_ptr) {

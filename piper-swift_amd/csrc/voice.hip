@@ -51,6 +51,16 @@ int launch_dp_init(hipStream_t s, const float* noise, const void* scalars, float
 int launch_dp_spline(hipStream_t s, const float* h, float* z, int N, int T, int bins, float tail_bound, float filter_channels, const int* len_ptr);
 int launch_dp_final(hipStream_t s, const float* z, const float* m, const float* logs, const void* scalars, float* logw, int32_t* dur, int N, int T,
                     const int* len_ptr);
+// prosody.hip: the checks of one prosody record, and the three kernels a plan of a request with prosody runs in the place of dp_final_kernel,
+// dp_paths_kernel and expand_noise_kernel
+int prosody_check_item(const piper_hip_prosody* p, int item);
+size_t prosody_report_entries(int n, int T);
+int launch_dp_final_prosody(hipStream_t s, const float* z, const float* m, const float* logs, const void* scalars, const float* len, const int32_t* minf,
+                            const int32_t* maxf, float* logw, float* w0, int32_t* dur, int N, int T, const int* len_ptr);
+int launch_dp_paths_prosody(hipStream_t s, const int32_t* dur, const int* lensT, const int32_t* fit, int T, int F, int cap, int32_t* frame2id, int* lensF,
+                            int32_t* rep, int n);
+int launch_expand_noise_prosody(hipStream_t s, const float* stats, const int32_t* frame2id, const float* noise, const float* id_noise, float* zp,
+                                float* zp_tap, int NB, int I, int T, int F, const float* noise_scale, const unsigned* rng, const int* lensF);
 bool attention_block_eligible(int H, int d, int w, int T);
 bool attention_block_wanted();
 int launch_attention_block(piper_hip_ctx* ctx, hipStream_t s, const float* q, const float* k, const float* v, const float* ek, const float* ev,
@@ -303,6 +313,17 @@ struct Slot {
   piper_hip_speaker* spk_in = nullptr;
   float* spk_g = nullptr;
   float* spk_bias = nullptr;
+  // A plan of requests that carry prosody (piper_hip.h "Per-phoneme prosody") is a plan kind of its own: `pro` is part of its cache key
+  // next to (kind, T, F, NB), its schedule runs the _prosody steps and it owns the per-id inputs below, staged with the ids. A plan
+  // without (pro = false) has none of them. Predictor plan: pro_len, pro_min, pro_max [NB][T] and dp_w [NB][T] (the "dp.w" tap); the
+  // others: pro_noise [NB][T] and pro_fit [NB] (read by the bounded route's generate_path).
+  bool pro = false;
+  float *pro_len = nullptr, *pro_noise = nullptr, *dp_w = nullptr;
+  int32_t *pro_min = nullptr, *pro_max = nullptr, *pro_fit = nullptr;
+  std::vector<int64_t> h_wanted;  // per item: Σ d of the frame rule before fitting (piper_hip_voice_prosody_report), where h_dur answers
+  std::vector<int32_t> h_fitted;  // per item: the bounded route compressed it to its bound
+  const Slot* ran_predict = nullptr;  // the predictor plan the latest prepare_batch on this plan ran (null: none) — only ever compared
+                                      // against the plans in the cache ("predict:" selectors), never dereferenced
   float* audio = nullptr;
   int64_t n_samples = 0;
   std::vector<Step> steps;
@@ -469,7 +490,17 @@ struct piper_hip_voice {
     std::vector<hipEvent_t> chunk_ev;  // collect, 1 … 16 MB waveforms: one event per 1 MB chunk landed in h_audio
     piper_hip_speaker* h_spk = nullptr;  // the items' speakers of a prepare (a voice with a speaker table)
     size_t cap_spk = 0;
+    int32_t* h_pro = nullptr;  // the per-id prosody arrays of a prepare in bucket rows: length, min, max, noise [n][T] each, then fit [n]
+    size_t cap_pro = 0;
   } staging[kMaxSlots];
+  // The prosody of a slot id's NEXT staging call (piper_hip_voice_slot_prosody): owned copies of the caller's arrays, an empty array = the
+  // field was NULL. The staging call takes the assignment (take_prosody) whether or not it succeeds.
+  struct Prosody {
+    std::vector<float> length, noise;
+    std::vector<int32_t> min_frames, max_frames;
+    int t = 0, fit = 0;
+  };
+  std::vector<Prosody> slot_pro[kMaxSlots];
   // Speaker table of a multi-speaker voice (piper_hip_voice_attach_speakers; spk.S == 0: none): the device tables of speaker.hip, where an
   // item's speaker row keeps the dp.pre rows [0, spk_dp_rows), the flow's from there and the conv_pre rows from spk_pre_off, and each
   // slot id's assignment (empty: speaker 0 alone; items past the end take the last entry).
@@ -807,6 +838,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.rs = StreamRate();                                                         // (and the resampling history and descriptor)
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
+  s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
   for (void* p : s.owned) (void)v->ctx->pool.release(p);
   s.owned.clear();
   s.steps.clear();
@@ -1689,6 +1721,11 @@ const float* build_flow(Builder& b, const FrontBuffers& fb) {
     const float* nsd = s.noise_scale;
     const unsigned* rngd = s.rng;
     // path expansion counted as the reference's two MatMuls mm(1,F,192,T)
+    if (s.pro) {  // a plan of requests with prosody: the noise multiplier per id, read through frame2id (prosody.hip)
+      const float* idn = s.pro_noise;
+      b.step("expand_noise_prosody", "", NB * 2.0 * 2.0 * F * (double)I * T, NB * 2.0 * 4.0 * ((double)F * T + (double)T * I + (double)F * I),
+             [=](hipStream_t q) { return launch_expand_noise_prosody(q, stats, f2i, nz, idn, zp, zp_tap, NB, I, T, F, nsd, rngd, lensF); });
+    } else
     b.step("expand_noise", "", NB * 2.0 * 2.0 * F * (double)I * T, NB * 2.0 * 4.0 * ((double)F * T + (double)T * I + (double)F * I), [=](hipStream_t q) {
       const int grid = (int)std::min<int64_t>(ceil_div((int64_t)I * F, kBlock), 4096);
       hipLaunchKernelGGL(expand_noise_kernel, dim3(grid, NB), dim3(kBlock), 0, q, stats, f2i, nz, zp, zp_tap, I, T, F, nsd, rngd, lensF);
@@ -1849,7 +1886,23 @@ int build_duration_predictor(Builder& b, const float* x) {
   {
     const float *m = v->dp_m, *lg = v->dp_logs;
     int32_t* dur = s.dp_dur;
-    b.step("dp.affine_exp_ceil", "", 0, 0, [=](hipStream_t q) { return launch_dp_final(q, z, m, lg, sc, logw, dur, NB, T, lensT); });
+    if (s.pro) {  // a plan of requests with prosody: length, ceiling and floor per id, and w0 kept for the "dp.w" tap (prosody.hip)
+      s.pro_len = ar.f32(B * T);
+      s.pro_min = (int32_t*)ar.raw(B * T * sizeof(int32_t));
+      s.pro_max = (int32_t*)ar.raw(B * T * sizeof(int32_t));
+      s.dp_w = ar.f32(B * T);
+      if (ar.rc) return ar.rc;
+      const float* pl = s.pro_len;
+      const int32_t *pmin = s.pro_min, *pmax = s.pro_max;
+      float* w0 = s.dp_w;
+      b.step("dp.affine_exp_ceil_prosody", "", 0, 0,
+             [=](hipStream_t q) { return launch_dp_final_prosody(q, z, m, lg, sc, pl, pmin, pmax, logw, w0, dur, NB, T, lensT); });
+      b.tap("dp.w", s.dp_w, 1, T, 0);
+      // the same two buffers as whole bucket rows [T] per item (fixed length, not compacted): what lies past an item's length, which is 0
+      b.tap("dp.w.row", s.dp_w, 1, T, -1);
+      b.tap("dp.dur.row", (const float*)s.dp_dur, 1, T, -1);
+    } else
+      b.step("dp.affine_exp_ceil", "", 0, 0, [=](hipStream_t q) { return launch_dp_final(q, z, m, lg, sc, logw, dur, NB, T, lensT); });
   }
   b.tap("logw", logw, 1, T, 0);
   // the predictor's work buffers ("@<step>" selector); dp.dur holds the int32 frames per id as raw bits
@@ -1864,7 +1917,7 @@ int build_duration_predictor(Builder& b, const float* x) {
 }
 
 // Buffer planning, then the builders of what the plan's kind asks for at the voice's precision.
-int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind kind = PLAN_WHOLE) {
+int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind kind = PLAN_WHOLE, bool pro = false) {
   const piper_hip_voice_config& c = v->cfg;
   const int H = c.hidden, I = c.inter;
   slot_release(v, s, false);
@@ -1874,6 +1927,7 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind k
   if (c.n_rb != 3) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice: n_rb=%d (only the 3-kernel MRF of Piper voices is scheduled)", c.n_rb);
   s.T = T; s.F = F; s.NB = NB;
   s.kind = kind;
+  s.pro = pro && kind != PLAN_GENERATOR;  // (a window plan reads latents: nothing of the prosody reaches it)
   s.prec = v->precision;
   s.arena_bytes = 0;
   s.parallel = sw.parallel_rb;
@@ -1935,6 +1989,10 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind k
     fb.acts = ar.f32(B * (size_t)H * F);
     fb.skip = ar.f32(B * (size_t)H * F);
     dec0 = ar.f32(B * (size_t)c.up_initial * F);
+    if (s.pro && kind != PLAN_PREDICT) {  // (behind everything a plan without prosody allocates)
+      s.pro_noise = ar.f32(B * T);
+      s.pro_fit = (int32_t*)ar.raw(B * sizeof(int32_t));
+    }
     if (ar.rc) return ar.rc;
     s.stats = fb.stats;
     // The front half's work buffers as taps: reused layer after layer, so only meaningful with the "@<step>" selector of piper_hip_voice_tap.
@@ -2292,6 +2350,28 @@ PH_EXPORT int piper_hip_voice_slot_speakers(piper_hip_voice* v, int slot, const 
   return PIPER_HIP_OK;
 }
 
+// ---- prosody (piper_hip.h "Per-phoneme prosody") ----------------------------------------------------------------------------------
+PH_EXPORT int piper_hip_voice_slot_prosody(piper_hip_voice* v, int slot, const piper_hip_prosody* items, int n) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (n < 0 || n > 256 || (n > 0 && !items)) PH_FAIL(PIPER_HIP_ERR_ARG, "voice_slot_prosody: %d entries (0 … 256)", n);
+  for (int i = 0; i < n; i++)
+    if (int rc = prosody_check_item(&items[i], i)) return rc;  // (the assignment in place stays on a refusal)
+  std::vector<piper_hip_voice::Prosody> own((size_t)n);
+  for (int i = 0; i < n; i++) {  // the arrays are copied: the caller's memory may go away at once
+    const piper_hip_prosody& p = items[i];
+    piper_hip_voice::Prosody& o = own[i];
+    o.t = p.t;
+    o.fit = p.fit != 0;
+    if (p.length) o.length.assign(p.length, p.length + p.t);
+    if (p.min_frames) o.min_frames.assign(p.min_frames, p.min_frames + p.t);
+    if (p.max_frames) o.max_frames.assign(p.max_frames, p.max_frames + p.t);
+    if (p.noise) o.noise.assign(p.noise, p.noise + p.t);
+  }
+  v->slot_pro[slot].swap(own);
+  return PIPER_HIP_OK;
+}
+
 PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16)
@@ -2396,6 +2476,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_desc) (void)hipHostFree(sg.h_desc);
     if (sg.h_peaks) (void)hipHostFree(sg.h_peaks);
     if (sg.h_spk) (void)hipHostFree(sg.h_spk);
+    if (sg.h_pro) (void)hipHostFree(sg.h_pro);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
   for (auto& st : v->free_sets) destroy_set(st);
@@ -2426,6 +2507,23 @@ Slot* slot_plan(const piper_hip_voice* v, int slot) {
   if (!v || slot < 0 || slot >= kMaxSlots) return nullptr;
   Slot* p = v->attached[slot];
   return (p && p->built) ? p : nullptr;
+}
+
+// The encoder + predictor plan the "predict:" selectors address for the prepared plan `owner` of slot id `slot`: the plan the slot's last
+// prepare ran — the one a bounded prepare left attached to the slot id, else the one prepare_batch remembered if the cache still holds
+// it — and only then the first cached plan of the slot's form (with or without prosody), bucket T and batch size. Null: none is cached.
+Slot* predict_plan_of(piper_hip_voice* v, int slot, const Slot& owner) {
+  auto fits = [&](const Slot* p) {
+    return p && p->built && p->kind == PLAN_PREDICT && p->pro == owner.pro && p->T == owner.T && p->NB == owner.NB && p->prec == v->precision;
+  };
+  if (slot >= 0 && slot < kMaxSlots && fits(v->attached_dp[slot])) return v->attached_dp[slot];
+  Slot* first = nullptr;
+  for (auto& p : v->plans) {
+    if (!fits(p.get())) continue;
+    if (p.get() == owner.ran_predict) return p.get();
+    if (!first) first = p.get();
+  }
+  return first;
 }
 
 void evict_idle_plans(piper_hip_voice* v) {
@@ -2464,11 +2562,12 @@ int launch_plan(piper_hip_voice* v, Slot& s, hipStream_t on = nullptr) {
 
 // An idle plan for (kind, Tb, Fb, NB) at the voice's precision, built (schedule + arena; its graph follows its first run) if
 // the cache has none. *built reports whether this call paid for a build ("cold" prepare).
-int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot** out, bool* built) {
+// pro: the plan of requests that carry prosody — a kind of its own in the cache, never handed to a request without (and the other way round).
+int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot** out, bool* built, bool pro = false) {
   *built = false;
   v->planned = true;
   for (auto& p : v->plans)
-    if (!p->in_use && p->built && p->kind == kind && p->T == Tb && p->F == Fb && p->NB == NB && p->prec == v->precision) {
+    if (!p->in_use && p->built && p->kind == kind && p->pro == pro && p->T == Tb && p->F == Fb && p->NB == NB && p->prec == v->precision) {
       const int rc0 = slot_init(v, *p);  // a plan that went idle gave its stream set back (detach)
       if (rc0) return rc0;
       *out = p.get();
@@ -2486,7 +2585,7 @@ int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot
   int rc = slot_init(v, *np);
   if (rc) { slot_release(v, *np, true); return rc; }
   lap();
-  if ((rc = build_schedule(v, *np, Tb, Fb, NB, kind))) { slot_release(v, *np, true); return rc; }
+  if ((rc = build_schedule(v, *np, Tb, Fb, NB, kind, pro))) { slot_release(v, *np, true); return rc; }
   lap();
   Slot& s = *np;
   // a plan may be captured / profiled before every input has been uploaded: give the length arrays and index inputs legal values
@@ -2503,6 +2602,13 @@ int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot
     if (e == hipSuccess && s.spk_g) e = hipMemsetAsync(s.spk_g, 0, (size_t)NB * v->spk.gin * sizeof(float), s.set.stream);
     if (e == hipSuccess && s.spk_bias)
       e = hipMemsetAsync(s.spk_bias, 0, (size_t)NB * (kind == PLAN_GENERATOR ? v->cfg.up_initial : v->spk.Ctot) * sizeof(float), s.set.stream);
+    // prosody inputs: neutral (length and noise 1.0f, no floor, no ceiling, no fit)
+    const int one_bits = 0x3f800000;
+    if (e == hipSuccess && s.pro_len) e = hipMemsetD32Async((hipDeviceptr_t)s.pro_len, one_bits, (size_t)NB * Tb, s.set.stream);
+    if (e == hipSuccess && s.pro_noise) e = hipMemsetD32Async((hipDeviceptr_t)s.pro_noise, one_bits, (size_t)NB * Tb, s.set.stream);
+    if (e == hipSuccess && s.pro_min) e = hipMemsetAsync(s.pro_min, 0, (size_t)NB * Tb * sizeof(int32_t), s.set.stream);
+    if (e == hipSuccess && s.pro_max) e = hipMemsetAsync(s.pro_max, 0, (size_t)NB * Tb * sizeof(int32_t), s.set.stream);
+    if (e == hipSuccess && s.pro_fit) e = hipMemsetAsync(s.pro_fit, 0, (size_t)NB * sizeof(int32_t), s.set.stream);
     if (e == hipSuccess) e = stream_wait(s.set.stream);
     if (e != hipSuccess) { slot_release(v, s, true); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "voice_prepare: arena initialisation failed: %s", hipGetErrorString(e)); }
   }
@@ -2540,14 +2646,14 @@ void detach(piper_hip_voice* v, int slot) {
 
 // The plan of bucket (kind, T, F, NB) on slot id `slot`: the one attached already if it matches, otherwise the attached one is detached and
 // the bucket's plan is taken from the cache (or built) and attached. Then, if `evict`, idle plans beyond the cache's bounds go.
-int attach_plan(piper_hip_voice* v, int slot, PlanKind kind, int T, int F, int NB, Slot** out, bool evict = true) {
+int attach_plan(piper_hip_voice* v, int slot, PlanKind kind, int T, int F, int NB, Slot** out, bool evict = true, bool pro = false) {
   pool_close(v, slot);  // a prepare replaces what the slot id holds, a streaming pool included
   v->windows[slot] = WindowRecord();  // (and the record of its latest stream step)
   Slot* cur = v->attached[slot];
-  if (!(cur && cur->built && cur->kind == kind && cur->T == T && cur->F == F && cur->NB == NB && cur->prec == v->precision)) {
+  if (!(cur && cur->built && cur->kind == kind && cur->pro == pro && cur->T == T && cur->F == F && cur->NB == NB && cur->prec == v->precision)) {
     if (cur) detach(v, slot);
     bool built = false;
-    const int rc = acquire_plan(v, kind, T, F, NB, &cur, &built);
+    const int rc = acquire_plan(v, kind, T, F, NB, &cur, &built, pro);
     if (rc) return rc;
     cur->in_use = true;
     v->attached[slot] = cur;
@@ -2575,9 +2681,56 @@ int grow_pinned(Tp*& p, size_t& cap, size_t need, size_t min_cap = 1024) {
   cap = c;
   return PIPER_HIP_OK;
 }
+
+// ---- prosody (piper_hip.h "Per-phoneme prosody") ----
+using ProsodyItems = std::vector<piper_hip_voice::Prosody>;
+// A staging call takes the slot id's assignment, whether or not it goes on to succeed.
+ProsodyItems take_prosody(piper_hip_voice* v, int slot) {
+  ProsodyItems p;
+  if (v && slot >= 0 && slot < kMaxSlots) p.swap(v->slot_pro[slot]);
+  return p;
+}
+// The entry points that reach prepare* only behind refusals of their own clear the assignment on every way out.
+struct ProsodyClear {
+  piper_hip_voice* v;
+  int slot;
+  ~ProsodyClear() { (void)take_prosody(v, slot); }
+};
+// What a staging call checks before it stages anything. bounded: the route has a frame bound (fit is allowed).
+int check_prosody(const ProsodyItems& pro, const piper_hip_utterance* utts, int n, bool bounded) {
+  for (int b = 0; b < n && b < (int)pro.size(); b++) {
+    const auto& p = pro[b];
+    if (p.t != utts[b].t) PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: its prosody has %d entries, the utterance %d ids", b, p.t, utts[b].t);
+    if (utts[b].durations && (!p.length.empty() || !p.min_frames.empty() || !p.max_frames.empty() || p.fit))
+      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: durations are supplied, so length, min_frames, max_frames and fit of its prosody do not apply (the "
+                                 "caller owns those durations; noise alone applies)", b);
+    if (p.fit && !bounded)
+      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: prosody fit needs a frame bound (prepare_batch_bounded / stream_pool_join_bounded)", b);
+  }
+  return PIPER_HIP_OK;
+}
+// The per-id arrays of n items in bucket rows [n][T] (null: not wanted), neutral where an item or a field has none, and fit [n].
+void pack_prosody(const ProsodyItems& pro, int n, int T, float* len, int32_t* mn, int32_t* mx, float* noise, int32_t* fit) {
+  for (int b = 0; b < n; b++) {
+    const piper_hip_voice::Prosody* p = b < (int)pro.size() ? &pro[b] : nullptr;
+    for (int t = 0; t < T; t++) {
+      const size_t i = (size_t)b * T + t;
+      const bool in = p && t < p->t;
+      if (len) len[i] = in && !p->length.empty() ? p->length[t] : 1.0f;
+      if (mn) mn[i] = in && !p->min_frames.empty() ? p->min_frames[t] : 0;
+      if (mx) mx[i] = in && !p->max_frames.empty() ? p->max_frames[t] : 0;
+      if (noise) noise[i] = in && !p->noise.empty() ? p->noise[t] : 1.0f;
+    }
+    if (fit) fit[b] = p ? p->fit : 0;
+  }
+}
+// predict_impl on the predictor plan of requests with prosody (pro non-null), its per-id inputs staged with the ids
+int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
+                     const piper_hip_speaker* speakers, const ProsodyItems* pro);
 }
 
 PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot) {
+  const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
@@ -2585,6 +2738,9 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   int Tmax = 0, rc;
   int64_t Fmax = 0;
   std::vector<int> hT(n), hF(n);
+  const bool has_pro = !pro.empty();  // the request runs the plans of requests with prosody
+  if ((rc = check_prosody(pro, utts, n, false))) return rc;
+  std::vector<int64_t> wanted(n, -1);  // Σ d of the frame rule per item (there is no fitting on this route)
   // utterances without durations: run the text encoder + duration predictor first (its own cached plan), then continue with
   // the predicted frames per id exactly as if the caller had supplied them
   std::vector<piper_hip_utterance> resolved;
@@ -2609,13 +2765,15 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
       predicted.resize((size_t)total);
       std::vector<piper_hip_speaker> spk;  // the predictor is conditioned too: x = dp.pre(x) + dp.cond(g)
       for (int b = 0; b < n && v->spk.S; b++) spk.push_back(speaker_of(v, slot, b));
-      if ((rc = predict_impl(v, utts, n, predicted.data(), nullptr, (int)total, &dp_plan, spk.empty() ? nullptr : spk.data()))) return rc;
+      if ((rc = predict_impl_pro(v, utts, n, predicted.data(), nullptr, (int)total, &dp_plan, spk.empty() ? nullptr : spk.data(), has_pro ? &pro : nullptr)))
+        return rc;
       resolved.assign(utts, utts + n);
       int64_t off = 0;
       for (int b = 0; b < n; b++) {
         if (!resolved[b].durations) {
           int64_t F = 0;
           for (int t = 0; t < utts[b].t; t++) F += predicted[off + t];
+          wanted[b] = F;
           if (F < 1) predicted[off] = 1;  // Piper: y_lengths = clamp_min(Σ w_ceil, 1)
           resolved[b].durations = predicted.data() + off;
         }
@@ -2629,6 +2787,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     if ((rc = check_item(utts[b], b)) || (rc = utt_frames(v, utts[b], b, &Fb))) return rc;
     hT[b] = utts[b].t;
     hF[b] = (int)Fb;
+    if (wanted[b] < 0) wanted[b] = Fb;
     Tmax = std::max(Tmax, utts[b].t);
     Fmax = std::max(Fmax, Fb);
   }
@@ -2637,7 +2796,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   const PlanKind kind = (dp_plan && dp_plan->stats && dp_plan->T == T && dp_plan->NB == n) ? PLAN_FROM_STATS : PLAN_WHOLE;
   Slot* cur = nullptr;
-  if ((rc = attach_plan(v, slot, kind, T, F, n, &cur))) return rc;
+  if ((rc = attach_plan(v, slot, kind, T, F, n, &cur, true, has_pro))) return rc;
   Slot& s = *cur;
   const hipStream_t q = s.set.stream;
   s.last_use = ++v->use_clock;
@@ -2658,6 +2817,9 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   s.h_T = hT;
   s.h_F = hF;
   s.h_dur.clear();
+  s.h_wanted = wanted;
+  s.h_fitted.assign(n, 0);
+  s.ran_predict = dp_plan;
   // Everything that goes to the device leaves from page-locked memory of the slot id (the plan's stream was synchronised above): an
   // asynchronous copy from PAGEABLE memory makes the runtime pin (or stage) the caller's pages on the spot. The noise tensor is copied into
   // bucket rows here, on the host.
@@ -2671,6 +2833,13 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   unsigned* p_rng = (unsigned*)sg.h_misc;
   float* p_ns = (float*)(p_rng + 2 * (size_t)n);
   if ((rc = stage_speakers(v, slot, s, n, q))) return rc;
+  if (s.pro) {  // the noise multiplier per id, a plan input like the ids (no fitting on this route)
+    if ((rc = grow_pinned(sg.h_pro, sg.cap_pro, (size_t)n * T + n))) return rc;
+    pack_prosody(pro, n, T, nullptr, nullptr, nullptr, (float*)sg.h_pro, nullptr);
+    memset(sg.h_pro + (size_t)n * T, 0, (size_t)n * sizeof(int32_t));
+    PH_HIP(hipMemcpyAsync(s.pro_noise, sg.h_pro, (size_t)n * T * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipMemcpyAsync(s.pro_fit, sg.h_pro + (size_t)n * T, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  }
   pack_ids(utts, n, T, sg.h_ids);
   for (int b = 0; b < n; b++) {
     const piper_hip_utterance* u = &utts[b];
@@ -2768,6 +2937,8 @@ __global__ __launch_bounds__(256) void dp_paths_kernel(const int32_t* __restrict
 // the frames per item; the plan is the bucket of that bound and every kernel masks by the frame count the device decides. One stream carries
 // uploads → encoder + predictor → generate_path (dp_paths_kernel) → flow + generator; the host learns the lengths with the waveform (collect).
 PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int max_frames) {
+  const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
+  const bool has_pro = !pro.empty();
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
@@ -2782,22 +2953,23 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
                                  "on them): pass durations = noise = NULL (noise_mode DEVICE draws it on the device)", b);
     Tmax = std::max(Tmax, u.t);
   }
+  if ((rc = check_prosody(pro, utts, n, true))) return rc;
   const int T = bucket_t(Tmax), F = bucket_f(max_frames), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot* cur = nullptr;
-  if ((rc = attach_plan(v, slot, PLAN_FROM_STATS, T, F, n, &cur, false))) return rc;
+  if ((rc = attach_plan(v, slot, PLAN_FROM_STATS, T, F, n, &cur, false, has_pro))) return rc;
   Slot& s = *cur;
   s.last_use = ++v->use_clock;
   PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);  // the previous request of this slot id: its staging and its predictor plan are idle now
   Slot* dp = v->attached_dp[slot];
-  if (dp && !(dp->built && dp->T == T && dp->NB == n && dp->prec == v->precision)) {
+  if (dp && !(dp->built && dp->pro == has_pro && dp->T == T && dp->NB == n && dp->prec == v->precision)) {
     release_dp(v, slot);
     dp = nullptr;
   }
   if (!dp) {
     bool built = false;
-    if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &dp, &built))) return rc;
+    if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &dp, &built, has_pro))) return rc;
     dp->in_use = true;
     v->attached_dp[slot] = dp;
   }
@@ -2806,7 +2978,9 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   auto& sg = v->staging[slot];
   const size_t misc_bytes = (size_t)n * (sizeof(int) + 2 * sizeof(unsigned) + sizeof(float)) + dp_scalars_bytes(n);
   if ((rc = grow_pinned(sg.h_ids, sg.cap_t, (size_t)T * n)) || (rc = grow_pinned(sg.h_misc, sg.cap_misc, misc_bytes)) ||
-      (rc = grow_pinned(sg.h_dpn, sg.cap_dpn, (size_t)n * 2 * T)) || (rc = grow_pinned(sg.h_res, sg.cap_res, (size_t)n + (size_t)n * T)))
+      (rc = grow_pinned(sg.h_dpn, sg.cap_dpn, (size_t)n * 2 * T)) ||
+      (rc = grow_pinned(sg.h_res, sg.cap_res, has_pro ? prosody_report_entries(n, T) : (size_t)n + (size_t)n * T)) ||
+      (has_pro && (rc = grow_pinned(sg.h_pro, sg.cap_pro, (size_t)4 * n * T + n))))
     return rc;
   int* h_lens = (int*)sg.h_misc;
   unsigned* h_rng = (unsigned*)(h_lens + n);
@@ -2824,6 +2998,18 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   }
   const hipStream_t q = s.set.stream;
   if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q))) return rc;
+  if (has_pro) {  // the per-id arrays: plan inputs of the predictor plan (length, floor, ceiling) and of this one (noise, fit)
+    const size_t nT = (size_t)n * T;
+    float* h_len = (float*)sg.h_pro;
+    int32_t *h_min = sg.h_pro + nT, *h_max = sg.h_pro + 2 * nT, *h_fit = sg.h_pro + 4 * nT;
+    float* h_noise = (float*)(sg.h_pro + 3 * nT);
+    pack_prosody(pro, n, T, h_len, h_min, h_max, h_noise, h_fit);
+    PH_HIP(hipMemcpyAsync(dp->pro_len, h_len, nT * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipMemcpyAsync(dp->pro_min, h_min, nT * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipMemcpyAsync(dp->pro_max, h_max, nT * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipMemcpyAsync(s.pro_noise, h_noise, nT * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipMemcpyAsync(s.pro_fit, h_fit, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  }
   PH_HIP(hipMemcpyAsync(dp->ids, sg.h_ids, (size_t)n * T * sizeof(int64_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(dp->lensT, h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(dp->dp_noise, sg.h_dpn, (size_t)n * 2 * T * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
@@ -2838,13 +3024,19 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   int32_t* rep = nullptr;
   if (hipHostGetDevicePointer((void**)&rep, sg.h_res, 0) != hipSuccess) { rep = nullptr; (void)hipGetLastError(); }
   if (!rep) PH_FAIL(PIPER_HIP_ERR_UNAVAILABLE, "prepare_batch_bounded: page-locked memory has no device mapping on this system");
-  hipLaunchKernelGGL(dp_paths_kernel, dim3(n), dim3(256), 0, q, dp->dp_dur, dp->lensT, T, F, std::min(max_frames, F), s.frame2id, s.lensF, rep, n);
+  if (has_pro) {  // generate_path with the fit step (prosody.hip), in the place of dp_paths_kernel
+    if ((rc = launch_dp_paths_prosody(q, dp->dp_dur, dp->lensT, s.pro_fit, T, F, std::min(max_frames, F), s.frame2id, s.lensF, rep, n))) return rc;
+  } else
+    hipLaunchKernelGGL(dp_paths_kernel, dim3(n), dim3(256), 0, q, dp->dp_dur, dp->lensT, T, F, std::min(max_frames, F), s.frame2id, s.lensF, rep, n);
   PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
   reset_stream_state(s);
   s.h_T.assign(n, 0);
   for (int b = 0; b < n; b++) s.h_T[b] = utts[b].t;
   s.h_F.assign(n, F);  // capacity until collect has the device's answer
   s.h_dur.clear();
+  s.h_wanted.clear();
+  s.h_fitted.clear();
+  s.ran_predict = nullptr;  // (the predictor plan stays attached to the slot id: attached_dp)
   s.bounded_pending = true;
   s.bounded_cap = std::min(max_frames, F);
   s.timed = false;
@@ -2873,10 +3065,16 @@ int bounded_finish(piper_hip_voice* v, int slot, Slot& s) {
   const auto& sg = v->staging[slot];
   s.bounded_pending = false;
   s.h_dur.clear();
+  s.h_wanted.assign(s.NB, 0);
+  s.h_fitted.assign(s.NB, 0);
+  // a plan of requests with prosody: behind the durations, the fitted flags and the totals before fitting (dp_paths_prosody_kernel)
+  const int32_t* tail = s.pro ? sg.h_res + s.NB + (size_t)s.NB * s.T : nullptr;
   int over = -1;
   for (int b = 0; b < s.NB; b++) {
     const int want = sg.h_res[b];
     if (want < 1) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "bounded utterance %d: the device reported no frame count (was the slot launched?)", b);
+    s.h_wanted[b] = tail ? (int64_t)(((uint64_t)(uint32_t)tail[s.NB + 2 * b + 1] << 32) | (uint32_t)tail[s.NB + 2 * b]) : want;
+    s.h_fitted[b] = tail ? tail[b] : 0;
     if (want > s.bounded_cap && over < 0) over = b;
     s.h_F[b] = std::min(want, s.bounded_cap);
     const int32_t* d = sg.h_res + s.NB + (size_t)b * s.T;
@@ -2919,6 +3117,10 @@ namespace {
 // speakers (optional): [n], one per utterance, checked by the caller; null on a voice with a table = speaker 0 alone
 int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
                  const piper_hip_speaker* speakers) {
+  return predict_impl_pro(v, utts, n, durations_out, logw_out, max_entries, plan_out, speakers, nullptr);
+}
+int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
+                     const piper_hip_speaker* speakers, const ProsodyItems* pro) {
   if (!v || !utts || !durations_out) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0)");
@@ -2942,10 +3144,13 @@ int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int
   const int T = bucket_t(Tmax);
   Slot* pl = nullptr;
   bool built = false;
-  if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &pl, &built))) return rc;
+  if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &pl, &built, pro != nullptr))) return rc;
   Slot& s = *pl;
   s.in_use = true;
   s.last_use = ++v->use_clock;
+  std::vector<float> plen(pro ? (size_t)n * T : 0);
+  std::vector<int32_t> pmin(plen.size()), pmax(plen.size());
+  if (pro) pack_prosody(*pro, n, T, plen.data(), pmin.data(), pmax.data(), nullptr, nullptr);
   std::vector<int64_t> ids((size_t)n * T);
   std::vector<int> lens(n);
   std::vector<float> nz((size_t)n * 2 * T);
@@ -2958,6 +3163,9 @@ int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int
   if (e == hipSuccess) e = hipMemcpyAsync(s.dp_noise, nz.data(), nz.size() * sizeof(float), hipMemcpyHostToDevice, s.set.stream);
   if (e == hipSuccess) e = hipMemcpyAsync(s.dp_scalars, sc.data(), sc.size(), hipMemcpyHostToDevice, s.set.stream);
   if (e == hipSuccess && s.spk_in) e = hipMemcpyAsync(s.spk_in, spk.data(), spk.size() * sizeof(piper_hip_speaker), hipMemcpyHostToDevice, s.set.stream);
+  if (e == hipSuccess && pro) e = hipMemcpyAsync(s.pro_len, plen.data(), plen.size() * sizeof(float), hipMemcpyHostToDevice, s.set.stream);
+  if (e == hipSuccess && pro) e = hipMemcpyAsync(s.pro_min, pmin.data(), pmin.size() * sizeof(int32_t), hipMemcpyHostToDevice, s.set.stream);
+  if (e == hipSuccess && pro) e = hipMemcpyAsync(s.pro_max, pmax.data(), pmax.size() * sizeof(int32_t), hipMemcpyHostToDevice, s.set.stream);
   if (e == hipSuccess && launch_plan(v, s)) e = hipErrorUnknown;
   std::vector<int32_t> dur((size_t)n * T);
   std::vector<float> lw(logw_out ? (size_t)n * T : 0);
@@ -2998,6 +3206,18 @@ PH_EXPORT int piper_hip_voice_durations(const piper_hip_voice* v, int slot, int3
   if (out) {
     if (max_entries < (int)p->h_dur.size()) PH_FAIL(PIPER_HIP_ERR_SHAPE, "durations: buffer too small");
     memcpy(out, p->h_dur.data(), p->h_dur.size() * sizeof(int32_t));
+  }
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_prosody_report(const piper_hip_voice* v, int slot, int64_t* wanted_frames, int32_t* fitted, int max_items) {
+  const Slot* p = slot_plan(v, slot);
+  if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
+  if (p->bounded_pending || (int)p->h_wanted.size() != p->NB)
+    PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "prosody_report: the slot's frame counts are still on the device (collect first)");
+  for (int b = 0; b < p->NB && b < max_items; b++) {
+    if (wanted_frames) wanted_frames[b] = p->h_wanted[b];
+    if (fitted) fitted[b] = p->h_fitted[b];
   }
   return PIPER_HIP_OK;
 }
@@ -3264,6 +3484,7 @@ int launch_front(Slot& s) {
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_utterance* u, int slot, int chunk_frames) {
+  const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
   if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin: chunk_frames must be >= 1");
   int rc = piper_hip_voice_prepare(v, u, slot);
   if (rc < 0) return rc;
@@ -3978,6 +4199,7 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, in
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames) {
+  const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: group of %d outside [1,%d]", n, kMaxGroup);
   if (int rc = check_step_size(v, "stream_begin_batch", n, chunk_frames)) return rc;
@@ -4101,6 +4323,7 @@ int launch_front_async(Slot& s) {
 // rows are pending until pool_resolve; nothing below waits for the GPU then, but for the two waits the header names.
 int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot, const piper_hip_stream_format* fmts,
               bool with_formats, int* items_out, int64_t* samples_out, int bound = 0) {
+  const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
   if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
@@ -4254,6 +4477,7 @@ PH_EXPORT int piper_hip_voice_stream_pool_join_formats(piper_hip_voice* v, int s
 
 PH_EXPORT int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
                                                        int max_frames, const piper_hip_stream_format* fmts, int* items_out) {
+  const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   // prepare_batch_bounded's own refusals, before anything of the pool is looked at or regrown (it repeats them)
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join_bounded: %d items outside [1,256]", n);
@@ -4415,6 +4639,7 @@ PH_EXPORT int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* p
 
 PH_EXPORT int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int16_t* host_pcm,
                                                int64_t max_samples, int64_t* n_samples) {
+  const ProsodyClear pc{v, 0};  // a staging call on slot 0
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   float gain;
   bool normalize;
@@ -4429,6 +4654,7 @@ PH_EXPORT int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_h
 
 PH_EXPORT int piper_hip_voice_synthesize_pcm16_rate(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params,
                                                     int32_t out_rate, int16_t* host_pcm, int64_t max_samples, int64_t* n_samples) {
+  const ProsodyClear pc{v, 0};  // a staging call on slot 0
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   float gain;
   bool normalize;
@@ -4716,6 +4942,7 @@ PH_EXPORT int piper_hip_voice_collect_g711(piper_hip_voice* v, int slot, const p
 
 PH_EXPORT int piper_hip_voice_synthesize_g711(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int law,
                                               int32_t out_rate, uint8_t* host, int64_t max_samples, int64_t* n_samples) {
+  const ProsodyClear pc{v, 0};  // a staging call on slot 0
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   float gain;
   bool normalize;
@@ -4787,9 +5014,7 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
   Slot* tp = sp;
   if (!win && full.compare(0, 8, "predict:") == 0) {  // the cached encoder + predictor plan of the slot's bucket T and batch size
     full.erase(0, 8);
-    tp = nullptr;
-    for (auto& p : v->plans)
-      if (p->built && p->kind == PLAN_PREDICT && p->T == owner.T && p->NB == owner.NB && p->prec == v->precision) { tp = p.get(); break; }
+    tp = predict_plan_of(v, slot, owner);
     if (!tp) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': no predictor plan of %d ids x %d items is cached", name, owner.T, owner.NB);
   }
   Slot& s = *tp;
@@ -4979,6 +5204,15 @@ PH_EXPORT int piper_hip_voice_time_subset(piper_hip_voice* v, int slot, const ch
   Slot* sp = slot_plan(v, slot);
   if (!sp) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
   if (iters < 1) iters = 1;
+  if (strncmp(name_filter, "predict:", 8) == 0) {  // the predictor plan the slot's last prepare ran, as for piper_hip_voice_tap
+    name_filter += 8;
+    Slot* tp = predict_plan_of(v, slot, *sp);
+    if (!tp) PH_FAIL(PIPER_HIP_ERR_ARG, "time_subset: no predictor plan of %d ids x %d items is cached", sp->T, sp->NB);
+    PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+    PH_HIP(stream_wait(sp->set.stream), PIPER_HIP_ERR_LAUNCH);  // (a bounded prepare ran it on the slot's stream)
+    if (int rc0 = slot_init(v, *tp)) return rc0;                 // an idle plan has given its stream set back
+    sp = tp;
+  }
   Slot& s = *sp;
   std::vector<int> pick;
   double fl = 0, by = 0;

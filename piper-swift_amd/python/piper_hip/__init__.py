@@ -139,6 +139,47 @@ def _speakers(speakers):
     return (Speaker * len(speakers))(*[_speaker(s) for s in speakers])
 
 
+class Prosody(C.Structure):
+    """piper_hip_prosody (40 bytes): per-id multipliers on the duration and on noise_scale, a floor and a ceiling on the id's frames (NULL =
+    neutral), the number of ids, and `fit` (bounded routes: compress to the bound instead of failing)."""
+    _fields_ = [("length", c_f32p), ("min_frames", c_i32p), ("max_frames", c_i32p), ("noise", c_f32p), ("t", C.c_int32), ("fit", C.c_int32)]
+
+
+def _prosody(p, t=None):
+    """None → the neutral record of t ids; a dict(length=, min_frames=, max_frames=, noise=, fit=) of arrays (a missing or None field is
+    neutral; t = the arrays' length, else `t`); a Prosody is passed through. Returns (record, the arrays that must outlive the call)."""
+    if isinstance(p, Prosody):
+        return p, ()
+    p = dict(p or {})
+    arrs = {k: (None if p.get(k) is None else np.ascontiguousarray(p[k], dt))
+            for k, dt in (("length", np.float32), ("min_frames", np.int32), ("max_frames", np.int32), ("noise", np.float32))}
+    sizes = [a.size for a in arrs.values() if a is not None]
+    n = int(p["t"]) if p.get("t") is not None else (sizes[0] if sizes else int(t or 0))
+    if any(s != n for s in sizes):
+        raise InvalidArgument("prosody: arrays of %s entries, t = %d" % (sorted(set(sizes)), n))
+    rec = Prosody(*[None if arrs[k] is None else arrs[k].ctypes.data_as(c_f32p if arrs[k].dtype == np.float32 else c_i32p)
+                    for k in ("length", "min_frames", "max_frames", "noise")], n, int(p.get("fit") or 0))
+    return rec, tuple(arrs.values())
+
+
+def prosody_check(p):
+    """piper_hip_prosody_check: raises InvalidArgument naming the field and the index of the first violation."""
+    rec, _keep = _prosody(p)
+    _check(load_library().piper_hip_prosody_check(C.byref(rec)))
+
+
+def prosody_frames(p, w0, cap=0):
+    """piper_hip_prosody_frames: the integer frame rule from w0 = exp(logw)·length_scale on (host only). Returns (frames int32 [t], wanted):
+    wanted = Σ frames before fitting; fitting happens with p's fit, cap > 0 and wanted > cap."""
+    w0 = np.ascontiguousarray(w0, np.float32)
+    rec, _keep = (None, ()) if p is None else _prosody(p, w0.size)
+    out = np.empty(w0.size, np.int32)
+    wanted = C.c_int64()
+    _check(load_library().piper_hip_prosody_frames(None if rec is None else C.byref(rec), w0.ctypes.data_as(c_f32p), w0.size, int(cap),
+                                                   out.ctypes.data_as(c_i32p), C.byref(wanted)))
+    return out, int(wanted.value)
+
+
 class PcmParams(C.Structure):
     """piper_hip_pcm_params: linear gain (0 = 1.0) and the peak-normalisation flag of the 16-bit PCM entry points."""
     _fields_ = [("gain", C.c_float), ("normalize", C.c_int32)]
@@ -381,6 +422,10 @@ _PROTOS = {
                                                            C.POINTER(C.c_int)]),
     "piper_hip_voice_stream_pool_item_samples": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "piper_hip_voice_stream_pool_joins_pending": (C.c_int, [c_vp, C.c_int]),
+    "piper_hip_prosody_check": (C.c_int, [C.POINTER(Prosody)]),
+    "piper_hip_prosody_frames": (C.c_int, [C.POINTER(Prosody), c_f32p, C.c_int32, C.c_int64, c_i32p, C.POINTER(C.c_int64)]),
+    "piper_hip_voice_slot_prosody": (C.c_int, [c_vp, C.c_int, C.POINTER(Prosody), C.c_int]),
+    "piper_hip_voice_prosody_report": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_int64), c_i32p, C.c_int]),
 }
 
 _lib = None
@@ -1160,7 +1205,7 @@ class StreamPool:
         self.rate = int(rate)
         self._buf = np.empty((self.rt.stream_step_capacity(self.slot) + 1) // 2, np.float32)
 
-    def join(self, utterances, noiseScale=0.667, formats=None):
+    def join(self, utterances, noiseScale=0.667, formats=None, prosody=None):
         """utterances as for synthesize_stream_batch: (phonemeIDs, durations-or-None, noise-or-None[, dict]). Returns [(item, samples)]:
         the row each session took and the samples it will deliver in all. Active from the next step().
         formats (a mixed pool): one StreamFormat (or dict of stream_format's arguments, or None) per utterance
@@ -1175,10 +1220,14 @@ class StreamPool:
             keep.append(k)
         items = (C.c_int * max(n, 1))()
         samples = (C.c_int64 * max(n, 1))()
+        fa = None
         if formats is not None:
             if len(formats) != n:
                 raise InvalidArgument("join: %d formats for %d utterances" % (len(formats), n))
             fa = _formats(formats)
+        # one entry per utterance, as for slot_prosody; staged behind every refusal made here, so that the join below is what takes it
+        rt._stage_prosody(self.work_slot, prosody, [len(u[0]) for u in utterances])
+        if fa is not None:
             _check(rt.lib.piper_hip_voice_stream_pool_join_formats(rt.voice, self.slot, arr, n, self.work_slot, fa, items, samples))
         else:
             _check(rt.lib.piper_hip_voice_stream_pool_join(rt.voice, self.slot, arr, n, self.work_slot, items, samples))
@@ -1191,7 +1240,7 @@ class StreamPool:
                 self._buf = np.empty((need + 3) // 4, np.float32)
         return [(int(items[i]), int(samples[i])) for i in range(n)]
 
-    def join_bounded(self, utterances, max_frames, noiseScale=0.667, formats=None):
+    def join_bounded(self, utterances, max_frames, noiseScale=0.667, formats=None, prosody=None):
         """join() for utterances whose durations are predicted, without the host round trip (piper_hip_voice_stream_pool_join_bounded):
         at most max_frames frames per item, durations and noise None (the dict's noise_mode="device" draws the noise on the device).
         Nothing waits for the GPU. Returns [item, ...], the rows taken; item_samples(item) tells what each will deliver once its length
@@ -1210,6 +1259,7 @@ class StreamPool:
             if len(formats) != n:
                 raise InvalidArgument("join_bounded: %d formats for %d utterances" % (len(formats), n))
             fa = _formats(formats)
+        rt._stage_prosody(self.work_slot, prosody, [len(u[0]) for u in utterances])  # one entry per utterance; fit=1 compresses to max_frames
         _check(rt.lib.piper_hip_voice_stream_pool_join_bounded(rt.voice, self.slot, arr, n, self.work_slot, int(max_frames), fa, items))
         rt._keep.pop(self.work_slot, None)  # the inputs were copied before the call returned
         if self.mixed:
@@ -1330,6 +1380,33 @@ class HipRuntime:
         arr = _speakers(speakers) if speakers else None
         _check(self.lib.piper_hip_voice_slot_speakers(self.voice, int(slot), arr, len(speakers)))
 
+    def slot_prosody(self, slot, items, ts=None):
+        """The prosody of the NEXT staging call on the slot id (piper_hip_voice_slot_prosody): entry i for item i, each a
+        dict(length=, min_frames=, max_frames=, noise=, fit=), a Prosody, or None (neutral: needs ts[i], the item's number of ids). The
+        library copies the arrays; the staging call takes the assignment whether or not it succeeds. None or [] clears it."""
+        items = list(items or [])
+        recs, keep = [], []
+        for i, p in enumerate(items):
+            r, k = _prosody(p, None if ts is None else ts[i])
+            recs.append(r)
+            keep.append(k)
+        arr = (Prosody * len(recs))(*recs) if recs else None
+        _check(self.lib.piper_hip_voice_slot_prosody(self.voice, int(slot), arr, len(recs)))
+
+    def _stage_prosody(self, slot, prosody, ts):
+        """The `prosody=` keyword of the staging methods: one entry per utterance (None entries neutral), or None for a request without."""
+        if prosody is not None:
+            self.slot_prosody(slot, prosody, ts)
+
+    def prosody_report(self, slot):
+        """Per item of the slot: (frames the rule wanted before fitting, fitted?) — piper_hip_voice_prosody_report; answers where
+        durations() answers."""
+        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
+        wanted = (C.c_int64 * max(nb, 1))()
+        fitted = (C.c_int32 * max(nb, 1))()
+        _check(self.lib.piper_hip_voice_prosody_report(self.voice, int(slot), wanted, fitted, nb))
+        return [int(x) for x in wanted[:nb]], [int(x) for x in fitted[:nb]]
+
     def set_precision(self, precision):
         """"f32" (default, the parity configuration) or "bf16" (generator convs on bf16 operands, fp32 accumulate)."""
         code = {"f32": 0, "fp32": 0, "bf16": 1}.get(precision, precision)
@@ -1352,7 +1429,7 @@ class HipRuntime:
         u, _k = self._utt(ids, durations, None, 0.0)
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
-    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, **kw):
+    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
         reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
         speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays."""
@@ -1360,21 +1437,24 @@ class HipRuntime:
             self.slot_speakers(0, [speaker])
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
+            self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
             n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
             out = np.empty(max(n, 1), np.float32)
             got = C.c_int64()
             _check(self.lib.piper_hip_voice_synthesize(self.voice, C.byref(u), out.ctypes.data_as(c_f32p), n, C.byref(got)))
             self._keep.pop(0, None)
             return out[:got.value]
-        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, **kw)
+        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, **kw)
         self.launch(0)
         return self.collect(0)
 
     def prepare(self, slot, phonemeIDs, durations=None, noise=None, noiseScale=0.667, noise_mode="injected", seed=1234, length_scale=1.0,
-                noise_w=0.8, dp_noise=None, max_frames=None):
+                noise_w=0.8, dp_noise=None, max_frames=None, prosody=None):
         """max_frames (durations must be None): predicted durations WITHOUT the host round trip — the plan is the bucket of that bound and the
-        frame count stays on the device until collect (piper_hip_voice_prepare_batch_bounded)."""
+        frame count stays on the device until collect (piper_hip_voice_prepare_batch_bounded).
+        prosody: the item's per-id prosody (slot_prosody), a dict(length=, min_frames=, max_frames=, noise=, fit=) or a Prosody."""
         u, k = self._utt(phonemeIDs, durations, noise, noiseScale, noise_mode, seed, length_scale, noise_w, dp_noise)
+        self._stage_prosody(slot, None if prosody is None else [prosody], [len(phonemeIDs)])
         if max_frames is not None:
             rc = self.lib.piper_hip_voice_prepare_batch_bounded(self.voice, C.byref(u), 1, slot, int(max_frames))
         else:
@@ -1386,8 +1466,10 @@ class HipRuntime:
         self._keep[slot] = (k, int(tot.value), max_frames is not None)
         return rc
 
-    def prepare_batch_bounded(self, slot, utterances, max_frames, noiseScale=0.667, noise_mode="device", seed=1234, length_scale=1.0, noise_w=0.8):
-        """utterances: list of (phonemeIDs, dp_noise-or-None); durations predicted on the device, at most max_frames frames per item."""
+    def prepare_batch_bounded(self, slot, utterances, max_frames, noiseScale=0.667, noise_mode="device", seed=1234, length_scale=1.0, noise_w=0.8,
+                              prosody=None):
+        """utterances: list of (phonemeIDs, dp_noise-or-None); durations predicted on the device, at most max_frames frames per item.
+        prosody: one entry per utterance (None entries neutral), as for slot_prosody; an entry's fit=1 compresses an item over the bound."""
         n = len(utterances)
         arr = (Utterance * n)()
         keep = []
@@ -1395,6 +1477,7 @@ class HipRuntime:
             u, k = self._utt(ids, None, None, noiseScale, noise_mode, seed, length_scale, noise_w, dpn)
             arr[i] = u
             keep.append(k)
+        self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
         rc = self.lib.piper_hip_voice_prepare_batch_bounded(self.voice, arr, n, slot, int(max_frames))
         if rc < 0:
             _check(rc)
@@ -1472,12 +1555,14 @@ class HipRuntime:
         return _count(self.lib.piper_hip_voice_stream_step_capacity_bytes(self.voice, slot))
 
     def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None,
-                          encoding=None):
+                          encoding=None, prosody=None):
         """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
+        prosody: the utterance's per-id prosody, as for prepare.
         pcm=True: int16 chunks converted on the device (piper_hip_voice_stream_next_pcm16), scaled by `gain`. rate: int16 chunks at that
         output rate (stream_set_rate; implies pcm). encoding "mulaw" / "alaw": uint8 chunks of G.711 bytes instead of int16
         (piper_hip_voice_stream_next_g711), at `rate` or the voice's own."""
         u, keep = self._utt(phonemeIDs, durations, noise, noiseScale)
+        self._stage_prosody(slot, None if prosody is None else [prosody], [len(phonemeIDs)])
         n_chunks = self.lib.piper_hip_voice_stream_begin(self.voice, C.byref(u), slot, int(chunkFrames))
         if n_chunks < 0:
             _check(n_chunks)
@@ -1503,8 +1588,9 @@ class HipRuntime:
             yield buf[:got.value].copy()
 
     def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None, encoding=None,
-                                formats=None):
-        """Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
+                                formats=None, prosody=None):
+        """prosody: one entry per utterance (None entries neutral), as for slot_prosody.
+        Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
         arrays — the next chunk of every item, empty once the item is finished or dropped (stream_drop). pcm=True: int16 chunks converted on
         the device (piper_hip_voice_stream_next_batch_pcm16), scaled by `gain`. rate: int16 chunks at that output rate (implies pcm).
@@ -1519,6 +1605,7 @@ class HipRuntime:
             u, k = self._utt(ids, dur, noise, noiseScale, **(item[3] if len(item) > 3 else {}))
             arr[i] = u
             keep.append(k)
+        self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
@@ -1579,16 +1666,19 @@ class HipRuntime:
             pool.set_mixed()
         return pool
 
-    def prepare_batch(self, slot, utterances, noiseScale=0.667):
-        """utterances: list of (phonemeIDs, durations, noise-or-None); lengths may differ (ragged batch, one bucket)."""
+    def prepare_batch(self, slot, utterances, noiseScale=0.667, prosody=None):
+        """utterances: list of (phonemeIDs, durations, noise-or-None[, dict of noise_mode / seed / length_scale / noise_w / dp_noise]); lengths
+        may differ (ragged batch, one bucket). prosody: one entry per utterance (None entries neutral), as for slot_prosody."""
         n = len(utterances)
         arr = (Utterance * n)()
         keep = []
         total = 0
-        for i, (ids, dur, noise) in enumerate(utterances):
-            u, k = self._utt(ids, dur, noise, noiseScale)
+        for i, item in enumerate(utterances):
+            ids, dur, noise = item[:3]
+            u, k = self._utt(ids, dur, noise, noiseScale, **(item[3] if len(item) > 3 else {}))
             arr[i] = u
             keep.append(k)
+        self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
         rc = self.lib.piper_hip_voice_prepare_batch(self.voice, arr, n, slot)
         if rc < 0:
             _check(rc)
@@ -1671,8 +1761,9 @@ class HipRuntime:
         return out[:sum(resample_count(src, rate, p) for p in per)]
 
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, rate=None, **kw):
-        """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate."""
+                         normalize=False, rate=None, prosody=None, **kw):
+        """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare."""
+        pro = None if prosody is None else [prosody]
         if rate is not None and int(rate) == self.cfg.sample_rate:
             rate = None
         if durations is not None and not kw and rate is not None:  # piper_hip_voice_synthesize_pcm16_rate
@@ -1681,6 +1772,7 @@ class HipRuntime:
             out = np.empty(max(n, 1), np.int16)
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
+            self._stage_prosody(0, pro, [len(phonemeIDs)])
             _check(self.lib.piper_hip_voice_synthesize_pcm16_rate(self.voice, C.byref(u), C.byref(prm), int(rate), out.ctypes.data_as(c_i16p), n,
                                                                   C.byref(got)))
             self._keep.pop(0, None)
@@ -1691,10 +1783,11 @@ class HipRuntime:
             out = np.empty(max(n, 1), np.int16)
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
+            self._stage_prosody(0, pro, [len(phonemeIDs)])
             _check(self.lib.piper_hip_voice_synthesize_pcm16(self.voice, C.byref(u), C.byref(prm), out.ctypes.data_as(c_i16p), n, C.byref(got)))
             self._keep.pop(0, None)
             return out[:got.value]
-        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, **kw)
+        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, **kw)
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
 
@@ -1718,8 +1811,9 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], total, False)
         return out[:sum(count(p) for p in per)]
 
-    def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None):
-        """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's."""
+    def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None):
+        """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's;
+        prosody: as for prepare (with supplied durations: noise alone)."""
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
@@ -1729,6 +1823,7 @@ class HipRuntime:
         out = np.empty(max(n, 1), np.uint8)
         got = C.c_int64()
         prm = PcmParams(float(gain), int(bool(normalize)))
+        self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
         _check(self.lib.piper_hip_voice_synthesize_g711(self.voice, C.byref(u), C.byref(prm), _law(law), rate, out.ctypes.data_as(c_u8p), n,
                                                         C.byref(got)))
         self._keep.pop(0, None)
@@ -1779,7 +1874,8 @@ class HipRuntime:
         return ms.value
 
     def time_subset(self, slot, name_filter, iters=20):
-        """Graph replay of the launches whose name contains `name_filter`: (avg µs per launch, launches, flops, bytes)."""
+        """Graph replay of the launches whose name contains `name_filter`: (avg µs per launch, launches, flops, bytes). A filter that
+        starts with "predict:" times the predictor plan the slot's last prepare ran."""
         us, n, fl, by = C.c_double(), C.c_int(), C.c_double(), C.c_double()
         _check(self.lib.piper_hip_voice_time_subset(self.voice, slot, name_filter.encode(), iters, C.byref(us), C.byref(n),
                                                     C.byref(fl), C.byref(by)))

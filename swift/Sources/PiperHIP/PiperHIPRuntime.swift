@@ -99,6 +99,77 @@ public final class PiperHIPRuntime {
     }
     public func slotSpeaker(slot: Int32, id: Int32) throws { try slotSpeakers(slot: slot, speakers: [[(id: id, weight: 1.0)]]) }
 
+    /// Per-phoneme prosody of one utterance (piper_hip_prosody): multipliers on the id's duration and on noise_scale, a floor (a pause) and a
+    /// ceiling (0 = none) on the id's frames — nil = neutral — and `fit` (bounded routes: compress to the bound instead of failing). The
+    /// reference shapes an utterance with the three scales alone (PiperMetalRuntime.swift:62-80).
+    public struct Prosody {
+        public var length: [Float]?
+        public var minFrames: [Int32]?
+        public var maxFrames: [Int32]?
+        public var noise: [Float]?
+        public var count: Int32
+        public var fit: Bool
+        public init(count: Int32, length: [Float]? = nil, minFrames: [Int32]? = nil, maxFrames: [Int32]? = nil, noise: [Float]? = nil, fit: Bool = false) {
+            self.count = count; self.length = length; self.minFrames = minFrames; self.maxFrames = maxFrames; self.noise = noise; self.fit = fit
+        }
+    }
+
+    /// The record over copies of the arrays that live until `body` returns (the library copies them inside slot_prosody).
+    private static func withRecords<R>(_ items: [Prosody], _ body: ([piper_hip_prosody]) throws -> R) rethrows -> R {
+        var keepF: [UnsafeMutablePointer<Float>] = [], keepI: [UnsafeMutablePointer<Int32>] = []
+        defer { keepF.forEach { $0.deallocate() }; keepI.forEach { $0.deallocate() } }
+        func floats(_ a: [Float]?) -> UnsafePointer<Float>? {
+            guard let a = a else { return nil }
+            let p = UnsafeMutablePointer<Float>.allocate(capacity: max(a.count, 1)); p.initialize(from: a, count: a.count); keepF.append(p)
+            return UnsafePointer(p)
+        }
+        func ints(_ a: [Int32]?) -> UnsafePointer<Int32>? {
+            guard let a = a else { return nil }
+            let p = UnsafeMutablePointer<Int32>.allocate(capacity: max(a.count, 1)); p.initialize(from: a, count: a.count); keepI.append(p)
+            return UnsafePointer(p)
+        }
+        let recs = items.map { piper_hip_prosody(length: floats($0.length), min_frames: ints($0.minFrames), max_frames: ints($0.maxFrames),
+                                                 noise: floats($0.noise), t: $0.count, fit: $0.fit ? 1 : 0) }
+        return try body(recs)
+    }
+
+    /// piper_hip_prosody_check: throws naming the field and the index of the first violation.
+    public static func prosodyCheck(_ p: Prosody) throws {
+        try withRecords([p]) { recs in var r = recs[0]; try HIPBackend.check(piper_hip_prosody_check(&r)) }
+    }
+
+    /// piper_hip_prosody_frames: the integer frame rule from w0 = exp(logw)·length_scale on (host only) → (frames per id, wanted = Σ before fitting).
+    public static func prosodyFrames(_ p: Prosody?, w0: [Float], cap: Int64 = 0) throws -> (frames: [Int32], wanted: Int64) {
+        var out = [Int32](repeating: 0, count: w0.count)
+        var wanted: Int64 = 0
+        try withRecords(p.map { [$0] } ?? []) { recs in
+            if var r = recs.first {
+                try HIPBackend.check(piper_hip_prosody_frames(&r, w0, Int32(w0.count), cap, &out, &wanted))
+            } else {
+                try HIPBackend.check(piper_hip_prosody_frames(nil, w0, Int32(w0.count), cap, &out, &wanted))   // no record: neutral
+            }
+        }
+        return (out, wanted)
+    }
+
+    /// The prosody of the NEXT staging call on the slot id (piper_hip_voice_slot_prosody): entry i for item i of prepare*, stream_begin*,
+    /// synthesize* (slot 0) or a pool join (its work slot). The staging call takes the assignment whether or not it succeeds; an empty list clears it.
+    public func slotProsody(slot: Int32, items: [Prosody]) throws {
+        try PiperHIPRuntime.withRecords(items) { recs in
+            var r = recs
+            try HIPBackend.check(piper_hip_voice_slot_prosody(voice, slot, &r, Int32(r.count)))
+        }
+    }
+
+    /// Per item of the slot: the frames the rule wanted before fitting, and whether the bounded route compressed the item to its bound
+    /// (piper_hip_voice_prosody_report); answers where the durations are known.
+    public func prosodyReport(slot: Int32) throws -> [(wanted: Int64, fitted: Bool)] {
+        let n = Int(piper_hip_voice_batch_size(voice, slot))
+        var wanted = [Int64](repeating: 0, count: max(n, 1)), fitted = [Int32](repeating: 0, count: max(n, 1))
+        try HIPBackend.check(piper_hip_voice_prosody_report(voice, slot, &wanted, &fitted, Int32(n)))
+        return (0..<n).map { (wanted[$0], fitted[$0] != 0) }
+    }
+
     /// PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:) — the whole graph on the device: `durations == nil` ⇒ the
     /// voice's stochastic duration predictor runs (part of the plan's HIP graph); `noise_mode = DEVICE` ⇒ both RandomNormalLike tensors are
     /// drawn on the device with the reference's xorshift32 + Box-Muller generator (elementwise.metal:132-163) from `seed`.
