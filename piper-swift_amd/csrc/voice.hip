@@ -244,7 +244,7 @@ struct RowFormat {
   float gain = 1.0f;
 };
 
-// One row of a batched stream on the host, the same record for an item of a group (Slot::bs_rows) and a row of a pool (StreamPool::Row):
+// One row of a stream on the host, the same record for a single stream, an item of a group and a row of a pool (Stream::rows):
 // the item's frames, its next frame, and whether the next step decodes a chunk of it (false: finished, dropped, or a pool row never taken).
 struct StreamRow {
   int F = 0, next = 0;
@@ -271,6 +271,21 @@ struct StreamRate {
   bool mixed = false;
   int mix_rows = 0;             // generator rows `mdesc` holds
   MixStepRow* mdesc = nullptr;  // device [mix_rows]
+};
+
+// A stream in progress, whoever holds it: a plan (Slot::stream — a single stream or a group) or a streaming pool (StreamPool::st).
+// `rows` empty: no stream. The device buffers come from stream_alloc and belong to `plan`, or to the context pool for a streaming pool.
+struct Slot;
+struct Stream {
+  int chunk = 0, halo = 0, NBg = 1;  // frames; the generator's batch (1 for a single stream), fixed for the life of the stream
+  bool single = false;               // stream_begin's: one row that stream_next steps, not a group of one
+  std::vector<StreamRow> rows;       // one per item / pool row
+  int* d_desc = nullptr;             // device: [NBg][kDescInts] descriptor of a batched step (one upload per step)
+  void* pack = nullptr;              // device: the packed chunks of one batched step
+  size_t pack_bytes = 0;             // of `pack`
+  StreamRate rs;                     // output rate of the stream
+  Slot* plan = nullptr;              // owner of the device buffers; nullptr = the context pool (a streaming pool)
+  int items() const { return (int)rows.size(); }
 };
 
 struct Slot {
@@ -342,31 +357,28 @@ struct Slot {
   // streaming state of a full-schedule slot (piper_hip_voice_stream_*)
   hipGraph_t front_graph = nullptr;
   hipGraphExec_t front_exec = nullptr;  // encoder + flow only
-  int st_chunk = 0, st_next = -1, st_halo = 0;
-  // batched stream of a full-schedule slot (piper_hip_voice_stream_*_batch): one StreamRow per item of the group (empty = none), F copied
-  // from h_F at stream_begin_batch; the per-step descriptor table and the packed chunks live in device buffers of this plan (released with it)
-  std::vector<StreamRow> bs_rows;
-  int* bs_desc = nullptr;     // [kMaxGroup][kDescInts] device
-  float* bs_pack = nullptr;   // the packed chunks of one step, device
-  size_t bs_pack_cap = 0;     // floats
+  // the stream of a full-schedule slot, single (piper_hip_voice_stream_begin) or a group (_stream_begin_batch: one row per item, F copied
+  // from h_F); its device buffers are in `owned`, kept across streams and released with the plan
+  Stream stream;
   // 16-bit PCM output (piper_hip_voice_collect_pcm16 / stream_next_pcm16): device buffers of this plan (in `owned`), allocated on first use
   void* pcm = nullptr;        // the items back to back, as they travel to the host (int16, or one G.711 byte per sample)
   size_t pcm_cap = 0;         // bytes
   float* peaks = nullptr;     // [NB] max |x| per item (normalize = 1)
   std::vector<float> h_peaks; // the same on the host after a normalising collect_pcm16 (empty: none since the last launch)
-  StreamRate rs;              // output rate of the stream in progress; its buffers are in `owned`
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
 void reset_stream_state(Slot& s) {
-  s.st_next = -1;
-  s.bs_rows.clear();
-  s.rs.rate = 0; s.rs.started = false; s.rs.parity = 0; s.rs.mixed = false;  // (a new stream starts at the voice's own rate; the buffers stay with the plan)
+  s.stream.rows.clear();
+  s.stream.single = false;
+  StreamRate& rs = s.stream.rs;
+  rs.rate = 0; rs.started = false; rs.parity = 0; rs.mixed = false;  // (a new stream starts at the voice's own rate; the buffers stay with the plan)
 }
 
 // Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
 // or stream_drop) while the stream runs. It belongs to the voice per slot id, not to a plan — a pool has no single front plan: every join
-// runs encoder + flow on a work slot's plan and moves the latents into the rows' own stores. A row is a group's StreamRow plus its store.
+// runs encoder + flow on a work slot's plan and moves the latents into the rows' own stores. A row is a group's StreamRow plus its store;
+// the stream's buffers come from the context pool and go back in pool_close.
 struct PoolRowRef {  // device table entry: where row r's latent [inter][stride] lives
   const float* z;
   int64_t stride;
@@ -375,17 +387,17 @@ struct PoolJoinEnt {  // per-join table entry of stream_adopt_kernel
   int src, row, F, pad;
 };
 struct StreamPool {
-  int capacity = 0, NBg = 1, chunk = 0, halo = 0;
-  struct Row : StreamRow {  // active = false: the row is free (never taken, finished or dropped)
-    float* z = nullptr;     // [inter][stride] row store (context pool), kept while the pool lives, regrown for a longer utterance
-    size_t cap = 0;         // floats
-    int stride = 0;         // bucket_f(F) of the item in the row
+  Stream st;               // rows.size() = the pool's capacity; a row with active = false is free (never taken, finished or dropped)
+  struct Row {             // what only a pool's row has, parallel to st.rows
+    float* z = nullptr;    // [inter][stride] row store (context pool), kept while the pool lives, regrown for a longer utterance
+    size_t cap = 0;        // floats
+    int stride = 0;        // bucket_f(F) of the item in the row
     // stream_pool_join_bounded: the row is taken (active) but its F is still on the device until pool_resolve has read the adopt's report
     bool pending = false;
-    bool held = false;      // F is the length of the row's latest occupant (stream_pool_item_samples)
+    bool held = false;     // F is the length of the row's latest occupant (stream_pool_item_samples)
     int over_want = 0, over_cap = 0;  // over_want > 0: the latest bounded occupant wanted more frames than its join allowed and never ran
   };
-  std::vector<Row> rows;
+  std::vector<Row> ext;
   struct BoundedJoin {  // a bounded join that pool_resolve has not seen yet: its event (one of ev_pending) and the work slot's prepare
     hipEvent_t ev;
     int work_slot;
@@ -396,11 +408,7 @@ struct StreamPool {
   int32_t* h_rep = nullptr;       // page-locked [capacity][2]: {wanted frames, allowed frames} per row, written by stream_adopt_bounded_kernel
   int32_t* d_rep = nullptr;       // its device mapping
   PoolRowRef* d_rows = nullptr;   // device: [NBg] row table, then the [capacity] PoolJoinEnt table of the latest join (one upload per join)
-  int* d_desc = nullptr;          // device: [NBg][kDescInts] descriptor of the step (one upload per step)
-  float* pack = nullptr;         // device: the packed chunks of one step, capacity · chunk · hop floats
   std::vector<hipEvent_t> ev_free, ev_pending;  // ev_pending: "the adopt of a join since the last step has run", one per join
-  StreamRate rs;                 // output rate of the pool; its buffers come from the context pool and go back in pool_close
-  size_t pack_bytes = 0;         // of `pack`
   float* spk_rows = nullptr;     // device: [capacity][up_initial] conv_pre rows of the sessions in the rows (a voice with speakers; else null)
 };
 
@@ -831,11 +839,9 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   if (s.graph) { (void)hipGraphDestroy(s.graph); s.graph = nullptr; }
   if (s.front_exec) { (void)hipGraphExecDestroy(s.front_exec); s.front_exec = nullptr; }
   if (s.front_graph) { (void)hipGraphDestroy(s.front_graph); s.front_graph = nullptr; }
-  reset_stream_state(s);
+  s.stream = Stream();  // (no stream any more; its device buffers — descriptor, packed chunks, history, tables — are in `owned`)
   s.zin = nullptr; s.z_out = nullptr;
-  s.bs_desc = nullptr; s.bs_pack = nullptr; s.bs_pack_cap = 0;  // (both buffers are in `owned`)
-  s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();      // (these too)
-  s.rs = StreamRate();                                                         // (and the resampling history and descriptor)
+  s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();  // (these too)
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
@@ -859,14 +865,12 @@ void pool_close(piper_hip_voice* v, int slot) {
   if (!P) return;
   for (hipEvent_t e : P->ev_pending) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
   for (hipEvent_t e : P->ev_free) (void)hipEventDestroy(e);
-  for (auto& r : P->rows)
+  for (auto& r : P->ext)
     if (r.z) (void)v->ctx->pool.release(r.z);
   if (P->d_rows) (void)v->ctx->pool.release(P->d_rows);
-  if (P->d_desc) (void)v->ctx->pool.release(P->d_desc);
-  if (P->pack) (void)v->ctx->pool.release(P->pack);
-  if (P->rs.hist) (void)v->ctx->pool.release(P->rs.hist);
-  if (P->rs.desc) (void)v->ctx->pool.release(P->rs.desc);
-  if (P->rs.mdesc) (void)v->ctx->pool.release(P->rs.mdesc);
+  const StreamRate& rs = P->st.rs;
+  for (void* p : {(void*)P->st.d_desc, P->st.pack, (void*)rs.hist, (void*)rs.desc, (void*)rs.mdesc})
+    if (p) (void)v->ctx->pool.release(p);
   if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
   if (P->h_rep) (void)hipHostFree(P->h_rep);  // (the adopts that write it have run: waited for above)
   v->pools[slot].reset();
@@ -2931,6 +2935,28 @@ __global__ __launch_bounds__(256) void dp_paths_kernel(const int32_t* __restrict
   }
 }
 
+// The argument refusals of a bounded prepare, in the words of the entry point that makes them: piper_hip_voice_prepare_batch_bounded
+// (join = false; it alone checks `slot`, between the batch size and the bound) or stream_pool_join_bounded (join = true), which makes them
+// before it looks at or regrows anything of its pool.
+int bounded_refusals(const piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int max_frames, bool join) {
+  const char* who = join ? "stream_pool_join_bounded" : "prepare_batch_bounded";
+  if (n < 1 || n > 256) {
+    if (join) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join_bounded: %d items outside [1,256]", n);
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
+  }
+  if (!join && (slot < 0 || slot >= kMaxSlots)) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (max_frames < 1 || (int64_t)max_frames * std::max(v->hop, 1) > 0x3fffffff / 64) PH_FAIL(PIPER_HIP_ERR_SHAPE, "%s: max_frames %d out of range", who, max_frames);
+  if (!v->cfg.dp_present)
+    PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0): supply durations%s", join ? " (stream_pool_join)" : "");
+  for (int b = 0; b < n; b++) {
+    if (int rc = check_item(utts[b], b)) return rc;
+    if (utts[b].durations || utts[b].noise)
+      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: %s predicts the durations and cannot take a host noise tensor (its shape depends on them): pass "
+                                 "durations = noise = NULL (noise_mode DEVICE draws it on the device)", b, who);
+  }
+  return PIPER_HIP_OK;
+}
+
 }  // namespace
 
 // Whole utterances with PREDICTED durations and no host round trip between the predictor and the rest: the caller states an upper bound on
@@ -2940,19 +2966,9 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
   const bool has_pro = !pro.empty();
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
-  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
-  if (max_frames < 1 || (int64_t)max_frames * std::max(v->hop, 1) > 0x3fffffff / 64) PH_FAIL(PIPER_HIP_ERR_SHAPE, "prepare_batch_bounded: max_frames %d out of range", max_frames);
-  if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0): supply durations");
   int Tmax = 0, rc;
-  for (int b = 0; b < n; b++) {
-    const piper_hip_utterance& u = utts[b];
-    if ((rc = check_item(u, b))) return rc;
-    if (u.durations || u.noise)
-      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: prepare_batch_bounded predicts the durations and cannot take a host noise tensor (its shape depends "
-                                 "on them): pass durations = noise = NULL (noise_mode DEVICE draws it on the device)", b);
-    Tmax = std::max(Tmax, u.t);
-  }
+  if ((rc = bounded_refusals(v, utts, n, slot, max_frames, false))) return rc;
+  for (int b = 0; b < n; b++) Tmax = std::max(Tmax, utts[b].t);
   if ((rc = check_prosody(pro, utts, n, true))) return rc;
   const int T = bucket_t(Tmax), F = bucket_f(max_frames), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
@@ -3466,15 +3482,19 @@ PH_EXPORT int piper_hip_voice_receptive_field(const piper_hip_voice* v) { return
 
 namespace {
 // The prepared slot's encoder + flow as their own graph (everything before the generator's first launch), captured on first use, then
-// launched; z is ready when the plan's ev1 fires. Shared by the single and the batched stream.
+// launched; z is ready when the plan's ev1 fires. Shared by the single and the batched stream. front_steps: the launches it consists of.
+std::vector<int> front_steps(const Slot& s) {
+  std::vector<int> front;
+  for (int i = 0; i < (int)s.steps.size(); i++) {
+    if (s.steps[i].name.compare(0, 4, "dec.") == 0) break;
+    if (s.steps[i].kind == Step::LAUNCH) front.push_back(i);
+  }
+  return front;
+}
+
 int launch_front(Slot& s) {
   if (!s.front_exec) {
-    std::vector<int> front;
-    for (int i = 0; i < (int)s.steps.size(); i++) {
-      if (s.steps[i].name.compare(0, 4, "dec.") == 0) break;
-      if (s.steps[i].kind == Step::LAUNCH) front.push_back(i);
-    }
-    const int rc = capture_steps(s, front, &s.front_graph, &s.front_exec);
+    const int rc = capture_steps(s, front_steps(s), &s.front_graph, &s.front_exec);
     if (rc) return rc;
   }
   PH_HIP(hipGraphLaunch(s.front_exec, s.set.stream), PIPER_HIP_ERR_LAUNCH);
@@ -3490,9 +3510,13 @@ PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_u
   if (rc < 0) return rc;
   Slot& s = *v->attached[slot];
   if ((rc = launch_front(s))) return rc;
-  s.st_chunk = chunk_frames;
-  s.st_halo = generator_halo_frames(v->cfg);
-  s.st_next = 0;
+  Stream& st = s.stream;
+  st.plan = &s;
+  st.chunk = chunk_frames;
+  st.halo = generator_halo_frames(v->cfg);
+  st.NBg = 1;
+  st.single = true;
+  st.rows.assign(1, StreamRow{s.h_F[0], 0, s.h_F[0] > 0});
   return (int)ceil_div(s.h_F[0], chunk_frames);
 }
 
@@ -3629,7 +3653,7 @@ static_assert(kDescStageInts * sizeof(int) % alignof(RsStepRow) == 0, "the RsSte
 static_assert(kDescStageInts * sizeof(int) % alignof(MixStepRow) == 0 && sizeof(MixStepRow) % sizeof(int) == 0, "the MixStepRow table starts aligned");
 
 // ---- mixed formats (include/piper_hip.h "Mixed formats"): what a row's format means on the host
-int fmt_elem(const RowFormat& f) { return f.enc == PIPER_HIP_ENC_F32 ? 4 : f.enc == PIPER_HIP_ENC_S16 ? 2 : 1; }
+int fmt_elem(int enc) { return enc == PIPER_HIP_ENC_F32 ? 4 : enc == PIPER_HIP_ENC_S16 ? 2 : 1; }  // bytes of a sample
 int64_t round_up4(int64_t bytes) { return (bytes + 3) & ~(int64_t)3; }
 
 // A caller's format → the row's record, every check of the header's table on the host; nothing is uploaded here.
@@ -3658,7 +3682,7 @@ int64_t fmt_step_bytes(const piper_hip_voice* v, const RowFormat& f, int64_t chu
     if (rs_design(v->cfg.sample_rate, f.rate, &d)) return 0;  // (checked when the format was supplied)
     n = rs_step_bound(*d, chunk_samples);
   }
-  return round_up4(n * fmt_elem(f));
+  return round_up4(n * fmt_elem(f.enc));
 }
 
 // What one stream step decodes of an utterance of F frames whose next frame is `next`: latent frames [a, a + Fc), of whose audio the first
@@ -3675,27 +3699,42 @@ Window window_of(int F, int next, int chunk, int halo, int hop) {
   return Window{a, b - a, (f0 - a) * hop, (f1 - f0) * hop, f1};
 }
 
-// stream_next; pcm: the chunk leaves as int16 (host_pcm, gain) — converted by a kernel behind the window's graph — instead of fp32, or,
-// with law = PIPER_HIP_G711_*, as one G.711 byte per sample (host_pcm is then a byte buffer); the step is the same in every other respect
-int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm, float gain,
-                int law) {
+// Where the output of a step or a collect goes: the caller's buffer (null: deliver nothing), the samples it holds, the encoding
+// (PIPER_HIP_ENC_*: F32 = the float entry points, S16 / MULAW / ALAW = the PCM and G.711 ones, converted by a kernel with `gain`).
+// byte_off != nullptr: a mixed step — every row in its own format (StreamRow::fmt) at the 4-byte-aligned byte offsets reported there,
+// `cap` counts BYTES, enc and gain are not read. Each exported entry point builds its sink once, after its own argument checks.
+struct Sink {
+  void* host = nullptr;
+  int64_t cap = 0;
+  int enc = PIPER_HIP_ENC_F32;
+  float gain = 1.0f;
+  int64_t* byte_off = nullptr;
+};
+// the `law` argument of the PCM kernels: the G.711 encodings are their own laws (PIPER_HIP_ENC_MULAW == PIPER_HIP_G711_MULAW …), 0 = int16
+int sink_law(const Sink& o) { return o.enc == PIPER_HIP_ENC_MULAW || o.enc == PIPER_HIP_ENC_ALAW ? o.enc : 0; }
+
+// stream_next. A PCM sink: the chunk leaves as int16 or one G.711 byte per sample — converted by a kernel behind the window's graph —
+// instead of fp32; the step is the same in every other respect
+int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_samples) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  const size_t elem = law ? 1 : sizeof(int16_t);
-  const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
+  const bool pcm = out.enc != PIPER_HIP_ENC_F32, want_out = out.host != nullptr;
+  const size_t elem = fmt_elem(out.enc);
+  const int law = sink_law(out);
   Slot* sp = slot_plan(v, slot);
-  if (sp && sp->bs_rows.size() > 1)
-    PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a group of %d streams: use stream_next_batch", slot, (int)sp->bs_rows.size());
-  if (!sp || sp->st_next < 0) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no stream in progress", slot);
+  if (sp && sp->stream.items() > 1)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a group of %d streams: use stream_next_batch", slot, sp->stream.items());
+  if (!sp || !sp->stream.single) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no stream in progress", slot);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *sp;
-  const int Ftrue = s.h_F[0];
+  StreamRow& row = s.stream.rows[0];
+  const int Ftrue = row.F;
   *n_samples = 0;
-  if (s.st_next >= Ftrue) return PIPER_HIP_OK;  // end of stream
-  const Window w = window_of(Ftrue, s.st_next, s.st_chunk, s.st_halo, v->hop);
+  if (row.next >= Ftrue) return PIPER_HIP_OK;  // end of stream
+  const Window w = window_of(Ftrue, row.next, s.stream.chunk, s.stream.halo, v->hop);
   const int a = w.a, Fc = w.Fc;
   int64_t want = w.n;
   // a slot with an output rate of its own delivers int16 only: the chunk goes through the resampling step kernel instead of the flat one
-  StreamRate& rs = s.rs;
+  StreamRate& rs = s.stream.rs;
   const RsDesign* rd = nullptr;
   RsFilter rf{};
   RsStepRow rrow{};
@@ -3706,11 +3745,11 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
     if (!rc0) rc0 = grow_pinned(v->staging[slot].h_desc, v->staging[slot].cap_desc, kRateStageInts);
     if (rc0) return rc0;
     int64_t j0, j1;
-    rate_range(*rd, (int64_t)s.st_next * v->hop, (int64_t)w.end * v->hop, (int64_t)Ftrue * v->hop, &j0, &j1);
-    rrow = RsStepRow{(int64_t)s.st_next * v->hop, j0, w.skip, w.n, (int)(j1 - j0), 0};
+    rate_range(*rd, (int64_t)row.next * v->hop, (int64_t)w.end * v->hop, (int64_t)Ftrue * v->hop, &j0, &j1);
+    rrow = RsStepRow{(int64_t)row.next * v->hop, j0, w.skip, w.n, (int)(j1 - j0), 0};
     want = j1 - j0;
   }
-  if (want_out && max_samples < want) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next: buffer holds %lld < %lld samples", (long long)max_samples, (long long)want);
+  if (want_out && out.cap < want) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next: buffer holds %lld < %lld samples", (long long)out.cap, (long long)want);
   // generator-only plan of the window's bucket (first / interior / last windows of a stream usually share one)
   Slot* gs = nullptr;
   bool built = false;
@@ -3732,22 +3771,22 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (pcm && want_out) {
     PcmRoute r;
     const size_t dev_samples = (size_t)std::max<int64_t>((int64_t)gs->F * v->hop, rd ? rs_step_bound(*rd, (int64_t)gs->F * v->hop) : 0);
-    if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], host_pcm, elem, (size_t)want, dev_samples, &r);
+    if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], out.host, elem, (size_t)want, dev_samples, &r);
     if (rd) {  // (every step ends with a wait: the staged descriptor of the previous one has been read)
       RsStepRow* h = (RsStepRow*)(v->staging[slot].h_desc + kDescStageInts);
       if (e == hipSuccess && !rc) { *h = rrow; e = hipMemcpyAsync(rs.desc, h, sizeof(RsStepRow), hipMemcpyHostToDevice, gs->set.stream); }
       if (e == hipSuccess && !rc)
         e = launch_resample_step(gs->set.stream, 1, rrow.count, gs->audio, 0, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, r.kdst, law);
+                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, out.gain, r.kdst, law);
     } else if (e == hipSuccess && !rc) {
-      e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, gain, r.kdst, law, v->ctx->num_cus);
+      e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, out.gain, r.kdst, law, v->ctx->num_cus);
     }
-    if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, host_pcm, elem, (size_t)want);
-    if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)want * elem);
+    if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, out.host, elem, (size_t)want);
+    if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(out.host, r.stage, (size_t)want * elem);
     if (e != hipSuccess || rc) (void)hipStreamSynchronize(gs->set.stream);  // nothing of the window may still run when its plan goes idle
   } else {
-    if (e == hipSuccess && host_audio)
-      e = hipMemcpyAsync(host_audio, gs->audio + w.skip, (size_t)want * sizeof(float), hipMemcpyDeviceToHost, gs->set.stream);
+    if (e == hipSuccess && want_out)
+      e = hipMemcpyAsync(out.host, gs->audio + w.skip, (size_t)want * elem, hipMemcpyDeviceToHost, gs->set.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(gs->set.stream);
   }
   gs->in_use = false;
@@ -3755,7 +3794,7 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next: %s", hipGetErrorString(e));
   if (rc) return rc;
   *n_samples = want;
-  s.st_next = w.end;
+  row.next = w.end;
   rs.started = true;
   if (rd) rs.parity ^= 1;
   return PIPER_HIP_OK;
@@ -3763,7 +3802,7 @@ int stream_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_sam
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_next(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
-  return stream_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f, 0);
+  return stream_step(v, slot, Sink{host_audio, max_samples}, n_samples);
 }
 
 // ---- batched streaming: a group of n utterances on one slot, the next chunk of every active item in one generator launch ------------
@@ -3870,6 +3909,31 @@ void plan_free(piper_hip_voice* v, Slot& s, void* p, size_t bytes) {
   (void)v->ctx->pool.release(p);
 }
 
+// A device buffer of a stream, from its owner: the plan (counted in its arena_bytes, kept across streams, released with it) or, for a
+// streaming pool, the context pool (given back in pool_close). The one place that knows the difference.
+int stream_alloc(piper_hip_voice* v, Stream& st, size_t bytes, void** out) {
+  return st.plan ? plan_alloc(v, *st.plan, bytes, out) : v->ctx->pool.alloc(bytes, out);
+}
+
+// Gives back a buffer that a larger one replaces. Every step ends with a host wait, so nothing on the GPU still reads it.
+void stream_free(piper_hip_voice* v, Stream& st, void* p, size_t bytes) {
+  if (!p) return;
+  if (st.plan) plan_free(v, *st.plan, p, bytes);
+  else (void)v->ctx->pool.release(p);
+}
+
+// A packed-output buffer of at least `bytes` for the batched stream (no step is in flight: every step ends with a wait).
+int pack_buffer(piper_hip_voice* v, Stream& st, size_t bytes) {
+  if (st.single || st.pack_bytes >= bytes) return PIPER_HIP_OK;  // (a single stream packs nothing: its chunk is the window's own audio)
+  bytes = round_up4((int64_t)bytes);
+  void* p = nullptr;
+  if (int rc = stream_alloc(v, st, bytes, &p)) return rc;
+  stream_free(v, st, st.pack, st.pack_bytes);
+  st.pack = p;
+  st.pack_bytes = bytes;
+  return PIPER_HIP_OK;
+}
+
 }  // namespace
 
 // ---- streaming pool: the rows of a batched stream are taken and freed while it runs ------------------------------------------------------
@@ -3942,7 +4006,7 @@ __global__ __launch_bounds__(256) void stream_adopt_bounded_kernel(const float* 
 
 int pool_free_rows(const StreamPool& P) {
   int k = 0;
-  for (const auto& r : P.rows) k += r.active ? 0 : 1;
+  for (const auto& r : P.st.rows) k += r.active ? 0 : 1;
   return k;
 }
 
@@ -3957,44 +4021,36 @@ int pool_event(StreamPool& P, hipEvent_t* out) {
   return PIPER_HIP_OK;
 }
 
-// A batched stream as one step sees it: a group's (batch_step) or a pool's (pool_step).
-template <class Row>  // StreamRow, or a record that extends it
-struct StepView {
-  Row* rows;                 // [n] host records
-  int n, NBg;                // items, and the generator's batch (group_batch(n), fixed for the life of the stream)
-  int chunk, halo;           // frames
-  int* d_desc;               // device: [NBg][kDescInts] descriptor of the step (one upload per step)
-  float* pack;               // device: the packed chunks of one step
-  size_t pack_cap;           // floats
+// What a batched step needs to be told that the stream's record does not hold: a group's (batch_step) or a pool's (pool_step).
+struct StepSource {
   const float* z;            // the latents as stream_window_gather_kernel takes them: z [n][I][Fz] …
   int Fz;
   const PoolRowRef* d_rows;  // … or the device row table
   const hipEvent_t* wait;    // "the latents are there": what the step's stream waits for (the GPU waits, the host does not)
   size_t n_wait;
-  StreamRate* rs;            // the stream's output rate; a resampling step packs int16 through resample_step_kernel and its own descriptor
-  const float* spk = nullptr;  // a voice with speakers: the items' conv_pre rows, item src at spk + src·spk_stride (null otherwise)
-  int64_t spk_stride = 0;
+  const float* spk;          // a voice with speakers: the items' conv_pre rows, item src at spk + src·spk_stride (null otherwise)
+  int64_t spk_stride;
 };
 
 // stream_next_batch: the next chunk of every active row in one generator launch at the stream's fixed batch; *ran = a step ran and has
 // been waited for (false: no active row, nothing was launched).
-// pcm: the chunks leave as int16 (host_pcm, gain) instead of fp32 (host_audio) — the int16 sibling of the pack kernel writes them into the
-// same device and staging buffers, half filled, and half the bytes cross the bus. law = PIPER_HIP_G711_* (with pcm): one G.711 byte per
-// sample instead, host_pcm a byte buffer — a quarter filled, a quarter of the bytes.
-// mix != nullptr: the step of a mixed slot (stream_next_batch_mixed) — every row in its own format (StreamRow::fmt) at 4-byte-aligned byte
-// offsets of host_pcm, max_samples counting BYTES; pcm, gain and law are not read. The generator part is the same.
-template <class Row>
-int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm,
-                 void* host_pcm, float gain, int law, bool* ran, int64_t* mix = nullptr) {
+// A PCM sink: the chunks leave as int16 instead of fp32 — the int16 sibling of the pack kernel writes them into the same device and
+// staging buffers, half filled, and half the bytes cross the bus — or as one G.711 byte per sample: a quarter filled, a quarter of the bytes.
+// A mixed sink (out.byte_off): the step of a mixed slot (stream_next_batch_mixed). The generator part is the same.
+// A resampling step packs int16 through resample_step_kernel and its own descriptor (st.rs).
+int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src, const Sink& out, int64_t* n_samples, bool* ran) {
   *ran = false;
-  StreamRate& rs = *s.rs;
+  StreamRate& rs = st.rs;
+  int64_t* const mix = out.byte_off;
   if (rs.mixed && !mix) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a mixed-format stream: use stream_next_batch_mixed", slot);
   if (!rs.mixed && mix) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch_mixed: slot %d is not mixed (stream_set_mixed)", slot);
-  if (mix) pcm = true;  // (the output is host_pcm)
-  const bool want_out = pcm ? host_pcm != nullptr : host_audio != nullptr;
-  const size_t sample_bytes = mix ? 1 : pcm ? (law ? 1 : sizeof(int16_t)) : sizeof(float);  // (a mixed step's totals count bytes)
+  const bool pcm = mix || out.enc != PIPER_HIP_ENC_F32, want_out = out.host != nullptr;
+  const size_t sample_bytes = mix ? 1 : fmt_elem(out.enc);  // (a mixed step's totals count bytes)
+  const int law = sink_law(out);
+  const float gain = out.gain;
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  const int n = s.n, NBg = s.NBg, hop = v->hop;
+  std::vector<StreamRow>& rows = st.rows;
+  const int n = st.items(), NBg = st.NBg, hop = v->hop;
   auto& sg = v->staging[slot];
   const RsDesign* rd = nullptr;
   RsFilter rf{};
@@ -4023,14 +4079,14 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     if (rd) rrow[r] = RsStepRow{0, 0, 0, 0, 0, 0};
     if (mix) mrow[r] = MixStepRow{};
     if (mix && r < n) mix[r] = round_up4(total);  // (a row that delivers nothing: where the next delivering row starts)
-    if (r < n && !s.rows[r].active && s.rows[r].ghost) {  // a dropped item: length 0 in the step, its window only sizes the plan
-      const Window g = window_of(s.rows[r].F, s.rows[r].next, s.chunk, s.halo, hop);
+    if (r < n && !rows[r].active && rows[r].ghost) {  // a dropped item: length 0 in the step, its window only sizes the plan
+      const Window g = window_of(rows[r].F, rows[r].next, st.chunk, st.halo, hop);
       Fmax = std::max(Fmax, g.Fc);
       ghost_end[r] = g.end;
     }
-    if (r >= n || !s.rows[r].active) continue;
+    if (r >= n || !rows[r].active) continue;
     live = true;
-    const Window w = win[r] = window_of(s.rows[r].F, s.rows[r].next, s.chunk, s.halo, hop);
+    const Window w = win[r] = window_of(rows[r].F, rows[r].next, st.chunk, st.halo, hop);
     e[kDescA] = w.a;
     e[kDescFc] = w.Fc;
     e[kDescSkip] = w.skip;
@@ -4039,17 +4095,17 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
     cnt[r] = w.n;
     if (rd) {
       int64_t j0, j1;
-      rate_range(*rd, (int64_t)s.rows[r].next * hop, (int64_t)w.end * hop, (int64_t)s.rows[r].F * hop, &j0, &j1);
-      rrow[r] = RsStepRow{(int64_t)s.rows[r].next * hop, j0, w.skip, w.n, (int)(j1 - j0), (int)total};
+      rate_range(*rd, (int64_t)rows[r].next * hop, (int64_t)w.end * hop, (int64_t)rows[r].F * hop, &j0, &j1);
+      rrow[r] = RsStepRow{(int64_t)rows[r].next * hop, j0, w.skip, w.n, (int)(j1 - j0), (int)total};
       cnt[r] = j1 - j0;
       max_cnt = std::max(max_cnt, (int)(j1 - j0));
     }
     if (mix) {  // the row's own design, count, byte offset and descriptor (the filter table was uploaded when the format was supplied)
-      const RowFormat& fm = s.rows[r].fmt;
+      const RowFormat& fm = rows[r].fmt;
       MixStepRow m{};
-      m.s = (int64_t)s.rows[r].next * hop;
+      m.s = (int64_t)rows[r].next * hop;
       m.skip = w.skip; m.n_in = w.n; m.count = w.n;
-      m.elem = fmt_elem(fm);
+      m.elem = fmt_elem(fm.enc);
       m.law = m.elem == 1 ? fm.enc : 0;
       m.gain = fm.gain;
       if (fm.rate) {
@@ -4057,7 +4113,7 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
         RsFilter ff{};
         if ((rc = voice_filter(v, fm.rate, &fd, &ff))) return rc;
         int64_t j0, j1;
-        rate_range(*fd, m.s, (int64_t)w.end * hop, (int64_t)s.rows[r].F * hop, &j0, &j1);
+        rate_range(*fd, m.s, (int64_t)w.end * hop, (int64_t)rows[r].F * hop, &j0, &j1);
         m.j0 = j0; m.count = (int)(j1 - j0);
         m.taps = ff.taps; m.L = ff.L; m.M = ff.M; m.P = ff.P;
       }
@@ -4071,10 +4127,11 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   }
   for (int i = 0; i < n; i++) n_samples[i] = 0;
   if (!live) return PIPER_HIP_OK;  // end of the group / an idle pool (dropped items alone run no step)
-  if (want_out && max_samples < total)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld %s", (long long)max_samples, (long long)total, mix ? "bytes" : "samples");
-  if (mix ? (size_t)total > s.pack_cap * sizeof(float) : rd ? (size_t)total * sizeof(int16_t) > s.pack_cap * sizeof(float) : (size_t)total > s.pack_cap)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, s.pack_cap);
+  if (want_out && out.cap < total)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld %s", (long long)out.cap, (long long)total, mix ? "bytes" : "samples");
+  const size_t total_bytes = (size_t)total * sample_bytes;  // what the pack kernel writes and the host receives
+  if (total_bytes > st.pack_bytes)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, st.pack_bytes / sizeof(float));
   if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, mix ? ((size_t)total + 3) / 4 : rd ? ((size_t)total + 1) / 2 : (size_t)total, kAudioMinCap))) return rc;
   // generator-only plan of the step's longest window at the stream's batch size (rows past their end have length 0): a pool and a group
   // of the same size use the same plans
@@ -4093,18 +4150,18 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
   const hipStream_t q = gs->set.stream;
   const int I = v->cfg.inter, Fg = gs->F;
   hipError_t e = hipSuccess;
-  for (size_t k = 0; k < s.n_wait; k++)
-    if (e == hipSuccess) e = hipStreamWaitEvent(q, s.wait[k], 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(s.d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
+  for (size_t k = 0; k < src.n_wait; k++)
+    if (e == hipSuccess) e = hipStreamWaitEvent(q, src.wait[k], 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(st.d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
   if (e == hipSuccess) {
     const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (Fg / 4), 256), 64);
-    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, s.z, s.Fz, s.d_rows, s.d_desc, gs->zin, gs->lensF, I, Fg, s.spk,
-                       s.spk_stride, s.spk ? gs->spk_bias : nullptr, v->cfg.up_initial);
+    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, src.z, src.Fz, src.d_rows, st.d_desc, gs->zin, gs->lensF, I, Fg, src.spk,
+                       src.spk_stride, src.spk ? gs->spk_bias : nullptr, v->cfg.up_initial);
     e = hipGetLastError();
   }
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
   if (e == hipSuccess) {
-    const int px = (int)std::min<int64_t>(ceil_div((int64_t)s.chunk * hop, 1024), 64);
+    const int px = (int)std::min<int64_t>(ceil_div((int64_t)st.chunk * hop, 1024), 64);
     if (mix) {
       int gx;
       size_t lds;
@@ -4112,37 +4169,37 @@ int batched_step(piper_hip_voice* v, int slot, const StepView<Row>& s, float* ho
       e = hipMemcpyAsync(rs.mdesc, mrow, (size_t)NBg * sizeof(MixStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
         e = launch_mixed_step(q, NBg, gx, lds, gs->audio, gs->n_samples, rs.mdesc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                              rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, s.pack);
+                              rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, st.pack);
     } else if (rd) {
       e = hipMemcpyAsync(rs.desc, rrow, (size_t)NBg * sizeof(RsStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
         e = launch_resample_step(q, NBg, max_cnt, gs->audio, gs->n_samples, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, s.pack, law);
+                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, st.pack, law);
     } else if (pcm) {
-      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, s.d_desc, gain, s.pack, law);
+      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, st.d_desc, gain, st.pack, law);
     } else {
-      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, s.d_desc, s.pack);
+      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, st.d_desc, (float*)st.pack);
       e = hipGetLastError();
     }
   }
-  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, s.pack, (size_t)total * sample_bytes, hipMemcpyDeviceToHost, q);
+  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, st.pack, total_bytes, hipMemcpyDeviceToHost, q);
   if (e == hipSuccess) e = stream_wait(q);
   gs->in_use = false;
   evict_idle_plans(v);
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_next_batch: %s", hipGetErrorString(e));
   *ran = true;
-  if (want_out) memcpy(pcm ? host_pcm : (void*)host_audio, sg.h_audio, (size_t)total * sample_bytes);
+  if (want_out) memcpy(out.host, sg.h_audio, total_bytes);
   rs.started = true;
   if (rd || mix) rs.parity ^= 1;  // (a mixed step: whichever rows had a filter)
   for (int i = 0; i < n; i++) {
     n_samples[i] = cnt[i];
     if (ghost_end[i] >= 0) {
-      s.rows[i].next = ghost_end[i];
-      if (ghost_end[i] >= s.rows[i].F) s.rows[i].ghost = false;
+      rows[i].next = ghost_end[i];
+      if (ghost_end[i] >= rows[i].F) rows[i].ghost = false;
     }
     if (!win[i].n) continue;
-    s.rows[i].next = win[i].end;
-    if (win[i].end >= s.rows[i].F) s.rows[i].active = false;  // last chunk delivered (a pool: the row is free for the next join)
+    rows[i].next = win[i].end;
+    if (win[i].end >= rows[i].F) rows[i].active = false;  // last chunk delivered (a pool: the row is free for the next join)
   }
   return PIPER_HIP_OK;
 }
@@ -4161,19 +4218,20 @@ int pool_resolve(piper_hip_voice* v, StreamPool& P) {
   }
   P.bounded.clear();
   int bad = -1;
-  for (int r = 0; r < P.capacity; r++) {
-    auto& row = P.rows[r];
-    if (!row.pending) continue;
-    row.pending = false;
+  for (int r = 0; r < P.st.items(); r++) {
+    StreamRow& row = P.st.rows[r];
+    StreamPool::Row& x = P.ext[r];
+    if (!x.pending) continue;
+    x.pending = false;
     const int want = P.h_rep[2 * r], cap = P.h_rep[2 * r + 1];
-    if (want >= 1 && want <= cap && cap <= row.stride) {
+    if (want >= 1 && want <= cap && cap <= x.stride) {
       row.F = want;
       row.next = 0;
-      row.held = true;
+      x.held = true;
     } else {
       row.active = false;
-      row.over_want = want > cap ? want : 0;
-      row.over_cap = cap;
+      x.over_want = want > cap ? want : 0;
+      x.over_cap = cap;
       if (want <= cap) bad = r;
     }
   }
@@ -4182,13 +4240,11 @@ int pool_resolve(piper_hip_voice* v, StreamPool& P) {
 }
 
 // stream_next_batch on a pool slot: the latents are the row stores, ready when the adopts of the joins since the last step have run
-int pool_step(piper_hip_voice* v, int slot, StreamPool& P, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm,
-              float gain, int law, int64_t* mix) {
+int pool_step(piper_hip_voice* v, int slot, StreamPool& P, const Sink& out, int64_t* n_samples) {
   if (int rc0 = pool_resolve(v, P)) return rc0;
-  const StepView<StreamPool::Row> view{P.rows.data(), P.capacity, P.NBg, P.chunk, P.halo, P.d_desc, P.pack, P.pack_bytes / sizeof(float),
-                                       nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), &P.rs, P.spk_rows, v->cfg.up_initial};
+  const StepSource src{nullptr, 0, P.d_rows, P.ev_pending.data(), P.ev_pending.size(), P.spk_rows, v->cfg.up_initial};
   bool ran = false;
-  const int rc = batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran, mix);
+  const int rc = batched_step(v, slot, P.st, src, out, n_samples, &ran);
   if (rc || !ran) return rc;  // (an idle pool: joins since the last step stay pending)
   // the step's wait covers the adopts its stream waited for: their events can be recorded again
   P.ev_free.insert(P.ev_free.end(), P.ev_pending.begin(), P.ev_pending.end());
@@ -4206,65 +4262,58 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
   int rc = piper_hip_voice_prepare_batch(v, utts, n, slot);  // encoder (+ predictor) inputs of the whole group on one plan
   if (rc < 0) return rc;
   Slot& s = *v->attached[slot];
-  void* p = nullptr;
-  if (!s.bs_desc) {
-    if ((rc = plan_alloc(v, s, (size_t)kMaxGroup * kDescInts * sizeof(int), &p))) return rc;
-    s.bs_desc = (int*)p;
+  Stream& st = s.stream;  // (no stream is in progress: the prepare reset it; the buffers of an earlier one are still the plan's)
+  st.plan = &s;
+  if (!st.d_desc) {
+    void* p = nullptr;
+    if ((rc = stream_alloc(v, st, (size_t)kMaxGroup * kDescInts * sizeof(int), &p))) return rc;
+    st.d_desc = (int*)p;
   }
-  const size_t pack = (size_t)n * chunk_frames * v->hop;
-  if (s.bs_pack_cap < pack) {
-    if (s.bs_pack) plan_free(v, s, s.bs_pack, s.bs_pack_cap * sizeof(float));
-    s.bs_pack = nullptr;
-    s.bs_pack_cap = 0;
-    if ((rc = plan_alloc(v, s, pack * sizeof(float), &p))) return rc;
-    s.bs_pack = (float*)p;
-    s.bs_pack_cap = pack;
-  }
+  if ((rc = pack_buffer(v, st, (size_t)n * chunk_frames * v->hop * sizeof(float)))) return rc;
   if ((rc = launch_front(s))) return rc;
-  s.st_chunk = chunk_frames;
-  s.st_halo = generator_halo_frames(v->cfg);
-  s.bs_rows.resize(n);
-  for (int b = 0; b < n; b++) s.bs_rows[b] = StreamRow{s.h_F[b], 0, s.h_F[b] > 0};
+  st.chunk = chunk_frames;
+  st.halo = generator_halo_frames(v->cfg);
+  st.NBg = group_batch(n);
+  st.rows.resize(n);
+  for (int b = 0; b < n; b++) st.rows[b] = StreamRow{s.h_F[b], 0, s.h_F[b] > 0};
   int steps = 0;
   for (int b = 0; b < n; b++) steps = std::max(steps, (int)ceil_div(s.h_F[b], chunk_frames));
   return steps;
 }
 
 namespace {
-// stream_next_batch; pcm / host_pcm / gain / law as for batched_step. A group's latents are the front plan's z, ready when its ev1 fires.
-int batch_step(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples, bool pcm, void* host_pcm, float gain,
-               int law, int64_t* mix = nullptr) {
+// stream_next_batch. A group's latents are the front plan's z, ready when its ev1 fires.
+int batch_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_samples) {
   if (!v || !n_samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, mix);
+  if (StreamPool* P = slot_pool(v, slot)) return pool_step(v, slot, *P, out, n_samples);
   Slot* sp = slot_plan(v, slot);
-  if (!sp || sp->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
+  if (!sp || sp->stream.single || sp->stream.rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
   Slot& s = *sp;
-  const int n = (int)s.bs_rows.size();
-  const StepView<StreamRow> view{s.bs_rows.data(), n, group_batch(n), s.st_chunk, s.st_halo, s.bs_desc, s.bs_pack, s.bs_pack_cap,
-                                 s.z_out, s.F, nullptr, &s.set.ev1, 1, &s.rs, s.spk_bias ? s.spk_bias + v->spk_pre_off : nullptr, v->spk.Ctot};
+  const StepSource src{s.z_out, s.F, nullptr, &s.set.ev1, 1, s.spk_bias ? s.spk_bias + v->spk_pre_off : nullptr, v->spk.Ctot};
   bool ran = false;
-  return batched_step(v, slot, view, host_audio, max_samples, n_samples, pcm, host_pcm, gain, law, &ran, mix);
+  return batched_step(v, slot, s.stream, src, out, n_samples, &ran);
 }
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_next_batch(piper_hip_voice* v, int slot, float* host_audio, int64_t max_samples, int64_t* n_samples) {
-  return batch_step(v, slot, host_audio, max_samples, n_samples, false, nullptr, 1.0f, 0);
+  return batch_step(v, slot, Sink{host_audio, max_samples}, n_samples);
 }
 
 PH_EXPORT int piper_hip_voice_stream_drop(piper_hip_voice* v, int slot, int item) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   if (StreamPool* P = slot_pool(v, slot)) {  // the session in that row leaves: the row is free for the next join
-    if (item < 0 || item >= P->capacity) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, P->capacity);
-    P->rows[item].active = false;
-    P->rows[item].pending = false;  // (a bounded join still in flight: ev_pending keeps its adopt away from the row's next occupant)
+    if (item < 0 || item >= P->st.items()) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, P->st.items());
+    P->st.rows[item].active = false;
+    P->ext[item].pending = false;  // (a bounded join still in flight: ev_pending keeps its adopt away from the row's next occupant)
     return PIPER_HIP_OK;
   }
   Slot* sp = slot_plan(v, slot);
-  if (!sp || sp->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
-  const int n = (int)sp->bs_rows.size();
+  if (!sp || sp->stream.single || sp->stream.rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d has no batched stream in progress", slot);
+  const int n = sp->stream.items();
   if (item < 0 || item >= n) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_drop: item %d outside [0,%d)", item, n);
-  if (sp->bs_rows[item].active) sp->bs_rows[item].ghost = sp->bs_rows[item].next < sp->bs_rows[item].F;
-  sp->bs_rows[item].active = false;
+  StreamRow& row = sp->stream.rows[item];
+  if (row.active) row.ghost = row.next < row.F;
+  row.active = false;
   return PIPER_HIP_OK;
 }
 
@@ -4278,17 +4327,17 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
   detach(v, slot);  // what the slot id held is replaced, as by a prepare
   v->planned = true;
   std::unique_ptr<StreamPool> P(new StreamPool());
-  P->capacity = capacity;
-  P->NBg = group_batch(capacity);
-  P->chunk = chunk_frames;
-  P->halo = generator_halo_frames(v->cfg);
-  P->rows.resize(capacity);
+  Stream& st = P->st;
+  st.NBg = group_batch(capacity);
+  st.chunk = chunk_frames;
+  st.halo = generator_halo_frames(v->cfg);
+  st.rows.resize(capacity);
+  P->ext.resize(capacity);
   void* p = nullptr;
-  int rc = v->ctx->pool.alloc((size_t)P->NBg * sizeof(PoolRowRef) + (size_t)capacity * sizeof(PoolJoinEnt), &p);
+  int rc = v->ctx->pool.alloc((size_t)st.NBg * sizeof(PoolRowRef) + (size_t)capacity * sizeof(PoolJoinEnt), &p);
   if (!rc) P->d_rows = (PoolRowRef*)p;
-  if (!rc) { rc = v->ctx->pool.alloc((size_t)P->NBg * kDescInts * sizeof(int), &p); if (!rc) P->d_desc = (int*)p; }
-  P->pack_bytes = (size_t)capacity * chunk_frames * v->hop * sizeof(float);
-  if (!rc) { rc = v->ctx->pool.alloc(P->pack_bytes, &p); if (!rc) P->pack = (float*)p; }
+  if (!rc) { rc = stream_alloc(v, st, (size_t)st.NBg * kDescInts * sizeof(int), &p); if (!rc) st.d_desc = (int*)p; }
+  if (!rc) rc = pack_buffer(v, st, (size_t)capacity * chunk_frames * v->hop * sizeof(float));
   if (!rc && v->spk.S) {  // the rows' conv_pre biases; a row never taken reads as 0.0
     const size_t bytes = (size_t)capacity * v->cfg.up_initial * sizeof(float);
     rc = v->ctx->pool.alloc(bytes, &p);
@@ -4307,11 +4356,7 @@ namespace {
 // answer — and captures the graph behind it, as launch_plan does for a plan's first run (the capture enqueues nothing).
 int launch_front_async(Slot& s) {
   if (s.front_exec) return launch_front(s);
-  std::vector<int> front;
-  for (int i = 0; i < (int)s.steps.size(); i++) {
-    if (s.steps[i].name.compare(0, 4, "dec.") == 0) break;
-    if (s.steps[i].kind == Step::LAUNCH) front.push_back(i);
-  }
+  const std::vector<int> front = front_steps(s);
   int rc = run_steps(s, front, s.set.stream);
   if (rc) return rc;
   PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);
@@ -4327,40 +4372,36 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
   if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
-  if (with_formats && !P->rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join_formats: the pool on slot %d is not mixed (stream_set_mixed)", slot);
+  Stream& st = P->st;
+  const int capacity = st.items();
+  if (with_formats && !st.rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join_formats: the pool on slot %d is not mixed (stream_set_mixed)", slot);
   if (with_formats && !fmts) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join_formats: null formats");
   if (work_slot < 0 || work_slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "work slot %d out of range [0,%d)", work_slot, kMaxSlots);
   if (work_slot == slot) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join: the work slot is the pool's slot %d", slot);
   if (slot_pool(v, work_slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_join: work slot %d holds a streaming pool", work_slot);
   if (n < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join: %d items", n);
   const int free_rows = pool_free_rows(*P);
-  if (n > free_rows) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join: %d items, %d free rows of %d", n, free_rows, P->capacity);
+  if (n > free_rows) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join: %d items, %d free rows of %d", n, free_rows, capacity);
   const RsDesign* rate_d = nullptr;  // samples_out counts what the pool delivers
-  if (P->rs.rate)
-    if (int rc0 = rs_design(v->cfg.sample_rate, P->rs.rate, &rate_d)) return rc0;
+  if (st.rs.rate)
+    if (int rc0 = rs_design(v->cfg.sample_rate, st.rs.rate, &rate_d)) return rc0;
   // a mixed pool: the joining items' formats, checked on the host, their filter tables uploaded here (never inside a step), and a packed
   // buffer that holds a step of the rows as they will stand (no step is in flight: every step ends with a wait)
-  std::vector<RowFormat> jf(P->rs.mixed ? n : 0);
+  std::vector<RowFormat> jf(st.rs.mixed ? n : 0);
   if (with_formats)
     for (int i = 0; i < n; i++)
       if (int rc0 = check_format(v, "stream_pool_join_formats", fmts[i], &jf[i])) return rc0;
-  if (P->rs.mixed) {
+  if (st.rs.mixed) {
     PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
     int64_t bytes = 0;
-    for (const auto& r : P->rows) bytes += r.active ? fmt_step_bytes(v, r.fmt, (int64_t)P->chunk * v->hop) : 0;
+    for (const auto& r : st.rows) bytes += r.active ? fmt_step_bytes(v, r.fmt, (int64_t)st.chunk * v->hop) : 0;
     for (int i = 0; i < n; i++) {
       RsFilter ff{};
       if (jf[i].rate)
         if (int rc0 = voice_filter(v, jf[i].rate, nullptr, &ff)) return rc0;
-      bytes += fmt_step_bytes(v, jf[i], (int64_t)P->chunk * v->hop);
+      bytes += fmt_step_bytes(v, jf[i], (int64_t)st.chunk * v->hop);
     }
-    if ((size_t)bytes > P->pack_bytes) {
-      void* p = nullptr;
-      if (int rc0 = v->ctx->pool.alloc((size_t)bytes, &p)) return rc0;
-      if (P->pack) (void)v->ctx->pool.release(P->pack);
-      P->pack = (float*)p;
-      P->pack_bytes = (size_t)bytes;
-    }
+    if (int rc0 = pack_buffer(v, st, (size_t)bytes)) return rc0;
   }
   // encoder (+ predictor) inputs of the join on the work slot's plan, then encoder + flow on that plan's stream
   int rc = bound ? piper_hip_voice_prepare_batch_bounded(v, utts, n, work_slot, bound) : piper_hip_voice_prepare_batch(v, utts, n, work_slot);
@@ -4372,7 +4413,7 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   int32_t* want_rep = nullptr;  // bounded: the device mapping of the work slot's report (dp_paths_kernel's counts before clamping)
   if (bound) {
     if (!P->h_rep) {
-      PH_HIP(hipHostMalloc((void**)&P->h_rep, (size_t)P->capacity * 2 * sizeof(int32_t)), PIPER_HIP_ERR_ALLOC);
+      PH_HIP(hipHostMalloc((void**)&P->h_rep, (size_t)capacity * 2 * sizeof(int32_t)), PIPER_HIP_ERR_ALLOC);
       if (hipHostGetDevicePointer((void**)&P->d_rep, P->h_rep, 0) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipHostFree(P->h_rep);
@@ -4387,14 +4428,14 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   }
   // rows, lowest free index first, and their stores. Nothing of the pool changes before everything that can fail has succeeded.
   std::vector<int> take;
-  for (int r = 0; r < P->capacity && (int)take.size() < n; r++)
-    if (!P->rows[r].active) take.push_back(r);
+  for (int r = 0; r < capacity && (int)take.size() < n; r++)
+    if (!st.rows[r].active) take.push_back(r);
   auto& sg = v->staging[work_slot];  // free: prepare_batch waited for whatever used this slot id's staging before
-  const size_t tab_ints = (size_t)P->NBg * sizeof(PoolRowRef) / sizeof(int), join_ints = (size_t)n * sizeof(PoolJoinEnt) / sizeof(int);
+  const size_t tab_ints = (size_t)st.NBg * sizeof(PoolRowRef) / sizeof(int), join_ints = (size_t)n * sizeof(PoolJoinEnt) / sizeof(int);
   if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * (sizeof(PoolRowRef) + sizeof(PoolJoinEnt)) / sizeof(int)))) return rc;
   int stride_max = 0;
   for (int i = 0; i < n; i++) {
-    auto& r = P->rows[take[i]];
+    auto& r = P->ext[take[i]];
     const int stride = item_stride(i);
     stride_max = std::max(stride_max, stride);
     const size_t need = (size_t)I * stride;
@@ -4417,9 +4458,9 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   const hipStream_t q = w.set.stream;
   PoolRowRef* tab = (PoolRowRef*)sg.h_desc;  // the whole row table as it stands after this join, then the join's own table
   PoolJoinEnt* jt = (PoolJoinEnt*)(sg.h_desc + tab_ints);
-  for (int r = 0; r < P->NBg; r++) {
-    tab[r].z = r < P->capacity ? P->rows[r].z : nullptr;
-    tab[r].stride = r < P->capacity ? P->rows[r].stride : 0;
+  for (int r = 0; r < st.NBg; r++) {
+    tab[r].z = r < capacity ? P->ext[r].z : nullptr;
+    tab[r].stride = r < capacity ? P->ext[r].stride : 0;
   }
   for (int i = 0; i < n; i++) {
     tab[take[i]].stride = item_stride(i);
@@ -4434,10 +4475,10 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
     const float* spk_src = w.spk_bias ? w.spk_bias + v->spk_pre_off : nullptr;
     if (bound)
       hipLaunchKernelGGL(stream_adopt_bounded_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, w.lensF, want_rep,
-                         (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I, spk_src, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr,
+                         (const PoolJoinEnt*)(P->d_rows + st.NBg), P->d_rows, I, spk_src, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr,
                          v->cfg.up_initial, P->d_rep);
     else
-      hipLaunchKernelGGL(stream_adopt_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, (const PoolJoinEnt*)(P->d_rows + P->NBg), P->d_rows, I,
+      hipLaunchKernelGGL(stream_adopt_kernel, dim3(gx, n), dim3(256), 0, q, w.z_out, w.F, (const PoolJoinEnt*)(P->d_rows + st.NBg), P->d_rows, I,
                          spk_src, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr, v->cfg.up_initial);
     e = hipGetLastError();
   }
@@ -4446,21 +4487,22 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   P->ev_pending.push_back(ev);
   if (bound) P->bounded.push_back(StreamPool::BoundedJoin{ev, work_slot, &w, w.last_use});
   for (int i = 0; i < n; i++) {  // active from the next step on
-    auto& r = P->rows[take[i]];
-    r.stride = item_stride(i);
+    StreamRow& r = st.rows[take[i]];
+    StreamPool::Row& x = P->ext[take[i]];
+    x.stride = item_stride(i);
     r.F = bound ? 0 : w.h_F[i];  // (bounded: pool_resolve brings it before any step reads it)
     r.next = 0;
     r.active = true;
-    r.pending = bound != 0;
-    r.held = !bound;
-    r.over_want = r.over_cap = 0;
-    r.fmt = P->rs.mixed ? jf[i] : RowFormat();
+    x.pending = bound != 0;
+    x.held = !bound;
+    x.over_want = x.over_cap = 0;
+    r.fmt = st.rs.mixed ? jf[i] : RowFormat();
     if (items_out) items_out[i] = take[i];
     const RsDesign* item_d = rate_d;
     if (r.fmt.rate) (void)rs_design(v->cfg.sample_rate, r.fmt.rate, &item_d);  // (checked above)
     if (samples_out) samples_out[i] = item_d ? rs_count(*item_d, (int64_t)w.h_F[i] * v->hop) : (int64_t)w.h_F[i] * v->hop;
   }
-  P->rs.started = true;  // the pool's output rate is fixed from its first join on
+  st.rs.started = true;  // the pool's output rate is fixed from its first join on
   return PIPER_HIP_OK;
 }
 }  // namespace
@@ -4480,16 +4522,7 @@ PH_EXPORT int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int s
   const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   // prepare_batch_bounded's own refusals, before anything of the pool is looked at or regrown (it repeats them)
-  if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join_bounded: %d items outside [1,256]", n);
-  if (max_frames < 1 || (int64_t)max_frames * std::max(v->hop, 1) > 0x3fffffff / 64)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_pool_join_bounded: max_frames %d out of range", max_frames);
-  if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0): supply durations (stream_pool_join)");
-  for (int b = 0; b < n; b++) {
-    if (int rc = check_item(utts[b], b)) return rc;
-    if (utts[b].durations || utts[b].noise)
-      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: stream_pool_join_bounded predicts the durations and cannot take a host noise tensor (its shape "
-                                 "depends on them): pass durations = noise = NULL (noise_mode DEVICE draws it on the device)", b);
-  }
+  if (int rc = bounded_refusals(v, utts, n, work_slot, max_frames, true)) return rc;
   return pool_join(v, slot, utts, n, work_slot, fmts, fmts != nullptr, items_out, nullptr, max_frames);
 }
 
@@ -4497,16 +4530,17 @@ PH_EXPORT int piper_hip_voice_stream_pool_item_samples(piper_hip_voice* v, int s
   if (!v || !samples) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
   if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
-  if (item < 0 || item >= P->capacity) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_item_samples: item %d outside [0,%d)", item, P->capacity);
-  if (P->rows[item].pending)
+  if (item < 0 || item >= P->st.items()) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_item_samples: item %d outside [0,%d)", item, P->st.items());
+  if (P->ext[item].pending)
     if (int rc = pool_resolve(v, *P)) return rc;
-  const auto& r = P->rows[item];
+  const StreamPool::Row& r = P->ext[item];
+  const StreamRow& row = P->st.rows[item];
   if (r.over_want > 0)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream pool row %d: the predictor wants %d frames, the join allowed %d — the item delivers nothing and its row is "
                                  "free: join it again with a larger bound", item, r.over_want, r.over_cap);
   if (!r.held) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_pool_item_samples: row %d of the pool on slot %d holds no item whose length is known", item, slot);
-  const int64_t N = (int64_t)r.F * v->hop;
-  const int rate = P->rs.mixed ? r.fmt.rate : P->rs.rate;
+  const int64_t N = (int64_t)row.F * v->hop;
+  const int rate = P->st.rs.mixed ? row.fmt.rate : P->st.rs.rate;
   const RsDesign* d = nullptr;
   if (rate)
     if (int rc = rs_design(v->cfg.sample_rate, rate, &d)) return rc;
@@ -4547,16 +4581,19 @@ PH_EXPORT int piper_hip_voice_stream_pool_close(piper_hip_voice* v, int slot) {
 namespace {
 // collect_pcm16, and collect_pcm16_rate where out_rate differs from the voice's own: then item b is J(its true samples) long and the pack
 // kernel's place is taken by the resampling one (rd / rf: its filter); everything else — the peaks, the route, the landing — is shared.
-// law = PIPER_HIP_G711_*: collect_g711 — the same kernels with their one-byte sink, host_pcm a byte buffer.
-int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int out_rate, void* host_pcm, int64_t max_samples, int law) {
+// A G.711 sink: collect_g711 — the same kernels with their one-byte sink, the host buffer a byte buffer. The sink's gain is the params',
+// read here behind the slot's own refusal.
+int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int out_rate, Sink out) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  const size_t elem = law ? 1 : sizeof(int16_t);
+  const size_t elem = fmt_elem(out.enc);
+  const int law = sink_law(out);
+  void* const host_pcm = out.host;
   Slot* p = slot_plan(v, slot);
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
-  float gain;
   bool normalize;
-  int rc = pcm_params(params, &gain, &normalize);
+  int rc = pcm_params(params, &out.gain, &normalize);
   if (rc) return rc;
+  const float gain = out.gain;
   const RsDesign* rd = nullptr;
   RsFilter rf{};
   if (out_rate != v->cfg.sample_rate) {
@@ -4579,11 +4616,11 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   int64_t need = 0;
   if (bounded) need = out_len((int64_t)F * hop) * NB;
   else for (int b = 0; b < NB; b++) need += out_len((int64_t)s.h_F[b] * hop);
-  if (max_samples < need) {
+  if (out.cap < need) {
     if (bounded)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_prepared_samples before collect), got %lld",
-              (long long)need, (long long)max_samples);
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: buffer holds %lld < %lld samples", (long long)max_samples, (long long)need);
+              (long long)need, (long long)out.cap);
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: buffer holds %lld < %lld samples", (long long)out.cap, (long long)need);
   }
   float* peaks_host = nullptr;
   if (normalize) {
@@ -4619,12 +4656,12 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
 
 PH_EXPORT int piper_hip_voice_collect_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm, int64_t max_samples) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  return collect_pcm(v, slot, params, v->cfg.sample_rate, host_pcm, max_samples, 0);
+  return collect_pcm(v, slot, params, v->cfg.sample_rate, Sink{host_pcm, max_samples, PIPER_HIP_ENC_S16});
 }
 
 PH_EXPORT int piper_hip_voice_collect_pcm16_rate(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int32_t out_rate, int16_t* host_pcm,
                                                  int64_t max_samples) {
-  return collect_pcm(v, slot, params, out_rate, host_pcm, max_samples, 0);
+  return collect_pcm(v, slot, params, out_rate, Sink{host_pcm, max_samples, PIPER_HIP_ENC_S16});
 }
 
 PH_EXPORT int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* peaks, int max_items) {
@@ -4637,248 +4674,191 @@ PH_EXPORT int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* p
   return PIPER_HIP_OK;
 }
 
-PH_EXPORT int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int16_t* host_pcm,
-                                               int64_t max_samples, int64_t* n_samples) {
-  const ProsodyClear pc{v, 0};  // a staging call on slot 0
-  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  float gain;
-  bool normalize;
-  int rc = pcm_params(params, &gain, &normalize);
-  if (rc) return rc;
-  if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
-  if ((rc = piper_hip_voice_launch(v, 0))) return rc;
-  if ((rc = piper_hip_voice_collect_pcm16(v, 0, params, host_pcm, max_samples))) return rc;
-  if (n_samples) *n_samples = (int64_t)v->attached[0]->h_F[0] * v->hop;
-  return PIPER_HIP_OK;
-}
+namespace {
+int g711_law(const char* who, int law);
 
-PH_EXPORT int piper_hip_voice_synthesize_pcm16_rate(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params,
-                                                    int32_t out_rate, int16_t* host_pcm, int64_t max_samples, int64_t* n_samples) {
+// synthesize_pcm16 / _pcm16_rate / _g711: prepare, launch and collect_pcm on slot 0. The refusals come in
+// the order law (who != nullptr: a G.711 entry point, enc is the caller's law), params, rate design, prepare.
+int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int out_rate, const char* who, int enc,
+                   void* host, int64_t max_samples, int64_t* n_samples) {
   const ProsodyClear pc{v, 0};  // a staging call on slot 0
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   float gain;
   bool normalize;
-  int rc = pcm_params(params, &gain, &normalize);
+  int rc = who ? g711_law(who, enc) : PIPER_HIP_OK;
+  if (!rc) rc = pcm_params(params, &gain, &normalize);
   if (rc) return rc;
   const RsDesign* rd = nullptr;
   if (out_rate != v->cfg.sample_rate && (rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
   if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
-  if ((rc = collect_pcm(v, 0, params, out_rate, host_pcm, max_samples, 0))) return rc;
+  if ((rc = collect_pcm(v, 0, params, out_rate, Sink{host, max_samples, enc}))) return rc;
   const int64_t n = (int64_t)v->attached[0]->h_F[0] * v->hop;
   if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
   return PIPER_HIP_OK;
 }
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int16_t* host_pcm,
+                                               int64_t max_samples, int64_t* n_samples) {
+  return synthesize_pcm(v, u, params, v ? v->cfg.sample_rate : 0, nullptr, PIPER_HIP_ENC_S16, host_pcm, max_samples, n_samples);
+}
+
+PH_EXPORT int piper_hip_voice_synthesize_pcm16_rate(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params,
+                                                    int32_t out_rate, int16_t* host_pcm, int64_t max_samples, int64_t* n_samples) {
+  return synthesize_pcm(v, u, params, out_rate, nullptr, PIPER_HIP_ENC_S16, host_pcm, max_samples, n_samples);
+}
 
 namespace {
-// The stream slot id `slot` holds, as the rate entry points see it: its rate record, generator rows, items and samples per row and step.
-struct StreamRef {
-  StreamRate* rs = nullptr;
-  int rows = 0, items = 0;
-  int64_t chunk_samples = 0;
-  StreamPool* pool = nullptr;
-  Slot* plan = nullptr;
-};
-int stream_ref(piper_hip_voice* v, int slot, const char* who, StreamRef* r) {
-  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  if (StreamPool* P = slot_pool(v, slot)) {
-    *r = StreamRef{&P->rs, P->NBg, P->capacity, (int64_t)P->chunk * v->hop, P, nullptr};
-    return PIPER_HIP_OK;
-  }
+// The stream slot id `slot` holds — a pool's, a group's or a single one — for the entry point `who`.
+Stream* slot_stream(piper_hip_voice* v, int slot, const char* who) {
+  if (!v) { ph::set_error("null voice"); return nullptr; }
+  if (StreamPool* P = slot_pool(v, slot)) return &P->st;
   Slot* sp = slot_plan(v, slot);
-  if (sp && !sp->bs_rows.empty()) {
-    const int n = (int)sp->bs_rows.size();
-    *r = StreamRef{&sp->rs, group_batch(n), n, (int64_t)sp->st_chunk * v->hop, nullptr, sp};
-    return PIPER_HIP_OK;
-  }
-  if (sp && sp->st_next >= 0) {
-    *r = StreamRef{&sp->rs, 1, 1, (int64_t)sp->st_chunk * v->hop, nullptr, sp};
-    return PIPER_HIP_OK;
-  }
-  PH_FAIL(PIPER_HIP_ERR_ARG, "%s: slot %d has no stream in progress", who, slot);
+  if (sp && !sp->stream.rows.empty()) return &sp->stream;
+  ph::set_error("%s: slot %d has no stream in progress", who, slot);
+  return nullptr;
 }
-int rate_buffers(piper_hip_voice* v, const StreamRef& r);
-int pack_buffer(piper_hip_voice* v, const StreamRef& r, size_t pack_bytes);
+// the same for the mixed entry points: a batched stream (group or pool) that stream_set_mixed has marked
+Stream* slot_stream_mixed(piper_hip_voice* v, int slot, const char* who) {
+  Stream* st = slot_stream(v, slot, who);
+  if (st && !st->rs.mixed) { ph::set_error("%s: slot %d is not mixed (stream_set_mixed)", who, slot); return nullptr; }
+  return st;
+}
+bool is_pool(const Stream& st) { return !st.plan; }
+int64_t chunk_samples(const piper_hip_voice* v, const Stream& st) { return (int64_t)st.chunk * v->hop; }
+int rate_buffers(piper_hip_voice* v, Stream& st);
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int32_t out_rate) {
-  StreamRef r;
-  int rc = stream_ref(v, slot, "stream_set_rate", &r);
-  if (rc) return rc;
-  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d is mixed: every row has its own rate", slot);
-  if (r.rs->started)
-    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d has %s: the rate is set before", slot, r.pool ? "stepped or been joined" : "stepped");
+  Stream* sp = slot_stream(v, slot, "stream_set_rate");
+  if (!sp) return PIPER_HIP_ERR_ARG;
+  Stream& st = *sp;
+  StreamRate& rs = st.rs;
+  if (rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d is mixed: every row has its own rate", slot);
+  if (rs.started)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d has %s: the rate is set before", slot, is_pool(st) ? "stepped or been joined" : "stepped");
   if (out_rate == v->cfg.sample_rate) {  // not a filter: the steps are the un-resampled ones
-    r.rs->rate = 0;
+    rs.rate = 0;
     return PIPER_HIP_OK;
   }
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   const RsDesign* rd = nullptr;
   RsFilter rf{};
+  int rc;
   if ((rc = voice_filter(v, out_rate, &rd, &rf))) return rc;
   // the history and the descriptor of the stream's rows, and a packed-output buffer that holds a step at this rate
-  const size_t pack_bytes = (size_t)r.items * (size_t)rs_step_bound(*rd, r.chunk_samples) * sizeof(int16_t);
-  if ((rc = rate_buffers(v, r))) return rc;
-  if ((rc = pack_buffer(v, r, pack_bytes))) return rc;
-  r.rs->parity = 0;
-  r.rs->rate = out_rate;
+  if ((rc = rate_buffers(v, st))) return rc;
+  if ((rc = pack_buffer(v, st, (size_t)st.items() * (size_t)rs_step_bound(*rd, chunk_samples(v, st)) * sizeof(int16_t)))) return rc;
+  rs.parity = 0;
+  rs.rate = out_rate;
   return PIPER_HIP_OK;
 }
 
 namespace {
 // The per-row history [2][rows][kRsHist] and the RsStepRow table of the stream's generator rows (kept when they are large enough already).
-int rate_buffers(piper_hip_voice* v, const StreamRef& r) {
-  const size_t hist_bytes = (size_t)2 * r.rows * kRsHist * sizeof(float), desc_bytes = (size_t)r.rows * sizeof(RsStepRow);
-  void* p = nullptr;
+int rate_buffers(piper_hip_voice* v, Stream& st) {
+  StreamRate& rs = st.rs;
+  if (rs.rows >= st.NBg) return PIPER_HIP_OK;
+  const size_t hist_row = (size_t)2 * kRsHist * sizeof(float);
+  stream_free(v, st, rs.hist, rs.rows * hist_row);
+  stream_free(v, st, rs.desc, rs.rows * sizeof(RsStepRow));
+  rs.hist = nullptr; rs.desc = nullptr; rs.rows = 0;
+  void *h = nullptr, *d = nullptr;
   int rc;
-  if (r.rs->rows < r.rows) {
-    if (r.pool) {
-      if (r.rs->hist) (void)v->ctx->pool.release(r.rs->hist);
-      if (r.rs->desc) (void)v->ctx->pool.release(r.rs->desc);
-      r.rs->hist = nullptr; r.rs->desc = nullptr; r.rs->rows = 0;
-      if ((rc = v->ctx->pool.alloc(hist_bytes, &p))) return rc;
-      r.rs->hist = (float*)p;
-      if ((rc = v->ctx->pool.alloc(desc_bytes, &p))) return rc;
-      r.rs->desc = (RsStepRow*)p;
-    } else {  // (a plan keeps what an earlier, smaller stream allocated until it is released)
-      r.rs->rows = 0;
-      if ((rc = plan_alloc(v, *r.plan, hist_bytes, &p))) return rc;
-      r.rs->hist = (float*)p;
-      if ((rc = plan_alloc(v, *r.plan, desc_bytes, &p))) return rc;
-      r.rs->desc = (RsStepRow*)p;
-    }
-    r.rs->rows = r.rows;
-  }
-  return PIPER_HIP_OK;
-}
-
-// A packed-output buffer of at least pack_bytes for the stream (no step is in flight: every step ends with a wait).
-int pack_buffer(piper_hip_voice* v, const StreamRef& r, size_t pack_bytes) {
-  void* p = nullptr;
-  int rc;
-  if (r.pool && r.pool->pack_bytes < pack_bytes) {
-    if ((rc = v->ctx->pool.alloc(pack_bytes, &p))) return rc;
-    if (r.pool->pack) (void)v->ctx->pool.release(r.pool->pack);  // (no step has run on this pool)
-    r.pool->pack = (float*)p;
-    r.pool->pack_bytes = pack_bytes;
-  }
-  if (r.plan && !r.plan->bs_rows.empty() && r.plan->bs_pack_cap * sizeof(float) < pack_bytes) {
-    Slot& s = *r.plan;  // (every step ends with a wait: nothing of an earlier stream on this plan still reads the buffer)
-    if (s.bs_pack) plan_free(v, s, s.bs_pack, s.bs_pack_cap * sizeof(float));
-    s.bs_pack = nullptr;
-    s.bs_pack_cap = 0;
-    const size_t floats = (pack_bytes + sizeof(float) - 1) / sizeof(float);
-    if ((rc = plan_alloc(v, s, floats * sizeof(float), &p))) return rc;
-    s.bs_pack = (float*)p;
-    s.bs_pack_cap = floats;
-  }
-  return PIPER_HIP_OK;
-}
-
-// the StreamRow of item / row i of the batched stream r refers to
-StreamRow& ref_row(const StreamRef& r, int i) { return r.pool ? (StreamRow&)r.pool->rows[i] : r.plan->bs_rows[i]; }
-
-// stream_ref for the mixed entry points: a batched stream (group or pool) that stream_set_mixed has marked
-int mixed_ref(piper_hip_voice* v, int slot, const char* who, StreamRef* r) {
-  if (int rc = stream_ref(v, slot, who, r)) return rc;
-  if (!r->rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "%s: slot %d is not mixed (stream_set_mixed)", who, slot);
+  if ((rc = stream_alloc(v, st, st.NBg * hist_row, &h))) return rc;
+  if ((rc = stream_alloc(v, st, st.NBg * sizeof(RsStepRow), &d))) { stream_free(v, st, h, st.NBg * hist_row); return rc; }
+  rs.hist = (float*)h;
+  rs.desc = (RsStepRow*)d;
+  rs.rows = st.NBg;
   return PIPER_HIP_OK;
 }
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot) {
-  StreamRef r;
-  const int rc = stream_ref(v, slot, "stream_rate", &r);
-  if (rc) return rc;
-  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_rate: slot %d is mixed: every row has its own rate (stream_item_format)", slot);
-  return r.rs->rate ? r.rs->rate : v->cfg.sample_rate;
+  const Stream* st = slot_stream(v, slot, "stream_rate");
+  if (!st) return PIPER_HIP_ERR_ARG;
+  if (st->rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_rate: slot %d is mixed: every row has its own rate (stream_item_format)", slot);
+  return st->rs.rate ? st->rs.rate : v->cfg.sample_rate;
 }
 
 // ---- mixed formats (include/piper_hip.h "Mixed formats")
 
 PH_EXPORT int piper_hip_voice_stream_set_mixed(piper_hip_voice* v, int slot) {
-  StreamRef r;
-  int rc = stream_ref(v, slot, "stream_set_mixed", &r);
-  if (rc) return rc;
-  if (!r.pool && r.plan->bs_rows.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d holds a single stream (stream_set_rate and a law per step serve it)", slot);
-  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d is mixed already", slot);
-  if (r.rs->rate) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has the output rate %d set", slot, r.rs->rate);
-  if (r.rs->started)
-    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has %s", slot, r.pool ? "stepped or been joined" : "stepped");
+  Stream* sp = slot_stream(v, slot, "stream_set_mixed");
+  if (!sp) return PIPER_HIP_ERR_ARG;
+  Stream& st = *sp;
+  StreamRate& rs = st.rs;
+  if (st.single) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d holds a single stream (stream_set_rate and a law per step serve it)", slot);
+  if (rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d is mixed already", slot);
+  if (rs.rate) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has the output rate %d set", slot, rs.rate);
+  if (rs.started)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has %s", slot, is_pool(st) ? "stepped or been joined" : "stepped");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  if ((rc = rate_buffers(v, r))) return rc;
-  if (r.rs->mix_rows < r.rows) {
+  int rc;
+  if ((rc = rate_buffers(v, st))) return rc;
+  if (rs.mix_rows < st.NBg) {
+    stream_free(v, st, rs.mdesc, (size_t)rs.mix_rows * sizeof(MixStepRow));
+    rs.mdesc = nullptr; rs.mix_rows = 0;
     void* p = nullptr;
-    const size_t bytes = (size_t)r.rows * sizeof(MixStepRow);
-    if (r.pool) {
-      if (r.rs->mdesc) (void)v->ctx->pool.release(r.rs->mdesc);
-      r.rs->mdesc = nullptr; r.rs->mix_rows = 0;
-      if ((rc = v->ctx->pool.alloc(bytes, &p))) return rc;
-    } else {  // (a plan keeps what an earlier, smaller stream allocated until it is released)
-      r.rs->mix_rows = 0;
-      if ((rc = plan_alloc(v, *r.plan, bytes, &p))) return rc;
-    }
-    r.rs->mdesc = (MixStepRow*)p;
-    r.rs->mix_rows = r.rows;
+    if ((rc = stream_alloc(v, st, (size_t)st.NBg * sizeof(MixStepRow), &p))) return rc;
+    rs.mdesc = (MixStepRow*)p;
+    rs.mix_rows = st.NBg;
   }
-  for (int i = 0; i < r.items; i++) ref_row(r, i).fmt = RowFormat();  // (s16 at the voice's rate: the buffer of the begin / open holds it)
-  r.rs->parity = 0;
-  r.rs->mixed = true;
+  for (StreamRow& row : st.rows) row.fmt = RowFormat();  // (s16 at the voice's rate: the buffer of the begin / open holds it)
+  rs.parity = 0;
+  rs.mixed = true;
   return PIPER_HIP_OK;
 }
 
 PH_EXPORT int piper_hip_voice_stream_item_formats(piper_hip_voice* v, int slot, const piper_hip_stream_format* fmts, int n) {
-  StreamRef r;
-  int rc = mixed_ref(v, slot, "stream_item_formats", &r);
-  if (rc) return rc;
-  if (r.pool) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: slot %d holds a pool: the join brings the formats (stream_pool_join_formats)", slot);
+  Stream* sp = slot_stream_mixed(v, slot, "stream_item_formats");
+  if (!sp) return PIPER_HIP_ERR_ARG;
+  Stream& st = *sp;
+  if (is_pool(st)) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: slot %d holds a pool: the join brings the formats (stream_pool_join_formats)", slot);
   if (!fmts || n < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: %d formats", fmts ? n : 0);
-  if (r.rs->started) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: slot %d has stepped: a row keeps its format", slot);
-  std::vector<RowFormat> f(r.items);
-  for (int i = 0; i < r.items; i++)
+  if (st.rs.started) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_formats: slot %d has stepped: a row keeps its format", slot);
+  const int items = st.items();
+  std::vector<RowFormat> f(items);
+  int rc;
+  for (int i = 0; i < items; i++)
     if ((rc = check_format(v, "stream_item_formats", fmts[std::min(i, n - 1)], &f[i]))) return rc;
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   int64_t bytes = 0;
-  for (int i = 0; i < r.items; i++) {
+  for (int i = 0; i < items; i++) {
     RsFilter ff{};
     if (f[i].rate && (rc = voice_filter(v, f[i].rate, nullptr, &ff))) return rc;
-    bytes += fmt_step_bytes(v, f[i], r.chunk_samples);
+    bytes += fmt_step_bytes(v, f[i], chunk_samples(v, st));
   }
-  if ((rc = pack_buffer(v, r, (size_t)bytes))) return rc;
-  for (int i = 0; i < r.items; i++) ref_row(r, i).fmt = f[i];
+  if ((rc = pack_buffer(v, st, (size_t)bytes))) return rc;
+  for (int i = 0; i < items; i++) st.rows[i].fmt = f[i];
   return PIPER_HIP_OK;
 }
 
 PH_EXPORT int piper_hip_voice_stream_next_batch_mixed(piper_hip_voice* v, int slot, void* host, int64_t max_bytes, int64_t* n_samples,
                                                       int64_t* byte_off) {
   if (!v || !n_samples || !byte_off) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  StreamRef r;
-  const int rc = mixed_ref(v, slot, "stream_next_batch_mixed", &r);
-  if (rc) return rc;
+  if (!slot_stream_mixed(v, slot, "stream_next_batch_mixed")) return PIPER_HIP_ERR_ARG;
   if (!host) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch_mixed: a mixed step needs a buffer");
-  return batch_step(v, slot, nullptr, max_bytes, n_samples, true, host, 1.0f, 0, byte_off);
+  return batch_step(v, slot, Sink{host, max_bytes, PIPER_HIP_ENC_S16, 1.0f, byte_off}, n_samples);
 }
 
 PH_EXPORT int64_t piper_hip_voice_stream_step_capacity_bytes(piper_hip_voice* v, int slot) {
-  StreamRef r;
-  const int rc = mixed_ref(v, slot, "stream_step_capacity_bytes", &r);
-  if (rc) return rc;
+  const Stream* st = slot_stream_mixed(v, slot, "stream_step_capacity_bytes");
+  if (!st) return PIPER_HIP_ERR_ARG;
   int64_t bytes = 0;
-  for (int i = 0; i < r.items; i++) {
-    const StreamRow& row = ref_row(r, i);
-    if (row.active) bytes += fmt_step_bytes(v, row.fmt, r.chunk_samples);
-  }
+  for (const StreamRow& row : st->rows)
+    if (row.active) bytes += fmt_step_bytes(v, row.fmt, chunk_samples(v, *st));
   return bytes;
 }
 
 PH_EXPORT int piper_hip_voice_stream_item_format(piper_hip_voice* v, int slot, int item, piper_hip_stream_format* out) {
-  StreamRef r;
-  const int rc = mixed_ref(v, slot, "stream_item_format", &r);
-  if (rc) return rc;
+  const Stream* st = slot_stream_mixed(v, slot, "stream_item_format");
+  if (!st) return PIPER_HIP_ERR_ARG;
   if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: null output");
-  if (item < 0 || item >= r.items) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: item %d outside [0,%d)", item, r.items);
-  const StreamRow& row = ref_row(r, item);
-  if (r.pool && !row.active) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: row %d of the pool on slot %d is free", item, slot);
+  if (item < 0 || item >= st->items()) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: item %d outside [0,%d)", item, st->items());
+  const StreamRow& row = st->rows[item];
+  if (is_pool(*st) && !row.active) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_item_format: row %d of the pool on slot %d is free", item, slot);
   out->out_rate = row.fmt.rate;
   out->encoding = row.fmt.enc;
   out->gain = row.fmt.gain;
@@ -4886,14 +4866,13 @@ PH_EXPORT int piper_hip_voice_stream_item_format(piper_hip_voice* v, int slot, i
 }
 
 PH_EXPORT int64_t piper_hip_voice_stream_step_capacity(piper_hip_voice* v, int slot) {
-  StreamRef r;
-  int rc = stream_ref(v, slot, "stream_step_capacity", &r);
-  if (rc) return rc;
-  if (r.rs->mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_step_capacity: slot %d is mixed: stream_step_capacity_bytes", slot);
-  if (!r.rs->rate) return (int64_t)r.items * r.chunk_samples;
+  const Stream* st = slot_stream(v, slot, "stream_step_capacity");
+  if (!st) return PIPER_HIP_ERR_ARG;
+  if (st->rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_step_capacity: slot %d is mixed: stream_step_capacity_bytes", slot);
+  if (!st->rs.rate) return (int64_t)st->items() * chunk_samples(v, *st);
   const RsDesign* rd = nullptr;
-  if ((rc = rs_design(v->cfg.sample_rate, r.rs->rate, &rd))) return rc;
-  return (int64_t)r.items * rs_step_bound(*rd, r.chunk_samples);
+  if (int rc = rs_design(v->cfg.sample_rate, st->rs.rate, &rd)) return rc;
+  return (int64_t)st->items() * rs_step_bound(*rd, chunk_samples(v, *st));
 }
 
 namespace {
@@ -4914,7 +4893,7 @@ PH_EXPORT int piper_hip_voice_stream_next_pcm16(piper_hip_voice* v, int slot, co
   const int rc = pcm_step_params(v, params, &gain);
   if (rc) return rc;
   if (slot_pool(v, slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a streaming pool: use stream_next_batch_pcm16", slot);
-  return stream_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain, 0);
+  return stream_step(v, slot, Sink{host_pcm, max_samples, PIPER_HIP_ENC_S16, gain}, n_samples);
 }
 
 PH_EXPORT int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
@@ -4922,7 +4901,7 @@ PH_EXPORT int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int sl
   float gain;
   const int rc = pcm_step_params(v, params, &gain);
   if (rc) return rc;
-  return batch_step(v, slot, nullptr, max_samples, n_samples, true, host_pcm, gain, 0);
+  return batch_step(v, slot, Sink{host_pcm, max_samples, PIPER_HIP_ENC_S16, gain}, n_samples);
 }
 
 // ---- G.711 (include/piper_hip.h "G.711 output"): the PCM entry points with a one-byte sink; the law is an argument of each call ---------
@@ -4937,26 +4916,12 @@ PH_EXPORT int piper_hip_voice_collect_g711(piper_hip_voice* v, int slot, const p
                                            uint8_t* host, int64_t max_samples) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   if (int rc = g711_law("collect_g711", law)) return rc;
-  return collect_pcm(v, slot, params, out_rate, host, max_samples, law);
+  return collect_pcm(v, slot, params, out_rate, Sink{host, max_samples, law});
 }
 
 PH_EXPORT int piper_hip_voice_synthesize_g711(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int law,
                                               int32_t out_rate, uint8_t* host, int64_t max_samples, int64_t* n_samples) {
-  const ProsodyClear pc{v, 0};  // a staging call on slot 0
-  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  float gain;
-  bool normalize;
-  int rc = g711_law("synthesize_g711", law);
-  if (!rc) rc = pcm_params(params, &gain, &normalize);
-  if (rc) return rc;
-  const RsDesign* rd = nullptr;
-  if (out_rate != v->cfg.sample_rate && (rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
-  if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
-  if ((rc = piper_hip_voice_launch(v, 0))) return rc;
-  if ((rc = collect_pcm(v, 0, params, out_rate, host, max_samples, law))) return rc;
-  const int64_t n = (int64_t)v->attached[0]->h_F[0] * v->hop;
-  if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
-  return PIPER_HIP_OK;
+  return synthesize_pcm(v, u, params, out_rate, "synthesize_g711", law, host, max_samples, n_samples);
 }
 
 PH_EXPORT int piper_hip_voice_stream_next_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
@@ -4966,7 +4931,7 @@ PH_EXPORT int piper_hip_voice_stream_next_g711(piper_hip_voice* v, int slot, con
   if (!rc) rc = g711_law("stream_next_g711", law);
   if (rc) return rc;
   if (slot_pool(v, slot)) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds a streaming pool: use stream_next_batch_g711", slot);
-  return stream_step(v, slot, nullptr, max_samples, n_samples, true, host, gain, law);
+  return stream_step(v, slot, Sink{host, max_samples, law, gain}, n_samples);
 }
 
 PH_EXPORT int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
@@ -4975,7 +4940,7 @@ PH_EXPORT int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slo
   int rc = pcm_step_params(v, params, &gain);
   if (!rc) rc = g711_law("stream_next_batch_g711", law);
   if (rc) return rc;
-  return batch_step(v, slot, nullptr, max_samples, n_samples, true, host, gain, law);
+  return batch_step(v, slot, Sink{host, max_samples, law, gain}, n_samples);
 }
 
 PH_EXPORT int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utterance* u, float* host_audio,

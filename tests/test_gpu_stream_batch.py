@@ -180,3 +180,43 @@ def test_limits_and_errors(rt_medium):
     assert lib.piper_hip_voice_stream_next_batch(v, 12, None, 0, got) != 0  # slot 12 holds no stream
     rest = list(it)  # the refused calls left the group intact
     assert len(rest) == -(-84 // 16) - 1
+
+
+def test_repeated_streams_keep_buffers_and_bits(backend, voices):
+    """Who owns a stream's device buffers, across repeated streams on one slot id: three factor-1 items at chunk 8 as a group in fp32, at
+    8000 Hz int16 and mixed (s16 at 8000, mu-law, f32), then through a mixed pool of 4 on another slot id that is closed again. Three
+    such cycles: the third delivers the first's chunks bit for bit, and neither the context pool's live bytes nor the plan cache grow
+    from the second to the third (a plan keeps its stream buffers across streams; a pool's go back when it closes)."""
+    cfg, blob = voices["medium"]
+    rt = ph.HipRuntime(backend, cfg, blob)
+    try:
+        group = [(kd.FIXTURE_IDS, [3] * 14, kd.sym(SD + 60 + k, (cfg.inter, 42), 1.7320508)) for k in range(3)]
+        fmts = [ph.stream_format(rate=8000, encoding="s16"), ph.stream_format(encoding="mulaw"), ph.stream_format(encoding="f32")]
+
+        def cycle():
+            out = []
+            for kw in ({}, {"rate": 8000}, {"formats": fmts}):
+                for chunks in rt.synthesize_stream_batch(group, 0.667, chunkFrames=8, slot=2, **kw):
+                    out.extend(chunks)
+            pool = rt.stream_pool(4, 4, chunkFrames=8, work_slot=5, mixed=True)
+            assert [r for r, _ in pool.join(group, formats=fmts)] == [0, 1, 2]
+            while True:
+                chunks = pool.step_mixed()
+                if not any(c.size for c in chunks):
+                    break
+                out.extend(chunks)
+            pool.close()
+            return out, (backend.memory_stats()["live"], rt.plan_info(2)["cached_plans"])
+
+        first, _ = cycle()
+        _, second = cycle()
+        third, after = cycle()
+        assert sum(c.size for c in first if c.dtype == np.float32) == (3 + 1 + 1) * 42 * cfg.hop  # fp32 group, the two f32 rows
+        assert {c.dtype for c in first if c.size} == {np.dtype(t) for t in (np.float32, np.int16, np.uint8)}
+        assert len(third) == len(first)
+        for i, (a, b) in enumerate(zip(first, third)):
+            assert a.dtype == b.dtype and np.array_equal(a, b), f"chunk {i} of cycle 3 differs from cycle 1"
+        print(f"after cycle 2: live bytes, cached plans = {second}; after cycle 3: {after}")
+        assert after == second
+    finally:
+        rt.close()
