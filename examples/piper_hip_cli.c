@@ -18,6 +18,8 @@
  *                            (piper_hip_voice_collect_g711 / synthesize_g711) — --output-raw is then one byte per sample, --output a
  *                            G.711 WAV at the output rate (piper_hip_wav_write_g711); combinable with --output-rate, --volume and
  *                            --normalize (with a law the last two act on --output as well: the file holds the same bytes).
+ *                            --drive X --ceiling Y --release-ms Z: a look-ahead limiter on the device in front of every output above
+ *                            (piper_hip_voice_slot_level on slot 0; a flag left out takes its default 1, 1, 50). Not with --normalize.
  *   --speaker N              both modes: speaker N of a multi-speaker voice (the graph's `sid`; piper_hip_voice_attach_speakers +
  *                            piper_hip_voice_slot_speakers). With --model the file's speaker table is loaded (opt-in: without the flag such a
  *                            file is refused; its node graph is NOT verified — no verifier for the conditioned graph exists yet); without
@@ -179,7 +181,7 @@ int main(int argc, char** argv) {
   if (!scale_bench && !ids_arg) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
-                    "                [--output-encoding s16le|mulaw|alaw]\n"
+                    "                [--output-encoding s16le|mulaw|alaw] [--drive X] [--ceiling Y] [--release-ms Z]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n"
                     "               [--speaker N [--speakers S]]\n", argv[0], argv[0]);
     return 2;
@@ -281,6 +283,13 @@ int main(int argc, char** argv) {
     piper_hip_pcm_params prm;
     prm.gain = arg_value(argc, argv, "--volume") ? (float)atof(arg_value(argc, argv, "--volume")) : 1.0f;
     prm.normalize = has_flag(argc, argv, "--normalize");
+    if (arg_value(argc, argv, "--drive") || arg_value(argc, argv, "--ceiling") || arg_value(argc, argv, "--release-ms")) {
+      piper_hip_level lv; /* slot 0's level: every collect below delivers the limited samples */
+      lv.drive = arg_value(argc, argv, "--drive") ? (float)atof(arg_value(argc, argv, "--drive")) : 0.0f;
+      lv.ceiling = arg_value(argc, argv, "--ceiling") ? (float)atof(arg_value(argc, argv, "--ceiling")) : 0.0f;
+      lv.release_ms = arg_value(argc, argv, "--release-ms") ? (float)atof(arg_value(argc, argv, "--release-ms")) : 0.0f;
+      CHECK(piper_hip_voice_slot_level(r.voice, 0, &lv));
+    }
     if (out) {
       CHECK(run_one(&r, ids, t, &n));
       CHECK(piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu));

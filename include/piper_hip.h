@@ -554,7 +554,7 @@ int piper_hip_voice_synthesize_pcm16(piper_hip_voice* v, const piper_hip_utteran
                                      int64_t max_samples, int64_t* n_samples);
 /* stream_next / stream_next_batch (groups and pools) with int16 samples. A PCM step consumes the step exactly as the float call does, and
  * float and PCM steps may alternate on one stream. normalize = 1 is PIPER_HIP_ERR_UNSUPPORTED and consumes nothing (an utterance's peak is
- * not known before its last window); gain is allowed. */
+ * not known before its last window); gain is allowed. The stream-safe alternative is a level ("Level control" below). */
 int piper_hip_voice_stream_next_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
                                       int64_t max_samples, int64_t* n_samples);
 int piper_hip_voice_stream_next_batch_pcm16(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int16_t* host_pcm,
@@ -611,7 +611,8 @@ int piper_hip_voice_synthesize_pcm16_rate(piper_hip_voice* v, const piper_hip_ut
  * J(N_i), and the float steps stream_next / stream_next_batch return PIPER_HIP_ERR_ARG and consume nothing. A max_samples too small is
  * PIPER_HIP_ERR_SHAPE and consumes nothing; normalize = 1 stays PIPER_HIP_ERR_UNSUPPORTED on steps; a step at a rate needs a buffer
  * (host_pcm == NULL is PIPER_HIP_ERR_ARG on single streams, groups and pools alike, and consumes nothing). A new begin / open resets the
- * slot to the voice's own rate. stream_rate reports the current rate (or a negative status). */
+ * slot to the voice's own rate. stream_rate reports the current rate (or a negative status). Where normalize = 1 is refused, a level
+ * ("Level control" below) is the stream-safe alternative. */
 int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int32_t out_rate);
 int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot);
 /* The int16 samples one step of that slot can deliver at its current rate (rows × the per-row bound), or a negative status. */
@@ -667,7 +668,8 @@ int piper_hip_voice_synthesize_g711(piper_hip_voice* v, const piper_hip_utteranc
  * the same output range [j0, j1), the same history update — so PCM and G.711 steps may alternate on one stream, and on a slot at the
  * voice's own rate float steps as well. n_samples[i] counts samples (= bytes); piper_hip_voice_stream_step_capacity answers for these
  * steps too. Refused calls follow the PCM steps and consume nothing: normalize = 1 is PIPER_HIP_ERR_UNSUPPORTED, a short buffer
- * PIPER_HIP_ERR_SHAPE, host == NULL on a slot with an output rate PIPER_HIP_ERR_ARG, a bad law PIPER_HIP_ERR_ARG. */
+ * PIPER_HIP_ERR_SHAPE, host == NULL on a slot with an output rate PIPER_HIP_ERR_ARG, a bad law PIPER_HIP_ERR_ARG. The stream-safe alternative to
+ * normalize = 1 is a level ("Level control" below). */
 int piper_hip_voice_stream_next_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
                                      int64_t max_samples, int64_t* n_samples);
 int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params, int law, uint8_t* host,
@@ -683,7 +685,7 @@ int piper_hip_voice_stream_next_batch_g711(piper_hip_voice* v, int slot, const p
  * whole-item conversion of the item's fp32 samples at the row's format, bit for bit; a mixed slot whose rows all carry one format
  * delivers, row by row, the bytes and counts of a slot with stream_set_rate and the matching step call.
  * Normalisation is not offered: a format has no field for it, because steps never could normalise. Single streams (stream_begin) are out
- * of scope: one row has stream_set_rate plus a law per step already.
+ * of scope: one row has stream_set_rate plus a law per step already. A level ("Level control" below) is the stream-safe alternative.
  *
  * Layout of one step's output. Rows are written in row order. Row r's chunk starts at byte_off[r] and holds n_samples[r] · elem(r) bytes,
  * elem = 2 for S16, 1 for G.711, 4 for F32. byte_off of the first delivering row is 0; every later one is the previous delivering row's
@@ -733,6 +735,69 @@ int64_t piper_hip_voice_stream_step_capacity_bytes(piper_hip_voice* v, int slot)
 /* The format of item / row `item` as the slot holds it: out_rate 0 when it is the voice's own rate, gain never 0. PIPER_HIP_ERR_ARG for
  * a free pool row, an item out of range, or a slot that is not mixed. */
 int piper_hip_voice_stream_item_format(piper_hip_voice* v, int slot, int item, piper_hip_stream_format* out);
+
+/* ---- Level control: a look-ahead limiter on every output route (DESIGN.md §4 "Level control") ----
+ * normalize = 1 needs an utterance's peak, which no stream step before the last knows. What a streaming pipeline uses instead is a
+ * look-ahead limiter: a drive, a ceiling and a short, known delay. It is one more stage of the output chain — generator → level →
+ * resampler → PCM / G.711 / mixed — on whole items and on every stream route, and it changes nothing for a request that does not ask
+ * for it. The limiter is a contract, bit for bit. All arithmetic is fp32, each operation rounded on its own (no FMA); fl() marks a rounding:
+ *   constants  B = 32 samples per block, W = 6 blocks of look-ahead      (PIPER_HIP_LEVEL_BLOCK, PIPER_HIP_LEVEL_LOOKAHEAD)
+ *   params     drive (0 is taken as 1.0), ceiling (0 → 1.0), release_ms (0 → 50)
+ *              drive finite in (0, 1000], ceiling in [0.001, 1], release_ms in [1, 10000]; otherwise PIPER_HIP_ERR_ARG
+ *   rel        = fp32( min(1, 32·1000 / (rate · release_ms)) ), computed in double and rounded once.
+ *              `rate` is the rate of the samples being limited: the voice's own rate on every voice route.
+ *   u[n]       = fl(x[n] · drive)                                          n in [0, N), at the voice's own rate, before any resampling
+ *   p[k]       = max |u[n]| over block k = [32k, 32k+32) ∩ [0, N).  NaN is ignored.  Blocks past the item have p = 0.
+ *   r[k]       = p[k] > ceiling ? the correctly rounded fp32 quotient ceiling / p[k] : 1.0f
+ *   m[k]       = min(r[k], r[k+1], …, r[k+W])
+ *   G[k]       = min(m[k], fl(G[k−1] + rel)),  G[−1] = 1.0f                 (linear release, instant hold)
+ *   node[0]    = G[0];  node[k] = min(G[k−1], G[k])                         k = 1 … K,  K = ceil(N / 32)
+ *   g(n)       = fl(node[k] + fl(fl(node[k+1] − node[k]) · (i / 32)))       k = n div 32, i = n mod 32.  i / 32 is exact.
+ *   y[n]       = fl(u[n] · g(n))
+ * y then goes through the contracts above unchanged: "Output rate", "16-bit PCM" with normalize = 0, "G.711 output", "Mixed formats"; the
+ * per-call or per-row gain is applied where it is applied without a level. Both nodes of block k are ≤ r[k], so |y| ≤ ceiling up to
+ * rounding (≤ ceiling · (1 + 2^−22)). An item that never exceeds the ceiling with drive 1 passes bit for bit: G stays 1.0 and ·1.0f is exact.
+ *
+ * Emit rule for streams. When samples [0, e) of N are known and more follow, y is final on [0, ready(e)), ready(e) = max(0, 32·(e div 32 −
+ * (W + 1))). A step whose chunk covers [s, e) hands the downstream stage the limited samples [lo, hi): lo where the previous step ended
+ * (0 at the start), hi = N when e == N, else ready(e). Downstream applies its own rule to that range as if it were the chunk: the
+ * "Output rate" emit rule with (s, e) = (lo, hi) on a rated or mixed row, hi − lo samples otherwise. The concatenation of a row's steps
+ * equals the whole-item result bit for bit, on every format. A step delivers at most (e − s) + 255 limited samples per row
+ * (piper_hip_level_step_bound); stream_step_capacity, stream_step_capacity_bytes and the share of a mixed row use that in place of
+ * chunk_frames · hop on a slot with a level. Enabling a level requires chunk_frames · hop ≥ 512, so that a non-final step never delivers
+ * nothing ("all zero" keeps meaning end / idle); smaller is PIPER_HIP_ERR_ARG. */
+#define PIPER_HIP_LEVEL_BLOCK     32
+#define PIPER_HIP_LEVEL_LOOKAHEAD 6
+typedef struct {
+  float drive;       /* 0 is taken as 1.0 */
+  float ceiling;     /* 0 is taken as 1.0 */
+  float release_ms;  /* 0 is taken as 50 */
+} piper_hip_level;   /* all zero = {1, 1, 50} */
+/* Host-only (no device needed). level_check: PIPER_HIP_ERR_ARG with a message that names the field. level_info: the fp32 rel of that level
+ * at `rate`. level_ready: ready(e). level_step_bound: n_in + 255. The two counts return a negative status on a negative argument. */
+int piper_hip_level_check(const piper_hip_level* level);
+int piper_hip_level_info(const piper_hip_level* level, int32_t rate, float* rel);
+int64_t piper_hip_level_ready(int64_t e);
+int64_t piper_hip_level_step_bound(int64_t n_in);
+/* Host-only twin of the kernels: n host floats → n host floats, the contract above. n may be 0. */
+int piper_hip_level_from_f32(const piper_hip_level* level, int32_t rate, const float* x, size_t n, float* y);
+/* Per-op: `count` device floats sampled at `rate` → `count` device floats. `*out` convention of the other ops; count may be 0. */
+int piper_hip_level_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t rate, const piper_hip_level* level, float** out,
+                        piper_hip_stream stream);
+/* Whole items: the level of slot id `slot`, state of the slot id like slot_speakers: it persists until replaced, or cleared with NULL.
+ * Every later collect, collect_pcm16, collect_pcm16_rate, collect_g711 and the synthesize twins (slot 0) on that slot deliver y instead of
+ * x, on plain, ragged and bounded slots. The fp32 audio in the plan stays raw: collects with and without a level may follow one launch in
+ * any order, and the `audio` tap keeps returning x. normalize = 1 together with a level is PIPER_HIP_ERR_ARG, before anything is waited for. */
+int piper_hip_voice_slot_level(piper_hip_voice* v, int slot, const piper_hip_level* level);
+/* Streams: the level of the stream on `slot`, for every row of it. Allowed exactly where stream_set_rate is: after stream_begin,
+ * stream_begin_batch or stream_pool_open, before the slot's first step, and for a pool also before its first join; later it is
+ * PIPER_HIP_ERR_ARG. It combines with stream_set_rate or stream_set_mixed in either order, and a new begin / open clears it. All step
+ * flavours work on such a slot — float, pcm16, g711, mixed — with their refusals unchanged. A pool row taken by a new occupant starts with
+ * lo = 0 and G[−1] = 1 and never reads its predecessor's carry. stream_pool_join's samples_out and stream_pool_item_samples are unchanged:
+ * the limiter neither adds nor drops samples over an item. stream_level reports what the slot holds, defaults resolved
+ * (PIPER_HIP_ERR_ARG if none). */
+int piper_hip_voice_stream_set_level(piper_hip_voice* v, int slot, const piper_hip_level* level);
+int piper_hip_voice_stream_level(piper_hip_voice* v, int slot, piper_hip_level* out);
 
 /* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
  * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]

@@ -23,6 +23,7 @@
 #include "conv.h"
 #include "conv_bf16.h"
 #include "conv_win.h"
+#include "level.h"
 #include "pcm16.h"
 #include "resample.h"
 #include "rng.h"
@@ -254,6 +255,21 @@ struct StreamRow {
   // have without the drop. A pool's rows are never ghosts: a dropped row is free for the next join at once.
   bool ghost = false;
   RowFormat fmt;  // read on a mixed slot only; set by stream_item_formats (group) or the join that took the row (pool)
+  int64_t lim_lo = 0;  // read on a slot with a level only: where the row's previous step ended, in limited samples (a step at next == 0 starts it at 0)
+};
+
+// The level of a stream — single, group or pool (piper_hip_voice_stream_set_level; include/piper_hip.h "Level control"): per generator row
+// a carry in device memory (the samples u a step could not finish yet and the last final G), the step's LvStepRow table, and the limited
+// samples of one step, lim [rows][row], which the output kernels then read in place of the window plan's audio.
+struct StreamLevel {
+  bool on = false;
+  piper_hip_level lv{};       // as stream_level reports it: defaults resolved
+  LvParams p{};
+  int rows = 0;               // generator rows the buffers below hold
+  int64_t row = 0;            // floats of a row of `lim`
+  float* carry = nullptr;     // device [rows][kLvCarry]
+  float* lim = nullptr;       // device [rows][row]
+  LvStepRow* desc = nullptr;  // device [rows]
 };
 
 // The output rate of a stream — single, group or pool (piper_hip_voice_stream_set_rate): 0 is the voice's own rate. A resampling stream
@@ -284,6 +300,7 @@ struct Stream {
   void* pack = nullptr;              // device: the packed chunks of one batched step
   size_t pack_bytes = 0;             // of `pack`
   StreamRate rs;                     // output rate of the stream
+  StreamLevel lv;                    // level of the stream
   Slot* plan = nullptr;              // owner of the device buffers; nullptr = the context pool (a streaming pool)
   int items() const { return (int)rows.size(); }
 };
@@ -365,6 +382,9 @@ struct Slot {
   size_t pcm_cap = 0;         // bytes
   float* peaks = nullptr;     // [NB] max |x| per item (normalize = 1)
   std::vector<float> h_peaks; // the same on the host after a normalising collect_pcm16 (empty: none since the last launch)
+  // Level control (piper_hip_voice_slot_level): device buffers of this plan (in `owned`), allocated on first use
+  float* lim = nullptr;          // [NB][n_samples] the limited items, the layout of `audio`
+  float* lim_scratch = nullptr;  // lv_scratch_floats(NB, F·hop)
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
@@ -373,6 +393,7 @@ void reset_stream_state(Slot& s) {
   s.stream.single = false;
   StreamRate& rs = s.stream.rs;
   rs.rate = 0; rs.started = false; rs.parity = 0; rs.mixed = false;  // (a new stream starts at the voice's own rate; the buffers stay with the plan)
+  s.stream.lv.on = false;                                            // (and without a level)
 }
 
 // Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
@@ -515,6 +536,8 @@ struct piper_hip_voice {
   SpeakerTables spk;
   int spk_dp_rows = 0, spk_pre_off = 0;
   std::vector<piper_hip_speaker> slot_spk[kMaxSlots];
+  // The level of each slot id's whole-item collects (piper_hip_voice_slot_level), as given; on = false: none.
+  struct SlotLevel { bool on = false; piper_hip_level lv{}; } slot_lv[kMaxSlots];
   bool planned = false;  // a plan has been asked for: the voice's schedules are fixed (no attach_speakers any more)
   Slot* attached[kMaxSlots] = {};
   std::unique_ptr<StreamPool> pools[kMaxSlots];  // the streaming pool a slot id holds (then attached[slot] is null)
@@ -842,6 +865,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.stream = Stream();  // (no stream any more; its device buffers — descriptor, packed chunks, history, tables — are in `owned`)
   s.zin = nullptr; s.z_out = nullptr;
   s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();  // (these too)
+  s.lim = nullptr; s.lim_scratch = nullptr;
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
@@ -869,7 +893,8 @@ void pool_close(piper_hip_voice* v, int slot) {
     if (r.z) (void)v->ctx->pool.release(r.z);
   if (P->d_rows) (void)v->ctx->pool.release(P->d_rows);
   const StreamRate& rs = P->st.rs;
-  for (void* p : {(void*)P->st.d_desc, P->st.pack, (void*)rs.hist, (void*)rs.desc, (void*)rs.mdesc})
+  const StreamLevel& lv = P->st.lv;
+  for (void* p : {(void*)P->st.d_desc, P->st.pack, (void*)rs.hist, (void*)rs.desc, (void*)rs.mdesc, (void*)lv.carry, (void*)lv.lim, (void*)lv.desc})
     if (p) (void)v->ctx->pool.release(p);
   if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
   if (P->h_rep) (void)hipHostFree(P->h_rep);  // (the adopts that write it have run: waited for above)
@@ -3288,6 +3313,34 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__
     for (int64_t i = tid; i < n; i += nth) dst[i] = src[i];
   }
 }
+
+int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
+
+// What a collect of slot id `slot` reads: the plan's audio, or — the slot id has a level (piper_hip_voice_slot_level) — the limited items
+// lim [NB][n_samples], computed here behind the plan's graph on its stream from lengths the device holds (plain, ragged and bounded
+// slots alike). The plan's audio stays raw.
+int level_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
+  *audio = s.audio;
+  const auto& sl = v->slot_lv[slot];
+  if (!sl.on) return PIPER_HIP_OK;
+  LvParams p;
+  int rc = lv_resolve(&sl.lv, v->cfg.sample_rate, &p);
+  if (rc) return rc;
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  if (F < 1) return PIPER_HIP_OK;
+  void* q = nullptr;
+  if (!s.lim) {
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
+    s.lim = (float*)q;
+  }
+  if (!s.lim_scratch) {
+    if ((rc = plan_alloc(v, s, lv_scratch_floats(s.NB, (int64_t)F * v->hop) * sizeof(float), &q))) return rc;
+    s.lim_scratch = (float*)q;
+  }
+  PH_HIP(launch_level_items(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, 0, p, s.lim_scratch, s.lim, s.n_samples), PIPER_HIP_ERR_LAUNCH);
+  *audio = s.lim;
+  return PIPER_HIP_OK;
+}
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
@@ -3314,6 +3367,9 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *p;
   auto& sg = v->staging[slot];
+  const float* audio = s.audio;  // (a slot id with a level: the limited items)
+  if (host_audio)
+    if (int lrc = level_audio(v, slot, s, &audio)) return lrc;
   // The slot id's page-locked landing buffer of the waveform (kAudioMinCap at least). Failing to grow it is not fatal: the waveform
   // then goes to the caller's buffer directly, and the sticky error of the failed hipHostMalloc is cleared (the next launch would report it).
   if (s.bounded_pending) {
@@ -3332,7 +3388,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     if (dst_dev) {
       for (int b = 0; b < s.NB; b++) {
         const int blocks = (int)std::min<int64_t>((row + 4 * 256 - 1) / (4 * 256), 1024);
-        hipLaunchKernelGGL(copy_out_len_kernel, dim3(blocks), dim3(256), 0, s.set.stream, s.audio + (int64_t)b * s.n_samples, dst_dev + (int64_t)b * row, s.lensF, b, v->hop);
+        hipLaunchKernelGGL(copy_out_len_kernel, dim3(blocks), dim3(256), 0, s.set.stream, audio + (int64_t)b * s.n_samples, dst_dev + (int64_t)b * row, s.lensF, b, v->hop);
         PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
       }
     }
@@ -3373,7 +3429,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
       int64_t off = 0;
       for (int b = 0; b < s.NB; b++) {
         const int64_t nb = (int64_t)s.h_F[b] * v->hop;
-        const float* src = s.audio + (int64_t)b * s.n_samples;
+        const float* src = audio + (int64_t)b * s.n_samples;
         for (int64_t c0 = 0; c0 < nb; c0 += (int64_t)(kChunk / sizeof(float))) {
           const int64_t cn = std::min<int64_t>((int64_t)(kChunk / sizeof(float)), nb - c0);
           PH_HIP(hipMemcpyAsync(h_audio + off + c0, src + c0, (size_t)cn * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
@@ -3416,7 +3472,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     int64_t off = 0;
     for (int b = 0; b < s.NB; b++) {
       const int64_t nb = (int64_t)s.h_F[b] * v->hop;
-      const float* src = s.audio + (int64_t)b * s.n_samples;
+      const float* src = audio + (int64_t)b * s.n_samples;
       if (dst_dev && nb > 0) {
         const int blocks = (int)std::min<int64_t>((nb + 4 * 256 - 1) / (4 * 256), 1024);
         hipLaunchKernelGGL(copy_out_kernel, dim3(blocks), dim3(256), 0, s.set.stream, src, dst_dev + off, nb);
@@ -3649,8 +3705,19 @@ void rate_range(const RsDesign& d, int64_t s, int64_t e, int64_t N, int64_t* j0,
 constexpr size_t kDescStageInts = (size_t)256 * kDescInts;
 constexpr size_t kRateStageInts = kDescStageInts + (size_t)256 * sizeof(RsStepRow) / sizeof(int);
 constexpr size_t kMixStageInts = kDescStageInts + (size_t)256 * sizeof(MixStepRow) / sizeof(int);  // (a mixed step: the MixStepRow table instead)
+// a step of a slot with a level: the LvStepRow table behind whichever of the tables above the step uses
+constexpr size_t kLvStageOff = kMixStageInts > kRateStageInts ? kMixStageInts : kRateStageInts;
+constexpr size_t kLvStageInts = kLvStageOff + (size_t)256 * sizeof(LvStepRow) / sizeof(int);
+static_assert(kLvStageOff * sizeof(int) % alignof(LvStepRow) == 0 && sizeof(LvStepRow) % sizeof(int) == 0, "the LvStepRow table starts aligned");
 static_assert(kDescStageInts * sizeof(int) % alignof(RsStepRow) == 0, "the RsStepRow table starts aligned");
 static_assert(kDescStageInts * sizeof(int) % alignof(MixStepRow) == 0 && sizeof(MixStepRow) % sizeof(int) == 0, "the MixStepRow table starts aligned");
+
+// Samples at the voice's rate one row hands its output stage in a step: the chunk, or on a slot with a level the limiter's bound
+// (include/piper_hip.h "Level control"). What every capacity and every packed buffer of a stream is sized by.
+int64_t step_samples(const piper_hip_voice* v, const Stream& st) {
+  const int64_t chunk = (int64_t)st.chunk * v->hop;
+  return st.lv.on ? lv_step_bound(chunk) : chunk;
+}
 
 // ---- mixed formats (include/piper_hip.h "Mixed formats"): what a row's format means on the host
 int fmt_elem(int enc) { return enc == PIPER_HIP_ENC_F32 ? 4 : enc == PIPER_HIP_ENC_S16 ? 2 : 1; }  // bytes of a sample
@@ -3713,6 +3780,15 @@ struct Sink {
 // the `law` argument of the PCM kernels: the G.711 encodings are their own laws (PIPER_HIP_ENC_MULAW == PIPER_HIP_G711_MULAW …), 0 = int16
 int sink_law(const Sink& o) { return o.enc == PIPER_HIP_ENC_MULAW || o.enc == PIPER_HIP_ENC_ALAW ? o.enc : 0; }
 
+// The limited samples [lo, hi) a step hands its output stage for a row whose window is w (include/piper_hip.h "Level control", the emit
+// rule), and the row of the limiter's own descriptor: the chunk behind the halo skip, and how many samples of the carry stand before it.
+LvStepRow level_range(const StreamRow& row, const Window& w, int hop, int64_t* lo, int64_t* hi) {
+  const int64_t s = (int64_t)row.next * hop, e = (int64_t)w.end * hop, N = (int64_t)row.F * hop;
+  *lo = row.next == 0 ? 0 : row.lim_lo;  // a row's new occupant starts from nothing
+  *hi = e >= N ? N : lv_ready(e);
+  return LvStepRow{w.skip, w.n, (int)(s - *lo), (int)(*hi - *lo)};
+}
+
 // stream_next. A PCM sink: the chunk leaves as int16 or one G.711 byte per sample — converted by a kernel behind the window's graph —
 // instead of fp32; the step is the same in every other respect
 int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_samples) {
@@ -3733,6 +3809,19 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   const Window w = window_of(Ftrue, row.next, s.stream.chunk, s.stream.halo, v->hop);
   const int a = w.a, Fc = w.Fc;
   int64_t want = w.n;
+  // a slot with a level: the limiter stands between the window's audio and the output stage, which then sees the limited range [lo, hi)
+  // as its chunk (include/piper_hip.h "Level control")
+  StreamLevel& lvl = s.stream.lv;
+  LvStepRow lrow{};
+  int64_t dn_s = (int64_t)row.next * v->hop, lim_hi = 0;  // where the output stage's chunk starts in the item
+  int dn_skip = w.skip;
+  if (lvl.on) {
+    if (int rc0 = grow_pinned(v->staging[slot].h_desc, v->staging[slot].cap_desc, kLvStageInts)) return rc0;
+    lrow = level_range(row, w, v->hop, &dn_s, &lim_hi);
+    want = lim_hi - dn_s;
+    dn_skip = 0;
+  }
+  const int64_t dn_n = want;
   // a slot with an output rate of its own delivers int16 only: the chunk goes through the resampling step kernel instead of the flat one
   StreamRate& rs = s.stream.rs;
   const RsDesign* rd = nullptr;
@@ -3745,8 +3834,8 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
     if (!rc0) rc0 = grow_pinned(v->staging[slot].h_desc, v->staging[slot].cap_desc, kRateStageInts);
     if (rc0) return rc0;
     int64_t j0, j1;
-    rate_range(*rd, (int64_t)row.next * v->hop, (int64_t)w.end * v->hop, (int64_t)Ftrue * v->hop, &j0, &j1);
-    rrow = RsStepRow{(int64_t)row.next * v->hop, j0, w.skip, w.n, (int)(j1 - j0), 0};
+    rate_range(*rd, dn_s, dn_s + dn_n, (int64_t)Ftrue * v->hop, &j0, &j1);
+    rrow = RsStepRow{dn_s, j0, dn_skip, (int)dn_n, (int)(j1 - j0), 0};
     want = j1 - j0;
   }
   if (want_out && out.cap < want) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next: buffer holds %lld < %lld samples", (long long)out.cap, (long long)want);
@@ -3768,25 +3857,33 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   if (e == hipSuccess && gs->spk_bias)  // the item's conv_pre row travels with its latent window
     e = hipMemcpyAsync(gs->spk_bias, s.spk_bias + v->spk_pre_off, (size_t)v->cfg.up_initial * sizeof(float), hipMemcpyDeviceToDevice, gs->set.stream);
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
+  const float* chunk_audio = gs->audio;  // what the output stage reads, its chunk behind dn_skip
+  if (lvl.on) {  // (with or without a buffer: the row's carry moves on with the stream)
+    LvStepRow* h = (LvStepRow*)(v->staging[slot].h_desc + kLvStageOff);
+    if (e == hipSuccess) { *h = lrow; e = hipMemcpyAsync(lvl.desc, h, sizeof(LvStepRow), hipMemcpyHostToDevice, gs->set.stream); }
+    if (e == hipSuccess)
+      e = launch_level_step(gs->set.stream, 1, s.stream.chunk * v->hop, gs->audio, 0, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
+    chunk_audio = lvl.lim;
+  }
   if (pcm && want_out) {
     PcmRoute r;
-    const size_t dev_samples = (size_t)std::max<int64_t>((int64_t)gs->F * v->hop, rd ? rs_step_bound(*rd, (int64_t)gs->F * v->hop) : 0);
+    const size_t dev_samples = (size_t)std::max<int64_t>(std::max<int64_t>((int64_t)gs->F * v->hop, want), rd ? rs_step_bound(*rd, (int64_t)gs->F * v->hop) : 0);
     if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], out.host, elem, (size_t)want, dev_samples, &r);
     if (rd) {  // (every step ends with a wait: the staged descriptor of the previous one has been read)
       RsStepRow* h = (RsStepRow*)(v->staging[slot].h_desc + kDescStageInts);
       if (e == hipSuccess && !rc) { *h = rrow; e = hipMemcpyAsync(rs.desc, h, sizeof(RsStepRow), hipMemcpyHostToDevice, gs->set.stream); }
       if (e == hipSuccess && !rc)
-        e = launch_resample_step(gs->set.stream, 1, rrow.count, gs->audio, 0, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
+        e = launch_resample_step(gs->set.stream, 1, rrow.count, chunk_audio, 0, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
                                  rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, out.gain, r.kdst, law);
     } else if (e == hipSuccess && !rc) {
-      e = launch_pcm16_flat(gs->set.stream, gs->audio + w.skip, want, out.gain, r.kdst, law, v->ctx->num_cus);
+      e = launch_pcm16_flat(gs->set.stream, chunk_audio + dn_skip, want, out.gain, r.kdst, law, v->ctx->num_cus);
     }
     if (e == hipSuccess && !rc) rc = pcm_land(v->staging[slot], r, gs->set.stream, out.host, elem, (size_t)want);
     if (e == hipSuccess && !rc && r.mapped && !r.caller_pinned) memcpy(out.host, r.stage, (size_t)want * elem);
     if (e != hipSuccess || rc) (void)hipStreamSynchronize(gs->set.stream);  // nothing of the window may still run when its plan goes idle
   } else {
     if (e == hipSuccess && want_out)
-      e = hipMemcpyAsync(out.host, gs->audio + w.skip, (size_t)want * elem, hipMemcpyDeviceToHost, gs->set.stream);
+      e = hipMemcpyAsync(out.host, chunk_audio + dn_skip, (size_t)want * elem, hipMemcpyDeviceToHost, gs->set.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(gs->set.stream);
   }
   gs->in_use = false;
@@ -3795,6 +3892,7 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   if (rc) return rc;
   *n_samples = want;
   row.next = w.end;
+  row.lim_lo = lim_hi;
   rs.started = true;
   if (rd) rs.parity ^= 1;
   return PIPER_HIP_OK;
@@ -4060,7 +4158,10 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     if (!want_out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_batch_pcm16: a stream with an output rate needs a buffer");
     if ((rc = voice_filter(v, rs.rate, &rd, &rf))) return rc;
   }
-  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, mix ? kMixStageInts : rd ? kRateStageInts : kDescStageInts))) return rc;
+  StreamLevel& lvl = st.lv;
+  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, lvl.on ? kLvStageInts : mix ? kMixStageInts : rd ? kRateStageInts : kDescStageInts))) return rc;
+  LvStepRow* lrow = (LvStepRow*)(sg.h_desc + kLvStageOff);  // (only touched on a slot with a level)
+  std::vector<int64_t> lim_hi(n, 0);
   RsStepRow* rrow = (RsStepRow*)(sg.h_desc + kDescStageInts);  // (only touched when rd)
   MixStepRow* mrow = (MixStepRow*)(sg.h_desc + kDescStageInts);  // (only touched when mix: the same place)
   std::vector<int64_t> cnt(n, 0);  // samples each item delivers in this step
@@ -4078,6 +4179,7 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     e[kDescSrc] = r < n ? r : 0;
     if (rd) rrow[r] = RsStepRow{0, 0, 0, 0, 0, 0};
     if (mix) mrow[r] = MixStepRow{};
+    if (lvl.on) lrow[r] = LvStepRow{0, 0, 0, 0};
     if (mix && r < n) mix[r] = round_up4(total);  // (a row that delivers nothing: where the next delivering row starts)
     if (r < n && !rows[r].active && rows[r].ghost) {  // a dropped item: length 0 in the step, its window only sizes the plan
       const Window g = window_of(rows[r].F, rows[r].next, st.chunk, st.halo, hop);
@@ -4089,22 +4191,30 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     const Window w = win[r] = window_of(rows[r].F, rows[r].next, st.chunk, st.halo, hop);
     e[kDescA] = w.a;
     e[kDescFc] = w.Fc;
-    e[kDescSkip] = w.skip;
-    e[kDescN] = w.n;
+    // what the output stage takes for its chunk: the window's, or — a slot with a level — the limited range [lo, hi) in the row of lvl.lim
+    int64_t dn_s = (int64_t)rows[r].next * hop, dn_n = w.n;
+    int dn_skip = w.skip;
+    if (lvl.on) {
+      lrow[r] = level_range(rows[r], w, hop, &dn_s, &lim_hi[r]);
+      dn_n = lim_hi[r] - dn_s;
+      dn_skip = 0;
+    }
+    e[kDescSkip] = dn_skip;
+    e[kDescN] = (int)dn_n;
     e[kDescOff] = (int)total;
-    cnt[r] = w.n;
+    cnt[r] = dn_n;
     if (rd) {
       int64_t j0, j1;
-      rate_range(*rd, (int64_t)rows[r].next * hop, (int64_t)w.end * hop, (int64_t)rows[r].F * hop, &j0, &j1);
-      rrow[r] = RsStepRow{(int64_t)rows[r].next * hop, j0, w.skip, w.n, (int)(j1 - j0), (int)total};
+      rate_range(*rd, dn_s, dn_s + dn_n, (int64_t)rows[r].F * hop, &j0, &j1);
+      rrow[r] = RsStepRow{dn_s, j0, dn_skip, (int)dn_n, (int)(j1 - j0), (int)total};
       cnt[r] = j1 - j0;
       max_cnt = std::max(max_cnt, (int)(j1 - j0));
     }
     if (mix) {  // the row's own design, count, byte offset and descriptor (the filter table was uploaded when the format was supplied)
       const RowFormat& fm = rows[r].fmt;
       MixStepRow m{};
-      m.s = (int64_t)rows[r].next * hop;
-      m.skip = w.skip; m.n_in = w.n; m.count = w.n;
+      m.s = dn_s;
+      m.skip = dn_skip; m.n_in = (int)dn_n; m.count = (int)dn_n;
       m.elem = fmt_elem(fm.enc);
       m.law = m.elem == 1 ? fm.enc : 0;
       m.gain = fm.gain;
@@ -4113,7 +4223,7 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
         RsFilter ff{};
         if ((rc = voice_filter(v, fm.rate, &fd, &ff))) return rc;
         int64_t j0, j1;
-        rate_range(*fd, m.s, (int64_t)w.end * hop, (int64_t)rows[r].F * hop, &j0, &j1);
+        rate_range(*fd, m.s, m.s + dn_n, (int64_t)rows[r].F * hop, &j0, &j1);
         m.j0 = j0; m.count = (int)(j1 - j0);
         m.taps = ff.taps; m.L = ff.L; m.M = ff.M; m.P = ff.P;
       }
@@ -4160,6 +4270,14 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     e = hipGetLastError();
   }
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
+  const float* chunk_audio = gs->audio;  // what the output stage reads: rows of chunk_row floats, each row's chunk behind its skip
+  int64_t chunk_row = gs->n_samples;
+  if (lvl.on) {
+    if (e == hipSuccess) e = hipMemcpyAsync(lvl.desc, lrow, (size_t)NBg * sizeof(LvStepRow), hipMemcpyHostToDevice, q);
+    if (e == hipSuccess) e = launch_level_step(q, NBg, st.chunk * hop, gs->audio, gs->n_samples, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
+    chunk_audio = lvl.lim;
+    chunk_row = lvl.row;
+  }
   if (e == hipSuccess) {
     const int px = (int)std::min<int64_t>(ceil_div((int64_t)st.chunk * hop, 1024), 64);
     if (mix) {
@@ -4168,17 +4286,17 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
       mix_step_plan(mrow, NBg, px, &gx, &lds);
       e = hipMemcpyAsync(rs.mdesc, mrow, (size_t)NBg * sizeof(MixStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
-        e = launch_mixed_step(q, NBg, gx, lds, gs->audio, gs->n_samples, rs.mdesc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
+        e = launch_mixed_step(q, NBg, gx, lds, chunk_audio, chunk_row, rs.mdesc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
                               rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, st.pack);
     } else if (rd) {
       e = hipMemcpyAsync(rs.desc, rrow, (size_t)NBg * sizeof(RsStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
-        e = launch_resample_step(q, NBg, max_cnt, gs->audio, gs->n_samples, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
+        e = launch_resample_step(q, NBg, max_cnt, chunk_audio, chunk_row, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
                                  rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, st.pack, law);
     } else if (pcm) {
-      e = launch_stream_chunk_pack_pcm16(q, px, NBg, gs->audio, gs->n_samples, st.d_desc, gain, st.pack, law);
+      e = launch_stream_chunk_pack_pcm16(q, px, NBg, chunk_audio, chunk_row, st.d_desc, gain, st.pack, law);
     } else {
-      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, gs->audio, gs->n_samples, st.d_desc, (float*)st.pack);
+      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, chunk_audio, chunk_row, st.d_desc, (float*)st.pack);
       e = hipGetLastError();
     }
   }
@@ -4199,6 +4317,7 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     }
     if (!win[i].n) continue;
     rows[i].next = win[i].end;
+    rows[i].lim_lo = lim_hi[i];
     if (win[i].end >= rows[i].F) rows[i].active = false;  // last chunk delivered (a pool: the row is free for the next join)
   }
   return PIPER_HIP_OK;
@@ -4394,12 +4513,12 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   if (st.rs.mixed) {
     PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
     int64_t bytes = 0;
-    for (const auto& r : st.rows) bytes += r.active ? fmt_step_bytes(v, r.fmt, (int64_t)st.chunk * v->hop) : 0;
+    for (const auto& r : st.rows) bytes += r.active ? fmt_step_bytes(v, r.fmt, step_samples(v, st)) : 0;
     for (int i = 0; i < n; i++) {
       RsFilter ff{};
       if (jf[i].rate)
         if (int rc0 = voice_filter(v, jf[i].rate, nullptr, &ff)) return rc0;
-      bytes += fmt_step_bytes(v, jf[i], (int64_t)st.chunk * v->hop);
+      bytes += fmt_step_bytes(v, jf[i], step_samples(v, st));
     }
     if (int rc0 = pack_buffer(v, st, (size_t)bytes)) return rc0;
   }
@@ -4593,6 +4712,8 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   bool normalize;
   int rc = pcm_params(params, &out.gain, &normalize);
   if (rc) return rc;
+  if (normalize && slot >= 0 && slot < kMaxSlots && v->slot_lv[slot].on)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "collect_pcm16: normalize = 1 on slot %d, which has a level (piper_hip_voice_slot_level)", slot);
   const float gain = out.gain;
   const RsDesign* rd = nullptr;
   RsFilter rf{};
@@ -4635,12 +4756,14 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   PcmRoute r;
   if ((rc = pcm_route(v, s, sg, host_pcm, elem, (size_t)need, (size_t)std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB, &r))) return rc;
   const hipStream_t q = s.set.stream;
+  const float* audio = s.audio;  // (a slot id with a level: the limited items)
+  if ((rc = level_audio(v, slot, s, &audio))) return rc;
   if (normalize) PH_HIP(launch_pcm16_peak(q, s.audio, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
   if (rd)
-    PH_HIP(launch_resample_items(q, s.audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
+    PH_HIP(launch_resample_items(q, audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
            PIPER_HIP_ERR_LAUNCH);
   else
-    PH_HIP(launch_pcm16_pack(q, s.audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(launch_pcm16_pack(q, audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
   if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, (size_t)NB * sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
   if ((rc = pcm_land(sg, r, q, host_pcm, elem, (size_t)need))) return rc;
   if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
@@ -4688,6 +4811,7 @@ int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper
   int rc = who ? g711_law(who, enc) : PIPER_HIP_OK;
   if (!rc) rc = pcm_params(params, &gain, &normalize);
   if (rc) return rc;
+  if (normalize && v->slot_lv[0].on) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16: normalize = 1 on slot 0, which has a level (piper_hip_voice_slot_level)");
   const RsDesign* rd = nullptr;
   if (out_rate != v->cfg.sample_rate && (rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
   if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
@@ -4749,7 +4873,7 @@ PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int3
   if ((rc = voice_filter(v, out_rate, &rd, &rf))) return rc;
   // the history and the descriptor of the stream's rows, and a packed-output buffer that holds a step at this rate
   if ((rc = rate_buffers(v, st))) return rc;
-  if ((rc = pack_buffer(v, st, (size_t)st.items() * (size_t)rs_step_bound(*rd, chunk_samples(v, st)) * sizeof(int16_t)))) return rc;
+  if ((rc = pack_buffer(v, st, (size_t)st.items() * (size_t)rs_step_bound(*rd, step_samples(v, st)) * sizeof(int16_t)))) return rc;
   rs.parity = 0;
   rs.rate = out_rate;
   return PIPER_HIP_OK;
@@ -4780,6 +4904,89 @@ PH_EXPORT int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot) {
   if (!st) return PIPER_HIP_ERR_ARG;
   if (st->rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_rate: slot %d is mixed: every row has its own rate (stream_item_format)", slot);
   return st->rs.rate ? st->rs.rate : v->cfg.sample_rate;
+}
+
+// ---- level control (include/piper_hip.h "Level control")
+
+PH_EXPORT int piper_hip_voice_slot_level(piper_hip_voice* v, int slot, const piper_hip_level* level) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (level)
+    if (int rc = piper_hip_level_check(level)) return rc;
+  v->slot_lv[slot].on = level != nullptr;
+  v->slot_lv[slot].lv = level ? *level : piper_hip_level{0.0f, 0.0f, 0.0f};
+  return PIPER_HIP_OK;
+}
+
+namespace {
+// The packed-output buffer of a batched stream for the rows as they stand: what begin_batch / pool_open, set_rate, item_formats and the
+// joins size, at the slot's current per-row bound (step_samples).
+int pack_resize(piper_hip_voice* v, Stream& st) {
+  const int64_t n_in = step_samples(v, st);
+  int64_t bytes = 0;
+  if (st.rs.mixed) {
+    for (const StreamRow& row : st.rows)
+      if (!is_pool(st) || row.active) bytes += fmt_step_bytes(v, row.fmt, n_in);
+  } else if (st.rs.rate) {
+    const RsDesign* rd = nullptr;
+    if (int rc = rs_design(v->cfg.sample_rate, st.rs.rate, &rd)) return rc;
+    bytes = (int64_t)st.items() * rs_step_bound(*rd, n_in) * (int64_t)sizeof(int16_t);
+  } else {
+    bytes = (int64_t)st.items() * n_in * (int64_t)sizeof(float);
+  }
+  return pack_buffer(v, st, (size_t)bytes);
+}
+}  // namespace
+
+PH_EXPORT int piper_hip_voice_stream_set_level(piper_hip_voice* v, int slot, const piper_hip_level* level) {
+  Stream* sp = slot_stream(v, slot, "stream_set_level");
+  if (!sp) return PIPER_HIP_ERR_ARG;
+  Stream& st = *sp;
+  StreamLevel& lv = st.lv;
+  if (!level) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_level: null level");
+  if (st.rs.started)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_level: slot %d has %s: the level is set before", slot, is_pool(st) ? "stepped or been joined" : "stepped");
+  LvParams p;
+  int rc = lv_resolve(level, v->cfg.sample_rate, &p);
+  if (rc) return rc;
+  const int64_t chunk = chunk_samples(v, st);
+  if (chunk < 512)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_level: chunk_frames · hop = %lld < 512 (a step before the last must deliver samples)", (long long)chunk);
+  if (chunk > 0x3fffffff || !lv_step_lds(chunk)) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_set_level: %lld samples per step too many", (long long)chunk);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  // the carry, the descriptor and the limited samples of one step for the stream's generator rows (kept when they are large enough)
+  const int64_t row = (lv_step_bound(chunk) + 1 + 3) & ~(int64_t)3;
+  if (lv.rows < st.NBg || lv.row < row) {
+    stream_free(v, st, lv.carry, (size_t)lv.rows * kLvCarry * sizeof(float));
+    stream_free(v, st, lv.lim, (size_t)lv.rows * lv.row * sizeof(float));
+    stream_free(v, st, lv.desc, (size_t)lv.rows * sizeof(LvStepRow));
+    lv.carry = lv.lim = nullptr; lv.desc = nullptr; lv.rows = 0; lv.row = 0;
+    void *c = nullptr, *l = nullptr, *d = nullptr;
+    if ((rc = stream_alloc(v, st, (size_t)st.NBg * kLvCarry * sizeof(float), &c))) return rc;
+    if ((rc = stream_alloc(v, st, (size_t)st.NBg * row * sizeof(float), &l))) { stream_free(v, st, c, (size_t)st.NBg * kLvCarry * sizeof(float)); return rc; }
+    if ((rc = stream_alloc(v, st, (size_t)st.NBg * sizeof(LvStepRow), &d))) {
+      stream_free(v, st, c, (size_t)st.NBg * kLvCarry * sizeof(float));
+      stream_free(v, st, l, (size_t)st.NBg * row * sizeof(float));
+      return rc;
+    }
+    lv.carry = (float*)c; lv.lim = (float*)l; lv.desc = (LvStepRow*)d;
+    lv.rows = st.NBg; lv.row = row;
+  }
+  const bool was = lv.on;
+  lv.on = true;
+  if ((rc = pack_resize(v, st))) { lv.on = was; return rc; }
+  lv.p = p;
+  lv.lv = piper_hip_level{p.drive, p.ceiling, level->release_ms == 0.0f ? 50.0f : level->release_ms};
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_level(piper_hip_voice* v, int slot, piper_hip_level* out) {
+  const Stream* st = slot_stream(v, slot, "stream_level");
+  if (!st) return PIPER_HIP_ERR_ARG;
+  if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_level: null output");
+  if (!st->lv.on) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_level: slot %d has no level", slot);
+  *out = st->lv.lv;
+  return PIPER_HIP_OK;
 }
 
 // ---- mixed formats (include/piper_hip.h "Mixed formats")
@@ -4828,7 +5035,7 @@ PH_EXPORT int piper_hip_voice_stream_item_formats(piper_hip_voice* v, int slot, 
   for (int i = 0; i < items; i++) {
     RsFilter ff{};
     if (f[i].rate && (rc = voice_filter(v, f[i].rate, nullptr, &ff))) return rc;
-    bytes += fmt_step_bytes(v, f[i], chunk_samples(v, st));
+    bytes += fmt_step_bytes(v, f[i], step_samples(v, st));
   }
   if ((rc = pack_buffer(v, st, (size_t)bytes))) return rc;
   for (int i = 0; i < items; i++) st.rows[i].fmt = f[i];
@@ -4848,7 +5055,7 @@ PH_EXPORT int64_t piper_hip_voice_stream_step_capacity_bytes(piper_hip_voice* v,
   if (!st) return PIPER_HIP_ERR_ARG;
   int64_t bytes = 0;
   for (const StreamRow& row : st->rows)
-    if (row.active) bytes += fmt_step_bytes(v, row.fmt, chunk_samples(v, *st));
+    if (row.active) bytes += fmt_step_bytes(v, row.fmt, step_samples(v, *st));
   return bytes;
 }
 
@@ -4869,10 +5076,10 @@ PH_EXPORT int64_t piper_hip_voice_stream_step_capacity(piper_hip_voice* v, int s
   const Stream* st = slot_stream(v, slot, "stream_step_capacity");
   if (!st) return PIPER_HIP_ERR_ARG;
   if (st->rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_step_capacity: slot %d is mixed: stream_step_capacity_bytes", slot);
-  if (!st->rs.rate) return (int64_t)st->items() * chunk_samples(v, *st);
+  if (!st->rs.rate) return (int64_t)st->items() * step_samples(v, *st);
   const RsDesign* rd = nullptr;
   if (int rc = rs_design(v->cfg.sample_rate, st->rs.rate, &rd)) return rc;
-  return (int64_t)st->items() * rs_step_bound(*rd, chunk_samples(v, *st));
+  return (int64_t)st->items() * rs_step_bound(*rd, step_samples(v, *st));
 }
 
 namespace {

@@ -241,6 +241,27 @@ def _formats(formats):
     return (StreamFormat * max(len(fs), 1))(*fs)
 
 
+class Level(C.Structure):
+    """piper_hip_level: the look-ahead limiter of include/piper_hip.h "Level control". A zero field takes its default: {1, 1, 50 ms}."""
+    _fields_ = [("drive", C.c_float), ("ceiling", C.c_float), ("release_ms", C.c_float)]
+
+    def __repr__(self):
+        return "Level(drive=%g, ceiling=%g, release_ms=%g)" % (self.drive, self.ceiling, self.release_ms)
+
+
+def _level(level):
+    """Level | (drive, ceiling, release_ms) | dict → a Level"""
+    if isinstance(level, Level):
+        return level
+    if isinstance(level, dict):
+        return Level(float(level.get("drive", 0.0)), float(level.get("ceiling", 0.0)), float(level.get("release_ms", 0.0)))
+    d, c, r = level
+    return Level(float(d), float(c), float(r))
+
+
+KEEP = object()  # level=KEEP: leave the slot id's level as it is
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("avg_us", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -393,6 +414,15 @@ _PROTOS = {
                                                   C.POINTER(C.c_int64)]),
     "piper_hip_voice_stream_next_g711": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
     "piper_hip_voice_stream_next_batch_g711": (C.c_int, [c_vp, C.c_int, C.POINTER(PcmParams), C.c_int, c_u8p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_level_check": (C.c_int, [C.POINTER(Level)]),
+    "piper_hip_level_info": (C.c_int, [C.POINTER(Level), C.c_int32, c_f32p]),
+    "piper_hip_level_ready": (C.c_int64, [C.c_int64]),
+    "piper_hip_level_step_bound": (C.c_int64, [C.c_int64]),
+    "piper_hip_level_from_f32": (C.c_int, [C.POINTER(Level), C.c_int32, c_f32p, C.c_size_t, c_f32p]),
+    "piper_hip_level_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_int32, C.POINTER(Level), C.POINTER(c_vp), c_vp]),
+    "piper_hip_voice_slot_level": (C.c_int, [c_vp, C.c_int, C.POINTER(Level)]),
+    "piper_hip_voice_stream_set_level": (C.c_int, [c_vp, C.c_int, C.POINTER(Level)]),
+    "piper_hip_voice_stream_level": (C.c_int, [c_vp, C.c_int, C.POINTER(Level)]),
     "piper_hip_voice_stream_set_mixed": (C.c_int, [c_vp, C.c_int]),
     "piper_hip_voice_stream_item_formats": (C.c_int, [c_vp, C.c_int, C.POINTER(StreamFormat), C.c_int]),
     "piper_hip_voice_stream_pool_join_formats": (C.c_int, [c_vp, C.c_int, C.POINTER(Utterance), C.c_int, C.c_int, C.POINTER(StreamFormat),
@@ -771,6 +801,15 @@ class HipBackend:
         p = c_vp(_ptr(out)) if out is not None else c_vp()
         _check(self.lib.piper_hip_pcm16_f32(self.ctx, _ptr(buf), n, float(gain), C.byref(p), commandBuffer))
         return DeviceBuffer(self, p.value, n, owned=out is None, dtype=np.int16)
+
+    def level_f32(self, buf, rate, level, count=None, out=None, commandBuffer=None):
+        """`count` device floats sampled at `rate` → the same number of limited device floats (piper_hip_level_f32): the look-ahead limiter
+        of include/piper_hip.h "Level control". Returns a DeviceBuffer of `count` float32."""
+        n = buf.count if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        lv = _level(level)
+        _check(self.lib.piper_hip_level_f32(self.ctx, _ptr(buf), n, int(rate), C.byref(lv), C.byref(p), commandBuffer))
+        return DeviceBuffer(self, p.value, n, owned=out is None)
 
     def resampleF32(self, buf, inRate, outRate, count=None, out=None, commandBuffer=None):
         """`count` device floats at inRate → J(count) device floats at outRate (piper_hip_resample_f32): the fp32 y of the output-rate
@@ -1172,6 +1211,38 @@ def resample_step_bound(in_rate, out_rate, n_in):
     return _count(load_library().piper_hip_resample_step_bound(int(in_rate), int(out_rate), int(n_in)))
 
 
+def level_check(level):
+    """InvalidArgument naming the field for a level outside the contract (piper_hip_level_check). Host-only."""
+    lv = _level(level)
+    _check(load_library().piper_hip_level_check(C.byref(lv)))
+
+
+def level_info(level, rate):
+    """The fp32 release step per block of that level at `rate`. Host-only."""
+    lv, rel = _level(level), C.c_float()
+    _check(load_library().piper_hip_level_info(C.byref(lv), int(rate), C.byref(rel)))
+    return np.float32(rel.value)
+
+
+def level_ready(e):
+    """The limited samples that are final when samples [0, e) of a longer item are known. Host-only."""
+    return _count(load_library().piper_hip_level_ready(int(e)))
+
+
+def level_step_bound(n_in):
+    """The most limited samples one stream row delivers in a step over n_in input samples. Host-only."""
+    return _count(load_library().piper_hip_level_step_bound(int(n_in)))
+
+
+def level_from_f32(samples, level, rate):
+    """The limiter on the host (piper_hip_level_from_f32), bit for bit what the device computes."""
+    x = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    y = np.empty(x.size, np.float32)
+    lv = _level(level)
+    _check(load_library().piper_hip_level_from_f32(C.byref(lv), int(rate), x.ctypes.data_as(c_f32p), x.size, y.ctypes.data_as(c_f32p)))
+    return y
+
+
 def piper_json(text):
     info = PiperJsonInfo()
     _check(load_library().piper_hip_piper_json(text.encode("utf-8"), C.byref(info)))
@@ -1188,6 +1259,7 @@ class StreamPool:
         self._off = (C.c_int64 * capacity)()
         self.rate = None
         self.mixed = False
+        self.level = None
         self._fmt = {}  # (mixed) row → the StreamFormat of the session in it
 
     def set_mixed(self):
@@ -1195,6 +1267,28 @@ class StreamPool:
         brings the formats and step_mixed() is the pool's step."""
         self.rt.stream_set_mixed(self.slot)
         self.mixed = True
+        self._resize()
+
+    def _resize(self):
+        """The step buffer for the pool as it stands: the level's per-row bound in place of the chunk, the rate's on top of it."""
+        rt = self.rt
+        if self.mixed:  # the largest share a row can have: f32 at the highest rate
+            per = self.chunk_frames * rt.cfg.hop
+            if self.level is not None:
+                per = level_step_bound(per)
+                per = max(per, resample_step_bound(rt.cfg.sample_rate, 48000, per))
+            self._buf = np.empty(max(self.capacity * (per + 1), self._buf.size), np.float32)
+        elif self.rate:
+            self._buf = np.empty((rt.stream_step_capacity(self.slot) + 1) // 2, np.float32)
+        else:
+            self._buf = np.empty(max(rt.stream_step_capacity(self.slot), 1), np.float32)
+
+    def set_level(self, level):
+        """A look-ahead limiter on every row (piper_hip_voice_stream_set_level): before the first join, with set_rate or set_mixed in
+        either order."""
+        self.rt.stream_set_level(self.slot, level)
+        self.level = _level(level)
+        self._resize()
 
     def set_rate(self, rate):
         """Deliver at `rate` Hz (piper_hip_voice_stream_set_rate): before the first join. step() then returns int16 chunks only."""
@@ -1203,7 +1297,7 @@ class StreamPool:
             self.rate = None
             return
         self.rate = int(rate)
-        self._buf = np.empty((self.rt.stream_step_capacity(self.slot) + 1) // 2, np.float32)
+        self._resize()
 
     def join(self, utterances, noiseScale=0.667, formats=None, prosody=None):
         """utterances as for synthesize_stream_batch: (phonemeIDs, durations-or-None, noise-or-None[, dict]). Returns [(item, samples)]:
@@ -1429,12 +1523,15 @@ class HipRuntime:
         u, _k = self._utt(ids, durations, None, 0.0)
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
-    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None, **kw):
+    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None,
+                   level=KEEP, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
         reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
-        speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays."""
+        speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays.
+        level: a Level (or tuple / dict) becomes slot 0's level (slot_level) and stays; None clears it."""
         if speaker is not None:
             self.slot_speakers(0, [speaker])
+        self._slot_level(0, level)
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
@@ -1537,6 +1634,28 @@ class HipRuntime:
         """The int16 samples one step of the stream on `slot` can deliver at its current rate."""
         return _count(self.lib.piper_hip_voice_stream_step_capacity(self.voice, slot))
 
+    def slot_level(self, slot, level):
+        """The level of slot id `slot`'s whole-item collects (piper_hip_voice_slot_level): it persists until replaced; None clears it."""
+        if level is None:
+            _check(self.lib.piper_hip_voice_slot_level(self.voice, slot, None))
+        else:
+            lv = _level(level)
+            _check(self.lib.piper_hip_voice_slot_level(self.voice, slot, C.byref(lv)))
+
+    def _slot_level(self, slot, level):
+        if level is not KEEP:
+            self.slot_level(slot, level)
+
+    def stream_set_level(self, slot, level):
+        """The level of the stream on `slot` (piper_hip_voice_stream_set_level): after its begin / open, before its first step."""
+        lv = _level(level)
+        _check(self.lib.piper_hip_voice_stream_set_level(self.voice, slot, C.byref(lv)))
+
+    def stream_level(self, slot):
+        out = Level()
+        _check(self.lib.piper_hip_voice_stream_level(self.voice, slot, C.byref(out)))
+        return out
+
     def stream_set_mixed(self, slot):
         """Marks the batched stream on `slot` mixed (piper_hip_voice_stream_set_mixed): every row picks its rate, encoding and gain."""
         _check(self.lib.piper_hip_voice_stream_set_mixed(self.voice, slot))
@@ -1555,7 +1674,7 @@ class HipRuntime:
         return _count(self.lib.piper_hip_voice_stream_step_capacity_bytes(self.voice, slot))
 
     def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None,
-                          encoding=None, prosody=None):
+                          encoding=None, prosody=None, level=None):
         """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
         prosody: the utterance's per-id prosody, as for prepare.
         pcm=True: int16 chunks converted on the device (piper_hip_voice_stream_next_pcm16), scaled by `gain`. rate: int16 chunks at that
@@ -1569,6 +1688,9 @@ class HipRuntime:
         law = None if encoding is None else _law(encoding)
         sample = np.uint8 if law is not None else np.int16
         buf = np.empty(int(chunkFrames) * self.cfg.hop, sample if pcm or rate or law is not None else np.float32)
+        if level is not None:  # a look-ahead limiter in front of the output stage (stream_set_level)
+            self.stream_set_level(slot, level)
+            buf = np.empty(self.stream_step_capacity(slot), buf.dtype)
         if rate:
             pcm = True
             self.stream_set_rate(slot, rate)
@@ -1588,7 +1710,7 @@ class HipRuntime:
             yield buf[:got.value].copy()
 
     def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None, encoding=None,
-                                formats=None, prosody=None):
+                                formats=None, prosody=None, level=None):
         """prosody: one entry per utterance (None entries neutral), as for slot_prosody.
         Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
@@ -1609,6 +1731,8 @@ class HipRuntime:
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
+        if level is not None:  # a look-ahead limiter on every row, in front of the output stage (stream_set_level)
+            self.stream_set_level(slot, level)
         if formats is not None:
             if pcm or rate or encoding is not None or gain != 1.0:
                 raise InvalidArgument("synthesize_stream_batch: formats= carries the rate, encoding and gain of every item")
@@ -1625,6 +1749,8 @@ class HipRuntime:
         law = None if encoding is None else _law(encoding)
         sample = np.uint8 if law is not None else np.int16
         buf = np.empty(max(n * int(chunkFrames) * self.cfg.hop, 1), sample if pcm or rate or law is not None else np.float32)
+        if level is not None:
+            buf = np.empty(self.stream_step_capacity(slot), buf.dtype)
         if rate:
             pcm = True
             self.stream_set_rate(slot, rate)
@@ -1651,7 +1777,7 @@ class HipRuntime:
         """The client of item `item` of the batched stream on `slot` went away: later steps skip it."""
         _check(self.lib.piper_hip_voice_stream_drop(self.voice, slot, int(item)))
 
-    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None, rate=None, mixed=False):
+    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None, rate=None, mixed=False, level=None):
         """A streaming pool (piper_hip_voice_stream_pool_open) of `capacity` rows on `slot`: sessions join and leave while it runs.
         work_slot: the slot id whose plan runs the joins' encoder + flow (default: the next slot id). mixed=True: every joining session
         brings its own format (join(formats=[...]), step_mixed())."""
@@ -1664,6 +1790,8 @@ class HipRuntime:
             pool.set_rate(rate)
         if mixed:
             pool.set_mixed()
+        if level is not None:
+            pool.set_level(level)
         return pool
 
     def prepare_batch(self, slot, utterances, noiseScale=0.667, prosody=None):
@@ -1712,7 +1840,9 @@ class HipRuntime:
         self._pinned.append(p)
         return np.ctypeslib.as_array(C.cast(p, c_f32p), shape=(int(count),))
 
-    def collect(self, slot, want_audio=True, out=None):
+    def collect(self, slot, want_audio=True, out=None, level=KEEP):
+        """level: a Level (or tuple / dict) sets the slot id's level before the call, None clears it (slot_level); it persists."""
+        self._slot_level(slot, level)
         n = self._keep[slot][1]
         if not want_audio:
             _check(self.lib.piper_hip_voice_collect(self.voice, slot, None, 0))
@@ -1726,11 +1856,12 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
-    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None):
+    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None, level=KEEP):
         """collect() with 16-bit PCM converted on the device (piper_hip_voice_collect_pcm16): the items back to back at their true lengths.
         normalize=False: the samples pcm16(collect(slot)) gives; normalize=True: Piper's peak normalisation per item (peaks(slot) afterwards).
         The fp32 waveform stays in the plan: collect / collect_pcm16 may follow in any order. rate: resampled on the device to that output
-        rate (piper_hip_voice_collect_pcm16_rate), item b at J(its true samples)."""
+        rate (piper_hip_voice_collect_pcm16_rate), item b at J(its true samples). level: as for collect."""
+        self._slot_level(slot, level)
         n = self._keep[slot][1]
         if rate is not None and int(rate) != self.cfg.sample_rate:  # (the voice's own rate is not a filter: the plain call)
             return self._collect_pcm16_rate(slot, gain, normalize, out, int(rate))
@@ -1761,8 +1892,10 @@ class HipRuntime:
         return out[:sum(resample_count(src, rate, p) for p in per)]
 
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, rate=None, prosody=None, **kw):
-        """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare."""
+                         normalize=False, rate=None, prosody=None, level=KEEP, **kw):
+        """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare;
+        level: as for collect (slot 0)."""
+        self._slot_level(0, level)
         pro = None if prosody is None else [prosody]
         if rate is not None and int(rate) == self.cfg.sample_rate:
             rate = None
@@ -1791,9 +1924,10 @@ class HipRuntime:
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
 
-    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None):
+    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None, level=KEEP):
         """collect_pcm16 ending in G.711 bytes ("mulaw" / "alaw") companded on the device (piper_hip_voice_collect_g711): one uint8 per
         sample, the items back to back at J(their true samples) at `rate` (default: the voice's own). Every rule of collect_pcm16 holds."""
+        self._slot_level(slot, level)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         count = (lambda p: p) if rate == src else (lambda p: resample_count(src, rate, p))
@@ -1811,9 +1945,11 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], total, False)
         return out[:sum(count(p) for p in per)]
 
-    def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None):
+    def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None,
+                        level=KEEP):
         """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's;
-        prosody: as for prepare (with supplied durations: noise alone)."""
+        prosody: as for prepare (with supplied durations: noise alone); level: as for collect (slot 0)."""
+        self._slot_level(0, level)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)

@@ -224,6 +224,52 @@ public final class HIPBackend {
         return b
     }
 
+    // ---- level control (include/piper_hip.h "Level control") ----
+
+    /// `count` device floats sampled at `rate` → `count` limited device floats (piper_hip_level_f32): the look-ahead limiter.
+    public func levelF32(input: HIPBuffer, count: Int, rate: Int32, level: piper_hip_level, commandBuffer: Stream? = nil) throws -> HIPBuffer {
+        var out: UnsafeMutablePointer<Float>? = nil
+        var lv = level
+        try Self.check(piper_hip_level_f32(ctx, input.f32, count, rate, &lv, &out, commandBuffer))
+        return HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx)
+    }
+
+    /// The limiter on the host (piper_hip_level_from_f32), bit for bit what the device computes.
+    public static func levelFromF32(_ x: [Float], level: piper_hip_level, rate: Int32) throws -> [Float] {
+        var lv = level
+        var y = [Float](repeating: 0, count: x.count)
+        try check(piper_hip_level_from_f32(&lv, rate, x, x.count, &y))
+        return y
+    }
+
+    /// InvalidArgument naming the field for a level outside the contract (piper_hip_level_check; host-only).
+    public static func levelCheck(_ level: piper_hip_level) throws {
+        var lv = level
+        try check(piper_hip_level_check(&lv))
+    }
+
+    /// The fp32 release step per block of `level` at `rate` (piper_hip_level_info; host-only).
+    public static func levelInfo(_ level: piper_hip_level, rate: Int32) throws -> Float {
+        var lv = level
+        var rel: Float = 0
+        try check(piper_hip_level_info(&lv, rate, &rel))
+        return rel
+    }
+
+    /// The limited samples that are final when samples [0, e) of a longer item are known (piper_hip_level_ready; host-only).
+    public static func levelReady(_ e: Int64) throws -> Int64 {
+        let r = piper_hip_level_ready(e)
+        if r < 0 { try check(Int32(r)) }
+        return r
+    }
+
+    /// The most limited samples one stream row delivers in a step over `n` input samples (piper_hip_level_step_bound; host-only).
+    public static func levelStepBound(_ n: Int64) throws -> Int64 {
+        let b = piper_hip_level_step_bound(n)
+        if b < 0 { try check(Int32(b)) }
+        return b
+    }
+
     // ---- binary with NumPy broadcasting, output rank ≤ 4 (MetalBackend.swift:2099-2134, 2592-2610) ----
     private func binaryBroadcastF32(_ op: piper_hip_binary_op, a: HIPBuffer, aShape: [Int], b: HIPBuffer, bShape: [Int],
                                     commandBuffer: Stream?) throws -> (out: HIPBuffer, outShape: [Int]) {

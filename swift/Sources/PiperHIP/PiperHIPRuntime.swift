@@ -450,6 +450,28 @@ public final class PiperHIPRuntime {
         try HIPBackend.check(piper_hip_voice_stream_set_rate(voice, slot, rate))
     }
 
+    /// The level of slot id `slot`'s whole-item collects (piper_hip_voice_slot_level): it persists until replaced; nil clears it.
+    public func slotLevel(slot: Int32, level: piper_hip_level?) throws {
+        if var lv = level {
+            try HIPBackend.check(piper_hip_voice_slot_level(voice, slot, &lv))
+        } else {
+            try HIPBackend.check(piper_hip_voice_slot_level(voice, slot, nil))
+        }
+    }
+
+    /// The level of the stream on `slot` (piper_hip_voice_stream_set_level): where streamSetRate is allowed, in either order with it.
+    public func streamSetLevel(slot: Int32, level: piper_hip_level) throws {
+        var lv = level
+        try HIPBackend.check(piper_hip_voice_stream_set_level(voice, slot, &lv))
+    }
+
+    /// The level the stream on `slot` holds, defaults resolved (piper_hip_voice_stream_level).
+    public func streamLevel(slot: Int32) throws -> piper_hip_level {
+        var lv = piper_hip_level(drive: 0, ceiling: 0, release_ms: 0)
+        try HIPBackend.check(piper_hip_voice_stream_level(voice, slot, &lv))
+        return lv
+    }
+
     public func streamRate(slot: Int32) throws -> Int32 {
         let r = piper_hip_voice_stream_rate(voice, slot)
         if r < 0 { try HIPBackend.check(r) }
