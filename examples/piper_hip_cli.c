@@ -20,6 +20,9 @@
  *                            --normalize (with a law the last two act on --output as well: the file holds the same bytes).
  *                            --drive X --ceiling Y --release-ms Z: a look-ahead limiter on the device in front of every output above
  *                            (piper_hip_voice_slot_level on slot 0; a flag left out takes its default 1, 1, 50). Not with --normalize.
+ *                            --loudness LUFS [--max-gain-db X]: BS.1770 integrated loudness measured on the device and the utterance
+ *                            brought to that target in front of the limiter and every output above (piper_hip_voice_slot_loudness on
+ *                            slot 0; X defaults to 20); the measured loudness and the gain go to stderr. Not with --normalize.
  *   --speaker N              both modes: speaker N of a multi-speaker voice (the graph's `sid`; piper_hip_voice_attach_speakers +
  *                            piper_hip_voice_slot_speakers). With --model the file's speaker table is loaded (opt-in: without the flag such a
  *                            file is refused; its node graph is NOT verified — no verifier for the conditioned graph exists yet); without
@@ -182,6 +185,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
                     "                [--output-encoding s16le|mulaw|alaw] [--drive X] [--ceiling Y] [--release-ms Z]\n"
+                    "                [--loudness LUFS [--max-gain-db X]]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n"
                     "               [--speaker N [--speakers S]]\n", argv[0], argv[0]);
     return 2;
@@ -290,6 +294,14 @@ int main(int argc, char** argv) {
       lv.release_ms = arg_value(argc, argv, "--release-ms") ? (float)atof(arg_value(argc, argv, "--release-ms")) : 0.0f;
       CHECK(piper_hip_voice_slot_level(r.voice, 0, &lv));
     }
+    const char* loud_arg = arg_value(argc, argv, "--loudness");
+    if (loud_arg) {
+      piper_hip_loudness ld; /* slot 0's loudness target: every collect below delivers the utterance at that loudness */
+      ld.target_lufs = (float)atof(loud_arg);
+      ld.max_gain_db = arg_value(argc, argv, "--max-gain-db") ? (float)atof(arg_value(argc, argv, "--max-gain-db")) : 0.0f;
+      if (ld.target_lufs == 0.0f) { fprintf(stderr, "--loudness %s: expected a target in LUFS, -70 ... -1\n", loud_arg); return 2; }
+      CHECK(piper_hip_voice_slot_loudness(r.voice, 0, &ld));
+    }
     if (out) {
       CHECK(run_one(&r, ids, t, &n));
       CHECK(piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu));
@@ -332,6 +344,11 @@ int main(int argc, char** argv) {
         piper_hip_destroy(ctx);
         return 1;
       }
+    }
+    if (loud_arg) { /* what the device measured on the utterance that ran, and the gain it applied */
+      float lufs = 0.0f, g = 1.0f;
+      CHECK(piper_hip_voice_loudness(r.voice, 0, &lufs, &g, 1));
+      fprintf(stderr, "loudness %.4f LUFS, gain %.6g\n", (double)lufs, (double)g);
     }
     free(r.audio);
     piper_hip_voice_destroy(r.voice);

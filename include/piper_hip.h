@@ -799,6 +799,60 @@ int piper_hip_voice_slot_level(piper_hip_voice* v, int slot, const piper_hip_lev
 int piper_hip_voice_stream_set_level(piper_hip_voice* v, int slot, const piper_hip_level* level);
 int piper_hip_voice_stream_level(piper_hip_voice* v, int slot, piper_hip_level* out);
 
+/* ---- Loudness: ITU-R BS.1770 / EBU R128 integrated loudness, measured and normalised on the device (DESIGN.md §4 "Loudness") ----
+ * normalize = 1 is peak normalisation and says nothing about how loud an item sounds; a host that wants every prompt at one programme
+ * loudness (−16 or −23 LUFS) measures by BS.1770. It is one more stage of the output chain on whole items — generator → loudness gain →
+ * level → resampler → PCM / G.711 — and it changes nothing for a request that does not ask for it. Each later stage is exactly as its
+ * contract stands, reading u in place of x. The measurement is mono integrated loudness at the rate of the samples measured: the voice's
+ * own rate on every voice route.
+ *   rates      8000, 16000, 22050, 24000, 32000, 44100, 48000. Any other rate is PIPER_HIP_ERR_UNSUPPORTED (11025: 100 ms is not a whole
+ *              number of samples).
+ *   K-weight   all in double; two biquads re-derived per rate fs with K = tan(π·f0 / fs):
+ *              shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *                         Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K²,
+ *                         b = [(Vh + Vb·K/Q + K²)/a0, 2(K² − Vh)/a0, (Vh − Vb·K/Q + K²)/a0],  a = [1, 2(K² − 1)/a0, (1 − K/Q + K²)/a0]
+ *              high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, a0 = 1 + K/Q + K²,
+ *                         b = [1, −2, 1],  a = [1, 2(K² − 1)/a0, (1 − K/Q + K²)/a0]
+ *              (at 48 000 Hz these are the standard's table). y = HP(shelf(x)), each a direct recurrence from zero state; a non-finite
+ *              x[n] reads as 0.
+ *   blocks     h = fs/10;  J = (N − 4h) div h + 1 for N ≥ 4h, else 0;  z_j = (1/4h)·Σ y[n]² over [jh, jh + 4h);  l_j = −0.691 + 10·log10 z_j
+ *   gates      A = {j : l_j > −70};  Γr = −0.691 + 10·log10(mean_A z) − 10;  R = {j ∈ A : l_j > Γr};  L = −0.691 + 10·log10(mean_R z).
+ *              J = 0 or A empty: L = −∞, the item is unmeasurable. L is held in double and reported rounded once to fp32.
+ *   target     target_lufs (0 is taken as −16; otherwise finite in [−70, −1]), max_gain_db (0 → 20; otherwise in (0, 60]); anything else is
+ *              PIPER_HIP_ERR_ARG with a message that names the field.
+ *   gain       d = min((double)target − (double)L, (double)max_gain_db) with L the reported fp32;  g = (float)pow(10, d/20).
+ *              Attenuation is unbounded. An unmeasurable item has g = 1.0f.
+ *   u[n]       = fl(x[n] · g), one fp32 multiply.
+ * The device's L lies within 0.002 LU of the sequential float64 recurrence, and the same samples give the same bits of L on every run
+ * (fixed-order sums, no floating-point atomics).
+ * Streams are out of scope: an item's integrated loudness is not known before its end. Measure a voice or a speaker once with
+ * piper_hip_voice_loudness and pass the resulting gain as a level's `drive` or a mixed row's `gain`; slot_loudness does not touch streams. */
+typedef struct {
+  float target_lufs;  /* 0 is taken as −16 */
+  float max_gain_db;  /* 0 is taken as 20 */
+} piper_hip_loudness; /* all zero = {−16, 20} */
+/* Host-only (no device needed). loudness_check: PIPER_HIP_ERR_ARG with a message that names the field. loudness_coeffs: the two biquads at
+ * `rate`, a[0] = 1. loudness_from_f32: the sequential double twin of the kernels, n host floats → L (n may be 0: −∞). loudness_gain: g for a
+ * reported L (−∞ → 1.0; NaN or +∞ is PIPER_HIP_ERR_ARG). */
+int piper_hip_loudness_check(const piper_hip_loudness* loudness);
+int piper_hip_loudness_coeffs(int32_t rate, double shelf_b[3], double shelf_a[3], double hp_b[3], double hp_a[3]);
+int piper_hip_loudness_from_f32(int32_t rate, const float* x, size_t n, float* lufs);
+int piper_hip_loudness_gain(const piper_hip_loudness* loudness, float lufs, float* gain);
+/* Per-op: `count` device floats sampled at `rate` → one fp32 L in host memory. With a non-NULL stream the value is there after
+ * piper_hip_stream_sync. count may be 0, which gives −∞. */
+int piper_hip_loudness_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t rate, float* lufs_host, piper_hip_stream stream);
+/* Whole items: the loudness target of slot id `slot`, state of the slot id exactly like slot_level: it persists until replaced, NULL
+ * clears it. Every later collect, collect_pcm16, collect_pcm16_rate, collect_g711 and the synthesize twins (slot 0) on that slot deliver u
+ * — or the limited u when the slot also has a level — on plain, ragged and bounded slots; on bounded slots the lengths are read from device
+ * memory, and nothing new waits for the GPU. The fp32 audio in the plan and the `audio` tap stay raw. normalize = 1 together with a
+ * loudness is PIPER_HIP_ERR_ARG, before anything is waited for. A voice whose rate is not in the list is PIPER_HIP_ERR_UNSUPPORTED here. */
+int piper_hip_voice_slot_loudness(piper_hip_voice* v, int slot, const piper_hip_loudness* loudness);
+/* Waits for the slot, measures the raw items of its latest launch if that has not happened yet (the measurement is kept until the next
+ * launch or prepare), and returns per item L and the g the slot's target implies, 1.0 when the slot has no target. Either array may be
+ * NULL; a non-NULL one holds max_items entries (fewer than the slot's items is PIPER_HIP_ERR_SHAPE). A bounded slot that has not been
+ * collected is PIPER_HIP_ERR_ARG. */
+int piper_hip_voice_loudness(piper_hip_voice* v, int slot, float* lufs, float* gain, int max_items);
+
 /* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
  * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]
  * (the graph's `sid` input, read by PiperMetalRuntime.synthesize next to `scales`, PiperMetalRuntime.swift:62-80; in the graph a Gather

@@ -24,6 +24,7 @@
 #include "conv_bf16.h"
 #include "conv_win.h"
 #include "level.h"
+#include "loudness.h"
 #include "pcm16.h"
 #include "resample.h"
 #include "rng.h"
@@ -385,6 +386,11 @@ struct Slot {
   // Level control (piper_hip_voice_slot_level): device buffers of this plan (in `owned`), allocated on first use
   float* lim = nullptr;          // [NB][n_samples] the limited items, the layout of `audio`
   float* lim_scratch = nullptr;  // lv_scratch_floats(NB, F·hop)
+  // Loudness (piper_hip_voice_slot_loudness, piper_hip_voice_loudness): device buffers of this plan (in `owned`), allocated on first use
+  float* gained = nullptr;       // [NB][n_samples] the items times their loudness gain, the layout of `audio`
+  double* loud_seg = nullptr;    // [NB][ld_work_row(F·hop)] the passes' shares of Σ y² per 100 ms segment of the latest launch's raw items
+  float* loud_rep = nullptr;     // [NB][2] {L, g} as the gate kernel last wrote them
+  bool loud_measured = false;    // loud_seg holds the latest launch (cleared where h_peaks is)
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
@@ -516,6 +522,8 @@ struct piper_hip_voice {
     size_t cap_desc = 0;
     float* h_peaks = nullptr;  // collect_pcm16 with normalize = 1: the items' peaks, written by the pack kernel through the host mapping
     size_t cap_peaks = 0;
+    float* h_loud = nullptr;   // piper_hip_voice_loudness: {L, g} per item as the gate kernel reported them
+    size_t cap_loud = 0;
     std::vector<hipEvent_t> chunk_ev;  // collect, 1 … 16 MB waveforms: one event per 1 MB chunk landed in h_audio
     piper_hip_speaker* h_spk = nullptr;  // the items' speakers of a prepare (a voice with a speaker table)
     size_t cap_spk = 0;
@@ -538,6 +546,8 @@ struct piper_hip_voice {
   std::vector<piper_hip_speaker> slot_spk[kMaxSlots];
   // The level of each slot id's whole-item collects (piper_hip_voice_slot_level), as given; on = false: none.
   struct SlotLevel { bool on = false; piper_hip_level lv{}; } slot_lv[kMaxSlots];
+  // The loudness target of each slot id's whole-item collects (piper_hip_voice_slot_loudness), as given; on = false: none.
+  struct SlotLoudness { bool on = false; piper_hip_loudness ld{}; } slot_ld[kMaxSlots];
   bool planned = false;  // a plan has been asked for: the voice's schedules are fixed (no attach_speakers any more)
   Slot* attached[kMaxSlots] = {};
   std::unique_ptr<StreamPool> pools[kMaxSlots];  // the streaming pool a slot id holds (then attached[slot] is null)
@@ -866,6 +876,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.zin = nullptr; s.z_out = nullptr;
   s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();  // (these too)
   s.lim = nullptr; s.lim_scratch = nullptr;
+  s.gained = nullptr; s.loud_seg = nullptr; s.loud_rep = nullptr; s.loud_measured = false;
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
@@ -2504,6 +2515,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_noise) (void)hipHostFree(sg.h_noise);
     if (sg.h_desc) (void)hipHostFree(sg.h_desc);
     if (sg.h_peaks) (void)hipHostFree(sg.h_peaks);
+    if (sg.h_loud) (void)hipHostFree(sg.h_loud);
     if (sg.h_spk) (void)hipHostFree(sg.h_spk);
     if (sg.h_pro) (void)hipHostFree(sg.h_pro);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
@@ -2903,6 +2915,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);  // noise / scalars come from caller memory
   s.timed = false;
   s.h_peaks.clear();
+  s.loud_measured = false;
   return slot;
 }
 
@@ -3082,6 +3095,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   s.bounded_cap = std::min(max_frames, F);
   s.timed = false;
   s.h_peaks.clear();
+  s.loud_measured = false;
   return slot;
 }
 
@@ -3316,11 +3330,61 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__
 
 int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
 
-// What a collect of slot id `slot` reads: the plan's audio, or — the slot id has a level (piper_hip_voice_slot_level) — the limited items
-// lim [NB][n_samples], computed here behind the plan's graph on its stream from lengths the device holds (plain, ragged and bounded
-// slots alike). The plan's audio stays raw.
-int level_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
+// {L, g} of the plan's raw items into s.loud_rep, behind the plan's graph on its stream, from lengths the device holds: the K-weighted
+// segment powers once per launch, the gates and the gain of target `t` every time (include/piper_hip.h "Loudness").
+int loudness_measure(piper_hip_voice* v, Slot& s, const LdTarget& t) {
+  LdFilter f;
+  int rc = ld_filter(v->cfg.sample_rate, &f);
+  if (rc) return rc;
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "loudness: the slot holds no samples");
+  void* q = nullptr;
+  if (!s.loud_seg) {
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * ld_work_row((int64_t)F * v->hop) * sizeof(double), &q))) return rc;
+    s.loud_seg = (double*)q;
+    s.loud_measured = false;
+  }
+  if (!s.loud_rep) {
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * 2 * sizeof(float), &q))) return rc;
+    s.loud_rep = (float*)q;
+  }
+  if (!s.loud_measured) {
+    PH_HIP(launch_loudness_measure(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, 0, f, s.loud_seg), PIPER_HIP_ERR_LAUNCH);
+    s.loud_measured = true;
+  }
+  PH_HIP(launch_loudness_gate(s.set.stream, s.lensF, F, v->hop, s.NB, 0, f.h, s.loud_seg, t, s.loud_rep), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
+// The items a slot id with a loudness target (piper_hip_voice_slot_loudness) hands the rest of the output chain: gained [NB][n_samples],
+// u = x·g per item. Without a target: the plan's audio.
+int loudness_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
   *audio = s.audio;
+  const auto& sl = v->slot_ld[slot];
+  if (!sl.on) return PIPER_HIP_OK;
+  LdTarget t;
+  int rc = ld_resolve(&sl.ld, &t);
+  if (rc) return rc;
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
+  if (F < 1) return PIPER_HIP_OK;
+  if ((rc = loudness_measure(v, s, t))) return rc;
+  if (!s.gained) {
+    void* q = nullptr;
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
+    s.gained = (float*)q;
+  }
+  PH_HIP(launch_loudness_gain(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, s.loud_rep, s.gained, s.n_samples), PIPER_HIP_ERR_LAUNCH);
+  *audio = s.gained;
+  return PIPER_HIP_OK;
+}
+
+// What a collect of slot id `slot` reads: the plan's audio, or — the slot id has a loudness target — the gained items, or — the slot id has
+// a level (piper_hip_voice_slot_level) — the limited (gained) items lim [NB][n_samples], computed here behind the plan's graph on its
+// stream from lengths the device holds (plain, ragged and bounded slots alike). The plan's audio stays raw.
+int level_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
+  const float* src = s.audio;
+  if (int lrc = loudness_audio(v, slot, s, &src)) return lrc;
+  *audio = src;
   const auto& sl = v->slot_lv[slot];
   if (!sl.on) return PIPER_HIP_OK;
   LvParams p;
@@ -3337,7 +3401,7 @@ int level_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
     if ((rc = plan_alloc(v, s, lv_scratch_floats(s.NB, (int64_t)F * v->hop) * sizeof(float), &q))) return rc;
     s.lim_scratch = (float*)q;
   }
-  PH_HIP(launch_level_items(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, 0, p, s.lim_scratch, s.lim, s.n_samples), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(launch_level_items(s.set.stream, src, s.n_samples, s.lensF, F, v->hop, s.NB, 0, p, s.lim_scratch, s.lim, s.n_samples), PIPER_HIP_ERR_LAUNCH);
   *audio = s.lim;
   return PIPER_HIP_OK;
 }
@@ -3357,6 +3421,7 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);
   s.timed = true;
   s.h_peaks.clear();  // the peaks a normalising collect_pcm16 reported belong to the previous run
+  s.loud_measured = false;  // (and so does the loudness measured there)
   return PIPER_HIP_OK;
 }
 
@@ -4714,6 +4779,8 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   if (rc) return rc;
   if (normalize && slot >= 0 && slot < kMaxSlots && v->slot_lv[slot].on)
     PH_FAIL(PIPER_HIP_ERR_ARG, "collect_pcm16: normalize = 1 on slot %d, which has a level (piper_hip_voice_slot_level)", slot);
+  if (normalize && slot >= 0 && slot < kMaxSlots && v->slot_ld[slot].on)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "collect_pcm16: normalize = 1 on slot %d, which has a loudness (piper_hip_voice_slot_loudness)", slot);
   const float gain = out.gain;
   const RsDesign* rd = nullptr;
   RsFilter rf{};
@@ -4812,6 +4879,7 @@ int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper
   if (!rc) rc = pcm_params(params, &gain, &normalize);
   if (rc) return rc;
   if (normalize && v->slot_lv[0].on) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16: normalize = 1 on slot 0, which has a level (piper_hip_voice_slot_level)");
+  if (normalize && v->slot_ld[0].on) PH_FAIL(PIPER_HIP_ERR_ARG, "pcm16: normalize = 1 on slot 0, which has a loudness (piper_hip_voice_slot_loudness)");
   const RsDesign* rd = nullptr;
   if (out_rate != v->cfg.sample_rate && (rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
   if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
@@ -4915,6 +4983,44 @@ PH_EXPORT int piper_hip_voice_slot_level(piper_hip_voice* v, int slot, const pip
     if (int rc = piper_hip_level_check(level)) return rc;
   v->slot_lv[slot].on = level != nullptr;
   v->slot_lv[slot].lv = level ? *level : piper_hip_level{0.0f, 0.0f, 0.0f};
+  return PIPER_HIP_OK;
+}
+
+// ---- loudness (include/piper_hip.h "Loudness")
+
+PH_EXPORT int piper_hip_voice_slot_loudness(piper_hip_voice* v, int slot, const piper_hip_loudness* loudness) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (loudness) {
+    if (int rc = piper_hip_loudness_check(loudness)) return rc;
+    LdFilter f;
+    if (int rc = ld_filter(v->cfg.sample_rate, &f)) return rc;  // (the voice's rate is outside the contract)
+  }
+  v->slot_ld[slot].on = loudness != nullptr;
+  v->slot_ld[slot].ld = loudness ? *loudness : piper_hip_loudness{0.0f, 0.0f};
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_loudness(piper_hip_voice* v, int slot, float* lufs, float* gain, int max_items) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  Slot* p = slot_plan(v, slot);
+  if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
+  Slot& s = *p;
+  if (s.bounded_pending) PH_FAIL(PIPER_HIP_ERR_ARG, "loudness: the slot's frame counts are still on the device (collect first)");
+  if ((lufs || gain) && max_items < s.NB) PH_FAIL(PIPER_HIP_ERR_SHAPE, "loudness: buffer holds %d < %d items", max_items, s.NB);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  LdTarget t;
+  int rc = ld_resolve(v->slot_ld[slot].on ? &v->slot_ld[slot].ld : nullptr, &t);
+  if (rc) return rc;
+  if ((rc = loudness_measure(v, s, t))) return rc;
+  auto& sg = v->staging[slot];
+  if ((rc = grow_pinned(sg.h_loud, sg.cap_loud, (size_t)2 * s.NB, (size_t)2 * kMaxGroup))) return rc;
+  PH_HIP(hipMemcpyAsync(sg.h_loud, s.loud_rep, (size_t)2 * s.NB * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
+  for (int b = 0; b < s.NB; b++) {
+    if (lufs) lufs[b] = sg.h_loud[2 * b];
+    if (gain) gain[b] = sg.h_loud[2 * b + 1];
+  }
   return PIPER_HIP_OK;
 }
 

@@ -59,6 +59,7 @@ RELU, LEAKYRELU, TANH, SIGMOID, EXP, NEG, SQRT, SOFTPLUS, CEIL, ERF = range(10)
 ADD, SUB, MUL, DIV, POW = range(5)
 
 c_f32p = C.POINTER(C.c_float)
+c_f64p = C.POINTER(C.c_double)
 c_i64p = C.POINTER(C.c_int64)
 c_i32p = C.POINTER(C.c_int32)
 c_vp = C.c_void_p
@@ -259,7 +260,27 @@ def _level(level):
     return Level(float(d), float(c), float(r))
 
 
-KEEP = object()  # level=KEEP: leave the slot id's level as it is
+KEEP = object()  # level=KEEP / loudness=KEEP: leave the slot id's level / loudness as it is
+
+
+class Loudness(C.Structure):
+    """piper_hip_loudness: the BS.1770 target of include/piper_hip.h "Loudness". A zero field takes its default: {−16 LUFS, 20 dB}."""
+    _fields_ = [("target_lufs", C.c_float), ("max_gain_db", C.c_float)]
+
+    def __repr__(self):
+        return "Loudness(target_lufs=%g, max_gain_db=%g)" % (self.target_lufs, self.max_gain_db)
+
+
+def _loudness(loudness):
+    """Loudness | target | (target_lufs, max_gain_db) | dict → a Loudness"""
+    if isinstance(loudness, Loudness):
+        return loudness
+    if isinstance(loudness, dict):
+        return Loudness(float(loudness.get("target_lufs", 0.0)), float(loudness.get("max_gain_db", 0.0)))
+    if isinstance(loudness, (int, float)):
+        return Loudness(float(loudness), 0.0)
+    t, m = loudness
+    return Loudness(float(t), float(m))
 
 
 class KernelStat(C.Structure):
@@ -423,6 +444,13 @@ _PROTOS = {
     "piper_hip_voice_slot_level": (C.c_int, [c_vp, C.c_int, C.POINTER(Level)]),
     "piper_hip_voice_stream_set_level": (C.c_int, [c_vp, C.c_int, C.POINTER(Level)]),
     "piper_hip_voice_stream_level": (C.c_int, [c_vp, C.c_int, C.POINTER(Level)]),
+    "piper_hip_loudness_check": (C.c_int, [C.POINTER(Loudness)]),
+    "piper_hip_loudness_coeffs": (C.c_int, [C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "piper_hip_loudness_from_f32": (C.c_int, [C.c_int32, c_f32p, C.c_size_t, c_f32p]),
+    "piper_hip_loudness_gain": (C.c_int, [C.POINTER(Loudness), C.c_float, c_f32p]),
+    "piper_hip_loudness_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_int32, c_f32p, c_vp]),
+    "piper_hip_voice_slot_loudness": (C.c_int, [c_vp, C.c_int, C.POINTER(Loudness)]),
+    "piper_hip_voice_loudness": (C.c_int, [c_vp, C.c_int, c_f32p, c_f32p, C.c_int]),
     "piper_hip_voice_stream_set_mixed": (C.c_int, [c_vp, C.c_int]),
     "piper_hip_voice_stream_item_formats": (C.c_int, [c_vp, C.c_int, C.POINTER(StreamFormat), C.c_int]),
     "piper_hip_voice_stream_pool_join_formats": (C.c_int, [c_vp, C.c_int, C.POINTER(Utterance), C.c_int, C.c_int, C.POINTER(StreamFormat),
@@ -810,6 +838,15 @@ class HipBackend:
         lv = _level(level)
         _check(self.lib.piper_hip_level_f32(self.ctx, _ptr(buf), n, int(rate), C.byref(lv), C.byref(p), commandBuffer))
         return DeviceBuffer(self, p.value, n, owned=out is None)
+
+    def loudness_f32(self, buf, rate, count=None, commandBuffer=None):
+        """`count` device floats sampled at `rate` → their BS.1770 integrated loudness in LUFS, measured on the device
+        (piper_hip_loudness_f32; include/piper_hip.h "Loudness"). −inf for an item too short to measure. With a commandBuffer the value
+        is final after its sync: then a one-element float32 array is returned instead of a number."""
+        n = buf.count if count is None else int(count)
+        out = np.empty(1, np.float32)
+        _check(self.lib.piper_hip_loudness_f32(self.ctx, _ptr(buf), n, int(rate), out.ctypes.data_as(c_f32p), commandBuffer))
+        return out if commandBuffer is not None else np.float32(out[0])
 
     def resampleF32(self, buf, inRate, outRate, count=None, out=None, commandBuffer=None):
         """`count` device floats at inRate → J(count) device floats at outRate (piper_hip_resample_f32): the fp32 y of the output-rate
@@ -1243,6 +1280,34 @@ def level_from_f32(samples, level, rate):
     return y
 
 
+def loudness_check(loudness):
+    """InvalidArgument naming the field for a loudness target outside the contract (piper_hip_loudness_check). Host-only."""
+    ld = _loudness(loudness)
+    _check(load_library().piper_hip_loudness_check(C.byref(ld)))
+
+
+def loudness_coeffs(rate):
+    """(shelf_b, shelf_a, hp_b, hp_a), float64 [3] each: the K-weighting biquads at `rate` (piper_hip_loudness_coeffs). Host-only."""
+    c = [np.empty(3, np.float64) for _ in range(4)]
+    _check(load_library().piper_hip_loudness_coeffs(int(rate), *[a.ctypes.data_as(c_f64p) for a in c]))
+    return tuple(c)
+
+
+def loudness_from_f32(samples, rate):
+    """BS.1770 integrated loudness of host floats in LUFS (piper_hip_loudness_from_f32): the sequential double twin of the kernels."""
+    x = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    out = C.c_float()
+    _check(load_library().piper_hip_loudness_from_f32(int(rate), x.ctypes.data_as(c_f32p), x.size, C.byref(out)))
+    return np.float32(out.value)
+
+
+def loudness_gain(loudness, lufs):
+    """The fp32 gain that target implies for an item measured at `lufs` (piper_hip_loudness_gain); 1.0 for −inf. Host-only."""
+    ld, g = _loudness(loudness), C.c_float()
+    _check(load_library().piper_hip_loudness_gain(C.byref(ld), float(lufs), C.byref(g)))
+    return np.float32(g.value)
+
+
 def piper_json(text):
     info = PiperJsonInfo()
     _check(load_library().piper_hip_piper_json(text.encode("utf-8"), C.byref(info)))
@@ -1524,14 +1589,16 @@ class HipRuntime:
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
     def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None,
-                   level=KEEP, **kw):
+                   level=KEEP, loudness=KEEP, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
         reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
         speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays.
-        level: a Level (or tuple / dict) becomes slot 0's level (slot_level) and stays; None clears it."""
+        level: a Level (or tuple / dict) becomes slot 0's level (slot_level) and stays; None clears it. loudness: the same for slot 0's
+        loudness target (slot_loudness)."""
         if speaker is not None:
             self.slot_speakers(0, [speaker])
         self._slot_level(0, level)
+        self._slot_loudness(0, loudness)
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
@@ -1645,6 +1712,27 @@ class HipRuntime:
     def _slot_level(self, slot, level):
         if level is not KEEP:
             self.slot_level(slot, level)
+
+    def slot_loudness(self, slot, loudness):
+        """The loudness target of slot id `slot`'s whole-item collects (piper_hip_voice_slot_loudness): a Loudness, a target in LUFS, a
+        (target_lufs, max_gain_db) pair or a dict; it persists until replaced; None clears it."""
+        if loudness is None:
+            _check(self.lib.piper_hip_voice_slot_loudness(self.voice, slot, None))
+        else:
+            ld = _loudness(loudness)
+            _check(self.lib.piper_hip_voice_slot_loudness(self.voice, slot, C.byref(ld)))
+
+    def _slot_loudness(self, slot, loudness):
+        if loudness is not KEEP:
+            self.slot_loudness(slot, loudness)
+
+    def loudness(self, slot):
+        """(lufs, gain), float32 per item: the BS.1770 integrated loudness of the raw items of the slot's latest launch, measured on the
+        device, and the gain the slot's target implies (1.0 without one) — piper_hip_voice_loudness. Waits for the slot."""
+        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
+        lufs, gain = np.empty(max(nb, 1), np.float32), np.empty(max(nb, 1), np.float32)
+        _check(self.lib.piper_hip_voice_loudness(self.voice, slot, lufs.ctypes.data_as(c_f32p), gain.ctypes.data_as(c_f32p), nb))
+        return lufs[:nb], gain[:nb]
 
     def stream_set_level(self, slot, level):
         """The level of the stream on `slot` (piper_hip_voice_stream_set_level): after its begin / open, before its first step."""
@@ -1840,9 +1928,11 @@ class HipRuntime:
         self._pinned.append(p)
         return np.ctypeslib.as_array(C.cast(p, c_f32p), shape=(int(count),))
 
-    def collect(self, slot, want_audio=True, out=None, level=KEEP):
-        """level: a Level (or tuple / dict) sets the slot id's level before the call, None clears it (slot_level); it persists."""
+    def collect(self, slot, want_audio=True, out=None, level=KEEP, loudness=KEEP):
+        """level: a Level (or tuple / dict) sets the slot id's level before the call, None clears it (slot_level); it persists.
+        loudness: the same for the slot id's loudness target (slot_loudness)."""
         self._slot_level(slot, level)
+        self._slot_loudness(slot, loudness)
         n = self._keep[slot][1]
         if not want_audio:
             _check(self.lib.piper_hip_voice_collect(self.voice, slot, None, 0))
@@ -1856,12 +1946,13 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
-    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None, level=KEEP):
+    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP):
         """collect() with 16-bit PCM converted on the device (piper_hip_voice_collect_pcm16): the items back to back at their true lengths.
         normalize=False: the samples pcm16(collect(slot)) gives; normalize=True: Piper's peak normalisation per item (peaks(slot) afterwards).
         The fp32 waveform stays in the plan: collect / collect_pcm16 may follow in any order. rate: resampled on the device to that output
-        rate (piper_hip_voice_collect_pcm16_rate), item b at J(its true samples). level: as for collect."""
+        rate (piper_hip_voice_collect_pcm16_rate), item b at J(its true samples). level, loudness: as for collect."""
         self._slot_level(slot, level)
+        self._slot_loudness(slot, loudness)
         n = self._keep[slot][1]
         if rate is not None and int(rate) != self.cfg.sample_rate:  # (the voice's own rate is not a filter: the plain call)
             return self._collect_pcm16_rate(slot, gain, normalize, out, int(rate))
@@ -1892,10 +1983,11 @@ class HipRuntime:
         return out[:sum(resample_count(src, rate, p) for p in per)]
 
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, rate=None, prosody=None, level=KEEP, **kw):
+                         normalize=False, rate=None, prosody=None, level=KEEP, loudness=KEEP, **kw):
         """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare;
-        level: as for collect (slot 0)."""
+        level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
+        self._slot_loudness(0, loudness)
         pro = None if prosody is None else [prosody]
         if rate is not None and int(rate) == self.cfg.sample_rate:
             rate = None
@@ -1924,10 +2016,11 @@ class HipRuntime:
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
 
-    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None, level=KEEP):
+    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP):
         """collect_pcm16 ending in G.711 bytes ("mulaw" / "alaw") companded on the device (piper_hip_voice_collect_g711): one uint8 per
         sample, the items back to back at J(their true samples) at `rate` (default: the voice's own). Every rule of collect_pcm16 holds."""
         self._slot_level(slot, level)
+        self._slot_loudness(slot, loudness)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         count = (lambda p: p) if rate == src else (lambda p: resample_count(src, rate, p))
@@ -1946,10 +2039,11 @@ class HipRuntime:
         return out[:sum(count(p) for p in per)]
 
     def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None,
-                        level=KEEP):
+                        level=KEEP, loudness=KEEP):
         """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's;
-        prosody: as for prepare (with supplied durations: noise alone); level: as for collect (slot 0)."""
+        prosody: as for prepare (with supplied durations: noise alone); level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
+        self._slot_loudness(0, loudness)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)

@@ -270,6 +270,44 @@ public final class HIPBackend {
         return b
     }
 
+    // ---- loudness (include/piper_hip.h "Loudness") ----
+
+    /// `count` device floats sampled at `rate` → their BS.1770 integrated loudness in LUFS, measured on the device
+    /// (piper_hip_loudness_f32); −∞ for an item too short to measure. The call blocks: the value is final when it returns.
+    public func loudnessF32(input: HIPBuffer, count: Int, rate: Int32) throws -> Float {
+        var lufs: Float = 0
+        try Self.check(piper_hip_loudness_f32(ctx, input.f32, count, rate, &lufs, nil))
+        return lufs
+    }
+
+    /// BS.1770 integrated loudness of host floats (piper_hip_loudness_from_f32): the sequential double twin of the kernels.
+    public static func loudnessFromF32(_ x: [Float], rate: Int32) throws -> Float {
+        var lufs: Float = 0
+        try check(piper_hip_loudness_from_f32(rate, x, x.count, &lufs))
+        return lufs
+    }
+
+    /// InvalidArgument naming the field for a loudness target outside the contract (piper_hip_loudness_check; host-only).
+    public static func loudnessCheck(_ loudness: piper_hip_loudness) throws {
+        var ld = loudness
+        try check(piper_hip_loudness_check(&ld))
+    }
+
+    /// The K-weighting biquads at `rate`, three coefficients each, a[0] = 1 (piper_hip_loudness_coeffs; host-only).
+    public static func loudnessCoeffs(rate: Int32) throws -> (shelfB: [Double], shelfA: [Double], hpB: [Double], hpA: [Double]) {
+        var sb = [Double](repeating: 0, count: 3), sa = sb, hb = sb, ha = sb
+        try check(piper_hip_loudness_coeffs(rate, &sb, &sa, &hb, &ha))
+        return (sb, sa, hb, ha)
+    }
+
+    /// The fp32 gain `loudness` implies for an item measured at `lufs` (piper_hip_loudness_gain; host-only); 1 for −∞.
+    public static func loudnessGain(_ loudness: piper_hip_loudness, lufs: Float) throws -> Float {
+        var ld = loudness
+        var g: Float = 1
+        try check(piper_hip_loudness_gain(&ld, lufs, &g))
+        return g
+    }
+
     // ---- binary with NumPy broadcasting, output rank ≤ 4 (MetalBackend.swift:2099-2134, 2592-2610) ----
     private func binaryBroadcastF32(_ op: piper_hip_binary_op, a: HIPBuffer, aShape: [Int], b: HIPBuffer, bShape: [Int],
                                     commandBuffer: Stream?) throws -> (out: HIPBuffer, outShape: [Int]) {

@@ -459,6 +459,25 @@ public final class PiperHIPRuntime {
         }
     }
 
+    /// The loudness target of slot id `slot`'s whole-item collects (piper_hip_voice_slot_loudness): it persists until replaced; nil
+    /// clears it. Every later collect* and synthesize* on the slot id delivers the items at that BS.1770 loudness, in front of the level.
+    public func slotLoudness(slot: Int32, loudness: piper_hip_loudness?) throws {
+        if var ld = loudness {
+            try HIPBackend.check(piper_hip_voice_slot_loudness(voice, slot, &ld))
+        } else {
+            try HIPBackend.check(piper_hip_voice_slot_loudness(voice, slot, nil))
+        }
+    }
+
+    /// Per item of the slot's latest launch: the integrated loudness of the raw samples, measured on the device, and the gain the
+    /// slot's target implies, 1 without one (piper_hip_voice_loudness). Waits for the slot.
+    public func loudness(slot: Int32) throws -> (lufs: [Float], gain: [Float]) {
+        let n = Int(piper_hip_voice_batch_size(voice, slot))
+        var lufs = [Float](repeating: 0, count: max(n, 1)), gain = lufs
+        try HIPBackend.check(piper_hip_voice_loudness(voice, slot, &lufs, &gain, Int32(n)))
+        return (Array(lufs[0..<n]), Array(gain[0..<n]))
+    }
+
     /// The level of the stream on `slot` (piper_hip_voice_stream_set_level): where streamSetRate is allowed, in either order with it.
     public func streamSetLevel(slot: Int32, level: piper_hip_level) throws {
         var lv = level
