@@ -23,6 +23,9 @@
  *                            --loudness LUFS [--max-gain-db X]: BS.1770 integrated loudness measured on the device and the utterance
  *                            brought to that target in front of the limiter and every output above (piper_hip_voice_slot_loudness on
  *                            slot 0; X defaults to 20); the measured loudness and the gain go to stderr. Not with --normalize.
+ *                            --id-volume I:J=G[,I:J=G…]: a volume per phoneme id, ids I … J − 1 at the linear gain G (0 … 16) and the
+ *                            others at 1.0, ramped between ids on the device in front of the loudness gain, the limiter and every
+ *                            output above (piper_hip_voice_slot_volume on slot 0).
  *   --speaker N              both modes: speaker N of a multi-speaker voice (the graph's `sid`; piper_hip_voice_attach_speakers +
  *                            piper_hip_voice_slot_speakers). With --model the file's speaker table is loaded (opt-in: without the flag such a
  *                            file is refused; its node graph is NOT verified — no verifier for the conditioned graph exists yet); without
@@ -95,7 +98,37 @@ typedef struct {
   int predict, pin_frames;
   float* audio;
   int64_t audio_cap;
+  float* id_gain; /* --id-volume: one gain per id of the utterance, NULL without the flag */
 } runner;
+
+/* --id-volume: the volume of the staging call that follows (the assignment is that call's alone, so it is made before each) */
+static int stage_volume(runner* r, int t) {
+  piper_hip_volume vol;
+  if (!r->id_gain) return 0;
+  vol.gain = r->id_gain; vol.t = t;
+  return piper_hip_voice_slot_volume(r->voice, 0, &vol, 1);
+}
+
+/* "I:J=G[,I:J=G…]" → gain[t], 1.0 where no range names the id; 0 on success */
+static int parse_id_volume(const char* s, float* gain, int t) {
+  for (int i = 0; i < t; i++) gain[i] = 1.0f;
+  while (*s) {
+    char* end = NULL;
+    const long a = strtol(s, &end, 10);
+    if (end == s || *end != ':') return -1;
+    s = end + 1;
+    const long b = strtol(s, &end, 10);
+    if (end == s || *end != '=') return -1;
+    s = end + 1;
+    const float g = strtof(s, &end);
+    if (end == s || a < 0 || b < a || b > t) return -1;
+    for (long i = a; i < b; i++) gain[i] = g;
+    s = end;
+    if (*s == ',') s++;
+    else if (*s) return -1;
+  }
+  return 0;
+}
 
 /* PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:) on slot 0; *samples = waveform length */
 static int run_one(runner* r, const int64_t* ids, int t, int64_t* samples) {
@@ -109,7 +142,8 @@ static int run_one(runner* r, const int64_t* ids, int t, int64_t* samples) {
     for (int i = 0; i < t; i++) dur[i] = r->pin_frames;
     u.durations = dur;
   }
-  int rc = piper_hip_voice_prepare(r->voice, &u, 0);
+  int rc = stage_volume(r, t);
+  if (rc >= 0) rc = piper_hip_voice_prepare(r->voice, &u, 0);
   free(dur);
   if (rc < 0) return rc;
   int64_t n = 0;
@@ -148,12 +182,13 @@ static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_p
     if (cap >= 0 && rate != in_rate) cap = piper_hip_resample_count(in_rate, rate, cap);
     rc = cap < 0 ? (int)cap : 0;
     if (!rc) *pcm = malloc(elem * (size_t)(cap > 0 ? cap : 1));
+    if (!rc) rc = stage_volume(r, t);
     if (!rc) rc = law ? piper_hip_voice_synthesize_g711(r->voice, &u, prm, law, rate, (uint8_t*)*pcm, cap, samples)
                       : piper_hip_voice_synthesize_pcm16_rate(r->voice, &u, prm, rate, (int16_t*)*pcm, cap, samples);
     free(dur);
     return rc;
   }
-  if (!ran && (rc = piper_hip_voice_prepare(r->voice, &u, 0)) < 0) return rc;
+  if (!ran && ((rc = stage_volume(r, t)) < 0 || (rc = piper_hip_voice_prepare(r->voice, &u, 0)) < 0)) return rc;
   if ((rc = piper_hip_voice_prepared_samples(r->voice, 0, NULL, 0, &cap)) < 0) return rc;
   if (rate != in_rate && (cap = piper_hip_resample_count(in_rate, rate, cap)) < 0) return (int)cap;
   *pcm = malloc(elem * (size_t)(cap > 0 ? cap : 1));
@@ -185,7 +220,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
                     "                [--output-encoding s16le|mulaw|alaw] [--drive X] [--ceiling Y] [--release-ms Z]\n"
-                    "                [--loudness LUFS [--max-gain-db X]]\n"
+                    "                [--loudness LUFS [--max-gain-db X]] [--id-volume I:J=G[,I:J=G...]]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n"
                     "               [--speaker N [--speakers S]]\n", argv[0], argv[0]);
     return 2;
@@ -302,6 +337,24 @@ int main(int argc, char** argv) {
       if (ld.target_lufs == 0.0f) { fprintf(stderr, "--loudness %s: expected a target in LUFS, -70 ... -1\n", loud_arg); return 2; }
       CHECK(piper_hip_voice_slot_loudness(r.voice, 0, &ld));
     }
+    const char* idvol_arg = arg_value(argc, argv, "--id-volume");
+    if (idvol_arg) { /* slot 0's volume for the utterance: ids I … J − 1 at gain G, ramped between ids on the device */
+      r.id_gain = (float*)malloc(sizeof(float) * (size_t)t);
+      piper_hip_volume vol;
+      int bad = parse_id_volume(idvol_arg, r.id_gain, t) != 0;
+      if (bad) fprintf(stderr, "--id-volume %s: expected I:J=G[,I:J=G...] with 0 <= I <= J <= %d ids\n", idvol_arg, t);
+      vol.gain = r.id_gain; vol.t = t;
+      if (!bad && piper_hip_volume_check(&vol) < 0) { /* a gain outside [0, 16] */
+        fprintf(stderr, "--id-volume %s: %s\n", idvol_arg, piper_hip_last_error());
+        bad = 1;
+      }
+      if (bad) { /* leave as the success path does */
+        free(r.id_gain);
+        piper_hip_voice_destroy(r.voice);
+        piper_hip_destroy(ctx);
+        return 2;
+      }
+    }
     if (out) {
       CHECK(run_one(&r, ids, t, &n));
       CHECK(piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu));
@@ -351,6 +404,7 @@ int main(int argc, char** argv) {
       fprintf(stderr, "loudness %.4f LUFS, gain %.6g\n", (double)lufs, (double)g);
     }
     free(r.audio);
+    free(r.id_gain);
     piper_hip_voice_destroy(r.voice);
     piper_hip_destroy(ctx);
     return 0;

@@ -853,6 +853,69 @@ int piper_hip_voice_slot_loudness(piper_hip_voice* v, int slot, const piper_hip_
  * collected is PIPER_HIP_ERR_ARG. */
 int piper_hip_voice_loudness(piper_hip_voice* v, int slot, float* lufs, float* gain, int max_items);
 
+/* ---- Per-phoneme volume: a gain envelope on the device (DESIGN.md §4 "Volume") ----
+ * Prosody controls how long an id lasts and how lively it is, level and loudness how loud a whole item is. What is left is the volume of a
+ * word or a phoneme: SSML <prosody volume>, <emphasis>, a ducked parenthesis, a muted id. A host cannot shape it afterwards: on the
+ * bounded route the frames per id are decided on the device, and on the PCM, rate and G.711 routes it receives integers at another rate,
+ * behind the limiter and the loudness gain. So the volume is one more stage of the output chain, on whole items and on every stream route
+ * — generator → volume → loudness gain → level → resampler → PCM / G.711 / mixed — and it changes nothing for a request that does not ask
+ * for it. The envelope is a
+ * contract, bit for bit. All arithmetic is fp32, each operation rounded on its own (no FMA); fl() marks a rounding:
+ *   gain[t]    one linear gain per phoneme id, finite, in [0, 16]; otherwise PIPER_HIP_ERR_ARG. A NULL array, or an item without a volume,
+ *              is all 1.0.
+ *   F, hop     the item's true frame count (the rule of every route: max(Σ d, 1)) and Π up_rates.
+ *   gf[f]      = gain[t(f)], f in [0, F). t(f) is the id frame f belongs to: the smallest t with cum[t] > f, cum the running sum of the
+ *              frames per id. The single frame of an all-zero duration row belongs to id 0. This is what the plan's frame-to-id map holds.
+ *   c          = hop div 2. Frame f is centred on sample f·hop + c.
+ *   for sample n in [0, F·hop):
+ *     m = n − c;  k = floor(m / hop) (k = −1 for n < c);  i = m − k·hop, in [0, hop)
+ *     a = gf[max(k, 0)];  b = gf[min(k + 1, F − 1)]
+ *     w = the correctly rounded fp32 quotient (float)i / (float)hop          (exact for hop = 256, the hop of every preset)
+ *     e(n) = fl(a + fl(fl(b − a) · w))
+ *     v[n] = fl(x[n] · e(n))
+ * Where neighbouring frames share a gain, b − a = 0 and e is that gain exactly; between two ids the gain moves linearly over one hop
+ * (11.6 ms at 22 050 Hz), so there is no step in the waveform. An all-1.0 volume gives v = x bit for bit on every finite sample; a gain of
+ * 0 mutes. Known answer: hop 4, gf = [1, 0.5], x all 1.0 → v = [1, 1, 1, 0.875, 0.75, 0.625, 0.5, 0.5].
+ * Every later stage reads v in place of x, its own contract unchanged: the loudness measurement and piper_hip_voice_loudness measure v;
+ * the limiter's u = fl(v · drive); the peak of normalize = 1, and piper_hip_voice_peaks, is max |v|; the resampler, PCM and G.711 follow.
+ * The fp32 audio in the plan and the `audio` tap stay raw.
+ * Streams (single, group, pool, mixed pool). A step whose chunk covers frames [fs, fe) shapes samples [fs·hop, fe·hop) with the absolute
+ * sample index n; it reads gf of frames fs − 1 … fe, all known from the begin or the join on (a bounded join: from its resolution on, and
+ * nothing in the join waits). There is no delay, no carry and no change to any count: n_samples, samples_out, stream_step_capacity* and
+ * every emit rule downstream are what they are without a volume, and "window:audio" stays raw. The concatenation of a row's steps equals
+ * the whole-item result bit for bit, on every format. A pool row's new occupant brings its own gains, or none, and never reads its
+ * predecessor's. A stream whose rows carry no volume adds no launch. */
+typedef struct {
+  const float* gain;  /* [t] linear gains, NULL = all 1.0 */
+  int32_t t;          /* the item's number of ids */
+} piper_hip_volume;   /* 16 bytes */
+/* Host-only (no device needed). volume_check: PIPER_HIP_ERR_ARG with a message that names the field and the index.
+ * volume_frames: gf of an item with `t` ids from the frames per id actually used, F = max(Σ d, 1) (Σ d = 0 gives gain[0]). `volume` NULL
+ * is all 1.0; its t different from `t` is PIPER_HIP_ERR_SHAPE. *frames receives F; frame_gain may be NULL to ask for F alone, otherwise it
+ * holds max_frames entries (fewer than F is PIPER_HIP_ERR_SHAPE).
+ * volume_from_f32: the sequential twin of the kernels, v from gf and x. n must equal frames · hop, otherwise PIPER_HIP_ERR_SHAPE; hop in
+ * [1, 65536]. */
+int piper_hip_volume_check(const piper_hip_volume* volume);
+int piper_hip_volume_frames(const piper_hip_volume* volume, const int32_t* durations, int32_t t, float* frame_gain, int64_t max_frames,
+                            int64_t* frames);
+int piper_hip_volume_from_f32(const float* frame_gain, int64_t frames, int32_t hop, const float* x, size_t n, float* y);
+/* Per-op: `count` device floats and a device frame_gain[frames] → `count` device floats. `*out` convention of the other ops; count must
+ * equal frames · hop (PIPER_HIP_ERR_SHAPE otherwise), hop in [1, 65536], count may be 0. The pointers need no alignment beyond a float's. */
+int piper_hip_volume_f32(piper_hip_ctx* ctx, const float* x, size_t count, const float* frame_gain, int64_t frames, int32_t hop, float** out,
+                         piper_hip_stream stream);
+/* The volume of the NEXT staging call on slot id `slot`, with the lifecycle of piper_hip_voice_slot_prosody: entry i is for item i, items
+ * past `n` have none; the arrays are copied here; n = 0 clears the assignment; n outside 0 … 256 is PIPER_HIP_ERR_ARG; every entry is
+ * checked here on the host (a refusal leaves the assignment in place as it was). The staging calls prepare, prepare_batch,
+ * prepare_batch_bounded, stream_begin, stream_begin_batch, synthesize* (slot 0) and stream_pool_join* (where `slot` is the work slot) take
+ * the assignment and clear it, whether or not they succeed; an entry whose t differs from its item's t is PIPER_HIP_ERR_SHAPE there, and
+ * nothing is staged. Unlike the duration fields of prosody, a volume is allowed on
+ * items with supplied durations: it does not touch them. It combines freely with prosody (including fit), speakers, level, loudness,
+ * output rates and mixed formats. Every later collect, collect_pcm16, collect_pcm16_rate and collect_g711 of that staging delivers v, on plain, ragged and
+ * bounded slots; on bounded slots lengths and the frame-to-id map are read from device memory, and nothing new waits for the GPU.
+ * Debug tap "vol.gain" [1, F] per item (piper_hip_voice_tap): gf compacted to the item's true F, on a slot whose last staging carried a
+ * volume; otherwise PIPER_HIP_ERR_ARG; on a bounded slot that has not been collected PIPER_HIP_ERR_UNSUPPORTED, like the other taps. */
+int piper_hip_voice_slot_volume(piper_hip_voice* v, int slot, const piper_hip_volume* items, int n);
+
 /* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
  * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]
  * (the graph's `sid` input, read by PiperMetalRuntime.synthesize next to `scales`, PiperMetalRuntime.swift:62-80; in the graph a Gather

@@ -25,6 +25,7 @@
 #include "conv_win.h"
 #include "level.h"
 #include "loudness.h"
+#include "volume.h"
 #include "pcm16.h"
 #include "resample.h"
 #include "rng.h"
@@ -256,6 +257,7 @@ struct StreamRow {
   // have without the drop. A pool's rows are never ghosts: a dropped row is free for the next join at once.
   bool ghost = false;
   RowFormat fmt;  // read on a mixed slot only; set by stream_item_formats (group) or the join that took the row (pool)
+  const float* gf = nullptr;  // the gains per frame [F] of an item with a volume, in device memory (piper_hip.h "Per-phoneme volume"); null: none
   int64_t lim_lo = 0;  // read on a slot with a level only: where the row's previous step ended, in limited samples (a step at next == 0 starts it at 0)
 };
 
@@ -302,6 +304,11 @@ struct Stream {
   size_t pack_bytes = 0;             // of `pack`
   StreamRate rs;                     // output rate of the stream
   StreamLevel lv;                    // level of the stream
+  // Per-phoneme volume: the shaped chunks of one step in the layout of the window plan's audio, and the step's VolStepRow table; both
+  // allocated by the first step that has a row with a volume
+  float* vol = nullptr;
+  size_t vol_bytes = 0;
+  VolStepRow* vol_desc = nullptr;    // device [NBg]
   Slot* plan = nullptr;              // owner of the device buffers; nullptr = the context pool (a streaming pool)
   int items() const { return (int)rows.size(); }
 };
@@ -391,6 +398,12 @@ struct Slot {
   double* loud_seg = nullptr;    // [NB][ld_work_row(F·hop)] the passes' shares of Σ y² per 100 ms segment of the latest launch's raw items
   float* loud_rep = nullptr;     // [NB][2] {L, g} as the gate kernel last wrote them
   bool loud_measured = false;    // loud_seg holds the latest launch (cleared where h_peaks is)
+  // Per-phoneme volume (piper_hip_voice_slot_volume): device buffers of this plan (in `owned`), allocated on first use
+  bool vol_on = false;           // the plan's latest staging carried a volume: vol_gain holds its gains
+  float* vol_gain = nullptr;     // [NB][T] the gain per id, staged with the ids (1.0 where an item or an id has none)
+  float* shaped = nullptr;       // [NB][n_samples] the items under their envelopes, the layout of `audio`
+  bool vol_shaped = false;       // shaped holds the latest launch (cleared where h_peaks is)
+  float* vol_gf = nullptr;       // [NB][F] the gain per frame, written for the "vol.gain" tap
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
@@ -418,6 +431,8 @@ struct StreamPool {
   struct Row {             // what only a pool's row has, parallel to st.rows
     float* z = nullptr;    // [inter][stride] row store (context pool), kept while the pool lives, regrown for a longer utterance
     size_t cap = 0;        // floats
+    float* gf = nullptr;   // [gf_cap] the gains per frame of an occupant with a volume (context pool), written behind the join's adopt
+    size_t gf_cap = 0;     // floats
     int stride = 0;        // bucket_f(F) of the item in the row
     // stream_pool_join_bounded: the row is taken (active) but its F is still on the device until pool_resolve has read the adopt's report
     bool pending = false;
@@ -529,6 +544,10 @@ struct piper_hip_voice {
     size_t cap_spk = 0;
     int32_t* h_pro = nullptr;  // the per-id prosody arrays of a prepare in bucket rows: length, min, max, noise [n][T] each, then fit [n]
     size_t cap_pro = 0;
+    float* h_vol = nullptr;    // the per-id gains of a prepare in bucket rows [n][T] (a request with a volume)
+    size_t cap_vol = 0;
+    VolStepRow* h_vstep = nullptr;  // a stream step's VolStepRow table (one H2D per step that shapes)
+    size_t cap_vstep = 0;
   } staging[kMaxSlots];
   // The prosody of a slot id's NEXT staging call (piper_hip_voice_slot_prosody): owned copies of the caller's arrays, an empty array = the
   // field was NULL. The staging call takes the assignment (take_prosody) whether or not it succeeds.
@@ -538,6 +557,13 @@ struct piper_hip_voice {
     int t = 0, fit = 0;
   };
   std::vector<Prosody> slot_pro[kMaxSlots];
+  // The volume of a slot id's NEXT staging call (piper_hip_voice_slot_volume), with the same lifecycle: owned copies of the caller's gains,
+  // an empty array = the field was NULL.
+  struct Volume {
+    std::vector<float> gain;
+    int t = 0;
+  };
+  std::vector<Volume> slot_vol[kMaxSlots];
   // Speaker table of a multi-speaker voice (piper_hip_voice_attach_speakers; spk.S == 0: none): the device tables of speaker.hip, where an
   // item's speaker row keeps the dp.pre rows [0, spk_dp_rows), the flow's from there and the conv_pre rows from spk_pre_off, and each
   // slot id's assignment (empty: speaker 0 alone; items past the end take the last entry).
@@ -877,6 +903,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();  // (these too)
   s.lim = nullptr; s.lim_scratch = nullptr;
   s.gained = nullptr; s.loud_seg = nullptr; s.loud_rep = nullptr; s.loud_measured = false;
+  s.vol_on = false; s.vol_gain = nullptr; s.shaped = nullptr; s.vol_shaped = false; s.vol_gf = nullptr;
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
@@ -902,6 +929,10 @@ void pool_close(piper_hip_voice* v, int slot) {
   for (hipEvent_t e : P->ev_free) (void)hipEventDestroy(e);
   for (auto& r : P->ext)
     if (r.z) (void)v->ctx->pool.release(r.z);
+  for (auto& r : P->ext)
+    if (r.gf) (void)v->ctx->pool.release(r.gf);
+  if (P->st.vol) (void)v->ctx->pool.release(P->st.vol);
+  if (P->st.vol_desc) (void)v->ctx->pool.release(P->st.vol_desc);
   if (P->d_rows) (void)v->ctx->pool.release(P->d_rows);
   const StreamRate& rs = P->st.rs;
   const StreamLevel& lv = P->st.lv;
@@ -2412,6 +2443,22 @@ PH_EXPORT int piper_hip_voice_slot_prosody(piper_hip_voice* v, int slot, const p
   return PIPER_HIP_OK;
 }
 
+// ---- per-phoneme volume (piper_hip.h "Per-phoneme volume") ------------------------------------------------------------------------
+PH_EXPORT int piper_hip_voice_slot_volume(piper_hip_voice* v, int slot, const piper_hip_volume* items, int n) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (n < 0 || n > 256 || (n > 0 && !items)) PH_FAIL(PIPER_HIP_ERR_ARG, "voice_slot_volume: %d entries (0 … 256)", n);
+  for (int i = 0; i < n; i++)
+    if (int rc = volume_check_item(&items[i], i)) return rc;  // (the assignment in place stays on a refusal)
+  std::vector<piper_hip_voice::Volume> own((size_t)n);
+  for (int i = 0; i < n; i++) {  // the arrays are copied: the caller's memory may go away at once
+    own[i].t = items[i].t;
+    if (items[i].gain) own[i].gain.assign(items[i].gain, items[i].gain + items[i].t);
+  }
+  v->slot_vol[slot].swap(own);
+  return PIPER_HIP_OK;
+}
+
 PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16)
@@ -2518,6 +2565,8 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_loud) (void)hipHostFree(sg.h_loud);
     if (sg.h_spk) (void)hipHostFree(sg.h_spk);
     if (sg.h_pro) (void)hipHostFree(sg.h_pro);
+    if (sg.h_vol) (void)hipHostFree(sg.h_vol);
+    if (sg.h_vstep) (void)hipHostFree(sg.h_vstep);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
   for (auto& st : v->free_sets) destroy_set(st);
@@ -2765,6 +2814,31 @@ void pack_prosody(const ProsodyItems& pro, int n, int T, float* len, int32_t* mn
     if (fit) fit[b] = p ? p->fit : 0;
   }
 }
+// ---- per-phoneme volume (piper_hip.h "Per-phoneme volume") ----
+using VolumeItems = std::vector<piper_hip_voice::Volume>;
+// A staging call takes the slot id's assignment, whether or not it goes on to succeed.
+VolumeItems take_volume(piper_hip_voice* v, int slot) {
+  VolumeItems p;
+  if (v && slot >= 0 && slot < kMaxSlots) p.swap(v->slot_vol[slot]);
+  return p;
+}
+// The entry points that reach prepare* only behind refusals of their own clear the assignment on every way out.
+struct VolumeClear {
+  piper_hip_voice* v;
+  int slot;
+  ~VolumeClear() { (void)take_volume(v, slot); }
+};
+// What a staging call checks before it stages anything.
+int check_volume(const VolumeItems& vol, const piper_hip_utterance* utts, int n) {
+  for (int b = 0; b < n && b < (int)vol.size(); b++)
+    if (vol[b].t != utts[b].t)
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "utterance %d: its volume has %d entries, the utterance %d ids", b, vol[b].t, utts[b].t);
+  return PIPER_HIP_OK;
+}
+// The gains of a request with a volume → the plan's vol_gain [n][T], from the slot id's page-locked staging on the plan's stream (which
+// the caller has synchronised: the previous request's copy is done). A request without: the plan has none.
+int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, int n, int T, hipStream_t q);
+
 // predict_impl on the predictor plan of requests with prosody (pro non-null), its per-id inputs staged with the ids
 int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
                      const piper_hip_speaker* speakers, const ProsodyItems* pro);
@@ -2772,6 +2846,7 @@ int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n,
 
 PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot) {
   const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
+  const VolumeItems vol = take_volume(v, slot);    // (piper_hip_voice_slot_volume)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
@@ -2780,7 +2855,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   int64_t Fmax = 0;
   std::vector<int> hT(n), hF(n);
   const bool has_pro = !pro.empty();  // the request runs the plans of requests with prosody
-  if ((rc = check_prosody(pro, utts, n, false))) return rc;
+  if ((rc = check_prosody(pro, utts, n, false)) || (rc = check_volume(vol, utts, n))) return rc;
   std::vector<int64_t> wanted(n, -1);  // Σ d of the frame rule per item (there is no fitting on this route)
   // utterances without durations: run the text encoder + duration predictor first (its own cached plan), then continue with
   // the predicted frames per id exactly as if the caller had supplied them
@@ -2873,7 +2948,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     return rc;
   unsigned* p_rng = (unsigned*)sg.h_misc;
   float* p_ns = (float*)(p_rng + 2 * (size_t)n);
-  if ((rc = stage_speakers(v, slot, s, n, q))) return rc;
+  if ((rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q))) return rc;
   if (s.pro) {  // the noise multiplier per id, a plan input like the ids (no fitting on this route)
     if ((rc = grow_pinned(sg.h_pro, sg.cap_pro, (size_t)n * T + n))) return rc;
     pack_prosody(pro, n, T, nullptr, nullptr, nullptr, (float*)sg.h_pro, nullptr);
@@ -2916,6 +2991,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   s.timed = false;
   s.h_peaks.clear();
   s.loud_measured = false;
+  s.vol_shaped = false;
   return slot;
 }
 
@@ -3003,11 +3079,12 @@ int bounded_refusals(const piper_hip_voice* v, const piper_hip_utterance* utts, 
 PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int max_frames) {
   const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
   const bool has_pro = !pro.empty();
+  const VolumeItems vol = take_volume(v, slot);  // (piper_hip_voice_slot_volume)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   int Tmax = 0, rc;
   if ((rc = bounded_refusals(v, utts, n, slot, max_frames, false))) return rc;
   for (int b = 0; b < n; b++) Tmax = std::max(Tmax, utts[b].t);
-  if ((rc = check_prosody(pro, utts, n, true))) return rc;
+  if ((rc = check_prosody(pro, utts, n, true)) || (rc = check_volume(vol, utts, n))) return rc;
   const int T = bucket_t(Tmax), F = bucket_f(max_frames), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
@@ -3051,7 +3128,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
     sg.h_res[b] = -1;
   }
   const hipStream_t q = s.set.stream;
-  if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q))) return rc;
+  if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q))) return rc;
   if (has_pro) {  // the per-id arrays: plan inputs of the predictor plan (length, floor, ceiling) and of this one (noise, fit)
     const size_t nT = (size_t)n * T;
     float* h_len = (float*)sg.h_pro;
@@ -3096,6 +3173,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   s.timed = false;
   s.h_peaks.clear();
   s.loud_measured = false;
+  s.vol_shaped = false;
   return slot;
 }
 
@@ -3330,6 +3408,50 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__
 
 int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
 
+int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, int n, int T, hipStream_t q) {
+  s.vol_on = !vol.empty();
+  s.vol_shaped = false;
+  if (!s.vol_on) return PIPER_HIP_OK;
+  auto& sg = v->staging[slot];
+  int rc;
+  if ((rc = grow_pinned(sg.h_vol, sg.cap_vol, (size_t)n * T))) return rc;
+  if (!s.vol_gain) {
+    void* p = nullptr;
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.T * sizeof(float), &p))) return rc;
+    s.vol_gain = (float*)p;
+  }
+  for (int b = 0; b < n; b++) {
+    const piper_hip_voice::Volume* it = b < (int)vol.size() ? &vol[b] : nullptr;
+    for (int t = 0; t < T; t++) sg.h_vol[(size_t)b * T + t] = it && !it->gain.empty() && t < it->t ? it->gain[t] : 1.0f;
+  }
+  PH_HIP(hipMemcpyAsync(s.vol_gain, sg.h_vol, (size_t)n * T * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
+// What the output chain of a plan reads for its items: the plan's audio, or — its latest staging carried a volume — shaped [NB][n_samples],
+// v = x·e per item (include/piper_hip.h "Per-phoneme volume"), computed here once per launch behind the plan's graph on its stream, from
+// lengths and the frame-to-id map the device holds (plain, ragged and bounded slots alike). The plan's audio stays raw.
+int volume_audio(piper_hip_voice* v, Slot& s, const float** audio) {
+  *audio = s.audio;
+  if (!s.vol_on) return PIPER_HIP_OK;
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  if (F < 1 || !s.vol_gain || !s.frame2id || !s.lensF) PH_FAIL(PIPER_HIP_ERR_SHAPE, "volume: the slot holds no samples to shape");
+  if (!s.shaped) {
+    void* q = nullptr;
+    if (int rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q)) return rc;
+    s.shaped = (float*)q;
+    s.vol_shaped = false;
+  }
+  if (!s.vol_shaped) {
+    PH_HIP(launch_volume_items(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, s.frame2id, s.F, s.vol_gain, s.T, s.shaped,
+                               s.n_samples),
+           PIPER_HIP_ERR_LAUNCH);
+    s.vol_shaped = true;
+  }
+  *audio = s.shaped;
+  return PIPER_HIP_OK;
+}
+
 // {L, g} of the plan's raw items into s.loud_rep, behind the plan's graph on its stream, from lengths the device holds: the K-weighted
 // segment powers once per launch, the gates and the gain of target `t` every time (include/piper_hip.h "Loudness").
 int loudness_measure(piper_hip_voice* v, Slot& s, const LdTarget& t) {
@@ -3349,7 +3471,9 @@ int loudness_measure(piper_hip_voice* v, Slot& s, const LdTarget& t) {
     s.loud_rep = (float*)q;
   }
   if (!s.loud_measured) {
-    PH_HIP(launch_loudness_measure(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, 0, f, s.loud_seg), PIPER_HIP_ERR_LAUNCH);
+    const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items)
+    if ((rc = volume_audio(v, s, &x))) return rc;
+    PH_HIP(launch_loudness_measure(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, 0, f, s.loud_seg), PIPER_HIP_ERR_LAUNCH);
     s.loud_measured = true;
   }
   PH_HIP(launch_loudness_gate(s.set.stream, s.lensF, F, v->hop, s.NB, 0, f.h, s.loud_seg, t, s.loud_rep), PIPER_HIP_ERR_LAUNCH);
@@ -3357,14 +3481,16 @@ int loudness_measure(piper_hip_voice* v, Slot& s, const LdTarget& t) {
 }
 
 // The items a slot id with a loudness target (piper_hip_voice_slot_loudness) hands the rest of the output chain: gained [NB][n_samples],
-// u = x·g per item. Without a target: the plan's audio.
+// u = x·g per item. Without a target: the plan's audio (x: the shaped items where the plan's staging carried a volume).
 int loudness_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
-  *audio = s.audio;
+  const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items)
+  int rc = volume_audio(v, s, &x);
+  if (rc) return rc;
+  *audio = x;
   const auto& sl = v->slot_ld[slot];
   if (!sl.on) return PIPER_HIP_OK;
   LdTarget t;
-  int rc = ld_resolve(&sl.ld, &t);
-  if (rc) return rc;
+  if ((rc = ld_resolve(&sl.ld, &t))) return rc;
   const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
   if (F < 1) return PIPER_HIP_OK;
   if ((rc = loudness_measure(v, s, t))) return rc;
@@ -3373,7 +3499,7 @@ int loudness_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
     if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
     s.gained = (float*)q;
   }
-  PH_HIP(launch_loudness_gain(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, s.loud_rep, s.gained, s.n_samples), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(launch_loudness_gain(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, s.loud_rep, s.gained, s.n_samples), PIPER_HIP_ERR_LAUNCH);
   *audio = s.gained;
   return PIPER_HIP_OK;
 }
@@ -3422,6 +3548,7 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   s.timed = true;
   s.h_peaks.clear();  // the peaks a normalising collect_pcm16 reported belong to the previous run
   s.loud_measured = false;  // (and so does the loudness measured there)
+  s.vol_shaped = false;     // (and the items shaped from it)
   return PIPER_HIP_OK;
 }
 
@@ -3604,6 +3731,7 @@ PH_EXPORT int piper_hip_voice_receptive_field(const piper_hip_voice* v) { return
 namespace {
 // The prepared slot's encoder + flow as their own graph (everything before the generator's first launch), captured on first use, then
 // launched; z is ready when the plan's ev1 fires. Shared by the single and the batched stream. front_steps: the launches it consists of.
+int stream_volume_begin(piper_hip_voice* v, Slot& s, const float** gf);
 std::vector<int> front_steps(const Slot& s) {
   std::vector<int> front;
   for (int i = 0; i < (int)s.steps.size(); i++) {
@@ -3626,10 +3754,13 @@ int launch_front(Slot& s) {
 
 PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_utterance* u, int slot, int chunk_frames) {
   const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
+  const VolumeClear vc{v, slot};  // (and its volume)
   if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin: chunk_frames must be >= 1");
   int rc = piper_hip_voice_prepare(v, u, slot);
   if (rc < 0) return rc;
   Slot& s = *v->attached[slot];
+  const float* gf = nullptr;  // the item's gains per frame where the request carried a volume
+  if ((rc = stream_volume_begin(v, s, &gf))) return rc;
   if ((rc = launch_front(s))) return rc;
   Stream& st = s.stream;
   st.plan = &s;
@@ -3638,6 +3769,7 @@ PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_u
   st.NBg = 1;
   st.single = true;
   st.rows.assign(1, StreamRow{s.h_F[0], 0, s.h_F[0] > 0});
+  st.rows[0].gf = gf;
   return (int)ceil_div(s.h_F[0], chunk_frames);
 }
 
@@ -3854,6 +3986,62 @@ LvStepRow level_range(const StreamRow& row, const Window& w, int hop, int64_t* l
   return LvStepRow{w.skip, w.n, (int)(s - *lo), (int)(*hi - *lo)};
 }
 
+int stream_alloc(piper_hip_voice* v, Stream& st, size_t bytes, void** out);
+void stream_free(piper_hip_voice* v, Stream& st, void* p, size_t bytes);
+
+// ---- per-phoneme volume on streams (include/piper_hip.h "Per-phoneme volume")
+// A begin on a plan whose staging carried a volume: the gains per frame of its items, gf [NB][F], written on the plan's stream in front of
+// its encoder + flow (so whatever waits for those finds them). Returns the row of item 0, null for a request without a volume.
+int stream_volume_begin(piper_hip_voice* v, Slot& s, const float** gf) {
+  *gf = nullptr;
+  if (!s.vol_on) return PIPER_HIP_OK;
+  if (!s.vol_gf) {
+    void* q = nullptr;
+    if (int rc = plan_alloc(v, s, (size_t)s.NB * s.F * sizeof(float), &q)) return rc;
+    s.vol_gf = (float*)q;
+  }
+  PH_HIP(launch_volume_frame_gains(s.set.stream, s.lensF, s.F, s.NB, s.frame2id, s.F, s.vol_gain, s.T, s.vol_gf), PIPER_HIP_ERR_LAUNCH);
+  *gf = s.vol_gf;
+  return PIPER_HIP_OK;
+}
+
+// The row of a step's VolStepRow table for a row whose window is w: the window's own chunk, at its absolute place in the item.
+VolStepRow volume_range(const StreamRow& row, const Window& w, int hop) {
+  return VolStepRow{row.gf, (int64_t)row.next * hop, row.F, w.skip, w.n, 0};
+}
+
+// What a step with a shaped row needs: st.vol of `bytes` (the window plan's audio), the device table and its page-locked staging.
+int volume_step_buffers(piper_hip_voice* v, int slot, Stream& st, size_t bytes) {
+  int rc;
+  void* p = nullptr;
+  if (st.vol_bytes < bytes) {  // (no step is in flight: every step ends with a wait)
+    if ((rc = stream_alloc(v, st, bytes, &p))) return rc;
+    stream_free(v, st, st.vol, st.vol_bytes);
+    st.vol = (float*)p;
+    st.vol_bytes = bytes;
+  }
+  if (!st.vol_desc) {
+    if ((rc = stream_alloc(v, st, (size_t)256 * sizeof(VolStepRow), &p))) return rc;
+    st.vol_desc = (VolStepRow*)p;
+  }
+  auto& sg = v->staging[slot];
+  return grow_pinned(sg.h_vstep, sg.cap_vstep, (size_t)256);
+}
+
+// One launch behind the window plan's graph: the chunks of `rows` generator rows of audio [rows][row] under their envelopes → st.vol.
+hipError_t volume_step(piper_hip_voice* v, int slot, Stream& st, const VolStepRow* tab, int rows, const float* audio, int64_t row, hipStream_t q) {
+  auto& sg = v->staging[slot];
+  int64_t max_n = 0;
+  for (int r = 0; r < rows; r++) {
+    sg.h_vstep[r] = tab[r];
+    max_n = std::max<int64_t>(max_n, tab[r].n);
+  }
+  if (max_n < 1) return hipSuccess;
+  hipError_t e = hipMemcpyAsync(st.vol_desc, sg.h_vstep, (size_t)rows * sizeof(VolStepRow), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) e = launch_volume_step(q, rows, max_n, audio, row, st.vol_desc, v->hop, st.vol);
+  return e;
+}
+
 // stream_next. A PCM sink: the chunk leaves as int16 or one G.711 byte per sample — converted by a kernel behind the window's graph —
 // instead of fp32; the step is the same in every other respect
 int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_samples) {
@@ -3909,6 +4097,7 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   bool built = false;
   int rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fc), 1, &gs, &built);
   if (rc) return rc;
+  if (row.gf && (rc = volume_step_buffers(v, slot, s.stream, (size_t)gs->n_samples * sizeof(float)))) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
   v->windows[slot] = WindowRecord{gs, gs->last_use, {Fc}};
@@ -3922,12 +4111,18 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   if (e == hipSuccess && gs->spk_bias)  // the item's conv_pre row travels with its latent window
     e = hipMemcpyAsync(gs->spk_bias, s.spk_bias + v->spk_pre_off, (size_t)v->cfg.up_initial * sizeof(float), hipMemcpyDeviceToDevice, gs->set.stream);
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
-  const float* chunk_audio = gs->audio;  // what the output stage reads, its chunk behind dn_skip
+  const float* win_audio = gs->audio;  // the window's audio, or — the item has a volume — its chunk under the envelope, at the same place
+  if (row.gf) {
+    const VolStepRow vr = volume_range(row, w, v->hop);
+    if (e == hipSuccess) e = volume_step(v, slot, s.stream, &vr, 1, gs->audio, 0, gs->set.stream);
+    win_audio = s.stream.vol;
+  }
+  const float* chunk_audio = win_audio;  // what the output stage reads, its chunk behind dn_skip
   if (lvl.on) {  // (with or without a buffer: the row's carry moves on with the stream)
     LvStepRow* h = (LvStepRow*)(v->staging[slot].h_desc + kLvStageOff);
     if (e == hipSuccess) { *h = lrow; e = hipMemcpyAsync(lvl.desc, h, sizeof(LvStepRow), hipMemcpyHostToDevice, gs->set.stream); }
     if (e == hipSuccess)
-      e = launch_level_step(gs->set.stream, 1, s.stream.chunk * v->hop, gs->audio, 0, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
+      e = launch_level_step(gs->set.stream, 1, s.stream.chunk * v->hop, win_audio, 0, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
     chunk_audio = lvl.lim;
   }
   if (pcm && want_out) {
@@ -4238,6 +4433,11 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
   int Fmax = 0;
   bool live = false;  // a row delivers in this step
   std::vector<int> ghost_end(n, -1);
+  // a stream with a volume on some row: the step's VolStepRow table. A stream without one never builds it.
+  bool any_vol = false;
+  for (int r = 0; r < n; r++) any_vol = any_vol || (rows[r].active && rows[r].gf != nullptr);
+  std::vector<VolStepRow> vrow;
+  if (any_vol) vrow.assign((size_t)NBg, VolStepRow{nullptr, 0, 0, 0, 0, 0});
   for (int r = 0; r < NBg; r++) {
     int* e = d + (size_t)r * kDescInts;
     for (int k = 0; k < kDescInts; k++) e[k] = 0;
@@ -4254,6 +4454,7 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     if (r >= n || !rows[r].active) continue;
     live = true;
     const Window w = win[r] = window_of(rows[r].F, rows[r].next, st.chunk, st.halo, hop);
+    if (any_vol) vrow[r] = volume_range(rows[r], w, hop);
     e[kDescA] = w.a;
     e[kDescFc] = w.Fc;
     // what the output stage takes for its chunk: the window's, or — a slot with a level — the limited range [lo, hi) in the row of lvl.lim
@@ -4313,6 +4514,7 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
   Slot* gs = nullptr;
   bool built = false;
   if ((rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
+  if (any_vol && (rc = volume_step_buffers(v, slot, st, (size_t)NBg * gs->n_samples * sizeof(float)))) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
   {
@@ -4335,11 +4537,16 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     e = hipGetLastError();
   }
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
-  const float* chunk_audio = gs->audio;  // what the output stage reads: rows of chunk_row floats, each row's chunk behind its skip
+  const float* win_audio = gs->audio;  // the windows' audio, or — a delivering row has a volume — every row's chunk as it leaves the volume stage
+  if (any_vol) {
+    if (e == hipSuccess) e = volume_step(v, slot, st, vrow.data(), NBg, gs->audio, gs->n_samples, q);
+    win_audio = st.vol;
+  }
+  const float* chunk_audio = win_audio;  // what the output stage reads: rows of chunk_row floats, each row's chunk behind its skip
   int64_t chunk_row = gs->n_samples;
   if (lvl.on) {
     if (e == hipSuccess) e = hipMemcpyAsync(lvl.desc, lrow, (size_t)NBg * sizeof(LvStepRow), hipMemcpyHostToDevice, q);
-    if (e == hipSuccess) e = launch_level_step(q, NBg, st.chunk * hop, gs->audio, gs->n_samples, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
+    if (e == hipSuccess) e = launch_level_step(q, NBg, st.chunk * hop, win_audio, gs->n_samples, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
     chunk_audio = lvl.lim;
     chunk_row = lvl.row;
   }
@@ -4440,6 +4647,7 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, const Sink& out, int6
 
 PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames) {
   const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
+  const VolumeClear vc{v, slot};  // (and its volume)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: group of %d outside [1,%d]", n, kMaxGroup);
   if (int rc = check_step_size(v, "stream_begin_batch", n, chunk_frames)) return rc;
@@ -4454,12 +4662,17 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
     st.d_desc = (int*)p;
   }
   if ((rc = pack_buffer(v, st, (size_t)n * chunk_frames * v->hop * sizeof(float)))) return rc;
+  const float* gf = nullptr;  // the items' gains per frame [n][F] where the request carried a volume
+  if ((rc = stream_volume_begin(v, s, &gf))) return rc;
   if ((rc = launch_front(s))) return rc;
   st.chunk = chunk_frames;
   st.halo = generator_halo_frames(v->cfg);
   st.NBg = group_batch(n);
   st.rows.resize(n);
-  for (int b = 0; b < n; b++) st.rows[b] = StreamRow{s.h_F[b], 0, s.h_F[b] > 0};
+  for (int b = 0; b < n; b++) {
+    st.rows[b] = StreamRow{s.h_F[b], 0, s.h_F[b] > 0};
+    st.rows[b].gf = gf ? gf + (size_t)b * s.F : nullptr;
+  }
   int steps = 0;
   for (int b = 0; b < n; b++) steps = std::max(steps, (int)ceil_div(s.h_F[b], chunk_frames));
   return steps;
@@ -4553,6 +4766,7 @@ int launch_front_async(Slot& s) {
 int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot, const piper_hip_stream_format* fmts,
               bool with_formats, int* items_out, int64_t* samples_out, int bound = 0) {
   const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
+  const VolumeClear vc{v, work_slot};  // (and its volume)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
   if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
@@ -4623,6 +4837,14 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
     const int stride = item_stride(i);
     stride_max = std::max(stride_max, stride);
     const size_t need = (size_t)I * stride;
+    if (w.vol_on && r.gf_cap < (size_t)stride) {  // the occupant's gains per frame, next to its latent (the wait: as for the latent below)
+      for (hipEvent_t ev : P->ev_pending) PH_HIP(hipEventSynchronize(ev), PIPER_HIP_ERR_LAUNCH);
+      void* p = nullptr;
+      if ((rc = v->ctx->pool.alloc((size_t)stride * sizeof(float), &p))) return rc;
+      if (r.gf) (void)v->ctx->pool.release(r.gf);
+      r.gf = (float*)p;
+      r.gf_cap = (size_t)stride;
+    }
     if (r.cap >= need) continue;
     // a longer utterance takes the row: a larger store. No step is in flight (every step ends with a host wait); an adopt of a join
     // since the last step may still be writing the old store (joined, dropped, row taken again) — wait for those.
@@ -4666,6 +4888,11 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
                          spk_src, (int64_t)v->spk.Ctot, w.spk_bias ? P->spk_rows : nullptr, v->cfg.up_initial);
     e = hipGetLastError();
   }
+  // a join with a volume: every item's gains per frame into its row's own store, behind the adopt on the same stream — from the work plan's
+  // frame-to-id map and the lengths the device holds (a bounded join: what generate_path decided), so nothing here waits
+  for (int i = 0; i < n && w.vol_on && e == hipSuccess; i++)
+    e = launch_volume_frame_gains(q, w.lensF + i, std::min(w.F, item_stride(i)), 1, w.frame2id + (size_t)i * w.F, w.F, w.vol_gain + (size_t)i * w.T, w.T,
+                                  P->ext[take[i]].gf);
   if (e == hipSuccess) e = hipEventRecord(ev, q);
   if (e != hipSuccess) { P->ev_free.push_back(ev); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "stream_pool_join: %s", hipGetErrorString(e)); }
   P->ev_pending.push_back(ev);
@@ -4677,6 +4904,7 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
     r.F = bound ? 0 : w.h_F[i];  // (bounded: pool_resolve brings it before any step reads it)
     r.next = 0;
     r.active = true;
+    r.gf = w.vol_on ? x.gf : nullptr;  // a new occupant brings its own gains, or none: never its predecessor's
     x.pending = bound != 0;
     x.held = !bound;
     x.over_want = x.over_cap = 0;
@@ -4704,6 +4932,7 @@ PH_EXPORT int piper_hip_voice_stream_pool_join_formats(piper_hip_voice* v, int s
 PH_EXPORT int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
                                                        int max_frames, const piper_hip_stream_format* fmts, int* items_out) {
   const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
+  const VolumeClear vc{v, work_slot};  // (and its volume)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   // prepare_batch_bounded's own refusals, before anything of the pool is looked at or regrown (it repeats them)
   if (int rc = bounded_refusals(v, utts, n, work_slot, max_frames, true)) return rc;
@@ -4825,7 +5054,9 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   const hipStream_t q = s.set.stream;
   const float* audio = s.audio;  // (a slot id with a level: the limited items)
   if ((rc = level_audio(v, slot, s, &audio))) return rc;
-  if (normalize) PH_HIP(launch_pcm16_peak(q, s.audio, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
+  const float* peak_src = s.audio;  // (the peak of normalize = 1 is that of the shaped items where the staging carried a volume)
+  if (normalize && (rc = volume_audio(v, s, &peak_src))) return rc;
+  if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
   if (rd)
     PH_HIP(launch_resample_items(q, audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
            PIPER_HIP_ERR_LAUNCH);
@@ -4872,6 +5103,7 @@ int g711_law(const char* who, int law);
 int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int out_rate, const char* who, int enc,
                    void* host, int64_t max_samples, int64_t* n_samples) {
   const ProsodyClear pc{v, 0};  // a staging call on slot 0
+  const VolumeClear vc{v, 0};
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   float gain;
   bool normalize;
@@ -5329,6 +5561,31 @@ PH_EXPORT int piper_hip_voice_tap(piper_hip_voice* v, int slot, const char* name
       if (max_floats < all.size()) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
       for (size_t i = 0; i < all.size(); i++) host[i] = (float)(unsigned char)all[i];
     }
+    return PIPER_HIP_OK;
+  }
+  if (!win && tp == sp && at == std::string::npos && tensor_name == "vol.gain") {
+    // gf of the items, each compacted to its true F: written by a kernel of its own from the plan's frame-to-id map and the staged gains
+    if (!s.vol_on) PH_FAIL(PIPER_HIP_ERR_ARG, "tap '%s': the last staging of slot %d carried no volume (piper_hip_voice_slot_volume)", name, slot);
+    if (s.bounded_pending) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "tap '%s': the slot's frame counts are still on the device (collect first)", name);
+    size_t total = 0;
+    for (int b = 0; b < s.NB; b++) total += (size_t)s.h_F[b];
+    if (n_floats) *n_floats = total;
+    if (!host) return PIPER_HIP_OK;
+    if (max_floats < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "tap buffer too small");
+    PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+    if (!s.vol_gf) {
+      void* q = nullptr;
+      if (int rc = plan_alloc(v, s, (size_t)s.NB * s.F * sizeof(float), &q)) return rc;
+      s.vol_gf = (float*)q;
+    }
+    PH_HIP(launch_volume_frame_gains(s.set.stream, s.lensF, s.F, s.NB, s.frame2id, s.F, s.vol_gain, s.T, s.vol_gf), PIPER_HIP_ERR_LAUNCH);
+    size_t off = 0;
+    for (int b = 0; b < s.NB; b++) {
+      PH_HIP(hipMemcpyAsync(host + off, s.vol_gf + (size_t)b * s.F, (size_t)s.h_F[b] * sizeof(float), hipMemcpyDeviceToHost, s.set.stream),
+             PIPER_HIP_ERR_LAUNCH);
+      off += (size_t)s.h_F[b];
+    }
+    PH_HIP(hipStreamSynchronize(s.set.stream), PIPER_HIP_ERR_LAUNCH);
     return PIPER_HIP_OK;
   }
   auto it = s.taps.find(tensor_name);

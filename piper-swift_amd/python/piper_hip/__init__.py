@@ -181,6 +181,55 @@ def prosody_frames(p, w0, cap=0):
     return out, int(wanted.value)
 
 
+class Volume(C.Structure):
+    """piper_hip_volume (16 bytes): one linear gain per phoneme id in [0, 16] (NULL = all 1.0) and the number of ids."""
+    _fields_ = [("gain", c_f32p), ("t", C.c_int32)]
+
+
+def _volume(g, t=None):
+    """None → the all-1.0 record of t ids; an array of gains (t = its length); a Volume is passed through. Returns (record, the array
+    that must outlive the call)."""
+    if isinstance(g, Volume):
+        return g, None
+    if g is None:
+        return Volume(None, int(t or 0)), None
+    arr = np.ascontiguousarray(g, np.float32).reshape(-1)
+    return Volume(arr.ctypes.data_as(c_f32p), arr.size), arr
+
+
+def volume_check(g, t=None):
+    """piper_hip_volume_check: raises InvalidArgument naming the field and the index of the first violation. Host-only. g None (all 1.0)
+    needs t, the number of ids."""
+    if g is None and t is None:
+        raise InvalidArgument("volume_check: a volume without gains needs t, the number of ids")
+    rec, _keep = _volume(g, t)
+    _check(load_library().piper_hip_volume_check(C.byref(rec)))
+
+
+def volume_frames(g, durations):
+    """piper_hip_volume_frames: the gain of every frame, gf [F], F = max(Σ d, 1), of an item whose ids last `durations` frames (host only).
+    g: the gains per id, a Volume, or None (all 1.0)."""
+    d = np.ascontiguousarray(durations, np.int32).reshape(-1)
+    rec, _keep = (None, None) if g is None else _volume(g)
+    lib, frames = load_library(), C.c_int64()
+    ref = None if rec is None else C.byref(rec)
+    _check(lib.piper_hip_volume_frames(ref, d.ctypes.data_as(c_i32p), d.size, None, 0, C.byref(frames)))
+    out = np.empty(frames.value, np.float32)
+    _check(lib.piper_hip_volume_frames(ref, d.ctypes.data_as(c_i32p), d.size, out.ctypes.data_as(c_f32p), out.size, C.byref(frames)))
+    return out
+
+
+def volume_from_f32(samples, frame_gain, hop):
+    """The envelope on the host (piper_hip_volume_from_f32), bit for bit what the device computes: samples [frames·hop] under the gains
+    per frame."""
+    x = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    gf = np.ascontiguousarray(frame_gain, np.float32).reshape(-1)
+    y = np.empty_like(x)
+    _check(load_library().piper_hip_volume_from_f32(gf.ctypes.data_as(c_f32p), gf.size, int(hop), x.ctypes.data_as(c_f32p), x.size,
+                                                    y.ctypes.data_as(c_f32p)))
+    return y
+
+
 class PcmParams(C.Structure):
     """piper_hip_pcm_params: linear gain (0 = 1.0) and the peak-normalisation flag of the 16-bit PCM entry points."""
     _fields_ = [("gain", C.c_float), ("normalize", C.c_int32)]
@@ -484,6 +533,11 @@ _PROTOS = {
     "piper_hip_prosody_frames": (C.c_int, [C.POINTER(Prosody), c_f32p, C.c_int32, C.c_int64, c_i32p, C.POINTER(C.c_int64)]),
     "piper_hip_voice_slot_prosody": (C.c_int, [c_vp, C.c_int, C.POINTER(Prosody), C.c_int]),
     "piper_hip_voice_prosody_report": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_int64), c_i32p, C.c_int]),
+    "piper_hip_volume_check": (C.c_int, [C.POINTER(Volume)]),
+    "piper_hip_volume_frames": (C.c_int, [C.POINTER(Volume), c_i32p, C.c_int32, c_f32p, C.c_int64, C.POINTER(C.c_int64)]),
+    "piper_hip_volume_from_f32": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_size_t, c_f32p]),
+    "piper_hip_volume_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, c_vp, C.c_int64, C.c_int32, C.POINTER(c_vp), c_vp]),
+    "piper_hip_voice_slot_volume": (C.c_int, [c_vp, C.c_int, C.POINTER(Volume), C.c_int]),
 }
 
 _lib = None
@@ -837,6 +891,16 @@ class HipBackend:
         p = c_vp(_ptr(out)) if out is not None else c_vp()
         lv = _level(level)
         _check(self.lib.piper_hip_level_f32(self.ctx, _ptr(buf), n, int(rate), C.byref(lv), C.byref(p), commandBuffer))
+        return DeviceBuffer(self, p.value, n, owned=out is None)
+
+    def volume(self, buf, frame_gain, hop, count=None, out=None, commandBuffer=None):
+        """`count` = frames·hop device floats under the envelope of the device gains per frame `frame_gain` [frames] (piper_hip_volume_f32;
+        include/piper_hip.h "Per-phoneme volume"). buf and out may be raw device addresses (4-byte alignment suffices). Returns a
+        DeviceBuffer of `count` float32."""
+        frames = frame_gain.count
+        n = frames * int(hop) if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        _check(self.lib.piper_hip_volume_f32(self.ctx, _ptr(buf), n, _ptr(frame_gain), frames, int(hop), C.byref(p), commandBuffer))
         return DeviceBuffer(self, p.value, n, owned=out is None)
 
     def loudness_f32(self, buf, rate, count=None, commandBuffer=None):
@@ -1364,11 +1428,13 @@ class StreamPool:
         self.rate = int(rate)
         self._resize()
 
-    def join(self, utterances, noiseScale=0.667, formats=None, prosody=None):
+    def join(self, utterances, noiseScale=0.667, formats=None, prosody=None, volume=None):
         """utterances as for synthesize_stream_batch: (phonemeIDs, durations-or-None, noise-or-None[, dict]). Returns [(item, samples)]:
         the row each session took and the samples it will deliver in all. Active from the next step().
         formats (a mixed pool): one StreamFormat (or dict of stream_format's arguments, or None) per utterance
-        (piper_hip_voice_stream_pool_join_formats); without it the sessions join in the default format."""
+        (piper_hip_voice_stream_pool_join_formats); without it the sessions join in the default format.
+        prosody, volume: one entry per utterance, as for slot_prosody / slot_volume (staged on the work slot); a session with a volume
+        delivers every chunk under its envelope, a session without brings none into its row."""
         rt, n = self.rt, len(utterances)
         arr = (Utterance * max(n, 1))()
         keep = []
@@ -1386,6 +1452,7 @@ class StreamPool:
             fa = _formats(formats)
         # one entry per utterance, as for slot_prosody; staged behind every refusal made here, so that the join below is what takes it
         rt._stage_prosody(self.work_slot, prosody, [len(u[0]) for u in utterances])
+        rt._stage_volume(self.work_slot, volume, [len(u[0]) for u in utterances])
         if fa is not None:
             _check(rt.lib.piper_hip_voice_stream_pool_join_formats(rt.voice, self.slot, arr, n, self.work_slot, fa, items, samples))
         else:
@@ -1399,11 +1466,13 @@ class StreamPool:
                 self._buf = np.empty((need + 3) // 4, np.float32)
         return [(int(items[i]), int(samples[i])) for i in range(n)]
 
-    def join_bounded(self, utterances, max_frames, noiseScale=0.667, formats=None, prosody=None):
+    def join_bounded(self, utterances, max_frames, noiseScale=0.667, formats=None, prosody=None, volume=None):
         """join() for utterances whose durations are predicted, without the host round trip (piper_hip_voice_stream_pool_join_bounded):
         at most max_frames frames per item, durations and noise None (the dict's noise_mode="device" draws the noise on the device).
         Nothing waits for the GPU. Returns [item, ...], the rows taken; item_samples(item) tells what each will deliver once its length
-        is known and raises ShapeMismatch for an item the predictor made longer than max_frames (that row is free again)."""
+        is known and raises ShapeMismatch for an item the predictor made longer than max_frames (that row is free again).
+        prosody (fit=1 compresses to max_frames), volume: one entry per utterance, as for join(); the gains follow the frames the device
+        decides."""
         rt, n = self.rt, len(utterances)
         arr = (Utterance * max(n, 1))()
         keep = []
@@ -1419,6 +1488,7 @@ class StreamPool:
                 raise InvalidArgument("join_bounded: %d formats for %d utterances" % (len(formats), n))
             fa = _formats(formats)
         rt._stage_prosody(self.work_slot, prosody, [len(u[0]) for u in utterances])  # one entry per utterance; fit=1 compresses to max_frames
+        rt._stage_volume(self.work_slot, volume, [len(u[0]) for u in utterances])
         _check(rt.lib.piper_hip_voice_stream_pool_join_bounded(rt.voice, self.slot, arr, n, self.work_slot, int(max_frames), fa, items))
         rt._keep.pop(self.work_slot, None)  # the inputs were copied before the call returned
         if self.mixed:
@@ -1557,6 +1627,24 @@ class HipRuntime:
         if prosody is not None:
             self.slot_prosody(slot, prosody, ts)
 
+    def slot_volume(self, slot, items, ts=None):
+        """The volume of the NEXT staging call on the slot id (piper_hip_voice_slot_volume): entry i for item i, each an array of linear
+        gains per id in [0, 16], a Volume, or None (all 1.0: needs ts[i], the item's number of ids). The library copies the arrays; the
+        staging call takes the assignment whether or not it succeeds. None or [] clears it."""
+        items = list(items or [])
+        recs, keep = [], []
+        for i, g in enumerate(items):
+            r, k = _volume(g, None if ts is None else ts[i])
+            recs.append(r)
+            keep.append(k)
+        arr = (Volume * len(recs))(*recs) if recs else None
+        _check(self.lib.piper_hip_voice_slot_volume(self.voice, int(slot), arr, len(recs)))
+
+    def _stage_volume(self, slot, volume, ts):
+        """The `volume=` keyword of the staging methods: one entry per utterance (None entries all 1.0), or None for a request without."""
+        if volume is not None:
+            self.slot_volume(slot, volume, ts)
+
     def prosody_report(self, slot):
         """Per item of the slot: (frames the rule wanted before fitting, fitted?) — piper_hip_voice_prosody_report; answers where
         durations() answers."""
@@ -1588,7 +1676,7 @@ class HipRuntime:
         u, _k = self._utt(ids, durations, None, 0.0)
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
-    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None,
+    def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None, volume=None,
                    level=KEEP, loudness=KEEP, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
         reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
@@ -1602,23 +1690,27 @@ class HipRuntime:
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
+            self._stage_volume(0, None if volume is None else [volume], [len(phonemeIDs)])
             n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
             out = np.empty(max(n, 1), np.float32)
             got = C.c_int64()
             _check(self.lib.piper_hip_voice_synthesize(self.voice, C.byref(u), out.ctypes.data_as(c_f32p), n, C.byref(got)))
             self._keep.pop(0, None)
             return out[:got.value]
-        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, **kw)
+        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, volume=volume, **kw)
         self.launch(0)
         return self.collect(0)
 
     def prepare(self, slot, phonemeIDs, durations=None, noise=None, noiseScale=0.667, noise_mode="injected", seed=1234, length_scale=1.0,
-                noise_w=0.8, dp_noise=None, max_frames=None, prosody=None):
+                noise_w=0.8, dp_noise=None, max_frames=None, prosody=None, volume=None):
         """max_frames (durations must be None): predicted durations WITHOUT the host round trip — the plan is the bucket of that bound and the
         frame count stays on the device until collect (piper_hip_voice_prepare_batch_bounded).
-        prosody: the item's per-id prosody (slot_prosody), a dict(length=, min_frames=, max_frames=, noise=, fit=) or a Prosody."""
+        prosody: the item's per-id prosody (slot_prosody), a dict(length=, min_frames=, max_frames=, noise=, fit=) or a Prosody.
+        volume: the item's linear gains per id in [0, 16] (slot_volume): every collect of this staging delivers the samples under that
+        envelope (include/piper_hip.h "Per-phoneme volume")."""
         u, k = self._utt(phonemeIDs, durations, noise, noiseScale, noise_mode, seed, length_scale, noise_w, dp_noise)
         self._stage_prosody(slot, None if prosody is None else [prosody], [len(phonemeIDs)])
+        self._stage_volume(slot, None if volume is None else [volume], [len(phonemeIDs)])
         if max_frames is not None:
             rc = self.lib.piper_hip_voice_prepare_batch_bounded(self.voice, C.byref(u), 1, slot, int(max_frames))
         else:
@@ -1631,7 +1723,7 @@ class HipRuntime:
         return rc
 
     def prepare_batch_bounded(self, slot, utterances, max_frames, noiseScale=0.667, noise_mode="device", seed=1234, length_scale=1.0, noise_w=0.8,
-                              prosody=None):
+                              prosody=None, volume=None):
         """utterances: list of (phonemeIDs, dp_noise-or-None); durations predicted on the device, at most max_frames frames per item.
         prosody: one entry per utterance (None entries neutral), as for slot_prosody; an entry's fit=1 compresses an item over the bound."""
         n = len(utterances)
@@ -1642,6 +1734,7 @@ class HipRuntime:
             arr[i] = u
             keep.append(k)
         self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
+        self._stage_volume(slot, volume, [len(u[0]) for u in utterances])
         rc = self.lib.piper_hip_voice_prepare_batch_bounded(self.voice, arr, n, slot, int(max_frames))
         if rc < 0:
             _check(rc)
@@ -1762,14 +1855,16 @@ class HipRuntime:
         return _count(self.lib.piper_hip_voice_stream_step_capacity_bytes(self.voice, slot))
 
     def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None,
-                          encoding=None, prosody=None, level=None):
+                          encoding=None, prosody=None, volume=None, level=None):
         """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
-        prosody: the utterance's per-id prosody, as for prepare.
+        prosody: the utterance's per-id prosody, as for prepare. volume: the utterance's linear gains per id, as for prepare: every chunk
+        leaves under the envelope, and the concatenated chunks equal the whole-item result bit for bit.
         pcm=True: int16 chunks converted on the device (piper_hip_voice_stream_next_pcm16), scaled by `gain`. rate: int16 chunks at that
         output rate (stream_set_rate; implies pcm). encoding "mulaw" / "alaw": uint8 chunks of G.711 bytes instead of int16
         (piper_hip_voice_stream_next_g711), at `rate` or the voice's own."""
         u, keep = self._utt(phonemeIDs, durations, noise, noiseScale)
         self._stage_prosody(slot, None if prosody is None else [prosody], [len(phonemeIDs)])
+        self._stage_volume(slot, None if volume is None else [volume], [len(phonemeIDs)])
         n_chunks = self.lib.piper_hip_voice_stream_begin(self.voice, C.byref(u), slot, int(chunkFrames))
         if n_chunks < 0:
             _check(n_chunks)
@@ -1798,7 +1893,7 @@ class HipRuntime:
             yield buf[:got.value].copy()
 
     def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None, encoding=None,
-                                formats=None, prosody=None, level=None):
+                                formats=None, prosody=None, volume=None, level=None):
         """prosody: one entry per utterance (None entries neutral), as for slot_prosody.
         Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
@@ -1816,6 +1911,7 @@ class HipRuntime:
             arr[i] = u
             keep.append(k)
         self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
+        self._stage_volume(slot, volume, [len(u[0]) for u in utterances])
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
@@ -1882,9 +1978,10 @@ class HipRuntime:
             pool.set_level(level)
         return pool
 
-    def prepare_batch(self, slot, utterances, noiseScale=0.667, prosody=None):
+    def prepare_batch(self, slot, utterances, noiseScale=0.667, prosody=None, volume=None):
         """utterances: list of (phonemeIDs, durations, noise-or-None[, dict of noise_mode / seed / length_scale / noise_w / dp_noise]); lengths
-        may differ (ragged batch, one bucket). prosody: one entry per utterance (None entries neutral), as for slot_prosody."""
+        may differ (ragged batch, one bucket). prosody: one entry per utterance (None entries neutral), as for slot_prosody.
+        volume: one array of gains per utterance (None entries all 1.0, utterances past the list have none), as for slot_volume."""
         n = len(utterances)
         arr = (Utterance * n)()
         keep = []
@@ -1895,6 +1992,7 @@ class HipRuntime:
             arr[i] = u
             keep.append(k)
         self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
+        self._stage_volume(slot, volume, [len(u[0]) for u in utterances])
         rc = self.lib.piper_hip_voice_prepare_batch(self.voice, arr, n, slot)
         if rc < 0:
             _check(rc)
@@ -1983,12 +2081,13 @@ class HipRuntime:
         return out[:sum(resample_count(src, rate, p) for p in per)]
 
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, rate=None, prosody=None, level=KEEP, loudness=KEEP, **kw):
+                         normalize=False, rate=None, prosody=None, volume=None, level=KEEP, loudness=KEEP, **kw):
         """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare;
         level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
         self._slot_loudness(0, loudness)
         pro = None if prosody is None else [prosody]
+        vol = None if volume is None else [volume]
         if rate is not None and int(rate) == self.cfg.sample_rate:
             rate = None
         if durations is not None and not kw and rate is not None:  # piper_hip_voice_synthesize_pcm16_rate
@@ -1998,6 +2097,7 @@ class HipRuntime:
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
             self._stage_prosody(0, pro, [len(phonemeIDs)])
+            self._stage_volume(0, vol, [len(phonemeIDs)])
             _check(self.lib.piper_hip_voice_synthesize_pcm16_rate(self.voice, C.byref(u), C.byref(prm), int(rate), out.ctypes.data_as(c_i16p), n,
                                                                   C.byref(got)))
             self._keep.pop(0, None)
@@ -2009,10 +2109,11 @@ class HipRuntime:
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
             self._stage_prosody(0, pro, [len(phonemeIDs)])
+            self._stage_volume(0, vol, [len(phonemeIDs)])
             _check(self.lib.piper_hip_voice_synthesize_pcm16(self.voice, C.byref(u), C.byref(prm), out.ctypes.data_as(c_i16p), n, C.byref(got)))
             self._keep.pop(0, None)
             return out[:got.value]
-        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, **kw)
+        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, volume=volume, **kw)
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
 
@@ -2038,7 +2139,7 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], total, False)
         return out[:sum(count(p) for p in per)]
 
-    def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None,
+    def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None, volume=None,
                         level=KEEP, loudness=KEEP):
         """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's;
         prosody: as for prepare (with supplied durations: noise alone); level, loudness: as for collect (slot 0)."""
@@ -2054,6 +2155,7 @@ class HipRuntime:
         got = C.c_int64()
         prm = PcmParams(float(gain), int(bool(normalize)))
         self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
+        self._stage_volume(0, None if volume is None else [volume], [len(phonemeIDs)])
         _check(self.lib.piper_hip_voice_synthesize_g711(self.voice, C.byref(u), C.byref(prm), _law(law), rate, out.ctypes.data_as(c_u8p), n,
                                                         C.byref(got)))
         self._keep.pop(0, None)

@@ -224,6 +224,49 @@ public final class HIPBackend {
         return b
     }
 
+    // ---- per-phoneme volume (include/piper_hip.h "Per-phoneme volume") ----
+
+    /// `frames`·`hop` device floats under the envelope of the device gains per frame (piper_hip_volume_f32).
+    public func volumeF32(input: HIPBuffer, frameGain: HIPBuffer, frames: Int64, hop: Int32, commandBuffer: Stream? = nil) throws -> HIPBuffer {
+        var out: UnsafeMutablePointer<Float>? = nil
+        try Self.check(piper_hip_volume_f32(ctx, input.f32, Int(frames) * Int(hop), frameGain.f32, frames, hop, &out, commandBuffer))
+        return HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx)
+    }
+
+    /// The envelope on the host (piper_hip_volume_from_f32), bit for bit what the device computes: x [frames·hop] under the gains per frame.
+    public static func volumeFromF32(_ x: [Float], frameGain: [Float], hop: Int32) throws -> [Float] {
+        var y = [Float](repeating: 0, count: x.count)
+        try check(piper_hip_volume_from_f32(frameGain, Int64(frameGain.count), hop, x, x.count, &y))
+        return y
+    }
+
+    /// The gain of every frame of an item whose ids last `durations` frames (piper_hip_volume_frames; host-only). gains nil: all 1.0.
+    public static func volumeFrames(gains: [Float]?, durations: [Int32]) throws -> [Float] {
+        var frames: Int64 = 0
+        func run(_ out: UnsafeMutablePointer<Float>?, _ cap: Int64) throws {
+            if let g = gains {
+                try g.withUnsafeBufferPointer { gp in
+                    var rec = piper_hip_volume(gain: gp.baseAddress, t: Int32(g.count))
+                    try check(piper_hip_volume_frames(&rec, durations, Int32(durations.count), out, cap, &frames))
+                }
+            } else {
+                try check(piper_hip_volume_frames(nil, durations, Int32(durations.count), out, cap, &frames))
+            }
+        }
+        try run(nil, 0)
+        var gf = [Float](repeating: 0, count: Int(frames))
+        try gf.withUnsafeMutableBufferPointer { try run($0.baseAddress, frames) }
+        return gf
+    }
+
+    /// InvalidArgument naming the field and the index for gains outside [0, 16] (piper_hip_volume_check; host-only).
+    public static func volumeCheck(gains: [Float]) throws {
+        try gains.withUnsafeBufferPointer { gp in
+            var rec = piper_hip_volume(gain: gp.baseAddress, t: Int32(gains.count))
+            try check(piper_hip_volume_check(&rec))
+        }
+    }
+
     // ---- level control (include/piper_hip.h "Level control") ----
 
     /// `count` device floats sampled at `rate` → `count` limited device floats (piper_hip_level_f32): the look-ahead limiter.

@@ -161,6 +161,21 @@ public final class PiperHIPRuntime {
         }
     }
 
+    /// The volume of the NEXT staging call on the slot id (piper_hip_voice_slot_volume): entry i holds item i's linear gains per id in
+    /// [0, 16] (nil: all 1.0, `counts[i]` ids), for prepare*, stream_begin*, synthesize* (slot 0) or a pool join (its work slot). The staging
+    /// call takes the assignment whether or not it succeeds; an empty list clears it.
+    public func slotVolume(slot: Int32, items: [[Float]?], counts: [Int32]) throws {
+        var keep: [UnsafeMutablePointer<Float>] = []
+        defer { keep.forEach { $0.deallocate() } }
+        var recs: [piper_hip_volume] = []
+        for (i, g) in items.enumerated() {
+            guard let g = g else { recs.append(piper_hip_volume(gain: nil, t: counts[i])); continue }
+            let p = UnsafeMutablePointer<Float>.allocate(capacity: max(g.count, 1)); p.initialize(from: g, count: g.count); keep.append(p)
+            recs.append(piper_hip_volume(gain: UnsafePointer(p), t: Int32(g.count)))
+        }
+        try HIPBackend.check(piper_hip_voice_slot_volume(voice, slot, &recs, Int32(recs.count)))
+    }
+
     /// Per item of the slot: the frames the rule wanted before fitting, and whether the bounded route compressed the item to its bound
     /// (piper_hip_voice_prosody_report); answers where the durations are known.
     public func prosodyReport(slot: Int32) throws -> [(wanted: Int64, fitted: Bool)] {
