@@ -26,6 +26,9 @@
  *                            --id-volume I:J=G[,I:J=G…]: a volume per phoneme id, ids I … J − 1 at the linear gain G (0 … 16) and the
  *                            others at 1.0, ramped between ids on the device in front of the loudness gain, the limiter and every
  *                            output above (piper_hip_voice_slot_volume on slot 0).
+ *                            --eq TYPE:F0:Q[:GAIN_DB], up to four times: a biquad section of the equaliser on the device (TYPE lowpass,
+ *                            highpass, bandpass, notch, peaking, lowshelf or highshelf; GAIN_DB for peaking and the shelves), in front
+ *                            of the loudness gain, the limiter and every output above (piper_hip_voice_slot_eq on slot 0).
  *   --speaker N              both modes: speaker N of a multi-speaker voice (the graph's `sid`; piper_hip_voice_attach_speakers +
  *                            piper_hip_voice_slot_speakers). With --model the file's speaker table is loaded (opt-in: without the flag such a
  *                            file is refused; its node graph is NOT verified — no verifier for the conditioned graph exists yet); without
@@ -200,6 +203,22 @@ static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_p
   return 0;
 }
 
+/* --eq TYPE:F0:Q[:GAIN_DB] → one section; nonzero on a malformed argument (the library checks the values) */
+static int parse_eq_section(const char* s, piper_hip_eq_section* out) {
+  static const char* const names[7] = {"lowpass", "highpass", "bandpass", "notch", "peaking", "lowshelf", "highshelf"};
+  char name[16];
+  float f0 = 0.0f, q = 0.0f, g = 0.0f;
+  const int k = sscanf(s, "%15[^:]:%f:%f:%f", name, &f0, &q, &g);
+  if (k < 3) return 1;
+  for (int i = 0; i < 7; i++)
+    if (strcmp(name, names[i]) == 0) {
+      out->type = PIPER_HIP_EQ_LOWPASS + i;
+      out->f0_hz = f0; out->q = q; out->gain_db = k == 4 ? g : 0.0f;
+      return 0;
+    }
+  return 1;
+}
+
 int main(int argc, char** argv) {
   const char* model = arg_value(argc, argv, "--model");
   const char* config = arg_value(argc, argv, "--config");
@@ -220,7 +239,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s --scale-bench [--warmup N] [--iters N] [--scale-factors 1,2,4,8,16] [--max-phonemes N]\n"
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
                     "                [--output-encoding s16le|mulaw|alaw] [--drive X] [--ceiling Y] [--release-ms Z]\n"
-                    "                [--loudness LUFS [--max-gain-db X]] [--id-volume I:J=G[,I:J=G...]]\n"
+                    "                [--loudness LUFS [--max-gain-db X]] [--id-volume I:J=G[,I:J=G...]] [--eq TYPE:F0:Q[:GAIN_DB] ...]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n"
                     "               [--speaker N [--speakers S]]\n", argv[0], argv[0]);
     return 2;
@@ -336,6 +355,21 @@ int main(int argc, char** argv) {
       ld.max_gain_db = arg_value(argc, argv, "--max-gain-db") ? (float)atof(arg_value(argc, argv, "--max-gain-db")) : 0.0f;
       if (ld.target_lufs == 0.0f) { fprintf(stderr, "--loudness %s: expected a target in LUFS, -70 ... -1\n", loud_arg); return 2; }
       CHECK(piper_hip_voice_slot_loudness(r.voice, 0, &ld));
+    }
+    { /* --eq, up to four times: slot 0's equaliser, sections in the order given */
+      piper_hip_eq eq;
+      memset(&eq, 0, sizeof eq);
+      for (int i = 1; i < argc; i++) {
+        if (strcmp(argv[i], "--eq") != 0) continue;
+        if (i + 1 == argc) { fprintf(stderr, "--eq: expected TYPE:F0:Q[:GAIN_DB] after the flag\n"); return 2; }
+        if (eq.n == PIPER_HIP_EQ_MAX_SECTIONS) { fprintf(stderr, "--eq: at most %d sections\n", PIPER_HIP_EQ_MAX_SECTIONS); return 2; }
+        if (parse_eq_section(argv[i + 1], &eq.section[eq.n]) != 0) {
+          fprintf(stderr, "--eq %s: expected TYPE:F0:Q[:GAIN_DB], TYPE lowpass|highpass|bandpass|notch|peaking|lowshelf|highshelf\n", argv[i + 1]);
+          return 2;
+        }
+        eq.n++;
+      }
+      if (eq.n) CHECK(piper_hip_voice_slot_eq(r.voice, 0, &eq));
     }
     const char* idvol_arg = arg_value(argc, argv, "--id-volume");
     if (idvol_arg) { /* slot 0's volume for the utterance: ids I … J − 1 at gain G, ramped between ids on the device */

@@ -738,8 +738,8 @@ int piper_hip_voice_stream_item_format(piper_hip_voice* v, int slot, int item, p
 
 /* ---- Level control: a look-ahead limiter on every output route (DESIGN.md §4 "Level control") ----
  * normalize = 1 needs an utterance's peak, which no stream step before the last knows. What a streaming pipeline uses instead is a
- * look-ahead limiter: a drive, a ceiling and a short, known delay. It is one more stage of the output chain — generator → level →
- * resampler → PCM / G.711 / mixed — on whole items and on every stream route, and it changes nothing for a request that does not ask
+ * look-ahead limiter: a drive, a ceiling and a short, known delay. It is one more stage of the output chain — generator → volume → EQ →
+ * loudness gain → level → resampler → PCM / G.711 / mixed — on whole items and on every stream route, and it changes nothing for a request that does not ask
  * for it. The limiter is a contract, bit for bit. All arithmetic is fp32, each operation rounded on its own (no FMA); fl() marks a rounding:
  *   constants  B = 32 samples per block, W = 6 blocks of look-ahead      (PIPER_HIP_LEVEL_BLOCK, PIPER_HIP_LEVEL_LOOKAHEAD)
  *   params     drive (0 is taken as 1.0), ceiling (0 → 1.0), release_ms (0 → 50)
@@ -801,8 +801,8 @@ int piper_hip_voice_stream_level(piper_hip_voice* v, int slot, piper_hip_level* 
 
 /* ---- Loudness: ITU-R BS.1770 / EBU R128 integrated loudness, measured and normalised on the device (DESIGN.md §4 "Loudness") ----
  * normalize = 1 is peak normalisation and says nothing about how loud an item sounds; a host that wants every prompt at one programme
- * loudness (−16 or −23 LUFS) measures by BS.1770. It is one more stage of the output chain on whole items — generator → loudness gain →
- * level → resampler → PCM / G.711 — and it changes nothing for a request that does not ask for it. Each later stage is exactly as its
+ * loudness (−16 or −23 LUFS) measures by BS.1770. It is one more stage of the output chain on whole items — generator → volume → EQ →
+ * loudness gain → level → resampler → PCM / G.711 — and it changes nothing for a request that does not ask for it. Each later stage is exactly as its
  * contract stands, reading u in place of x. The measurement is mono integrated loudness at the rate of the samples measured: the voice's
  * own rate on every voice route.
  *   rates      8000, 16000, 22050, 24000, 32000, 44100, 48000. Any other rate is PIPER_HIP_ERR_UNSUPPORTED (11025: 100 ms is not a whole
@@ -858,7 +858,7 @@ int piper_hip_voice_loudness(piper_hip_voice* v, int slot, float* lufs, float* g
  * word or a phoneme: SSML <prosody volume>, <emphasis>, a ducked parenthesis, a muted id. A host cannot shape it afterwards: on the
  * bounded route the frames per id are decided on the device, and on the PCM, rate and G.711 routes it receives integers at another rate,
  * behind the limiter and the loudness gain. So the volume is one more stage of the output chain, on whole items and on every stream route
- * — generator → volume → loudness gain → level → resampler → PCM / G.711 / mixed — and it changes nothing for a request that does not ask
+ * — generator → volume → EQ → loudness gain → level → resampler → PCM / G.711 / mixed — and it changes nothing for a request that does not ask
  * for it. The envelope is a
  * contract, bit for bit. All arithmetic is fp32, each operation rounded on its own (no FMA); fl() marks a rounding:
  *   gain[t]    one linear gain per phoneme id, finite, in [0, 16]; otherwise PIPER_HIP_ERR_ARG. A NULL array, or an item without a volume,
@@ -915,6 +915,89 @@ int piper_hip_volume_f32(piper_hip_ctx* ctx, const float* x, size_t count, const
  * Debug tap "vol.gain" [1, F] per item (piper_hip_voice_tap): gf compacted to the item's true F, on a slot whose last staging carried a
  * volume; otherwise PIPER_HIP_ERR_ARG; on a bounded slot that has not been collected PIPER_HIP_ERR_UNSUPPORTED, like the other taps. */
 int piper_hip_voice_slot_volume(piper_hip_voice* v, int slot, const piper_hip_volume* items, int n);
+
+/* ---- Equaliser: a biquad cascade on the device (DESIGN.md §4 "Equaliser") ----
+ * A high-pass for rumble, a presence lift for small loudspeakers, a telephone band ahead of 8 kHz G.711: a spectral stage that a host
+ * cannot add afterwards without giving up the device's output formats, and that must sit in front of the loudness measurement and the
+ * limiter. It is one more stage of the output chain on whole items — generator → volume → EQ → loudness gain → level → resampler →
+ * PCM / G.711 / mixed — and it changes nothing for a request that does not ask for it. Every later stage reads the EQ's output in place of
+ * its input, its own contract unchanged: the loudness measurement and piper_hip_voice_loudness measure it, the limiter reads it, the peak
+ * of normalize = 1 and piper_hip_voice_peaks are taken over it. The fp32 audio in the plan and the `audio` tap stay raw.
+ * The EQ is a contract, bit for bit. All of it is in double, every operation rounded on its own (no FMA), the fp32 fields widened:
+ *   params     n sections in 1 … 4, each {type, f0_hz, q, gain_db}; type 1 lowpass, 2 highpass, 3 bandpass (0 dB peak), 4 notch, 5 peaking,
+ *              6 lowshelf, 7 highshelf. f0_hz finite in [10, 0.45·rate], q finite in [0.1, 30], gain_db finite in [−30, 30] for peaking
+ *              and the shelves and exactly 0 for the other types; rate in [8000, 48000]: the rate of the samples being filtered, the
+ *              voice's own rate on every voice route. Anything else is PIPER_HIP_ERR_ARG with a message that names the field and the index.
+ *   design     w0 = 2.0·M_PI·f0 / fs,  c = cos(w0),  s = sin(w0),  α = s / (2.0·Q),  A = pow(10.0, gain_db / 40.0),  r = 2.0·sqrt(A)·α
+ *              (evaluated left to right as written, the RBJ Audio-EQ-Cookbook):
+ *              lowpass    b = [(1.0 − c)/2.0, 1.0 − c, (1.0 − c)/2.0]                a = [1.0 + α, −2.0·c, 1.0 − α]
+ *              highpass   b = [(1.0 + c)/2.0, −(1.0 + c), (1.0 + c)/2.0]             a = [1.0 + α, −2.0·c, 1.0 − α]
+ *              bandpass   b = [α, 0.0, −α]                                           a = [1.0 + α, −2.0·c, 1.0 − α]
+ *              notch      b = [1.0, −2.0·c, 1.0]                                     a = [1.0 + α, −2.0·c, 1.0 − α]
+ *              peaking    b = [1.0 + α·A, −2.0·c, 1.0 − α·A]                         a = [1.0 + α/A, −2.0·c, 1.0 − α/A]
+ *              lowshelf   b = [A·((A + 1.0) − (A − 1.0)·c + r), 2.0·A·((A − 1.0) − (A + 1.0)·c), A·((A + 1.0) − (A − 1.0)·c − r)]
+ *                         a = [(A + 1.0) + (A − 1.0)·c + r, −2.0·((A − 1.0) + (A + 1.0)·c), (A + 1.0) + (A − 1.0)·c − r]
+ *              highshelf  b = [A·((A + 1.0) + (A − 1.0)·c + r), −2.0·A·((A − 1.0) + (A + 1.0)·c), A·((A + 1.0) + (A − 1.0)·c − r)]
+ *                         a = [(A + 1.0) − (A − 1.0)·c + r, 2.0·((A − 1.0) − (A + 1.0)·c), (A + 1.0) − (A − 1.0)·c − r]
+ *              then b_i = b_i / a0 and a_i = a_i / a0: coefficients {b0, b1, b2, a1, a2}. A peaking section at 0 dB has b = a, b0 = 1 exactly.
+ *   recurrence sections in order, each in transposed direct form II: y = b0·v + s1;  s1 = (b1·v − a1·y) + s2;  s2 = b2·v − a2·y;  v = y.
+ *              v starts as x[n] widened (a non-finite x reads as 0); the output is y[n] = (float)v. The state is D = 2·n doubles, section i
+ *              at (s1, s2) = (2i, 2i + 1).
+ *   blocks     B = 64 samples; block k covers [64k, 64k + 64) ∩ [0, N). A [D][D] is the zero-input transition of one sample (column j: unit
+ *              state j stepped once with v = 0). P_0 = A^64 by six squarings, P_{l+1} = P_l·P_l. In every matrix product and matrix-vector
+ *              product the sum runs over ascending j, starting from the j = 0 product, each product and each sum rounded; P·S + T adds T
+ *              after the sum.
+ *              E[k] = the state after running block k from zero state over its true length. T_0[k] = E[k], T_{l+1}[m] = P_l·T_l[2m] +
+ *              T_l[2m+1]. Start state of block k: S = 0, then for each set bit l of k, highest first, S ← P_l·S + T_l[(k >> l) − 1].
+ *              Block k is run from S and its samples are output.
+ * The block form differs from the plain sequential recurrence only by rounding (about 1e-12 of max|y| for a moderate set). A 0 dB
+ * peaking EQ gives y = x bit for bit on every finite sample but −0, which becomes +0.
+ * Streams (single, group, pool, mixed pool) need hop % 64 == 0 (every preset: hop 256), otherwise stream_set_eq is
+ * PIPER_HIP_ERR_UNSUPPORTED. A row keeps as its carry one aggregate per set bit of its block count k (T_l[(k >> l) − 1]); a step folds the
+ * carry into the start state of each of its blocks and pushes each block's E, merging equal levels as a binary counter does, so the
+ * concatenated steps of a row equal the whole-item result bit for bit, on every format. The EQ adds no delay and changes no sample count,
+ * capacity or emit rule; it runs behind the volume and in front of the level. A pool row taken by a new occupant starts at block 0 with
+ * an empty carry and never reads its predecessor's. A stream without an EQ has no buffer and no launch. */
+#define PIPER_HIP_EQ_MAX_SECTIONS 4
+#define PIPER_HIP_EQ_BLOCK        64
+#define PIPER_HIP_EQ_LOWPASS      1
+#define PIPER_HIP_EQ_HIGHPASS     2
+#define PIPER_HIP_EQ_BANDPASS     3
+#define PIPER_HIP_EQ_NOTCH        4
+#define PIPER_HIP_EQ_PEAKING      5
+#define PIPER_HIP_EQ_LOWSHELF     6
+#define PIPER_HIP_EQ_HIGHSHELF    7
+typedef struct {
+  int32_t type;     /* PIPER_HIP_EQ_LOWPASS … PIPER_HIP_EQ_HIGHSHELF */
+  float f0_hz;
+  float q;
+  float gain_db;    /* peaking and shelves; exactly 0 otherwise */
+} piper_hip_eq_section;
+typedef struct {
+  int32_t n;        /* sections in use, 1 … PIPER_HIP_EQ_MAX_SECTIONS */
+  piper_hip_eq_section section[PIPER_HIP_EQ_MAX_SECTIONS];
+} piper_hip_eq;
+/* Host-only (no device needed). eq_check: the rules above at `rate`. eq_design: coeffs[i] = {b0, b1, b2, a1, a2} of section i, eq->n rows.
+ * eq_from_f32: the host twin of the kernels, the same block tree: n host floats → n host floats (n may be 0). */
+int piper_hip_eq_check(const piper_hip_eq* eq, int32_t rate);
+int piper_hip_eq_design(const piper_hip_eq* eq, int32_t rate, double coeffs[][5]);
+int piper_hip_eq_from_f32(const piper_hip_eq* eq, int32_t rate, const float* x, size_t n, float* y);
+/* Per-op: `count` device floats sampled at `rate` → `count` device floats. `*out` convention of the other ops; count may be 0; the
+ * pointers need no alignment beyond a float's. */
+int piper_hip_eq_f32(piper_hip_ctx* ctx, const float* x, size_t count, int32_t rate, const piper_hip_eq* eq, float** out,
+                     piper_hip_stream stream);
+/* Whole items: the EQ of slot id `slot`, state of the slot id like slot_level: it persists until replaced, NULL clears it. Every later
+ * collect, collect_pcm16, collect_pcm16_rate, collect_g711 and the synthesize twins (slot 0) on that slot deliver the chain above, on
+ * plain, ragged and bounded slots; on bounded slots the lengths are read from device memory and nothing new waits for the GPU. Collects
+ * with different EQs may follow one launch in any order: the EQ'd items, and the loudness measured over them, are recomputed when the
+ * slot's EQ changes. The EQ is checked here at the voice's rate (PIPER_HIP_ERR_ARG). */
+int piper_hip_voice_slot_eq(piper_hip_voice* v, int slot, const piper_hip_eq* eq);
+/* Streams: the EQ of the stream on `slot`, for every row of it. Allowed exactly where stream_set_level is: after stream_begin,
+ * stream_begin_batch or stream_pool_open, before the slot's first step, and for a pool also before its first join; later it is
+ * PIPER_HIP_ERR_ARG. It combines with stream_set_rate, stream_set_mixed and stream_set_level in either order, and a new begin / open clears
+ * it. The design is built and uploaded here. stream_eq reports what the slot holds (PIPER_HIP_ERR_ARG if none). */
+int piper_hip_voice_stream_set_eq(piper_hip_voice* v, int slot, const piper_hip_eq* eq);
+int piper_hip_voice_stream_eq(piper_hip_voice* v, int slot, piper_hip_eq* out);
 
 /* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
  * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]

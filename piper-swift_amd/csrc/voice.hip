@@ -23,6 +23,7 @@
 #include "conv.h"
 #include "conv_bf16.h"
 #include "conv_win.h"
+#include "eq.h"
 #include "level.h"
 #include "loudness.h"
 #include "volume.h"
@@ -275,6 +276,22 @@ struct StreamLevel {
   LvStepRow* desc = nullptr;  // device [rows]
 };
 
+// The equaliser of a stream — single, group or pool (piper_hip_voice_stream_set_eq; include/piper_hip.h "Equaliser"): the design in device
+// memory, per generator row a carry (the aggregates of the set bits of the row's block count), the step's EqStepRow table and scratch,
+// and the EQ'd chunks of one step in the layout of the window plan's audio, which the later stages read in place of it.
+struct StreamEq {
+  bool on = false;
+  piper_hip_eq eq{};
+  int rows = 0;               // generator rows carry, scratch and desc hold
+  int blocks = 0;             // scratch blocks per row
+  EqDesign* dev = nullptr;    // device
+  double* carry = nullptr;    // device [rows][kEqCarry]
+  double* scratch = nullptr;  // device [rows][blocks][2·kEqMaxD]
+  EqStepRow* desc = nullptr;  // device [rows]
+  float* out = nullptr;       // device, out_bytes: the EQ'd chunks of one step
+  size_t out_bytes = 0;
+};
+
 // The output rate of a stream — single, group or pool (piper_hip_voice_stream_set_rate): 0 is the voice's own rate. A resampling stream
 // keeps, per generator row, the last kRsHist samples of the previous chunk in device memory, in two buffers that change roles every step
 // (one launch reads the old history and writes the new one), and uploads a descriptor of its own per step.
@@ -304,6 +321,7 @@ struct Stream {
   size_t pack_bytes = 0;             // of `pack`
   StreamRate rs;                     // output rate of the stream
   StreamLevel lv;                    // level of the stream
+  StreamEq eq;                       // equaliser of the stream
   // Per-phoneme volume: the shaped chunks of one step in the layout of the window plan's audio, and the step's VolStepRow table; both
   // allocated by the first step that has a row with a volume
   float* vol = nullptr;
@@ -404,6 +422,15 @@ struct Slot {
   float* shaped = nullptr;       // [NB][n_samples] the items under their envelopes, the layout of `audio`
   bool vol_shaped = false;       // shaped holds the latest launch (cleared where h_peaks is)
   float* vol_gf = nullptr;       // [NB][F] the gain per frame, written for the "vol.gain" tap
+  // Equaliser (piper_hip_voice_slot_eq): device buffers of this plan (in `owned`), allocated on first use
+  float* eqd = nullptr;          // [NB][n_samples] the EQ'd items, the layout of `audio`
+  double* eq_work = nullptr;     // [NB][eq_work_row(F·hop, kEqMaxD)] the block tree
+  EqDesign* eq_dev = nullptr;    // the design eqd was filtered with
+  bool eq_done = false;          // eqd holds the latest launch under eq_held (cleared where h_peaks is)
+  bool eq_on = false;            // the EQ the chain last read the items through: eq_held, or none (the loudness measured behind it too)
+  piper_hip_eq eq_held{};
+  bool eq_dev_ok = false;        // eq_dev holds the design of eq_dev_eq at eq_dev_rate
+  piper_hip_eq eq_dev_eq{};
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
@@ -413,6 +440,7 @@ void reset_stream_state(Slot& s) {
   StreamRate& rs = s.stream.rs;
   rs.rate = 0; rs.started = false; rs.parity = 0; rs.mixed = false;  // (a new stream starts at the voice's own rate; the buffers stay with the plan)
   s.stream.lv.on = false;                                            // (and without a level)
+  s.stream.eq.on = false;                                            // (and without an EQ)
 }
 
 // Streaming pool (piper_hip_voice_stream_pool_*): `capacity` generator rows on one slot id that sessions enter (join) and leave (last chunk
@@ -548,6 +576,11 @@ struct piper_hip_voice {
     size_t cap_vol = 0;
     VolStepRow* h_vstep = nullptr;  // a stream step's VolStepRow table (one H2D per step that shapes)
     size_t cap_vstep = 0;
+    EqDesign* h_eq = nullptr;  // the design of the slot id's EQ on its way to a plan (one H2D when the EQ or the plan changes)
+    size_t cap_eq = 0;
+    hipEvent_t eq_ev = nullptr;  // recorded behind the latest copy from h_eq
+    EqStepRow* h_estep = nullptr;  // a stream step's EqStepRow table (one H2D per step of a stream with an EQ)
+    size_t cap_estep = 0;
   } staging[kMaxSlots];
   // The prosody of a slot id's NEXT staging call (piper_hip_voice_slot_prosody): owned copies of the caller's arrays, an empty array = the
   // field was NULL. The staging call takes the assignment (take_prosody) whether or not it succeeds.
@@ -574,6 +607,8 @@ struct piper_hip_voice {
   struct SlotLevel { bool on = false; piper_hip_level lv{}; } slot_lv[kMaxSlots];
   // The loudness target of each slot id's whole-item collects (piper_hip_voice_slot_loudness), as given; on = false: none.
   struct SlotLoudness { bool on = false; piper_hip_loudness ld{}; } slot_ld[kMaxSlots];
+  // The equaliser of each slot id's whole-item collects (piper_hip_voice_slot_eq), as given and checked; on = false: none.
+  struct SlotEq { bool on = false; piper_hip_eq eq{}; } slot_eq[kMaxSlots];
   bool planned = false;  // a plan has been asked for: the voice's schedules are fixed (no attach_speakers any more)
   Slot* attached[kMaxSlots] = {};
   std::unique_ptr<StreamPool> pools[kMaxSlots];  // the streaming pool a slot id holds (then attached[slot] is null)
@@ -904,6 +939,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.lim = nullptr; s.lim_scratch = nullptr;
   s.gained = nullptr; s.loud_seg = nullptr; s.loud_rep = nullptr; s.loud_measured = false;
   s.vol_on = false; s.vol_gain = nullptr; s.shaped = nullptr; s.vol_shaped = false; s.vol_gf = nullptr;
+  s.eqd = nullptr; s.eq_work = nullptr; s.eq_dev = nullptr; s.eq_done = false; s.eq_on = false; s.eq_dev_ok = false;
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
@@ -936,6 +972,9 @@ void pool_close(piper_hip_voice* v, int slot) {
   if (P->d_rows) (void)v->ctx->pool.release(P->d_rows);
   const StreamRate& rs = P->st.rs;
   const StreamLevel& lv = P->st.lv;
+  const StreamEq& sq = P->st.eq;
+  for (void* p : {(void*)sq.dev, (void*)sq.carry, (void*)sq.scratch, (void*)sq.desc, (void*)sq.out})
+    if (p) (void)v->ctx->pool.release(p);
   for (void* p : {(void*)P->st.d_desc, P->st.pack, (void*)rs.hist, (void*)rs.desc, (void*)rs.mdesc, (void*)lv.carry, (void*)lv.lim, (void*)lv.desc})
     if (p) (void)v->ctx->pool.release(p);
   if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
@@ -2563,6 +2602,9 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_desc) (void)hipHostFree(sg.h_desc);
     if (sg.h_peaks) (void)hipHostFree(sg.h_peaks);
     if (sg.h_loud) (void)hipHostFree(sg.h_loud);
+    if (sg.eq_ev) { (void)hipEventSynchronize(sg.eq_ev); (void)hipEventDestroy(sg.eq_ev); }
+    if (sg.h_eq) (void)hipHostFree(sg.h_eq);
+    if (sg.h_estep) (void)hipHostFree(sg.h_estep);
     if (sg.h_spk) (void)hipHostFree(sg.h_spk);
     if (sg.h_pro) (void)hipHostFree(sg.h_pro);
     if (sg.h_vol) (void)hipHostFree(sg.h_vol);
@@ -2992,6 +3034,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   s.h_peaks.clear();
   s.loud_measured = false;
   s.vol_shaped = false;
+  s.eq_done = false;
   return slot;
 }
 
@@ -3174,6 +3217,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   s.h_peaks.clear();
   s.loud_measured = false;
   s.vol_shaped = false;
+  s.eq_done = false;
   return slot;
 }
 
@@ -3452,12 +3496,70 @@ int volume_audio(piper_hip_voice* v, Slot& s, const float** audio) {
   return PIPER_HIP_OK;
 }
 
-// {L, g} of the plan's raw items into s.loud_rep, behind the plan's graph on its stream, from lengths the device holds: the K-weighted
+// What the stages behind the EQ read for a slot id's items: volume_audio's, or — the slot id has an EQ (piper_hip_voice_slot_eq) — eqd
+// [NB][n_samples], computed here behind the plan's graph on its stream from lengths the device holds (plain, ragged and bounded slots
+// alike), once per launch and EQ. Whenever the EQ the chain reads through changes, the loudness measured behind it is dropped.
+int eq_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
+  const float* x = s.audio;
+  int rc = volume_audio(v, s, &x);
+  if (rc) return rc;
+  *audio = x;
+  const auto& se = v->slot_eq[slot];
+  if (s.eq_on != se.on || (se.on && memcmp(&s.eq_held, &se.eq, sizeof(piper_hip_eq)) != 0)) {
+    s.eq_on = se.on;
+    s.eq_held = se.eq;
+    s.eq_done = false;
+    s.loud_measured = false;
+  }
+  if (!se.on) return PIPER_HIP_OK;
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "eq: the slot holds no samples to filter");
+  void* q = nullptr;
+  if (!s.eqd) {
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
+    s.eqd = (float*)q;
+    s.eq_done = false;
+  }
+  if (!s.eq_work) {
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * eq_work_row((int64_t)F * v->hop, kEqMaxD) * sizeof(double), &q))) return rc;
+    s.eq_work = (double*)q;
+  }
+  if (!s.eq_dev) {
+    if ((rc = plan_alloc(v, s, sizeof(EqDesign), &q))) return rc;
+    s.eq_dev = (EqDesign*)q;
+    s.eq_dev_ok = false;
+  }
+  if (!s.eq_done) {
+    if (!s.eq_dev_ok || memcmp(&s.eq_dev_eq, &se.eq, sizeof(piper_hip_eq)) != 0) {
+      // (the staging buffer is rewritten only once the copy queued from it last time has run, even where that call failed before its wait)
+      auto& sg = v->staging[slot];
+      if (sg.eq_ev) PH_HIP(hipEventSynchronize(sg.eq_ev), PIPER_HIP_ERR_LAUNCH);
+      else PH_HIP(hipEventCreateWithFlags(&sg.eq_ev, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+      if ((rc = grow_pinned(sg.h_eq, sg.cap_eq, 1, 1))) return rc;
+      if ((rc = eq_build(&se.eq, v->cfg.sample_rate, sg.h_eq))) return rc;
+      PH_HIP(hipMemcpyAsync(s.eq_dev, sg.h_eq, sizeof(EqDesign), hipMemcpyHostToDevice, s.set.stream), PIPER_HIP_ERR_LAUNCH);
+      PH_HIP(hipEventRecord(sg.eq_ev, s.set.stream), PIPER_HIP_ERR_LAUNCH);
+      s.eq_dev_ok = true;
+      s.eq_dev_eq = se.eq;
+    }
+    PH_HIP(launch_eq_items(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, 0, s.eq_dev, se.eq.n,
+                           s.eq_work, s.eqd, s.n_samples),
+           PIPER_HIP_ERR_LAUNCH);
+    s.eq_done = true;
+  }
+  *audio = s.eqd;
+  return PIPER_HIP_OK;
+}
+
+// {L, g} of the items the loudness stage reads — the plan's audio, shaped by the staging's volume and filtered by the slot id's EQ where
+// there are such — into s.loud_rep, behind the plan's graph on its stream, from lengths the device holds: the K-weighted
 // segment powers once per launch, the gates and the gain of target `t` every time (include/piper_hip.h "Loudness").
-int loudness_measure(piper_hip_voice* v, Slot& s, const LdTarget& t) {
+int loudness_measure(piper_hip_voice* v, int slot, Slot& s, const LdTarget& t) {
   LdFilter f;
   int rc = ld_filter(v->cfg.sample_rate, &f);
   if (rc) return rc;
+  const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items; a slot id with an EQ: the EQ'd ones)
+  if ((rc = eq_audio(v, slot, s, &x))) return rc;  // (first: a change of the slot id's EQ invalidates the measurement)
   const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
   if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "loudness: the slot holds no samples");
   void* q = nullptr;
@@ -3471,8 +3573,6 @@ int loudness_measure(piper_hip_voice* v, Slot& s, const LdTarget& t) {
     s.loud_rep = (float*)q;
   }
   if (!s.loud_measured) {
-    const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items)
-    if ((rc = volume_audio(v, s, &x))) return rc;
     PH_HIP(launch_loudness_measure(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, 0, f, s.loud_seg), PIPER_HIP_ERR_LAUNCH);
     s.loud_measured = true;
   }
@@ -3483,8 +3583,8 @@ int loudness_measure(piper_hip_voice* v, Slot& s, const LdTarget& t) {
 // The items a slot id with a loudness target (piper_hip_voice_slot_loudness) hands the rest of the output chain: gained [NB][n_samples],
 // u = x·g per item. Without a target: the plan's audio (x: the shaped items where the plan's staging carried a volume).
 int loudness_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
-  const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items)
-  int rc = volume_audio(v, s, &x);
+  const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items; a slot id with an EQ: the EQ'd ones)
+  int rc = eq_audio(v, slot, s, &x);
   if (rc) return rc;
   *audio = x;
   const auto& sl = v->slot_ld[slot];
@@ -3493,7 +3593,7 @@ int loudness_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
   if ((rc = ld_resolve(&sl.ld, &t))) return rc;
   const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
   if (F < 1) return PIPER_HIP_OK;
-  if ((rc = loudness_measure(v, s, t))) return rc;
+  if ((rc = loudness_measure(v, slot, s, t))) return rc;
   if (!s.gained) {
     void* q = nullptr;
     if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
@@ -3549,6 +3649,7 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   s.h_peaks.clear();  // the peaks a normalising collect_pcm16 reported belong to the previous run
   s.loud_measured = false;  // (and so does the loudness measured there)
   s.vol_shaped = false;     // (and the items shaped from it)
+  s.eq_done = false;        // (and the items EQ'd from those)
   return PIPER_HIP_OK;
 }
 
@@ -4042,6 +4143,34 @@ hipError_t volume_step(piper_hip_voice* v, int slot, Stream& st, const VolStepRo
   return e;
 }
 
+// One launch behind the volume step: the chunks of `rows` generator rows of audio [rows][row] through the stream's EQ → st.eq.out, at the
+// same places (include/piper_hip.h "Equaliser"). A row's chunk is the one the volume step reads: the window's, from sample next · hop.
+hipError_t eq_step(piper_hip_voice* v, int slot, Stream& st, const std::vector<EqStepRow>& tab, const float* audio, int64_t row, size_t bytes,
+                   hipStream_t q) {
+  StreamEq& sq = st.eq;
+  auto& sg = v->staging[slot];
+  if (sq.out_bytes < bytes) {  // (no step is in flight: every step ends with a wait)
+    void* p = nullptr;
+    if (stream_alloc(v, st, bytes, &p)) return hipErrorOutOfMemory;
+    stream_free(v, st, sq.out, sq.out_bytes);
+    sq.out = (float*)p;
+    sq.out_bytes = bytes;
+  }
+  if (grow_pinned(sg.h_estep, sg.cap_estep, (size_t)sq.rows, (size_t)256)) return hipErrorOutOfMemory;
+  const int rows = (int)tab.size();
+  if (rows > sq.rows) return hipErrorInvalidValue;
+  int max_n = 0;
+  for (int r = 0; r < rows; r++) {
+    sg.h_estep[r] = tab[r];
+    max_n = std::max(max_n, tab[r].n);
+  }
+  if (max_n < 1) return hipSuccess;
+  if (max_n > sq.blocks * kEqBlock) return hipErrorInvalidValue;
+  hipError_t e = hipMemcpyAsync(sq.desc, sg.h_estep, (size_t)rows * sizeof(EqStepRow), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) e = launch_eq_step(q, rows, sq.blocks * kEqBlock, audio, row, sq.desc, sq.dev, sq.eq.n, sq.carry, sq.scratch, sq.out);
+  return e;
+}
+
 // stream_next. A PCM sink: the chunk leaves as int16 or one G.711 byte per sample — converted by a kernel behind the window's graph —
 // instead of fp32; the step is the same in every other respect
 int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_samples) {
@@ -4116,6 +4245,11 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
     const VolStepRow vr = volume_range(row, w, v->hop);
     if (e == hipSuccess) e = volume_step(v, slot, s.stream, &vr, 1, gs->audio, 0, gs->set.stream);
     win_audio = s.stream.vol;
+  }
+  if (s.stream.eq.on) {  // (the EQ'd chunk at the same place: the later stages read it as they read the window's)
+    const std::vector<EqStepRow> er{EqStepRow{(int64_t)row.next * v->hop, w.skip, (int)w.n}};
+    if (e == hipSuccess) e = eq_step(v, slot, s.stream, er, win_audio, 0, (size_t)gs->n_samples * sizeof(float), gs->set.stream);
+    win_audio = s.stream.eq.out;
   }
   const float* chunk_audio = win_audio;  // what the output stage reads, its chunk behind dn_skip
   if (lvl.on) {  // (with or without a buffer: the row's carry moves on with the stream)
@@ -4541,6 +4675,13 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
   if (any_vol) {
     if (e == hipSuccess) e = volume_step(v, slot, st, vrow.data(), NBg, gs->audio, gs->n_samples, q);
     win_audio = st.vol;
+  }
+  if (st.eq.on) {  // every delivering row's chunk through the EQ, at the same place; a row that delivers nothing has n = 0
+    std::vector<EqStepRow> er((size_t)NBg, EqStepRow{0, 0, 0});
+    for (int r = 0; r < n; r++)
+      if (rows[r].active) er[r] = EqStepRow{(int64_t)rows[r].next * hop, win[r].skip, (int)win[r].n};
+    if (e == hipSuccess) e = eq_step(v, slot, st, er, win_audio, gs->n_samples, (size_t)NBg * gs->n_samples * sizeof(float), q);
+    win_audio = st.eq.out;
   }
   const float* chunk_audio = win_audio;  // what the output stage reads: rows of chunk_row floats, each row's chunk behind its skip
   int64_t chunk_row = gs->n_samples;
@@ -5054,8 +5195,8 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   const hipStream_t q = s.set.stream;
   const float* audio = s.audio;  // (a slot id with a level: the limited items)
   if ((rc = level_audio(v, slot, s, &audio))) return rc;
-  const float* peak_src = s.audio;  // (the peak of normalize = 1 is that of the shaped items where the staging carried a volume)
-  if (normalize && (rc = volume_audio(v, s, &peak_src))) return rc;
+  const float* peak_src = s.audio;  // (the peak of normalize = 1 is that of the shaped, EQ'd items where there are a volume, an EQ)
+  if (normalize && (rc = eq_audio(v, slot, s, &peak_src))) return rc;
   if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
   if (rd)
     PH_HIP(launch_resample_items(q, audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
@@ -5218,6 +5359,22 @@ PH_EXPORT int piper_hip_voice_slot_level(piper_hip_voice* v, int slot, const pip
   return PIPER_HIP_OK;
 }
 
+// ---- equaliser (include/piper_hip.h "Equaliser")
+
+PH_EXPORT int piper_hip_voice_slot_eq(piper_hip_voice* v, int slot, const piper_hip_eq* eq) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (eq)
+    if (int rc = piper_hip_eq_check(eq, v->cfg.sample_rate)) return rc;
+  v->slot_eq[slot].on = eq != nullptr;
+  v->slot_eq[slot].eq = piper_hip_eq{};
+  if (eq) {  // (only the sections in use: two EQs that differ past n are the same EQ)
+    v->slot_eq[slot].eq.n = eq->n;
+    for (int i = 0; i < eq->n; i++) v->slot_eq[slot].eq.section[i] = eq->section[i];
+  }
+  return PIPER_HIP_OK;
+}
+
 // ---- loudness (include/piper_hip.h "Loudness")
 
 PH_EXPORT int piper_hip_voice_slot_loudness(piper_hip_voice* v, int slot, const piper_hip_loudness* loudness) {
@@ -5244,7 +5401,7 @@ PH_EXPORT int piper_hip_voice_loudness(piper_hip_voice* v, int slot, float* lufs
   LdTarget t;
   int rc = ld_resolve(v->slot_ld[slot].on ? &v->slot_ld[slot].ld : nullptr, &t);
   if (rc) return rc;
-  if ((rc = loudness_measure(v, s, t))) return rc;
+  if ((rc = loudness_measure(v, slot, s, t))) return rc;
   auto& sg = v->staging[slot];
   if ((rc = grow_pinned(sg.h_loud, sg.cap_loud, (size_t)2 * s.NB, (size_t)2 * kMaxGroup))) return rc;
   PH_HIP(hipMemcpyAsync(sg.h_loud, s.loud_rep, (size_t)2 * s.NB * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
@@ -5324,6 +5481,68 @@ PH_EXPORT int piper_hip_voice_stream_level(piper_hip_voice* v, int slot, piper_h
   if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_level: null output");
   if (!st->lv.on) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_level: slot %d has no level", slot);
   *out = st->lv.lv;
+  return PIPER_HIP_OK;
+}
+
+// ---- equaliser on streams (include/piper_hip.h "Equaliser")
+
+PH_EXPORT int piper_hip_voice_stream_set_eq(piper_hip_voice* v, int slot, const piper_hip_eq* eq) {
+  Stream* sp = slot_stream(v, slot, "stream_set_eq");
+  if (!sp) return PIPER_HIP_ERR_ARG;
+  Stream& st = *sp;
+  StreamEq& sq = st.eq;
+  if (!eq) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_eq: null eq");
+  if (st.rs.started)
+    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_eq: slot %d has %s: the EQ is set before", slot, is_pool(st) ? "stepped or been joined" : "stepped");
+  int rc = piper_hip_eq_check(eq, v->cfg.sample_rate);
+  if (rc) return rc;
+  if (v->hop % kEqBlock != 0)
+    PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "stream_set_eq: hop %d is not a multiple of %d: a step's chunk would not start on a block", v->hop, kEqBlock);
+  const int64_t chunk = chunk_samples(v, st);
+  if (chunk < 1 || chunk > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_set_eq: %lld samples per step", (long long)chunk);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  const int blocks = (int)ceil_div(chunk, kEqBlock);
+  if (!sq.dev) {
+    void* p = nullptr;
+    if ((rc = stream_alloc(v, st, sizeof(EqDesign), &p))) return rc;
+    sq.dev = (EqDesign*)p;
+  }
+  if (sq.rows < st.NBg || sq.blocks < blocks) {  // the carry, the scratch and the descriptor of the stream's generator rows
+    stream_free(v, st, sq.carry, (size_t)sq.rows * kEqCarry * sizeof(double));
+    stream_free(v, st, sq.scratch, (size_t)sq.rows * sq.blocks * 2 * kEqMaxD * sizeof(double));
+    stream_free(v, st, sq.desc, (size_t)sq.rows * sizeof(EqStepRow));
+    sq.carry = sq.scratch = nullptr; sq.desc = nullptr; sq.rows = 0; sq.blocks = 0;
+    void *c = nullptr, *w = nullptr, *d = nullptr;
+    if ((rc = stream_alloc(v, st, (size_t)st.NBg * kEqCarry * sizeof(double), &c))) return rc;
+    if ((rc = stream_alloc(v, st, (size_t)st.NBg * blocks * 2 * kEqMaxD * sizeof(double), &w))) {
+      stream_free(v, st, c, (size_t)st.NBg * kEqCarry * sizeof(double));
+      return rc;
+    }
+    if ((rc = stream_alloc(v, st, (size_t)st.NBg * sizeof(EqStepRow), &d))) {
+      stream_free(v, st, c, (size_t)st.NBg * kEqCarry * sizeof(double));
+      stream_free(v, st, w, (size_t)st.NBg * blocks * 2 * kEqMaxD * sizeof(double));
+      return rc;
+    }
+    sq.carry = (double*)c; sq.scratch = (double*)w; sq.desc = (EqStepRow*)d;
+    sq.rows = st.NBg; sq.blocks = blocks;
+  }
+  // the design, built and uploaded here, never inside a step (a blocking copy: no step of this stream has run)
+  std::vector<EqDesign> hold(1);
+  if ((rc = eq_build(eq, v->cfg.sample_rate, hold.data()))) return rc;
+  PH_HIP(hipMemcpy(sq.dev, hold.data(), sizeof(EqDesign), hipMemcpyHostToDevice), PIPER_HIP_ERR_LAUNCH);
+  sq.eq = piper_hip_eq{};
+  sq.eq.n = eq->n;
+  for (int i = 0; i < eq->n; i++) sq.eq.section[i] = eq->section[i];
+  sq.on = true;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_stream_eq(piper_hip_voice* v, int slot, piper_hip_eq* out) {
+  const Stream* st = slot_stream(v, slot, "stream_eq");
+  if (!st) return PIPER_HIP_ERR_ARG;
+  if (!out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_eq: null output");
+  if (!st->eq.on) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_eq: slot %d has no EQ", slot);
+  *out = st->eq.eq;
   return PIPER_HIP_OK;
 }
 

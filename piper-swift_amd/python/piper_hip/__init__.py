@@ -309,7 +309,48 @@ def _level(level):
     return Level(float(d), float(c), float(r))
 
 
-KEEP = object()  # level=KEEP / loudness=KEEP: leave the slot id's level / loudness as it is
+KEEP = object()  # level=KEEP / loudness=KEEP / eq=KEEP: leave the slot id's level / loudness / EQ as it is
+
+EQ_LOWPASS, EQ_HIGHPASS, EQ_BANDPASS, EQ_NOTCH, EQ_PEAKING, EQ_LOWSHELF, EQ_HIGHSHELF = range(1, 8)
+EQ_MAX_SECTIONS = 4
+_EQ_TYPES = {"lowpass": 1, "highpass": 2, "bandpass": 3, "notch": 4, "peaking": 5, "lowshelf": 6, "highshelf": 7}
+
+
+class EqSection(C.Structure):
+    """piper_hip_eq_section: one biquad of include/piper_hip.h "Equaliser"."""
+    _fields_ = [("type", C.c_int32), ("f0_hz", C.c_float), ("q", C.c_float), ("gain_db", C.c_float)]
+
+
+class Eq(C.Structure):
+    """piper_hip_eq: up to four sections run in order. Eq([(type, f0, q, gain_db), ...]) also works; a type may be a name
+    ("lowpass", "highpass", "bandpass", "notch", "peaking", "lowshelf", "highshelf") and gain_db may be left out (0)."""
+    _fields_ = [("n", C.c_int32), ("section", EqSection * 4)]
+
+    def __init__(self, sections=None, *args):
+        super().__init__()
+        if sections is None:
+            return
+        if isinstance(sections, int):  # the ctypes form: Eq(n, section array)
+            super().__init__(sections, *args)
+            return
+        secs = list(sections)
+        self.n = len(secs)
+        for i, sec in enumerate(secs[:EQ_MAX_SECTIONS]):
+            typ, f0, q = sec[0], sec[1], sec[2]
+            g = sec[3] if len(sec) > 3 else 0.0
+            typ = _EQ_TYPES[typ.lower()] if isinstance(typ, str) else int(typ)
+            self.section[i] = EqSection(typ, float(f0), float(q), float(g))
+
+    def sections(self):
+        return [(s.type, s.f0_hz, s.q, s.gain_db) for s in self.section[:max(0, min(self.n, EQ_MAX_SECTIONS))]]
+
+    def __repr__(self):
+        return "Eq(%r)" % (self.sections(),)
+
+
+def _eq(eq):
+    """Eq | [(type, f0, q[, gain_db])] → an Eq"""
+    return eq if isinstance(eq, Eq) else Eq(eq)
 
 
 class Loudness(C.Structure):
@@ -538,6 +579,13 @@ _PROTOS = {
     "piper_hip_volume_from_f32": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_size_t, c_f32p]),
     "piper_hip_volume_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, c_vp, C.c_int64, C.c_int32, C.POINTER(c_vp), c_vp]),
     "piper_hip_voice_slot_volume": (C.c_int, [c_vp, C.c_int, C.POINTER(Volume), C.c_int]),
+    "piper_hip_eq_check": (C.c_int, [C.POINTER(Eq), C.c_int32]),
+    "piper_hip_eq_design": (C.c_int, [C.POINTER(Eq), C.c_int32, c_f64p]),
+    "piper_hip_eq_from_f32": (C.c_int, [C.POINTER(Eq), C.c_int32, c_f32p, C.c_size_t, c_f32p]),
+    "piper_hip_eq_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_int32, C.POINTER(Eq), C.POINTER(c_vp), c_vp]),
+    "piper_hip_voice_slot_eq": (C.c_int, [c_vp, C.c_int, C.POINTER(Eq)]),
+    "piper_hip_voice_stream_set_eq": (C.c_int, [c_vp, C.c_int, C.POINTER(Eq)]),
+    "piper_hip_voice_stream_eq": (C.c_int, [c_vp, C.c_int, C.POINTER(Eq)]),
 }
 
 _lib = None
@@ -891,6 +939,15 @@ class HipBackend:
         p = c_vp(_ptr(out)) if out is not None else c_vp()
         lv = _level(level)
         _check(self.lib.piper_hip_level_f32(self.ctx, _ptr(buf), n, int(rate), C.byref(lv), C.byref(p), commandBuffer))
+        return DeviceBuffer(self, p.value, n, owned=out is None)
+
+    def eq_f32(self, buf, rate, eq, count=None, out=None, commandBuffer=None):
+        """`count` device floats sampled at `rate` → the same number of EQ'd device floats (piper_hip_eq_f32): the biquad cascade of
+        include/piper_hip.h "Equaliser". Returns a DeviceBuffer of `count` float32."""
+        n = buf.count if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        e = _eq(eq)
+        _check(self.lib.piper_hip_eq_f32(self.ctx, _ptr(buf), n, int(rate), C.byref(e), C.byref(p), commandBuffer))
         return DeviceBuffer(self, p.value, n, owned=out is None)
 
     def volume(self, buf, frame_gain, hop, count=None, out=None, commandBuffer=None):
@@ -1335,6 +1392,29 @@ def level_step_bound(n_in):
     return _count(load_library().piper_hip_level_step_bound(int(n_in)))
 
 
+def eq_check(eq, rate):
+    """InvalidArgument naming the field and the section for an EQ outside the contract at `rate` (piper_hip_eq_check). Host-only."""
+    e = _eq(eq)
+    _check(load_library().piper_hip_eq_check(C.byref(e), int(rate)))
+
+
+def eq_design(eq, rate):
+    """[n][5] float64 {b0, b1, b2, a1, a2} per section (piper_hip_eq_design). Host-only."""
+    e = _eq(eq)
+    out = np.zeros((max(e.n, 1), 5), np.float64)
+    _check(load_library().piper_hip_eq_design(C.byref(e), int(rate), out.ctypes.data_as(c_f64p)))
+    return out[:e.n]
+
+
+def eq_from_f32(samples, eq, rate):
+    """The equaliser on the host (piper_hip_eq_from_f32), bit for bit what the device computes."""
+    x = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    y = np.empty(max(x.size, 1), np.float32)
+    e = _eq(eq)
+    _check(load_library().piper_hip_eq_from_f32(C.byref(e), int(rate), x.ctypes.data_as(c_f32p), x.size, y.ctypes.data_as(c_f32p)))
+    return y[:x.size]
+
+
 def level_from_f32(samples, level, rate):
     """The limiter on the host (piper_hip_level_from_f32), bit for bit what the device computes."""
     x = np.ascontiguousarray(samples, np.float32).reshape(-1)
@@ -1411,6 +1491,11 @@ class StreamPool:
             self._buf = np.empty((rt.stream_step_capacity(self.slot) + 1) // 2, np.float32)
         else:
             self._buf = np.empty(max(rt.stream_step_capacity(self.slot), 1), np.float32)
+
+    def set_eq(self, eq):
+        """An equaliser on every row (piper_hip_voice_stream_set_eq): before the first join, with set_rate, set_mixed or set_level in
+        either order."""
+        self.rt.stream_set_eq(self.slot, eq)
 
     def set_level(self, level):
         """A look-ahead limiter on every row (piper_hip_voice_stream_set_level): before the first join, with set_rate or set_mixed in
@@ -1677,7 +1762,7 @@ class HipRuntime:
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
     def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None, volume=None,
-                   level=KEEP, loudness=KEEP, **kw):
+                   level=KEEP, loudness=KEEP, eq=KEEP, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
         reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
         speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays.
@@ -1687,6 +1772,7 @@ class HipRuntime:
             self.slot_speakers(0, [speaker])
         self._slot_level(0, level)
         self._slot_loudness(0, loudness)
+        self._slot_eq(0, eq)
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
@@ -1802,6 +1888,19 @@ class HipRuntime:
             lv = _level(level)
             _check(self.lib.piper_hip_voice_slot_level(self.voice, slot, C.byref(lv)))
 
+    def slot_eq(self, slot, eq):
+        """The equaliser of slot id `slot`'s whole-item collects (piper_hip_voice_slot_eq): an Eq or a list of (type, f0, q[, gain_db]);
+        it persists until replaced; None clears it."""
+        if eq is None:
+            _check(self.lib.piper_hip_voice_slot_eq(self.voice, slot, None))
+        else:
+            e = _eq(eq)
+            _check(self.lib.piper_hip_voice_slot_eq(self.voice, slot, C.byref(e)))
+
+    def _slot_eq(self, slot, eq):
+        if eq is not KEEP:
+            self.slot_eq(slot, eq)
+
     def _slot_level(self, slot, level):
         if level is not KEEP:
             self.slot_level(slot, level)
@@ -1832,6 +1931,16 @@ class HipRuntime:
         lv = _level(level)
         _check(self.lib.piper_hip_voice_stream_set_level(self.voice, slot, C.byref(lv)))
 
+    def stream_set_eq(self, slot, eq):
+        """The EQ of the stream on `slot` (piper_hip_voice_stream_set_eq): after its begin / open, before its first step."""
+        e = _eq(eq)
+        _check(self.lib.piper_hip_voice_stream_set_eq(self.voice, slot, C.byref(e)))
+
+    def stream_eq(self, slot):
+        out = Eq()
+        _check(self.lib.piper_hip_voice_stream_eq(self.voice, slot, C.byref(out)))
+        return out
+
     def stream_level(self, slot):
         out = Level()
         _check(self.lib.piper_hip_voice_stream_level(self.voice, slot, C.byref(out)))
@@ -1855,7 +1964,7 @@ class HipRuntime:
         return _count(self.lib.piper_hip_voice_stream_step_capacity_bytes(self.voice, slot))
 
     def synthesize_stream(self, phonemeIDs, durations, noise=None, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None,
-                          encoding=None, prosody=None, volume=None, level=None):
+                          encoding=None, prosody=None, volume=None, level=None, eq=None):
         """Generator of waveform chunks (PiperMetalRuntime.synthesizeStream): encoder + flow once, generator per window.
         prosody: the utterance's per-id prosody, as for prepare. volume: the utterance's linear gains per id, as for prepare: every chunk
         leaves under the envelope, and the concatenated chunks equal the whole-item result bit for bit.
@@ -1871,6 +1980,8 @@ class HipRuntime:
         law = None if encoding is None else _law(encoding)
         sample = np.uint8 if law is not None else np.int16
         buf = np.empty(int(chunkFrames) * self.cfg.hop, sample if pcm or rate or law is not None else np.float32)
+        if eq is not None:  # an equaliser behind the volume (stream_set_eq)
+            self.stream_set_eq(slot, eq)
         if level is not None:  # a look-ahead limiter in front of the output stage (stream_set_level)
             self.stream_set_level(slot, level)
             buf = np.empty(self.stream_step_capacity(slot), buf.dtype)
@@ -1893,7 +2004,7 @@ class HipRuntime:
             yield buf[:got.value].copy()
 
     def synthesize_stream_batch(self, utterances, noiseScale=0.667, chunkFrames=64, slot=0, pcm=False, gain=1.0, rate=None, encoding=None,
-                                formats=None, prosody=None, volume=None, level=None):
+                                formats=None, prosody=None, volume=None, level=None, eq=None):
         """prosody: one entry per utterance (None entries neutral), as for slot_prosody.
         Batched stream (piper_hip_voice_stream_begin_batch): utterances = list of (phonemeIDs, durations-or-None, noise-or-None[, dict of
         noise_mode / seed / length_scale / noise_w]). Encoder + flow once for the group; yields, per step, a list of len(utterances)
@@ -1915,6 +2026,8 @@ class HipRuntime:
         steps = self.lib.piper_hip_voice_stream_begin_batch(self.voice, arr, n, slot, int(chunkFrames))
         if steps < 0:
             _check(steps)
+        if eq is not None:  # an equaliser on every row, behind the volume (stream_set_eq)
+            self.stream_set_eq(slot, eq)
         if level is not None:  # a look-ahead limiter on every row, in front of the output stage (stream_set_level)
             self.stream_set_level(slot, level)
         if formats is not None:
@@ -1961,7 +2074,7 @@ class HipRuntime:
         """The client of item `item` of the batched stream on `slot` went away: later steps skip it."""
         _check(self.lib.piper_hip_voice_stream_drop(self.voice, slot, int(item)))
 
-    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None, rate=None, mixed=False, level=None):
+    def stream_pool(self, slot, capacity, chunkFrames=64, work_slot=None, rate=None, mixed=False, level=None, eq=None):
         """A streaming pool (piper_hip_voice_stream_pool_open) of `capacity` rows on `slot`: sessions join and leave while it runs.
         work_slot: the slot id whose plan runs the joins' encoder + flow (default: the next slot id). mixed=True: every joining session
         brings its own format (join(formats=[...]), step_mixed())."""
@@ -1974,6 +2087,8 @@ class HipRuntime:
             pool.set_rate(rate)
         if mixed:
             pool.set_mixed()
+        if eq is not None:
+            pool.set_eq(eq)
         if level is not None:
             pool.set_level(level)
         return pool
@@ -2026,11 +2141,12 @@ class HipRuntime:
         self._pinned.append(p)
         return np.ctypeslib.as_array(C.cast(p, c_f32p), shape=(int(count),))
 
-    def collect(self, slot, want_audio=True, out=None, level=KEEP, loudness=KEEP):
+    def collect(self, slot, want_audio=True, out=None, level=KEEP, loudness=KEEP, eq=KEEP):
         """level: a Level (or tuple / dict) sets the slot id's level before the call, None clears it (slot_level); it persists.
         loudness: the same for the slot id's loudness target (slot_loudness)."""
         self._slot_level(slot, level)
         self._slot_loudness(slot, loudness)
+        self._slot_eq(slot, eq)
         n = self._keep[slot][1]
         if not want_audio:
             _check(self.lib.piper_hip_voice_collect(self.voice, slot, None, 0))
@@ -2044,13 +2160,14 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
-    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP):
+    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP, eq=KEEP):
         """collect() with 16-bit PCM converted on the device (piper_hip_voice_collect_pcm16): the items back to back at their true lengths.
         normalize=False: the samples pcm16(collect(slot)) gives; normalize=True: Piper's peak normalisation per item (peaks(slot) afterwards).
         The fp32 waveform stays in the plan: collect / collect_pcm16 may follow in any order. rate: resampled on the device to that output
         rate (piper_hip_voice_collect_pcm16_rate), item b at J(its true samples). level, loudness: as for collect."""
         self._slot_level(slot, level)
         self._slot_loudness(slot, loudness)
+        self._slot_eq(slot, eq)
         n = self._keep[slot][1]
         if rate is not None and int(rate) != self.cfg.sample_rate:  # (the voice's own rate is not a filter: the plain call)
             return self._collect_pcm16_rate(slot, gain, normalize, out, int(rate))
@@ -2081,11 +2198,12 @@ class HipRuntime:
         return out[:sum(resample_count(src, rate, p) for p in per)]
 
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, rate=None, prosody=None, volume=None, level=KEEP, loudness=KEEP, **kw):
+                         normalize=False, rate=None, prosody=None, volume=None, level=KEEP, loudness=KEEP, eq=KEEP, **kw):
         """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare;
         level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
         self._slot_loudness(0, loudness)
+        self._slot_eq(0, eq)
         pro = None if prosody is None else [prosody]
         vol = None if volume is None else [volume]
         if rate is not None and int(rate) == self.cfg.sample_rate:
@@ -2117,11 +2235,12 @@ class HipRuntime:
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
 
-    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP):
+    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP, eq=KEEP):
         """collect_pcm16 ending in G.711 bytes ("mulaw" / "alaw") companded on the device (piper_hip_voice_collect_g711): one uint8 per
         sample, the items back to back at J(their true samples) at `rate` (default: the voice's own). Every rule of collect_pcm16 holds."""
         self._slot_level(slot, level)
         self._slot_loudness(slot, loudness)
+        self._slot_eq(slot, eq)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         count = (lambda p: p) if rate == src else (lambda p: resample_count(src, rate, p))
@@ -2140,11 +2259,12 @@ class HipRuntime:
         return out[:sum(count(p) for p in per)]
 
     def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None, volume=None,
-                        level=KEEP, loudness=KEEP):
+                        level=KEEP, loudness=KEEP, eq=KEEP):
         """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's;
         prosody: as for prepare (with supplied durations: noise alone); level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
         self._slot_loudness(0, loudness)
+        self._slot_eq(0, eq)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)

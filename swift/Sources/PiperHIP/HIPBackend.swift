@@ -351,6 +351,39 @@ public final class HIPBackend {
         return g
     }
 
+    // ---- equaliser (include/piper_hip.h "Equaliser") ----
+
+    /// `count` device floats sampled at `rate` → the same number of EQ'd device floats (piper_hip_eq_f32): up to four biquads in double,
+    /// bit for bit the host twin.
+    public func eqF32(input: HIPBuffer, count: Int, rate: Int32, eq: piper_hip_eq, commandBuffer: Stream? = nil) throws -> HIPBuffer {
+        var out: UnsafeMutablePointer<Float>? = nil
+        var e = eq
+        try Self.check(piper_hip_eq_f32(ctx, input.f32, count, rate, &e, &out, commandBuffer))
+        return HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx)
+    }
+
+    /// The equaliser on the host (piper_hip_eq_from_f32), bit for bit what the device computes.
+    public static func eqFromF32(_ x: [Float], eq: piper_hip_eq, rate: Int32) throws -> [Float] {
+        var e = eq
+        var y = [Float](repeating: 0, count: x.count)
+        try check(piper_hip_eq_from_f32(&e, rate, x, x.count, &y))
+        return y
+    }
+
+    /// InvalidArgument naming the field and the section for an EQ outside the contract at `rate` (piper_hip_eq_check; host-only).
+    public static func eqCheck(_ eq: piper_hip_eq, rate: Int32) throws {
+        var e = eq
+        try check(piper_hip_eq_check(&e, rate))
+    }
+
+    /// {b0, b1, b2, a1, a2} of every section in use (piper_hip_eq_design; host-only).
+    public static func eqDesign(_ eq: piper_hip_eq, rate: Int32) throws -> [[Double]] {
+        var e = eq
+        var rows = [(Double, Double, Double, Double, Double)](repeating: (0, 0, 0, 0, 0), count: Int(PIPER_HIP_EQ_MAX_SECTIONS))
+        try check(piper_hip_eq_design(&e, rate, &rows))
+        return rows.prefix(Int(max(0, min(eq.n, PIPER_HIP_EQ_MAX_SECTIONS)))).map { [$0.0, $0.1, $0.2, $0.3, $0.4] }
+    }
+
     // ---- binary with NumPy broadcasting, output rank ≤ 4 (MetalBackend.swift:2099-2134, 2592-2610) ----
     private func binaryBroadcastF32(_ op: piper_hip_binary_op, a: HIPBuffer, aShape: [Int], b: HIPBuffer, bShape: [Int],
                                     commandBuffer: Stream?) throws -> (out: HIPBuffer, outShape: [Int]) {

@@ -484,6 +484,16 @@ public final class PiperHIPRuntime {
         }
     }
 
+    /// The equaliser of slot id `slot`'s whole-item collects (piper_hip_voice_slot_eq): it persists until replaced; nil clears it.
+    /// Every later collect* and synthesize* on the slot id delivers the EQ'd items, behind the volume and in front of the loudness gain.
+    public func slotEq(slot: Int32, eq: piper_hip_eq?) throws {
+        if var e = eq {
+            try HIPBackend.check(piper_hip_voice_slot_eq(voice, slot, &e))
+        } else {
+            try HIPBackend.check(piper_hip_voice_slot_eq(voice, slot, nil))
+        }
+    }
+
     /// Per item of the slot's latest launch: the integrated loudness of the raw samples, measured on the device, and the gain the
     /// slot's target implies, 1 without one (piper_hip_voice_loudness). Waits for the slot.
     public func loudness(slot: Int32) throws -> (lufs: [Float], gain: [Float]) {
@@ -491,6 +501,19 @@ public final class PiperHIPRuntime {
         var lufs = [Float](repeating: 0, count: max(n, 1)), gain = lufs
         try HIPBackend.check(piper_hip_voice_loudness(voice, slot, &lufs, &gain, Int32(n)))
         return (Array(lufs[0..<n]), Array(gain[0..<n]))
+    }
+
+    /// The EQ of the stream on `slot` (piper_hip_voice_stream_set_eq): where streamSetLevel is allowed, in either order with it.
+    public func streamSetEq(slot: Int32, eq: piper_hip_eq) throws {
+        var e = eq
+        try HIPBackend.check(piper_hip_voice_stream_set_eq(voice, slot, &e))
+    }
+
+    /// The EQ the stream on `slot` holds (piper_hip_voice_stream_eq).
+    public func streamEq(slot: Int32) throws -> piper_hip_eq {
+        var e = piper_hip_eq()
+        try HIPBackend.check(piper_hip_voice_stream_eq(voice, slot, &e))
+        return e
     }
 
     /// The level of the stream on `slot` (piper_hip_voice_stream_set_level): where streamSetRate is allowed, in either order with it.
