@@ -29,6 +29,12 @@
  *                            --eq TYPE:F0:Q[:GAIN_DB], up to four times: a biquad section of the equaliser on the device (TYPE lowpass,
  *                            highpass, bandpass, notch, peaking, lowshelf or highshelf; GAIN_DB for peaking and the shelves), in front
  *                            of the loudness gain, the limiter and every output above (piper_hip_voice_slot_eq on slot 0).
+ *                            --phoneme-ids A/B/…: several id lists separated by '/', the sentences of one text. They run as ONE
+ *                            piper_hip_voice_prepare_batch and leave as ONE programme joined on the device (piper_hip_voice_slot_join on
+ *                            slot 0), with --sentence-silence SECONDS (Piper's flag) between them, --lead-ms X / --tail-ms X of silence
+ *                            around them and --trim-silence THRESHOLD[:PAD_MS[:FADE_MS]] cutting each sentence's quiet head and tail
+ *                            (linear amplitude; the cut edges fade). Any of the four flags joins a single list too. Each sentence's
+ *                            start in the programme is printed on stderr. One list without these flags behaves as before.
  *   --speaker N              both modes: speaker N of a multi-speaker voice (the graph's `sid`; piper_hip_voice_attach_speakers +
  *                            piper_hip_voice_slot_speakers). With --model the file's speaker table is loaded (opt-in: without the flag such a
  *                            file is refused; its node graph is NOT verified — no verifier for the conditioned graph exists yet); without
@@ -203,6 +209,43 @@ static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_p
   return 0;
 }
 
+/* Several sentences (or one under a join flag): one prepare_batch on slot 0, joined on the device into ONE programme, converted (and
+ * resampled, as one signal) there. *pcm is malloc'ed; the caller frees it, after a failure too. The starts go to stderr. */
+static int run_programme(runner* r, const int64_t* ids, const int* off, const int* len, int n_lists, const piper_hip_join* join,
+                         const piper_hip_pcm_params* prm, int in_rate, int rate, int law, void** pcm, int64_t* samples) {
+  piper_hip_utterance u[PIPER_HIP_JOIN_MAX_ITEMS];
+  int64_t start[PIPER_HIP_JOIN_MAX_ITEMS], total = 0, cap = 0;
+  int32_t* dur = NULL;
+  int rc;
+  *pcm = NULL;
+  memset(u, 0, sizeof u);
+  if (!r->predict) {
+    int t_max = 0;
+    for (int i = 0; i < n_lists; i++) t_max = len[i] > t_max ? len[i] : t_max;
+    dur = (int32_t*)malloc(sizeof(int32_t) * (size_t)t_max);
+    for (int i = 0; i < t_max; i++) dur[i] = r->pin_frames;
+  }
+  for (int i = 0; i < n_lists; i++) {
+    u[i].phoneme_ids = ids + off[i]; u[i].t = len[i]; u[i].noise_scale = r->noise_scale; u[i].seed = 1234;
+    u[i].length_scale = r->length_scale; u[i].noise_w = r->noise_w; u[i].noise_mode = PIPER_HIP_NOISE_DEVICE;
+    u[i].durations = dur;
+  }
+  rc = piper_hip_voice_slot_join(r->voice, 0, join, NULL, 0);
+  if (rc >= 0) rc = piper_hip_voice_prepare_batch(r->voice, u, n_lists, 0);
+  free(dur);
+  if (rc < 0) return rc;
+  if ((rc = piper_hip_voice_join_capacity(r->voice, 0, rate, &cap)) < 0) return rc;
+  *pcm = malloc((law ? 1 : sizeof(int16_t)) * (size_t)(cap > 0 ? cap : 1));
+  if ((rc = piper_hip_voice_launch(r->voice, 0)) < 0) return rc;
+  rc = law ? piper_hip_voice_collect_g711(r->voice, 0, prm, law, rate, (uint8_t*)*pcm, cap)
+           : piper_hip_voice_collect_pcm16_rate(r->voice, 0, prm, rate, (int16_t*)*pcm, cap);
+  if (rc < 0) return rc;
+  if ((rc = piper_hip_voice_join_report(r->voice, 0, start, NULL, PIPER_HIP_JOIN_MAX_ITEMS, &total)) < 0) return rc;
+  for (int i = 0; i < n_lists; i++) fprintf(stderr, "sentence %d starts at %.3f s\n", i, (double)start[i] / in_rate);
+  *samples = rate == in_rate ? total : piper_hip_resample_count(in_rate, rate, total);
+  return 0;
+}
+
 /* --eq TYPE:F0:Q[:GAIN_DB] → one section; nonzero on a malformed argument (the library checks the values) */
 static int parse_eq_section(const char* s, piper_hip_eq_section* out) {
   static const char* const names[7] = {"lowpass", "highpass", "bandpass", "notch", "peaking", "lowshelf", "highshelf"};
@@ -240,6 +283,7 @@ int main(int argc, char** argv) {
                     "       %s --phoneme-ids 1,20,0,… --output out.wav | --output-raw out.s16le [--volume V] [--normalize] [--output-rate N]\n"
                     "                [--output-encoding s16le|mulaw|alaw] [--drive X] [--ceiling Y] [--release-ms Z]\n"
                     "                [--loudness LUFS [--max-gain-db X]] [--id-volume I:J=G[,I:J=G...]] [--eq TYPE:F0:Q[:GAIN_DB] ...]\n"
+                    "                [--phoneme-ids A/B/... --sentence-silence SECONDS --lead-ms X --tail-ms X --trim-silence THRESHOLD[:PAD_MS[:FADE_MS]]]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n"
                     "               [--speaker N [--speakers S]]\n", argv[0], argv[0]);
     return 2;
@@ -331,7 +375,23 @@ int main(int argc, char** argv) {
 
   if (!scale_bench) { /* one shot: ids → WAV */
     int64_t ids[4096];
-    const int t = parse_csv_i64(ids_arg, ids, 4096);
+    /* several id lists separated by '/': the sentences of one text (one list: exactly the former behaviour) */
+    int list_off[PIPER_HIP_JOIN_MAX_ITEMS], list_len[PIPER_HIP_JOIN_MAX_ITEMS], n_lists = 0, t = 0;
+    {
+      char* copy = (char*)malloc(strlen(ids_arg) + 1);
+      strcpy(copy, ids_arg);
+      for (char* part = copy; part && n_lists < PIPER_HIP_JOIN_MAX_ITEMS;) {
+        char* bar = strchr(part, '/');
+        if (bar) *bar = 0;
+        const int k = parse_csv_i64(part, ids + t, 4096 - t);
+        if (k < 1) { t = 0; break; }
+        list_off[n_lists] = t; list_len[n_lists] = k; n_lists++;
+        t += k;
+        part = bar ? bar + 1 : NULL;
+        if (part && n_lists == PIPER_HIP_JOIN_MAX_ITEMS) t = 0; /* more sentences than a join takes */
+      }
+      free(copy);
+    }
     const char* out = arg_value(argc, argv, "--output");
     const char* out_raw = arg_value(argc, argv, "--output-raw");
     if (t < 1 || (!out && !out_raw)) { fprintf(stderr, "--phoneme-ids needs a comma-separated list and --output or --output-raw a path\n"); return 2; }
@@ -388,6 +448,53 @@ int main(int argc, char** argv) {
         piper_hip_destroy(ctx);
         return 2;
       }
+    }
+    const char* sil_arg = arg_value(argc, argv, "--sentence-silence");
+    const char* trim_arg = arg_value(argc, argv, "--trim-silence");
+    if (n_lists > 1 || sil_arg || trim_arg || arg_value(argc, argv, "--lead-ms") || arg_value(argc, argv, "--tail-ms")) {
+      /* the programme: the sentences as one batch, joined, converted and resampled on the device */
+      piper_hip_join jn;
+      void* pcm = NULL;
+      int failed = 0;
+      memset(&jn, 0, sizeof jn);
+      jn.gap_ms = sil_arg ? (float)(atof(sil_arg) * 1000.0) : 0.0f;
+      jn.lead_ms = arg_value(argc, argv, "--lead-ms") ? (float)atof(arg_value(argc, argv, "--lead-ms")) : 0.0f;
+      jn.tail_ms = arg_value(argc, argv, "--tail-ms") ? (float)atof(arg_value(argc, argv, "--tail-ms")) : 0.0f;
+      if (trim_arg) {
+        jn.trim = 1;
+        if (sscanf(trim_arg, "%f:%f:%f", &jn.trim_threshold, &jn.trim_pad_ms, &jn.fade_ms) < 1) {
+          fprintf(stderr, "--trim-silence %s: expected THRESHOLD[:PAD_MS[:FADE_MS]]\n", trim_arg);
+          return 2;
+        }
+      }
+      if (piper_hip_join_check(&jn, NULL, 0) < 0) { fprintf(stderr, "%s\n", piper_hip_last_error()); return 2; }
+      if (idvol_arg) { fprintf(stderr, "--id-volume is for a single sentence without a join\n"); return 2; }
+      const int prc = run_programme(&r, ids, list_off, list_len, n_lists, &jn, &prm, cfg.sample_rate, rate, law, &pcm, &n);
+      if (prc < 0) {
+        fprintf(stderr, "the programme failed (%d): %s\n", prc, piper_hip_last_error());
+        failed = 1;
+      } else {
+        (void)piper_hip_voice_last_gpu_ms(r.voice, 0, &gpu);
+        if (out && (law ? piper_hip_wav_write_g711(out, law, (const uint8_t*)pcm, (size_t)n, rate)
+                        : piper_hip_wav_write_pcm16(out, (const int16_t*)pcm, (size_t)n, rate)) < 0) {
+          fprintf(stderr, "cannot write %s: %s\n", out, piper_hip_last_error());
+          failed = 1;
+        }
+        if (out_raw && !failed) {
+          FILE* fr = fopen(out_raw, "wb");
+          failed = !fr || fwrite(pcm, law ? 1 : sizeof(int16_t), (size_t)n, fr) != (size_t)n;
+          if (fr && fclose(fr) != 0) failed = 1;
+          if (failed) fprintf(stderr, "cannot write %s\n", out_raw);
+        }
+        if (!failed)
+          fprintf(stderr, "%d sentences, %lld samples (%.3f s at %d Hz) as %s, %.3f ms on the GPU -> %s\n", n_lists, (long long)n, (double)n / rate, rate,
+                  enc ? enc : "s16le", gpu, out_raw ? out_raw : out);
+      }
+      free(pcm);
+      free(r.id_gain);
+      piper_hip_voice_destroy(r.voice);
+      piper_hip_destroy(ctx);
+      return failed;
     }
     if (out) {
       CHECK(run_one(&r, ids, t, &n));

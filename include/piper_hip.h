@@ -999,6 +999,75 @@ int piper_hip_voice_slot_eq(piper_hip_voice* v, int slot, const piper_hip_eq* eq
 int piper_hip_voice_stream_set_eq(piper_hip_voice* v, int slot, const piper_hip_eq* eq);
 int piper_hip_voice_stream_eq(piper_hip_voice* v, int slot, piper_hip_eq* out);
 
+/* ---- Join: trim, fade and gap a batch into one programme on the device (DESIGN.md §4 "Join") ----
+ * A text is a batch of sentences, and what a host plays is ONE piece of audio with a pause between them (Piper's --sentence-silence).
+ * Putting it together on the host means floats down, a scan for the model's quiet head and tail, a second copy with silences, and the
+ * resampler or compander on one core; on a bounded slot the host does not even know where an item ends before the device tells it. So
+ * the join is one more stage of the whole-item output chain — generator → volume → EQ → loudness gain → level → join → resampler →
+ * PCM / G.711 — and it changes nothing for a request that does not ask for it. It turns the NB items of a slot into one signal, the
+ * programme:   lead silence, item 0 (trimmed, faded), gap 0, item 1, …, item NB − 1, tail silence.
+ * Every later stage treats the programme as a single item of a length only the device knows. In particular, at an output rate other
+ * than the voice's the programme is resampled as ONE signal; it is NOT the concatenation of the per-item resamples.
+ * The join is a contract, bit for bit:
+ *   counts     S(ms) = (int64) floor((double)ms · rate / 1000.0 + 0.5), the float widened first; rate = the rate of the samples being
+ *              joined, on voice routes the voice's own. P = S(trim_pad_ms), Fd = S(fade_ms).
+ *   kept range item i has N_i samples x. trim = 0: [s, t) = [0, N_i). trim = 1: a = the least index with fabsf(x[n]) > trim_threshold,
+ *              e = the greatest (the compare is fp32 and false for NaN; ±Inf is above every threshold). None: s = t = 0, the item is
+ *              empty and its gap is still emitted. Otherwise s = max(0, a − P), t = min(N_i, e + 1 + P).
+ *   fades      only at an edge that was cut. g(k) = (float)((double)(k + 1) / (double)(Fd + 1)). Head, if s > 0: for k in
+ *              [0, min(Fd, t − s)): y[s + k] = fl(x[s + k] · g(k)). Tail, if t < N_i: for k in [0, min(Fd, t − s)):
+ *              y[t − 1 − k] = fl(y[t − 1 − k] · g(k)), applied after the head where they overlap. Every other kept sample is copied bit
+ *              for bit.
+ *   layout     S(lead_ms) samples of +0.0f; for each item its kept samples, and after every item but the last S(gap_i) zeros;
+ *              S(tail_ms) zeros after the last item. gap_i = gaps[i] where the caller gave one (i < n_gaps), else gap_ms.
+ *              start_i = the programme index of item i's first kept sample, len_i = t − s, total = the programme length.
+ *   downstream collect delivers the `total` floats; collect_pcm16 / _rate / _g711 apply their contracts to the programme as one item of
+ *              `total` samples: normalize = 1 takes ONE peak over the programme and piper_hip_voice_peaks reports one value; the delivered
+ *              count is piper_hip_resample_count(rate, out_rate, total).
+ *   identities the neutral join (all three silences 0, trim = 0) of one item reproduces the un-joined collect bit for bit on every sink;
+ *              of a batch it reproduces the back-to-back items bit for bit on the sinks at the voice's own rate.
+ * Anything outside the ranges below is PIPER_HIP_ERR_ARG with a message that names the field. */
+#define PIPER_HIP_JOIN_MAX_ITEMS 256
+typedef struct {
+  float lead_ms, gap_ms, tail_ms;   /* each finite in [0, 10000] */
+  int32_t trim;                     /* 0 or 1 */
+  float trim_threshold;             /* finite, >= 0: linear amplitude of the signal that enters the join */
+  float trim_pad_ms;                /* finite in [0, 1000] */
+  float fade_ms;                    /* finite in [0, 100] */
+} piper_hip_join;
+/* Host-only (no device needed). join_check: the rules above; gaps (NULL with n = 0, else n values in 0 … 256): each finite in
+ * [0, 10000]. join_counts: the S() values at `rate` (rate ≥ 1; any output pointer may be NULL). join_capacity: the no-trim upper bound
+ * on total, lead + Σ N_i + the gaps + tail. join_from_f32: the host twin of the kernels: item i is x[item_off[i] … + item_len[i]), the
+ * programme goes to y[max] (a shorter y is PIPER_HIP_ERR_SHAPE; only `total` samples are written), start / len ([n_items], optional)
+ * and total receive the report. n_items in 1 … 256; items of length 0 are allowed. */
+int piper_hip_join_check(const piper_hip_join* join, const float* gaps, int n);
+int piper_hip_join_counts(const piper_hip_join* join, int32_t rate, int64_t* lead, int64_t* gap, int64_t* tail, int64_t* pad, int64_t* fade);
+int piper_hip_join_capacity(const piper_hip_join* join, const float* gaps, int n_gaps, int32_t rate, const int64_t* item_samples, int n_items,
+                            int64_t* samples);
+int piper_hip_join_from_f32(const piper_hip_join* join, const float* gaps, int n_gaps, int32_t rate, const float* x, const int64_t* item_off,
+                            const int64_t* item_len, int n_items, float* y, int64_t max, int64_t* start, int64_t* len, int64_t* total);
+/* Per-op: arbitrary device floats x (4-byte alignment suffices), item i at x[item_off[i] … + item_len[i]) (host arrays) → the programme
+ * in device memory: `*out` convention of the other ops, a caller's buffer holds piper_hip_join_capacity samples. start_host / len_host
+ * ([n_items], optional) and total_host receive the report; the call waits for the device before it returns, whatever `stream` is
+ * (the report is its answer). A capacity that does not fit an int is PIPER_HIP_ERR_SHAPE. */
+int piper_hip_join_f32(piper_hip_ctx* ctx, const float* x, const int64_t* item_off, const int64_t* item_len, int n_items, int32_t rate,
+                       const piper_hip_join* join, const float* gaps, int n_gaps, float** out, int64_t* start_host, int64_t* len_host,
+                       int64_t* total_host, piper_hip_stream stream);
+/* Whole items: the join of slot id `slot`, state of the slot id like slot_level / slot_eq: it persists until replaced, join = NULL clears
+ * it; checked at the voice's rate. Every later collect, collect_pcm16, collect_pcm16_rate, collect_g711 and the synthesize twins (slot 0,
+ * one item; their n_samples is the programme's count) on that slot deliver the programme, on plain, ragged and bounded slots. On a
+ * bounded slot nothing new waits for the GPU: trims and offsets are decided on the device, where the lengths live. Collects with
+ * different joins, or with and without one, may follow one launch in any order. The fp32 audio in the plan, the `audio` tap,
+ * prepared_samples, durations, piper_hip_voice_loudness and prosody_report are unchanged. Streams have no join: a stream row is one item.
+ * join_capacity: the samples a collect on the prepared slot needs room for at `out_rate` (0 = the voice's own):
+ * piper_hip_resample_count of the no-trim bound, a bounded slot's items taken at their frame capacity; a shorter buffer is
+ * PIPER_HIP_ERR_SHAPE and leaves the slot collectable, and a bound that does not fit an int is PIPER_HIP_ERR_SHAPE.
+ * join_report: after a joined collect, start / len of each item ([max_items] ≥ the batch size, optional) and total, at the voice's rate;
+ * PIPER_HIP_ERR_ARG if the slot was not collected with a join since its last launch. */
+int piper_hip_voice_slot_join(piper_hip_voice* v, int slot, const piper_hip_join* join, const float* gaps, int n_gaps);
+int piper_hip_voice_join_capacity(piper_hip_voice* v, int slot, int32_t out_rate, int64_t* samples);
+int piper_hip_voice_join_report(const piper_hip_voice* v, int slot, int64_t* start, int64_t* len, int max_items, int64_t* total);
+
 /* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
  * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]
  * (the graph's `sid` input, read by PiperMetalRuntime.synthesize next to `scales`, PiperMetalRuntime.swift:62-80; in the graph a Gather

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <chrono>
+#include <climits>
 #include <functional>
 #include <memory>
 
@@ -24,6 +25,7 @@
 #include "conv_bf16.h"
 #include "conv_win.h"
 #include "eq.h"
+#include "join.h"
 #include "level.h"
 #include "loudness.h"
 #include "volume.h"
@@ -431,6 +433,12 @@ struct Slot {
   piper_hip_eq eq_held{};
   bool eq_dev_ok = false;        // eq_dev holds the design of eq_dev_eq at eq_dev_rate
   piper_hip_eq eq_dev_eq{};
+  // Join (piper_hip_voice_slot_join): device buffers of this plan (in `owned`), allocated on first use
+  float* jn_buf = nullptr;       // [jn_cap] the programme
+  int64_t jn_cap = 0;            // samples
+  char* jn_dev = nullptr;        // JoinParams | report [kJoinReport] | rows [kJoinMaxItems] | edges [2·kJoinMaxItems], total
+  uint64_t jn_gen = 0;           // the slot_join call whose params jn_dev holds (0: none)
+  std::vector<int64_t> h_jrep;   // {total, start[NB], len[NB]} of the latest joined collect (empty: none since the last launch)
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
@@ -581,6 +589,11 @@ struct piper_hip_voice {
     hipEvent_t eq_ev = nullptr;  // recorded behind the latest copy from h_eq
     EqStepRow* h_estep = nullptr;  // a stream step's EqStepRow table (one H2D per step of a stream with an EQ)
     size_t cap_estep = 0;
+    JoinParams* h_join = nullptr;  // the params of the slot id's join on their way to a plan (one H2D when the join or the plan changes)
+    size_t cap_join = 0;
+    hipEvent_t join_ev = nullptr;  // recorded behind the latest copy from h_join
+    int64_t* h_jrep = nullptr;     // the report of a joined collect: written by the plan kernel through the mapping, or by a D2H behind it
+    size_t cap_jrep = 0;
   } staging[kMaxSlots];
   // The prosody of a slot id's NEXT staging call (piper_hip_voice_slot_prosody): owned copies of the caller's arrays, an empty array = the
   // field was NULL. The staging call takes the assignment (take_prosody) whether or not it succeeds.
@@ -609,6 +622,10 @@ struct piper_hip_voice {
   struct SlotLoudness { bool on = false; piper_hip_loudness ld{}; } slot_ld[kMaxSlots];
   // The equaliser of each slot id's whole-item collects (piper_hip_voice_slot_eq), as given and checked; on = false: none.
   struct SlotEq { bool on = false; piper_hip_eq eq{}; } slot_eq[kMaxSlots];
+  // The join of each slot id's whole-item collects (piper_hip_voice_slot_join), checked and counted at the voice's rate; on = false:
+  // none. gen numbers the slot_join calls voice-wide: a plan knows by it whether its device copy of the params is this one.
+  struct SlotJoin { bool on = false; uint64_t gen = 0; JoinParams p{}; } slot_jn[kMaxSlots];
+  uint64_t join_clock = 0;
   bool planned = false;  // a plan has been asked for: the voice's schedules are fixed (no attach_speakers any more)
   Slot* attached[kMaxSlots] = {};
   std::unique_ptr<StreamPool> pools[kMaxSlots];  // the streaming pool a slot id holds (then attached[slot] is null)
@@ -940,6 +957,7 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.gained = nullptr; s.loud_seg = nullptr; s.loud_rep = nullptr; s.loud_measured = false;
   s.vol_on = false; s.vol_gain = nullptr; s.shaped = nullptr; s.vol_shaped = false; s.vol_gf = nullptr;
   s.eqd = nullptr; s.eq_work = nullptr; s.eq_dev = nullptr; s.eq_done = false; s.eq_on = false; s.eq_dev_ok = false;
+  s.jn_buf = nullptr; s.jn_cap = 0; s.jn_dev = nullptr; s.jn_gen = 0; s.h_jrep.clear();
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
@@ -2605,6 +2623,9 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.eq_ev) { (void)hipEventSynchronize(sg.eq_ev); (void)hipEventDestroy(sg.eq_ev); }
     if (sg.h_eq) (void)hipHostFree(sg.h_eq);
     if (sg.h_estep) (void)hipHostFree(sg.h_estep);
+    if (sg.join_ev) { (void)hipEventSynchronize(sg.join_ev); (void)hipEventDestroy(sg.join_ev); }
+    if (sg.h_join) (void)hipHostFree(sg.h_join);
+    if (sg.h_jrep) (void)hipHostFree(sg.h_jrep);
     if (sg.h_spk) (void)hipHostFree(sg.h_spk);
     if (sg.h_pro) (void)hipHostFree(sg.h_pro);
     if (sg.h_vol) (void)hipHostFree(sg.h_vol);
@@ -3035,6 +3056,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   s.loud_measured = false;
   s.vol_shaped = false;
   s.eq_done = false;
+  s.h_jrep.clear();
   return slot;
 }
 
@@ -3218,6 +3240,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   s.loud_measured = false;
   s.vol_shaped = false;
   s.eq_done = false;
+  s.h_jrep.clear();
   return slot;
 }
 
@@ -3451,6 +3474,7 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__
 }
 
 int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
+void plan_free(piper_hip_voice* v, Slot& s, void* p, size_t bytes);
 
 int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, int n, int T, hipStream_t q) {
   s.vol_on = !vol.empty();
@@ -3631,6 +3655,124 @@ int level_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
   *audio = s.lim;
   return PIPER_HIP_OK;
 }
+
+// ---- join (include/piper_hip.h "Join"): the items a collect reads → ONE programme in the plan's jn_buf
+
+// The no-trim bound on the programme of slot id `slot`'s join over the prepared plan, at the voice's rate: a bounded slot whose lengths
+// are still on the device counts every item at its frame capacity.
+int join_capacity(const piper_hip_voice* v, int slot, const Slot& s, int64_t* cap) {
+  const auto& sj = v->slot_jn[slot];
+  if (s.NB > kJoinMaxItems) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join: %d items (at most %d)", s.NB, kJoinMaxItems);
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  int64_t sum = 0;
+  for (int b = 0; b < s.NB; b++) sum += (int64_t)(s.bounded_pending ? F : std::min(s.h_F[b], F)) * v->hop;
+  *cap = join_bound(sj.p, s.NB, sum);
+  if (*cap > INT_MAX) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join: a programme of up to %lld samples does not fit an int", (long long)*cap);
+  return PIPER_HIP_OK;
+}
+
+// What the sinks read in place of the items: one row of `cap` floats whose true length is the device int `total`.
+struct Joined {
+  const float* prog = nullptr;
+  const int* total = nullptr;
+  int64_t cap = 0;
+};
+
+// The join of slot id `slot` over `items` (the layout of s.audio: what level_audio handed out) behind the plan's graph on its stream,
+// from lengths the device holds. The report lands in the slot id's page-locked h_jrep — through its mapping where there is one, else by
+// a copy behind the launches — and is the host's once the stream has been waited for (join_landed).
+int join_items(piper_hip_voice* v, int slot, Slot& s, const float* items, Joined* out) {
+  const auto& sj = v->slot_jn[slot];
+  auto& sg = v->staging[slot];
+  int64_t cap = 0;
+  int rc = join_capacity(v, slot, s, &cap);
+  if (rc) return rc;
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
+  void* q = nullptr;
+  if (s.jn_cap < std::max<int64_t>(cap, 1)) {  // (nothing on the GPU still reads the old one: every collect ends with a wait)
+    if ((rc = plan_alloc(v, s, (size_t)std::max<int64_t>(cap, 1) * sizeof(float), &q))) return rc;
+    if (s.jn_buf) plan_free(v, s, s.jn_buf, (size_t)s.jn_cap * sizeof(float));
+    s.jn_buf = (float*)q;
+    s.jn_cap = std::max<int64_t>(cap, 1);
+  }
+  const size_t o_rep = sizeof(JoinParams), o_rows = o_rep + (size_t)kJoinReport * sizeof(int64_t);
+  const size_t o_edges = o_rows + (size_t)kJoinMaxItems * sizeof(JoinRow);
+  if (!s.jn_dev) {
+    if ((rc = plan_alloc(v, s, o_edges + (2 * (size_t)kJoinMaxItems + 1) * sizeof(int), &q))) return rc;
+    s.jn_dev = (char*)q;
+    s.jn_gen = 0;
+  }
+  const hipStream_t st = s.set.stream;
+  if (s.jn_gen != sj.gen) {
+    // (the staging buffer is rewritten only once the copy queued from it last time has run)
+    if (sg.join_ev) PH_HIP(hipEventSynchronize(sg.join_ev), PIPER_HIP_ERR_LAUNCH);
+    else PH_HIP(hipEventCreateWithFlags(&sg.join_ev, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+    if ((rc = grow_pinned(sg.h_join, sg.cap_join, 1, 1))) return rc;
+    *sg.h_join = sj.p;
+    PH_HIP(hipMemcpyAsync(s.jn_dev, sg.h_join, sizeof(JoinParams), hipMemcpyHostToDevice, st), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipEventRecord(sg.join_ev, st), PIPER_HIP_ERR_LAUNCH);
+    s.jn_gen = sj.gen;
+  }
+  if ((rc = grow_pinned(sg.h_jrep, sg.cap_jrep, (size_t)kJoinReport, (size_t)kJoinReport))) return rc;
+  int64_t* rep_host = nullptr;
+  if (hipHostGetDevicePointer((void**)&rep_host, sg.h_jrep, 0) != hipSuccess) { rep_host = nullptr; (void)hipGetLastError(); }
+  int64_t z = sj.p.tail;
+  for (int b = 0; b + 1 < s.NB; b++) z = std::max(z, sj.p.gap[b]);
+  int* edges = (int*)(s.jn_dev + o_edges);
+  const JoinSrc src{items, s.n_samples, s.lensF, F, v->hop, nullptr, nullptr};
+  PH_HIP(launch_join(st, src, s.NB, (int64_t)F * v->hop, sj.p.lead + z, (const JoinParams*)s.jn_dev, sj.p.trim != 0, edges,
+                     (JoinRow*)(s.jn_dev + o_rows), edges + 2 * kJoinMaxItems, (int64_t*)(s.jn_dev + o_rep), rep_host, s.jn_buf),
+         PIPER_HIP_ERR_LAUNCH);
+  if (!rep_host)
+    PH_HIP(hipMemcpyAsync(sg.h_jrep, s.jn_dev + o_rep, (size_t)(1 + 2 * s.NB) * sizeof(int64_t), hipMemcpyDeviceToHost, st), PIPER_HIP_ERR_LAUNCH);
+  out->prog = s.jn_buf;
+  out->total = edges + 2 * kJoinMaxItems;
+  out->cap = cap;
+  return PIPER_HIP_OK;
+}
+
+// after the slot's stream has been synchronised behind join_items: the report → h_jrep (piper_hip_voice_join_report); returns the total
+int64_t join_landed(piper_hip_voice* v, int slot, Slot& s) {
+  const auto& sg = v->staging[slot];
+  s.h_jrep.assign(sg.h_jrep, sg.h_jrep + 1 + 2 * s.NB);
+  return s.h_jrep[0];
+}
+
+// collect on a slot id with a join: the programme's floats. Up to kPinnedMax they leave through the slot id's page-locked buffer by a
+// kernel that reads the length from device memory — one synchronisation for report, lengths and samples; a longer programme waits for
+// its length first and is copied at it.
+int collect_joined(piper_hip_voice* v, int slot, Slot& s, const float* items, float* host_audio, int64_t max_samples) {
+  auto& sg = v->staging[slot];
+  int64_t cap = 0;
+  int rc = join_capacity(v, slot, s, &cap);
+  if (rc) return rc;
+  if (max_samples < cap)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)cap,
+            (long long)max_samples);
+  Joined j;
+  if ((rc = join_items(v, slot, s, items, &j))) return rc;
+  const hipStream_t st = s.set.stream;
+  float* dst_dev = nullptr;
+  if ((size_t)cap * sizeof(float) <= kPinnedMax && !is_caller_pinned(host_audio)) {
+    if (grow_pinned(sg.h_audio, sg.audio_cap, (size_t)std::max<int64_t>(cap, 1), kAudioMinCap)) (void)hipGetLastError();
+    if (sg.h_audio && hipHostGetDevicePointer((void**)&dst_dev, sg.h_audio, 0) != hipSuccess) { dst_dev = nullptr; (void)hipGetLastError(); }
+  }
+  if (dst_dev) {
+    const int blocks = (int)std::min<int64_t>(std::max<int64_t>((cap + 4 * 256 - 1) / (4 * 256), 1), 1024);
+    hipLaunchKernelGGL(copy_out_len_kernel, dim3(blocks), dim3(256), 0, st, j.prog, dst_dev, j.total, 0, 1);
+    PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
+  }
+  PH_HIP(stream_wait(st), PIPER_HIP_ERR_LAUNCH);
+  const int64_t total = join_landed(v, slot, s);
+  if (s.bounded_pending && (rc = bounded_finish(v, slot, s))) return rc;
+  if (dst_dev) {
+    memcpy(host_audio, sg.h_audio, (size_t)total * sizeof(float));
+  } else if (total > 0) {
+    PH_HIP(hipMemcpyAsync(host_audio, j.prog, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, st), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(hipStreamSynchronize(st), PIPER_HIP_ERR_LAUNCH);
+  }
+  return PIPER_HIP_OK;
+}
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
@@ -3650,6 +3792,7 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   s.loud_measured = false;  // (and so does the loudness measured there)
   s.vol_shaped = false;     // (and the items shaped from it)
   s.eq_done = false;        // (and the items EQ'd from those)
+  s.h_jrep.clear();         // (and the report of a joined collect)
   return PIPER_HIP_OK;
 }
 
@@ -3661,8 +3804,17 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
   Slot& s = *p;
   auto& sg = v->staging[slot];
   const float* audio = s.audio;  // (a slot id with a level: the limited items)
+  const bool joined = host_audio && slot >= 0 && slot < kMaxSlots && v->slot_jn[slot].on;
+  if (joined) {  // (a buffer too short for the programme is refused before anything is enqueued)
+    int64_t cap = 0;
+    if (int jrc = join_capacity(v, slot, s, &cap)) return jrc;
+    if (max_samples < cap)
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)cap,
+              (long long)max_samples);
+  }
   if (host_audio)
     if (int lrc = level_audio(v, slot, s, &audio)) return lrc;
+  if (joined) return collect_joined(v, slot, s, audio, host_audio, max_samples);  // (a slot id with a join: the programme)
   // The slot id's page-locked landing buffer of the waveform (kAudioMinCap at least). Failing to grow it is not fatal: the waveform
   // then goes to the caller's buffer directly, and the sticky error of the failed hipHostMalloc is cleared (the next launch would report it).
   if (s.bounded_pending) {
@@ -5170,11 +5322,19 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   if (NB > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: %d items (at most %d)", NB, kMaxGroup);
   const int F = (int)std::min<int64_t>(s.F, s.n_samples / hop);  // frames of a row of s.audio
   const bool bounded = s.bounded_pending;
+  // a slot id with a join: the sinks read the programme, ONE item whose length the device knows, the caller makes room for its bound
+  const bool joined = slot >= 0 && slot < kMaxSlots && v->slot_jn[slot].on;
+  int64_t jcap = 0;
+  if (joined && (rc = join_capacity(v, slot, s, &jcap))) return rc;
   // a bounded slot's lengths are still on the device: the caller makes room for the capacity, as for collect
   int64_t need = 0;
-  if (bounded) need = out_len((int64_t)F * hop) * NB;
+  if (joined) need = out_len(jcap);
+  else if (bounded) need = out_len((int64_t)F * hop) * NB;
   else for (int b = 0; b < NB; b++) need += out_len((int64_t)s.h_F[b] * hop);
   if (out.cap < need) {
+    if (joined)
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)need,
+              (long long)out.cap);
     if (bounded)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_prepared_samples before collect), got %lld",
               (long long)need, (long long)out.cap);
@@ -5191,10 +5351,31 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
     if (hipHostGetDevicePointer((void**)&peaks_host, sg.h_peaks, 0) != hipSuccess) { peaks_host = nullptr; (void)hipGetLastError(); }
   }
   PcmRoute r;
-  if ((rc = pcm_route(v, s, sg, host_pcm, elem, (size_t)need, (size_t)std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB, &r))) return rc;
+  const int64_t dev_samples = joined ? std::max(out_len(jcap), jcap) : std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB;
+  if ((rc = pcm_route(v, s, sg, host_pcm, elem, (size_t)need, (size_t)dev_samples, &r))) return rc;
   const hipStream_t q = s.set.stream;
   const float* audio = s.audio;  // (a slot id with a level: the limited items)
   if ((rc = level_audio(v, slot, s, &audio))) return rc;
+  if (joined) {
+    // The programme is one row of device-known length: the sinks take it as NB = 1, hop = 1, F = its bound, with the device's total as
+    // the length. normalize = 1 takes ONE peak, over the programme (no level and no loudness then: the joined EQ'd items).
+    Joined j;
+    if ((rc = join_items(v, slot, s, audio, &j))) return rc;
+    const int JF = (int)std::max<int64_t>(j.cap, 1);
+    if (normalize) PH_HIP(launch_pcm16_peak(q, j.prog, JF, j.total, JF, 1, 1, s.peaks), PIPER_HIP_ERR_LAUNCH);
+    if (rd)
+      PH_HIP(launch_resample_items(q, j.prog, JF, j.total, JF, 1, 1, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
+             PIPER_HIP_ERR_LAUNCH);
+    else
+      PH_HIP(launch_pcm16_pack(q, j.prog, JF, j.total, JF, 1, 1, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
+    if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
+    if ((rc = pcm_land(sg, r, q, host_pcm, elem, (size_t)need))) return rc;
+    const int64_t total = out_len(join_landed(v, slot, s));
+    if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
+    if (r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)total * elem);
+    if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + 1);
+    return PIPER_HIP_OK;
+  }
   const float* peak_src = s.audio;  // (the peak of normalize = 1 is that of the shaped, EQ'd items where there are a volume, an EQ)
   if (normalize && (rc = eq_audio(v, slot, s, &peak_src))) return rc;
   if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
@@ -5258,7 +5439,8 @@ int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper
   if ((rc = piper_hip_voice_prepare(v, u, 0)) < 0) return rc;
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
   if ((rc = collect_pcm(v, 0, params, out_rate, Sink{host, max_samples, enc}))) return rc;
-  const int64_t n = (int64_t)v->attached[0]->h_F[0] * v->hop;
+  const Slot& s0 = *v->attached[0];
+  const int64_t n = v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)s0.h_F[0] * v->hop;  // (a join: the programme's count)
   if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
   return PIPER_HIP_OK;
 }
@@ -5372,6 +5554,51 @@ PH_EXPORT int piper_hip_voice_slot_eq(piper_hip_voice* v, int slot, const piper_
     v->slot_eq[slot].eq.n = eq->n;
     for (int i = 0; i < eq->n; i++) v->slot_eq[slot].eq.section[i] = eq->section[i];
   }
+  return PIPER_HIP_OK;
+}
+
+// ---- join (include/piper_hip.h "Join")
+
+PH_EXPORT int piper_hip_voice_slot_join(piper_hip_voice* v, int slot, const piper_hip_join* join, const float* gaps, int n_gaps) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  JoinParams p{};
+  if (join)
+    if (int rc = join_build(join, gaps, n_gaps, v->cfg.sample_rate, &p)) return rc;
+  auto& sj = v->slot_jn[slot];
+  sj.on = join != nullptr;
+  sj.p = p;
+  sj.gen = ++v->join_clock;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_join_capacity(piper_hip_voice* v, int slot, int32_t out_rate, int64_t* samples) {
+  if (!v || !samples) PH_FAIL(PIPER_HIP_ERR_ARG, "join_capacity: null argument");
+  const Slot* p = slot_plan(v, slot);
+  if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
+  if (!v->slot_jn[slot].on) PH_FAIL(PIPER_HIP_ERR_ARG, "join_capacity: slot %d has no join (piper_hip_voice_slot_join)", slot);
+  int64_t cap = 0;
+  int rc = join_capacity(v, slot, *p, &cap);
+  if (rc) return rc;
+  if (out_rate != 0 && out_rate != v->cfg.sample_rate) {
+    const RsDesign* rd = nullptr;
+    if ((rc = rs_design(v->cfg.sample_rate, out_rate, &rd))) return rc;
+    cap = rs_count(*rd, cap);
+  }
+  *samples = cap;
+  return PIPER_HIP_OK;
+}
+
+PH_EXPORT int piper_hip_voice_join_report(const piper_hip_voice* v, int slot, int64_t* start, int64_t* len, int max_items, int64_t* total) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "join_report: null voice");
+  const Slot* p = slot_plan(v, slot);
+  if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
+  if (p->h_jrep.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "join_report: slot %d has not been collected with a join since its last launch", slot);
+  const int NB = (int)(p->h_jrep.size() - 1) / 2;
+  if ((start || len) && max_items < NB) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join_report: buffer holds %d < %d items", max_items, NB);
+  if (start) memcpy(start, p->h_jrep.data() + 1, (size_t)NB * sizeof(int64_t));
+  if (len) memcpy(len, p->h_jrep.data() + 1 + NB, (size_t)NB * sizeof(int64_t));
+  if (total) *total = p->h_jrep[0];
   return PIPER_HIP_OK;
 }
 
@@ -5713,7 +5940,8 @@ PH_EXPORT int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utt
   if (rc < 0) return rc;
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
   if ((rc = piper_hip_voice_collect(v, 0, host_audio, max_samples))) return rc;
-  if (n_samples) *n_samples = (int64_t)v->attached[0]->h_F[0] * v->hop;
+  const Slot& s0 = *v->attached[0];
+  if (n_samples) *n_samples = host_audio && v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)s0.h_F[0] * v->hop;
   return PIPER_HIP_OK;
 }
 

@@ -309,7 +309,34 @@ def _level(level):
     return Level(float(d), float(c), float(r))
 
 
-KEEP = object()  # level=KEEP / loudness=KEEP / eq=KEEP: leave the slot id's level / loudness / EQ as it is
+KEEP = object()  # level=KEEP / loudness=KEEP / eq=KEEP / join=KEEP: leave the slot id's level / loudness / EQ / join as it is
+
+JOIN_MAX_ITEMS = 256
+
+
+class Join(C.Structure):
+    """piper_hip_join: lead / gap / tail silences in ms, trim (0 / 1) with its linear threshold and pad, fade in ms
+    (include/piper_hip.h "Join"). Join(gap_ms=200, trim=1, trim_threshold=0.01) also works: fields left out are 0."""
+    _fields_ = [("lead_ms", C.c_float), ("gap_ms", C.c_float), ("tail_ms", C.c_float), ("trim", C.c_int32),
+                ("trim_threshold", C.c_float), ("trim_pad_ms", C.c_float), ("fade_ms", C.c_float)]
+
+    def __repr__(self):
+        return "Join(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+def _join(join, gaps=None):
+    """Join | dict (which may carry gaps=[...]) | None → (Join or None, C array of gaps or None, their number)"""
+    if join is None:
+        return None, None, 0
+    if isinstance(join, dict):
+        d = dict(join)
+        if "gaps" in d:
+            g = d.pop("gaps")
+            gaps = g if gaps is None else gaps
+        d["trim"] = int(d.get("trim", 0))
+        join = Join(**d)
+    g = [] if gaps is None else [float(x) for x in gaps]
+    return join, ((C.c_float * len(g))(*g) if g else None), len(g)
 
 EQ_LOWPASS, EQ_HIGHPASS, EQ_BANDPASS, EQ_NOTCH, EQ_PEAKING, EQ_LOWSHELF, EQ_HIGHSHELF = range(1, 8)
 EQ_MAX_SECTIONS = 4
@@ -579,6 +606,16 @@ _PROTOS = {
     "piper_hip_volume_from_f32": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_size_t, c_f32p]),
     "piper_hip_volume_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, c_vp, C.c_int64, C.c_int32, C.POINTER(c_vp), c_vp]),
     "piper_hip_voice_slot_volume": (C.c_int, [c_vp, C.c_int, C.POINTER(Volume), C.c_int]),
+    "piper_hip_join_check": (C.c_int, [C.POINTER(Join), c_f32p, C.c_int]),
+    "piper_hip_join_counts": (C.c_int, [C.POINTER(Join), C.c_int32, c_i64p, c_i64p, c_i64p, c_i64p, c_i64p]),
+    "piper_hip_join_capacity": (C.c_int, [C.POINTER(Join), c_f32p, C.c_int, C.c_int32, c_i64p, C.c_int, c_i64p]),
+    "piper_hip_join_from_f32": (C.c_int, [C.POINTER(Join), c_f32p, C.c_int, C.c_int32, c_f32p, c_i64p, c_i64p, C.c_int, c_f32p, C.c_int64,
+                                          c_i64p, c_i64p, c_i64p]),
+    "piper_hip_join_f32": (C.c_int, [c_vp, c_vp, c_i64p, c_i64p, C.c_int, C.c_int32, C.POINTER(Join), c_f32p, C.c_int, C.POINTER(c_vp),
+                                     c_i64p, c_i64p, c_i64p, c_vp]),
+    "piper_hip_voice_slot_join": (C.c_int, [c_vp, C.c_int, C.POINTER(Join), c_f32p, C.c_int]),
+    "piper_hip_voice_join_capacity": (C.c_int, [c_vp, C.c_int, C.c_int32, c_i64p]),
+    "piper_hip_voice_join_report": (C.c_int, [c_vp, C.c_int, c_i64p, c_i64p, C.c_int, c_i64p]),
     "piper_hip_eq_check": (C.c_int, [C.POINTER(Eq), C.c_int32]),
     "piper_hip_eq_design": (C.c_int, [C.POINTER(Eq), C.c_int32, c_f64p]),
     "piper_hip_eq_from_f32": (C.c_int, [C.POINTER(Eq), C.c_int32, c_f32p, C.c_size_t, c_f32p]),
@@ -940,6 +977,21 @@ class HipBackend:
         lv = _level(level)
         _check(self.lib.piper_hip_level_f32(self.ctx, _ptr(buf), n, int(rate), C.byref(lv), C.byref(p), commandBuffer))
         return DeviceBuffer(self, p.value, n, owned=out is None)
+
+    def join_f32(self, buf, item_off, item_len, rate, join, gaps=None, out=None, commandBuffer=None):
+        """Items of the device floats `buf` (item i at buf[item_off[i] … + item_len[i])) → ONE programme in device memory
+        (piper_hip_join_f32; include/piper_hip.h "Join"): trimmed, faded, with silences. buf and out may be raw device addresses (4-byte
+        alignment suffices). Returns (DeviceBuffer of `total` float32, start [n], len [n], total)."""
+        off = np.ascontiguousarray(item_off, np.int64).reshape(-1)
+        ln = np.ascontiguousarray(item_len, np.int64).reshape(-1)
+        assert off.size == ln.size
+        jn, g, ng = _join(join, gaps)
+        start, length, total = np.zeros(max(off.size, 1), np.int64), np.zeros(max(off.size, 1), np.int64), C.c_int64()
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        _check(self.lib.piper_hip_join_f32(self.ctx, _ptr(buf), off.ctypes.data_as(c_i64p), ln.ctypes.data_as(c_i64p), off.size, int(rate),
+                                           C.byref(jn), g, ng, C.byref(p), start.ctypes.data_as(c_i64p), length.ctypes.data_as(c_i64p),
+                                           C.byref(total), commandBuffer))
+        return DeviceBuffer(self, p.value, total.value, owned=out is None), start[:off.size], length[:off.size], int(total.value)
 
     def eq_f32(self, buf, rate, eq, count=None, out=None, commandBuffer=None):
         """`count` device floats sampled at `rate` → the same number of EQ'd device floats (piper_hip_eq_f32): the biquad cascade of
@@ -1392,6 +1444,46 @@ def level_step_bound(n_in):
     return _count(load_library().piper_hip_level_step_bound(int(n_in)))
 
 
+def join_check(join, gaps=None):
+    """InvalidArgument naming the field for a join outside the contract (piper_hip_join_check). Host-only."""
+    jn, g, ng = _join(join, gaps)
+    _check(load_library().piper_hip_join_check(C.byref(jn) if jn is not None else None, g, ng))
+
+
+def join_counts(join, rate):
+    """dict(lead=, gap=, tail=, pad=, fade=): the S() sample counts of the join at `rate` (piper_hip_join_counts). Host-only."""
+    jn, _g, _n = _join(join)
+    v = [C.c_int64() for _ in range(5)]
+    _check(load_library().piper_hip_join_counts(C.byref(jn), int(rate), *[C.byref(x) for x in v]))
+    return dict(zip(("lead", "gap", "tail", "pad", "fade"), (int(x.value) for x in v)))
+
+
+def join_capacity(join, rate, item_samples, gaps=None):
+    """The no-trim upper bound on the programme's samples (piper_hip_join_capacity). Host-only."""
+    jn, g, ng = _join(join, gaps)
+    n = np.ascontiguousarray(item_samples, np.int64).reshape(-1)
+    out = C.c_int64()
+    _check(load_library().piper_hip_join_capacity(C.byref(jn), g, ng, int(rate), n.ctypes.data_as(c_i64p), n.size, C.byref(out)))
+    return int(out.value)
+
+
+def join_from_f32(items, join, rate, gaps=None):
+    """The join on the host (piper_hip_join_from_f32), bit for bit what the device computes: items = a list of float32 arrays →
+    (programme, start [n], len [n], total)."""
+    arrs = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in items]
+    ln = np.array([a.size for a in arrs], np.int64)
+    off = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.int64) if arrs else np.zeros(0, np.int64)
+    x = np.concatenate(arrs + [np.zeros(1, np.float32)])
+    jn, g, ng = _join(join, gaps)
+    cap = join_capacity(jn, rate, ln, gaps)
+    y = np.empty(max(cap, 1), np.float32)
+    start, length, total = np.zeros(max(ln.size, 1), np.int64), np.zeros(max(ln.size, 1), np.int64), C.c_int64()
+    _check(load_library().piper_hip_join_from_f32(C.byref(jn), g, ng, int(rate), x.ctypes.data_as(c_f32p), off.ctypes.data_as(c_i64p),
+                                                  ln.ctypes.data_as(c_i64p), ln.size, y.ctypes.data_as(c_f32p), cap,
+                                                  start.ctypes.data_as(c_i64p), length.ctypes.data_as(c_i64p), C.byref(total)))
+    return y[:total.value], start[:ln.size], length[:ln.size], int(total.value)
+
+
 def eq_check(eq, rate):
     """InvalidArgument naming the field and the section for an EQ outside the contract at `rate` (piper_hip_eq_check). Host-only."""
     e = _eq(eq)
@@ -1664,6 +1756,7 @@ class HipRuntime:
         _check(self.lib.piper_hip_voice_create(backend.ctx, C.byref(cfg), ptr, int(on_device), C.byref(v)))
         self.voice = v
         self._keep = {}
+        self._joins = {}  # slot id → (Join, gaps) while the slot id has a join (slot_join)
         self._pinned = []
 
     def close(self):
@@ -1762,7 +1855,7 @@ class HipRuntime:
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
     def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None, volume=None,
-                   level=KEEP, loudness=KEEP, eq=KEEP, **kw):
+                   level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
         reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
         speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays.
@@ -1773,11 +1866,12 @@ class HipRuntime:
         self._slot_level(0, level)
         self._slot_loudness(0, loudness)
         self._slot_eq(0, eq)
+        self._slot_join(0, join)
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
             self._stage_volume(0, None if volume is None else [volume], [len(phonemeIDs)])
-            n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
+            n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
             out = np.empty(max(n, 1), np.float32)
             got = C.c_int64()
             _check(self.lib.piper_hip_voice_synthesize(self.voice, C.byref(u), out.ctypes.data_as(c_f32p), n, C.byref(got)))
@@ -1887,6 +1981,53 @@ class HipRuntime:
         else:
             lv = _level(level)
             _check(self.lib.piper_hip_voice_slot_level(self.voice, slot, C.byref(lv)))
+
+    def slot_join(self, slot, join, gaps=None):
+        """The join of slot id `slot`'s whole-item collects (piper_hip_voice_slot_join): a Join or a dict (gaps= may be a list of per-item
+        gaps in ms); it persists until replaced; None clears it. Every later collect* of the slot delivers ONE programme."""
+        jn, g, ng = _join(join, gaps)
+        _check(self.lib.piper_hip_voice_slot_join(self.voice, slot, C.byref(jn) if jn is not None else None, g, ng))
+        if jn is None:
+            self._joins.pop(slot, None)
+        else:
+            self._joins[slot] = (jn, [float(x) for x in g] if g is not None else None)
+
+    def _slot_join(self, slot, join):
+        if join is not KEEP:
+            self.slot_join(slot, join)
+
+    def join_capacity(self, slot, rate=None):
+        """The samples a collect* of the prepared, joined slot needs room for at `rate` (piper_hip_voice_join_capacity)."""
+        out = C.c_int64()
+        _check(self.lib.piper_hip_voice_join_capacity(self.voice, slot, 0 if rate is None else int(rate), C.byref(out)))
+        return int(out.value)
+
+    def join_report(self, slot):
+        """(start [NB], len [NB], total) of the slot's latest joined collect, at the voice's rate (piper_hip_voice_join_report)."""
+        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
+        start, length, total = np.zeros(max(nb, 1), np.int64), np.zeros(max(nb, 1), np.int64), C.c_int64()
+        _check(self.lib.piper_hip_voice_join_report(self.voice, slot, start.ctypes.data_as(c_i64p), length.ctypes.data_as(c_i64p), nb, C.byref(total)))
+        return start[:nb], length[:nb], int(total.value)
+
+    def _collect_joined(self, slot, dtype, rate, out, call):
+        """A collect* of a joined slot: room for join_capacity at `rate`, call(pointer-able array, room), then the programme's count."""
+        src = self.cfg.sample_rate
+        room = self.join_capacity(slot, rate)
+        if out is None:
+            out = np.empty(max(room, 1), dtype)
+        assert out.dtype == dtype and out.size >= room and out.flags.c_contiguous
+        call(out, room)
+        if len(self._keep[slot]) > 2 and self._keep[slot][2]:  # bounded: the true lengths are known now
+            self._keep[slot] = (self._keep[slot][0], self.prepared_samples(slot)[1], False)
+        total = self.join_report(slot)[2]
+        return out[:total if rate is None or int(rate) == src else resample_count(src, int(rate), total)]
+
+    def _one_call_room(self, n):
+        """samples of slot 0's one-item programme for an utterance of n samples (the synthesize twins)"""
+        if 0 not in self._joins:
+            return n
+        jn, g = self._joins[0]
+        return join_capacity(jn, self.cfg.sample_rate, [n], g)
 
     def slot_eq(self, slot, eq):
         """The equaliser of slot id `slot`'s whole-item collects (piper_hip_voice_slot_eq): an Eq or a list of (type, f0, q[, gain_db]);
@@ -2141,16 +2282,21 @@ class HipRuntime:
         self._pinned.append(p)
         return np.ctypeslib.as_array(C.cast(p, c_f32p), shape=(int(count),))
 
-    def collect(self, slot, want_audio=True, out=None, level=KEEP, loudness=KEEP, eq=KEEP):
+    def collect(self, slot, want_audio=True, out=None, level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP):
         """level: a Level (or tuple / dict) sets the slot id's level before the call, None clears it (slot_level); it persists.
-        loudness: the same for the slot id's loudness target (slot_loudness)."""
+        loudness: the same for the slot id's loudness target (slot_loudness). join: the same for the slot id's join (slot_join): the
+        items then leave as ONE programme (join_report(slot) afterwards)."""
         self._slot_level(slot, level)
         self._slot_loudness(slot, loudness)
         self._slot_eq(slot, eq)
+        self._slot_join(slot, join)
         n = self._keep[slot][1]
         if not want_audio:
             _check(self.lib.piper_hip_voice_collect(self.voice, slot, None, 0))
             return None
+        if slot in self._joins:
+            return self._collect_joined(slot, np.float32, None, out,
+                                        lambda o, room: _check(self.lib.piper_hip_voice_collect(self.voice, slot, o.ctypes.data_as(c_f32p), room)))
         if out is None:
             out = np.empty(max(n, 1), np.float32)
         assert out.dtype == np.float32 and out.size >= n and out.flags.c_contiguous
@@ -2160,7 +2306,7 @@ class HipRuntime:
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
-    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP, eq=KEEP):
+    def collect_pcm16(self, slot, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP):
         """collect() with 16-bit PCM converted on the device (piper_hip_voice_collect_pcm16): the items back to back at their true lengths.
         normalize=False: the samples pcm16(collect(slot)) gives; normalize=True: Piper's peak normalisation per item (peaks(slot) afterwards).
         The fp32 waveform stays in the plan: collect / collect_pcm16 may follow in any order. rate: resampled on the device to that output
@@ -2168,7 +2314,13 @@ class HipRuntime:
         self._slot_level(slot, level)
         self._slot_loudness(slot, loudness)
         self._slot_eq(slot, eq)
+        self._slot_join(slot, join)
         n = self._keep[slot][1]
+        if slot in self._joins:  # ONE programme, at `rate` resampled as one signal
+            prm = PcmParams(float(gain), int(bool(normalize)))
+            r = self.cfg.sample_rate if rate is None else int(rate)
+            return self._collect_joined(slot, np.int16, r, out, lambda o, room: _check(self.lib.piper_hip_voice_collect_pcm16_rate(
+                self.voice, slot, C.byref(prm), r, o.ctypes.data_as(c_i16p), room)))
         if rate is not None and int(rate) != self.cfg.sample_rate:  # (the voice's own rate is not a filter: the plain call)
             return self._collect_pcm16_rate(slot, gain, normalize, out, int(rate))
         if out is None:
@@ -2198,19 +2350,20 @@ class HipRuntime:
         return out[:sum(resample_count(src, rate, p) for p in per)]
 
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, rate=None, prosody=None, volume=None, level=KEEP, loudness=KEEP, eq=KEEP, **kw):
+                         normalize=False, rate=None, prosody=None, volume=None, level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP, **kw):
         """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare;
         level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
         self._slot_loudness(0, loudness)
         self._slot_eq(0, eq)
+        self._slot_join(0, join)
         pro = None if prosody is None else [prosody]
         vol = None if volume is None else [volume]
         if rate is not None and int(rate) == self.cfg.sample_rate:
             rate = None
         if durations is not None and not kw and rate is not None:  # piper_hip_voice_synthesize_pcm16_rate
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
-            n = resample_count(self.cfg.sample_rate, rate, int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
+            n = resample_count(self.cfg.sample_rate, rate, self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))))
             out = np.empty(max(n, 1), np.int16)
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
@@ -2222,7 +2375,7 @@ class HipRuntime:
             return out[:got.value]
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
-            n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
+            n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
             out = np.empty(max(n, 1), np.int16)
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
@@ -2235,14 +2388,19 @@ class HipRuntime:
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
 
-    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP, eq=KEEP):
+    def collect_g711(self, slot, law, gain=1.0, normalize=False, out=None, rate=None, level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP):
         """collect_pcm16 ending in G.711 bytes ("mulaw" / "alaw") companded on the device (piper_hip_voice_collect_g711): one uint8 per
         sample, the items back to back at J(their true samples) at `rate` (default: the voice's own). Every rule of collect_pcm16 holds."""
         self._slot_level(slot, level)
         self._slot_loudness(slot, loudness)
         self._slot_eq(slot, eq)
+        self._slot_join(slot, join)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
+        if slot in self._joins:  # ONE programme
+            prm = PcmParams(float(gain), int(bool(normalize)))
+            return self._collect_joined(slot, np.uint8, rate, out, lambda o, room: _check(self.lib.piper_hip_voice_collect_g711(
+                self.voice, slot, C.byref(prm), _law(law), rate, o.ctypes.data_as(c_u8p), room)))
         count = (lambda p: p) if rate == src else (lambda p: resample_count(src, rate, p))
         bounded = len(self._keep[slot]) > 2 and self._keep[slot][2]
         nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
@@ -2259,16 +2417,17 @@ class HipRuntime:
         return out[:sum(count(p) for p in per)]
 
     def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None, volume=None,
-                        level=KEEP, loudness=KEEP, eq=KEEP):
+                        level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP):
         """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's;
         prosody: as for prepare (with supplied durations: noise alone); level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
         self._slot_loudness(0, loudness)
         self._slot_eq(0, eq)
+        self._slot_join(0, join)
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
-        n = int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
+        n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
         if rate != src:
             n = resample_count(src, rate, n)
         out = np.empty(max(n, 1), np.uint8)
@@ -2282,11 +2441,12 @@ class HipRuntime:
         return out[:got.value]
 
     def peaks(self, slot):
-        """max |x| of each item of the slot, after a collect_pcm16(normalize=True) of its latest run."""
+        """max |x| of each item of the slot, after a collect_pcm16(normalize=True) of its latest run (a joined slot: ONE value, the
+        programme's)."""
         nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
         out = np.empty(max(nb, 1), np.float32)
         _check(self.lib.piper_hip_voice_peaks(self.voice, slot, out.ctypes.data_as(c_f32p), nb))
-        return out[:nb]
+        return out[:1 if slot in self._joins else nb]
 
     def tap(self, slot, name, max_floats=None):
         """A named intermediate of the slot, items back to back at their true lengths (max_floats None: sized by the library).

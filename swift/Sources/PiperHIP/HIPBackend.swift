@@ -384,6 +384,49 @@ public final class HIPBackend {
         return rows.prefix(Int(max(0, min(eq.n, PIPER_HIP_EQ_MAX_SECTIONS)))).map { [$0.0, $0.1, $0.2, $0.3, $0.4] }
     }
 
+    // ---- join (include/piper_hip.h "Join") ----
+
+    /// Items of device floats (item i at input[itemOff[i] ..< itemOff[i] + itemLen[i]]) → ONE programme in device memory
+    /// (piper_hip_join_f32): trimmed, faded, with silences; bit for bit the host twin. Waits for the device: the report is its answer.
+    public func joinF32(input: HIPBuffer, itemOff: [Int64], itemLen: [Int64], rate: Int32, join: piper_hip_join, gaps: [Float] = [],
+                        commandBuffer: Stream? = nil) throws -> (out: HIPBuffer, start: [Int64], len: [Int64], total: Int64) {
+        var out: UnsafeMutablePointer<Float>? = nil
+        var j = join
+        var start = [Int64](repeating: 0, count: itemOff.count), len = [Int64](repeating: 0, count: itemOff.count)
+        var total: Int64 = 0
+        try Self.check(piper_hip_join_f32(ctx, input.f32, itemOff, itemLen, Int32(itemOff.count), rate, &j, gaps.isEmpty ? nil : gaps,
+                                          Int32(gaps.count), &out, &start, &len, &total, commandBuffer))
+        return (HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx), start, len, total)
+    }
+
+    /// The join on the host (piper_hip_join_from_f32), bit for bit what the device computes.
+    public static func joinFromF32(_ x: [Float], itemOff: [Int64], itemLen: [Int64], rate: Int32, join: piper_hip_join,
+                                   gaps: [Float] = []) throws -> (programme: [Float], start: [Int64], len: [Int64]) {
+        var j = join
+        var cap: Int64 = 0
+        try check(piper_hip_join_capacity(&j, gaps.isEmpty ? nil : gaps, Int32(gaps.count), rate, itemLen, Int32(itemLen.count), &cap))
+        var y = [Float](repeating: 0, count: Int(max(cap, 1)))
+        var start = [Int64](repeating: 0, count: itemOff.count), len = [Int64](repeating: 0, count: itemOff.count)
+        var total: Int64 = 0
+        try check(piper_hip_join_from_f32(&j, gaps.isEmpty ? nil : gaps, Int32(gaps.count), rate, x, itemOff, itemLen, Int32(itemOff.count), &y, cap,
+                                          &start, &len, &total))
+        return (Array(y.prefix(Int(total))), start, len)
+    }
+
+    /// InvalidArgument naming the field for a join outside the contract (piper_hip_join_check; host-only).
+    public static func joinCheck(_ join: piper_hip_join, gaps: [Float] = []) throws {
+        var j = join
+        try check(piper_hip_join_check(&j, gaps.isEmpty ? nil : gaps, Int32(gaps.count)))
+    }
+
+    /// The S() sample counts of the join at `rate` (piper_hip_join_counts; host-only).
+    public static func joinCounts(_ join: piper_hip_join, rate: Int32) throws -> (lead: Int64, gap: Int64, tail: Int64, pad: Int64, fade: Int64) {
+        var j = join
+        var c: (Int64, Int64, Int64, Int64, Int64) = (0, 0, 0, 0, 0)
+        try check(piper_hip_join_counts(&j, rate, &c.0, &c.1, &c.2, &c.3, &c.4))
+        return c
+    }
+
     // ---- binary with NumPy broadcasting, output rank ≤ 4 (MetalBackend.swift:2099-2134, 2592-2610) ----
     private func binaryBroadcastF32(_ op: piper_hip_binary_op, a: HIPBuffer, aShape: [Int], b: HIPBuffer, bShape: [Int],
                                     commandBuffer: Stream?) throws -> (out: HIPBuffer, outShape: [Int]) {

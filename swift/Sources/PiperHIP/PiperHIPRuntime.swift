@@ -503,6 +503,33 @@ public final class PiperHIPRuntime {
         return (Array(lufs[0..<n]), Array(gain[0..<n]))
     }
 
+    /// The join of slot id `slot`'s whole-item collects (piper_hip_voice_slot_join): it persists until replaced; nil clears it. Every
+    /// later collect* and synthesize* on the slot id delivers ONE programme: the items trimmed, faded and separated by silences.
+    public func slotJoin(slot: Int32, join: piper_hip_join?, gaps: [Float] = []) throws {
+        if var j = join {
+            try HIPBackend.check(piper_hip_voice_slot_join(voice, slot, &j, gaps.isEmpty ? nil : gaps, Int32(gaps.count)))
+        } else {
+            try HIPBackend.check(piper_hip_voice_slot_join(voice, slot, nil, nil, 0))
+        }
+    }
+
+    /// The samples a collect* of the prepared, joined slot needs room for at `outRate` (0: the voice's own) (piper_hip_voice_join_capacity).
+    public func joinCapacity(slot: Int32, outRate: Int32 = 0) throws -> Int64 {
+        var n: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_join_capacity(voice, slot, outRate, &n))
+        return n
+    }
+
+    /// Where each item starts in the programme of the slot's latest joined collect, how long it is, and the total, at the voice's rate
+    /// (piper_hip_voice_join_report).
+    public func joinReport(slot: Int32) throws -> (start: [Int64], len: [Int64], total: Int64) {
+        let nb = Int(piper_hip_voice_batch_size(voice, slot))
+        var start = [Int64](repeating: 0, count: max(nb, 1)), len = [Int64](repeating: 0, count: max(nb, 1))
+        var total: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_join_report(voice, slot, &start, &len, Int32(nb), &total))
+        return (Array(start.prefix(nb)), Array(len.prefix(nb)), total)
+    }
+
     /// The EQ of the stream on `slot` (piper_hip_voice_stream_set_eq): where streamSetLevel is allowed, in either order with it.
     public func streamSetEq(slot: Int32, eq: piper_hip_eq) throws {
         var e = eq
