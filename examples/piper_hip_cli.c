@@ -35,6 +35,11 @@
  *                            around them and --trim-silence THRESHOLD[:PAD_MS[:FADE_MS]] cutting each sentence's quiet head and tail
  *                            (linear amplitude; the cut edges fade). Any of the four flags joins a single list too. Each sentence's
  *                            start in the programme is printed on stderr. One list without these flags behaves as before.
+ *                            --pitch ST[/ST…]: a shift in semitones (−12 … 12) for every sentence, or one per sentence, applied on the
+ *                            device behind the volume and in front of the EQ and every output above (piper_hip_voice_slot_pitch on
+ *                            slot 0). The tempo is kept: the predicted durations are scaled so that the sentence keeps its length (so
+ *                            this needs --predict, or a real voice); --pitch-varispeed turns that off: the sentence comes out 1/ρ as
+ *                            long, with pinned durations too.
  *   --speaker N              both modes: speaker N of a multi-speaker voice (the graph's `sid`; piper_hip_voice_attach_speakers +
  *                            piper_hip_voice_slot_speakers). With --model the file's speaker table is loaded (opt-in: without the flag such a
  *                            file is refused; its node graph is NOT verified — no verifier for the conditioned graph exists yet); without
@@ -108,7 +113,14 @@ typedef struct {
   float* audio;
   int64_t audio_cap;
   float* id_gain; /* --id-volume: one gain per id of the utterance, NULL without the flag */
+  piper_hip_pitch pitch[PIPER_HIP_JOIN_MAX_ITEMS]; /* --pitch: one per sentence */
+  int n_pitch;                                     /* 0 without the flag */
 } runner;
+
+/* --pitch: the pitch of the staging call that follows (the assignment is that call's alone, so it is made before each) */
+static int stage_pitch(runner* r) {
+  return r->n_pitch ? piper_hip_voice_slot_pitch(r->voice, 0, r->pitch, r->n_pitch) : 0;
+}
 
 /* --id-volume: the volume of the staging call that follows (the assignment is that call's alone, so it is made before each) */
 static int stage_volume(runner* r, int t) {
@@ -152,11 +164,12 @@ static int run_one(runner* r, const int64_t* ids, int t, int64_t* samples) {
     u.durations = dur;
   }
   int rc = stage_volume(r, t);
+  if (rc >= 0) rc = stage_pitch(r);
   if (rc >= 0) rc = piper_hip_voice_prepare(r->voice, &u, 0);
   free(dur);
   if (rc < 0) return rc;
   int64_t n = 0;
-  if ((rc = piper_hip_voice_prepared_samples(r->voice, 0, NULL, 0, &n)) < 0) return rc;
+  if ((rc = piper_hip_voice_pitch_samples(r->voice, 0, NULL, 0, &n)) < 0) return rc; /* (without a pitch: prepared_samples) */
   if (n > r->audio_cap) {
     free(r->audio);
     r->audio = (float*)malloc(sizeof(float) * (size_t)n);
@@ -183,7 +196,8 @@ static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_p
   int rc;
   int64_t cap = 0;
   *pcm = NULL;
-  if (!ran && !r->predict) {
+  int32_t* pinned = NULL;
+  if (!ran && !r->predict && !r->n_pitch) {
     int32_t* dur = (int32_t*)malloc(sizeof(int32_t) * (size_t)t);
     for (int i = 0; i < t; i++) dur[i] = r->pin_frames;
     u.durations = dur;
@@ -197,8 +211,17 @@ static int run_one_pcm16(runner* r, const int64_t* ids, int t, const piper_hip_p
     free(dur);
     return rc;
   }
-  if (!ran && ((rc = stage_volume(r, t)) < 0 || (rc = piper_hip_voice_prepare(r->voice, &u, 0)) < 0)) return rc;
-  if ((rc = piper_hip_voice_prepared_samples(r->voice, 0, NULL, 0, &cap)) < 0) return rc;
+  if (!ran && !r->predict) { /* a pitch: the length is the library's to say, so the slot is prepared and asked */
+    pinned = (int32_t*)malloc(sizeof(int32_t) * (size_t)t);
+    for (int i = 0; i < t; i++) pinned[i] = r->pin_frames;
+    u.durations = pinned;
+  }
+  rc = ran ? 0 : stage_volume(r, t);
+  if (!ran && rc >= 0) rc = stage_pitch(r);
+  if (!ran && rc >= 0) rc = piper_hip_voice_prepare(r->voice, &u, 0);
+  free(pinned);
+  if (rc < 0) return rc;
+  if ((rc = piper_hip_voice_pitch_samples(r->voice, 0, NULL, 0, &cap)) < 0) return rc;
   if (rate != in_rate && (cap = piper_hip_resample_count(in_rate, rate, cap)) < 0) return (int)cap;
   *pcm = malloc(elem * (size_t)(cap > 0 ? cap : 1));
   if (!ran && (rc = piper_hip_voice_launch(r->voice, 0)) < 0) return rc;
@@ -231,6 +254,7 @@ static int run_programme(runner* r, const int64_t* ids, const int* off, const in
     u[i].durations = dur;
   }
   rc = piper_hip_voice_slot_join(r->voice, 0, join, NULL, 0);
+  if (rc >= 0) rc = stage_pitch(r);
   if (rc >= 0) rc = piper_hip_voice_prepare_batch(r->voice, u, n_lists, 0);
   free(dur);
   if (rc < 0) return rc;
@@ -284,6 +308,7 @@ int main(int argc, char** argv) {
                     "                [--output-encoding s16le|mulaw|alaw] [--drive X] [--ceiling Y] [--release-ms Z]\n"
                     "                [--loudness LUFS [--max-gain-db X]] [--id-volume I:J=G[,I:J=G...]] [--eq TYPE:F0:Q[:GAIN_DB] ...]\n"
                     "                [--phoneme-ids A/B/... --sentence-silence SECONDS --lead-ms X --tail-ms X --trim-silence THRESHOLD[:PAD_MS[:FADE_MS]]]\n"
+                    "                [--pitch ST[/ST...] [--pitch-varispeed]]\n"
                     "       common: [--model voice.onnx [--config voice.onnx.json]] [--quality medium|high|low|x_low] [--predict] [--pin-frames N]\n"
                     "               [--speaker N [--speakers S]]\n", argv[0], argv[0]);
     return 2;
@@ -448,6 +473,26 @@ int main(int argc, char** argv) {
         piper_hip_destroy(ctx);
         return 2;
       }
+    }
+    const char* pitch_arg = arg_value(argc, argv, "--pitch");
+    if (pitch_arg) { /* one shift for every sentence, or one per sentence; the tempo kept unless --pitch-varispeed */
+      const int keep = !has_flag(argc, argv, "--pitch-varispeed");
+      int k = 0, bad = 0;
+      for (const char* s = pitch_arg; !bad;) {
+        char* end = NULL;
+        const float st = strtof(s, &end);
+        if (end == s || k == PIPER_HIP_JOIN_MAX_ITEMS) { bad = 1; break; }
+        r.pitch[k].semitones = st; r.pitch[k].keep_tempo = keep;
+        k++;
+        if (*end == '/') s = end + 1;
+        else { bad = *end != 0; break; }
+      }
+      if (!bad && k != 1 && k != n_lists) bad = 1;
+      if (bad) { fprintf(stderr, "--pitch %s: expected ST or ST/ST/... with one value per sentence (%d)\n", pitch_arg, n_lists); return 2; }
+      for (; k < n_lists; k++) r.pitch[k] = r.pitch[0];
+      r.n_pitch = n_lists;
+      for (int i = 0; i < r.n_pitch; i++)
+        if (piper_hip_pitch_check(&r.pitch[i]) < 0) { fprintf(stderr, "--pitch %s: %s\n", pitch_arg, piper_hip_last_error()); return 2; }
     }
     const char* sil_arg = arg_value(argc, argv, "--sentence-silence");
     const char* trim_arg = arg_value(argc, argv, "--trim-silence");

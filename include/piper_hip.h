@@ -1068,6 +1068,72 @@ int piper_hip_voice_slot_join(piper_hip_voice* v, int slot, const piper_hip_join
 int piper_hip_voice_join_capacity(piper_hip_voice* v, int slot, int32_t out_rate, int64_t* samples);
 int piper_hip_voice_join_report(const piper_hip_voice* v, int slot, int64_t* start, int64_t* len, int max_items, int64_t* total);
 
+/* ---- Pitch: per-item semitone shift on the device, on whole-item routes (DESIGN.md §4 "Pitch") ----
+ * SSML <prosody pitch>, the `pitch` field of a speech API's audio config: the one control of a TTS front end that a host had to apply
+ * with a tool of its own, floats down, behind the device's whole output chain. An engine that owns the durations needs no overlap-add
+ * and no search: to raise the pitch by ρ = 2^(st/12) it synthesises ρ times slower (length_scale, on the device already) and plays the
+ * result ρ times faster. The only new arithmetic is a variable-ratio resampler, one more stage of the whole-item output chain —
+ * generator → volume → pitch → EQ → loudness gain → level → join → resampler → PCM / G.711 — which changes nothing for a request that
+ * does not ask for it. Formants move with the pitch (this is not a formant-preserving shift). The stage is a contract, bit for bit:
+ *   parameters semitones is a finite float in [−12, 12]; keep_tempo is 0 or 1. Anything else is PIPER_HIP_ERR_ARG with a message that names
+ *              the field.
+ *   step       ρ = exp2((double)semitones / 12.0).  Q = (uint64) floor(ρ·2^32 + 0.5), a 32.32 fixed-point step in [2^31, 2^33].
+ *              ρq = Q / 2^32, exact in double. Q == 2^32 is not a filter (semitones ±0 and anything that rounds there): the item passes
+ *              bit for bit and N' = N.
+ *   count      N' = ceil(N·2^32 / Q), for N < 2^30, in 64-bit integers.
+ *   positions  output j reads input position u = j·Q (uint64): n = u >> 32, frac = u & 0xffffffff. p = frac >> 25 (128 phases).
+ *              α = (float)((frac >> 1) & 0xffffff) · 2^−24, which is exact.
+ *   filter     designed in double, once per Q. P = 2·((24·max(Q, 2^32) + 2^32 − 1) >> 32) taps: 48 for ρ ≤ 1, up to 96 at +12 semitones.
+ *              fc = 0.93·min(1, 1/ρq). Rows p = 0 … 128 inclusive, taps t = 0 … P − 1: tau = t − (P/2 − 1) − p/128, h = fc·sinc(fc·tau),
+ *              times the Kaiser window of "Output rate" (β = 9, half-width P/2, 0 for |tau| ≥ P/2). Every row is divided by its own sum
+ *              in double and rounded once to fp32: the table c[129][P], at most 49 536 bytes.
+ *   sample     y0 = Σ_t c[p][t]·x[n − (P/2 − 1) + t], y1 the same sum with c[p + 1]; x reads as 0 outside [0, N). Both sums are accumulated
+ *              in fp32 in ascending t from 0.0f, each product rounded, then each sum (no FMA).  y[j] = fl(y0 + fl(α·fl(y1 − y0))).
+ *   voice      the pitched item of a slot has F' = ceil(N' / hop) frames; samples [N', F'·hop) are +0.0f, a tail of less than one hop
+ *              (under 12 ms). So every later stage keeps its interface: rows of frames × hop, lengths in frames on the device.
+ *   tempo      rf = (float)ρq. keep_tempo = 1: the staging call uses length_scale' = fl(ls·rf) for that item, ls = the utterance's
+ *              length_scale with 0 taken as 1.0; nothing else changes — the prosody rule and a bounded route's max_frames see the frames
+ *              the model actually generates. keep_tempo = 1 on an item with supplied durations is PIPER_HIP_ERR_ARG: the caller owns
+ *              those. keep_tempo = 0 is plain varispeed: the item comes out 1/ρ as long.
+ *   chain      volume shapes the un-pitched frames it was computed for; every stage after the pitch sees the pitched items: the EQ, the
+ *              loudness measurement and piper_hip_voice_loudness, the limiter, the peaks of normalize = 1 and piper_hip_voice_peaks, the
+ *              join with join_report and join_capacity, the resampler, PCM and G.711.
+ * One second of a 0.5 sine at 200, 1000 and 4000 Hz (22 050 Hz), shifted by −12 … +12 semitones, comes out at f·ρq with an SNR of
+ * 92 … 114 dB against the ideal sine and a gain within 2e-5 of 1.
+ * Streams have no pitch: stream_begin, stream_begin_batch and stream_pool_join* with a pitch pending on their slot return
+ * PIPER_HIP_ERR_UNSUPPORTED, stage nothing and clear the pitch. */
+typedef struct {
+  float semitones;      /* finite, in [−12, 12] */
+  int32_t keep_tempo;   /* 1: scale the predicted durations by ρ so that the item keeps its length; 0: varispeed */
+} piper_hip_pitch;      /* 8 bytes */
+/* Host-only (no device needed). pitch_check: the rules above. pitch_info: Q, P and rf of a shift (any output pointer may be NULL).
+ * pitch_count: N' for n_in in [0, 2^30), a negative status code otherwise. pitch_taps: the [129][P] table (a shorter buffer is
+ * PIPER_HIP_ERR_SHAPE); it exists for Q == 2^32 as well, where no route applies it. pitch_from_f32: the host twin of the kernel: n host
+ * floats → N' host floats in y[max_out] (a shorter y is PIPER_HIP_ERR_SHAPE and nothing is written); *n_out receives N'. */
+int piper_hip_pitch_check(const piper_hip_pitch* pitch);
+int piper_hip_pitch_info(float semitones, uint64_t* step, int32_t* taps, float* length_factor);
+int64_t piper_hip_pitch_count(float semitones, int64_t n_in);
+int piper_hip_pitch_taps(float semitones, float* table, size_t max_floats);
+int piper_hip_pitch_from_f32(float semitones, const float* x, size_t n, float* y, size_t max_out, size_t* n_out);
+/* Per-op: `count` device floats (below 2^30) → N' device floats, no padding. `*out` convention of the other ops; *out_count receives N';
+ * count may be 0; the pointers need no alignment beyond a float's. */
+int piper_hip_pitch_f32(piper_hip_ctx* ctx, const float* x, size_t count, float semitones, float** out, size_t* out_count,
+                        piper_hip_stream stream);
+/* The pitch of the NEXT staging call on slot id `slot`, with the lifecycle of piper_hip_voice_slot_prosody and slot_volume: entry i is
+ * for item i, items past `n` have none; n = 0 clears the assignment; n outside 0 … 256 is PIPER_HIP_ERR_ARG; every entry is checked here
+ * on the host, with a message that names the entry and the field (a refusal leaves the assignment in place as it was). The staging calls
+ * prepare, prepare_batch, prepare_batch_bounded and synthesize* (slot 0) take the assignment and clear it, whether or not they succeed.
+ * An entry that resolves to Q == 2^32 with keep_tempo 0 is no pitch; if no item has one, the plan carries no pitch and launches nothing
+ * new. Every later collect, collect_pcm16, collect_pcm16_rate and collect_g711 of that staging delivers the pitched items, on plain,
+ * ragged and bounded slots; on bounded slots the lengths are read from device memory and nothing new waits for the GPU. The tables live
+ * in the plan's device memory, one per distinct Q of the batch, uploaded by the staging call. prepared_samples, durations,
+ * prosody_report, the `audio` tap and the plan's fp32 audio stay raw.
+ * pitch_samples: the samples every item of the prepared slot delivers at the voice's rate, F'·hop (per_item [max_items] ≥ the batch
+ * size, optional), and their sum; on a bounded slot the capacity before collect and the true values after it. Collect buffers are
+ * checked against it. Without a pitch it reports what prepared_samples reports. */
+int piper_hip_voice_slot_pitch(piper_hip_voice* v, int slot, const piper_hip_pitch* items, int n);
+int piper_hip_voice_pitch_samples(piper_hip_voice* v, int slot, int64_t* per_item, int max_items, int64_t* total);
+
 /* ---- Multi-speaker voices: speaker-conditioned synthesis (DESIGN.md §4 "Speakers") ----
  * A multi-speaker Piper voice carries a speaker table `emb_g` [S, gin] and three kinds of k = 1 `cond` convs over g = emb_g[sid] [gin, 1]
  * (the graph's `sid` input, read by PiperMetalRuntime.synthesize next to `scales`, PiperMetalRuntime.swift:62-80; in the graph a Gather

@@ -26,6 +26,7 @@
 #include "conv_win.h"
 #include "eq.h"
 #include "join.h"
+#include "pitch.h"
 #include "level.h"
 #include "loudness.h"
 #include "volume.h"
@@ -439,6 +440,21 @@ struct Slot {
   char* jn_dev = nullptr;        // JoinParams | report [kJoinReport] | rows [kJoinMaxItems] | edges [2·kJoinMaxItems], total
   uint64_t jn_gen = 0;           // the slot_join call whose params jn_dev holds (0: none)
   std::vector<int64_t> h_jrep;   // {total, start[NB], len[NB]} of the latest joined collect (empty: none since the last launch)
+  // Pitch (piper_hip_voice_slot_pitch): device buffers of this plan (in `owned`), allocated on first use
+  bool pt_on = false;            // the plan's latest staging carried a pitch: pt_q holds the items' steps, pt_dev their tables
+  std::vector<uint64_t> pt_q;    // [NB] the 32.32 step per item (kPtOne: the item has no pitch)
+  uint64_t pt_qmin = kPtOne, pt_qmax = kPtOne;  // over the batch, items without a pitch included
+  int pt_pmax = 0;               // the most taps of the batch
+  char* pt_dev = nullptr;        // PtItem [NB] | the [129][P] tables, one per distinct step of the batch
+  size_t pt_dev_cap = 0;         // bytes
+  float* pitched = nullptr;      // [NB][F'cap·hop] the pitched items, each zero from N' up to its F'·hop
+  size_t pt_cap = 0;             // floats
+  int* pt_lensF = nullptr;       // [NB] F' per item, as the kernel wrote them
+  bool pt_done = false;          // pitched holds the latest launch (cleared where h_peaks is)
+  // The row (samples, frames) the buffers of the stages behind the pitch — eqd, eq_work, gained, loud_seg, lim, lim_scratch — were
+  // allocated for: a staging with a lower pitch makes longer rows, and pitch_audio then gives them back to be allocated again.
+  int64_t chain_row = 0;
+  int chain_F = 0;
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
@@ -594,6 +610,8 @@ struct piper_hip_voice {
     hipEvent_t join_ev = nullptr;  // recorded behind the latest copy from h_join
     int64_t* h_jrep = nullptr;     // the report of a joined collect: written by the plan kernel through the mapping, or by a D2H behind it
     size_t cap_jrep = 0;
+    char* h_pt = nullptr;          // the PtItem table and the filter tables of a prepare with a pitch, as they go to the plan's pt_dev
+    size_t cap_pt = 0;
   } staging[kMaxSlots];
   // The prosody of a slot id's NEXT staging call (piper_hip_voice_slot_prosody): owned copies of the caller's arrays, an empty array = the
   // field was NULL. The staging call takes the assignment (take_prosody) whether or not it succeeds.
@@ -610,6 +628,8 @@ struct piper_hip_voice {
     int t = 0;
   };
   std::vector<Volume> slot_vol[kMaxSlots];
+  // The pitch of a slot id's NEXT staging call (piper_hip_voice_slot_pitch), with the same lifecycle; checked when it was given.
+  std::vector<piper_hip_pitch> slot_pt[kMaxSlots];
   // Speaker table of a multi-speaker voice (piper_hip_voice_attach_speakers; spk.S == 0: none): the device tables of speaker.hip, where an
   // item's speaker row keeps the dp.pre rows [0, spk_dp_rows), the flow's from there and the conv_pre rows from spk_pre_off, and each
   // slot id's assignment (empty: speaker 0 alone; items past the end take the last entry).
@@ -2516,6 +2536,23 @@ PH_EXPORT int piper_hip_voice_slot_volume(piper_hip_voice* v, int slot, const pi
   return PIPER_HIP_OK;
 }
 
+// ---- pitch (piper_hip.h "Pitch") ---------------------------------------------------------------------------------------------------
+PH_EXPORT int piper_hip_voice_slot_pitch(piper_hip_voice* v, int slot, const piper_hip_pitch* items, int n) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
+  if (n < 0 || n > 256 || (n > 0 && !items)) PH_FAIL(PIPER_HIP_ERR_ARG, "voice_slot_pitch: %d entries (0 … 256)", n);
+  for (int i = 0; i < n; i++) {  // (the assignment in place stays on a refusal)
+    char who[48];
+    snprintf(who, sizeof who, "voice_slot_pitch: entry %d", i);
+    uint64_t Q;
+    if (int rc = pt_step(who, items[i].semitones, &Q)) return rc;
+    if (items[i].keep_tempo != 0 && items[i].keep_tempo != 1)
+      PH_FAIL(PIPER_HIP_ERR_ARG, "voice_slot_pitch: entry %d: keep_tempo %d (0 or 1)", i, items[i].keep_tempo);
+  }
+  v->slot_pt[slot].assign(items, items + n);
+  return PIPER_HIP_OK;
+}
+
 PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16)
@@ -2629,6 +2666,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
     if (sg.h_spk) (void)hipHostFree(sg.h_spk);
     if (sg.h_pro) (void)hipHostFree(sg.h_pro);
     if (sg.h_vol) (void)hipHostFree(sg.h_vol);
+    if (sg.h_pt) (void)hipHostFree(sg.h_pt);
     if (sg.h_vstep) (void)hipHostFree(sg.h_vstep);
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
@@ -2902,6 +2940,45 @@ int check_volume(const VolumeItems& vol, const piper_hip_utterance* utts, int n)
 // the caller has synchronised: the previous request's copy is done). A request without: the plan has none.
 int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, int n, int T, hipStream_t q);
 
+// ---- pitch (piper_hip.h "Pitch") ----
+using PitchItems = std::vector<piper_hip_pitch>;
+// A staging call takes the slot id's assignment, whether or not it goes on to succeed.
+PitchItems take_pitch(piper_hip_voice* v, int slot) {
+  PitchItems p;
+  if (v && slot >= 0 && slot < kMaxSlots) p.swap(v->slot_pt[slot]);
+  return p;
+}
+struct PitchClear {
+  piper_hip_voice* v;
+  int slot;
+  ~PitchClear() { (void)take_pitch(v, slot); }
+};
+// Streams have no pitch: a stream's staging call with one pending on its slot id refuses, stages nothing and clears it.
+int refuse_pitch(piper_hip_voice* v, int slot, const char* who) {
+  if (take_pitch(v, slot).empty()) return PIPER_HIP_OK;
+  PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "%s: slot %d has a pitch pending (piper_hip_voice_slot_pitch), and streams have no pitch: it has been cleared", who, slot);
+}
+// What a staging call checks before it stages anything, and the tempo: `tempo` receives the utterances with length_scale' = fl(ls·rf)
+// on the items that keep theirs (it stays empty where no item does).
+int check_pitch(const PitchItems& pit, const piper_hip_utterance* utts, int n, std::vector<piper_hip_utterance>* tempo) {
+  for (int b = 0; b < n && b < (int)pit.size(); b++) {
+    if (!pit[b].keep_tempo) continue;
+    if (utts[b].durations)
+      PH_FAIL(PIPER_HIP_ERR_ARG, "utterance %d: durations are supplied, so keep_tempo of its pitch does not apply (the caller owns those durations)", b);
+    uint64_t Q;
+    if (int rc = pt_step("pitch", pit[b].semitones, &Q)) return rc;
+    if (tempo->empty()) tempo->assign(utts, utts + n);
+    const float rf = (float)((double)Q / 4294967296.0);
+    const float ls = utts[b].length_scale == 0.0f ? 1.0f : utts[b].length_scale;
+    (*tempo)[b].length_scale = ls * rf;
+  }
+  return PIPER_HIP_OK;
+}
+// The steps and tables of a request with a pitch → the plan's pt_dev, from the slot id's page-locked staging on the plan's stream (which
+// the caller has synchronised: the previous request's copy is done). A request without, or whose entries are all neutral: the plan has none.
+int stage_pitch(piper_hip_voice* v, int slot, Slot& s, const PitchItems& pit, int n, hipStream_t q);
+int pitch_frames(const piper_hip_voice* v, const Slot& s, int b, int frames);
+
 // predict_impl on the predictor plan of requests with prosody (pro non-null), its per-id inputs staged with the ids
 int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
                      const piper_hip_speaker* speakers, const ProsodyItems* pro);
@@ -2910,6 +2987,7 @@ int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n,
 PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot) {
   const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
   const VolumeItems vol = take_volume(v, slot);    // (piper_hip_voice_slot_volume)
+  const PitchItems pit = take_pitch(v, slot);      // (piper_hip_voice_slot_pitch)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
@@ -2919,6 +2997,9 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   std::vector<int> hT(n), hF(n);
   const bool has_pro = !pro.empty();  // the request runs the plans of requests with prosody
   if ((rc = check_prosody(pro, utts, n, false)) || (rc = check_volume(vol, utts, n))) return rc;
+  std::vector<piper_hip_utterance> tempo;  // the utterances at length_scale' where a pitch keeps the tempo
+  if ((rc = check_pitch(pit, utts, n, &tempo))) return rc;
+  if (!tempo.empty()) utts = tempo.data();
   std::vector<int64_t> wanted(n, -1);  // Σ d of the frame rule per item (there is no fitting on this route)
   // utterances without durations: run the text encoder + duration predictor first (its own cached plan), then continue with
   // the predicted frames per id exactly as if the caller had supplied them
@@ -3011,7 +3092,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     return rc;
   unsigned* p_rng = (unsigned*)sg.h_misc;
   float* p_ns = (float*)(p_rng + 2 * (size_t)n);
-  if ((rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q))) return rc;
+  if ((rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q)) || (rc = stage_pitch(v, slot, s, pit, n, q))) return rc;
   if (s.pro) {  // the noise multiplier per id, a plan input like the ids (no fitting on this route)
     if ((rc = grow_pinned(sg.h_pro, sg.cap_pro, (size_t)n * T + n))) return rc;
     pack_prosody(pro, n, T, nullptr, nullptr, nullptr, (float*)sg.h_pro, nullptr);
@@ -3145,11 +3226,15 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
   const bool has_pro = !pro.empty();
   const VolumeItems vol = take_volume(v, slot);  // (piper_hip_voice_slot_volume)
+  const PitchItems pit = take_pitch(v, slot);    // (piper_hip_voice_slot_pitch)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   int Tmax = 0, rc;
   if ((rc = bounded_refusals(v, utts, n, slot, max_frames, false))) return rc;
   for (int b = 0; b < n; b++) Tmax = std::max(Tmax, utts[b].t);
   if ((rc = check_prosody(pro, utts, n, true)) || (rc = check_volume(vol, utts, n))) return rc;
+  std::vector<piper_hip_utterance> tempo;  // the utterances at length_scale' where a pitch keeps the tempo
+  if ((rc = check_pitch(pit, utts, n, &tempo))) return rc;
+  if (!tempo.empty()) utts = tempo.data();
   const int T = bucket_t(Tmax), F = bucket_f(max_frames), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
@@ -3193,7 +3278,9 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
     sg.h_res[b] = -1;
   }
   const hipStream_t q = s.set.stream;
-  if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q))) return rc;
+  if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q)) ||
+      (rc = stage_pitch(v, slot, s, pit, n, q)))
+    return rc;
   if (has_pro) {  // the per-id arrays: plan inputs of the predictor plan (length, floor, ceiling) and of this one (noise, fit)
     const size_t nT = (size_t)n * T;
     float* h_len = (float*)sg.h_pro;
@@ -3399,6 +3486,20 @@ PH_EXPORT int piper_hip_voice_prepared_samples(const piper_hip_voice* v, int slo
   return PIPER_HIP_OK;
 }
 
+PH_EXPORT int piper_hip_voice_pitch_samples(piper_hip_voice* v, int slot, int64_t* per_item, int max_items, int64_t* total) {
+  if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
+  const Slot* p = slot_plan(v, slot);
+  if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
+  int64_t sum = 0;
+  for (int b = 0; b < p->NB; b++) {  // (a bounded slot before collect: h_F is the capacity)
+    const int64_t nb = (int64_t)pitch_frames(v, *p, b, p->h_F[b]) * v->hop;
+    if (per_item && b < max_items) per_item[b] = nb;
+    sum += nb;
+  }
+  if (total) *total = sum;
+  return PIPER_HIP_OK;
+}
+
 PH_EXPORT int piper_hip_voice_durations(const piper_hip_voice* v, int slot, int32_t* out, int max_entries, int* n_entries) {
   const Slot* p = slot_plan(v, slot);
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
@@ -3520,14 +3621,138 @@ int volume_audio(piper_hip_voice* v, Slot& s, const float** audio) {
   return PIPER_HIP_OK;
 }
 
-// What the stages behind the EQ read for a slot id's items: volume_audio's, or — the slot id has an EQ (piper_hip_voice_slot_eq) — eqd
-// [NB][n_samples], computed here behind the plan's graph on its stream from lengths the device holds (plain, ragged and bounded slots
-// alike), once per launch and EQ. Whenever the EQ the chain reads through changes, the loudness measured behind it is dropped.
-int eq_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
+int stage_pitch(piper_hip_voice* v, int slot, Slot& s, const PitchItems& pit, int n, hipStream_t q) {
+  s.pt_on = false;
+  s.pt_done = false;
+  s.pt_q.assign((size_t)s.NB, kPtOne);
+  s.pt_qmin = s.pt_qmax = kPtOne;
+  s.pt_pmax = 0;
+  std::vector<const PtDesign*> tabs;  // one per distinct step of the batch
+  int rc;
+  for (int b = 0; b < n && b < (int)pit.size(); b++) {
+    uint64_t Q;
+    if ((rc = pt_step("pitch", pit[b].semitones, &Q))) return rc;
+    if (Q == kPtOne) continue;  // not a filter: the item has no pitch
+    s.pt_q[b] = Q;
+    s.pt_qmin = std::min(s.pt_qmin, Q);
+    s.pt_qmax = std::max(s.pt_qmax, Q);
+    const PtDesign* d = nullptr;
+    if ((rc = pt_design(Q, &d))) return rc;
+    s.pt_pmax = std::max(s.pt_pmax, d->P);
+    if (std::find(tabs.begin(), tabs.end(), d) == tabs.end()) tabs.push_back(d);
+  }
+  if (tabs.empty()) return PIPER_HIP_OK;
+  const size_t head = ((size_t)s.NB * sizeof(PtItem) + 15) & ~(size_t)15;
+  size_t bytes = head;
+  for (const PtDesign* d : tabs) bytes += (d->taps.size() * sizeof(float) + 15) & ~(size_t)15;
+  auto& sg = v->staging[slot];
+  if ((rc = grow_pinned(sg.h_pt, sg.cap_pt, bytes))) return rc;
+  if (s.pt_dev_cap < bytes) {  // (nothing on the GPU still reads the old one: the caller has waited for the plan's stream)
+    void* p = nullptr;
+    if ((rc = plan_alloc(v, s, bytes, &p))) return rc;
+    if (s.pt_dev) plan_free(v, s, s.pt_dev, s.pt_dev_cap);
+    s.pt_dev = (char*)p;
+    s.pt_dev_cap = bytes;
+  }
+  PtItem* items = (PtItem*)sg.h_pt;
+  for (int b = 0; b < s.NB; b++) items[b] = PtItem{nullptr, kPtOne, 0, 0};
+  size_t off = head;
+  for (const PtDesign* d : tabs) {
+    memcpy(sg.h_pt + off, d->taps.data(), d->taps.size() * sizeof(float));
+    for (int b = 0; b < s.NB; b++)
+      if (s.pt_q[b] == d->Q) items[b] = PtItem{(const float*)(s.pt_dev + off), d->Q, d->P, 0};
+    off += (d->taps.size() * sizeof(float) + 15) & ~(size_t)15;
+  }
+  PH_HIP(hipMemcpyAsync(s.pt_dev, sg.h_pt, bytes, hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  s.pt_on = true;
+  return PIPER_HIP_OK;
+}
+
+// Frames item b of the plan delivers when it has `frames` of its own: F' = ceil(N' / hop) under the item's pitch, `frames` without one.
+int pitch_frames(const piper_hip_voice* v, const Slot& s, int b, int frames) {
+  if (!s.pt_on || s.pt_q[b] == kPtOne) return frames;
+  return (int)ceil_div(pt_count((int64_t)frames * v->hop, s.pt_q[b]), v->hop);
+}
+
+// The rows every stage behind the pitch reads: [NB][row] floats, item b over lensF[b] frames (device memory) of at most F.
+struct Chain {
+  const float* audio = nullptr;
+  int64_t row = 0;
+  const int* lensF = nullptr;
+  int F = 0;
+};
+
+// The geometry of pitch_audio's rows without a launch: what the host-side bounds of the later stages are taken from.
+void chain_geometry(const piper_hip_voice* v, const Slot& s, int64_t* row, int* F) {
+  *F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  *row = s.n_samples;
+  if (!s.pt_on || *F < 1) return;
+  *F = (int)ceil_div(pt_count((int64_t)*F * v->hop, s.pt_qmin), v->hop);  // the plan's frame bucket under the least step of the batch
+  *row = (int64_t)*F * v->hop;
+}
+
+// What the stages behind the pitch read for a plan's items, and the single owner of their geometry: volume_audio's rows at the plan's
+// own lengths, or — the plan's latest staging carried a pitch — pitched [NB][F'cap·hop] with the frame counts the kernel wrote, computed
+// here once per launch behind the plan's graph on its stream, from lengths the device holds (plain, ragged and bounded slots alike).
+// A plan without a pitch hands out exactly the plan's own rows, stride, lengths and frames.
+int pitch_audio(piper_hip_voice* v, Slot& s, Chain* c) {
   const float* x = s.audio;
   int rc = volume_audio(v, s, &x);
   if (rc) return rc;
-  *audio = x;
+  c->audio = x;
+  c->lensF = s.lensF;
+  chain_geometry(v, s, &c->row, &c->F);
+  if (c->row > s.chain_row) {
+    // the later stages' buffers were allocated for shorter rows (nothing on the GPU still reads them: every collect ends with a wait)
+    const size_t items = (size_t)s.NB * s.chain_row * sizeof(float);
+    const int64_t n_old = (int64_t)s.chain_F * v->hop;
+    if (s.eqd) plan_free(v, s, s.eqd, items);
+    if (s.eq_work) plan_free(v, s, s.eq_work, (size_t)s.NB * eq_work_row(n_old, kEqMaxD) * sizeof(double));
+    if (s.gained) plan_free(v, s, s.gained, items);
+    if (s.loud_seg) plan_free(v, s, s.loud_seg, (size_t)s.NB * ld_work_row(n_old) * sizeof(double));
+    if (s.lim) plan_free(v, s, s.lim, items);
+    if (s.lim_scratch) plan_free(v, s, s.lim_scratch, lv_scratch_floats(s.NB, n_old) * sizeof(float));
+    s.eqd = s.gained = s.lim = s.lim_scratch = nullptr;
+    s.eq_work = s.loud_seg = nullptr;
+    s.eq_done = false;
+    s.loud_measured = false;
+    s.chain_row = c->row;
+    s.chain_F = c->F;
+  }
+  if (!s.pt_on) return PIPER_HIP_OK;
+  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
+  if (F < 1 || !s.pt_dev || !s.lensF) PH_FAIL(PIPER_HIP_ERR_SHAPE, "pitch: the slot holds no samples to shift");
+  void* q = nullptr;
+  if (s.pt_cap < (size_t)s.NB * c->row) {
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * c->row * sizeof(float), &q))) return rc;
+    if (s.pitched) plan_free(v, s, s.pitched, s.pt_cap * sizeof(float));
+    s.pitched = (float*)q;
+    s.pt_cap = (size_t)s.NB * c->row;
+    s.pt_done = false;
+  }
+  if (!s.pt_lensF) {
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * sizeof(int), &q))) return rc;
+    s.pt_lensF = (int*)q;
+    s.pt_done = false;
+  }
+  if (!s.pt_done) {
+    PH_HIP(launch_pitch_items(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, 0, (const PtItem*)s.pt_dev, PtItem{}, s.pt_qmin, s.pt_qmax,
+                              s.pt_pmax, s.pitched, c->row, s.pt_lensF),
+           PIPER_HIP_ERR_LAUNCH);
+    s.pt_done = true;
+  }
+  c->audio = s.pitched;
+  c->lensF = s.pt_lensF;
+  return PIPER_HIP_OK;
+}
+
+// What the stages behind the EQ read for a slot id's items: pitch_audio's, or — the slot id has an EQ (piper_hip_voice_slot_eq) — eqd
+// [NB][row], computed here behind the plan's graph on its stream from lengths the device holds (plain, ragged and bounded slots
+// alike), once per launch and EQ. Whenever the EQ the chain reads through changes, the loudness measured behind it is dropped.
+int eq_audio(piper_hip_voice* v, int slot, Slot& s, Chain* c) {
+  int rc = pitch_audio(v, s, c);
+  if (rc) return rc;
+  const float* x = c->audio;
   const auto& se = v->slot_eq[slot];
   if (s.eq_on != se.on || (se.on && memcmp(&s.eq_held, &se.eq, sizeof(piper_hip_eq)) != 0)) {
     s.eq_on = se.on;
@@ -3536,16 +3761,16 @@ int eq_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
     s.loud_measured = false;
   }
   if (!se.on) return PIPER_HIP_OK;
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  const int F = c->F;  // frames of a row of the items
   if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "eq: the slot holds no samples to filter");
   void* q = nullptr;
   if (!s.eqd) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.chain_row * sizeof(float), &q))) return rc;
     s.eqd = (float*)q;
     s.eq_done = false;
   }
   if (!s.eq_work) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * eq_work_row((int64_t)F * v->hop, kEqMaxD) * sizeof(double), &q))) return rc;
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * eq_work_row((int64_t)s.chain_F * v->hop, kEqMaxD) * sizeof(double), &q))) return rc;
     s.eq_work = (double*)q;
   }
   if (!s.eq_dev) {
@@ -3566,12 +3791,12 @@ int eq_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
       s.eq_dev_ok = true;
       s.eq_dev_eq = se.eq;
     }
-    PH_HIP(launch_eq_items(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, 0, s.eq_dev, se.eq.n,
-                           s.eq_work, s.eqd, s.n_samples),
+    PH_HIP(launch_eq_items(s.set.stream, x, c->row, c->lensF, F, v->hop, s.NB, 0, s.eq_dev, se.eq.n,
+                           s.eq_work, s.eqd, c->row),
            PIPER_HIP_ERR_LAUNCH);
     s.eq_done = true;
   }
-  *audio = s.eqd;
+  c->audio = s.eqd;
   return PIPER_HIP_OK;
 }
 
@@ -3582,13 +3807,14 @@ int loudness_measure(piper_hip_voice* v, int slot, Slot& s, const LdTarget& t) {
   LdFilter f;
   int rc = ld_filter(v->cfg.sample_rate, &f);
   if (rc) return rc;
-  const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items; a slot id with an EQ: the EQ'd ones)
-  if ((rc = eq_audio(v, slot, s, &x))) return rc;  // (first: a change of the slot id's EQ invalidates the measurement)
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  Chain c;  // (a plan whose staging carried a volume or a pitch: the shaped, pitched items; a slot id with an EQ: the EQ'd ones)
+  if ((rc = eq_audio(v, slot, s, &c))) return rc;  // (first: a change of the slot id's EQ invalidates the measurement)
+  const float* x = c.audio;
+  const int F = c.F;  // frames of a row of the items
   if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "loudness: the slot holds no samples");
   void* q = nullptr;
   if (!s.loud_seg) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * ld_work_row((int64_t)F * v->hop) * sizeof(double), &q))) return rc;
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * ld_work_row((int64_t)s.chain_F * v->hop) * sizeof(double), &q))) return rc;
     s.loud_seg = (double*)q;
     s.loud_measured = false;
   }
@@ -3597,62 +3823,60 @@ int loudness_measure(piper_hip_voice* v, int slot, Slot& s, const LdTarget& t) {
     s.loud_rep = (float*)q;
   }
   if (!s.loud_measured) {
-    PH_HIP(launch_loudness_measure(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, 0, f, s.loud_seg), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(launch_loudness_measure(s.set.stream, x, c.row, c.lensF, F, v->hop, s.NB, 0, f, s.loud_seg), PIPER_HIP_ERR_LAUNCH);
     s.loud_measured = true;
   }
-  PH_HIP(launch_loudness_gate(s.set.stream, s.lensF, F, v->hop, s.NB, 0, f.h, s.loud_seg, t, s.loud_rep), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(launch_loudness_gate(s.set.stream, c.lensF, F, v->hop, s.NB, 0, f.h, s.loud_seg, t, s.loud_rep), PIPER_HIP_ERR_LAUNCH);
   return PIPER_HIP_OK;
 }
 
 // The items a slot id with a loudness target (piper_hip_voice_slot_loudness) hands the rest of the output chain: gained [NB][n_samples],
 // u = x·g per item. Without a target: the plan's audio (x: the shaped items where the plan's staging carried a volume).
-int loudness_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
-  const float* x = s.audio;  // (a plan whose staging carried a volume: the shaped items; a slot id with an EQ: the EQ'd ones)
-  int rc = eq_audio(v, slot, s, &x);
+int loudness_audio(piper_hip_voice* v, int slot, Slot& s, Chain* c) {
+  int rc = eq_audio(v, slot, s, c);  // (a plan whose staging carried a volume or a pitch: the shaped, pitched items; a slot id with an EQ: the EQ'd ones)
   if (rc) return rc;
-  *audio = x;
+  const float* x = c->audio;
   const auto& sl = v->slot_ld[slot];
   if (!sl.on) return PIPER_HIP_OK;
   LdTarget t;
   if ((rc = ld_resolve(&sl.ld, &t))) return rc;
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
+  const int F = c->F;
   if (F < 1) return PIPER_HIP_OK;
   if ((rc = loudness_measure(v, slot, s, t))) return rc;
   if (!s.gained) {
     void* q = nullptr;
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.chain_row * sizeof(float), &q))) return rc;
     s.gained = (float*)q;
   }
-  PH_HIP(launch_loudness_gain(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, s.loud_rep, s.gained, s.n_samples), PIPER_HIP_ERR_LAUNCH);
-  *audio = s.gained;
+  PH_HIP(launch_loudness_gain(s.set.stream, x, c->row, c->lensF, F, v->hop, s.NB, s.loud_rep, s.gained, c->row), PIPER_HIP_ERR_LAUNCH);
+  c->audio = s.gained;
   return PIPER_HIP_OK;
 }
 
 // What a collect of slot id `slot` reads: the plan's audio, or — the slot id has a loudness target — the gained items, or — the slot id has
 // a level (piper_hip_voice_slot_level) — the limited (gained) items lim [NB][n_samples], computed here behind the plan's graph on its
 // stream from lengths the device holds (plain, ragged and bounded slots alike). The plan's audio stays raw.
-int level_audio(piper_hip_voice* v, int slot, Slot& s, const float** audio) {
-  const float* src = s.audio;
-  if (int lrc = loudness_audio(v, slot, s, &src)) return lrc;
-  *audio = src;
+int level_audio(piper_hip_voice* v, int slot, Slot& s, Chain* c) {
+  if (int lrc = loudness_audio(v, slot, s, c)) return lrc;
+  const float* src = c->audio;
   const auto& sl = v->slot_lv[slot];
   if (!sl.on) return PIPER_HIP_OK;
   LvParams p;
   int rc = lv_resolve(&sl.lv, v->cfg.sample_rate, &p);
   if (rc) return rc;
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  const int F = c->F;  // frames of a row of the items
   if (F < 1) return PIPER_HIP_OK;
   void* q = nullptr;
   if (!s.lim) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q))) return rc;
+    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.chain_row * sizeof(float), &q))) return rc;
     s.lim = (float*)q;
   }
   if (!s.lim_scratch) {
-    if ((rc = plan_alloc(v, s, lv_scratch_floats(s.NB, (int64_t)F * v->hop) * sizeof(float), &q))) return rc;
+    if ((rc = plan_alloc(v, s, lv_scratch_floats(s.NB, (int64_t)s.chain_F * v->hop) * sizeof(float), &q))) return rc;
     s.lim_scratch = (float*)q;
   }
-  PH_HIP(launch_level_items(s.set.stream, src, s.n_samples, s.lensF, F, v->hop, s.NB, 0, p, s.lim_scratch, s.lim, s.n_samples), PIPER_HIP_ERR_LAUNCH);
-  *audio = s.lim;
+  PH_HIP(launch_level_items(s.set.stream, src, c->row, c->lensF, F, v->hop, s.NB, 0, p, s.lim_scratch, s.lim, c->row), PIPER_HIP_ERR_LAUNCH);
+  c->audio = s.lim;
   return PIPER_HIP_OK;
 }
 
@@ -3664,8 +3888,8 @@ int join_capacity(const piper_hip_voice* v, int slot, const Slot& s, int64_t* ca
   const auto& sj = v->slot_jn[slot];
   if (s.NB > kJoinMaxItems) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join: %d items (at most %d)", s.NB, kJoinMaxItems);
   const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
-  int64_t sum = 0;
-  for (int b = 0; b < s.NB; b++) sum += (int64_t)(s.bounded_pending ? F : std::min(s.h_F[b], F)) * v->hop;
+  int64_t sum = 0;  // (under a pitch: of the pitched items)
+  for (int b = 0; b < s.NB; b++) sum += (int64_t)pitch_frames(v, s, b, s.bounded_pending ? F : std::min(s.h_F[b], F)) * v->hop;
   *cap = join_bound(sj.p, s.NB, sum);
   if (*cap > INT_MAX) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join: a programme of up to %lld samples does not fit an int", (long long)*cap);
   return PIPER_HIP_OK;
@@ -3681,13 +3905,13 @@ struct Joined {
 // The join of slot id `slot` over `items` (the layout of s.audio: what level_audio handed out) behind the plan's graph on its stream,
 // from lengths the device holds. The report lands in the slot id's page-locked h_jrep — through its mapping where there is one, else by
 // a copy behind the launches — and is the host's once the stream has been waited for (join_landed).
-int join_items(piper_hip_voice* v, int slot, Slot& s, const float* items, Joined* out) {
+int join_items(piper_hip_voice* v, int slot, Slot& s, const Chain& items, Joined* out) {
   const auto& sj = v->slot_jn[slot];
   auto& sg = v->staging[slot];
   int64_t cap = 0;
   int rc = join_capacity(v, slot, s, &cap);
   if (rc) return rc;
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
+  const int F = items.F;
   void* q = nullptr;
   if (s.jn_cap < std::max<int64_t>(cap, 1)) {  // (nothing on the GPU still reads the old one: every collect ends with a wait)
     if ((rc = plan_alloc(v, s, (size_t)std::max<int64_t>(cap, 1) * sizeof(float), &q))) return rc;
@@ -3719,7 +3943,7 @@ int join_items(piper_hip_voice* v, int slot, Slot& s, const float* items, Joined
   int64_t z = sj.p.tail;
   for (int b = 0; b + 1 < s.NB; b++) z = std::max(z, sj.p.gap[b]);
   int* edges = (int*)(s.jn_dev + o_edges);
-  const JoinSrc src{items, s.n_samples, s.lensF, F, v->hop, nullptr, nullptr};
+  const JoinSrc src{items.audio, items.row, items.lensF, F, v->hop, nullptr, nullptr};
   PH_HIP(launch_join(st, src, s.NB, (int64_t)F * v->hop, sj.p.lead + z, (const JoinParams*)s.jn_dev, sj.p.trim != 0, edges,
                      (JoinRow*)(s.jn_dev + o_rows), edges + 2 * kJoinMaxItems, (int64_t*)(s.jn_dev + o_rep), rep_host, s.jn_buf),
          PIPER_HIP_ERR_LAUNCH);
@@ -3741,7 +3965,7 @@ int64_t join_landed(piper_hip_voice* v, int slot, Slot& s) {
 // collect on a slot id with a join: the programme's floats. Up to kPinnedMax they leave through the slot id's page-locked buffer by a
 // kernel that reads the length from device memory — one synchronisation for report, lengths and samples; a longer programme waits for
 // its length first and is copied at it.
-int collect_joined(piper_hip_voice* v, int slot, Slot& s, const float* items, float* host_audio, int64_t max_samples) {
+int collect_joined(piper_hip_voice* v, int slot, Slot& s, const Chain& items, float* host_audio, int64_t max_samples) {
   auto& sg = v->staging[slot];
   int64_t cap = 0;
   int rc = join_capacity(v, slot, s, &cap);
@@ -3791,6 +4015,7 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   s.h_peaks.clear();  // the peaks a normalising collect_pcm16 reported belong to the previous run
   s.loud_measured = false;  // (and so does the loudness measured there)
   s.vol_shaped = false;     // (and the items shaped from it)
+  s.pt_done = false;        // (and the items pitched from those)
   s.eq_done = false;        // (and the items EQ'd from those)
   s.h_jrep.clear();         // (and the report of a joined collect)
   return PIPER_HIP_OK;
@@ -3803,7 +4028,9 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *p;
   auto& sg = v->staging[slot];
-  const float* audio = s.audio;  // (a slot id with a level: the limited items)
+  Chain chain;  // the items the collect reads (a slot id with a level: the limited items), rows and lengths as pitch_audio hands them out
+  chain.audio = s.audio; chain.lensF = s.lensF;
+  chain_geometry(v, s, &chain.row, &chain.F);
   const bool joined = host_audio && slot >= 0 && slot < kMaxSlots && v->slot_jn[slot].on;
   if (joined) {  // (a buffer too short for the programme is refused before anything is enqueued)
     int64_t cap = 0;
@@ -3812,19 +4039,24 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)cap,
               (long long)max_samples);
   }
+  if (host_audio && !joined && s.bounded_pending) {  // (a buffer too short for the capacity is refused before anything is enqueued)
+    int64_t need = 0;
+    for (int b = 0; b < s.NB; b++) need += (int64_t)pitch_frames(v, s, b, s.F) * v->hop;
+    if (max_samples < need)
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_%s_samples before collect), got %lld",
+              (long long)need, s.pt_on ? "pitch" : "prepared", (long long)max_samples);
+  }
   if (host_audio)
-    if (int lrc = level_audio(v, slot, s, &audio)) return lrc;
-  if (joined) return collect_joined(v, slot, s, audio, host_audio, max_samples);  // (a slot id with a join: the programme)
+    if (int lrc = level_audio(v, slot, s, &chain)) return lrc;
+  const float* audio = chain.audio;
+  if (joined) return collect_joined(v, slot, s, chain, host_audio, max_samples);  // (a slot id with a join: the programme)
   // The slot id's page-locked landing buffer of the waveform (kAudioMinCap at least). Failing to grow it is not fatal: the waveform
   // then goes to the caller's buffer directly, and the sticky error of the failed hipHostMalloc is cleared (the next launch would report it).
   if (s.bounded_pending) {
     // lengths still on the device. Short buckets: the waveform rows go to the slot id's page-locked buffer at bucket stride by a kernel that
     // reads each length from device memory — ONE synchronisation for lengths and samples; long ones: synchronise, then the usual copy.
-    const int64_t row = (int64_t)s.F * v->hop;
+    const int64_t row = s.pt_on ? chain.row : (int64_t)s.F * v->hop;
     const size_t ub = (size_t)row * s.NB * sizeof(float);
-    if (host_audio && max_samples < row * s.NB)
-      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_prepared_samples before collect), got %lld",
-              (long long)(row * s.NB), (long long)max_samples);
     float* dst_dev = nullptr;
     if (host_audio && ub <= ((size_t)1 << 20) && (v->hop & 3) == 0) {
       if (grow_pinned(sg.h_audio, sg.audio_cap, (size_t)row * s.NB, kAudioMinCap)) (void)hipGetLastError();
@@ -3833,7 +4065,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     if (dst_dev) {
       for (int b = 0; b < s.NB; b++) {
         const int blocks = (int)std::min<int64_t>((row + 4 * 256 - 1) / (4 * 256), 1024);
-        hipLaunchKernelGGL(copy_out_len_kernel, dim3(blocks), dim3(256), 0, s.set.stream, audio + (int64_t)b * s.n_samples, dst_dev + (int64_t)b * row, s.lensF, b, v->hop);
+        hipLaunchKernelGGL(copy_out_len_kernel, dim3(blocks), dim3(256), 0, s.set.stream, audio + (int64_t)b * chain.row, dst_dev + (int64_t)b * row, chain.lensF, b, v->hop);
         PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
       }
     }
@@ -3843,7 +4075,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     if (dst_dev) {
       int64_t off = 0;
       for (int b = 0; b < s.NB; b++) {
-        const int64_t nb = (int64_t)s.h_F[b] * v->hop;
+        const int64_t nb = (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
         memcpy(host_audio + off, sg.h_audio + (int64_t)b * row, (size_t)nb * sizeof(float));
         off += nb;
       }
@@ -3853,7 +4085,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
   }
   if (host_audio) {
     int64_t total = 0;  // batch items back to back, each at its own true length
-    for (int b = 0; b < s.NB; b++) total += (int64_t)s.h_F[b] * v->hop;
+    for (int b = 0; b < s.NB; b++) total += (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
     if (max_samples < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
     // A copy into the caller's (pageable) buffer goes through the runtime's own staging in chunks and its time varies from
     // box to box (r2z: 45 … 130 µs for 344 KB). Up to 1 MB (a factor-8 … 16 utterance) the waveform lands in a pinned buffer of
@@ -3873,8 +4105,8 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
       std::vector<int64_t> cuts;
       int64_t off = 0;
       for (int b = 0; b < s.NB; b++) {
-        const int64_t nb = (int64_t)s.h_F[b] * v->hop;
-        const float* src = audio + (int64_t)b * s.n_samples;
+        const int64_t nb = (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
+        const float* src = audio + (int64_t)b * chain.row;
         for (int64_t c0 = 0; c0 < nb; c0 += (int64_t)(kChunk / sizeof(float))) {
           const int64_t cn = std::min<int64_t>((int64_t)(kChunk / sizeof(float)), nb - c0);
           PH_HIP(hipMemcpyAsync(h_audio + off + c0, src + c0, (size_t)cn * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
@@ -3916,8 +4148,8 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     }
     int64_t off = 0;
     for (int b = 0; b < s.NB; b++) {
-      const int64_t nb = (int64_t)s.h_F[b] * v->hop;
-      const float* src = audio + (int64_t)b * s.n_samples;
+      const int64_t nb = (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
+      const float* src = audio + (int64_t)b * chain.row;
       if (dst_dev && nb > 0) {
         const int blocks = (int)std::min<int64_t>((nb + 4 * 256 - 1) / (4 * 256), 1024);
         hipLaunchKernelGGL(copy_out_kernel, dim3(blocks), dim3(256), 0, s.set.stream, src, dst_dev + off, nb);
@@ -4008,6 +4240,7 @@ int launch_front(Slot& s) {
 PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_utterance* u, int slot, int chunk_frames) {
   const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
   const VolumeClear vc{v, slot};  // (and its volume)
+  if (int prc = refuse_pitch(v, slot, "stream_begin")) return prc;
   if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin: chunk_frames must be >= 1");
   int rc = piper_hip_voice_prepare(v, u, slot);
   if (rc < 0) return rc;
@@ -4941,6 +5174,7 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, const Sink& out, int6
 PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames) {
   const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
   const VolumeClear vc{v, slot};  // (and its volume)
+  if (int prc = refuse_pitch(v, slot, "stream_begin_batch")) return prc;
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: group of %d outside [1,%d]", n, kMaxGroup);
   if (int rc = check_step_size(v, "stream_begin_batch", n, chunk_frames)) return rc;
@@ -5060,6 +5294,7 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
               bool with_formats, int* items_out, int64_t* samples_out, int bound = 0) {
   const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
   const VolumeClear vc{v, work_slot};  // (and its volume)
+  if (int prc = refuse_pitch(v, work_slot, "stream_pool_join")) return prc;
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
   if (!P) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d holds no streaming pool", slot);
@@ -5226,6 +5461,7 @@ PH_EXPORT int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int s
                                                        int max_frames, const piper_hip_stream_format* fmts, int* items_out) {
   const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
   const VolumeClear vc{v, work_slot};  // (and its volume)
+  if (int prc = refuse_pitch(v, work_slot, "stream_pool_join_bounded")) return prc;
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   // prepare_batch_bounded's own refusals, before anything of the pool is looked at or regrown (it repeats them)
   if (int rc = bounded_refusals(v, utts, n, work_slot, max_frames, true)) return rc;
@@ -5320,7 +5556,11 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   auto& sg = v->staging[slot];
   const int NB = s.NB, hop = v->hop;
   if (NB > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: %d items (at most %d)", NB, kMaxGroup);
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / hop);  // frames of a row of s.audio
+  Chain chain;  // the items the sinks read, rows and lengths as pitch_audio hands them out
+  chain.audio = s.audio; chain.lensF = s.lensF;
+  chain_geometry(v, s, &chain.row, &chain.F);
+  const int F = chain.F;  // frames of a row of the items
+  const int F_own = (int)std::min<int64_t>(s.F, s.n_samples / hop);  // frames of a row of s.audio
   const bool bounded = s.bounded_pending;
   // a slot id with a join: the sinks read the programme, ONE item whose length the device knows, the caller makes room for its bound
   const bool joined = slot >= 0 && slot < kMaxSlots && v->slot_jn[slot].on;
@@ -5329,15 +5569,14 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   // a bounded slot's lengths are still on the device: the caller makes room for the capacity, as for collect
   int64_t need = 0;
   if (joined) need = out_len(jcap);
-  else if (bounded) need = out_len((int64_t)F * hop) * NB;
-  else for (int b = 0; b < NB; b++) need += out_len((int64_t)s.h_F[b] * hop);
+  else for (int b = 0; b < NB; b++) need += out_len((int64_t)pitch_frames(v, s, b, bounded ? F_own : s.h_F[b]) * hop);
   if (out.cap < need) {
     if (joined)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)need,
               (long long)out.cap);
     if (bounded)
-      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_prepared_samples before collect), got %lld",
-              (long long)need, (long long)out.cap);
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_%s_samples before collect), got %lld",
+              (long long)need, s.pt_on ? "pitch" : "prepared", (long long)out.cap);
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: buffer holds %lld < %lld samples", (long long)out.cap, (long long)need);
   }
   float* peaks_host = nullptr;
@@ -5354,13 +5593,13 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   const int64_t dev_samples = joined ? std::max(out_len(jcap), jcap) : std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB;
   if ((rc = pcm_route(v, s, sg, host_pcm, elem, (size_t)need, (size_t)dev_samples, &r))) return rc;
   const hipStream_t q = s.set.stream;
-  const float* audio = s.audio;  // (a slot id with a level: the limited items)
-  if ((rc = level_audio(v, slot, s, &audio))) return rc;
+  if ((rc = level_audio(v, slot, s, &chain))) return rc;  // (a slot id with a level: the limited items)
+  const float* audio = chain.audio;
   if (joined) {
     // The programme is one row of device-known length: the sinks take it as NB = 1, hop = 1, F = its bound, with the device's total as
     // the length. normalize = 1 takes ONE peak, over the programme (no level and no loudness then: the joined EQ'd items).
     Joined j;
-    if ((rc = join_items(v, slot, s, audio, &j))) return rc;
+    if ((rc = join_items(v, slot, s, chain, &j))) return rc;
     const int JF = (int)std::max<int64_t>(j.cap, 1);
     if (normalize) PH_HIP(launch_pcm16_peak(q, j.prog, JF, j.total, JF, 1, 1, s.peaks), PIPER_HIP_ERR_LAUNCH);
     if (rd)
@@ -5376,20 +5615,20 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
     if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + 1);
     return PIPER_HIP_OK;
   }
-  const float* peak_src = s.audio;  // (the peak of normalize = 1 is that of the shaped, EQ'd items where there are a volume, an EQ)
+  Chain peak_src = chain;  // (the peak of normalize = 1 is that of the shaped, pitched, EQ'd items where there are a volume, a pitch, an EQ)
   if (normalize && (rc = eq_audio(v, slot, s, &peak_src))) return rc;
-  if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src, s.n_samples, s.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
+  if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src.audio, chain.row, chain.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
   if (rd)
-    PH_HIP(launch_resample_items(q, audio, s.n_samples, s.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
+    PH_HIP(launch_resample_items(q, audio, chain.row, chain.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
            PIPER_HIP_ERR_LAUNCH);
   else
-    PH_HIP(launch_pcm16_pack(q, audio, s.n_samples, s.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(launch_pcm16_pack(q, audio, chain.row, chain.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
   if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, (size_t)NB * sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
   if ((rc = pcm_land(sg, r, q, host_pcm, elem, (size_t)need))) return rc;
   if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
   if (r.mapped && !r.caller_pinned) {  // the kernel stored into the staging: the true total is known by now
     int64_t total = 0;
-    for (int b = 0; b < NB; b++) total += out_len((int64_t)s.h_F[b] * hop);
+    for (int b = 0; b < NB; b++) total += out_len((int64_t)pitch_frames(v, s, b, s.h_F[b]) * hop);
     memcpy(host_pcm, r.stage, (size_t)total * elem);
   }
   if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + NB);
@@ -5426,6 +5665,7 @@ int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper
                    void* host, int64_t max_samples, int64_t* n_samples) {
   const ProsodyClear pc{v, 0};  // a staging call on slot 0
   const VolumeClear vc{v, 0};
+  const PitchClear tc{v, 0};
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   float gain;
   bool normalize;
@@ -5440,7 +5680,7 @@ int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
   if ((rc = collect_pcm(v, 0, params, out_rate, Sink{host, max_samples, enc}))) return rc;
   const Slot& s0 = *v->attached[0];
-  const int64_t n = v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)s0.h_F[0] * v->hop;  // (a join: the programme's count)
+  const int64_t n = v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)pitch_frames(v, s0, 0, s0.h_F[0]) * v->hop;  // (a join: the programme's count)
   if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
   return PIPER_HIP_OK;
 }
@@ -5941,7 +6181,7 @@ PH_EXPORT int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utt
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
   if ((rc = piper_hip_voice_collect(v, 0, host_audio, max_samples))) return rc;
   const Slot& s0 = *v->attached[0];
-  if (n_samples) *n_samples = host_audio && v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)s0.h_F[0] * v->hop;
+  if (n_samples) *n_samples = host_audio && v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)pitch_frames(v, s0, 0, s0.h_F[0]) * v->hop;
   return PIPER_HIP_OK;
 }
 

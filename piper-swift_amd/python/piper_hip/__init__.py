@@ -400,6 +400,27 @@ def _loudness(loudness):
     return Loudness(float(t), float(m))
 
 
+class Pitch(C.Structure):
+    """piper_hip_pitch (include/piper_hip.h "Pitch"): semitones in [−12, 12]; keep_tempo 1 scales the predicted durations so that the item
+    keeps its length, 0 is varispeed."""
+    _fields_ = [("semitones", C.c_float), ("keep_tempo", C.c_int32)]
+
+    def __repr__(self):
+        return "Pitch(semitones=%g, keep_tempo=%d)" % (self.semitones, self.keep_tempo)
+
+
+def _pitch(p):
+    """A Pitch from a Pitch, a number (keep_tempo on), a (semitones, keep_tempo) pair or None (no pitch)"""
+    if isinstance(p, Pitch):
+        return p
+    if p is None:
+        return Pitch(0.0, 0)
+    if isinstance(p, (tuple, list)):
+        st, keep = p
+        return Pitch(float(st), int(keep))
+    return Pitch(float(p), 1)
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("avg_us", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -623,6 +644,14 @@ _PROTOS = {
     "piper_hip_voice_slot_eq": (C.c_int, [c_vp, C.c_int, C.POINTER(Eq)]),
     "piper_hip_voice_stream_set_eq": (C.c_int, [c_vp, C.c_int, C.POINTER(Eq)]),
     "piper_hip_voice_stream_eq": (C.c_int, [c_vp, C.c_int, C.POINTER(Eq)]),
+    "piper_hip_pitch_check": (C.c_int, [C.POINTER(Pitch)]),
+    "piper_hip_pitch_info": (C.c_int, [C.c_float, C.POINTER(C.c_uint64), c_i32p, c_f32p]),
+    "piper_hip_pitch_count": (C.c_int64, [C.c_float, C.c_int64]),
+    "piper_hip_pitch_taps": (C.c_int, [C.c_float, c_f32p, C.c_size_t]),
+    "piper_hip_pitch_from_f32": (C.c_int, [C.c_float, c_f32p, C.c_size_t, c_f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "piper_hip_pitch_f32": (C.c_int, [c_vp, c_vp, C.c_size_t, C.c_float, C.POINTER(c_vp), C.POINTER(C.c_size_t), c_vp]),
+    "piper_hip_voice_slot_pitch": (C.c_int, [c_vp, C.c_int, C.POINTER(Pitch), C.c_int]),
+    "piper_hip_voice_pitch_samples": (C.c_int, [c_vp, C.c_int, c_i64p, C.c_int, c_i64p]),
 }
 
 _lib = None
@@ -1030,6 +1059,15 @@ class HipBackend:
         _check(self.lib.piper_hip_resample_f32(self.ctx, _ptr(buf), n, int(inRate), int(outRate), C.byref(p), C.byref(got), commandBuffer))
         return DeviceBuffer(self, p.value, got.value, owned=out is None)
 
+    def pitch_f32(self, buf, semitones, count=None, out=None, commandBuffer=None):
+        """`count` device floats → N' device floats shifted by `semitones` (piper_hip_pitch_f32): the contract of include/piper_hip.h
+        "Pitch", no padding. Returns a DeviceBuffer of N' float32."""
+        n = buf.count if count is None else int(count)
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
+        got = C.c_size_t()
+        _check(self.lib.piper_hip_pitch_f32(self.ctx, _ptr(buf), n, float(semitones), C.byref(p), C.byref(got), commandBuffer))
+        return DeviceBuffer(self, p.value, got.value, owned=out is None)
+
     def resamplePcm16F32(self, buf, inRate, outRate, gain=1.0, count=None, out=None, commandBuffer=None):
         """The same ending in 16-bit PCM (piper_hip_resample_pcm16_f32): y · gain through pcm16F32's arithmetic. Returns a DeviceBuffer of
         J(count) int16 (downloadInt16); `out`: a device address to write to (2-byte alignment suffices), returned as it is."""
@@ -1414,6 +1452,42 @@ def _count(rc):
 def resample_count(in_rate, out_rate, n_in):
     """J(n_in): the samples an item of n_in samples yields at out_rate. Host-only."""
     return _count(load_library().piper_hip_resample_count(int(in_rate), int(out_rate), int(n_in)))
+
+
+def pitch_check(pitch):
+    """Raises InvalidArgument, naming the field, for a pitch outside the contract (piper_hip_pitch_check). Host-only."""
+    _check(load_library().piper_hip_pitch_check(C.byref(_pitch(pitch))))
+
+
+def pitch_info(semitones):
+    """(Q, taps, length_factor) of a shift: the 32.32 step, P, and rf = (float)(Q / 2^32) (piper_hip_pitch_info). Host-only."""
+    q, p, f = C.c_uint64(), C.c_int32(), C.c_float()
+    _check(load_library().piper_hip_pitch_info(float(semitones), C.byref(q), C.byref(p), C.byref(f)))
+    return q.value, p.value, np.float32(f.value)
+
+
+def pitch_count(semitones, n_in):
+    """N': the samples an item of n_in samples yields under a shift (piper_hip_pitch_count). Host-only."""
+    return _count(load_library().piper_hip_pitch_count(float(semitones), int(n_in)))
+
+
+def pitch_taps(semitones):
+    """The [129][P] float32 coefficient table the kernel uses for a shift (piper_hip_pitch_taps). Host-only."""
+    _, P, _ = pitch_info(semitones)
+    out = np.empty((129, P), np.float32)
+    _check(load_library().piper_hip_pitch_taps(float(semitones), out.ctypes.data_as(c_f32p), out.size))
+    return out
+
+
+def pitch_from_f32(samples, semitones):
+    """The host twin of the pitch kernel (piper_hip_pitch_from_f32): n float32 → N' float32. Host-only."""
+    x = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    y = np.empty(pitch_count(semitones, x.size), np.float32)
+    got = C.c_size_t()
+    _check(load_library().piper_hip_pitch_from_f32(float(semitones), x.ctypes.data_as(c_f32p), x.size, y.ctypes.data_as(c_f32p), y.size,
+                                                   C.byref(got)))
+    assert got.value == y.size
+    return y
 
 
 def resample_step_bound(in_rate, out_rate, n_in):
@@ -1823,6 +1897,32 @@ class HipRuntime:
         if volume is not None:
             self.slot_volume(slot, volume, ts)
 
+    def slot_pitch(self, slot, items):
+        """The pitch of the NEXT staging call on the slot id (piper_hip_voice_slot_pitch): entry i for item i, each a number of semitones
+        in [−12, 12] (keep_tempo on), a (semitones, keep_tempo) pair, a Pitch, or None (no pitch). The staging call takes the assignment
+        whether or not it succeeds. None or [] clears it."""
+        recs = [_pitch(p) for p in (items or [])]
+        arr = (Pitch * len(recs))(*recs) if recs else None
+        _check(self.lib.piper_hip_voice_slot_pitch(self.voice, int(slot), arr, len(recs)))
+
+    def _stage_pitch(self, slot, pitch, n):
+        """The `pitch=` keyword of the staging methods: one value for all n utterances, a list with one entry per utterance, or None."""
+        if pitch is None:
+            return
+        if isinstance(pitch, list):
+            self.slot_pitch(slot, pitch)
+        else:
+            self.slot_pitch(slot, [pitch] * n)
+
+    def pitch_samples(self, slot):
+        """Samples per batch item the slot delivers at the voice's rate, F'·hop under a pitch (piper_hip_voice_pitch_samples), and their
+        sum; a bounded slot: its capacity before collect, the true values after. Without a pitch: prepared_samples."""
+        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
+        per = (C.c_int64 * max(nb, 1))()
+        tot = C.c_int64()
+        _check(self.lib.piper_hip_voice_pitch_samples(self.voice, slot, per, nb, C.byref(tot)))
+        return [int(x) for x in per[:nb]], int(tot.value)
+
     def prosody_report(self, slot):
         """Per item of the slot: (frames the rule wanted before fitting, fitted?) — piper_hip_voice_prosody_report; answers where
         durations() answers."""
@@ -1855,7 +1955,7 @@ class HipRuntime:
         return int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))
 
     def synthesize(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, speaker=None, prosody=None, volume=None,
-                   level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP, **kw):
+                   level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP, pitch=None, **kw):
         """PiperMetalRuntime.synthesize(phonemeIDs:noiseScale:lengthScale:noiseW:); `durations` / `noise` / dp_noise are the
         reference's `overrides`. Without durations the frames per id come from the voice's duration predictor.
         speaker (a voice with a speaker table): an id or a {id: weight} mix; it becomes slot 0's assignment (slot_speakers) and stays.
@@ -1871,26 +1971,31 @@ class HipRuntime:
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
             self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
             self._stage_volume(0, None if volume is None else [volume], [len(phonemeIDs)])
-            n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
+            self._stage_pitch(0, pitch, 1)
+            n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))), pitch)
             out = np.empty(max(n, 1), np.float32)
             got = C.c_int64()
             _check(self.lib.piper_hip_voice_synthesize(self.voice, C.byref(u), out.ctypes.data_as(c_f32p), n, C.byref(got)))
             self._keep.pop(0, None)
             return out[:got.value]
-        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, volume=volume, **kw)
+        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, volume=volume,
+                     pitch=pitch, **kw)
         self.launch(0)
         return self.collect(0)
 
     def prepare(self, slot, phonemeIDs, durations=None, noise=None, noiseScale=0.667, noise_mode="injected", seed=1234, length_scale=1.0,
-                noise_w=0.8, dp_noise=None, max_frames=None, prosody=None, volume=None):
+                noise_w=0.8, dp_noise=None, max_frames=None, prosody=None, volume=None, pitch=None):
         """max_frames (durations must be None): predicted durations WITHOUT the host round trip — the plan is the bucket of that bound and the
         frame count stays on the device until collect (piper_hip_voice_prepare_batch_bounded).
         prosody: the item's per-id prosody (slot_prosody), a dict(length=, min_frames=, max_frames=, noise=, fit=) or a Prosody.
         volume: the item's linear gains per id in [0, 16] (slot_volume): every collect of this staging delivers the samples under that
-        envelope (include/piper_hip.h "Per-phoneme volume")."""
+        envelope (include/piper_hip.h "Per-phoneme volume").
+        pitch: semitones in [−12, 12] (the tempo kept: predicted durations only), or a (semitones, keep_tempo) pair (slot_pitch): every
+        collect of this staging delivers the pitched item (include/piper_hip.h "Pitch"); pitch_samples(slot) is its length."""
         u, k = self._utt(phonemeIDs, durations, noise, noiseScale, noise_mode, seed, length_scale, noise_w, dp_noise)
         self._stage_prosody(slot, None if prosody is None else [prosody], [len(phonemeIDs)])
         self._stage_volume(slot, None if volume is None else [volume], [len(phonemeIDs)])
+        self._stage_pitch(slot, pitch, 1)
         if max_frames is not None:
             rc = self.lib.piper_hip_voice_prepare_batch_bounded(self.voice, C.byref(u), 1, slot, int(max_frames))
         else:
@@ -1898,14 +2003,16 @@ class HipRuntime:
         if rc < 0:
             _check(rc)
         tot = C.c_int64()
-        _check(self.lib.piper_hip_voice_prepared_samples(self.voice, slot, None, 0, C.byref(tot)))
+        _check(self.lib.piper_hip_voice_pitch_samples(self.voice, slot, None, 0, C.byref(tot)))
         self._keep[slot] = (k, int(tot.value), max_frames is not None)
         return rc
 
     def prepare_batch_bounded(self, slot, utterances, max_frames, noiseScale=0.667, noise_mode="device", seed=1234, length_scale=1.0, noise_w=0.8,
-                              prosody=None, volume=None):
+                              prosody=None, volume=None, pitch=None):
         """utterances: list of (phonemeIDs, dp_noise-or-None); durations predicted on the device, at most max_frames frames per item.
-        prosody: one entry per utterance (None entries neutral), as for slot_prosody; an entry's fit=1 compresses an item over the bound."""
+        prosody: one entry per utterance (None entries neutral), as for slot_prosody; an entry's fit=1 compresses an item over the bound.
+        pitch: one value for all utterances or a list with one per utterance, as for slot_pitch; max_frames bounds the frames the model
+        generates, before the pitch."""
         n = len(utterances)
         arr = (Utterance * n)()
         keep = []
@@ -1915,11 +2022,12 @@ class HipRuntime:
             keep.append(k)
         self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
         self._stage_volume(slot, volume, [len(u[0]) for u in utterances])
+        self._stage_pitch(slot, pitch, n)
         rc = self.lib.piper_hip_voice_prepare_batch_bounded(self.voice, arr, n, slot, int(max_frames))
         if rc < 0:
             _check(rc)
         tot = C.c_int64()
-        _check(self.lib.piper_hip_voice_prepared_samples(self.voice, slot, None, 0, C.byref(tot)))
+        _check(self.lib.piper_hip_voice_pitch_samples(self.voice, slot, None, 0, C.byref(tot)))
         self._keep[slot] = (keep, int(tot.value), True)
         return rc
 
@@ -2018,12 +2126,15 @@ class HipRuntime:
         assert out.dtype == dtype and out.size >= room and out.flags.c_contiguous
         call(out, room)
         if len(self._keep[slot]) > 2 and self._keep[slot][2]:  # bounded: the true lengths are known now
-            self._keep[slot] = (self._keep[slot][0], self.prepared_samples(slot)[1], False)
+            self._keep[slot] = (self._keep[slot][0], self.pitch_samples(slot)[1], False)
         total = self.join_report(slot)[2]
         return out[:total if rate is None or int(rate) == src else resample_count(src, int(rate), total)]
 
-    def _one_call_room(self, n):
-        """samples of slot 0's one-item programme for an utterance of n samples (the synthesize twins)"""
+    def _one_call_room(self, n, pitch=None):
+        """samples of slot 0's one-item programme for an utterance of n samples under `pitch` (the synthesize twins)"""
+        if pitch is not None:
+            hop = self.cfg.hop
+            n = -(-pitch_count(_pitch(pitch).semitones, n) // hop) * hop
         if 0 not in self._joins:
             return n
         jn, g = self._joins[0]
@@ -2234,10 +2345,11 @@ class HipRuntime:
             pool.set_level(level)
         return pool
 
-    def prepare_batch(self, slot, utterances, noiseScale=0.667, prosody=None, volume=None):
+    def prepare_batch(self, slot, utterances, noiseScale=0.667, prosody=None, volume=None, pitch=None):
         """utterances: list of (phonemeIDs, durations, noise-or-None[, dict of noise_mode / seed / length_scale / noise_w / dp_noise]); lengths
         may differ (ragged batch, one bucket). prosody: one entry per utterance (None entries neutral), as for slot_prosody.
-        volume: one array of gains per utterance (None entries all 1.0, utterances past the list have none), as for slot_volume."""
+        volume: one array of gains per utterance (None entries all 1.0, utterances past the list have none), as for slot_volume.
+        pitch: one value for all utterances or a list with one per utterance (None entries no pitch), as for slot_pitch."""
         n = len(utterances)
         arr = (Utterance * n)()
         keep = []
@@ -2249,11 +2361,12 @@ class HipRuntime:
             keep.append(k)
         self._stage_prosody(slot, prosody, [len(u[0]) for u in utterances])
         self._stage_volume(slot, volume, [len(u[0]) for u in utterances])
+        self._stage_pitch(slot, pitch, n)
         rc = self.lib.piper_hip_voice_prepare_batch(self.voice, arr, n, slot)
         if rc < 0:
             _check(rc)
         tot = C.c_int64()
-        _check(self.lib.piper_hip_voice_prepared_samples(self.voice, slot, None, 0, C.byref(tot)))
+        _check(self.lib.piper_hip_voice_pitch_samples(self.voice, slot, None, 0, C.byref(tot)))
         self._keep[slot] = (keep, int(tot.value))
         return rc
 
@@ -2302,7 +2415,7 @@ class HipRuntime:
         assert out.dtype == np.float32 and out.size >= n and out.flags.c_contiguous
         _check(self.lib.piper_hip_voice_collect(self.voice, slot, out.ctypes.data_as(c_f32p), n))
         if len(self._keep[slot]) > 2 and self._keep[slot][2]:  # bounded: n was the capacity; the true lengths are known now
-            n = self.prepared_samples(slot)[1]
+            n = self.pitch_samples(slot)[1]
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
@@ -2329,28 +2442,27 @@ class HipRuntime:
         prm = PcmParams(float(gain), int(bool(normalize)))
         _check(self.lib.piper_hip_voice_collect_pcm16(self.voice, slot, C.byref(prm), out.ctypes.data_as(c_i16p), n))
         if len(self._keep[slot]) > 2 and self._keep[slot][2]:  # bounded: n was the capacity; the true lengths are known now
-            n = self.prepared_samples(slot)[1]
+            n = self.pitch_samples(slot)[1]
             self._keep[slot] = (self._keep[slot][0], n, False)
         return out[:n]
 
     def _collect_pcm16_rate(self, slot, gain, normalize, out, rate):
         src = self.cfg.sample_rate
         bounded = len(self._keep[slot]) > 2 and self._keep[slot][2]
-        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
-        per, total = self.prepared_samples(slot)  # (a bounded slot: the capacity, spread evenly over the items)
-        room = nb * resample_count(src, rate, total // max(nb, 1)) if bounded else sum(resample_count(src, rate, p) for p in per)
+        per, total = self.pitch_samples(slot)  # (a bounded slot: the capacity of every item)
+        room = sum(resample_count(src, rate, p) for p in per)
         if out is None:
             out = np.empty(max(room, 1), np.int16)
         assert out.dtype == np.int16 and out.size >= room and out.flags.c_contiguous
         prm = PcmParams(float(gain), int(bool(normalize)))
         _check(self.lib.piper_hip_voice_collect_pcm16_rate(self.voice, slot, C.byref(prm), rate, out.ctypes.data_as(c_i16p), room))
         if bounded:  # the true lengths are known now
-            per, total = self.prepared_samples(slot)
+            per, total = self.pitch_samples(slot)
             self._keep[slot] = (self._keep[slot][0], total, False)
         return out[:sum(resample_count(src, rate, p) for p in per)]
 
     def synthesize_pcm16(self, phonemeIDs, durations=None, noise=None, noiseScale=0.667, lengthScale=1.0, noiseW=0.8, gain=1.0,
-                         normalize=False, rate=None, prosody=None, volume=None, level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP, **kw):
+                         normalize=False, rate=None, prosody=None, volume=None, level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP, pitch=None, **kw):
         """synthesize() ending in 16-bit PCM converted on the device (slot 0); rate: at that output rate; prosody: as for prepare;
         level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
@@ -2363,28 +2475,31 @@ class HipRuntime:
             rate = None
         if durations is not None and not kw and rate is not None:  # piper_hip_voice_synthesize_pcm16_rate
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
-            n = resample_count(self.cfg.sample_rate, rate, self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u)))))
+            n = resample_count(self.cfg.sample_rate, rate, self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))), pitch))
             out = np.empty(max(n, 1), np.int16)
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
             self._stage_prosody(0, pro, [len(phonemeIDs)])
             self._stage_volume(0, vol, [len(phonemeIDs)])
+            self._stage_pitch(0, pitch, 1)
             _check(self.lib.piper_hip_voice_synthesize_pcm16_rate(self.voice, C.byref(u), C.byref(prm), int(rate), out.ctypes.data_as(c_i16p), n,
                                                                   C.byref(got)))
             self._keep.pop(0, None)
             return out[:got.value]
         if durations is not None and not kw:  # the one-call C entry point
             u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
-            n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
+            n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))), pitch)
             out = np.empty(max(n, 1), np.int16)
             got = C.c_int64()
             prm = PcmParams(float(gain), int(bool(normalize)))
             self._stage_prosody(0, pro, [len(phonemeIDs)])
             self._stage_volume(0, vol, [len(phonemeIDs)])
+            self._stage_pitch(0, pitch, 1)
             _check(self.lib.piper_hip_voice_synthesize_pcm16(self.voice, C.byref(u), C.byref(prm), out.ctypes.data_as(c_i16p), n, C.byref(got)))
             self._keep.pop(0, None)
             return out[:got.value]
-        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, volume=volume, **kw)
+        self.prepare(0, phonemeIDs, durations, noise, noiseScale, length_scale=lengthScale, noise_w=noiseW, prosody=prosody, volume=volume,
+                     pitch=pitch, **kw)
         self.launch(0)
         return self.collect_pcm16(0, gain, normalize, rate=rate)
 
@@ -2403,21 +2518,20 @@ class HipRuntime:
                 self.voice, slot, C.byref(prm), _law(law), rate, o.ctypes.data_as(c_u8p), room)))
         count = (lambda p: p) if rate == src else (lambda p: resample_count(src, rate, p))
         bounded = len(self._keep[slot]) > 2 and self._keep[slot][2]
-        nb = self.lib.piper_hip_voice_batch_size(self.voice, slot)
-        per, total = self.prepared_samples(slot)  # (a bounded slot: the capacity, spread evenly over the items)
-        room = nb * count(total // max(nb, 1)) if bounded else sum(count(p) for p in per)
+        per, total = self.pitch_samples(slot)  # (a bounded slot: the capacity of every item)
+        room = sum(count(p) for p in per)
         if out is None:
             out = np.empty(max(room, 1), np.uint8)
         assert out.dtype == np.uint8 and out.size >= room and out.flags.c_contiguous
         prm = PcmParams(float(gain), int(bool(normalize)))
         _check(self.lib.piper_hip_voice_collect_g711(self.voice, slot, C.byref(prm), _law(law), rate, out.ctypes.data_as(c_u8p), room))
         if bounded:  # the true lengths are known now
-            per, total = self.prepared_samples(slot)
+            per, total = self.pitch_samples(slot)
             self._keep[slot] = (self._keep[slot][0], total, False)
         return out[:sum(count(p) for p in per)]
 
     def synthesize_g711(self, phonemeIDs, durations, law, noise=None, noiseScale=0.667, gain=1.0, normalize=False, rate=None, prosody=None, volume=None,
-                        level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP):
+                        level=KEEP, loudness=KEEP, eq=KEEP, join=KEEP, pitch=None):
         """synthesize() ending in G.711 bytes companded on the device (piper_hip_voice_synthesize_g711, slot 0), at `rate` or the voice's;
         prosody: as for prepare (with supplied durations: noise alone); level, loudness: as for collect (slot 0)."""
         self._slot_level(0, level)
@@ -2427,7 +2541,7 @@ class HipRuntime:
         src = self.cfg.sample_rate
         rate = src if rate is None else int(rate)
         u, _k = self._utt(phonemeIDs, durations, noise, noiseScale)
-        n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))))
+        n = self._one_call_room(int(self.lib.piper_hip_voice_num_samples(self.voice, C.byref(u))), pitch)
         if rate != src:
             n = resample_count(src, rate, n)
         out = np.empty(max(n, 1), np.uint8)
@@ -2435,6 +2549,7 @@ class HipRuntime:
         prm = PcmParams(float(gain), int(bool(normalize)))
         self._stage_prosody(0, None if prosody is None else [prosody], [len(phonemeIDs)])
         self._stage_volume(0, None if volume is None else [volume], [len(phonemeIDs)])
+        self._stage_pitch(0, pitch, 1)
         _check(self.lib.piper_hip_voice_synthesize_g711(self.voice, C.byref(u), C.byref(prm), _law(law), rate, out.ctypes.data_as(c_u8p), n,
                                                         C.byref(got)))
         self._keep.pop(0, None)

@@ -427,6 +427,47 @@ public final class HIPBackend {
         return c
     }
 
+    // ---- pitch (include/piper_hip.h "Pitch") ----
+
+    /// `count` device floats → N' device floats shifted by `semitones` in [−12, 12] (piper_hip_pitch_f32): the variable-ratio resampler
+    /// of the pitch contract, bit for bit the host twin; no padding.
+    public func pitchF32(input: HIPBuffer, count: Int, semitones: Float, commandBuffer: Stream? = nil) throws -> (out: HIPBuffer, count: Int) {
+        var out: UnsafeMutablePointer<Float>? = nil
+        var n = 0
+        try Self.check(piper_hip_pitch_f32(ctx, input.f32, count, semitones, &out, &n, commandBuffer))
+        return (HIPBuffer(UnsafeMutableRawPointer(out!), ctx: ctx), n)
+    }
+
+    /// The pitch on the host (piper_hip_pitch_from_f32), bit for bit what the device computes.
+    public static func pitchFromF32(_ x: [Float], semitones: Float) throws -> [Float] {
+        let want = piper_hip_pitch_count(semitones, Int64(x.count))
+        if want < 0 { try check(Int32(want)) }
+        var y = [Float](repeating: 0, count: Int(max(want, 1)))
+        var n = 0
+        try check(piper_hip_pitch_from_f32(semitones, x, x.count, &y, Int(want), &n))
+        return Array(y.prefix(n))
+    }
+
+    /// (Q, taps, length factor) of a shift: the 32.32 step, P and rf = (float)(Q / 2^32) (piper_hip_pitch_info; host-only).
+    public static func pitchInfo(semitones: Float) throws -> (step: UInt64, taps: Int32, lengthFactor: Float) {
+        var q: UInt64 = 0, p: Int32 = 0, f: Float = 0
+        try check(piper_hip_pitch_info(semitones, &q, &p, &f))
+        return (q, p, f)
+    }
+
+    /// N': the samples an item of `count` samples yields under a shift (piper_hip_pitch_count; host-only).
+    public static func pitchCount(semitones: Float, count: Int64) throws -> Int64 {
+        let n = piper_hip_pitch_count(semitones, count)
+        if n < 0 { try check(Int32(n)) }
+        return n
+    }
+
+    /// InvalidArgument naming the field for a pitch outside the contract (piper_hip_pitch_check; host-only).
+    public static func pitchCheck(_ pitch: piper_hip_pitch) throws {
+        var p = pitch
+        try check(piper_hip_pitch_check(&p))
+    }
+
     // ---- binary with NumPy broadcasting, output rank ≤ 4 (MetalBackend.swift:2099-2134, 2592-2610) ----
     private func binaryBroadcastF32(_ op: piper_hip_binary_op, a: HIPBuffer, aShape: [Int], b: HIPBuffer, bShape: [Int],
                                     commandBuffer: Stream?) throws -> (out: HIPBuffer, outShape: [Int]) {

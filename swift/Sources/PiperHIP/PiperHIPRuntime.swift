@@ -530,6 +530,23 @@ public final class PiperHIPRuntime {
         return (Array(start.prefix(nb)), Array(len.prefix(nb)), total)
     }
 
+    /// The pitch of the NEXT staging call on slot id `slot` (piper_hip_voice_slot_pitch): entry i for item i, semitones in [−12, 12];
+    /// keep_tempo 1 scales the predicted durations so that the item keeps its length, 0 is varispeed. For prepare* and synthesize*
+    /// (slot 0); the staging call takes the assignment whether or not it succeeds; an empty list clears it. Streams refuse a pending pitch.
+    public func slotPitch(slot: Int32, items: [piper_hip_pitch]) throws {
+        try HIPBackend.check(piper_hip_voice_slot_pitch(voice, slot, items.isEmpty ? nil : items, Int32(items.count)))
+    }
+
+    /// The samples each item of the prepared slot delivers at the voice's rate, F'·hop under a pitch, and their sum
+    /// (piper_hip_voice_pitch_samples): a bounded slot's capacity before collect, the true values after. Collect buffers hold the sum.
+    public func pitchSamples(slot: Int32) throws -> (perItem: [Int64], total: Int64) {
+        let nb = Int(piper_hip_voice_batch_size(voice, slot))
+        var per = [Int64](repeating: 0, count: max(nb, 1))
+        var total: Int64 = 0
+        try HIPBackend.check(piper_hip_voice_pitch_samples(voice, slot, &per, Int32(nb), &total))
+        return (Array(per.prefix(nb)), total)
+    }
+
     /// The EQ of the stream on `slot` (piper_hip_voice_stream_set_eq): where streamSetLevel is allowed, in either order with it.
     public func streamSetEq(slot: Int32, eq: piper_hip_eq) throws {
         var e = eq
