@@ -13,6 +13,7 @@
 // (the reference re-decodes 401 initializers and re-uploads every Conv weight per synthesize: GraphExecutor.swift:187-189,
 // 1774-1780).  Utterances are independent, so a voice has several slots (stream + arena + graph) that overlap on the GPU.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <chrono>
@@ -334,6 +335,73 @@ struct Stream {
   int items() const { return (int)rows.size(); }
 };
 
+// A device buffer of a plan's output chain (in the plan's `owned`) that knows its own size: plan_ensure allocates it on first use and
+// replaces it where it is too small, plan_release gives it back.
+struct PlanBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  template <class T> T* as() const { return (T*)p; }
+};
+
+// The output chain of a whole-item plan: what the stages between the plan's graph and the sinks — volume, pitch, EQ, loudness, level,
+// join, and the peaks of a normalising PCM collect — keep with the plan. chain_walk runs the stages in that order; every stage reads
+// the rows its predecessor hands on and writes rows of its own, in the layout of the plan's audio. The plan's audio stays raw.
+struct OutputChain {
+  // What was computed from the audio of the latest launch. chain_invalidate clears all of it where the plan's audio is new or about to be.
+  bool shaped_ok = false;         // shaped holds the latest launch
+  bool pitched_ok = false;        // pitched and pt_lensF do
+  bool eq_ok = false;             // eqd does, under eq_held
+  bool loud_ok = false;           // loud_seg does, measured behind eq_held
+  std::vector<float> h_peaks;     // [NB] max |x| per item of a normalising collect_pcm16 (empty: none since the last launch)
+  std::vector<int64_t> h_jrep;    // {total, start[NB], len[NB]} of the latest joined collect (empty: none since the last launch)
+  // volume (the staged gains are the plan's vol_gain)
+  PlanBuf shaped;                 // float [NB][n_samples] the items under their envelopes
+  // pitch (piper_hip_voice_slot_pitch), as the plan's latest staging left it (stage_pitch)
+  bool pt_on = false;             // the staging carried a pitch: pt_q holds the items' steps, pt_dev their tables
+  std::vector<uint64_t> pt_q;     // [NB] the 32.32 step per item (kPtOne: the item has no pitch)
+  uint64_t pt_qmin = kPtOne, pt_qmax = kPtOne;  // over the batch, items without a pitch included
+  int pt_pmax = 0;                // the most taps of the batch
+  PlanBuf pt_dev;                 // PtItem [NB] | the [129][P] tables, one per distinct step of the batch
+  PlanBuf pitched;                // float [NB][F'cap·hop] the pitched items, each zero from N' up to its F'·hop
+  PlanBuf pt_lensF;               // int [NB] F' per item, as the kernel wrote them
+  // The row (samples, frames) the buffers of the stages behind the pitch (row_sized) were allocated for: a staging with a lower pitch
+  // makes longer rows, and the walk then gives them all back to be allocated again by the stage that next needs one.
+  int64_t row = 0;
+  int F = 0;
+  // EQ (piper_hip_voice_slot_eq)
+  PlanBuf eqd;                    // float [NB][row] the EQ'd items
+  PlanBuf eq_work;                // double [NB][eq_work_row(F·hop, kEqMaxD)] the block tree
+  PlanBuf eq_dev;                 // EqDesign: the design eqd was filtered with
+  bool eq_on = false;             // the EQ the chain last read the items through: eq_held, or none (the loudness measured behind it too)
+  piper_hip_eq eq_held{};
+  bool eq_dev_ok = false;         // eq_dev holds the design of eq_dev_eq
+  piper_hip_eq eq_dev_eq{};
+  // loudness (piper_hip_voice_slot_loudness, piper_hip_voice_loudness)
+  PlanBuf loud_seg;               // double [NB][ld_work_row(F·hop)] the passes' shares of Σ y² per 100 ms segment
+  PlanBuf loud_rep;               // float [NB][2] {L, g} as the gate kernel last wrote them
+  PlanBuf gained;                 // float [NB][row] the items times their loudness gain
+  // level (piper_hip_voice_slot_level)
+  PlanBuf lim;                    // float [NB][row] the limited items
+  PlanBuf lim_scratch;            // float lv_scratch_floats(NB, F·hop)
+  // join (piper_hip_voice_slot_join)
+  PlanBuf jn_buf;                 // float: the programme
+  PlanBuf jn_dev;                 // JoinParams | report [kJoinReport] | rows [kJoinMaxItems] | edges [2·kJoinMaxItems], total
+  uint64_t jn_gen = 0;            // the slot_join call whose params jn_dev holds (0: none)
+  // normalize = 1
+  PlanBuf peaks;                  // float [NB] max |x| per item
+  std::array<PlanBuf*, 6> row_sized() { return {&eqd, &eq_work, &gained, &loud_seg, &lim, &lim_scratch}; }
+};
+
+// The plan's audio is new, or about to be (a launch, a staging): everything computed from the old audio is stale.
+void chain_invalidate(OutputChain& ch) {
+  ch.h_peaks.clear();
+  ch.loud_ok = false;
+  ch.shaped_ok = false;
+  ch.pitched_ok = false;
+  ch.eq_ok = false;
+  ch.h_jrep.clear();
+}
+
 struct Slot {
   StreamSet set;  // empty (set.stream == nullptr) while the plan is idle: slot_init takes one, give_back_set returns it
   // A Slot is a PLAN: schedule + arena + graph for one bucket (kind, T, F, NB). T and F are the bucket's row lengths; the
@@ -406,55 +474,14 @@ struct Slot {
   // the stream of a full-schedule slot, single (piper_hip_voice_stream_begin) or a group (_stream_begin_batch: one row per item, F copied
   // from h_F); its device buffers are in `owned`, kept across streams and released with the plan
   Stream stream;
-  // 16-bit PCM output (piper_hip_voice_collect_pcm16 / stream_next_pcm16): device buffers of this plan (in `owned`), allocated on first use
+  // 16-bit PCM output (piper_hip_voice_collect_pcm16 / stream_next_pcm16): a device buffer of this plan (in `owned`), allocated on first use
   void* pcm = nullptr;        // the items back to back, as they travel to the host (int16, or one G.711 byte per sample)
   size_t pcm_cap = 0;         // bytes
-  float* peaks = nullptr;     // [NB] max |x| per item (normalize = 1)
-  std::vector<float> h_peaks; // the same on the host after a normalising collect_pcm16 (empty: none since the last launch)
-  // Level control (piper_hip_voice_slot_level): device buffers of this plan (in `owned`), allocated on first use
-  float* lim = nullptr;          // [NB][n_samples] the limited items, the layout of `audio`
-  float* lim_scratch = nullptr;  // lv_scratch_floats(NB, F·hop)
-  // Loudness (piper_hip_voice_slot_loudness, piper_hip_voice_loudness): device buffers of this plan (in `owned`), allocated on first use
-  float* gained = nullptr;       // [NB][n_samples] the items times their loudness gain, the layout of `audio`
-  double* loud_seg = nullptr;    // [NB][ld_work_row(F·hop)] the passes' shares of Σ y² per 100 ms segment of the latest launch's raw items
-  float* loud_rep = nullptr;     // [NB][2] {L, g} as the gate kernel last wrote them
-  bool loud_measured = false;    // loud_seg holds the latest launch (cleared where h_peaks is)
-  // Per-phoneme volume (piper_hip_voice_slot_volume): device buffers of this plan (in `owned`), allocated on first use
+  // Per-phoneme volume (piper_hip_voice_slot_volume): plan inputs staged with the ids, read by the output chain and by the streams alike
   bool vol_on = false;           // the plan's latest staging carried a volume: vol_gain holds its gains
-  float* vol_gain = nullptr;     // [NB][T] the gain per id, staged with the ids (1.0 where an item or an id has none)
-  float* shaped = nullptr;       // [NB][n_samples] the items under their envelopes, the layout of `audio`
-  bool vol_shaped = false;       // shaped holds the latest launch (cleared where h_peaks is)
+  float* vol_gain = nullptr;     // [NB][T] the gain per id (1.0 where an item or an id has none)
   float* vol_gf = nullptr;       // [NB][F] the gain per frame, written for the "vol.gain" tap
-  // Equaliser (piper_hip_voice_slot_eq): device buffers of this plan (in `owned`), allocated on first use
-  float* eqd = nullptr;          // [NB][n_samples] the EQ'd items, the layout of `audio`
-  double* eq_work = nullptr;     // [NB][eq_work_row(F·hop, kEqMaxD)] the block tree
-  EqDesign* eq_dev = nullptr;    // the design eqd was filtered with
-  bool eq_done = false;          // eqd holds the latest launch under eq_held (cleared where h_peaks is)
-  bool eq_on = false;            // the EQ the chain last read the items through: eq_held, or none (the loudness measured behind it too)
-  piper_hip_eq eq_held{};
-  bool eq_dev_ok = false;        // eq_dev holds the design of eq_dev_eq at eq_dev_rate
-  piper_hip_eq eq_dev_eq{};
-  // Join (piper_hip_voice_slot_join): device buffers of this plan (in `owned`), allocated on first use
-  float* jn_buf = nullptr;       // [jn_cap] the programme
-  int64_t jn_cap = 0;            // samples
-  char* jn_dev = nullptr;        // JoinParams | report [kJoinReport] | rows [kJoinMaxItems] | edges [2·kJoinMaxItems], total
-  uint64_t jn_gen = 0;           // the slot_join call whose params jn_dev holds (0: none)
-  std::vector<int64_t> h_jrep;   // {total, start[NB], len[NB]} of the latest joined collect (empty: none since the last launch)
-  // Pitch (piper_hip_voice_slot_pitch): device buffers of this plan (in `owned`), allocated on first use
-  bool pt_on = false;            // the plan's latest staging carried a pitch: pt_q holds the items' steps, pt_dev their tables
-  std::vector<uint64_t> pt_q;    // [NB] the 32.32 step per item (kPtOne: the item has no pitch)
-  uint64_t pt_qmin = kPtOne, pt_qmax = kPtOne;  // over the batch, items without a pitch included
-  int pt_pmax = 0;               // the most taps of the batch
-  char* pt_dev = nullptr;        // PtItem [NB] | the [129][P] tables, one per distinct step of the batch
-  size_t pt_dev_cap = 0;         // bytes
-  float* pitched = nullptr;      // [NB][F'cap·hop] the pitched items, each zero from N' up to its F'·hop
-  size_t pt_cap = 0;             // floats
-  int* pt_lensF = nullptr;       // [NB] F' per item, as the kernel wrote them
-  bool pt_done = false;          // pitched holds the latest launch (cleared where h_peaks is)
-  // The row (samples, frames) the buffers of the stages behind the pitch — eqd, eq_work, gained, loud_seg, lim, lim_scratch — were
-  // allocated for: a staging with a lower pitch makes longer rows, and pitch_audio then gives them back to be allocated again.
-  int64_t chain_row = 0;
-  int chain_F = 0;
+  OutputChain chain;             // everything the whole-item stages between the plan's graph and the sinks keep
 };
 
 // No stream, single or batched, is in progress on the plan any more (a prepare, a detach, a release).
@@ -965,19 +992,17 @@ int ensure_side_streams(Slot& s) {
   return PIPER_HIP_OK;
 }
 
-void slot_release(piper_hip_voice* v, Slot& s, bool all) {
+// The end of a plan: no Slot is used again after it (its callers erase it, or clear the cache).
+void slot_release(piper_hip_voice* v, Slot& s) {
   if (s.exec) { (void)hipGraphExecDestroy(s.exec); s.exec = nullptr; }
   if (s.graph) { (void)hipGraphDestroy(s.graph); s.graph = nullptr; }
   if (s.front_exec) { (void)hipGraphExecDestroy(s.front_exec); s.front_exec = nullptr; }
   if (s.front_graph) { (void)hipGraphDestroy(s.front_graph); s.front_graph = nullptr; }
   s.stream = Stream();  // (no stream any more; its device buffers — descriptor, packed chunks, history, tables — are in `owned`)
   s.zin = nullptr; s.z_out = nullptr;
-  s.pcm = nullptr; s.pcm_cap = 0; s.peaks = nullptr; s.h_peaks.clear();  // (these too)
-  s.lim = nullptr; s.lim_scratch = nullptr;
-  s.gained = nullptr; s.loud_seg = nullptr; s.loud_rep = nullptr; s.loud_measured = false;
-  s.vol_on = false; s.vol_gain = nullptr; s.shaped = nullptr; s.vol_shaped = false; s.vol_gf = nullptr;
-  s.eqd = nullptr; s.eq_work = nullptr; s.eq_dev = nullptr; s.eq_done = false; s.eq_on = false; s.eq_dev_ok = false;
-  s.jn_buf = nullptr; s.jn_cap = 0; s.jn_dev = nullptr; s.jn_gen = 0; s.h_jrep.clear();
+  s.pcm = nullptr; s.pcm_cap = 0;  // (these too)
+  s.vol_on = false; s.vol_gain = nullptr; s.vol_gf = nullptr;
+  s.chain = OutputChain();
   s.dp_noise = nullptr; s.dp_scalars = nullptr; s.dp_dur = nullptr;
   s.spk_in = nullptr; s.spk_g = nullptr; s.spk_bias = nullptr;
   s.pro = false; s.pro_len = s.pro_noise = s.dp_w = nullptr; s.pro_min = s.pro_max = s.pro_fit = nullptr;
@@ -987,11 +1012,10 @@ void slot_release(piper_hip_voice* v, Slot& s, bool all) {
   s.taps.clear();
   s.T = s.F = -1;
   s.built = false;
-  if (all) {  // (the pinned staging buffers are the slot id's: piper_hip_voice::staging)
-    if (s.ev_in) (void)hipEventDestroy(s.ev_in);
-    s.ev_in = nullptr;
-    give_back_set(v, s);  // piper_hip_voice_destroy destroys the sets
-  }
+  // (the pinned staging buffers are the slot id's: piper_hip_voice::staging)
+  if (s.ev_in) (void)hipEventDestroy(s.ev_in);
+  s.ev_in = nullptr;
+  give_back_set(v, s);  // piper_hip_voice_destroy destroys the sets
 }
 
 // Closes the streaming pool of slot id `slot`, if it holds one: waits for the adopts still queued (they write the row stores), then gives
@@ -2068,7 +2092,6 @@ int build_duration_predictor(Builder& b, const float* x) {
 int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind kind = PLAN_WHOLE, bool pro = false) {
   const piper_hip_voice_config& c = v->cfg;
   const int H = c.hidden, I = c.inter;
-  slot_release(v, s, false);
   const GenF32Switches& sw = gen_f32_switches();
   Builder b(v, s, T, F, NB);
   Arena& ar = b.ar;
@@ -2630,7 +2653,7 @@ PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "voice_set_precision: packing failed: %s", hipGetErrorString(e));
   }
-  for (auto& pl : v->plans) slot_release(v, *pl, true);  // every plan was built for the old precision: the next prepare rebuilds
+  for (auto& pl : v->plans) slot_release(v, *pl);  // every plan was built for the old precision: the next prepare rebuilds
   v->plans.clear();
   for (auto& at : v->attached) at = nullptr;
   v->precision = precision;
@@ -2644,7 +2667,7 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
   (void)hipSetDevice(v->ctx->device);
   (void)hipDeviceSynchronize();
   for (int i = 0; i < kMaxSlots; i++) pool_close(v, i);
-  for (auto& pl : v->plans) slot_release(v, *pl, true);
+  for (auto& pl : v->plans) slot_release(v, *pl);
   for (auto& sg : v->staging) {
     if (sg.h_ids) (void)hipHostFree(sg.h_ids);
     if (sg.h_f2i) (void)hipHostFree(sg.h_f2i);
@@ -2726,7 +2749,7 @@ void evict_idle_plans(piper_hip_voice* v) {
     if (victim < 0) return;  // everything is attached: nothing to evict
     Slot& d = *v->plans[victim];
     if (d.set.stream) (void)hipStreamSynchronize(d.set.stream);
-    slot_release(v, d, true);
+    slot_release(v, d);
     v->plans.erase(v->plans.begin() + victim);
   }
 }
@@ -2774,9 +2797,9 @@ int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot
     t_prev = now;
   };
   int rc = slot_init(v, *np);
-  if (rc) { slot_release(v, *np, true); return rc; }
+  if (rc) { slot_release(v, *np); return rc; }
   lap();
-  if ((rc = build_schedule(v, *np, Tb, Fb, NB, kind, pro))) { slot_release(v, *np, true); return rc; }
+  if ((rc = build_schedule(v, *np, Tb, Fb, NB, kind, pro))) { slot_release(v, *np); return rc; }
   lap();
   Slot& s = *np;
   // a plan may be captured / profiled before every input has been uploaded: give the length arrays and index inputs legal values
@@ -2801,7 +2824,7 @@ int acquire_plan(piper_hip_voice* v, PlanKind kind, int Tb, int Fb, int NB, Slot
     if (e == hipSuccess && s.pro_max) e = hipMemsetAsync(s.pro_max, 0, (size_t)NB * Tb * sizeof(int32_t), s.set.stream);
     if (e == hipSuccess && s.pro_fit) e = hipMemsetAsync(s.pro_fit, 0, (size_t)NB * sizeof(int32_t), s.set.stream);
     if (e == hipSuccess) e = stream_wait(s.set.stream);
-    if (e != hipSuccess) { slot_release(v, s, true); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "voice_prepare: arena initialisation failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { slot_release(v, s); PH_FAIL(PIPER_HIP_ERR_LAUNCH, "voice_prepare: arena initialisation failed: %s", hipGetErrorString(e)); }
   }
   lap();
   // No validation pass and no capture here (until round 3 a build ran the schedule once eagerly, waited for it, captured it and
@@ -2977,7 +3000,28 @@ int check_pitch(const PitchItems& pit, const piper_hip_utterance* utts, int n, s
 // The steps and tables of a request with a pitch → the plan's pt_dev, from the slot id's page-locked staging on the plan's stream (which
 // the caller has synchronised: the previous request's copy is done). A request without, or whose entries are all neutral: the plan has none.
 int stage_pitch(piper_hip_voice* v, int slot, Slot& s, const PitchItems& pit, int n, hipStream_t q);
-int pitch_frames(const piper_hip_voice* v, const Slot& s, int b, int frames);
+
+// ---- the geometry of what a whole-item plan delivers
+// Frames of a row of s.audio.
+int row_frames(const piper_hip_voice* v, const Slot& s) { return (int)std::min<int64_t>(s.F, s.n_samples / v->hop); }
+// Frames item b of the plan delivers when it has `frames` of its own: F' = ceil(N' / hop) under the item's pitch, `frames` without one.
+int pitch_frames(const piper_hip_voice* v, const Slot& s, int b, int frames) {
+  if (!s.chain.pt_on || s.chain.pt_q[b] == kPtOne) return frames;
+  return (int)ceil_div(pt_count((int64_t)frames * v->hop, s.chain.pt_q[b]), v->hop);
+}
+// Samples item b delivers, under a pitch or not, when it has `frames` of its own, and at its true length (a bounded slot before its
+// collect: at its capacity).
+int64_t item_samples(const piper_hip_voice* v, const Slot& s, int b, int frames) { return (int64_t)pitch_frames(v, s, b, frames) * v->hop; }
+int64_t item_samples(const piper_hip_voice* v, const Slot& s, int b) { return item_samples(v, s, b, s.h_F[b]); }
+// Samples the latest collect of slot id `slot` delivered, at the voice's rate or through the resampler `rd`: the programme's count where
+// a join reported one, otherwise the items back to back, each at its own true length.
+int64_t delivered_samples(const piper_hip_voice* v, int slot, const Slot& s, const RsDesign* rd = nullptr) {
+  const auto out_len = [&](int64_t samples) { return rd ? rs_count(*rd, samples) : samples; };
+  if (v->slot_jn[slot].on && !s.chain.h_jrep.empty()) return out_len(s.chain.h_jrep[0]);
+  int64_t total = 0;
+  for (int b = 0; b < s.NB; b++) total += out_len(item_samples(v, s, b));
+  return total;
+}
 
 // predict_impl on the predictor plan of requests with prosody (pro non-null), its per-id inputs staged with the ids
 int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
@@ -3133,11 +3177,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   PH_HIP(hipMemcpyAsync(s.lensF, sg.h_lens + n, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);  // noise / scalars come from caller memory
   s.timed = false;
-  s.h_peaks.clear();
-  s.loud_measured = false;
-  s.vol_shaped = false;
-  s.eq_done = false;
-  s.h_jrep.clear();
+  chain_invalidate(s.chain);
   return slot;
 }
 
@@ -3323,11 +3363,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   s.bounded_pending = true;
   s.bounded_cap = std::min(max_frames, F);
   s.timed = false;
-  s.h_peaks.clear();
-  s.loud_measured = false;
-  s.vol_shaped = false;
-  s.eq_done = false;
-  s.h_jrep.clear();
+  chain_invalidate(s.chain);
   return slot;
 }
 
@@ -3492,7 +3528,7 @@ PH_EXPORT int piper_hip_voice_pitch_samples(piper_hip_voice* v, int slot, int64_
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
   int64_t sum = 0;
   for (int b = 0; b < p->NB; b++) {  // (a bounded slot before collect: h_F is the capacity)
-    const int64_t nb = (int64_t)pitch_frames(v, *p, b, p->h_F[b]) * v->hop;
+    const int64_t nb = item_samples(v, *p, b);
     if (per_item && b < max_items) per_item[b] = nb;
     sum += nb;
   }
@@ -3577,9 +3613,27 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__
 int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
 void plan_free(piper_hip_voice* v, Slot& s, void* p, size_t bytes);
 
+void plan_release(piper_hip_voice* v, Slot& s, PlanBuf& b) {
+  if (b.p) plan_free(v, s, b.p, b.bytes);
+  b = PlanBuf();
+}
+
+// `bytes` at least in buffer `b` of the plan's chain: allocated on first use, replaced where it is too small (nothing on the GPU still
+// reads the old one: every collect ends with a wait, and a staging call has waited for the plan's stream). What a stage had computed
+// into it is gone then: `*holds`, where given, is cleared.
+int plan_ensure(piper_hip_voice* v, Slot& s, PlanBuf& b, size_t bytes, bool* holds = nullptr) {
+  if (b.p && b.bytes >= bytes) return PIPER_HIP_OK;
+  void* q = nullptr;
+  if (int rc = plan_alloc(v, s, bytes, &q)) return rc;
+  plan_release(v, s, b);
+  b = PlanBuf{q, bytes};
+  if (holds) *holds = false;
+  return PIPER_HIP_OK;
+}
+
 int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, int n, int T, hipStream_t q) {
   s.vol_on = !vol.empty();
-  s.vol_shaped = false;
+  s.chain.shaped_ok = false;
   if (!s.vol_on) return PIPER_HIP_OK;
   auto& sg = v->staging[slot];
   int rc;
@@ -3597,48 +3651,57 @@ int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, 
   return PIPER_HIP_OK;
 }
 
-// What the output chain of a plan reads for its items: the plan's audio, or — its latest staging carried a volume — shaped [NB][n_samples],
-// v = x·e per item (include/piper_hip.h "Per-phoneme volume"), computed here once per launch behind the plan's graph on its stream, from
-// lengths and the frame-to-id map the device holds (plain, ragged and bounded slots alike). The plan's audio stays raw.
-int volume_audio(piper_hip_voice* v, Slot& s, const float** audio) {
-  *audio = s.audio;
+// ---- the output chain of a whole-item plan: one forward walk over its stages (chain_walk)
+
+// The rows a stage reads and the rows it hands on: [NB][row] floats, item b over lensF[b] frames (device memory) of at most F. Every
+// stage below takes the view of its predecessor in `c` and leaves its own there; a stage that is off leaves `c` as it is. All launches
+// go behind the plan's graph on its stream and read lengths the device holds (plain, ragged and bounded slots alike).
+struct Chain {
+  const float* audio = nullptr;
+  int64_t row = 0;
+  const int* lensF = nullptr;
+  int F = 0;
+};
+
+// The plan's own rows: what the walk starts from, and what a plan without a stage hands to the sinks.
+Chain chain_source(const piper_hip_voice* v, const Slot& s) { return Chain{s.audio, s.n_samples, s.lensF, row_frames(v, s)}; }
+
+// Volume — the plan's latest staging carried one: shaped [NB][n_samples], v = x·e per item (include/piper_hip.h "Per-phoneme volume"),
+// once per launch, from the frame-to-id map the device holds.
+int chain_volume(piper_hip_voice* v, Slot& s, Chain& c) {
+  OutputChain& ch = s.chain;
   if (!s.vol_on) return PIPER_HIP_OK;
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
-  if (F < 1 || !s.vol_gain || !s.frame2id || !s.lensF) PH_FAIL(PIPER_HIP_ERR_SHAPE, "volume: the slot holds no samples to shape");
-  if (!s.shaped) {
-    void* q = nullptr;
-    if (int rc = plan_alloc(v, s, (size_t)s.NB * s.n_samples * sizeof(float), &q)) return rc;
-    s.shaped = (float*)q;
-    s.vol_shaped = false;
-  }
-  if (!s.vol_shaped) {
-    PH_HIP(launch_volume_items(s.set.stream, s.audio, s.n_samples, s.lensF, F, v->hop, s.NB, s.frame2id, s.F, s.vol_gain, s.T, s.shaped,
-                               s.n_samples),
+  if (c.F < 1 || !s.vol_gain || !s.frame2id || !s.lensF) PH_FAIL(PIPER_HIP_ERR_SHAPE, "volume: the slot holds no samples to shape");
+  if (int rc = plan_ensure(v, s, ch.shaped, (size_t)s.NB * s.n_samples * sizeof(float), &ch.shaped_ok)) return rc;
+  if (!ch.shaped_ok) {
+    PH_HIP(launch_volume_items(s.set.stream, c.audio, c.row, c.lensF, c.F, v->hop, s.NB, s.frame2id, s.F, s.vol_gain, s.T,
+                               ch.shaped.as<float>(), s.n_samples),
            PIPER_HIP_ERR_LAUNCH);
-    s.vol_shaped = true;
+    ch.shaped_ok = true;
   }
-  *audio = s.shaped;
+  c.audio = ch.shaped.as<float>();
   return PIPER_HIP_OK;
 }
 
 int stage_pitch(piper_hip_voice* v, int slot, Slot& s, const PitchItems& pit, int n, hipStream_t q) {
-  s.pt_on = false;
-  s.pt_done = false;
-  s.pt_q.assign((size_t)s.NB, kPtOne);
-  s.pt_qmin = s.pt_qmax = kPtOne;
-  s.pt_pmax = 0;
+  OutputChain& ch = s.chain;
+  ch.pt_on = false;
+  ch.pitched_ok = false;
+  ch.pt_q.assign((size_t)s.NB, kPtOne);
+  ch.pt_qmin = ch.pt_qmax = kPtOne;
+  ch.pt_pmax = 0;
   std::vector<const PtDesign*> tabs;  // one per distinct step of the batch
   int rc;
   for (int b = 0; b < n && b < (int)pit.size(); b++) {
     uint64_t Q;
     if ((rc = pt_step("pitch", pit[b].semitones, &Q))) return rc;
     if (Q == kPtOne) continue;  // not a filter: the item has no pitch
-    s.pt_q[b] = Q;
-    s.pt_qmin = std::min(s.pt_qmin, Q);
-    s.pt_qmax = std::max(s.pt_qmax, Q);
+    ch.pt_q[b] = Q;
+    ch.pt_qmin = std::min(ch.pt_qmin, Q);
+    ch.pt_qmax = std::max(ch.pt_qmax, Q);
     const PtDesign* d = nullptr;
     if ((rc = pt_design(Q, &d))) return rc;
-    s.pt_pmax = std::max(s.pt_pmax, d->P);
+    ch.pt_pmax = std::max(ch.pt_pmax, d->P);
     if (std::find(tabs.begin(), tabs.end(), d) == tabs.end()) tabs.push_back(d);
   }
   if (tabs.empty()) return PIPER_HIP_OK;
@@ -3647,236 +3710,170 @@ int stage_pitch(piper_hip_voice* v, int slot, Slot& s, const PitchItems& pit, in
   for (const PtDesign* d : tabs) bytes += (d->taps.size() * sizeof(float) + 15) & ~(size_t)15;
   auto& sg = v->staging[slot];
   if ((rc = grow_pinned(sg.h_pt, sg.cap_pt, bytes))) return rc;
-  if (s.pt_dev_cap < bytes) {  // (nothing on the GPU still reads the old one: the caller has waited for the plan's stream)
-    void* p = nullptr;
-    if ((rc = plan_alloc(v, s, bytes, &p))) return rc;
-    if (s.pt_dev) plan_free(v, s, s.pt_dev, s.pt_dev_cap);
-    s.pt_dev = (char*)p;
-    s.pt_dev_cap = bytes;
-  }
+  if ((rc = plan_ensure(v, s, ch.pt_dev, bytes))) return rc;
+  char* const dev = ch.pt_dev.as<char>();
   PtItem* items = (PtItem*)sg.h_pt;
   for (int b = 0; b < s.NB; b++) items[b] = PtItem{nullptr, kPtOne, 0, 0};
   size_t off = head;
   for (const PtDesign* d : tabs) {
     memcpy(sg.h_pt + off, d->taps.data(), d->taps.size() * sizeof(float));
     for (int b = 0; b < s.NB; b++)
-      if (s.pt_q[b] == d->Q) items[b] = PtItem{(const float*)(s.pt_dev + off), d->Q, d->P, 0};
+      if (ch.pt_q[b] == d->Q) items[b] = PtItem{(const float*)(dev + off), d->Q, d->P, 0};
     off += (d->taps.size() * sizeof(float) + 15) & ~(size_t)15;
   }
-  PH_HIP(hipMemcpyAsync(s.pt_dev, sg.h_pt, bytes, hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  s.pt_on = true;
+  PH_HIP(hipMemcpyAsync(dev, sg.h_pt, bytes, hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  ch.pt_on = true;
   return PIPER_HIP_OK;
 }
 
-// Frames item b of the plan delivers when it has `frames` of its own: F' = ceil(N' / hop) under the item's pitch, `frames` without one.
-int pitch_frames(const piper_hip_voice* v, const Slot& s, int b, int frames) {
-  if (!s.pt_on || s.pt_q[b] == kPtOne) return frames;
-  return (int)ceil_div(pt_count((int64_t)frames * v->hop, s.pt_q[b]), v->hop);
+// The geometry of the rows behind the pitch without a launch, over the plan's own audio and lengths: what the host-side bounds of the
+// sinks are taken from. A plan without a pitch: exactly the plan's own rows.
+Chain chain_geometry(const piper_hip_voice* v, const Slot& s) {
+  Chain c = chain_source(v, s);
+  if (!s.chain.pt_on || c.F < 1) return c;
+  c.F = (int)ceil_div(pt_count((int64_t)c.F * v->hop, s.chain.pt_qmin), v->hop);  // the plan's frame bucket under the least step of the batch
+  c.row = (int64_t)c.F * v->hop;
+  return c;
 }
 
-// The rows every stage behind the pitch reads: [NB][row] floats, item b over lensF[b] frames (device memory) of at most F.
-struct Chain {
-  const float* audio = nullptr;
-  int64_t row = 0;
-  const int* lensF = nullptr;
-  int F = 0;
-};
-
-// The geometry of pitch_audio's rows without a launch: what the host-side bounds of the later stages are taken from.
-void chain_geometry(const piper_hip_voice* v, const Slot& s, int64_t* row, int* F) {
-  *F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
-  *row = s.n_samples;
-  if (!s.pt_on || *F < 1) return;
-  *F = (int)ceil_div(pt_count((int64_t)*F * v->hop, s.pt_qmin), v->hop);  // the plan's frame bucket under the least step of the batch
-  *row = (int64_t)*F * v->hop;
-}
-
-// What the stages behind the pitch read for a plan's items, and the single owner of their geometry: volume_audio's rows at the plan's
-// own lengths, or — the plan's latest staging carried a pitch — pitched [NB][F'cap·hop] with the frame counts the kernel wrote, computed
-// here once per launch behind the plan's graph on its stream, from lengths the device holds (plain, ragged and bounded slots alike).
-// A plan without a pitch hands out exactly the plan's own rows, stride, lengths and frames.
-int pitch_audio(piper_hip_voice* v, Slot& s, Chain* c) {
-  const float* x = s.audio;
-  int rc = volume_audio(v, s, &x);
-  if (rc) return rc;
-  c->audio = x;
-  c->lensF = s.lensF;
-  chain_geometry(v, s, &c->row, &c->F);
-  if (c->row > s.chain_row) {
-    // the later stages' buffers were allocated for shorter rows (nothing on the GPU still reads them: every collect ends with a wait)
-    const size_t items = (size_t)s.NB * s.chain_row * sizeof(float);
-    const int64_t n_old = (int64_t)s.chain_F * v->hop;
-    if (s.eqd) plan_free(v, s, s.eqd, items);
-    if (s.eq_work) plan_free(v, s, s.eq_work, (size_t)s.NB * eq_work_row(n_old, kEqMaxD) * sizeof(double));
-    if (s.gained) plan_free(v, s, s.gained, items);
-    if (s.loud_seg) plan_free(v, s, s.loud_seg, (size_t)s.NB * ld_work_row(n_old) * sizeof(double));
-    if (s.lim) plan_free(v, s, s.lim, items);
-    if (s.lim_scratch) plan_free(v, s, s.lim_scratch, lv_scratch_floats(s.NB, n_old) * sizeof(float));
-    s.eqd = s.gained = s.lim = s.lim_scratch = nullptr;
-    s.eq_work = s.loud_seg = nullptr;
-    s.eq_done = false;
-    s.loud_measured = false;
-    s.chain_row = c->row;
-    s.chain_F = c->F;
+// Pitch, and the single owner of the geometry of every later stage — the plan's latest staging carried one: pitched [NB][F'cap·hop] with
+// the frame counts the kernel wrote, once per launch. Where the rows have grown, the row-sized buffers of the later stages go back.
+int chain_pitch(piper_hip_voice* v, Slot& s, Chain& c) {
+  OutputChain& ch = s.chain;
+  const Chain g = chain_geometry(v, s);
+  if (g.row > ch.row) {
+    for (PlanBuf* b : ch.row_sized()) plan_release(v, s, *b);
+    ch.eq_ok = false;
+    ch.loud_ok = false;
+    ch.row = g.row;
+    ch.F = g.F;
   }
-  if (!s.pt_on) return PIPER_HIP_OK;
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);
-  if (F < 1 || !s.pt_dev || !s.lensF) PH_FAIL(PIPER_HIP_ERR_SHAPE, "pitch: the slot holds no samples to shift");
-  void* q = nullptr;
-  if (s.pt_cap < (size_t)s.NB * c->row) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * c->row * sizeof(float), &q))) return rc;
-    if (s.pitched) plan_free(v, s, s.pitched, s.pt_cap * sizeof(float));
-    s.pitched = (float*)q;
-    s.pt_cap = (size_t)s.NB * c->row;
-    s.pt_done = false;
-  }
-  if (!s.pt_lensF) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * sizeof(int), &q))) return rc;
-    s.pt_lensF = (int*)q;
-    s.pt_done = false;
-  }
-  if (!s.pt_done) {
-    PH_HIP(launch_pitch_items(s.set.stream, x, s.n_samples, s.lensF, F, v->hop, s.NB, 0, (const PtItem*)s.pt_dev, PtItem{}, s.pt_qmin, s.pt_qmax,
-                              s.pt_pmax, s.pitched, c->row, s.pt_lensF),
+  if (!ch.pt_on) return PIPER_HIP_OK;
+  if (c.F < 1 || !ch.pt_dev.p || !s.lensF) PH_FAIL(PIPER_HIP_ERR_SHAPE, "pitch: the slot holds no samples to shift");
+  int rc;
+  if ((rc = plan_ensure(v, s, ch.pitched, (size_t)s.NB * g.row * sizeof(float), &ch.pitched_ok))) return rc;
+  if ((rc = plan_ensure(v, s, ch.pt_lensF, (size_t)s.NB * sizeof(int), &ch.pitched_ok))) return rc;
+  if (!ch.pitched_ok) {
+    PH_HIP(launch_pitch_items(s.set.stream, c.audio, c.row, c.lensF, c.F, v->hop, s.NB, 0, ch.pt_dev.as<const PtItem>(), PtItem{}, ch.pt_qmin,
+                              ch.pt_qmax, ch.pt_pmax, ch.pitched.as<float>(), g.row, ch.pt_lensF.as<int>()),
            PIPER_HIP_ERR_LAUNCH);
-    s.pt_done = true;
+    ch.pitched_ok = true;
   }
-  c->audio = s.pitched;
-  c->lensF = s.pt_lensF;
+  c = Chain{ch.pitched.as<float>(), g.row, ch.pt_lensF.as<int>(), g.F};
   return PIPER_HIP_OK;
 }
 
-// What the stages behind the EQ read for a slot id's items: pitch_audio's, or — the slot id has an EQ (piper_hip_voice_slot_eq) — eqd
-// [NB][row], computed here behind the plan's graph on its stream from lengths the device holds (plain, ragged and bounded slots
-// alike), once per launch and EQ. Whenever the EQ the chain reads through changes, the loudness measured behind it is dropped.
-int eq_audio(piper_hip_voice* v, int slot, Slot& s, Chain* c) {
-  int rc = pitch_audio(v, s, c);
-  if (rc) return rc;
-  const float* x = c->audio;
+// Settings of a slot id on their way to a plan: one T in the slot id's page-locked `host`, written by `fill`, then copied to `dev` on q.
+// The staging buffer is rewritten only once the copy queued from it last time has run (`ev`), even where that call failed before its wait.
+template <class T, class Fill>
+int upload_settings(T*& host, size_t& cap, hipEvent_t& ev, void* dev, hipStream_t q, Fill fill) {
+  if (ev) PH_HIP(hipEventSynchronize(ev), PIPER_HIP_ERR_LAUNCH);
+  else PH_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+  int rc;
+  if ((rc = grow_pinned(host, cap, 1, 1)) || (rc = fill(host))) return rc;
+  PH_HIP(hipMemcpyAsync(dev, host, sizeof(T), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipEventRecord(ev, q), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
+// EQ — the slot id has one (piper_hip_voice_slot_eq): eqd [NB][row], once per launch and EQ. Whenever the EQ the chain reads through
+// changes, the loudness measured behind it is dropped.
+int chain_eq(piper_hip_voice* v, int slot, Slot& s, Chain& c) {
+  OutputChain& ch = s.chain;
   const auto& se = v->slot_eq[slot];
-  if (s.eq_on != se.on || (se.on && memcmp(&s.eq_held, &se.eq, sizeof(piper_hip_eq)) != 0)) {
-    s.eq_on = se.on;
-    s.eq_held = se.eq;
-    s.eq_done = false;
-    s.loud_measured = false;
+  if (ch.eq_on != se.on || (se.on && memcmp(&ch.eq_held, &se.eq, sizeof(piper_hip_eq)) != 0)) {
+    ch.eq_on = se.on;
+    ch.eq_held = se.eq;
+    ch.eq_ok = false;
+    ch.loud_ok = false;
   }
   if (!se.on) return PIPER_HIP_OK;
-  const int F = c->F;  // frames of a row of the items
-  if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "eq: the slot holds no samples to filter");
-  void* q = nullptr;
-  if (!s.eqd) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.chain_row * sizeof(float), &q))) return rc;
-    s.eqd = (float*)q;
-    s.eq_done = false;
-  }
-  if (!s.eq_work) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * eq_work_row((int64_t)s.chain_F * v->hop, kEqMaxD) * sizeof(double), &q))) return rc;
-    s.eq_work = (double*)q;
-  }
-  if (!s.eq_dev) {
-    if ((rc = plan_alloc(v, s, sizeof(EqDesign), &q))) return rc;
-    s.eq_dev = (EqDesign*)q;
-    s.eq_dev_ok = false;
-  }
-  if (!s.eq_done) {
-    if (!s.eq_dev_ok || memcmp(&s.eq_dev_eq, &se.eq, sizeof(piper_hip_eq)) != 0) {
-      // (the staging buffer is rewritten only once the copy queued from it last time has run, even where that call failed before its wait)
+  if (c.F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "eq: the slot holds no samples to filter");
+  int rc;
+  if ((rc = plan_ensure(v, s, ch.eqd, (size_t)s.NB * ch.row * sizeof(float), &ch.eq_ok))) return rc;
+  if ((rc = plan_ensure(v, s, ch.eq_work, (size_t)s.NB * eq_work_row((int64_t)ch.F * v->hop, kEqMaxD) * sizeof(double)))) return rc;
+  if ((rc = plan_ensure(v, s, ch.eq_dev, sizeof(EqDesign), &ch.eq_dev_ok))) return rc;
+  if (!ch.eq_ok) {
+    if (!ch.eq_dev_ok || memcmp(&ch.eq_dev_eq, &se.eq, sizeof(piper_hip_eq)) != 0) {
       auto& sg = v->staging[slot];
-      if (sg.eq_ev) PH_HIP(hipEventSynchronize(sg.eq_ev), PIPER_HIP_ERR_LAUNCH);
-      else PH_HIP(hipEventCreateWithFlags(&sg.eq_ev, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
-      if ((rc = grow_pinned(sg.h_eq, sg.cap_eq, 1, 1))) return rc;
-      if ((rc = eq_build(&se.eq, v->cfg.sample_rate, sg.h_eq))) return rc;
-      PH_HIP(hipMemcpyAsync(s.eq_dev, sg.h_eq, sizeof(EqDesign), hipMemcpyHostToDevice, s.set.stream), PIPER_HIP_ERR_LAUNCH);
-      PH_HIP(hipEventRecord(sg.eq_ev, s.set.stream), PIPER_HIP_ERR_LAUNCH);
-      s.eq_dev_ok = true;
-      s.eq_dev_eq = se.eq;
+      if ((rc = upload_settings(sg.h_eq, sg.cap_eq, sg.eq_ev, ch.eq_dev.p, s.set.stream,
+                                [&](EqDesign* d) { return eq_build(&se.eq, v->cfg.sample_rate, d); })))
+        return rc;
+      ch.eq_dev_ok = true;
+      ch.eq_dev_eq = se.eq;
     }
-    PH_HIP(launch_eq_items(s.set.stream, x, c->row, c->lensF, F, v->hop, s.NB, 0, s.eq_dev, se.eq.n,
-                           s.eq_work, s.eqd, c->row),
+    PH_HIP(launch_eq_items(s.set.stream, c.audio, c.row, c.lensF, c.F, v->hop, s.NB, 0, ch.eq_dev.as<EqDesign>(), se.eq.n,
+                           ch.eq_work.as<double>(), ch.eqd.as<float>(), c.row),
            PIPER_HIP_ERR_LAUNCH);
-    s.eq_done = true;
+    ch.eq_ok = true;
   }
-  c->audio = s.eqd;
+  c.audio = ch.eqd.as<float>();
   return PIPER_HIP_OK;
 }
 
-// {L, g} of the items the loudness stage reads — the plan's audio, shaped by the staging's volume and filtered by the slot id's EQ where
-// there are such — into s.loud_rep, behind the plan's graph on its stream, from lengths the device holds: the K-weighted
-// segment powers once per launch, the gates and the gain of target `t` every time (include/piper_hip.h "Loudness").
-int loudness_measure(piper_hip_voice* v, int slot, Slot& s, const LdTarget& t) {
-  LdFilter f;
-  int rc = ld_filter(v->cfg.sample_rate, &f);
-  if (rc) return rc;
-  Chain c;  // (a plan whose staging carried a volume or a pitch: the shaped, pitched items; a slot id with an EQ: the EQ'd ones)
-  if ((rc = eq_audio(v, slot, s, &c))) return rc;  // (first: a change of the slot id's EQ invalidates the measurement)
-  const float* x = c.audio;
-  const int F = c.F;  // frames of a row of the items
-  if (F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "loudness: the slot holds no samples");
-  void* q = nullptr;
-  if (!s.loud_seg) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * ld_work_row((int64_t)s.chain_F * v->hop) * sizeof(double), &q))) return rc;
-    s.loud_seg = (double*)q;
-    s.loud_measured = false;
+// {L, g} of the rows `c` (what the walk hands out behind the EQ) into loud_rep: the K-weighted segment powers once per launch, the
+// gates and the gain of target `t` every time (include/piper_hip.h "Loudness").
+int chain_measure(piper_hip_voice* v, Slot& s, const Chain& c, const LdFilter& f, const LdTarget& t) {
+  OutputChain& ch = s.chain;
+  if (c.F < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "loudness: the slot holds no samples");
+  int rc;
+  if ((rc = plan_ensure(v, s, ch.loud_seg, (size_t)s.NB * ld_work_row((int64_t)ch.F * v->hop) * sizeof(double), &ch.loud_ok))) return rc;
+  if ((rc = plan_ensure(v, s, ch.loud_rep, (size_t)s.NB * 2 * sizeof(float)))) return rc;
+  if (!ch.loud_ok) {
+    PH_HIP(launch_loudness_measure(s.set.stream, c.audio, c.row, c.lensF, c.F, v->hop, s.NB, 0, f, ch.loud_seg.as<double>()), PIPER_HIP_ERR_LAUNCH);
+    ch.loud_ok = true;
   }
-  if (!s.loud_rep) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * 2 * sizeof(float), &q))) return rc;
-    s.loud_rep = (float*)q;
-  }
-  if (!s.loud_measured) {
-    PH_HIP(launch_loudness_measure(s.set.stream, x, c.row, c.lensF, F, v->hop, s.NB, 0, f, s.loud_seg), PIPER_HIP_ERR_LAUNCH);
-    s.loud_measured = true;
-  }
-  PH_HIP(launch_loudness_gate(s.set.stream, c.lensF, F, v->hop, s.NB, 0, f.h, s.loud_seg, t, s.loud_rep), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(launch_loudness_gate(s.set.stream, c.lensF, c.F, v->hop, s.NB, 0, f.h, ch.loud_seg.as<double>(), t, ch.loud_rep.as<float>()),
+         PIPER_HIP_ERR_LAUNCH);
   return PIPER_HIP_OK;
 }
 
-// The items a slot id with a loudness target (piper_hip_voice_slot_loudness) hands the rest of the output chain: gained [NB][n_samples],
-// u = x·g per item. Without a target: the plan's audio (x: the shaped items where the plan's staging carried a volume).
-int loudness_audio(piper_hip_voice* v, int slot, Slot& s, Chain* c) {
-  int rc = eq_audio(v, slot, s, c);  // (a plan whose staging carried a volume or a pitch: the shaped, pitched items; a slot id with an EQ: the EQ'd ones)
-  if (rc) return rc;
-  const float* x = c->audio;
+// Loudness — the slot id has a target (piper_hip_voice_slot_loudness): measure, gate, then gained [NB][row], u = x·g per item.
+int chain_loudness(piper_hip_voice* v, int slot, Slot& s, Chain& c) {
+  OutputChain& ch = s.chain;
   const auto& sl = v->slot_ld[slot];
   if (!sl.on) return PIPER_HIP_OK;
   LdTarget t;
-  if ((rc = ld_resolve(&sl.ld, &t))) return rc;
-  const int F = c->F;
-  if (F < 1) return PIPER_HIP_OK;
-  if ((rc = loudness_measure(v, slot, s, t))) return rc;
-  if (!s.gained) {
-    void* q = nullptr;
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.chain_row * sizeof(float), &q))) return rc;
-    s.gained = (float*)q;
-  }
-  PH_HIP(launch_loudness_gain(s.set.stream, x, c->row, c->lensF, F, v->hop, s.NB, s.loud_rep, s.gained, c->row), PIPER_HIP_ERR_LAUNCH);
-  c->audio = s.gained;
+  int rc = ld_resolve(&sl.ld, &t);
+  if (rc) return rc;
+  if (c.F < 1) return PIPER_HIP_OK;
+  LdFilter f;
+  if ((rc = ld_filter(v->cfg.sample_rate, &f)) || (rc = chain_measure(v, s, c, f, t))) return rc;
+  if ((rc = plan_ensure(v, s, ch.gained, (size_t)s.NB * ch.row * sizeof(float)))) return rc;
+  PH_HIP(launch_loudness_gain(s.set.stream, c.audio, c.row, c.lensF, c.F, v->hop, s.NB, ch.loud_rep.as<float>(), ch.gained.as<float>(), c.row),
+         PIPER_HIP_ERR_LAUNCH);
+  c.audio = ch.gained.as<float>();
   return PIPER_HIP_OK;
 }
 
-// What a collect of slot id `slot` reads: the plan's audio, or — the slot id has a loudness target — the gained items, or — the slot id has
-// a level (piper_hip_voice_slot_level) — the limited (gained) items lim [NB][n_samples], computed here behind the plan's graph on its
-// stream from lengths the device holds (plain, ragged and bounded slots alike). The plan's audio stays raw.
-int level_audio(piper_hip_voice* v, int slot, Slot& s, Chain* c) {
-  if (int lrc = loudness_audio(v, slot, s, c)) return lrc;
-  const float* src = c->audio;
+// Level — the slot id has one (piper_hip_voice_slot_level): lim [NB][row], the limited items.
+int chain_level(piper_hip_voice* v, int slot, Slot& s, Chain& c) {
+  OutputChain& ch = s.chain;
   const auto& sl = v->slot_lv[slot];
   if (!sl.on) return PIPER_HIP_OK;
   LvParams p;
   int rc = lv_resolve(&sl.lv, v->cfg.sample_rate, &p);
   if (rc) return rc;
-  const int F = c->F;  // frames of a row of the items
-  if (F < 1) return PIPER_HIP_OK;
-  void* q = nullptr;
-  if (!s.lim) {
-    if ((rc = plan_alloc(v, s, (size_t)s.NB * s.chain_row * sizeof(float), &q))) return rc;
-    s.lim = (float*)q;
-  }
-  if (!s.lim_scratch) {
-    if ((rc = plan_alloc(v, s, lv_scratch_floats(s.NB, (int64_t)s.chain_F * v->hop) * sizeof(float), &q))) return rc;
-    s.lim_scratch = (float*)q;
-  }
-  PH_HIP(launch_level_items(s.set.stream, src, c->row, c->lensF, F, v->hop, s.NB, 0, p, s.lim_scratch, s.lim, c->row), PIPER_HIP_ERR_LAUNCH);
-  c->audio = s.lim;
+  if (c.F < 1) return PIPER_HIP_OK;
+  if ((rc = plan_ensure(v, s, ch.lim, (size_t)s.NB * ch.row * sizeof(float)))) return rc;
+  if ((rc = plan_ensure(v, s, ch.lim_scratch, lv_scratch_floats(s.NB, (int64_t)ch.F * v->hop) * sizeof(float)))) return rc;
+  PH_HIP(launch_level_items(s.set.stream, c.audio, c.row, c.lensF, c.F, v->hop, s.NB, 0, p, ch.lim_scratch.as<float>(), ch.lim.as<float>(), c.row),
+         PIPER_HIP_ERR_LAUNCH);
+  c.audio = ch.lim.as<float>();
+  return PIPER_HIP_OK;
+}
+
+// The walk: volume, pitch, EQ — `behind_eq` receives that view, what piper_hip_voice_loudness measures and normalize = 1 takes its
+// peaks from — and, where `items` is given, on through loudness and level to what the sinks and the join read. A plan and a slot id with
+// no stage: the plan's own rows, and nothing is launched or allocated.
+int chain_walk(piper_hip_voice* v, int slot, Slot& s, Chain* behind_eq, Chain* items) {
+  Chain c = chain_source(v, s);
+  int rc;
+  if ((rc = chain_volume(v, s, c)) || (rc = chain_pitch(v, s, c)) || (rc = chain_eq(v, slot, s, c))) return rc;
+  if (behind_eq) *behind_eq = c;
+  if (!items) return PIPER_HIP_OK;
+  if ((rc = chain_loudness(v, slot, s, c)) || (rc = chain_level(v, slot, s, c))) return rc;
+  *items = c;
   return PIPER_HIP_OK;
 }
 
@@ -3887,9 +3884,9 @@ int level_audio(piper_hip_voice* v, int slot, Slot& s, Chain* c) {
 int join_capacity(const piper_hip_voice* v, int slot, const Slot& s, int64_t* cap) {
   const auto& sj = v->slot_jn[slot];
   if (s.NB > kJoinMaxItems) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join: %d items (at most %d)", s.NB, kJoinMaxItems);
-  const int F = (int)std::min<int64_t>(s.F, s.n_samples / v->hop);  // frames of a row of s.audio
+  const int F = row_frames(v, s);
   int64_t sum = 0;  // (under a pitch: of the pitched items)
-  for (int b = 0; b < s.NB; b++) sum += (int64_t)pitch_frames(v, s, b, s.bounded_pending ? F : std::min(s.h_F[b], F)) * v->hop;
+  for (int b = 0; b < s.NB; b++) sum += item_samples(v, s, b, s.bounded_pending ? F : std::min(s.h_F[b], F));
   *cap = join_bound(sj.p, s.NB, sum);
   if (*cap > INT_MAX) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join: a programme of up to %lld samples does not fit an int", (long long)*cap);
   return PIPER_HIP_OK;
@@ -3902,54 +3899,38 @@ struct Joined {
   int64_t cap = 0;
 };
 
-// The join of slot id `slot` over `items` (the layout of s.audio: what level_audio handed out) behind the plan's graph on its stream,
-// from lengths the device holds. The report lands in the slot id's page-locked h_jrep — through its mapping where there is one, else by
-// a copy behind the launches — and is the host's once the stream has been waited for (join_landed).
-int join_items(piper_hip_voice* v, int slot, Slot& s, const Chain& items, Joined* out) {
+// The join of slot id `slot` over `items` (what the walk handed out) into a programme of at most `cap` samples (join_capacity), behind
+// the plan's graph on its stream, from lengths the device holds. The report lands in the slot id's page-locked h_jrep — through its
+// mapping where there is one, else by a copy behind the launches — and is the host's once the stream has been waited for (join_landed).
+int join_items(piper_hip_voice* v, int slot, Slot& s, const Chain& items, int64_t cap, Joined* out) {
+  OutputChain& ch = s.chain;
   const auto& sj = v->slot_jn[slot];
   auto& sg = v->staging[slot];
-  int64_t cap = 0;
-  int rc = join_capacity(v, slot, s, &cap);
-  if (rc) return rc;
   const int F = items.F;
-  void* q = nullptr;
-  if (s.jn_cap < std::max<int64_t>(cap, 1)) {  // (nothing on the GPU still reads the old one: every collect ends with a wait)
-    if ((rc = plan_alloc(v, s, (size_t)std::max<int64_t>(cap, 1) * sizeof(float), &q))) return rc;
-    if (s.jn_buf) plan_free(v, s, s.jn_buf, (size_t)s.jn_cap * sizeof(float));
-    s.jn_buf = (float*)q;
-    s.jn_cap = std::max<int64_t>(cap, 1);
-  }
+  int rc;
+  if ((rc = plan_ensure(v, s, ch.jn_buf, (size_t)std::max<int64_t>(cap, 1) * sizeof(float)))) return rc;
   const size_t o_rep = sizeof(JoinParams), o_rows = o_rep + (size_t)kJoinReport * sizeof(int64_t);
   const size_t o_edges = o_rows + (size_t)kJoinMaxItems * sizeof(JoinRow);
-  if (!s.jn_dev) {
-    if ((rc = plan_alloc(v, s, o_edges + (2 * (size_t)kJoinMaxItems + 1) * sizeof(int), &q))) return rc;
-    s.jn_dev = (char*)q;
-    s.jn_gen = 0;
-  }
+  if ((rc = plan_ensure(v, s, ch.jn_dev, o_edges + (2 * (size_t)kJoinMaxItems + 1) * sizeof(int)))) return rc;  // (allocated once: jn_gen is 0 then)
+  char* const dev = ch.jn_dev.as<char>();
   const hipStream_t st = s.set.stream;
-  if (s.jn_gen != sj.gen) {
-    // (the staging buffer is rewritten only once the copy queued from it last time has run)
-    if (sg.join_ev) PH_HIP(hipEventSynchronize(sg.join_ev), PIPER_HIP_ERR_LAUNCH);
-    else PH_HIP(hipEventCreateWithFlags(&sg.join_ev, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
-    if ((rc = grow_pinned(sg.h_join, sg.cap_join, 1, 1))) return rc;
-    *sg.h_join = sj.p;
-    PH_HIP(hipMemcpyAsync(s.jn_dev, sg.h_join, sizeof(JoinParams), hipMemcpyHostToDevice, st), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipEventRecord(sg.join_ev, st), PIPER_HIP_ERR_LAUNCH);
-    s.jn_gen = sj.gen;
+  if (ch.jn_gen != sj.gen) {
+    if ((rc = upload_settings(sg.h_join, sg.cap_join, sg.join_ev, dev, st, [&](JoinParams* p) { *p = sj.p; return PIPER_HIP_OK; }))) return rc;
+    ch.jn_gen = sj.gen;
   }
   if ((rc = grow_pinned(sg.h_jrep, sg.cap_jrep, (size_t)kJoinReport, (size_t)kJoinReport))) return rc;
   int64_t* rep_host = nullptr;
   if (hipHostGetDevicePointer((void**)&rep_host, sg.h_jrep, 0) != hipSuccess) { rep_host = nullptr; (void)hipGetLastError(); }
   int64_t z = sj.p.tail;
   for (int b = 0; b + 1 < s.NB; b++) z = std::max(z, sj.p.gap[b]);
-  int* edges = (int*)(s.jn_dev + o_edges);
+  int* edges = (int*)(dev + o_edges);
   const JoinSrc src{items.audio, items.row, items.lensF, F, v->hop, nullptr, nullptr};
-  PH_HIP(launch_join(st, src, s.NB, (int64_t)F * v->hop, sj.p.lead + z, (const JoinParams*)s.jn_dev, sj.p.trim != 0, edges,
-                     (JoinRow*)(s.jn_dev + o_rows), edges + 2 * kJoinMaxItems, (int64_t*)(s.jn_dev + o_rep), rep_host, s.jn_buf),
+  PH_HIP(launch_join(st, src, s.NB, (int64_t)F * v->hop, sj.p.lead + z, (const JoinParams*)dev, sj.p.trim != 0, edges,
+                     (JoinRow*)(dev + o_rows), edges + 2 * kJoinMaxItems, (int64_t*)(dev + o_rep), rep_host, ch.jn_buf.as<float>()),
          PIPER_HIP_ERR_LAUNCH);
   if (!rep_host)
-    PH_HIP(hipMemcpyAsync(sg.h_jrep, s.jn_dev + o_rep, (size_t)(1 + 2 * s.NB) * sizeof(int64_t), hipMemcpyDeviceToHost, st), PIPER_HIP_ERR_LAUNCH);
-  out->prog = s.jn_buf;
+    PH_HIP(hipMemcpyAsync(sg.h_jrep, dev + o_rep, (size_t)(1 + 2 * s.NB) * sizeof(int64_t), hipMemcpyDeviceToHost, st), PIPER_HIP_ERR_LAUNCH);
+  out->prog = ch.jn_buf.as<float>();
   out->total = edges + 2 * kJoinMaxItems;
   out->cap = cap;
   return PIPER_HIP_OK;
@@ -3958,23 +3939,39 @@ int join_items(piper_hip_voice* v, int slot, Slot& s, const Chain& items, Joined
 // after the slot's stream has been synchronised behind join_items: the report → h_jrep (piper_hip_voice_join_report); returns the total
 int64_t join_landed(piper_hip_voice* v, int slot, Slot& s) {
   const auto& sg = v->staging[slot];
-  s.h_jrep.assign(sg.h_jrep, sg.h_jrep + 1 + 2 * s.NB);
-  return s.h_jrep[0];
+  s.chain.h_jrep.assign(sg.h_jrep, sg.h_jrep + 1 + 2 * s.NB);
+  return s.chain.h_jrep[0];
 }
 
-// collect on a slot id with a join: the programme's floats. Up to kPinnedMax they leave through the slot id's page-locked buffer by a
-// kernel that reads the length from device memory — one synchronisation for report, lengths and samples; a longer programme waits for
-// its length first and is copied at it.
-int collect_joined(piper_hip_voice* v, int slot, Slot& s, const Chain& items, float* host_audio, int64_t max_samples) {
+// A chunked landing in the slot id's page-locked buffer (collect, pcm_land): chunk_mark records event k behind the copy of chunk k on q,
+// chunk_wait polls for it — the chunks arrive every ≈ 20 µs — and reports a failure under the caller's name.
+int chunk_mark(piper_hip_voice::Staging& sg, size_t k, hipStream_t q) {
+  if (sg.chunk_ev.size() <= k) {
+    hipEvent_t e = nullptr;
+    PH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
+    sg.chunk_ev.push_back(e);
+  }
+  PH_HIP(hipEventRecord(sg.chunk_ev[k], q), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+int chunk_wait(const piper_hip_voice::Staging& sg, size_t k, const char* who) {
+  for (;;) {
+    const hipError_t e = hipEventQuery(sg.chunk_ev[k]);
+    if (e == hipSuccess) return PIPER_HIP_OK;
+    if (e != hipErrorNotReady) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "%s: %s", who, hipGetErrorString(e));
+    (void)hipGetLastError();
+    for (int i = 0; i < 16; i++) __builtin_ia32_pause();
+  }
+}
+
+// collect on a slot id with a join: the programme's floats, of which the caller's buffer holds `cap` (join_capacity) at least. Up to
+// kPinnedMax they leave through the slot id's page-locked buffer by a kernel that reads the length from device memory — one
+// synchronisation for report, lengths and samples; a longer programme waits for its length first and is copied at it.
+int collect_joined(piper_hip_voice* v, int slot, Slot& s, const Chain& items, int64_t cap, float* host_audio) {
   auto& sg = v->staging[slot];
-  int64_t cap = 0;
-  int rc = join_capacity(v, slot, s, &cap);
-  if (rc) return rc;
-  if (max_samples < cap)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)cap,
-            (long long)max_samples);
   Joined j;
-  if ((rc = join_items(v, slot, s, items, &j))) return rc;
+  int rc = join_items(v, slot, s, items, cap, &j);
+  if (rc) return rc;
   const hipStream_t st = s.set.stream;
   float* dst_dev = nullptr;
   if ((size_t)cap * sizeof(float) <= kPinnedMax && !is_caller_pinned(host_audio)) {
@@ -4012,12 +4009,7 @@ PH_EXPORT int piper_hip_voice_launch(piper_hip_voice* v, int slot) {
   }
   PH_HIP(hipEventRecord(s.set.ev1, s.set.stream), PIPER_HIP_ERR_LAUNCH);
   s.timed = true;
-  s.h_peaks.clear();  // the peaks a normalising collect_pcm16 reported belong to the previous run
-  s.loud_measured = false;  // (and so does the loudness measured there)
-  s.vol_shaped = false;     // (and the items shaped from it)
-  s.pt_done = false;        // (and the items pitched from those)
-  s.eq_done = false;        // (and the items EQ'd from those)
-  s.h_jrep.clear();         // (and the report of a joined collect)
+  chain_invalidate(s.chain);  // (the peaks, the measurement, the rows and the report of earlier collects belong to the previous run)
   return PIPER_HIP_OK;
 }
 
@@ -4028,34 +4020,32 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   Slot& s = *p;
   auto& sg = v->staging[slot];
-  Chain chain;  // the items the collect reads (a slot id with a level: the limited items), rows and lengths as pitch_audio hands them out
-  chain.audio = s.audio; chain.lensF = s.lensF;
-  chain_geometry(v, s, &chain.row, &chain.F);
-  const bool joined = host_audio && slot >= 0 && slot < kMaxSlots && v->slot_jn[slot].on;
+  Chain chain = chain_geometry(v, s);  // the items the collect reads: the walk's where there is a buffer to fill, else only their geometry
+  const bool joined = host_audio && v->slot_jn[slot].on;
+  int64_t jcap = 0;
   if (joined) {  // (a buffer too short for the programme is refused before anything is enqueued)
-    int64_t cap = 0;
-    if (int jrc = join_capacity(v, slot, s, &cap)) return jrc;
-    if (max_samples < cap)
-      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)cap,
+    if (int jrc = join_capacity(v, slot, s, &jcap)) return jrc;
+    if (max_samples < jcap)
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)jcap,
               (long long)max_samples);
   }
   if (host_audio && !joined && s.bounded_pending) {  // (a buffer too short for the capacity is refused before anything is enqueued)
     int64_t need = 0;
-    for (int b = 0; b < s.NB; b++) need += (int64_t)pitch_frames(v, s, b, s.F) * v->hop;
+    for (int b = 0; b < s.NB; b++) need += item_samples(v, s, b, s.F);
     if (max_samples < need)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_%s_samples before collect), got %lld",
-              (long long)need, s.pt_on ? "pitch" : "prepared", (long long)max_samples);
+              (long long)need, s.chain.pt_on ? "pitch" : "prepared", (long long)max_samples);
   }
   if (host_audio)
-    if (int lrc = level_audio(v, slot, s, &chain)) return lrc;
+    if (int wrc = chain_walk(v, slot, s, nullptr, &chain)) return wrc;
   const float* audio = chain.audio;
-  if (joined) return collect_joined(v, slot, s, chain, host_audio, max_samples);  // (a slot id with a join: the programme)
+  if (joined) return collect_joined(v, slot, s, chain, jcap, host_audio);  // (a slot id with a join: the programme)
   // The slot id's page-locked landing buffer of the waveform (kAudioMinCap at least). Failing to grow it is not fatal: the waveform
   // then goes to the caller's buffer directly, and the sticky error of the failed hipHostMalloc is cleared (the next launch would report it).
   if (s.bounded_pending) {
     // lengths still on the device. Short buckets: the waveform rows go to the slot id's page-locked buffer at bucket stride by a kernel that
     // reads each length from device memory — ONE synchronisation for lengths and samples; long ones: synchronise, then the usual copy.
-    const int64_t row = s.pt_on ? chain.row : (int64_t)s.F * v->hop;
+    const int64_t row = s.chain.pt_on ? chain.row : (int64_t)s.F * v->hop;
     const size_t ub = (size_t)row * s.NB * sizeof(float);
     float* dst_dev = nullptr;
     if (host_audio && ub <= ((size_t)1 << 20) && (v->hop & 3) == 0) {
@@ -4075,7 +4065,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     if (dst_dev) {
       int64_t off = 0;
       for (int b = 0; b < s.NB; b++) {
-        const int64_t nb = (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
+        const int64_t nb = item_samples(v, s, b);
         memcpy(host_audio + off, sg.h_audio + (int64_t)b * row, (size_t)nb * sizeof(float));
         off += nb;
       }
@@ -4084,8 +4074,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     // fall through: the lengths are known now
   }
   if (host_audio) {
-    int64_t total = 0;  // batch items back to back, each at its own true length
-    for (int b = 0; b < s.NB; b++) total += (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
+    const int64_t total = delivered_samples(v, slot, s);  // (no join here: batch items back to back, each at its own true length)
     if (max_samples < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect: buffer holds %lld < %lld samples", (long long)max_samples, (long long)total);
     // A copy into the caller's (pageable) buffer goes through the runtime's own staging in chunks and its time varies from
     // box to box (r2z: 45 … 130 µs for 344 KB). Up to 1 MB (a factor-8 … 16 utterance) the waveform lands in a pinned buffer of
@@ -4105,31 +4094,19 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
       std::vector<int64_t> cuts;
       int64_t off = 0;
       for (int b = 0; b < s.NB; b++) {
-        const int64_t nb = (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
+        const int64_t nb = item_samples(v, s, b);
         const float* src = audio + (int64_t)b * chain.row;
         for (int64_t c0 = 0; c0 < nb; c0 += (int64_t)(kChunk / sizeof(float))) {
           const int64_t cn = std::min<int64_t>((int64_t)(kChunk / sizeof(float)), nb - c0);
           PH_HIP(hipMemcpyAsync(h_audio + off + c0, src + c0, (size_t)cn * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
-          const size_t k = cuts.size();
-          if (sg.chunk_ev.size() <= k) {
-            hipEvent_t e = nullptr;
-            PH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
-            sg.chunk_ev.push_back(e);
-          }
-          PH_HIP(hipEventRecord(sg.chunk_ev[k], s.set.stream), PIPER_HIP_ERR_LAUNCH);
+          if (int mrc = chunk_mark(sg, cuts.size(), s.set.stream)) return mrc;
           cuts.push_back(off + c0 + cn);
         }
         off += nb;
       }
       int64_t done = 0;
       for (size_t k = 0; k < cuts.size(); k++) {
-        for (;;) {  // poll: the chunks arrive every ≈ 20 µs
-          const hipError_t e = hipEventQuery(sg.chunk_ev[k]);
-          if (e == hipSuccess) break;
-          if (e != hipErrorNotReady) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "collect: %s", hipGetErrorString(e));
-          (void)hipGetLastError();
-          for (int i = 0; i < 16; i++) __builtin_ia32_pause();
-        }
+        if (int wrc = chunk_wait(sg, k, "collect")) return wrc;
         memcpy(host_audio + done, h_audio + done, (size_t)(cuts[k] - done) * sizeof(float));
         done = cuts[k];
       }
@@ -4148,7 +4125,7 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     }
     int64_t off = 0;
     for (int b = 0; b < s.NB; b++) {
-      const int64_t nb = (int64_t)pitch_frames(v, s, b, s.h_F[b]) * v->hop;
+      const int64_t nb = item_samples(v, s, b);
       const float* src = audio + (int64_t)b * chain.row;
       if (dst_dev && nb > 0) {
         const int blocks = (int)std::min<int64_t>((nb + 4 * 256 - 1) / (4 * 256), 1024);
@@ -4316,21 +4293,10 @@ int pcm_land(piper_hip_voice::Staging& sg, const PcmRoute& r, hipStream_t q, voi
     for (size_t k = 0; k < nchunks; k++) {
       const size_t at = k * kChunk, cb = std::min(kChunk, bytes - at);
       PH_HIP(hipMemcpyAsync((char*)r.stage + at, (const char*)r.kdst + at, cb, hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
-      if (sg.chunk_ev.size() <= k) {
-        hipEvent_t e = nullptr;
-        PH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
-        sg.chunk_ev.push_back(e);
-      }
-      PH_HIP(hipEventRecord(sg.chunk_ev[k], q), PIPER_HIP_ERR_LAUNCH);
+      if (int rc = chunk_mark(sg, k, q)) return rc;
     }
     for (size_t k = 0; k < nchunks; k++) {
-      for (;;) {  // poll, as collect does: the chunks arrive every ≈ 20 µs
-        const hipError_t e = hipEventQuery(sg.chunk_ev[k]);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "pcm16: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        for (int i = 0; i < 16; i++) __builtin_ia32_pause();
-      }
+      if (int rc = chunk_wait(sg, k, "pcm16")) return rc;
       const size_t at = k * kChunk;
       memcpy((char*)host + at, (const char*)r.stage + at, std::min(kChunk, bytes - at));
     }
@@ -5535,9 +5501,9 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   bool normalize;
   int rc = pcm_params(params, &out.gain, &normalize);
   if (rc) return rc;
-  if (normalize && slot >= 0 && slot < kMaxSlots && v->slot_lv[slot].on)
+  if (normalize && v->slot_lv[slot].on)
     PH_FAIL(PIPER_HIP_ERR_ARG, "collect_pcm16: normalize = 1 on slot %d, which has a level (piper_hip_voice_slot_level)", slot);
-  if (normalize && slot >= 0 && slot < kMaxSlots && v->slot_ld[slot].on)
+  if (normalize && v->slot_ld[slot].on)
     PH_FAIL(PIPER_HIP_ERR_ARG, "collect_pcm16: normalize = 1 on slot %d, which has a loudness (piper_hip_voice_slot_loudness)", slot);
   const float gain = out.gain;
   const RsDesign* rd = nullptr;
@@ -5556,36 +5522,30 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   auto& sg = v->staging[slot];
   const int NB = s.NB, hop = v->hop;
   if (NB > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: %d items (at most %d)", NB, kMaxGroup);
-  Chain chain;  // the items the sinks read, rows and lengths as pitch_audio hands them out
-  chain.audio = s.audio; chain.lensF = s.lensF;
-  chain_geometry(v, s, &chain.row, &chain.F);
+  Chain chain = chain_geometry(v, s);  // the items the sinks read: their geometry for the bounds, then the walk's
   const int F = chain.F;  // frames of a row of the items
-  const int F_own = (int)std::min<int64_t>(s.F, s.n_samples / hop);  // frames of a row of s.audio
+  const int F_own = row_frames(v, s);
   const bool bounded = s.bounded_pending;
   // a slot id with a join: the sinks read the programme, ONE item whose length the device knows, the caller makes room for its bound
-  const bool joined = slot >= 0 && slot < kMaxSlots && v->slot_jn[slot].on;
+  const bool joined = v->slot_jn[slot].on;
   int64_t jcap = 0;
   if (joined && (rc = join_capacity(v, slot, s, &jcap))) return rc;
   // a bounded slot's lengths are still on the device: the caller makes room for the capacity, as for collect
   int64_t need = 0;
   if (joined) need = out_len(jcap);
-  else for (int b = 0; b < NB; b++) need += out_len((int64_t)pitch_frames(v, s, b, bounded ? F_own : s.h_F[b]) * hop);
+  else for (int b = 0; b < NB; b++) need += out_len(item_samples(v, s, b, bounded ? F_own : s.h_F[b]));
   if (out.cap < need) {
     if (joined)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: the join needs room for %lld samples (piper_hip_voice_join_capacity), got %lld", (long long)need,
               (long long)out.cap);
     if (bounded)
       PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: a bounded slot needs room for its capacity (%lld samples: piper_hip_voice_%s_samples before collect), got %lld",
-              (long long)need, s.pt_on ? "pitch" : "prepared", (long long)out.cap);
+              (long long)need, s.chain.pt_on ? "pitch" : "prepared", (long long)out.cap);
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "collect_pcm16: buffer holds %lld < %lld samples", (long long)out.cap, (long long)need);
   }
   float* peaks_host = nullptr;
   if (normalize) {
-    if (!s.peaks) {
-      void* q = nullptr;
-      if ((rc = plan_alloc(v, s, (size_t)NB * sizeof(float), &q))) return rc;
-      s.peaks = (float*)q;
-    }
+    if ((rc = plan_ensure(v, s, s.chain.peaks, (size_t)NB * sizeof(float)))) return rc;
     if ((rc = grow_pinned(sg.h_peaks, sg.cap_peaks, (size_t)kMaxGroup, (size_t)kMaxGroup))) return rc;
     if (hipHostGetDevicePointer((void**)&peaks_host, sg.h_peaks, 0) != hipSuccess) { peaks_host = nullptr; (void)hipGetLastError(); }
   }
@@ -5593,45 +5553,43 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   const int64_t dev_samples = joined ? std::max(out_len(jcap), jcap) : std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB;
   if ((rc = pcm_route(v, s, sg, host_pcm, elem, (size_t)need, (size_t)dev_samples, &r))) return rc;
   const hipStream_t q = s.set.stream;
-  if ((rc = level_audio(v, slot, s, &chain))) return rc;  // (a slot id with a level: the limited items)
+  Chain peak_src;  // (the peak of normalize = 1 is that of the shaped, pitched, EQ'd items where there are a volume, a pitch, an EQ)
+  if ((rc = chain_walk(v, slot, s, &peak_src, &chain))) return rc;
   const float* audio = chain.audio;
+  float* const peaks = s.chain.peaks.as<float>();
   if (joined) {
     // The programme is one row of device-known length: the sinks take it as NB = 1, hop = 1, F = its bound, with the device's total as
     // the length. normalize = 1 takes ONE peak, over the programme (no level and no loudness then: the joined EQ'd items).
     Joined j;
-    if ((rc = join_items(v, slot, s, chain, &j))) return rc;
+    if ((rc = join_items(v, slot, s, chain, jcap, &j))) return rc;
     const int JF = (int)std::max<int64_t>(j.cap, 1);
-    if (normalize) PH_HIP(launch_pcm16_peak(q, j.prog, JF, j.total, JF, 1, 1, s.peaks), PIPER_HIP_ERR_LAUNCH);
+    if (normalize) PH_HIP(launch_pcm16_peak(q, j.prog, JF, j.total, JF, 1, 1, peaks), PIPER_HIP_ERR_LAUNCH);
     if (rd)
-      PH_HIP(launch_resample_items(q, j.prog, JF, j.total, JF, 1, 1, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
+      PH_HIP(launch_resample_items(q, j.prog, JF, j.total, JF, 1, 1, 0, rf, gain, normalize ? peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
              PIPER_HIP_ERR_LAUNCH);
     else
-      PH_HIP(launch_pcm16_pack(q, j.prog, JF, j.total, JF, 1, 1, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
-    if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
+      PH_HIP(launch_pcm16_pack(q, j.prog, JF, j.total, JF, 1, 1, gain, normalize ? peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
+    if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, peaks, sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
     if ((rc = pcm_land(sg, r, q, host_pcm, elem, (size_t)need))) return rc;
     const int64_t total = out_len(join_landed(v, slot, s));
     if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
     if (r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)total * elem);
-    if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + 1);
+    if (normalize) s.chain.h_peaks.assign(sg.h_peaks, sg.h_peaks + 1);
     return PIPER_HIP_OK;
   }
-  Chain peak_src = chain;  // (the peak of normalize = 1 is that of the shaped, pitched, EQ'd items where there are a volume, a pitch, an EQ)
-  if (normalize && (rc = eq_audio(v, slot, s, &peak_src))) return rc;
-  if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src.audio, chain.row, chain.lensF, F, hop, NB, s.peaks), PIPER_HIP_ERR_LAUNCH);
+  if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src.audio, chain.row, chain.lensF, F, hop, NB, peaks), PIPER_HIP_ERR_LAUNCH);
   if (rd)
-    PH_HIP(launch_resample_items(q, audio, chain.row, chain.lensF, F, hop, NB, 0, rf, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
+    PH_HIP(launch_resample_items(q, audio, chain.row, chain.lensF, F, hop, NB, 0, rf, gain, normalize ? peaks : nullptr, peaks_host, r.kdst, (int)elem, law),
            PIPER_HIP_ERR_LAUNCH);
   else
-    PH_HIP(launch_pcm16_pack(q, audio, chain.row, chain.lensF, F, hop, NB, gain, normalize ? s.peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
-  if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, s.peaks, (size_t)NB * sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
+    PH_HIP(launch_pcm16_pack(q, audio, chain.row, chain.lensF, F, hop, NB, gain, normalize ? peaks : nullptr, peaks_host, r.kdst, law), PIPER_HIP_ERR_LAUNCH);
+  if (normalize && !peaks_host) PH_HIP(hipMemcpyAsync(sg.h_peaks, peaks, (size_t)NB * sizeof(float), hipMemcpyDeviceToHost, q), PIPER_HIP_ERR_LAUNCH);
   if ((rc = pcm_land(sg, r, q, host_pcm, elem, (size_t)need))) return rc;
   if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
   if (r.mapped && !r.caller_pinned) {  // the kernel stored into the staging: the true total is known by now
-    int64_t total = 0;
-    for (int b = 0; b < NB; b++) total += out_len((int64_t)pitch_frames(v, s, b, s.h_F[b]) * hop);
-    memcpy(host_pcm, r.stage, (size_t)total * elem);
+    memcpy(host_pcm, r.stage, (size_t)delivered_samples(v, slot, s, rd) * elem);
   }
-  if (normalize) s.h_peaks.assign(sg.h_peaks, sg.h_peaks + NB);
+  if (normalize) s.chain.h_peaks.assign(sg.h_peaks, sg.h_peaks + NB);
   return PIPER_HIP_OK;
 }
 }  // namespace
@@ -5650,9 +5608,9 @@ PH_EXPORT int piper_hip_voice_peaks(const piper_hip_voice* v, int slot, float* p
   if (!v || !peaks) PH_FAIL(PIPER_HIP_ERR_ARG, "peaks: null argument");
   const Slot* p = slot_plan(v, slot);
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
-  if (p->h_peaks.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "peaks: slot %d has not been collected with normalize = 1 since its last launch", slot);
-  if (max_items < (int)p->h_peaks.size()) PH_FAIL(PIPER_HIP_ERR_SHAPE, "peaks: buffer holds %d < %d items", max_items, (int)p->h_peaks.size());
-  memcpy(peaks, p->h_peaks.data(), p->h_peaks.size() * sizeof(float));
+  if (p->chain.h_peaks.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "peaks: slot %d has not been collected with normalize = 1 since its last launch", slot);
+  if (max_items < (int)p->chain.h_peaks.size()) PH_FAIL(PIPER_HIP_ERR_SHAPE, "peaks: buffer holds %d < %d items", max_items, (int)p->chain.h_peaks.size());
+  memcpy(peaks, p->chain.h_peaks.data(), p->chain.h_peaks.size() * sizeof(float));
   return PIPER_HIP_OK;
 }
 
@@ -5680,8 +5638,7 @@ int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
   if ((rc = collect_pcm(v, 0, params, out_rate, Sink{host, max_samples, enc}))) return rc;
   const Slot& s0 = *v->attached[0];
-  const int64_t n = v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)pitch_frames(v, s0, 0, s0.h_F[0]) * v->hop;  // (a join: the programme's count)
-  if (n_samples) *n_samples = rd ? rs_count(*rd, n) : n;
+  if (n_samples) *n_samples = delivered_samples(v, 0, s0, rd);  // (a join: the programme's count)
   return PIPER_HIP_OK;
 }
 }  // namespace
@@ -5833,12 +5790,12 @@ PH_EXPORT int piper_hip_voice_join_report(const piper_hip_voice* v, int slot, in
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "join_report: null voice");
   const Slot* p = slot_plan(v, slot);
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
-  if (p->h_jrep.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "join_report: slot %d has not been collected with a join since its last launch", slot);
-  const int NB = (int)(p->h_jrep.size() - 1) / 2;
+  if (p->chain.h_jrep.empty()) PH_FAIL(PIPER_HIP_ERR_ARG, "join_report: slot %d has not been collected with a join since its last launch", slot);
+  const int NB = (int)(p->chain.h_jrep.size() - 1) / 2;
   if ((start || len) && max_items < NB) PH_FAIL(PIPER_HIP_ERR_SHAPE, "join_report: buffer holds %d < %d items", max_items, NB);
-  if (start) memcpy(start, p->h_jrep.data() + 1, (size_t)NB * sizeof(int64_t));
-  if (len) memcpy(len, p->h_jrep.data() + 1 + NB, (size_t)NB * sizeof(int64_t));
-  if (total) *total = p->h_jrep[0];
+  if (start) memcpy(start, p->chain.h_jrep.data() + 1, (size_t)NB * sizeof(int64_t));
+  if (len) memcpy(len, p->chain.h_jrep.data() + 1 + NB, (size_t)NB * sizeof(int64_t));
+  if (total) *total = p->chain.h_jrep[0];
   return PIPER_HIP_OK;
 }
 
@@ -5868,10 +5825,13 @@ PH_EXPORT int piper_hip_voice_loudness(piper_hip_voice* v, int slot, float* lufs
   LdTarget t;
   int rc = ld_resolve(v->slot_ld[slot].on ? &v->slot_ld[slot].ld : nullptr, &t);
   if (rc) return rc;
-  if ((rc = loudness_measure(v, slot, s, t))) return rc;
+  LdFilter f;
+  if ((rc = ld_filter(v->cfg.sample_rate, &f))) return rc;
+  Chain c;  // the items the loudness stage reads: shaped, pitched and EQ'd where there are a volume, a pitch, an EQ
+  if ((rc = chain_walk(v, slot, s, &c, nullptr)) || (rc = chain_measure(v, s, c, f, t))) return rc;
   auto& sg = v->staging[slot];
   if ((rc = grow_pinned(sg.h_loud, sg.cap_loud, (size_t)2 * s.NB, (size_t)2 * kMaxGroup))) return rc;
-  PH_HIP(hipMemcpyAsync(sg.h_loud, s.loud_rep, (size_t)2 * s.NB * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(sg.h_loud, s.chain.loud_rep.p, (size_t)2 * s.NB * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
   for (int b = 0; b < s.NB; b++) {
     if (lufs) lufs[b] = sg.h_loud[2 * b];
@@ -6181,7 +6141,7 @@ PH_EXPORT int piper_hip_voice_synthesize(piper_hip_voice* v, const piper_hip_utt
   if ((rc = piper_hip_voice_launch(v, 0))) return rc;
   if ((rc = piper_hip_voice_collect(v, 0, host_audio, max_samples))) return rc;
   const Slot& s0 = *v->attached[0];
-  if (n_samples) *n_samples = host_audio && v->slot_jn[0].on && !s0.h_jrep.empty() ? s0.h_jrep[0] : (int64_t)pitch_frames(v, s0, 0, s0.h_F[0]) * v->hop;
+  if (n_samples) *n_samples = delivered_samples(v, 0, s0);  // (a join: the programme's count; no buffer: none was made, the item's own)
   return PIPER_HIP_OK;
 }
 

@@ -9,13 +9,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import join_ref as jr
 import katdata as kd
 import level_ref as lr
 import loudness_ref as ld
 import mixed_ref as mr
 import pitch_ref as pr
 import piper_hip as ph
-from test_gpu_level import DEV, SINKS, collect_as, item, rt_medium, same  # noqa: F401  (rt_medium: a fixture)
+from test_gpu_level import DEV, SINKS, collect_as, item, level_for, rt_medium, same  # noqa: F401  (rt_medium: a fixture)
 from test_gpu_resample import same_bits
 from test_gpu_stream_mixed import TABLES
 
@@ -196,6 +197,50 @@ def test_join_takes_the_pitched_items(rt_medium, fix):
     assert t == total and list(s) == list(start) and list(l) == list(length)
     assert same(rt.collect_pcm16(FIX, rate=8000), mr.whole(y[:total], SINKS["s16@8000"], rate, TABLES))
     assert same_bits(rt.collect(FIX, join=None), fix["got"])
+
+
+def test_every_stage_together(rt_medium):
+    """Volume, pitch, EQ, loudness, level and join on one launch: every sink, in two orders, equals the existing references chained on the
+    float collect that has only the volume and the pitch."""
+    rt, rate, hop = rt_medium, rt_medium.cfg.sample_rate, rt_medium.cfg.hop
+    clear(rt, SLOT)
+    items = batch(rt.cfg)
+    vols = [np.resize(np.array([1.0, 0.25, 1.0, 2.0, 0.0, 1.5], F32), len(it[0])) for it in items]
+    rt.prepare_batch(SLOT, items, 0.667, volume=vols, pitch=SHIFTS3)
+    rt.launch(SLOT)
+    got = rt.collect(SLOT).copy()  # volume and pitch only
+    per, total = rt.pitch_samples(SLOT)
+    raw_per, _ = rt.prepared_samples(SLOT)
+    assert got.size == total and per != raw_per  # (the pitch shows)
+    assert not same_bits(got, np.concatenate(pitched_items(split(rt.tap(SLOT, "audio").reshape(-1), raw_per), SHIFTS3, hop)))  # (the volume shows)
+    y = split(got, per)
+    e = [ph.eq_from_f32(x, EQ, rate) for x in y]
+    rt.slot_eq(SLOT, EQ)
+    rt.slot_loudness(SLOT, (-16.0, 0.0))
+    lufs, g = rt.loudness(SLOT)
+    for b, x in enumerate(e):
+        L = ld.lufs(x, rate)
+        print(f"item {b}: L device {float(lufs[b]):.4f}, loudness_ref {L:.4f}, gain {float(g[b]):.4f}")
+        assert abs(float(lufs[b]) - L) <= 0.002, (b, lufs[b], L)
+    u = [ld.apply(x, gk) for x, gk in zip(e, g)]
+    level = level_for(u)  # (asserts that the limiter works on some blocks and rests on others)
+    lim = [lr.apply(x, level, rate) for x in u]
+    J = dict(lead_ms=1.5, gap_ms=20.0, tail_ms=3.0, trim=1, trim_threshold=max(float(np.abs(x).max()) for x in lim) * 0.05, trim_pad_ms=2.0,
+             fade_ms=3.0)
+    prog, start, length, jtotal = jr.join(lim, J, rate)
+    print(f"items {per}, kept {list(length)}, programme {jtotal}")
+    for b in range(3):  # every stage changes the signal: one that was skipped would be seen
+        assert not same_bits(e[b], y[b]) and not same_bits(u[b], e[b]) and not same_bits(lim[b], u[b]), b
+    assert sum(int(n) for n in length) < total  # (the trim removes something)
+    want = {name: mr.whole(prog[:jtotal], f, rate, TABLES) for name, f in SINKS.items()}
+    rt.slot_level(SLOT, level)
+    rt.slot_join(SLOT, J)
+    for name in list(SINKS) + list(SINKS)[::-1]:
+        assert same(collect_as(rt, SLOT, name), want[name]), name
+        s, l, t = rt.join_report(SLOT)
+        assert t == jtotal and list(s) == list(start) and list(l) == list(length), name
+    clear(rt, SLOT)
+    assert same_bits(rt.collect(SLOT), got)
 
 
 def test_collect_pcm16(rt_medium, fix):
