@@ -343,6 +343,38 @@ struct PlanBuf {
   template <class T> T* as() const { return (T*)p; }
 };
 
+// Page-locked host memory of a slot id's staging (piper_hip_voice::Staging), the host twin of PlanBuf: the pointer and its capacity in
+// elements. THE INVARIANT of every one of them: a slot id's staging is regrown or rewritten only after that slot id's stream has been
+// waited for (both prepares wait before their first ensure; every stream step and every collect ends with a wait).
+template <typename Tp>
+struct PinnedBuf {
+  Tp* p = nullptr;
+  size_t cap = 0;
+  operator Tp*() const { return p; }
+  // Room for `need` elements: nothing to do where there is, otherwise freed and allocated again (contents dropped) at `min_cap` elements
+  // or a power of two times that. On failure p is null and cap 0.
+  int ensure(size_t need, size_t min_cap = 1024) {
+    if (cap >= need) return PIPER_HIP_OK;
+    release();
+    size_t c = min_cap;
+    while (c < need) c <<= 1;
+    PH_HIP(hipHostMalloc((void**)&p, c * sizeof(Tp)), PIPER_HIP_ERR_ALLOC);
+    cap = c;
+    return PIPER_HIP_OK;
+  }
+  // The device's view of the memory, or null: none allocated, or no mapping on this system (the runtime's sticky error is cleared then,
+  // and nothing else happens: a caller that refuses says so in its own words).
+  Tp* mapped() const {
+    Tp* d = nullptr;
+    if (p && hipHostGetDevicePointer((void**)&d, p, 0) != hipSuccess) { d = nullptr; (void)hipGetLastError(); }
+    return d;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+  }
+};
+
 // The output chain of a whole-item plan: what the stages between the plan's graph and the sinks — volume, pitch, EQ, loudness, level,
 // join, and the peaks of a normalising PCM collect — keep with the plan. chain_walk runs the stages in that order; every stage reads
 // the rows its predecessor hands on and writes rows of its own, in the layout of the plan's audio. The plan's audio stays raw.
@@ -526,7 +558,7 @@ struct StreamPool {
     uint64_t prepared;  // the plan's last_use at the join: the same value later = the work slot has not been prepared again
   };
   std::vector<BoundedJoin> bounded;
-  int32_t* h_rep = nullptr;       // page-locked [capacity][2]: {wanted frames, allowed frames} per row, written by stream_adopt_bounded_kernel
+  PinnedBuf<int32_t> h_rep;       // page-locked [capacity][2]: {wanted frames, allowed frames} per row, written by stream_adopt_bounded_kernel
   int32_t* d_rep = nullptr;       // its device mapping
   PoolRowRef* d_rows = nullptr;   // device: [NBg] row table, then the [capacity] PoolJoinEnt table of the latest join (one upload per join)
   std::vector<hipEvent_t> ev_free, ev_pending;  // ev_pending: "the adopt of a join since the last step has run", one per join
@@ -602,46 +634,43 @@ struct piper_hip_voice {
   double last_build_ms[6] = {0, 0, 0, 0, 0, 0};  // the latest plan build: stream/events, schedule + arena, arena init, 0 (ABI), capture, instantiate
   size_t plan_cache_max = 128, plan_cache_bytes = (size_t)24 << 30;
   // Page-locked staging of a slot id's inputs and of its (short) waveform: it belongs to the SLOT ID, not to the plan attached to it —
-  // a new bucket then costs no hipHostMalloc (≈ 0.3–1 ms each, four per plan until round 3). Grown in powers of two, freed with the voice.
+  // a new bucket then costs no hipHostMalloc (≈ 0.3–1 ms each). Every buffer is a PinnedBuf (its invariant is told there), listed in
+  // each(): what is freed with the voice.
   struct Staging {
-    int64_t* h_ids = nullptr; int32_t* h_f2i = nullptr; int* h_lens = nullptr; float* h_audio = nullptr;
-    size_t cap_t = 0, cap_f = 0, cap_lens = 0, audio_cap = 0;  // (every cap_* / *_cap counts elements: grow_pinned)
-    // bounded prepare (durations predicted, no host round trip): scalars of the request, the predictor's noise, and what the device reports
-    // back (frames per item, durations) — the last two written by a kernel through the host mapping
-    char* h_misc = nullptr; float* h_dpn = nullptr; int32_t* h_res = nullptr;
-    size_t cap_misc = 0, cap_dpn = 0, cap_res = 0;
-    float* h_noise = nullptr;  // the caller's noise tensors, laid out in bucket rows (prepare_batch)
-    size_t cap_noise = 0;
-    int* h_desc = nullptr;     // batched stream: the step's descriptor table (one H2D per step)
-    size_t cap_desc = 0;
-    float* h_peaks = nullptr;  // collect_pcm16 with normalize = 1: the items' peaks, written by the pack kernel through the host mapping
-    size_t cap_peaks = 0;
-    float* h_loud = nullptr;   // piper_hip_voice_loudness: {L, g} per item as the gate kernel reported them
-    size_t cap_loud = 0;
+    PinnedBuf<int64_t> h_ids;
+    PinnedBuf<int32_t> h_f2i;
+    PinnedBuf<int> h_lens;
+    PinnedBuf<float> h_audio;
+    // the whole-plan scalars of a request (RequestScalars) and, on the bounded route, the predictor's scalars behind them
+    PinnedBuf<char> h_misc;
+    // bounded prepare (durations predicted, no host round trip): the predictor's noise, and what the device reports back (frames per
+    // item, durations) — written by a kernel through the host mapping
+    PinnedBuf<float> h_dpn;
+    PinnedBuf<int32_t> h_res;
+    PinnedBuf<float> h_noise;  // the caller's noise tensors, laid out in bucket rows (prepare_batch)
+    PinnedBuf<int> h_desc;     // batched stream: the step's descriptor table (one H2D per step)
+    PinnedBuf<float> h_peaks;  // collect_pcm16 with normalize = 1: the items' peaks, written by the pack kernel through the host mapping
+    PinnedBuf<float> h_loud;   // piper_hip_voice_loudness: {L, g} per item as the gate kernel reported them
     std::vector<hipEvent_t> chunk_ev;  // collect, 1 … 16 MB waveforms: one event per 1 MB chunk landed in h_audio
-    piper_hip_speaker* h_spk = nullptr;  // the items' speakers of a prepare (a voice with a speaker table)
-    size_t cap_spk = 0;
-    int32_t* h_pro = nullptr;  // the per-id prosody arrays of a prepare in bucket rows: length, min, max, noise [n][T] each, then fit [n]
-    size_t cap_pro = 0;
-    float* h_vol = nullptr;    // the per-id gains of a prepare in bucket rows [n][T] (a request with a volume)
-    size_t cap_vol = 0;
-    VolStepRow* h_vstep = nullptr;  // a stream step's VolStepRow table (one H2D per step that shapes)
-    size_t cap_vstep = 0;
-    EqDesign* h_eq = nullptr;  // the design of the slot id's EQ on its way to a plan (one H2D when the EQ or the plan changes)
-    size_t cap_eq = 0;
+    PinnedBuf<piper_hip_speaker> h_spk;  // the items' speakers of a prepare (a voice with a speaker table): kMaxGroup records
+    PinnedBuf<int32_t> h_pro;  // the per-id prosody arrays of a prepare in bucket rows: noise [n][T], fit [n], then (bounded) length, min, max [n][T] each
+    PinnedBuf<float> h_vol;    // the per-id gains of a prepare in bucket rows [n][T] (a request with a volume)
+    PinnedBuf<VolStepRow> h_vstep;  // a stream step's VolStepRow table (one H2D per step that shapes)
+    PinnedBuf<EqDesign> h_eq;  // the design of the slot id's EQ on its way to a plan (one H2D when the EQ or the plan changes)
     hipEvent_t eq_ev = nullptr;  // recorded behind the latest copy from h_eq
-    EqStepRow* h_estep = nullptr;  // a stream step's EqStepRow table (one H2D per step of a stream with an EQ)
-    size_t cap_estep = 0;
-    JoinParams* h_join = nullptr;  // the params of the slot id's join on their way to a plan (one H2D when the join or the plan changes)
-    size_t cap_join = 0;
+    PinnedBuf<EqStepRow> h_estep;  // a stream step's EqStepRow table (one H2D per step of a stream with an EQ)
+    PinnedBuf<JoinParams> h_join;  // the params of the slot id's join on their way to a plan (one H2D when the join or the plan changes)
     hipEvent_t join_ev = nullptr;  // recorded behind the latest copy from h_join
-    int64_t* h_jrep = nullptr;     // the report of a joined collect: written by the plan kernel through the mapping, or by a D2H behind it
-    size_t cap_jrep = 0;
-    char* h_pt = nullptr;          // the PtItem table and the filter tables of a prepare with a pitch, as they go to the plan's pt_dev
-    size_t cap_pt = 0;
+    PinnedBuf<int64_t> h_jrep;     // the report of a joined collect: written by the plan kernel through the mapping, or by a D2H behind it
+    PinnedBuf<char> h_pt;          // the PtItem table and the filter tables of a prepare with a pitch, as they go to the plan's pt_dev
+    template <class Fn>
+    void each(Fn f) {
+      f(h_ids), f(h_f2i), f(h_lens), f(h_audio), f(h_misc), f(h_dpn), f(h_res), f(h_noise), f(h_desc), f(h_peaks), f(h_loud), f(h_eq), f(h_estep),
+          f(h_join), f(h_jrep), f(h_spk), f(h_pro), f(h_vol), f(h_pt), f(h_vstep);
+    }
   } staging[kMaxSlots];
   // The prosody of a slot id's NEXT staging call (piper_hip_voice_slot_prosody): owned copies of the caller's arrays, an empty array = the
-  // field was NULL. The staging call takes the assignment (take_prosody) whether or not it succeeds.
+  // field was NULL. The staging call takes the assignment (take_controls) whether or not it succeeds.
   struct Prosody {
     std::vector<float> length, noise;
     std::vector<int32_t> min_frames, max_frames;
@@ -1040,7 +1069,7 @@ void pool_close(piper_hip_voice* v, int slot) {
   for (void* p : {(void*)P->st.d_desc, P->st.pack, (void*)rs.hist, (void*)rs.desc, (void*)rs.mdesc, (void*)lv.carry, (void*)lv.lim, (void*)lv.desc})
     if (p) (void)v->ctx->pool.release(p);
   if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
-  if (P->h_rep) (void)hipHostFree(P->h_rep);  // (the adopts that write it have run: waited for above)
+  P->h_rep.release();  // (the adopts that write it have run: waited for above)
   v->pools[slot].reset();
 }
 
@@ -2337,10 +2366,7 @@ int check_speaker(const piper_hip_voice* v, const piper_hip_speaker& sp, int i) 
 int stage_speakers(piper_hip_voice* v, int slot, Slot& plan, int n, hipStream_t q) {
   if (!v->spk.S || !plan.spk_in) return PIPER_HIP_OK;
   auto& sg = v->staging[slot];
-  if (!sg.h_spk) {  // kMaxGroup records, once per slot id
-    PH_HIP(hipHostMalloc((void**)&sg.h_spk, 256 * sizeof(piper_hip_speaker)), PIPER_HIP_ERR_ALLOC);
-    sg.cap_spk = 256;
-  }
+  if (int rc = sg.h_spk.ensure((size_t)n, 256)) return rc;  // kMaxGroup records, once per slot id
   for (int b = 0; b < n; b++) sg.h_spk[b] = speaker_of(v, slot, b);
   PH_HIP(hipMemcpyAsync(plan.spk_in, sg.h_spk, (size_t)n * sizeof(piper_hip_speaker), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   return PIPER_HIP_OK;
@@ -2669,28 +2695,9 @@ PH_EXPORT void piper_hip_voice_destroy(piper_hip_voice* v) {
   for (int i = 0; i < kMaxSlots; i++) pool_close(v, i);
   for (auto& pl : v->plans) slot_release(v, *pl);
   for (auto& sg : v->staging) {
-    if (sg.h_ids) (void)hipHostFree(sg.h_ids);
-    if (sg.h_f2i) (void)hipHostFree(sg.h_f2i);
-    if (sg.h_lens) (void)hipHostFree(sg.h_lens);
-    if (sg.h_audio) (void)hipHostFree(sg.h_audio);
-    if (sg.h_misc) (void)hipHostFree(sg.h_misc);
-    if (sg.h_dpn) (void)hipHostFree(sg.h_dpn);
-    if (sg.h_res) (void)hipHostFree(sg.h_res);
-    if (sg.h_noise) (void)hipHostFree(sg.h_noise);
-    if (sg.h_desc) (void)hipHostFree(sg.h_desc);
-    if (sg.h_peaks) (void)hipHostFree(sg.h_peaks);
-    if (sg.h_loud) (void)hipHostFree(sg.h_loud);
-    if (sg.eq_ev) { (void)hipEventSynchronize(sg.eq_ev); (void)hipEventDestroy(sg.eq_ev); }
-    if (sg.h_eq) (void)hipHostFree(sg.h_eq);
-    if (sg.h_estep) (void)hipHostFree(sg.h_estep);
-    if (sg.join_ev) { (void)hipEventSynchronize(sg.join_ev); (void)hipEventDestroy(sg.join_ev); }
-    if (sg.h_join) (void)hipHostFree(sg.h_join);
-    if (sg.h_jrep) (void)hipHostFree(sg.h_jrep);
-    if (sg.h_spk) (void)hipHostFree(sg.h_spk);
-    if (sg.h_pro) (void)hipHostFree(sg.h_pro);
-    if (sg.h_vol) (void)hipHostFree(sg.h_vol);
-    if (sg.h_pt) (void)hipHostFree(sg.h_pt);
-    if (sg.h_vstep) (void)hipHostFree(sg.h_vstep);
+    for (hipEvent_t* ev : {&sg.eq_ev, &sg.join_ev})  // the copies queued from h_eq / h_join have run before their buffers go
+      if (*ev) { (void)hipEventSynchronize(*ev); (void)hipEventDestroy(*ev); }
+    sg.each([](auto& b) { b.release(); });
     for (hipEvent_t e : sg.chunk_ev) (void)hipEventDestroy(e);
   }
   for (auto& st : v->free_sets) destroy_set(st);
@@ -2880,36 +2887,33 @@ int attach_plan(piper_hip_voice* v, int slot, PlanKind kind, int T, int F, int N
 }  // namespace
 
 namespace {
-int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
-                 const piper_hip_speaker* speakers = nullptr);
-// Page-locked staging `p` of `cap` elements, grown (contents dropped) to hold `need`: `min_cap` elements or a power of two times that.
-// On failure p is null and cap 0.
-template <typename Tp>
-int grow_pinned(Tp*& p, size_t& cap, size_t need, size_t min_cap = 1024) {
-  if (cap >= need) return PIPER_HIP_OK;
-  if (p) (void)hipHostFree(p);
-  p = nullptr; cap = 0;
-  size_t c = min_cap;
-  while (c < need) c <<= 1;
-  PH_HIP(hipHostMalloc((void**)&p, c * sizeof(Tp)), PIPER_HIP_ERR_ALLOC);
-  cap = c;
-  return PIPER_HIP_OK;
-}
-
-// ---- prosody (piper_hip.h "Per-phoneme prosody") ----
+// ---- the controls of a staging call: what piper_hip_voice_slot_prosody / _volume / _pitch left pending on its slot id
 using ProsodyItems = std::vector<piper_hip_voice::Prosody>;
-// A staging call takes the slot id's assignment, whether or not it goes on to succeed.
-ProsodyItems take_prosody(piper_hip_voice* v, int slot) {
-  ProsodyItems p;
-  if (v && slot >= 0 && slot < kMaxSlots) p.swap(v->slot_pro[slot]);
-  return p;
+using VolumeItems = std::vector<piper_hip_voice::Volume>;
+using PitchItems = std::vector<piper_hip_pitch>;
+struct Controls {
+  ProsodyItems pro;
+  VolumeItems vol;
+  PitchItems pit;
+};
+// A staging call takes the slot id's assignments, whether or not it goes on to succeed.
+Controls take_controls(piper_hip_voice* v, int slot) {
+  Controls c;
+  if (v && slot >= 0 && slot < kMaxSlots) {
+    c.pro.swap(v->slot_pro[slot]);
+    c.vol.swap(v->slot_vol[slot]);
+    c.pit.swap(v->slot_pt[slot]);
+  }
+  return c;
 }
-// The entry points that reach prepare* only behind refusals of their own clear the assignment on every way out.
-struct ProsodyClear {
+// The entry points that reach prepare* only behind refusals of their own clear the assignments on every way out.
+struct ControlsClear {
   piper_hip_voice* v;
   int slot;
-  ~ProsodyClear() { (void)take_prosody(v, slot); }
+  ~ControlsClear() { (void)take_controls(v, slot); }
 };
+
+// ---- prosody (piper_hip.h "Per-phoneme prosody") ----
 // What a staging call checks before it stages anything. bounded: the route has a frame bound (fit is allowed).
 int check_prosody(const ProsodyItems& pro, const piper_hip_utterance* utts, int n, bool bounded) {
   for (int b = 0; b < n && b < (int)pro.size(); b++) {
@@ -2939,19 +2943,6 @@ void pack_prosody(const ProsodyItems& pro, int n, int T, float* len, int32_t* mn
   }
 }
 // ---- per-phoneme volume (piper_hip.h "Per-phoneme volume") ----
-using VolumeItems = std::vector<piper_hip_voice::Volume>;
-// A staging call takes the slot id's assignment, whether or not it goes on to succeed.
-VolumeItems take_volume(piper_hip_voice* v, int slot) {
-  VolumeItems p;
-  if (v && slot >= 0 && slot < kMaxSlots) p.swap(v->slot_vol[slot]);
-  return p;
-}
-// The entry points that reach prepare* only behind refusals of their own clear the assignment on every way out.
-struct VolumeClear {
-  piper_hip_voice* v;
-  int slot;
-  ~VolumeClear() { (void)take_volume(v, slot); }
-};
 // What a staging call checks before it stages anything.
 int check_volume(const VolumeItems& vol, const piper_hip_utterance* utts, int n) {
   for (int b = 0; b < n && b < (int)vol.size(); b++)
@@ -2964,21 +2955,10 @@ int check_volume(const VolumeItems& vol, const piper_hip_utterance* utts, int n)
 int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, int n, int T, hipStream_t q);
 
 // ---- pitch (piper_hip.h "Pitch") ----
-using PitchItems = std::vector<piper_hip_pitch>;
-// A staging call takes the slot id's assignment, whether or not it goes on to succeed.
-PitchItems take_pitch(piper_hip_voice* v, int slot) {
-  PitchItems p;
-  if (v && slot >= 0 && slot < kMaxSlots) p.swap(v->slot_pt[slot]);
-  return p;
-}
-struct PitchClear {
-  piper_hip_voice* v;
-  int slot;
-  ~PitchClear() { (void)take_pitch(v, slot); }
-};
 // Streams have no pitch: a stream's staging call with one pending on its slot id refuses, stages nothing and clears it.
 int refuse_pitch(piper_hip_voice* v, int slot, const char* who) {
-  if (take_pitch(v, slot).empty()) return PIPER_HIP_OK;
+  if (!v || slot < 0 || slot >= kMaxSlots || v->slot_pt[slot].empty()) return PIPER_HIP_OK;
+  v->slot_pt[slot].clear();
   PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "%s: slot %d has a pitch pending (piper_hip_voice_slot_pitch), and streams have no pitch: it has been cleared", who, slot);
 }
 // What a staging call checks before it stages anything, and the tempo: `tempo` receives the utterances with length_scale' = fl(ls·rf)
@@ -3000,6 +2980,13 @@ int check_pitch(const PitchItems& pit, const piper_hip_utterance* utts, int n, s
 // The steps and tables of a request with a pitch → the plan's pt_dev, from the slot id's page-locked staging on the plan's stream (which
 // the caller has synchronised: the previous request's copy is done). A request without, or whose entries are all neutral: the plan has none.
 int stage_pitch(piper_hip_voice* v, int slot, Slot& s, const PitchItems& pit, int n, hipStream_t q);
+
+// Everything a staging call checks of its controls before it stages anything: prosody, volume, pitch, in that order.
+int check_controls(const Controls& ctl, const piper_hip_utterance* utts, int n, bool bounded, std::vector<piper_hip_utterance>* tempo) {
+  int rc;
+  if ((rc = check_prosody(ctl.pro, utts, n, bounded)) || (rc = check_volume(ctl.vol, utts, n))) return rc;
+  return check_pitch(ctl.pit, utts, n, tempo);
+}
 
 // ---- the geometry of what a whole-item plan delivers
 // Frames of a row of s.audio.
@@ -3023,26 +3010,189 @@ int64_t delivered_samples(const piper_hip_voice* v, int slot, const Slot& s, con
   return total;
 }
 
-// predict_impl on the predictor plan of requests with prosody (pro non-null), its per-id inputs staged with the ids
-int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
-                     const piper_hip_speaker* speakers, const ProsodyItems* pro);
+// ---- the inputs of a predictor plan (PLAN_PREDICT) of n items in rows of T, in host memory the caller supplies: the bounded prepare its
+// slot id's page-locked staging, predict_impl pageable vectors (it has no slot id). spk: null where the caller stages the speakers itself
+// (stage_speakers) or the voice has no table; pro: null on a plan without prosody.
+struct PredictorInputs {
+  int64_t* ids;        // [n][T]
+  int* lensT;          // [n]
+  float* dp_noise;     // [n][2][T]
+  void* dp_scalars;    // dp_scalars_bytes(n)
+  const piper_hip_speaker* spk;  // [n]
+  int32_t* pro;        // [3][n][T]: length (floats), min_frames, max_frames
+};
+void pack_predictor_inputs(const piper_hip_utterance* utts, int n, int T, const ProsodyItems* pro, const PredictorInputs& h) {
+  pack_ids(utts, n, T, h.ids);
+  pack_dp_inputs(utts, n, T, h.dp_noise, h.dp_scalars);
+  for (int b = 0; b < n; b++) h.lensT[b] = utts[b].t;
+  if (h.pro) pack_prosody(*pro, n, T, (float*)h.pro, h.pro + (size_t)n * T, h.pro + 2 * (size_t)n * T, nullptr, nullptr);
+}
+// One copy per array to plan dp on q; the first failure is returned and ends it.
+hipError_t upload_predictor_inputs(Slot& dp, int n, const PredictorInputs& h, hipStream_t q) {
+  const size_t nT = (size_t)n * dp.T;
+  hipError_t e = hipMemcpyAsync(dp.ids, h.ids, nT * sizeof(int64_t), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) e = hipMemcpyAsync(dp.lensT, h.lensT, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) e = hipMemcpyAsync(dp.dp_noise, h.dp_noise, 2 * nT * sizeof(float), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) e = hipMemcpyAsync(dp.dp_scalars, h.dp_scalars, dp_scalars_bytes(n), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess && dp.spk_in && h.spk) e = hipMemcpyAsync(dp.spk_in, h.spk, (size_t)n * sizeof(piper_hip_speaker), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess && h.pro) e = hipMemcpyAsync(dp.pro_len, h.pro, nT * sizeof(float), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess && h.pro) e = hipMemcpyAsync(dp.pro_min, h.pro + nT, nT * sizeof(int32_t), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess && h.pro) e = hipMemcpyAsync(dp.pro_max, h.pro + 2 * nT, nT * sizeof(int32_t), hipMemcpyHostToDevice, q);
+  return e;
+}
+
+// ---- the whole-plan scalars of a request of n items, at the front of the slot id's h_misc (request_scalars_bytes; what a route keeps
+// behind them is its own): rng {drawn on the device?, seed} [n][2], noise_scale [n], lensT [n]. One upload to plan s on q, with zero noise
+// for the items that bring none: INJECTED without a tensor.
+struct RequestScalars {
+  unsigned* rng;
+  float* ns;
+  int* lensT;
+  char* end;  // h + request_scalars_bytes(n)
+};
+size_t request_scalars_bytes(int n) { return (size_t)n * (2 * sizeof(unsigned) + sizeof(float) + sizeof(int)); }
+RequestScalars request_scalars(char* h, int n) {
+  unsigned* rng = (unsigned*)h;
+  float* ns = (float*)(rng + 2 * (size_t)n);
+  int* lensT = (int*)(ns + n);
+  return RequestScalars{rng, ns, lensT, (char*)(lensT + n)};
+}
+int stage_request_scalars(const piper_hip_voice* v, Slot& s, char* h, const piper_hip_utterance* utts, int n, hipStream_t q) {
+  const auto [rng, ns, lensT, end] = request_scalars(h, n);
+  const size_t row = (size_t)v->cfg.inter * s.F;
+  for (int b = 0; b < n; b++) {
+    const piper_hip_utterance& u = utts[b];
+    rng[2 * b] = (!u.noise && u.noise_mode == PIPER_HIP_NOISE_DEVICE) ? 1u : 0u;
+    rng[2 * b + 1] = u.seed;
+    ns[b] = u.noise_scale;
+    lensT[b] = u.t;
+    if (!u.noise && !rng[2 * b]) PH_HIP(hipMemsetAsync(s.noise + b * row, 0, row * sizeof(float), q), PIPER_HIP_ERR_LAUNCH);
+  }
+  PH_HIP(hipMemcpyAsync(s.rng, rng, 2 * (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.noise_scale, ns, (size_t)n * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.lensT, lensT, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
+// The inputs a plan of requests with prosody has of its own, from the front of the slot id's h_pro: the noise multiplier per id [n][T],
+// then fit [n] (all zero on a route without a frame bound: check_prosody has refused a fit there).
+int stage_prosody_noise(Slot& s, int32_t* h, const ProsodyItems& pro, int n, int T, hipStream_t q) {
+  const size_t nT = (size_t)n * T;
+  pack_prosody(pro, n, T, nullptr, nullptr, nullptr, (float*)h, h + nT);
+  PH_HIP(hipMemcpyAsync(s.pro_noise, h, nT * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.pro_fit, h + nT, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  return PIPER_HIP_OK;
+}
+
+// The host's record of the request just staged on plan s. frames: the items' true frame counts (their durations are utts[b].durations),
+// or null — a bounded prepare: the plan's capacity F stands in until collect has the device's answer, at most bounded_cap per item.
+// wanted: Σ d of the frame rule per item, or null where the device reports it with the lengths. ran_predict: the predictor plan that ran.
+void plan_staged(Slot& s, const piper_hip_utterance* utts, int n, const std::vector<int>* frames, const std::vector<int64_t>* wanted, Slot* ran_predict,
+                 int bounded_cap) {
+  reset_stream_state(s);
+  s.h_T.assign(n, 0);
+  s.h_dur.clear();
+  for (int b = 0; b < n; b++) {
+    s.h_T[b] = utts[b].t;
+    if (frames) s.h_dur.insert(s.h_dur.end(), utts[b].durations, utts[b].durations + utts[b].t);
+  }
+  if (frames) s.h_F = *frames;
+  else s.h_F.assign(n, s.F);
+  s.h_wanted = wanted ? *wanted : std::vector<int64_t>();
+  s.h_fitted.assign(wanted ? n : 0, 0);
+  s.ran_predict = ran_predict;
+  s.bounded_pending = !frames;
+  if (!frames) s.bounded_cap = bounded_cap;
+  s.timed = false;
+  chain_invalidate(s.chain);
+}
+
+// piper_hip_voice_predict_durations, and the predictor pass of a prepare_batch whose items have no durations.
+// plan_out (optional): the encoder + predictor plan that ran, left marked in_use so that its m_p / logs_p stay put until the caller
+// has enqueued the copy into the plan that continues from them (the caller clears in_use); set on success only
+// speakers (optional): [n], one per utterance, checked by the caller; null on a voice with a table = speaker 0 alone
+// pro (optional): the request has a prosody: the predictor plan of such requests runs, its per-id inputs staged with the ids
+int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
+                 const piper_hip_speaker* speakers = nullptr, const ProsodyItems* pro = nullptr) {
+  if (!v || !utts || !durations_out) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
+  if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
+  if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0)");
+  std::vector<piper_hip_speaker> spk;
+  if (v->spk.S) {
+    piper_hip_speaker d{};
+    d.n = 1;
+    d.weights[0] = 1.0f;
+    spk.assign((size_t)n, d);
+    if (speakers) spk.assign(speakers, speakers + n);
+  }
+  int Tmax = 0, rc;
+  int64_t total = 0;
+  for (int b = 0; b < n; b++) {
+    if ((rc = check_item(utts[b], b))) return rc;
+    Tmax = std::max(Tmax, utts[b].t);
+    total += utts[b].t;
+  }
+  if (max_entries < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "predict_durations: output holds %d < %lld entries", max_entries, (long long)total);
+  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
+  const int T = bucket_t(Tmax);
+  Slot* pl = nullptr;
+  bool built = false;
+  if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &pl, &built, pro != nullptr))) return rc;
+  Slot& s = *pl;
+  s.in_use = true;
+  s.last_use = ++v->use_clock;
+  struct Release {  // on every way out but the one that hands the plan on: the plan is idle again, and the cache is brought back to its bounds
+    piper_hip_voice* v;
+    Slot* pl;
+    ~Release() {
+      if (pl) pl->in_use = false;
+      evict_idle_plans(v);
+    }
+  } release{v, pl};
+  const hipStream_t q = s.set.stream;
+  const auto failed = [](hipError_t e) { PH_FAIL(PIPER_HIP_ERR_LAUNCH, "predict_durations: %s", hipGetErrorString(e)); };
+  const size_t nT = (size_t)n * T;
+  std::vector<int64_t> ids(nT);
+  std::vector<int> lens(n);
+  std::vector<float> nz(2 * nT);
+  std::vector<int32_t> pr(pro ? 3 * nT : 0);
+  std::vector<char> sc(dp_scalars_bytes(n));
+  const PredictorInputs in{ids.data(), lens.data(), nz.data(), sc.data(), spk.empty() ? nullptr : spk.data(), pro ? pr.data() : nullptr};
+  pack_predictor_inputs(utts, n, T, pro, in);
+  if (hipError_t e = upload_predictor_inputs(s, n, in, q)) return failed(e);
+  if (launch_plan(v, s)) return failed(hipErrorUnknown);
+  std::vector<int32_t> dur(nT);
+  std::vector<float> lw(logw_out ? nT : 0);
+  if (hipError_t e = hipMemcpyAsync(dur.data(), s.dp_dur, dur.size() * sizeof(int32_t), hipMemcpyDeviceToHost, q)) return failed(e);
+  if (logw_out)
+    if (hipError_t e = hipMemcpyAsync(lw.data(), s.taps["logw"].p, lw.size() * sizeof(float), hipMemcpyDeviceToHost, q)) return failed(e);
+  if (hipError_t e = stream_wait(q)) return failed(e);
+  if (plan_out) {  // stays in_use: see above
+    *plan_out = pl;
+    release.pl = nullptr;
+  }
+  int64_t off = 0;
+  for (int b = 0; b < n; b++) {
+    memcpy(durations_out + off, dur.data() + (size_t)b * T, (size_t)utts[b].t * sizeof(int32_t));
+    if (logw_out) memcpy(logw_out + off, lw.data() + (size_t)b * T, (size_t)utts[b].t * sizeof(float));
+    off += utts[b].t;
+  }
+  return PIPER_HIP_OK;
+}
 }
 
 PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot) {
-  const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
-  const VolumeItems vol = take_volume(v, slot);    // (piper_hip_voice_slot_volume)
-  const PitchItems pit = take_pitch(v, slot);      // (piper_hip_voice_slot_pitch)
+  const Controls ctl = take_controls(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody / _volume / _pitch)
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
   if (slot < 0 || slot >= kMaxSlots) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d out of range [0,%d)", slot, kMaxSlots);
   // the batch items may differ in length: the plan is the bucket of the longest, each item carries its own true lengths
   int Tmax = 0, rc;
   int64_t Fmax = 0;
-  std::vector<int> hT(n), hF(n);
-  const bool has_pro = !pro.empty();  // the request runs the plans of requests with prosody
-  if ((rc = check_prosody(pro, utts, n, false)) || (rc = check_volume(vol, utts, n))) return rc;
+  std::vector<int> hF(n);
+  const bool has_pro = !ctl.pro.empty();  // the request runs the plans of requests with prosody
   std::vector<piper_hip_utterance> tempo;  // the utterances at length_scale' where a pitch keeps the tempo
-  if ((rc = check_pitch(pit, utts, n, &tempo))) return rc;
+  if ((rc = check_controls(ctl, utts, n, false, &tempo))) return rc;
   if (!tempo.empty()) utts = tempo.data();
   std::vector<int64_t> wanted(n, -1);  // Σ d of the frame rule per item (there is no fitting on this route)
   // utterances without durations: run the text encoder + duration predictor first (its own cached plan), then continue with
@@ -3069,7 +3219,7 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
       predicted.resize((size_t)total);
       std::vector<piper_hip_speaker> spk;  // the predictor is conditioned too: x = dp.pre(x) + dp.cond(g)
       for (int b = 0; b < n && v->spk.S; b++) spk.push_back(speaker_of(v, slot, b));
-      if ((rc = predict_impl_pro(v, utts, n, predicted.data(), nullptr, (int)total, &dp_plan, spk.empty() ? nullptr : spk.data(), has_pro ? &pro : nullptr)))
+      if ((rc = predict_impl(v, utts, n, predicted.data(), nullptr, (int)total, &dp_plan, spk.empty() ? nullptr : spk.data(), has_pro ? &ctl.pro : nullptr)))
         return rc;
       resolved.assign(utts, utts + n);
       int64_t off = 0;
@@ -3089,7 +3239,6 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
   for (int b = 0; b < n; b++) {
     int64_t Fb = 0;
     if ((rc = check_item(utts[b], b)) || (rc = utt_frames(v, utts[b], b, &Fb))) return rc;
-    hT[b] = utts[b].t;
     hF[b] = (int)Fb;
     if (wanted[b] < 0) wanted[b] = Fb;
     Tmax = std::max(Tmax, utts[b].t);
@@ -3117,67 +3266,43 @@ PH_EXPORT int piper_hip_voice_prepare_batch(piper_hip_voice* v, const piper_hip_
     PH_HIP(hipEventRecord(s.ev_in, q), PIPER_HIP_ERR_LAUNCH);
     PH_HIP(hipStreamWaitEvent(dp_plan->set.stream, s.ev_in, 0), PIPER_HIP_ERR_LAUNCH);
   }
-  reset_stream_state(s);
-  s.h_T = hT;
-  s.h_F = hF;
-  s.h_dur.clear();
-  s.h_wanted = wanted;
-  s.h_fitted.assign(n, 0);
-  s.ran_predict = dp_plan;
+  plan_staged(s, utts, n, &hF, &wanted, dp_plan, 0);  // (in front of the uploads: a prepare that fails below leaves this request's record)
   // Everything that goes to the device leaves from page-locked memory of the slot id (the plan's stream was synchronised above): an
   // asynchronous copy from PAGEABLE memory makes the runtime pin (or stage) the caller's pages on the spot. The noise tensor is copied into
   // bucket rows here, on the host.
   auto& sg = v->staging[slot];
   bool any_noise = false;
   for (int b = 0; b < n; b++) any_noise = any_noise || utts[b].noise;
-  if ((rc = grow_pinned(sg.h_ids, sg.cap_t, (size_t)T * n)) || (rc = grow_pinned(sg.h_f2i, sg.cap_f, (size_t)F * n)) ||
-      (rc = grow_pinned(sg.h_lens, sg.cap_lens, (size_t)2 * n)) || (any_noise && (rc = grow_pinned(sg.h_noise, sg.cap_noise, (size_t)n * I * F))) ||
-      (rc = grow_pinned(sg.h_misc, sg.cap_misc, (size_t)n * (2 * sizeof(unsigned) + sizeof(float)) + 64)))
+  if ((rc = sg.h_ids.ensure((size_t)T * n)) || (rc = sg.h_f2i.ensure((size_t)F * n)) || (rc = sg.h_lens.ensure((size_t)n)) ||
+      (any_noise && (rc = sg.h_noise.ensure((size_t)n * I * F))) || (rc = sg.h_misc.ensure(request_scalars_bytes(n))))
     return rc;
-  unsigned* p_rng = (unsigned*)sg.h_misc;
-  float* p_ns = (float*)(p_rng + 2 * (size_t)n);
-  if ((rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q)) || (rc = stage_pitch(v, slot, s, pit, n, q))) return rc;
-  if (s.pro) {  // the noise multiplier per id, a plan input like the ids (no fitting on this route)
-    if ((rc = grow_pinned(sg.h_pro, sg.cap_pro, (size_t)n * T + n))) return rc;
-    pack_prosody(pro, n, T, nullptr, nullptr, nullptr, (float*)sg.h_pro, nullptr);
-    memset(sg.h_pro + (size_t)n * T, 0, (size_t)n * sizeof(int32_t));
-    PH_HIP(hipMemcpyAsync(s.pro_noise, sg.h_pro, (size_t)n * T * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipMemcpyAsync(s.pro_fit, sg.h_pro + (size_t)n * T, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  }
+  if ((rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, ctl.vol, n, T, q)) || (rc = stage_pitch(v, slot, s, ctl.pit, n, q)))
+    return rc;
+  if (s.pro)  // the noise multiplier per id, a plan input like the ids (no fitting on this route)
+    if ((rc = sg.h_pro.ensure((size_t)n * T + n)) || (rc = stage_prosody_noise(s, sg.h_pro, ctl.pro, n, T, q))) return rc;
+  if ((rc = stage_request_scalars(v, s, sg.h_misc, utts, n, q))) return rc;
   pack_ids(utts, n, T, sg.h_ids);
   for (int b = 0; b < n; b++) {
     const piper_hip_utterance* u = &utts[b];
-    const int Tb = hT[b], Fb = hF[b];
-    s.h_dur.insert(s.h_dur.end(), u->durations, u->durations + Tb);
-    sg.h_lens[b] = Tb;
-    sg.h_lens[n + b] = Fb;
+    const int Tb = u->t, Fb = hF[b];
+    sg.h_lens[b] = Fb;
     int f = 0;  // generate_path: frame f belongs to the phoneme whose cumulative duration covers it
     for (int t = 0; t < Tb; t++)
       for (int j = 0; j < u->durations[t]; j++) sg.h_f2i[(size_t)b * F + f++] = t;
     for (; f < F; f++) sg.h_f2i[(size_t)b * F + f] = 0;
-    p_rng[2 * b] = (!u->noise && u->noise_mode == PIPER_HIP_NOISE_DEVICE) ? 1u : 0u;
-    p_rng[2 * b + 1] = u->seed;
-    p_ns[b] = u->noise_scale;
+    if (!u->noise) continue;
     // noise [I, Fb] → rows of the bucket [I, F]
-    if (u->noise) {
-      float* hb = sg.h_noise + (size_t)b * I * F;
-      for (int c = 0; c < I; c++) {
-        memcpy(hb + (size_t)c * F, u->noise + (size_t)c * Fb, (size_t)Fb * sizeof(float));
-        if (Fb < F) memset(hb + (size_t)c * F + Fb, 0, (size_t)(F - Fb) * sizeof(float));
-      }
-      PH_HIP(hipMemcpyAsync(s.noise + (size_t)b * I * F, hb, (size_t)I * F * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-    } else if (!p_rng[2 * b])
-      PH_HIP(hipMemsetAsync(s.noise + (size_t)b * I * F, 0, (size_t)I * F * sizeof(float), q), PIPER_HIP_ERR_LAUNCH);
+    float* hb = sg.h_noise + (size_t)b * I * F;
+    for (int c = 0; c < I; c++) {
+      memcpy(hb + (size_t)c * F, u->noise + (size_t)c * Fb, (size_t)Fb * sizeof(float));
+      if (Fb < F) memset(hb + (size_t)c * F + Fb, 0, (size_t)(F - Fb) * sizeof(float));
+    }
+    PH_HIP(hipMemcpyAsync(s.noise + (size_t)b * I * F, hb, (size_t)I * F * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   }
-  PH_HIP(hipMemcpyAsync(s.rng, p_rng, 2 * (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.noise_scale, p_ns, (size_t)n * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(s.ids, sg.h_ids, (size_t)T * n * sizeof(int64_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipMemcpyAsync(s.frame2id, sg.h_f2i, (size_t)F * n * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.lensT, sg.h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.lensF, sg.h_lens + n, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpyAsync(s.lensF, sg.h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(stream_wait(q), PIPER_HIP_ERR_LAUNCH);  // noise / scalars come from caller memory
-  s.timed = false;
-  chain_invalidate(s.chain);
   return slot;
 }
 
@@ -3263,17 +3388,14 @@ int bounded_refusals(const piper_hip_voice* v, const piper_hip_utterance* utts, 
 // the frames per item; the plan is the bucket of that bound and every kernel masks by the frame count the device decides. One stream carries
 // uploads → encoder + predictor → generate_path (dp_paths_kernel) → flow + generator; the host learns the lengths with the waveform (collect).
 PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int max_frames) {
-  const ProsodyItems pro = take_prosody(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody)
-  const bool has_pro = !pro.empty();
-  const VolumeItems vol = take_volume(v, slot);  // (piper_hip_voice_slot_volume)
-  const PitchItems pit = take_pitch(v, slot);    // (piper_hip_voice_slot_pitch)
+  const Controls ctl = take_controls(v, slot);  // this call's, whatever becomes of it (piper_hip_voice_slot_prosody / _volume / _pitch)
+  const bool has_pro = !ctl.pro.empty();
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   int Tmax = 0, rc;
   if ((rc = bounded_refusals(v, utts, n, slot, max_frames, false))) return rc;
   for (int b = 0; b < n; b++) Tmax = std::max(Tmax, utts[b].t);
-  if ((rc = check_prosody(pro, utts, n, true)) || (rc = check_volume(vol, utts, n))) return rc;
   std::vector<piper_hip_utterance> tempo;  // the utterances at length_scale' where a pitch keeps the tempo
-  if ((rc = check_pitch(pit, utts, n, &tempo))) return rc;
+  if ((rc = check_controls(ctl, utts, n, true, &tempo))) return rc;
   if (!tempo.empty()) utts = tempo.data();
   const int T = bucket_t(Tmax), F = bucket_f(max_frames), I = v->cfg.inter;
   if ((int64_t)F * v->hop * n > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch too large");
@@ -3297,73 +3419,33 @@ PH_EXPORT int piper_hip_voice_prepare_batch_bounded(piper_hip_voice* v, const pi
   dp->last_use = s.last_use;
   evict_idle_plans(v);  // only now: neither plan can be evicted between the two acquires
   auto& sg = v->staging[slot];
-  const size_t misc_bytes = (size_t)n * (sizeof(int) + 2 * sizeof(unsigned) + sizeof(float)) + dp_scalars_bytes(n);
-  if ((rc = grow_pinned(sg.h_ids, sg.cap_t, (size_t)T * n)) || (rc = grow_pinned(sg.h_misc, sg.cap_misc, misc_bytes)) ||
-      (rc = grow_pinned(sg.h_dpn, sg.cap_dpn, (size_t)n * 2 * T)) ||
-      (rc = grow_pinned(sg.h_res, sg.cap_res, has_pro ? prosody_report_entries(n, T) : (size_t)n + (size_t)n * T)) ||
-      (has_pro && (rc = grow_pinned(sg.h_pro, sg.cap_pro, (size_t)4 * n * T + n))))
+  const size_t nT = (size_t)n * T;
+  if ((rc = sg.h_ids.ensure(nT)) || (rc = sg.h_misc.ensure(request_scalars_bytes(n) + dp_scalars_bytes(n))) || (rc = sg.h_dpn.ensure(2 * nT)) ||
+      (rc = sg.h_res.ensure(has_pro ? prosody_report_entries(n, T) : (size_t)n + nT)) || (has_pro && (rc = sg.h_pro.ensure(4 * nT + n))))
     return rc;
-  int* h_lens = (int*)sg.h_misc;
-  unsigned* h_rng = (unsigned*)(h_lens + n);
-  float* h_ns = (float*)(h_rng + 2 * n);
-  char* h_sc = (char*)(h_ns + n);
-  pack_ids(utts, n, T, sg.h_ids);
-  pack_dp_inputs(utts, n, T, sg.h_dpn, h_sc);
-  for (int b = 0; b < n; b++) {
-    const piper_hip_utterance& u = utts[b];
-    h_lens[b] = u.t;
-    h_rng[2 * b] = u.noise_mode == PIPER_HIP_NOISE_DEVICE ? 1u : 0u;
-    h_rng[2 * b + 1] = u.seed;
-    h_ns[b] = u.noise_scale;
-    sg.h_res[b] = -1;
-  }
+  for (int b = 0; b < n; b++) sg.h_res[b] = -1;
   const hipStream_t q = s.set.stream;
-  if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, vol, n, T, q)) ||
-      (rc = stage_pitch(v, slot, s, pit, n, q)))
+  if ((rc = stage_speakers(v, slot, *dp, n, q)) || (rc = stage_speakers(v, slot, s, n, q)) || (rc = stage_volume(v, slot, s, ctl.vol, n, T, q)) ||
+      (rc = stage_pitch(v, slot, s, ctl.pit, n, q)))
     return rc;
-  if (has_pro) {  // the per-id arrays: plan inputs of the predictor plan (length, floor, ceiling) and of this one (noise, fit)
-    const size_t nT = (size_t)n * T;
-    float* h_len = (float*)sg.h_pro;
-    int32_t *h_min = sg.h_pro + nT, *h_max = sg.h_pro + 2 * nT, *h_fit = sg.h_pro + 4 * nT;
-    float* h_noise = (float*)(sg.h_pro + 3 * nT);
-    pack_prosody(pro, n, T, h_len, h_min, h_max, h_noise, h_fit);
-    PH_HIP(hipMemcpyAsync(dp->pro_len, h_len, nT * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipMemcpyAsync(dp->pro_min, h_min, nT * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipMemcpyAsync(dp->pro_max, h_max, nT * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipMemcpyAsync(s.pro_noise, h_noise, nT * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-    PH_HIP(hipMemcpyAsync(s.pro_fit, h_fit, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  }
-  PH_HIP(hipMemcpyAsync(dp->ids, sg.h_ids, (size_t)n * T * sizeof(int64_t), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(dp->lensT, h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(dp->dp_noise, sg.h_dpn, (size_t)n * 2 * T * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(dp->dp_scalars, h_sc, dp_scalars_bytes(n), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.lensT, h_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.rng, h_rng, 2 * (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  PH_HIP(hipMemcpyAsync(s.noise_scale, h_ns, (size_t)n * sizeof(float), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  for (int b = 0; b < n; b++)  // INJECTED without a tensor = zero noise, as in prepare_batch
-    if (!h_rng[2 * b]) PH_HIP(hipMemsetAsync(s.noise + (size_t)b * I * F, 0, (size_t)I * F * sizeof(float), q), PIPER_HIP_ERR_LAUNCH);
+  // this plan's own inputs: the request scalars, and of a request with prosody the noise multipliers and fit (the front of h_pro)
+  if ((rc = stage_request_scalars(v, s, sg.h_misc, utts, n, q)) || (has_pro && (rc = stage_prosody_noise(s, sg.h_pro, ctl.pro, n, T, q)))) return rc;
+  // the predictor plan's: lensT is the one of the request scalars, the predictor's own scalars lie behind them, and length, floor and
+  // ceiling behind this plan's part of h_pro
+  const RequestScalars rq = request_scalars(sg.h_misc, n);
+  const PredictorInputs in{sg.h_ids, rq.lensT, sg.h_dpn, rq.end, nullptr, has_pro ? sg.h_pro + nT + n : nullptr};
+  pack_predictor_inputs(utts, n, T, &ctl.pro, in);
+  PH_HIP(upload_predictor_inputs(*dp, n, in, q), PIPER_HIP_ERR_LAUNCH);
   if ((rc = launch_plan(v, *dp, q))) return rc;
   PH_HIP(hipMemcpyAsync(s.stats, dp->stats, (size_t)n * 2 * I * T * sizeof(float), hipMemcpyDeviceToDevice, q), PIPER_HIP_ERR_LAUNCH);
-  int32_t* rep = nullptr;
-  if (hipHostGetDevicePointer((void**)&rep, sg.h_res, 0) != hipSuccess) { rep = nullptr; (void)hipGetLastError(); }
+  int32_t* const rep = sg.h_res.mapped();
   if (!rep) PH_FAIL(PIPER_HIP_ERR_UNAVAILABLE, "prepare_batch_bounded: page-locked memory has no device mapping on this system");
   if (has_pro) {  // generate_path with the fit step (prosody.hip), in the place of dp_paths_kernel
     if ((rc = launch_dp_paths_prosody(q, dp->dp_dur, dp->lensT, s.pro_fit, T, F, std::min(max_frames, F), s.frame2id, s.lensF, rep, n))) return rc;
   } else
     hipLaunchKernelGGL(dp_paths_kernel, dim3(n), dim3(256), 0, q, dp->dp_dur, dp->lensT, T, F, std::min(max_frames, F), s.frame2id, s.lensF, rep, n);
   PH_HIP(hipGetLastError(), PIPER_HIP_ERR_LAUNCH);
-  reset_stream_state(s);
-  s.h_T.assign(n, 0);
-  for (int b = 0; b < n; b++) s.h_T[b] = utts[b].t;
-  s.h_F.assign(n, F);  // capacity until collect has the device's answer
-  s.h_dur.clear();
-  s.h_wanted.clear();
-  s.h_fitted.clear();
-  s.ran_predict = nullptr;  // (the predictor plan stays attached to the slot id: attached_dp)
-  s.bounded_pending = true;
-  s.bounded_cap = std::min(max_frames, F);
-  s.timed = false;
-  chain_invalidate(s.chain);
+  plan_staged(s, utts, n, nullptr, nullptr, nullptr, std::min(max_frames, F));  // (the predictor plan stays attached to the slot id: attached_dp)
   return slot;
 }
 
@@ -3434,81 +3516,6 @@ PH_EXPORT int piper_hip_voice_predict_durations_speakers(piper_hip_voice* v, con
   }
   return predict_impl(v, utts, n, durations_out, logw_out, max_entries, nullptr, speakers);
 }
-namespace {
-// plan_out (optional): the encoder + predictor plan that ran, left marked in_use so that its m_p / logs_p stay put until the caller
-// has enqueued the copy into the plan that continues from them (the caller clears in_use)
-// speakers (optional): [n], one per utterance, checked by the caller; null on a voice with a table = speaker 0 alone
-int predict_impl(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
-                 const piper_hip_speaker* speakers) {
-  return predict_impl_pro(v, utts, n, durations_out, logw_out, max_entries, plan_out, speakers, nullptr);
-}
-int predict_impl_pro(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int32_t* durations_out, float* logw_out, int max_entries, Slot** plan_out,
-                     const piper_hip_speaker* speakers, const ProsodyItems* pro) {
-  if (!v || !utts || !durations_out) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
-  if (n < 1 || n > 256) PH_FAIL(PIPER_HIP_ERR_SHAPE, "batch size %d outside [1,256]", n);
-  if (!v->cfg.dp_present) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "voice has no duration predictor (dp_present = 0)");
-  std::vector<piper_hip_speaker> spk;
-  if (v->spk.S) {
-    piper_hip_speaker d{};
-    d.n = 1;
-    d.weights[0] = 1.0f;
-    spk.assign((size_t)n, d);
-    if (speakers) spk.assign(speakers, speakers + n);
-  }
-  int Tmax = 0, rc;
-  int64_t total = 0;
-  for (int b = 0; b < n; b++) {
-    if ((rc = check_item(utts[b], b))) return rc;
-    Tmax = std::max(Tmax, utts[b].t);
-    total += utts[b].t;
-  }
-  if (max_entries < total) PH_FAIL(PIPER_HIP_ERR_SHAPE, "predict_durations: output holds %d < %lld entries", max_entries, (long long)total);
-  PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  const int T = bucket_t(Tmax);
-  Slot* pl = nullptr;
-  bool built = false;
-  if ((rc = acquire_plan(v, PLAN_PREDICT, T, 16, n, &pl, &built, pro != nullptr))) return rc;
-  Slot& s = *pl;
-  s.in_use = true;
-  s.last_use = ++v->use_clock;
-  std::vector<float> plen(pro ? (size_t)n * T : 0);
-  std::vector<int32_t> pmin(plen.size()), pmax(plen.size());
-  if (pro) pack_prosody(*pro, n, T, plen.data(), pmin.data(), pmax.data(), nullptr, nullptr);
-  std::vector<int64_t> ids((size_t)n * T);
-  std::vector<int> lens(n);
-  std::vector<float> nz((size_t)n * 2 * T);
-  std::vector<char> sc(dp_scalars_bytes(n));
-  pack_ids(utts, n, T, ids.data());
-  pack_dp_inputs(utts, n, T, nz.data(), sc.data());
-  for (int b = 0; b < n; b++) lens[b] = utts[b].t;
-  hipError_t e = hipMemcpyAsync(s.ids, ids.data(), ids.size() * sizeof(int64_t), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s.lensT, lens.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s.dp_noise, nz.data(), nz.size() * sizeof(float), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s.dp_scalars, sc.data(), sc.size(), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess && s.spk_in) e = hipMemcpyAsync(s.spk_in, spk.data(), spk.size() * sizeof(piper_hip_speaker), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess && pro) e = hipMemcpyAsync(s.pro_len, plen.data(), plen.size() * sizeof(float), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess && pro) e = hipMemcpyAsync(s.pro_min, pmin.data(), pmin.size() * sizeof(int32_t), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess && pro) e = hipMemcpyAsync(s.pro_max, pmax.data(), pmax.size() * sizeof(int32_t), hipMemcpyHostToDevice, s.set.stream);
-  if (e == hipSuccess && launch_plan(v, s)) e = hipErrorUnknown;
-  std::vector<int32_t> dur((size_t)n * T);
-  std::vector<float> lw(logw_out ? (size_t)n * T : 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(dur.data(), s.dp_dur, dur.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s.set.stream);
-  if (e == hipSuccess && logw_out) e = hipMemcpyAsync(lw.data(), s.taps["logw"].p, lw.size() * sizeof(float), hipMemcpyDeviceToHost, s.set.stream);
-  if (e == hipSuccess) e = stream_wait(s.set.stream);
-  if (plan_out && e == hipSuccess) *plan_out = pl;  // stays in_use: see above
-  else s.in_use = false;
-  evict_idle_plans(v);
-  if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "predict_durations: %s", hipGetErrorString(e));
-  int64_t off = 0;
-  for (int b = 0; b < n; b++) {
-    memcpy(durations_out + off, dur.data() + (size_t)b * T, (size_t)utts[b].t * sizeof(int32_t));
-    if (logw_out) memcpy(logw_out + off, lw.data() + (size_t)b * T, (size_t)utts[b].t * sizeof(float));
-    off += utts[b].t;
-  }
-  return PIPER_HIP_OK;
-}
-}  // namespace
-
 PH_EXPORT int piper_hip_voice_prepared_samples(const piper_hip_voice* v, int slot, int64_t* per_item, int max_items, int64_t* total) {
   const Slot* p = slot_plan(v, slot);
   if (!p) PH_FAIL(PIPER_HIP_ERR_ARG, "slot %d is not prepared", slot);
@@ -3637,7 +3644,7 @@ int stage_volume(piper_hip_voice* v, int slot, Slot& s, const VolumeItems& vol, 
   if (!s.vol_on) return PIPER_HIP_OK;
   auto& sg = v->staging[slot];
   int rc;
-  if ((rc = grow_pinned(sg.h_vol, sg.cap_vol, (size_t)n * T))) return rc;
+  if ((rc = sg.h_vol.ensure((size_t)n * T))) return rc;
   if (!s.vol_gain) {
     void* p = nullptr;
     if ((rc = plan_alloc(v, s, (size_t)s.NB * s.T * sizeof(float), &p))) return rc;
@@ -3709,10 +3716,10 @@ int stage_pitch(piper_hip_voice* v, int slot, Slot& s, const PitchItems& pit, in
   size_t bytes = head;
   for (const PtDesign* d : tabs) bytes += (d->taps.size() * sizeof(float) + 15) & ~(size_t)15;
   auto& sg = v->staging[slot];
-  if ((rc = grow_pinned(sg.h_pt, sg.cap_pt, bytes))) return rc;
+  if ((rc = sg.h_pt.ensure(bytes))) return rc;
   if ((rc = plan_ensure(v, s, ch.pt_dev, bytes))) return rc;
   char* const dev = ch.pt_dev.as<char>();
-  PtItem* items = (PtItem*)sg.h_pt;
+  PtItem* items = (PtItem*)sg.h_pt.p;
   for (int b = 0; b < s.NB; b++) items[b] = PtItem{nullptr, kPtOne, 0, 0};
   size_t off = head;
   for (const PtDesign* d : tabs) {
@@ -3766,11 +3773,11 @@ int chain_pitch(piper_hip_voice* v, Slot& s, Chain& c) {
 // Settings of a slot id on their way to a plan: one T in the slot id's page-locked `host`, written by `fill`, then copied to `dev` on q.
 // The staging buffer is rewritten only once the copy queued from it last time has run (`ev`), even where that call failed before its wait.
 template <class T, class Fill>
-int upload_settings(T*& host, size_t& cap, hipEvent_t& ev, void* dev, hipStream_t q, Fill fill) {
+int upload_settings(PinnedBuf<T>& host, hipEvent_t& ev, void* dev, hipStream_t q, Fill fill) {
   if (ev) PH_HIP(hipEventSynchronize(ev), PIPER_HIP_ERR_LAUNCH);
   else PH_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming), PIPER_HIP_ERR_LAUNCH);
   int rc;
-  if ((rc = grow_pinned(host, cap, 1, 1)) || (rc = fill(host))) return rc;
+  if ((rc = host.ensure(1, 1)) || (rc = fill(host.p))) return rc;
   PH_HIP(hipMemcpyAsync(dev, host, sizeof(T), hipMemcpyHostToDevice, q), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(hipEventRecord(ev, q), PIPER_HIP_ERR_LAUNCH);
   return PIPER_HIP_OK;
@@ -3796,7 +3803,7 @@ int chain_eq(piper_hip_voice* v, int slot, Slot& s, Chain& c) {
   if (!ch.eq_ok) {
     if (!ch.eq_dev_ok || memcmp(&ch.eq_dev_eq, &se.eq, sizeof(piper_hip_eq)) != 0) {
       auto& sg = v->staging[slot];
-      if ((rc = upload_settings(sg.h_eq, sg.cap_eq, sg.eq_ev, ch.eq_dev.p, s.set.stream,
+      if ((rc = upload_settings(sg.h_eq, sg.eq_ev, ch.eq_dev.p, s.set.stream,
                                 [&](EqDesign* d) { return eq_build(&se.eq, v->cfg.sample_rate, d); })))
         return rc;
       ch.eq_dev_ok = true;
@@ -3915,12 +3922,11 @@ int join_items(piper_hip_voice* v, int slot, Slot& s, const Chain& items, int64_
   char* const dev = ch.jn_dev.as<char>();
   const hipStream_t st = s.set.stream;
   if (ch.jn_gen != sj.gen) {
-    if ((rc = upload_settings(sg.h_join, sg.cap_join, sg.join_ev, dev, st, [&](JoinParams* p) { *p = sj.p; return PIPER_HIP_OK; }))) return rc;
+    if ((rc = upload_settings(sg.h_join, sg.join_ev, dev, st, [&](JoinParams* p) { *p = sj.p; return PIPER_HIP_OK; }))) return rc;
     ch.jn_gen = sj.gen;
   }
-  if ((rc = grow_pinned(sg.h_jrep, sg.cap_jrep, (size_t)kJoinReport, (size_t)kJoinReport))) return rc;
-  int64_t* rep_host = nullptr;
-  if (hipHostGetDevicePointer((void**)&rep_host, sg.h_jrep, 0) != hipSuccess) { rep_host = nullptr; (void)hipGetLastError(); }
+  if ((rc = sg.h_jrep.ensure((size_t)kJoinReport, (size_t)kJoinReport))) return rc;
+  int64_t* const rep_host = sg.h_jrep.mapped();
   int64_t z = sj.p.tail;
   for (int b = 0; b + 1 < s.NB; b++) z = std::max(z, sj.p.gap[b]);
   int* edges = (int*)(dev + o_edges);
@@ -3939,7 +3945,7 @@ int join_items(piper_hip_voice* v, int slot, Slot& s, const Chain& items, int64_
 // after the slot's stream has been synchronised behind join_items: the report → h_jrep (piper_hip_voice_join_report); returns the total
 int64_t join_landed(piper_hip_voice* v, int slot, Slot& s) {
   const auto& sg = v->staging[slot];
-  s.chain.h_jrep.assign(sg.h_jrep, sg.h_jrep + 1 + 2 * s.NB);
+  s.chain.h_jrep.assign(sg.h_jrep.p, sg.h_jrep + 1 + 2 * s.NB);
   return s.chain.h_jrep[0];
 }
 
@@ -3975,8 +3981,8 @@ int collect_joined(piper_hip_voice* v, int slot, Slot& s, const Chain& items, in
   const hipStream_t st = s.set.stream;
   float* dst_dev = nullptr;
   if ((size_t)cap * sizeof(float) <= kPinnedMax && !is_caller_pinned(host_audio)) {
-    if (grow_pinned(sg.h_audio, sg.audio_cap, (size_t)std::max<int64_t>(cap, 1), kAudioMinCap)) (void)hipGetLastError();
-    if (sg.h_audio && hipHostGetDevicePointer((void**)&dst_dev, sg.h_audio, 0) != hipSuccess) { dst_dev = nullptr; (void)hipGetLastError(); }
+    if (sg.h_audio.ensure((size_t)std::max<int64_t>(cap, 1), kAudioMinCap)) (void)hipGetLastError();
+    dst_dev = sg.h_audio.mapped();
   }
   if (dst_dev) {
     const int blocks = (int)std::min<int64_t>(std::max<int64_t>((cap + 4 * 256 - 1) / (4 * 256), 1), 1024);
@@ -4049,8 +4055,8 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     const size_t ub = (size_t)row * s.NB * sizeof(float);
     float* dst_dev = nullptr;
     if (host_audio && ub <= ((size_t)1 << 20) && (v->hop & 3) == 0) {
-      if (grow_pinned(sg.h_audio, sg.audio_cap, (size_t)row * s.NB, kAudioMinCap)) (void)hipGetLastError();
-      if (sg.h_audio && hipHostGetDevicePointer((void**)&dst_dev, sg.h_audio, 0) != hipSuccess) { dst_dev = nullptr; (void)hipGetLastError(); }
+      if (sg.h_audio.ensure((size_t)row * s.NB, kAudioMinCap)) (void)hipGetLastError();
+      dst_dev = sg.h_audio.mapped();
     }
     if (dst_dev) {
       for (int b = 0; b < s.NB; b++) {
@@ -4087,8 +4093,8 @@ PH_EXPORT int piper_hip_voice_collect(piper_hip_voice* v, int slot, float* host_
     const size_t bytes = (size_t)total * sizeof(float);
     // a destination the caller page-locked itself (piper_hip_host_alloc) takes the DMA directly
     const bool caller_pinned = is_caller_pinned(host_audio);
-    if (!caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (size_t)total, kAudioMinCap)) (void)hipGetLastError();
-    float* h_audio = sg.audio_cap >= (size_t)total ? sg.h_audio : nullptr;
+    if (!caller_pinned && bytes <= kChunkedMax && sg.h_audio.ensure((size_t)total, kAudioMinCap)) (void)hipGetLastError();
+    float* h_audio = sg.h_audio.cap >= (size_t)total ? sg.h_audio.p : nullptr;
     if (!caller_pinned && bytes > kPinnedMax && bytes <= kChunkedMax && h_audio) {
       // the items back to back in the staging buffer, cut into chunks; `cuts` = end offset (floats) of each chunk
       std::vector<int64_t> cuts;
@@ -4215,8 +4221,7 @@ int launch_front(Slot& s) {
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_utterance* u, int slot, int chunk_frames) {
-  const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
-  const VolumeClear vc{v, slot};  // (and its volume)
+  const ControlsClear cc{v, slot};  // a staging call: the slot id's prosody, volume and pitch are this call's, on every way out
   if (int prc = refuse_pitch(v, slot, "stream_begin")) return prc;
   if (chunk_frames < 1) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_begin: chunk_frames must be >= 1");
   int rc = piper_hip_voice_prepare(v, u, slot);
@@ -4237,8 +4242,6 @@ PH_EXPORT int piper_hip_voice_stream_begin(piper_hip_voice* v, const piper_hip_u
 }
 
 namespace {
-int plan_alloc(piper_hip_voice* v, Slot& s, size_t bytes, void** out);
-
 // ---- 16-bit PCM out of a plan: where the convert kernel stores and how the samples reach the caller. The policy and the thresholds are
 // collect's (see there for the measurements behind them): a destination the caller page-locked takes kernel stores through its host
 // mapping up to 16 MB; a pageable one is served through the slot id's page-locked staging — kernel stores up to 1 MB, 1 MB chunks by the
@@ -4258,8 +4261,8 @@ int pcm_route(piper_hip_voice* v, Slot& plan, piper_hip_voice::Staging& sg, void
               PcmRoute* r) {
   const size_t bytes = samples * elem;
   r->caller_pinned = is_caller_pinned(host);
-  if (!r->caller_pinned && bytes <= kChunkedMax && grow_pinned(sg.h_audio, sg.audio_cap, (bytes + 3) / 4, kAudioMinCap)) (void)hipGetLastError();
-  r->stage = (!r->caller_pinned && sg.h_audio && sg.audio_cap * sizeof(float) >= bytes) ? (void*)sg.h_audio : nullptr;
+  if (!r->caller_pinned && bytes <= kChunkedMax && sg.h_audio.ensure((bytes + 3) / 4, kAudioMinCap)) (void)hipGetLastError();
+  r->stage = (!r->caller_pinned && sg.h_audio && sg.h_audio.cap * sizeof(float) >= bytes) ? (void*)sg.h_audio.p : nullptr;
   static const bool dma_only = getenv("PIPER_HIP_COLLECT_DMA") != nullptr;
   void* target = r->caller_pinned ? (bytes <= kChunkedMax ? (void*)host : nullptr) : (bytes <= kPinnedMax ? (void*)r->stage : nullptr);
   if (!dma_only && target) {
@@ -4477,7 +4480,7 @@ int volume_step_buffers(piper_hip_voice* v, int slot, Stream& st, size_t bytes) 
     st.vol_desc = (VolStepRow*)p;
   }
   auto& sg = v->staging[slot];
-  return grow_pinned(sg.h_vstep, sg.cap_vstep, (size_t)256);
+  return sg.h_vstep.ensure((size_t)256);
 }
 
 // One launch behind the window plan's graph: the chunks of `rows` generator rows of audio [rows][row] under their envelopes → st.vol.
@@ -4507,7 +4510,7 @@ hipError_t eq_step(piper_hip_voice* v, int slot, Stream& st, const std::vector<E
     sq.out = (float*)p;
     sq.out_bytes = bytes;
   }
-  if (grow_pinned(sg.h_estep, sg.cap_estep, (size_t)sq.rows, (size_t)256)) return hipErrorOutOfMemory;
+  if (sg.h_estep.ensure((size_t)sq.rows, (size_t)256)) return hipErrorOutOfMemory;
   const int rows = (int)tab.size();
   if (rows > sq.rows) return hipErrorInvalidValue;
   int max_n = 0;
@@ -4549,7 +4552,7 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   int64_t dn_s = (int64_t)row.next * v->hop, lim_hi = 0;  // where the output stage's chunk starts in the item
   int dn_skip = w.skip;
   if (lvl.on) {
-    if (int rc0 = grow_pinned(v->staging[slot].h_desc, v->staging[slot].cap_desc, kLvStageInts)) return rc0;
+    if (int rc0 = v->staging[slot].h_desc.ensure(kLvStageInts)) return rc0;
     lrow = level_range(row, w, v->hop, &dn_s, &lim_hi);
     want = lim_hi - dn_s;
     dn_skip = 0;
@@ -4564,7 +4567,7 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
     if (!pcm) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next: slot %d delivers at %d Hz: use stream_next_pcm16", slot, rs.rate);
     if (!want_out) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_next_pcm16: a stream with an output rate needs a buffer");
     int rc0 = voice_filter(v, rs.rate, &rd, &rf);
-    if (!rc0) rc0 = grow_pinned(v->staging[slot].h_desc, v->staging[slot].cap_desc, kRateStageInts);
+    if (!rc0) rc0 = v->staging[slot].h_desc.ensure(kRateStageInts);
     if (rc0) return rc0;
     int64_t j0, j1;
     rate_range(*rd, dn_s, dn_s + dn_n, (int64_t)Ftrue * v->hop, &j0, &j1);
@@ -4904,7 +4907,7 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
     if ((rc = voice_filter(v, rs.rate, &rd, &rf))) return rc;
   }
   StreamLevel& lvl = st.lv;
-  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, lvl.on ? kLvStageInts : mix ? kMixStageInts : rd ? kRateStageInts : kDescStageInts))) return rc;
+  if ((rc = sg.h_desc.ensure(lvl.on ? kLvStageInts : mix ? kMixStageInts : rd ? kRateStageInts : kDescStageInts))) return rc;
   LvStepRow* lrow = (LvStepRow*)(sg.h_desc + kLvStageOff);  // (only touched on a slot with a level)
   std::vector<int64_t> lim_hi(n, 0);
   RsStepRow* rrow = (RsStepRow*)(sg.h_desc + kDescStageInts);  // (only touched when rd)
@@ -4993,7 +4996,7 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
   const size_t total_bytes = (size_t)total * sample_bytes;  // what the pack kernel writes and the host receives
   if (total_bytes > st.pack_bytes)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, st.pack_bytes / sizeof(float));
-  if (want_out && (rc = grow_pinned(sg.h_audio, sg.audio_cap, mix ? ((size_t)total + 3) / 4 : rd ? ((size_t)total + 1) / 2 : (size_t)total, kAudioMinCap))) return rc;
+  if (want_out && (rc = sg.h_audio.ensure(mix ? ((size_t)total + 3) / 4 : rd ? ((size_t)total + 1) / 2 : (size_t)total, kAudioMinCap))) return rc;
   // generator-only plan of the step's longest window at the stream's batch size (rows past their end have length 0): a pool and a group
   // of the same size use the same plans
   Slot* gs = nullptr;
@@ -5138,8 +5141,7 @@ int pool_step(piper_hip_voice* v, int slot, StreamPool& P, const Sink& out, int6
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper_hip_utterance* utts, int n, int slot, int chunk_frames) {
-  const ProsodyClear pc{v, slot};  // a staging call: the slot id's prosody is this call's, on every way out
-  const VolumeClear vc{v, slot};  // (and its volume)
+  const ControlsClear cc{v, slot};  // a staging call: the slot id's prosody, volume and pitch are this call's, on every way out
   if (int prc = refuse_pitch(v, slot, "stream_begin_batch")) return prc;
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   if (n < 1 || n > kMaxGroup) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_begin_batch: group of %d outside [1,%d]", n, kMaxGroup);
@@ -5258,8 +5260,7 @@ int launch_front_async(Slot& s) {
 // rows are pending until pool_resolve; nothing below waits for the GPU then, but for the two waits the header names.
 int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot, const piper_hip_stream_format* fmts,
               bool with_formats, int* items_out, int64_t* samples_out, int bound = 0) {
-  const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
-  const VolumeClear vc{v, work_slot};  // (and its volume)
+  const ControlsClear cc{v, work_slot};  // a staging call: the work slot's prosody, volume and pitch are this join's, on every way out
   if (int prc = refuse_pitch(v, work_slot, "stream_pool_join")) return prc;
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   StreamPool* P = slot_pool(v, slot);
@@ -5304,19 +5305,14 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   auto item_stride = [&](int i) { return bound ? w.F : bucket_f(w.h_F[i]); };
   int32_t* want_rep = nullptr;  // bounded: the device mapping of the work slot's report (dp_paths_kernel's counts before clamping)
   if (bound) {
-    if (!P->h_rep) {
-      PH_HIP(hipHostMalloc((void**)&P->h_rep, (size_t)capacity * 2 * sizeof(int32_t)), PIPER_HIP_ERR_ALLOC);
-      if (hipHostGetDevicePointer((void**)&P->d_rep, P->h_rep, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipHostFree(P->h_rep);
-        P->h_rep = nullptr;
-        PH_FAIL(PIPER_HIP_ERR_UNAVAILABLE, "stream_pool_join_bounded: page-locked memory has no device mapping on this system");
-      }
+    // the pool's own report, allocated by its first bounded join (capacity >= 1: pool_open refuses less), and the work slot's
+    if (!P->d_rep) {
+      if ((rc = P->h_rep.ensure((size_t)capacity * 2, (size_t)capacity * 2))) return rc;
+      P->d_rep = P->h_rep.mapped();
     }
-    if (hipHostGetDevicePointer((void**)&want_rep, v->staging[work_slot].h_res, 0) != hipSuccess) {
-      (void)hipGetLastError();
+    want_rep = v->staging[work_slot].h_res.mapped();
+    if (!P->d_rep || !want_rep)
       PH_FAIL(PIPER_HIP_ERR_UNAVAILABLE, "stream_pool_join_bounded: page-locked memory has no device mapping on this system");
-    }
   }
   // rows, lowest free index first, and their stores. Nothing of the pool changes before everything that can fail has succeeded.
   std::vector<int> take;
@@ -5324,7 +5320,7 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
     if (!st.rows[r].active) take.push_back(r);
   auto& sg = v->staging[work_slot];  // free: prepare_batch waited for whatever used this slot id's staging before
   const size_t tab_ints = (size_t)st.NBg * sizeof(PoolRowRef) / sizeof(int), join_ints = (size_t)n * sizeof(PoolJoinEnt) / sizeof(int);
-  if ((rc = grow_pinned(sg.h_desc, sg.cap_desc, (size_t)kMaxGroup * (sizeof(PoolRowRef) + sizeof(PoolJoinEnt)) / sizeof(int)))) return rc;
+  if ((rc = sg.h_desc.ensure((size_t)kMaxGroup * (sizeof(PoolRowRef) + sizeof(PoolJoinEnt)) / sizeof(int)))) return rc;
   int stride_max = 0;
   for (int i = 0; i < n; i++) {
     auto& r = P->ext[take[i]];
@@ -5356,7 +5352,7 @@ int pool_join(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int
   // plan's arena is reused (prepare on the same plan, detach, evict_idle_plans). It first waits for the adopts of earlier joins since the
   // last step: they read the tables this join uploads anew, and one of them may write a row this join takes again.
   const hipStream_t q = w.set.stream;
-  PoolRowRef* tab = (PoolRowRef*)sg.h_desc;  // the whole row table as it stands after this join, then the join's own table
+  PoolRowRef* tab = (PoolRowRef*)sg.h_desc.p;  // the whole row table as it stands after this join, then the join's own table
   PoolJoinEnt* jt = (PoolJoinEnt*)(sg.h_desc + tab_ints);
   for (int r = 0; r < st.NBg; r++) {
     tab[r].z = r < capacity ? P->ext[r].z : nullptr;
@@ -5425,8 +5421,7 @@ PH_EXPORT int piper_hip_voice_stream_pool_join_formats(piper_hip_voice* v, int s
 
 PH_EXPORT int piper_hip_voice_stream_pool_join_bounded(piper_hip_voice* v, int slot, const piper_hip_utterance* utts, int n, int work_slot,
                                                        int max_frames, const piper_hip_stream_format* fmts, int* items_out) {
-  const ProsodyClear pc{v, work_slot};  // a staging call: the work slot's prosody is this join's, on every way out
-  const VolumeClear vc{v, work_slot};  // (and its volume)
+  const ControlsClear cc{v, work_slot};  // a staging call: the work slot's prosody, volume and pitch are this join's, on every way out
   if (int prc = refuse_pitch(v, work_slot, "stream_pool_join_bounded")) return prc;
   if (!v || !utts) PH_FAIL(PIPER_HIP_ERR_ARG, "null argument");
   // prepare_batch_bounded's own refusals, before anything of the pool is looked at or regrown (it repeats them)
@@ -5546,8 +5541,8 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   float* peaks_host = nullptr;
   if (normalize) {
     if ((rc = plan_ensure(v, s, s.chain.peaks, (size_t)NB * sizeof(float)))) return rc;
-    if ((rc = grow_pinned(sg.h_peaks, sg.cap_peaks, (size_t)kMaxGroup, (size_t)kMaxGroup))) return rc;
-    if (hipHostGetDevicePointer((void**)&peaks_host, sg.h_peaks, 0) != hipSuccess) { peaks_host = nullptr; (void)hipGetLastError(); }
+    if ((rc = sg.h_peaks.ensure((size_t)kMaxGroup, (size_t)kMaxGroup))) return rc;
+    peaks_host = sg.h_peaks.mapped();
   }
   PcmRoute r;
   const int64_t dev_samples = joined ? std::max(out_len(jcap), jcap) : std::max<int64_t>(out_len((int64_t)F * hop), (int64_t)F * hop) * NB;
@@ -5574,7 +5569,7 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
     const int64_t total = out_len(join_landed(v, slot, s));
     if (bounded && (rc = bounded_finish(v, slot, s))) return rc;
     if (r.mapped && !r.caller_pinned) memcpy(host_pcm, r.stage, (size_t)total * elem);
-    if (normalize) s.chain.h_peaks.assign(sg.h_peaks, sg.h_peaks + 1);
+    if (normalize) s.chain.h_peaks.assign(sg.h_peaks.p, sg.h_peaks + 1);
     return PIPER_HIP_OK;
   }
   if (normalize) PH_HIP(launch_pcm16_peak(q, peak_src.audio, chain.row, chain.lensF, F, hop, NB, peaks), PIPER_HIP_ERR_LAUNCH);
@@ -5589,7 +5584,7 @@ int collect_pcm(piper_hip_voice* v, int slot, const piper_hip_pcm_params* params
   if (r.mapped && !r.caller_pinned) {  // the kernel stored into the staging: the true total is known by now
     memcpy(host_pcm, r.stage, (size_t)delivered_samples(v, slot, s, rd) * elem);
   }
-  if (normalize) s.chain.h_peaks.assign(sg.h_peaks, sg.h_peaks + NB);
+  if (normalize) s.chain.h_peaks.assign(sg.h_peaks.p, sg.h_peaks + NB);
   return PIPER_HIP_OK;
 }
 }  // namespace
@@ -5621,9 +5616,7 @@ int g711_law(const char* who, int law);
 // the order law (who != nullptr: a G.711 entry point, enc is the caller's law), params, rate design, prepare.
 int synthesize_pcm(piper_hip_voice* v, const piper_hip_utterance* u, const piper_hip_pcm_params* params, int out_rate, const char* who, int enc,
                    void* host, int64_t max_samples, int64_t* n_samples) {
-  const ProsodyClear pc{v, 0};  // a staging call on slot 0
-  const VolumeClear vc{v, 0};
-  const PitchClear tc{v, 0};
+  const ControlsClear cc{v, 0};  // a staging call on slot 0
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
   float gain;
   bool normalize;
@@ -5830,7 +5823,7 @@ PH_EXPORT int piper_hip_voice_loudness(piper_hip_voice* v, int slot, float* lufs
   Chain c;  // the items the loudness stage reads: shaped, pitched and EQ'd where there are a volume, a pitch, an EQ
   if ((rc = chain_walk(v, slot, s, &c, nullptr)) || (rc = chain_measure(v, s, c, f, t))) return rc;
   auto& sg = v->staging[slot];
-  if ((rc = grow_pinned(sg.h_loud, sg.cap_loud, (size_t)2 * s.NB, (size_t)2 * kMaxGroup))) return rc;
+  if ((rc = sg.h_loud.ensure((size_t)2 * s.NB, (size_t)2 * kMaxGroup))) return rc;
   PH_HIP(hipMemcpyAsync(sg.h_loud, s.chain.loud_rep.p, (size_t)2 * s.NB * sizeof(float), hipMemcpyDeviceToHost, s.set.stream), PIPER_HIP_ERR_LAUNCH);
   PH_HIP(stream_wait(s.set.stream), PIPER_HIP_ERR_LAUNCH);
   for (int b = 0; b < s.NB; b++) {
