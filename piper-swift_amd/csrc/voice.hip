@@ -266,18 +266,26 @@ struct StreamRow {
   int64_t lim_lo = 0;  // read on a slot with a level only: where the row's previous step ended, in limited samples (a step at next == 0 starts it at 0)
 };
 
+// A device buffer that knows its own size, kept by its owner until a larger one is needed: of a plan's output chain (in the plan's
+// `owned`; plan_ensure allocates it on first use and replaces it where it is too small, plan_release gives it back), or of a stream
+// (stream_ensure, stream_release: the same rule, with the stream's owner).
+struct PlanBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  template <class T> T* as() const { return (T*)p; }
+};
+
 // The level of a stream — single, group or pool (piper_hip_voice_stream_set_level; include/piper_hip.h "Level control"): per generator row
 // a carry in device memory (the samples u a step could not finish yet and the last final G), the step's LvStepRow table, and the limited
-// samples of one step, lim [rows][row], which the output kernels then read in place of the window plan's audio.
+// samples of one step, lim [NBg][row], which the output kernels then read in place of the window plan's audio.
 struct StreamLevel {
   bool on = false;
   piper_hip_level lv{};       // as stream_level reports it: defaults resolved
   LvParams p{};
-  int rows = 0;               // generator rows the buffers below hold
-  int64_t row = 0;            // floats of a row of `lim`
-  float* carry = nullptr;     // device [rows][kLvCarry]
-  float* lim = nullptr;       // device [rows][row]
-  LvStepRow* desc = nullptr;  // device [rows]
+  int64_t row = 0;            // floats of a row of `lim` for the current stream: set once all three buffers hold it
+  PlanBuf carry;              // float [NBg][kLvCarry]
+  PlanBuf lim;                // float [NBg][row] (an earlier stream's larger buffer is kept, and laid out at this row)
+  PlanBuf desc;               // LvStepRow [NBg]
 };
 
 // The equaliser of a stream — single, group or pool (piper_hip_voice_stream_set_eq; include/piper_hip.h "Equaliser"): the design in device
@@ -286,61 +294,53 @@ struct StreamLevel {
 struct StreamEq {
   bool on = false;
   piper_hip_eq eq{};
-  int rows = 0;               // generator rows carry, scratch and desc hold
-  int blocks = 0;             // scratch blocks per row
-  EqDesign* dev = nullptr;    // device
-  double* carry = nullptr;    // device [rows][kEqCarry]
-  double* scratch = nullptr;  // device [rows][blocks][2·kEqMaxD]
-  EqStepRow* desc = nullptr;  // device [rows]
-  float* out = nullptr;       // device, out_bytes: the EQ'd chunks of one step
-  size_t out_bytes = 0;
+  int blocks = 0;             // scratch blocks per row for the current stream: set once carry, scratch and desc hold it
+  PlanBuf dev;                // EqDesign
+  PlanBuf carry;              // double [NBg][kEqCarry]
+  PlanBuf scratch;            // double [NBg][blocks][2·kEqMaxD]
+  PlanBuf desc;               // EqStepRow [NBg]
+  PlanBuf out;                // float: the EQ'd chunks of one step (sized by the first step that needs it)
 };
 
 // The output rate of a stream — single, group or pool (piper_hip_voice_stream_set_rate): 0 is the voice's own rate. A resampling stream
-// keeps, per generator row, the last kRsHist samples of the previous chunk in device memory, in two buffers that change roles every step
-// (one launch reads the old history and writes the new one), and uploads a descriptor of its own per step.
+// keeps, per generator row, the last kRsHist samples of the previous chunk in device memory, in two halves that change roles every step
+// (one launch reads the old history and writes the new one: rate_hist), and uploads a descriptor of its own per step.
 struct StreamRate {
   int rate = 0;
   bool started = false;       // a step has run (a pool: or a session has joined): the rate can no longer change
-  int parity = 0;             // which history buffer the next step reads
-  int rows = 0;               // generator rows the buffers below hold
-  float* hist = nullptr;      // device [2][rows][kRsHist]
-  RsStepRow* desc = nullptr;  // device [rows]
+  int parity = 0;             // which history half the next step reads
+  PlanBuf hist;               // float [2][NBg][kRsHist]
+  PlanBuf desc;               // RsStepRow [NBg]
   // Mixed formats (piper_hip_voice_stream_set_mixed): every row brings its own rate, encoding and gain (StreamRow::fmt); `rate` stays 0.
   // The history is the one above, used by the rows that have a filter; the step's descriptor is a MixStepRow table of its own.
   bool mixed = false;
-  int mix_rows = 0;             // generator rows `mdesc` holds
-  MixStepRow* mdesc = nullptr;  // device [mix_rows]
+  PlanBuf mdesc;              // MixStepRow [NBg]
 };
 
 // A stream in progress, whoever holds it: a plan (Slot::stream — a single stream or a group) or a streaming pool (StreamPool::st).
-// `rows` empty: no stream. The device buffers come from stream_alloc and belong to `plan`, or to the context pool for a streaming pool.
+// `rows` empty: no stream. The device buffers (each()) come from stream_ensure and belong to `plan`, or to the context pool for a
+// streaming pool. NBg never changes while a record holds buffers — a plan's batch is exact, a pool's capacity fixed at its open — so
+// a buffer with one entry per generator row is either empty or holds NBg of them.
 struct Slot;
 struct Stream {
   int chunk = 0, halo = 0, NBg = 1;  // frames; the generator's batch (1 for a single stream), fixed for the life of the stream
   bool single = false;               // stream_begin's: one row that stream_next steps, not a group of one
   std::vector<StreamRow> rows;       // one per item / pool row
-  int* d_desc = nullptr;             // device: [NBg][kDescInts] descriptor of a batched step (one upload per step)
-  void* pack = nullptr;              // device: the packed chunks of one batched step
-  size_t pack_bytes = 0;             // of `pack`
+  PlanBuf d_desc;                    // int [NBg][kDescInts] descriptor of a batched step (one upload per step)
+  PlanBuf pack;                      // the packed chunks of one batched step
   StreamRate rs;                     // output rate of the stream
   StreamLevel lv;                    // level of the stream
   StreamEq eq;                       // equaliser of the stream
   // Per-phoneme volume: the shaped chunks of one step in the layout of the window plan's audio, and the step's VolStepRow table; both
   // allocated by the first step that has a row with a volume
-  float* vol = nullptr;
-  size_t vol_bytes = 0;
-  VolStepRow* vol_desc = nullptr;    // device [NBg]
+  PlanBuf vol;                       // float
+  PlanBuf vol_desc;                  // VolStepRow [256]
   Slot* plan = nullptr;              // owner of the device buffers; nullptr = the context pool (a streaming pool)
   int items() const { return (int)rows.size(); }
-};
-
-// A device buffer of a plan's output chain (in the plan's `owned`) that knows its own size: plan_ensure allocates it on first use and
-// replaces it where it is too small, plan_release gives it back.
-struct PlanBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  template <class T> T* as() const { return (T*)p; }
+  std::array<PlanBuf*, 15> each() {
+    return {&vol, &vol_desc, &eq.dev, &eq.carry, &eq.scratch, &eq.desc, &eq.out, &d_desc, &pack, &rs.hist, &rs.desc, &rs.mdesc, &lv.carry, &lv.lim,
+            &lv.desc};
+  }
 };
 
 // Page-locked host memory of a slot id's staging (piper_hip_voice::Staging), the host twin of PlanBuf: the pointer and its capacity in
@@ -1047,8 +1047,10 @@ void slot_release(piper_hip_voice* v, Slot& s) {
   give_back_set(v, s);  // piper_hip_voice_destroy destroys the sets
 }
 
+void stream_release(piper_hip_voice* v, Stream& st, PlanBuf& b);
+
 // Closes the streaming pool of slot id `slot`, if it holds one: waits for the adopts still queued (they write the row stores), then gives
-// the row stores and tables back to the context pool.
+// the row stores, the stream's buffers and the tables back to the context pool.
 void pool_close(piper_hip_voice* v, int slot) {
   StreamPool* P = v->pools[slot].get();
   if (!P) return;
@@ -1058,16 +1060,8 @@ void pool_close(piper_hip_voice* v, int slot) {
     if (r.z) (void)v->ctx->pool.release(r.z);
   for (auto& r : P->ext)
     if (r.gf) (void)v->ctx->pool.release(r.gf);
-  if (P->st.vol) (void)v->ctx->pool.release(P->st.vol);
-  if (P->st.vol_desc) (void)v->ctx->pool.release(P->st.vol_desc);
+  for (PlanBuf* b : P->st.each()) stream_release(v, P->st, *b);
   if (P->d_rows) (void)v->ctx->pool.release(P->d_rows);
-  const StreamRate& rs = P->st.rs;
-  const StreamLevel& lv = P->st.lv;
-  const StreamEq& sq = P->st.eq;
-  for (void* p : {(void*)sq.dev, (void*)sq.carry, (void*)sq.scratch, (void*)sq.desc, (void*)sq.out})
-    if (p) (void)v->ctx->pool.release(p);
-  for (void* p : {(void*)P->st.d_desc, P->st.pack, (void*)rs.hist, (void*)rs.desc, (void*)rs.mdesc, (void*)lv.carry, (void*)lv.lim, (void*)lv.desc})
-    if (p) (void)v->ctx->pool.release(p);
   if (P->spk_rows) (void)v->ctx->pool.release(P->spk_rows);
   P->h_rep.release();  // (the adopts that write it have run: waited for above)
   v->pools[slot].reset();
@@ -4441,8 +4435,40 @@ LvStepRow level_range(const StreamRow& row, const Window& w, int hop, int64_t* l
   return LvStepRow{w.skip, w.n, (int)(s - *lo), (int)(*hi - *lo)};
 }
 
-int stream_alloc(piper_hip_voice* v, Stream& st, size_t bytes, void** out);
-void stream_free(piper_hip_voice* v, Stream& st, void* p, size_t bytes);
+// A device buffer of a stream, from its owner: the plan (counted in its arena_bytes, kept across streams, released with it) or, for a
+// streaming pool, the context pool (given back in pool_close). The one place that knows the difference.
+int stream_alloc(piper_hip_voice* v, Stream& st, size_t bytes, void** out) {
+  return st.plan ? plan_alloc(v, *st.plan, bytes, out) : v->ctx->pool.alloc(bytes, out);
+}
+
+void stream_free(piper_hip_voice* v, Stream& st, void* p, size_t bytes) {
+  if (st.plan) plan_free(v, *st.plan, p, bytes);
+  else (void)v->ctx->pool.release(p);
+}
+
+void stream_release(piper_hip_voice* v, Stream& st, PlanBuf& b) {
+  if (b.p) stream_free(v, st, b.p, b.bytes);
+  b = PlanBuf();
+}
+
+// `bytes` at least in buffer `b` of the stream, by plan_ensure's rule: nothing to do where it is large enough, otherwise the new one is
+// allocated and then the old one given back, so a failure leaves `b` as it was. Nothing on the GPU still reads the old one: every step
+// ends with a host wait, and the setters run before a stream's first step. The new buffer's contents are undefined; no stage relies on
+// them (DESIGN.md "Stream buffers").
+int stream_ensure(piper_hip_voice* v, Stream& st, PlanBuf& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return PIPER_HIP_OK;
+  void* q = nullptr;
+  if (int rc = stream_alloc(v, st, bytes, &q)) return rc;
+  stream_release(v, st, b);
+  b = PlanBuf{q, bytes};
+  return PIPER_HIP_OK;
+}
+
+// The window plan's audio in bytes, [NBg][n_samples]: what the volume and the EQ of a step each write a copy of
+size_t window_bytes(const Stream& st, const Slot& gs) { return (size_t)st.NBg * gs.n_samples * sizeof(float); }
+
+// The half of the resampling history a step reads (which = 0) and the one it writes (1); they change roles with rs.parity
+float* rate_hist(const Stream& st, int which) { return st.rs.hist.as<float>() + (size_t)(st.rs.parity ^ which) * st.NBg * kRsHist; }
 
 // ---- per-phoneme volume on streams (include/piper_hip.h "Per-phoneme volume")
 // A begin on a plan whose staging carried a volume: the gains per frame of its items, gf [NB][F], written on the plan's stream in front of
@@ -4465,22 +4491,11 @@ VolStepRow volume_range(const StreamRow& row, const Window& w, int hop) {
   return VolStepRow{row.gf, (int64_t)row.next * hop, row.F, w.skip, w.n, 0};
 }
 
-// What a step with a shaped row needs: st.vol of `bytes` (the window plan's audio), the device table and its page-locked staging.
-int volume_step_buffers(piper_hip_voice* v, int slot, Stream& st, size_t bytes) {
+// What a step with a shaped row needs: st.vol for the audio of the window plan gs, the device table and its page-locked staging.
+int volume_step_buffers(piper_hip_voice* v, int slot, Stream& st, const Slot& gs) {
   int rc;
-  void* p = nullptr;
-  if (st.vol_bytes < bytes) {  // (no step is in flight: every step ends with a wait)
-    if ((rc = stream_alloc(v, st, bytes, &p))) return rc;
-    stream_free(v, st, st.vol, st.vol_bytes);
-    st.vol = (float*)p;
-    st.vol_bytes = bytes;
-  }
-  if (!st.vol_desc) {
-    if ((rc = stream_alloc(v, st, (size_t)256 * sizeof(VolStepRow), &p))) return rc;
-    st.vol_desc = (VolStepRow*)p;
-  }
-  auto& sg = v->staging[slot];
-  return sg.h_vstep.ensure((size_t)256);
+  if ((rc = stream_ensure(v, st, st.vol, window_bytes(st, gs))) || (rc = stream_ensure(v, st, st.vol_desc, (size_t)256 * sizeof(VolStepRow)))) return rc;
+  return v->staging[slot].h_vstep.ensure((size_t)256);
 }
 
 // One launch behind the window plan's graph: the chunks of `rows` generator rows of audio [rows][row] under their envelopes → st.vol.
@@ -4492,27 +4507,19 @@ hipError_t volume_step(piper_hip_voice* v, int slot, Stream& st, const VolStepRo
     max_n = std::max<int64_t>(max_n, tab[r].n);
   }
   if (max_n < 1) return hipSuccess;
-  hipError_t e = hipMemcpyAsync(st.vol_desc, sg.h_vstep, (size_t)rows * sizeof(VolStepRow), hipMemcpyHostToDevice, q);
-  if (e == hipSuccess) e = launch_volume_step(q, rows, max_n, audio, row, st.vol_desc, v->hop, st.vol);
+  hipError_t e = hipMemcpyAsync(st.vol_desc.p, sg.h_vstep, (size_t)rows * sizeof(VolStepRow), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess) e = launch_volume_step(q, rows, max_n, audio, row, st.vol_desc.as<VolStepRow>(), v->hop, st.vol.as<float>());
   return e;
 }
 
 // One launch behind the volume step: the chunks of `rows` generator rows of audio [rows][row] through the stream's EQ → st.eq.out, at the
 // same places (include/piper_hip.h "Equaliser"). A row's chunk is the one the volume step reads: the window's, from sample next · hop.
-hipError_t eq_step(piper_hip_voice* v, int slot, Stream& st, const std::vector<EqStepRow>& tab, const float* audio, int64_t row, size_t bytes,
-                   hipStream_t q) {
+hipError_t eq_step(piper_hip_voice* v, int slot, Stream& st, const EqStepRow* tab, int rows, const Slot& gs, const float* audio, hipStream_t q) {
   StreamEq& sq = st.eq;
   auto& sg = v->staging[slot];
-  if (sq.out_bytes < bytes) {  // (no step is in flight: every step ends with a wait)
-    void* p = nullptr;
-    if (stream_alloc(v, st, bytes, &p)) return hipErrorOutOfMemory;
-    stream_free(v, st, sq.out, sq.out_bytes);
-    sq.out = (float*)p;
-    sq.out_bytes = bytes;
-  }
-  if (sg.h_estep.ensure((size_t)sq.rows, (size_t)256)) return hipErrorOutOfMemory;
-  const int rows = (int)tab.size();
-  if (rows > sq.rows) return hipErrorInvalidValue;
+  if (stream_ensure(v, st, sq.out, window_bytes(st, gs))) return hipErrorOutOfMemory;
+  if (sg.h_estep.ensure((size_t)st.NBg, (size_t)256)) return hipErrorOutOfMemory;
+  if (rows > st.NBg) return hipErrorInvalidValue;
   int max_n = 0;
   for (int r = 0; r < rows; r++) {
     sg.h_estep[r] = tab[r];
@@ -4520,8 +4527,41 @@ hipError_t eq_step(piper_hip_voice* v, int slot, Stream& st, const std::vector<E
   }
   if (max_n < 1) return hipSuccess;
   if (max_n > sq.blocks * kEqBlock) return hipErrorInvalidValue;
-  hipError_t e = hipMemcpyAsync(sq.desc, sg.h_estep, (size_t)rows * sizeof(EqStepRow), hipMemcpyHostToDevice, q);
-  if (e == hipSuccess) e = launch_eq_step(q, rows, sq.blocks * kEqBlock, audio, row, sq.desc, sq.dev, sq.eq.n, sq.carry, sq.scratch, sq.out);
+  hipError_t e = hipMemcpyAsync(sq.desc.p, sg.h_estep, (size_t)rows * sizeof(EqStepRow), hipMemcpyHostToDevice, q);
+  if (e == hipSuccess)
+    e = launch_eq_step(q, rows, sq.blocks * kEqBlock, audio, gs.n_samples, sq.desc.as<EqStepRow>(), sq.dev.as<EqDesign>(), sq.eq.n, sq.carry.as<double>(),
+                       sq.scratch.as<double>(), sq.out.as<float>());
+  return e;
+}
+
+// The stages of one step between the window plan's graph and the sink, in their order — volume (vol given: a delivering row has one),
+// EQ (the stream has one: eq given), level (the same: lv given, in page-locked staging) — over `rows` generator rows of the window plan
+// gs, whose tables have one entry per row; a single stream is the one-row case. Continues the step's error chain `e`: nothing more is
+// enqueued behind the first failure. Hands the sink what it reads: rows of *chunk_row floats at *chunk_audio, each row's chunk behind
+// its skip (a stream with a level: the limited range at the start of its row).
+hipError_t step_stages(piper_hip_voice* v, int slot, Stream& st, const Slot& gs, int rows, const VolStepRow* vol, const EqStepRow* eq,
+                       const LvStepRow* lv, hipError_t e, const float** chunk_audio, int64_t* chunk_row) {
+  const hipStream_t q = gs.set.stream;
+  const float* audio = gs.audio;  // every stage writes its rows at the places of the window plan's, so all share its row stride
+  if (vol) {
+    if (e == hipSuccess) e = volume_step(v, slot, st, vol, rows, audio, gs.n_samples, q);
+    audio = st.vol.as<float>();
+  }
+  if (eq) {
+    if (e == hipSuccess) e = eq_step(v, slot, st, eq, rows, gs, audio, q);
+    audio = st.eq.out.as<float>();
+  }
+  *chunk_audio = audio;
+  *chunk_row = gs.n_samples;
+  if (lv) {  // (with or without a buffer at the sink: the rows' carries move on with the stream)
+    StreamLevel& lvl = st.lv;
+    if (e == hipSuccess) e = hipMemcpyAsync(lvl.desc.p, lv, (size_t)rows * sizeof(LvStepRow), hipMemcpyHostToDevice, q);
+    if (e == hipSuccess)
+      e = launch_level_step(q, rows, st.chunk * v->hop, audio, gs.n_samples, lvl.desc.as<LvStepRow>(), lvl.carry.as<float>(), lvl.p,
+                            lvl.lim.as<float>(), lvl.row);
+    *chunk_audio = lvl.lim.as<float>();
+    *chunk_row = lvl.row;
+  }
   return e;
 }
 
@@ -4580,7 +4620,7 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   bool built = false;
   int rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fc), 1, &gs, &built);
   if (rc) return rc;
-  if (row.gf && (rc = volume_step_buffers(v, slot, s.stream, (size_t)gs->n_samples * sizeof(float)))) return rc;
+  if (row.gf && (rc = volume_step_buffers(v, slot, s.stream, *gs))) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
   v->windows[slot] = WindowRecord{gs, gs->last_use, {Fc}};
@@ -4594,35 +4634,27 @@ int stream_step(piper_hip_voice* v, int slot, const Sink& out, int64_t* n_sample
   if (e == hipSuccess && gs->spk_bias)  // the item's conv_pre row travels with its latent window
     e = hipMemcpyAsync(gs->spk_bias, s.spk_bias + v->spk_pre_off, (size_t)v->cfg.up_initial * sizeof(float), hipMemcpyDeviceToDevice, gs->set.stream);
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
-  const float* win_audio = gs->audio;  // the window's audio, or — the item has a volume — its chunk under the envelope, at the same place
-  if (row.gf) {
-    const VolStepRow vr = volume_range(row, w, v->hop);
-    if (e == hipSuccess) e = volume_step(v, slot, s.stream, &vr, 1, gs->audio, 0, gs->set.stream);
-    win_audio = s.stream.vol;
+  // the item's chunk under its envelope and through the EQ, at the window's own place, then the limited range
+  const VolStepRow vr = volume_range(row, w, v->hop);
+  const EqStepRow er{(int64_t)row.next * v->hop, w.skip, (int)w.n};
+  const float* chunk_audio = nullptr;  // what the output stage reads, its chunk behind dn_skip
+  int64_t chunk_row = 0;
+  LvStepRow* lstage = nullptr;
+  if (lvl.on) {  // (every step ends with a wait: the staged row of the previous one has been read)
+    lstage = (LvStepRow*)(v->staging[slot].h_desc + kLvStageOff);
+    *lstage = lrow;
   }
-  if (s.stream.eq.on) {  // (the EQ'd chunk at the same place: the later stages read it as they read the window's)
-    const std::vector<EqStepRow> er{EqStepRow{(int64_t)row.next * v->hop, w.skip, (int)w.n}};
-    if (e == hipSuccess) e = eq_step(v, slot, s.stream, er, win_audio, 0, (size_t)gs->n_samples * sizeof(float), gs->set.stream);
-    win_audio = s.stream.eq.out;
-  }
-  const float* chunk_audio = win_audio;  // what the output stage reads, its chunk behind dn_skip
-  if (lvl.on) {  // (with or without a buffer: the row's carry moves on with the stream)
-    LvStepRow* h = (LvStepRow*)(v->staging[slot].h_desc + kLvStageOff);
-    if (e == hipSuccess) { *h = lrow; e = hipMemcpyAsync(lvl.desc, h, sizeof(LvStepRow), hipMemcpyHostToDevice, gs->set.stream); }
-    if (e == hipSuccess)
-      e = launch_level_step(gs->set.stream, 1, s.stream.chunk * v->hop, win_audio, 0, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
-    chunk_audio = lvl.lim;
-  }
+  e = step_stages(v, slot, s.stream, *gs, 1, row.gf ? &vr : nullptr, s.stream.eq.on ? &er : nullptr, lstage, e, &chunk_audio, &chunk_row);
   if (pcm && want_out) {
     PcmRoute r;
     const size_t dev_samples = (size_t)std::max<int64_t>(std::max<int64_t>((int64_t)gs->F * v->hop, want), rd ? rs_step_bound(*rd, (int64_t)gs->F * v->hop) : 0);
     if (e == hipSuccess) rc = pcm_route(v, *gs, v->staging[slot], out.host, elem, (size_t)want, dev_samples, &r);
     if (rd) {  // (every step ends with a wait: the staged descriptor of the previous one has been read)
       RsStepRow* h = (RsStepRow*)(v->staging[slot].h_desc + kDescStageInts);
-      if (e == hipSuccess && !rc) { *h = rrow; e = hipMemcpyAsync(rs.desc, h, sizeof(RsStepRow), hipMemcpyHostToDevice, gs->set.stream); }
+      if (e == hipSuccess && !rc) { *h = rrow; e = hipMemcpyAsync(rs.desc.p, h, sizeof(RsStepRow), hipMemcpyHostToDevice, gs->set.stream); }
       if (e == hipSuccess && !rc)
-        e = launch_resample_step(gs->set.stream, 1, rrow.count, chunk_audio, 0, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, out.gain, r.kdst, law);
+        e = launch_resample_step(gs->set.stream, 1, rrow.count, chunk_audio, chunk_row, rs.desc.as<RsStepRow>(), rate_hist(s.stream, 0),
+                                 rate_hist(s.stream, 1), rf, out.gain, r.kdst, law);
     } else if (e == hipSuccess && !rc) {
       e = launch_pcm16_flat(gs->set.stream, chunk_audio + dn_skip, want, out.gain, r.kdst, law, v->ctx->num_cus);
     }
@@ -4755,29 +4787,10 @@ void plan_free(piper_hip_voice* v, Slot& s, void* p, size_t bytes) {
   (void)v->ctx->pool.release(p);
 }
 
-// A device buffer of a stream, from its owner: the plan (counted in its arena_bytes, kept across streams, released with it) or, for a
-// streaming pool, the context pool (given back in pool_close). The one place that knows the difference.
-int stream_alloc(piper_hip_voice* v, Stream& st, size_t bytes, void** out) {
-  return st.plan ? plan_alloc(v, *st.plan, bytes, out) : v->ctx->pool.alloc(bytes, out);
-}
-
-// Gives back a buffer that a larger one replaces. Every step ends with a host wait, so nothing on the GPU still reads it.
-void stream_free(piper_hip_voice* v, Stream& st, void* p, size_t bytes) {
-  if (!p) return;
-  if (st.plan) plan_free(v, *st.plan, p, bytes);
-  else (void)v->ctx->pool.release(p);
-}
-
 // A packed-output buffer of at least `bytes` for the batched stream (no step is in flight: every step ends with a wait).
 int pack_buffer(piper_hip_voice* v, Stream& st, size_t bytes) {
-  if (st.single || st.pack_bytes >= bytes) return PIPER_HIP_OK;  // (a single stream packs nothing: its chunk is the window's own audio)
-  bytes = round_up4((int64_t)bytes);
-  void* p = nullptr;
-  if (int rc = stream_alloc(v, st, bytes, &p)) return rc;
-  stream_free(v, st, st.pack, st.pack_bytes);
-  st.pack = p;
-  st.pack_bytes = bytes;
-  return PIPER_HIP_OK;
+  if (st.single || st.pack.bytes >= bytes) return PIPER_HIP_OK;  // (a single stream packs nothing: its chunk is the window's own audio)
+  return stream_ensure(v, st, st.pack, (size_t)round_up4((int64_t)bytes));
 }
 
 }  // namespace
@@ -4994,15 +5007,15 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
   if (want_out && out.cap < total)
     PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: buffer holds %lld < %lld %s", (long long)out.cap, (long long)total, mix ? "bytes" : "samples");
   const size_t total_bytes = (size_t)total * sample_bytes;  // what the pack kernel writes and the host receives
-  if (total_bytes > st.pack_bytes)
-    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, st.pack_bytes / sizeof(float));
+  if (total_bytes > st.pack.bytes)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_next_batch: %lld samples exceed the group's %zu", (long long)total, st.pack.bytes / sizeof(float));
   if (want_out && (rc = sg.h_audio.ensure(mix ? ((size_t)total + 3) / 4 : rd ? ((size_t)total + 1) / 2 : (size_t)total, kAudioMinCap))) return rc;
   // generator-only plan of the step's longest window at the stream's batch size (rows past their end have length 0): a pool and a group
   // of the same size use the same plans
   Slot* gs = nullptr;
   bool built = false;
   if ((rc = acquire_plan(v, PLAN_GENERATOR, 0, bucket_f(Fmax), NBg, &gs, &built))) return rc;
-  if (any_vol && (rc = volume_step_buffers(v, slot, st, (size_t)NBg * gs->n_samples * sizeof(float)))) return rc;
+  if (any_vol && (rc = volume_step_buffers(v, slot, st, *gs))) return rc;
   gs->in_use = true;
   gs->last_use = ++v->use_clock;
   {
@@ -5017,57 +5030,46 @@ int batched_step(piper_hip_voice* v, int slot, Stream& st, const StepSource& src
   hipError_t e = hipSuccess;
   for (size_t k = 0; k < src.n_wait; k++)
     if (e == hipSuccess) e = hipStreamWaitEvent(q, src.wait[k], 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(st.d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
+  int* const d_desc = st.d_desc.as<int>();
+  if (e == hipSuccess) e = hipMemcpyAsync(d_desc, d, (size_t)NBg * kDescInts * sizeof(int), hipMemcpyHostToDevice, q);
   if (e == hipSuccess) {
     const int gx = (int)std::min<int64_t>(ceil_div((int64_t)I * (Fg / 4), 256), 64);
-    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, src.z, src.Fz, src.d_rows, st.d_desc, gs->zin, gs->lensF, I, Fg, src.spk,
+    hipLaunchKernelGGL(stream_window_gather_kernel, dim3(gx, NBg), dim3(256), 0, q, src.z, src.Fz, src.d_rows, d_desc, gs->zin, gs->lensF, I, Fg, src.spk,
                        src.spk_stride, src.spk ? gs->spk_bias : nullptr, v->cfg.up_initial);
     e = hipGetLastError();
   }
   if (e == hipSuccess && launch_plan(v, *gs)) e = hipErrorUnknown;
-  const float* win_audio = gs->audio;  // the windows' audio, or — a delivering row has a volume — every row's chunk as it leaves the volume stage
-  if (any_vol) {
-    if (e == hipSuccess) e = volume_step(v, slot, st, vrow.data(), NBg, gs->audio, gs->n_samples, q);
-    win_audio = st.vol;
-  }
-  if (st.eq.on) {  // every delivering row's chunk through the EQ, at the same place; a row that delivers nothing has n = 0
-    std::vector<EqStepRow> er((size_t)NBg, EqStepRow{0, 0, 0});
-    for (int r = 0; r < n; r++)
-      if (rows[r].active) er[r] = EqStepRow{(int64_t)rows[r].next * hop, win[r].skip, (int)win[r].n};
-    if (e == hipSuccess) e = eq_step(v, slot, st, er, win_audio, gs->n_samples, (size_t)NBg * gs->n_samples * sizeof(float), q);
-    win_audio = st.eq.out;
-  }
-  const float* chunk_audio = win_audio;  // what the output stage reads: rows of chunk_row floats, each row's chunk behind its skip
-  int64_t chunk_row = gs->n_samples;
-  if (lvl.on) {
-    if (e == hipSuccess) e = hipMemcpyAsync(lvl.desc, lrow, (size_t)NBg * sizeof(LvStepRow), hipMemcpyHostToDevice, q);
-    if (e == hipSuccess) e = launch_level_step(q, NBg, st.chunk * hop, win_audio, gs->n_samples, lvl.desc, lvl.carry, lvl.p, lvl.lim, lvl.row);
-    chunk_audio = lvl.lim;
-    chunk_row = lvl.row;
-  }
+  // every delivering row's chunk through the stages, at the window's own place; a row that delivers nothing has n = 0 in every table
+  std::vector<EqStepRow> er;
+  if (st.eq.on) er.assign((size_t)NBg, EqStepRow{0, 0, 0});
+  for (int r = 0; r < n && st.eq.on; r++)
+    if (rows[r].active) er[r] = EqStepRow{(int64_t)rows[r].next * hop, win[r].skip, (int)win[r].n};
+  const float* chunk_audio = nullptr;  // what the output stage reads: rows of chunk_row floats, each row's chunk behind its skip
+  int64_t chunk_row = 0;
+  e = step_stages(v, slot, st, *gs, NBg, any_vol ? vrow.data() : nullptr, st.eq.on ? er.data() : nullptr, lvl.on ? lrow : nullptr, e, &chunk_audio,
+                  &chunk_row);
   if (e == hipSuccess) {
     const int px = (int)std::min<int64_t>(ceil_div((int64_t)st.chunk * hop, 1024), 64);
     if (mix) {
       int gx;
       size_t lds;
       mix_step_plan(mrow, NBg, px, &gx, &lds);
-      e = hipMemcpyAsync(rs.mdesc, mrow, (size_t)NBg * sizeof(MixStepRow), hipMemcpyHostToDevice, q);
+      e = hipMemcpyAsync(rs.mdesc.p, mrow, (size_t)NBg * sizeof(MixStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
-        e = launch_mixed_step(q, NBg, gx, lds, chunk_audio, chunk_row, rs.mdesc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                              rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, st.pack);
+        e = launch_mixed_step(q, NBg, gx, lds, chunk_audio, chunk_row, rs.mdesc.as<MixStepRow>(), rate_hist(st, 0), rate_hist(st, 1), st.pack.p);
     } else if (rd) {
-      e = hipMemcpyAsync(rs.desc, rrow, (size_t)NBg * sizeof(RsStepRow), hipMemcpyHostToDevice, q);
+      e = hipMemcpyAsync(rs.desc.p, rrow, (size_t)NBg * sizeof(RsStepRow), hipMemcpyHostToDevice, q);
       if (e == hipSuccess)
-        e = launch_resample_step(q, NBg, max_cnt, chunk_audio, chunk_row, rs.desc, rs.hist + (size_t)rs.parity * rs.rows * kRsHist,
-                                 rs.hist + (size_t)(rs.parity ^ 1) * rs.rows * kRsHist, rf, gain, st.pack, law);
+        e = launch_resample_step(q, NBg, max_cnt, chunk_audio, chunk_row, rs.desc.as<RsStepRow>(), rate_hist(st, 0), rate_hist(st, 1), rf, gain,
+                                 st.pack.p, law);
     } else if (pcm) {
-      e = launch_stream_chunk_pack_pcm16(q, px, NBg, chunk_audio, chunk_row, st.d_desc, gain, st.pack, law);
+      e = launch_stream_chunk_pack_pcm16(q, px, NBg, chunk_audio, chunk_row, d_desc, gain, st.pack.p, law);
     } else {
-      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, chunk_audio, chunk_row, st.d_desc, (float*)st.pack);
+      hipLaunchKernelGGL(stream_chunk_pack_kernel, dim3(px, NBg), dim3(256), 0, q, chunk_audio, chunk_row, d_desc, st.pack.as<float>());
       e = hipGetLastError();
     }
   }
-  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, st.pack, total_bytes, hipMemcpyDeviceToHost, q);
+  if (e == hipSuccess && want_out) e = hipMemcpyAsync(sg.h_audio, st.pack.p, total_bytes, hipMemcpyDeviceToHost, q);
   if (e == hipSuccess) e = stream_wait(q);
   gs->in_use = false;
   evict_idle_plans(v);
@@ -5151,11 +5153,7 @@ PH_EXPORT int piper_hip_voice_stream_begin_batch(piper_hip_voice* v, const piper
   Slot& s = *v->attached[slot];
   Stream& st = s.stream;  // (no stream is in progress: the prepare reset it; the buffers of an earlier one are still the plan's)
   st.plan = &s;
-  if (!st.d_desc) {
-    void* p = nullptr;
-    if ((rc = stream_alloc(v, st, (size_t)kMaxGroup * kDescInts * sizeof(int), &p))) return rc;
-    st.d_desc = (int*)p;
-  }
+  if ((rc = stream_ensure(v, st, st.d_desc, (size_t)kMaxGroup * kDescInts * sizeof(int)))) return rc;  // (room for any group: allocated once)
   if ((rc = pack_buffer(v, st, (size_t)n * chunk_frames * v->hop * sizeof(float)))) return rc;
   const float* gf = nullptr;  // the items' gains per frame [n][F] where the request carried a volume
   if ((rc = stream_volume_begin(v, s, &gf))) return rc;
@@ -5228,7 +5226,7 @@ PH_EXPORT int piper_hip_voice_stream_pool_open(piper_hip_voice* v, int slot, int
   void* p = nullptr;
   int rc = v->ctx->pool.alloc((size_t)st.NBg * sizeof(PoolRowRef) + (size_t)capacity * sizeof(PoolJoinEnt), &p);
   if (!rc) P->d_rows = (PoolRowRef*)p;
-  if (!rc) { rc = stream_alloc(v, st, (size_t)st.NBg * kDescInts * sizeof(int), &p); if (!rc) st.d_desc = (int*)p; }
+  if (!rc) rc = stream_ensure(v, st, st.d_desc, (size_t)st.NBg * kDescInts * sizeof(int));
   if (!rc) rc = pack_buffer(v, st, (size_t)capacity * chunk_frames * v->hop * sizeof(float));
   if (!rc && v->spk.S) {  // the rows' conv_pre biases; a row never taken reads as 0.0
     const size_t bytes = (size_t)capacity * v->cfg.up_initial * sizeof(float);
@@ -5664,7 +5662,19 @@ Stream* slot_stream_mixed(piper_hip_voice* v, int slot, const char* who) {
 }
 bool is_pool(const Stream& st) { return !st.plan; }
 int64_t chunk_samples(const piper_hip_voice* v, const Stream& st) { return (int64_t)st.chunk * v->hop; }
-int rate_buffers(piper_hip_voice* v, Stream& st);
+
+// What the setter `who` fixes for the whole stream is set before its first step (a pool's: before its first join); `tail` is what the
+// refusal says behind that.
+int refuse_started(const Stream& st, int slot, const char* who, const char* tail) {
+  if (!st.rs.started) return PIPER_HIP_OK;
+  PH_FAIL(PIPER_HIP_ERR_ARG, "%s: slot %d has %s%s", who, slot, is_pool(st) ? "stepped or been joined" : "stepped", tail);
+}
+
+// The two history halves and the RsStepRow table of the stream's generator rows
+int rate_buffers(piper_hip_voice* v, Stream& st) {
+  if (int rc = stream_ensure(v, st, st.rs.hist, (size_t)st.NBg * 2 * kRsHist * sizeof(float))) return rc;
+  return stream_ensure(v, st, st.rs.desc, (size_t)st.NBg * sizeof(RsStepRow));
+}
 }  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int32_t out_rate) {
@@ -5673,8 +5683,7 @@ PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int3
   Stream& st = *sp;
   StreamRate& rs = st.rs;
   if (rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d is mixed: every row has its own rate", slot);
-  if (rs.started)
-    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_rate: slot %d has %s: the rate is set before", slot, is_pool(st) ? "stepped or been joined" : "stepped");
+  if (int rc0 = refuse_started(st, slot, "stream_set_rate", ": the rate is set before")) return rc0;
   if (out_rate == v->cfg.sample_rate) {  // not a filter: the steps are the un-resampled ones
     rs.rate = 0;
     return PIPER_HIP_OK;
@@ -5691,26 +5700,6 @@ PH_EXPORT int piper_hip_voice_stream_set_rate(piper_hip_voice* v, int slot, int3
   rs.rate = out_rate;
   return PIPER_HIP_OK;
 }
-
-namespace {
-// The per-row history [2][rows][kRsHist] and the RsStepRow table of the stream's generator rows (kept when they are large enough already).
-int rate_buffers(piper_hip_voice* v, Stream& st) {
-  StreamRate& rs = st.rs;
-  if (rs.rows >= st.NBg) return PIPER_HIP_OK;
-  const size_t hist_row = (size_t)2 * kRsHist * sizeof(float);
-  stream_free(v, st, rs.hist, rs.rows * hist_row);
-  stream_free(v, st, rs.desc, rs.rows * sizeof(RsStepRow));
-  rs.hist = nullptr; rs.desc = nullptr; rs.rows = 0;
-  void *h = nullptr, *d = nullptr;
-  int rc;
-  if ((rc = stream_alloc(v, st, st.NBg * hist_row, &h))) return rc;
-  if ((rc = stream_alloc(v, st, st.NBg * sizeof(RsStepRow), &d))) { stream_free(v, st, h, st.NBg * hist_row); return rc; }
-  rs.hist = (float*)h;
-  rs.desc = (RsStepRow*)d;
-  rs.rows = st.NBg;
-  return PIPER_HIP_OK;
-}
-}  // namespace
 
 PH_EXPORT int piper_hip_voice_stream_rate(piper_hip_voice* v, int slot) {
   const Stream* st = slot_stream(v, slot, "stream_rate");
@@ -5859,34 +5848,21 @@ PH_EXPORT int piper_hip_voice_stream_set_level(piper_hip_voice* v, int slot, con
   Stream& st = *sp;
   StreamLevel& lv = st.lv;
   if (!level) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_level: null level");
-  if (st.rs.started)
-    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_level: slot %d has %s: the level is set before", slot, is_pool(st) ? "stepped or been joined" : "stepped");
-  LvParams p;
-  int rc = lv_resolve(level, v->cfg.sample_rate, &p);
+  int rc = refuse_started(st, slot, "stream_set_level", ": the level is set before");
   if (rc) return rc;
+  LvParams p;
+  if ((rc = lv_resolve(level, v->cfg.sample_rate, &p))) return rc;
   const int64_t chunk = chunk_samples(v, st);
   if (chunk < 512)
     PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_level: chunk_frames · hop = %lld < 512 (a step before the last must deliver samples)", (long long)chunk);
   if (chunk > 0x3fffffff || !lv_step_lds(chunk)) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_set_level: %lld samples per step too many", (long long)chunk);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  // the carry, the descriptor and the limited samples of one step for the stream's generator rows (kept when they are large enough)
+  // the carry, the limited samples of one step and the descriptor for the stream's generator rows
   const int64_t row = (lv_step_bound(chunk) + 1 + 3) & ~(int64_t)3;
-  if (lv.rows < st.NBg || lv.row < row) {
-    stream_free(v, st, lv.carry, (size_t)lv.rows * kLvCarry * sizeof(float));
-    stream_free(v, st, lv.lim, (size_t)lv.rows * lv.row * sizeof(float));
-    stream_free(v, st, lv.desc, (size_t)lv.rows * sizeof(LvStepRow));
-    lv.carry = lv.lim = nullptr; lv.desc = nullptr; lv.rows = 0; lv.row = 0;
-    void *c = nullptr, *l = nullptr, *d = nullptr;
-    if ((rc = stream_alloc(v, st, (size_t)st.NBg * kLvCarry * sizeof(float), &c))) return rc;
-    if ((rc = stream_alloc(v, st, (size_t)st.NBg * row * sizeof(float), &l))) { stream_free(v, st, c, (size_t)st.NBg * kLvCarry * sizeof(float)); return rc; }
-    if ((rc = stream_alloc(v, st, (size_t)st.NBg * sizeof(LvStepRow), &d))) {
-      stream_free(v, st, c, (size_t)st.NBg * kLvCarry * sizeof(float));
-      stream_free(v, st, l, (size_t)st.NBg * row * sizeof(float));
-      return rc;
-    }
-    lv.carry = (float*)c; lv.lim = (float*)l; lv.desc = (LvStepRow*)d;
-    lv.rows = st.NBg; lv.row = row;
-  }
+  if ((rc = stream_ensure(v, st, lv.carry, (size_t)st.NBg * kLvCarry * sizeof(float))) ||
+      (rc = stream_ensure(v, st, lv.lim, (size_t)st.NBg * row * sizeof(float))) || (rc = stream_ensure(v, st, lv.desc, (size_t)st.NBg * sizeof(LvStepRow))))
+    return rc;
+  lv.row = row;
   const bool was = lv.on;
   lv.on = true;
   if ((rc = pack_resize(v, st))) { lv.on = was; return rc; }
@@ -5912,44 +5888,24 @@ PH_EXPORT int piper_hip_voice_stream_set_eq(piper_hip_voice* v, int slot, const 
   Stream& st = *sp;
   StreamEq& sq = st.eq;
   if (!eq) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_eq: null eq");
-  if (st.rs.started)
-    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_eq: slot %d has %s: the EQ is set before", slot, is_pool(st) ? "stepped or been joined" : "stepped");
-  int rc = piper_hip_eq_check(eq, v->cfg.sample_rate);
-  if (rc) return rc;
+  int rc = refuse_started(st, slot, "stream_set_eq", ": the EQ is set before");
+  if (rc || (rc = piper_hip_eq_check(eq, v->cfg.sample_rate))) return rc;
   if (v->hop % kEqBlock != 0)
     PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "stream_set_eq: hop %d is not a multiple of %d: a step's chunk would not start on a block", v->hop, kEqBlock);
   const int64_t chunk = chunk_samples(v, st);
   if (chunk < 1 || chunk > 0x3fffffff) PH_FAIL(PIPER_HIP_ERR_SHAPE, "stream_set_eq: %lld samples per step", (long long)chunk);
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   const int blocks = (int)ceil_div(chunk, kEqBlock);
-  if (!sq.dev) {
-    void* p = nullptr;
-    if ((rc = stream_alloc(v, st, sizeof(EqDesign), &p))) return rc;
-    sq.dev = (EqDesign*)p;
-  }
-  if (sq.rows < st.NBg || sq.blocks < blocks) {  // the carry, the scratch and the descriptor of the stream's generator rows
-    stream_free(v, st, sq.carry, (size_t)sq.rows * kEqCarry * sizeof(double));
-    stream_free(v, st, sq.scratch, (size_t)sq.rows * sq.blocks * 2 * kEqMaxD * sizeof(double));
-    stream_free(v, st, sq.desc, (size_t)sq.rows * sizeof(EqStepRow));
-    sq.carry = sq.scratch = nullptr; sq.desc = nullptr; sq.rows = 0; sq.blocks = 0;
-    void *c = nullptr, *w = nullptr, *d = nullptr;
-    if ((rc = stream_alloc(v, st, (size_t)st.NBg * kEqCarry * sizeof(double), &c))) return rc;
-    if ((rc = stream_alloc(v, st, (size_t)st.NBg * blocks * 2 * kEqMaxD * sizeof(double), &w))) {
-      stream_free(v, st, c, (size_t)st.NBg * kEqCarry * sizeof(double));
-      return rc;
-    }
-    if ((rc = stream_alloc(v, st, (size_t)st.NBg * sizeof(EqStepRow), &d))) {
-      stream_free(v, st, c, (size_t)st.NBg * kEqCarry * sizeof(double));
-      stream_free(v, st, w, (size_t)st.NBg * blocks * 2 * kEqMaxD * sizeof(double));
-      return rc;
-    }
-    sq.carry = (double*)c; sq.scratch = (double*)w; sq.desc = (EqStepRow*)d;
-    sq.rows = st.NBg; sq.blocks = blocks;
-  }
+  // the design, and the carry, the scratch and the descriptor of the stream's generator rows
+  if ((rc = stream_ensure(v, st, sq.dev, sizeof(EqDesign))) || (rc = stream_ensure(v, st, sq.carry, (size_t)st.NBg * kEqCarry * sizeof(double))) ||
+      (rc = stream_ensure(v, st, sq.scratch, (size_t)st.NBg * blocks * 2 * kEqMaxD * sizeof(double))) ||
+      (rc = stream_ensure(v, st, sq.desc, (size_t)st.NBg * sizeof(EqStepRow))))
+    return rc;
+  sq.blocks = blocks;
   // the design, built and uploaded here, never inside a step (a blocking copy: no step of this stream has run)
   std::vector<EqDesign> hold(1);
   if ((rc = eq_build(eq, v->cfg.sample_rate, hold.data()))) return rc;
-  PH_HIP(hipMemcpy(sq.dev, hold.data(), sizeof(EqDesign), hipMemcpyHostToDevice), PIPER_HIP_ERR_LAUNCH);
+  PH_HIP(hipMemcpy(sq.dev.p, hold.data(), sizeof(EqDesign), hipMemcpyHostToDevice), PIPER_HIP_ERR_LAUNCH);
   sq.eq = piper_hip_eq{};
   sq.eq.n = eq->n;
   for (int i = 0; i < eq->n; i++) sq.eq.section[i] = eq->section[i];
@@ -5976,19 +5932,10 @@ PH_EXPORT int piper_hip_voice_stream_set_mixed(piper_hip_voice* v, int slot) {
   if (st.single) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d holds a single stream (stream_set_rate and a law per step serve it)", slot);
   if (rs.mixed) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d is mixed already", slot);
   if (rs.rate) PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has the output rate %d set", slot, rs.rate);
-  if (rs.started)
-    PH_FAIL(PIPER_HIP_ERR_ARG, "stream_set_mixed: slot %d has %s", slot, is_pool(st) ? "stepped or been joined" : "stepped");
+  int rc = refuse_started(st, slot, "stream_set_mixed", "");
+  if (rc) return rc;
   PH_HIP(hipSetDevice(v->ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
-  int rc;
-  if ((rc = rate_buffers(v, st))) return rc;
-  if (rs.mix_rows < st.NBg) {
-    stream_free(v, st, rs.mdesc, (size_t)rs.mix_rows * sizeof(MixStepRow));
-    rs.mdesc = nullptr; rs.mix_rows = 0;
-    void* p = nullptr;
-    if ((rc = stream_alloc(v, st, (size_t)st.NBg * sizeof(MixStepRow), &p))) return rc;
-    rs.mdesc = (MixStepRow*)p;
-    rs.mix_rows = st.NBg;
-  }
+  if ((rc = rate_buffers(v, st)) || (rc = stream_ensure(v, st, rs.mdesc, (size_t)st.NBg * sizeof(MixStepRow)))) return rc;
   for (StreamRow& row : st.rows) row.fmt = RowFormat();  // (s16 at the voice's rate: the buffer of the begin / open holds it)
   rs.parity = 0;
   rs.mixed = true;
