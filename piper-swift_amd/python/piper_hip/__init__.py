@@ -888,10 +888,11 @@ class HipBackend:
                                                       commandBuffer))
         return self._out(p, shape)
 
-    def unaryF32(self, op, input, count, alpha=0.0, commandBuffer=None):
-        p = c_vp()
+    def unaryF32(self, op, input, count, alpha=0.0, commandBuffer=None, out=None):
+        """`out`: a device address of `count` floats to write to (the ABI's caller-provided *out; 4-byte alignment suffices), returned as it is."""
+        p = c_vp(_ptr(out)) if out is not None else c_vp()
         _check(self.lib.piper_hip_unary_f32(self.ctx, op, _ptr(input), count, alpha, C.byref(p), commandBuffer))
-        return DeviceBuffer(self, p.value, count)
+        return DeviceBuffer(self, p.value, count, owned=out is None)
 
     def reluF32(self, input, count, commandBuffer=None):
         return self.unaryF32(RELU, input, count, 0.0, commandBuffer)
@@ -905,13 +906,16 @@ class HipBackend:
     def sigmoidF32(self, input, count, commandBuffer=None):
         return self.unaryF32(SIGMOID, input, count, 0.0, commandBuffer)
 
-    def binaryBroadcastF32(self, op, a, aShape, b, bShape, commandBuffer=None):
+    def binaryBroadcastF32(self, op, a, aShape, b, bShape, commandBuffer=None, out=None):
+        """`out`: a device address holding the broadcast shape's floats to write to (4-byte alignment suffices), returned as it is."""
         r = max(len(aShape), len(bShape))
-        p, osh, orank = c_vp(), (C.c_int64 * max(r, 1))(), C.c_int()
+        p, osh, orank = c_vp(_ptr(out)) if out is not None else c_vp(), (C.c_int64 * max(r, 1))(), C.c_int()
         _check(self.lib.piper_hip_binary_broadcast_f32(self.ctx, op, _ptr(a), _i64(aShape), len(aShape), _ptr(b),
                                                        _i64(bShape), len(bShape), C.byref(p), osh, C.byref(orank),
                                                        commandBuffer))
-        return self._out(p, list(osh)[:orank.value])
+        buf, shp = self._out(p, list(osh)[:orank.value])
+        buf.owned = out is None
+        return buf, shp
 
     def addF32(self, a, aShape, b, bShape, commandBuffer=None):
         return self.binaryBroadcastF32(ADD, a, aShape, b, bShape, commandBuffer)

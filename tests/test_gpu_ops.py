@@ -116,7 +116,8 @@ def test_unary(backend, golden_ops):
         assert np.array_equal(backend.downloadFloat32(backend.unaryF32(op, xd, x.size)), orc.unary(op, x))
     xs = np.abs(x)
     assert_close(backend.downloadFloat32(backend.unaryF32(ph.SQRT, up(backend, xs), x.size)), orc.unary(ph.SQRT, xs), 1e-6)
-    # odd length + misaligned view exercise the scalar tail
+    # an odd length on the aligned buffer: the float4 body and its one-element scalar tail (pointers off 16-byte alignment, which take the
+    # scalar loop instead, are in tests/test_gpu_ops_edges.py)
     y = backend.downloadFloat32(backend.unaryF32(ph.TANH, xd, 4097))
     assert_close(y, orc.unary(ph.TANH, x[:4097]), 2e-6)
 
