@@ -163,6 +163,19 @@ int piper_hip_convtranspose1d_bf16(piper_hip_ctx* ctx, const float* input, const
                                    const float* weight, const int64_t weight_shape[3], const float* bias,
                                    const piper_hip_convtranspose1d_params* p, float** out, int64_t out_shape[3],
                                    piper_hip_stream stream);
+/* Split-bf16 variants: the same shapes, parameter structs, refusals and covered geometry as the _bf16 pair, fp32 tensors in and out,
+ * with the arithmetic of PIPER_HIP_PRECISION_BF16X3 (below): both operands are split into hi + lo bf16 parts on the device and the
+ * contraction is three bf16 MFMA terms in one fp32 accumulator. Also UNSUPPORTED when both bf16 planes of the smallest tile's input
+ * window, 2 · (C_in / 8) · (32·(4 / WM) + reach) · 16 bytes, exceed the 160 KB of LDS (WM = 4, 2 or 1 waves along the rows: the
+ * largest of them that divides the number of 32-row tiles, convT: of C_out / 32; reach = (K − 1) · dilation, convT:
+ * ⌊(stride − 1 + pad) / stride⌋ + K / stride − 1). */
+int piper_hip_conv1d_bf16x3(piper_hip_ctx* ctx, const float* input, const int64_t input_shape[3], const float* weight,
+                            const int64_t weight_shape[3], const float* bias, const piper_hip_conv1d_params* p, float** out,
+                            int64_t out_shape[3], piper_hip_stream stream);
+int piper_hip_convtranspose1d_bf16x3(piper_hip_ctx* ctx, const float* input, const int64_t input_shape[3],
+                                     const float* weight, const int64_t weight_shape[3], const float* bias,
+                                     const piper_hip_convtranspose1d_params* p, float** out, int64_t out_shape[3],
+                                     piper_hip_stream stream);
 
 /* MetalBackend.matmulF32 (MetalBackend.swift:1232-1323) → matmul_f32 (matmul.metal:22-49), with the
  * executor's rank-4 lead-dim broadcast (GraphExecutor.swift:1870-1899) done by stride-0 addressing
@@ -342,9 +355,20 @@ void piper_hip_voice_destroy(piper_hip_voice* v);
  * configuration. BF16: every generator Conv / ConvTranspose takes bf16 operands (weights, and
  * the LeakyReLU'd activations written by the producing conv) with fp32 accumulation; bias, residual stream, MRF mean,
  * conv_post, the text encoder and the flow stay fp32. Stated tolerance: waveform SNR ≥ 35 dB against the fp32 result.
- * Drops every prepared slot (prepare again). UNSUPPORTED when a generator conv is outside the bf16 kernels' geometry. */
+ * BF16X3 (split bf16), the arithmetic as a contract: every operand a of a generator Conv / ConvTranspose (weight, LeakyReLU'd activation)
+ * is carried as a_hi = bf16(a) and a_lo = bf16(a − a_hi), nearest even, the residual a − a_hi being exact in fp32; the contraction is
+ *   W_lo·X_hi + W_hi·X_lo + W_hi·X_hi
+ * as three bf16 MFMA terms into one fp32 accumulator (every product is exact in fp32; the lo·lo term, ≤ 2⁻¹⁶ relative, is dropped).
+ * Everything BF16 keeps in fp32 stays fp32: bias, residual stream, MRF mean, conv_post, the text encoder and the flow. A-priori bound
+ * per conv output: |error| ≤ 3·2⁻¹⁶·Σ|w||x| plus fp32 accumulation of the 3·C_in·K terms (BF16: 2·2⁻⁸·Σ|w||x|). ResBlock1 pairs run as
+ * two launches (no fused pair kernel). Speed: profiles/bf16x3.md gives launch → collect against F32 and BF16 per voice and factor,
+ * including the geometries where BF16X3 is not faster than F32.
+ * Drops every prepared slot (prepare again); the fragment images of a precision are packed the first time it is selected and kept, so
+ * switching back costs no packing. UNSUPPORTED when a generator conv is outside the bf16 kernels' geometry (BF16X3: the same geometry,
+ * and also when both planes of a conv's smallest input window do not fit LDS, see piper_hip_conv1d_bf16x3). */
 #define PIPER_HIP_PRECISION_F32 0
 #define PIPER_HIP_PRECISION_BF16 1
+#define PIPER_HIP_PRECISION_BF16X3 2
 int piper_hip_voice_set_precision(piper_hip_voice* v, int precision);
 int piper_hip_voice_precision(const piper_hip_voice* v);
 
@@ -1312,13 +1336,13 @@ int piper_hip_voice_prosody_report(const piper_hip_voice* v, int slot, int64_t* 
  * predictor is available through piper_hip_voice_predict_durations.
  * Generator taps (fp32 tensors [C_u, F · up_rates[0..u]] of stage u; a name exists only where the slot's schedule keeps that tensor
  * until the plan has run, any other name is PIPER_HIP_ERR_ARG):
- *   "dec.s{u}.up"            the stage's ConvTranspose output (every schedule, fp32 and bf16);
+ *   "dec.s{u}.up"            the stage's ConvTranspose output (every schedule, fp32 and bf16; "bf16" in this list includes BF16X3);
  *   "dec.s{u}.rb{j}.c{d}"    ResBlock j after dilation step d. bf16 and the fp32 per-conv schedule: the last three steps, except the
  *                            closing step of the last ResBlock where the MRF mean is folded into its epilogue. fp32 merged schedule:
  *                            the last two steps (ping-pong buffers); a step fused inside a pair launch has no tensor, so a ResBlock2
  *                            stage that runs as one pair launch keeps "c1" only;
  *   "dec.s{u}.mean_lrelu"    fp32 per-conv schedule: lrelu(MRF mean) as the next stage reads it (slope 0.1; last stage 0.01);
- *   "dec.s{u}.mean_act"      bf16, u < n_ups − 1: the bf16 image of lrelu(MRF mean, 0.1) as raw bits, [C_u / 8][len][8] bf16 words
+ *   "dec.s{u}.mean_act"      bf16 only (not registered under BF16X3, whose image is two planes), u < n_ups − 1: the bf16 image of lrelu(MRF mean, 0.1) as raw bits, [C_u / 8][len][8] bf16 words
  *                            (4 floats per position and channel group);
  *   "dec.mean"               bf16: the last stage's fp32 MRF mean;
  *   "audio"                  the waveform rows [1][F·hop] of the plan (every plan kind), items at F_b·hop samples.

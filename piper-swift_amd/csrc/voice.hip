@@ -23,7 +23,7 @@
 
 #include "../../include/piper_hip_voice_layout.h"
 #include "conv.h"
-#include "conv_bf16.h"
+#include "conv_bf16x3.h"
 #include "conv_win.h"
 #include "eq.h"
 #include "join.h"
@@ -626,6 +626,11 @@ struct piper_hip_voice {
   ConvWB conv_pre_b;
   std::vector<ConvWB> up_b;                             // [stage]
   std::vector<std::vector<std::vector<ConvWB>>> rb_b;   // [stage][rb][conv]
+  // split-bf16 generator (PIPER_HIP_PRECISION_BF16X3): planar hi/lo fragment images (conv_bf16x3.h) of the same convs, kept beside the
+  // bf16 ones so that switching among the three precisions never repacks
+  ConvWB conv_pre_x;
+  std::vector<ConvWB> up_x;
+  std::vector<std::vector<std::vector<ConvWB>>> rb_x;
   std::vector<void*> owned;
   // Plans are cached voice-wide, least-recently-used first out; a user slot id is a handle on one of them. A TTS server sees
   // a new (T, F) almost every call: with buckets the plan for it usually exists already (prepare = input upload only).
@@ -1089,10 +1094,11 @@ struct Arena {
 
 double conv_bytes(int Cin, int Cout, int K, int64_t L) { return 4.0 * ((double)Cin * L + (double)Cout * L + (double)Cout * Cin * K + Cout); }
 
-// what a bf16 conv moves: the bf16 input image and weights, the bf16 output image, the fp32 result / residual / MRF operands
-double conv_bf16_bytes(const ConvBf16Args& a) {
-  const double cols = (double)a.N * a.Lout, out_cols = a.ct_stride > 0 ? cols * a.ct_stride : cols;
-  return 2.0 * (a.Cin * cols + (double)a.Cout * a.Cin * a.K) + (a.act ? 2.0 : 0.0) * a.Cout * out_cols +
+// what a bf16 conv moves: the bf16 input image and weights, the bf16 output image (split: two planes of each), the fp32 result /
+// residual / MRF operands
+double conv_bf16_bytes(const ConvBf16Args& a, bool split) {
+  const double cols = (double)a.N * a.Lout, out_cols = a.ct_stride > 0 ? cols * a.ct_stride : cols, el = split ? 4.0 : 2.0;
+  return el * (a.Cin * cols + (double)a.Cout * a.Cin * a.K) + (a.act ? el : 0.0) * a.Cout * out_cols +
          ((a.y ? 4.0 : 0.0) + (a.res ? 4.0 : 0.0) + (a.mrf_a ? 8.0 : 0.0)) * a.Cout * out_cols;
 }
 
@@ -1164,12 +1170,18 @@ struct Builder {
          [ctx, a, mfma](hipStream_t q) { return mfma ? launch_conv_mfma(ctx, q, a) : launch_conv_direct(ctx, q, a); });
   }
 
+  // the bf16 step constructors below serve both bf16 precisions: split ⇒ planar hi/lo images and the conv_bf16x3 launchers
+  bool split() const { return v->precision == PIPER_HIP_PRECISION_BF16X3; }
+
   // conv step over a bf16 fragment image
   void conv_bf16(const std::string& name, const piper_hip_voice::ConvWB& w, ConvBf16Args a, double flops) {
     a.w = w.w; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
     if (!a.bias) a.bias = w.bias;  // (conv_pre of a voice with speakers comes with its items' effective biases)
     piper_hip_ctx* ctx = v->ctx;
-    step(name, "conv_bf16", flops, conv_bf16_bytes(a), [ctx, a](hipStream_t q) { return launch_conv_bf16(ctx, q, a); });
+    if (split())
+      step(name, "conv_bf16x3", flops, conv_bf16_bytes(a, true), [ctx, a](hipStream_t q) { return launch_conv_bf16x3(ctx, q, a); });
+    else
+      step(name, "conv_bf16", flops, conv_bf16_bytes(a, false), [ctx, a](hipStream_t q) { return launch_conv_bf16(ctx, q, a); });
   }
 
   // several same-shape bf16 convs (the stage's ResBlocks) as one launch
@@ -1180,10 +1192,13 @@ struct Builder {
       ConvBf16Args& a = pk.a[i] = args[i];
       const auto& w = *ws[i];
       a.w = w.w; a.bias = w.bias; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
-      bytes += conv_bf16_bytes(a);
+      bytes += conv_bf16_bytes(a, split());
     }
     piper_hip_ctx* ctx = v->ctx;
-    step(name, "conv_bf16", flops, bytes, [ctx, pk, count](hipStream_t q) { return launch_conv_bf16_multi(ctx, q, pk.a, count); });
+    if (split())
+      step(name, "conv_bf16x3", flops, bytes, [ctx, pk, count](hipStream_t q) { return launch_conv_bf16x3_multi(ctx, q, pk.a, count); });
+    else
+      step(name, "conv_bf16", flops, bytes, [ctx, pk, count](hipStream_t q) { return launch_conv_bf16_multi(ctx, q, pk.a, count); });
   }
 };
 
@@ -1315,6 +1330,9 @@ ConvBf16Args rb_args_bf16(const Builder& b, const uint16_t* in, int K, int dil, 
 // what changes is the data each conv READS: the C8 bf16 image of LeakyReLU(x) written by its producer's epilogue
 // (conv_bf16.h). The residual stream, the bias adds and the MRF mean stay fp32, so rounding enters only through the
 // operands of each contraction and does not accumulate along the residual chain.
+// PIPER_HIP_PRECISION_BF16X3 (split mode) is the same schedule — step names, lanes, fork / join, merged versus per-conv — on planar hi/lo
+// images and the conv_bf16x3 launchers. It has no fused ResBlock1 pair (two doubled windows and the intermediate exceed LDS at 128
+// channels): pairs take the two-launch path, the one PIPER_HIP_NO_RB_PAIR selects for bf16.
 int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   piper_hip_voice* v = b.v;
   Slot& s = b.s;
@@ -1327,12 +1345,16 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   hipStream_t zs = s.set.stream;
   static const bool no_par = getenv("PIPER_HIP_BF16_SERIAL_RB") != nullptr;
   const bool no_merge = no_merged_rb();
+  const bool split = b.split();
+  const piper_hip_voice::ConvWB& conv_pre_w = split ? v->conv_pre_x : v->conv_pre_b;
+  const auto& up_w = split ? v->up_x : v->up_b;
+  const auto& rb_w = split ? v->rb_x : v->rb_b;
   // short utterances / small batches: the three ResBlocks advance in one launch; otherwise one launch per conv, as parallel
   // graph branches for the 18-conv ResBlock1 stages (+10 %; the 6-conv ResBlock2 stages do not gain)
   const bool merged = !no_merge && c.n_rb == 3 && (int64_t)NB * F <= 1536;
   s.parallel = !merged && !no_par && c.resblock_type == 1;
   auto image = [&](int C, int L) -> uint16_t* {  // zeroed once per build: kernels write the interior only
-    const size_t bytes = (size_t)c8_elems(NB, C, L) * 2;
+    const size_t bytes = (size_t)(split ? c8x2_elems(NB, C, L) : c8_elems(NB, C, L)) * 2;  // split: the hi plane, then the lo plane
     void* p = ar.raw(bytes);
     if (p && hipMemsetAsync(p, 0, bytes, zs) != hipSuccess) ar.rc = PIPER_HIP_ERR_LAUNCH;
     return (uint16_t*)p;
@@ -1342,7 +1364,9 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   if (ar.rc) return ar.rc;
   {
     const int* lf = b.lensF;
-    b.step("dec.z_to_bf16", "", 0, 0, [=](hipStream_t q) { return pack_act_c8(q, z, NB, I, F, 1.0f, zc8, 0, lf); });
+    b.step("dec.z_to_bf16", "", 0, 0, [=](hipStream_t q) {
+      return split ? pack_act_c8x2(q, z, NB, I, F, 1.0f, zc8, 0, lf) : pack_act_c8(q, z, NB, I, F, 1.0f, zc8, 0, lf);
+    });
   }
   {
     ConvBf16Args a;
@@ -1350,7 +1374,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
     a.N = NB; a.dil = 1; a.padL = 3; a.Lout = F; a.x_row = (int)c8_row_len(F); a.act_row = (int)c8_row_len(F); a.y_len = F;
     a.len_ptr = b.lensF; a.len_mul = 1;
     b.speaker_bias(a, s.kind == PLAN_GENERATOR ? -1 : v->spk_pre_off);  // x = dec.conv_pre(z) + dec.cond(g), the bias stays fp32
-    b.conv_bf16("dec.conv_pre", v->conv_pre_b, a, NB * conv_flops(c.up_initial, I, 7, F));
+    b.conv_bf16("dec.conv_pre", conv_pre_w, a, NB * conv_flops(c.up_initial, I, 7, F));
   }
   b.tap("dec_pre", dec0, c.up_initial, F, 1);
   int L = F;
@@ -1391,14 +1415,14 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
     tap_f32(p + "up", up);
     if (last_stage) tap_f32("dec.mean", m);
     // the bf16 image of lrelu(MRF mean) that the next stage reads, as raw bits: row cb holds positions × 8 channels × bf16 = 4 floats per position
-    if (a_next) b.tap(p + "mean_act", (const float*)a_next + kC8Halo * 4, S.Cout / 8, row * 4, Lo / F * 4);
+    if (a_next && !split) b.tap(p + "mean_act", (const float*)a_next + kC8Halo * 4, S.Cout / 8, row * 4, Lo / F * 4);
     {
       ConvBf16Args a;
       a.x = a_in; a.y = up; a.act = a_up; a.act_alpha = 0.1f;
       a.N = NB; a.Lout = L; a.x_row = (int)c8_row_len(L); a.act_row = row; a.y_len = Lo;
       a.ct_stride = S.stride; a.ct_pad = S.pad;
       a.len_ptr = b.lensF; a.len_mul = Lo / F;
-      b.conv_bf16(p + "lrelu_convT", v->up_b[u], a, NB * 2.0 * S.Cin * S.Cout * (double)S.K * L);
+      b.conv_bf16(p + "lrelu_convT", up_w[u], a, NB * 2.0 * S.Cin * S.Cout * (double)S.K * L);
     }
     if (merged) {
       // conv i of rb0, rb1, rb2 have the same shape and no dependence on each other: one launch advances all three. Only the
@@ -1420,11 +1444,11 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
           fin.res = src[j]; fin.y = dst; fin.act = dst_act;
           if (lastd && j == 2) { fin.mrf_a = r[0]; fin.mrf_b = r[1]; }
           bb[j] = fin;
-          wb[j] = c.resblock_type == 1 ? &v->rb_b[u][j][2 * di + 1] : &v->rb_b[u][j][di];
+          wb[j] = c.resblock_type == 1 ? &rb_w[u][j][2 * di + 1] : &rb_w[u][j][di];
           if (c.resblock_type == 1) {
             aa[j] = rb_args_bf16(b, src_act[j], K, dl, Lo, row);
             aa[j].act = mid[j];
-            wa[j] = &v->rb_b[u][j][2 * di];
+            wa[j] = &rb_w[u][j][2 * di];
           }
           src[j] = dst;
           src_act[j] = dst_act;
@@ -1432,7 +1456,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
         }
         // ResBlock1 pairs that are not the stage's last: both convs in one launch, intermediate in LDS (rb_pair_bf16.hip)
         const bool no_pair = no_rb_pair();
-        if (c.resblock_type == 1 && !no_pair) {
+        if (c.resblock_type == 1 && !no_pair && !split) {
           struct Pack { RbPairBf16Args a[3]; } pk;
           bool ok = true;
           for (int j = 0; j < 3 && ok; j++) {
@@ -1514,13 +1538,13 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
         if (c.resblock_type == 1) {
           ConvBf16Args a1 = rb_args_bf16(b, src_act, K, dil, Lo, row);
           a1.act = mid[j];
-          b.conv_bf16(nm + "a_lrelu_conv", v->rb_b[u][j][2 * di], a1, fl);
+          b.conv_bf16(nm + "a_lrelu_conv", rb_w[u][j][2 * di], a1, fl);
           join();
-          b.conv_bf16(nm + (fuse_mean ? "b_lrelu_conv_res_mrfmean" : "b_lrelu_conv_res"), v->rb_b[u][j][2 * di + 1],
+          b.conv_bf16(nm + (fuse_mean ? "b_lrelu_conv_res_mrfmean" : "b_lrelu_conv_res"), rb_w[u][j][2 * di + 1],
                       finish(rb_args_bf16(b, mid[j], K, 1, Lo, row)), fl);
         } else {
           join();
-          b.conv_bf16(nm + (fuse_mean ? "_lrelu_conv_res_mrfmean" : "_lrelu_conv_res"), v->rb_b[u][j][di],
+          b.conv_bf16(nm + (fuse_mean ? "_lrelu_conv_res_mrfmean" : "_lrelu_conv_res"), rb_w[u][j][di],
                       finish(rb_args_bf16(b, src_act, K, dil, Lo, row)), fl);
         }
         if (!fuse_mean) tap_step(j, di, dst);
@@ -2212,7 +2236,7 @@ int build_schedule(piper_hip_voice* v, Slot& s, int T, int F, int NB, PlanKind k
     z = s.z_out = build_flow(b, fb);
   }
   b.tap("z", z, I, F, 1);
-  if (v->precision == PIPER_HIP_PRECISION_BF16) return build_generator_bf16(b, z, dec0);
+  if (v->precision != PIPER_HIP_PRECISION_F32) return build_generator_bf16(b, z, dec0);
   // ---------------- HiFi-GAN generator, fp32
   {
     ConvArgs a = b.plain(z, dec0, I, c.up_initial, F, b.lensF);
@@ -2598,28 +2622,36 @@ PH_EXPORT int piper_hip_voice_slot_pitch(piper_hip_voice* v, int slot, const pip
 
 PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16)
+  if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16 && precision != PIPER_HIP_PRECISION_BF16X3)
     PH_FAIL(PIPER_HIP_ERR_ARG, "voice_set_precision: unknown precision %d", precision);
   if (precision == v->precision) return PIPER_HIP_OK;
   piper_hip_ctx* ctx = v->ctx;
   const piper_hip_voice_config& c = v->cfg;
   PH_HIP(hipSetDevice(ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   PH_HIP(hipDeviceSynchronize(), PIPER_HIP_ERR_LAUNCH);
-  if (precision == PIPER_HIP_PRECISION_BF16 && v->up_b.empty()) {
-    // every generator conv must fall inside the bf16 kernels' geometry; otherwise the voice stays fp32
-    if (!conv_bf16_eligible(c.up_initial, c.inter, 7, 1, 3, 3))
+  // the fragment images of a bf16 precision are packed the first time it is selected and kept: bf16 and split bf16 each have their own
+  const bool split = precision == PIPER_HIP_PRECISION_BF16X3;
+  auto& conv_pre_w = split ? v->conv_pre_x : v->conv_pre_b;
+  auto& up_w = split ? v->up_x : v->up_b;
+  auto& rb_w = split ? v->rb_x : v->rb_b;
+  if (precision != PIPER_HIP_PRECISION_F32 && up_w.empty()) {
+    // every generator conv must fall inside the bf16 kernels' geometry (split: and both planes of its smallest window inside LDS);
+    // otherwise the voice stays as it is
+    const size_t planes = split ? 2 : 1;
+    if (!conv_bf16_eligible(c.up_initial, c.inter, 7, 1, 3, 3) || (split && !conv_bf16x3_fits((c.up_initial + 31) / 32, c.inter, conv_reach(7, 1))))
       PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "bf16 generator: conv_pre %d→%d not covered", c.inter, c.up_initial);
-    size_t elems = packed_conv_bf16_elems(c.up_initial, c.inter, 7);
+    size_t elems = planes * packed_conv_bf16_elems(c.up_initial, c.inter, 7);
     for (const auto& S : v->stages) {
-      if (!convt_bf16_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, S.pad, 1, 0))
+      if (!convt_bf16_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, S.pad, 1, 0) ||
+          (split && !conv_bf16x3_fits(S.Cout / 32, S.Cin, convt_reach(S.K, S.stride, S.pad))))
         PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "bf16 generator: ConvTranspose %d→%d k%d s%d not covered", S.Cin, S.Cout, S.K, S.stride);
-      elems += packed_convt_bf16_elems(S.Cin, S.Cout, S.K, S.stride);
+      elems += planes * packed_convt_bf16_elems(S.Cin, S.Cout, S.K, S.stride);
       for (int j = 0; j < c.n_rb; j++)
         for (int di = 0; di < c.rb_n_dil; di++) {
           const int K = c.rb_kernels[j], dl = c.rb_dilations[j][di], pad = (K * dl - dl) / 2;
-          if (!conv_bf16_eligible(S.Cout, S.Cout, K, dl, pad, pad))
+          if (!conv_bf16_eligible(S.Cout, S.Cout, K, dl, pad, pad) || (split && !conv_bf16x3_fits((S.Cout + 31) / 32, S.Cout, conv_reach(K, dl))))
             PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "bf16 generator: ResBlock conv C=%d k%d d%d not covered", S.Cout, K, dl);
-          elems += (c.resblock_type == 1 ? 2 : 1) * packed_conv_bf16_elems(S.Cout, S.Cout, K);
+          elems += (c.resblock_type == 1 ? 2 : 1) * planes * packed_conv_bf16_elems(S.Cout, S.Cout, K);
         }
     }
     void* p = nullptr;
@@ -2632,24 +2664,30 @@ PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
     auto conv = [&](const std::string& prefix, int Cout, int Cin, int K) {
       piper_hip_voice::ConvWB w;
       w.Cout = Cout; w.Cin = Cin; w.K = K;
-      uint16_t* img = take(packed_conv_bf16_elems(Cout, Cin, K));
-      pack_conv_weights_bf16(q, tensor(v, prefix + ".weight"), Cout, Cin, K, img);
+      uint16_t* img = take(planes * packed_conv_bf16_elems(Cout, Cin, K));
+      if (split)
+        pack_conv_weights_bf16x3(q, tensor(v, prefix + ".weight"), Cout, Cin, K, img);
+      else
+        pack_conv_weights_bf16(q, tensor(v, prefix + ".weight"), Cout, Cin, K, img);
       w.w = img;
       w.bias = tensor(v, prefix + ".bias");
       return w;
     };
-    v->conv_pre_b = conv("dec.conv_pre", c.up_initial, c.inter, 7);
+    conv_pre_w = conv("dec.conv_pre", c.up_initial, c.inter, 7);
     char nm[128];
     for (int u = 0; u < c.n_ups; u++) {
       const auto& S = v->stages[u];
       piper_hip_voice::ConvWB w;
       w.Cout = S.Cout; w.Cin = S.Cin; w.K = S.K;
-      uint16_t* img = take(packed_convt_bf16_elems(S.Cin, S.Cout, S.K, S.stride));
+      uint16_t* img = take(planes * packed_convt_bf16_elems(S.Cin, S.Cout, S.K, S.stride));
       snprintf(nm, sizeof nm, "dec.ups.%d", u);
-      pack_convt_weights_bf16(q, tensor(v, std::string(nm) + ".weight"), S.Cin, S.Cout, S.K, S.stride, S.pad, img);
+      if (split)
+        pack_convt_weights_bf16x3(q, tensor(v, std::string(nm) + ".weight"), S.Cin, S.Cout, S.K, S.stride, S.pad, img);
+      else
+        pack_convt_weights_bf16(q, tensor(v, std::string(nm) + ".weight"), S.Cin, S.Cout, S.K, S.stride, S.pad, img);
       w.w = img;
       w.bias = tensor(v, std::string(nm) + ".bias");
-      v->up_b.push_back(w);
+      up_w.push_back(w);
       std::vector<std::vector<piper_hip_voice::ConvWB>> rbs;
       for (int j = 0; j < c.n_rb; j++) {
         std::vector<piper_hip_voice::ConvWB> convs;
@@ -2667,7 +2705,7 @@ PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
         }
         rbs.push_back(convs);
       }
-      v->rb_b.push_back(rbs);
+      rb_w.push_back(rbs);
     }
     hipError_t e = hipStreamSynchronize(q);
     if (e == hipSuccess) e = hipGetLastError();

@@ -453,6 +453,10 @@ _PROTOS = {
                                         C.POINTER(c_vp), c_i64p, c_vp]),
     "piper_hip_convtranspose1d_bf16": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, c_vp,
                                                  C.POINTER(ConvTranspose1dParams), C.POINTER(c_vp), c_i64p, c_vp]),
+    "piper_hip_conv1d_bf16x3": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, c_vp, C.POINTER(Conv1dParams),
+                                          C.POINTER(c_vp), c_i64p, c_vp]),
+    "piper_hip_convtranspose1d_bf16x3": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, c_vp,
+                                                   C.POINTER(ConvTranspose1dParams), C.POINTER(c_vp), c_i64p, c_vp]),
     "piper_hip_matmul_f32": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, C.c_int, C.POINTER(c_vp), c_i64p, c_vp]),
     "piper_hip_softmax_lastdim_f32": (C.c_int, [c_vp, c_vp, c_i64p, C.c_int, C.POINTER(c_vp), c_vp]),
     "piper_hip_unary_f32": (C.c_int, [c_vp, C.c_int, c_vp, C.c_size_t, C.c_float, C.POINTER(c_vp), c_vp]),
@@ -867,6 +871,32 @@ class HipBackend:
         _check(self.lib.piper_hip_convtranspose1d_bf16(self.ctx, _ptr(input), _i64(inputShape), _ptr(weight),
                                                        _i64(weightShape), _ptr(bias), C.byref(prm), C.byref(p), osh,
                                                        commandBuffer))
+        return self._out(p, list(osh))
+
+    def conv1dBF16x3(self, input, inputShape, weight, weightShape, bias, stride=1, dilation=1, padL=0, padR=0, groups=1,
+                     commandBuffer=None):
+        """conv1dBF16's contract on split operands: a = bf16(a) + bf16(a − bf16(a)), three bf16 MFMA terms, fp32-grade results."""
+        if len(inputShape) != 3:
+            raise ShapeMismatch("conv1dBF16x3 input must be [N,C,L]")
+        if len(weightShape) != 3:
+            raise ShapeMismatch("conv1dBF16x3 weight must be [C_out,C_in,K]")
+        prm = Conv1dParams(stride, dilation, padL, padR, groups)
+        p, osh = c_vp(), (C.c_int64 * 3)()
+        _check(self.lib.piper_hip_conv1d_bf16x3(self.ctx, _ptr(input), _i64(inputShape), _ptr(weight), _i64(weightShape),
+                                                _ptr(bias), C.byref(prm), C.byref(p), osh, commandBuffer))
+        return self._out(p, list(osh))
+
+    def convTranspose1dBF16x3(self, input, inputShape, weight, weightShape, bias, stride=1, dilation=1, padL=0, padR=0,
+                              outputPadding=0, groups=1, commandBuffer=None):
+        if len(inputShape) != 3:
+            raise ShapeMismatch("convTranspose1dBF16x3 input must be [N,C,L]")
+        if len(weightShape) != 3:
+            raise ShapeMismatch("convTranspose1dBF16x3 weight must be [C_in,C_out,K]")
+        prm = ConvTranspose1dParams(stride, dilation, padL, padR, outputPadding, groups)
+        p, osh = c_vp(), (C.c_int64 * 3)()
+        _check(self.lib.piper_hip_convtranspose1d_bf16x3(self.ctx, _ptr(input), _i64(inputShape), _ptr(weight),
+                                                         _i64(weightShape), _ptr(bias), C.byref(prm), C.byref(p), osh,
+                                                         commandBuffer))
         return self._out(p, list(osh))
 
     def matmulF32(self, a, aShape, b, bShape, commandBuffer=None):
@@ -1937,8 +1967,9 @@ class HipRuntime:
         return [int(x) for x in wanted[:nb]], [int(x) for x in fitted[:nb]]
 
     def set_precision(self, precision):
-        """"f32" (default, the parity configuration) or "bf16" (generator convs on bf16 operands, fp32 accumulate)."""
-        code = {"f32": 0, "fp32": 0, "bf16": 1}.get(precision, precision)
+        """"f32" (default, the parity configuration), "bf16" (generator convs on bf16 operands, fp32 accumulate) or "bf16x3" (split bf16
+        operands, three MFMA terms per contraction: the fp32 path's error floor on the bf16 matrix pipe)."""
+        code = {"f32": 0, "fp32": 0, "bf16": 1, "bf16x3": 2}.get(precision, precision)
         _check(self.lib.piper_hip_voice_set_precision(self.voice, int(code)))
         self._keep.clear()  # prepared slots are dropped by the library
 

@@ -1,0 +1,112 @@
+"""The three generator precisions side by side: launch → samples on the host for f32, bf16 and bf16x3 (split bf16, include/piper_hip.h
+PIPER_HIP_PRECISION_BF16X3) on the same utterance, in one process.
+
+Per voice (medium, high) three runtimes on one backend, one per precision; per factor (8, 64) the fixture utterance tiled by `factor`
+(F = 42 · factor frames, 3 frames per id, injected noise) is prepared once on each and then replayed: launch, collect into a pageable buffer,
+host clock around both (collect waits for the slot's stream). The precisions are interleaved replay by replay, `--warmup` untimed rounds, then
+`--reps` timed ones, and the whole leg `--runs` times: a cell is the median of the runs' medians, its spread max − min of them. The waveform
+RMS error of each precision against the fp32 result of the same process is printed next to the times (the oracle comparison is the test's,
+tests/test_gpu_bf16x3.py). Needs the GPU: there is no fallback.
+
+Writes <out>/bf16x3.json and the table of <out>/bf16x3.md (everything from a "## Notes" heading on is kept)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PRECISIONS = ("f32", "bf16", "bf16x3")
+
+
+def med(x):
+    return round(float(np.median(np.asarray(x, np.float64))), 4)
+
+
+def leg(ph, rts, n, warmup, reps):
+    """median ms per precision of launch → collect on slot 0 (prepared by the caller), interleaved"""
+    buf = np.empty(n, np.float32)
+    times = {p: [] for p in PRECISIONS}
+    for k in range(warmup + reps):
+        for p in PRECISIONS:
+            rt = rts[p]
+            t0 = time.perf_counter()
+            ph._check(rt.lib.piper_hip_voice_launch(rt.voice, 0))
+            ph._check(rt.lib.piper_hip_voice_collect(rt.voice, 0, buf.ctypes.data_as(ph.c_f32p), n))
+            t1 = time.perf_counter()
+            if k >= warmup:
+                times[p].append((t1 - t0) * 1e3)
+    return {p: med(t) for p, t in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--voices", default="medium,high")
+    ap.add_argument("--factors", default="8,64")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.join(ROOT, "piper-swift_amd", "python"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import katdata as kd
+    import piper_hip as ph
+    backend = ph.HipBackend(0)  # DeviceUnavailable without the library or the GPU: no fallback
+    out = {"probe": "bf16x3", "warmup": args.warmup, "reps": args.reps, "runs": args.runs, "legs": []}
+    for quality in [q for q in args.voices.split(",") if q]:
+        cfg = ph.voice_config(quality)
+        blob = ph.synthetic_blob(cfg, 1234)
+        rts = {}
+        for p in PRECISIONS:
+            rts[p] = ph.HipRuntime(backend, cfg, blob)
+            rts[p].set_precision(p)
+        for factor in [int(f) for f in args.factors.split(",") if f]:
+            ids = kd.FIXTURE_IDS * factor
+            dur = [3] * len(ids)
+            noise = kd.sym(4321 + factor, (cfg.inter, sum(dur)), 1.7320508)
+            wave = {}
+            for p in PRECISIONS:
+                rts[p].prepare(0, ids, dur, noise, 0.667)
+                rts[p].launch(0)
+                wave[p] = rts[p].collect(0).astype(np.float64)
+            n = wave["f32"].size
+            runs = [leg(ph, rts, n, args.warmup, args.reps) for _ in range(args.runs)]
+            r = {"voice": quality, "factor": factor, "samples": int(n), "runs": runs}
+            for p in PRECISIONS:
+                vals = [x[p] for x in runs]
+                r[p] = med(vals)
+                r[p + "_spread"] = round(max(vals) - min(vals), 4)
+                r[p + "_rms_vs_f32"] = float(np.sqrt(np.mean((wave[p] - wave["f32"]) ** 2)))
+            out["legs"].append(r)
+            print(json.dumps({k: w for k, w in r.items() if k != "runs"}), file=sys.stderr, flush=True)
+        for rt in rts.values():
+            rt.close()
+    backend.close()
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, "bf16x3.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    lines = ["# Split bf16 (PIPER_HIP_PRECISION_BF16X3) against f32 and bf16", "",
+             f"One launch → samples on the host (pageable), median ms over {args.reps} replays per precision, the three interleaved, after "
+             f"{args.warmup} untimed rounds; ± = max − min of the medians of {args.runs} runs of the leg (`tools/probe/bf16x3_probe.py`; raw figures "
+             "in `bf16x3.json`). rms = RMS difference of the waveform from the f32 waveform of the same process.", "",
+             "| voice | factor | samples | f32 ms | bf16 ms | bf16x3 ms | bf16x3 / f32 | bf16 rms | bf16x3 rms |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in out["legs"]:
+        cell = lambda k: f"{r[k]} ± {r[k + '_spread']}"  # noqa: E731
+        lines.append(f"| {r['voice']} | {r['factor']} | {r['samples']} | {cell('f32')} | {cell('bf16')} | {cell('bf16x3')} | "
+                     f"{r['bf16x3'] / r['f32']:.3f} | {r['bf16_rms_vs_f32']:.3e} | {r['bf16x3_rms_vs_f32']:.3e} |")
+    md = os.path.join(args.out, "bf16x3.md")
+    notes = ""
+    if os.path.exists(md):
+        old = open(md).read()
+        if "\n## Notes" in old:
+            notes = old[old.index("\n## Notes"):]
+    with open(md, "w") as fh:
+        fh.write("\n".join(lines) + "\n" + notes)
+
+
+if __name__ == "__main__":
+    main()
