@@ -176,6 +176,16 @@ int piper_hip_convtranspose1d_bf16x3(piper_hip_ctx* ctx, const float* input, con
                                      const float* weight, const int64_t weight_shape[3], const float* bias,
                                      const piper_hip_convtranspose1d_params* p, float** out, int64_t out_shape[3],
                                      piper_hip_stream stream);
+/* The HiFi-GAN residual block with that arithmetic: the arguments, shapes and `*out` convention of piper_hip_hifigan_resblock_f32
+ * (below), every conv as three bf16 MFMA terms in one fp32 accumulator started at the bias; the residual stream, and ResBlock2's
+ * intermediate x1, stay fp32. Weights are split and packed on every call. With C = 32 or 64 and T % 4 == 0 two chained convs run per
+ * launch, the intermediate split in registers and kept in LDS (type 1: every (c1_i, c2_i); type 2: steps (i, i+1)); every other shape,
+ * an odd trailing step of type 2 included, runs as single split-bf16 convs. Refused as piper_hip_conv1d_bf16x3 refuses its convs:
+ * C % 32 != 0 or a `same` padding above 64 → UNSUPPORTED, as is a window that does not fit LDS. */
+int piper_hip_hifigan_resblock_bf16x3(piper_hip_ctx* ctx, int type, const float* x, int64_t n, int64_t c, int64_t t,
+                                      int64_t k, const int32_t* dilations, int n_dil, const float* const* weights,
+                                      const float* const* biases, float lrelu_slope, float** out,
+                                      piper_hip_stream stream);
 
 /* MetalBackend.matmulF32 (MetalBackend.swift:1232-1323) → matmul_f32 (matmul.metal:22-49), with the
  * executor's rank-4 lead-dim broadcast (GraphExecutor.swift:1870-1899) done by stride-0 addressing

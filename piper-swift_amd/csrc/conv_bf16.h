@@ -87,6 +87,9 @@ struct RbPairBf16Args {
   int N = 1, C = 0, L = 0;       // L % 4 == 0
   const int* len_ptr = nullptr;  // true length of item n = len_ptr[n]·len_mul; null ⇒ L
   int len_mul = 1;
+  // rb_pair_bf16x3.hip only: 1 — the ResBlock1 pair above; 2 — ResBlock2 steps (i, i+1), x1 = x + conv_a(lrelu x) + ba,
+  // y = x1 + conv_b(lrelu x1) + bb
+  int form = 1;
 };
 bool rb_pair_bf16_eligible(int C, int Ka, int dila, int Kb, int dilb, int L);
 int launch_rb_pair_bf16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairBf16Args* pairs, int count);  // ≤ 3 pairs, same N, C, L

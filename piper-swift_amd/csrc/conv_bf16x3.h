@@ -33,4 +33,14 @@ inline int convt_reach(int K, int stride, int pad) { return (stride - 1 + pad) /
 int launch_conv_bf16x3(piper_hip_ctx* ctx, hipStream_t s, const ConvBf16Args& a);
 int launch_conv_bf16x3_multi(piper_hip_ctx* ctx, hipStream_t s, const ConvBf16Args* convs, int count);  // the kBf16Multi contract
 
+// C8 planes of lrelu(((a + b) + c) / 3, alpha): pack_mean3_c8 on planar images (true length of item n = len_ptr[n]·len_mul)
+int pack_mean3_c8x2(hipStream_t s, const float* a, const float* b, const float* c, int N, int C, int L, float alpha, uint16_t* act, int64_t row,
+                    const int* len_ptr, int len_mul);
+
+// ---- rb_pair_bf16x3.hip: two chained ResBlock convs in one kernel on the fp32 stream, C ∈ {32, 64}, L % 4 == 0, odd kernels, any
+// dilations (reach ≤ 64 each side); RbPairBf16Args with wa / wb = the planar fragment images above and `form` = 1 (ResBlock1 pair) or
+// 2 (ResBlock2 steps i, i+1); `act` is a planar image. The launch refuses (UNSUPPORTED) whatever rb_pair_bf16x3_eligible refuses.
+bool rb_pair_bf16x3_eligible(int C, int Ka, int dila, int Kb, int dilb, int L, int form);
+int launch_rb_pair_bf16x3_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairBf16Args* pairs, int count);  // ≤ 3 pairs, same N, C, L, form
+
 }  // namespace ph

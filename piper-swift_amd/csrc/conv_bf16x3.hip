@@ -112,6 +112,33 @@ __global__ __launch_bounds__(kBT) void pack_act_c8x2_kernel(const float* __restr
   }
 }
 
+// both C8 planes of lrelu(((a + b) + c) / 3): the MRF mean of three fp32 [N][C][L] tensors, C % 8 == 0; zeros past the true length
+__global__ __launch_bounds__(kBT) void pack_mean3_c8x2_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c, int C,
+                                                             int L, int64_t row, float alpha, uint16_t* __restrict__ act, const int* __restrict__ len_ptr,
+                                                             int len_mul) {
+  const int CB = C >> 3;
+  const int n = blockIdx.z, cb = blockIdx.y;
+  const int Lv = len_ptr ? min(len_ptr[n] * len_mul, L) : L;
+  if (len_ptr && Lv == 0) return;  // a row of length 0 is read by nobody (block-uniform)
+  const int64_t off = ((int64_t)n * C + cb * 8) * L;
+  uint4* hi_p = (uint4*)act + ((int64_t)n * CB + cb) * row + kC8Halo;
+  uint4* lo_p = hi_p + (int64_t)gridDim.z * CB * row;
+  for (int pos = blockIdx.x * kBT + threadIdx.x; pos < L; pos += gridDim.x * kBT) {
+    float va[8], vb[8], vc[8], v[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const int64_t i = off + (int64_t)e * L + pos;
+      va[e] = a[i]; vb[e] = b[i]; vc[e] = c[i];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) v[e] = pos < Lv ? lrelu1(((va[e] + vb[e]) + vc[e]) / 3.0f, alpha) : 0.0f;
+    uint4 hi, lo;
+    split8_bf16(v, hi, lo);
+    hi_p[pos] = hi;
+    lo_p[pos] = lo;
+  }
+}
+
 // ---------------------------------------------------------------- the conv
 // WM waves along rows × (4/WM) along columns; each wave MTW × NTW tiles of 32×32.
 struct ConvBf16x3Multi {
@@ -397,6 +424,14 @@ int pack_act_c8x2(hipStream_t s, const float* x, int N, int C, int L, float alph
   if (row <= 0) row = c8_row_len(L);
   const dim3 grid((unsigned)std::min<int64_t>(ceil_div(L, kBT), 1024), (unsigned)((C + 7) / 8), (unsigned)N);  // gridDim.z = N: the plane offset
   return launch_pack(s, pack_act_c8x2_kernel, grid, x, C, L, row, alpha, act, len_ptr);
+}
+int pack_mean3_c8x2(hipStream_t s, const float* a, const float* b, const float* c, int N, int C, int L, float alpha, uint16_t* act, int64_t row,
+                    const int* len_ptr, int len_mul) {
+  if (N <= 0 || C <= 0 || L <= 0) return PIPER_HIP_OK;
+  if (C & 7) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "pack_mean3_c8x2: %d channels (multiples of 8)", C);
+  if (row <= 0) row = c8_row_len(L);
+  const dim3 grid((unsigned)std::min<int64_t>(ceil_div(L, kBT), 1024), (unsigned)(C / 8), (unsigned)N);  // gridDim.z = N: the plane offset
+  return launch_pack(s, pack_mean3_c8x2_kernel, grid, a, b, c, C, L, row, alpha, act, len_ptr, len_mul);
 }
 bool conv_bf16x3_fits(int row_tiles, int Cin, int reach) { return lds_bytes(Cin, 4 / waves_along_rows(row_tiles) * 32, reach) <= kLdsMax; }
 

@@ -1326,13 +1326,30 @@ ConvBf16Args rb_args_bf16(const Builder& b, const uint16_t* in, int K, int dil, 
   return a;
 }
 
+// … and a split-bf16 pair launch (rb_pair_bf16x3.hip) on the fp32 stream x → y over rows of Lo positions; form 1: a ResBlock1 pair,
+// 2: two ResBlock2 steps. `act`: the planar image of lrelu(y, 0.1) for a consumer that is not fused, or null
+RbPairBf16Args rb_pair_args_x3(const Builder& b, const piper_hip_voice::ConvWB& wa, int dila, const piper_hip_voice::ConvWB& wb, int dilb, int form,
+                               const float* x, float* y, uint16_t* act, int row, int Lo) {
+  RbPairBf16Args q;
+  q.x = x; q.y = y; q.act = act; q.act_row = row;
+  q.wa = wa.w; q.ba = wa.bias; q.wb = wb.w; q.bb = wb.bias;
+  q.Ka = wa.K; q.dila = dila; q.Kb = wb.K; q.dilb = dilb; q.alpha = 0.1f; q.form = form;
+  q.N = b.NB; q.C = wa.Cout; q.L = Lo; q.len_ptr = b.lensF; q.len_mul = Lo / b.F;
+  return q;
+}
+bool rb_pair_x3_ok(const RbPairBf16Args& q, int C, const piper_hip_voice::ConvWB& wa, const piper_hip_voice::ConvWB& wb) {
+  return q.x && (q.y || q.act) && q.wa && q.wb && q.ba && q.bb && wa.Cin == C && wa.Cout == C && wb.Cin == C && wb.Cout == C &&
+         rb_pair_bf16x3_eligible(C, q.Ka, q.dila, q.Kb, q.dilb, q.L, q.form);
+}
+
 // HiFi-GAN generator with bf16 contraction operands. Same graph as the fp32 generators below;
 // what changes is the data each conv READS: the C8 bf16 image of LeakyReLU(x) written by its producer's epilogue
 // (conv_bf16.h). The residual stream, the bias adds and the MRF mean stay fp32, so rounding enters only through the
 // operands of each contraction and does not accumulate along the residual chain.
 // PIPER_HIP_PRECISION_BF16X3 (split mode) is the same schedule — step names, lanes, fork / join, merged versus per-conv — on planar hi/lo
-// images and the conv_bf16x3 launchers. It has no fused ResBlock1 pair (two doubled windows and the intermediate exceed LDS at 128
-// channels): pairs take the two-launch path, the one PIPER_HIP_NO_RB_PAIR selects for bf16.
+// images and the conv_bf16x3 launchers. Its 32- and 64-channel stages run two chained convs per launch (rb_pair_bf16x3.hip: ResBlock1
+// pairs and ResBlock2 step pairs); at 128 channels and up two doubled windows and the intermediate exceed LDS, and the convs take the
+// two-launch path, the one PIPER_HIP_NO_RB_PAIR selects everywhere.
 int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   piper_hip_voice* v = b.v;
   Slot& s = b.s;
@@ -1429,9 +1446,50 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
       // very last conv of rb2 runs alone, after the others, because its epilogue folds the MRF mean over r0, r1.
       const float* src[3] = {up, up, up};
       const uint16_t* src_act[3] = {a_up, a_up, a_up};
+      const bool no_pair = no_rb_pair();
+      // the MRF mean as a small elementwise launch, behind a launch that closed all three ResBlocks into r[0..2]
+      auto add_stage_mean = [&]() {
+        const std::string mn = p + "mrf_mean" + (last_stage ? "" : "_lrelu_to_bf16");
+        const float *r0 = r[0], *r1 = r[1], *r2 = r[2];
+        const int* lf = b.lensF;
+        const int Cc = S.Cout, lm = Lo / F;
+        if (last_stage)  // conv_post applies its LeakyReLU(0.01) itself: slope 1 here
+          add_mrf_mean(b, mn, r0, r1, r2, m, (int64_t)NB * S.Cout * Lo, 1.0f);
+        else
+          b.step(mn, "", 0, 0, [=](hipStream_t q) {
+            return split ? pack_mean3_c8x2(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm) : pack_mean3_c8(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm);
+          });
+      };
       for (int di = 0; di < c.rb_n_dil; di++) {
         const bool lastd = di + 1 == c.rb_n_dil;
         const std::string nm = p + "rb012.c" + std::to_string(di);
+        // split mode, ResBlock2 steps (di, di+1) of a 32- / 64-channel stage: both convs of all three ResBlocks in one launch, the
+        // intermediate in LDS, x1 in fp32 (rb_pair_bf16x3.hip)
+        if (split && c.resblock_type == 2 && !no_pair && !lastd) {
+          const bool lastp = di + 2 == c.rb_n_dil;
+          struct Pack { RbPairBf16Args a[3]; } pk;
+          bool ok = true;
+          double fl2 = 0;
+          for (int j = 0; j < 3 && ok; j++) {
+            float* y = lastp ? r[j] : (src[j] == tmp[j][0] ? tmp[j][1] : tmp[j][0]);  // never the buffer being read
+            pk.a[j] = rb_pair_args_x3(b, rb_w[u][j][di], c.rb_dilations[j][di], rb_w[u][j][di + 1], c.rb_dilations[j][di + 1], 2, src[j], y,
+                                      lastp ? nullptr : act[j][0], row, Lo);
+            ok = rb_pair_x3_ok(pk.a[j], S.Cout, rb_w[u][j][di], rb_w[u][j][di + 1]);
+            fl2 += 2.0 * NB * conv_flops(S.Cout, S.Cout, c.rb_kernels[j], Lo);
+          }
+          if (ok) {
+            for (int j = 0; j < 3; j++) {
+              src[j] = pk.a[j].y;
+              src_act[j] = pk.a[j].act;
+              tap_step(j, di + 1, pk.a[j].y);
+            }
+            b.step(nm + "_lrelu_conv_res_lrelu_conv_res_x3", "conv_bf16x3", fl2, NB * 3 * (2.0 * 4.0 * S.Cout * (double)Lo),
+                   [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16x3_multi(ctx, q, pk.a, 3); });
+            if (lastp) add_stage_mean();
+            di++;
+            continue;
+          }
+        }
         ConvBf16Args aa[3], bb[3];
         const piper_hip_voice::ConvWB *wa[3], *wb[3];
         double fl[3];
@@ -1454,17 +1512,19 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
           src_act[j] = dst_act;
           if (!(lastd && j == 2)) tap_step(j, di, dst);
         }
-        // ResBlock1 pairs that are not the stage's last: both convs in one launch, intermediate in LDS (rb_pair_bf16.hip)
-        const bool no_pair = no_rb_pair();
-        if (c.resblock_type == 1 && !no_pair && !split) {
+        // ResBlock1 pairs: both convs in one launch, intermediate in LDS (rb_pair_bf16.hip; split mode: rb_pair_bf16x3.hip, 32 / 64 channels)
+        if (c.resblock_type == 1 && !no_pair) {
           struct Pack { RbPairBf16Args a[3]; } pk;
           bool ok = true;
+          auto eligible = [&](int K, int dila) {
+            return split ? rb_pair_bf16x3_eligible(S.Cout, K, dila, K, 1, Lo, 1) : rb_pair_bf16_eligible(S.Cout, K, dila, K, 1, Lo);
+          };
           for (int j = 0; j < 3 && ok; j++) {
             RbPairBf16Args& q = pk.a[j];
             q.x = bb[j].res; q.y = bb[j].y;
             // fused pairs stage from the fp32 stream themselves; the stage's last pair writes the next stage's input image, and a
             // pair in front of an UNFUSED one writes the image that one reads
-            const bool next_fused = !lastd && rb_pair_bf16_eligible(S.Cout, c.rb_kernels[j], c.rb_dilations[j][di + 1], c.rb_kernels[j], 1, Lo);
+            const bool next_fused = !lastd && eligible(c.rb_kernels[j], c.rb_dilations[j][di + 1]);
             q.act = (lastd || !next_fused) ? bb[j].act : nullptr;
             q.mrf_a = bb[j].mrf_a; q.mrf_b = bb[j].mrf_b;
             q.act_row = row;
@@ -1472,7 +1532,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
             q.Ka = wa[j]->K; q.dila = aa[j].dil; q.Kb = wb[j]->K; q.dilb = 1; q.alpha = 0.1f;
             q.N = NB; q.C = S.Cout; q.L = Lo; q.len_ptr = b.lensF; q.len_mul = Lo / F;
             ok = q.x && (q.y || q.act) && q.wa && q.wb && q.ba && q.bb && wa[j]->Cin == S.Cout && wa[j]->Cout == S.Cout && wb[j]->Cin == S.Cout && wb[j]->Cout == S.Cout &&
-                 rb_pair_bf16_eligible(S.Cout, q.Ka, q.dila, q.Kb, q.dilb, Lo);
+                 eligible(q.Ka, q.dila);
           }
           if (ok) {
             if (lastd) {
@@ -1481,18 +1541,12 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
               pk.a[2].y = r[2]; pk.a[2].act = nullptr; pk.a[2].mrf_a = nullptr; pk.a[2].mrf_b = nullptr;
               tap_step(2, di, r[2]);
             }
-            b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16", 2.0 * (fl[0] + fl[1] + fl[2]), NB * 3 * (2.0 * 4.0 * S.Cout * (double)Lo),
-                   [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16_multi(ctx, q, pk.a, 3); });
-            if (lastd) {
-              const std::string mn = p + "mrf_mean" + (last_stage ? "" : "_lrelu_to_bf16");
-              const float *r0 = r[0], *r1 = r[1], *r2 = r[2];
-              const int* lf = b.lensF;
-              const int Cc = S.Cout, lm = Lo / F;
-              if (last_stage)  // conv_post applies its LeakyReLU(0.01) itself: slope 1 here
-                add_mrf_mean(b, mn, r0, r1, r2, m, (int64_t)NB * S.Cout * Lo, 1.0f);
-              else
-                b.step(mn, "", 0, 0, [=](hipStream_t q) { return pack_mean3_c8(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm); });
-            }
+            const double pfl = 2.0 * (fl[0] + fl[1] + fl[2]), pby = NB * 3 * (2.0 * 4.0 * S.Cout * (double)Lo);
+            if (split)
+              b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16x3", pfl, pby, [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16x3_multi(ctx, q, pk.a, 3); });
+            else
+              b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16", pfl, pby, [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16_multi(ctx, q, pk.a, 3); });
+            if (lastd) add_stage_mean();
             continue;
           }
         }
@@ -1535,6 +1589,29 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
         auto join = [&]() {
           if (fuse_mean && s.parallel) b.join(p + "join");
         };
+        // split mode, 32- / 64-channel stages: two chained convs per launch on this ResBlock's lane (rb_pair_bf16x3.hip) — a ResBlock1
+        // pair, or ResBlock2 steps (di, di+1); the stage's closing pair folds the MRF mean into its epilogue
+        if (split && !no_rb_pair() && (c.resblock_type == 1 || !lastd)) {
+          const bool t1 = c.resblock_type == 1;
+          const int ib = t1 ? 2 * di + 1 : di + 1, db = t1 ? 1 : c.rb_dilations[j][di + 1];
+          const bool lastp = t1 ? lastd : di + 2 == c.rb_n_dil;
+          const bool mean_p = lastp && j + 1 == c.n_rb;
+          const piper_hip_voice::ConvWB &wa = rb_w[u][j][t1 ? 2 * di : di], &wb = rb_w[u][j][ib];
+          float* y = lastp ? (mean_p ? m : r[j]) : (src == tmp[j][0] ? tmp[j][1] : tmp[j][0]);  // never the buffer being read
+          uint16_t* ya = lastp ? (mean_p ? a_next : nullptr) : act[j][0];  // (a following pair stages from the fp32 stream and ignores it)
+          RbPairBf16Args q = rb_pair_args_x3(b, wa, dil, wb, db, t1 ? 1 : 2, src, y, ya, row, Lo);
+          if (mean_p) { q.mrf_a = r[0]; q.mrf_b = r[1]; }
+          if (rb_pair_x3_ok(q, S.Cout, wa, wb)) {
+            if (mean_p && s.parallel) b.join(p + "join");
+            b.step(nm + (t1 ? "ab_lrelu_conv_lrelu_conv_res" : "_lrelu_conv_res_lrelu_conv_res") + (mean_p ? "_mrfmean" : ""), "conv_bf16x3", 2.0 * fl,
+                   NB * (2.0 * 4.0 * S.Cout * (double)Lo), [ctx, q](hipStream_t qs) { return launch_rb_pair_bf16x3_multi(ctx, qs, &q, 1); });
+            if (!t1) di++;
+            if (!mean_p) tap_step(j, di, y);
+            src = y;
+            src_act = ya;
+            continue;
+          }
+        }
         if (c.resblock_type == 1) {
           ConvBf16Args a1 = rb_args_bf16(b, src_act, K, dil, Lo, row);
           a1.act = mid[j];
