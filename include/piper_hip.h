@@ -176,7 +176,19 @@ int piper_hip_convtranspose1d_bf16x3(piper_hip_ctx* ctx, const float* input, con
                                      const float* weight, const int64_t weight_shape[3], const float* bias,
                                      const piper_hip_convtranspose1d_params* p, float** out, int64_t out_shape[3],
                                      piper_hip_stream stream);
-/* The HiFi-GAN residual block with that arithmetic: the arguments, shapes and `*out` convention of piper_hip_hifigan_resblock_f32
+/* fp16 variants: the same shapes, parameter structs, refusals and covered geometry as the _bf16 pair (stride 1, or K % stride == 0 for
+ * convT; groups 1; C_in % 32 == 0; reach ≤ 64), fp32 tensors in and out, with the arithmetic of PIPER_HIP_PRECISION_F16 (below, "F16,
+ * the numeric contract") on v_mfma_f32_32x32x16_f16. Also UNSUPPORTED when the smallest tile's input window,
+ * (C_in / 8) · (32·(4 / WM) + reach) · 16 bytes with WM and reach as for the _bf16x3 pair, exceeds the 160 KB of LDS. A window that
+ * leaves no room for the block's weight ring in LDS is not refused: that instance streams its weights per wave from L2. */
+int piper_hip_conv1d_f16(piper_hip_ctx* ctx, const float* input, const int64_t input_shape[3], const float* weight,
+                         const int64_t weight_shape[3], const float* bias, const piper_hip_conv1d_params* p, float** out,
+                         int64_t out_shape[3], piper_hip_stream stream);
+int piper_hip_convtranspose1d_f16(piper_hip_ctx* ctx, const float* input, const int64_t input_shape[3],
+                                  const float* weight, const int64_t weight_shape[3], const float* bias,
+                                  const piper_hip_convtranspose1d_params* p, float** out, int64_t out_shape[3],
+                                  piper_hip_stream stream);
+/* The HiFi-GAN residual block with the split-bf16 arithmetic: the arguments, shapes and `*out` convention of piper_hip_hifigan_resblock_f32
  * (below), every conv as three bf16 MFMA terms in one fp32 accumulator started at the bias; the residual stream, and ResBlock2's
  * intermediate x1, stay fp32. Weights are split and packed on every call. With C = 32 or 64 and T % 4 == 0 two chained convs run per
  * launch, the intermediate split in registers and kept in LDS (type 1: every (c1_i, c2_i); type 2: steps (i, i+1)); every other shape,
@@ -373,12 +385,27 @@ void piper_hip_voice_destroy(piper_hip_voice* v);
  * per conv output: |error| ≤ 3·2⁻¹⁶·Σ|w||x| plus fp32 accumulation of the 3·C_in·K terms (BF16: 2·2⁻⁸·Σ|w||x|). ResBlock1 pairs run as
  * two launches (no fused pair kernel). Speed: profiles/bf16x3.md gives launch → collect against F32 and BF16 per voice and factor,
  * including the geometries where BF16X3 is not faster than F32.
+ * F16, the numeric contract: BF16's schedule, bytes and MFMA count with fp16 operands (11 significand bits against bf16's 8: operand
+ * rounding 8 times, 18 dB, smaller), ResBlock1 pairs as two launches. Everything BF16 keeps in fp32 stays fp32.
+ *   Activations: each conv input element is x' = fp16_rne(clamp(x, −65504, 65504)) — round to nearest even; the clamp is one
+ *     v_med3_f32 before the conversion, so an outlier costs a bounded error and not an inf that poisons the rest of the utterance.
+ *   Weights: one power-of-two scale per output channel. m = max|w[co,·,·]| (ConvTranspose: over all C_in and all K),
+ *     e_co = 14 − ⌊log₂ m⌋ (0 for an all-zero row), w' = fp16_rne(w · 2^e_co), so max|w'| ∈ [2¹⁴, 2¹⁵). The scale is exact and keeps
+ *     every weight that matters out of fp16's subnormal range (below 6.1e-5), whatever the voice's weight magnitudes are.
+ *   Accumulation: fp32 in the MFMA accumulator (a product of two fp16 values is exact in fp32). The epilogue multiplies the
+ *     accumulator by 2^−e_co (exact), then adds bias, residual and MRF mean in fp32, where BF16 adds them.
+ *   A-priori bound per conv output against the unrounded operands: (2·2⁻¹¹ + 2⁻²²)·Σ|w||x| plus fp32 accumulation, with no clamped
+ *     element and activations that are zero or ≥ 2⁻¹⁴ in magnitude.
+ *   Subnormal inputs: whether the fp16 MFMA honours or flushes subnormal inputs is not relied on — the row scale removes them from the
+ *     weights; an activation below 2⁻¹⁴ in magnitude may count as zero (an absolute error ≤ 2⁻¹⁴·|w| per term).
  * Drops every prepared slot (prepare again); the fragment images of a precision are packed the first time it is selected and kept, so
  * switching back costs no packing. UNSUPPORTED when a generator conv is outside the bf16 kernels' geometry (BF16X3: the same geometry,
- * and also when both planes of a conv's smallest input window do not fit LDS, see piper_hip_conv1d_bf16x3). */
+ * and also when both planes of a conv's smallest input window do not fit LDS, see piper_hip_conv1d_bf16x3; F16: when that window's one
+ * plane does not, see piper_hip_conv1d_f16). */
 #define PIPER_HIP_PRECISION_F32 0
 #define PIPER_HIP_PRECISION_BF16 1
 #define PIPER_HIP_PRECISION_BF16X3 2
+#define PIPER_HIP_PRECISION_F16 3
 int piper_hip_voice_set_precision(piper_hip_voice* v, int precision);
 int piper_hip_voice_precision(const piper_hip_voice* v);
 
@@ -1352,7 +1379,7 @@ int piper_hip_voice_prosody_report(const piper_hip_voice* v, int slot, int64_t* 
  *                            the last two steps (ping-pong buffers); a step fused inside a pair launch has no tensor, so a ResBlock2
  *                            stage that runs as one pair launch keeps "c1" only;
  *   "dec.s{u}.mean_lrelu"    fp32 per-conv schedule: lrelu(MRF mean) as the next stage reads it (slope 0.1; last stage 0.01);
- *   "dec.s{u}.mean_act"      bf16 only (not registered under BF16X3, whose image is two planes), u < n_ups − 1: the bf16 image of lrelu(MRF mean, 0.1) as raw bits, [C_u / 8][len][8] bf16 words
+ *   "dec.s{u}.mean_act"      bf16 only (not registered under BF16X3, whose image is two planes, nor under F16, whose words are fp16), u < n_ups − 1: the bf16 image of lrelu(MRF mean, 0.1) as raw bits, [C_u / 8][len][8] bf16 words
  *                            (4 floats per position and channel group);
  *   "dec.mean"               bf16: the last stage's fp32 MRF mean;
  *   "audio"                  the waveform rows [1][F·hop] of the plan (every plan kind), items at F_b·hop samples.

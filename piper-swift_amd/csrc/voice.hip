@@ -24,6 +24,7 @@
 #include "../../include/piper_hip_voice_layout.h"
 #include "conv.h"
 #include "conv_bf16x3.h"
+#include "conv_f16.h"
 #include "conv_win.h"
 #include "eq.h"
 #include "join.h"
@@ -620,6 +621,7 @@ struct piper_hip_voice {
   struct ConvWB {
     const uint16_t* w = nullptr;
     const float* bias = nullptr;
+    const float* scale = nullptr;  // fp16 images only: 2^−e per output channel (conv_f16.h)
     int Cout = 0, Cin = 0, K = 0;
   };
   int precision = PIPER_HIP_PRECISION_F32;
@@ -631,6 +633,10 @@ struct piper_hip_voice {
   ConvWB conv_pre_x;
   std::vector<ConvWB> up_x;
   std::vector<std::vector<std::vector<ConvWB>>> rb_x;
+  // fp16 generator (PIPER_HIP_PRECISION_F16): fp16 fragment images with their per-channel scales (conv_f16.h), kept beside the others
+  ConvWB conv_pre_h;
+  std::vector<ConvWB> up_h;
+  std::vector<std::vector<std::vector<ConvWB>>> rb_h;
   std::vector<void*> owned;
   // Plans are cached voice-wide, least-recently-used first out; a user slot id is a handle on one of them. A TTS server sees
   // a new (T, F) almost every call: with buckets the plan for it usually exists already (prepare = input upload only).
@@ -1172,13 +1178,24 @@ struct Builder {
 
   // the bf16 step constructors below serve both bf16 precisions: split ⇒ planar hi/lo images and the conv_bf16x3 launchers
   bool split() const { return v->precision == PIPER_HIP_PRECISION_BF16X3; }
+  // … and the fp16 precision: the bf16 geometry and schedule on fp16 images, scales beside the weights, the conv_f16 launchers
+  bool f16() const { return v->precision == PIPER_HIP_PRECISION_F16; }
+  static ConvF16Args f16_args(const ConvBf16Args& a, const piper_hip_voice::ConvWB& w) {
+    ConvF16Args h;
+    static_cast<ConvBf16Args&>(h) = a;
+    h.wscale = w.scale;
+    return h;
+  }
 
   // conv step over a bf16 fragment image
   void conv_bf16(const std::string& name, const piper_hip_voice::ConvWB& w, ConvBf16Args a, double flops) {
     a.w = w.w; a.Cin = w.Cin; a.Cout = w.Cout; a.K = w.K;
     if (!a.bias) a.bias = w.bias;  // (conv_pre of a voice with speakers comes with its items' effective biases)
     piper_hip_ctx* ctx = v->ctx;
-    if (split())
+    if (f16()) {
+      const ConvF16Args h = f16_args(a, w);
+      step(name, "conv_f16", flops, conv_bf16_bytes(a, false), [ctx, h](hipStream_t q) { return launch_conv_f16(ctx, q, h); });
+    } else if (split())
       step(name, "conv_bf16x3", flops, conv_bf16_bytes(a, true), [ctx, a](hipStream_t q) { return launch_conv_bf16x3(ctx, q, a); });
     else
       step(name, "conv_bf16", flops, conv_bf16_bytes(a, false), [ctx, a](hipStream_t q) { return launch_conv_bf16(ctx, q, a); });
@@ -1195,7 +1212,11 @@ struct Builder {
       bytes += conv_bf16_bytes(a, split());
     }
     piper_hip_ctx* ctx = v->ctx;
-    if (split())
+    if (f16()) {
+      struct PackH { ConvF16Args a[kBf16Multi]; } ph;
+      for (int i = 0; i < count; i++) ph.a[i] = f16_args(pk.a[i], *ws[i]);
+      step(name, "conv_f16", flops, bytes, [ctx, ph, count](hipStream_t q) { return launch_conv_f16_multi(ctx, q, ph.a, count); });
+    } else if (split())
       step(name, "conv_bf16x3", flops, bytes, [ctx, pk, count](hipStream_t q) { return launch_conv_bf16x3_multi(ctx, q, pk.a, count); });
     else
       step(name, "conv_bf16", flops, bytes, [ctx, pk, count](hipStream_t q) { return launch_conv_bf16_multi(ctx, q, pk.a, count); });
@@ -1350,6 +1371,8 @@ bool rb_pair_x3_ok(const RbPairBf16Args& q, int C, const piper_hip_voice::ConvWB
 // images and the conv_bf16x3 launchers. Its 32- and 64-channel stages run two chained convs per launch (rb_pair_bf16x3.hip: ResBlock1
 // pairs and ResBlock2 step pairs); at 128 channels and up two doubled windows and the intermediate exceed LDS, and the convs take the
 // two-launch path, the one PIPER_HIP_NO_RB_PAIR selects everywhere.
+// PIPER_HIP_PRECISION_F16 is the bf16 schedule on fp16 images of the same geometry (conv_f16.h), ResBlock1 pairs unfused: every conv is a
+// conv_f16 launch (a two-conv pair kernel for fp16 does not exist yet).
 int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   piper_hip_voice* v = b.v;
   Slot& s = b.s;
@@ -1362,10 +1385,10 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   hipStream_t zs = s.set.stream;
   static const bool no_par = getenv("PIPER_HIP_BF16_SERIAL_RB") != nullptr;
   const bool no_merge = no_merged_rb();
-  const bool split = b.split();
-  const piper_hip_voice::ConvWB& conv_pre_w = split ? v->conv_pre_x : v->conv_pre_b;
-  const auto& up_w = split ? v->up_x : v->up_b;
-  const auto& rb_w = split ? v->rb_x : v->rb_b;
+  const bool split = b.split(), f16 = b.f16();
+  const piper_hip_voice::ConvWB& conv_pre_w = f16 ? v->conv_pre_h : split ? v->conv_pre_x : v->conv_pre_b;
+  const auto& up_w = f16 ? v->up_h : split ? v->up_x : v->up_b;
+  const auto& rb_w = f16 ? v->rb_h : split ? v->rb_x : v->rb_b;
   // short utterances / small batches: the three ResBlocks advance in one launch; otherwise one launch per conv, as parallel
   // graph branches for the 18-conv ResBlock1 stages (+10 %; the 6-conv ResBlock2 stages do not gain)
   const bool merged = !no_merge && c.n_rb == 3 && (int64_t)NB * F <= 1536;
@@ -1382,6 +1405,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   {
     const int* lf = b.lensF;
     b.step("dec.z_to_bf16", "", 0, 0, [=](hipStream_t q) {
+      if (f16) return pack_act_c8_f16(q, z, NB, I, F, 1.0f, zc8, 0, lf);
       return split ? pack_act_c8x2(q, z, NB, I, F, 1.0f, zc8, 0, lf) : pack_act_c8(q, z, NB, I, F, 1.0f, zc8, 0, lf);
     });
   }
@@ -1432,7 +1456,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
     tap_f32(p + "up", up);
     if (last_stage) tap_f32("dec.mean", m);
     // the bf16 image of lrelu(MRF mean) that the next stage reads, as raw bits: row cb holds positions × 8 channels × bf16 = 4 floats per position
-    if (a_next && !split) b.tap(p + "mean_act", (const float*)a_next + kC8Halo * 4, S.Cout / 8, row * 4, Lo / F * 4);
+    if (a_next && !split && !f16) b.tap(p + "mean_act", (const float*)a_next + kC8Halo * 4, S.Cout / 8, row * 4, Lo / F * 4);
     {
       ConvBf16Args a;
       a.x = a_in; a.y = up; a.act = a_up; a.act_alpha = 0.1f;
@@ -1446,7 +1470,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
       // very last conv of rb2 runs alone, after the others, because its epilogue folds the MRF mean over r0, r1.
       const float* src[3] = {up, up, up};
       const uint16_t* src_act[3] = {a_up, a_up, a_up};
-      const bool no_pair = no_rb_pair();
+      const bool no_pair = no_rb_pair() || f16;  // (fp16: no pair kernel)
       // the MRF mean as a small elementwise launch, behind a launch that closed all three ResBlocks into r[0..2]
       auto add_stage_mean = [&]() {
         const std::string mn = p + "mrf_mean" + (last_stage ? "" : "_lrelu_to_bf16");
@@ -1457,6 +1481,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
           add_mrf_mean(b, mn, r0, r1, r2, m, (int64_t)NB * S.Cout * Lo, 1.0f);
         else
           b.step(mn, "", 0, 0, [=](hipStream_t q) {
+            if (f16) return pack_mean3_c8_f16(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm);
             return split ? pack_mean3_c8x2(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm) : pack_mean3_c8(q, r0, r1, r2, NB, Cc, Lo, 0.1f, a_next, row, lf, lm);
           });
       };
@@ -2699,7 +2724,8 @@ PH_EXPORT int piper_hip_voice_slot_pitch(piper_hip_voice* v, int slot, const pip
 
 PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
   if (!v) PH_FAIL(PIPER_HIP_ERR_ARG, "null voice");
-  if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16 && precision != PIPER_HIP_PRECISION_BF16X3)
+  if (precision != PIPER_HIP_PRECISION_F32 && precision != PIPER_HIP_PRECISION_BF16 && precision != PIPER_HIP_PRECISION_BF16X3 &&
+      precision != PIPER_HIP_PRECISION_F16)
     PH_FAIL(PIPER_HIP_ERR_ARG, "voice_set_precision: unknown precision %d", precision);
   if (precision == v->precision) return PIPER_HIP_OK;
   piper_hip_ctx* ctx = v->ctx;
@@ -2707,28 +2733,33 @@ PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
   PH_HIP(hipSetDevice(ctx->device), PIPER_HIP_ERR_UNAVAILABLE);
   PH_HIP(hipDeviceSynchronize(), PIPER_HIP_ERR_LAUNCH);
   // the fragment images of a bf16 precision are packed the first time it is selected and kept: bf16 and split bf16 each have their own
-  const bool split = precision == PIPER_HIP_PRECISION_BF16X3;
-  auto& conv_pre_w = split ? v->conv_pre_x : v->conv_pre_b;
-  auto& up_w = split ? v->up_x : v->up_b;
-  auto& rb_w = split ? v->rb_x : v->rb_b;
+  const bool split = precision == PIPER_HIP_PRECISION_BF16X3, f16 = precision == PIPER_HIP_PRECISION_F16;
+  auto& conv_pre_w = f16 ? v->conv_pre_h : split ? v->conv_pre_x : v->conv_pre_b;
+  auto& up_w = f16 ? v->up_h : split ? v->up_x : v->up_b;
+  auto& rb_w = f16 ? v->rb_h : split ? v->rb_x : v->rb_b;
   if (precision != PIPER_HIP_PRECISION_F32 && up_w.empty()) {
     // every generator conv must fall inside the bf16 kernels' geometry (split: and both planes of its smallest window inside LDS);
     // otherwise the voice stays as it is
     const size_t planes = split ? 2 : 1;
-    if (!conv_bf16_eligible(c.up_initial, c.inter, 7, 1, 3, 3) || (split && !conv_bf16x3_fits((c.up_initial + 31) / 32, c.inter, conv_reach(7, 1))))
+    // (fp16: the smallest window inside LDS; a float scale per output channel rides behind each image)
+    auto fits = [&](int row_tiles, int Cin, int reach) {
+      return f16 ? conv_f16_fits(row_tiles, Cin, reach) : !split || conv_bf16x3_fits(row_tiles, Cin, reach);
+    };
+    auto scales = [&](int Cout) { return f16 ? (size_t)2 * ((Cout + 63) & ~63) : (size_t)0; };  // in 16-bit elements
+    if (!conv_bf16_eligible(c.up_initial, c.inter, 7, 1, 3, 3) || !fits((c.up_initial + 31) / 32, c.inter, conv_reach(7, 1)))
       PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "bf16 generator: conv_pre %d→%d not covered", c.inter, c.up_initial);
-    size_t elems = planes * packed_conv_bf16_elems(c.up_initial, c.inter, 7);
+    size_t elems = planes * packed_conv_bf16_elems(c.up_initial, c.inter, 7) + scales(c.up_initial);
     for (const auto& S : v->stages) {
       if (!convt_bf16_eligible(S.Cin, S.Cout, S.K, S.stride, S.pad, S.pad, 1, 0) ||
-          (split && !conv_bf16x3_fits(S.Cout / 32, S.Cin, convt_reach(S.K, S.stride, S.pad))))
+          !fits(S.Cout / 32, S.Cin, convt_reach(S.K, S.stride, S.pad)))
         PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "bf16 generator: ConvTranspose %d→%d k%d s%d not covered", S.Cin, S.Cout, S.K, S.stride);
-      elems += planes * packed_convt_bf16_elems(S.Cin, S.Cout, S.K, S.stride);
+      elems += planes * packed_convt_bf16_elems(S.Cin, S.Cout, S.K, S.stride) + scales(S.Cout);
       for (int j = 0; j < c.n_rb; j++)
         for (int di = 0; di < c.rb_n_dil; di++) {
           const int K = c.rb_kernels[j], dl = c.rb_dilations[j][di], pad = (K * dl - dl) / 2;
-          if (!conv_bf16_eligible(S.Cout, S.Cout, K, dl, pad, pad) || (split && !conv_bf16x3_fits((S.Cout + 31) / 32, S.Cout, conv_reach(K, dl))))
+          if (!conv_bf16_eligible(S.Cout, S.Cout, K, dl, pad, pad) || !fits((S.Cout + 31) / 32, S.Cout, conv_reach(K, dl)))
             PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "bf16 generator: ResBlock conv C=%d k%d d%d not covered", S.Cout, K, dl);
-          elems += (c.resblock_type == 1 ? 2 : 1) * planes * packed_conv_bf16_elems(S.Cout, S.Cout, K);
+          elems += (c.resblock_type == 1 ? 2 : 1) * (planes * packed_conv_bf16_elems(S.Cout, S.Cout, K) + scales(S.Cout));
         }
     }
     void* p = nullptr;
@@ -2742,7 +2773,11 @@ PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
       piper_hip_voice::ConvWB w;
       w.Cout = Cout; w.Cin = Cin; w.K = K;
       uint16_t* img = take(planes * packed_conv_bf16_elems(Cout, Cin, K));
-      if (split)
+      if (f16) {
+        float* sc = (float*)take(scales(Cout));
+        pack_conv_weights_f16(q, tensor(v, prefix + ".weight"), Cout, Cin, K, img, sc);
+        w.scale = sc;
+      } else if (split)
         pack_conv_weights_bf16x3(q, tensor(v, prefix + ".weight"), Cout, Cin, K, img);
       else
         pack_conv_weights_bf16(q, tensor(v, prefix + ".weight"), Cout, Cin, K, img);
@@ -2758,7 +2793,11 @@ PH_EXPORT int piper_hip_voice_set_precision(piper_hip_voice* v, int precision) {
       w.Cout = S.Cout; w.Cin = S.Cin; w.K = S.K;
       uint16_t* img = take(planes * packed_convt_bf16_elems(S.Cin, S.Cout, S.K, S.stride));
       snprintf(nm, sizeof nm, "dec.ups.%d", u);
-      if (split)
+      if (f16) {
+        float* sc = (float*)take(scales(S.Cout));
+        pack_convt_weights_f16(q, tensor(v, std::string(nm) + ".weight"), S.Cin, S.Cout, S.K, S.stride, S.pad, img, sc);
+        w.scale = sc;
+      } else if (split)
         pack_convt_weights_bf16x3(q, tensor(v, std::string(nm) + ".weight"), S.Cin, S.Cout, S.K, S.stride, S.pad, img);
       else
         pack_convt_weights_bf16(q, tensor(v, std::string(nm) + ".weight"), S.Cin, S.Cout, S.K, S.stride, S.pad, img);

@@ -457,6 +457,10 @@ _PROTOS = {
                                           C.POINTER(c_vp), c_i64p, c_vp]),
     "piper_hip_convtranspose1d_bf16x3": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, c_vp,
                                                    C.POINTER(ConvTranspose1dParams), C.POINTER(c_vp), c_i64p, c_vp]),
+    "piper_hip_conv1d_f16": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, c_vp, C.POINTER(Conv1dParams),
+                                       C.POINTER(c_vp), c_i64p, c_vp]),
+    "piper_hip_convtranspose1d_f16": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, c_vp,
+                                                C.POINTER(ConvTranspose1dParams), C.POINTER(c_vp), c_i64p, c_vp]),
     "piper_hip_matmul_f32": (C.c_int, [c_vp, c_vp, c_i64p, c_vp, c_i64p, C.c_int, C.POINTER(c_vp), c_i64p, c_vp]),
     "piper_hip_softmax_lastdim_f32": (C.c_int, [c_vp, c_vp, c_i64p, C.c_int, C.POINTER(c_vp), c_vp]),
     "piper_hip_unary_f32": (C.c_int, [c_vp, C.c_int, c_vp, C.c_size_t, C.c_float, C.POINTER(c_vp), c_vp]),
@@ -900,6 +904,33 @@ class HipBackend:
         _check(self.lib.piper_hip_convtranspose1d_bf16x3(self.ctx, _ptr(input), _i64(inputShape), _ptr(weight),
                                                          _i64(weightShape), _ptr(bias), C.byref(prm), C.byref(p), osh,
                                                          commandBuffer))
+        return self._out(p, list(osh))
+
+    def conv1dF16(self, input, inputShape, weight, weightShape, bias, stride=1, dilation=1, padL=0, padR=0, groups=1,
+                  commandBuffer=None):
+        """conv1dBF16's contract on fp16 operands: clamped round-to-nearest-even activations, weights scaled by a power of two per
+        output channel, fp32 accumulation (the arithmetic of set_precision("f16"))."""
+        if len(inputShape) != 3:
+            raise ShapeMismatch("conv1dF16 input must be [N,C,L]")
+        if len(weightShape) != 3:
+            raise ShapeMismatch("conv1dF16 weight must be [C_out,C_in,K]")
+        prm = Conv1dParams(stride, dilation, padL, padR, groups)
+        p, osh = c_vp(), (C.c_int64 * 3)()
+        _check(self.lib.piper_hip_conv1d_f16(self.ctx, _ptr(input), _i64(inputShape), _ptr(weight), _i64(weightShape),
+                                             _ptr(bias), C.byref(prm), C.byref(p), osh, commandBuffer))
+        return self._out(p, list(osh))
+
+    def convTranspose1dF16(self, input, inputShape, weight, weightShape, bias, stride=1, dilation=1, padL=0, padR=0,
+                           outputPadding=0, groups=1, commandBuffer=None):
+        if len(inputShape) != 3:
+            raise ShapeMismatch("convTranspose1dF16 input must be [N,C,L]")
+        if len(weightShape) != 3:
+            raise ShapeMismatch("convTranspose1dF16 weight must be [C_in,C_out,K]")
+        prm = ConvTranspose1dParams(stride, dilation, padL, padR, outputPadding, groups)
+        p, osh = c_vp(), (C.c_int64 * 3)()
+        _check(self.lib.piper_hip_convtranspose1d_f16(self.ctx, _ptr(input), _i64(inputShape), _ptr(weight),
+                                                      _i64(weightShape), _ptr(bias), C.byref(prm), C.byref(p), osh,
+                                                      commandBuffer))
         return self._out(p, list(osh))
 
     def matmulF32(self, a, aShape, b, bShape, commandBuffer=None):
@@ -1982,8 +2013,9 @@ class HipRuntime:
 
     def set_precision(self, precision):
         """"f32" (default, the parity configuration), "bf16" (generator convs on bf16 operands, fp32 accumulate) or "bf16x3" (split bf16
-        operands, three MFMA terms per contraction: the fp32 path's error floor on the bf16 matrix pipe)."""
-        code = {"f32": 0, "fp32": 0, "bf16": 1, "bf16x3": 2}.get(precision, precision)
+        operands, three MFMA terms per contraction: the fp32 path's error floor on the bf16 matrix pipe) or "f16" / "fp16" (bf16's
+        schedule and cost on fp16 operands with per-channel weight scales: 18 dB less operand rounding)."""
+        code = {"f32": 0, "fp32": 0, "bf16": 1, "bf16x3": 2, "f16": 3, "fp16": 3}.get(precision, precision)
         _check(self.lib.piper_hip_voice_set_precision(self.voice, int(code)))
         self._keep.clear()  # prepared slots are dropped by the library
 

@@ -597,6 +597,24 @@ public final class HIPBackend {
         try Self.check(piper_hip_convtranspose1d_bf16x3(ctx, input.f32, Self.i64(inputShape), weight.f32, Self.i64(weightShape), bias?.f32, &p, &out, &oshape, commandBuffer))
         return (wrap(out), oshape.map(Int.init))
     }
+    // ---- fp16 contractions: clamped round-to-nearest-even activations, one power-of-two weight scale per output channel (same contract again) ----
+    public func conv1dF16(input: HIPBuffer, inputShape: [Int], weight: HIPBuffer, weightShape: [Int], bias: HIPBuffer?, stride: Int, dilation: Int,
+                          padL: Int, padR: Int, groups: Int, commandBuffer: Stream? = nil) throws -> (out: HIPBuffer, outShape: [Int]) {
+        var p = piper_hip_conv1d_params(stride: Int32(stride), dilation: Int32(dilation), pad_l: Int32(padL), pad_r: Int32(padR), groups: Int32(groups))
+        var out: UnsafeMutablePointer<Float>? = nil
+        var oshape = [Int64](repeating: 0, count: 3)
+        try Self.check(piper_hip_conv1d_f16(ctx, input.f32, Self.i64(inputShape), weight.f32, Self.i64(weightShape), bias?.f32, &p, &out, &oshape, commandBuffer))
+        return (wrap(out), oshape.map(Int.init))
+    }
+    public func convTranspose1dF16(input: HIPBuffer, inputShape: [Int], weight: HIPBuffer, weightShape: [Int], bias: HIPBuffer?, stride: Int, dilation: Int,
+                                   padL: Int, padR: Int, outputPadding: Int, groups: Int, commandBuffer: Stream? = nil) throws -> (out: HIPBuffer, outShape: [Int]) {
+        var p = piper_hip_convtranspose1d_params(stride: Int32(stride), dilation: Int32(dilation), pad_l: Int32(padL), pad_r: Int32(padR),
+                                                 output_padding: Int32(outputPadding), groups: Int32(groups))
+        var out: UnsafeMutablePointer<Float>? = nil
+        var oshape = [Int64](repeating: 0, count: 3)
+        try Self.check(piper_hip_convtranspose1d_f16(ctx, input.f32, Self.i64(inputShape), weight.f32, Self.i64(weightShape), bias?.f32, &p, &out, &oshape, commandBuffer))
+        return (wrap(out), oshape.map(Int.init))
+    }
 
     // ---- fused blocks (results equal the composition of the ops above; tests/test_gpu_ops.py) ----
     /// out = LN_c(x + y)·gamma + beta (the Add + ReduceMean … Div chain, GraphExecutor.swift:2071-2125); y may be nil

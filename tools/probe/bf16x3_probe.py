@@ -8,7 +8,10 @@ host clock around both (collect waits for the slot's stream). The precisions are
 RMS error of each precision against the fp32 result of the same process is printed next to the times (the oracle comparison is the test's,
 tests/test_gpu_bf16x3.py). Needs the GPU: there is no fallback.
 
-Writes <out>/bf16x3.json and the table of <out>/bf16x3.md (everything from a "## Notes" heading on is kept)."""
+`--precisions` picks the list that runs interleaved (f32 first: the rms baseline) and `--name` the files: `--precisions f32,bf16,bf16x3,f16
+--name f16` is profiles/f16.md, the fp16 precision (PIPER_HIP_PRECISION_F16) beside the other three in one process.
+
+Writes <out>/<name>.json and the table of <out>/<name>.md (everything from a "## Notes" heading on is kept)."""
 import argparse
 import json
 import os
@@ -26,6 +29,7 @@ def med(x):
 
 
 def leg(ph, rts, n, warmup, reps):
+    PRECISIONS = tuple(rts)
     """median ms per precision of launch → collect on slot 0 (prepared by the caller), interleaved"""
     buf = np.empty(n, np.float32)
     times = {p: [] for p in PRECISIONS}
@@ -49,18 +53,24 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--precisions", default=",".join(PRECISIONS))
+    ap.add_argument("--name", default="bf16x3")
     args = ap.parse_args()
+    precisions = tuple(p for p in args.precisions.split(",") if p)
+    if precisions[0] != "f32":
+        ap.error("--precisions starts with f32 (the rms baseline)")
+    last = precisions[-1]
     sys.path.insert(0, os.path.join(ROOT, "piper-swift_amd", "python"))
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import katdata as kd
     import piper_hip as ph
     backend = ph.HipBackend(0)  # DeviceUnavailable without the library or the GPU: no fallback
-    out = {"probe": "bf16x3", "warmup": args.warmup, "reps": args.reps, "runs": args.runs, "legs": []}
+    out = {"probe": args.name, "precisions": list(precisions), "warmup": args.warmup, "reps": args.reps, "runs": args.runs, "legs": []}
     for quality in [q for q in args.voices.split(",") if q]:
         cfg = ph.voice_config(quality)
         blob = ph.synthetic_blob(cfg, 1234)
         rts = {}
-        for p in PRECISIONS:
+        for p in precisions:
             rts[p] = ph.HipRuntime(backend, cfg, blob)
             rts[p].set_precision(p)
         for factor in [int(f) for f in args.factors.split(",") if f]:
@@ -68,14 +78,14 @@ def main():
             dur = [3] * len(ids)
             noise = kd.sym(4321 + factor, (cfg.inter, sum(dur)), 1.7320508)
             wave = {}
-            for p in PRECISIONS:
+            for p in precisions:
                 rts[p].prepare(0, ids, dur, noise, 0.667)
                 rts[p].launch(0)
                 wave[p] = rts[p].collect(0).astype(np.float64)
             n = wave["f32"].size
             runs = [leg(ph, rts, n, args.warmup, args.reps) for _ in range(args.runs)]
             r = {"voice": quality, "factor": factor, "samples": int(n), "runs": runs}
-            for p in PRECISIONS:
+            for p in precisions:
                 vals = [x[p] for x in runs]
                 r[p] = med(vals)
                 r[p + "_spread"] = round(max(vals) - min(vals), 4)
@@ -86,19 +96,21 @@ def main():
             rt.close()
     backend.close()
     os.makedirs(args.out, exist_ok=True)
-    with open(os.path.join(args.out, "bf16x3.json"), "w") as fh:
+    with open(os.path.join(args.out, args.name + ".json"), "w") as fh:
         json.dump(out, fh, indent=1)
         fh.write("\n")
-    lines = ["# Split bf16 (PIPER_HIP_PRECISION_BF16X3) against f32 and bf16", "",
-             f"One launch → samples on the host (pageable), median ms over {args.reps} replays per precision, the three interleaved, after "
+    title = "# Split bf16 (PIPER_HIP_PRECISION_BF16X3) against f32 and bf16" if last == "bf16x3" else f"# {last} against " + ", ".join(precisions[:-1])
+    lines = [title, "",
+             f"One launch → samples on the host (pageable), median ms over {args.reps} replays per precision, the {len(precisions)} interleaved, after "
              f"{args.warmup} untimed rounds; ± = max − min of the medians of {args.runs} runs of the leg (`tools/probe/bf16x3_probe.py`; raw figures "
-             "in `bf16x3.json`). rms = RMS difference of the waveform from the f32 waveform of the same process.", "",
-             "| voice | factor | samples | f32 ms | bf16 ms | bf16x3 ms | bf16x3 / f32 | bf16 rms | bf16x3 rms |", "|---|---|---|---|---|---|---|---|---|"]
+             f"in `{args.name}.json`). rms = RMS difference of the waveform from the f32 waveform of the same process.", "",
+             "| voice | factor | samples | " + " | ".join(p + " ms" for p in precisions) + f" | {last} / f32 | " + " | ".join(p + " rms" for p in precisions[1:]) + " |",
+             "|" + "---|" * (4 + 2 * len(precisions) - 1)]
     for r in out["legs"]:
         cell = lambda k: f"{r[k]} ± {r[k + '_spread']}"  # noqa: E731
-        lines.append(f"| {r['voice']} | {r['factor']} | {r['samples']} | {cell('f32')} | {cell('bf16')} | {cell('bf16x3')} | "
-                     f"{r['bf16x3'] / r['f32']:.3f} | {r['bf16_rms_vs_f32']:.3e} | {r['bf16x3_rms_vs_f32']:.3e} |")
-    md = os.path.join(args.out, "bf16x3.md")
+        lines.append(f"| {r['voice']} | {r['factor']} | {r['samples']} | " + " | ".join(cell(p) for p in precisions) + f" | {r[last] / r['f32']:.3f} | " +
+                     " | ".join(f"{r[p + '_rms_vs_f32']:.3e}" for p in precisions[1:]) + " |")
+    md = os.path.join(args.out, args.name + ".md")
     notes = ""
     if os.path.exists(md):
         old = open(md).read()
