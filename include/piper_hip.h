@@ -198,6 +198,14 @@ int piper_hip_hifigan_resblock_bf16x3(piper_hip_ctx* ctx, int type, const float*
                                       int64_t k, const int32_t* dilations, int n_dil, const float* const* weights,
                                       const float* const* biases, float lrelu_slope, float** out,
                                       piper_hip_stream stream);
+/* The HiFi-GAN residual block with the fp16 arithmetic (below, "F16, the numeric contract"): the arguments, shapes and `*out` convention
+ * of piper_hip_hifigan_resblock_bf16x3. Weight images and their per-channel scales are packed on every call. Type 1 with C = 32, 64 or
+ * 128 and T % 4 == 0 runs every (c1_i, c2_i) as one launch, the intermediate rounded in registers and kept in LDS with the rounding
+ * points of two single convs; every other shape, and type 2 entirely, runs as single fp16 convs. Refused as piper_hip_conv1d_f16
+ * refuses its convs. */
+int piper_hip_hifigan_resblock_f16(piper_hip_ctx* ctx, int type, const float* x, int64_t n, int64_t c, int64_t t, int64_t k,
+                                   const int32_t* dilations, int n_dil, const float* const* weights,
+                                   const float* const* biases, float lrelu_slope, float** out, piper_hip_stream stream);
 
 /* MetalBackend.matmulF32 (MetalBackend.swift:1232-1323) → matmul_f32 (matmul.metal:22-49), with the
  * executor's rank-4 lead-dim broadcast (GraphExecutor.swift:1870-1899) done by stride-0 addressing
@@ -386,7 +394,9 @@ void piper_hip_voice_destroy(piper_hip_voice* v);
  * two launches (no fused pair kernel). Speed: profiles/bf16x3.md gives launch → collect against F32 and BF16 per voice and factor,
  * including the geometries where BF16X3 is not faster than F32.
  * F16, the numeric contract: BF16's schedule, bytes and MFMA count with fp16 operands (11 significand bits against bf16's 8: operand
- * rounding 8 times, 18 dB, smaller), ResBlock1 pairs as two launches. Everything BF16 keeps in fp32 stays fp32.
+ * rounding 8 times, 18 dB, smaller). ResBlock1 pairs of the 32-, 64- and 128-channel stages run as one launch each, as under BF16,
+ * with the rounding points of two single convs (the intermediate is clamped and rounded to fp16 exactly as the image a single conv
+ * writes). Everything BF16 keeps in fp32 stays fp32.
  *   Activations: each conv input element is x' = fp16_rne(clamp(x, −65504, 65504)) — round to nearest even; the clamp is one
  *     v_med3_f32 before the conversion, so an outlier costs a bounded error and not an inf that poisons the rest of the utterance.
  *   Weights: one power-of-two scale per output channel. m = max|w[co,·,·]| (ConvTranspose: over all C_in and all K),

@@ -724,3 +724,117 @@ PH_EXPORT int piper_hip_hifigan_resblock_bf16x3(piper_hip_ctx* ctx, int type, co
   }
   return ss.finish("hifigan_resblock_bf16x3");
 }
+
+// The fp16 ResBlock (conv_f16.h): piper_hip_hifigan_resblock_bf16x3's contract and walk on the fp16 pipe. Weight images and their
+// per-channel scales are packed per call (the scales behind each image, in one allocation). ResBlock1 pairs (convs1[i], convs2[i]) of
+// 32, 64 or 128 channels with T % 4 == 0 run as one launch (rb_pair_f16.hip); every other conv, and ResBlock2 entirely, is a single
+// conv_f16 launch on C8 images. What piper_hip_conv1d_f16 refuses is refused here, with its codes.
+PH_EXPORT int piper_hip_hifigan_resblock_f16(piper_hip_ctx* ctx, int type, const float* x, int64_t n, int64_t c, int64_t t, int64_t k,
+                                             const int32_t* dilations, int n_dil, const float* const* weights, const float* const* biases,
+                                             float lrelu_slope, float** out, piper_hip_stream stream) {
+  PH_CHECK_CTX(ctx);
+  if (type != 1 && type != 2) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "hifigan_resblock_f16: type %d", type);
+  if (n < 0 || c <= 0 || t < 0 || k <= 0 || n_dil < 1 || n_dil > 8 || !dilations || !weights || !biases)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_resblock_f16: bad arguments");
+  if (!(k & 1)) PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_resblock_f16: kernel size must be odd");
+  if (!fits_i32(c * t) || !fits_i32(c * c * k)) PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_resblock_f16: tensor too large");
+  const int C = (int)c, T = (int)t, K = (int)k;
+  for (int i = 0; i < n_dil; i++) {
+    if (dilations[i] < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_resblock_f16: dilation must be >= 1");
+    const int pad = (K - 1) * dilations[i] / 2;
+    if (!conv_bf16_eligible(C, C, K, dilations[i], pad, pad))
+      PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "hifigan_resblock_f16: geometry not covered (channels %% 32 == 0, padding <= 64)");
+  }
+  const size_t cnt = (size_t)(n * c * t);
+  int rc = ensure_out(ctx, out, cnt, 0);
+  if (rc) return rc;
+  if (cnt == 0) return PIPER_HIP_OK;
+  if (!x) PH_FAIL(PIPER_HIP_ERR_ARG, "hifigan_resblock_f16: null input");
+  const int n_conv = type == 1 ? 2 * n_dil : n_dil;
+  for (int i = 0; i < n_conv; i++)
+    if (!weights[i]) PH_FAIL(PIPER_HIP_ERR_ARG, "hifigan_resblock_f16: null weight");
+  StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
+  const uint16_t* pw[16];
+  const float* sc[16];
+  const size_t w_bytes = packed_conv_bf16_elems(C, C, K) * 2;
+  for (int i = 0; i < n_conv; i++) {
+    void* q = nullptr;
+    if ((rc = ctx->pool.alloc(w_bytes + (size_t)C * sizeof(float), &q))) return rc;
+    defer_free(ctx, q);
+    float* scale = (float*)((char*)q + w_bytes);
+    pack_conv_weights_f16(ss.s, weights[i], C, C, K, (uint16_t*)q, scale);
+    pw[i] = (const uint16_t*)q;
+    sc[i] = scale;
+  }
+  float* tmp[2] = {nullptr, nullptr};  // ping-pong so the residual source is never the buffer being written
+  for (int i = 0; i < 2; i++) {
+    if ((rc = pool_floats(ctx, cnt, &tmp[i]))) return rc;
+    defer_free(ctx, tmp[i]);
+  }
+  // C8 images of lrelu(·) for the single convs: two for the stream (ping-pong), one for ResBlock1's intermediate; allocated and zeroed
+  // when the first single conv needs them
+  const int row = (int)c8_row_len(T);
+  const size_t img_bytes = (size_t)c8_elems(n, C, T) * 2;
+  uint16_t* img[3] = {nullptr, nullptr, nullptr};
+  auto image = [&](int i) -> int {
+    if (img[i]) return PIPER_HIP_OK;
+    void* q = nullptr;
+    int r = ctx->pool.alloc(img_bytes, &q);
+    if (r) return r;
+    defer_free(ctx, q);
+    PH_HIP(hipMemsetAsync(q, 0, img_bytes, ss.s), PIPER_HIP_ERR_LAUNCH);
+    img[i] = (uint16_t*)q;
+    return PIPER_HIP_OK;
+  };
+  static const bool no_pair = getenv("PIPER_HIP_NO_RB_PAIR") != nullptr;
+  // the pair kernel reads the stream with 16-byte loads and takes its biases from memory
+  const bool pairs_ok = !no_pair && type == 1 && ((uintptr_t)x & 15) == 0;
+  auto pair_at = [&](int i) {  // does the walk take a pair launch at step i?
+    return pairs_ok && i < n_dil && biases[2 * i] && biases[2 * i + 1] && rb_pair_f16_eligible(C, K, dilations[i], K, 1, T);
+  };
+  auto conv = [&](const uint16_t* src, int wi, int dil, const float* res, float* y, uint16_t* act) -> int {
+    ConvF16Args a;
+    a.x = src; a.w = pw[wi]; a.wscale = sc[wi]; a.bias = biases[wi]; a.res = res; a.y = y; a.act = act; a.act_alpha = lrelu_slope;
+    a.N = (int)n; a.Cin = C; a.Cout = C; a.K = K; a.dil = dil; a.padL = (K - 1) * dil / 2;
+    a.Lout = T; a.x_row = row; a.act_row = row; a.y_len = T;
+    return launch_conv_f16(ctx, ss.s, a);
+  };
+  const float* cur = x;
+  int cur_img = -1;  // index of the image that holds lrelu(cur), −1: none yet
+  auto next_buf = [&](bool last) { return last ? *out : (cur == tmp[0] ? tmp[1] : tmp[0]); };  // never the buffer being read
+  for (int i = 0; i < n_dil; i++) {
+    const bool last = i == n_dil - 1;
+    if (pair_at(i)) {
+      const int ni = last || pair_at(i + 1) ? -1 : (cur_img == 0 ? 1 : 0);  // a single conv follows: it reads the image this launch writes
+      if (ni >= 0 && (rc = image(ni))) return rc;
+      RbPairF16Args q;
+      q.x = cur; q.y = next_buf(last); q.act = ni >= 0 ? img[ni] : nullptr; q.act_row = row;
+      q.wa = pw[2 * i]; q.sa = sc[2 * i]; q.ba = biases[2 * i]; q.wb = pw[2 * i + 1]; q.sb = sc[2 * i + 1]; q.bb = biases[2 * i + 1];
+      q.Ka = K; q.dila = dilations[i]; q.Kb = K; q.dilb = 1; q.alpha = lrelu_slope;
+      q.N = (int)n; q.C = C; q.L = T;
+      if ((rc = launch_rb_pair_f16_multi(ctx, ss.s, &q, 1))) return rc;
+      cur = q.y;
+      cur_img = ni;
+      continue;
+    }
+    if (cur_img < 0) {  // the stream was produced by a pair launch, or is the input
+      if ((rc = image(0))) return rc;
+      pack_act_c8_f16(ss.s, cur, (int)n, C, T, lrelu_slope, img[0], row);
+      cur_img = 0;
+    }
+    float* dst = next_buf(last);
+    const int ni = last || pair_at(i + 1) ? -1 : 1 - cur_img;
+    if (ni >= 0 && (rc = image(ni))) return rc;
+    if (type == 1) {
+      if ((rc = image(2))) return rc;
+      if ((rc = conv(img[cur_img], 2 * i, dilations[i], nullptr, nullptr, img[2]))) return rc;
+      if ((rc = conv(img[2], 2 * i + 1, 1, cur, dst, ni >= 0 ? img[ni] : nullptr))) return rc;
+    } else {
+      if ((rc = conv(img[cur_img], i, dilations[i], cur, dst, ni >= 0 ? img[ni] : nullptr))) return rc;
+    }
+    cur = dst;
+    cur_img = ni;
+  }
+  return ss.finish("hifigan_resblock_f16");
+}

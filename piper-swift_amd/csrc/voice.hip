@@ -1371,8 +1371,8 @@ bool rb_pair_x3_ok(const RbPairBf16Args& q, int C, const piper_hip_voice::ConvWB
 // images and the conv_bf16x3 launchers. Its 32- and 64-channel stages run two chained convs per launch (rb_pair_bf16x3.hip: ResBlock1
 // pairs and ResBlock2 step pairs); at 128 channels and up two doubled windows and the intermediate exceed LDS, and the convs take the
 // two-launch path, the one PIPER_HIP_NO_RB_PAIR selects everywhere.
-// PIPER_HIP_PRECISION_F16 is the bf16 schedule on fp16 images of the same geometry (conv_f16.h), ResBlock1 pairs unfused: every conv is a
-// conv_f16 launch (a two-conv pair kernel for fp16 does not exist yet).
+// PIPER_HIP_PRECISION_F16 is the bf16 schedule on fp16 images of the same geometry (conv_f16.h): conv_f16 launches, and the merged ResBlock1
+// pairs of the 32-, 64- and 128-channel stages as one launch each (rb_pair_f16.hip), as under bf16. The per-ResBlock lanes stay unfused.
 int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   piper_hip_voice* v = b.v;
   Slot& s = b.s;
@@ -1470,7 +1470,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
       // very last conv of rb2 runs alone, after the others, because its epilogue folds the MRF mean over r0, r1.
       const float* src[3] = {up, up, up};
       const uint16_t* src_act[3] = {a_up, a_up, a_up};
-      const bool no_pair = no_rb_pair() || f16;  // (fp16: no pair kernel)
+      const bool no_pair = no_rb_pair();
       // the MRF mean as a small elementwise launch, behind a launch that closed all three ResBlocks into r[0..2]
       auto add_stage_mean = [&]() {
         const std::string mn = p + "mrf_mean" + (last_stage ? "" : "_lrelu_to_bf16");
@@ -1537,15 +1537,18 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
           src_act[j] = dst_act;
           if (!(lastd && j == 2)) tap_step(j, di, dst);
         }
-        // ResBlock1 pairs: both convs in one launch, intermediate in LDS (rb_pair_bf16.hip; split mode: rb_pair_bf16x3.hip, 32 / 64 channels)
+        // ResBlock1 pairs: both convs in one launch, intermediate in LDS (rb_pair_bf16.hip; split mode: rb_pair_bf16x3.hip, 32 / 64
+        // channels; fp16: rb_pair_f16.hip)
         if (c.resblock_type == 1 && !no_pair) {
-          struct Pack { RbPairBf16Args a[3]; } pk;
+          struct Pack { RbPairF16Args a[3]; } pk;  // the scales travel only under fp16
           bool ok = true;
           auto eligible = [&](int K, int dila) {
+            if (f16) return rb_pair_f16_eligible(S.Cout, K, dila, K, 1, Lo);
             return split ? rb_pair_bf16x3_eligible(S.Cout, K, dila, K, 1, Lo, 1) : rb_pair_bf16_eligible(S.Cout, K, dila, K, 1, Lo);
           };
           for (int j = 0; j < 3 && ok; j++) {
-            RbPairBf16Args& q = pk.a[j];
+            RbPairF16Args& q = pk.a[j];
+            q.sa = wa[j]->scale; q.sb = wb[j]->scale;
             q.x = bb[j].res; q.y = bb[j].y;
             // fused pairs stage from the fp32 stream themselves; the stage's last pair writes the next stage's input image, and a
             // pair in front of an UNFUSED one writes the image that one reads
@@ -1557,7 +1560,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
             q.Ka = wa[j]->K; q.dila = aa[j].dil; q.Kb = wb[j]->K; q.dilb = 1; q.alpha = 0.1f;
             q.N = NB; q.C = S.Cout; q.L = Lo; q.len_ptr = b.lensF; q.len_mul = Lo / F;
             ok = q.x && (q.y || q.act) && q.wa && q.wb && q.ba && q.bb && wa[j]->Cin == S.Cout && wa[j]->Cout == S.Cout && wb[j]->Cin == S.Cout && wb[j]->Cout == S.Cout &&
-                 eligible(q.Ka, q.dila);
+                 (!f16 || (q.sa && q.sb)) && eligible(q.Ka, q.dila);
           }
           if (ok) {
             if (lastd) {
@@ -1567,10 +1570,14 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
               tap_step(2, di, r[2]);
             }
             const double pfl = 2.0 * (fl[0] + fl[1] + fl[2]), pby = NB * 3 * (2.0 * 4.0 * S.Cout * (double)Lo);
-            if (split)
-              b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16x3", pfl, pby, [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16x3_multi(ctx, q, pk.a, 3); });
+            struct PackB { RbPairBf16Args a[3]; } pb;
+            for (int j = 0; j < 3; j++) pb.a[j] = pk.a[j];
+            if (f16)
+              b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_f16", pfl, pby, [ctx, pk](hipStream_t q) { return launch_rb_pair_f16_multi(ctx, q, pk.a, 3); });
+            else if (split)
+              b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16x3", pfl, pby, [ctx, pb](hipStream_t q) { return launch_rb_pair_bf16x3_multi(ctx, q, pb.a, 3); });
             else
-              b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16", pfl, pby, [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16_multi(ctx, q, pk.a, 3); });
+              b.step(nm + "ab_lrelu_conv_lrelu_conv_res_x3", "conv_bf16", pfl, pby, [ctx, pb](hipStream_t q) { return launch_rb_pair_bf16_multi(ctx, q, pb.a, 3); });
             if (lastd) add_stage_mean();
             continue;
           }

@@ -490,6 +490,9 @@ _PROTOS = {
     "piper_hip_hifigan_resblock_bf16x3": (C.c_int, [c_vp, C.c_int, c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_i32p,
                                                     C.c_int, C.POINTER(c_vp), C.POINTER(c_vp), C.c_float, C.POINTER(c_vp),
                                                     c_vp]),
+    "piper_hip_hifigan_resblock_f16": (C.c_int, [c_vp, C.c_int, c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_i32p,
+                                                 C.c_int, C.POINTER(c_vp), C.POINTER(c_vp), C.c_float, C.POINTER(c_vp),
+                                                 c_vp]),
     "piper_hip_voice_config_preset": (C.c_int, [C.c_int, C.POINTER(VoiceConfig)]),
     "piper_hip_voice_blob_floats": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(C.c_size_t)]),
     "piper_hip_voice_blob_layout": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(TensorInfo), C.c_int,
@@ -1223,6 +1226,17 @@ class HipBackend:
         p = c_vp()
         _check(self.lib.piper_hip_hifigan_resblock_bf16x3(self.ctx, type, _ptr(x), n, c, t, k, d, nd, w, b, slope, C.byref(p),
                                                           commandBuffer))
+        return self._out(p, [n, c, t])[0]
+
+    def hifiganResblockF16(self, type, x, n, c, t, k, dilations, weights, biases, slope=0.1, commandBuffer=None):
+        """hifiganResblockF32 with fp16 contractions (the arithmetic of set_precision("f16")); eligible ResBlock1 pairs run fused."""
+        nd = len(dilations)
+        d = (C.c_int32 * nd)(*dilations)
+        w = (c_vp * len(weights))(*[_ptr(b) for b in weights])
+        b = (c_vp * len(biases))(*[_ptr(x_) for x_ in biases])
+        p = c_vp()
+        _check(self.lib.piper_hip_hifigan_resblock_f16(self.ctx, type, _ptr(x), n, c, t, k, d, nd, w, b, slope, C.byref(p),
+                                                       commandBuffer))
         return self._out(p, [n, c, t])[0]
 
 

@@ -661,4 +661,14 @@ public final class HIPBackend {
                                                          Int32(dilations.count), w, b, slope, &out, commandBuffer))
         return wrap(out)
     }
+    /// hifiganResblockF32 with fp16 contractions (the arithmetic of the f16 voice precision): ResBlock1 pairs of 32 / 64 / 128 channels as one launch each
+    public func hifiganResblockF16(type: Int, x: HIPBuffer, batch: Int, channels: Int, length: Int, kernel: Int, dilations: [Int], weights: [HIPBuffer],
+                                   biases: [HIPBuffer], slope: Float = 0.1, commandBuffer: Stream? = nil) throws -> HIPBuffer {
+        var out: UnsafeMutablePointer<Float>? = nil
+        let w: [UnsafePointer<Float>?] = weights.map { UnsafePointer($0.f32) }
+        let b: [UnsafePointer<Float>?] = biases.map { UnsafePointer($0.f32) }
+        try Self.check(piper_hip_hifigan_resblock_f16(ctx, Int32(type), x.f32, Int64(batch), Int64(channels), Int64(length), Int64(kernel), dilations.map(Int32.init),
+                                                      Int32(dilations.count), w, b, slope, &out, commandBuffer))
+        return wrap(out)
+    }
 }
