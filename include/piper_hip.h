@@ -206,6 +206,17 @@ int piper_hip_hifigan_resblock_bf16x3(piper_hip_ctx* ctx, int type, const float*
 int piper_hip_hifigan_resblock_f16(piper_hip_ctx* ctx, int type, const float* x, int64_t n, int64_t c, int64_t t, int64_t k,
                                    const int32_t* dilations, int n_dil, const float* const* weights,
                                    const float* const* biases, float lrelu_slope, float** out, piper_hip_stream stream);
+/* HiFi-GAN MRF stage with the fp16 arithmetic: *out = ((rb_0(x) + rb_1(x)) + rb_2(x)) / 3, each rb_j a residual block of `type`
+ * with kernel kernels[j] and dilations[j·n_dil … ]; weights / biases ordered block by block as piper_hip_hifigan_resblock_f16 orders one.
+ * n_rb != 3 → UNSUPPORTED. Weight images and scales are packed on every call. The three blocks advance together, as the voice's merged
+ * schedule advances them: with C = 32 or 64 (type 1: 128 too), T % 4 == 0 and every block's convs within the pair kernel's geometry, one
+ * launch runs two chained convs of all three blocks — type 2: steps (i, i+1) with the intermediate x1 kept in fp32 in LDS for the second
+ * residual add and rounded to fp16 only as the second conv's operand; type 1: every (c1_i, c2_i) — with the rounding points of single
+ * convs. Every other shape, an odd trailing step of type 2 and type 2 at 128 channels included, runs as single fp16 convs. The mean is
+ * one elementwise launch in fp32. Refused as piper_hip_conv1d_f16 refuses its convs; a NULL context → PIPER_HIP_ERR_ARG. */
+int piper_hip_hifigan_mrf_f16(piper_hip_ctx* ctx, int type, const float* x, int64_t n, int64_t c, int64_t t, int n_rb,
+                              const int32_t* kernels, const int32_t* dilations, int n_dil, const float* const* weights,
+                              const float* const* biases, float lrelu_slope, float** out, piper_hip_stream stream);
 
 /* MetalBackend.matmulF32 (MetalBackend.swift:1232-1323) → matmul_f32 (matmul.metal:22-49), with the
  * executor's rank-4 lead-dim broadcast (GraphExecutor.swift:1870-1899) done by stride-0 addressing

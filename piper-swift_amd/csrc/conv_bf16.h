@@ -62,6 +62,9 @@ int pack_act_c8(hipStream_t s, const float* x, int N, int C, int L, float alpha,
 int pack_mean3_c8(hipStream_t s, const float* a, const float* b, const float* c, int N, int C, int L, float alpha, uint16_t* act, int64_t row,
                   const int* len_ptr, int len_mul);
 
+// the same mean as an fp32 tensor: y = lrelu(((a + b) + c) / 3, alpha) over cnt floats (voice.hip)
+int launch_mrf_mean_lrelu(hipStream_t s, const float* a, const float* b, const float* c, float* y, int64_t cnt, float alpha);
+
 // geometry the bf16 kernels cover (stride-1, ungrouped, Cin % 32 == 0, padding within the halo)
 bool conv_bf16_eligible(int Cout, int Cin, int K, int dil, int padL, int padR);
 bool convt_bf16_eligible(int Cin, int Cout, int K, int stride, int padL, int padR, int dil, int out_pad);

@@ -36,14 +36,17 @@ bool conv_f16_fits(int row_tiles, int Cin, int reach);
 int launch_conv_f16(piper_hip_ctx* ctx, hipStream_t s, const ConvF16Args& a);
 int launch_conv_f16_multi(piper_hip_ctx* ctx, hipStream_t s, const ConvF16Args* convs, int count);  // the kBf16Multi contract
 
-// ---- rb_pair_f16.hip: a ResBlock1 pair  y = x + conv_b(lrelu(conv_a(lrelu x) + ba)) + bb  in one kernel on the fp16 pipe (C ∈ {32, 64, 128},
-// odd kernels, both reaches ≤ kC8Halo, L % 4 == 0, the window within 160 KB of LDS). launch_rb_pair_bf16_multi's contract (form 1 only);
-// wa / wb are fp16 fragment images, `act` an fp16 C8 image. Column tiles are 256 − 2·(conv b's reach) outputs wide.
+// ---- rb_pair_f16.hip: two chained ResBlock convs in one kernel on the fp16 pipe (C ∈ {32, 64, 128}, odd kernels, both reaches ≤ kC8Halo,
+// L % 4 == 0, the window within 160 KB of LDS). RbPairBf16Args::form as in rb_pair_bf16x3.hip:
+//   1: a ResBlock1 pair                 y = x + conv_b(lrelu(conv_a(lrelu x) + ba)) + bb
+//   2: ResBlock2 steps (i, i+1)         x1 = x + conv_a(lrelu x) + ba ;  y = x1 + conv_b(lrelu x1) + bb      (x1 stays fp32)
+// launch_rb_pair_bf16_multi's contract; wa / wb are fp16 fragment images, `act` an fp16 C8 image. Column tiles are 256 − 2·(conv b's reach)
+// outputs wide.
 struct RbPairF16Args : RbPairBf16Args {
   const float* sa = nullptr;  // [C] 2^−e per output channel of conv a
   const float* sb = nullptr;  // … of conv b
 };
-bool rb_pair_f16_eligible(int C, int Ka, int dila, int Kb, int dilb, int L);
-int launch_rb_pair_f16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairF16Args* pairs, int count);  // ≤ 3 pairs, same N, C, L
+bool rb_pair_f16_eligible(int C, int Ka, int dila, int Kb, int dilb, int L, int form);
+int launch_rb_pair_f16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairF16Args* pairs, int count);  // ≤ 3 pairs, same N, C, L, form
 
 }  // namespace ph

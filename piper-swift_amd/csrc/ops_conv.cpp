@@ -791,7 +791,7 @@ PH_EXPORT int piper_hip_hifigan_resblock_f16(piper_hip_ctx* ctx, int type, const
   // the pair kernel reads the stream with 16-byte loads and takes its biases from memory
   const bool pairs_ok = !no_pair && type == 1 && ((uintptr_t)x & 15) == 0;
   auto pair_at = [&](int i) {  // does the walk take a pair launch at step i?
-    return pairs_ok && i < n_dil && biases[2 * i] && biases[2 * i + 1] && rb_pair_f16_eligible(C, K, dilations[i], K, 1, T);
+    return pairs_ok && i < n_dil && biases[2 * i] && biases[2 * i + 1] && rb_pair_f16_eligible(C, K, dilations[i], K, 1, T, 1);
   };
   auto conv = [&](const uint16_t* src, int wi, int dil, const float* res, float* y, uint16_t* act) -> int {
     ConvF16Args a;
@@ -837,4 +837,142 @@ PH_EXPORT int piper_hip_hifigan_resblock_f16(piper_hip_ctx* ctx, int type, const
     cur_img = ni;
   }
   return ss.finish("hifigan_resblock_f16");
+}
+
+// The fp16 MRF stage (conv_f16.h): the mean of three residual blocks of one input, walked step by step for all three together as the voice's
+// merged schedule walks them. Where every block's step is eligible the three run as ONE rb_pair_f16 launch — ResBlock1: the pair
+// (convs1[i], convs2[i]), form 1; ResBlock2: steps (i, i+1), form 2 — and otherwise each block takes single conv_f16 launches on C8 images
+// (an odd trailing ResBlock2 step included). The mean is the plans' elementwise launch. Weight images and scales are packed per call.
+PH_EXPORT int piper_hip_hifigan_mrf_f16(piper_hip_ctx* ctx, int type, const float* x, int64_t n, int64_t c, int64_t t, int n_rb,
+                                        const int32_t* kernels, const int32_t* dilations, int n_dil, const float* const* weights,
+                                        const float* const* biases, float lrelu_slope, float** out, piper_hip_stream stream) {
+  PH_CHECK_CTX(ctx);
+  if (type != 1 && type != 2) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "hifigan_mrf_f16: type %d", type);
+  if (n_rb != 3) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "hifigan_mrf_f16: %d residual blocks (3)", n_rb);
+  if (n < 0 || c <= 0 || t < 0 || n_dil < 1 || n_dil > 8 || !kernels || !dilations || !weights || !biases)
+    PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_mrf_f16: bad arguments");
+  const int per = type == 1 ? 2 * n_dil : n_dil;  // convs per block
+  auto dil_of = [&](int j, int i) { return (int)dilations[j * n_dil + i]; };
+  for (int j = 0; j < 3; j++) {
+    const int64_t k = kernels[j];
+    if (k <= 0 || !(k & 1)) PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_mrf_f16: kernel sizes must be odd");
+    if (!fits_i32(c * t) || !fits_i32(c * c * k)) PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_mrf_f16: tensor too large");
+    for (int i = 0; i < n_dil; i++) {
+      if (dil_of(j, i) < 1) PH_FAIL(PIPER_HIP_ERR_SHAPE, "hifigan_mrf_f16: dilation must be >= 1");
+      const int pad = ((int)k - 1) * dil_of(j, i) / 2;
+      if (!conv_bf16_eligible((int)c, (int)c, (int)k, dil_of(j, i), pad, pad))
+        PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "hifigan_mrf_f16: geometry not covered (channels %% 32 == 0, padding <= 64)");
+    }
+  }
+  const int C = (int)c, T = (int)t;
+  const size_t cnt = (size_t)(n * c * t);
+  int rc = ensure_out(ctx, out, cnt, 0);
+  if (rc) return rc;
+  if (cnt == 0) return PIPER_HIP_OK;
+  if (!x) PH_FAIL(PIPER_HIP_ERR_ARG, "hifigan_mrf_f16: null input");
+  for (int i = 0; i < 3 * per; i++)
+    if (!weights[i]) PH_FAIL(PIPER_HIP_ERR_ARG, "hifigan_mrf_f16: null weight");
+  StreamScope ss(ctx, stream);
+  RouteScope routes(ctx);
+  struct Block {
+    int K = 0;
+    const uint16_t* pw[16];
+    const float* sc[16];
+    const float* const* bias = nullptr;
+    float* buf[3] = {nullptr, nullptr, nullptr};  // two for the stream (ping-pong), the block's result
+    uint16_t* img[3] = {nullptr, nullptr, nullptr};  // C8 images of lrelu(·) for single convs: two for the stream, ResBlock1's intermediate
+    const float* cur = nullptr;
+    int cur_img = -1;  // index of the image that holds lrelu(cur), −1: none yet
+  } blk[3];
+  for (int j = 0; j < 3; j++) {
+    Block& B = blk[j];
+    B.K = kernels[j]; B.bias = biases + j * per; B.cur = x;
+    const size_t w_bytes = packed_conv_bf16_elems(C, C, B.K) * 2;
+    for (int i = 0; i < per; i++) {
+      void* q = nullptr;
+      if ((rc = ctx->pool.alloc(w_bytes + (size_t)C * sizeof(float), &q))) return rc;
+      defer_free(ctx, q);
+      float* scale = (float*)((char*)q + w_bytes);
+      pack_conv_weights_f16(ss.s, weights[j * per + i], C, C, B.K, (uint16_t*)q, scale);
+      B.pw[i] = (const uint16_t*)q;
+      B.sc[i] = scale;
+    }
+    for (int i = 0; i < 3; i++) {
+      if ((rc = pool_floats(ctx, cnt, &B.buf[i]))) return rc;
+      defer_free(ctx, B.buf[i]);
+    }
+  }
+  const int row = (int)c8_row_len(T);
+  const size_t img_bytes = (size_t)c8_elems(n, C, T) * 2;
+  auto image = [&](Block& B, int i) -> int {  // allocated and zeroed when the first single conv needs it
+    if (i < 0 || B.img[i]) return PIPER_HIP_OK;
+    void* q = nullptr;
+    int r = ctx->pool.alloc(img_bytes, &q);
+    if (r) return r;
+    defer_free(ctx, q);
+    PH_HIP(hipMemsetAsync(q, 0, img_bytes, ss.s), PIPER_HIP_ERR_LAUNCH);
+    B.img[i] = (uint16_t*)q;
+    return PIPER_HIP_OK;
+  };
+  static const bool no_pair = getenv("PIPER_HIP_NO_RB_PAIR") != nullptr;
+  const bool pairs_ok = !no_pair && ((uintptr_t)x & 15) == 0;  // the pair kernel reads the stream with 16-byte loads
+  const int adv = type == 2 ? 2 : 1;                            // dilation steps one pair launch covers
+  auto pair_at = [&](int i) {  // do all three blocks take the pair launch at step i?
+    if (!pairs_ok || i + adv > n_dil) return false;
+    for (int j = 0; j < 3; j++) {
+      const int ia = type == 1 ? 2 * i : i;
+      if (!blk[j].bias[ia] || !blk[j].bias[ia + 1] ||
+          !rb_pair_f16_eligible(C, blk[j].K, dil_of(j, i), blk[j].K, type == 1 ? 1 : dil_of(j, i + 1), T, type))
+        return false;
+    }
+    return true;
+  };
+  auto conv = [&](const Block& B, const uint16_t* src, int wi, int dil, const float* res, float* y, uint16_t* act) -> int {
+    ConvF16Args a;
+    a.x = src; a.w = B.pw[wi]; a.wscale = B.sc[wi]; a.bias = B.bias[wi]; a.res = res; a.y = y; a.act = act; a.act_alpha = lrelu_slope;
+    a.N = (int)n; a.Cin = C; a.Cout = C; a.K = B.K; a.dil = dil; a.padL = (B.K - 1) * dil / 2;
+    a.Lout = T; a.x_row = row; a.act_row = row; a.y_len = T;
+    return launch_conv_f16(ctx, ss.s, a);
+  };
+  for (int i = 0; i < n_dil;) {
+    const bool fused = pair_at(i);
+    const int step = fused ? adv : 1;
+    const bool last = i + step == n_dil;
+    const bool image_next = !last && !pair_at(i + step);  // a single conv follows: it reads the image this step writes
+    RbPairF16Args q[3];
+    for (int j = 0; j < 3; j++) {
+      Block& B = blk[j];
+      float* dst = last ? B.buf[2] : (B.cur == B.buf[0] ? B.buf[1] : B.buf[0]);  // never the buffer being read
+      if (!fused && B.cur_img < 0) {  // the stream was produced by a pair launch, or is the input
+        if ((rc = image(B, 0))) return rc;
+        pack_act_c8_f16(ss.s, B.cur, (int)n, C, T, lrelu_slope, B.img[0], row);
+        B.cur_img = 0;
+      }
+      const int ni = image_next ? (B.cur_img == 0 ? 1 : 0) : -1;
+      if ((rc = image(B, ni))) return rc;
+      uint16_t* act = ni >= 0 ? B.img[ni] : nullptr;
+      if (fused) {
+        const int ia = type == 1 ? 2 * i : i;
+        RbPairF16Args& p = q[j];
+        p.x = B.cur; p.y = dst; p.act = act; p.act_row = row; p.form = type;
+        p.wa = B.pw[ia]; p.sa = B.sc[ia]; p.ba = B.bias[ia]; p.wb = B.pw[ia + 1]; p.sb = B.sc[ia + 1]; p.bb = B.bias[ia + 1];
+        p.Ka = B.K; p.dila = dil_of(j, i); p.Kb = B.K; p.dilb = type == 1 ? 1 : dil_of(j, i + 1); p.alpha = lrelu_slope;
+        p.N = (int)n; p.C = C; p.L = T;
+      } else {
+        if (type == 1) {
+          if ((rc = image(B, 2))) return rc;
+          if ((rc = conv(B, B.img[B.cur_img], 2 * i, dil_of(j, i), nullptr, nullptr, B.img[2]))) return rc;
+          if ((rc = conv(B, B.img[2], 2 * i + 1, 1, B.cur, dst, act))) return rc;
+        } else {
+          if ((rc = conv(B, B.img[B.cur_img], i, dil_of(j, i), B.cur, dst, act))) return rc;
+        }
+      }
+      B.cur = dst;
+      B.cur_img = ni;
+    }
+    if (fused && (rc = launch_rb_pair_f16_multi(ctx, ss.s, q, 3))) return rc;
+    i += step;
+  }
+  launch_mrf_mean_lrelu(ss.s, blk[0].buf[2], blk[1].buf[2], blk[2].buf[2], *out, (int64_t)cnt, 1.0f);  // slope 1: the mean itself
+  return ss.finish("hifigan_mrf_f16");
 }

@@ -1,5 +1,6 @@
-// rb_pair_f16.hip — a ResBlock1 pair of the HiFi-GAN generator with fp16 operands in ONE kernel, C ∈ {32, 64, 128}:
-//     y = x + conv_b(lrelu(conv_a(lrelu x) + b_a)) + b_b          (convs1[i] dilated, convs2[i] dilation 1; Piper "high")
+// rb_pair_f16.hip — two chained ResBlock convs of the HiFi-GAN generator with fp16 operands in ONE kernel:
+//     form 1 (ResBlock1 pair, C ∈ {32, 64, 128})       y = x + conv_b(lrelu(conv_a(lrelu x) + b_a)) + b_b      (Piper "high")
+//     form 2 (ResBlock2 steps i, i+1, C ∈ {32, 64})    x1 = x + conv_a(lrelu x) + b_a ;  y = x1 + conv_b(lrelu x1) + b_b   ("medium", "low")
 // The arithmetic is conv_f16.h's with the rounding points of the two-launch path — lrelu(·) clamped to ±65504 and rounded to nearest
 // even into fp16, weights as the scaled fp16 fragment images, v_mfma_f32_32x32x16_f16 into fp32, accumulator · 2^−e, THEN the bias in
 // fp32 — so fused equals unfused up to fp32 summation order.
@@ -28,8 +29,21 @@
 //             LDS for two MFMAs, a third ds_read_b128 for A adds half again to the traffic of the pipe this loop leans on hardest, and
 //             both sets at K = 11 (45 KB) beside the 36 KB of planes end the two blocks per CU. It saves what the profile says is not
 //             scarce and spends what is. The K-loops hold no block barrier: the kernel has two, one behind each staging phase.
+//   x1        Form 2 needs x1 twice: rounded to fp16 as conv b's operand (the middle plane, as in form 1) and in fp32 as conv b's residual,
+//             at other lanes than the ones that computed it (conv b's output column c is the intermediate's column c + pb). Split-bf16
+//             parks it over its dead x planes (4·C·Wx bytes); one fp16 plane has 2·C·Wx and the Wo ≤ 256 output columns need 4·C·Wo, so it
+//             does not fit there. Here conv a's epilogue adds the fp32 x (buffer loads, 0 outside the row), stores the rounded lrelu(x1) to
+//             the middle plane and x1 itself to a region of its own behind the epilogue table, [C][Wo] floats sized for Wo = 256
+//             (32 / 64 KB), under the barrier the kernel has anyway; conv b's epilogue reads it in the place of form 1's x. At 32
+//             channels the block grows from 35 to 67 KB: two per CU where form 1's registers allow three. At 64 channels 134 KB is
+//             one block per CU, which is what form 1 has there already (140 registers, 512 threads). The
+//             alternative — x1 held in conv a's accumulator registers through conv b's K-loop and exchanged through the dead planes behind
+//             two more barriers — costs no LDS and was built for 128 channels, the one count where LDS cannot hold x1 (268 KB): at
+//             16·MTW·kNTW = 64 more live registers the instance spilled (448 bytes of scratch per lane at this ring depth, 176 at half, 32
+//             with a ring of two steps, where the loop would wait on L2). No instance may use scratch, so form 2 is not eligible at
+//             128 channels and that stage keeps the two-launch path; it is the medium voice's shortest row (8·F columns).
 //   rows      A row of true length 0 is skipped; a tile entirely past the true length only zeroes its part of `act`.
-// Per pair this removes one launch and the round trip of the intermediate's fp16 image through HBM.
+// Per pair this removes one launch and the round trip of the intermediate's fp16 image through HBM; form 2 also the fp32 x1's.
 #include <algorithm>
 #include <type_traits>
 
@@ -66,12 +80,13 @@ struct RbPairF16Multi {
   RbPairF16Args c[kWinMulti];
 };
 
-// C = 32·MT channels; a wave owns MTW row tiles × kNTW column tiles; the block has (MT / MTW) · kWN waves.
-template <int MT, int MTW>
+// C = 32·MT channels; a wave owns MTW row tiles × kNTW column tiles; the block has (MT / MTW) · kWN waves. FORM: 1 or 2 (header).
+template <int MT, int MTW, int FORM>
 __global__ __launch_bounds__((MT / MTW) * kWN * 64, 2) void rb_pair_f16_kernel(const RbPairF16Multi multi, const int batch, const int order, const int Wx) {
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   constexpr int WMB = MT / MTW, BT = WMB * kWN * 64;
   constexpr int C = 32 * MT, CB = C / 8, C16 = C / 16;
+  constexpr bool RB2 = FORM == 2;
   const int jz = blockIdx.y / batch;
   const RbPairF16Args& p = multi.c[(order >> (4 * jz)) & 15];  // heaviest pair first
   const int n = blockIdx.y - jz * batch;
@@ -101,6 +116,7 @@ __global__ __launch_bounds__((MT / MTW) * kWN * 64, 2) void rb_pair_f16_kernel(c
   uint4* xs = lds;                                  // lrelu(x) as fp16 C8 [CB][Wx]
   uint4* x1s = lds + CB * Wx;                       // the intermediate as fp16 C8 [CB][kW1], kTail readable entries
   float* epS = (float*)(x1s + CB * kW1 + kTail);    // [4][C]: 2^−e_a, b_a, 2^−e_b, b_b
+  float* x1f = epS + 4 * C;                         // form 2: x1 in fp32, [C][Wo]
   for (int i = threadIdx.x; i < 4 * C; i += BT) {
     const int which = i / C, co = i - which * C;
     epS[i] = which == 0 ? p.sa[co] : which == 1 ? p.ba[co] : which == 2 ? p.sb[co] : p.bb[co];
@@ -233,14 +249,32 @@ __global__ __launch_bounds__((MT / MTW) * kWN * 64, 2) void rb_pair_f16_kernel(c
       const int colw = (wn * kNTW + j) * 32 + r;
       const int g = c0 - pb + colw;
       const bool in = g >= 0 && g < Lv;  // zero outside [0, true length): conv b's zero padding
+      f32x16 x1;
+      if constexpr (RB2) {  // the residual of conv a: x at the intermediate's columns, 0 outside the row
+        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (int64_t)n * C * p.L), 0, C * p.L * 4, 0x00020000);
+        const int voff = (g >= 0 && g < p.L) ? (((mt0 + m) * 32 + 4 * h) * p.L + g) * 4 : -4;
+#pragma unroll
+        for (int q = 0; q < 16; q++) x1[q] = bload(rx, voff, ((q & 3) + 8 * (q >> 2)) * p.L * 4);
+      }
 #pragma unroll
       for (int g4 = 0; g4 < 4; g4++) {  // a lane holds 4 consecutive channels of one column: 8 bytes of an entry
         float v[4];
         scale_bias(acc[m][j], 0, (mt0 + m) * 32 + 4 * h, g4, v);
+        if constexpr (RB2) {  // x1 = (acc · 2^−e_a + b_a) + x in fp32; only conv b's operand below is rounded
+#pragma unroll
+          for (int i = 0; i < 4; i++) x1[4 * g4 + i] = v[i] = v[i] + x1[4 * g4 + i];
+        }
         uint2 o;
         o.x = in ? pack2_f16(lrelu1(v[0], alpha), lrelu1(v[1], alpha)) : 0u;
         o.y = in ? pack2_f16(lrelu1(v[2], alpha), lrelu1(v[3], alpha)) : 0u;
         ((uint2*)(x1s + ((mt0 + m) * 4 + g4) * kW1 + colw))[h] = o;
+      }
+      if constexpr (RB2) {  // the output columns' x1 → x1f: the lane that owns a column here is not the one that adds it below
+        const int colo = colw - pb;
+        if (colo >= 0 && colo < Wo) {
+#pragma unroll
+          for (int q = 0; q < 16; q++) x1f[((mt0 + m) * 32 + 4 * h + (q & 3) + 8 * (q >> 2)) * Wo + colo] = x1[q];
+        }
       }
     }
   __syncthreads();
@@ -251,7 +285,7 @@ __global__ __launch_bounds__((MT / MTW) * kWN * 64, 2) void rb_pair_f16_kernel(c
   if (ntb == 2) run_conv(std::integral_constant<int, 2>{}, x1s, kW1, Sb, p.dilb, wn * kNTW * 32);
   else run_conv(std::integral_constant<int, 1>{}, x1s, kW1, Sb, p.dilb, wn * kNTW * 32);
 
-  {  // y = (acc · 2^−e_b + b_b) + x → fp32; optionally the C8 image of lrelu(y) for a conv that is not fused
+  {  // y = (acc · 2^−e_b + b_b) + x (form 2: + x1) → fp32; optionally the C8 image of lrelu(y) for a conv that is not fused
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (int64_t)n * C * p.L), 0, C * p.L * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y ? p.y + (int64_t)n * C * p.L : nullptr), 0, p.y ? C * p.L * 4 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rma = __builtin_amdgcn_make_buffer_rsrc((void*)(p.mrf_a ? p.mrf_a + (int64_t)n * C * p.L : nullptr), 0, p.mrf_a ? C * p.L * 4 : 0, 0x00020000);
@@ -268,7 +302,8 @@ __global__ __launch_bounds__((MT / MTW) * kWN * 64, 2) void rb_pair_f16_kernel(c
         const int voff = ok ? (rowl * p.L + g) * 4 : -4;  // −4: out of range ⇒ loads give 0, stores are dropped
         float xr[16];
 #pragma unroll
-        for (int q = 0; q < 16; q++) xr[q] = bload(rx, voff, ((q & 3) + 8 * (q >> 2)) * p.L * 4);
+        for (int q = 0; q < 16; q++)
+          xr[q] = RB2 ? x1f[(rowl + (q & 3) + 8 * (q >> 2)) * Wo + min(colo, Wo - 1)] : bload(rx, voff, ((q & 3) + 8 * (q >> 2)) * p.L * 4);
         float v[16];
 #pragma unroll
         for (int g4 = 0; g4 < 4; g4++) {
@@ -307,30 +342,38 @@ struct PairGeom {
   int Wx;
   size_t lds;
 };
-// x window: 256 + 2·pa columns, up to 3 more in front for the float4 alignment, rounded up to whole float4s
-PairGeom pair_geom(int C, int pa_max) {
+// x window: 256 + 2·pa columns, up to 3 more in front for the float4 alignment, rounded up to whole float4s; form 2: the fp32 x1 of up to
+// 256 output columns behind the epilogue table
+PairGeom pair_geom(int C, int pa_max, int form) {
   PairGeom g;
   g.Wx = (kW1 + 2 * pa_max + 3 + 3) & ~3;
   g.lds = ((size_t)(C / 8) * (g.Wx + kW1) + kTail) * 16 + (size_t)4 * C * sizeof(float);
+  if (form == 2) g.lds += (size_t)C * kW1 * sizeof(float);
   return g;
 }
 
-template <int MT, int MTW>
+template <int MT, int MTW, int FORM>
 void launch_inst(hipStream_t s, const RbPairF16Multi& m, int batch, int order, const PairGeom& g, dim3 grid) {
   static bool raised[kMaxDevices] = {};
   if (g.lds > 64 * 1024 && lds_optin_needed(raised))
-    (void)hipFuncSetAttribute((const void*)rb_pair_f16_kernel<MT, MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-  hipLaunchKernelGGL((rb_pair_f16_kernel<MT, MTW>), grid, dim3((MT / MTW) * kWN * 64), g.lds, s, m, batch, order, g.Wx);
+    (void)hipFuncSetAttribute((const void*)rb_pair_f16_kernel<MT, MTW, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
+  hipLaunchKernelGGL((rb_pair_f16_kernel<MT, MTW, FORM>), grid, dim3((MT / MTW) * kWN * 64), g.lds, s, m, batch, order, g.Wx);
+}
+template <int MT, int MTW>
+void launch_form(int form, hipStream_t s, const RbPairF16Multi& m, int batch, int order, const PairGeom& g, dim3 grid) {
+  if (form == 2) launch_inst<MT, MTW, 2>(s, m, batch, order, g, grid);
+  else launch_inst<MT, MTW, 1>(s, m, batch, order, g, grid);
 }
 
 }  // namespace
 
-bool rb_pair_f16_eligible(int C, int Ka, int dila, int Kb, int dilb, int L) {
+bool rb_pair_f16_eligible(int C, int Ka, int dila, int Kb, int dilb, int L, int form) {
   if (C != 32 && C != 64 && C != 128) return false;
+  if (form != 1 && !(form == 2 && C <= 64)) return false;  // form 2 at 128 channels: header, "x1"
   if (Ka < 1 || Kb < 1 || !(Ka & 1) || !(Kb & 1) || dila < 1 || dilb < 1 || L < 4 || (L & 3)) return false;
   if ((int64_t)(Ka - 1) * dila / 2 > kC8Halo || (int64_t)(Kb - 1) * dilb / 2 > kC8Halo) return false;  // pb ≤ 64: Wo ≥ 128
   if ((int64_t)C * L * 4 >= (int64_t)1 << 31) return false;  // 32-bit byte offsets into one item
-  return pair_geom(C, (Ka - 1) * dila / 2).lds <= kLdsMax;
+  return pair_geom(C, (Ka - 1) * dila / 2, form).lds <= kLdsMax;
 }
 
 int launch_rb_pair_f16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairF16Args* pairs, int count) {
@@ -340,8 +383,9 @@ int launch_rb_pair_f16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairF16A
   int pa_max = 0, pb_max = 0, idx[kWinMulti] = {0, 1, 2};
   for (int i = 0; i < count; i++) {
     const RbPairF16Args& b = pairs[i];
-    if (b.N != a.N || b.C != a.C || b.L != a.L) PH_FAIL(PIPER_HIP_ERR_SHAPE, "rb_pair_f16: pairs of one launch must share N, C and L");
-    if (b.form != 1 || !rb_pair_f16_eligible(b.C, b.Ka, b.dila, b.Kb, b.dilb, b.L))
+    if (b.N != a.N || b.C != a.C || b.L != a.L || b.form != a.form)
+      PH_FAIL(PIPER_HIP_ERR_SHAPE, "rb_pair_f16: pairs of one launch must share N, C, L and form");
+    if (!rb_pair_f16_eligible(b.C, b.Ka, b.dila, b.Kb, b.dilb, b.L, b.form))
       PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "rb_pair_f16: geometry not covered (C=%d K=%d,%d d=%d,%d L=%d form=%d)", b.C, b.Ka, b.Kb, b.dila, b.dilb, b.L, b.form);
     if (!b.x || (!b.y && !b.act) || b.x == b.y || !b.wa || !b.wb || !b.sa || !b.sb || !b.ba || !b.bb || (!b.mrf_a != !b.mrf_b) ||
         (b.act && b.act_row < kC8Halo + b.L))
@@ -349,7 +393,7 @@ int launch_rb_pair_f16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairF16A
     pa_max = std::max(pa_max, (b.Ka - 1) * b.dila / 2);
     pb_max = std::max(pb_max, (b.Kb - 1) * b.dilb / 2);
   }
-  const PairGeom g = pair_geom(a.C, pa_max);
+  const PairGeom g = pair_geom(a.C, pa_max, a.form);
   if (g.lds > kLdsMax) PH_FAIL(PIPER_HIP_ERR_UNSUPPORTED, "rb_pair_f16: window of %zu bytes exceeds LDS", g.lds);
   std::sort(idx, idx + count, [&](int l, int r2) { return pairs[l].Ka + pairs[l].Kb > pairs[r2].Ka + pairs[r2].Kb; });
   int order = 0;
@@ -358,16 +402,22 @@ int launch_rb_pair_f16_multi(piper_hip_ctx* ctx, hipStream_t s, const RbPairF16A
   for (int i = 0; i < kWinMulti; i++) m.c[i] = pairs[i < count ? i : 0];
   // each pair's tiles are sized by its own conv b; the grid by the narrowest, blocks past a pair's last tile leave at once
   const dim3 grid((unsigned)ceil_div(a.L, kW1 - 2 * pb_max), (unsigned)(a.N * count));
-  if (a.C == 32) launch_inst<1, 1>(s, m, a.N, order, g, grid);
-  else if (a.C == 64) launch_inst<2, 1>(s, m, a.N, order, g, grid);
-  else launch_inst<4, 2>(s, m, a.N, order, g, grid);
-  for (int i = 0; i < count; i++)
-    PH_ROUTE(ctx, pairs[i].C, pairs[i].C, pairs[i].L, pairs[i].N, "rb_pair_f16 MT=%d MTW=%d Ka=%d da=%d Kb=%d db=%d W1=%d wsrc=l2 multi=%d conv", a.C / 32,
-             a.C == 128 ? 2 : 1, pairs[i].Ka, pairs[i].dila, pairs[i].Kb, pairs[i].dilb, kW1, count);
+  if (a.C == 32) launch_form<1, 1>(a.form, s, m, a.N, order, g, grid);
+  else if (a.C == 64) launch_form<2, 1>(a.form, s, m, a.N, order, g, grid);
+  else launch_inst<4, 2, 1>(s, m, a.N, order, g, grid);
+  for (int i = 0; i < count; i++) {
+    const RbPairF16Args& b = pairs[i];
+    if (a.form == 2)
+      PH_ROUTE(ctx, b.C, b.C, b.L, b.N, "rb_pair_f16 MT=%d MTW=%d form=2 Ka=%d da=%d Kb=%d db=%d W1=%d wsrc=l2 multi=%d conv", a.C / 32, a.C == 128 ? 2 : 1, b.Ka,
+               b.dila, b.Kb, b.dilb, kW1, count);
+    else
+      PH_ROUTE(ctx, b.C, b.C, b.L, b.N, "rb_pair_f16 MT=%d MTW=%d Ka=%d da=%d Kb=%d db=%d W1=%d wsrc=l2 multi=%d conv", a.C / 32, a.C == 128 ? 2 : 1, b.Ka, b.dila,
+               b.Kb, b.dilb, kW1, count);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) PH_FAIL(PIPER_HIP_ERR_LAUNCH, "rb_pair_f16 launch failed: %s", hipGetErrorString(e));
   return PIPER_HIP_OK;
 }
 
 }  // namespace ph
-namespace ph { namespace { PH_WARM(rb_pair_f16, (rb_pair_f16_kernel<1, 1>)); } }
+namespace ph { namespace { PH_WARM(rb_pair_f16, (rb_pair_f16_kernel<1, 1, 1>)); } }

@@ -577,6 +577,13 @@ struct WindowRecord {
 
 }  // namespace
 
+// y = lrelu(((r0 + r1) + r2) / 3, alpha) over cnt floats (conv_bf16.h: the op level reaches the plans' mean launch through it)
+int ph::launch_mrf_mean_lrelu(hipStream_t q, const float* r0, const float* r1, const float* r2, float* y, int64_t cnt, float alpha) {
+  const int grid = (int)std::min<int64_t>(ceil_div(cnt, (int64_t)kBlock * 4), 2048);
+  hipLaunchKernelGGL(mrf_mean_lrelu_kernel, dim3(grid), dim3(kBlock), 0, q, r0, r1, r2, y, cnt, alpha);
+  return PIPER_HIP_OK;
+}
+
 struct piper_hip_voice {
   piper_hip_ctx* ctx = nullptr;
   piper_hip_voice_config cfg{};
@@ -1304,11 +1311,7 @@ void add_convt_f32(Builder& b, const std::string& name, const piper_hip_voice::S
 
 // y = lrelu(((r0 + r1) + r2) / 3, alpha) over cnt floats, as a launch of its own
 void add_mrf_mean(Builder& b, const std::string& name, const float* r0, const float* r1, const float* r2, float* y, int64_t cnt, float alpha) {
-  b.step(name, "", 0, 0, [=](hipStream_t q) {
-    const int grid = (int)std::min<int64_t>(ceil_div(cnt, (int64_t)kBlock * 4), 2048);
-    hipLaunchKernelGGL(mrf_mean_lrelu_kernel, dim3(grid), dim3(kBlock), 0, q, r0, r1, r2, y, cnt, alpha);
-    return PIPER_HIP_OK;
-  });
+  b.step(name, "", 0, 0, [=](hipStream_t q) { return launch_mrf_mean_lrelu(q, r0, r1, r2, y, cnt, alpha); });
 }
 
 // The waveform: conv_post (→ 1 channel, k7: thread-per-output fp32 kernel) + tanh over rows of L samples. `prologue` says what its input still
@@ -1347,20 +1350,23 @@ ConvBf16Args rb_args_bf16(const Builder& b, const uint16_t* in, int K, int dil, 
   return a;
 }
 
-// … and a split-bf16 pair launch (rb_pair_bf16x3.hip) on the fp32 stream x → y over rows of Lo positions; form 1: a ResBlock1 pair,
-// 2: two ResBlock2 steps. `act`: the planar image of lrelu(y, 0.1) for a consumer that is not fused, or null
-RbPairBf16Args rb_pair_args_x3(const Builder& b, const piper_hip_voice::ConvWB& wa, int dila, const piper_hip_voice::ConvWB& wb, int dilb, int form,
-                               const float* x, float* y, uint16_t* act, int row, int Lo) {
-  RbPairBf16Args q;
+// … and a split-bf16 or fp16 pair launch (rb_pair_bf16x3.hip, rb_pair_f16.hip) on the fp32 stream x → y over rows of Lo positions; form 1: a
+// ResBlock1 pair, 2: two ResBlock2 steps. `act`: the image of lrelu(y, 0.1) for a consumer that is not fused, or null. The per-channel
+// scales of fp16 weight images travel along (null under split-bf16, which reads the RbPairBf16Args part)
+RbPairF16Args rb_pair_args_x3(const Builder& b, const piper_hip_voice::ConvWB& wa, int dila, const piper_hip_voice::ConvWB& wb, int dilb, int form,
+                              const float* x, float* y, uint16_t* act, int row, int Lo) {
+  RbPairF16Args q;
   q.x = x; q.y = y; q.act = act; q.act_row = row;
   q.wa = wa.w; q.ba = wa.bias; q.wb = wb.w; q.bb = wb.bias;
+  q.sa = wa.scale; q.sb = wb.scale;
   q.Ka = wa.K; q.dila = dila; q.Kb = wb.K; q.dilb = dilb; q.alpha = 0.1f; q.form = form;
   q.N = b.NB; q.C = wa.Cout; q.L = Lo; q.len_ptr = b.lensF; q.len_mul = Lo / b.F;
   return q;
 }
-bool rb_pair_x3_ok(const RbPairBf16Args& q, int C, const piper_hip_voice::ConvWB& wa, const piper_hip_voice::ConvWB& wb) {
+bool rb_pair_x3_ok(const RbPairF16Args& q, int C, const piper_hip_voice::ConvWB& wa, const piper_hip_voice::ConvWB& wb, bool f16) {
   return q.x && (q.y || q.act) && q.wa && q.wb && q.ba && q.bb && wa.Cin == C && wa.Cout == C && wb.Cin == C && wb.Cout == C &&
-         rb_pair_bf16x3_eligible(C, q.Ka, q.dila, q.Kb, q.dilb, q.L, q.form);
+         (f16 ? q.sa && q.sb && rb_pair_f16_eligible(C, q.Ka, q.dila, q.Kb, q.dilb, q.L, q.form)
+              : rb_pair_bf16x3_eligible(C, q.Ka, q.dila, q.Kb, q.dilb, q.L, q.form));
 }
 
 // HiFi-GAN generator with bf16 contraction operands. Same graph as the fp32 generators below;
@@ -1372,7 +1378,8 @@ bool rb_pair_x3_ok(const RbPairBf16Args& q, int C, const piper_hip_voice::ConvWB
 // pairs and ResBlock2 step pairs); at 128 channels and up two doubled windows and the intermediate exceed LDS, and the convs take the
 // two-launch path, the one PIPER_HIP_NO_RB_PAIR selects everywhere.
 // PIPER_HIP_PRECISION_F16 is the bf16 schedule on fp16 images of the same geometry (conv_f16.h): conv_f16 launches, and the merged ResBlock1
-// pairs of the 32-, 64- and 128-channel stages as one launch each (rb_pair_f16.hip), as under bf16. The per-ResBlock lanes stay unfused.
+// pairs of the 32-, 64- and 128-channel stages as one launch each (rb_pair_f16.hip), as under bf16; its per-ResBlock lanes stay unfused.
+// ResBlock2 steps (i, i+1) of those stages run as one launch on both schedules, where split mode runs them (rb_pair_f16.hip, form 2).
 int build_generator_bf16(Builder& b, const float* z, float* dec0) {
   piper_hip_voice* v = b.v;
   Slot& s = b.s;
@@ -1488,18 +1495,18 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
       for (int di = 0; di < c.rb_n_dil; di++) {
         const bool lastd = di + 1 == c.rb_n_dil;
         const std::string nm = p + "rb012.c" + std::to_string(di);
-        // split mode, ResBlock2 steps (di, di+1) of a 32- / 64-channel stage: both convs of all three ResBlocks in one launch, the
-        // intermediate in LDS, x1 in fp32 (rb_pair_bf16x3.hip)
-        if (split && c.resblock_type == 2 && !no_pair && !lastd) {
+        // split mode and fp16, ResBlock2 steps (di, di+1) of a 32- / 64-channel stage (fp16: 128 too): both convs of all three ResBlocks
+        // in one launch, the intermediate in LDS, x1 in fp32 (rb_pair_bf16x3.hip, rb_pair_f16.hip)
+        if ((split || f16) && c.resblock_type == 2 && !no_pair && !lastd) {
           const bool lastp = di + 2 == c.rb_n_dil;
-          struct Pack { RbPairBf16Args a[3]; } pk;
+          struct Pack { RbPairF16Args a[3]; } pk;
           bool ok = true;
           double fl2 = 0;
           for (int j = 0; j < 3 && ok; j++) {
             float* y = lastp ? r[j] : (src[j] == tmp[j][0] ? tmp[j][1] : tmp[j][0]);  // never the buffer being read
             pk.a[j] = rb_pair_args_x3(b, rb_w[u][j][di], c.rb_dilations[j][di], rb_w[u][j][di + 1], c.rb_dilations[j][di + 1], 2, src[j], y,
                                       lastp ? nullptr : act[j][0], row, Lo);
-            ok = rb_pair_x3_ok(pk.a[j], S.Cout, rb_w[u][j][di], rb_w[u][j][di + 1]);
+            ok = rb_pair_x3_ok(pk.a[j], S.Cout, rb_w[u][j][di], rb_w[u][j][di + 1], f16);
             fl2 += 2.0 * NB * conv_flops(S.Cout, S.Cout, c.rb_kernels[j], Lo);
           }
           if (ok) {
@@ -1508,8 +1515,13 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
               src_act[j] = pk.a[j].act;
               tap_step(j, di + 1, pk.a[j].y);
             }
-            b.step(nm + "_lrelu_conv_res_lrelu_conv_res_x3", "conv_bf16x3", fl2, NB * 3 * (2.0 * 4.0 * S.Cout * (double)Lo),
-                   [ctx, pk](hipStream_t q) { return launch_rb_pair_bf16x3_multi(ctx, q, pk.a, 3); });
+            const double by2 = NB * 3 * (2.0 * 4.0 * S.Cout * (double)Lo);
+            struct PackB { RbPairBf16Args a[3]; } pb;
+            for (int j = 0; j < 3; j++) pb.a[j] = pk.a[j];
+            if (f16)
+              b.step(nm + "_lrelu_conv_res_lrelu_conv_res_x3", "conv_f16", fl2, by2, [ctx, pk](hipStream_t q) { return launch_rb_pair_f16_multi(ctx, q, pk.a, 3); });
+            else
+              b.step(nm + "_lrelu_conv_res_lrelu_conv_res_x3", "conv_bf16x3", fl2, by2, [ctx, pb](hipStream_t q) { return launch_rb_pair_bf16x3_multi(ctx, q, pb.a, 3); });
             if (lastp) add_stage_mean();
             di++;
             continue;
@@ -1543,7 +1555,7 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
           struct Pack { RbPairF16Args a[3]; } pk;  // the scales travel only under fp16
           bool ok = true;
           auto eligible = [&](int K, int dila) {
-            if (f16) return rb_pair_f16_eligible(S.Cout, K, dila, K, 1, Lo);
+            if (f16) return rb_pair_f16_eligible(S.Cout, K, dila, K, 1, Lo, 1);
             return split ? rb_pair_bf16x3_eligible(S.Cout, K, dila, K, 1, Lo, 1) : rb_pair_bf16_eligible(S.Cout, K, dila, K, 1, Lo);
           };
           for (int j = 0; j < 3 && ok; j++) {
@@ -1622,8 +1634,9 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
           if (fuse_mean && s.parallel) b.join(p + "join");
         };
         // split mode, 32- / 64-channel stages: two chained convs per launch on this ResBlock's lane (rb_pair_bf16x3.hip) — a ResBlock1
-        // pair, or ResBlock2 steps (di, di+1); the stage's closing pair folds the MRF mean into its epilogue
-        if (split && !no_rb_pair() && (c.resblock_type == 1 || !lastd)) {
+        // pair, or ResBlock2 steps (di, di+1); the stage's closing pair folds the MRF mean into its epilogue. fp16: the ResBlock2 steps
+        // alone, at 128 channels too (rb_pair_f16.hip); its ResBlock1 lanes stay unfused
+        if ((split || (f16 && c.resblock_type == 2)) && !no_rb_pair() && (c.resblock_type == 1 || !lastd)) {
           const bool t1 = c.resblock_type == 1;
           const int ib = t1 ? 2 * di + 1 : di + 1, db = t1 ? 1 : c.rb_dilations[j][di + 1];
           const bool lastp = t1 ? lastd : di + 2 == c.rb_n_dil;
@@ -1631,12 +1644,14 @@ int build_generator_bf16(Builder& b, const float* z, float* dec0) {
           const piper_hip_voice::ConvWB &wa = rb_w[u][j][t1 ? 2 * di : di], &wb = rb_w[u][j][ib];
           float* y = lastp ? (mean_p ? m : r[j]) : (src == tmp[j][0] ? tmp[j][1] : tmp[j][0]);  // never the buffer being read
           uint16_t* ya = lastp ? (mean_p ? a_next : nullptr) : act[j][0];  // (a following pair stages from the fp32 stream and ignores it)
-          RbPairBf16Args q = rb_pair_args_x3(b, wa, dil, wb, db, t1 ? 1 : 2, src, y, ya, row, Lo);
+          RbPairF16Args q = rb_pair_args_x3(b, wa, dil, wb, db, t1 ? 1 : 2, src, y, ya, row, Lo);
           if (mean_p) { q.mrf_a = r[0]; q.mrf_b = r[1]; }
-          if (rb_pair_x3_ok(q, S.Cout, wa, wb)) {
+          if (rb_pair_x3_ok(q, S.Cout, wa, wb, f16)) {
             if (mean_p && s.parallel) b.join(p + "join");
-            b.step(nm + (t1 ? "ab_lrelu_conv_lrelu_conv_res" : "_lrelu_conv_res_lrelu_conv_res") + (mean_p ? "_mrfmean" : ""), "conv_bf16x3", 2.0 * fl,
-                   NB * (2.0 * 4.0 * S.Cout * (double)Lo), [ctx, q](hipStream_t qs) { return launch_rb_pair_bf16x3_multi(ctx, qs, &q, 1); });
+            const std::string pn = nm + (t1 ? "ab_lrelu_conv_lrelu_conv_res" : "_lrelu_conv_res_lrelu_conv_res") + (mean_p ? "_mrfmean" : "");
+            const double by2 = NB * (2.0 * 4.0 * S.Cout * (double)Lo);
+            if (f16) b.step(pn, "conv_f16", 2.0 * fl, by2, [ctx, q](hipStream_t qs) { return launch_rb_pair_f16_multi(ctx, qs, &q, 1); });
+            else b.step(pn, "conv_bf16x3", 2.0 * fl, by2, [ctx, q](hipStream_t qs) { return launch_rb_pair_bf16x3_multi(ctx, qs, &q, 1); });
             if (!t1) di++;
             if (!mean_p) tap_step(j, di, y);
             src = y;

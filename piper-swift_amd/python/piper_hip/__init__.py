@@ -493,6 +493,8 @@ _PROTOS = {
     "piper_hip_hifigan_resblock_f16": (C.c_int, [c_vp, C.c_int, c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_i32p,
                                                  C.c_int, C.POINTER(c_vp), C.POINTER(c_vp), C.c_float, C.POINTER(c_vp),
                                                  c_vp]),
+    "piper_hip_hifigan_mrf_f16": (C.c_int, [c_vp, C.c_int, c_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, c_i32p, c_i32p, C.c_int,
+                                            C.POINTER(c_vp), C.POINTER(c_vp), C.c_float, C.POINTER(c_vp), c_vp]),
     "piper_hip_voice_config_preset": (C.c_int, [C.c_int, C.POINTER(VoiceConfig)]),
     "piper_hip_voice_blob_floats": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(C.c_size_t)]),
     "piper_hip_voice_blob_layout": (C.c_int, [C.POINTER(VoiceConfig), C.POINTER(TensorInfo), C.c_int,
@@ -1237,6 +1239,20 @@ class HipBackend:
         p = c_vp()
         _check(self.lib.piper_hip_hifigan_resblock_f16(self.ctx, type, _ptr(x), n, c, t, k, d, nd, w, b, slope, C.byref(p),
                                                        commandBuffer))
+        return self._out(p, [n, c, t])[0]
+
+    def hifiganMrfF16(self, type, x, n, c, t, kernels, dilations, weights, biases, slope=0.1, commandBuffer=None):
+        """The mean of len(kernels) residual blocks of x with fp16 contractions; dilations: one list per block (equal lengths), weights /
+        biases block by block. Eligible steps of the three blocks run as one fused launch (ResBlock2: steps (i, i+1))."""
+        nd = len(dilations[0])
+        assert all(len(d_) == nd for d_ in dilations) and len(dilations) == len(kernels)
+        ks = (C.c_int32 * len(kernels))(*kernels)
+        d = (C.c_int32 * (nd * len(kernels)))(*[v for d_ in dilations for v in d_])
+        w = (c_vp * len(weights))(*[_ptr(b) for b in weights])
+        b = (c_vp * len(biases))(*[_ptr(x_) for x_ in biases])
+        p = c_vp()
+        _check(self.lib.piper_hip_hifigan_mrf_f16(self.ctx, type, _ptr(x), n, c, t, len(kernels), ks, d, nd, w, b, slope, C.byref(p),
+                                                  commandBuffer))
         return self._out(p, [n, c, t])[0]
 
 

@@ -671,4 +671,15 @@ public final class HIPBackend {
                                                       Int32(dilations.count), w, b, slope, &out, commandBuffer))
         return wrap(out)
     }
+    /// The MRF stage with fp16 contractions: the mean of three residual blocks of x (dilations: one array per block, weights / biases block by block);
+    /// eligible steps of the three blocks run as one fused launch (ResBlock2: steps (i, i+1) at 32 / 64 channels)
+    public func hifiganMrfF16(type: Int, x: HIPBuffer, batch: Int, channels: Int, length: Int, kernels: [Int], dilations: [[Int]], weights: [HIPBuffer],
+                              biases: [HIPBuffer], slope: Float = 0.1, commandBuffer: Stream? = nil) throws -> HIPBuffer {
+        var out: UnsafeMutablePointer<Float>? = nil
+        let w: [UnsafePointer<Float>?] = weights.map { UnsafePointer($0.f32) }
+        let b: [UnsafePointer<Float>?] = biases.map { UnsafePointer($0.f32) }
+        try Self.check(piper_hip_hifigan_mrf_f16(ctx, Int32(type), x.f32, Int64(batch), Int64(channels), Int64(length), Int32(kernels.count), kernels.map(Int32.init),
+                                                 dilations.flatMap { $0.map(Int32.init) }, Int32(dilations.first?.count ?? 0), w, b, slope, &out, commandBuffer))
+        return wrap(out)
+    }
 }
